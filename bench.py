@@ -11,8 +11,15 @@ Step      = one level-0 Gauss-Newton iteration of RegisterPhotoICP::alignFrames3
             the previous pass is the prologue of the next pass's launch; the two-launch schedule {k_eval, k_solve} is a test hook, rgbd360_debug_set_schedule).
             Frames are resident in HBM before the timed region.
 value     = N * K / t, t = the MEDIAN over `--repeats` timed regions of exactly K steps each (every region bracketed by a
-            barrier + device synchronisation on both sides, the maximum over the ranks taken per region): with the driver's
-            K = 20 a single region is 0.4 ms of wall time, far too short to be one sample.
+            barrier + device synchronisation on both sides, the maximum over the ranks taken per region).  A plain run times ONE
+            region (exactly K timed steps); `--full` times 25 by default (with K = 20 a single region is 0.4 ms of wall time).
+ms_per_step = t / K.
+Plain run = set-up, warm-up, the timed region(s), `--dump-outputs DIR` if given, the JSON line.  The `sequence`, `roofline*`,
+            `iteration*`, `sustained`, `alignment`, `reference_arithmetic` and `cpu_baseline` blocks described below are measurements
+            or checks of their own and run only with `--full`.
+--dump-outputs DIR = after the timed steps, what the timed call returned in its last step: pose.npy (float32 4x4 solved pose),
+            rms.npy and status.npy (float64 [1]); with N > 1 also poses_all_ranks.npy (float32 [N, 16], the RCCL-gathered
+            column-major poses).  Inputs are seeded: the same arguments give the same inputs in every run.
 N > 1     = weak scaling of `value` (every rank iterates on its own pair, the solved poses are all-gathered over RCCL inside
             every timed region), AND the `sequence` block: BASELINE.json configs[3] itself -- 256 consecutive pairs of an
             odometry sequence in contiguous shards over the ranks, every rank aligning its shard with the library's sequence
@@ -186,7 +193,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=25, help="timed regions of exactly --steps steps; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of exactly --steps steps; the median is reported "
+                    "(default: 1, with --full 25)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beyond the headline figure: full-pyramid "
+                    "alignments, sustained burst, salient fractions, sequence block, rooflines, reference arithmetic, 4096x2048, "
+                    "native multi-GPU entry, CPU baseline (the --no-* options below apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed call computed "
+                    "in its last step as DIR/<name>.npy")
     ap.add_argument("--width", type=int, default=2048)
     ap.add_argument("--height", type=int, default=1024)
     ap.add_argument("--method", type=int, default=0, help="0 photo (configs[1]), 2 photo+depth (configs[2])")
@@ -201,6 +214,8 @@ def main():
     ap.add_argument("--seq-pairs", type=int, default=256, help="pairs of the configs[3] sequence (whole job)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 25 if args.full else 1
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -246,12 +261,13 @@ def main():
 
     # full coarse-to-fine alignment (natural accept/reject schedule): pose + per-level iteration counts
     t_align = []
-    for _ in range(5):
+    for _ in range(5 if args.full else 0):
         t0 = time.perf_counter()
         rc = reg.alignFrames360(np.eye(4), method)
         t_align.append(time.perf_counter() - t0)
-    pose_gpu = reg.getOptimalPose()
-    iters_nat = list(reg.num_iterations)
+    if args.full:
+        pose_gpu = reg.getOptimalPose()
+        iters_nat = list(reg.num_iterations)
     start_pose = np.eye(4)     # forced schedule starts from the identity guess at level 0
 
     def sync_all():
@@ -297,6 +313,45 @@ def main():
         rccl_ranks_seen = 1
     srt = sorted(elapsed_all)
     elapsed = srt[len(srt) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out["pose"], run_k_steps._keep[1].value, rc_forced, poses)      # (_keep[1]: the rms the call wrote)
+
+    value = n_gpus * args.steps / elapsed
+    result = {
+        "metric": "Gauss-Newton iters/sec on 2048x1024 spherical pair; SE(3) err vs CPU ref",
+        "value": value,
+        "unit": "GN iterations/s",
+        "n_gpus": n_gpus,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "env": {k: os.environ.get(k) for k in ("GPU_MAX_HW_QUEUES", "RGBD360_HOST_SPIN_US", "RGBD360_RECOMPUTE_MIN_PX", "RGBD360_SEQ_RECOMPUTE_MIN_PX",
+                                                "RGBD360_SEQ_ENGINES", "RGBD360_FORCE_RCCL")},      # the six runtime knobs of a product build (csrc/knobs.h)
+        "full": bool(args.full),
+        "rccl_ranks_seen": rccl_ranks_seen,
+        "config": {
+            "workload": ("configs[1]: single %dx%d synthetic sphere pair per GPU, %s RegisterPhotoICP, level-0 forced "
+                         "Gauss-Newton iterations (one launch each: solve of the previous pass + fused warp/residual/Jacobian pass)" % (W, H, METHOD_NAMES[method])),
+            "width": W, "height": H, "method": METHOD_NAMES[method], "n_pyr": 4,
+            "pairs_per_gpu": 1, "parallelism": "independent pairs per GPU, RCCL all-gather of poses" if world > 1 else "1 GPU",
+        },
+        "timed_regions": {"repeats": repeats, "steps_each": args.steps, "statistic": "median of per-region max over ranks",
+                          "elapsed_s_min": srt[0], "elapsed_s_median": elapsed, "elapsed_s_max": srt[-1],
+                          "value_from_fastest_region": n_gpus * args.steps / srt[0],
+                          "value_from_slowest_region": n_gpus * args.steps / srt[-1]},
+    }
+    if not args.full:
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        return
 
     # ---- sustained burst (NOT part of `value`): the same forced schedule for >= 2 s in few large C calls, so that a utilisation
     #      sampler sees the GPU busy and the rate cross-checks `value` (which is the median of 25 regions of 0.3 ms) ----
@@ -324,36 +379,8 @@ def main():
                         "residuals_per_pixel_photo_depth": float(e_pd["n_valid"]) / n_px,
                         "note": "level 0, at the solved pose; photo / depth = pixels contributing a photometric / depth residual over all %d source pixels" % n_px}
 
-    value = n_gpus * args.steps / elapsed
-    result = {
-        "metric": "Gauss-Newton iters/sec on 2048x1024 spherical pair; SE(3) err vs CPU ref",
-        "value": value,
-        "unit": "GN iterations/s",
-        "n_gpus": n_gpus,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "env": {k: os.environ.get(k) for k in ("GPU_MAX_HW_QUEUES", "RGBD360_HOST_SPIN_US", "RGBD360_RECOMPUTE_MIN_PX", "RGBD360_SEQ_RECOMPUTE_MIN_PX",
-                                                "RGBD360_SEQ_ENGINES", "RGBD360_FORCE_RCCL")},      # the six runtime knobs of a product build (csrc/knobs.h)
-        "sustained": sustained,
-        "rccl_ranks_seen": rccl_ranks_seen,
-        "salient_fraction": salient_fraction,
-        "config": {
-            "workload": ("configs[1]: single %dx%d synthetic sphere pair per GPU, %s RegisterPhotoICP, level-0 forced "
-                         "Gauss-Newton iterations (one launch each: solve of the previous pass + fused warp/residual/Jacobian pass)" % (W, H, METHOD_NAMES[method])),
-            "width": W, "height": H, "method": METHOD_NAMES[method], "n_pyr": 4,
-            "pairs_per_gpu": 1, "parallelism": "independent pairs per GPU, RCCL all-gather of poses" if world > 1 else "1 GPU",
-        },
-        "timed_regions": {"repeats": repeats, "steps_each": args.steps, "statistic": "median of per-region max over ranks",
-                          "elapsed_s_min": srt[0], "elapsed_s_median": elapsed, "elapsed_s_max": srt[-1],
-                          "value_from_fastest_region": n_gpus * args.steps / srt[0],
-                          "value_from_slowest_region": n_gpus * args.steps / srt[-1]},
-    }
+    result["sustained"] = sustained
+    result["salient_fraction"] = salient_fraction
 
     # ---- BASELINE.json configs[3]: the odometry sequence, contiguous shards of pairs over the ranks ----------
     seq_block = None
@@ -602,6 +629,16 @@ def main():
                         "the sweep never exceeds it; single_thread_value = the reference-faithful single-thread figure (SURVEY.md 8d)",
             }
         print(json.dumps(result), flush=True)
+
+
+def dump_outputs(out_dir, pose, rms, status, gathered=None):
+    """What the timed call returned in its last step, as out_dir/<name>.npy (float32 / float64, a few hundred bytes)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pose.npy"), np.asarray(pose, np.float32).reshape(4, 4))
+    np.save(os.path.join(out_dir, "rms.npy"), np.array([rms], np.float64))
+    np.save(os.path.join(out_dir, "status.npy"), np.array([status], np.float64))
+    if gathered is not None:
+        np.save(os.path.join(out_dir, "poses_all_ranks.npy"), gathered.detach().cpu().numpy().astype(np.float32).reshape(-1, 16))
 
 
 def run_sequence_block(args, torch, dist, synth, reg0, rank, world, local_rank, xdev, W, H, gather_poses, shard_range, sync_all):

@@ -1,8 +1,7 @@
 """BASELINE.json configs[0] (plumbing, CPU only): the reference's own sample frames through the restated .bin reader,
-the restated spherical stitcher and the CPU oracle.  Where /root/reference is mounted (the build container) the frames are parsed
-from its files in place; elsewhere they come from the committed data fixture tests/golden/sample_pair.npz, which the first test
-below proves equal to those files.  Expected values: tests/golden/config1_samples.json (tests/tools/config1_samples.py --write).
-The same pair on the DEVICE: tests/test_samples_gpu.py."""
+the restated spherical stitcher and the CPU oracle.  The frames and the extrinsics come from the committed data fixture
+tests/golden/sample_pair/, which the first test below proves equal to the reference's files (digests recorded in files.json).
+Expected values: tests/golden/config1_samples.json (tests/tools/config1_samples.py --write).  The same pair on the DEVICE: tests/test_samples_gpu.py."""
 import json
 import os
 import sys
@@ -11,26 +10,42 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAMPLES = "/root/reference/samples/sphere_images_1.bin"
+SAMPLE_FILES = os.path.join(ROOT, "tests", "golden", "sample_pair", "files.json")
 
 
-@pytest.mark.skipif(not os.path.exists(SAMPLES), reason="reference samples are only present in the build container")
-def test_data_fixture_holds_the_reference_sample_frames_and_extrinsics():
-    """tests/golden/sample_pair.npz (what the GPU box sees) = the sensor images of samples/sphere_images_{1,10}.bin and the numbers of
-    Calibration/Extrinsics/Rt_0N.txt, value for value; written back in the archive layout it is the reference's file except for the
-    15 version bytes of the Boost header no reader looks at."""
+@pytest.fixture(scope="module")
+def sample_bin(tmp_path_factory):
+    """samples/sphere_images_1.bin as the fixture writes it back in the archive layout (the first test proves it the reference's file
+    but for the 15 version bytes of the Boost header)."""
     sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
     import config1_samples as c1
+    path = str(tmp_path_factory.mktemp("samples") / "sphere_images_1.bin")
+    c1.write_bin(path, c1.frames(1, "fixture"))
+    return path
+
+
+def test_data_fixture_holds_the_reference_sample_frames_and_extrinsics(tmp_path):
+    """tests/golden/sample_pair/ = the sensor images of samples/sphere_images_{1,10}.bin and Calibration/Extrinsics/Rt_0N.txt: written
+    back in the archive layout, each frame is the reference's file (its size and sha256, recorded in files.json) except for the
+    15 version bytes of the Boost header no reader looks at; the extrinsics are the reference's text files byte for byte."""
+    import hashlib
+    sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+    import config1_samples as c1
+    rec = json.load(open(SAMPLE_FILES))
     for idx in (1, 10):
-        ref, fix = c1.frames(idx, "reference"), c1.frames(idx, "fixture")
-        assert all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) for a, b in zip(ref, fix))
-    assert all(np.array_equal(a, b) for a, b in zip(c1.extrinsics("reference"), c1.extrinsics("fixture")))
-    import tempfile
-    with tempfile.TemporaryDirectory() as tmp:
-        path = os.path.join(tmp, "s.bin")
-        c1.write_bin(path, c1.frames(1, "fixture"))
-        a, b = open(path, "rb").read(), open(SAMPLES, "rb").read()
-        assert len(a) == len(b) and a[:30] == b[:30] and a[45:] == b[45:]
+        path = str(tmp_path / ("sphere_images_%d.bin" % idx))
+        c1.write_bin(path, c1.frames(idx, "fixture"))
+        raw = open(path, "rb").read()
+        want = rec["sphere_images_%d.bin" % idx]
+        assert len(raw) == want["size"] and c1.archive_digest(raw) == want["sha256_without_version_bytes"]
+        back = c1.load_frame(path)
+        assert all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) for a, b in zip(back, c1.frames(idx, "fixture")))
+    for s in range(8):
+        name = "Rt_0%d.txt" % (s + 1)
+        raw = open(os.path.join(c1.FIXTURE, name), "rb").read()
+        assert hashlib.sha256(raw).hexdigest() == rec[name]["sha256"]
+    Rt = c1.extrinsics("fixture")
+    assert len(Rt) == 8 and all(M.shape == (4, 4) and np.array_equal(M[3], [0, 0, 0, 1]) for M in Rt)
 
 
 def test_sample_pair_fixture_stitches_to_the_committed_checksums():
@@ -46,8 +61,7 @@ def test_sample_pair_fixture_stitches_to_the_committed_checksums():
     assert set(gold["alignments"]) == {"m%d_o%d" % mo for mo in c1.ALIGNMENTS}
 
 
-@pytest.mark.skipif(not os.path.exists(SAMPLES), reason="reference samples are only present in the build container")
-def test_sample_pair_stitches_and_aligns_like_the_committed_record():
+def test_sample_pair_stitches_and_aligns_like_the_committed_record(sample_bin):
     sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
     import config1_samples as c1
     from rgbd360_amd import synth
@@ -58,8 +72,8 @@ def test_sample_pair_stitches_and_aligns_like_the_committed_record():
     assert max(out["numpy_vs_cpp_stitch_mismatching_pixels"]) <= 30      # the independent numpy stitcher agrees (of 614,400 px)
     # the product's host-side .bin reader returns the same 8 x (rgb, depth) as the test-side parser
     from rgbd360_amd.register import load_frame_bin
-    rgb8, d8 = load_frame_bin(SAMPLES)
-    fr = c1.load_frame(SAMPLES)
+    rgb8, d8 = load_frame_bin(sample_bin)
+    fr = c1.load_frame(sample_bin)
     assert all(np.array_equal(rgb8[s], fr[s][0]) and np.array_equal(d8[s], fr[s][1]) for s in range(8))
     assert all(f > 0.5 for f in out["valid_depth_fraction"])
     for name in ("PHOTO_CONSISTENCY", "PHOTO_DEPTH"):
@@ -74,7 +88,6 @@ def test_sample_pair_stitches_and_aligns_like_the_committed_record():
     assert 0.05 < trans < 0.6 and rot < 0.1
 
 
-@pytest.mark.skipif(not os.path.exists(SAMPLES), reason="reference samples are only present in the build container")
 def test_sample_pair_plane_registration_reports_an_unobservable_translation():
     """RegisterPairRGBD360.cpp:94-110 runs RegisterPbMap on this very pair.  With the reference's PCL parameters
     (Frame360.h:949-977: depth-change factor 0.02, smoothing 8, 80 inliers, 0.0398 rad, 0.02 m) applied to the stitched panorama
@@ -126,7 +139,6 @@ def _downsample_median(xyz, step=2, min_depth=0.3, max_depth=10.0):
     return out.astype(np.float32)
 
 
-@pytest.mark.skipif(not os.path.exists(SAMPLES), reason="reference samples are only present in the build container")
 def test_sample_pair_per_sensor_planes_with_the_bilateral_filter():
     """The reference's route for the rig's planes (Frame360.h:40-41, 479-499, 949-1075): per sensor, pinhole cloud down-sampled by 2,
     pcl::FastBilateralFilter (10 px, 0.05 m), normal map, segmentation, planes moved into the rig frame by Rt -- here with the
@@ -138,12 +150,12 @@ def test_sample_pair_per_sensor_planes_with_the_bilateral_filter():
     import config1_samples as c1
     from oracle import oracle as O
     from rgbd360_amd import pbmap
-    Rt = [np.loadtxt("/root/reference/Calibration/Extrinsics/Rt_0%d.txt" % (s + 1)) for s in range(8)]
+    Rt = c1.extrinsics("fixture")
     frames = []
     walls_raw = walls_filtered = 0
     for idx in (1, 10):
         planes_rig = []
-        for s, (_, depth) in enumerate(c1.load_frame("/root/reference/samples/sphere_images_%d.bin" % idx)):
+        for s, (_, depth) in enumerate(c1.frames(idx, "fixture")):
             cloud = O.sensor_cloud(depth, 2, 0.3, 10.0)                       # (numpy twins above: same cloud to 1 ulp)
             assert np.nanmax(np.abs(cloud - _downsample_median(_pinhole_cloud(depth)))) < 1e-6
             H, W, _ = cloud.shape

@@ -1,9 +1,10 @@
 """Frame360::undistort's intrinsic depth model (clams::DiscreteDepthDistortionModel; Frame360.h:293-311, 1084-1097, Calib360.h:104-119):
 `rgbd360_depth_model_*` (host code of the HIP library: runs without a GPU) against the independent numpy restatement in oracle/oracle.py
-on model files written by the test, and -- in the build container, where the reference's own eight model files can be read in place --
-against those files, pinned by a small committed fixture (tests/golden/depth_model.json: probes of the corrected image).  The model's
+on model files written by the test, and against the reference's own eight model files (Calibration/Intrinsics, committed compressed
+under tests/golden/depth_models/), pinned by a small committed fixture (tests/golden/depth_model.json: probes of the corrected image).  The model's
 code is third-party (CLAMS, vendored by the reference): parity means "equals the restatement of that source, bit for bit"."""
 import json
+import lzma
 import os
 import struct
 
@@ -13,7 +14,7 @@ import pytest
 from oracle import oracle as O
 from rgbd360_amd.register import DepthModel, Rgbd360Error
 
-REF_MODELS = "/root/reference/Calibration/Intrinsics"
+MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "depth_models")      # distortion_model<k>.xz
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "depth_model.json")
 
 
@@ -87,15 +88,22 @@ def _probe_image():
     return depth
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="the reference's model files are read in place in the build container only")
-def test_reference_model_files_in_place():
+def unpack_model(k, out_dir):
+    """The reference's Calibration/Intrinsics/distortion_model<k>, byte for byte, written into out_dir; returns its path."""
+    path = os.path.join(str(out_dir), "distortion_model%d" % k)
+    with open(path, "wb") as f:
+        f.write(lzma.decompress(open(os.path.join(MODELS, "distortion_model%d.xz" % k), "rb").read()))
+    return path
+
+
+def test_reference_model_files_in_place(tmp_path):
     """The eight files of Calibration/Intrinsics load (no byte left over: the restatement's parser asserts it), have the geometry
     Calib360 expects after downsampleParams(2) -- 320 x 240 images, 4 x 3-pixel bins, 80 x 80 of them, 2 m slices -- and correct a seeded
     depth image exactly like the numpy restatement; the committed fixture pins probes of model 1's result."""
     depth = _probe_image()
     G = json.load(open(GOLDEN))
     for k in range(1, 9):
-        path = os.path.join(REF_MODELS, "distortion_model%d" % k)
+        path = unpack_model(k, tmp_path)
         m = DepthModel(path, 2)
         assert (m.width, m.height, m.bin_width, m.bin_height, m.num_bins_x, m.num_bins_y, m.bin_depth) == (320, 240, 4, 3, 80, 80, 2.0)
         got = m.undistort(depth)

@@ -165,7 +165,7 @@ def test_bench_under_torch_distributed_run_with_two_ranks(hip_lib):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--repeats", "5",
-           "--no-cpu-baseline", "--no-4k", "--no-rotating", "--seq-pairs", "24"]
+           "--full", "--no-cpu-baseline", "--no-4k", "--no-rotating", "--seq-pairs", "24"]
     env = dict(os.environ, BENCH_SHARE_DEVICE="1", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="4")
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=ROOT)
     out, err = p.stdout.decode(errors="replace"), p.stderr.decode(errors="replace")
@@ -185,6 +185,34 @@ def test_bench_under_torch_distributed_run_with_two_ranks(hip_lib):
         assert v["max_forward_backward_residual"] < 1e-3
     pcie = seq["host_frames"]["pcie"]          # the host-frame leg against the box's measured host-to-device copy rate
     assert pcie["bound"] == "pcie" and pcie["bytes_per_alignment"] == 2048 * 1024 * 5 and 0 < pcie["frac"] < 1.5 and pcie["peak"] > 1.0, pcie
+
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_exactly_the_steps_and_dumps_the_last_step(hip_lib, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: one timed region of exactly K steps, none of the
+    --full blocks in the line, and DIR holds what the timed call returned in its last step -- the same for two runs."""
+    import json
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("out%d" % run)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                            "--width", "512", "--height", "256", "--dump-outputs", str(d)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, cwd=ROOT)
+        out = p.stdout.decode(errors="replace")
+        assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
+        lines = [l for l in out.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out[-2000:]
+        r = json.loads(lines[0])
+        assert r["steps"] == 7 and r["warmup"] == 3 and r["timed_regions"]["repeats"] == 1 and not r["full"]
+        assert r["unit"] == "GN iterations/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+        assert abs(r["value"] - 7 / (r["ms_per_step"] * 7e-3)) <= 1e-6 * r["value"]
+        assert not {"roofline", "sustained", "sequence", "cpu_baseline", "alignment"} & set(r)
+        z = {n: np.load(d / (n + ".npy")) for n in ("pose", "rms", "status")}
+        assert z["pose"].shape == (4, 4) and z["pose"].dtype == np.float32 and np.isfinite(z["pose"]).all()
+        assert z["rms"].dtype == np.float64 and z["status"].dtype == np.float64 and z["status"][0] >= 0
+        dumps.append(z)
+    assert all(np.array_equal(dumps[0][n], dumps[1][n]) for n in dumps[0])
 
 
 _F360_BLOCK_SCRIPT = r"""

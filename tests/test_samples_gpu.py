@@ -1,8 +1,8 @@
 """BASELINE.json configs[0] ON THE DEVICE: the one real RGB-D pair the reference ships (samples/sphere_images_1.bin vs _10.bin, the
 sequence of Registration/RegisterPairRGBD360.cpp:56-142 and OdometryRGBD360.cpp:141-193) through the HIP path.
 
-The sensor images and the rig's extrinsics travel as a data fixture (tests/golden/sample_pair.npz, written by
-tests/golden/make_golden_samples.py from the reference's files in the build container); the expected values are
+The sensor images and the rig's extrinsics travel as a data fixture (tests/golden/sample_pair/, written by
+tests/golden/make_golden_samples.py from the reference's files); the expected values are
 tests/golden/config1_samples.json (tests/tools/config1_samples.py --write: the CPU oracle on the same data) AND the oracle run
 live beside the device.  What this pair has that the synthetic room does not: sensor noise, 21 % of the panorama without depth,
 seams between the eight sensors, levels that end at the iteration limit ([10, 10, 10, 7] accepted steps per level).

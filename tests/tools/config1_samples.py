@@ -1,8 +1,8 @@
 """BASELINE.json configs[0] plumbing: RegisterPairRGBD360-style run on the reference's own sample frames, CPU only.
 
-Reads /root/reference/samples/sphere_images_{1,10}.bin and Calibration/Extrinsics/Rt_0N.txt IN PLACE where the reference is
-mounted (the build container); elsewhere (the GPU box) the same sensor images and calibration numbers come from the committed data
-fixture tests/golden/sample_pair.npz (tests/golden/make_golden_samples.py; round 6, so that the HIP path sees the pair).  Restates
+The sensor images of samples/sphere_images_{1,10}.bin and the extrinsics of Calibration/Extrinsics/Rt_0N.txt come from the committed
+data fixture tests/golden/sample_pair/ (tests/golden/make_golden_samples.py writes it from a reference tree; files.json there records
+the digests of the reference's files, which tests/test_config1_samples.py checks the fixture against).  Restates
   * the Boost binary archive layout of Frame360::loadFrame (Frame360.h:231-266 + cvmat_serialization.h:23-55):
     a 45-byte archive header, then 8 x {RGB 8UC3, depth 16UC1 mm} cv::Mat records + a timestamp Mat, each record
     int32 cols, int32 rows, uint64 elemSize, uint64 cvType, raw bytes;
@@ -10,11 +10,12 @@ fixture tests/golden/sample_pair.npz (tests/golden/make_golden_samples.py; round
     matrix (Calib360.h:74-77) and extrinsics (Calib360.h:122-131),
 and runs the CPU oracle's dense spherical alignment on the stitched 1920x320 pair.  The PbMap / GICP stages of the
 original app (Registration/RegisterPairRGBD360.cpp:94-142) and the CLAMS undistortion (Frame360.h:293) are third-party
-and skipped.  Used by tests/test_config1_samples.py (runs only where /root/reference exists) and to (re)generate
+and skipped.  Used by tests/test_config1_samples.py and tests/test_samples_gpu.py, and to (re)generate
 tests/golden/config1_samples.json.
 """
 from __future__ import annotations
 
+import hashlib
 import json
 import os
 import struct
@@ -25,7 +26,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-REF = "/root/reference"
 PI = 3.14159265359
 
 
@@ -53,35 +53,38 @@ def load_frame(path):
     return out
 
 
-FIXTURE = os.path.join(ROOT, "tests", "golden", "sample_pair.npz")      # the same data as arrays (tests/golden/make_golden_samples.py)
-_fixture = None
+FIXTURE = os.path.join(ROOT, "tests", "golden", "sample_pair")      # the same data as arrays (tests/golden/make_golden_samples.py)
+_fixture = {}
 
 
-def have_reference():
-    return os.path.exists(os.path.join(REF, "samples", "sphere_images_1.bin"))
+def fixture_part(idx, lo):
+    """File of the fixture that holds sensors lo .. lo + 3 of sample frame idx."""
+    return "frame%d_sensors%d-%d.npz" % (idx, lo, lo + 3)
 
 
-def fixture():
-    global _fixture
-    if _fixture is None:
-        _fixture = dict(np.load(FIXTURE))
-    return _fixture
+def archive_digest(raw):
+    """sha256 of an archive's bytes without the 15 version bytes of the Boost header (offsets 30-44), which no reader looks at."""
+    return hashlib.sha256(raw[:30] + raw[45:]).hexdigest()
 
 
 def frames(idx, source=None):
-    """The eight (rgb, depth) sensor images of sample frame 1 or 10: parsed from the reference's .bin in place where the reference is
-    mounted (build container), else from the committed data fixture.  source: "reference" | "fixture" | None (= whichever exists)."""
-    if source == "reference" or (source is None and have_reference()):
-        return load_frame(os.path.join(REF, "samples", "sphere_images_%d.bin" % idx))
-    z = fixture()
-    return [(z["rgb_%d" % idx][s], z["depth_%d" % idx][s]) for s in range(8)]
+    """The eight (rgb, depth) sensor images of sample frame 1 or 10 from the committed data fixture.  source: None | "fixture", or the
+    path of a reference tree whose samples/sphere_images_<idx>.bin is parsed instead."""
+    if source not in (None, "fixture"):
+        return load_frame(os.path.join(source, "samples", "sphere_images_%d.bin" % idx))
+    if idx not in _fixture:
+        fr = []
+        for lo in (0, 4):
+            z = np.load(os.path.join(FIXTURE, fixture_part(idx, lo)))
+            fr += [(z["rgb"][s], z["depth"][s]) for s in range(4)]
+        _fixture[idx] = fr
+    return _fixture[idx]
 
 
 def extrinsics(source=None):
-    """Rt [8] (sensor -> rig, float64 as the text files give them)."""
-    if source == "reference" or (source is None and have_reference()):
-        return [np.loadtxt(os.path.join(REF, "Calibration", "Extrinsics", "Rt_0%d.txt" % (s + 1))) for s in range(8)]
-    return list(fixture()["Rt"])
+    """Rt [8] (sensor -> rig, float64 as the text files give them): the fixture's copies of the files, or a reference tree's."""
+    where = FIXTURE if source in (None, "fixture") else os.path.join(source, "Calibration", "Extrinsics")
+    return [np.loadtxt(os.path.join(where, "Rt_0%d.txt" % (s + 1))) for s in range(8)]
 
 
 def write_bin(path, fr):

@@ -23,7 +23,7 @@ if os.path.exists(log):
     lines = open(log).read().split("\n")
     body = [l for l in lines if not l.startswith("{\"metric\"")]
     open(os.path.join(dst, rnd + "_pmc_and_trace_summary.txt"), "w").write(
-        "# tools/collect_profiles.sh %s on one MI355X box: per-kernel durations and gaps of `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 "
+        "# tools/collect_profiles.sh %s on one MI355X box: per-kernel durations and gaps of `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 5 "
         "--no-cpu-baseline --no-4k --no-native-multi --no-rotating --no-sequence` (tools/trace_gaps.py), the PMC passes of tools/prof_eval.py and tools/prof_hbm_legs.py "
         "(each counter set in its own run; FETCH_SIZE / WRITE_SIZE in KB, bytes = 2 x FETCH_SIZE + WRITE_SIZE for 16 B/lane streams, MI355X_MICROARCH.md), and the kernel traces "
         "of the HBM-fed legs (rotating over 8 copies of the pair, 4096 x 2048, 16-slot batch) beside the HIP-event figures of the same runs.\n" % tag + "\n".join(body))
