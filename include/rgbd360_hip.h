@@ -385,8 +385,10 @@ int rgbd360_set_plane_color_image(rgbd360_ctx* ctx, const uint8_t* rgb, size_t r
  * The inlier sums are exact 64-bit integer sums of terms rounded to 2^-28 m (m^2) -- order independent, ~20 x finer than the float
  * accumulators of PCL 1.7's computeMeanAndCovarianceMatrix; a region a few millimetres across whose smallest eigenvalue lies within
  * ~1e-8 m^2 of max_curvature x trace may still fall on the other side of the filter than a float64 evaluation puts it.  Errors of the
- * plane calls: -7 more than 4096 regions exceed min_inliers; -8 the sums left their range (N r^2 >= 3.4e10 m^2: a whole 4096 x 2048
- * frame that is one region beyond 64 m). */
+ * plane calls: -7 more than 4096 regions exceed min_inliers; -8 a region's sums would leave their exact range, decided before they are
+ * used from its count N and m = the largest |x|, |y|, |z| of its points (of the grown inlier set with the refinement on): refused when
+ * N (m^2 2^28 + 1) >= 2^63, i.e. N m^2 >= 3.4e10 m^2 (a whole 4096 x 2048 frame that is one region beyond 64 m), or when m >= 2896 m
+ * (m^2 2^28 >= 2^51: a single term no longer rounds exactly). */
 int rgbd360_plane_fit(rgbd360_ctx* ctx, const float* xyz, const float* normals, int rows, int cols, int min_inliers,
                       float angular_threshold, float distance_threshold, float max_curvature, int depth_mode,
                       int32_t* labels_out, rgbd360_plane* planes_out, int max_planes, int* n_planes_out);

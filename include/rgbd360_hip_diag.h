@@ -76,6 +76,14 @@ int rgbd360_debug_knobs_enabled(void);
 int rgbd360_frame_planes_stage_timing(rgbd360_ctx* ctx, int on);
 int rgbd360_frame_planes_stage_times(rgbd360_ctx* ctx, float us[3]);
 
+/* The per-region records the host turned into the plane records of the context's last plane call (rgbd360_plane_fit,
+ * _frame_planes[_dev], _cloud_planes, _sensor_planes), after the refinement's commit when the refinement is on: region slot s (the
+ * order the device assigned, not PCL's) has root pixel root[s], count[s] points and the nine exact sums mom[9 s + 0 .. 8] =
+ * sum x, y, z, xx, xy, xz, yy, yz, zz in units of 2^-28 m (m^2), each term rounded to the unit (half to even), two's complement.
+ * Every region that exceeded min_inliers is listed, also those the curvature filter dropped.  *n = number of regions (at most 4096; 0
+ * before the first plane call), of which the first `max` are copied; root / count / mom may be NULL.  Copies host memory only. */
+int rgbd360_debug_plane_sums(rgbd360_ctx* ctx, int max, int* n, int32_t* root, int32_t* count, int64_t* mom);
+
 int rgbd360_selftest_math(rgbd360_ctx* ctx, uint32_t first_bits, uint32_t count, unsigned long long mismatches[3]);
 /* csrc/libm_f32.h (asinf / atanf / roundf / atan2f restated operation for operation, what rgbd360_set_index_arithmetic(ctx, 1) computes
  * with) as the DEVICE evaluates it, against the C library of this process: the floats first_bits .. first_bits + count - 1 through the

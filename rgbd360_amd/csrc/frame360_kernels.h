@@ -1243,10 +1243,29 @@ constexpr int kMomPerThread = 8;
 // C = sum(x x) / N - (sum(x) / N)^2 that 6e-8 m^2 stands against a smallest eigenvalue of ~1e-7 m^2 for a region of a dozen pixels --
 // curvatures 2 % off the float64 checker's, planes on the other side of max_curvature (tests/tools/planes_soak.py: 2 of 5 k planes).
 // The sums stay inside 64 bits while N r^2 < 2^63 / 2^28 = 3.4e10 m^2: a full 4096 x 2048 frame that is ONE region at 64 m, the whole
-// range of a 16-bit millimetre image; the host checks the decoded sums (f360_planes_dev) and refuses a frame beyond that.
+// range of a 16-bit millimetre image.  The bound is checked BEFORE the sums are trusted: every slot also carries m = the largest |x|, |y|,
+// |z| of its points (an atomicMax on the float bits, folded in the same scan and hash as the sums), and the host refuses a region with
+// m^2 2^28 >= 2^51 (d2ll rounds exactly only below 2^51) or N (m^2 2^28 + 1) >= 2^63 (no term exceeds m^2 2^28 + 1/2 in magnitude, so
+// no sum, cross terms included, can wrap) -- f360_mom_in_range.
 constexpr double kMomScale = 268435456.0;
 constexpr int kMomReplicas = 16;              // copies of the global moment table (block b adds into copy b % 16): a wall is hit by
                                               // every block it spans, and same-address global atomics serialise; the host adds the copies
+// the per-slot maxima (one uint = float bits of m per slot, NOT replicated) live behind the replicas of the moment table
+__device__ __forceinline__ void atomic_max_bits(unsigned int* p, unsigned int v) {
+    // a maximum only grows during a launch: a value already as large makes the atomic a no-op, and a stale read only costs one
+    // (a wall's one word is otherwise hit by every block it spans)
+    if (*p < v) atomicMax(p, v);
+}
+__host__ __device__ inline unsigned int* mom_max_of(unsigned long long* mom, int max_slots) {
+    return reinterpret_cast<unsigned int*>(mom + (size_t)kMomReplicas * max_slots * 9);
+}
+__host__ __device__ inline const unsigned int* mom_max_of(const unsigned long long* mom, int max_slots) {
+    return reinterpret_cast<const unsigned int*>(mom + (size_t)kMomReplicas * max_slots * 9);
+}
+inline bool f360_mom_in_range(int count, float max_abs) {
+    const double t = (double)max_abs * max_abs * kMomScale;           // exact: a float squared has 48 significant bits
+    return t < 0x1p51 && (double)count * (t + 1.0) < 0x1p63;
+}
 
 // sum over the wave, the same in every lane: an add-scan on the DPP paths (row_shr 1 / 2 / 4 / 8, row_bcast 15 / 31) leaves the total in lane 63.
 // (Six __shfl_xor steps of a 64-bit value are twelve trips through the LDS crossbar; the moment kernel sums nine values per wave.)
@@ -1401,6 +1420,7 @@ __global__ __launch_bounds__(kAssignThreads) void k_f360_assign_list(const int* 
             fresh &= fresh - 1;
             const int s = __builtin_amdgcn_readlane(slot, src);
             for (int q = lane; q < mom_replicas * 9; q += 64) mom[((size_t)(q / 9) * max_slots + s) * 9 + q % 9] = 0ull;
+            if (lane == 0) mom_max_of(mom, max_slots)[s] = 0u;
         }
     }
 }
@@ -1424,14 +1444,19 @@ __device__ __forceinline__ int mom_run_slot(int* keys, int key) {
     }
     return -1;
 }
-__global__ __launch_bounds__(kAggThreads) void k_f360_moments(const float* __restrict__ xyz, const int* __restrict__ label,
+// waves_per_eu 8 = two 1024-thread blocks per CU: the range maximum took the kernel from 64 to 67 VGPRs, i.e. one block per CU, 52 instead
+// of 32 us at 4096 x 2048; capped at 64 it spills 16 bytes per lane and takes 43 us (18 instead of 15 us at 2048 x 1024)
+__global__ __launch_bounds__(kAggThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_f360_moments(const float* __restrict__ xyz, const int* __restrict__ label,
                                                                   const int* __restrict__ slot_of_root, int n,
                                                                   unsigned long long* __restrict__ mom, int max_slots) {
     __shared__ int keys[kMomRunHash];
     __shared__ unsigned long long vals[kMomRunHash][9];
+    __shared__ unsigned int vmax[kMomRunHash];              // float bits of the run's largest |coordinate| (f360_mom_in_range)
     unsigned long long* mom_rep = mom + (size_t)(blockIdx.x % kMomReplicas) * max_slots * 9;
+    unsigned int* mom_max = mom_max_of(mom, max_slots);
     if (threadIdx.x < kMomRunHash) {
         keys[threadIdx.x] = -1;
+        vmax[threadIdx.x] = 0u;
 #pragma unroll
         for (int k = 0; k < 9; ++k) vals[threadIdx.x][k] = 0ull;
     }
@@ -1465,27 +1490,32 @@ __global__ __launch_bounds__(kAggThreads) void k_f360_moments(const float* __res
     for (int j = 0; j < kMomPerThread; ++j)
         if (sl[j] >= 0) sl[j] = slot_of_root[sl[j]];
     auto d2ll = [](double v) -> long long { return __double_as_longlong(v + 6755399441055744.0) - 0x4338000000000000LL; };
-    auto flush = [&](int k, const long long t[9]) {
+    auto flush = [&](int k, const long long t[9], int mb) {
         const int e = mom_run_slot(keys, k);
 #pragma unroll
         for (int q = 0; q < 9; ++q) {
             if (e >= 0) atomicAdd(&vals[e][q], (unsigned long long)t[q]);
             else atomicAdd(&mom_rep[(size_t)k * 9 + q], (unsigned long long)t[q]);
         }
+        if (e >= 0) atomicMax(&vmax[e], (unsigned int)mb);
+        else atomic_max_bits(&mom_max[k], (unsigned int)mb);
     };
     long long v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     int key = -1;
+    int mb = 0;              // float bits of the largest |x|, |y|, |z| of the pending run (non-negative floats order as integers)
 #pragma unroll
     for (int j = 0; j < kMomPerThread; ++j) {
         if (sl[j] < 0) continue;
         if (sl[j] != key) {
             if (key >= 0) {          // a second run inside the lane's 8 pixels: the first one goes out on its own
-                flush(key, v);
+                flush(key, v, mb);
 #pragma unroll
                 for (int q = 0; q < 9; ++q) v[q] = 0;
+                mb = 0;
             }
             key = sl[j];
         }
+        mb = max(mb, __float_as_int(fmaxf(fabsf(pt[3 * j]), fmaxf(fabsf(pt[3 * j + 1]), fabsf(pt[3 * j + 2])))));
         const double x = pt[3 * j], y = pt[3 * j + 1], z = pt[3 * j + 2];
         v[0] += d2ll(x * kMomScale); v[1] += d2ll(y * kMomScale); v[2] += d2ll(z * kMomScale);
         v[3] += d2ll(x * x * kMomScale); v[4] += d2ll(x * y * kMomScale); v[5] += d2ll(x * z * kMomScale);
@@ -1498,7 +1528,8 @@ __global__ __launch_bounds__(kAggThreads) void k_f360_moments(const float* __res
             long long t[9];
 #pragma unroll
             for (int q = 0; q < 9; ++q) t[q] = wave_sum_ll(v[q]);
-            if (lane == 0) flush(first, t);
+            const int wmb = __builtin_amdgcn_readlane(wave_scan_max(mb), 63);
+            if (lane == 0) flush(first, t, wmb);
         }
     } else {
         const int prev = __shfl_up(key, 1);
@@ -1516,6 +1547,20 @@ __global__ __launch_bounds__(kAggThreads) void k_f360_moments(const float* __res
                 v[q] += take ? (long long)(((unsigned long long)hi << 32) | lo) : 0ll;                                     \
             }                                                                                                              \
         }
+        // the maxima first, on their own (one register across the six steps instead of one more beside the nine sums')
+#define F360_SEG_MAX(ctrl_, rows_)                                                                                         \
+        {                                                                                                                  \
+            const bool take = __builtin_amdgcn_update_dpp(-1, seg, ctrl_, rows_, 0xF, false) == seg;                       \
+            const int mo = __builtin_amdgcn_update_dpp(0, mb, ctrl_, rows_, 0xF, false);                                   \
+            mb = take && mo > mb ? mo : mb;                                                                                \
+        }
+        F360_SEG_MAX(0x111, 0xF)
+        F360_SEG_MAX(0x112, 0xF)
+        F360_SEG_MAX(0x114, 0xF)
+        F360_SEG_MAX(0x118, 0xF)
+        F360_SEG_MAX(0x142, 0xA)
+        F360_SEG_MAX(0x143, 0xC)
+#undef F360_SEG_MAX
         F360_SEG_STEP(0x111, 0xF)
         F360_SEG_STEP(0x112, 0xF)
         F360_SEG_STEP(0x114, 0xF)
@@ -1524,12 +1569,13 @@ __global__ __launch_bounds__(kAggThreads) void k_f360_moments(const float* __res
         F360_SEG_STEP(0x143, 0xC)
 #undef F360_SEG_STEP
         const bool tail = lane == 63 || ((heads >> (lane + 1)) & 1ull);
-        if (tail && key >= 0) flush(key, v);
+        if (tail && key >= 0) flush(key, v, mb);
     }
     __syncthreads();
     if (threadIdx.x < kMomRunHash && keys[threadIdx.x] >= 0) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) atomicAdd(&mom_rep[(size_t)keys[threadIdx.x] * 9 + k], vals[threadIdx.x][k]);
+        atomic_max_bits(&mom_max[keys[threadIdx.x]], vmax[threadIdx.x]);
     }
 }
 
@@ -1538,6 +1584,8 @@ __global__ __launch_bounds__(kAggThreads) void k_f360_moments(const float* __res
 struct F360SlotRecord {
     int root, count;
     unsigned long long mom[9];
+    float max_abs;                             // largest |x|, |y|, |z| of the region's points (the range bound, f360_mom_in_range)
+    int pad_;
 };
 constexpr int kF360PackHeader = 16;            // bytes: int n_slots + padding, the records follow (8-byte aligned)
 __global__ void k_f360_mom_reduce(const unsigned long long* __restrict__ mom, const int* __restrict__ n_slots, int max_slots,
@@ -1560,6 +1608,7 @@ __global__ void k_f360_mom_reduce(const unsigned long long* __restrict__ mom, co
     if (q == 0) {
         rec->root = root_of_slot[slot];
         rec->count = count_of_slot[slot];
+        rec->max_abs = __uint_as_float(mom_max_of(mom, max_slots)[slot]);
     }
 }
 
@@ -2050,6 +2099,7 @@ __global__ __launch_bounds__(64) void k_f360_slot_frames(const unsigned long lon
             if (lane == 0) {
                 rec->root = root_of_slot[slot];
                 rec->count = count_of_slot[slot];
+                rec->max_abs = __uint_as_float(mom_max_of(mom, max_slots)[slot]);
             }
         }
     }
@@ -2765,6 +2815,8 @@ __global__ __launch_bounds__(kCommitThreads) void k_f360_refine_commit(const flo
     unsigned long long* mom_rep = mom + (size_t)(blockIdx.x % kMomReplicas) * max_slots * 9;      // any copy will do: k_f360_mom_reduce sums them
     __shared__ int keys[kMomRunHash];
     __shared__ unsigned long long vals[kMomRunHash][10];
+    __shared__ unsigned int vmax[kMomRunHash];              // float bits of the largest grown |coordinate| (f360_mom_in_range)
+    unsigned int* mom_max = mom_max_of(mom, max_slots);
     const int lane = threadIdx.x & 63;
     const int base = blockIdx.x * kCommitThreads * kCommitPerThread;
     int slot[kCommitPerThread];
@@ -2780,6 +2832,7 @@ __global__ __launch_bounds__(kCommitThreads) void k_f360_refine_commit(const flo
     if (!__syncthreads_or(any ? 1 : 0)) return;            // most blocks of a clean frame hold no grown pixel
     if (threadIdx.x < kMomRunHash) {
         keys[threadIdx.x] = -1;
+        vmax[threadIdx.x] = 0u;
 #pragma unroll
         for (int q = 0; q < 10; ++q) vals[threadIdx.x][q] = 0ull;
     }
@@ -2790,6 +2843,7 @@ __global__ __launch_bounds__(kCommitThreads) void k_f360_refine_commit(const flo
         if (gm == 0ull) continue;                          // wave-uniform
         const int i = base + j * kCommitThreads + (int)threadIdx.x;
         unsigned long long v[10] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+        int mb = 0;
         if (grown[j]) {
             label[i] = root_of_slot[slot[j]];
             auto d2ll = [](double v) -> long long { return __double_as_longlong(v + 6755399441055744.0) - 0x4338000000000000LL; };
@@ -2799,6 +2853,7 @@ __global__ __launch_bounds__(kCommitThreads) void k_f360_refine_commit(const flo
             v[5] = (unsigned long long)d2ll(x * z * kMomScale); v[6] = (unsigned long long)d2ll(y * y * kMomScale);
             v[7] = (unsigned long long)d2ll(y * z * kMomScale); v[8] = (unsigned long long)d2ll(z * z * kMomScale);
             v[9] = 1ull;
+            mb = __float_as_int(fmaxf(fabsf(xyz[3 * (size_t)i]), fmaxf(fabsf(xyz[3 * (size_t)i + 1]), fabsf(xyz[3 * (size_t)i + 2]))));
         }
         // a noisy patch sends whole waves to ONE plane: those are summed across the wave first (sums of integers: order free) and
         // enter the hash once; 64 lanes x 10 atomics on one LDS address each took most of the first version's 118 us
@@ -2808,17 +2863,20 @@ __global__ __launch_bounds__(kCommitThreads) void k_f360_refine_commit(const flo
         if (one_plane) {
 #pragma unroll
             for (int q = 0; q < 10; ++q) v[q] = wave_sum_ll(v[q]);
+            mb = __builtin_amdgcn_readlane(wave_scan_max(mb), 63);
         }
         if (one_plane ? lane == first : grown[j]) {
             const int h = mom_run_slot(keys, slot[j]);
             if (h >= 0) {
 #pragma unroll
                 for (int q = 0; q < 10; ++q) atomicAdd(&vals[h][q], v[q]);
+                atomicMax(&vmax[h], (unsigned int)mb);
             } else {                                       // hash full (more than 256 planes meet in one block): straight to memory
 #pragma unroll
                 for (int q = 0; q < 9; ++q) atomicAdd(&mom_rep[(size_t)slot[j] * 9 + q], v[q]);
                 atomicAdd(&count_of_slot[slot[j]], (int)v[9]);
                 atomicAdd(n_changed, (int)v[9]);
+                atomic_max_bits(&mom_max[slot[j]], (unsigned int)mb);
             }
         }
     }
@@ -2830,6 +2888,7 @@ __global__ __launch_bounds__(kCommitThreads) void k_f360_refine_commit(const flo
             for (int q = 0; q < 9; ++q) atomicAdd(&mom_rep[(size_t)hs * 9 + q], vals[threadIdx.x][q]);
             atomicAdd(&count_of_slot[hs], (int)vals[threadIdx.x][9]);
             atomicAdd(n_changed, (int)vals[threadIdx.x][9]);
+            atomic_max_bits(&mom_max[hs], vmax[threadIdx.x]);
         }
     }
 }

@@ -72,6 +72,7 @@ struct F360State {
     hipEvent_t f_stage_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool f_stage_timing = false, f_stage_valid = false;
     int f_planes_available = 0;     // regions that passed every filter in the last plane call (may exceed the caller's max_planes)
+    bool f_planes_ran = false;      // the pinned pack holds the records of a plane call (rgbd360_debug_plane_sums)
     int f_refine = 0;               // segmentAndRefine's refinement after `segment` (rgbd360_set_plane_refinement)
     float f_refine_dist = 0.02f;    // PlaneRefinementComparator's default distance threshold
     int f_refine_changed = 0, f_refine_sweeps = 0;      // pixels relabelled / Jacobi sweeps of the last call
@@ -174,7 +175,8 @@ int f360_ensure(F360State* ctx, size_t n) {
     HIPC(ctx, hipMalloc(&ctx->f_window, n * sizeof(int)));
     HIPC(ctx, hipMalloc(&ctx->f_root_of_slot, kF360MaxSlots * sizeof(int)));
     HIPC(ctx, hipMalloc(&ctx->f_nslots, sizeof(int)));
-    HIPC(ctx, hipMalloc(&ctx->f_mom, (size_t)f360::kMomReplicas * kF360MaxSlots * 9 * sizeof(unsigned long long)));
+    HIPC(ctx, hipMalloc(&ctx->f_mom, (size_t)f360::kMomReplicas * kF360MaxSlots * 9 * sizeof(unsigned long long)      // + the per-slot maxima (mom_max_of)
+                                     + (size_t)kF360MaxSlots * sizeof(unsigned int)));
     HIPC(ctx, hipMalloc(&ctx->f_count_of_slot, kF360MaxSlots * sizeof(int)));
     // pinned: header, one moment record per slot, one hull record per slot behind them
     const size_t pack_bytes = f360::kF360PackHeader + (size_t)kF360MaxSlots * (sizeof(f360::F360SlotRecord) + sizeof(f360::F360HullRecord));
@@ -647,6 +649,9 @@ int f360_refine_dev(F360State* ctx, int rows, int cols, int nslots, std::vector<
     // count and the extent descriptors of the grown inlier sets (Frame360.h:1010-1037 derives them from the refined inlier cloud);
     // centroid / normal / d / curvature stay those of `segment`, as PCL's PlanarRegion keeps them
     const F360SlotRecord* recs = reinterpret_cast<const F360SlotRecord*>(ctx->f_pack_host + kF360PackHeader);
+    for (size_t k = 0; k < planes.size(); ++k)          // the grown inlier sets against the same a-priori bound as the segment's
+        if (!f360_mom_in_range(recs[plane_slot[k]].count, recs[plane_slot[k]].max_abs))
+            return fail(ctx, -8, "region moments out of range (N max(|x|,|y|,|z|)^2 >= 3.4e10 m^2, or a point beyond 2896 m)");
     for (size_t k = 0; k < planes.size(); ++k) {
         const F360SlotRecord& R = recs[plane_slot[k]];
         double m[9];
@@ -748,11 +753,16 @@ int f360_planes_dev(F360State* ctx, int rows, int cols, int min_inliers, float a
     // kernel published the tag from its last block: 256 blocks x a system-scope fence cost 10-22 us more than this launch.
     HIPC(ctx, hostwait::tag_and_wait(ctx->tag, ctx->stream));
     const int nslots = *reinterpret_cast<const volatile int*>(ctx->f_pack_host);
+    ctx->f_planes_ran = true;
     if (nslots > kF360MaxSlots) return fail(ctx, -7, "more than 4096 regions exceed min_inliers");
     const F360SlotRecord* recs = reinterpret_cast<const F360SlotRecord*>(ctx->f_pack_host + kF360PackHeader);
     std::vector<int> roots(nslots), counts(nslots);
     std::vector<double> mom((size_t)nslots * 9);
     for (int s = 0; s < nslots; ++s) {
+        // the fixed-point sums are exact only inside their range (frame360_kernels.h, kMomScale): refused a priori, from the
+        // region's count and largest coordinate, before any sum is decoded -- a wrapped sum can look as plausible as a right one
+        if (!f360_mom_in_range(recs[s].count, recs[s].max_abs))
+            return fail(ctx, -8, "region moments out of range (N max(|x|,|y|,|z|)^2 >= 3.4e10 m^2, or a point beyond 2896 m)");
         roots[s] = recs[s].root;
         counts[s] = recs[s].count;
         for (int k = 0; k < 9; ++k) mom[(size_t)s * 9 + k] = (double)(long long)recs[s].mom[k] / kMomScale;     // fixed point -> metres
@@ -774,10 +784,6 @@ int f360_planes_dev(F360State* ctx, int rows, int cols, int min_inliers, float a
         const double C[3][3] = {{m[3] / N - cx * cx, m[4] / N - cx * cy, m[5] / N - cx * cz},
                                 {m[4] / N - cx * cy, m[6] / N - cy * cy, m[7] / N - cy * cz},
                                 {m[5] / N - cx * cz, m[7] / N - cy * cz, m[8] / N - cz * cz}};
-        // the fixed-point sums wrap beyond N r^2 = 2^63 / kMomScale (frame360_kernels.h): a wrapped sum of squares is off by
-        // 6.9e10 / N m^2, i.e. negative or absurd -- refused, not returned
-        if (!(m[3] >= 0.0 && m[6] >= 0.0 && m[8] >= 0.0) || C[0][0] < -1e-3 || C[1][1] < -1e-3 || C[2][2] < -1e-3)
-            return fail(ctx, -8, "region moments out of range (points beyond ~60 m over a whole frame)");
         double evs[3], vecs[3][3];
         sorted_eigen3(C, evs, vecs);
         const double ev = evs[0];
@@ -1061,6 +1067,23 @@ extern "C" int rgbd360_set_plane_color_image(rgbd360_ctx* ctx_, const uint8_t* r
         ctx->f_col_img = {ctx->f_col_owned, (size_t)cols * 3, step};
     }
     ctx->f_col_rows = rows; ctx->f_col_cols = cols;
+    return 0;
+}
+extern "C" int rgbd360_debug_plane_sums(rgbd360_ctx* ctx_, int max, int* n, int32_t* root, int32_t* count, int64_t* mom) {
+    F360_ENTER(ctx_);
+    if (!ctx || !n || max < 0) return -1;
+    *n = 0;
+    if (!ctx->f_pack_host || !ctx->f_planes_ran) return 0;
+    const int ns_all = *reinterpret_cast<const volatile int*>(ctx->f_pack_host);
+    const int ns = ns_all < kF360MaxSlots ? ns_all : kF360MaxSlots;
+    const f360::F360SlotRecord* recs = reinterpret_cast<const f360::F360SlotRecord*>(ctx->f_pack_host + f360::kF360PackHeader);
+    for (int s = 0; s < ns && s < max; ++s) {
+        if (root) root[s] = recs[s].root;
+        if (count) count[s] = recs[s].count;
+        if (mom)
+            for (int q = 0; q < 9; ++q) mom[(size_t)s * 9 + q] = (int64_t)recs[s].mom[q];
+    }
+    *n = ns;
     return 0;
 }
 extern "C" int rgbd360_plane_refinement_stats(rgbd360_ctx* ctx_, int* pixels_relabelled, int* sweeps) {

@@ -569,6 +569,16 @@ class Frame360Stages:
         self._reg._check(self._L.rgbd360_plane_refinement_stats(self._reg._ctx(), C.byref(a), C.byref(b)))
         return dict(pixels_relabelled=a.value, sweeps=b.value)
 
+    def plane_sums(self):
+        """rgbd360_debug_plane_sums: the per-region records behind the last plane call's planes -- root pixel, count and the nine exact
+        int64 sums (x, y, z, xx, xy, xz, yy, yz, zz in 2^-28 m units) of every region slot, in the device's slot order."""
+        n = C.c_int()
+        self._reg._check(self._L.rgbd360_debug_plane_sums(self._reg._ctx(), 0, C.byref(n), None, None, None))
+        root, count = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        mom = np.zeros((n.value, 9), np.int64)
+        self._reg._check(self._L.rgbd360_debug_plane_sums(self._reg._ctx(), n.value, C.byref(n), _ptr(root), _ptr(count), _ptr(mom)))
+        return dict(root=root, count=count, mom=mom)
+
     def normals(self, xyz, rows, cols, max_depth_change_factor=0.05, normal_smoothing_size=8.0, depth_mode=1):
         xyz = np.ascontiguousarray(xyz, np.float32).reshape(rows * cols, 3)
         out = np.empty_like(xyz)
