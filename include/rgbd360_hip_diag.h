@@ -38,6 +38,28 @@ int rgbd360_forced_iters_batch(rgbd360_ctx* ctx, int n_pairs, const uint8_t* rgb
  * out_i: {status, done, level_active, it, n_evals, pend_nb}; cand_out / update_out (may be NULL): the state's candidate pose / update. */
 int rgbd360_debug_solve_partials(rgbd360_ctx* ctx, int level, const double row[32], int method, int fused, int out_i[6],
                                  float cand_out[16], float update_out[6]);
+/* One solve from a chosen Gauss-Newton state: the state of `level` is initialised at in->pose (pose and cand), then update, lambda,
+ * error, first and it are overwritten with the given values; the solve runs with the given termination settings (max_iters,
+ * tol_residual, tol_update, forced) and error form (occlusion 0: sqrt(sum / n); 1 / 2: photo RMS + depth RMS) on the partial row
+ * `row` (as rgbd360_debug_solve_partials).  route 0: k_solve; 1: the prologue of the fused launch k_eval_fs; 2: the same with the
+ * row at table row 40 behind a launch told to expect one pending row (needs a level of more than 40 block rows).  The state is read
+ * as the launch leaves it. */
+typedef struct {
+    float pose[16];      /* column-major */
+    float update[6];
+    double lambda, error;
+    int first, it;
+    int max_iters, forced;
+    double tol_residual, tol_update;
+} rgbd360_solve_state_in;
+typedef struct {
+    int status, done, level_active, it, n_evals, pend_nb;
+    int iters_level;     /* iters[level] */
+    float cand[16], pose[16], update[6];
+    double lambda, error, new_error, diff_error;
+} rgbd360_solve_state_out;
+int rgbd360_debug_solve_state(rgbd360_ctx* ctx, int level, const double row[32], const rgbd360_solve_state_in* in, int method,
+                              int occlusion, int route, rgbd360_solve_state_out* out);
 /* Average duration in microseconds of `reps` back-to-back launches of the fused per-pixel kernel alone
  * (HIP events on the stream the kernel is launched on). want_hg = 0 times the error-only variant, want_hg = 2 the launch of the
  * single-pair product schedule: k_eval_fs in the forced schedule, i.e. {solve of the previous pass, pass} = one whole Gauss-Newton

@@ -1538,7 +1538,7 @@ int alignFrames360(Ctx& ctx, const float* pose_guess, int method, float* pose_ou
     memset(ctx.g, 0, sizeof(ctx.g));
     for (int level = ctx.p.n_pyr - 1; level >= 0; --level) {
         prepare_level(ctx, level);
-        float lambda = 1.f;  // double lambda = 1e0 converted to float by Eigen's scalar*matrix
+        double lambda = 1.0;  // RPI.h:4589 double lambda = 1e0, lambda /= step in double; converted to float where Eigen scales the matrix
         const double step = 5;
         int it = 0;
         const int maxIters = ctx.p.max_iters;
@@ -1564,7 +1564,7 @@ int alignFrames360(Ctx& ctx, const float* pose_guess, int method, float* pose_ou
         };
         while (it < maxIters && unorm() > tol_update && diff_error > tol_residual) {
             hessgrad_fn(level, pose_estim);
-            if (gn_step(ctx.H, ctx.g, lambda, pose_estim, pose_estim_temp, update_pose) != 0) {
+            if (gn_step(ctx.H, ctx.g, (float)lambda, pose_estim, pose_estim_temp, update_pose) != 0) {
                 memcpy(pose_out, pose_estim, sizeof(pose_estim));  // relPose = pose_estim; avResidual = 0; return
                 res->status = 1;
                 for (int k = 0; k < 36; ++k) res->hessian[k] = ctx.H[k];

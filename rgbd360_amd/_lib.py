@@ -23,6 +23,7 @@ SYMBOLS = [
     "rgbd360_align360_batch_multi", "rgbd360_time_eval_kernel_rotating", "rgbd360_forced_iters_batch",
     "rgbd360_rig_create", "rgbd360_rig_destroy", "rgbd360_rig_last_error", "rgbd360_rig_set_target", "rgbd360_rig_set_source",
     "rgbd360_rig_eval", "rgbd360_rig_align", "rgbd360_rig_use_saliency", "rgbd360_debug_solve_partials",
+    "rgbd360_debug_solve_state",
 ]
 
 
@@ -37,6 +38,19 @@ class Result(C.Structure):
     _fields_ = [("status", C.c_int), ("iters", C.c_int * 8), ("sso", C.c_float), ("err_final", C.c_double),
                 ("rms_photo", C.c_double), ("rms_depth", C.c_double), ("hessian", C.c_float * 36),
                 ("gradient", C.c_float * 6)]
+
+
+class SolveStateIn(C.Structure):       # rgbd360_solve_state_in (rgbd360_hip_diag.h)
+    _fields_ = [("pose", C.c_float * 16), ("update", C.c_float * 6), ("lambda_", C.c_double), ("error", C.c_double),
+                ("first", C.c_int), ("it", C.c_int), ("max_iters", C.c_int), ("forced", C.c_int),
+                ("tol_residual", C.c_double), ("tol_update", C.c_double)]
+
+
+class SolveStateOut(C.Structure):      # rgbd360_solve_state_out
+    _fields_ = [("status", C.c_int), ("done", C.c_int), ("level_active", C.c_int), ("it", C.c_int), ("n_evals", C.c_int),
+                ("pend_nb", C.c_int), ("iters_level", C.c_int), ("cand", C.c_float * 16), ("pose", C.c_float * 16),
+                ("update", C.c_float * 6), ("lambda_", C.c_double), ("error", C.c_double), ("new_error", C.c_double),
+                ("diff_error", C.c_double)]
 
 
 class Plane(C.Structure):
@@ -153,6 +167,7 @@ def load() -> C.CDLL:
     L.rgbd360_forced_iters_batch.argtypes = [vp, i32, vp, vp, vp, vp, C.c_size_t, C.c_size_t, i32, i32, i32, i32, f32p, i32, i32, f32p,
                                              C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rgbd360_debug_solve_partials.argtypes = [vp, i32, vp, i32, i32, vp, f32p, f32p]
+    L.rgbd360_debug_solve_state.argtypes = [vp, i32, vp, C.POINTER(SolveStateIn), i32, i32, i32, C.POINTER(SolveStateOut)]
     L.rgbd360_set_plane_refinement.argtypes = [vp, i32, C.c_float]
     L.rgbd360_set_plane_color_image.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32]
     L.rgbd360_plane_refinement_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

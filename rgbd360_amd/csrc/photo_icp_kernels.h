@@ -871,8 +871,12 @@ __device__ __forceinline__ void level_init_one(GNState* st, const Pose16& pose, 
 
 // ---------------------------------------------------------------------------------------------------------
 // Lane-parallel 6x6 kernels for k_solve: matrix columns live on lanes, rows in registers with compile-time
-// indices (no scratch memory).  They perform the same float32 operations in the same order as gn::inverse6 /
-// gn::rank6 (gn_math.h), which the tests compare against through k_gn_step and the CPU oracle.
+// indices (no scratch memory).  qr_rank6_lanes performs the float32 operations of gn::rank6 (gn_math.h) in the same
+// order, IEEE divisions and square roots included.  lu_inverse6_lanes performs those
+// of gn::inverse6 in the same order except for the quotients: each multiplier is c_r * rcp_rn(p) instead of c_r / p, and
+// the back substitution multiplies by rcp_rn(U[r][r]) instead of dividing -- one extra rounding per quotient.  The tests
+// pin both (tests/test_gn_solve_exact.py): the rank verdict equals the oracle's, the update is the float32 restatement of
+// the reciprocal form bit for bit and lies within the float64 error bound.
 // ---------------------------------------------------------------------------------------------------------
 // Broadcast of one lane's value to the whole wave through a scalar register (v_readlane_b32): the lane index is
 // wave-uniform everywhere below, so no LDS crossbar (ds_bpermute) round trip is needed.
@@ -1001,14 +1005,16 @@ __device__ __forceinline__ int qr_rank6_lanes(const float* M /*LDS, column-major
                 tau = 0.f;
                 beta = c0;
             } else {
-                // exact sqrt / reciprocals in 6 / 3 instructions (sqrt_rn, rcp_rn); the quotients become products with an exact
-                // reciprocal (one extra rounding each, far below the rank thresholds)
-                beta = sqrt_rn(c0 * c0 + tailSq);
+                // IEEE square root and divisions like gn::rank6's.  The quotients as products with a correctly rounded reciprocal
+                // (one extra rounding each) gave another verdict than the oracle's on matrices whose smallest pivot sits at Eigen's
+                // threshold, and sqrt_rn (exact on [2^-60, 2^60] only) another one on matrices scaled by 2^-70
+                // (tests/test_gn_solve_exact.py: the near-threshold sweep, the 2^j edges)
+                beta = sqrtf(c0 * c0 + tailSq);
                 if (c0 >= 0.f) beta = -beta;
-                const float rden = rcp_rn(c0 - beta);
+                const float den = c0 - beta;
 #pragma unroll
-                for (int r = k + 1; r < 6; ++r) v[r] = ck[r] * rden;
-                tau = (beta - c0) * rcp_rn(beta);
+                for (int r = k + 1; r < 6; ++r) v[r] = ck[r] / den;
+                tau = (beta - c0) / beta;
             }
             v[k] = 1.f;
             float dot = 0.f;

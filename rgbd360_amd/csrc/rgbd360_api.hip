@@ -338,12 +338,16 @@ void launch_eval(rgbd360_ctx* ctx, int level, int method, bool hg, int occ = 0) 
 }
 
 // publish: the solve also writes the state into ctx->h_state and bumps the context's host tag (hostwait::wait picks it up)
-void launch_solve(rgbd360_ctx* ctx, int level, int mode, int forced, int occ = 0, bool publish = false) {
+// cfg_in (may be NULL): termination settings and error form of the solve instead of the context's (rgbd360_debug_solve_state)
+void launch_solve(rgbd360_ctx* ctx, int level, int mode, int forced, int occ = 0, bool publish = false, const SolveCfg* cfg_in = nullptr) {
     const Level& L = ctx->levels[level];
     SolveCfg cfg;
-    cfg.level = level; cfg.mode = mode; cfg.forced = forced; cfg.max_iters = ctx->p.max_iters; cfg.n_pixels = L.n;
-    cfg.occ = occ;
-    cfg.tol_residual = ctx->p.tol_residual; cfg.tol_update = ctx->p.tol_update;
+    if (cfg_in) cfg = *cfg_in;
+    cfg.level = level; cfg.mode = mode; cfg.n_pixels = L.n;
+    if (!cfg_in) {
+        cfg.forced = forced; cfg.max_iters = ctx->p.max_iters; cfg.occ = occ;
+        cfg.tol_residual = ctx->p.tol_residual; cfg.tol_update = ctx->p.tol_update;
+    }
     if (publish) {
         cfg.host_state = ctx->h_state;
         cfg.host_tag = ctx->tag.h;
@@ -364,8 +368,9 @@ SolveCfg fused_cfg(const rgbd360_ctx* ctx, int forced, int occ = 0) {
     cfg.tol_residual = ctx->p.tol_residual; cfg.tol_update = ctx->p.tol_update;
     return cfg;
 }
-// init_pose != nullptr: the launch starts the schedule itself at that pose (no k_level_init in front of it)
-void launch_eval_fused(rgbd360_ctx* ctx, int level, int method, int forced, const float* init_pose = nullptr) {
+// init_pose != nullptr: the launch starts the schedule itself at that pose (no k_level_init in front of it); cfg_in (may be NULL):
+// the solve's settings instead of fused_cfg(ctx, forced) (rgbd360_debug_solve_state)
+void launch_eval_fused(rgbd360_ctx* ctx, int level, int method, int forced, const float* init_pose = nullptr, const SolveCfg* cfg_in = nullptr) {
     FsInit init;
     init.on = init_pose ? 1 : 0;
     if (init_pose) memcpy(init.pose.v, init_pose, sizeof(init.pose.v));
@@ -374,7 +379,7 @@ void launch_eval_fused(rgbd360_ctx* ctx, int level, int method, int forced, cons
     LevelDev lv = level_dev(L);
     lv.min_depth = ctx->p.min_depth; lv.max_depth = ctx->p.max_depth;
     const EvalConsts ec = eval_consts(ctx->p);
-    const SolveCfg cfg = fused_cfg(ctx, forced);
+    const SolveCfg cfg = cfg_in ? *cfg_in : fused_cfg(ctx, forced);
     dim3 g(L.nblocks), b(kEvalThreads);
 #define LAUNCHF(M, S) hipLaunchKernelGGL((k_eval_fs<M, S>), g, b, 0, ctx->stream, (const GNState*)ctx->d_state, ctx->d_state_alt, (const double*)ctx->d_partials, \
                                       ctx->d_partials_alt, lv.src, lv.n, L.chunk, level, L.nblocks, ctx->pend_rows_hint, lv, ec, cfg, init)
@@ -1245,6 +1250,53 @@ int rgbd360_debug_solve_partials(rgbd360_ctx* ctx, int level, const double row[3
     out_i[0] = S.status; out_i[1] = S.done; out_i[2] = S.level_active; out_i[3] = S.it; out_i[4] = S.n_evals; out_i[5] = S.pend_nb;
     if (cand_out) memcpy(cand_out, S.cand, sizeof(float) * 16);
     if (update_out) memcpy(update_out, S.update, sizeof(float) * 6);
+    return 0;
+}
+
+// One solve from a chosen state (rgbd360_hip_diag.h): the state is initialised at in->pose like a level entry, the rest of the
+// chosen state is written over it field by field, and the row is placed as in rgbd360_debug_solve_partials.
+int rgbd360_debug_solve_state(rgbd360_ctx* ctx, int level, const double row[32], const rgbd360_solve_state_in* in, int method,
+                              int occlusion, int route, rgbd360_solve_state_out* out) {
+    int rc = check_args(ctx, level, method);
+    if (rc) return rc;
+    if (!row || !in || !out || route < 0 || route > 2 || occlusion < 0 || occlusion > 2) return fail(ctx, -1, "bad arguments");
+    if (route && !fused_ok(ctx, 0)) return fail(ctx, -1, "the fused-solve schedule is switched off");
+    hipSetDevice(ctx->p.device);
+    const Level& L = ctx->levels[level];
+    const int row_at = route == 2 ? 40 : 0;
+    if (row_at >= L.nblocks) return fail(ctx, -1, "the level has too few block rows for the late-row form");
+    launch_level_init(ctx, level, in->pose, 1);
+    GNState* d = ctx->d_state;
+    HIPC(ctx, hipMemcpyAsync(d->update, in->update, sizeof(float) * 6, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(&d->lambda, &in->lambda, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(&d->error, &in->error, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(&d->first, &in->first, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(&d->it, &in->it, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    const size_t rows = (size_t)std::max((ctx->max_blocks + 31) / 32 * 32, kPendingRows);
+    HIPC(ctx, hipMemsetAsync(ctx->d_partials, 0, rows * kNumPartials * sizeof(double), ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(ctx->d_partials + (size_t)row_at * kNumPartials, row, kNumPartials * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    SolveCfg cfg = fused_cfg(ctx, in->forced, occlusion);
+    cfg.max_iters = in->max_iters;
+    cfg.tol_residual = in->tol_residual;
+    cfg.tol_update = in->tol_update;
+    if (route) {
+        const int pend[2] = {L.nblocks, L.n};       // as if a pass of this level had just written the table
+        HIPC(ctx, hipMemcpyAsync(&d->pend_nb, pend, sizeof(pend), hipMemcpyHostToDevice, ctx->stream));
+        ctx->pend_rows_hint = route == 2 ? 1 : kPendingRows;
+        launch_eval_fused(ctx, level, method, in->forced, nullptr, &cfg);
+    } else {
+        launch_solve(ctx, level, 0, in->forced, occlusion, false, &cfg);
+    }
+    HIPC(ctx, hipGetLastError());
+    rc = read_state_sync(ctx);
+    if (rc) return rc;
+    const GNState& S = *ctx->h_state;
+    out->status = S.status; out->done = S.done; out->level_active = S.level_active; out->it = S.it; out->n_evals = S.n_evals;
+    out->pend_nb = S.pend_nb; out->iters_level = S.iters[level & 7];
+    memcpy(out->cand, S.cand, sizeof(out->cand));
+    memcpy(out->pose, S.pose, sizeof(out->pose));
+    memcpy(out->update, S.update, sizeof(out->update));
+    out->lambda = S.lambda; out->error = S.error; out->new_error = S.new_error; out->diff_error = S.diff_error;
     return 0;
 }
 

@@ -402,6 +402,25 @@ class RegisterPhotoICP:
         return dict(status=int(out_i[0]), done=int(out_i[1]), level_active=int(out_i[2]), it=int(out_i[3]), n_evals=int(out_i[4]),
                     pend_nb=int(out_i[5]), cand=pose_from_cm(cand), update=upd)
 
+    def debug_solve_state(self, level: int, row, pose=None, update=(1, 1, 1, 1, 1, 1), lam=1.0, error=0.0, first=1, it=0,
+                          max_iters=10, tol_residual=1e-3, tol_update=1e-4, forced=0, method: int = 0, occlusion: int = 0, route: int = 0):
+        """rgbd360_debug_solve_state: one solve on the partial row `row` (as debug_solve_partials) from a chosen state -- pose (4x4; cand
+        too), update, lambda, error, first, it -- with the given termination settings and error form, through k_solve (route 0), the
+        fused launch (1) or the fused launch with the row late in the table (2).  Returns the state as the launch leaves it."""
+        row = np.ascontiguousarray(row, np.float64)
+        assert row.shape == (32,)
+        si = _lib.SolveStateIn()
+        si.pose[:] = [float(x) for x in pose_to_cm(np.eye(4) if pose is None else pose)]
+        si.update[:] = [float(x) for x in np.asarray(update, np.float32)]
+        si.lambda_, si.error, si.first, si.it = float(lam), float(error), int(first), int(it)
+        si.max_iters, si.forced, si.tol_residual, si.tol_update = int(max_iters), int(forced), float(tol_residual), float(tol_update)
+        so = _lib.SolveStateOut()
+        self._check(self._L.rgbd360_debug_solve_state(self._ctx(), level, _ptr(row), C.byref(si), method, occlusion, route, C.byref(so)))
+        return dict(status=so.status, done=so.done, level_active=so.level_active, it=so.it, n_evals=so.n_evals, pend_nb=so.pend_nb,
+                    iters=so.iters_level, cand=pose_from_cm(np.array(so.cand[:], np.float32)),
+                    pose=pose_from_cm(np.array(so.pose[:], np.float32)), update=np.array(so.update[:], np.float32),
+                    lam=so.lambda_, error=so.error, new_error=so.new_error, diff_error=so.diff_error)
+
     def forced_iters_call(self, level: int, pose0, method: int, n_iters: int):
         """A closure that runs rgbd360_forced_iters with every argument converted ONCE (for timed loops: the numpy / ctypes
         conversions of forced_iters cost 10-15 us per call, as much as a Gauss-Newton iteration).  call() -> status;
