@@ -245,6 +245,11 @@ class RegisterRGBD360 {
     }
     int status() const { return status_; }      // 0 good, 1 insufficient matching, 2 unobservable / inconsistent
 
+    /*! Not in the reference: RegisterDensePhotoICP warps in the reference's OWN arithmetic -- both chains of calcPhotoICPError_robot /
+     *  calcHessianGradient_robot in Eigen's product order, double projection, round half away from zero -- instead of the device
+     *  definition (rgbd360_rig_set_index_arithmetic; the name of RegisterPhotoICP::setReferenceArithmetic). */
+    void setReferenceArithmetic(bool on) { rig_index_libm_ = on ? 1 : 0; }
+
     // :344-520 RegisterDensePhotoICP(frame1, frame2, pose_estim, method): dense registration of the two frames' 8 sensor image pairs
     // (frame->frameRGBD_[s].getRGBImage() / getDepthImage()) in the rig frame, rgbd360_rig_* (csrc/rig_dense.h).  Rt: the sensors'
     // sensor -> rig poses (frame1->calib->Rt_); the intrinsics are the reference's 525 * width / 640, centre (:357-365).  The
@@ -278,6 +283,8 @@ class RegisterRGBD360 {
             throw std::runtime_error("rgbd360_rig_create failed: no usable HIP device (there is no CPU fallback)");
         const std::unique_ptr<rgbd360_rig, void (*)(rgbd360_rig*)> rig_owner(rig_raw, rgbd360_rig_destroy);
         rgbd360_rig* rig = rig_raw;
+        if (rgbd360_rig_set_index_arithmetic(rig, rig_index_libm_) != 0)
+            throw std::runtime_error(std::string("rgbd360_rig_set_index_arithmetic: ") + rgbd360_rig_last_error(rig));
         auto set = [&](bool target, const std::vector<ImageView>& rgb, const std::vector<ImageView>& depth) {
             std::vector<const uint8_t*> rp(S);
             std::vector<const void*> dp(S);
@@ -362,6 +369,7 @@ class RegisterRGBD360 {
     size_t max_ref_ = 0, max_trg_ = 0;
     registrationType mode_ = DEFAULT_6DoF;
     bool done_ = false;
+    int rig_index_libm_ = 0;           // setReferenceArithmetic
     int status_ = 1;
     Mat4f rigidTransf_ = Mat4f::Identity();
     Mat6f informationM_{};

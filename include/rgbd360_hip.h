@@ -101,7 +101,7 @@ int rgbd360_promote_source_to_target(rgbd360_ctx* ctx);
  * row / column = round(...)) and pinhole (RPI.h:701-708: column = round(x fx / z + ox), ...) -- for every later pass of this context:
  * rgbd360_align360 and its _begin / _finish, the batch and sequence entries that run on this context, the occlusion-aware passes,
  * rgbd360_eval*, rgbd360_warp_indices*, rgbd360_align_pinhole; the sibling contexts and engines a sequence call creates inherit it, a
- * multi-GPU handle has rgbd360_multi_set_index_arithmetic (the 8-sensor rgbd360_rig_* objects keep the device definition):
+ * multi-GPU handle has rgbd360_multi_set_index_arithmetic, an 8-sensor rig rgbd360_rig_set_index_arithmetic:
  *   0 (default): the device definition -- fused multiply-adds, two correctly rounded arctangent evaluations by one polynomial,
  *      round-half-up; mirrored bit for bit by the CPU checker's math_mode 1.  About 1e-4 of the pixels land on a neighbouring target
  *      pixel compared with the reference built against glibc.
@@ -269,6 +269,15 @@ int  rgbd360_rig_align(rgbd360_rig* rig, const float guess[16], int method, floa
  * calcGradientXY_saliency from the TARGET's gray gradients, RPI.h:401-425, used as source pixel indices).  Off by default, as in
  * every application of the reference. */
 int  rgbd360_rig_use_saliency(rgbd360_rig* rig, int on, float thres_saliency);
+/* The arithmetic of the rig's warp (rgbd360_set_index_arithmetic's modes) for every later rgbd360_rig_eval / rgbd360_rig_align; may be
+ * set before or after the frames.  0 (default): the device definition -- one chain q = (T Rt_s) p, P' = Rt_s^-1 q for both passes,
+ * fused multiply-adds, round-half-up.  1: the REFERENCE's arithmetic, whose two passes warp a pixel differently:
+ * calcPhotoICPError_robot through relPoseCam = (Rt_s^-1 T) Rt_s formed in float (RPI.h:4923-4924, 5021-5029), calcHessianGradient_robot
+ * through Rt_s^-1 (T (Rt_s p)) (RPI.h:5278-5290); Eigen's product order without fused multiply-adds, 1.0 / Z' and the projection in
+ * double, round half away from zero.  Target indices, visibility and counts of both passes are bit-equal to the CPU checker's math_mode 0
+ * restatement of the reference.  The Levenberg-Marquardt loop is the same in both modes.  Returns -1 for another mode. */
+int  rgbd360_rig_set_index_arithmetic(rgbd360_rig* rig, int mode);
+int  rgbd360_rig_get_index_arithmetic(rgbd360_rig* rig);
 
 /* ---- Frame360 per-pixel stages ------------------------------------------------------------------------------ */
 

@@ -106,6 +106,14 @@ int rgbd360_frame_planes_stage_times(rgbd360_ctx* ctx, float us[3]);
  * before the first plane call), of which the first `max` are copied; root / count / mom may be NULL.  Copies host memory only. */
 int rgbd360_debug_plane_sums(rgbd360_ctx* ctx, int max, int* n, int32_t* root, int32_t* count, int64_t* mom);
 
+/* The target pixel of every source pixel of every sensor of an 8-sensor rig at rig pose `pose` on `level`, in the rig's current
+ * arithmetic (rgbd360_rig_set_index_arithmetic) -- the warp k_eval_rig runs.  chain 0: the error pass's (calcPhotoICPError_robot),
+ * 1: the H / g pass's (calcHessianGradient_robot); in the device definition (mode 0) both are the same.  out: [S][rows * cols][2]
+ * int32 (row, col), the convention of rgbd360_warp_indices_pinhole: (-1, -1) for a source pixel without a valid point (depth outside
+ * (min_depth, max_depth)) and for a projection outside the image or not finite.  The saliency list is not applied.  Needs the
+ * source frame only. */
+int rgbd360_rig_warp_indices(rgbd360_rig* rig, int level, const float pose[16], int chain, int32_t* out);
+
 int rgbd360_selftest_math(rgbd360_ctx* ctx, uint32_t first_bits, uint32_t count, unsigned long long mismatches[3]);
 /* csrc/libm_f32.h (asinf / atanf / roundf / atan2f restated operation for operation, what rgbd360_set_index_arithmetic(ctx, 1) computes
  * with) as the DEVICE evaluates it, against the C library of this process: the floats first_bits .. first_bits + count - 1 through the

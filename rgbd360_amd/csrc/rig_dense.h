@@ -13,7 +13,15 @@
 // oracle/photo_icp_ref.cpp, which restates the same fixed function line by line and is this file's checker.
 //
 // Device arithmetic definition of the warp (the oracle's math_mode 1 repeats it): q = (T Rt_s) p and P' = Rt_s^-1 q with fused
-// multiply-adds, correctly rounded 1/Z', column = round(fma(X' fx, 1/Z', ox)), row likewise, round = floor(x + 0.5).
+// multiply-adds, correctly rounded 1/Z', column = round(fma(X' fx, 1/Z', ox)), row likewise, round = floor(x + 0.5).  One chain serves
+// both passes.
+// The REFERENCE's arithmetic (LIBM = 1, rgbd360_rig_set_index_arithmetic(rig, 1); the oracle's math_mode 0): the two passes warp a
+// pixel differently, so every pixel goes through both chains --
+//   chain 0, calcPhotoICPError_robot (RPI.h:4923-4924, 5021-5029): P' = C_s p with C_s = (Rt_s^-1 T) Rt_s formed in float,
+//            column = round((double)(X' fx) * inv + ox), inv = 1.0 / (double)Z';
+//   chain 1, calcHessianGradient_robot (RPI.h:5278-5290): q = T (Rt_s p), P' = Rt_s^-1 q, column = round(((double)X' * fx) * inv + ox);
+// Eigen's product order without fused multiply-adds, round half away from zero, a |x| > 1e9 or non-finite projection is invisible.
+// The error sums (and FIX C's depth Z') follow chain 0, the Jacobian rows (q, X', Y', Z', 1/Z' and the target they read) chain 1.
 // Row algebra: jacobianT36 = R_s^-1 [I | -skew(q)], so a camera-frame row vector a contributes (b, q x b) with b = R_s a.
 #pragma once
 
@@ -24,6 +32,18 @@ struct RigPoses {
     float M[kMaxRigSensors][12];       // rows of (T * Rt_s):   q  = M p      (r00 r01 r02 tx | r10 ... | r20 ...)
     float Ri[kMaxRigSensors][12];      // rows of Rt_s^-1:      P' = Ri q
 };
+// What the reference's arithmetic needs besides.  A kernel argument of its own BEHIND the others: the argument offsets of the default
+// instantiation stay what they were, and k_eval_rig<M, 0> compiles to the former k_eval_rig<M> (hipcc -S: one commutative s_and_b64 of the
+// projection's sane mask has its operands swapped; nothing else differs).
+struct RigPosesRef {
+    float Rt[kMaxRigSensors][12];      // rows of Rt_s
+    float C[kMaxRigSensors][12];       // rows of C_s = (Rt_s^-1 T) Rt_s   (relPoseCam; gn::mat4_mul = the oracle's mat4_mul_f32)
+    float T[12];                       // rows of T
+};
+// k_eval_rig's argument block: 4 pointers, 6 ints / floats, PinK, EvalConsts and both pose blocks (~1.7 KiB) -- within the 4 KiB a
+// kernel argument block may hold
+static_assert(sizeof(RigPoses) + sizeof(RigPosesRef) + sizeof(PinK) + sizeof(EvalConsts) + 4 * sizeof(void*) + 6 * sizeof(int) <= 4096,
+              "rig kernel arguments exceed 4 KiB: pass the pose blocks in a device buffer");
 
 __device__ __forceinline__ void xform12(const float* m, float x, float y, float z, float& X, float& Y, float& Z) {
     X = fmaf(m[2], z, fmaf(m[1], y, fmaf(m[0], x, m[3])));
@@ -31,10 +51,155 @@ __device__ __forceinline__ void xform12(const float* m, float x, float y, float 
     Z = fmaf(m[10], z, fmaf(m[9], y, fmaf(m[8], x, m[11])));
 }
 
+// the oracle's xform_f32: ((m0 x + m1 y) + m2 z) + t, no contraction
+__device__ __forceinline__ void xform12_ref(const float* m, float x, float y, float z, float& X, float& Y, float& Z) {
+#pragma clang fp contract(off)
+    X = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
+    Y = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
+    Z = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+}
+
+// The warp of one source point of sensor s: q (the point in the rig frame after the motion; not formed by LIBM = 1's chain 0), P' = (X,
+// Y, Z), iz = 1 / Z and the target pixel (ri, ci); returns whether the projection is finite and within 1e9 (the caller tests the image
+// bounds and the point's own validity).  LIBM = 0: the device definition, `chain` unused.  LIBM = 1: the reference's chain `chain` (0:
+// error pass, 1: H / g pass).  k_eval_rig and the diagnostic k_rig_warp_indices both warp through this function.
+template <int LIBM>
+__device__ __forceinline__ bool rig_warp(const float* Mq, const float* Ri, const RigPosesRef& ref, int s, int chain, float px, float py, float pz,
+                                         const PinK& K, float& qx, float& qy, float& qz, float& X, float& Y, float& Z, float& iz, int& ri,
+                                         int& ci) {
+    if (LIBM == 0) {
+        xform12(Mq, px, py, pz, qx, qy, qz);
+        xform12(Ri, qx, qy, qz, X, Y, Z);
+        iz = rcp_rn(Z);
+        const float tc = fmaf(X * K.fx, iz, K.ox);
+        const float tr = fmaf(Y * K.fy, iz, K.oy);
+        const bool sane = (fabsf(tr) < 1e9f) && (fabsf(tc) < 1e9f);
+        ri = round_index(sane ? tr : -1.f);
+        ci = round_index(sane ? tc : -1.f);
+        return sane;
+    }
+    double dc, dr;
+    if (chain == 0) {                                     // uniform
+#pragma clang fp contract(off)
+        qx = qy = qz = 0.f;
+        xform12_ref(ref.C[s], px, py, pz, X, Y, Z);       // relPoseCam * p
+        const double inv = 1.0 / (double)Z;
+        iz = (float)inv;
+        dc = (double)(X * K.fx) * inv + (double)K.ox;
+        dr = (double)(Y * K.fy) * inv + (double)K.oy;
+    } else {
+#pragma clang fp contract(off)
+        float ux, uy, uz;
+        xform12_ref(ref.Rt[s], px, py, pz, ux, uy, uz);   // Rt_s * p
+        xform12_ref(ref.T, ux, uy, uz, qx, qy, qz);       // T * (Rt_s * p)
+        xform12_ref(Ri, qx, qy, qz, X, Y, Z);             // Rt_s^-1 * q
+        const double inv = 1.0 / (double)Z;
+        iz = (float)inv;
+        dc = ((double)X * (double)K.fx) * inv + (double)K.ox;
+        dr = ((double)Y * (double)K.fy) * inv + (double)K.oy;
+    }
+    const bool sane = fabs(dr) <= 1e9 && fabs(dc) <= 1e9;      // false for inf and NaN too
+    ri = (int)round(sane ? dr : -1.0);                          // round(): half away from zero
+    ci = (int)round(sane ? dc : -1.0);
+    return sane;
+}
+
+// One pixel of k_eval_rig in the reference's arithmetic: the error terms from chain 0, the Jacobian rows from chain 1.  The target is
+// gathered once, and a second time only by the lanes whose chain-1 pixel differs (rare: a projection within rounding of a pixel border).
 template <int METHOD>
+__device__ __forceinline__ void eval_rig_ref_pixel(EvalAcc& A, const float* Ri, const RigPosesRef& ref, int s, const float4& p, int i,
+                                                   bool in_range, const F3* __restrict__ trgP, const F3* __restrict__ trgD, int rows, int cols,
+                                                   const PinK& K, const EvalConsts& ec, float sal_thr) {
+    float qx, qy, qz, X0, Y0, Z0, iz0, X, Y, Z, iz;
+    int r0, c0, r1, c1;
+    const bool ok0 = rig_warp<1>(nullptr, Ri, ref, s, 0, p.x, p.y, p.z, K, qx, qy, qz, X0, Y0, Z0, iz0, r0, c0) &&
+                     ((unsigned)r0 < (unsigned)rows) && ((unsigned)c0 < (unsigned)cols);
+    const bool ok1 = rig_warp<1>(nullptr, Ri, ref, s, 1, p.x, p.y, p.z, K, qx, qy, qz, X, Y, Z, iz, r1, c1) &&
+                     ((unsigned)r1 < (unsigned)rows) && ((unsigned)c1 < (unsigned)cols);
+    bool live = in_range && (p.x != kInvalidPoint);
+    if (sal_thr >= 0.f) {      // uniform: bUseSalientPixels -- the list holds source indices, both passes read it
+        const F3 ts = trgP[in_range ? i : 0];
+        live = live && (fabsf(ts.b) > sal_thr || fabsf(ts.c) > sal_thr);
+    }
+    const bool vis0 = ok0 && live, vis = ok1 && live;
+    const unsigned t0 = vis0 ? (unsigned)(r0 * cols + c0) : 0u, t1 = vis ? (unsigned)(r1 * cols + c1) : 0u;
+    F3 tp0 = {0.f, 0.f, 0.f}, td0 = {0.f, 0.f, 0.f};
+    if (METHOD != 1) tp0 = trgP[t0];
+    if (METHOD != 0) td0 = trgD[t0];
+    F3 tp = tp0, td = td0;
+    if (vis && t1 != t0) {
+        if (METHOD != 1) tp = trgP[t1];
+        if (METHOD != 0) td = trgD[t1];
+    }
+    // b = R_s a: R_s = (Rt_s^-1 rotation)^T, i.e. b_i = sum_j Ri[j][i] a_j
+    auto to_rig = [&](float ax, float ay, float az, float& bx, float& by, float& bz) {
+#pragma clang fp contract(fast)
+        bx = Ri[0] * ax + Ri[4] * ay + Ri[8] * az;
+        by = Ri[1] * ax + Ri[5] * ay + Ri[9] * az;
+        bz = Ri[2] * ax + Ri[6] * ay + Ri[10] * az;
+    };
+    // calcPhotoICPError_robot: every visible pixel of chain 0, no saliency test
+    if (METHOD != 1) {
+        A.nP += ballot_count(vis0);
+        if (vis0) {
+#pragma clang fp contract(fast)
+            const float photoDiff = tp0.a - p.w;
+            const float res = weight_huber_fast(photoDiff, ec.sigma_photo) * ec.sigma_photo_inv_f * photoDiff;
+            A.e2p += res * res;
+        }
+    }
+    if (METHOD != 0) {
+        const bool err_on = vis0 && isfinite(td0.a);
+        A.nD += ballot_count(err_on);
+        if (err_on) {
+#pragma clang fp contract(fast)
+            const float depthDiff = td0.a - Z0;                                   // FIX C: chain 0's transformed depth
+            const float sd = ec.sigma_depth * Z0;
+            const float res = weight_huber_fast(depthDiff, sd) * fast_rcp(sd) * depthDiff;
+            A.e2d += res * res;
+        }
+    }
+    // calcHessianGradient_robot: the rows of chain 1's pixel, with its saliency `continue`s (RPI.h:5331-5332, 5352-5353)
+    const bool sal_p = !(fabsf(tp.b) < ec.thr_photo && fabsf(tp.c) < ec.thr_photo);
+    const bool sal_d = !(fabsf(td.b) < ec.thr_depth && fabsf(td.c) < ec.thr_depth);
+    const bool fin_d = METHOD != 0 && isfinite(td.a);
+    const float iz2 = iz * iz;
+    if (METHOD != 1) {
+        const bool row_on = vis && sal_p && (METHOD == 0 || !fin_d || sal_d);
+        A.nVis += ballot_count(row_on);
+        if (row_on) {
+#pragma clang fp contract(fast)
+            const float photoDiff = tp.a - p.w;
+            const float wpf = weight_huber_fast(photoDiff, ec.sigma_photo) * ec.sigma_photo_inv_f;
+            const float res = wpf * photoDiff;
+            const float wgx = wpf * tp.b * K.fx, wgy = wpf * tp.c * K.fy;
+            float bx, by, bz;
+            to_rig(wgx * iz, wgy * iz, -(wgx * X + wgy * Y) * iz2, bx, by, bz);
+            accumulate_row(A, bx, by, bz, qx, qy, qz, res);
+        }
+    }
+    if (METHOD != 0) {
+        const bool row_on = vis && fin_d && sal_d && (METHOD == 1 || sal_p);
+        A.nVis += ballot_count(row_on);
+        if (row_on) {
+#pragma clang fp contract(fast)
+            const float depthDiff = td.a - Z;                                     // FIX C
+            const float sd = ec.sigma_depth * Z;
+            const float wd = weight_huber_fast(depthDiff, sd) * fast_rcp(sd);
+            const float res = wd * depthDiff;
+            const float gx = td.b * K.fx, gy = td.c * K.fy;
+            float bx, by, bz;
+            to_rig(wd * (gx * iz), wd * (gy * iz), wd * (-(gx * X + gy * Y) * iz2 - 1.f), bx, by, bz);      // FIX B: - jacobianT36.row(2)
+            accumulate_row(A, bx, by, bz, qx, qy, qz, res);
+        }
+    }
+}
+
+template <int METHOD, int LIBM>
 __global__ __launch_bounds__(kEvalThreads) void k_eval_rig(const float4* __restrict__ src, const F3* __restrict__ trgP,
                                                             const F3* __restrict__ trgD, int rows, int cols, int n, PinK K, EvalConsts ec,
-                                                            RigPoses poses, double* __restrict__ partials, int partials_stride, int chunk, float sal_thr) {
+                                                            RigPoses poses, double* __restrict__ partials, int partials_stride, int chunk, float sal_thr,
+                                                            RigPosesRef ref) {
     const int b = blockIdx.x, s = blockIdx.y;
     const int base = b * chunk;
     const int end = min(base + chunk, n);
@@ -53,14 +218,13 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_rig(const float4* __restr
         const int i = base + k * kEvalThreads + (int)threadIdx.x;
         const bool in_range = i < end;
         const float4 p = src[in_range ? i : n - 1];
-        float qx, qy, qz, X, Y, Z;
-        xform12(Mq, p.x, p.y, p.z, qx, qy, qz);
-        xform12(Ri, qx, qy, qz, X, Y, Z);
-        const float iz = rcp_rn(Z);
-        const float tc = fmaf(X * K.fx, iz, K.ox);
-        const float tr = fmaf(Y * K.fy, iz, K.oy);
-        const bool sane = (fabsf(tr) < 1e9f) && (fabsf(tc) < 1e9f);
-        const int ri = round_index(sane ? tr : -1.f), ci = round_index(sane ? tc : -1.f);
+        if constexpr (LIBM != 0) {
+            eval_rig_ref_pixel<METHOD>(A, Ri, ref, s, p, i, in_range, trgP, trgD, rows, cols, K, ec, sal_thr);
+            continue;
+        }
+        float qx, qy, qz, X, Y, Z, iz;
+        int ri, ci;
+        const bool sane = rig_warp<0>(Mq, Ri, ref, s, 0, p.x, p.y, p.z, K, qx, qy, qz, X, Y, Z, iz, ri, ci);
         bool vis = sane && ((unsigned)ri < (unsigned)rows) && ((unsigned)ci < (unsigned)cols) && in_range && (p.x != kInvalidPoint);
         if (sal_thr >= 0.f) {      // uniform: bUseSalientPixels (RPI.h:4930-5003, 5121-5262) -- both passes run over vSalientPixels only, the
             const F3 ts = trgP[in_range ? i : 0];      // interior pixels whose TARGET gray gradient exceeds thresSaliency, used as source indices
@@ -182,6 +346,26 @@ __global__ __launch_bounds__(256) void k_rig_reduce(const double* __restrict__ p
     }
 }
 
+// rgbd360_rig_warp_indices: the (row, col) every source pixel of sensor blockIdx.y warps to, through rig_warp; (-1, -1) for an invalid
+// source point or an invisible projection.  out = [S][n][2].
+template <int LIBM>
+__global__ __launch_bounds__(256) void k_rig_warp_indices(const float4* __restrict__ src, int rows, int cols, int n, PinK K, RigPoses poses,
+                                                          RigPosesRef ref, int chain, int32_t* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
+    if (i >= n) return;
+    const size_t o = (size_t)s * n + i;
+    const float4 p = src[o];
+    int r = -1, c = -1;
+    if (p.x != kInvalidPoint) {
+        float qx, qy, qz, X, Y, Z, iz;
+        int ri, ci;
+        const bool sane = rig_warp<LIBM>(poses.M[s], poses.Ri[s], ref, s, chain, p.x, p.y, p.z, K, qx, qy, qz, X, Y, Z, iz, ri, ci);
+        if (sane && ((unsigned)ri < (unsigned)rows) && ((unsigned)ci < (unsigned)cols)) { r = ri; c = ci; }
+    }
+    out[2 * o] = r;
+    out[2 * o + 1] = c;
+}
+
 }  // namespace r360
 
 struct rgbd360_rig {
@@ -195,6 +379,7 @@ struct rgbd360_rig {
     unsigned* d_ticket = nullptr;     // device counter of k_rig_reduce's blocks
     bool have_src = false, have_trg = false;
     float sal_thr = -1.f;             // useSaliency(true) on the per-sensor objects: thresSaliency (RPI.h:217); < 0 = off
+    int index_libm = 0;               // rgbd360_rig_set_index_arithmetic: 1 = the warp in the reference's arithmetic (k_eval_rig<M, 1>)
     std::string err;
 };
 
@@ -292,28 +477,54 @@ struct RigSums {
     double error() const { return e2p + e2d; }      // calcPhotoICPError_robot returns error2, the plain sum
 };
 
+// the pose blocks of the warp at rig pose T (column-major); Q is filled for the reference's arithmetic only
+void rig_poses(const rgbd360_rig* R, const float* T, RigPoses* P, RigPosesRef* Q) {
+    for (int s = 0; s < R->S; ++s) {
+        float M[16];
+        gn::mat4_mul(T, R->Rt[s], M);
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) {
+                P->M[s][4 * r + c] = M[c * 4 + r];
+                P->Ri[s][4 * r + c] = R->Rt_inv[s][c * 4 + r];
+            }
+    }
+    memset(Q, 0, sizeof(*Q));
+    if (!R->index_libm) return;
+    for (int s = 0; s < R->S; ++s) {
+        float A[16], C[16];
+        gn::mat4_mul(R->Rt_inv[s], T, A);
+        gn::mat4_mul(A, R->Rt[s], C);                     // relPoseCam = poseCamRobot_inv * poseGuess * poseCamRobot   RPI.h:4923-4924
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) {
+                Q->Rt[s][4 * r + c] = R->Rt[s][c * 4 + r];
+                Q->C[s][4 * r + c] = C[c * 4 + r];
+            }
+    }
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) Q->T[4 * r + c] = T[c * 4 + r];
+}
+
 // one fused pass over all sensors at rig pose T; per-sensor totals are cast to float and added in sensor order like
 // `Hessian += alignSensorID[sensor_id].getHessian()` (RegisterRGBD360.h:435-440)
 int rig_eval(rgbd360_rig* R, int level, const float* T, int method, RigSums* out) {
     SeqEngine* E = R->E;
     const SeqLevel& L = E->levels[level];
     RigPoses P;
-    for (int s = 0; s < R->S; ++s) {
-        float M[16];
-        gn::mat4_mul(T, R->Rt[s], M);
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 4; ++c) {
-                P.M[s][4 * r + c] = M[c * 4 + r];
-                P.Ri[s][4 * r + c] = R->Rt_inv[s][c * 4 + r];
-            }
-    }
+    RigPosesRef Q;
+    rig_poses(R, T, &P, &Q);
     const PinK K = rig_level_K(R, level);
     const EvalConsts ec = eval_consts(R->p);
     const dim3 g(L.nblocks, R->S), b(kEvalThreads);
-#define LAUNCHR(Mth) hipLaunchKernelGGL((k_eval_rig<Mth>), g, b, 0, E->stream, L.srcRec, L.trgP[0], L.trgD[0], L.rows, L.cols, L.n, K, ec, P, E->d_partials, E->partials_stride, L.chunk, R->sal_thr)
-    if (method == 0) LAUNCHR(0);
-    else if (method == 1) LAUNCHR(1);
-    else LAUNCHR(2);
+#define LAUNCHR(Mth, Lm) hipLaunchKernelGGL((k_eval_rig<Mth, Lm>), g, b, 0, E->stream, L.srcRec, L.trgP[0], L.trgD[0], L.rows, L.cols, L.n, K, ec, P, E->d_partials, E->partials_stride, L.chunk, R->sal_thr, Q)
+    if (R->index_libm) {
+        if (method == 0) LAUNCHR(0, 1);
+        else if (method == 1) LAUNCHR(1, 1);
+        else LAUNCHR(2, 1);
+    } else {
+        if (method == 0) LAUNCHR(0, 0);
+        else if (method == 1) LAUNCHR(1, 0);
+        else LAUNCHR(2, 0);
+    }
 #undef LAUNCHR
     hipLaunchKernelGGL(k_rig_reduce, dim3(R->S), dim3(256), 0, E->stream, E->d_partials, E->partials_stride, L.nblocks, R->h_tot, R->d_ticket,
                        R->tag.h, ++R->tag.seq);
@@ -415,6 +626,43 @@ int rgbd360_rig_use_saliency(rgbd360_rig* R, int on, float thres_saliency) {
     if (!R) return -1;
     if (on && !(thres_saliency >= 0.f)) return rfail(R, -1, "thres_saliency must be >= 0");
     R->sal_thr = on ? thres_saliency : -1.f;
+    return 0;
+}
+
+int rgbd360_rig_set_index_arithmetic(rgbd360_rig* R, int mode) {
+    if (!R) return -1;
+    if (mode != 0 && mode != 1) return rfail(R, -1, "index arithmetic: 0 (device definition) or 1 (the reference's arithmetic)");
+    R->index_libm = mode;
+    return 0;
+}
+int rgbd360_rig_get_index_arithmetic(rgbd360_rig* R) { return R ? R->index_libm : -1; }
+
+int rgbd360_rig_warp_indices(rgbd360_rig* R, int level, const float pose[16], int chain, int32_t* host_out_rc) {
+    if (!R) return -1;
+    if (!R->have_src) return rfail(R, -2, "rgbd360_rig_set_source must be called first");
+    if (level < 0 || level >= R->p.n_pyr) return rfail(R, -3, "bad pyramid level");
+    if (chain != 0 && chain != 1) return rfail(R, -4, "chain must be 0 (error pass) or 1 (H / g pass)");
+    if (!pose || !host_out_rc) return rfail(R, -1, "null pointer");
+    hipSetDevice(R->p.device);
+    SeqEngine* E = R->E;
+    const SeqLevel& L = E->levels[level];
+    RigPoses P;
+    RigPosesRef Q;
+    rig_poses(R, pose, &P, &Q);
+    const size_t bytes = (size_t)R->S * L.n * 2 * sizeof(int32_t);
+    int32_t* d_out = nullptr;
+    hipError_t e = hipMalloc(&d_out, bytes);
+    if (e != hipSuccess) return rfail(R, -(int)e - 1000, hipGetErrorString(e));
+    const dim3 g((L.n + 255) / 256, R->S);
+    if (R->index_libm)
+        hipLaunchKernelGGL(k_rig_warp_indices<1>, g, dim3(256), 0, E->stream, L.srcRec, L.rows, L.cols, L.n, rig_level_K(R, level), P, Q, chain, d_out);
+    else
+        hipLaunchKernelGGL(k_rig_warp_indices<0>, g, dim3(256), 0, E->stream, L.srcRec, L.rows, L.cols, L.n, rig_level_K(R, level), P, Q, chain, d_out);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(host_out_rc, d_out, bytes, hipMemcpyDeviceToHost, E->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(E->stream);
+    hipFree(d_out);
+    if (e != hipSuccess) return rfail(R, -(int)e - 1000, hipGetErrorString(e));
     return 0;
 }
 

@@ -36,6 +36,7 @@ class RegisterDensePhotoICP:
         self._pose = np.eye(4, dtype=np.float32)
         self.num_iterations = []
         self.status = 0
+        self._dims = None
 
     def close(self):
         if getattr(self, "_h", None) is not None:
@@ -67,6 +68,7 @@ class RegisterDensePhotoICP:
         rp = (C.c_void_p * self.n_sensors)(*[r.ctypes.data for r in rgbs])
         dp = (C.c_void_p * self.n_sensors)(*[d.ctypes.data for d in deps])
         self._check(fn(self._h, rp, shape[1] * 3, dp, shape[1] * dtype.itemsize, 0 if dtype == np.uint16 else 1, shape[0], shape[1]))
+        self._dims = shape
 
     def setTargetFrame(self, frame1):       # frame1->frameRGBD_[s] (RegisterRGBD360.h:376)
         self._set(self._L.rgbd360_rig_set_target, frame1)
@@ -77,6 +79,31 @@ class RegisterDensePhotoICP:
     def useSaliency(self, flag: bool, thresSaliency: float = 0.01):
         """useSaliency(bool) on the per-sensor RegisterPhotoICP objects (RPI.h:266): both passes run over vSalientPixels only."""
         self._check(self._L.rgbd360_rig_use_saliency(self._h, int(bool(flag)), float(thresSaliency)))
+
+    def set_index_arithmetic(self, mode: int):
+        """rgbd360_rig_set_index_arithmetic: 0 = the device definition of the warp (default), 1 = the reference's arithmetic (both of its
+        chains: the error pass through relPoseCam, the H / g pass through Rt^-1 (T (Rt p)); no fused multiply-adds, double projection,
+        round half away from zero).  Holds for every later eval / align; may be set before or after the frames."""
+        self._check(self._L.rgbd360_rig_set_index_arithmetic(self._h, int(mode)))
+
+    def get_index_arithmetic(self) -> int:
+        return int(self._L.rgbd360_rig_get_index_arithmetic(self._h))
+
+    def warp_indices(self, level: int, pose, chain: int = 0) -> np.ndarray:
+        """rgbd360_rig_warp_indices: (row, col) of every source pixel of every sensor, shape (S, rows * cols, 2), (-1, -1) where the
+        source point is invalid or its projection invisible; chain 0 = the error pass's warp, 1 = the H / g pass's."""
+        r = self._level_dims(level)
+        out = np.empty((self.n_sensors, r[0] * r[1], 2), np.int32)
+        self._check(self._L.rgbd360_rig_warp_indices(self._h, int(level), _ptr(pose_to_cm(pose)), int(chain), _ptr(out)))
+        return out
+
+    def _level_dims(self, level: int):
+        if self._dims is None:
+            raise Rgbd360Error("rgbd360_rig_set_source must be called first")
+        r, c = self._dims
+        for _ in range(level):
+            r, c = r // 2, c // 2                  # the pyramid of csrc/sequence_engine.h
+        return r, c
 
     def eval(self, level: int, pose, method: int):
         e2, ns = np.zeros(2, np.float64), np.zeros(2, np.int64)
