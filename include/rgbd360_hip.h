@@ -150,6 +150,44 @@ int rgbd360_align360_batch_dev(rgbd360_ctx* ctx, int n_frames, const uint8_t* co
                                size_t depth_step, int depth_type, int rows, int cols, const float guess[16], int method,
                                int occlusion, int n_inflight, float* poses_out, rgbd360_result* results_out);
 
+/* ---- resident frame store: arbitrary pairs in lock step (csrc/frame_store.h) -----------------------------------------------
+ * The sequence entry above aligns CONSECUTIVE pairs from ONE guess (OdometryRGBD360.cpp:141-297).  The reference's other callers
+ * align one keyframe against many frames, or one frame against several keyframes in both roles, each pair from its own guess
+ * (OdometryKeyFrame360.cpp:244-253, KFsphere_SLAM.cpp:146-150, 370-375, 423-428, LoopClosure360.h:309-312, 348-351).  A store
+ * keeps `capacity` frames of one size in HBM in prepared form (per pyramid level the source records and both target record
+ * streams of the per-pixel pass): a frame is prepared once, when it is put, whatever number of pairs it later takes part in and
+ * in whichever role.  An align call takes (target entry, source entry, guess) triples and runs them through the lock-step
+ * schedule of the sequence engine.  Per pair, pose / status / iters / hessian are bit-identical to rgbd360_align360 on the same
+ * two frames and guess.  The store takes the context's parameters when it is created and its index arithmetic at every align
+ * call; it is destroyed BEFORE its context and used from one thread at a time.
+ * Out of scope: occlusion 1 / 2, the pinhole and rig paths, several GPUs, eviction (the caller picks the entry to overwrite),
+ * PbMap (the guess is an input). */
+typedef struct rgbd360_store rgbd360_store;
+/* capacity frames of rows x cols on ctx's device.  0; -1 bad arguments (capacity < 1, the size limits of the sequence entry);
+ * -103 out of device memory (nothing stays allocated).  The message of a failed create is the CONTEXT's last error. */
+int  rgbd360_store_create(rgbd360_ctx* ctx, int capacity, int rows, int cols, rgbd360_store** out);
+void rgbd360_store_destroy(rgbd360_store* st);
+const char* rgbd360_store_last_error(rgbd360_store* st);
+/* bytes of HBM one entry occupies (the store: capacity times that, plus the set-up scratch of at most 32 frames). */
+size_t rgbd360_store_entry_bytes(const rgbd360_store* st);
+/* Prepares n frames into the entries entry[0..n) (any order, distinct, 0 <= entry < capacity; an occupied entry is
+ * overwritten).  Images as rgbd360_set_target (on_device = 0: host images, copied before the call returns) or as
+ * rgbd360_set_target_dev (on_device = 1).  All n frames go through the fused set-up together, at most 32 per launch.
+ * 0, -1 bad arguments (nothing launched), other negatives: HIP errors (the named entries are then empty). */
+int  rgbd360_store_put(rgbd360_store* st, int n, const int* entry, const uint8_t* const* rgb, size_t rgb_step,
+                       const void* const* depth, size_t depth_step, int depth_type, int on_device);
+/* 1 occupied, 0 empty, -1 out of range. */
+int  rgbd360_store_occupied(const rgbd360_store* st, int entry);
+/* n_pairs alignments: pair k = alignFrames360 with entry trg[k] as target frame, entry src[k] as source frame and the 16 floats
+ * at guesses + 16 k (column-major; guesses == NULL: identity for all) as pose_guess.  trg[k] == src[k], repeated entries and
+ * repeated pairs are allowed.  method 0 / 1 / 2 (-4 otherwise); occlusion must be 0 (-1 otherwise); n_inflight 1..64 as in
+ * rgbd360_align360_batch: pairs run in rounds of n_inflight in list order, the result does not depend on it.  poses_out
+ * n_pairs x 16 floats, results_out (may be NULL) n_pairs records, both in list order.  n_pairs == 0 returns 0 and writes
+ * nothing.  -1 and no launch at all if any index is out of range or names an empty entry (the message names the first such
+ * pair). */
+int  rgbd360_store_align(rgbd360_store* st, int n_pairs, const int* trg, const int* src, const float* guesses, int method,
+                         int occlusion, int n_inflight, float* poses_out, rgbd360_result* results_out);
+
 /* ---- one process, several GPUs (BASELINE.json configs[3]) ---------------------------------------------------
  * The sequence path shards by independent frame pairs: device d gets the contiguous pairs rgbd360_shard_range(n_frames-1, d,
  * n_gpus) and therefore the frames lo..hi (one boundary frame is shared by two neighbours); one host thread per device drives

@@ -25,6 +25,8 @@ SYMBOLS = [
     "rgbd360_rig_eval", "rgbd360_rig_align", "rgbd360_rig_use_saliency", "rgbd360_rig_set_index_arithmetic", "rgbd360_rig_get_index_arithmetic",
     "rgbd360_rig_warp_indices", "rgbd360_debug_solve_partials",
     "rgbd360_debug_solve_state",
+    "rgbd360_store_create", "rgbd360_store_destroy", "rgbd360_store_last_error", "rgbd360_store_entry_bytes", "rgbd360_store_put",
+    "rgbd360_store_occupied", "rgbd360_store_align",
 ]
 
 
@@ -204,5 +206,15 @@ def load() -> C.CDLL:
     L.rgbd360_multi_align_resident.argtypes = [vp, f32p, i32, i32, i32, f32p, vp]
     L.rgbd360_align360_batch_multi.argtypes = [C.POINTER(Params), i32, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, f32p, i32, i32, i32,
                                                i32, vp, f32p, vp]
+    L.rgbd360_store_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
+    L.rgbd360_store_destroy.argtypes = [vp]
+    L.rgbd360_store_destroy.restype = None
+    L.rgbd360_store_last_error.argtypes = [vp]
+    L.rgbd360_store_last_error.restype = C.c_char_p
+    L.rgbd360_store_entry_bytes.argtypes = [vp]
+    L.rgbd360_store_entry_bytes.restype = C.c_size_t
+    L.rgbd360_store_put.argtypes = [vp, i32, vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32]
+    L.rgbd360_store_occupied.argtypes = [vp, i32]
+    L.rgbd360_store_align.argtypes = [vp, i32, vp, vp, f32p, i32, i32, i32, f32p, vp]
     _lib = L
     return L

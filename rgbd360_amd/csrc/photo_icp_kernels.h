@@ -814,6 +814,27 @@ __global__ __launch_bounds__(kEvalThreadsBatch) void k_eval_b(const GNState* __r
                                                    partials + (size_t)slot * (size_t)partials_stride, lv, ec);
 }
 
+// Frame store (frame_store.h): the slot's target and source frames are ENTRIES of the store, any two of them; every record stream of
+// a level is one [capacity][n] allocation.  The two entry numbers are block-uniform reads of the kernel arguments (scalar loads at
+// an SGPR offset), the pointers arithmetic in SGPRs: as in k_eval_b nothing a vector load depends on stands in front of the first
+// record loads, and the body is the same eval_block -- same work split, partial rows and summation order, same bits.  A parked slot
+// (outside the round's live mask) still issues its first two record loads before it tests the gate: the host gives it entry 0.
+struct PairTable {
+    int trg[32], src[32];
+};
+template <int METHOD, bool HG, int SRC = 0>
+__global__ __launch_bounds__(kEvalThreadsBatch) void k_eval_p(const GNState* __restrict__ states, const float4* __restrict__ src0, int n_px,
+                                                          int chunk, int level, int nb_arg, double* __restrict__ partials,
+                                                          int partials_stride, LevelDev lv, EvalConsts ec, PairTable pt) {
+    const int slot = blockIdx.y;
+    const size_t to = (size_t)pt.trg[slot] * (size_t)n_px, so = (size_t)pt.src[slot] * (size_t)n_px;
+    lv.trgP += to;
+    lv.trgD += to;
+    if (SRC == 2) lv.src2 += so;
+    eval_block<METHOD, HG, kEvalThreadsBatch, SRC>(states + slot, SRC == 0 ? src0 + so : src0, n_px, chunk, level, nb_arg,
+                                                   partials + (size_t)slot * (size_t)partials_stride, lv, ec);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // k_level_init: entering a pyramid level (RPI.h:4590-4604): it = 0, update = (1,..,1), lambda = 1, the first
 // pass is evaluated at the incoming pose.  use_pose != 0 loads `pose` (first level / stage calls).
@@ -842,6 +863,19 @@ __global__ void k_level_init_b(GNState* states, Pose16 pose, int use_pose, int r
         return;
     }
     level_init_one(st, pose, use_pose, reset_all, level);
+}
+// Frame store: as k_level_init_b with one start pose per slot, poses[slot] of a device array the host fills in front of the round.
+__global__ void k_level_init_p(GNState* states, const Pose16* __restrict__ poses, int use_pose, int reset_all, int level,
+                               unsigned long long live_mask) {
+    if (threadIdx.x != 0) return;
+    GNState* st = states + blockIdx.x;
+    if (!((live_mask >> blockIdx.x) & 1ull)) {
+        st->done = 1;
+        st->level_active = -1;
+        st->status = 0;
+        return;
+    }
+    level_init_one(st, poses[blockIdx.x], use_pose, reset_all, level);
 }
 __device__ __forceinline__ void level_init_one(GNState* st, const Pose16& pose, int use_pose, int reset_all, int level) {
     if (reset_all) {
@@ -2034,9 +2068,10 @@ __device__ __forceinline__ float rcp_ieee(float x) {
 // sign here, 2 * RN(1 / s) == RN(2 / s) (scaling by 2 is exact), so this equals gradient_rec_px's three IEEE divisions bit for bit.
 __device__ __forceinline__ float harmonic2(float a, float b) { return 2.f * rcp_ieee(rcp_ieee(a) + rcp_ieee(b)); }
 
+// Body of one workgroup.  `slot` selects the frame, the level >= 1 input planes and the next level's planes; `rec` the [rec][n] slice
+// the records go to: the slot itself in the sequence engine and the rig (k_frame_level_b), an entry of a frame store (k_frame_level_e).
 template <bool RAW>
-__global__ __launch_bounds__(256) void k_frame_level_b(FrameLevelArgs A, FramePtrs fp) {
-    const int slot = blockIdx.z;
+__device__ __forceinline__ void frame_level_body(const FrameLevelArgs& A, const FramePtrs& fp, const int slot, const int rec) {
     if (!((A.live_mask >> slot) & 1ull)) return;
     __shared__ float sg[kFsLH][kFsLW], sd[kFsLH][kFsLW];
     __shared__ uint32_t raw[RAW ? kFsLH : 1][RAW ? kFsRawDw : 1];
@@ -2141,7 +2176,7 @@ __global__ __launch_bounds__(256) void k_frame_level_b(FrameLevelArgs A, FramePt
             const bool want_src = (A.src_mask >> slot) & 1ull, want_trg = (A.trg_mask >> slot) & 1ull;
             const int ly = ty + kFsRing;
             if (want_src && A.compact_src) {       // {depth, Isrc}: validity and direction are the pass's business (src_point)
-                float2* out = reinterpret_cast<float2*>(A.src_rec) + (size_t)slot * n + (size_t)r * cols;
+                float2* out = reinterpret_cast<float2*>(A.src_rec) + (size_t)rec * n + (size_t)r * cols;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int c = c0 + tj + 16 * k;
@@ -2149,7 +2184,7 @@ __global__ __launch_bounds__(256) void k_frame_level_b(FrameLevelArgs A, FramePt
                 }
             } else if (want_src) {
                 const float sp = A.pinhole ? 0.f : A.sin_phi[r], cp = A.pinhole ? 0.f : A.cos_phi[r];
-                float4* out = A.src_rec + (size_t)slot * n + (size_t)r * cols;
+                float4* out = A.src_rec + (size_t)rec * n + (size_t)r * cols;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int c = c0 + tj + 16 * k;
@@ -2181,8 +2216,8 @@ __global__ __launch_bounds__(256) void k_frame_level_b(FrameLevelArgs A, FramePt
                 }
             }
             if (want_trg) {
-                F3* recP = A.trg_p + (size_t)slot * n + (size_t)r * cols;
-                F3* recD = A.trg_d + (size_t)slot * n + (size_t)r * cols;
+                F3* recP = A.trg_p + (size_t)rec * n + (size_t)r * cols;
+                F3* recD = A.trg_d + (size_t)rec * n + (size_t)r * cols;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int c = c0 + tj + 16 * k;
@@ -2248,6 +2283,20 @@ __global__ __launch_bounds__(256) void k_frame_level_b(FrameLevelArgs A, FramePt
             A.depth_next[(size_t)slot * dn + (size_t)y * A.dcols + x] = cnt > 0 ? av / cnt : 0.f;
         }
     }
+}
+
+template <bool RAW>
+__global__ __launch_bounds__(256) void k_frame_level_b(FrameLevelArgs A, FramePtrs fp) {
+    frame_level_body<RAW>(A, fp, blockIdx.z, blockIdx.z);
+}
+// Frame store (frame_store.h): the frame of slot s becomes entry et.e[s] of the store.  A.src_rec / trg_p / trg_d are the store's
+// [capacity][n] arrays (the host has checked every entry of a live slot against the capacity), the planes stay [slot][n] scratch.
+struct EntryTable {
+    int e[kMaxSlots];
+};
+template <bool RAW>
+__global__ __launch_bounds__(256) void k_frame_level_e(FrameLevelArgs A, FramePtrs fp, EntryTable et) {
+    frame_level_body<RAW>(A, fp, blockIdx.z, et.e[blockIdx.z]);
 }
 
 

@@ -28,6 +28,19 @@ struct SeqLevel {
     int nblocks = 0, chunk = 0;
 };
 
+// Frame-store mode of an engine (frame_store.h): the records of a level are not the engine's [P][n] slot buffers but the store's
+// [capacity][n] entry arrays, and slot s of a round aligns entry pt.trg[s] (target) with entry pt.src[s] (source) from its own guess.
+struct StoreLevelView {
+    float4* src = nullptr;                // [capacity][n] source records (16 B, or 8 B on a compact level)
+    F3 *trgP = nullptr, *trgD = nullptr;  // [capacity][n]
+};
+struct StoreView {
+    std::vector<StoreLevelView> levels;
+    PairTable pt;                         // the pairs of the round in flight (parked slots: entry 0)
+    Pose16* d_guess = nullptr;            // [P] start poses of the round, filled by one async copy in front of it ...
+    Pose16* h_guess = nullptr;            // ... from this pinned array
+};
+
 struct SeqEngine {
     rgbd360_params p;
     int P = 0, rows = 0, cols = 0;
@@ -44,6 +57,7 @@ struct SeqEngine {
     int max_eval_blocks = 256;
     int libm = 0;                 // the warp in the reference's libm arithmetic (the owning context's rgbd360_set_index_arithmetic)
     int chunk_top = 8, chunk_mid = 4, chunk_l0 = 4;      // {pass, solve} pairs enqueued ahead per level and visit
+    StoreView* sv = nullptr;          // frame-store mode (owned by the store, not by the engine)
     std::string err;
 };
 
@@ -79,7 +93,11 @@ void seq_free(SeqEngine* E) {
 }
 
 // Geometry, tables and work split exactly as ensure_levels() builds them for a one-pair context.
-int seq_create(const rgbd360_params& p, int P, int rows, int cols, int max_eval_blocks, SeqEngine** out, std::string* err) {
+// alloc: kSeqPlanes = the [P][n] float planes of levels >= 1, kSeqRecords = the [P][n] record buffers.  A frame store's engines
+// leave out what the store holds per entry (frame_store.h).
+enum { kSeqPlanes = 1, kSeqRecords = 2 };
+int seq_create(const rgbd360_params& p, int P, int rows, int cols, int max_eval_blocks, SeqEngine** out, std::string* err,
+               int alloc = kSeqPlanes | kSeqRecords) {
     *out = nullptr;
     if (P < 1 || P > kMaxSlots) { *err = "slots per engine must be in 1..32"; return -1; }
     if (rows < 2 || cols < 8) { *err = "image too small"; return -1; }
@@ -116,9 +134,10 @@ int seq_create(const rgbd360_params& p, int P, int rows, int cols, int max_eval_
         L.half_nRows = 0.5 * r - 0.5;               // RPI.h:2557
         const size_t np = (size_t)P * L.n;
         bool ok = true;
-        if (l > 0) ok = ok && hipMalloc(&L.gray, np * sizeof(float)) == hipSuccess && hipMalloc(&L.depth, np * sizeof(float)) == hipSuccess;
-        ok = ok && hipMalloc(&L.srcRec, np * sizeof(float4)) == hipSuccess;
-        for (int k = 0; k < 2; ++k)
+        if (l > 0 && (alloc & kSeqPlanes))
+            ok = ok && hipMalloc(&L.gray, np * sizeof(float)) == hipSuccess && hipMalloc(&L.depth, np * sizeof(float)) == hipSuccess;
+        if (alloc & kSeqRecords) ok = ok && hipMalloc(&L.srcRec, np * sizeof(float4)) == hipSuccess;
+        for (int k = 0; k < 2 && (alloc & kSeqRecords); ++k)
             ok = ok && hipMalloc(&L.trgP[k], np * sizeof(F3)) == hipSuccess && hipMalloc(&L.trgD[k], np * sizeof(F3)) == hipSuccess;
         ok = ok && hipMalloc(&L.sinT, c * sizeof(float)) == hipSuccess && hipMalloc(&L.cosT, c * sizeof(float)) == hipSuccess &&
              hipMalloc(&L.sinP, r * sizeof(float)) == hipSuccess && hipMalloc(&L.cosP, r * sizeof(float)) == hipSuccess;
@@ -188,7 +207,19 @@ void seq_launch_eval(SeqEngine* E, int level, int method) {
     lv.libm = E->libm;
     const EvalConsts ec = eval_consts(E->p);
     const dim3 g(L.nblocks, E->P), b(kEvalThreadsBatch);
-#define LAUNCHB(M, S) hipLaunchKernelGGL((k_eval_b<M, true, S>), g, b, 0, E->stream, E->d_states, lv.src, lv.n, L.chunk, level, L.nblocks, E->d_partials, E->partials_stride, lv, ec)
+    if (E->sv) {
+        const StoreLevelView& V = E->sv->levels[level];
+        lv.src = V.src; lv.src2 = reinterpret_cast<const float2*>(V.src); lv.trgP = V.trgP; lv.trgD = V.trgD;
+    }
+#define LAUNCHB(M, S)                                                                                                                          \
+    do {                                                                                                                                       \
+        if (E->sv)                                                                                                                             \
+            hipLaunchKernelGGL((k_eval_p<M, true, S>), g, b, 0, E->stream, E->d_states, lv.src, lv.n, L.chunk, level, L.nblocks, E->d_partials, \
+                               E->partials_stride, lv, ec, E->sv->pt);                                                                         \
+        else                                                                                                                                   \
+            hipLaunchKernelGGL((k_eval_b<M, true, S>), g, b, 0, E->stream, E->d_states, lv.src, lv.n, L.chunk, level, L.nblocks, E->d_partials, \
+                               E->partials_stride, lv, ec);                                                                                    \
+    } while (0)
     if (L.compact) {
         if (method == 0) LAUNCHB(0, 2);
         else if (method == 1) LAUNCHB(1, 2);
@@ -210,13 +241,18 @@ void seq_launch_solve(SeqEngine* E, int level, int forced = 0) {
     hipLaunchKernelGGL(k_solve_b, dim3(E->P), dim3(kSolveThreads), 0, E->stream, E->d_states, E->d_partials, E->partials_stride, L.nblocks, cfg);
 }
 
+// guess: the start pose of every slot; a frame-store engine takes one pose per slot from sv->d_guess instead.
 void seq_enqueue_schedule(SeqEngine* E, int pending, bool pending_started, const float* guess, int method, unsigned long long live) {
     const int top = E->p.n_pyr - 1;
     for (int level = pending; level >= 0; --level) {
         if (level == top && !pending_started) {
-            Pose16 Pz;
-            memcpy(Pz.v, guess, sizeof(Pz.v));
-            hipLaunchKernelGGL(k_level_init_b, dim3(E->P), dim3(64), 0, E->stream, E->d_states, Pz, 1, 1, level, live);
+            if (E->sv) {
+                hipLaunchKernelGGL(k_level_init_p, dim3(E->P), dim3(64), 0, E->stream, E->d_states, E->sv->d_guess, 1, 1, level, live);
+            } else {
+                Pose16 Pz;
+                memcpy(Pz.v, guess, sizeof(Pz.v));
+                hipLaunchKernelGGL(k_level_init_b, dim3(E->P), dim3(64), 0, E->stream, E->d_states, Pz, 1, 1, level, live);
+            }
         }
         const int n_pairs = (level == top && !pending_started) ? E->chunk_top : (level == 0 ? E->chunk_l0 : E->chunk_mid);
         for (int k = 0; k < n_pairs; ++k) {
@@ -228,8 +264,10 @@ void seq_enqueue_schedule(SeqEngine* E, int pending, bool pending_started, const
 
 // One frame per live slot through the fused set-up (k_frame_level_b, one launch per pyramid level): source records for the slots
 // of src_mask, target records (into buffer trg_buf) for those of trg_mask, next-level planes for all.
+// store / et (frame store): the records of slot s go to entry et->e[s] of the store's arrays instead (k_frame_level_e).
 void seq_frame_setup(SeqEngine* E, const FramePtrs& fp, size_t rgb_step, size_t depth_step, int depth_type, unsigned long long live,
-                     unsigned long long src_mask, unsigned long long trg_mask, int trg_buf) {
+                     unsigned long long src_mask, unsigned long long trg_mask, int trg_buf, const StoreView* store = nullptr,
+                     const EntryTable* et = nullptr) {
     for (int l = 0; l < E->p.n_pyr; ++l) {
         const SeqLevel& L = E->levels[l];
         FrameLevelArgs A;
@@ -245,12 +283,16 @@ void seq_frame_setup(SeqEngine* E, const FramePtrs& fp, size_t rgb_step, size_t 
         A.rgb_step = rgb_step; A.depth_step = depth_step;
         A.gray_in = L.gray; A.depth_in = L.depth;
         A.src_rec = L.srcRec; A.trg_p = L.trgP[trg_buf]; A.trg_d = L.trgD[trg_buf];
+        if (store) { A.src_rec = store->levels[l].src; A.trg_p = store->levels[l].trgP; A.trg_d = store->levels[l].trgD; }
         A.sin_theta = L.sinT; A.cos_theta = L.cosT; A.sin_phi = L.sinP; A.cos_phi = L.cosP;
         A.min_depth = E->p.min_depth; A.max_depth = E->p.max_depth;
         A.compact_src = L.compact ? 1 : 0;
         A.live_mask = live; A.src_mask = src_mask; A.trg_mask = trg_mask;
         const dim3 g((L.cols + kFsTW - 1) / kFsTW, (L.rows + kFsTH - 1) / kFsTH, E->P);
-        if (l == 0) hipLaunchKernelGGL((k_frame_level_b<true>), g, dim3(256), 0, E->stream, A, fp);
+        if (store) {
+            if (l == 0) hipLaunchKernelGGL((k_frame_level_e<true>), g, dim3(256), 0, E->stream, A, fp, *et);
+            else hipLaunchKernelGGL((k_frame_level_e<false>), g, dim3(256), 0, E->stream, A, fp, *et);
+        } else if (l == 0) hipLaunchKernelGGL((k_frame_level_b<true>), g, dim3(256), 0, E->stream, A, fp);
         else hipLaunchKernelGGL((k_frame_level_b<false>), g, dim3(256), 0, E->stream, A, fp);
     }
 }
@@ -293,6 +335,27 @@ void result_from_state(const GNState& S, int n_pyr, int occ, float pose_out[16],
     R.rms_photo = S.acc_np > 0 ? sqrt(S.acc_e2p / (double)S.acc_np) : 0.0;
     R.rms_depth = S.acc_nd > 0 ? sqrt(S.acc_e2d / (double)S.acc_nd) : 0.0;
     if (res) *res = R;
+}
+
+// Waits for the round whose first schedule is enqueued: reads the slots' states back (E->h_states holds them on return) and tops the
+// schedule up until every live slot has finished its finest level or carries a status.
+int seq_finish_round(SeqEngine* E, int n_slots, const float* guess, int method, unsigned long long live) {
+    for (int round = 0;; ++round) {
+        SEQC(E, hipMemcpyAsync(E->h_states, E->d_states, (size_t)n_slots * sizeof(GNState), hipMemcpyDeviceToHost, E->stream));
+        SEQC(E, hipStreamSynchronize(E->stream));
+        int pending = -1;
+        for (int s = 0; s < n_slots; ++s) {
+            if (!((live >> s) & 1ull)) continue;
+            const GNState& S = E->h_states[s];
+            if (S.status != 0 || (S.level_active == 0 && S.done)) continue;
+            if (S.done) { E->err = "alignment schedule stalled between levels"; return -6; }
+            pending = std::max(pending, S.level_active);
+        }
+        if (pending < 0) return 0;
+        if (round > (E->p.max_iters + 4) * E->p.n_pyr) { E->err = "alignment loop did not terminate"; return -6; }
+        seq_enqueue_schedule(E, pending, true, guess, method, live);      // the stalled level gets another chunk, then the finer ones
+        SEQC(E, hipGetLastError());
+    }
 }
 
 // Slot s aligns the pairs [a[s], b[s]) of the sequence rgb[] / depth[] (global frame indices; pair j = frames j, j+1).
@@ -380,22 +443,7 @@ int seq_run_body(SeqEngine* E, int n_slots, const int* a, const int* b, const ui
         // next round's sources travel while this round is being aligned (a pageable-memory copy keeps the host in the call, so
         // it is issued only now that the round's launches are queued)
         if (!on_device && r + 1 < rounds && (rc = upload(r + 1, 1, par, live_of(r + 1))) != 0) return rc;
-        for (int round = 0;; ++round) {
-            SEQC(E, hipMemcpyAsync(E->h_states, E->d_states, (size_t)n_slots * sizeof(GNState), hipMemcpyDeviceToHost, E->stream));
-            SEQC(E, hipStreamSynchronize(E->stream));
-            int pending = -1;
-            for (int s = 0; s < n_slots; ++s) {
-                if (!((live >> s) & 1ull)) continue;
-                const GNState& S = E->h_states[s];
-                if (S.status != 0 || (S.level_active == 0 && S.done)) continue;
-                if (S.done) { E->err = "alignment schedule stalled between levels"; return -6; }
-                pending = std::max(pending, S.level_active);
-            }
-            if (pending < 0) break;
-            if (round > (E->p.max_iters + 4) * E->p.n_pyr) { E->err = "alignment loop did not terminate"; return -6; }
-            seq_enqueue_schedule(E, pending, true, guess, method, live);      // the stalled level gets another chunk, then the finer ones
-            SEQC(E, hipGetLastError());
-        }
+        if ((rc = seq_finish_round(E, n_slots, guess, method, live)) != 0) return rc;
         for (int s = 0; s < n_slots; ++s) {
             if (!((live >> s) & 1ull)) continue;
             const int j = a[s] + r;
