@@ -88,7 +88,6 @@ int store_ensure_engines(rgbd360_store* st, int n_eng, int P) {
 // The pairs [lo, hi) of the list on one engine, n_slots per round in list order; the last round is partial under the live mask.
 int store_run_engine(SeqEngine* E, int n_slots, int lo, int hi, const int* trg, const int* src, const float* guesses, int method,
                      float* poses_out, rgbd360_result* results_out) {
-    static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     hipSetDevice(E->p.device);
     StoreView& V = *E->sv;
     for (int k = lo; k < hi; k += n_slots) {
@@ -99,7 +98,7 @@ int store_run_engine(SeqEngine* E, int n_slots, int lo, int hi, const int* trg, 
             V.pt.src[s] = s < m ? src[k + s] : 0;
         }
         // the previous round ended with a synchronisation of this stream: its copy of h_guess has landed
-        for (int s = 0; s < m; ++s) memcpy(V.h_guess[s].v, guesses ? guesses + (size_t)16 * (k + s) : kIdentity, sizeof(Pose16));
+        for (int s = 0; s < m; ++s) memcpy(V.h_guess[s].v, guesses ? guesses + (size_t)16 * (k + s) : kIdentityPose, sizeof(Pose16));
         SEQC(E, hipMemcpyAsync(V.d_guess, V.h_guess, (size_t)m * sizeof(Pose16), hipMemcpyHostToDevice, E->stream));
         seq_enqueue_schedule(E, E->p.n_pyr - 1, false, nullptr, method, live);
         SEQC(E, hipGetLastError());
@@ -200,10 +199,8 @@ int rgbd360_store_put(rgbd360_store* st, int n, const int* entry, const uint8_t*
                 } else {      // stream-ordered behind the set-up launches that read the staging before
                     fp.rgb[s] = E->stage_rgb[0] + (size_t)s * E->stage_rgb_frame;
                     fp.depth[s] = E->stage_depth[0] + (size_t)s * E->stage_depth_frame;
-                    SEQC(E, hipMemcpy2DAsync((void*)fp.rgb[s], (size_t)st->cols * 3, rgb[k + s], rgb_step, (size_t)st->cols * 3, st->rows,
-                                             hipMemcpyHostToDevice, E->stream));
-                    SEQC(E, hipMemcpy2DAsync((void*)fp.depth[s], (size_t)st->cols * dpx, depth[k + s], depth_step, (size_t)st->cols * dpx, st->rows,
-                                             hipMemcpyHostToDevice, E->stream));
+                    SEQC(E, copy_frame_h2d((uint8_t*)fp.rgb[s], (void*)fp.depth[s], rgb[k + s], rgb_step, depth[k + s], depth_step, depth_type, st->rows,
+                                           st->cols, E->stream));
                 }
             }
             seq_frame_setup(E, fp, on_device ? rgb_step : (size_t)st->cols * 3, on_device ? depth_step : (size_t)st->cols * dpx, depth_type, live, live,
@@ -259,20 +256,7 @@ int rgbd360_store_align(rgbd360_store* st, int n_pairs, const int* trg, const in
         rcs[e] = store_run_engine(st->eng[e], cnt[e], lo[e], hi[e], trg, src, guesses, method, poses_out, results_out);
         if (rcs[e]) (void)hipStreamSynchronize(st->eng[e]->stream);
     };
-    {
-        std::vector<std::thread> workers;
-        bool inline_second = false;
-        if (n_eng == 2) {
-            try {
-                workers.emplace_back(run_engine, 1);
-            } catch (const std::exception&) {        // no exception may cross the C boundary
-                inline_second = true;
-            }
-        }
-        run_engine(0);
-        if (inline_second) run_engine(1);
-        for (std::thread& w : workers) w.join();
-    }
+    run_on_threads(n_eng, run_engine);
     for (int e = 0; e < n_eng; ++e)
         if (rcs[e]) return store_fail(st, rcs[e], st->eng[e]->err);
     return 0;

@@ -275,4 +275,27 @@ GN_HD inline int step(const float* H, const float* g, float lambda, const float*
     return 0;
 }
 
+// The Levenberg-Marquardt step of the host-driven paths (pinhole RPI.h:4355-4358, 4389-4391; rig RegisterRGBD360.h:452-455):
+// update = -(H + lambda diag H)^-1 g, pose_tmp = exp(update) * pose with the full exponential.  lambda < 0: no damping (the
+// pinhole driver's first, Gauss-Newton, trip).  false: the matrix has no inverse.
+GN_HD inline bool lm_update(const float* H, const float* g, float lambda, const float* pose, float* pose_tmp, float* update) {
+    float M[36], inv[36];
+    for (int k = 0; k < 36; ++k) M[k] = H[k];
+    if (lambda >= 0.f)
+        for (int i = 0; i < 6; ++i) M[i * 6 + i] = H[i * 6 + i] + lambda * H[i * 6 + i];
+    if (!inverse6(M, inv)) return false;
+    for (int r = 0; r < 6; ++r) {
+        float s = 0.f;
+        for (int c = 0; c < 6; ++c) s += (-inv[c * 6 + r]) * g[c];
+        update[r] = s;
+    }
+    double ud[6], E[16];
+    for (int i = 0; i < 6; ++i) ud[i] = (double)update[i];
+    se3_exp(ud, E);
+    float Ef[16];
+    for (int k = 0; k < 16; ++k) Ef[k] = (float)E[k];
+    mat4_mul(Ef, pose, pose_tmp);
+    return true;
+}
+
 }  // namespace gn

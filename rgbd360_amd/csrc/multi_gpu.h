@@ -37,12 +37,6 @@ int mfail(rgbd360_multi* m, int code, const std::string& msg) {
     return code;
 }
 
-void shard_range(int n_items, int rank, int world, int* lo, int* hi) {      // contiguous, balanced: the first n % world ranks get one more
-    const int base = n_items / world, extra = n_items % world;
-    *lo = rank * base + std::min(rank, extra);
-    *hi = *lo + base + (rank < extra ? 1 : 0);
-}
-
 // The exchange buffer's layout (pure index arithmetic, exported as rgbd360_gather_slot for the CPU tests): every rank contributes
 // max_chunk = ceil(n_pairs / world) rows -- ncclAllGather wants equal counts -- of which the first hi - lo are its pairs; global pair
 // j therefore sits in row rank_of(j) * max_chunk + (j - lo_rank) of the gathered table, and the rows behind a rank's last pair are
@@ -109,20 +103,7 @@ int multi_run(rgbd360_multi* m, int n_frames, FrameOf frames_of, size_t rgb_step
             memcpy(row + 16 * sizeof(float), &res[j], sizeof(rgbd360_result));
         }
     };
-    {
-        std::vector<std::thread> workers;
-        std::vector<int> inline_devs;
-        for (int d = 1; d < G; ++d) {
-            try {
-                workers.emplace_back(run_device, d);
-            } catch (const std::exception&) {
-                inline_devs.push_back(d);
-            }
-        }
-        run_device(0);
-        for (int d : inline_devs) run_device(d);
-        for (std::thread& w : workers) w.join();
-    }
+    run_on_threads(G, run_device);
     for (int d = 0; d < G; ++d)
         if (rcs[d]) return mfail(m, rcs[d], std::string("device ") + std::to_string(m->dev[d]) + ": " + m->ctx[d]->err);
 

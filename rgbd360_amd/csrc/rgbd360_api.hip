@@ -15,10 +15,12 @@
 #include <exception>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 
 #include <memory>
+#include <new>
 
 #include "../../include/rgbd360_hip.h"
 #include "../../include/rgbd360_hip_diag.h"
@@ -31,26 +33,60 @@
 
 using namespace r360;
 
+#include "level_geom.h"
+
 namespace {
 
-struct Level {
-    int rows = 0, cols = 0, n = 0;
-    float half_nRows = 0.f, angle_res_inv = 0.f;
+struct Level : LevelGeom {
     float *graySrc = nullptr, *depthSrc = nullptr, *grayTrg = nullptr, *depthTrg = nullptr;
     float4* srcRec = nullptr;
     float4* srcRecPin = nullptr;     // pinhole LUT record of the source (built per alignment, RPI.h:4277-4300)
     F3 *trgP = nullptr, *trgD = nullptr;
     float *sinT = nullptr, *cosT = nullptr, *sinP = nullptr, *cosP = nullptr;
     float2 *tabT = nullptr, *tabP = nullptr;      // the same values interleaved {sin, cos}: one 8-byte load per pixel in the recompute form of the pass
-    int nblocks = 0, chunk = 0;
     int libm = 0;                    // rgbd360_set_index_arithmetic: the warp in the reference's libm arithmetic
 };
 
-}  // namespace
+const float kIdentityPose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
-namespace {
-struct SeqEngine;      // sequence_engine.h
+// contiguous, balanced spans of n_items over `world` ranks: the first n_items % world ranks get one more
+void shard_range(int n_items, int rank, int world, int* lo, int* hi) {
+    const int base = n_items / world, extra = n_items % world;
+    *lo = rank * base + std::min(rank, extra);
+    *hi = *lo + base + (rank < extra ? 1 : 0);
 }
+
+// job(0) .. job(n - 1) side by side: jobs 1 .. n-1 on a host thread each, job 0 -- and every job whose thread could not be started --
+// on the caller's thread; returns when all have ended.  Never throws: no exception may cross the C boundary, so a job reports through
+// what it captures (one return code per job; the callers take the first that is set).
+template <class F>
+void run_on_threads(int n, F job) {
+    std::unique_ptr<std::thread[]> workers(n > 1 ? new (std::nothrow) std::thread[n - 1] : nullptr);
+    for (int k = 1; k < n && workers; ++k) {
+        try {
+            workers[k - 1] = std::thread(job, k);
+        } catch (const std::exception&) {      // left unstarted (not joinable)
+        }
+    }
+    if (n > 0) job(0);
+    for (int k = 1; k < n; ++k)
+        if (!workers || !workers[k - 1].joinable()) job(k);
+    for (int k = 1; k < n && workers; ++k)
+        if (workers[k - 1].joinable()) workers[k - 1].join();
+}
+
+// one host frame (rows x cols, rgb8 + depth of depth_type) into packed device staging
+hipError_t copy_frame_h2d(uint8_t* dst_rgb, void* dst_depth, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step,
+                          int depth_type, int rows, int cols, hipStream_t stream) {
+    const size_t dpx = depth_type == 0 ? 2 : 4;
+    const hipError_t e = hipMemcpy2DAsync(dst_rgb, (size_t)cols * 3, rgb, rgb_step, (size_t)cols * 3, rows, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return e;
+    return hipMemcpy2DAsync(dst_depth, (size_t)cols * dpx, depth, depth_step, (size_t)cols * dpx, rows, hipMemcpyHostToDevice, stream);
+}
+
+struct SeqEngine;      // sequence_engine.h
+
+}  // namespace
 
 struct rgbd360_ctx {
     rgbd360_params p;
@@ -149,11 +185,7 @@ void free_levels(rgbd360_ctx* ctx) {
 
 int ensure_levels(rgbd360_ctx* ctx, int rows, int cols) {
     if (ctx->rows == rows && ctx->cols == cols && !ctx->levels.empty()) return 0;
-    if (rows < 2 || cols < 8) return fail(ctx, -1, "image too small");
-    if ((rows >> (ctx->p.n_pyr - 1)) < 2 || (cols >> (ctx->p.n_pyr - 1)) < 8)
-        return fail(ctx, -1, "too many pyramid levels for this image size (coarsest level must be >= 2 x 8)");
-    if ((long long)rows * cols >= (1ll << 24) || rows >= (1 << 15) || cols >= (1 << 15))
-        return fail(ctx, -1, "image too large (the fused pass uses 24-bit index arithmetic: < 16 Mpx)");
+    if (const char* why = check_image_size(ctx->p, rows, cols)) return fail(ctx, -1, why);
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     free_levels(ctx);
     ctx->levels.resize(ctx->p.n_pyr);
@@ -172,10 +204,7 @@ int ensure_levels(rgbd360_ctx* ctx, int rows, int cols) {
     int max_blocks = 0;
     for (int l = 0; l < ctx->p.n_pyr; ++l) {
         Level& L = ctx->levels[l];
-        L.rows = r; L.cols = c; L.n = r * c;
-        const float angle_res = 2 * kPI / c;        // RPI.h:2554
-        L.angle_res_inv = 1 / angle_res;            // RPI.h:2555
-        L.half_nRows = 0.5 * r - 0.5;               // RPI.h:2557
+        static_cast<LevelGeom&>(L) = level_geom(r, c, ctx->max_eval_blocks);
         // every buffer of every level out of ONE allocation (sized below on the first level's visit): a context is ~110 MB at
         // 2048 x 1024, and one large range keeps its pages' translations together (fewer, larger fragments) instead of scattering
         // ~45 small allocations over the address space
@@ -195,34 +224,7 @@ int ensure_levels(rgbd360_ctx* ctx, int rows, int cols) {
         if (!L.tabT || !L.tabP) return fail(ctx, -103, "cannot allocate the pyramid levels");
         if (!L.graySrc || !L.depthSrc || !L.grayTrg || !L.depthTrg || !L.srcRec || !L.trgP || !L.trgD || !L.sinT || !L.cosT || !L.sinP || !L.cosP)
             return fail(ctx, -103, "cannot allocate the pyramid levels");
-        // RPI.h:4556-4571: per-column / per-row sin, cos of float arguments (host libm, once per size)
-        std::vector<float> st(c), ct(c), sp(r), cp(r);
-        for (int j = 0; j < c; ++j) {
-            float theta = j * angle_res;
-            st[j] = sinf(theta);
-            ct[j] = cosf(theta);
-        }
-        for (int i = 0; i < r; ++i) {
-            float phi = (L.half_nRows - i) * angle_res;
-            sp[i] = sinf(phi);
-            cp[i] = cosf(phi);
-        }
-        HIPC(ctx, hipMemcpy(L.sinT, st.data(), c * sizeof(float), hipMemcpyHostToDevice));
-        HIPC(ctx, hipMemcpy(L.cosT, ct.data(), c * sizeof(float), hipMemcpyHostToDevice));
-        HIPC(ctx, hipMemcpy(L.sinP, sp.data(), r * sizeof(float), hipMemcpyHostToDevice));
-        HIPC(ctx, hipMemcpy(L.cosP, cp.data(), r * sizeof(float), hipMemcpyHostToDevice));
-        {
-            std::vector<float2> tt(c), tp(r);
-            for (int j = 0; j < c; ++j) tt[j] = make_float2(st[j], ct[j]);
-            for (int i = 0; i < r; ++i) tp[i] = make_float2(sp[i], cp[i]);
-            HIPC(ctx, hipMemcpy(L.tabT, tt.data(), c * sizeof(float2), hipMemcpyHostToDevice));
-            HIPC(ctx, hipMemcpy(L.tabP, tp.data(), r * sizeof(float2), hipMemcpyHostToDevice));
-        }
-        // work split of the fused pass: <= max_eval_blocks blocks, contiguous spans that are multiples of 256 pixels
-        int chunk = (L.n + ctx->max_eval_blocks - 1) / ctx->max_eval_blocks;
-        chunk = ((chunk + kEvalThreads - 1) / kEvalThreads) * kEvalThreads;
-        L.chunk = chunk;
-        L.nblocks = (L.n + chunk - 1) / chunk;
+        HIPC(ctx, upload_angle_tables(angle_tables(L), L.sinT, L.cosT, L.sinP, L.cosP, L.tabT, L.tabP));
         L.libm = ctx->index_libm;
         if (L.nblocks > max_blocks) max_blocks = L.nblocks;
         r /= 2; c /= 2;
@@ -242,9 +244,7 @@ int ensure_levels(rgbd360_ctx* ctx, int rows, int cols) {
 
 LevelDev level_dev(const Level& L) {
     LevelDev d;
-    d.rows = L.rows; d.cols = L.cols; d.n = L.n;
-    d.half_nRows = L.half_nRows; d.angle_res_inv = L.angle_res_inv;
-    d.pi_k = (float)(kPI * (double)L.angle_res_inv);
+    fill_level_dev(d, L);
     d.src = L.srcRec; d.trgP = L.trgP; d.trgD = L.trgD;
     d.depth_src = L.depthSrc; d.gray_src = L.graySrc; d.tabT = L.tabT; d.tabP = L.tabP;
     d.libm = L.libm;
@@ -287,6 +287,52 @@ int occ_ensure(rgbd360_ctx* ctx) {
     return 0;
 }
 
+// Runtime selector -> template parameter: f is called once, with a std::integral_constant of the selected value, so that each branch
+// is a plain launch of its own instantiation.  with_method: METHOD 0 / 1 / 2 (validated by the callers; anything else runs as 2).
+// with_choice<A, B>: a two-way parameter (source form, occlusion mode, index arithmetic) -- B if `second`, else A.
+template <class F>
+void with_method(int method, F&& f) {
+    if (method == 0) f(std::integral_constant<int, 0>{});
+    else if (method == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 2>{});
+}
+template <int A, int B, class F>
+void with_choice(bool second, F&& f) {
+    if (second) f(std::integral_constant<int, B>{});
+    else f(std::integral_constant<int, A>{});
+}
+
+// The head entries of the occlusion lists carry their pass's generation (1..kOccGenMax) in their top byte: one memset per kOccGenMax
+// passes instead of one per pass.  Returns the generation of the pass about to be enqueued.
+int occ_next_gen(rgbd360_ctx* ctx) {
+    if (++ctx->occ_gen > kOccGenMax) {
+        hipMemsetAsync(ctx->occ_head, 0, ctx->occ_n * sizeof(int), ctx->stream);
+        ctx->occ_gen = 1;
+    }
+    return ctx->occ_gen;
+}
+
+FsInit fs_init(const float* init_pose) {
+    FsInit init;
+    init.on = init_pose ? 1 : 0;
+    if (init_pose) memcpy(init.pose.v, init_pose, sizeof(init.pose.v));
+    else memset(init.pose.v, 0, sizeof(init.pose.v));
+    return init;
+}
+
+// the occlusion-aware pass over the run lists of generation `gen`, gate and pose from `st`
+void launch_eval_occ(rgbd360_ctx* ctx, int level, int method, int occ, const LevelDev& lv, const EvalConsts& ec, const GNState* st,
+                     double* partials, int gen) {
+    const Level& L = ctx->levels[level];
+    const dim3 g(L.nblocks), b(kEvalThreads);
+    with_choice<1, 2>(occ != 1, [&](auto O) {
+        with_method(method, [&](auto M) {
+            hipLaunchKernelGGL((k_eval_occ<M, O>), g, b, 0, ctx->stream, lv, ec, st, partials, L.chunk, level, gen, ctx->occ_head,
+                               (const int4*)ctx->occ_nodes, (const unsigned char*)ctx->occ_runinfo);
+        });
+    });
+}
+
 void launch_eval(rgbd360_ctx* ctx, int level, int method, bool hg, int occ = 0) {
     const Level& L = ctx->levels[level];
     LevelDev lv = level_dev(L);
@@ -294,47 +340,21 @@ void launch_eval(rgbd360_ctx* ctx, int level, int method, bool hg, int occ = 0) 
     const EvalConsts ec = eval_consts(ctx->p);
     dim3 g(L.nblocks), b(kEvalThreads);
     if (occ != 0) {
-        // per-target lists of candidate RUNS at the pose under evaluation, then the occlusion-aware fused pass, which decides per pixel.
-        // The head entries carry the pass's generation (1..127) in their top byte: one memset per 127 passes instead of one per pass.
-        if (++ctx->occ_gen > kOccGenMax) {
-            hipMemsetAsync(ctx->occ_head, 0, ctx->occ_n * sizeof(int), ctx->stream);
-            ctx->occ_gen = 1;
-        }
-        const int gen = ctx->occ_gen;
+        // per-target lists of candidate RUNS at the pose under evaluation, then the occlusion-aware fused pass, which decides per pixel
+        const int gen = occ_next_gen(ctx);
         const dim3 gb((L.n + 255) / 256), bb(256);
-        if (occ == 1) hipLaunchKernelGGL((k_occ_build<1>), gb, bb, 0, ctx->stream, lv, ctx->d_state, level, gen, ctx->occ_head, ctx->occ_nodes, ctx->occ_runinfo);
-        else hipLaunchKernelGGL((k_occ_build<2>), gb, bb, 0, ctx->stream, lv, ctx->d_state, level, gen, ctx->occ_head, ctx->occ_nodes, ctx->occ_runinfo);
-#define LAUNCH_OCC(M, O) hipLaunchKernelGGL((k_eval_occ<M, O>), g, b, 0, ctx->stream, lv, ec, ctx->d_state, ctx->d_partials, L.chunk, level, gen, ctx->occ_head, (const int4*)ctx->occ_nodes, (const unsigned char*)ctx->occ_runinfo)
-        if (occ == 1) {
-            if (method == 0) LAUNCH_OCC(0, 1);
-            else if (method == 1) LAUNCH_OCC(1, 1);
-            else LAUNCH_OCC(2, 1);
-        } else {
-            if (method == 0) LAUNCH_OCC(0, 2);
-            else if (method == 1) LAUNCH_OCC(1, 2);
-            else LAUNCH_OCC(2, 2);
-        }
-#undef LAUNCH_OCC
+        with_choice<1, 2>(occ != 1, [&](auto O) {
+            hipLaunchKernelGGL((k_occ_build<O>), gb, bb, 0, ctx->stream, lv, ctx->d_state, level, gen, ctx->occ_head, ctx->occ_nodes, ctx->occ_runinfo);
+        });
+        launch_eval_occ(ctx, level, method, occ, lv, ec, ctx->d_state, ctx->d_partials, gen);
         return;
     }
-#define LAUNCH(M, HG, S) hipLaunchKernelGGL((k_eval<M, HG, S>), g, b, 0, ctx->stream, ctx->d_state, lv.src, lv.n, L.chunk, level, L.nblocks, ctx->d_partials, lv, ec)
-    const bool rc = L.n >= recompute_min_px();
-    if (hg) {
-        if (rc) {
-            if (method == 0) LAUNCH(0, true, 1);
-            else if (method == 1) LAUNCH(1, true, 1);
-            else LAUNCH(2, true, 1);
-        } else {
-            if (method == 0) LAUNCH(0, true, 0);
-            else if (method == 1) LAUNCH(1, true, 0);
-            else LAUNCH(2, true, 0);
-        }
-    } else {
-        if (method == 0) LAUNCH(0, false, 0);
-        else if (method == 1) LAUNCH(1, false, 0);
-        else LAUNCH(2, false, 0);
-    }
-#undef LAUNCH
+    auto launch = [&](auto M, auto HG, auto S) {
+        hipLaunchKernelGGL((k_eval<M, HG, S>), g, b, 0, ctx->stream, ctx->d_state, lv.src, lv.n, L.chunk, level, L.nblocks, ctx->d_partials, lv, ec);
+    };
+    // (the error-only pass exists in the record form alone)
+    if (!hg) with_method(method, [&](auto M) { launch(M, std::false_type{}, std::integral_constant<int, 0>{}); });
+    else with_choice<0, 1>(L.n >= recompute_min_px(), [&](auto S) { with_method(method, [&](auto M) { launch(M, std::true_type{}, S); }); });
 }
 
 // publish: the solve also writes the state into ctx->h_state and bumps the context's host tag (hostwait::wait picks it up)
@@ -371,28 +391,19 @@ SolveCfg fused_cfg(const rgbd360_ctx* ctx, int forced, int occ = 0) {
 // init_pose != nullptr: the launch starts the schedule itself at that pose (no k_level_init in front of it); cfg_in (may be NULL):
 // the solve's settings instead of fused_cfg(ctx, forced) (rgbd360_debug_solve_state)
 void launch_eval_fused(rgbd360_ctx* ctx, int level, int method, int forced, const float* init_pose = nullptr, const SolveCfg* cfg_in = nullptr) {
-    FsInit init;
-    init.on = init_pose ? 1 : 0;
-    if (init_pose) memcpy(init.pose.v, init_pose, sizeof(init.pose.v));
-    else memset(init.pose.v, 0, sizeof(init.pose.v));
+    const FsInit init = fs_init(init_pose);
     const Level& L = ctx->levels[level];
     LevelDev lv = level_dev(L);
     lv.min_depth = ctx->p.min_depth; lv.max_depth = ctx->p.max_depth;
     const EvalConsts ec = eval_consts(ctx->p);
     const SolveCfg cfg = cfg_in ? *cfg_in : fused_cfg(ctx, forced);
     dim3 g(L.nblocks), b(kEvalThreads);
-#define LAUNCHF(M, S) hipLaunchKernelGGL((k_eval_fs<M, S>), g, b, 0, ctx->stream, (const GNState*)ctx->d_state, ctx->d_state_alt, (const double*)ctx->d_partials, \
-                                      ctx->d_partials_alt, lv.src, lv.n, L.chunk, level, L.nblocks, ctx->pend_rows_hint, lv, ec, cfg, init)
-    if (L.n >= recompute_min_px()) {
-        if (method == 0) LAUNCHF(0, 1);
-        else if (method == 1) LAUNCHF(1, 1);
-        else LAUNCHF(2, 1);
-    } else {
-        if (method == 0) LAUNCHF(0, 0);
-        else if (method == 1) LAUNCHF(1, 0);
-        else LAUNCHF(2, 0);
-    }
-#undef LAUNCHF
+    with_choice<0, 1>(L.n >= recompute_min_px(), [&](auto S) {
+        with_method(method, [&](auto M) {
+            hipLaunchKernelGGL((k_eval_fs<M, S>), g, b, 0, ctx->stream, (const GNState*)ctx->d_state, ctx->d_state_alt, (const double*)ctx->d_partials,
+                               ctx->d_partials_alt, lv.src, lv.n, L.chunk, level, L.nblocks, ctx->pend_rows_hint, lv, ec, cfg, init);
+        });
+    });
     ctx->pend_rows_hint = L.nblocks;             // what this launch can leave pending bounds what the next one has to load
     std::swap(ctx->d_state, ctx->d_state_alt);
     std::swap(ctx->d_partials, ctx->d_partials_alt);
@@ -400,38 +411,19 @@ void launch_eval_fused(rgbd360_ctx* ctx, int level, int method, int forced, cons
 // The occlusion-aware iteration of the fused schedule: k_occ_build_fs (solve of the pending pass + run lists at the new pose; writes
 // the new state) and k_eval_occ (gate and pose from that state; leaves its rows pending) -- two launches instead of three.
 void launch_occ_fused(rgbd360_ctx* ctx, int level, int method, int occ, int forced, const float* init_pose = nullptr) {
-    FsInit init;
-    init.on = init_pose ? 1 : 0;
-    if (init_pose) memcpy(init.pose.v, init_pose, sizeof(init.pose.v));
-    else memset(init.pose.v, 0, sizeof(init.pose.v));
+    const FsInit init = fs_init(init_pose);
     const Level& L = ctx->levels[level];
     LevelDev lv = level_dev(L);
     lv.min_depth = ctx->p.min_depth; lv.max_depth = ctx->p.max_depth;
     const EvalConsts ec = eval_consts(ctx->p);
     const SolveCfg cfg = fused_cfg(ctx, forced, occ);
-    if (++ctx->occ_gen > kOccGenMax) {
-        hipMemsetAsync(ctx->occ_head, 0, ctx->occ_n * sizeof(int), ctx->stream);
-        ctx->occ_gen = 1;
-    }
-    const int gen = ctx->occ_gen;
+    const int gen = occ_next_gen(ctx);
     dim3 g(L.nblocks), b(kEvalThreads);
-#define LAUNCH_BUILD(O) hipLaunchKernelGGL((k_occ_build_fs<O>), g, b, 0, ctx->stream, (const GNState*)ctx->d_state, ctx->d_state_alt, (const double*)ctx->d_partials, \
-                                           L.chunk, level, L.nblocks, ctx->pend_rows_hint, lv, cfg, init, gen, ctx->occ_head, ctx->occ_nodes, ctx->occ_runinfo)
-    if (occ == 1) LAUNCH_BUILD(1);
-    else LAUNCH_BUILD(2);
-#undef LAUNCH_BUILD
-#define LAUNCH_OCC(M, O) hipLaunchKernelGGL((k_eval_occ<M, O>), g, b, 0, ctx->stream, lv, ec, (const GNState*)ctx->d_state_alt, ctx->d_partials_alt, L.chunk, level, gen, \
-                                            ctx->occ_head, (const int4*)ctx->occ_nodes, (const unsigned char*)ctx->occ_runinfo)
-    if (occ == 1) {
-        if (method == 0) LAUNCH_OCC(0, 1);
-        else if (method == 1) LAUNCH_OCC(1, 1);
-        else LAUNCH_OCC(2, 1);
-    } else {
-        if (method == 0) LAUNCH_OCC(0, 2);
-        else if (method == 1) LAUNCH_OCC(1, 2);
-        else LAUNCH_OCC(2, 2);
-    }
-#undef LAUNCH_OCC
+    with_choice<1, 2>(occ != 1, [&](auto O) {
+        hipLaunchKernelGGL((k_occ_build_fs<O>), g, b, 0, ctx->stream, (const GNState*)ctx->d_state, ctx->d_state_alt, (const double*)ctx->d_partials,
+                           L.chunk, level, L.nblocks, ctx->pend_rows_hint, lv, cfg, init, gen, ctx->occ_head, ctx->occ_nodes, ctx->occ_runinfo);
+    });
+    launch_eval_occ(ctx, level, method, occ, lv, ec, ctx->d_state_alt, ctx->d_partials_alt, gen);
     ctx->pend_rows_hint = L.nblocks;
     std::swap(ctx->d_state, ctx->d_state_alt);
     std::swap(ctx->d_partials, ctx->d_partials_alt);
@@ -548,10 +540,7 @@ static int upload_stage(rgbd360_ctx* ctx, int slot, const uint8_t* rgb, size_t r
     int rc = ensure_stage(ctx, slot, (size_t)rows * cols * 3, (size_t)rows * cols * dpx);
     if (rc) return rc;
     HIPC(ctx, hipStreamWaitEvent(ctx->up_stream, ctx->conv_ev[slot], 0));      // the slot's previous frame has been converted
-    HIPC(ctx, hipMemcpy2DAsync(ctx->d_stage_rgb[slot], (size_t)cols * 3, rgb, rgb_step, (size_t)cols * 3, rows,
-                               hipMemcpyHostToDevice, ctx->up_stream));
-    HIPC(ctx, hipMemcpy2DAsync(ctx->d_stage_depth[slot], (size_t)cols * dpx, depth, d_step, (size_t)cols * dpx, rows,
-                               hipMemcpyHostToDevice, ctx->up_stream));
+    HIPC(ctx, copy_frame_h2d(ctx->d_stage_rgb[slot], ctx->d_stage_depth[slot], rgb, rgb_step, depth, d_step, depth_type, rows, cols, ctx->up_stream));
     HIPC(ctx, hipEventRecord(ctx->up_ev[slot], ctx->up_stream));
     return 0;
 }
@@ -579,10 +568,7 @@ int set_frame(rgbd360_ctx* ctx, bool target, const uint8_t* rgb, size_t rgb_step
     } else if (!on_device) {
         rc = ensure_stage(ctx, 0, (size_t)rows * cols * 3, (size_t)rows * cols * dpx);
         if (rc) return rc;
-        HIPC(ctx, hipMemcpy2DAsync(ctx->d_stage_rgb[0], (size_t)cols * 3, rgb, rgb_step, (size_t)cols * 3, rows,
-                                   hipMemcpyHostToDevice, ctx->stream));
-        HIPC(ctx, hipMemcpy2DAsync(ctx->d_stage_depth[0], (size_t)cols * dpx, depth, d_step, (size_t)cols * dpx, rows,
-                                   hipMemcpyHostToDevice, ctx->stream));
+        HIPC(ctx, copy_frame_h2d(ctx->d_stage_rgb[0], ctx->d_stage_depth[0], rgb, rgb_step, depth, d_step, depth_type, rows, cols, ctx->stream));
         d_rgb = ctx->d_stage_rgb[0]; d_depth = ctx->d_stage_depth[0];
         s_rgb = (size_t)cols * 3; s_depth = (size_t)cols * dpx;
     }
@@ -863,8 +849,7 @@ static int align360_batch_threads(rgbd360_ctx* ctx, int n_frames, const uint8_t*
     if (n == 0) return 0;
     for (int k = 0; k < n_frames; ++k)
         if (!rgb[k] || !depth[k]) return fail(ctx, -1, "null frame pointer");
-    static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    const float* g = guess ? guess : kIdentity;
+    const float* g = guess ? guess : kIdentityPose;
     const int k_ctx = std::min(n_inflight, n);
     while ((int)ctx->siblings.size() < k_ctx - 1) {
         rgbd360_ctx* sib = nullptr;
@@ -880,11 +865,7 @@ static int align360_batch_threads(rgbd360_ctx* ctx, int n_frames, const uint8_t*
     }
     // contiguous balanced spans [a, b) of pairs per context
     std::vector<int> a(k_ctx), b(k_ctx);
-    for (int c = 0; c < k_ctx; ++c) {
-        const int base = n / k_ctx, extra = n % k_ctx;
-        a[c] = c * base + std::min(c, extra);
-        b[c] = a[c] + base + (c < extra ? 1 : 0);
-    }
+    for (int c = 0; c < k_ctx; ++c) shard_range(n, c, k_ctx, &a[c], &b[c]);
     // One host thread per sub-chunk: a 4-level alignment is ~65 dependent launches, so a single enqueueing thread (≈2.7 us
     // per launch) caps a GPU at ≈5.7 k alignments/s however many contexts are in flight.  The sub-chunks share nothing
     // (own context, stream, buffers, error string; disjoint output slots), so each walks its pairs on its own thread:
@@ -920,21 +901,7 @@ static int align360_batch_threads(rgbd360_ctx* ctx, int n_frames, const uint8_t*
         if (rc) hipStreamSynchronize(cc->stream);
         rcs[c] = rc;
     };
-    {
-        std::vector<std::thread> workers;
-        workers.reserve(k_ctx - 1);
-        std::vector<int> inline_chunks;              // sub-chunks whose thread could not be started run on the caller's thread
-        for (int c = 1; c < k_ctx; ++c) {
-            try {
-                workers.emplace_back(run_chunk, c);
-            } catch (const std::exception&) {        // no exception may cross the C boundary
-                inline_chunks.push_back(c);
-            }
-        }
-        run_chunk(0);
-        for (int c : inline_chunks) run_chunk(c);
-        for (std::thread& w : workers) w.join();
-    }
+    run_on_threads(k_ctx, run_chunk);
     for (int c = 0; c < k_ctx; ++c)
         if (rcs[c]) return cs[c] == ctx ? rcs[c] : fail(ctx, rcs[c], cs[c]->err.c_str());
     return 0;
@@ -995,31 +962,14 @@ static int align360_batch_lockstep(rgbd360_ctx* ctx, int n_frames, const uint8_t
         }
     }
     std::vector<int> a(S), b(S);      // contiguous balanced spans [a, b) of pairs per slot
-    for (int c = 0; c < S; ++c) {
-        const int base = n / S, extra = n % S;
-        a[c] = c * base + std::min(c, extra);
-        b[c] = a[c] + base + (c < extra ? 1 : 0);
-    }
+    for (int c = 0; c < S; ++c) shard_range(n, c, S, &a[c], &b[c]);
     std::vector<int> rcs(n_eng, 0);
     auto run_engine = [&](int e) {
         rcs[e] = seq_run(ctx->engines[e], cnt[e], a.data() + off[e], b.data() + off[e], rgb, rgb_step, depth, depth_step, depth_type, g, method,
                          on_device, poses_out, results_out);
         if (rcs[e]) hipStreamSynchronize(ctx->engines[e]->stream);
     };
-    {
-        std::vector<std::thread> workers;
-        std::vector<int> inline_engines;
-        for (int e = 1; e < n_eng; ++e) {
-            try {
-                workers.emplace_back(run_engine, e);
-            } catch (const std::exception&) {        // no exception may cross the C boundary
-                inline_engines.push_back(e);
-            }
-        }
-        run_engine(0);
-        for (int e : inline_engines) run_engine(e);
-        for (std::thread& w : workers) w.join();
-    }
+    run_on_threads(n_eng, run_engine);
     for (int e = 0; e < n_eng; ++e)
         if (rcs[e]) return fail(ctx, rcs[e], ctx->engines[e]->err.c_str());
     return 0;
@@ -1038,14 +988,13 @@ static int align360_batch_impl(rgbd360_ctx* ctx, int n_frames, const uint8_t* co
     if (n_frames == 1) return 0;
     for (int k = 0; k < n_frames; ++k)
         if (!rgb[k] || !depth[k]) return fail(ctx, -1, "null frame pointer");
-    static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     const char* route = knobs::debug("RGBD360_SEQ_ROUTE");          // "contexts": the per-context route for every sequence (A/B measurements)
     // the occlusion-aware passes have no slot dimension: those sequences run one context per sub-chunk
     if (occlusion != 0 || ctx->seq_route_contexts || (route && strcmp(route, "contexts") == 0))
         // (capped: more busy streams than hardware queues run side by side costs a factor of three, see ctx_route_cap)
         return align360_batch_threads(ctx, n_frames, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, guess, method, occlusion,
                                       std::min(n_inflight, ctx->seq_route_cap > 0 ? ctx->seq_route_cap : ctx_route_cap()), poses_out, results_out, on_device);
-    return align360_batch_lockstep(ctx, n_frames, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, guess ? guess : kIdentity, method,
+    return align360_batch_lockstep(ctx, n_frames, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, guess ? guess : kIdentityPose, method,
                                    n_inflight, poses_out, results_out, on_device);
 }
 
@@ -1625,9 +1574,9 @@ int pin_eval(rgbd360_ctx* ctx, int level, const float* pose, int method) {
     Pose16 P;
     memcpy(P.v, pose, sizeof(P.v));
     const dim3 g(L.nblocks), b(kEvalThreads);
-    if (method == 0) hipLaunchKernelGGL((k_eval_pinhole<0>), g, b, 0, ctx->stream, lv, K, ec, P, ctx->d_partials, L.chunk, level, ctx->sal_thr);
-    else if (method == 1) hipLaunchKernelGGL((k_eval_pinhole<1>), g, b, 0, ctx->stream, lv, K, ec, P, ctx->d_partials, L.chunk, level, ctx->sal_thr);
-    else hipLaunchKernelGGL((k_eval_pinhole<2>), g, b, 0, ctx->stream, lv, K, ec, P, ctx->d_partials, L.chunk, level, ctx->sal_thr);
+    with_method(method, [&](auto M) {
+        hipLaunchKernelGGL((k_eval_pinhole<M>), g, b, 0, ctx->stream, lv, K, ec, P, ctx->d_partials, L.chunk, level, ctx->sal_thr);
+    });
     launch_solve(ctx, level, 1, 0, 0, /*publish=*/true);
     HIPC(ctx, hipGetLastError());
     HIPC(ctx, hostwait::wait(ctx->tag, ctx->stream));
@@ -1663,13 +1612,14 @@ int pin_eval_occ(rgbd360_ctx* ctx, int level, const float* pose, int method, int
     Pose16 P;
     memcpy(P.v, pose, sizeof(P.v));
     const dim3 gk((L.n + 255) / 256), bk(256);
-    if (occ == 1) hipLaunchKernelGGL((k_pin_occ_keys<1>), gk, bk, 0, ctx->stream, lv, K, P, ctx->pin_keys, ctx->pin_vals, ctx->pin_lists);
-    else hipLaunchKernelGGL((k_pin_occ_keys<2>), gk, bk, 0, ctx->stream, lv, K, P, ctx->pin_keys, ctx->pin_vals, ctx->pin_lists);
+    with_choice<1, 2>(occ != 1, [&](auto O) {
+        hipLaunchKernelGGL((k_pin_occ_keys<O>), gk, bk, 0, ctx->stream, lv, K, P, ctx->pin_keys, ctx->pin_vals, ctx->pin_lists);
+    });
     const int nblk = (L.n + kPinWalkThreads - 1) / kPinWalkThreads;
     const dim3 gw(nblk), bw(kPinWalkThreads);
-    if (method == 0) hipLaunchKernelGGL((k_pin_occ_walk<0>), gw, bw, 0, ctx->stream, lv, K, ec, P, ctx->pin_keys, ctx->pin_vals, ctx->pin_lists, ctx->pin_partials);
-    else if (method == 1) hipLaunchKernelGGL((k_pin_occ_walk<1>), gw, bw, 0, ctx->stream, lv, K, ec, P, ctx->pin_keys, ctx->pin_vals, ctx->pin_lists, ctx->pin_partials);
-    else hipLaunchKernelGGL((k_pin_occ_walk<2>), gw, bw, 0, ctx->stream, lv, K, ec, P, ctx->pin_keys, ctx->pin_vals, ctx->pin_lists, ctx->pin_partials);
+    with_method(method, [&](auto M) {
+        hipLaunchKernelGGL((k_pin_occ_walk<M>), gw, bw, 0, ctx->stream, lv, K, ec, P, ctx->pin_keys, ctx->pin_vals, ctx->pin_lists, ctx->pin_partials);
+    });
     SolveCfg cfg;
     cfg.level = level; cfg.mode = 1; cfg.forced = 0; cfg.max_iters = ctx->p.max_iters; cfg.n_pixels = L.n;
     cfg.occ = 0;
@@ -1699,26 +1649,6 @@ PinSums pin_sums(const GNState& S) {
     return o;
 }
 
-// update = -(H [+ lambda diag H])^-1 g ; pose_tmp = exp(update) * pose   (RPI.h:4355-4358, 4389-4391)
-bool pin_lm_update(const float* H, const float* g, float lambda_or_neg, const float* pose, float* pose_tmp, float* update) {
-    float M[36], inv[36];
-    for (int k = 0; k < 36; ++k) M[k] = H[k];
-    if (lambda_or_neg >= 0.f)
-        for (int i = 0; i < 6; ++i) M[i * 6 + i] = H[i * 6 + i] + lambda_or_neg * H[i * 6 + i];
-    if (!gn::inverse6(M, inv)) return false;
-    for (int r = 0; r < 6; ++r) {
-        float s = 0.f;
-        for (int c = 0; c < 6; ++c) s += (-inv[c * 6 + r]) * g[c];
-        update[r] = s;
-    }
-    double ud[6], E[16];
-    for (int i = 0; i < 6; ++i) ud[i] = (double)update[i];
-    gn::se3_exp(ud, E);
-    float Ef[16];
-    for (int k = 0; k < 16; ++k) Ef[k] = (float)E[k];
-    gn::mat4_mul(Ef, pose, pose_tmp);
-    return true;
-}
 }  // namespace
 
 extern "C" int rgbd360_set_camera(rgbd360_ctx* ctx, float fx, float fy, float ox, float oy) {
@@ -1860,7 +1790,7 @@ extern "C" int rgbd360_align_pinhole(rgbd360_ctx* ctx, const float guess[16], in
             float M[36];
             for (int k = 0; k < 36; ++k) M[k] = H[k];
             for (int i = 0; i < 6; ++i) M[i * 6 + i] = H[i * 6 + i] + lambda * H[i * 6 + i];
-            if (gn::rank6(M) != 6 || !pin_lm_update(H, g, -1.f, pose_estim, pose_estim_temp, update_pose)) {
+            if (gn::rank6(M) != 6 || !gn::lm_update(H, g, -1.f, pose_estim, pose_estim_temp, update_pose)) {
                 status = 1;                            // "The problem is ILL-POSED": relPose = pose_estim, return   RPI.h:4346-4353
                 break;
             }
@@ -1887,7 +1817,7 @@ extern "C" int rgbd360_align_pinhole(rgbd360_ctx* ctx, const float guess[16], in
                 unsigned LM_it = 0;
                 while (LM_it < LM_maxIters && diff_error < 0) {
                     lambda = lambda * step;
-                    if (!pin_lm_update(H, g, lambda, pose_estim, pose_estim_temp, update_pose)) break;
+                    if (!gn::lm_update(H, g, lambda, pose_estim, pose_estim_temp, update_pose)) break;
                     if ((rc = eval(level, pose_estim_temp, new_error)) != 0) return rc;
                     cand = P;
                     diff_error = error - new_error;

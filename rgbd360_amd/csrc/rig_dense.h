@@ -427,14 +427,12 @@ int rig_set_frames(rgbd360_rig* R, bool target, const uint8_t* const* rgb, size_
     FramePtrs fp;
     memset(&fp, 0, sizeof(fp));
     for (int s = 0; s < R->S; ++s) {
-        hipError_t e = hipMemcpy2DAsync(E->stage_rgb[0] + (size_t)s * E->stage_rgb_frame, (size_t)cols * 3, rgb[s], rgb_step, (size_t)cols * 3, rows,
-                                        hipMemcpyHostToDevice, E->stream);
-        if (e == hipSuccess)
-            e = hipMemcpy2DAsync(E->stage_depth[0] + (size_t)s * E->stage_depth_frame, (size_t)cols * dpx, depth[s], depth_step, (size_t)cols * dpx,
-                                 rows, hipMemcpyHostToDevice, E->stream);
+        uint8_t* const s_rgb = E->stage_rgb[0] + (size_t)s * E->stage_rgb_frame;
+        uint8_t* const s_depth = E->stage_depth[0] + (size_t)s * E->stage_depth_frame;
+        const hipError_t e = copy_frame_h2d(s_rgb, s_depth, rgb[s], rgb_step, depth[s], depth_step, depth_type, rows, cols, E->stream);
         if (e != hipSuccess) return rfail(R, -(int)e - 1000, hipGetErrorString(e));
-        fp.rgb[s] = E->stage_rgb[0] + (size_t)s * E->stage_rgb_frame;
-        fp.depth[s] = E->stage_depth[0] + (size_t)s * E->stage_depth_frame;
+        fp.rgb[s] = s_rgb;
+        fp.depth[s] = s_depth;
     }
     const unsigned long long live = (1ull << R->S) - 1ull;
     for (int l = 0; l < R->p.n_pyr; ++l) {
@@ -515,17 +513,12 @@ int rig_eval(rgbd360_rig* R, int level, const float* T, int method, RigSums* out
     const PinK K = rig_level_K(R, level);
     const EvalConsts ec = eval_consts(R->p);
     const dim3 g(L.nblocks, R->S), b(kEvalThreads);
-#define LAUNCHR(Mth, Lm) hipLaunchKernelGGL((k_eval_rig<Mth, Lm>), g, b, 0, E->stream, L.srcRec, L.trgP[0], L.trgD[0], L.rows, L.cols, L.n, K, ec, P, E->d_partials, E->partials_stride, L.chunk, R->sal_thr, Q)
-    if (R->index_libm) {
-        if (method == 0) LAUNCHR(0, 1);
-        else if (method == 1) LAUNCHR(1, 1);
-        else LAUNCHR(2, 1);
-    } else {
-        if (method == 0) LAUNCHR(0, 0);
-        else if (method == 1) LAUNCHR(1, 0);
-        else LAUNCHR(2, 0);
-    }
-#undef LAUNCHR
+    with_choice<0, 1>(R->index_libm != 0, [&](auto Lm) {
+        with_method(method, [&](auto M) {
+            hipLaunchKernelGGL((k_eval_rig<M, Lm>), g, b, 0, E->stream, L.srcRec, L.trgP[0], L.trgD[0], L.rows, L.cols, L.n, K, ec, P, E->d_partials,
+                               E->partials_stride, L.chunk, R->sal_thr, Q);
+        });
+    });
     hipLaunchKernelGGL(k_rig_reduce, dim3(R->S), dim3(256), 0, E->stream, E->d_partials, E->partials_stride, L.nblocks, R->h_tot, R->d_ticket,
                        R->tag.h, ++R->tag.seq);
     hipError_t e = hipGetLastError();
@@ -554,25 +547,6 @@ int rig_eval(rgbd360_rig* R, int level, const float* T, int method, RigSums* out
     }
     *out = S;
     return 0;
-}
-
-bool rig_lm_update(const float* H, const float* g, float lambda, const float* pose, float* pose_tmp, float* update) {
-    float M[36], inv[36];
-    for (int k = 0; k < 36; ++k) M[k] = H[k];
-    for (int i = 0; i < 6; ++i) M[i * 6 + i] = H[i * 6 + i] + lambda * H[i * 6 + i];
-    if (!gn::inverse6(M, inv)) return false;
-    for (int r = 0; r < 6; ++r) {
-        float s = 0.f;
-        for (int c = 0; c < 6; ++c) s += (-inv[c * 6 + r]) * g[c];
-        update[r] = s;
-    }
-    double ud[6], Ex[16];
-    for (int i = 0; i < 6; ++i) ud[i] = (double)update[i];
-    gn::se3_exp(ud, Ex);                                 // CPose3D::exp(update) -- the full exponential   RegisterRGBD360.h:455
-    float Ef[16];
-    for (int k = 0; k < 16; ++k) Ef[k] = (float)Ex[k];
-    gn::mat4_mul(Ef, pose, pose_tmp);
-    return true;
 }
 
 }  // namespace
@@ -654,10 +628,9 @@ int rgbd360_rig_warp_indices(rgbd360_rig* R, int level, const float pose[16], in
     hipError_t e = hipMalloc(&d_out, bytes);
     if (e != hipSuccess) return rfail(R, -(int)e - 1000, hipGetErrorString(e));
     const dim3 g((L.n + 255) / 256, R->S);
-    if (R->index_libm)
-        hipLaunchKernelGGL(k_rig_warp_indices<1>, g, dim3(256), 0, E->stream, L.srcRec, L.rows, L.cols, L.n, rig_level_K(R, level), P, Q, chain, d_out);
-    else
-        hipLaunchKernelGGL(k_rig_warp_indices<0>, g, dim3(256), 0, E->stream, L.srcRec, L.rows, L.cols, L.n, rig_level_K(R, level), P, Q, chain, d_out);
+    with_choice<0, 1>(R->index_libm != 0, [&](auto Lm) {
+        hipLaunchKernelGGL(k_rig_warp_indices<Lm>, g, dim3(256), 0, E->stream, L.srcRec, L.rows, L.cols, L.n, rig_level_K(R, level), P, Q, chain, d_out);
+    });
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(host_out_rc, d_out, bytes, hipMemcpyDeviceToHost, E->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(E->stream);
@@ -735,7 +708,9 @@ int rgbd360_rig_align(rgbd360_rig* R, const float guess[16], int method, float p
             float M[36];
             for (int k = 0; k < 36; ++k) M[k] = Hessian[k];
             for (int i = 0; i < 6; ++i) M[i * 6 + i] = Hessian[i * 6 + i] + lambda * Hessian[i * 6 + i];
-            if (gn::rank6(M) != 6 || !rig_lm_update(Hessian, Gradient, lambda, pose_estim, pose_estim_temp, update_pose)) {
+            // (lambda starts at 0.001 and is only ever multiplied or divided by step = 10: never negative, gn::lm_update always damps here;
+            // the exponential is CPose3D::exp(update), the full one   RegisterRGBD360.h:455)
+            if (gn::rank6(M) != 6 || !gn::lm_update(Hessian, Gradient, lambda, pose_estim, pose_estim_temp, update_pose)) {
                 status = 1;                      // "The problem is ILL-POSED"   RegisterRGBD360.h:443-449
                 break;
             }
@@ -752,7 +727,7 @@ int rgbd360_rig_align(rgbd360_rig* R, const float guess[16], int method, float p
                 unsigned LM_it = 0;
                 while (LM_it < LM_maxIters && diff_error < 0) {
                     lambda = lambda * step;
-                    if (!rig_lm_update(Hessian, Gradient, lambda, pose_estim, pose_estim_temp, update_pose)) break;
+                    if (!gn::lm_update(Hessian, Gradient, lambda, pose_estim, pose_estim_temp, update_pose)) break;
                     if ((rc = rig_eval(R, level, pose_estim_temp, method, &cand)) != 0) return rc;
                     new_error = cand.error();
                     diff_error = error - new_error;

@@ -15,9 +15,7 @@
 
 namespace {
 
-struct SeqLevel {
-    int rows = 0, cols = 0, n = 0;
-    float half_nRows = 0.f, angle_res_inv = 0.f;
+struct SeqLevel : LevelGeom {      // geometry, tables and work split as a one-pair context has them (level_geom.h)
     float *gray = nullptr, *depth = nullptr;                                    // [P][n] planes of levels >= 1 (level 0 is never stored)
     float4* srcRec = nullptr;                                                   // [P][n]
     F3 *trgP[2] = {nullptr, nullptr}, *trgD[2] = {nullptr, nullptr};            // [P][n] x 2: the records of a frame are built when it
@@ -25,7 +23,6 @@ struct SeqLevel {
     float *sinT = nullptr, *cosT = nullptr, *sinP = nullptr, *cosP = nullptr;
     float2 *tabT = nullptr, *tabP = nullptr;      // interleaved {sin, cos} (recompute form of the pass)
     bool compact = false;                         // source records of this level are {depth, Isrc} (8 B) and k_eval_b re-forms the point
-    int nblocks = 0, chunk = 0;
 };
 
 // Frame-store mode of an engine (frame_store.h): the records of a level are not the engine's [P][n] slot buffers but the store's
@@ -92,7 +89,6 @@ void seq_free(SeqEngine* E) {
     delete E;
 }
 
-// Geometry, tables and work split exactly as ensure_levels() builds them for a one-pair context.
 // alloc: kSeqPlanes = the [P][n] float planes of levels >= 1, kSeqRecords = the [P][n] record buffers.  A frame store's engines
 // leave out what the store holds per entry (frame_store.h).
 enum { kSeqPlanes = 1, kSeqRecords = 2 };
@@ -100,15 +96,7 @@ int seq_create(const rgbd360_params& p, int P, int rows, int cols, int max_eval_
                int alloc = kSeqPlanes | kSeqRecords) {
     *out = nullptr;
     if (P < 1 || P > kMaxSlots) { *err = "slots per engine must be in 1..32"; return -1; }
-    if (rows < 2 || cols < 8) { *err = "image too small"; return -1; }
-    if ((rows >> (p.n_pyr - 1)) < 2 || (cols >> (p.n_pyr - 1)) < 8) {
-        *err = "too many pyramid levels for this image size (coarsest level must be >= 2 x 8)";
-        return -1;
-    }
-    if ((long long)rows * cols >= (1ll << 24) || rows >= (1 << 15) || cols >= (1 << 15)) {
-        *err = "image too large (the fused pass uses 24-bit index arithmetic: < 16 Mpx)";
-        return -1;
-    }
+    if (const char* why = check_image_size(p, rows, cols)) { *err = why; return -1; }
     if (hipSetDevice(p.device) != hipSuccess) { *err = "hipSetDevice failed"; return -102; }
     SeqEngine* E = new SeqEngine();
     E->p = p; E->P = P; E->rows = rows; E->cols = cols; E->max_eval_blocks = max_eval_blocks;
@@ -128,10 +116,7 @@ int seq_create(const rgbd360_params& p, int P, int rows, int cols, int max_eval_
     int r = rows, c = cols, max_blocks = 0;
     for (int l = 0; l < p.n_pyr; ++l) {
         SeqLevel& L = E->levels[l];
-        L.rows = r; L.cols = c; L.n = r * c;
-        const float angle_res = 2 * kPI / c;        // RPI.h:2554
-        L.angle_res_inv = 1 / angle_res;            // RPI.h:2555
-        L.half_nRows = 0.5 * r - 0.5;               // RPI.h:2557
+        static_cast<LevelGeom&>(L) = level_geom(r, c, max_eval_blocks);
         const size_t np = (size_t)P * L.n;
         bool ok = true;
         if (l > 0 && (alloc & kSeqPlanes))
@@ -142,41 +127,15 @@ int seq_create(const rgbd360_params& p, int P, int rows, int cols, int max_eval_
         ok = ok && hipMalloc(&L.sinT, c * sizeof(float)) == hipSuccess && hipMalloc(&L.cosT, c * sizeof(float)) == hipSuccess &&
              hipMalloc(&L.sinP, r * sizeof(float)) == hipSuccess && hipMalloc(&L.cosP, r * sizeof(float)) == hipSuccess;
         if (!ok) return bad("out of device memory for the sequence engine");
-        std::vector<float> st(c), ct(c), sp(r), cp(r);      // RPI.h:4556-4571 (host libm, as ensure_levels)
-        for (int j = 0; j < c; ++j) {
-            float theta = j * angle_res;
-            st[j] = sinf(theta);
-            ct[j] = cosf(theta);
-        }
-        for (int i = 0; i < r; ++i) {
-            float phi = (L.half_nRows - i) * angle_res;
-            sp[i] = sinf(phi);
-            cp[i] = cosf(phi);
-        }
-        ok = hipMemcpy(L.sinT, st.data(), c * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(L.cosT, ct.data(), c * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(L.sinP, sp.data(), r * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(L.cosP, cp.data(), r * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+        ok = hipMalloc(&L.tabT, c * sizeof(float2)) == hipSuccess && hipMalloc(&L.tabP, r * sizeof(float2)) == hipSuccess &&
+             upload_angle_tables(angle_tables(L), L.sinT, L.cosT, L.sinP, L.cosP, L.tabT, L.tabP) == hipSuccess;
         if (!ok) return bad("table upload failed");
-        {
-            std::vector<float2> tt(c), tp(r);
-            for (int j = 0; j < c; ++j) tt[j] = make_float2(st[j], ct[j]);
-            for (int i = 0; i < r; ++i) tp[i] = make_float2(sp[i], cp[i]);
-            ok = hipMalloc(&L.tabT, c * sizeof(float2)) == hipSuccess && hipMalloc(&L.tabP, r * sizeof(float2)) == hipSuccess &&
-                 hipMemcpy(L.tabT, tt.data(), c * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess &&
-                 hipMemcpy(L.tabP, tp.data(), r * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess;
-            if (!ok) return bad("table upload failed");
-        }
         // The engine's launches serve P pairs at once, so its large levels are fed from HBM whatever the image size: they carry the
         // 8-byte {depth, Isrc} source record and k_eval_b re-forms the point (SrcForm<2>: 32 instead of 40 B/px per pass, 32 instead of
         // 40 B/px written by the set-up).  The latency-bound small levels keep the 16-byte record.  RGBD360_SEQ_RECOMPUTE_MIN_PX moves
         // the bound (0: every level; a huge value: none).  The rig's pinhole records never take this form (rig_dense.h builds its own).
         static const int seq_min_px = [] { const char* e = knobs::product("RGBD360_SEQ_RECOMPUTE_MIN_PX"); return e ? atoi(e) : 256 * 1024; }();
         L.compact = L.n >= seq_min_px;
-        int chunk = (L.n + max_eval_blocks - 1) / max_eval_blocks;
-        chunk = ((chunk + kEvalThreads - 1) / kEvalThreads) * kEvalThreads;
-        L.chunk = chunk;
-        L.nblocks = (L.n + chunk - 1) / chunk;
         max_blocks = std::max(max_blocks, L.nblocks);
         r /= 2; c /= 2;
     }
@@ -192,9 +151,7 @@ int seq_create(const rgbd360_params& p, int P, int rows, int cols, int max_eval_
 
 LevelDev seq_level_dev(const SeqLevel& L, int tb) {
     LevelDev d;
-    d.rows = L.rows; d.cols = L.cols; d.n = L.n;
-    d.half_nRows = L.half_nRows; d.angle_res_inv = L.angle_res_inv;
-    d.pi_k = (float)(kPI * (double)L.angle_res_inv);
+    fill_level_dev(d, L);
     d.src = L.srcRec; d.trgP = L.trgP[tb]; d.trgD = L.trgD[tb];
     d.src2 = reinterpret_cast<const float2*>(L.srcRec); d.tabT = L.tabT; d.tabP = L.tabP;
     return d;
@@ -211,25 +168,16 @@ void seq_launch_eval(SeqEngine* E, int level, int method) {
         const StoreLevelView& V = E->sv->levels[level];
         lv.src = V.src; lv.src2 = reinterpret_cast<const float2*>(V.src); lv.trgP = V.trgP; lv.trgD = V.trgD;
     }
-#define LAUNCHB(M, S)                                                                                                                          \
-    do {                                                                                                                                       \
-        if (E->sv)                                                                                                                             \
-            hipLaunchKernelGGL((k_eval_p<M, true, S>), g, b, 0, E->stream, E->d_states, lv.src, lv.n, L.chunk, level, L.nblocks, E->d_partials, \
-                               E->partials_stride, lv, ec, E->sv->pt);                                                                         \
-        else                                                                                                                                   \
-            hipLaunchKernelGGL((k_eval_b<M, true, S>), g, b, 0, E->stream, E->d_states, lv.src, lv.n, L.chunk, level, L.nblocks, E->d_partials, \
-                               E->partials_stride, lv, ec);                                                                                    \
-    } while (0)
-    if (L.compact) {
-        if (method == 0) LAUNCHB(0, 2);
-        else if (method == 1) LAUNCHB(1, 2);
-        else LAUNCHB(2, 2);
-    } else {
-        if (method == 0) LAUNCHB(0, 0);
-        else if (method == 1) LAUNCHB(1, 0);
-        else LAUNCHB(2, 0);
-    }
-#undef LAUNCHB
+    with_choice<0, 2>(L.compact, [&](auto S) {
+        with_method(method, [&](auto M) {
+            if (E->sv)
+                hipLaunchKernelGGL((k_eval_p<M, true, S>), g, b, 0, E->stream, E->d_states, lv.src, lv.n, L.chunk, level, L.nblocks, E->d_partials,
+                                   E->partials_stride, lv, ec, E->sv->pt);
+            else
+                hipLaunchKernelGGL((k_eval_b<M, true, S>), g, b, 0, E->stream, E->d_states, lv.src, lv.n, L.chunk, level, L.nblocks, E->d_partials,
+                                   E->partials_stride, lv, ec);
+        });
+    });
 }
 
 void seq_launch_solve(SeqEngine* E, int level, int forced = 0) {
@@ -388,10 +336,8 @@ int seq_run_body(SeqEngine* E, int n_slots, const int* a, const int* b, const ui
         for (int s = 0; s < n_slots; ++s) {
             if (!((live >> s) & 1ull)) continue;
             const int f = frame_of(s, r, which);
-            SEQC(E, hipMemcpy2DAsync(E->stage_rgb[par] + (size_t)s * E->stage_rgb_frame, (size_t)E->cols * 3, rgb[f], rgb_step, (size_t)E->cols * 3,
-                                     E->rows, hipMemcpyHostToDevice, E->up_stream));
-            SEQC(E, hipMemcpy2DAsync(E->stage_depth[par] + (size_t)s * E->stage_depth_frame, (size_t)E->cols * dpx, depth[f], depth_step,
-                                     (size_t)E->cols * dpx, E->rows, hipMemcpyHostToDevice, E->up_stream));
+            SEQC(E, copy_frame_h2d(E->stage_rgb[par] + (size_t)s * E->stage_rgb_frame, E->stage_depth[par] + (size_t)s * E->stage_depth_frame, rgb[f],
+                                   rgb_step, depth[f], depth_step, depth_type, E->rows, E->cols, E->up_stream));
         }
         SEQC(E, hipEventRecord(E->up_ev[par], E->up_stream));
         return 0;

@@ -189,13 +189,13 @@ class RegisterPhotoICP:
         rc = self._L.rgbd360_align360_finish(self._ctx(), _ptr(out), C.byref(self._res))
         return self._take_result(rc, out)
 
-    def _take_result(self, rc, out):
+    def _take_result(self, rc, out, zero_ill_posed=True):
         self._check(rc, allow=(0, 1, 2))
         self.status = rc
         self._pose = pose_from_cm(out)
         r = self._res
-        self.SSO = float(r.sso)
-        self.avResidual = 0.0 if rc == 1 else float(r.err_final)     # ill-posed: avResidual = 0 (RPI.h:4688)
+        self.SSO = float(r.sso)          # on the pinhole path only calcHessGrad_Occ2 sets it (RPI.h:2016)
+        self.avResidual = 0.0 if rc == 1 and zero_ill_posed else float(r.err_final)     # ill-posed: avResidual = 0 (RPI.h:4688)
         self.avPhotoResidual = float(r.rms_photo)
         self.avDepthResidual = float(r.rms_depth)
         self.num_iterations = [int(r.iters[l]) for l in range(self._p.n_pyr)]
@@ -214,16 +214,7 @@ class RegisterPhotoICP:
         g = pose_to_cm(np.eye(4) if pose_guess is None else pose_guess)
         out = np.zeros(16, dtype=np.float32)
         rc = self._L.rgbd360_align_pinhole(self._ctx(), _ptr(g), int(method), int(occlusion), _ptr(out), C.byref(self._res))
-        self._check(rc, allow=(0, 1, 2))
-        self.status = rc
-        self._pose = pose_from_cm(out)
-        r = self._res
-        self.SSO = float(r.sso)          # only calcHessGrad_Occ2 sets it on this path (RPI.h:2016)
-        self.avResidual = float(r.err_final)
-        self.avPhotoResidual = float(r.rms_photo)
-        self.avDepthResidual = float(r.rms_depth)
-        self.num_iterations = [int(r.iters[l]) for l in range(self._p.n_pyr)]
-        return rc
+        return self._take_result(rc, out, zero_ill_posed=False)      # (this path hands the library's err_final through as it is)
 
     def eval_pinhole(self, level: int, pose, method: int, occlusion: int = 0):
         p = pose_to_cm(pose)
@@ -251,11 +242,8 @@ class RegisterPhotoICP:
         Returns (poses [n,4,4] float32, status [n] int32, iters [n, n_pyr] int32)."""
         from ._lib import Result
         n = len(frames) - 1
-        poses = np.zeros((max(n, 0), 4, 4), np.float32)
-        status = np.zeros(max(n, 0), np.int32)
-        iters = np.zeros((max(n, 0), self._p.n_pyr), np.int32)
         if n <= 0:
-            return poses, status, iters
+            return self._unpack_batch(None, None, 0)
         rgbs = [np.ascontiguousarray(f[0], np.uint8) for f in frames]
         deps = [np.ascontiguousarray(f[1]) for f in frames]
         shape, dtype = deps[0].shape, deps[0].dtype
@@ -272,6 +260,13 @@ class RegisterPhotoICP:
         self._check(self._L.rgbd360_align360_batch(self._ctx(), len(frames), rgb_ptrs, shape[1] * 3, dep_ptrs,
                                                    shape[1] * dtype.itemsize, 0 if dtype == np.uint16 else 1, shape[0], shape[1],
                                                    g, int(method), int(occlusion), int(n_inflight), _ptr(out), res))
+        return self._unpack_batch(out, res, n)
+
+    def _unpack_batch(self, out, res, n):
+        """(poses [n,4,4] float32, status [n] int32, iters [n, n_pyr] int32) of a batch call's output arrays."""
+        poses = np.zeros((n, 4, 4), np.float32)
+        status = np.zeros(n, np.int32)
+        iters = np.zeros((n, self._p.n_pyr), np.int32)
         for j in range(n):
             poses[j] = pose_from_cm(out[16 * j:16 * j + 16])
             status[j] = res[j].status
@@ -284,11 +279,8 @@ class RegisterPhotoICP:
         rgb_ptrs / depth_ptrs: raw device pointers (e.g. torch_tensor.data_ptr()), row-major, steps in bytes (0 = packed)."""
         from ._lib import Result
         n = len(rgb_ptrs) - 1
-        poses = np.zeros((max(n, 0), 4, 4), np.float32)
-        status = np.zeros(max(n, 0), np.int32)
-        iters = np.zeros((max(n, 0), self._p.n_pyr), np.int32)
         if n <= 0:
-            return poses, status, iters
+            return self._unpack_batch(None, None, 0)
         if len(depth_ptrs) != len(rgb_ptrs):
             raise Rgbd360Error("rgb_ptrs and depth_ptrs must have the same length")
         rp = (C.c_void_p * len(rgb_ptrs))(*[int(x) for x in rgb_ptrs])
@@ -299,11 +291,7 @@ class RegisterPhotoICP:
         self._check(self._L.rgbd360_align360_batch_dev(self._ctx(), len(rgb_ptrs), rp, rgb_step or cols * 3, dp,
                                                        depth_step or cols * (2 if depth_type == 0 else 4), int(depth_type), rows, cols,
                                                        g, int(method), int(occlusion), int(n_inflight), _ptr(out), res))
-        for j in range(n):
-            poses[j] = pose_from_cm(out[16 * j:16 * j + 16])
-            status[j] = res[j].status
-            iters[j] = [int(res[j].iters[l]) for l in range(self._p.n_pyr)]
-        return poses, status, iters
+        return self._unpack_batch(out, res, n)
 
     def getOptimalPose(self) -> np.ndarray:       # RPI.h:273
         return self._pose.copy()
