@@ -11,10 +11,13 @@
 // Frames: raw files written by tools/dump_sequence.py, frame_%03d.rgb (H*W*3 uint8), frame_%03d.depth (H*W uint16 mm).
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/keyframe_odometry.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o keyframe_odometry
-// Usage:  keyframe_odometry <dir> <n_frames> <width> <height> [window = 4] [max avDepthResidual = 0.9]
+// Usage:  keyframe_odometry <dir> <n_frames> <width> <height> [window = 4] [max avDepthResidual = 0.9] [--warp-images <prefix>]
+//         --warp-images: after the last alignment, the last frame warped into its keyframe at the solved pose and the photometric
+//         difference (RegisterPhotoICP::warpImages, level 0) as <prefix>_warped_gray.pgm and <prefix>_diff_gray.pgm (binary PGM)
 // Prints per frame:  frame <i> kf <keyframe> status <s> pose <16 floats, column-major: the frame in its keyframe> res <avDepthResidual> sso <SSO>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <string>
 #include <vector>
@@ -41,7 +44,25 @@ struct Frame {
     }
 };
 
+// float plane in [0, 1] -> 8-bit binary PGM
+static bool write_pgm(const std::string& path, const std::vector<float>& v, int rows, int cols) {
+    std::vector<uint8_t> px(v.size());
+    for (size_t i = 0; i < v.size(); ++i) px[i] = (uint8_t)(255.f * (v[i] < 0.f ? 0.f : (v[i] > 1.f ? 1.f : v[i])) + 0.5f);
+    std::ofstream f(path, std::ios::binary);
+    f << "P5\n" << cols << " " << rows << "\n255\n";
+    f.write((const char*)px.data(), px.size());
+    return (bool)f;
+}
+
 int main(int argc, char** argv) {
+    std::string warp_prefix;
+    for (int a = 1; a + 1 < argc; ++a)
+        if (!strcmp(argv[a], "--warp-images")) {      // taken out of the positional arguments
+            warp_prefix = argv[a + 1];
+            for (int b = a; b + 2 < argc; ++b) argv[b] = argv[b + 2];
+            argc -= 2;
+            break;
+        }
     if (argc < 5) {
         fprintf(stderr, "usage: %s <dir> <n_frames> <width> <height> [window] [max avDepthResidual]\n", argv[0]);
         return 2;
@@ -68,6 +89,8 @@ int main(int argc, char** argv) {
         };
         std::vector<Pending> pending;      // resident frames waiting for their alignment against the current keyframe
         int next = 1;
+        int last_kf = -1, last_frame = -1;      // the last alignment that succeeded, for --warp-images
+        rgbd360::Mat4f last_pose = rgbd360::Mat4f::Identity();
         while (next < n || !pending.empty()) {
             std::vector<Frame> fresh;
             std::vector<int> entries;
@@ -93,6 +116,7 @@ int main(int argc, char** argv) {
                 printf("frame %d kf %d status %d pose", pending[j].frame, kf, res[j].status);
                 for (int k = 0; k < 16; ++k) printf(" %.9g", poses[j].m[k]);
                 printf(" res %.9g sso %.9g\n", res[j].rms_depth, (double)res[j].sso);
+                if (res[j].status == 0) { last_kf = kf; last_frame = pending[j].frame; last_pose = poses[j]; }
                 if (res[j].status == 0 && res[j].rms_depth < max_residual) {      // "skip frame": the keyframe stays
                     guess = poses[j];
                     free_entries.push_back(pending[j].entry);
@@ -106,6 +130,19 @@ int main(int argc, char** argv) {
                 break;
             }
             pending.erase(pending.begin(), pending.begin() + j);
+        }
+        if (!warp_prefix.empty() && last_frame >= 0) {
+            // a one-pair object of its own (the store's frames are not the context's target / source): the pair is read again
+            Frame trg, src;
+            if (!trg.load(dir, last_kf, w, h) || !src.load(dir, last_frame, w, h)) return 3;
+            rgbd360::RegisterPhotoICP viz;
+            viz.setNumPyr(4);
+            viz.setTargetFrame(trg.sphereRGB, trg.sphereDepth);
+            viz.setSourceFrame(src.sphereRGB, src.sphereDepth);
+            const rgbd360::WarpedImages wi = viz.warpImages(last_pose, rgbd360::RegisterPhotoICP::PHOTO_DEPTH, 0);
+            if (!write_pgm(warp_prefix + "_warped_gray.pgm", wi.gray, wi.rows, wi.cols) ||
+                !write_pgm(warp_prefix + "_diff_gray.pgm", wi.diffGray, wi.rows, wi.cols)) return 3;
+            fprintf(stderr, "warp-images: frame %d into keyframe %d, %d x %d\n", last_frame, last_kf, wi.cols, wi.rows);
         }
     } catch (const std::exception& e) {
         fprintf(stderr, "%s\n", e.what());

@@ -61,6 +61,14 @@ struct ImageView {
     enum Type { U8C3, U16C1, F32C1 } type = U8C3;
 };
 
+// What warpImages() returns: the source frame warped into the target frame at a pose and the difference images, rows x cols of
+// the pyramid level, row-major (rgbd360_warp_images).  winner: the source pixel index that wrote each target pixel, -1 in holes.
+struct WarpedImages {
+    int rows = 0, cols = 0;
+    std::vector<float> gray, depth, diffGray, diffDepth;
+    std::vector<int32_t> winner;
+};
+
 class RegisterPhotoICP {
    public:
     enum costFuncType { PHOTO_CONSISTENCY, DEPTH_CONSISTENCY, PHOTO_DEPTH };   // RPI.h:194
@@ -191,6 +199,14 @@ class RegisterPhotoICP {
         return poses;
     }
 
+    // warped_source_grayImage / warped_source_depthImage (RPI.h:163-166) and the two difference images of alignFrames360's
+    // visualisation branch (RPI.h:4664-4676) at `pose`, without the windows: what setVisualization(true) would have shown.  Where
+    // several source pixels land on one target pixel the largest source index wins, as in the reference's sequential loop
+    // (rgbd360_warp_images).  A plane that does not apply to `method` comes back zero.
+    WarpedImages warpImages(const Mat4f& pose, costFuncType method, int level = 0) { return warp_images(false, pose, method, level); }
+    // ... of the pinhole path (calcHessGrad, RPI.h:805-811, 1025-1026, 1050-1051; needs setCameraMatrix and setMaskSeams(false))
+    WarpedImages warpImagesPinhole(const Mat4f& pose, costFuncType method, int level = 0) { return warp_images(true, pose, method, level); }
+
     // results as PODs (always), and under the reference's names: Eigen types when Eigen is there (below), else the PODs
     Mat4f getOptimalPosePod() const { return relPose_; }
     Mat6f getHessianPod() const { return hessian_; }
@@ -281,6 +297,8 @@ class RegisterPhotoICP {
     }
 #endif
 #ifdef RGBD360_HAVE_OPENCV
+    // RPI.h:163-166: CV_32FC1 images of the last warpImages / warpImagesPinhole call (empty before the first)
+    cv::Mat warped_source_grayImage, warped_source_depthImage;
     // RPI.h:198-199: the public pyramids (CV_32FC1 per level).  They live in HBM; downloadPyramids() fills the vectors for
     // callers that read them (RegisterRGBD360.h:385-388 does; the alignment itself never needs them on the host).
     std::vector<cv::Mat> graySrcPyr, grayTrgPyr, depthSrcPyr, depthTrgPyr, grayTrgGradXPyr, grayTrgGradYPyr, depthTrgGradXPyr, depthTrgGradYPyr;
@@ -329,6 +347,24 @@ class RegisterPhotoICP {
             if (index_libm_) rgbd360_set_index_arithmetic(ctx_, index_libm_);
         }
         return ctx_;
+    }
+    WarpedImages warp_images(bool pinhole, const Mat4f& pose, costFuncType method, int level) {
+        WarpedImages w;
+        if (rgbd360_level_dims(ctx(), level, &w.rows, &w.cols) != 0) throw std::runtime_error(std::string("rgbd360_level_dims: ") + rgbd360_last_error(ctx_));
+        const size_t n = (size_t)w.rows * w.cols;
+        w.gray.resize(n); w.depth.resize(n); w.diffGray.resize(n); w.diffDepth.resize(n); w.winner.resize(n);
+        const int rc = (pinhole ? rgbd360_warp_images_pinhole : rgbd360_warp_images)(ctx_, level, pose.m, (int)method, w.gray.data(), w.depth.data(),
+                                                                                    w.diffGray.data(), w.diffDepth.data(), w.winner.data());
+        if (rc != 0) throw std::runtime_error(std::string("rgbd360_warp_images: ") + rgbd360_last_error(ctx_));
+#ifdef RGBD360_HAVE_OPENCV
+        warped_source_grayImage.create(w.rows, w.cols, CV_32FC1);
+        warped_source_depthImage.create(w.rows, w.cols, CV_32FC1);
+        for (int r = 0; r < w.rows; ++r) {
+            std::memcpy(warped_source_grayImage.data + (size_t)r * warped_source_grayImage.step, &w.gray[(size_t)r * w.cols], (size_t)w.cols * sizeof(float));
+            std::memcpy(warped_source_depthImage.data + (size_t)r * warped_source_depthImage.step, &w.depth[(size_t)r * w.cols], (size_t)w.cols * sizeof(float));
+        }
+#endif
+        return w;
     }
     void set(bool target, const ImageView& rgb, const ImageView& depth) {
         if (rgb.type != ImageView::U8C3) throw std::invalid_argument("rgbd360: imgRGB must be CV_8UC3");

@@ -258,6 +258,31 @@ int rgbd360_eval_occ(rgbd360_ctx* ctx, int level, const float pose[16], int meth
 /* Warped target pixel of every source pixel of `level` under `pose`: out[2i] = r', out[2i+1] = c', -1 if the
  * pixel is invalid or leaves the image (RPI.h:2663-2684).  Host output, n x 2 int32. */
 int rgbd360_warp_indices(rgbd360_ctx* ctx, int level, const float pose[16], int32_t* host_out_rc);
+/* The source frame warped into the target frame at `pose`, and the two difference images: the per-pixel product of the
+ * reference's visualisation path (warped_source_grayImage / warped_source_depthImage RPI.h:163-166, filled inside
+ * calcHessGrad_sphere RPI.h:2779-2785, 3032-3033, 3066-3067; imgDiff / depthDiff RPI.h:4664-4676) without its windows.  Every
+ * plane has the geometry of the target level (rows x cols, row-major); any output pointer may be NULL.
+ *  - A source pixel i (flat index) is VISIBLE exactly when rgbd360_warp_indices reports a target (r', c') for it, in whichever
+ *    index arithmetic the context is set to (rgbd360_set_index_arithmetic).
+ *  - warped_gray (methods 0 and 2; zero-filled, RPI.h:2782): every visible i writes Isrc[i] at its target pixel, BEFORE the
+ *    saliency test (RPI.h:3033 precedes 3038): non-salient target pixels take a value too.
+ *  - warped_depth (methods 1 and 2; zero-filled): a visible i writes dist = |R p + t| (RPI.h:2976, 3067) where the target depth
+ *    at (r', c') is finite (RPI.h:3064).  With method 2 the photometric `continue` (RPI.h:3038-3039) skips the depth block:
+ *    only where NOT (|gx| < thres_sal_photo && |gy| < thres_sal_photo) of the target's gray gradient.
+ *  - Collisions: the reference's loop runs i ascending and each write overwrites (RPI.h:2953; its OpenMP build races there).
+ *    The sequential semantics hold here: the LARGEST source index that lands on a target pixel wins, identically from run to
+ *    run.  Whether a target pixel takes depth writes depends on the target pixel alone, so the depth winner is the gray winner.
+ *    winner: that source index per target pixel, -1 where nothing landed (any method).
+ *  - diff_gray = |Itrg - warped_gray| (methods 0 and 2), diff_depth = |Dtrg - warped_depth| (methods 1 and 2), over the whole
+ *    level, holes included (cv::absdiff, RPI.h:4664-4676); a non-finite target depth propagates.
+ * A plane that does not apply to the method comes back zero.  Returns 0, -1 bad arguments, -2 frame missing, -3 bad level,
+ * -4 bad method, -6 an rgbd360_align360_begin alignment is in flight. */
+int rgbd360_warp_images(rgbd360_ctx* ctx, int level, const float pose[16], int method, float* warped_gray, float* warped_depth,
+                        float* diff_gray, float* diff_depth, int32_t* winner);
+/* The same with DEVICE output pointers (on the context's device): enqueued on the context's stream, returns without waiting
+ * (rgbd360_sync, or further work on rgbd360_stream). */
+int rgbd360_warp_images_dev(rgbd360_ctx* ctx, int level, const float pose[16], int method, float* warped_gray_dev,
+                            float* warped_depth_dev, float* diff_gray_dev, float* diff_depth_dev, int32_t* winner_dev);
 /* One Gauss-Newton step on the device from the H,g of the preceding rgbd360_eval... exposed for tests:
  * pose_tmp = exp(-H^-1 g) * pose (RPI.h:4682-4697).  Returns RGBD360_ILL_POSED when the rank test fails. */
 int rgbd360_gn_step(rgbd360_ctx* ctx, const float H[36], const float g[6], float lambda, const float pose[16],
@@ -549,6 +574,11 @@ int rgbd360_eval_pinhole(rgbd360_ctx* ctx, int level, const float pose[16], int 
 int rgbd360_eval_pinhole_occ(rgbd360_ctx* ctx, int level, const float pose[16], int method, int occlusion, double err2_split[2],
                              long long n_split[2], float H[36], float g[6], double H64[36], double g64[6], long long* n_rows);
 int rgbd360_warp_indices_pinhole(rgbd360_ctx* ctx, int level, const float pose[16], int32_t* host_out_rc);
+/* rgbd360_warp_images for the pinhole path (needs rgbd360_set_camera; calcHessGrad RPI.h:805-811, 1025-1026, 1050-1051):
+ * visibility is rgbd360_warp_indices_pinhole's; warped_depth takes the transformed z (RPI.h:1051) WITHOUT a test of the target
+ * depth, with method 2 under the same photometric `continue` (RPI.h:1031-1032).  Host outputs, same return codes. */
+int rgbd360_warp_images_pinhole(rgbd360_ctx* ctx, int level, const float pose[16], int method, float* warped_gray,
+                                float* warped_depth, float* diff_gray, float* diff_depth, int32_t* winner);
 
 /* The same chain with the depth image already in HBM and the maps left there: *xyz_dev, *normals_dev (rows*cols*3 floats) and
  * *labels_dev (rows*cols int32; root pixel index of the region, -1 for invalid points) point into buffers owned by the context,

@@ -67,6 +67,12 @@ int rgbd360_debug_solve_state(rgbd360_ctx* ctx, int level, const double row[32],
 int rgbd360_time_eval_kernel(rgbd360_ctx* ctx, int level, const float pose[16], int method, int want_hg, int reps,
                              float* avg_us);
 
+/* rgbd360_warp_images (rgbd360_hip.h) under HIP events, averages over `reps` back-to-back launches on `level` in microseconds:
+ * avg_us[0] the winner pass, [1] the resolve pass (all four float planes), [2] the whole rgbd360_warp_images_dev sequence (clear of
+ * the winner plane + both passes), [3] ONE k_warp_indices launch (the kernel of rgbd360_warp_indices) at the same size: the cost of
+ * the warp alone, the yardstick for what scatter and resolve add.  Outputs go to the context's staging. */
+int rgbd360_time_warp_images(rgbd360_ctx* ctx, int level, const float pose[16], int method, int reps, float avg_us[4]);
+
 /* The same timer with the launches rotating over n_ctx contexts of one device (each with its own copy of a frame pair) on
  * ctxs[0]'s stream: once n_ctx x the level's working set exceeds the 256 MiB Infinity Cache every launch is fed from HBM. */
 int rgbd360_time_eval_kernel_rotating(rgbd360_ctx* const* ctxs, int n_ctx, int level, const float pose[16], int method,

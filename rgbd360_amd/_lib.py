@@ -27,6 +27,7 @@ SYMBOLS = [
     "rgbd360_debug_solve_state",
     "rgbd360_store_create", "rgbd360_store_destroy", "rgbd360_store_last_error", "rgbd360_store_entry_bytes", "rgbd360_store_put",
     "rgbd360_store_occupied", "rgbd360_store_align",
+    "rgbd360_warp_images", "rgbd360_warp_images_dev", "rgbd360_warp_images_pinhole", "rgbd360_time_warp_images",
 ]
 
 
@@ -117,6 +118,9 @@ def load() -> C.CDLL:
     L.rgbd360_eval_pinhole_occ.argtypes = [vp, i32, f32p, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_longlong)]
     L.rgbd360_use_saliency.argtypes = [vp, i32, C.c_float]
     L.rgbd360_warp_indices_pinhole.argtypes = [vp, i32, f32p, vp]
+    for f in (L.rgbd360_warp_images, L.rgbd360_warp_images_dev, L.rgbd360_warp_images_pinhole):
+        f.argtypes = [vp, i32, f32p, i32, vp, vp, vp, vp, vp]
+    L.rgbd360_time_warp_images.argtypes = [vp, i32, f32p, i32, i32, vp]
     L.rgbd360_gn_step.argtypes = [vp, f32p, f32p, C.c_float, f32p, f32p, f32p]
     L.rgbd360_forced_iters.argtypes = [vp, i32, f32p, i32, i32, f32p, C.POINTER(C.c_double), C.POINTER(C.c_float)]
     L.rgbd360_time_eval_kernel.argtypes = [vp, i32, f32p, i32, i32, i32, C.POINTER(C.c_float)]

@@ -40,6 +40,9 @@ LevelGeom level_geom(int rows, int cols, int max_eval_blocks) {
     return g;
 }
 
+// grid of a stage kernel that runs one lane per pixel of the level, in blocks of `threads` lanes (warp_images.h)
+dim3 level_pixel_grid(const LevelGeom& g, int threads) { return dim3((g.n + threads - 1) / threads); }
+
 struct AngleTables {
     std::vector<float> st, ct, sp, cp;      // sin / cos of theta per column, of phi per row
     std::vector<float2> tt, tp;             // the same values interleaved {sin, cos}: one 8-byte load per pixel in the recompute forms of the pass

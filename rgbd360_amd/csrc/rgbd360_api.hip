@@ -29,6 +29,7 @@
 #include "photo_icp_kernels.h"
 #include "occlusion_kernels.h"
 #include "pinhole_kernels.h"
+#include "warp_images.h"
 #include "f360_state.h"
 
 using namespace r360;
@@ -140,6 +141,11 @@ struct rgbd360_ctx {
     unsigned char* occ_runinfo = nullptr;              // ... per source pixel: candidate / prefix maximum within its run / offset to the run's first pixel
     int occ_gen = 0;                                   // generation tag of the head entries (no memset between passes)
     size_t occ_n = 0;
+    // rgbd360_warp_images*: the winner plane and the four float planes the host entries stage their outputs in, sized for the finest level on
+    // first use and freed with the levels
+    int32_t* wi_winner = nullptr;
+    float* wi_stage = nullptr;
+    size_t wi_n = 0;
     int max_eval_blocks = 256;    // grid cap of the fused pass (debug knob RGBD360_EVAL_BLOCKS, csrc/knobs.h)
     int index_libm = 0;           // rgbd360_set_index_arithmetic: 1 = the spherical warp in the reference's libm arithmetic
     unsigned char* arena = nullptr;   // ONE allocation behind every per-level buffer of the context (planes, records, angle tables)
@@ -176,6 +182,10 @@ void free_levels(rgbd360_ctx* ctx) {
         hipFree(L.srcRecPin);
     }
     pin_occ_free(ctx);
+    hipFree(ctx->wi_winner); hipFree(ctx->wi_stage);
+    ctx->wi_winner = nullptr;
+    ctx->wi_stage = nullptr;
+    ctx->wi_n = 0;
     hipFree(ctx->arena);
     ctx->arena = nullptr;
     ctx->levels.clear();
@@ -1731,6 +1741,122 @@ extern "C" int rgbd360_warp_indices_pinhole(rgbd360_ctx* ctx, int level, const f
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     hipFree(d_out);
     HIPC(ctx, e);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The source frame warped into the target frame at one pose, and the difference images (warp_images.h).
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+int wi_check(rgbd360_ctx* ctx, int level, const float* pose, int method, bool pinhole) {
+    const int rc = pinhole ? pin_check(ctx, level, method) : check_args(ctx, level, method);
+    if (rc) return rc;
+    if (!pose) return fail(ctx, -1, "null pose pointer");
+    if (ctx->al_active) return fail(ctx, -6, "an alignment is in flight");
+    return 0;
+}
+
+int wi_ensure(rgbd360_ctx* ctx) {
+    const size_t n = (size_t)ctx->levels[0].n;
+    if (ctx->wi_n >= n) return 0;
+    HIPC(ctx, hipMalloc(&ctx->wi_winner, n * sizeof(int32_t)));
+    HIPC(ctx, hipMalloc(&ctx->wi_stage, 4 * n * sizeof(float)));
+    ctx->wi_n = n;
+    return 0;
+}
+
+// both passes on the context's stream; `winner` is the plane the first pass fills (the caller's or the context's)
+template <bool PINHOLE>
+int wi_launch(rgbd360_ctx* ctx, int level, const float* pose, int method, int32_t* winner, const WarpImagesOut& out) {
+    const Level& L = ctx->levels[level];
+    const LevelDev lv = PINHOLE ? pin_level_dev(L) : level_dev(L);
+    const PinK K = PINHOLE ? pin_level_K(ctx, level) : PinK{0.f, 0.f, 0.f, 0.f};
+    Pose16 P;
+    memcpy(P.v, pose, sizeof(P.v));
+    const dim3 grid = level_pixel_grid(L, kPixelThreads);
+    HIPC(ctx, hipMemsetAsync(winner, 0xff, (size_t)L.n * sizeof(int32_t), ctx->stream));      // -1: nothing landed
+    hipLaunchKernelGGL(k_warp_winner<PINHOLE>, grid, dim3(kPixelThreads), 0, ctx->stream, lv, K, P, winner);
+    hipLaunchKernelGGL(k_warp_resolve<PINHOLE>, grid, dim3(kPixelThreads), 0, ctx->stream, lv, K, P, method, ctx->p.thres_sal_photo,
+                       (const int32_t*)winner, out);
+    HIPC(ctx, hipGetLastError());
+    return 0;
+}
+
+template <bool PINHOLE>
+int wi_host(rgbd360_ctx* ctx, int level, const float* pose, int method, float* warped_gray, float* warped_depth, float* diff_gray,
+            float* diff_depth, int32_t* winner) {
+    int rc = wi_check(ctx, level, pose, method, PINHOLE);
+    if (rc) return rc;
+    hipSetDevice(ctx->p.device);
+    if (PINHOLE && (rc = pin_prepare_level(ctx, level)) != 0) return rc;
+    if ((rc = wi_ensure(ctx)) != 0) return rc;
+    const size_t n = (size_t)ctx->levels[level].n;
+    float* const host[4] = {warped_gray, warped_depth, diff_gray, diff_depth};
+    float* dev[4];
+    for (int k = 0; k < 4; ++k) dev[k] = host[k] ? ctx->wi_stage + k * ctx->wi_n : nullptr;
+    if ((rc = wi_launch<PINHOLE>(ctx, level, pose, method, ctx->wi_winner, WarpImagesOut{dev[0], dev[1], dev[2], dev[3]})) != 0) return rc;
+    for (int k = 0; k < 4; ++k)
+        if (host[k]) HIPC(ctx, hipMemcpyAsync(host[k], dev[k], n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (winner) HIPC(ctx, hipMemcpyAsync(winner, ctx->wi_winner, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+}  // namespace
+
+extern "C" int rgbd360_warp_images(rgbd360_ctx* ctx, int level, const float pose[16], int method, float* warped_gray, float* warped_depth,
+                                   float* diff_gray, float* diff_depth, int32_t* winner) {
+    return wi_host<false>(ctx, level, pose, method, warped_gray, warped_depth, diff_gray, diff_depth, winner);
+}
+
+extern "C" int rgbd360_warp_images_pinhole(rgbd360_ctx* ctx, int level, const float pose[16], int method, float* warped_gray,
+                                           float* warped_depth, float* diff_gray, float* diff_depth, int32_t* winner) {
+    return wi_host<true>(ctx, level, pose, method, warped_gray, warped_depth, diff_gray, diff_depth, winner);
+}
+
+extern "C" int rgbd360_warp_images_dev(rgbd360_ctx* ctx, int level, const float pose[16], int method, float* warped_gray_dev,
+                                       float* warped_depth_dev, float* diff_gray_dev, float* diff_depth_dev, int32_t* winner_dev) {
+    int rc = wi_check(ctx, level, pose, method, false);
+    if (rc) return rc;
+    hipSetDevice(ctx->p.device);
+    if (!winner_dev && (rc = wi_ensure(ctx)) != 0) return rc;
+    return wi_launch<false>(ctx, level, pose, method, winner_dev ? winner_dev : ctx->wi_winner,
+                            WarpImagesOut{warped_gray_dev, warped_depth_dev, diff_gray_dev, diff_depth_dev});
+}
+
+// rgbd360_hip_diag.h: HIP-event averages over `reps` back-to-back launches of {the winner pass, the resolve pass, the whole
+// rgbd360_warp_images_dev sequence (clear + both passes), one k_warp_indices launch} on this level, outputs into the context's staging.
+extern "C" int rgbd360_time_warp_images(rgbd360_ctx* ctx, int level, const float pose[16], int method, int reps, float avg_us[4]) {
+    int rc = wi_check(ctx, level, pose, method, false);
+    if (rc) return rc;
+    if (reps < 1 || !avg_us) return fail(ctx, -1, "bad arguments");
+    hipSetDevice(ctx->p.device);
+    if ((rc = wi_ensure(ctx)) != 0) return rc;
+    const Level& L = ctx->levels[level];
+    const LevelDev lv = level_dev(L);
+    const PinK K = {0.f, 0.f, 0.f, 0.f};
+    Pose16 P;
+    memcpy(P.v, pose, sizeof(P.v));
+    const dim3 grid = level_pixel_grid(L, kPixelThreads);
+    const WarpImagesOut out = {ctx->wi_stage, ctx->wi_stage + ctx->wi_n, ctx->wi_stage + 2 * ctx->wi_n, ctx->wi_stage + 3 * ctx->wi_n};
+    int32_t* const winner = ctx->wi_winner;
+    for (int what = 0; what < 4; ++what) {
+        auto one = [&]() {
+            if (what == 0) hipLaunchKernelGGL(k_warp_winner<false>, grid, dim3(kPixelThreads), 0, ctx->stream, lv, K, P, winner);
+            if (what == 1) hipLaunchKernelGGL(k_warp_resolve<false>, grid, dim3(kPixelThreads), 0, ctx->stream, lv, K, P, method, ctx->p.thres_sal_photo, (const int32_t*)winner, out);
+            if (what == 2) (void)wi_launch<false>(ctx, level, pose, method, winner, out);
+            if (what == 3) hipLaunchKernelGGL(k_warp_indices, grid, dim3(kPixelThreads), 0, ctx->stream, lv, P, (int32_t*)ctx->wi_stage);      // 8 of the staging's 16 B/px
+        };
+        if (what == 0) HIPC(ctx, hipMemsetAsync(winner, 0xff, (size_t)L.n * sizeof(int32_t), ctx->stream));
+        one();      // warm-up
+        HIPC(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        for (int k = 0; k < reps; ++k) one();
+        HIPC(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        HIPC(ctx, hipGetLastError());
+        HIPC(ctx, hipStreamSynchronize(ctx->stream));
+        float ms = 0.f;
+        HIPC(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        avg_us[what] = ms * 1000.f / reps;
+    }
     return 0;
 }
 

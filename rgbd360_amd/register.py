@@ -359,6 +359,19 @@ class RegisterPhotoICP:
         self._check(self._L.rgbd360_warp_indices(self._ctx(), level, _ptr(pose_to_cm(pose)), _ptr(out)))
         return out
 
+    def warpImages(self, pose, method: int, level: int = 0, pinhole: bool = False) -> dict:
+        """rgbd360_warp_images / _pinhole: the source frame warped into the target frame at `pose` (warped_source_grayImage /
+        warped_source_depthImage, RPI.h:163-166) and the difference images (RPI.h:4664-4676), as rows x cols arrays of the level:
+        warped_gray, warped_depth, diff_gray, diff_depth (float32) and winner (int32: the source index that wrote the pixel, the
+        largest that landed there; -1 in holes).  A plane that does not apply to `method` is zero."""
+        r, c = self.level_dims(level)
+        out = {k: np.empty((r, c), np.float32) for k in ("warped_gray", "warped_depth", "diff_gray", "diff_depth")}
+        out["winner"] = np.empty((r, c), np.int32)
+        fn = self._L.rgbd360_warp_images_pinhole if pinhole else self._L.rgbd360_warp_images
+        self._check(fn(self._ctx(), int(level), _ptr(pose_to_cm(pose)), int(method), _ptr(out["warped_gray"]), _ptr(out["warped_depth"]),
+                       _ptr(out["diff_gray"]), _ptr(out["diff_depth"]), _ptr(out["winner"])))
+        return out
+
     def gn_step(self, H, g, lam: float, pose):
         Hc = np.ascontiguousarray(np.asarray(H, np.float32).reshape(6, 6).T.reshape(36))
         gc = np.ascontiguousarray(np.asarray(g, np.float32))
