@@ -26,6 +26,7 @@
 #include "../../include/rgbd360_hip_diag.h"
 #include "knobs.h"
 #include "host_wait.h"
+#include "dispatch.h"
 #include "photo_icp_kernels.h"
 #include "occlusion_kernels.h"
 #include "pinhole_kernels.h"
@@ -295,21 +296,6 @@ int occ_ensure(rgbd360_ctx* ctx) {
     ctx->occ_gen = 0;
     ctx->occ_n = n;
     return 0;
-}
-
-// Runtime selector -> template parameter: f is called once, with a std::integral_constant of the selected value, so that each branch
-// is a plain launch of its own instantiation.  with_method: METHOD 0 / 1 / 2 (validated by the callers; anything else runs as 2).
-// with_choice<A, B>: a two-way parameter (source form, occlusion mode, index arithmetic) -- B if `second`, else A.
-template <class F>
-void with_method(int method, F&& f) {
-    if (method == 0) f(std::integral_constant<int, 0>{});
-    else if (method == 1) f(std::integral_constant<int, 1>{});
-    else f(std::integral_constant<int, 2>{});
-}
-template <int A, int B, class F>
-void with_choice(bool second, F&& f) {
-    if (second) f(std::integral_constant<int, B>{});
-    else f(std::integral_constant<int, A>{});
 }
 
 // The head entries of the occlusion lists carry their pass's generation (1..kOccGenMax) in their top byte: one memset per kOccGenMax

@@ -2,7 +2,8 @@
 // regions with their moments, hulls and colour descriptors, the bilateral grid filter, the spherical stitcher (SURVEY.md 8 rows
 // a13-a15, 8f rank 2).  A translation unit of its own since round 6: an experiment on the alignment kernels (rgbd360_api.hip) no longer
 // rebuilds these 50 kernels and vice versa.  It sees a context only through f360_state.h: the stages' scratch lives in an F360State the
-// context owns (created on the first Frame360 call, on the context's device and stream).  No CPU fallback anywhere in this file.
+// context owns (created on the first Frame360 call, on the context's device and stream), every buffer of it an owner of its memory
+// (dev_buf.h); runtime choices reach the kernels' template parameters through dispatch.h.  No CPU fallback anywhere in this file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +18,8 @@
 #include "../../include/rgbd360_hip_diag.h"
 #include "knobs.h"
 #include "host_wait.h"
+#include "dispatch.h"
+#include "dev_buf.h"
 #include "device_math.h"
 #include "frame360_kernels.h"
 #include "pbmap_register.h"
@@ -24,49 +27,44 @@
 
 using namespace r360;
 
+constexpr int kF360MaxSlots = 4096;
+
 // What the stages keep between calls.  `ctx` in this file is an F360State: the member names are those the code used while it lived in
-// rgbd360_ctx (stream, p.device, tag, err + the f_* / b_* scratch).
+// rgbd360_ctx (stream, p.device, tag, err + the f_* / b_* scratch).  Every buffer owns its memory (dev_buf.h): the state's destructor
+// frees them, f360_ensure and the stages grow them.
 struct F360State {
     struct { int device = 0; } p;
     hipStream_t stream = nullptr;       // the owning context's stream (not owned)
     hostwait::SpinTag tag;              // pinned sequence number the stages' last kernel stores (host_wait.h); this state's own
     std::string err;                    // copied into the context's error string when an entry point returns (F360Enter)
-    // Frame360 stage scratch (normals / plane segmentation), grown on demand
-    size_t f360_n = 0;
-    float *f_xyz = nullptr, *f_normals = nullptr, *f_dist = nullptr;
-    uint8_t *f_change = nullptr, *f_hd = nullptr;
+    // Frame360 stage scratch (normals / plane segmentation), grown with the frame (f360_ensure)
+    DevBuf<float> f_xyz, f_normals, f_dist;
+    DevBuf<uint8_t> f_change, f_hd, f_depth_raw;
     f360::EdgeCloudSrc f_cloud_pending = {nullptr, 0, 0, 0, nullptr, nullptr, nullptr, nullptr};      // a sphere cloud the depth-edge kernel is to form (frame_planes)
-    int *f_label = nullptr, *f_slot_of_root = nullptr, *f_root_of_slot = nullptr, *f_nslots = nullptr, *f_window = nullptr;
-    unsigned long long *f_count = nullptr, *f_mom = nullptr;
-    int* f_count_of_slot = nullptr;
-    unsigned char *f_pack = nullptr, *f_pack_host = nullptr;      // packed region records: written by the device straight into pinned host memory (f_pack unused)
-    f360::SlotFrame* f_frames = nullptr;                          // per region slot: centroid + in-plane basis (hull stage)
-    unsigned long long* f_ext = nullptr;                          // per region slot: 256 directional extremes {ordered dot, pixel} (overflow path of the block tables)
-    int* f_hull_keys = nullptr;                                   // per block of k_f360_hull_extremes: the slots of its table rows ...
-    unsigned long long* f_hull_vals = nullptr;                    // ... and the rows (256 extremes each)
-    int f_hull_blocks = 0;
+    DevBuf<int> f_label, f_slot_of_root, f_root_of_slot, f_nslots, f_window, f_count_of_slot;
+    DevBuf<unsigned long long> f_count, f_mom;
+    PinnedBuf<unsigned char> f_pack_host{hostwait::kPublishedFlags};      // packed region records: written by the device straight into pinned host memory
+    DevBuf<f360::SlotFrame> f_frames;                             // per region slot: centroid + in-plane basis (hull stage)
+    DevBuf<unsigned long long> f_ext;                             // per region slot: 256 directional extremes {ordered dot, pixel} (overflow path of the block tables)
+    DevBuf<int> f_hull_keys;                                      // per block of k_f360_hull_extremes: the slots of its table rows ...
+    DevBuf<unsigned long long> f_hull_vals;                       // ... and the rows (256 extremes each)
     // colour image of the next plane calls (rgbd360_set_plane_color_image) and the per-region colour table (k_f360_colour)
-    uint8_t* f_col_owned = nullptr;                               // device copy of a host image
-    size_t f_col_owned_bytes = 0;
+    DevBuf<uint8_t> f_col_owned;                                  // device copy of a host image
     f360::ColourImage f_col_img = {nullptr, 0, 1};
     int f_col_rows = 0, f_col_cols = 0;                           // size of the registered image
-    unsigned long long *f_col = nullptr, *f_col_host = nullptr;   // [kF360MaxSlots][kColWords]: device table, pinned copy of the rows in use
-    int *f_samp_off = nullptr, *f_samp_n = nullptr;               // the dominant colour's samples: where a slot's start in the pool, how many arrived
-    int2* f_samp_grid = nullptr;                                  // ... and the slot's sample grid {sr, sc}
-    unsigned* f_samp_pool = nullptr;                              // one entry per pixel of the largest frame seen
-    size_t f_samp_pool_n = 0;
+    DevBuf<unsigned long long> f_col;                             // [kF360MaxSlots][kColWords]: device table ...
+    PinnedBuf<unsigned long long> f_col_host{hostwait::kPublishedFlags};      // ... and the pinned copy of the rows in use
+    DevBuf<int> f_samp_off, f_samp_n;                             // the dominant colour's samples: where a slot's start in the pool, how many arrived
+    DevBuf<int2> f_samp_grid;                                     // ... and the slot's sample grid {sr, sc}
+    DevBuf<unsigned> f_samp_pool;                                 // one entry per pixel of the largest frame seen
     bool f_col_ran = false;                                       // the last plane call filled f_col_host
-    unsigned long long* b_sum = nullptr;                          // bilateral grid: fixed-point sums, counts, two float2 ping-pong arrays
-    int* b_cnt = nullptr;
-    float2 *b_a = nullptr, *b_b = nullptr;
-    float4* f_models_host = nullptr;                              // pinned staging of the refinement's plane models
-    unsigned* b_mm = nullptr;                                     // per-block {min, max} codes of the depth range
-    unsigned* b_mm_host = nullptr;                                // ... the pair, published into pinned memory
-    size_t b_cells = 0;
-    float* f_tab = nullptr;
-    size_t f_tab_n = 0;
+    DevBuf<unsigned char> b_sum;                                  // bilateral grid: fixed-point sums, then the counts (one allocation, one memset) ...
+    DevBuf<float2> b_a, b_b;                                      // ... and two float2 ping-pong arrays
+    PinnedBuf<float4> f_models_host;                              // pinned staging of the refinement's plane models
+    DevBuf<unsigned> b_mm;                                        // per-block {min, max} codes of the depth range
+    PinnedBuf<unsigned> b_mm_host{hostwait::kPublishedFlags};     // ... the pair, published into pinned memory
+    DevBuf<float> f_tab;
     int f_tab_rows = 0, f_tab_cols = 0, f_tab_conv = -1;      // what the resident angle tables were built for
-    uint8_t* f_depth_raw = nullptr;
     // measurement (rgbd360_frame_planes_stage_timing): events on `stream` at the stage boundaries of a frame_planes call -- before the
     // cloud / depth-edge kernel, behind it (row a13), behind the normal map (a14), behind the last kernel of the plane stage (a15)
     hipEvent_t f_stage_ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -76,8 +74,8 @@ struct F360State {
     int f_refine = 0;               // segmentAndRefine's refinement after `segment` (rgbd360_set_plane_refinement)
     float f_refine_dist = 0.02f;    // PlaneRefinementComparator's default distance threshold
     int f_refine_changed = 0, f_refine_sweeps = 0;      // pixels relabelled / Jacobi sweeps of the last call
-    float4* f_models = nullptr;     // per slot {a, b, c, d} of the planes `segment` produced (x = NaN: no plane)
-    int* f_flags_host = nullptr;    // pinned, device-visible: per-sweep "something changed" flags + the relabelled-pixel counter
+    DevBuf<float4> f_models;        // per slot {a, b, c, d} of the planes `segment` produced (x = NaN: no plane)
+    PinnedBuf<int> f_flags_host{hostwait::kPublishedFlags};      // device-visible: per-sweep "something changed" flags + the relabelled-pixel counter
 };
 
 namespace {
@@ -94,7 +92,6 @@ int fail(F360State* ctx, int code, const char* msg) {
     ctx->err = msg;
     return code;
 }
-dim3 grid2d(int rows, int cols, int bx = 256) { return dim3((cols + bx - 1) / bx, rows, 1); }
 
 // Every entry point: the context's F360State (created on first use) as `ctx`; whatever error text the call leaves goes into the context
 // (rgbd360_last_error) on every return path.
@@ -126,19 +123,6 @@ F360State* f360_state_create(int device, hipStream_t stream) {
 }
 void f360_state_destroy(F360State* ctx) {
     if (!ctx) return;
-    hipFree(ctx->f_frames); hipFree(ctx->f_ext); hipFree(ctx->f_hull_keys); hipFree(ctx->f_hull_vals);
-    hipFree(ctx->f_xyz); hipFree(ctx->f_normals); hipFree(ctx->f_dist);
-    hipFree(ctx->f_change); hipFree(ctx->f_hd); hipFree(ctx->f_label); hipFree(ctx->f_count); hipFree(ctx->f_slot_of_root);
-    hipFree(ctx->f_root_of_slot); hipFree(ctx->f_nslots); hipFree(ctx->f_window); hipFree(ctx->f_mom);
-    hipFree(ctx->f_count_of_slot); hipFree(ctx->f_depth_raw); hipFree(ctx->f_pack);
-    if (ctx->f_pack_host) hipHostFree(ctx->f_pack_host);
-    hipFree(ctx->f_col_owned); hipFree(ctx->f_col); hipFree(ctx->f_samp_off); hipFree(ctx->f_samp_n); hipFree(ctx->f_samp_grid); hipFree(ctx->f_samp_pool);
-    ctx->f_samp_off = ctx->f_samp_n = nullptr; ctx->f_samp_grid = nullptr; ctx->f_samp_pool = nullptr; ctx->f_samp_pool_n = 0;
-    if (ctx->f_col_host) hipHostFree(ctx->f_col_host);
-    ctx->f_col_owned = nullptr; ctx->f_col = nullptr; ctx->f_col_host = nullptr; ctx->f_col_owned_bytes = 0;
-    hipFree(ctx->f_models);
-    if (ctx->f_flags_host) hipHostFree(ctx->f_flags_host);
-    hipFree(ctx->b_sum); hipFree(ctx->b_a); hipFree(ctx->b_b); hipFree(ctx->b_mm); if (ctx->b_mm_host) hipHostFree(ctx->b_mm_host); if (ctx->f_models_host) hipHostFree(ctx->f_models_host);
     for (hipEvent_t e : ctx->f_stage_ev)
         if (e) hipEventDestroy(e);
     hostwait::spin_tag_free(&ctx->tag);
@@ -149,45 +133,33 @@ void f360_state_destroy(F360State* ctx) {
 // Frame360 stages: normal map (row a14) and planar regions + inlier moments (row a15)
 // ---------------------------------------------------------------------------------------------------------
 namespace {
-constexpr int kF360MaxSlots = 4096;
-
+// the scratch of a frame of n pixels: every buffer and its element count (a buffer that is large enough stays as it is; the tables
+// per region slot have one size for good)
 int f360_ensure(F360State* ctx, size_t n) {
-    if (ctx->f360_n >= n) return 0;
-    hipFree(ctx->f_xyz); hipFree(ctx->f_normals); hipFree(ctx->f_dist);
-    hipFree(ctx->f_change); hipFree(ctx->f_hd); hipFree(ctx->f_label); hipFree(ctx->f_count); hipFree(ctx->f_slot_of_root);
-    hipFree(ctx->f_root_of_slot); hipFree(ctx->f_nslots); hipFree(ctx->f_window); hipFree(ctx->f_mom);
-    hipFree(ctx->f_count_of_slot); hipFree(ctx->f_depth_raw); hipFree(ctx->f_pack); hipFree(ctx->f_frames); hipFree(ctx->f_ext); hipFree(ctx->f_hull_keys); hipFree(ctx->f_hull_vals);
-    if (ctx->f_pack_host) hipHostFree(ctx->f_pack_host);
-    ctx->f_frames = nullptr; ctx->f_ext = nullptr; ctx->f_hull_keys = nullptr; ctx->f_hull_vals = nullptr;
-    ctx->f_xyz = ctx->f_normals = ctx->f_dist = nullptr;         // a failed allocation below must not leave freed pointers behind
-    ctx->f_change = nullptr; ctx->f_hd = nullptr; ctx->f_label = nullptr; ctx->f_count = nullptr; ctx->f_slot_of_root = nullptr;
-    ctx->f_root_of_slot = nullptr; ctx->f_nslots = nullptr; ctx->f_window = nullptr; ctx->f_mom = nullptr;
-    ctx->f_count_of_slot = nullptr; ctx->f_depth_raw = nullptr; ctx->f_pack = nullptr; ctx->f_pack_host = nullptr;
-    ctx->f360_n = 0;
-    HIPC(ctx, hipMalloc(&ctx->f_xyz, n * 3 * sizeof(float)));
-    HIPC(ctx, hipMalloc(&ctx->f_normals, n * 3 * sizeof(float)));
-    HIPC(ctx, hipMalloc(&ctx->f_dist, n * sizeof(float)));
-    HIPC(ctx, hipMalloc(&ctx->f_change, n));
-    HIPC(ctx, hipMalloc(&ctx->f_hd, 3 * n + 64));      // depth-change bit mask: rows x ceil(cols / 64) words <= n/8 + 8 rows bytes, cols >= 3
-    HIPC(ctx, hipMalloc(&ctx->f_label, n * sizeof(int)));
-    HIPC(ctx, hipMalloc(&ctx->f_count, n * sizeof(unsigned long long)));
-    HIPC(ctx, hipMalloc(&ctx->f_slot_of_root, n * sizeof(int)));
-    HIPC(ctx, hipMalloc(&ctx->f_window, n * sizeof(int)));
-    HIPC(ctx, hipMalloc(&ctx->f_root_of_slot, kF360MaxSlots * sizeof(int)));
-    HIPC(ctx, hipMalloc(&ctx->f_nslots, sizeof(int)));
-    HIPC(ctx, hipMalloc(&ctx->f_mom, (size_t)f360::kMomReplicas * kF360MaxSlots * 9 * sizeof(unsigned long long)      // + the per-slot maxima (mom_max_of)
-                                     + (size_t)kF360MaxSlots * sizeof(unsigned int)));
-    HIPC(ctx, hipMalloc(&ctx->f_count_of_slot, kF360MaxSlots * sizeof(int)));
+    using namespace f360;
+    const size_t hull_blocks = (n + (size_t)kHullBlock * kHullChunks - 1) / ((size_t)kHullBlock * kHullChunks);
+    HIPC(ctx, ctx->f_xyz.ensure(n * 3));
+    HIPC(ctx, ctx->f_normals.ensure(n * 3));
+    HIPC(ctx, ctx->f_dist.ensure(n));
+    HIPC(ctx, ctx->f_change.ensure(n));
+    HIPC(ctx, ctx->f_hd.ensure(3 * n + 64));       // depth-change bit mask: rows x ceil(cols / 64) words <= n/8 + 8 rows bytes, cols >= 3
+    HIPC(ctx, ctx->f_label.ensure(n));
+    HIPC(ctx, ctx->f_count.ensure(n));             // (the refinement's two work label planes later: 2 n ints)
+    HIPC(ctx, ctx->f_slot_of_root.ensure(n));
+    HIPC(ctx, ctx->f_window.ensure(n));
+    HIPC(ctx, ctx->f_hull_keys.ensure(hull_blocks * kHullHash));
+    HIPC(ctx, ctx->f_hull_vals.ensure(hull_blocks * kHullHash * kHullDirs));
+    HIPC(ctx, ctx->f_depth_raw.ensure(n * 4));
+    HIPC(ctx, ctx->f_root_of_slot.ensure(kF360MaxSlots));
+    HIPC(ctx, ctx->f_nslots.ensure(1));
+    static_assert(kF360MaxSlots * sizeof(unsigned int) % sizeof(unsigned long long) == 0, "the maxima fill whole words of f_mom");
+    HIPC(ctx, ctx->f_mom.ensure((size_t)kMomReplicas * kF360MaxSlots * 9       // + the per-slot maxima (mom_max_of), unsigned ints
+                                + (size_t)kF360MaxSlots * sizeof(unsigned int) / sizeof(unsigned long long)));
+    HIPC(ctx, ctx->f_count_of_slot.ensure(kF360MaxSlots));
     // pinned: header, one moment record per slot, one hull record per slot behind them
-    const size_t pack_bytes = f360::kF360PackHeader + (size_t)kF360MaxSlots * (sizeof(f360::F360SlotRecord) + sizeof(f360::F360HullRecord));
-    HIPC(ctx, hipHostMalloc(&ctx->f_pack_host, pack_bytes, hostwait::kPublishedFlags));
-    HIPC(ctx, hipMalloc(&ctx->f_frames, (size_t)kF360MaxSlots * sizeof(f360::SlotFrame)));
-    HIPC(ctx, hipMalloc(&ctx->f_ext, (size_t)kF360MaxSlots * f360::kHullPhases * f360::kHullDirs * sizeof(unsigned long long)));
-    ctx->f_hull_blocks = (int)((n + (size_t)f360::kHullBlock * f360::kHullChunks - 1) / ((size_t)f360::kHullBlock * f360::kHullChunks));
-    HIPC(ctx, hipMalloc(&ctx->f_hull_keys, (size_t)ctx->f_hull_blocks * f360::kHullHash * sizeof(int)));
-    HIPC(ctx, hipMalloc(&ctx->f_hull_vals, (size_t)ctx->f_hull_blocks * f360::kHullHash * f360::kHullDirs * sizeof(unsigned long long)));
-    HIPC(ctx, hipMalloc(&ctx->f_depth_raw, n * 4));
-    ctx->f360_n = n;
+    HIPC(ctx, ctx->f_pack_host.ensure(kF360PackHeader + (size_t)kF360MaxSlots * (sizeof(F360SlotRecord) + sizeof(F360HullRecord))));
+    HIPC(ctx, ctx->f_frames.ensure(kF360MaxSlots));
+    HIPC(ctx, ctx->f_ext.ensure((size_t)kF360MaxSlots * kHullPhases * kHullDirs));
     return 0;
 }
 
@@ -196,29 +168,15 @@ static void launch_distance_map(F360State* ctx, int rows, int cols, float max_de
                                 int n_clear = 0) {
     using namespace f360;
     const int pitch = (cols + 63) / 64;
-    unsigned long long* bits = reinterpret_cast<unsigned long long*>(ctx->f_hd);
+    unsigned long long* bits = reinterpret_cast<unsigned long long*>(ctx->f_hd.get());
     const dim3 ge((cols + kEdgeTW - 1) / kEdgeTW, (rows + kEdgeTH - 1) / kEdgeTH);
     if (ctx->f_cloud_pending.depth) {       // rgbd360_frame_planes: the cloud has not been formed yet -- this kernel does it on the way
         const EdgeCloudSrc& cs = ctx->f_cloud_pending;
         const int spec = (cs.convention >= 0 && cs.convention <= 2 && (cs.depth_type | 1) == 1 && (depth_mode | 1) == 1) ? cs.convention * 4 + cs.depth_type * 2 + depth_mode : -1;
-#define EDGE_CLOUD(S) hipLaunchKernelGGL((k_f360_edge_bits<true, S>), ge, dim3(kEdgeTW), 0, ctx->stream, ctx->f_xyz, rows, cols, max_depth_change_factor, depth_mode, \
-                                         pitch, bits, ctx->f_cloud_pending, ctx->f_xyz)
-        switch (spec) {
-            case 0: EDGE_CLOUD(0); break;
-            case 1: EDGE_CLOUD(1); break;
-            case 2: EDGE_CLOUD(2); break;
-            case 3: EDGE_CLOUD(3); break;
-            case 4: EDGE_CLOUD(4); break;
-            case 5: EDGE_CLOUD(5); break;
-            case 6: EDGE_CLOUD(6); break;
-            case 7: EDGE_CLOUD(7); break;
-            case 8: EDGE_CLOUD(8); break;
-            case 9: EDGE_CLOUD(9); break;
-            case 10: EDGE_CLOUD(10); break;
-            case 11: EDGE_CLOUD(11); break;
-            default: EDGE_CLOUD(-1); break;
-        }
-#undef EDGE_CLOUD
+        with_int<-1, 11>(spec, [&](auto S) {
+            hipLaunchKernelGGL((k_f360_edge_bits<true, S>), ge, dim3(kEdgeTW), 0, ctx->stream, ctx->f_xyz, rows, cols, max_depth_change_factor, depth_mode,
+                               pitch, bits, ctx->f_cloud_pending, ctx->f_xyz);
+        });
         ctx->f_cloud_pending.depth = nullptr;
     } else {
         hipLaunchKernelGGL((k_f360_edge_bits<false>), ge, dim3(kEdgeTW), 0, ctx->stream, ctx->f_xyz, rows, cols, max_depth_change_factor, depth_mode,
@@ -232,6 +190,7 @@ static void launch_distance_map(F360State* ctx, int rows, int cols, float max_de
 // normals of the organised cloud in ctx->f_xyz -> ctx->f_normals (device)
 int f360_normals_dev(F360State* ctx, int rows, int cols, float max_depth_change_factor, float smoothing_size, int depth_mode) {
     using namespace f360;
+    // (the upper bound leaves smoothing_size <= 9.5: the widest sweep window is R = 9, and no k_f360_normals_sweep<10> is built)
     if (smoothing_size < 1.f || smoothing_size + 2.5f > (float)kF360R)
         return fail(ctx, -1, "normal_smoothing_size out of range (the distance map is truncated at 12 px)");
     const dim3 gt((cols + kNT_W - 1) / kNT_W, (rows + kNT_H - 1) / kNT_H);
@@ -239,12 +198,12 @@ int f360_normals_dev(F360State* ctx, int rows, int cols, float max_depth_change_
     // for the 32 x 16 tiles the sweep lists (depth edges, far points).  Claim flags + tile list: the first bytes of f_change, which the
     // distance map does not touch (the plane stage rewrites it); the distance-map kernel clears them on its way.
     const int R = (int)smoothing_size;
-    const bool use_sweep = R >= 3 && R <= 10 && ((size_t)gt.x * gt.y * 2 + 2) * sizeof(unsigned) <= (size_t)rows * cols &&
+    const bool use_sweep = R >= 3 && R <= 9 && ((size_t)gt.x * gt.y * 2 + 2) * sizeof(unsigned) <= (size_t)rows * cols &&
                            (size_t)rows * cols * 12 < ((size_t)1 << 31);      // the sweep addresses its rows with 32-bit buffer offsets
     const int n_tiles = (int)(gt.x * gt.y);
     unsigned *flags = nullptr, *list = nullptr;            // {claimed flag per tile}, {count, tile ids ...}
     if (use_sweep) {
-        flags = reinterpret_cast<unsigned*>(ctx->f_change);
+        flags = reinterpret_cast<unsigned*>(ctx->f_change.get());
         list = flags + n_tiles;
     }
     launch_distance_map(ctx, rows, cols, max_depth_change_factor, depth_mode, flags, use_sweep ? n_tiles + 1 : 0);
@@ -268,18 +227,10 @@ int f360_normals_dev(F360State* ctx, int rows, int cols, float max_depth_change_
         const dim3 gs((units + kSweepWaves - 1) / kSweepWaves), bs(64 * kSweepWaves);
         // (no window plane: nothing downstream reads the per-pixel window size -- it was a 4 B/px store of both normal-map kernels,
         // 33 MB at 4096 x 2048, kept from the days the two kernels were compared through it; round 6)
-#define SWEEP(RR) hipLaunchKernelGGL((k_f360_normals_sweep<RR>), gs, bs, 0, ctx->stream, ctx->f_xyz, ctx->f_dist, rows, cols, smoothing_size, depth_mode, seg, ctx->f_normals, (int*)nullptr, flags, list, (int)gt.x)
-        switch (R) {
-            case 3: SWEEP(3); break;
-            case 4: SWEEP(4); break;
-            case 5: SWEEP(5); break;
-            case 6: SWEEP(6); break;
-            case 7: SWEEP(7); break;
-            case 8: SWEEP(8); break;
-            case 9: SWEEP(9); break;
-            default: SWEEP(10); break;
-        }
-#undef SWEEP
+        with_int<3, 9>(R, [&](auto RR) {
+            hipLaunchKernelGGL((k_f360_normals_sweep<RR>), gs, bs, 0, ctx->stream, ctx->f_xyz, ctx->f_dist, rows, cols, smoothing_size, depth_mode, seg,
+                               ctx->f_normals, (int*)nullptr, flags, list, (int)gt.x);
+        });
     }
     // two tiles fit a CU: 512 blocks walk the sweep's list (every tile of the frame when there was no sweep)
     hipLaunchKernelGGL(k_f360_normals_tiled, dim3(list ? std::min(n_tiles, 512) : n_tiles), dim3(kNT_THREADS), 0, ctx->stream, ctx->f_xyz,
@@ -296,15 +247,15 @@ int f360_bilateral_dev(F360State* ctx, int rows, int cols, float sigma_s, float 
     if (!(sigma_s > 0.f) || !(sigma_r > 0.f)) return fail(ctx, -1, "sigma_s and sigma_r must be positive");
     const int n = rows * cols;
     constexpr int kMmBlocks = 64;
-    if (!ctx->b_mm) HIPC(ctx, hipMalloc(&ctx->b_mm, 2 * kMmBlocks * sizeof(unsigned)));
-    if (!ctx->b_mm_host) HIPC(ctx, hipHostMalloc((void**)&ctx->b_mm_host, 2 * sizeof(unsigned), hostwait::kPublishedFlags));
+    HIPC(ctx, ctx->b_mm.ensure(2 * kMmBlocks));
+    HIPC(ctx, ctx->b_mm_host.ensure(2));
     // the depth range: per-block pairs, folded and published by a one-wave kernel; the host spins on the tag (no memset, copy or stream synchronise)
     const int mm_blocks = std::min(kMmBlocks, (n + 4 * kBilatMmThreads - 1) / (4 * kBilatMmThreads));
     hipLaunchKernelGGL(k_bilat_minmax, dim3(mm_blocks), dim3(kBilatMmThreads), 0, ctx->stream, ctx->f_xyz, n, ctx->b_mm);
     hipLaunchKernelGGL(k_bilat_minmax_publish, dim3(1), dim3(64), 0, ctx->stream, ctx->b_mm, mm_blocks, ctx->b_mm_host, ctx->tag.h, ++ctx->tag.seq);
     HIPC(ctx, hipGetLastError());
     HIPC(ctx, hostwait::wait(ctx->tag, ctx->stream));
-    const unsigned mm[2] = {reinterpret_cast<const volatile unsigned*>(ctx->b_mm_host)[0], reinterpret_cast<const volatile unsigned*>(ctx->b_mm_host)[1]};
+    const unsigned mm[2] = {reinterpret_cast<const volatile unsigned*>(ctx->b_mm_host.get())[0], reinterpret_cast<const volatile unsigned*>(ctx->b_mm_host.get())[1]};
     if (mm[0] > mm[1]) return 0;                                   // no finite z: the cloud stays as it is
     auto decode = [](unsigned e) {
         const unsigned u = (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e;
@@ -323,20 +274,15 @@ int f360_bilateral_dev(F360State* ctx, int rows, int cols, float sigma_s, float 
     if (!(cells_d < 64e6)) return fail(ctx, -1, "bilateral grid too large (depth range / sigma_r)");
     g.nz = (int)(base_delta / sigma_r) + 1 + 2 * kBilatPadZ;
     const size_t cells = (size_t)g.nx * g.ny * g.nz;
-    if (ctx->b_cells < cells) {
-        hipFree(ctx->b_sum); hipFree(ctx->b_a); hipFree(ctx->b_b);
-        ctx->b_sum = nullptr; ctx->b_cnt = nullptr; ctx->b_a = ctx->b_b = nullptr; ctx->b_cells = 0;
-        HIPC(ctx, hipMalloc(&ctx->b_sum, cells * (sizeof(unsigned long long) + sizeof(int))));      // sums, then counts: one allocation, one memset
-        ctx->b_cnt = reinterpret_cast<int*>(ctx->b_sum + cells);
-        HIPC(ctx, hipMalloc(&ctx->b_a, cells * sizeof(float2)));
-        HIPC(ctx, hipMalloc(&ctx->b_b, cells * sizeof(float2)));
-        ctx->b_cells = cells;
-    }
-    ctx->b_cnt = reinterpret_cast<int*>(ctx->b_sum + cells);      // (behind THIS call's cells: the buffer may be larger)
-    HIPC(ctx, hipMemsetAsync(ctx->b_sum, 0, cells * (sizeof(unsigned long long) + sizeof(int)), ctx->stream));
+    HIPC(ctx, ctx->b_sum.ensure(cells * (sizeof(unsigned long long) + sizeof(int))));      // sums, then counts: one allocation, one memset
+    HIPC(ctx, ctx->b_a.ensure(cells));
+    HIPC(ctx, ctx->b_b.ensure(cells));
+    unsigned long long* b_sum = reinterpret_cast<unsigned long long*>(ctx->b_sum.get());
+    int* b_cnt = reinterpret_cast<int*>(b_sum + cells);      // (behind THIS call's cells: the buffer may be larger)
+    HIPC(ctx, hipMemsetAsync(b_sum, 0, cells * (sizeof(unsigned long long) + sizeof(int)), ctx->stream));
     const dim3 gp((n + 255) / 256), gc((unsigned)((cells + 255) / 256)), b(256);
-    hipLaunchKernelGGL(k_bilat_scatter, gp, b, 0, ctx->stream, ctx->f_xyz, rows, cols, g, ctx->b_sum, ctx->b_cnt);
-    hipLaunchKernelGGL(k_bilat_init, gc, b, 0, ctx->stream, ctx->b_sum, ctx->b_cnt, cells, ctx->b_a, ctx->b_b);
+    hipLaunchKernelGGL(k_bilat_scatter, gp, b, 0, ctx->stream, ctx->f_xyz, rows, cols, g, b_sum, b_cnt);
+    hipLaunchKernelGGL(k_bilat_init, gc, b, 0, ctx->stream, b_sum, b_cnt, cells, ctx->b_a, ctx->b_b);
     float2 *data = ctx->b_a, *buffer = ctx->b_b;
     const int offs[3] = {g.ny * g.nz, g.nz, 1};
     for (int dim = 0; dim < 3; ++dim)
@@ -455,23 +401,24 @@ void apply_hull(rgbd360_plane& P, const f360::F360HullRecord& R) {
 const f360::F360HullRecord* hull_records(const F360State* ctx) {
     return reinterpret_cast<const f360::F360HullRecord*>(ctx->f_pack_host + f360::kF360PackHeader + (size_t)kF360MaxSlots * sizeof(f360::F360SlotRecord));
 }
+// ... and its moment records, behind the header (read after the wait that follows the kernels which wrote them)
+const f360::F360SlotRecord* slot_records(const F360State* ctx) {
+    return reinterpret_cast<const f360::F360SlotRecord*>(ctx->f_pack_host + f360::kF360PackHeader);
+}
 // the extremes of the CURRENT labels (ctx->f_label) against the frames of the slots, packed for the host; enqueued on the stream
 int launch_hull(F360State* ctx, int rows, int cols, bool clear_first) {
     using namespace f360;
     const int n = rows * cols;
     if (clear_first) hipLaunchKernelGGL(k_f360_hull_clear, dim3((kF360MaxSlots * kHullPhases * kHullDirs + 255) / 256), dim3(256), 0, ctx->stream, ctx->f_nslots, kF360MaxSlots, ctx->f_ext);
-    const int nblk = (n + kHullBlock * kHullChunks - 1) / (kHullBlock * kHullChunks);      // <= ctx->f_hull_blocks (sized for the context's largest frame)
+    const int nblk = (n + kHullBlock * kHullChunks - 1) / (kHullBlock * kHullChunks);      // (f_hull_keys / f_hull_vals hold the rows of the context's largest frame)
     static const int n_cus = [] {
         int dev = 0, v = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         return v;
     }();
-    if (nblk > n_cus)        // more blocks than CUs: the two-per-CU build of the kernel
-        hipLaunchKernelGGL(k_f360_hull_extremes_two, dim3(nblk), dim3(kHullBlock), 0, ctx->stream, ctx->f_xyz, ctx->f_label, ctx->f_slot_of_root, rows, cols,
-                           ctx->f_frames, ctx->f_ext, ctx->f_hull_keys, ctx->f_hull_vals, kHullFramesLds);
-    else
-        hipLaunchKernelGGL(k_f360_hull_extremes, dim3(nblk), dim3(kHullBlock), 0, ctx->stream, ctx->f_xyz, ctx->f_label, ctx->f_slot_of_root, rows, cols,
-                           ctx->f_frames, ctx->f_ext, ctx->f_hull_keys, ctx->f_hull_vals, kHullFramesLds);
+    const auto extremes = nblk > n_cus ? k_f360_hull_extremes_two : k_f360_hull_extremes;       // more blocks than CUs: the two-per-CU build of the kernel
+    hipLaunchKernelGGL(extremes, dim3(nblk), dim3(kHullBlock), 0, ctx->stream, ctx->f_xyz, ctx->f_label, ctx->f_slot_of_root, rows, cols,
+                       ctx->f_frames, ctx->f_ext, ctx->f_hull_keys, ctx->f_hull_vals, kHullFramesLds);
     hipLaunchKernelGGL(k_f360_hull_merge, dim3(64, kHullMergeSplit), dim3(kHullDirs), 0, ctx->stream, ctx->f_nslots, kF360MaxSlots, ctx->f_hull_keys, ctx->f_hull_vals,
                        nblk, ctx->f_ext);
     hipLaunchKernelGGL(k_f360_hull_pack, dim3(256), dim3(kHullDirs), 0, ctx->stream, ctx->f_xyz, ctx->f_frames, ctx->f_ext, ctx->f_nslots, kF360MaxSlots,
@@ -490,6 +437,37 @@ void sorted_eigen3(const double C[3][3], double evals[3], double evecs[3][3]) { 
         for (int i = 0; i < 3; ++i) evecs[k][i] = V[i][o[k]];
     }
 }
+// What a region's exact sums say about it (float64): centroid, covariance, its eigenpairs in ascending order -- evecs[0] is the plane
+// normal -- and the extent descriptors of rgbd360_hip.h from the two in-plane moments.
+struct RegionFit {
+    double c[3], C[3][3], evals[3], evecs[3][3];
+    float area_moment, elongation, ppal_dir[3];
+};
+RegionFit region_fit(const f360::F360SlotRecord& R) {
+    RegionFit f;
+    double m[9];
+    for (int q = 0; q < 9; ++q) m[q] = (double)(long long)R.mom[q] / f360::kMomScale;      // fixed point -> metres
+    const double N = R.count;
+    const double cx = m[0] / N, cy = m[1] / N, cz = m[2] / N;
+    const double C[3][3] = {{m[3] / N - cx * cx, m[4] / N - cx * cy, m[5] / N - cx * cz},
+                            {m[4] / N - cx * cy, m[6] / N - cy * cy, m[7] / N - cy * cz},
+                            {m[5] / N - cx * cz, m[7] / N - cy * cz, m[8] / N - cz * cz}};
+    f.c[0] = cx; f.c[1] = cy; f.c[2] = cz;
+    memcpy(f.C, C, sizeof(C));
+    sorted_eigen3(C, f.evals, f.evecs);
+    const double l1 = std::max(f.evals[1], 0.0), l2 = std::max(f.evals[2], 0.0);    // in-plane moments
+    f.area_moment = (float)(12.0 * sqrt(l1 * l2));
+    f.elongation = (float)(l1 > 0 ? sqrt(l2 / l1) : INFINITY);
+    for (int q = 0; q < 3; ++q) f.ppal_dir[q] = (float)f.evecs[2][q];
+    return f;
+}
+// ... into the plane record (f360_planes_dev for the regions of `segment`, f360_refine_dev again for the grown inlier sets)
+void apply_extent(rgbd360_plane& P, const RegionFit& f, int count) {
+    P.count = count;
+    P.area_moment = f.area_moment;
+    P.elongation = f.elongation;
+    for (int q = 0; q < 3; ++q) P.ppal_dir[q] = f.ppal_dir[q];
+}
 
 // Colour descriptors of the regions in their slots (k_f360_colour over the CURRENT labels), enqueued on the stream: the table rows in
 // use land in pinned host memory.  Only when a colour image of this cloud's geometry is registered.
@@ -498,21 +476,12 @@ bool launch_colour(F360State* ctx, int rows, int cols) {
     ctx->f_col_ran = false;
     const ColourImage& im = ctx->f_col_img;
     if (!im.rgb || im.sub < 1 || ctx->f_col_rows / im.sub != rows || ctx->f_col_cols / im.sub != cols) return false;
-    const size_t bytes = (size_t)kF360MaxSlots * kColWords * sizeof(unsigned long long);
-    if (!ctx->f_col && hipMalloc(&ctx->f_col, bytes) != hipSuccess) return false;
-    if (!ctx->f_col_host && hipHostMalloc((void**)&ctx->f_col_host, bytes, hostwait::kPublishedFlags) != hipSuccess) return false;
     const int n = rows * cols;
-    // the dominant colour's sample pool (one entry per pixel bounds the sum of min(count, kModeCap) over the regions)
-    if (!ctx->f_samp_off && hipMalloc(&ctx->f_samp_off, kF360MaxSlots * sizeof(int)) != hipSuccess) return false;
-    if (!ctx->f_samp_n && hipMalloc(&ctx->f_samp_n, kF360MaxSlots * sizeof(int)) != hipSuccess) return false;
-    if (!ctx->f_samp_grid && hipMalloc(&ctx->f_samp_grid, kF360MaxSlots * sizeof(int2)) != hipSuccess) return false;
-    if (ctx->f_samp_pool_n < (size_t)n) {
-        hipFree(ctx->f_samp_pool);
-        ctx->f_samp_pool = nullptr;
-        ctx->f_samp_pool_n = 0;
-        if (hipMalloc(&ctx->f_samp_pool, (size_t)n * sizeof(unsigned)) != hipSuccess) return false;
-        ctx->f_samp_pool_n = (size_t)n;
-    }
+    // the table, its pinned copy, and the dominant colour's sample pool (one entry per pixel bounds the sum of min(count, kModeCap) over the regions)
+    const size_t words = (size_t)kF360MaxSlots * kColWords;
+    if (ctx->f_col.ensure(words) != hipSuccess || ctx->f_col_host.ensure(words) != hipSuccess || ctx->f_samp_off.ensure(kF360MaxSlots) != hipSuccess ||
+        ctx->f_samp_n.ensure(kF360MaxSlots) != hipSuccess || ctx->f_samp_grid.ensure(kF360MaxSlots) != hipSuccess || ctx->f_samp_pool.ensure((size_t)n) != hipSuccess)
+        return false;
     const ColourSamples smp = {ctx->f_count_of_slot, ctx->f_samp_off, ctx->f_samp_n, ctx->f_samp_grid, ctx->f_samp_pool};
     hipLaunchKernelGGL(k_f360_colour_offsets, dim3(1), dim3(1024), 0, ctx->stream, ctx->f_nslots, kF360MaxSlots, ctx->f_count_of_slot, ctx->f_samp_off, ctx->f_samp_n,
                        ctx->f_samp_grid, ctx->f_col);
@@ -563,13 +532,13 @@ void apply_colour(const F360State* ctx, rgbd360_plane& P, int slot) {
 int f360_refine_dev(F360State* ctx, int rows, int cols, int nslots, std::vector<rgbd360_plane>& planes, const std::vector<int>& plane_slot) {
     using namespace f360;
     const int n = rows * cols;
-    if (!ctx->f_models) HIPC(ctx, hipMalloc(&ctx->f_models, (kF360MaxSlots + 1) * sizeof(float4)));      // + one slot: the relabelled-pixel counter
+    HIPC(ctx, ctx->f_models.ensure(kF360MaxSlots + 1));      // + one slot: the relabelled-pixel counter
     int* d_changed = reinterpret_cast<int*>(ctx->f_models + kF360MaxSlots);     // (device memory: 166 k atomics into pinned host memory took 8 ms)
     int* d_activity = d_changed + 1;                                            // bumped by every relaxation step that changed a label
     constexpr int kFlags = 64;
-    if (!ctx->f_flags_host) HIPC(ctx, hipHostMalloc((void**)&ctx->f_flags_host, (kFlags + 1) * sizeof(int), hostwait::kPublishedFlags));
+    HIPC(ctx, ctx->f_flags_host.ensure(kFlags + 1));
     // (the plane models go up from a pinned buffer: a copy out of pageable memory is staged by the runtime)
-    if (!ctx->f_models_host) HIPC(ctx, hipHostMalloc((void**)&ctx->f_models_host, kF360MaxSlots * sizeof(float4), 0));
+    HIPC(ctx, ctx->f_models_host.ensure(kF360MaxSlots));
     float4* models = ctx->f_models_host;
     for (int s2 = 0; s2 < nslots; ++s2) models[s2] = make_float4(NAN, 0.f, 0.f, 0.f);
     for (size_t k = 0; k < planes.size(); ++k)
@@ -577,9 +546,9 @@ int f360_refine_dev(F360State* ctx, int rows, int cols, int nslots, std::vector<
     HIPC(ctx, hipMemcpyAsync(ctx->f_models, models, (size_t)nslots * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
     // work labels (plane slot / -1 invalid / -2 free): the two halves of f_count (its counts are spent once the slots are assigned) and
     // f_window (only live during the normal-map stage); tile flags: the first bytes of f_dist (normal-map stage only)
-    int* w[3] = {reinterpret_cast<int*>(ctx->f_count), reinterpret_cast<int*>(ctx->f_count) + n, ctx->f_window};
+    int* w[3] = {reinterpret_cast<int*>(ctx->f_count.get()), reinterpret_cast<int*>(ctx->f_count.get()) + n, ctx->f_window};
     const int tiles_y = (rows + kRefTH - 1) / kRefTH, tiles_x = (cols + 63) / 64;
-    unsigned char* tile_free = reinterpret_cast<unsigned char*>(ctx->f_dist);
+    unsigned char* tile_free = reinterpret_cast<unsigned char*>(ctx->f_dist.get());
     HIPC(ctx, hipMemsetAsync(tile_free, 0, (size_t)tiles_x * tiles_y, ctx->stream));
     // X (w[1]) starts as the pass labels (written by the same launch) and is relaxed in place; pass 2 starts from a copy of pass 1's result (w[2])
     hipLaunchKernelGGL(k_f360_refine_init, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->f_label, ctx->f_slot_of_root, ctx->f_models, n, cols, tiles_x,
@@ -603,14 +572,12 @@ int f360_refine_dev(F360State* ctx, int rows, int cols, int nslots, std::vector<
             volatile int* flags = ctx->f_flags_host;
             for (int k = 0; k < kPerCheck; ++k) flags[k] = 0;
             for (int k = 0; k < kPerCheck; ++k) {
-#define REFINE_TILE(P, L) hipLaunchKernelGGL((k_f360_refine_tile<P, L>), g, b, lds_bytes, ctx->stream, ctx->f_xyz, W0, w[1], ctx->f_models, ctx->f_refine_dist, rows, cols, \
-                                             tiles_y, tile_free, ctx->f_flags_host + k, d_activity, kPolls, kQuiet, n_lds)
-                if (pass == 1) {
-                    if (n_lds > 0) REFINE_TILE(1, true); else REFINE_TILE(1, false);
-                } else {
-                    if (n_lds > 0) REFINE_TILE(2, true); else REFINE_TILE(2, false);
-                }
-#undef REFINE_TILE
+                with_choice<1, 2>(pass == 2, [&](auto P) {
+                    with_choice<0, 1>(n_lds > 0, [&](auto L) {
+                        hipLaunchKernelGGL((k_f360_refine_tile<P, decltype(L)::value != 0>), g, b, lds_bytes, ctx->stream, ctx->f_xyz, W0, w[1], ctx->f_models, ctx->f_refine_dist,
+                                           rows, cols, tiles_y, tile_free, ctx->f_flags_host + k, d_activity, kPolls, kQuiet, n_lds);
+                    });
+                });
                 ++sweeps;
             }
             HIPC(ctx, hipGetLastError());
@@ -648,27 +615,14 @@ int f360_refine_dev(F360State* ctx, int rows, int cols, int nslots, std::vector<
     ctx->f_refine_sweeps = sweeps;
     // count and the extent descriptors of the grown inlier sets (Frame360.h:1010-1037 derives them from the refined inlier cloud);
     // centroid / normal / d / curvature stay those of `segment`, as PCL's PlanarRegion keeps them
-    const F360SlotRecord* recs = reinterpret_cast<const F360SlotRecord*>(ctx->f_pack_host + kF360PackHeader);
+    const F360SlotRecord* recs = slot_records(ctx);
     for (size_t k = 0; k < planes.size(); ++k)          // the grown inlier sets against the same a-priori bound as the segment's
         if (!f360_mom_in_range(recs[plane_slot[k]].count, recs[plane_slot[k]].max_abs))
             return fail(ctx, -8, "region moments out of range (N max(|x|,|y|,|z|)^2 >= 3.4e10 m^2, or a point beyond 2896 m)");
     for (size_t k = 0; k < planes.size(); ++k) {
         const F360SlotRecord& R = recs[plane_slot[k]];
-        double m[9];
-        for (int q = 0; q < 9; ++q) m[q] = (double)(long long)R.mom[q] / kMomScale;
-        const double N = R.count;
-        const double cx = m[0] / N, cy = m[1] / N, cz = m[2] / N;
-        const double C[3][3] = {{m[3] / N - cx * cx, m[4] / N - cx * cy, m[5] / N - cx * cz},
-                                {m[4] / N - cx * cy, m[6] / N - cy * cy, m[7] / N - cy * cz},
-                                {m[5] / N - cx * cz, m[7] / N - cy * cz, m[8] / N - cz * cz}};
-        double evs[3], vecs[3][3];
-        sorted_eigen3(C, evs, vecs);
         rgbd360_plane& P = planes[k];
-        P.count = R.count;
-        const double l1 = std::max(evs[1], 0.0), l2 = std::max(evs[2], 0.0);
-        P.area_moment = (float)(12.0 * sqrt(l1 * l2));
-        P.elongation = (float)(l1 > 0 ? sqrt(l2 / l1) : INFINITY);
-        for (int q = 0; q < 3; ++q) P.ppal_dir[q] = (float)vecs[2][q];
+        apply_extent(P, region_fit(R), R.count);
         apply_hull(P, hull_records(ctx)[plane_slot[k]]);
         apply_colour(ctx, P, plane_slot[k]);
     }
@@ -694,10 +648,9 @@ int f360_planes_dev(F360State* ctx, int rows, int cols, int min_inliers, float a
                            flags, rows, cols, ctx->f_label, run_starts, n_run_starts);
     {
         const dim3 gb((cols + kBandCols - 1) / kBandCols, (rows + kBandRows - 1) / kBandRows);
-        if (kBandGroupsMax >= 16 && gb.x * gb.y >= 1536)
-            hipLaunchKernelGGL((k_f360_ccl_merge_band<kBandGroupsMax / 2>), gb, dim3(kBandCols * (kBandGroupsMax / 2)), 0, ctx->stream, flags, rows, cols, ctx->f_label);
-        else
-            hipLaunchKernelGGL((k_f360_ccl_merge_band<kBandGroupsMax>), gb, dim3(kBandCols * kBandGroupsMax), 0, ctx->stream, flags, rows, cols, ctx->f_label);
+        with_choice<kBandGroupsMax, kBandGroupsMax / 2>(kBandGroupsMax >= 16 && gb.x * gb.y >= 1536, [&](auto G) {
+            hipLaunchKernelGGL((k_f360_ccl_merge_band<G>), gb, dim3(kBandCols * G), 0, ctx->stream, flags, rows, cols, ctx->f_label);
+        });
     }
     constexpr int kTopLevel = kBandRows == 64 ? kBandLevels : kBandLevels + 2;      // 64-row bands: every 64th row in one launch behind them
     for (int level = kBandLevels; level <= kTopLevel && (1 << level) < rows; ++level) {
@@ -752,24 +705,18 @@ int f360_planes_dev(F360State* ctx, int rows, int cols, int min_inliers, float a
     // one tag kernel behind the chain + a host spin (~10 us less than hipStreamSynchronize, host_wait.h).  Until round 5 the chain's last
     // kernel published the tag from its last block: 256 blocks x a system-scope fence cost 10-22 us more than this launch.
     HIPC(ctx, hostwait::tag_and_wait(ctx->tag, ctx->stream));
-    const int nslots = *reinterpret_cast<const volatile int*>(ctx->f_pack_host);
+    const int nslots = *reinterpret_cast<const volatile int*>(ctx->f_pack_host.get());
     ctx->f_planes_ran = true;
     if (nslots > kF360MaxSlots) return fail(ctx, -7, "more than 4096 regions exceed min_inliers");
-    const F360SlotRecord* recs = reinterpret_cast<const F360SlotRecord*>(ctx->f_pack_host + kF360PackHeader);
-    std::vector<int> roots(nslots), counts(nslots);
-    std::vector<double> mom((size_t)nslots * 9);
-    for (int s = 0; s < nslots; ++s) {
-        // the fixed-point sums are exact only inside their range (frame360_kernels.h, kMomScale): refused a priori, from the
-        // region's count and largest coordinate, before any sum is decoded -- a wrapped sum can look as plausible as a right one
+    const F360SlotRecord* recs = slot_records(ctx);
+    // the fixed-point sums are exact only inside their range (frame360_kernels.h, kMomScale): refused a priori, from the
+    // region's count and largest coordinate, before any sum is decoded -- a wrapped sum can look as plausible as a right one
+    for (int s = 0; s < nslots; ++s)
         if (!f360_mom_in_range(recs[s].count, recs[s].max_abs))
             return fail(ctx, -8, "region moments out of range (N max(|x|,|y|,|z|)^2 >= 3.4e10 m^2, or a point beyond 2896 m)");
-        roots[s] = recs[s].root;
-        counts[s] = recs[s].count;
-        for (int k = 0; k < 9; ++k) mom[(size_t)s * 9 + k] = (double)(long long)recs[s].mom[k] / kMomScale;     // fixed point -> metres
-    }
     std::vector<int> order(nslots);
     for (int s = 0; s < nslots; ++s) order[s] = s;
-    std::sort(order.begin(), order.end(), [&](int a, int c) { return roots[a] < roots[c]; });   // PCL's order: by first pixel
+    std::sort(order.begin(), order.end(), [&](int a, int c) { return recs[a].root < recs[c].root; });   // PCL's order: by first pixel
     // Planes are built for every region first: when more than max_planes pass the curvature filter the LARGEST ones are kept
     // (still in PCL's order) instead of the first -- the regions lowest in the image (typically the floor) used to be the ones
     // cut -- and the total is remembered for rgbd360_planes_available so that an adapter can grow its buffer and call again.
@@ -778,22 +725,16 @@ int f360_planes_dev(F360State* ctx, int rows, int cols, int min_inliers, float a
     all.reserve(nslots);
     for (int oi = 0; oi < nslots; ++oi) {
         const int s = order[oi];
-        const double* m = &mom[(size_t)s * 9];
-        const double N = counts[s];
-        const double cx = m[0] / N, cy = m[1] / N, cz = m[2] / N;
-        const double C[3][3] = {{m[3] / N - cx * cx, m[4] / N - cx * cy, m[5] / N - cx * cz},
-                                {m[4] / N - cx * cy, m[6] / N - cy * cy, m[7] / N - cy * cz},
-                                {m[5] / N - cx * cz, m[7] / N - cy * cz, m[8] / N - cz * cz}};
-        double evs[3], vecs[3][3];
-        sorted_eigen3(C, evs, vecs);
-        const double ev = evs[0];
-        double* v = vecs[0];
+        RegionFit f = region_fit(recs[s]);
+        const double cx = f.c[0], cy = f.c[1], cz = f.c[2];
+        const double ev = f.evals[0];
+        double* v = f.evecs[0];
         double d = -(v[0] * cx + v[1] * cy + v[2] * cz);
         if ((-cx) * v[0] + (-cy) * v[1] + (-cz) * v[2] < 0) {     // orient towards the viewpoint (origin)
             v[0] = -v[0]; v[1] = -v[1]; v[2] = -v[2];
             d = -(v[0] * cx + v[1] * cy + v[2] * cz);
         }
-        const double tr = C[0][0] + C[1][1] + C[2][2];
+        const double tr = f.C[0][0] + f.C[1][1] + f.C[2][2];
         const double curvature = tr != 0 ? fabs(ev / tr) : 0;
         if (!(curvature < max_curvature)) continue;
         all.emplace_back();
@@ -803,12 +744,8 @@ int f360_planes_dev(F360State* ctx, int rows, int cols, int min_inliers, float a
         P.normal[0] = (float)v[0]; P.normal[1] = (float)v[1]; P.normal[2] = (float)v[2];
         P.d = (float)d;
         P.curvature = (float)curvature;
-        P.count = counts[s];
-        P.root = roots[s];
-        const double l1 = std::max(evs[1], 0.0), l2 = std::max(evs[2], 0.0);    // in-plane moments (rgbd360_hip.h)
-        P.area_moment = (float)(12.0 * sqrt(l1 * l2));
-        P.elongation = (float)(l1 > 0 ? sqrt(l2 / l1) : INFINITY);
-        for (int k = 0; k < 3; ++k) P.ppal_dir[k] = (float)vecs[2][k];
+        P.root = recs[s].root;
+        apply_extent(P, f, recs[s].count);
         apply_colour(ctx, P, s);      // (with the refinement on: empty here, filled by f360_refine_dev below)
         if (!ctx->f_refine) apply_hull(P, hull_records(ctx)[s]);
         else {                   // filled by f360_refine_dev below
@@ -846,66 +783,54 @@ int f360_planes_dev(F360State* ctx, int rows, int cols, int min_inliers, float a
 int sphere_cloud_dev(F360State* ctx, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
                      bool depth_on_device = false, bool defer_to_edge_kernel = false) {
     if (convention < 0 || convention > 2 || (depth_type != 0 && depth_type != 1)) return fail(ctx, -1, "bad arguments");
-    const bool tables_resident = ctx->f_tab && ctx->f_tab_rows == rows && ctx->f_tab_cols == cols && ctx->f_tab_conv == convention;
-    std::vector<float> st(cols), ct(cols), sp(rows), cp(rows);
-    if (tables_resident) {          // the angle tables of this geometry are already on the device
-    } else if (convention == 0) {   // Frame360.h:562-585
-        const float angle_pixel(cols / (2 * kPI));
-        const float angle_pixel_inv(1 / angle_pixel);
-        const float offset_phi = kPI * 31.5 / 180;
-        for (int r = 0; r < rows; ++r) {
-            float phi_i = offset_phi - r * angle_pixel_inv;
-            sp[r] = sinf(phi_i);
-            cp[r] = cosf(phi_i);
-        }
-        for (int c = 0; c < cols; ++c) {
-            float theta_i = c * angle_pixel_inv;
-            st[c] = sinf(theta_i);
-            ct[c] = cosf(theta_i);
-        }
-    } else if (convention == 1) {   // Frame360_stereo.h:470-490
-        const float step_theta = 2 * kPI / cols;
-        const float step_phi = step_theta;
-        const int start_phi = 166;
-        for (int r = 0; r < rows; ++r) {
-            float phi = (r + start_phi) * step_phi - kPI / 2;
-            cp[r] = cosf(phi);
-            sp[r] = sinf(phi);
-        }
-        for (int c = 0; c < cols; ++c) {
-            float theta = c * step_theta - kPI;
-            st[c] = sinf(theta);
-            ct[c] = cosf(theta);
-        }
-    } else {                        // RPI.h:4556-4571
-        const float angle_res = 2 * kPI / cols;
-        const float half_nRows = 0.5 * rows - 0.5;
-        for (int c = 0; c < cols; ++c) {
-            float theta = c * angle_res;
-            st[c] = sinf(theta);
-            ct[c] = cosf(theta);
-        }
-        for (int r = 0; r < rows; ++r) {
-            float phi = (half_nRows - r) * angle_res;
-            sp[r] = sinf(phi);
-            cp[r] = cosf(phi);
-        }
-    }
     const size_t dpx = depth_type == 0 ? 2 : 4;
-    if (!tables_resident) {
+    if (!(ctx->f_tab && ctx->f_tab_rows == rows && ctx->f_tab_cols == cols && ctx->f_tab_conv == convention)) {      // else: the angle tables of this geometry are already on the device
         const size_t ntab = (size_t)2 * cols + 2 * rows;
-        if (ctx->f_tab_n < ntab) {
-            hipFree(ctx->f_tab);
-            ctx->f_tab = nullptr;
-            ctx->f_tab_n = 0;
-            HIPC(ctx, hipMalloc(&ctx->f_tab, ntab * sizeof(float)));
-            ctx->f_tab_n = ntab;
+        std::vector<float> tab(ntab);
+        float *st = tab.data(), *ct = st + cols, *sp = ct + cols, *cp = sp + rows;
+        if (convention == 0) {          // Frame360.h:562-585
+            const float angle_pixel(cols / (2 * kPI));
+            const float angle_pixel_inv(1 / angle_pixel);
+            const float offset_phi = kPI * 31.5 / 180;
+            for (int r = 0; r < rows; ++r) {
+                float phi_i = offset_phi - r * angle_pixel_inv;
+                sp[r] = sinf(phi_i);
+                cp[r] = cosf(phi_i);
+            }
+            for (int c = 0; c < cols; ++c) {
+                float theta_i = c * angle_pixel_inv;
+                st[c] = sinf(theta_i);
+                ct[c] = cosf(theta_i);
+            }
+        } else if (convention == 1) {   // Frame360_stereo.h:470-490
+            const float step_theta = 2 * kPI / cols;
+            const float step_phi = step_theta;
+            const int start_phi = 166;
+            for (int r = 0; r < rows; ++r) {
+                float phi = (r + start_phi) * step_phi - kPI / 2;
+                cp[r] = cosf(phi);
+                sp[r] = sinf(phi);
+            }
+            for (int c = 0; c < cols; ++c) {
+                float theta = c * step_theta - kPI;
+                st[c] = sinf(theta);
+                ct[c] = cosf(theta);
+            }
+        } else {                        // RPI.h:4556-4571
+            const float angle_res = 2 * kPI / cols;
+            const float half_nRows = 0.5 * rows - 0.5;
+            for (int c = 0; c < cols; ++c) {
+                float theta = c * angle_res;
+                st[c] = sinf(theta);
+                ct[c] = cosf(theta);
+            }
+            for (int r = 0; r < rows; ++r) {
+                float phi = (half_nRows - r) * angle_res;
+                sp[r] = sinf(phi);
+                cp[r] = cosf(phi);
+            }
         }
-        std::vector<float> tab;
-        tab.insert(tab.end(), st.begin(), st.end());
-        tab.insert(tab.end(), ct.begin(), ct.end());
-        tab.insert(tab.end(), sp.begin(), sp.end());
-        tab.insert(tab.end(), cp.begin(), cp.end());
+        HIPC(ctx, ctx->f_tab.ensure(ntab));
         ctx->f_tab_conv = -1;
         HIPC(ctx, hipMemcpyAsync(ctx->f_tab, tab.data(), ntab * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
         HIPC(ctx, hipStreamSynchronize(ctx->stream));      // `tab` (pageable) must outlive the copy
@@ -933,79 +858,65 @@ int sphere_cloud_dev(F360State* ctx, const void* depth, size_t depth_step, int d
     if (!depth_on_device) HIPC(ctx, hipStreamSynchronize(ctx->stream));      // the caller may reuse its host image
     return 0;
 }
+
+// How an entry point that works on a rows x cols frame begins: the size check (min_side: 1, or what the stage's neighbourhoods need),
+// the context's device, the scratch of that many pixels and -- when the caller brings a cloud -- its upload into ctx->f_xyz
+int f360_begin(F360State* ctx, int rows, int cols, int min_side, const float* xyz = nullptr) {
+    if (rows < min_side || cols < min_side || (long long)rows * cols >= (1ll << 30)) return fail(ctx, -1, "bad image size");
+    hipSetDevice(ctx->p.device);
+    const size_t n = (size_t)rows * cols;
+    if (const int rc = f360_ensure(ctx, n)) return rc;
+    if (xyz) HIPC(ctx, hipMemcpyAsync(ctx->f_xyz, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+// ... and how it ends when the caller wants a map on the host: `count` floats, complete when the call returns
+int f360_download(F360State* ctx, float* host, const float* dev, size_t count) {
+    HIPC(ctx, hipMemcpyAsync(host, dev, count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
 }  // namespace
 
 extern "C" int rgbd360_sphere_cloud(rgbd360_ctx* ctx_, const void* depth, size_t depth_step, int depth_type, int rows, int cols,
                          int convention, float* host_out_xyz) {
     F360_ENTER(ctx_);
-    if (!ctx || !depth || !host_out_xyz) return -1;
-    if (rows < 1 || cols < 1 || (long long)rows * cols >= (1ll << 30)) return fail(ctx, -1, "bad image size");
-    hipSetDevice(ctx->p.device);
-    const size_t n = (size_t)rows * cols;
-    int rc = f360_ensure(ctx, n);
-    if (rc) return rc;
-    rc = sphere_cloud_dev(ctx, depth, depth_step, depth_type, rows, cols, convention);
-    if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(host_out_xyz, ctx->f_xyz, n * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    if (!depth || !host_out_xyz) return -1;
+    if (const int rc = f360_begin(ctx, rows, cols, 1)) return rc;
+    if (const int rc = sphere_cloud_dev(ctx, depth, depth_step, depth_type, rows, cols, convention)) return rc;
+    return f360_download(ctx, host_out_xyz, ctx->f_xyz, (size_t)rows * cols * 3);
 }
 
 extern "C" int rgbd360_normals(rgbd360_ctx* ctx_, const float* xyz, int rows, int cols, float max_depth_change_factor,
                                float normal_smoothing_size, int depth_mode, float* normals_out) {
     F360_ENTER(ctx_);
-    if (!ctx || !xyz || !normals_out) return -1;
-    if (rows < 3 || cols < 3 || (long long)rows * cols >= (1ll << 30)) return fail(ctx, -1, "bad image size");
-    hipSetDevice(ctx->p.device);
-    const size_t n = (size_t)rows * cols;
-    int rc = f360_ensure(ctx, n);
-    if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(ctx->f_xyz, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    rc = f360_normals_dev(ctx, rows, cols, max_depth_change_factor, normal_smoothing_size, depth_mode);
-    if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(normals_out, ctx->f_normals, n * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    if (!xyz || !normals_out) return -1;
+    if (const int rc = f360_begin(ctx, rows, cols, 3, xyz)) return rc;
+    if (const int rc = f360_normals_dev(ctx, rows, cols, max_depth_change_factor, normal_smoothing_size, depth_mode)) return rc;
+    return f360_download(ctx, normals_out, ctx->f_normals, (size_t)rows * cols * 3);
 }
 
 extern "C" int rgbd360_bilateral_filter(rgbd360_ctx* ctx_, const float* xyz, int rows, int cols, float sigma_s, float sigma_r,
                                        float* xyz_out) {
     F360_ENTER(ctx_);
-    if (!ctx || !xyz || !xyz_out) return -1;
-    if (rows < 1 || cols < 1 || (long long)rows * cols >= (1ll << 30)) return fail(ctx, -1, "bad image size");
-    hipSetDevice(ctx->p.device);
-    const size_t n = (size_t)rows * cols;
-    int rc = f360_ensure(ctx, n);
-    if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(ctx->f_xyz, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    rc = f360_bilateral_dev(ctx, rows, cols, sigma_s, sigma_r);
-    if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(xyz_out, ctx->f_xyz, n * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    if (!xyz || !xyz_out) return -1;
+    if (const int rc = f360_begin(ctx, rows, cols, 1, xyz)) return rc;
+    if (const int rc = f360_bilateral_dev(ctx, rows, cols, sigma_s, sigma_r)) return rc;
+    return f360_download(ctx, xyz_out, ctx->f_xyz, (size_t)rows * cols * 3);
 }
 
 extern "C" int rgbd360_distance_map(rgbd360_ctx* ctx_, const float* xyz, int rows, int cols, float max_depth_change_factor,
                                     int depth_mode, float* dist_out) {
     F360_ENTER(ctx_);
-    if (!ctx || !xyz || !dist_out) return -1;
-    if (rows < 3 || cols < 3 || (long long)rows * cols >= (1ll << 30)) return fail(ctx, -1, "bad image size");
-    hipSetDevice(ctx->p.device);
-    const size_t n = (size_t)rows * cols;
-    int rc = f360_ensure(ctx, n);
-    if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(ctx->f_xyz, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (!xyz || !dist_out) return -1;
+    if (const int rc = f360_begin(ctx, rows, cols, 3, xyz)) return rc;
     launch_distance_map(ctx, rows, cols, max_depth_change_factor, depth_mode);
     HIPC(ctx, hipGetLastError());
-    HIPC(ctx, hipMemcpyAsync(dist_out, ctx->f_dist, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return f360_download(ctx, dist_out, ctx->f_dist, (size_t)rows * cols);
 }
 
 // measurement: HIP events at the stage boundaries of the context's later frame_planes calls (rgbd360_hip_diag.h)
 extern "C" int rgbd360_frame_planes_stage_timing(rgbd360_ctx* ctx_, int on) {
     F360_ENTER(ctx_);
-    if (!ctx) return -1;
     hipSetDevice(ctx->p.device);
     if (on)
         for (hipEvent_t& e : ctx->f_stage_ev)
@@ -1016,7 +927,7 @@ extern "C" int rgbd360_frame_planes_stage_timing(rgbd360_ctx* ctx_, int on) {
 }
 extern "C" int rgbd360_frame_planes_stage_times(rgbd360_ctx* ctx_, float us[3]) {
     F360_ENTER(ctx_);
-    if (!ctx || !us) return -1;
+    if (!us) return -1;
     if (!ctx->f_stage_timing || !ctx->f_stage_valid) return fail(ctx, -1, "no timed frame_planes call (rgbd360_frame_planes_stage_timing(ctx, 1) first; the refinement must be off)");
     hipSetDevice(ctx->p.device);
     HIPC(ctx, hipEventSynchronize(ctx->f_stage_ev[3]));
@@ -1035,7 +946,6 @@ extern "C" int rgbd360_planes_available(rgbd360_ctx* ctx_) {
 
 extern "C" int rgbd360_set_plane_refinement(rgbd360_ctx* ctx_, int enabled, float distance_threshold) {
     F360_ENTER(ctx_);
-    if (!ctx) return -1;
     if (enabled && !(distance_threshold > 0.f)) return fail(ctx, -1, "the refinement distance threshold must be positive");
     ctx->f_refine = enabled ? 1 : 0;
     if (enabled) ctx->f_refine_dist = distance_threshold;
@@ -1043,7 +953,6 @@ extern "C" int rgbd360_set_plane_refinement(rgbd360_ctx* ctx_, int enabled, floa
 }
 extern "C" int rgbd360_set_plane_color_image(rgbd360_ctx* ctx_, const uint8_t* rgb, size_t rgb_step, int rows, int cols, int step, int on_device) {
     F360_ENTER(ctx_);
-    if (!ctx) return -1;
     hipSetDevice(ctx->p.device);
     if (!rgb) {
         ctx->f_col_img = {nullptr, 0, 1};
@@ -1056,13 +965,7 @@ extern "C" int rgbd360_set_plane_color_image(rgbd360_ctx* ctx_, const uint8_t* r
     } else {
         const size_t bytes = (size_t)rows * cols * 3;
         HIPC(ctx, hipStreamSynchronize(ctx->stream));       // a plane call still reading the previous copy
-        if (ctx->f_col_owned_bytes < bytes) {
-            hipFree(ctx->f_col_owned);
-            ctx->f_col_owned = nullptr;
-            ctx->f_col_owned_bytes = 0;
-            HIPC(ctx, hipMalloc(&ctx->f_col_owned, bytes));
-            ctx->f_col_owned_bytes = bytes;
-        }
+        HIPC(ctx, ctx->f_col_owned.ensure(bytes));
         HIPC(ctx, hipMemcpy2D(ctx->f_col_owned, (size_t)cols * 3, rgb, rgb_step, (size_t)cols * 3, rows, hipMemcpyHostToDevice));
         ctx->f_col_img = {ctx->f_col_owned, (size_t)cols * 3, step};
     }
@@ -1071,12 +974,12 @@ extern "C" int rgbd360_set_plane_color_image(rgbd360_ctx* ctx_, const uint8_t* r
 }
 extern "C" int rgbd360_debug_plane_sums(rgbd360_ctx* ctx_, int max, int* n, int32_t* root, int32_t* count, int64_t* mom) {
     F360_ENTER(ctx_);
-    if (!ctx || !n || max < 0) return -1;
+    if (!n || max < 0) return -1;
     *n = 0;
     if (!ctx->f_pack_host || !ctx->f_planes_ran) return 0;
-    const int ns_all = *reinterpret_cast<const volatile int*>(ctx->f_pack_host);
+    const int ns_all = *reinterpret_cast<const volatile int*>(ctx->f_pack_host.get());
     const int ns = ns_all < kF360MaxSlots ? ns_all : kF360MaxSlots;
-    const f360::F360SlotRecord* recs = reinterpret_cast<const f360::F360SlotRecord*>(ctx->f_pack_host + f360::kF360PackHeader);
+    const f360::F360SlotRecord* recs = slot_records(ctx);
     for (int s = 0; s < ns && s < max; ++s) {
         if (root) root[s] = recs[s].root;
         if (count) count[s] = recs[s].count;
@@ -1088,7 +991,6 @@ extern "C" int rgbd360_debug_plane_sums(rgbd360_ctx* ctx_, int max, int* n, int3
 }
 extern "C" int rgbd360_plane_refinement_stats(rgbd360_ctx* ctx_, int* pixels_relabelled, int* sweeps) {
     F360_ENTER(ctx_);
-    if (!ctx) return -1;
     if (pixels_relabelled) *pixels_relabelled = ctx->f_refine_changed;
     if (sweeps) *sweeps = ctx->f_refine_sweeps;
     return 0;
@@ -1098,13 +1000,10 @@ extern "C" int rgbd360_plane_fit(rgbd360_ctx* ctx_, const float* xyz, const floa
                                  float angular_threshold, float distance_threshold, float max_curvature, int depth_mode,
                                  int32_t* labels_out, rgbd360_plane* planes_out, int max_planes, int* n_planes_out) {
     F360_ENTER(ctx_);
-    if (!ctx || !xyz || !normals || !planes_out || !n_planes_out || max_planes < 1) return -1;
-    if (rows < 2 || cols < 2 || (long long)rows * cols >= (1ll << 30)) return fail(ctx, -1, "bad image size");
-    hipSetDevice(ctx->p.device);
-    const size_t n = (size_t)rows * cols;
-    int rc = f360_ensure(ctx, n);
+    if (!xyz || !normals || !planes_out || !n_planes_out || max_planes < 1) return -1;
+    int rc = f360_begin(ctx, rows, cols, 2, xyz);
     if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(ctx->f_xyz, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    const size_t n = (size_t)rows * cols;
     HIPC(ctx, hipMemcpyAsync(ctx->f_normals, normals, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     rc = f360_planes_dev(ctx, rows, cols, min_inliers, angular_threshold, distance_threshold, max_curvature, depth_mode, planes_out,
                          max_planes, n_planes_out);
@@ -1118,12 +1017,10 @@ static int frame_planes_impl(F360State* ctx, const void* depth, size_t depth_ste
                              float angular_threshold, float distance_threshold, float max_curvature, int depth_mode,
                              float* xyz_out, float* normals_out, int32_t* labels_out, rgbd360_plane* planes_out,
                              int max_planes, int* n_planes_out, bool depth_on_device) {
-    if (!ctx || !depth || !planes_out || !n_planes_out || max_planes < 1) return -1;
-    if (rows < 3 || cols < 3 || (long long)rows * cols >= (1ll << 30)) return fail(ctx, -1, "bad image size");
-    hipSetDevice(ctx->p.device);
-    const size_t n = (size_t)rows * cols;
-    int rc = f360_ensure(ctx, n);
+    if (!depth || !planes_out || !n_planes_out || max_planes < 1) return -1;
+    int rc = f360_begin(ctx, rows, cols, 3);
     if (rc) return rc;
+    const size_t n = (size_t)rows * cols;
     // the cloud stays on the device; a host copy is only made when asked for
     ctx->f_stage_valid = false;
     if (ctx->f_stage_timing) hipEventRecord(ctx->f_stage_ev[0], ctx->stream);
@@ -1150,10 +1047,7 @@ static int sensor_cloud_upload(F360State* ctx, const void* depth, size_t depth_s
     if (rows < 1 || cols < 1 || step < 1 || step > 4 || rows / step < 1 || cols / step < 1 || depth_step < (size_t)cols * dpx ||
         (depth_type != 0 && depth_type != 1) || (long long)rows * cols >= (1ll << 30))
         return fail(ctx, -1, "bad arguments");
-    hipSetDevice(ctx->p.device);
-    const size_t n = (size_t)rows * cols;
-    int rc = f360_ensure(ctx, n);
-    if (rc) return rc;
+    if (const int rc = f360_begin(ctx, rows, cols, 1)) return rc;
     HIPC(ctx, hipMemcpy2DAsync(ctx->f_depth_raw, (size_t)cols * dpx, depth, depth_step, (size_t)cols * dpx, rows, hipMemcpyHostToDevice, ctx->stream));
     f360::SensorCloudArgs a;
     a.rows = rows; a.cols = cols; a.step = step;
@@ -1172,13 +1066,9 @@ static int sensor_cloud_upload(F360State* ctx, const void* depth, size_t depth_s
 extern "C" int rgbd360_sensor_cloud_ex(rgbd360_ctx* ctx_, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int step,
                                       float min_depth, float max_depth, float* xyz_out) {
     F360_ENTER(ctx_);
-    if (!ctx || !depth || !xyz_out) return -1;
-    const int rc = sensor_cloud_upload(ctx, depth, depth_step, depth_type, rows, cols, step, min_depth, max_depth);
-    if (rc) return rc;
-    const size_t on = (size_t)(rows / step) * (cols / step);
-    HIPC(ctx, hipMemcpyAsync(xyz_out, ctx->f_xyz, on * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    if (!depth || !xyz_out) return -1;
+    if (const int rc = sensor_cloud_upload(ctx, depth, depth_step, depth_type, rows, cols, step, min_depth, max_depth)) return rc;
+    return f360_download(ctx, xyz_out, ctx->f_xyz, (size_t)(rows / step) * (cols / step) * 3);
 }
 extern "C" int rgbd360_sensor_cloud(rgbd360_ctx* ctx_, const uint16_t* depth, size_t depth_step, int rows, int cols, int step, float min_depth,
                                    float max_depth, float* xyz_out) {
@@ -1251,7 +1141,7 @@ extern "C" int rgbd360_sensor_planes_ex(rgbd360_ctx* ctx_, const void* depth, si
                                        float normal_smoothing_size, int min_inliers, float angular_threshold, float distance_threshold,
                                        float max_curvature, const float Rt[16], rgbd360_plane* planes_out, int max_planes, int* n_planes_out) {
     F360_ENTER(ctx_);
-    if (!ctx || !depth || !planes_out || !n_planes_out || max_planes < 1) return -1;
+    if (!depth || !planes_out || !n_planes_out || max_planes < 1) return -1;
     if (step < 1 || rows / step < 3 || cols / step < 3) return fail(ctx, -1, "bad image size");
     const int rc = sensor_cloud_upload(ctx, depth, depth_step, depth_type, rows, cols, step, min_depth, max_depth);
     if (rc) return rc;
@@ -1272,13 +1162,8 @@ extern "C" int rgbd360_cloud_planes(rgbd360_ctx* ctx_, const float* xyz, int row
                                    float distance_threshold, float max_curvature, int depth_mode, const float Rt[16],
                                    rgbd360_plane* planes_out, int max_planes, int* n_planes_out) {
     F360_ENTER(ctx_);
-    if (!ctx || !xyz || !planes_out || !n_planes_out || max_planes < 1) return -1;
-    if (rows < 3 || cols < 3 || (long long)rows * cols >= (1ll << 30)) return fail(ctx, -1, "bad image size");
-    hipSetDevice(ctx->p.device);
-    const size_t n = (size_t)rows * cols;
-    const int rc = f360_ensure(ctx, n);
-    if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(ctx->f_xyz, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (!xyz || !planes_out || !n_planes_out || max_planes < 1) return -1;
+    if (const int rc = f360_begin(ctx, rows, cols, 3, xyz)) return rc;
     return cloud_planes_tail(ctx, rows, cols, sigma_s, sigma_r, max_depth_change_factor, normal_smoothing_size, min_inliers, angular_threshold,
                              distance_threshold, max_curvature, depth_mode, Rt, planes_out, max_planes, n_planes_out);
 }
@@ -1314,7 +1199,7 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
                                      const float Rt_inv[128], const float K[4], uint8_t* sphere_rgb_out, uint16_t* sphere_depth_out,
                                      int* out_rows, int* out_cols) {
     F360_ENTER(ctx_);
-    if (!ctx || !rgb8 || !depth8 || !Rt_inv || !K || !sphere_rgb_out || !sphere_depth_out) return -1;
+    if (!rgb8 || !depth8 || !Rt_inv || !K || !sphere_rgb_out || !sphere_depth_out) return -1;
     if (sensor_rows < 1 || sensor_cols < 1 || sensor_rows > 4096 || sensor_cols > 4096) return fail(ctx, -1, "bad sensor image size");
     hipSetDevice(ctx->p.device);
     f360::StitchArgs a;
@@ -1340,27 +1225,25 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
         tab[2 * a.H + a.W + c] = cosf(theta_i);
     }
     const size_t n_in = (size_t)8 * sensor_rows * sensor_cols, n_out = (size_t)a.H * a.W;
-    uint8_t *d_rgb = nullptr, *d_out_rgb = nullptr;
-    uint16_t *d_depth = nullptr, *d_out_depth = nullptr;
-    float* d_tab = nullptr;
-    hipError_t e = hipMalloc(&d_rgb, n_in * 3);
-    if (e == hipSuccess) e = hipMalloc(&d_depth, n_in * 2);
-    if (e == hipSuccess) e = hipMalloc(&d_out_rgb, n_out * 3);
-    if (e == hipSuccess) e = hipMalloc(&d_out_depth, n_out * 2);
-    if (e == hipSuccess) e = hipMalloc(&d_tab, tab.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rgb, rgb8, n_in * 3, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_depth, depth8, n_in * 2, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(f360::k_stitch_sphere, grid2d(a.H, a.W), dim3(256), 0, ctx->stream, a, d_rgb, d_depth, d_tab, d_tab + a.H,
-                           d_tab + 2 * a.H, d_tab + 2 * a.H + a.W, d_out_rgb, d_out_depth);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(sphere_rgb_out, d_out_rgb, n_out * 3, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sphere_depth_out, d_out_depth, n_out * 2, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    hipFree(d_rgb); hipFree(d_depth); hipFree(d_out_rgb); hipFree(d_out_depth); hipFree(d_tab);
-    HIPC(ctx, e);
+    // (a failed step returns at once: the temporaries' destructors free them, which waits for whatever the stream still holds -- and
+    // `tab`, declared before them, outlives that wait)
+    DevBuf<uint8_t> d_rgb, d_out_rgb;
+    DevBuf<uint16_t> d_depth, d_out_depth;
+    DevBuf<float> d_tab;
+    HIPC(ctx, d_rgb.ensure(n_in * 3));
+    HIPC(ctx, d_depth.ensure(n_in));
+    HIPC(ctx, d_out_rgb.ensure(n_out * 3));
+    HIPC(ctx, d_out_depth.ensure(n_out));
+    HIPC(ctx, d_tab.ensure(tab.size()));
+    HIPC(ctx, hipMemcpyAsync(d_rgb, rgb8, n_in * 3, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(d_depth, depth8, n_in * 2, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(f360::k_stitch_sphere, dim3((a.W + 255) / 256, a.H), dim3(256), 0, ctx->stream, a, d_rgb, d_depth, d_tab, d_tab + a.H,
+                       d_tab + 2 * a.H, d_tab + 2 * a.H + a.W, d_out_rgb, d_out_depth);
+    HIPC(ctx, hipGetLastError());
+    HIPC(ctx, hipMemcpyAsync(sphere_rgb_out, d_out_rgb, n_out * 3, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(sphere_depth_out, d_out_depth, n_out * 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
