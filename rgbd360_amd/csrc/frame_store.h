@@ -26,6 +26,11 @@ struct rgbd360_store {
     rgbd360_ctx* ctx = nullptr;
     rgbd360_params p;
     int capacity = 0, rows = 0, cols = 0, max_eval_blocks = 256;
+    struct Entries {                      // one level's [capacity][n] arrays
+        DevBuf<float2> src;               // source records: one float2 per pixel on a compact level, two (a float4) otherwise
+        DevBuf<F3> trgP, trgD;
+    };
+    std::vector<Entries> entries;         // owned here; `view` and the engines' views point into them
     StoreView view;                       // the entry arrays (view.levels); pt / guesses unused here
     std::vector<char> occupied;
     size_t entry_bytes = 0;
@@ -47,9 +52,8 @@ void store_free_engines(rgbd360_store* st) {
     for (int e = 0; e < 2; ++e) {
         if (st->eng[e]) seq_free(st->eng[e]);      // drains the engine's stream first
         st->eng[e] = nullptr;
-        hipFree(st->eng_view[e].d_guess);
-        if (st->eng_view[e].h_guess) hipHostFree(st->eng_view[e].h_guess);
-        st->eng_view[e].d_guess = st->eng_view[e].h_guess = nullptr;
+        st->eng_view[e].d_guess.release();
+        st->eng_view[e].h_guess.release();
     }
     st->n_eng = 0;
 }
@@ -59,8 +63,7 @@ void store_free(rgbd360_store* st) {
     hipSetDevice(st->p.device);
     store_free_engines(st);
     if (st->put_eng) seq_free(st->put_eng);
-    for (StoreLevelView& V : st->view.levels) { hipFree(V.src); hipFree(V.trgP); hipFree(V.trgD); }
-    delete st;
+    delete st;      // the entry arrays: nothing of an engine is left to read them
 }
 
 // n_eng engines of P slots each, kept between calls
@@ -74,8 +77,7 @@ int store_ensure_engines(rgbd360_store* st, int n_eng, int P) {
         StoreView& V = st->eng_view[e];
         V.levels = st->view.levels;
         memset(&V.pt, 0, sizeof(V.pt));
-        if (hipMalloc(&V.d_guess, (size_t)P * sizeof(Pose16)) != hipSuccess ||
-            hipHostMalloc((void**)&V.h_guess, (size_t)P * sizeof(Pose16), hipHostMallocDefault) != hipSuccess) {
+        if (V.d_guess.ensure(P) != hipSuccess || V.h_guess.ensure(P) != hipSuccess) {
             store_free_engines(st);
             return store_fail(st, -103, "out of memory for the store's alignment engines");
         }
@@ -99,7 +101,7 @@ int store_run_engine(SeqEngine* E, int n_slots, int lo, int hi, const int* trg, 
         }
         // the previous round ended with a synchronisation of this stream: its copy of h_guess has landed
         for (int s = 0; s < m; ++s) memcpy(V.h_guess[s].v, guesses ? guesses + (size_t)16 * (k + s) : kIdentityPose, sizeof(Pose16));
-        SEQC(E, hipMemcpyAsync(V.d_guess, V.h_guess, (size_t)m * sizeof(Pose16), hipMemcpyHostToDevice, E->stream));
+        SEQC(E, hipMemcpyAsync(V.d_guess, V.h_guess.get(), (size_t)m * sizeof(Pose16), hipMemcpyHostToDevice, E->stream));
         seq_enqueue_schedule(E, E->p.n_pyr - 1, false, nullptr, method, live);
         SEQC(E, hipGetLastError());
         const int rc = seq_finish_round(E, m, nullptr, method, live);
@@ -128,18 +130,19 @@ int rgbd360_store_create(rgbd360_ctx* ctx, int capacity, int rows, int cols, rgb
         store_free(st);
         return fail(ctx, rc, err.c_str());
     }
+    st->entries.resize(st->p.n_pyr);
     st->view.levels.resize(st->p.n_pyr);
     for (int l = 0; l < st->p.n_pyr; ++l) {
         const SeqLevel& L = st->put_eng->levels[l];
-        StoreLevelView& V = st->view.levels[l];
+        rgbd360_store::Entries& A = st->entries[l];
         const size_t src_px = L.compact ? sizeof(float2) : sizeof(float4);
         const size_t np = (size_t)capacity * (size_t)L.n;
-        if (hipMalloc((void**)&V.src, np * src_px) != hipSuccess || hipMalloc(&V.trgP, np * sizeof(F3)) != hipSuccess ||
-            hipMalloc(&V.trgD, np * sizeof(F3)) != hipSuccess) {
+        if (A.src.ensure(np * (src_px / sizeof(float2))) != hipSuccess || A.trgP.ensure(np) != hipSuccess || A.trgD.ensure(np) != hipSuccess) {
             (void)hipGetLastError();
             store_free(st);
             return fail(ctx, -103, "out of device memory for the frame store");
         }
+        st->view.levels[l] = StoreLevelView{reinterpret_cast<float4*>(A.src.get()), A.trgP, A.trgD};
         st->entry_bytes += (size_t)L.n * (src_px + 2 * sizeof(F3));
     }
     st->occupied.assign(capacity, 0);
@@ -197,8 +200,8 @@ int rgbd360_store_put(rgbd360_store* st, int n, const int* entry, const uint8_t*
                     fp.rgb[s] = rgb[k + s];
                     fp.depth[s] = depth[k + s];
                 } else {      // stream-ordered behind the set-up launches that read the staging before
-                    fp.rgb[s] = E->stage_rgb[0] + (size_t)s * E->stage_rgb_frame;
-                    fp.depth[s] = E->stage_depth[0] + (size_t)s * E->stage_depth_frame;
+                    fp.rgb[s] = E->ring.rgb[0] + s * E->frame_bytes(3);
+                    fp.depth[s] = E->ring.depth[0] + s * E->frame_bytes(dpx);
                     SEQC(E, copy_frame_h2d((uint8_t*)fp.rgb[s], (void*)fp.depth[s], rgb[k + s], rgb_step, depth[k + s], depth_step, depth_type, st->rows,
                                            st->cols, E->stream));
                 }

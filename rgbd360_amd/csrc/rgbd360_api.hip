@@ -26,6 +26,7 @@
 #include "../../include/rgbd360_hip_diag.h"
 #include "knobs.h"
 #include "host_wait.h"
+#include "dev_buf.h"
 #include "dispatch.h"
 #include "photo_icp_kernels.h"
 #include "occlusion_kernels.h"
@@ -42,7 +43,7 @@ namespace {
 struct Level : LevelGeom {
     float *graySrc = nullptr, *depthSrc = nullptr, *grayTrg = nullptr, *depthTrg = nullptr;
     float4* srcRec = nullptr;
-    float4* srcRecPin = nullptr;     // pinhole LUT record of the source (built per alignment, RPI.h:4277-4300)
+    DevBuf<float4> srcRecPin;        // pinhole LUT record of the source (built per alignment, RPI.h:4277-4300)
     F3 *trgP = nullptr, *trgD = nullptr;
     float *sinT = nullptr, *cosT = nullptr, *sinP = nullptr, *cosP = nullptr;
     float2 *tabT = nullptr, *tabP = nullptr;      // the same values interleaved {sin, cos}: one 8-byte load per pixel in the recompute form of the pass
@@ -86,6 +87,39 @@ hipError_t copy_frame_h2d(uint8_t* dst_rgb, void* dst_depth, const uint8_t* rgb,
     return hipMemcpy2DAsync(dst_depth, (size_t)cols * dpx, depth, depth_step, (size_t)cols * dpx, rows, hipMemcpyHostToDevice, stream);
 }
 
+// The upload ring of a frame sequence: host frames travel on a copy stream of their own through two staging slots, ahead of the
+// alignment that converts them (up_ev[k]: slot k's upload has landed; conv_ev[k]: slot k has been consumed).  The one-pair context
+// holds one (a frame per slot; slot 0 also serves the single-frame entries, which copy on the context's own stream and never open
+// the ring) and so does the lock-step engine (a round of P frames per slot).  The slots grow only.
+struct UploadRing {
+    hipStream_t stream = nullptr;
+    hipEvent_t up_ev[2] = {nullptr, nullptr}, conv_ev[2] = {nullptr, nullptr};
+    DevBuf<uint8_t> rgb[2], depth[2];
+    hipError_t open() {      // the copy stream and the four events, on first use
+        if (stream) return hipSuccess;
+        hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+        for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+            e = hipEventCreateWithFlags(&up_ev[k], hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&conv_ev[k], hipEventDisableTiming);
+        }
+        return e;
+    }
+    bool holds(size_t bytes_rgb, size_t bytes_depth, int slot) const { return rgb[slot].capacity() >= bytes_rgb && depth[slot].capacity() >= bytes_depth; }
+    hipError_t ensure(size_t bytes_rgb, size_t bytes_depth, int slot) {
+        const hipError_t e = rgb[slot].ensure(bytes_rgb);
+        return e != hipSuccess ? e : depth[slot].ensure(bytes_depth);
+    }
+};
+// drains and destroys the ring's stream and events; the staging goes with the ring's owner
+void upload_ring_destroy(UploadRing& U) {
+    if (U.stream) hipStreamSynchronize(U.stream);
+    for (int k = 0; k < 2; ++k) {
+        if (U.up_ev[k]) hipEventDestroy(U.up_ev[k]);
+        if (U.conv_ev[k]) hipEventDestroy(U.conv_ev[k]);
+    }
+    if (U.stream) hipStreamDestroy(U.stream);
+}
+
 struct SeqEngine;      // sequence_engine.h
 
 }  // namespace
@@ -97,26 +131,22 @@ struct rgbd360_ctx {
     std::vector<Level> levels;
     int rows = 0, cols = 0;
     bool have_src = false, have_trg = false;
-    GNState* d_state = nullptr;       // the CURRENT state buffer: every launch of the stream reads / updates this one ...
-    GNState* d_state_alt = nullptr;   // ... except the fused pass (k_eval_fs), which reads d_state, writes d_state_alt, after which the two swap
-    GNState* h_state = nullptr;   // pinned
+    DevBuf<GNState> d_state;          // the CURRENT state buffer: every launch of the stream reads / updates this one ...
+    DevBuf<GNState> d_state_alt;      // ... except the fused pass (k_eval_fs), which reads d_state, writes d_state_alt, after which the two swap
+    PinnedBuf<GNState> h_state{hostwait::kPublishedFlags};
     hostwait::SpinTag tag;        // pinned sequence number the stream's last kernel stores (host_wait.h)
     int pend_rows_hint = r360::kPendingRows;      // upper bound of the partial rows the next fused launch finds pending (stage_pending)
-    double* d_partials = nullptr;     // partial rows of the last pass enqueued (current) ...
-    double* d_partials_alt = nullptr; // ... and where a fused pass puts its rows while its blocks still read the previous table
+    DevBuf<double> d_partials;        // partial rows of the last pass enqueued (current) ...
+    DevBuf<double> d_partials_alt;    // ... and where a fused pass puts its rows while its blocks still read the previous table
     int max_blocks = 0;               // rows of a partial table = blocks of the largest level
     bool fused_occ = true;            // the occlusion-aware alignments on the fused schedule too (rgbd360_debug_set_schedule: {build, pass, k_solve} triples)
     bool seq_route_contexts = false;  // rgbd360_debug_set_sequence_route: every sequence over the per-context route (the occlusion-aware ones always are)
     int seq_route_cap = 0;            // ... with this many contexts at most (0: ctx_route_cap())
     bool fused_solve = true;          // single-pair schedule: solve in the prologue of the next pass (rgbd360_debug_set_schedule: {k_eval, k_solve} pairs)
-    GnIO* d_gnio = nullptr;
+    DevBuf<GnIO> d_gnio;
     // upload staging: slot 0 serves the single-frame entries (copies on `stream`); the sequence entry alternates both slots,
-    // copying on `up_stream` one frame ahead of the alignment (up_ev: upload landed, conv_ev: slot consumed)
-    uint8_t* d_stage_rgb[2] = {nullptr, nullptr};
-    uint8_t* d_stage_depth[2] = {nullptr, nullptr};
-    size_t stage_rgb_bytes[2] = {0, 0}, stage_depth_bytes[2] = {0, 0};
-    hipStream_t up_stream = nullptr;
-    hipEvent_t up_ev[2] = {nullptr, nullptr}, conv_ev[2] = {nullptr, nullptr};
+    // copying on the ring's stream one frame ahead of the alignment
+    UploadRing ring;
     int poll_chunk = 3;           // {pass, solve} pairs per level enqueued ahead of the device
     int first_chunk_top = 8;      // ... and for the first visit of the coarsest level (cheap passes, most iterations)
     int chunk_level0 = 3;         // ... and for the finest level (most expensive passes; a second chunk costs a host round trip)
@@ -133,23 +163,22 @@ struct rgbd360_ctx {
     bool have_cam = false;
     float sal_thr = -1.f;                               // useSaliency(true): thresSaliency (RPI.h:217, 266); < 0 = off
     // pinhole occlusion passes: (target index, source index) pairs before / after the sort, the sort's scratch, one partial row per walk block
-    unsigned *pin_keys = nullptr, *pin_vals = nullptr;      // the pinhole occlusion passes: per source pixel its target + pass flags,
-    PinOccLists pin_lists = {nullptr, nullptr, nullptr};      // per target pixel its arrivals (pinhole_kernels.h)
-    size_t pin_occ_n = 0;
-    double* pin_partials = nullptr;
-    int* occ_head = nullptr;                           // occlusion modes: per-target lists of candidate runs (generation-tagged heads)
-    int4* occ_nodes = nullptr;                         // ... run nodes, indexed by the run's last source pixel
-    unsigned char* occ_runinfo = nullptr;              // ... per source pixel: candidate / prefix maximum within its run / offset to the run's first pixel
+    DevBuf<unsigned> pin_keys, pin_vals;               // the pinhole occlusion passes: per source pixel its target + pass flags,
+    DevBuf<int> pin_cnt;                               // per target pixel its arrivals (PinOccLists, pinhole_kernels.h: filled from these
+    DevBuf<int4> pin_box;                              // three at launch)
+    DevBuf<unsigned> pin_slots;
+    DevBuf<double> pin_partials;
+    DevBuf<int> occ_head;                              // occlusion modes: per-target lists of candidate runs (generation-tagged heads)
+    DevBuf<int4> occ_nodes;                            // ... run nodes, indexed by the run's last source pixel
+    DevBuf<unsigned char> occ_runinfo;                 // ... per source pixel: candidate / prefix maximum within its run / offset to the run's first pixel
     int occ_gen = 0;                                   // generation tag of the head entries (no memset between passes)
-    size_t occ_n = 0;
     // rgbd360_warp_images*: the winner plane and the four float planes the host entries stage their outputs in, sized for the finest level on
-    // first use and freed with the levels
-    int32_t* wi_winner = nullptr;
-    float* wi_stage = nullptr;
-    size_t wi_n = 0;
+    // first use (wi_winner.capacity() pixels per plane) and freed with the levels
+    DevBuf<int32_t> wi_winner;
+    DevBuf<float> wi_stage;
     int max_eval_blocks = 256;    // grid cap of the fused pass (debug knob RGBD360_EVAL_BLOCKS, csrc/knobs.h)
     int index_libm = 0;           // rgbd360_set_index_arithmetic: 1 = the spherical warp in the reference's libm arithmetic
-    unsigned char* arena = nullptr;   // ONE allocation behind every per-level buffer of the context (planes, records, angle tables)
+    DevBuf<unsigned char> arena;      // ONE allocation behind every per-level buffer of the context (planes, records, angle tables)
     std::string err;
 };
 
@@ -169,27 +198,14 @@ int fail(rgbd360_ctx* ctx, int code, const char* msg) {
     return code;
 }
 
-void pin_occ_free(rgbd360_ctx* ctx) {
-    hipFree(ctx->pin_keys); hipFree(ctx->pin_vals); hipFree(ctx->pin_partials);
-    hipFree(ctx->pin_lists.cnt); hipFree(ctx->pin_lists.box); hipFree(ctx->pin_lists.slots);
-    ctx->pin_keys = ctx->pin_vals = nullptr;
-    ctx->pin_partials = nullptr;
-    ctx->pin_lists = PinOccLists{nullptr, nullptr, nullptr};
-    ctx->pin_occ_n = 0;
-}
-
+// what a change of the frame size frees (the occlusion set of the spherical path, the staging and the states stay, and grow only)
 void free_levels(rgbd360_ctx* ctx) {
-    for (Level& L : ctx->levels) {
-        hipFree(L.srcRecPin);
-    }
-    pin_occ_free(ctx);
-    hipFree(ctx->wi_winner); hipFree(ctx->wi_stage);
-    ctx->wi_winner = nullptr;
-    ctx->wi_stage = nullptr;
-    ctx->wi_n = 0;
-    hipFree(ctx->arena);
-    ctx->arena = nullptr;
-    ctx->levels.clear();
+    ctx->pin_keys.release(); ctx->pin_vals.release(); ctx->pin_partials.release();
+    ctx->pin_cnt.release(); ctx->pin_box.release(); ctx->pin_slots.release();
+    ctx->wi_winner.release(); ctx->wi_stage.release();
+    ctx->d_partials.release(); ctx->d_partials_alt.release();
+    ctx->arena.release();
+    ctx->levels.clear();      // (and every level's srcRecPin)
     ctx->rows = ctx->cols = 0;
     ctx->have_src = ctx->have_trg = false;
 }
@@ -209,7 +225,7 @@ int ensure_levels(rgbd360_ctx* ctx, int rows, int cols) {
                      2 * (((size_t)cc * 4 + 255) & ~(size_t)255) + 2 * (((size_t)rr * 4 + 255) & ~(size_t)255) +
                      (((size_t)cc * 8 + 255) & ~(size_t)255) + (((size_t)rr * 8 + 255) & ~(size_t)255);
         }
-        HIPC(ctx, hipMalloc(&ctx->arena, total));
+        HIPC(ctx, ctx->arena.ensure(total));
     }
     int r = rows, c = cols;
     int max_blocks = 0;
@@ -240,14 +256,12 @@ int ensure_levels(rgbd360_ctx* ctx, int rows, int cols) {
         if (L.nblocks > max_blocks) max_blocks = L.nblocks;
         r /= 2; c /= 2;
     }
-    hipFree(ctx->d_partials); hipFree(ctx->d_partials_alt);
-    ctx->d_partials = ctx->d_partials_alt = nullptr;
-    // at least the kPendingRows rows stage_pending always loads, + diagnostic rows
-    const size_t part_bytes = (size_t)(std::max((max_blocks + 31) / 32 * 32, kPendingRows) + 32 + max_blocks / 2 + 2) * kNumPartials * sizeof(double);      // + the diagnostic rows of the stamp builds
-    HIPC(ctx, hipMalloc(&ctx->d_partials, part_bytes));
-    HIPC(ctx, hipMalloc(&ctx->d_partials_alt, part_bytes));
-    HIPC(ctx, hipMemset(ctx->d_partials, 0, part_bytes));          // the fused pass loads max_blocks rows whatever the pending count
-    HIPC(ctx, hipMemset(ctx->d_partials_alt, 0, part_bytes));
+    // at least the kPendingRows rows stage_pending always loads, + diagnostic rows; both tables are new here (free_levels released them)
+    const size_t part_n = (size_t)(std::max((max_blocks + 31) / 32 * 32, kPendingRows) + 32 + max_blocks / 2 + 2) * kNumPartials;      // + the diagnostic rows of the stamp builds
+    HIPC(ctx, ctx->d_partials.ensure(part_n));
+    HIPC(ctx, ctx->d_partials_alt.ensure(part_n));
+    HIPC(ctx, hipMemset(ctx->d_partials, 0, part_n * sizeof(double)));          // the fused pass loads max_blocks rows whatever the pending count
+    HIPC(ctx, hipMemset(ctx->d_partials_alt, 0, part_n * sizeof(double)));
     ctx->max_blocks = max_blocks;
     ctx->rows = rows; ctx->cols = cols;
     return 0;
@@ -283,18 +297,13 @@ dim3 grid2d(int rows, int cols, int bx = 256) { return dim3((cols + bx - 1) / bx
 
 int occ_ensure(rgbd360_ctx* ctx) {
     const size_t n = ctx->levels.empty() ? 0 : (size_t)ctx->levels[0].n;
-    if (ctx->occ_n >= n && n > 0) return 0;
-    hipFree(ctx->occ_head); hipFree(ctx->occ_nodes); hipFree(ctx->occ_runinfo);
-    ctx->occ_head = nullptr;
-    ctx->occ_nodes = nullptr;
-    ctx->occ_runinfo = nullptr;
-    ctx->occ_n = 0;
-    HIPC(ctx, hipMalloc(&ctx->occ_head, n * sizeof(int)));
-    HIPC(ctx, hipMalloc(&ctx->occ_nodes, n * sizeof(int4)));
-    HIPC(ctx, hipMalloc(&ctx->occ_runinfo, n));
-    HIPC(ctx, hipMemsetAsync(ctx->occ_head, 0, n * sizeof(int), ctx->stream));      // generation 0 = empty; the passes count from 1
+    if (n > 0 && ctx->occ_head.capacity() >= n && ctx->occ_nodes.capacity() >= n && ctx->occ_runinfo.capacity() >= n) return 0;
+    // the three grow together (and survive a smaller frame size); the heads of a set that grew start empty
+    HIPC(ctx, ctx->occ_head.ensure(n));
+    HIPC(ctx, ctx->occ_nodes.ensure(n));
+    HIPC(ctx, ctx->occ_runinfo.ensure(n));
+    HIPC(ctx, hipMemsetAsync(ctx->occ_head, 0, ctx->occ_head.capacity() * sizeof(int), ctx->stream));      // generation 0 = empty; the passes count from 1
     ctx->occ_gen = 0;
-    ctx->occ_n = n;
     return 0;
 }
 
@@ -302,7 +311,7 @@ int occ_ensure(rgbd360_ctx* ctx) {
 // passes instead of one per pass.  Returns the generation of the pass about to be enqueued.
 int occ_next_gen(rgbd360_ctx* ctx) {
     if (++ctx->occ_gen > kOccGenMax) {
-        hipMemsetAsync(ctx->occ_head, 0, ctx->occ_n * sizeof(int), ctx->stream);
+        hipMemsetAsync(ctx->occ_head, 0, ctx->occ_head.capacity() * sizeof(int), ctx->stream);
         ctx->occ_gen = 1;
     }
     return ctx->occ_gen;
@@ -506,38 +515,16 @@ void launch_src_recs(rgbd360_ctx* ctx) {
     hipLaunchKernelGGL(k_src_rec_multi, dim3(nb), dim3(256), 0, ctx->stream, jobs);
 }
 
-static int ensure_stage(rgbd360_ctx* ctx, int slot, size_t need_rgb, size_t need_d) {
-    if (ctx->stage_rgb_bytes[slot] < need_rgb) {
-        hipFree(ctx->d_stage_rgb[slot]);
-        ctx->d_stage_rgb[slot] = nullptr; ctx->stage_rgb_bytes[slot] = 0;
-        HIPC(ctx, hipMalloc(&ctx->d_stage_rgb[slot], need_rgb));
-        ctx->stage_rgb_bytes[slot] = need_rgb;
-    }
-    if (ctx->stage_depth_bytes[slot] < need_d) {
-        hipFree(ctx->d_stage_depth[slot]);
-        ctx->d_stage_depth[slot] = nullptr; ctx->stage_depth_bytes[slot] = 0;
-        HIPC(ctx, hipMalloc(&ctx->d_stage_depth[slot], need_d));
-        ctx->stage_depth_bytes[slot] = need_d;
-    }
-    return 0;
-}
-
 // Sequence path: copy one host frame into staging slot `slot` on the context's upload stream, ahead of its use.
 static int upload_stage(rgbd360_ctx* ctx, int slot, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t d_step,
                         int depth_type, int rows, int cols) {
     const size_t dpx = depth_type == 0 ? 2 : 4;
-    if (!ctx->up_stream) {
-        HIPC(ctx, hipStreamCreateWithFlags(&ctx->up_stream, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k) {
-            HIPC(ctx, hipEventCreateWithFlags(&ctx->up_ev[k], hipEventDisableTiming));
-            HIPC(ctx, hipEventCreateWithFlags(&ctx->conv_ev[k], hipEventDisableTiming));
-        }
-    }
-    int rc = ensure_stage(ctx, slot, (size_t)rows * cols * 3, (size_t)rows * cols * dpx);
-    if (rc) return rc;
-    HIPC(ctx, hipStreamWaitEvent(ctx->up_stream, ctx->conv_ev[slot], 0));      // the slot's previous frame has been converted
-    HIPC(ctx, copy_frame_h2d(ctx->d_stage_rgb[slot], ctx->d_stage_depth[slot], rgb, rgb_step, depth, d_step, depth_type, rows, cols, ctx->up_stream));
-    HIPC(ctx, hipEventRecord(ctx->up_ev[slot], ctx->up_stream));
+    UploadRing& U = ctx->ring;
+    HIPC(ctx, U.open());
+    HIPC(ctx, U.ensure((size_t)rows * cols * 3, (size_t)rows * cols * dpx, slot));
+    HIPC(ctx, hipStreamWaitEvent(U.stream, U.conv_ev[slot], 0));      // the slot's previous frame has been converted
+    HIPC(ctx, copy_frame_h2d(U.rgb[slot], U.depth[slot], rgb, rgb_step, depth, d_step, depth_type, rows, cols, U.stream));
+    HIPC(ctx, hipEventRecord(U.up_ev[slot], U.stream));
     return 0;
 }
 
@@ -558,14 +545,13 @@ int set_frame(rgbd360_ctx* ctx, bool target, const uint8_t* rgb, size_t rgb_step
     const void* d_depth = depth;
     size_t s_rgb = rgb_step, s_depth = d_step;
     if (staged_slot >= 0) {
-        HIPC(ctx, hipStreamWaitEvent(ctx->stream, ctx->up_ev[staged_slot], 0));
-        d_rgb = ctx->d_stage_rgb[staged_slot]; d_depth = ctx->d_stage_depth[staged_slot];
+        HIPC(ctx, hipStreamWaitEvent(ctx->stream, ctx->ring.up_ev[staged_slot], 0));
+        d_rgb = ctx->ring.rgb[staged_slot]; d_depth = ctx->ring.depth[staged_slot];
         s_rgb = (size_t)cols * 3; s_depth = (size_t)cols * dpx;
     } else if (!on_device) {
-        rc = ensure_stage(ctx, 0, (size_t)rows * cols * 3, (size_t)rows * cols * dpx);
-        if (rc) return rc;
-        HIPC(ctx, copy_frame_h2d(ctx->d_stage_rgb[0], ctx->d_stage_depth[0], rgb, rgb_step, depth, d_step, depth_type, rows, cols, ctx->stream));
-        d_rgb = ctx->d_stage_rgb[0]; d_depth = ctx->d_stage_depth[0];
+        HIPC(ctx, ctx->ring.ensure((size_t)rows * cols * 3, (size_t)rows * cols * dpx, 0));
+        HIPC(ctx, copy_frame_h2d(ctx->ring.rgb[0], ctx->ring.depth[0], rgb, rgb_step, depth, d_step, depth_type, rows, cols, ctx->stream));
+        d_rgb = ctx->ring.rgb[0]; d_depth = ctx->ring.depth[0];
         s_rgb = (size_t)cols * 3; s_depth = (size_t)cols * dpx;
     }
     Level& L0 = ctx->levels[0];
@@ -575,7 +561,7 @@ int set_frame(rgbd360_ctx* ctx, bool target, const uint8_t* rgb, size_t rgb_step
         dim3 g = grid2d(rows, (cols + 3) / 4);
         g.z = 2;                                        // colour -> intensity and depth -> metres in one launch
         hipLaunchKernelGGL(k_convert_pair, g, dim3(256), 0, ctx->stream, d_rgb, s_rgb, d_depth, s_depth, depth_type, rows, cols, gray0, dep0);
-        if (staged_slot >= 0) HIPC(ctx, hipEventRecord(ctx->conv_ev[staged_slot], ctx->stream));
+        if (staged_slot >= 0) HIPC(ctx, hipEventRecord(ctx->ring.conv_ev[staged_slot], ctx->stream));
     }
     for (int l = 1; l < ctx->p.n_pyr; ++l) {
         Level &P = ctx->levels[l - 1], &C = ctx->levels[l];
@@ -659,12 +645,12 @@ int rgbd360_create(const rgbd360_params* p, rgbd360_ctx** out) {
     }
     bool ok = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreate(&ctx->ev0) == hipSuccess && hipEventCreate(&ctx->ev1) == hipSuccess &&
-              hipMalloc(&ctx->d_state, sizeof(GNState)) == hipSuccess &&
+              ctx->d_state.ensure(1) == hipSuccess &&
               hipMemset(ctx->d_state, 0, sizeof(GNState)) == hipSuccess &&
-              hipMalloc(&ctx->d_state_alt, sizeof(GNState)) == hipSuccess &&
+              ctx->d_state_alt.ensure(1) == hipSuccess &&
               hipMemset(ctx->d_state_alt, 0, sizeof(GNState)) == hipSuccess &&
-              hipMalloc(&ctx->d_gnio, sizeof(GnIO)) == hipSuccess &&
-              hipHostMalloc((void**)&ctx->h_state, sizeof(GNState), hostwait::kPublishedFlags) == hipSuccess &&
+              ctx->d_gnio.ensure(1) == hipSuccess &&
+              ctx->h_state.ensure(1) == hipSuccess &&
               hostwait::spin_tag_init(&ctx->tag) == hipSuccess;
     if (!ok) {
         rgbd360_destroy(ctx);
@@ -682,22 +668,13 @@ void rgbd360_destroy(rgbd360_ctx* ctx) {
     for (SeqEngine* e : ctx->engines) seq_free(e);
     ctx->engines.clear();
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
-    free_levels(ctx);
-    hipFree(ctx->d_state); hipFree(ctx->d_state_alt); hipFree(ctx->d_partials); hipFree(ctx->d_partials_alt); hipFree(ctx->d_gnio);
-    for (int k = 0; k < 2; ++k) {
-        hipFree(ctx->d_stage_rgb[k]); hipFree(ctx->d_stage_depth[k]);
-        if (ctx->up_ev[k]) hipEventDestroy(ctx->up_ev[k]);
-        if (ctx->conv_ev[k]) hipEventDestroy(ctx->conv_ev[k]);
-    }
-    if (ctx->up_stream) { hipStreamSynchronize(ctx->up_stream); hipStreamDestroy(ctx->up_stream); }
+    upload_ring_destroy(ctx->ring);
     if (ctx->f360) f360_state_destroy(ctx->f360);
-    hipFree(ctx->occ_head); hipFree(ctx->occ_nodes); hipFree(ctx->occ_runinfo);
-    if (ctx->h_state) hipHostFree(ctx->h_state);
     hostwait::spin_tag_free(&ctx->tag);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;      // every buffer the context owns, with its device current and nothing of its streams left
 }
 
 const char* rgbd360_last_error(rgbd360_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -813,7 +790,7 @@ int rgbd360_align360_finish(rgbd360_ctx* ctx, float pose_out[16], rgbd360_result
     }
     rgbd360_result R;
     result_from_state(*ctx->h_state, ctx->p.n_pyr, ctx->al_occ, pose_out, &R);
-    for (int l = 0; l < 8; ++l) ctx->hist_iters[l] = (R.status == 0 && l < ctx->p.n_pyr) ? ctx->h_state->iters[l] : -1;
+    for (int l = 0; l < 8; ++l) ctx->hist_iters[l] = (R.status == 0 && l < ctx->p.n_pyr) ? ctx->h_state[0].iters[l] : -1;
     if (res) *res = R;
     return R.status;
 }
@@ -893,7 +870,7 @@ static int align360_batch_threads(rgbd360_ctx* ctx, int n_frames, const uint8_t*
             if (results_out) results_out[j] = R;
             if (rc >= 0) rc = j + 1 < b[c] ? std::min(0, rgbd360_promote_source_to_target(cc)) : 0;
         }
-        if (cc->up_stream) hipStreamSynchronize(cc->up_stream);      // no upload may outlive the caller's buffers
+        if (cc->ring.stream) hipStreamSynchronize(cc->ring.stream);      // no upload may outlive the caller's buffers
         if (rc) hipStreamSynchronize(cc->stream);
         rcs[c] = rc;
     };
@@ -1098,15 +1075,13 @@ int rgbd360_warp_indices(rgbd360_ctx* ctx, int level, const float pose[16], int3
     if (!ctx->have_src) return fail(ctx, -2, "no source frame");
     hipSetDevice(ctx->p.device);
     const Level& L = ctx->levels[level];
-    int32_t* d_out = nullptr;
-    HIPC(ctx, hipMalloc(&d_out, (size_t)L.n * 2 * sizeof(int32_t)));
+    DevBuf<int32_t> d_out;
+    HIPC(ctx, d_out.ensure((size_t)L.n * 2));
     Pose16 P;
     memcpy(P.v, pose, sizeof(P.v));
-    hipLaunchKernelGGL(k_warp_indices, dim3((L.n + 255) / 256), dim3(256), 0, ctx->stream, level_dev(L), P, d_out);
-    hipError_t e = hipMemcpyAsync(host_out_rc, d_out, (size_t)L.n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    hipFree(d_out);
-    HIPC(ctx, e);
+    hipLaunchKernelGGL(k_warp_indices, dim3((L.n + 255) / 256), dim3(256), 0, ctx->stream, level_dev(L), P, d_out.get());
+    HIPC(ctx, hipMemcpyAsync(host_out_rc, d_out, (size_t)L.n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
@@ -1154,9 +1129,10 @@ int rgbd360_forced_iters(rgbd360_ctx* ctx, int level, const float pose0[16], int
     else HIPC(ctx, hostwait::wait(ctx->tag, ctx->stream));
     if (rc) return rc;
     if (elapsed_ms) HIPC(ctx, hipEventElapsedTime(elapsed_ms, ctx->ev0, ctx->ev1));
-    if (pose_out) memcpy(pose_out, ctx->h_state->pose, sizeof(float) * 16);
-    if (last_rms) *last_rms = ctx->h_state->error;
-    return ctx->h_state->status;
+    const GNState& S = *ctx->h_state;
+    if (pose_out) memcpy(pose_out, S.pose, sizeof(float) * 16);
+    if (last_rms) *last_rms = S.error;
+    return S.status;
 }
 
 // One solve on a hand-made partial table (row 0 = `row`, every other row zero) at the identity pose, through the two-launch form
@@ -1182,7 +1158,7 @@ int rgbd360_debug_solve_partials(rgbd360_ctx* ctx, int level, const double row[3
     HIPC(ctx, hipMemcpyAsync(ctx->d_partials + (size_t)row_at * kNumPartials, row, kNumPartials * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (fused) {
         const int pend[2] = {L.nblocks, L.n};       // as if a pass of this level had just written the table
-        HIPC(ctx, hipMemcpyAsync(&ctx->d_state->pend_nb, pend, sizeof(pend), hipMemcpyHostToDevice, ctx->stream));
+        HIPC(ctx, hipMemcpyAsync(&ctx->d_state[0].pend_nb, pend, sizeof(pend), hipMemcpyHostToDevice, ctx->stream));
         ctx->pend_rows_hint = fused == 2 ? 1 : kPendingRows;      // a hand-made pending pass: no bound known
         launch_eval_fused(ctx, level, method, 0);      // the state is read as this launch leaves it: its own pass (if it ran one) stays pending
     } else {
@@ -1338,19 +1314,16 @@ int rgbd360_forced_iters_batch(rgbd360_ctx* ctx, int n_pairs, const uint8_t* rgb
     if (rc) return fail(ctx, rc, err.c_str());
     const size_t dpx = depth_type == 0 ? 2 : 4;
     const size_t fr = (size_t)rows * cols * 3, fd = (size_t)rows * cols * dpx;
-    uint8_t *d_rgb[2] = {nullptr, nullptr}, *d_dep[2] = {nullptr, nullptr};
-    auto cleanup = [&]() {
-        for (int k = 0; k < 2; ++k) { hipFree(d_rgb[k]); hipFree(d_dep[k]); }
-        seq_free(E);
-    };
+    const std::unique_ptr<SeqEngine, void (*)(SeqEngine*)> engine(E, seq_free);      // drained and freed on every way out
+    DevBuf<uint8_t> d_rgb[2], d_dep[2];
     hipError_t e = hipSuccess;
     for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        e = hipMalloc(&d_rgb[k], fr);
-        if (e == hipSuccess) e = hipMalloc(&d_dep[k], fd);
+        e = d_rgb[k].ensure(fr);
+        if (e == hipSuccess) e = d_dep[k].ensure(fd);
         if (e == hipSuccess) e = hipMemcpy2D(d_rgb[k], (size_t)cols * 3, k == 0 ? rgb_trg : rgb_src, rgb_step, (size_t)cols * 3, rows, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy2D(d_dep[k], (size_t)cols * dpx, k == 0 ? depth_trg : depth_src, depth_step, (size_t)cols * dpx, rows, hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) { cleanup(); return fail(ctx, -(int)e - 1000, hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(ctx, -(int)e - 1000, hipGetErrorString(e));
     const unsigned long long live = n_pairs >= 64 ? ~0ull : ((1ull << n_pairs) - 1ull);
     FramePtrs fp;
     memset(&fp, 0, sizeof(fp));
@@ -1395,7 +1368,6 @@ int rgbd360_forced_iters_batch(rgbd360_ctx* ctx, int n_pairs, const uint8_t* rgb
             if (E->h_states[s].status != 0) status = E->h_states[s].status;
         }
     }
-    cleanup();
     if (e != hipSuccess) return fail(ctx, -(int)e - 1000, hipGetErrorString(e));
     return status;
 }
@@ -1455,23 +1427,19 @@ int rgbd360_debug_solve_stamps(rgbd360_ctx* ctx, unsigned long long out[8]) {
     if (!ctx || !out) return -1;
     int rc = read_state(ctx);
     if (rc) return rc;
-    memcpy(out, ctx->h_state->stamps, sizeof(unsigned long long) * 8);
+    memcpy(out, ctx->h_state[0].stamps, sizeof(unsigned long long) * 8);
     return 0;
 }
 
 int rgbd360_selftest_math(rgbd360_ctx* ctx, uint32_t first_bits, uint32_t count, unsigned long long mismatches[3]) {
     if (!ctx || !mismatches) return -1;
     hipSetDevice(ctx->p.device);
-    unsigned long long* d = nullptr;
-    HIPC(ctx, hipMalloc(&d, 3 * sizeof(unsigned long long)));
-    hipError_t e = hipMemsetAsync(d, 0, 3 * sizeof(unsigned long long), ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_selftest_math, dim3(2048), dim3(256), 0, ctx->stream, first_bits, count, d);
-        e = hipMemcpyAsync(mismatches, d, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    hipFree(d);
-    HIPC(ctx, e);
+    DevBuf<unsigned long long> d;
+    HIPC(ctx, d.ensure(3));
+    HIPC(ctx, hipMemsetAsync(d, 0, 3 * sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_selftest_math, dim3(2048), dim3(256), 0, ctx->stream, first_bits, count, d.get());
+    HIPC(ctx, hipMemcpyAsync(mismatches, d, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
@@ -1482,8 +1450,8 @@ int rgbd360_selftest_libm(rgbd360_ctx* ctx, uint32_t first_bits, uint32_t count,
     hipSetDevice(ctx->p.device);
     for (int k = 0; k < 4; ++k) mismatches[k] = 0;
     constexpr uint32_t kChunk = 1u << 22;
-    float* d = nullptr;
-    HIPC(ctx, hipMalloc(&d, 4 * (size_t)kChunk * sizeof(float)));
+    DevBuf<float> d;
+    HIPC(ctx, d.ensure(4 * (size_t)kChunk));
     std::vector<float> h(4 * (size_t)kChunk);
     auto differ = [](float a, float b) {
         uint32_t x, y;
@@ -1494,7 +1462,7 @@ int rgbd360_selftest_libm(rgbd360_ctx* ctx, uint32_t first_bits, uint32_t count,
     int shown = 0;
     for (uint64_t done = 0; done < count && e == hipSuccess; done += kChunk) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(kChunk, count - done), first = first_bits + (uint32_t)done;
-        hipLaunchKernelGGL(k_selftest_libm, dim3(2048), dim3(256), 0, ctx->stream, first, n, d);
+        hipLaunchKernelGGL(k_selftest_libm, dim3(2048), dim3(256), 0, ctx->stream, first, n, d.get());
         e = hipMemcpyAsync(h.data(), d, 4 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) break;
@@ -1517,7 +1485,6 @@ int rgbd360_selftest_libm(rgbd360_ctx* ctx, uint32_t first_bits, uint32_t count,
             mismatches[3] += differ(h[3 * (size_t)n + k], atan2f(y, x));
         }
     }
-    hipFree(d);
     HIPC(ctx, e);
     return 0;
 }
@@ -1544,11 +1511,11 @@ int pin_check(rgbd360_ctx* ctx, int level, int method) {
 
 int pin_prepare_level(rgbd360_ctx* ctx, int level) {
     Level& L = ctx->levels[level];
-    if (!L.srcRecPin) HIPC(ctx, hipMalloc(&L.srcRecPin, (size_t)L.n * sizeof(float4)));
+    HIPC(ctx, L.srcRecPin.ensure((size_t)L.n));
     const PinK K = pin_level_K(ctx, level);
     const float inv_fx = 1. / K.fx, inv_fy = 1. / K.fy;
     hipLaunchKernelGGL(k_src_rec_pinhole, grid2d(L.rows, L.cols), dim3(256), 0, ctx->stream, L.depthSrc, L.graySrc, L.rows, L.cols, K,
-                       inv_fx, inv_fy, ctx->p.min_depth, ctx->p.max_depth, L.srcRecPin);
+                       inv_fx, inv_fy, ctx->p.min_depth, ctx->p.max_depth, L.srcRecPin.get());
     HIPC(ctx, hipGetLastError());
     return 0;
 }
@@ -1582,21 +1549,20 @@ int pin_eval(rgbd360_ctx* ctx, int level, const float* pose, int method) {
 // The occlusion-aware evaluation (pinhole_kernels.h, second half): per-target arrival lists, one walk per target pixel in source-index
 // order; the reduce-only solve publishes the sums like pin_eval's.
 int pin_occ_ensure(rgbd360_ctx* ctx, size_t n) {
-    if (ctx->pin_occ_n >= n) return 0;
-    pin_occ_free(ctx);
-    PinOccLists& Ls = ctx->pin_lists;
-    HIPC(ctx, hipMalloc(&ctx->pin_keys, n * sizeof(unsigned)));
-    HIPC(ctx, hipMalloc(&ctx->pin_vals, n * sizeof(unsigned)));
-    HIPC(ctx, hipMalloc(&Ls.cnt, n * sizeof(int)));
-    HIPC(ctx, hipMalloc(&Ls.box, n * sizeof(int4)));
-    HIPC(ctx, hipMalloc(&Ls.slots, n * kPinShort * sizeof(unsigned)));
+    // the set is complete once its last member is there (pin_partials: allocated behind the arming launch)
+    if (ctx->pin_partials.capacity() > 0 && ctx->pin_keys.capacity() >= n) return 0;
+    HIPC(ctx, ctx->pin_keys.ensure(n));
+    HIPC(ctx, ctx->pin_vals.ensure(n));
+    HIPC(ctx, ctx->pin_cnt.ensure(n));
+    HIPC(ctx, ctx->pin_box.ensure(n));
+    HIPC(ctx, ctx->pin_slots.ensure(n * kPinShort));
     // armed once; every walk re-arms the words of the target pixels it visited
-    hipLaunchKernelGGL(k_pin_occ_arm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, Ls.cnt, Ls.box, (int)n);
+    hipLaunchKernelGGL(k_pin_occ_arm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->pin_cnt.get(), ctx->pin_box.get(), (int)n);
     HIPC(ctx, hipGetLastError());
-    HIPC(ctx, hipMalloc(&ctx->pin_partials, ((n + kPinWalkThreads - 1) / kPinWalkThreads) * kNumPartials * sizeof(double)));
-    ctx->pin_occ_n = n;
+    HIPC(ctx, ctx->pin_partials.ensure(((n + kPinWalkThreads - 1) / kPinWalkThreads) * kNumPartials));
     return 0;
 }
+PinOccLists pin_lists(const rgbd360_ctx* ctx) { return PinOccLists{ctx->pin_cnt, ctx->pin_box, ctx->pin_slots}; }
 
 int pin_eval_occ(rgbd360_ctx* ctx, int level, const float* pose, int method, int occ) {
     const Level& L = ctx->levels[level];
@@ -1609,12 +1575,12 @@ int pin_eval_occ(rgbd360_ctx* ctx, int level, const float* pose, int method, int
     memcpy(P.v, pose, sizeof(P.v));
     const dim3 gk((L.n + 255) / 256), bk(256);
     with_choice<1, 2>(occ != 1, [&](auto O) {
-        hipLaunchKernelGGL((k_pin_occ_keys<O>), gk, bk, 0, ctx->stream, lv, K, P, ctx->pin_keys, ctx->pin_vals, ctx->pin_lists);
+        hipLaunchKernelGGL((k_pin_occ_keys<O>), gk, bk, 0, ctx->stream, lv, K, P, ctx->pin_keys.get(), ctx->pin_vals.get(), pin_lists(ctx));
     });
     const int nblk = (L.n + kPinWalkThreads - 1) / kPinWalkThreads;
     const dim3 gw(nblk), bw(kPinWalkThreads);
     with_method(method, [&](auto M) {
-        hipLaunchKernelGGL((k_pin_occ_walk<M>), gw, bw, 0, ctx->stream, lv, K, ec, P, ctx->pin_keys, ctx->pin_vals, ctx->pin_lists, ctx->pin_partials);
+        hipLaunchKernelGGL((k_pin_occ_walk<M>), gw, bw, 0, ctx->stream, lv, K, ec, P, ctx->pin_keys.get(), ctx->pin_vals.get(), pin_lists(ctx), ctx->pin_partials.get());
     });
     SolveCfg cfg;
     cfg.level = level; cfg.mode = 1; cfg.forced = 0; cfg.max_iters = ctx->p.max_iters; cfg.n_pixels = L.n;
@@ -1717,16 +1683,14 @@ extern "C" int rgbd360_warp_indices_pinhole(rgbd360_ctx* ctx, int level, const f
     hipSetDevice(ctx->p.device);
     if ((rc = pin_prepare_level(ctx, level)) != 0) return rc;
     const Level& L = ctx->levels[level];
-    int32_t* d_out = nullptr;
-    HIPC(ctx, hipMalloc(&d_out, (size_t)L.n * 2 * sizeof(int32_t)));
+    DevBuf<int32_t> d_out;
+    HIPC(ctx, d_out.ensure((size_t)L.n * 2));
     Pose16 P;
     memcpy(P.v, pose, sizeof(P.v));
     hipLaunchKernelGGL(k_warp_indices_pinhole, dim3((L.n + 255) / 256), dim3(256), 0, ctx->stream, pin_level_dev(L), pin_level_K(ctx, level),
-                       P, d_out);
-    hipError_t e = hipMemcpyAsync(host_out_rc, d_out, (size_t)L.n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    hipFree(d_out);
-    HIPC(ctx, e);
+                       P, d_out.get());
+    HIPC(ctx, hipMemcpyAsync(host_out_rc, d_out, (size_t)L.n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
@@ -1744,10 +1708,8 @@ int wi_check(rgbd360_ctx* ctx, int level, const float* pose, int method, bool pi
 
 int wi_ensure(rgbd360_ctx* ctx) {
     const size_t n = (size_t)ctx->levels[0].n;
-    if (ctx->wi_n >= n) return 0;
-    HIPC(ctx, hipMalloc(&ctx->wi_winner, n * sizeof(int32_t)));
-    HIPC(ctx, hipMalloc(&ctx->wi_stage, 4 * n * sizeof(float)));
-    ctx->wi_n = n;
+    HIPC(ctx, ctx->wi_winner.ensure(n));
+    HIPC(ctx, ctx->wi_stage.ensure(4 * n));
     return 0;
 }
 
@@ -1779,7 +1741,7 @@ int wi_host(rgbd360_ctx* ctx, int level, const float* pose, int method, float* w
     const size_t n = (size_t)ctx->levels[level].n;
     float* const host[4] = {warped_gray, warped_depth, diff_gray, diff_depth};
     float* dev[4];
-    for (int k = 0; k < 4; ++k) dev[k] = host[k] ? ctx->wi_stage + k * ctx->wi_n : nullptr;
+    for (int k = 0; k < 4; ++k) dev[k] = host[k] ? ctx->wi_stage + k * ctx->wi_winner.capacity() : nullptr;
     if ((rc = wi_launch<PINHOLE>(ctx, level, pose, method, ctx->wi_winner, WarpImagesOut{dev[0], dev[1], dev[2], dev[3]})) != 0) return rc;
     for (int k = 0; k < 4; ++k)
         if (host[k]) HIPC(ctx, hipMemcpyAsync(host[k], dev[k], n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -1823,14 +1785,15 @@ extern "C" int rgbd360_time_warp_images(rgbd360_ctx* ctx, int level, const float
     Pose16 P;
     memcpy(P.v, pose, sizeof(P.v));
     const dim3 grid = level_pixel_grid(L, kPixelThreads);
-    const WarpImagesOut out = {ctx->wi_stage, ctx->wi_stage + ctx->wi_n, ctx->wi_stage + 2 * ctx->wi_n, ctx->wi_stage + 3 * ctx->wi_n};
+    const size_t wi_n = ctx->wi_winner.capacity();
+    const WarpImagesOut out = {ctx->wi_stage, ctx->wi_stage + wi_n, ctx->wi_stage + 2 * wi_n, ctx->wi_stage + 3 * wi_n};
     int32_t* const winner = ctx->wi_winner;
     for (int what = 0; what < 4; ++what) {
         auto one = [&]() {
             if (what == 0) hipLaunchKernelGGL(k_warp_winner<false>, grid, dim3(kPixelThreads), 0, ctx->stream, lv, K, P, winner);
             if (what == 1) hipLaunchKernelGGL(k_warp_resolve<false>, grid, dim3(kPixelThreads), 0, ctx->stream, lv, K, P, method, ctx->p.thres_sal_photo, (const int32_t*)winner, out);
             if (what == 2) (void)wi_launch<false>(ctx, level, pose, method, winner, out);
-            if (what == 3) hipLaunchKernelGGL(k_warp_indices, grid, dim3(kPixelThreads), 0, ctx->stream, lv, P, (int32_t*)ctx->wi_stage);      // 8 of the staging's 16 B/px
+            if (what == 3) hipLaunchKernelGGL(k_warp_indices, grid, dim3(kPixelThreads), 0, ctx->stream, lv, P, (int32_t*)ctx->wi_stage.get());      // 8 of the staging's 16 B/px
         };
         if (what == 0) HIPC(ctx, hipMemsetAsync(winner, 0xff, (size_t)L.n * sizeof(int32_t), ctx->stream));
         one();      // warm-up

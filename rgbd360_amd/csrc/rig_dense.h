@@ -374,9 +374,9 @@ struct rgbd360_rig {
     float cam[4] = {0, 0, 0, 0};
     float Rt[r360::kMaxRigSensors][16], Rt_inv[r360::kMaxRigSensors][16];
     SeqEngine* E = nullptr;           // buffers + fused set-up of S "slots" (one per sensor), created at the first frame
-    double* h_tot = nullptr;          // pinned, [S][32]
+    PinnedBuf<double> h_tot{hostwait::kPublishedFlags};      // [S][32]
     hostwait::SpinTag tag;
-    unsigned* d_ticket = nullptr;     // device counter of k_rig_reduce's blocks
+    DevBuf<unsigned> d_ticket;        // device counter of k_rig_reduce's blocks
     bool have_src = false, have_trg = false;
     float sal_thr = -1.f;             // useSaliency(true) on the per-sensor objects: thresSaliency (RPI.h:217); < 0 = off
     int index_libm = 0;               // rgbd360_rig_set_index_arithmetic: 1 = the warp in the reference's arithmetic (k_eval_rig<M, 1>)
@@ -421,14 +421,14 @@ int rig_set_frames(rgbd360_rig* R, bool target, const uint8_t* const* rgb, size_
         R->rows = rows; R->cols = cols;
     }
     SeqEngine* E = R->E;
+    const size_t dpx = depth_type == 0 ? 2 : 4;
     int rc = seq_ensure_stage(E, depth_type);
     if (rc) return rfail(R, rc, E->err);
-    const size_t dpx = depth_type == 0 ? 2 : 4;
     FramePtrs fp;
     memset(&fp, 0, sizeof(fp));
     for (int s = 0; s < R->S; ++s) {
-        uint8_t* const s_rgb = E->stage_rgb[0] + (size_t)s * E->stage_rgb_frame;
-        uint8_t* const s_depth = E->stage_depth[0] + (size_t)s * E->stage_depth_frame;
+        uint8_t* const s_rgb = E->ring.rgb[0] + s * E->frame_bytes(3);
+        uint8_t* const s_depth = E->ring.depth[0] + s * E->frame_bytes(dpx);
         const hipError_t e = copy_frame_h2d(s_rgb, s_depth, rgb[s], rgb_step, depth[s], depth_step, depth_type, rows, cols, E->stream);
         if (e != hipSuccess) return rfail(R, -(int)e - 1000, hipGetErrorString(e));
         fp.rgb[s] = s_rgb;
@@ -515,11 +515,11 @@ int rig_eval(rgbd360_rig* R, int level, const float* T, int method, RigSums* out
     const dim3 g(L.nblocks, R->S), b(kEvalThreads);
     with_choice<0, 1>(R->index_libm != 0, [&](auto Lm) {
         with_method(method, [&](auto M) {
-            hipLaunchKernelGGL((k_eval_rig<M, Lm>), g, b, 0, E->stream, L.srcRec, L.trgP[0], L.trgD[0], L.rows, L.cols, L.n, K, ec, P, E->d_partials,
+            hipLaunchKernelGGL((k_eval_rig<M, Lm>), g, b, 0, E->stream, L.srcRec.get(), L.trgP[0].get(), L.trgD[0].get(), L.rows, L.cols, L.n, K, ec, P, E->d_partials.get(),
                                E->partials_stride, L.chunk, R->sal_thr, Q);
         });
     });
-    hipLaunchKernelGGL(k_rig_reduce, dim3(R->S), dim3(256), 0, E->stream, E->d_partials, E->partials_stride, L.nblocks, R->h_tot, R->d_ticket,
+    hipLaunchKernelGGL(k_rig_reduce, dim3(R->S), dim3(256), 0, E->stream, E->d_partials.get(), E->partials_stride, L.nblocks, R->h_tot.get(), R->d_ticket.get(),
                        R->tag.h, ++R->tag.seq);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hostwait::wait(R->tag, E->stream);      // (spin on a pinned tag: one round trip per LM evaluation)
@@ -557,9 +557,7 @@ void rgbd360_rig_destroy(rgbd360_rig* R) {
     if (!R) return;
     hipSetDevice(R->p.device);
     seq_free(R->E);
-    if (R->h_tot) hipHostFree(R->h_tot);
     hostwait::spin_tag_free(&R->tag);
-    if (R->d_ticket) hipFree(R->d_ticket);
     delete R;
 }
 
@@ -581,13 +579,9 @@ int rgbd360_rig_create(const rgbd360_params* p, int n_sensors, const float* Rt, 
         memcpy(R->Rt[s], Rt + 16 * s, sizeof(float) * 16);
         rigid_inverse(R->Rt[s], R->Rt_inv[s]);
     }
-    if (hipHostMalloc((void**)&R->h_tot, sizeof(double) * kNumPartials * kMaxRigSensors, hostwait::kPublishedFlags) != hipSuccess ||
-        hostwait::spin_tag_init(&R->tag) != hipSuccess || hipMalloc(&R->d_ticket, sizeof(unsigned)) != hipSuccess ||
-        hipMemset(R->d_ticket, 0, sizeof(unsigned)) != hipSuccess) {
-        if (R->h_tot) hipHostFree(R->h_tot);
-        hostwait::spin_tag_free(&R->tag);
-        if (R->d_ticket) hipFree(R->d_ticket);
-        delete R;
+    if (R->h_tot.ensure((size_t)kNumPartials * kMaxRigSensors) != hipSuccess || hostwait::spin_tag_init(&R->tag) != hipSuccess ||
+        R->d_ticket.ensure(1) != hipSuccess || hipMemset(R->d_ticket, 0, sizeof(unsigned)) != hipSuccess) {
+        rgbd360_rig_destroy(R);
         return -103;
     }
     *out = R;
@@ -624,17 +618,16 @@ int rgbd360_rig_warp_indices(rgbd360_rig* R, int level, const float pose[16], in
     RigPosesRef Q;
     rig_poses(R, pose, &P, &Q);
     const size_t bytes = (size_t)R->S * L.n * 2 * sizeof(int32_t);
-    int32_t* d_out = nullptr;
-    hipError_t e = hipMalloc(&d_out, bytes);
+    DevBuf<int32_t> d_out;
+    hipError_t e = d_out.ensure(bytes / sizeof(int32_t));
     if (e != hipSuccess) return rfail(R, -(int)e - 1000, hipGetErrorString(e));
     const dim3 g((L.n + 255) / 256, R->S);
     with_choice<0, 1>(R->index_libm != 0, [&](auto Lm) {
-        hipLaunchKernelGGL(k_rig_warp_indices<Lm>, g, dim3(256), 0, E->stream, L.srcRec, L.rows, L.cols, L.n, rig_level_K(R, level), P, Q, chain, d_out);
+        hipLaunchKernelGGL(k_rig_warp_indices<Lm>, g, dim3(256), 0, E->stream, L.srcRec.get(), L.rows, L.cols, L.n, rig_level_K(R, level), P, Q, chain, d_out.get());
     });
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(host_out_rc, d_out, bytes, hipMemcpyDeviceToHost, E->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(E->stream);
-    hipFree(d_out);
     if (e != hipSuccess) return rfail(R, -(int)e - 1000, hipGetErrorString(e));
     return 0;
 }

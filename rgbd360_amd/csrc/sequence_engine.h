@@ -16,40 +16,39 @@
 namespace {
 
 struct SeqLevel : LevelGeom {      // geometry, tables and work split as a one-pair context has them (level_geom.h)
-    float *gray = nullptr, *depth = nullptr;                                    // [P][n] planes of levels >= 1 (level 0 is never stored)
-    float4* srcRec = nullptr;                                                   // [P][n]
-    F3 *trgP[2] = {nullptr, nullptr}, *trgD[2] = {nullptr, nullptr};            // [P][n] x 2: the records of a frame are built when it
-                                                                                // arrives as a source, one round before it is the target
-    float *sinT = nullptr, *cosT = nullptr, *sinP = nullptr, *cosP = nullptr;
-    float2 *tabT = nullptr, *tabP = nullptr;      // interleaved {sin, cos} (recompute form of the pass)
+    DevBuf<float> gray, depth;                    // [P][n] planes of levels >= 1 (level 0 is never stored)
+    DevBuf<float4> srcRec;                        // [P][n]
+    DevBuf<F3> trgP[2], trgD[2];                  // [P][n] x 2: the records of a frame are built when it arrives as a source, one round
+                                                  // before it is the target
+    DevBuf<float> sinT, cosT, sinP, cosP;
+    DevBuf<float2> tabT, tabP;                    // interleaved {sin, cos} (recompute form of the pass)
     bool compact = false;                         // source records of this level are {depth, Isrc} (8 B) and k_eval_b re-forms the point
 };
 
 // Frame-store mode of an engine (frame_store.h): the records of a level are not the engine's [P][n] slot buffers but the store's
 // [capacity][n] entry arrays, and slot s of a round aligns entry pt.trg[s] (target) with entry pt.src[s] (source) from its own guess.
-struct StoreLevelView {
+struct StoreLevelView {                   // non-owning: the arrays belong to the store (rgbd360_store::entries)
     float4* src = nullptr;                // [capacity][n] source records (16 B, or 8 B on a compact level)
     F3 *trgP = nullptr, *trgD = nullptr;  // [capacity][n]
 };
 struct StoreView {
     std::vector<StoreLevelView> levels;
     PairTable pt;                         // the pairs of the round in flight (parked slots: entry 0)
-    Pose16* d_guess = nullptr;            // [P] start poses of the round, filled by one async copy in front of it ...
-    Pose16* h_guess = nullptr;            // ... from this pinned array
+    DevBuf<Pose16> d_guess;               // [P] start poses of the round, filled by one async copy in front of it ...
+    PinnedBuf<Pose16> h_guess;            // ... from this pinned array (default flags)
 };
 
 struct SeqEngine {
     rgbd360_params p;
     int P = 0, rows = 0, cols = 0;
-    hipStream_t stream = nullptr, up_stream = nullptr;
-    hipEvent_t up_ev[2] = {nullptr, nullptr}, conv_ev[2] = {nullptr, nullptr};
+    hipStream_t stream = nullptr;
+    UploadRing ring;                  // host-frame sequences: [P] packed frames per slot, frame s at s * frame_bytes(bytes per pixel)
     std::vector<SeqLevel> levels;
-    GNState* d_states = nullptr;
-    GNState* h_states = nullptr;      // pinned
-    double* d_partials = nullptr;
+    DevBuf<GNState> d_states;
+    PinnedBuf<GNState> h_states{hostwait::kPublishedFlags};
+    DevBuf<double> d_partials;
     int partials_stride = 0;          // doubles per slot
-    uint8_t *stage_rgb[2] = {nullptr, nullptr}, *stage_depth[2] = {nullptr, nullptr};      // [P] frames each (host-frame sequences)
-    size_t stage_rgb_frame = 0, stage_depth_frame = 0;
+    size_t frame_bytes(size_t px_bytes) const { return (size_t)rows * cols * px_bytes; }
     int tb = 0;                       // which target-record buffer holds the TARGETS of the round
     int max_eval_blocks = 256;
     int libm = 0;                 // the warp in the reference's libm arithmetic (the owning context's rgbd360_set_index_arithmetic)
@@ -71,22 +70,9 @@ void seq_free(SeqEngine* E) {
     if (!E) return;
     hipSetDevice(E->p.device);
     if (E->stream) hipStreamSynchronize(E->stream);
-    if (E->up_stream) hipStreamSynchronize(E->up_stream);
-    for (SeqLevel& L : E->levels) {
-        hipFree(L.gray); hipFree(L.depth); hipFree(L.srcRec);
-        for (int k = 0; k < 2; ++k) { hipFree(L.trgP[k]); hipFree(L.trgD[k]); }
-        hipFree(L.sinT); hipFree(L.cosT); hipFree(L.sinP); hipFree(L.cosP); hipFree(L.tabT); hipFree(L.tabP);
-    }
-    hipFree(E->d_states); hipFree(E->d_partials);
-    if (E->h_states) hipHostFree(E->h_states);
-    for (int k = 0; k < 2; ++k) {
-        hipFree(E->stage_rgb[k]); hipFree(E->stage_depth[k]);
-        if (E->up_ev[k]) hipEventDestroy(E->up_ev[k]);
-        if (E->conv_ev[k]) hipEventDestroy(E->conv_ev[k]);
-    }
-    if (E->up_stream) hipStreamDestroy(E->up_stream);
+    upload_ring_destroy(E->ring);
     if (E->stream) hipStreamDestroy(E->stream);
-    delete E;
+    delete E;      // every buffer of the engine and of its levels
 }
 
 // alloc: kSeqPlanes = the [P][n] float planes of levels >= 1, kSeqRecords = the [P][n] record buffers.  A frame store's engines
@@ -119,17 +105,17 @@ int seq_create(const rgbd360_params& p, int P, int rows, int cols, int max_eval_
         static_cast<LevelGeom&>(L) = level_geom(r, c, max_eval_blocks);
         const size_t np = (size_t)P * L.n;
         bool ok = true;
-        if (l > 0 && (alloc & kSeqPlanes))
-            ok = ok && hipMalloc(&L.gray, np * sizeof(float)) == hipSuccess && hipMalloc(&L.depth, np * sizeof(float)) == hipSuccess;
-        if (alloc & kSeqRecords) ok = ok && hipMalloc(&L.srcRec, np * sizeof(float4)) == hipSuccess;
-        for (int k = 0; k < 2 && (alloc & kSeqRecords); ++k)
-            ok = ok && hipMalloc(&L.trgP[k], np * sizeof(F3)) == hipSuccess && hipMalloc(&L.trgD[k], np * sizeof(F3)) == hipSuccess;
-        ok = ok && hipMalloc(&L.sinT, c * sizeof(float)) == hipSuccess && hipMalloc(&L.cosT, c * sizeof(float)) == hipSuccess &&
-             hipMalloc(&L.sinP, r * sizeof(float)) == hipSuccess && hipMalloc(&L.cosP, r * sizeof(float)) == hipSuccess;
+        auto need = [&ok](auto& buf, size_t count) { ok = ok && buf.ensure(count) == hipSuccess; };
+        if (l > 0 && (alloc & kSeqPlanes)) { need(L.gray, np); need(L.depth, np); }
+        if (alloc & kSeqRecords) {
+            need(L.srcRec, np);
+            for (int k = 0; k < 2; ++k) { need(L.trgP[k], np); need(L.trgD[k], np); }
+        }
+        need(L.sinT, c); need(L.cosT, c); need(L.sinP, r); need(L.cosP, r);
         if (!ok) return bad("out of device memory for the sequence engine");
-        ok = hipMalloc(&L.tabT, c * sizeof(float2)) == hipSuccess && hipMalloc(&L.tabP, r * sizeof(float2)) == hipSuccess &&
-             upload_angle_tables(angle_tables(L), L.sinT, L.cosT, L.sinP, L.cosP, L.tabT, L.tabP) == hipSuccess;
-        if (!ok) return bad("table upload failed");
+        if (L.tabT.ensure(c) != hipSuccess || L.tabP.ensure(r) != hipSuccess ||
+            upload_angle_tables(angle_tables(L), L.sinT, L.cosT, L.sinP, L.cosP, L.tabT, L.tabP) != hipSuccess)
+            return bad("table upload failed");
         // The engine's launches serve P pairs at once, so its large levels are fed from HBM whatever the image size: they carry the
         // 8-byte {depth, Isrc} source record and k_eval_b re-forms the point (SrcForm<2>: 32 instead of 40 B/px per pass, 32 instead of
         // 40 B/px written by the set-up).  The latency-bound small levels keep the 16-byte record.  RGBD360_SEQ_RECOMPUTE_MIN_PX moves
@@ -140,10 +126,8 @@ int seq_create(const rgbd360_params& p, int P, int rows, int cols, int max_eval_
         r /= 2; c /= 2;
     }
     E->partials_stride = max_blocks * kNumPartials;
-    if (hipMalloc(&E->d_partials, (size_t)P * E->partials_stride * sizeof(double)) != hipSuccess ||
-        hipMalloc(&E->d_states, (size_t)P * sizeof(GNState)) != hipSuccess ||
-        hipMemset(E->d_states, 0, (size_t)P * sizeof(GNState)) != hipSuccess ||
-        hipHostMalloc((void**)&E->h_states, (size_t)P * sizeof(GNState), hostwait::kPublishedFlags) != hipSuccess)
+    if (E->d_partials.ensure((size_t)P * E->partials_stride) != hipSuccess || E->d_states.ensure(P) != hipSuccess ||
+        hipMemset(E->d_states, 0, (size_t)P * sizeof(GNState)) != hipSuccess || E->h_states.ensure(P) != hipSuccess)
         return bad("out of memory for the engine state");
     *out = E;
     return 0;
@@ -153,7 +137,7 @@ LevelDev seq_level_dev(const SeqLevel& L, int tb) {
     LevelDev d;
     fill_level_dev(d, L);
     d.src = L.srcRec; d.trgP = L.trgP[tb]; d.trgD = L.trgD[tb];
-    d.src2 = reinterpret_cast<const float2*>(L.srcRec); d.tabT = L.tabT; d.tabP = L.tabP;
+    d.src2 = reinterpret_cast<const float2*>(L.srcRec.get()); d.tabT = L.tabT; d.tabP = L.tabP;
     return d;
 }
 
@@ -171,10 +155,10 @@ void seq_launch_eval(SeqEngine* E, int level, int method) {
     with_choice<0, 2>(L.compact, [&](auto S) {
         with_method(method, [&](auto M) {
             if (E->sv)
-                hipLaunchKernelGGL((k_eval_p<M, true, S>), g, b, 0, E->stream, E->d_states, lv.src, lv.n, L.chunk, level, L.nblocks, E->d_partials,
+                hipLaunchKernelGGL((k_eval_p<M, true, S>), g, b, 0, E->stream, E->d_states.get(), lv.src, lv.n, L.chunk, level, L.nblocks, E->d_partials.get(),
                                    E->partials_stride, lv, ec, E->sv->pt);
             else
-                hipLaunchKernelGGL((k_eval_b<M, true, S>), g, b, 0, E->stream, E->d_states, lv.src, lv.n, L.chunk, level, L.nblocks, E->d_partials,
+                hipLaunchKernelGGL((k_eval_b<M, true, S>), g, b, 0, E->stream, E->d_states.get(), lv.src, lv.n, L.chunk, level, L.nblocks, E->d_partials.get(),
                                    E->partials_stride, lv, ec);
         });
     });
@@ -186,7 +170,7 @@ void seq_launch_solve(SeqEngine* E, int level, int forced = 0) {
     cfg.level = level; cfg.mode = 0; cfg.forced = forced; cfg.max_iters = E->p.max_iters; cfg.n_pixels = L.n;
     cfg.occ = 0;
     cfg.tol_residual = E->p.tol_residual; cfg.tol_update = E->p.tol_update;
-    hipLaunchKernelGGL(k_solve_b, dim3(E->P), dim3(kSolveThreads), 0, E->stream, E->d_states, E->d_partials, E->partials_stride, L.nblocks, cfg);
+    hipLaunchKernelGGL(k_solve_b, dim3(E->P), dim3(kSolveThreads), 0, E->stream, E->d_states.get(), E->d_partials.get(), E->partials_stride, L.nblocks, cfg);
 }
 
 // guess: the start pose of every slot; a frame-store engine takes one pose per slot from sv->d_guess instead.
@@ -195,11 +179,11 @@ void seq_enqueue_schedule(SeqEngine* E, int pending, bool pending_started, const
     for (int level = pending; level >= 0; --level) {
         if (level == top && !pending_started) {
             if (E->sv) {
-                hipLaunchKernelGGL(k_level_init_p, dim3(E->P), dim3(64), 0, E->stream, E->d_states, E->sv->d_guess, 1, 1, level, live);
+                hipLaunchKernelGGL(k_level_init_p, dim3(E->P), dim3(64), 0, E->stream, E->d_states.get(), E->sv->d_guess.get(), 1, 1, level, live);
             } else {
                 Pose16 Pz;
                 memcpy(Pz.v, guess, sizeof(Pz.v));
-                hipLaunchKernelGGL(k_level_init_b, dim3(E->P), dim3(64), 0, E->stream, E->d_states, Pz, 1, 1, level, live);
+                hipLaunchKernelGGL(k_level_init_b, dim3(E->P), dim3(64), 0, E->stream, E->d_states.get(), Pz, 1, 1, level, live);
             }
         }
         const int n_pairs = (level == top && !pending_started) ? E->chunk_top : (level == 0 ? E->chunk_l0 : E->chunk_mid);
@@ -245,25 +229,16 @@ void seq_frame_setup(SeqEngine* E, const FramePtrs& fp, size_t rgb_step, size_t 
     }
 }
 
+// Both staging slots of the engine's ring for P frames of this depth type.  The image size of an engine is fixed, so only the depth
+// type moves the need: the slots grow for float32 depth and stay that size for uint16 frames afterwards.
 int seq_ensure_stage(SeqEngine* E, int depth_type) {
-    const size_t fr = (size_t)E->rows * E->cols * 3, fd = (size_t)E->rows * E->cols * (depth_type == 0 ? 2 : 4);
-    if (E->stage_rgb_frame == fr && E->stage_depth_frame == fd && E->up_stream) return 0;
-    if (!E->up_stream) {
-        SEQC(E, hipStreamCreateWithFlags(&E->up_stream, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k) {
-            SEQC(E, hipEventCreateWithFlags(&E->up_ev[k], hipEventDisableTiming));
-            SEQC(E, hipEventCreateWithFlags(&E->conv_ev[k], hipEventDisableTiming));
-        }
-    }
-    SEQC(E, hipStreamSynchronize(E->stream));
-    SEQC(E, hipStreamSynchronize(E->up_stream));
-    for (int k = 0; k < 2; ++k) {
-        hipFree(E->stage_rgb[k]); hipFree(E->stage_depth[k]);
-        E->stage_rgb[k] = E->stage_depth[k] = nullptr;
-        SEQC(E, hipMalloc(&E->stage_rgb[k], fr * E->P));
-        SEQC(E, hipMalloc(&E->stage_depth[k], fd * E->P));
-    }
-    E->stage_rgb_frame = fr; E->stage_depth_frame = fd;
+    UploadRing& U = E->ring;
+    const size_t need_rgb = E->frame_bytes(3) * E->P, need_depth = E->frame_bytes(depth_type == 0 ? 2 : 4) * E->P;
+    SEQC(E, U.open());
+    if (U.holds(need_rgb, need_depth, 0) && U.holds(need_rgb, need_depth, 1)) return 0;
+    SEQC(E, hipStreamSynchronize(E->stream));      // nothing in flight reads what is about to be freed
+    SEQC(E, hipStreamSynchronize(U.stream));
+    for (int k = 0; k < 2; ++k) SEQC(E, U.ensure(need_rgb, need_depth, k));
     return 0;
 }
 
@@ -318,6 +293,8 @@ int seq_run_body(SeqEngine* E, int n_slots, const int* a, const int* b, const ui
     for (int s = 0; s < n_slots; ++s) rounds = std::max(rounds, b[s] - a[s]);
     if (rounds == 0) return 0;
     const size_t dpx = depth_type == 0 ? 2 : 4;
+    const size_t fr = E->frame_bytes(3), fd = E->frame_bytes(dpx);      // a staged frame
+    UploadRing& U = E->ring;
     if (!on_device) {
         const int rc = seq_ensure_stage(E, depth_type);
         if (rc) return rc;
@@ -332,14 +309,14 @@ int seq_run_body(SeqEngine* E, int n_slots, const int* a, const int* b, const ui
     auto frame_of = [&](int s, int r, int which) { return which == 0 ? a[s] : a[s] + r + 1; };
     // host frames travel through staging parity `par`: upload on the copy stream (after the parity's previous frames were converted)
     auto upload = [&](int r, int which, int par, unsigned long long live) -> int {
-        SEQC(E, hipStreamWaitEvent(E->up_stream, E->conv_ev[par], 0));
+        SEQC(E, hipStreamWaitEvent(U.stream, U.conv_ev[par], 0));
         for (int s = 0; s < n_slots; ++s) {
             if (!((live >> s) & 1ull)) continue;
             const int f = frame_of(s, r, which);
-            SEQC(E, copy_frame_h2d(E->stage_rgb[par] + (size_t)s * E->stage_rgb_frame, E->stage_depth[par] + (size_t)s * E->stage_depth_frame, rgb[f],
-                                   rgb_step, depth[f], depth_step, depth_type, E->rows, E->cols, E->up_stream));
+            SEQC(E, copy_frame_h2d(U.rgb[par] + s * fr, U.depth[par] + s * fd, rgb[f], rgb_step, depth[f], depth_step, depth_type, E->rows, E->cols,
+                                   U.stream));
         }
-        SEQC(E, hipEventRecord(E->up_ev[par], E->up_stream));
+        SEQC(E, hipEventRecord(U.up_ev[par], U.stream));
         return 0;
     };
     auto frame_ptrs = [&](int r, int which, int par, unsigned long long live, FramePtrs* fp, size_t* rs, size_t* ds) {
@@ -351,8 +328,8 @@ int seq_run_body(SeqEngine* E, int n_slots, const int* a, const int* b, const ui
                 fp->rgb[s] = rgb[f];
                 fp->depth[s] = depth[f];
             } else {
-                fp->rgb[s] = E->stage_rgb[par] + (size_t)s * E->stage_rgb_frame;
-                fp->depth[s] = E->stage_depth[par] + (size_t)s * E->stage_depth_frame;
+                fp->rgb[s] = U.rgb[par] + s * fr;
+                fp->depth[s] = U.depth[par] + s * fd;
             }
         }
         *rs = on_device ? rgb_step : (size_t)E->cols * 3;
@@ -371,17 +348,17 @@ int seq_run_body(SeqEngine* E, int n_slots, const int* a, const int* b, const ui
         if (r == 0) {
             // first targets: frames a[s], target records only, into buffer tb
             frame_ptrs(0, 0, par, live, &fp, &rs, &ds);
-            if (!on_device) SEQC(E, hipStreamWaitEvent(E->stream, E->up_ev[par], 0));
+            if (!on_device) SEQC(E, hipStreamWaitEvent(E->stream, U.up_ev[par], 0));
             seq_frame_setup(E, fp, rs, ds, depth_type, live, 0ull, live, E->tb);
-            if (!on_device) { SEQC(E, hipEventRecord(E->conv_ev[par], E->stream)); par ^= 1; }
+            if (!on_device) { SEQC(E, hipEventRecord(U.conv_ev[par], E->stream)); par ^= 1; }
         }
         // sources of this round; they are the targets of the next one in every slot that has another pair: their target
         // records go into the other buffer now, while the tile is in LDS anyway
         frame_ptrs(r, 1, par, live, &fp, &rs, &ds);
-        if (!on_device) SEQC(E, hipStreamWaitEvent(E->stream, E->up_ev[par], 0));
+        if (!on_device) SEQC(E, hipStreamWaitEvent(E->stream, U.up_ev[par], 0));
         seq_frame_setup(E, fp, rs, ds, depth_type, live, live, live & live_of(r + 1), E->tb ^ 1);
         if (!on_device) {
-            SEQC(E, hipEventRecord(E->conv_ev[par], E->stream));
+            SEQC(E, hipEventRecord(U.conv_ev[par], E->stream));
             par ^= 1;
         }
         seq_enqueue_schedule(E, E->p.n_pyr - 1, false, guess, method, live);
@@ -397,7 +374,7 @@ int seq_run_body(SeqEngine* E, int n_slots, const int* a, const int* b, const ui
         }
         E->tb ^= 1;      // this round's sources are the next round's targets
     }
-    if (E->up_stream) SEQC(E, hipStreamSynchronize(E->up_stream));      // no upload may outlive the caller's buffers
+    if (U.stream) SEQC(E, hipStreamSynchronize(U.stream));      // no upload may outlive the caller's buffers
     return 0;
 }
 
@@ -408,7 +385,7 @@ int seq_run(SeqEngine* E, int n_slots, const int* a, const int* b, const uint8_t
         // an error return left the body early: hipMemcpy2DAsync copies from the caller's host images may still be queued on the copy
         // stream, staged frames unconverted and event waits pending on the engine's stream.  Drain both (errors here change nothing:
         // the call already failed) so that the caller may free its buffers and the kept engine starts its next call clean.
-        if (E->up_stream) (void)hipStreamSynchronize(E->up_stream);
+        if (E->ring.stream) (void)hipStreamSynchronize(E->ring.stream);
         if (E->stream) (void)hipStreamSynchronize(E->stream);
     }
     return rc;
