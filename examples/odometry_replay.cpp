@@ -4,7 +4,7 @@
 //     frame_%03d.rgb  (H*W*3 uint8)   frame_%03d.depth (H*W uint16 mm)
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/odometry_replay.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o odometry_replay
-// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link]
+// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L]]
 //         --sequence: all frames are loaded first and the frame loop runs inside the library (alignSequence)
 //         --multi N:  the same sequence sharded over N GPUs of this node from this one process (rgbd360_multi_*: one host thread
 //                     per device, contiguous shards of pairs, one ncclAllGather of the solved poses over xGMI); prints the
@@ -14,12 +14,17 @@
 //                     (KFsphere_SLAM.cpp:149); prints one extra "pbmap" line per pair
 //         --link:     the same per pair through the one-call form rgbd360::RegisterFrames (planes, RegisterPbMap, seeded dense
 //                     alignment, the reference's isApprox(1e-1) validity test); prints "link <pair> <ok> rel_t ..."
+//         --map FILE: (frame loop and --pbmap only; ignored with a warning otherwise) the global map of OdometryRGBD360.cpp:242-268
+//                     -- every frame is inserted at currentPose into a resident voxel grid (rgbd360::GlobalMap: filterEuclidean's box, transformPointCloud, globalMap +=,
+//                     filterVoxel) and the map is written to FILE as "x y z r g b count" lines; --leaf L: the voxel size (0.05 m)
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
+#include <memory>
 #include <string>
 #include <vector>
 
+#include "rgbd360/GlobalMap.hpp"
 #include "rgbd360/RegisterPhotoICP.hpp"
 #include "rgbd360/RegisterRGBD360.hpp"
 
@@ -67,6 +72,12 @@ int main(int argc, char** argv) {
     align360.setNumPyr(4);
     align360.useSaliency(false);
     rgbd360::Mat4f currentPose = rgbd360::Mat4f::Identity();
+    if (argc > 5) {      // only the frame loop below builds the map
+        const std::string mode = argv[5];
+        if (mode == "--sequence" || mode == "--multi" || mode == "--link")
+            for (int a = 6; a < argc; ++a)
+                if (std::string(argv[a]) == "--map") fprintf(stderr, "warning: --map is ignored with %s\n", mode.c_str());
+    }
     if (argc > 5 && std::string(argv[5]) == "--sequence") {
         std::vector<Frame> frames(n);
         std::vector<rgbd360::ImageView> rgb, depth;
@@ -144,6 +155,17 @@ int main(int argc, char** argv) {
         return 0;
     }
     const bool use_pbmap = argc > 5 && std::string(argv[5]) == "--pbmap";
+    std::string map_file;
+    float leaf = 0.05f;
+    for (int a = 5; a + 1 < argc; ++a) {
+        if (std::string(argv[a]) == "--map") map_file = argv[a + 1];
+        if (std::string(argv[a]) == "--leaf") leaf = (float)atof(argv[a + 1]);
+    }
+    std::unique_ptr<rgbd360::GlobalMap> globalMap;      // declared behind align360: destroyed before its context
+    auto add_to_map = [&](const Frame& f) {                                                      // :242, 266-268
+        if (!globalMap->insert(f.sphereRGB, f.sphereDepth, currentPose, /*convention=*/0))
+            fprintf(stderr, "map full: %lld points dropped\n", globalMap->stats().n_dropped_full);
+    };
     rgbd360::RegisterRGBD360 registerer(/*odometry_config=*/true);
     rgbd360::SegmentParams seg;
     seg.max_depth_change_factor = 0.05f;        // the synthetic frames are full spheres: Frame360_stereo.h:854-882 set-up
@@ -154,6 +176,10 @@ int main(int argc, char** argv) {
     Frame frame1, frame2;
     if (!frame1.load(dir, 0, w, h)) return 3;
     if (use_pbmap) planes1 = rgbd360::segmentPlanes(align360, frame1.sphereDepth, seg);
+    if (!map_file.empty()) {
+        globalMap.reset(new rgbd360::GlobalMap(align360, rgbd360::FilterPointCloud(leaf)));
+        add_to_map(frame1);                                                                     // the first frame, at the identity
+    }
     for (int k = 1; k < n; ++k) {
         if (!frame2.load(dir, k, w, h)) return 3;
         rgbd360::Mat4f guess = rgbd360::Mat4f::Identity();
@@ -174,8 +200,15 @@ int main(int argc, char** argv) {
         printf("pair %d status %d sso %.4f rel_t %.5f %.5f %.5f pose_t %.5f %.5f %.5f\n", k - 1, align360.status(), align360.SSO,
                rel(0, 3), rel(1, 3), rel(2, 3), currentPose(0, 3), currentPose(1, 3), currentPose(2, 3));
         fprintf(stderr, "entropy %d %.5f\n", k - 1, align360.calcEntropy());                     // :207 (commented out in the source)
+        if (globalMap) add_to_map(frame2);
         std::swap(frame1, frame2);
         std::swap(planes1, planes2);
+    }
+    if (globalMap) {
+        FILE* f = fopen(map_file.c_str(), "w");
+        if (!f) return 6;
+        for (const rgbd360::MapPoint& p : globalMap->points()) fprintf(f, "%.6f %.6f %.6f %d %d %d %d\n", p.x, p.y, p.z, p.r, p.g, p.b, p.count);
+        fclose(f);
     }
     return 0;
 }

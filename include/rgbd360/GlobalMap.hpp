@@ -1,0 +1,99 @@
+// rgbd360/GlobalMap.hpp -- the global point-cloud map of the reference's odometry and SLAM programs as a resident voxel grid
+// (rgbd360_map_*, ../rgbd360_hip.h).  Header-only, depends on the C ABI and on the PODs of RegisterPhotoICP.hpp; no Eigen, OpenCV
+// or PCL.  What it replaces, per frame (OdometryRGBD360.cpp:242-268; OdometryKeyFrame360.cpp:316-343, SphereGraphSLAM.cpp:116-137,
+// 193-209, KFsphere_SLAM.cpp:236, 558):
+//     filter.filterEuclidean(frame->sphereCloud);                            FilterPointCloud.h:78-89
+//     pcl::transformPointCloud(*frame->sphereCloud, *tc, currentPose);
+//     *viewer.globalMap += *tc;
+//     filter.filterVoxel(viewer.globalMap);                                  FilterPointCloud.h:92-99
+// becomes   globalMap.insert(frame.sphereRGB, frame.sphereDepth, currentPose);   and   globalMap.points()   when the map is wanted.
+// Two deliberate differences (rgbd360_hip.h): every inserted point has weight one -- the map is the voxel filter applied ONCE to the
+// concatenation of all inserted clouds, where the reference's per-frame re-filter makes the order of the frames decide the result --
+// and the sums are integers instead of PCL's float accumulators.
+#pragma once
+
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "RegisterPhotoICP.hpp"
+
+namespace rgbd360 {
+
+// The two parameter sets of the reference's filter class (FilterPointCloud.h:63-74): the voxel size, and the box
+// x in [-2, 1] (the vertical axis of the sphere clouds), y and z in [-euclideanBox, euclideanBox].
+struct FilterPointCloud {
+    float voxelSize, lo[3], hi[3];
+    explicit FilterPointCloud(float voxelSize_ = 0.05f, float euclideanBox = 4.0f)
+        : voxelSize(voxelSize_), lo{-2.0f, -euclideanBox, -euclideanBox}, hi{1.0f, euclideanBox, euclideanBox} {}
+};
+
+struct MapPoint {      // one voxel: centroid, mean colour (bytes in the order of the inserted images), points it averages
+    float x, y, z;
+    uint8_t r, g, b;
+    int count;
+};
+
+class GlobalMap {
+   public:
+    // The map lives on align's context (device, stream): keep `align` alive and its setters untouched while the map exists.
+    // capacity: voxels the table has room for (rounded up to a power of two, 64 bytes each).
+    GlobalMap(RegisterPhotoICP& align, const FilterPointCloud& filter = FilterPointCloud(), long long capacity = 1 << 22) {
+        rgbd360_ctx* ctx = align.context();
+        const int rc = rgbd360_map_create(ctx, filter.voxelSize, capacity, &map_);
+        if (rc != 0) throw std::runtime_error("rgbd360_map_create (" + std::to_string(rc) + "): " + rgbd360_last_error(ctx));
+        check(rgbd360_map_set_box(map_, filter.lo, filter.hi), "rgbd360_map_set_box");
+    }
+    ~GlobalMap() { rgbd360_map_destroy(map_); }
+    GlobalMap(const GlobalMap&) = delete;
+    GlobalMap& operator=(const GlobalMap&) = delete;
+
+    // A sphere frame at `pose` (world <- frame).  rgb may be an empty view (data == nullptr): the colours stay 0.  convention as in
+    // rgbd360_sphere_cloud: 0 Frame360 (Frame360.h:555-612), 1 Frame360_stereo, 2 RegisterPhotoICP.  Returns false when the table was
+    // full and points of new voxels were dropped (stats().n_dropped_full); everything else throws.
+    bool insert(const ImageView& rgb, const ImageView& depth, const Mat4f& pose, int convention = 0) {
+        if (depth.type == ImageView::U8C3 || (rgb.data && (rgb.type != ImageView::U8C3 || rgb.rows != depth.rows || rgb.cols != depth.cols)))
+            throw std::runtime_error("GlobalMap::insert: an 8UC3 colour image and a 16UC1 / 32FC1 depth image of one size");
+        return full(rgbd360_map_insert_sphere(map_, (const uint8_t*)rgb.data, rgb.step, depth.data, depth.step, depth.type == ImageView::U16C1 ? 0 : 1,
+                                              depth.rows, depth.cols, convention, pose.m, 0, &stats_),
+                    "rgbd360_map_insert_sphere");
+    }
+    // Any cloud in its frame's coordinates: xyz[3 n], rgb3[3 n] or nullptr.
+    bool insert(const float* xyz, const uint8_t* rgb3, long long n, const Mat4f& pose) {
+        return full(rgbd360_map_insert_cloud(map_, xyz, rgb3, n, pose.m, 0, &stats_), "rgbd360_map_insert_cloud");
+    }
+
+    long long size() const { return rgbd360_map_size(map_); }
+    size_t bytes() const { return rgbd360_map_bytes(map_); }
+    void clear() { check(rgbd360_map_clear(map_), "rgbd360_map_clear"); }
+    const rgbd360_map_stats& stats() const { return stats_; }      // of the last insert
+
+    // One point per voxel, sorted by (i_z, i_y, i_x): the order of pcl::VoxelGrid's output.
+    std::vector<MapPoint> points() const {
+        const long long n = size();
+        std::vector<float> xyz((size_t)n * 3);
+        std::vector<uint8_t> rgb((size_t)n * 3);
+        std::vector<int32_t> count((size_t)n);
+        const long long got = n ? rgbd360_map_extract(map_, n, xyz.data(), rgb.data(), count.data(), nullptr) : 0;
+        if (got != n) throw std::runtime_error(std::string("rgbd360_map_extract: ") + rgbd360_map_last_error(map_));
+        std::vector<MapPoint> out((size_t)n);
+        for (size_t k = 0; k < out.size(); ++k)
+            out[k] = {xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2], rgb[3 * k], rgb[3 * k + 1], rgb[3 * k + 2], count[k]};
+        return out;
+    }
+
+    rgbd360_map* handle() { return map_; }
+
+   private:
+    void check(int rc, const char* what) const {
+        if (rc < 0) throw std::runtime_error(std::string(what) + " (" + std::to_string(rc) + "): " + rgbd360_map_last_error(map_));
+    }
+    bool full(int rc, const char* what) const {
+        check(rc, what);
+        return rc != RGBD360_MAP_FULL;
+    }
+    rgbd360_map* map_ = nullptr;
+    rgbd360_map_stats stats_{};
+};
+
+}  // namespace rgbd360

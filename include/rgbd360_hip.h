@@ -40,7 +40,8 @@ enum { RGBD360_PHOTO_CONSISTENCY = 0, RGBD360_DEPTH_CONSISTENCY = 1, RGBD360_PHO
 enum {
     RGBD360_OK = 0,
     RGBD360_ILL_POSED = 1,      /* rank(H + lambda diag H) != 6, RPI.h:4682-4690: pose_out = last accepted pose */
-    RGBD360_NO_VALID_PIXELS = 2 /* the error pass found no residual (the reference would divide by zero) */
+    RGBD360_NO_VALID_PIXELS = 2, /* the error pass found no residual (the reference would divide by zero) */
+    RGBD360_MAP_FULL = 3        /* rgbd360_map_insert_*: points of new voxels found no free slot (within the probe bound) and were dropped (counted) */
 };
 
 /* Replaces the constructor defaults + setters of RegisterPhotoICP (RPI.h:201-221, 224-269) and the
@@ -187,6 +188,70 @@ int  rgbd360_store_occupied(const rgbd360_store* st, int entry);
  * pair). */
 int  rgbd360_store_align(rgbd360_store* st, int n_pairs, const int* trg, const int* src, const float* guesses, int method,
                          int occlusion, int n_inflight, float* poses_out, rgbd360_result* results_out);
+
+/* ---- resident voxel-grid global map (csrc/voxel_map.h) ----------------------------------------------------------------------
+ * The other half of the reference's odometry loop: after the alignment every frame is added to a global point-cloud map,
+ *   filter.filterEuclidean(frame->sphereCloud); currentPose = currentPose * rigidTransf;
+ *   pcl::transformPointCloud(*frame->sphereCloud, *tc, currentPose); *viewer.globalMap += *tc; filter.filterVoxel(viewer.globalMap);
+ * (OdometryRGBD360.cpp:242-268; OdometryKeyFrame360.cpp:316-343, SphereGraphSLAM.cpp:116-137, 193-209, KFsphere_SLAM.cpp:236, 558;
+ * the filter class is FilterPointCloud.h:63-99).  A map is a hash grid in HBM: inserting a frame costs O(frame), not the O(map) of
+ * the reference's re-filtering.  Per input point, in this order:
+ *   1 point   from a sphere image: the point rgbd360_sphere_cloud gives for that pixel and convention, bit for bit; from a cloud: the
+ *             three floats.  Skipped (and not counted as valid) unless all three are finite.
+ *   2 box     in the frame's own coordinates, before the pose: kept iff lo[k] <= p[k] <= hi[k], limits included (pcl::PassThrough).
+ *   3 pose    16 floats, column-major, world <- frame: w_k = ((R_k0 x + R_k1 y) + R_k2 z) + t_k in float32, every product and sum
+ *             rounded on its own (no fused multiply-add).
+ *   4 range   dropped and counted if a w_k is not finite or |w_k| >= 4096.
+ *   5 voxel   i_k = (int)floorf(w_k * inv_leaf), inv_leaf = 1.0f / leaf in float32 (PCL's floor(x * inverse_leaf_size)): the cell
+ *             boundaries do not depend on the cloud's bounds; negative coordinates floor.
+ *   6 sums    per voxel, exact: count, S_k += llrint((double)w_k * 1048576.0) in int64 (half to even), integer sums of r, g, b.
+ * Read-out per occupied voxel: centroid_k = (float)((double)S_k / ((double)count * 1048576.0)), colour_c = S_c / count (integer
+ * division; PCL's float-to-uint8 cast truncates too), the key (i_x, i_y, i_z) and the count.  The result does not depend on the
+ * order in which points or frames arrive and is the same from run to run.
+ * Two deliberate differences from the reference.  Every point has weight one: the map is pcl::VoxelGrid applied ONCE to the
+ * concatenation of all inserted clouds, whereas the reference's per-frame re-filter turns the previous centroid into a single point
+ * of the next average, so that there the order of the frames decides the result.  And the sums are integers instead of PCL's float
+ * accumulators.  (PCL is not part of the reference tree: parity with pcl::VoxelGrid itself is unpinned, as for the other PCL-backed
+ * stages.)
+ * A map is destroyed BEFORE its context and used from one thread at a time, like a store.
+ * Out of scope: removing points, moving the grid, several GPUs, normals, surfaces. */
+typedef struct rgbd360_map rgbd360_map;
+typedef struct { long long n_valid, n_box_rejected, n_out_of_range, n_added, n_dropped_full, n_voxels; } rgbd360_map_stats;
+/* A map of `leaf` metres (>= 0.004) with room for capacity_voxels voxels (rounded up to a power of two, 64 bytes each) on ctx's
+ * device; the box starts as FilterPointCloud's default (FilterPointCloud.h:63-74).  0; -1 bad arguments; -103 out of memory (nothing
+ * stays allocated).  The message of a failed create is the CONTEXT's last error.
+ * A new voxel looks for a free slot in at most 2048 consecutive slots of the table (all of it when the table is smaller): when it
+ * finds none its points are dropped as if the table were full (RGBD360_MAP_FULL), which bounds the cost of a frame on a crowded
+ * table.  Below about 85 % load such a run of taken slots does not occur (probability < 1e-11 per voxel); give the map twice the
+ * voxels expected. */
+int    rgbd360_map_create(rgbd360_ctx* ctx, float leaf, long long capacity_voxels, rgbd360_map** out);
+void   rgbd360_map_destroy(rgbd360_map* map);
+const char* rgbd360_map_last_error(rgbd360_map* map);
+/* bytes of HBM the table occupies */
+size_t rgbd360_map_bytes(const rgbd360_map* map);
+/* filterEuclidean's limits (FilterPointCloud.h:66-71, 78-89): x in [-2, 1], y and z in [-4, 4] by default.  NULL, NULL: no box. */
+int    rgbd360_map_set_box(rgbd360_map* map, const float lo[3], const float hi[3]);
+/* OdometryRGBD360.cpp:242, 266-268 for one sphere frame: images as in rgbd360_set_target (on_device = 0: host images, free when the
+ * call returns; 1: device memory on the map's device), convention as in rgbd360_sphere_cloud, the points formed inside the kernel.
+ * rgb may be NULL: the colour sums stay 0.  stats (may be NULL) is filled per call; n_voxels is the map's size after the call.
+ * 0; RGBD360_MAP_FULL when points of new voxels were dropped (points of voxels already in the table are still added); -1 bad
+ * arguments (a bad convention or depth type, NULL depth or pose: nothing is launched); an empty image returns 0 and touches nothing. */
+int    rgbd360_map_insert_sphere(rgbd360_map* map, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step,
+                                 int depth_type, int rows, int cols, int convention, const float pose[16], int on_device,
+                                 rgbd360_map_stats* stats);
+/* The same for n points xyz[3 n] with colours rgb3[3 n] (may be NULL) in the frame's coordinates (pcl::transformPointCloud +
+ * globalMap += of any cloud, e.g. KFsphere_SLAM.cpp:236, 558).  n == 0 returns 0 and touches nothing. */
+int    rgbd360_map_insert_cloud(rgbd360_map* map, const float* xyz, const uint8_t* rgb3, long long n, const float pose[16],
+                                int on_device, rgbd360_map_stats* stats);
+/* occupied voxels */
+long long rgbd360_map_size(rgbd360_map* map);
+int    rgbd360_map_clear(rgbd360_map* map);
+/* The filtered map (what filterVoxel leaves in viewer.globalMap, OdometryRGBD360.cpp:268): per voxel the centroid xyz[3], colour
+ * rgb3[3], count and key key3[3] = (i_x, i_y, i_z); any pointer may be NULL.  Returns the map's size and writes min(size, max_out)
+ * records.  _extract: host arrays, sorted ascending by (i_z, i_y, i_x) -- the order of PCL's idx = i0 + i1 dx + i2 dx dy.
+ * _extract_dev: device arrays, unsorted (which records are written when max_out < size is not defined).  Negative: an error. */
+long long rgbd360_map_extract(rgbd360_map* map, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3);
+long long rgbd360_map_extract_dev(rgbd360_map* map, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3);
 
 /* ---- one process, several GPUs (BASELINE.json configs[3]) ---------------------------------------------------
  * The sequence path shards by independent frame pairs: device d gets the contiguous pairs rgbd360_shard_range(n_frames-1, d,

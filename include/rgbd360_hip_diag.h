@@ -73,6 +73,16 @@ int rgbd360_time_eval_kernel(rgbd360_ctx* ctx, int level, const float pose[16], 
  * the warp alone, the yardstick for what scatter and resolve add.  Outputs go to the context's staging. */
 int rgbd360_time_warp_images(rgbd360_ctx* ctx, int level, const float pose[16], int method, int reps, float avg_us[4]);
 
+/* The voxel map's kernels (rgbd360_map_*, rgbd360_hip.h) under HIP events on a sphere frame in device memory, averages over `reps`
+ * rounds in microseconds: avg_us[0] k_vmap_insert into the EMPTY map, [1] k_vmap_insert into the map that already holds the frame's
+ * voxels (the steady state of odometry), [2] k_vmap_extract (centroids only), [3] ONE k_sphere_cloud_s4 launch of the same size,
+ * [4] a device-to-device copy of the frame's input bytes (the copy rate of the input-bytes floor).  *global_updates (may be NULL):
+ * slot updates the insert into the empty map issued after on-chip combining.  The map is cleared first and holds the frame twice
+ * afterwards. */
+int rgbd360_map_time_kernels(rgbd360_map* map, const uint8_t* rgb_dev, size_t rgb_step, const void* depth_dev, size_t depth_step,
+                             int depth_type, int rows, int cols, int convention, const float pose[16], int reps, float avg_us[5],
+                             long long* global_updates);
+
 /* The same timer with the launches rotating over n_ctx contexts of one device (each with its own copy of a frame pair) on
  * ctxs[0]'s stream: once n_ctx x the level's working set exceeds the 256 MiB Infinity Cache every launch is fed from HBM. */
 int rgbd360_time_eval_kernel_rotating(rgbd360_ctx* const* ctxs, int n_ctx, int level, const float pose[16], int method,

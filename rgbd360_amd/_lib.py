@@ -28,6 +28,9 @@ SYMBOLS = [
     "rgbd360_store_create", "rgbd360_store_destroy", "rgbd360_store_last_error", "rgbd360_store_entry_bytes", "rgbd360_store_put",
     "rgbd360_store_occupied", "rgbd360_store_align",
     "rgbd360_warp_images", "rgbd360_warp_images_dev", "rgbd360_warp_images_pinhole", "rgbd360_time_warp_images",
+    "rgbd360_map_create", "rgbd360_map_destroy", "rgbd360_map_last_error", "rgbd360_map_bytes", "rgbd360_map_set_box",
+    "rgbd360_map_insert_sphere", "rgbd360_map_insert_cloud", "rgbd360_map_size", "rgbd360_map_clear", "rgbd360_map_extract",
+    "rgbd360_map_extract_dev", "rgbd360_map_time_kernels",
 ]
 
 
@@ -64,6 +67,10 @@ class Plane(C.Structure):
                 ("color_count", C.c_int), ("color_nrgb", C.c_float * 3), ("color_dev", C.c_float * 3), ("intensity", C.c_float),
                 ("hist_h", C.c_float * 74), ("hull_n", C.c_int), ("hull", (C.c_float * 3) * 64),
                 ("color_mode_count", C.c_int), ("color_mode", C.c_float * 3), ("intensity_mode", C.c_float), ("color_concentration", C.c_float)]
+
+
+class MapStats(C.Structure):       # rgbd360_map_stats
+    _fields_ = [(n, C.c_longlong) for n in ("n_valid", "n_box_rejected", "n_out_of_range", "n_added", "n_dropped_full", "n_voxels")]
 
 
 class PbmapParams(C.Structure):
@@ -220,5 +227,23 @@ def load() -> C.CDLL:
     L.rgbd360_store_put.argtypes = [vp, i32, vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32]
     L.rgbd360_store_occupied.argtypes = [vp, i32]
     L.rgbd360_store_align.argtypes = [vp, i32, vp, vp, f32p, i32, i32, i32, f32p, vp]
+    ll = C.c_longlong
+    L.rgbd360_map_create.argtypes = [vp, C.c_float, ll, C.POINTER(vp)]
+    L.rgbd360_map_destroy.argtypes = [vp]
+    L.rgbd360_map_destroy.restype = None
+    L.rgbd360_map_last_error.argtypes = [vp]
+    L.rgbd360_map_last_error.restype = C.c_char_p
+    L.rgbd360_map_bytes.argtypes = [vp]
+    L.rgbd360_map_bytes.restype = C.c_size_t
+    L.rgbd360_map_set_box.argtypes = [vp, vp, vp]
+    L.rgbd360_map_insert_sphere.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, C.POINTER(MapStats)]
+    L.rgbd360_map_insert_cloud.argtypes = [vp, vp, vp, ll, f32p, i32, C.POINTER(MapStats)]
+    L.rgbd360_map_size.argtypes = [vp]
+    L.rgbd360_map_size.restype = ll
+    L.rgbd360_map_clear.argtypes = [vp]
+    for f in (L.rgbd360_map_extract, L.rgbd360_map_extract_dev):
+        f.argtypes = [vp, ll, vp, vp, vp, vp]
+        f.restype = ll
+    L.rgbd360_map_time_kernels.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, vp, C.POINTER(ll)]
     _lib = L
     return L

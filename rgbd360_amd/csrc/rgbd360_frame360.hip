@@ -776,14 +776,10 @@ int f360_planes_dev(F360State* ctx, int rows, int cols, int min_inliers, float a
     *n_planes = np;
     return 0;
 }
-// organised cloud of one spherical depth image -> ctx->f_xyz (device); the per-row/column sin/cos tables follow the
-// reference's float expressions and are computed on the host (rows + cols values)
-// defer_to_edge_kernel: tables and depth are put in place, the points themselves are left to k_f360_edge_bits<true> (the next stage
-// of rgbd360_frame_planes), which forms them anyway
-int sphere_cloud_dev(F360State* ctx, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
-                     bool depth_on_device = false, bool defer_to_edge_kernel = false) {
-    if (convention < 0 || convention > 2 || (depth_type != 0 && depth_type != 1)) return fail(ctx, -1, "bad arguments");
-    const size_t dpx = depth_type == 0 ? 2 : 4;
+// The angle tables of a rows x cols sphere image in `convention` (0 .. 2), resident in ctx->f_tab: sin / cos of the azimuth per column,
+// then sin / cos of the polar angle per row.  They follow the reference's float expressions and are computed on the host (rows + cols
+// values).  Shared by the sphere cloud and the voxel map's image insert (voxel_map.h).
+int sphere_tables_dev(F360State* ctx, int rows, int cols, int convention) {
     if (!(ctx->f_tab && ctx->f_tab_rows == rows && ctx->f_tab_cols == cols && ctx->f_tab_conv == convention)) {      // else: the angle tables of this geometry are already on the device
         const size_t ntab = (size_t)2 * cols + 2 * rows;
         std::vector<float> tab(ntab);
@@ -836,6 +832,16 @@ int sphere_cloud_dev(F360State* ctx, const void* depth, size_t depth_step, int d
         HIPC(ctx, hipStreamSynchronize(ctx->stream));      // `tab` (pageable) must outlive the copy
         ctx->f_tab_rows = rows; ctx->f_tab_cols = cols; ctx->f_tab_conv = convention;
     }
+    return 0;
+}
+// organised cloud of one spherical depth image -> ctx->f_xyz (device)
+// defer_to_edge_kernel: tables and depth are put in place, the points themselves are left to k_f360_edge_bits<true> (the next stage
+// of rgbd360_frame_planes), which forms them anyway
+int sphere_cloud_dev(F360State* ctx, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                     bool depth_on_device = false, bool defer_to_edge_kernel = false) {
+    if (convention < 0 || convention > 2 || (depth_type != 0 && depth_type != 1)) return fail(ctx, -1, "bad arguments");
+    const size_t dpx = depth_type == 0 ? 2 : 4;
+    if (const int rc = sphere_tables_dev(ctx, rows, cols, convention)) return rc;
     const void* d_depth = depth;
     size_t d_step = depth_step;
     if (!depth_on_device) {
@@ -1247,6 +1253,10 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// the resident voxel-grid global map (rgbd360_map_*)
+// ---------------------------------------------------------------------------------------------------------
+#include "voxel_map.h"
 
 #ifdef RGBD360_HULL_DBG
 extern "C" int rgbd360_debug_hull_stats(unsigned long long* out /* [4096][8] */) {

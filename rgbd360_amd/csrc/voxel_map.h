@@ -1,0 +1,645 @@
+// voxel_map.h -- a resident voxel-grid global map built from posed frames: the map half of the reference's odometry loop
+//   filter.filterEuclidean(frame->sphereCloud); currentPose = currentPose * rigidTransf;
+//   pcl::transformPointCloud(*frame->sphereCloud, *tc, currentPose); *viewer.globalMap += *tc; filter.filterVoxel(viewer.globalMap);
+// (OdometryRGBD360.cpp:242-268; the same steps at OdometryKeyFrame360.cpp:316-343, SphereGraphSLAM.cpp:116-137, 193-209,
+// KFsphere_SLAM.cpp:236, 558; the filter class is FilterPointCloud.h:63-99).  Part of the Frame360 translation unit
+// (rgbd360_frame360.hip includes it behind its helpers: F360State, HIPC, sphere_tables_dev).
+//
+// Definition, per input point and in this order (tests/voxel_map_reference.py restates it in numpy):
+//   1 point   from a sphere image: r360::sphere_point of the pixel, the bits of rgbd360_sphere_cloud; from a cloud: the three floats.
+//             Skipped unless all three are finite.
+//   2 box     in the frame's own coordinates, BEFORE the pose (filterEuclidean precedes transformPointCloud): kept iff
+//             lo[k] <= p[k] <= hi[k], limits included (pcl::PassThrough).
+//   3 pose    w_k = ((R_k0 x + R_k1 y) + R_k2 z) + t_k in float32, every product and sum rounded on its own (no fused multiply-add).
+//   4 range   dropped and counted if a w_k is not finite or |w_k| >= 4096.
+//   5 voxel   i_k = (int)floorf(w_k * inv_leaf), inv_leaf = 1.0f / leaf (PCL's floor(x * inverse_leaf_size)); the cell boundaries
+//             do not depend on the cloud's bounds.
+//   6 sums    per voxel: count, S_k += llrint((double)w_k * 2^20) in int64 (the product is exact, half to even), integer sums of
+//             r, g, b.  Integer sums do not depend on the order of arrival: the map is the same from run to run and whatever the
+//             order of the frames (the fixed-point moments of the plane stage, frame360_kernels.h).
+// Read-out per occupied voxel: centroid_k = (float)((double)S_k / ((double)count * 2^20)), colour = S_c / count (integer division),
+// the key and the count.
+//
+// Two deliberate differences from the reference:
+//   * every point has weight one: the map is pcl::VoxelGrid applied ONCE to the concatenation of all inserted clouds.  The reference
+//     re-filters the accumulated map for every frame (O(map) per frame), which turns the previous centroid into a single point of
+//     the next average: there the order of the frames decides the result.  Insertion here is O(frame).
+//   * the sums are integers, not PCL's float accumulators.
+//
+// The table: open addressing with linear probing in HBM, a power of two of 64-byte slots {key, count, Sx, Sy, Sz, Sr, Sg, Sb}, all
+// 64-bit words.  key = the three biased 21-bit indices packed (i_z, i_y, i_x from the top: ascending keys are the order of PCL's
+// idx = i0 + i1 dx + i2 dx dy), ~0 = empty, claimed by compare-and-swap; a key never changes once set and nothing is removed.
+//
+//   k_vmap_insert   one lane per point (four per thread, 256 apart: the shape of k_sphere_cloud_s4).  Neighbouring pixels share
+//                   voxels, so the block first merges its 1024 points in a 512-entry LDS hash (LDS atomics); then one lane per
+//                   occupied LDS entry finds or claims the global slot, and eight lanes per entry add its seven sums over the
+//                   slot's 64 contiguous bytes: one global update per distinct key per workgroup.  (The add phase walks all 512
+//                   entries and skips the empty ones, so a wave-instruction carries as many slots as eight consecutive entries
+//                   hold; listing the occupied entries densely first is the open alternative, to be decided by measurement.)  A
+//                   point whose LDS probe sequence (16) is exhausted goes to the global table on its own.  A new voxel that finds
+//                   no free slot is dropped and counted; points of voxels already in the table are still added.
+//   probe bound     a key's probe sequence in HBM ends after kMaxProbes = 2048 slots (the whole table when it is smaller): a key not
+//                   found by then is dropped and counted as if the table were full.  Without the bound a full table would make
+//                   every new key walk all of it (a frame of new voxels in a full 2^22-slot table: 10^11 dependent loads, one
+//                   kernel running for minutes).  With it a key costs at most 128 KiB of loads.  A linear-probing run of length L at
+//                   load a has probability about exp(-(a - 1 - ln a) L): below 1e-11 at a = 0.85 and L = 2048, so the bound binds
+//                   only above about 90 % load -- size the table for twice the voxels expected.
+//   k_vmap_extract  one lane per slot; a wave reserves its output range with one counter add and every lane stores its record.
+#pragma once
+
+struct rgbd360_map {
+    rgbd360_ctx* ctx = nullptr;
+    F360State* s = nullptr;              // the context's Frame360 state: device, stream, the resident angle tables (not owned)
+    float leaf = 0.f, inv_leaf = 0.f;
+    unsigned long long n_slots = 0;      // a power of two
+    bool has_box = true;
+    float lo[3] = {-2.f, -4.f, -4.f}, hi[3] = {1.f, 4.f, 4.f};      // FilterPointCloud.h:66-71
+    long long n_voxels = 0;
+    long long last_updates = 0;          // global updates of the last insert call (measurement)
+    std::string err;
+    DevBuf<unsigned long long> table, d_stats;
+    PinnedBuf<unsigned long long> h_stats;
+    DevBuf<uint8_t> up_depth, up_rgb;    // a host frame / cloud on its way to the kernel
+    DevBuf<float> x_xyz;                 // the host read-out's device side
+    DevBuf<uint8_t> x_rgb;
+    DevBuf<int32_t> x_count, x_key;
+};
+
+namespace vmap {
+
+constexpr int kThreads = 256, kPerThread = 4, kTile = kThreads * kPerThread;
+constexpr int kLdsSlots = 512, kLdsProbes = 16;
+constexpr unsigned long long kMaxProbes = 2048;             // of one key in the HBM table (the head comment: probe bound)
+constexpr int kFields = 8;                                  // 64-bit words per slot: key, count, Sx, Sy, Sz, Sr, Sg, Sb
+constexpr unsigned long long kEmpty = ~0ull;
+constexpr int kBias = 1 << 20;                              // |i_k| <= 4096 / 0.004 * (1 + 2^-23) < 2^20
+constexpr double kFix = 1048576.0;
+enum { kStValid, kStBox, kStRange, kStAdded, kStDropped, kStNew, kStUpdates, kStExtract, kStWords };
+
+struct Params {
+    float pose[16];
+    float lo[3], hi[3];
+    int has_box;
+    float inv_leaf;
+};
+struct Source {                  // SRC 0: a sphere image; SRC 1: a cloud of n points
+    const void* depth;
+    size_t depth_step;
+    const uint8_t* rgb;          // 8UC3 rows / n x 3 bytes; null: the colour sums stay 0
+    size_t rgb_step;
+    int depth_type, rows, cols, convention;
+    const float *sin_theta, *cos_theta, *sin_phi, *cos_phi;
+    const float* xyz;
+    long long n;
+};
+
+__host__ __device__ inline unsigned long long mix64(unsigned long long k) {      // (the 64-bit finaliser of MurmurHash3)
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return k;
+}
+
+// steps 1-6 of one point: 0 skipped, 1 outside the box, 2 out of range, 3 kept (key and the three fixed-point terms)
+__device__ __forceinline__ int classify(const Params& P, float x, float y, float z, unsigned long long& key, long long f[3]) {
+#pragma clang fp contract(off)
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) return 0;
+    if (P.has_box && !(P.lo[0] <= x && x <= P.hi[0] && P.lo[1] <= y && y <= P.hi[1] && P.lo[2] <= z && z <= P.hi[2])) return 1;
+    float w[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) w[k] = ((P.pose[k] * x + P.pose[k + 4] * y) + P.pose[k + 8] * z) + P.pose[k + 12];
+    if (!(fabsf(w[0]) < 4096.f && fabsf(w[1]) < 4096.f && fabsf(w[2]) < 4096.f)) return 2;
+    unsigned long long i[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        i[k] = (unsigned long long)((int)floorf(w[k] * P.inv_leaf) + kBias);
+        f[k] = llrint((double)w[k] * kFix);
+    }
+    key = (i[2] << 42) | (i[1] << 21) | i[0];
+    return 3;
+}
+
+// the slot of `key`, claimed if the key is new; -1: the key is new and no free slot lies within the probe bound
+__device__ __forceinline__ long long find_or_claim(unsigned long long* table, unsigned long long mask, unsigned long long key, bool& claimed) {
+    unsigned long long slot = mix64(key) & mask;
+    const unsigned long long n_probes = mask < kMaxProbes ? mask + 1 : kMaxProbes;
+    for (unsigned long long p = 0; p < n_probes; ++p) {
+        unsigned long long* kp = table + slot * kFields;
+        unsigned long long k0 = __hip_atomic_load(kp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k0 == kEmpty) {
+            k0 = atomicCAS(kp, kEmpty, key);
+            if (k0 == kEmpty) {
+                claimed = true;
+                return (long long)slot;
+            }
+        }
+        if (k0 == key) return (long long)slot;
+        slot = (slot + 1) & mask;
+    }
+    return -1;
+}
+
+template <int SRC>
+__global__ __launch_bounds__(kThreads) void k_vmap_insert(Params P, Source src, unsigned long long* __restrict__ table, unsigned long long mask,
+                                                          unsigned long long* __restrict__ stats) {
+    __shared__ unsigned long long s_key[kLdsSlots];
+    __shared__ unsigned long long s_sum[3][kLdsSlots];
+    __shared__ unsigned s_cnt[kLdsSlots], s_rgb[3][kLdsSlots];
+    __shared__ long long s_slot[kLdsSlots];
+    __shared__ unsigned s_stat[kStWords];
+    const int t = threadIdx.x;
+    for (int h = t; h < kLdsSlots; h += kThreads) {
+        s_key[h] = kEmpty;
+        s_sum[0][h] = s_sum[1][h] = s_sum[2][h] = 0;
+        s_cnt[h] = s_rgb[0][h] = s_rgb[1][h] = s_rgb[2][h] = 0;
+    }
+    if (t < kStWords) s_stat[t] = 0;
+
+    // all loads of the thread first
+    float x[kPerThread], y[kPerThread], z[kPerThread];
+    unsigned c[kPerThread][3];
+    bool in[kPerThread];
+    if (SRC == 0) {
+        const int r = blockIdx.y;
+        const uint8_t* drow = (const uint8_t*)src.depth + (size_t)r * src.depth_step;
+        const uint8_t* crow = src.rgb ? src.rgb + (size_t)r * src.rgb_step : nullptr;
+        const float sp = src.sin_phi[r], cp = src.cos_phi[r];
+        float d[kPerThread], st[kPerThread], ct[kPerThread];
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const int col = blockIdx.x * kTile + t + kThreads * k;
+            in[k] = col < src.cols;
+            const int cc = in[k] ? col : src.cols - 1;
+            d[k] = src.depth_type == 0 ? 0.001f * (float)((const uint16_t*)drow)[cc] : ((const float*)drow)[cc];
+            st[k] = src.sin_theta[cc];
+            ct[k] = src.cos_theta[cc];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) c[k][q] = crow ? crow[3 * (size_t)cc + q] : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) r360::sphere_point(src.convention, d[k], sp, cp, st[k], ct[k], x[k], y[k], z[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const long long i = (long long)blockIdx.x * kTile + t + kThreads * k;
+            in[k] = i < src.n;
+            const size_t ii = in[k] ? (size_t)i : 0;
+            x[k] = src.xyz[3 * ii];
+            y[k] = src.xyz[3 * ii + 1];
+            z[k] = src.xyz[3 * ii + 2];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) c[k][q] = src.rgb ? src.rgb[3 * ii + q] : 0u;
+        }
+    }
+    __syncthreads();
+
+    unsigned tally = 0;      // this thread's points: valid | outside the box << 10 | out of range << 20 (a wave's sums stay below 1024)
+#pragma unroll
+    for (int k = 0; k < kPerThread; ++k) {
+        unsigned long long key = 0;
+        long long f[3] = {0, 0, 0};
+        const int cls = in[k] ? classify(P, x[k], y[k], z[k], key, f) : 0;
+        tally += (cls >= 1 ? 1u : 0u) + (cls == 1 ? 1u << 10 : 0u) + (cls == 2 ? 1u << 20 : 0u);
+        if (cls != 3) continue;
+        unsigned h = (unsigned)(mix64(key) >> 40) & (kLdsSlots - 1);      // (bits the global table's index does not use below 2^40 slots)
+        bool merged = false;
+        for (int p = 0; p < kLdsProbes && !merged; ++p) {
+            unsigned long long k0 = __hip_atomic_load(&s_key[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (k0 == kEmpty) {
+                k0 = atomicCAS(&s_key[h], kEmpty, key);
+                if (k0 == kEmpty) k0 = key;
+            }
+            if (k0 == key) {
+                atomicAdd(&s_cnt[h], 1u);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) atomicAdd(&s_sum[q][h], (unsigned long long)f[q]);
+                if (src.rgb) {
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) atomicAdd(&s_rgb[q][h], c[k][q]);
+                }
+                merged = true;
+            }
+            h = (h + 1) & (kLdsSlots - 1);
+        }
+        if (!merged) {       // the block's table is crowded around this key: the point goes to the map on its own
+            bool claimed = false;
+            const long long slot = find_or_claim(table, mask, key, claimed);
+            if (claimed) atomicAdd(&s_stat[kStNew], 1u);
+            if (slot < 0) {
+                atomicAdd(&s_stat[kStDropped], 1u);
+            } else {
+                unsigned long long* rec = table + (unsigned long long)slot * kFields;
+                atomicAdd(rec + 1, 1ull);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) atomicAdd(rec + 2 + q, (unsigned long long)f[q]);
+                if (src.rgb) {
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) atomicAdd(rec + 5 + q, (unsigned long long)c[k][q]);
+                }
+                atomicAdd(&s_stat[kStAdded], 1u);
+                atomicAdd(&s_stat[kStUpdates], 1u);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) tally += __shfl_xor(tally, off);
+    if ((t & 63) == 0 && tally) {
+        atomicAdd(&s_stat[kStValid], tally & 1023u);
+        atomicAdd(&s_stat[kStBox], (tally >> 10) & 1023u);
+        atomicAdd(&s_stat[kStRange], tally >> 20);
+    }
+    __syncthreads();
+
+    // one lane per merged entry: its slot in the map
+    for (int h = t; h < kLdsSlots; h += kThreads) {
+        long long slot = -1;
+        if (s_key[h] != kEmpty) {
+            bool claimed = false;
+            slot = find_or_claim(table, mask, s_key[h], claimed);
+            if (claimed) atomicAdd(&s_stat[kStNew], 1u);
+            atomicAdd(&s_stat[slot < 0 ? kStDropped : kStAdded], s_cnt[h]);
+            if (slot >= 0) atomicAdd(&s_stat[kStUpdates], 1u);
+        }
+        s_slot[h] = slot;
+    }
+    __syncthreads();
+    // eight lanes per entry: lane q adds word q of the slot (word 0 is the key); empty entries are skipped
+    for (int e = t >> 3; e < kLdsSlots; e += kThreads / 8) {
+        const int q = t & 7;
+        const long long slot = s_slot[e];
+        if (slot < 0 || q == 0) continue;
+        const unsigned long long v = q == 1 ? (unsigned long long)s_cnt[e] : q <= 4 ? s_sum[q - 2][e] : (unsigned long long)s_rgb[q - 5][e];
+        if (v) atomicAdd(table + (unsigned long long)slot * kFields + q, v);
+    }
+    if (t < kStWords && s_stat[t]) atomicAdd(stats + t, (unsigned long long)s_stat[t]);
+}
+
+__global__ __launch_bounds__(256) void k_vmap_clear(unsigned long long* __restrict__ table, unsigned long long n_words) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_words) table[i] = (i & (kFields - 1)) == 0 ? kEmpty : 0ull;
+}
+
+// any output may be null; records beyond max_out are counted, not written
+__global__ __launch_bounds__(256) void k_vmap_extract(const unsigned long long* __restrict__ table, unsigned long long n_slots, long long max_out,
+                                                      unsigned long long* __restrict__ counter, float* __restrict__ xyz, uint8_t* __restrict__ rgb3,
+                                                      int32_t* __restrict__ count, int32_t* __restrict__ key3) {
+    const unsigned long long s = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long* rec = table + (s < n_slots ? s : 0) * kFields;
+    const unsigned long long key = rec[0];
+    const bool occupied = s < n_slots && key != kEmpty;
+    const unsigned long long wave = __ballot(occupied);
+    unsigned long long base = 0;
+    if (lane == 0 && wave) base = atomicAdd(counter, (unsigned long long)__popcll(wave));      // one add per wave
+    base = __shfl(base, 0);
+    const unsigned long long o = base + (unsigned long long)__popcll(wave & ((1ull << lane) - 1ull));
+    if (!occupied || (long long)o >= max_out) return;
+    const unsigned long long n = rec[1];
+    if (xyz) {
+        const double den = (double)n * kFix;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xyz[3 * o + k] = (float)((double)(long long)rec[2 + k] / den);
+    }
+    if (rgb3) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) rgb3[3 * o + k] = (uint8_t)(rec[5 + k] / n);
+    }
+    if (count) count[o] = (int32_t)n;
+    if (key3) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) key3[3 * o + k] = (int32_t)((key >> (21 * k)) & 0x1fffffull) - kBias;
+    }
+}
+
+}  // namespace vmap
+
+namespace {
+
+int vmap_fail(rgbd360_map* m, int code, const char* msg) {
+    m->err = msg;
+    return code;
+}
+int vmap_clear_dev(rgbd360_map* m) {
+    const unsigned long long words = m->n_slots * vmap::kFields;
+    hipLaunchKernelGGL(vmap::k_vmap_clear, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, m->s->stream, m->table, words);
+    HIPC(m, hipGetLastError());
+    m->n_voxels = 0;
+    return 0;
+}
+vmap::Params vmap_params(const rgbd360_map* m, const float pose[16]) {
+    vmap::Params P;
+    memcpy(P.pose, pose, sizeof(P.pose));
+    for (int k = 0; k < 3; ++k) {
+        P.lo[k] = m->lo[k];
+        P.hi[k] = m->hi[k];
+    }
+    P.has_box = m->has_box ? 1 : 0;
+    P.inv_leaf = m->inv_leaf;
+    return P;
+}
+void vmap_fill_stats(const rgbd360_map* m, const unsigned long long* w, rgbd360_map_stats* st) {
+    if (!st) return;
+    st->n_valid = w ? (long long)w[vmap::kStValid] : 0;
+    st->n_box_rejected = w ? (long long)w[vmap::kStBox] : 0;
+    st->n_out_of_range = w ? (long long)w[vmap::kStRange] : 0;
+    st->n_added = w ? (long long)w[vmap::kStAdded] : 0;
+    st->n_dropped_full = w ? (long long)w[vmap::kStDropped] : 0;
+    st->n_voxels = m->n_voxels;
+}
+// the insert kernel over `src` (device memory), enqueued on the stream; the statistics words are cleared in front of it
+int vmap_launch_insert(rgbd360_map* m, const vmap::Params& P, const vmap::Source& src, bool cloud) {
+    HIPC(m, hipMemsetAsync(m->d_stats, 0, vmap::kStWords * sizeof(unsigned long long), m->s->stream));
+    const dim3 grid = cloud ? dim3((unsigned)((src.n + vmap::kTile - 1) / vmap::kTile)) : dim3((src.cols + vmap::kTile - 1) / vmap::kTile, src.rows);
+    with_choice<0, 1>(cloud, [&](auto S) {
+        hipLaunchKernelGGL((vmap::k_vmap_insert<decltype(S)::value>), grid, dim3(vmap::kThreads), 0, m->s->stream, P, src, m->table, m->n_slots - 1, m->d_stats);
+    });
+    HIPC(m, hipGetLastError());
+    return 0;
+}
+// ... and how an insert call ends: the statistics on the host, the map's size brought up to date
+int vmap_finish_insert(rgbd360_map* m, rgbd360_map_stats* stats) {
+    HIPC(m, hipMemcpyAsync(m->h_stats, m->d_stats, vmap::kStWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->s->stream));
+    HIPC(m, hipStreamSynchronize(m->s->stream));
+    const unsigned long long* w = m->h_stats;
+    m->n_voxels += (long long)w[vmap::kStNew];
+    m->last_updates = (long long)w[vmap::kStUpdates];
+    vmap_fill_stats(m, w, stats);
+    if (w[vmap::kStDropped]) {
+        m->err = "the map is full: points of new voxels were dropped";
+        return RGBD360_MAP_FULL;
+    }
+    return 0;
+}
+// what an insert_sphere call checks before anything is launched; 1: an empty image (nothing to do)
+int vmap_check_sphere(rgbd360_map* m, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type, int rows, int cols,
+                      int convention, const float* pose) {
+    if (!depth || !pose) return vmap_fail(m, -1, "depth and pose must not be null");
+    if (convention < 0 || convention > 2 || (depth_type != 0 && depth_type != 1)) return vmap_fail(m, -1, "bad convention or depth type");
+    if (rows < 0 || cols < 0 || (long long)rows * cols >= (1ll << 30)) return vmap_fail(m, -1, "bad image size");
+    if (rows == 0 || cols == 0) return 1;
+    if (depth_step < (size_t)cols * (depth_type == 0 ? 2 : 4) || (rgb && rgb_step < (size_t)cols * 3)) return vmap_fail(m, -1, "row step shorter than a row");
+    return 0;
+}
+// the kernel's view of a sphere image in device memory, with the context's angle tables of that geometry
+int vmap_sphere_source(rgbd360_map* m, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type, int rows, int cols,
+                       int convention, vmap::Source& src) {
+    if (const int rc = sphere_tables_dev(m->s, rows, cols, convention)) {
+        m->err = m->s->err;
+        return rc;
+    }
+    const float* tab = m->s->f_tab;
+    src = {depth, depth_step, rgb, rgb_step, depth_type, rows, cols, convention, tab, tab + cols, tab + 2 * cols, tab + 2 * cols + rows, nullptr, 0};
+    return 0;
+}
+}  // namespace
+
+extern "C" int rgbd360_map_create(rgbd360_ctx* ctx_, float leaf, long long capacity_voxels, rgbd360_map** out) {
+    if (out) *out = nullptr;
+    if (!ctx_ || !out) return -1;
+    F360_ENTER(ctx_);
+    if (!(leaf >= 0.004f) || !std::isfinite(leaf) || capacity_voxels < 1 || capacity_voxels > (1ll << 30))
+        return fail(ctx, -1, "rgbd360_map_create: leaf must be >= 0.004 m and capacity in 1 .. 2^30 voxels");
+    hipSetDevice(ctx->p.device);
+    rgbd360_map* m = new rgbd360_map();
+    m->ctx = ctx_;
+    m->s = ctx;
+    m->leaf = leaf;
+    m->inv_leaf = 1.0f / leaf;
+    m->n_slots = 1;
+    while (m->n_slots < (unsigned long long)capacity_voxels) m->n_slots <<= 1;
+    if (m->table.ensure(m->n_slots * vmap::kFields) != hipSuccess || m->d_stats.ensure(vmap::kStWords) != hipSuccess ||
+        m->h_stats.ensure(vmap::kStWords) != hipSuccess) {
+        (void)hipGetLastError();
+        delete m;
+        return fail(ctx, -103, "rgbd360_map_create: out of memory");
+    }
+    if (vmap_clear_dev(m) != 0 || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        ctx->err = "rgbd360_map_create: " + m->err;
+        delete m;
+        return -103;
+    }
+    *out = m;
+    return 0;
+}
+extern "C" void rgbd360_map_destroy(rgbd360_map* m) {
+    if (!m) return;
+    hipSetDevice(m->s->p.device);
+    hipStreamSynchronize(m->s->stream);
+    delete m;
+}
+extern "C" const char* rgbd360_map_last_error(rgbd360_map* m) { return m ? m->err.c_str() : "null map"; }
+extern "C" size_t rgbd360_map_bytes(const rgbd360_map* m) { return m ? (size_t)m->n_slots * vmap::kFields * sizeof(unsigned long long) : 0; }
+extern "C" int rgbd360_map_set_box(rgbd360_map* m, const float lo[3], const float hi[3]) {
+    if (!m) return -1;
+    m->err.clear();
+    if (!lo != !hi) return vmap_fail(m, -1, "both limits or none");
+    m->has_box = lo != nullptr;
+    for (int k = 0; k < 3 && lo; ++k) {
+        m->lo[k] = lo[k];
+        m->hi[k] = hi[k];
+    }
+    return 0;
+}
+
+extern "C" int rgbd360_map_insert_sphere(rgbd360_map* m, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type,
+                                         int rows, int cols, int convention, const float pose[16], int on_device, rgbd360_map_stats* stats) {
+    if (!m) return -1;
+    m->err.clear();
+    const int chk = vmap_check_sphere(m, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, pose);
+    if (chk < 0) return chk;
+    vmap_fill_stats(m, nullptr, stats);
+    if (chk == 1) return 0;
+    hipSetDevice(m->s->p.device);
+    if (!on_device) {        // packed copies of the host images; the caller's memory is free when the call returns (vmap_finish_insert waits)
+        const size_t drow = (size_t)cols * (depth_type == 0 ? 2 : 4);
+        HIPC(m, m->up_depth.ensure(drow * rows));
+        HIPC(m, hipMemcpy2DAsync(m->up_depth, drow, depth, depth_step, drow, rows, hipMemcpyHostToDevice, m->s->stream));
+        depth = m->up_depth;
+        depth_step = drow;
+        if (rgb) {
+            HIPC(m, m->up_rgb.ensure((size_t)cols * 3 * rows));
+            HIPC(m, hipMemcpy2DAsync(m->up_rgb, (size_t)cols * 3, rgb, rgb_step, (size_t)cols * 3, rows, hipMemcpyHostToDevice, m->s->stream));
+            rgb = m->up_rgb;
+            rgb_step = (size_t)cols * 3;
+        }
+    }
+    vmap::Source src;
+    if (const int rc = vmap_sphere_source(m, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, src)) return rc;
+    if (const int rc = vmap_launch_insert(m, vmap_params(m, pose), src, false)) return rc;
+    return vmap_finish_insert(m, stats);
+}
+
+extern "C" int rgbd360_map_insert_cloud(rgbd360_map* m, const float* xyz, const uint8_t* rgb3, long long n, const float pose[16], int on_device,
+                                        rgbd360_map_stats* stats) {
+    if (!m) return -1;
+    m->err.clear();
+    if (n < 0 || n >= (1ll << 40)) return vmap_fail(m, -1, "bad point count");
+    if (n > 0 && (!xyz || !pose)) return vmap_fail(m, -1, "xyz and pose must not be null");
+    vmap_fill_stats(m, nullptr, stats);
+    if (n == 0) return 0;
+    hipSetDevice(m->s->p.device);
+    if (!on_device) {
+        HIPC(m, m->up_depth.ensure((size_t)n * 3 * sizeof(float)));
+        HIPC(m, hipMemcpyAsync(m->up_depth, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, m->s->stream));
+        xyz = reinterpret_cast<const float*>(m->up_depth.get());
+        if (rgb3) {
+            HIPC(m, m->up_rgb.ensure((size_t)n * 3));
+            HIPC(m, hipMemcpyAsync(m->up_rgb, rgb3, (size_t)n * 3, hipMemcpyHostToDevice, m->s->stream));
+            rgb3 = m->up_rgb;
+        }
+    }
+    const vmap::Source src = {nullptr, 0, rgb3, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, xyz, n};
+    if (const int rc = vmap_launch_insert(m, vmap_params(m, pose), src, true)) return rc;
+    return vmap_finish_insert(m, stats);
+}
+
+extern "C" long long rgbd360_map_size(rgbd360_map* m) { return m ? m->n_voxels : -1; }
+extern "C" int rgbd360_map_clear(rgbd360_map* m) {
+    if (!m) return -1;
+    m->err.clear();
+    hipSetDevice(m->s->p.device);
+    if (const int rc = vmap_clear_dev(m)) return rc;
+    HIPC(m, hipStreamSynchronize(m->s->stream));
+    return 0;
+}
+
+namespace {
+// the extract kernel into device arrays (any may be null), complete when the call returns
+int vmap_extract_dev(rgbd360_map* m, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3) {
+    unsigned long long* counter = m->d_stats + vmap::kStExtract;
+    HIPC(m, hipMemsetAsync(counter, 0, sizeof(unsigned long long), m->s->stream));
+    hipLaunchKernelGGL(vmap::k_vmap_extract, dim3((unsigned)((m->n_slots + 255) / 256)), dim3(256), 0, m->s->stream, m->table, m->n_slots, max_out, counter,
+                       xyz, rgb3, count, key3);
+    HIPC(m, hipGetLastError());
+    HIPC(m, hipStreamSynchronize(m->s->stream));
+    return 0;
+}
+}  // namespace
+
+extern "C" long long rgbd360_map_extract_dev(rgbd360_map* m, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3) {
+    if (!m) return -1;
+    m->err.clear();
+    if (max_out < 0) return vmap_fail(m, -1, "max_out must not be negative");
+    hipSetDevice(m->s->p.device);
+    if (m->n_voxels == 0 || max_out == 0) return m->n_voxels;
+    if (const int rc = vmap_extract_dev(m, max_out, xyz, rgb3, count, key3)) return rc;
+    return m->n_voxels;
+}
+
+extern "C" long long rgbd360_map_extract(rgbd360_map* m, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3) {
+    if (!m) return -1;
+    m->err.clear();
+    if (max_out < 0) return vmap_fail(m, -1, "max_out must not be negative");
+    const size_t n = (size_t)m->n_voxels, n_out = std::min(n, (size_t)max_out);
+    if (n_out == 0) return m->n_voxels;
+    hipSetDevice(m->s->p.device);
+    // the whole map unsorted (the first max_out of the SORTED map are wanted), then the order of the keys on the host
+    HIPC(m, m->x_xyz.ensure(3 * n));
+    HIPC(m, m->x_rgb.ensure(3 * n));
+    HIPC(m, m->x_count.ensure(n));
+    HIPC(m, m->x_key.ensure(3 * n));
+    if (const int rc = vmap_extract_dev(m, (long long)n, m->x_xyz, m->x_rgb, m->x_count, m->x_key)) return rc;
+    std::vector<float> h_xyz(3 * n);
+    std::vector<uint8_t> h_rgb(3 * n);
+    std::vector<int32_t> h_count(n), h_key(3 * n);
+    HIPC(m, hipMemcpy(h_key.data(), m->x_key, 3 * n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (xyz) HIPC(m, hipMemcpy(h_xyz.data(), m->x_xyz, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    if (rgb3) HIPC(m, hipMemcpy(h_rgb.data(), m->x_rgb, 3 * n, hipMemcpyDeviceToHost));
+    if (count) HIPC(m, hipMemcpy(h_count.data(), m->x_count, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<size_t> order(n);
+    for (size_t k = 0; k < n; ++k) order[k] = k;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {      // (i_z, i_y, i_x) ascending: PCL's idx = i0 + i1 dx + i2 dx dy
+        for (int q = 2; q >= 0; --q)
+            if (h_key[3 * a + q] != h_key[3 * b + q]) return h_key[3 * a + q] < h_key[3 * b + q];
+        return false;
+    });
+    for (size_t o = 0; o < n_out; ++o) {
+        const size_t k = order[o];
+        for (int q = 0; q < 3; ++q) {
+            if (xyz) xyz[3 * o + q] = h_xyz[3 * k + q];
+            if (rgb3) rgb3[3 * o + q] = h_rgb[3 * k + q];
+            if (key3) key3[3 * o + q] = h_key[3 * k + q];
+        }
+        if (count) count[o] = h_count[k];
+    }
+    return m->n_voxels;
+}
+
+// measurement (rgbd360_hip_diag.h)
+extern "C" int rgbd360_map_time_kernels(rgbd360_map* m, const uint8_t* rgb_dev, size_t rgb_step, const void* depth_dev, size_t depth_step, int depth_type,
+                                        int rows, int cols, int convention, const float pose[16], int reps, float avg_us[5],
+                                        long long* global_updates) {
+    if (!m) return -1;
+    m->err.clear();
+    const int chk = vmap_check_sphere(m, rgb_dev, rgb_step, depth_dev, depth_step, depth_type, rows, cols, convention, pose);
+    if (chk < 0) return chk;
+    if (chk == 1 || reps < 1 || !avg_us) return vmap_fail(m, -1, "bad arguments");
+    F360State* ctx = m->s;
+    hipSetDevice(ctx->p.device);
+    if (const int rc = f360_begin(ctx, rows, cols, 1)) {
+        m->err = ctx->err;
+        return rc;
+    }
+    vmap::Source src;
+    if (const int rc = vmap_sphere_source(m, rgb_dev, rgb_step, depth_dev, depth_step, depth_type, rows, cols, convention, src)) return rc;
+    const vmap::Params P = vmap_params(m, pose);
+    const size_t drow = (size_t)cols * (depth_type == 0 ? 2 : 4), crow = rgb_dev ? (size_t)cols * 3 : 0;
+    HIPC(m, m->up_depth.ensure(drow * rows));
+    if (crow) HIPC(m, m->up_rgb.ensure(crow * rows));
+    hipEvent_t e0 = nullptr, e1 = nullptr;       // made last, destroyed on every path below
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+        if (e0) hipEventDestroy(e0);
+        (void)hipGetLastError();
+        return vmap_fail(m, -103, "hipEventCreate failed");
+    }
+    double sum[5] = {0, 0, 0, 0, 0};
+    int rc = 0;
+    auto timed = [&](int which, auto&& body) {
+        float ms = 0.f;
+        if (rc != 0) return;         // nothing is recorded around a stream that has already failed
+        if (hipEventRecord(e0, ctx->stream) != hipSuccess) rc = vmap_fail(m, -100, "hipEventRecord failed");
+        if (rc == 0) rc = body();
+        if (rc == 0 && (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                        hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+            rc = vmap_fail(m, -100, "timing the kernels failed");
+        sum[which] += (double)ms * 1000.0;
+    };
+    rgbd360_map_stats st;
+    for (int r = 0; r < reps && rc == 0; ++r) {
+        if ((rc = vmap_clear_dev(m)) != 0) break;
+        // (the statistics' clear is a 64-byte memset in front of the kernel, inside the window: it is part of every insert)
+        timed(0, [&] { return vmap_launch_insert(m, P, src, false); });       // an empty map
+        if (rc == 0) rc = std::min(vmap_finish_insert(m, &st), 0);
+        if (global_updates) *global_updates = m->last_updates;
+        timed(1, [&] { return vmap_launch_insert(m, P, src, false); });       // the map holds the frame's voxels: odometry's steady state
+        if (rc == 0) rc = std::min(vmap_finish_insert(m, &st), 0);
+        if (rc == 0 && m->x_xyz.ensure(3 * (size_t)m->n_voxels + 3) != hipSuccess) rc = vmap_fail(m, -103, "out of memory");
+        timed(2, [&] {       // (with the clear of its counter, as in every extract call)
+            hipMemsetAsync(m->d_stats + vmap::kStExtract, 0, sizeof(unsigned long long), ctx->stream);
+            hipLaunchKernelGGL(vmap::k_vmap_extract, dim3((unsigned)((m->n_slots + 255) / 256)), dim3(256), 0, ctx->stream, m->table, m->n_slots, m->n_voxels,
+                               m->d_stats + vmap::kStExtract, m->x_xyz, (uint8_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+            return 0;
+        });
+        timed(3, [&] {
+            hipLaunchKernelGGL(r360::k_sphere_cloud_s4, dim3((cols + 1023) / 1024, rows), dim3(256), 0, ctx->stream, depth_dev, depth_step, depth_type, rows, cols,
+                               convention, src.sin_theta, src.cos_theta, src.sin_phi, src.cos_phi, ctx->f_xyz);
+            return 0;
+        });
+        timed(4, [&] {       // the input bytes once through the device: the copy rate of the floor
+            hipMemcpy2DAsync(m->up_depth, drow, depth_dev, depth_step, drow, rows, hipMemcpyDeviceToDevice, ctx->stream);
+            if (crow) hipMemcpy2DAsync(m->up_rgb, crow, rgb_dev, rgb_step, crow, rows, hipMemcpyDeviceToDevice, ctx->stream);
+            return 0;
+        });
+    }
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    if (rc) {
+        (void)hipGetLastError();
+        return rc;
+    }
+    HIPC(m, hipGetLastError());
+    for (int k = 0; k < 5; ++k) avg_us[k] = (float)(sum[k] / reps);
+    return 0;
+}
