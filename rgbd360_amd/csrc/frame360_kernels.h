@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "device_math.h"      // r360::sphere_point for the fused cloud stage of k_f360_edge_bits
+#include "wave_scan.h"
 
 namespace r360 {
 // Consecutive lanes own consecutive pixels and every lane stores its 12-byte point with ONE instruction (768 contiguous bytes per
@@ -55,6 +56,9 @@ __global__ __launch_bounds__(256) void k_sphere_cloud_s4(const void* __restrict_
 }  // namespace r360
 
 namespace f360 {
+using r360::wave_scan_add;      // wave_scan.h: inclusive add-scan and max-scan (values >= -1) over the 64 lanes of a wave
+using r360::wave_scan_fold;
+using r360::wave_scan_max;
 
 constexpr int kF360R = 12;          // truncation radius of the distance map (>= smoothing_size + max depth / 10)
 
@@ -892,29 +896,6 @@ __global__ __launch_bounds__(kLinkTW) void k_f360_link_flags(const float* __rest
 // pixels (an inclusive max-scan of "column where a run starts"; a lane owns 4 consecutive pixels), so pass 3 only has to
 // join runs vertically.  Invalid pixels get -1.
 constexpr int kRunRowsPerBlock = 4;
-// Inclusive max-scan over the 64 lanes of a wave for values >= -1, on the VALU's data-parallel-primitive paths: shifts by 1, 2, 4, 8 inside
-// the rows of 16 lanes, then lane 15 of a row to the next row and lane 31 to the upper half (lanes without a source take -1).  Twelve vector
-// instructions; six __shfl_up steps are six trips through the LDS crossbar (~100 cycles each for a wave that has the SIMD to itself).
-__device__ __forceinline__ int wave_scan_max(int x) {
-    int t;
-    t = __builtin_amdgcn_update_dpp(-1, x, 0x111, 0xF, 0xF, false); x = t > x ? t : x;      // row_shr:1
-    t = __builtin_amdgcn_update_dpp(-1, x, 0x112, 0xF, 0xF, false); x = t > x ? t : x;      // row_shr:2
-    t = __builtin_amdgcn_update_dpp(-1, x, 0x114, 0xF, 0xF, false); x = t > x ? t : x;      // row_shr:4
-    t = __builtin_amdgcn_update_dpp(-1, x, 0x118, 0xF, 0xF, false); x = t > x ? t : x;      // row_shr:8
-    t = __builtin_amdgcn_update_dpp(-1, x, 0x142, 0xA, 0xF, false); x = t > x ? t : x;      // row_bcast:15 -> rows 1, 3
-    t = __builtin_amdgcn_update_dpp(-1, x, 0x143, 0xC, 0xF, false); x = t > x ? t : x;      // row_bcast:31 -> rows 2, 3
-    return x;
-}
-// inclusive add-scan over the wave for small non-negative counts, same paths (lanes without a source add 0)
-__device__ __forceinline__ int wave_scan_add(int x) {
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);
-    return x;
-}
 // starts / nstarts (optional): the row's run starts as a compact list (row r's k-th start at starts[r cols + k]) for k_f360_ccl_roots_list
 __global__ __launch_bounds__(64 * kRunRowsPerBlock) void k_f360_ccl_runs(const uint8_t* __restrict__ flags, int rows, int cols,
                                                                         int* __restrict__ label, int* __restrict__ starts,
@@ -1272,8 +1253,8 @@ inline bool f360_mom_in_range(int count, float max_abs) {
 __device__ __forceinline__ long long wave_sum_ll(long long v) {
 #define F360_SUM_STEP(ctrl_, rows_)                                                                                    \
     {                                                                                                                  \
-        const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(unsigned long long)v, ctrl_, rows_, 0xF, false);          \
-        const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)((unsigned long long)v >> 32), ctrl_, rows_, 0xF, false);  \
+        const unsigned lo = (unsigned)R360_DPP(0, (unsigned)(unsigned long long)v, ctrl_, rows_);                      \
+        const unsigned hi = (unsigned)R360_DPP(0, (unsigned)((unsigned long long)v >> 32), ctrl_, rows_);              \
         v += (long long)(((unsigned long long)hi << 32) | lo);                                                         \
     }
     F360_SUM_STEP(0x111, 0xF)
@@ -1536,38 +1517,30 @@ __global__ __launch_bounds__(kAggThreads) __attribute__((amdgpu_waves_per_eu(8))
         const bool head = lane == 0 || prev != key;
         const unsigned long long heads = __ballot(head);
         const int seg = __popcll(heads & (~0ull >> (63 - lane)));          // number of heads at or below this lane
-        // segmented add-scan along the runs, on the DPP paths like wave_sum_ll (a source lane counts when it lies in the same run;
-        // runs are contiguous, so lane 15 / lane 31 of the rows below stand for everything of the run below them)
-#define F360_SEG_STEP(ctrl_, rows_)                                                                                        \
-        {                                                                                                                  \
-            const bool take = __builtin_amdgcn_update_dpp(-1, seg, ctrl_, rows_, 0xF, false) == seg;                       \
-            _Pragma("unroll") for (int q = 0; q < 9; ++q) {                                                                \
-                const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(unsigned long long)v[q], ctrl_, rows_, 0xF, false);          \
-                const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)((unsigned long long)v[q] >> 32), ctrl_, rows_, 0xF, false);  \
-                v[q] += take ? (long long)(((unsigned long long)hi << 32) | lo) : 0ll;                                     \
-            }                                                                                                              \
-        }
+        // segmented scans along the runs (wave_scan.h): a source lane counts when it lies in the same run; runs are contiguous, so lane 15 /
+        // lane 31 of the rows below stand for everything of the run below them.
         // the maxima first, on their own (one register across the six steps instead of one more beside the nine sums')
-#define F360_SEG_MAX(ctrl_, rows_)                                                                                         \
-        {                                                                                                                  \
-            const bool take = __builtin_amdgcn_update_dpp(-1, seg, ctrl_, rows_, 0xF, false) == seg;                       \
-            const int mo = __builtin_amdgcn_update_dpp(0, mb, ctrl_, rows_, 0xF, false);                                   \
-            mb = take && mo > mb ? mo : mb;                                                                                \
-        }
-        F360_SEG_MAX(0x111, 0xF)
-        F360_SEG_MAX(0x112, 0xF)
-        F360_SEG_MAX(0x114, 0xF)
-        F360_SEG_MAX(0x118, 0xF)
-        F360_SEG_MAX(0x142, 0xA)
-        F360_SEG_MAX(0x143, 0xC)
-#undef F360_SEG_MAX
-        F360_SEG_STEP(0x111, 0xF)
-        F360_SEG_STEP(0x112, 0xF)
-        F360_SEG_STEP(0x114, 0xF)
-        F360_SEG_STEP(0x118, 0xF)
-        F360_SEG_STEP(0x142, 0xA)
-        F360_SEG_STEP(0x143, 0xC)
-#undef F360_SEG_STEP
+        mb = wave_scan_fold(mb, [seg](int mb, auto ctrl, auto rows) __attribute__((always_inline)) {
+            const bool take = R360_DPP(-1, seg, ctrl.value, rows.value) == seg;
+            const int mo = R360_DPP(0, mb, ctrl.value, rows.value);
+            return take && mo > mb ? mo : mb;
+        });
+        struct Sums { long long v[9]; };      // the nine sums, through the steps by value
+        Sums sm;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) sm.v[q] = v[q];
+        sm = wave_scan_fold(sm, [seg](Sums s, auto ctrl, auto rows) __attribute__((always_inline)) {
+            const bool take = R360_DPP(-1, seg, ctrl.value, rows.value) == seg;
+#pragma unroll
+            for (int q = 0; q < 9; ++q) {
+                const unsigned lo = (unsigned)R360_DPP(0, (unsigned)(unsigned long long)s.v[q], ctrl.value, rows.value);
+                const unsigned hi = (unsigned)R360_DPP(0, (unsigned)((unsigned long long)s.v[q] >> 32), ctrl.value, rows.value);
+                s.v[q] += take ? (long long)(((unsigned long long)hi << 32) | lo) : 0ll;
+            }
+            return s;
+        });
+#pragma unroll
+        for (int q = 0; q < 9; ++q) v[q] = sm.v[q];
         const bool tail = lane == 63 || ((heads >> (lane + 1)) & 1ull);
         if (tail && key >= 0) flush(key, v, mb);
     }

@@ -34,6 +34,7 @@
 // few long runs, so the run lists are a handful of nodes.
 #pragma once
 #include "photo_icp_kernels.h"
+#include "wave_scan.h"
 
 namespace r360 {
 
@@ -48,40 +49,20 @@ constexpr int kOccGenMax = 127;
 constexpr unsigned kOccMulti = 0x80000000u;
 __device__ __forceinline__ int occ_decode(int tagged, int gen) { return (((unsigned)tagged >> 24) & 0x7Fu) == (unsigned)gen ? (tagged & 0xFFFFFF) : -1; }
 
-// Wave scans on the VALU's data-parallel-primitive paths (row_shr 1 / 2 / 4 / 8 inside the rows of 16 lanes, then lane 15 of a row to the
-// next row and lane 31 to the upper half) instead of __shfl_up steps through the LDS crossbar: k_occ_build made 27 crossbar trips per wave,
-// 3456 per CU and launch at 2048 x 1024, on the one LDS unit its four SIMDs share.
-#define R360_DPP(old_, src_, ctrl_, rows_) __builtin_amdgcn_update_dpp((int)(old_), (int)(src_), ctrl_, rows_, 0xF, false)
-__device__ __forceinline__ int occ_scan_max(int x) {                 // inclusive max-scan of values >= 0
-    int t;
-    t = R360_DPP(-1, x, 0x111, 0xF); x = t > x ? t : x;
-    t = R360_DPP(-1, x, 0x112, 0xF); x = t > x ? t : x;
-    t = R360_DPP(-1, x, 0x114, 0xF); x = t > x ? t : x;
-    t = R360_DPP(-1, x, 0x118, 0xF); x = t > x ? t : x;
-    t = R360_DPP(-1, x, 0x142, 0xA); x = t > x ? t : x;
-    t = R360_DPP(-1, x, 0x143, 0xC); x = t > x ? t : x;
-    return x;
-}
+// The scans of the build run on the VALU's data-parallel-primitive paths (wave_scan.h: wave_scan_max, R360_DPP) instead of __shfl_up steps
+// through the LDS crossbar: k_occ_build made 27 crossbar trips per wave, 3456 per CU and launch at 2048 x 1024, on the one LDS unit its
+// four SIMDs share.
 // segmented inclusive max-scan of a 64-bit key over the runs `lead` names (lead = lane of the run's first member, constant along a run,
 // increasing from run to run): a source lane counts when it has the same lead (lanes without a source offer lead -1)
 __device__ __forceinline__ unsigned long long occ_seg_scan_max(unsigned long long key, int lead) {
-    unsigned lo = (unsigned)key, hi = (unsigned)(key >> 32);
-#define R360_SEG_STEP(ctrl_, rows_)                                                                              \
-    {                                                                                                            \
-        const int ol = R360_DPP(-1, lead, ctrl_, rows_);                                                         \
-        const unsigned olo = (unsigned)R360_DPP(0, lo, ctrl_, rows_), ohi = (unsigned)R360_DPP(0, hi, ctrl_, rows_); \
-        const bool take = ol == lead && (ohi > hi || (ohi == hi && olo > lo));                                   \
-        lo = take ? olo : lo;                                                                                    \
-        hi = take ? ohi : hi;                                                                                    \
-    }
-    R360_SEG_STEP(0x111, 0xF)
-    R360_SEG_STEP(0x112, 0xF)
-    R360_SEG_STEP(0x114, 0xF)
-    R360_SEG_STEP(0x118, 0xF)
-    R360_SEG_STEP(0x142, 0xA)
-    R360_SEG_STEP(0x143, 0xC)
-#undef R360_SEG_STEP
-    return ((unsigned long long)hi << 32) | lo;
+    struct Key { unsigned lo, hi; };
+    const Key k = wave_scan_fold(Key{(unsigned)key, (unsigned)(key >> 32)}, [lead](Key k, auto ctrl, auto rows) __attribute__((always_inline)) {
+        const int ol = R360_DPP(-1, lead, ctrl.value, rows.value);
+        const unsigned olo = (unsigned)R360_DPP(0, k.lo, ctrl.value, rows.value), ohi = (unsigned)R360_DPP(0, k.hi, ctrl.value, rows.value);
+        const bool take = ol == lead && (ohi > k.hi || (ohi == k.hi && olo > k.lo));
+        return Key{take ? olo : k.lo, take ? ohi : k.hi};
+    });
+    return ((unsigned long long)k.hi << 32) | k.lo;
 }
 
 // runinfo byte of a source pixel: bit 6 candidate, bit 7 no earlier member of its run is closer, bits 0-5 offset to the run's first pixel
@@ -129,7 +110,7 @@ __device__ __forceinline__ void occ_build_px(const LevelDev& lv, const PoseRT& T
     // Away from the poles and from depth edges no two neighbouring source pixels land on one target pixel: every lane of the wave is a
     // run of its own, and the scans (a third of the kernel's vector instructions) would return what each lane already holds.
     if (__builtin_amdgcn_ballot_w64(!run_head) != 0ull) {      // uniform
-        lead = occ_scan_max(run_head ? lane : 0);            // lane of the run's first member
+        lead = wave_scan_max(run_head ? lane : 0);            // lane of the run's first member
         // segmented inclusive max-scan of the key (1/dist bits, pixel): positive floats order like their bit patterns
         key = occ_seg_scan_max(key, lead);
         // the run's maximum BEFORE this member

@@ -70,6 +70,37 @@ __device__ __forceinline__ unsigned warp_pinhole(const PoseRT& T, float px, floa
     return (unsigned)(ri * cols + ci);
 }
 
+// The two residual rows of the pinhole model, for every pixel body that uses it (k_eval_pinhole, k_pin_occ_walk, k_eval_rig in both
+// arithmetics): the arithmetic alone, contracted per function (float32 data, not index work); the gating is the caller's.
+struct PinRes { float w, res; };      // weight of the row (Huber weight / sigma) and the weighted residual
+// photometric: w = huber(dI) / sigma_photo, res = w dI   (RPI.h:712-721, 906-925)
+__device__ __forceinline__ PinRes pin_photo_res(float gray_trg, float gray_src, const EvalConsts& ec) {
+#pragma clang fp contract(fast)
+    const float photoDiff = gray_trg - gray_src;
+    const float wpf = weight_huber_fast(photoDiff, ec.sigma_photo) * ec.sigma_photo_inv_f;
+    return {wpf, wpf * photoDiff};
+}
+// depth: sigma = sigma_depth Z, w = huber(dD) / sigma, res = w dD with dD = target depth - Z   (RPI.h:722-735, 929-948)
+__device__ __forceinline__ PinRes pin_depth_res(float depth_trg, float Z, const EvalConsts& ec) {
+#pragma clang fp contract(fast)
+    const float depthDiff = depth_trg - Z;
+    const float sd = ec.sigma_depth * Z;
+    const float wd = weight_huber_fast(depthDiff, sd) * fast_rcp(sd);
+    return {wd, wd * depthDiff};
+}
+// w * (image gradient (gx, gy)) * d(pixel) / d(P'): the row's first three entries, (w gx fx / Z, w gy fy / Z, -(w gx fx X + w gy fy Y) / Z^2)
+__device__ __forceinline__ F3 pin_photo_row(float gx, float gy, const PinK& K, float X, float Y, float iz, float iz2, float wpf) {
+#pragma clang fp contract(fast)
+    const float wgx = wpf * gx * K.fx, wgy = wpf * gy * K.fy;
+    return {wgx * iz, wgy * iz, -(wgx * X + wgy * Y) * iz2};
+}
+// the depth row: the same with the depth gradient, and - 1 on Z (the residual's own dependence on the transformed depth)
+__device__ __forceinline__ F3 pin_depth_row(float gdx, float gdy, const PinK& K, float X, float Y, float iz, float iz2, float wd) {
+#pragma clang fp contract(fast)
+    const float gx = gdx * K.fx, gy = gdy * K.fy;
+    return {wd * (gx * iz), wd * (gy * iz), wd * (-(gx * X + gy * Y) * iz2 - 1.f)};
+}
+
 template <int METHOD>
 // The pose of the pass arrives as a kernel argument: the Levenberg-Marquardt loop lives on the host and evaluates one pose per
 // round trip, so there is no device state to gate on and no initialisation launch in front of the pass.
@@ -119,13 +150,11 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_pinhole(LevelDev lv, PinK
             A.nVis += ballot_count(row_on);
             if (vis) {
 #pragma clang fp contract(fast)
-                const float photoDiff = tp.a - s.w;
-                const float wpf = weight_huber_fast(photoDiff, ec.sigma_photo) * ec.sigma_photo_inv_f;
-                const float res = wpf * photoDiff;
-                A.e2p += evis ? res * res : 0.f;
+                const PinRes ph = pin_photo_res(tp.a, s.w, ec);
+                A.e2p += evis ? ph.res * ph.res : 0.f;
                 if (row_on) {
-                    const float wgx = wpf * tp.b * K.fx, wgy = wpf * tp.c * K.fy;
-                    accumulate_row(A, wgx * iz, wgy * iz, -(wgx * X + wgy * Y) * iz2, X, Y, Z, res);
+                    const F3 j = pin_photo_row(tp.b, tp.c, K, X, Y, iz, iz2, ph.w);
+                    accumulate_row(A, j.a, j.b, j.c, X, Y, Z, ph.res);
                 }
             }
         }
@@ -136,14 +165,11 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_pinhole(LevelDev lv, PinK
             A.nVis += ballot_count(row_on);
             if (err_on) {
 #pragma clang fp contract(fast)
-                const float depthDiff = depth2 - Z;
-                const float sd = ec.sigma_depth * Z;
-                const float wd = weight_huber_fast(depthDiff, sd) * fast_rcp(sd);
-                const float res = wd * depthDiff;
-                A.e2d += evis ? res * res : 0.f;
+                const PinRes dp = pin_depth_res(depth2, Z, ec);
+                A.e2d += evis ? dp.res * dp.res : 0.f;
                 if (row_on) {
-                    const float gx = td.b * K.fx, gy = td.c * K.fy;
-                    accumulate_row(A, wd * (gx * iz), wd * (gy * iz), wd * (-(gx * X + gy * Y) * iz2 - 1.f), X, Y, Z, res);
+                    const F3 j = pin_depth_row(td.b, td.c, K, X, Y, iz, iz2, dp.w);
+                    accumulate_row(A, j.a, j.b, j.c, X, Y, Z, dp.res);
                 }
             }
         }
@@ -326,21 +352,10 @@ __global__ __launch_bounds__(kPinWalkThreads) void k_pin_occ_walk(LevelDev lv, P
             bool vis;
             (void)warp_pinhole(T, s.x, s.y, s.z, K, lv.rows, lv.cols, X, Y, Z, iz, vis, lv.libm);
             // the photometric and depth residuals of this pixel on this target (both passes use the same expressions)
-            float wpf = 0.f, rp = 0.f, wd = 0.f, rd = 0.f;
-            {
-#pragma clang fp contract(fast)
-                if (METHOD != 1) {
-                    const float photoDiff = tp.a - s.w;
-                    wpf = weight_huber_fast(photoDiff, ec.sigma_photo) * ec.sigma_photo_inv_f;
-                    rp = wpf * photoDiff;
-                }
-                if (METHOD != 0) {
-                    const float depthDiff = depth2 - Z;
-                    const float sd = ec.sigma_depth * Z;
-                    wd = weight_huber_fast(depthDiff, sd) * fast_rcp(sd);
-                    rd = wd * depthDiff;
-                }
-            }
+            PinRes ph = {0.f, 0.f}, dp = {0.f, 0.f};
+            if (METHOD != 1) ph = pin_photo_res(tp.a, s.w, ec);
+            if (METHOD != 0) dp = pin_depth_res(depth2, Z, ec);
+            const float rp = ph.res, rd = dp.res;
             if (v & kPinOccErr) {                    // errorPhotoICP_Occ1 / _Occ2
                 if (!(buf_e > 0.f && iz < buf_e)) {  // RPI.h:1248-1250
                     buf_e = iz;
@@ -361,13 +376,12 @@ __global__ __launch_bounds__(kPinWalkThreads) void k_pin_occ_walk(LevelDev lv, P
                     buf_h = iz;
                     // rows exist where the photometric residual was stored and is non-zero (RPI.h:1523, 1531: both sums test it)
                     if (METHOD != 1 && sal_p && rp != 0.f) {
-#pragma clang fp contract(fast)
                         const float iz2 = iz * iz;
-                        const float wgx = wpf * tp.b * K.fx, wgy = wpf * tp.c * K.fy;
-                        accumulate_row(A, wgx * iz, wgy * iz, -(wgx * X + wgy * Y) * iz2, X, Y, Z, rp);
+                        const F3 j = pin_photo_row(tp.b, tp.c, K, X, Y, iz, iz2, ph.w);
+                        accumulate_row(A, j.a, j.b, j.c, X, Y, Z, rp);
                         if (METHOD == 2 && sal_d && fin_d) {
-                            const float gx = td.b * K.fx, gy = td.c * K.fy;
-                            accumulate_row(A, wd * (gx * iz), wd * (gy * iz), wd * (-(gx * X + gy * Y) * iz2 - 1.f), X, Y, Z, rd);
+                            const F3 jd = pin_depth_row(td.b, td.c, K, X, Y, iz, iz2, dp.w);
+                            accumulate_row(A, jd.a, jd.b, jd.c, X, Y, Z, rd);
                         }
                     }
                 }

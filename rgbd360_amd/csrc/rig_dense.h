@@ -104,6 +104,12 @@ __device__ __forceinline__ bool rig_warp(const float* Mq, const float* Ri, const
     return sane;
 }
 
+// b = R_s a, a residual row taken from sensor s into the rig frame: R_s = (Rt_s^-1 rotation)^T, i.e. b_i = sum_j Ri[j][i] a_j
+__device__ __forceinline__ F3 to_rig(const float* Ri, const F3& a) {
+#pragma clang fp contract(fast)
+    return {Ri[0] * a.a + Ri[4] * a.b + Ri[8] * a.c, Ri[1] * a.a + Ri[5] * a.b + Ri[9] * a.c, Ri[2] * a.a + Ri[6] * a.b + Ri[10] * a.c};
+}
+
 // One pixel of k_eval_rig in the reference's arithmetic: the error terms from chain 0, the Jacobian rows from chain 1.  The target is
 // gathered once, and a second time only by the lanes whose chain-1 pixel differs (rare: a projection within rounding of a pixel border).
 template <int METHOD>
@@ -131,20 +137,12 @@ __device__ __forceinline__ void eval_rig_ref_pixel(EvalAcc& A, const float* Ri, 
         if (METHOD != 1) tp = trgP[t1];
         if (METHOD != 0) td = trgD[t1];
     }
-    // b = R_s a: R_s = (Rt_s^-1 rotation)^T, i.e. b_i = sum_j Ri[j][i] a_j
-    auto to_rig = [&](float ax, float ay, float az, float& bx, float& by, float& bz) {
-#pragma clang fp contract(fast)
-        bx = Ri[0] * ax + Ri[4] * ay + Ri[8] * az;
-        by = Ri[1] * ax + Ri[5] * ay + Ri[9] * az;
-        bz = Ri[2] * ax + Ri[6] * ay + Ri[10] * az;
-    };
     // calcPhotoICPError_robot: every visible pixel of chain 0, no saliency test
     if (METHOD != 1) {
         A.nP += ballot_count(vis0);
         if (vis0) {
 #pragma clang fp contract(fast)
-            const float photoDiff = tp0.a - p.w;
-            const float res = weight_huber_fast(photoDiff, ec.sigma_photo) * ec.sigma_photo_inv_f * photoDiff;
+            const float res = pin_photo_res(tp0.a, p.w, ec).res;
             A.e2p += res * res;
         }
     }
@@ -153,9 +151,7 @@ __device__ __forceinline__ void eval_rig_ref_pixel(EvalAcc& A, const float* Ri, 
         A.nD += ballot_count(err_on);
         if (err_on) {
 #pragma clang fp contract(fast)
-            const float depthDiff = td0.a - Z0;                                   // FIX C: chain 0's transformed depth
-            const float sd = ec.sigma_depth * Z0;
-            const float res = weight_huber_fast(depthDiff, sd) * fast_rcp(sd) * depthDiff;
+            const float res = pin_depth_res(td0.a, Z0, ec).res;                   // FIX C: chain 0's transformed depth
             A.e2d += res * res;
         }
     }
@@ -168,29 +164,18 @@ __device__ __forceinline__ void eval_rig_ref_pixel(EvalAcc& A, const float* Ri, 
         const bool row_on = vis && sal_p && (METHOD == 0 || !fin_d || sal_d);
         A.nVis += ballot_count(row_on);
         if (row_on) {
-#pragma clang fp contract(fast)
-            const float photoDiff = tp.a - p.w;
-            const float wpf = weight_huber_fast(photoDiff, ec.sigma_photo) * ec.sigma_photo_inv_f;
-            const float res = wpf * photoDiff;
-            const float wgx = wpf * tp.b * K.fx, wgy = wpf * tp.c * K.fy;
-            float bx, by, bz;
-            to_rig(wgx * iz, wgy * iz, -(wgx * X + wgy * Y) * iz2, bx, by, bz);
-            accumulate_row(A, bx, by, bz, qx, qy, qz, res);
+            const PinRes ph = pin_photo_res(tp.a, p.w, ec);
+            const F3 j = to_rig(Ri, pin_photo_row(tp.b, tp.c, K, X, Y, iz, iz2, ph.w));
+            accumulate_row(A, j.a, j.b, j.c, qx, qy, qz, ph.res);
         }
     }
     if (METHOD != 0) {
         const bool row_on = vis && fin_d && sal_d && (METHOD == 1 || sal_p);
         A.nVis += ballot_count(row_on);
         if (row_on) {
-#pragma clang fp contract(fast)
-            const float depthDiff = td.a - Z;                                     // FIX C
-            const float sd = ec.sigma_depth * Z;
-            const float wd = weight_huber_fast(depthDiff, sd) * fast_rcp(sd);
-            const float res = wd * depthDiff;
-            const float gx = td.b * K.fx, gy = td.c * K.fy;
-            float bx, by, bz;
-            to_rig(wd * (gx * iz), wd * (gy * iz), wd * (-(gx * X + gy * Y) * iz2 - 1.f), bx, by, bz);      // FIX B: - jacobianT36.row(2)
-            accumulate_row(A, bx, by, bz, qx, qy, qz, res);
+            const PinRes dp = pin_depth_res(td.a, Z, ec);                         // FIX C
+            const F3 j = to_rig(Ri, pin_depth_row(td.b, td.c, K, X, Y, iz, iz2, dp.w));      // FIX B: - jacobianT36.row(2)
+            accumulate_row(A, j.a, j.b, j.c, qx, qy, qz, dp.res);
         }
     }
 }
@@ -239,13 +224,6 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_rig(const float4* __restr
         const bool sal_d = !(fabsf(td.b) < ec.thr_depth && fabsf(td.c) < ec.thr_depth);
         const bool fin_d = METHOD != 0 && isfinite(depth2);
         const float iz2 = iz * iz;
-        // b = R_s a: R_s = (Rt_s^-1 rotation)^T, i.e. b_i = sum_j Ri[j][i] a_j
-        auto to_rig = [&](float ax, float ay, float az, float& bx, float& by, float& bz) {
-#pragma clang fp contract(fast)
-            bx = Ri[0] * ax + Ri[4] * ay + Ri[8] * az;
-            by = Ri[1] * ax + Ri[5] * ay + Ri[9] * az;
-            bz = Ri[2] * ax + Ri[6] * ay + Ri[10] * az;
-        };
         if (METHOD != 1) {
             A.nP += ballot_count(vis);                                             // calcPhotoICPError_robot: no saliency test
             // calcHessianGradient_robot: a non-salient intensity gradient skips the pixel (RPI.h:5331-5332); a finite target depth with a
@@ -254,15 +232,11 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_rig(const float4* __restr
             A.nVis += ballot_count(row_on);
             if (vis) {
 #pragma clang fp contract(fast)
-                const float photoDiff = tp.a - p.w;
-                const float wpf = weight_huber_fast(photoDiff, ec.sigma_photo) * ec.sigma_photo_inv_f;
-                const float res = wpf * photoDiff;
-                A.e2p += res * res;
+                const PinRes ph = pin_photo_res(tp.a, p.w, ec);
+                A.e2p += ph.res * ph.res;
                 if (row_on) {
-                    const float wgx = wpf * tp.b * K.fx, wgy = wpf * tp.c * K.fy;
-                    float bx, by, bz;
-                    to_rig(wgx * iz, wgy * iz, -(wgx * X + wgy * Y) * iz2, bx, by, bz);
-                    accumulate_row(A, bx, by, bz, qx, qy, qz, res);
+                    const F3 j = to_rig(Ri, pin_photo_row(tp.b, tp.c, K, X, Y, iz, iz2, ph.w));
+                    accumulate_row(A, j.a, j.b, j.c, qx, qy, qz, ph.res);
                 }
             }
         }
@@ -273,16 +247,11 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_rig(const float4* __restr
             A.nVis += ballot_count(row_on);
             if (err_on) {
 #pragma clang fp contract(fast)
-                const float depthDiff = depth2 - Z;                                 // FIX C: the transformed point's depth
-                const float sd = ec.sigma_depth * Z;
-                const float wd = weight_huber_fast(depthDiff, sd) * fast_rcp(sd);
-                const float res = wd * depthDiff;
-                A.e2d += res * res;
+                const PinRes dp = pin_depth_res(depth2, Z, ec);                     // FIX C: the transformed point's depth
+                A.e2d += dp.res * dp.res;
                 if (row_on) {
-                    const float gx = td.b * K.fx, gy = td.c * K.fy;
-                    float bx, by, bz;
-                    to_rig(wd * (gx * iz), wd * (gy * iz), wd * (-(gx * X + gy * Y) * iz2 - 1.f), bx, by, bz);      // FIX B: - jacobianT36.row(2)
-                    accumulate_row(A, bx, by, bz, qx, qy, qz, res);
+                    const F3 j = to_rig(Ri, pin_depth_row(td.b, td.c, K, X, Y, iz, iz2, dp.w));      // FIX B: - jacobianT36.row(2)
+                    accumulate_row(A, j.a, j.b, j.c, qx, qy, qz, dp.res);
                 }
             }
         }
