@@ -4,7 +4,7 @@
 //     frame_%03d.rgb  (H*W*3 uint8)   frame_%03d.depth (H*W uint16 mm)
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/odometry_replay.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o odometry_replay
-// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L]]
+// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map]]
 //         --sequence: all frames are loaded first and the frame loop runs inside the library (alignSequence)
 //         --multi N:  the same sequence sharded over N GPUs of this node from this one process (rgbd360_multi_*: one host thread
 //                     per device, contiguous shards of pairs, one ncclAllGather of the solved poses over xGMI); prints the
@@ -17,6 +17,10 @@
 //         --map FILE: (frame loop and --pbmap only; ignored with a warning otherwise) the global map of OdometryRGBD360.cpp:242-268
 //                     -- every frame is inserted at currentPose into a resident voxel grid (rgbd360::GlobalMap: filterEuclidean's box, transformPointCloud, globalMap +=,
 //                     filterVoxel) and the map is written to FILE as "x y z r g b count" lines; --leaf L: the voxel size (0.05 m)
+//         --refine-on-map: (with --map) before a frame is inserted its pose is refined against the map by point-to-point ICP
+//                     (GlobalMap::alignSphere; the cloud ICP of OdometryRGBD360.cpp:98-114, 210-222 with the map as its target): a
+//                     correction against everything seen so far.  An accepted refinement (status 0) replaces currentPose; prints one
+//                     extra "refine" line per frame.  Without the option the output is what it was.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -157,9 +161,11 @@ int main(int argc, char** argv) {
     const bool use_pbmap = argc > 5 && std::string(argv[5]) == "--pbmap";
     std::string map_file;
     float leaf = 0.05f;
-    for (int a = 5; a + 1 < argc; ++a) {
-        if (std::string(argv[a]) == "--map") map_file = argv[a + 1];
-        if (std::string(argv[a]) == "--leaf") leaf = (float)atof(argv[a + 1]);
+    bool refine_on_map = false;
+    for (int a = 5; a < argc; ++a) {
+        if (a + 1 < argc && std::string(argv[a]) == "--map") map_file = argv[a + 1];
+        if (a + 1 < argc && std::string(argv[a]) == "--leaf") leaf = (float)atof(argv[a + 1]);
+        if (std::string(argv[a]) == "--refine-on-map") refine_on_map = true;
     }
     std::unique_ptr<rgbd360::GlobalMap> globalMap;      // declared behind align360: destroyed before its context
     auto add_to_map = [&](const Frame& f) {                                                      // :242, 266-268
@@ -200,6 +206,14 @@ int main(int argc, char** argv) {
         printf("pair %d status %d sso %.4f rel_t %.5f %.5f %.5f pose_t %.5f %.5f %.5f\n", k - 1, align360.status(), align360.SSO,
                rel(0, 3), rel(1, 3), rel(2, 3), currentPose(0, 3), currentPose(1, 3), currentPose(2, 3));
         fprintf(stderr, "entropy %d %.5f\n", k - 1, align360.calcEntropy());                     // :207 (commented out in the source)
+        if (globalMap && refine_on_map) {
+            rgbd360::Mat4f refined = currentPose;
+            const int status = globalMap->alignSphere(frame2.sphereDepth, currentPose, refined, /*convention=*/0);
+            const rgbd360_map_align_result& r = globalMap->alignResult();
+            printf("refine %d status %d iterations %d matched %lld fitness %.6f pose_t %.5f %.5f %.5f\n", k - 1, status, r.iterations, r.n_matched, r.fitness,
+                   refined(0, 3), refined(1, 3), refined(2, 3));
+            if (status == RGBD360_OK) currentPose = refined;
+        }
         if (globalMap) add_to_map(frame2);
         std::swap(frame1, frame2);
         std::swap(planes1, planes2);

@@ -10,6 +10,9 @@
 // Two deliberate differences (rgbd360_hip.h): every inserted point has weight one -- the map is the voxel filter applied ONCE to the
 // concatenation of all inserted clouds, where the reference's per-frame re-filter makes the order of the frames decide the result --
 // and the sums are integers instead of PCL's float accumulators.
+// The cloud ICP of the same programs (OdometryRGBD360.cpp:98-114, 210-222: filterVoxel, icp.setInputSource / setInputTarget / align(guess);
+// RegisterPairRGBD360.cpp:111-118, MethodsRegisterRGBD360.cpp:294-320, OdometryKeyFrame360.cpp:124-140) with the map as its target:
+//     globalMap.alignSphere(frame.sphereDepth, guess, pose)     point-to-point, nearest voxel centroid within max_dist <= leaf
 #pragma once
 
 #include <stdexcept>
@@ -63,6 +66,28 @@ class GlobalMap {
         return full(rgbd360_map_insert_cloud(map_, xyz, rgb3, n, pose.m, 0, &stats_), "rgbd360_map_insert_cloud");
     }
 
+    // Point-to-point ICP of a sphere frame, or of a cloud in its frame's coordinates, against the map from `guess` (rgbd360_map_align_*:
+    // the nearest neighbour is the nearest voxel centroid in the 27 cells around the point, max_dist in (0, leaf]).  The map is not changed.
+    // Returns the status (RGBD360_OK / ILL_POSED / NO_VALID_PIXELS); alignResult() has the iterations, matches, fitness, hessian.
+    rgbd360_map_align_params alignParams() const {
+        rgbd360_map_align_params p;
+        rgbd360_map_default_align_params(map_, &p);
+        return p;
+    }
+    int alignSphere(const ImageView& depth, const Mat4f& guess, Mat4f& pose, int convention = 0, const rgbd360_map_align_params* params = nullptr) {
+        if (depth.type == ImageView::U8C3) throw std::runtime_error("GlobalMap::alignSphere: a 16UC1 / 32FC1 depth image");
+        const int rc = rgbd360_map_align_sphere(map_, depth.data, depth.step, depth.type == ImageView::U16C1 ? 0 : 1, depth.rows, depth.cols, convention, guess.m, 0,
+                                                params, pose.m, &align_);
+        check(rc, "rgbd360_map_align_sphere");
+        return rc;
+    }
+    int alignCloud(const float* xyz, long long n, const Mat4f& guess, Mat4f& pose, const rgbd360_map_align_params* params = nullptr) {
+        const int rc = rgbd360_map_align_cloud(map_, xyz, n, guess.m, 0, params, pose.m, &align_);
+        check(rc, "rgbd360_map_align_cloud");
+        return rc;
+    }
+    const rgbd360_map_align_result& alignResult() const { return align_; }      // of the last align call
+
     long long size() const { return rgbd360_map_size(map_); }
     size_t bytes() const { return rgbd360_map_bytes(map_); }
     void clear() { check(rgbd360_map_clear(map_), "rgbd360_map_clear"); }
@@ -94,6 +119,7 @@ class GlobalMap {
     }
     rgbd360_map* map_ = nullptr;
     rgbd360_map_stats stats_{};
+    rgbd360_map_align_result align_{};
 };
 
 }  // namespace rgbd360

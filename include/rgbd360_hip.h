@@ -253,6 +253,66 @@ int    rgbd360_map_clear(rgbd360_map* map);
 long long rgbd360_map_extract(rgbd360_map* map, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3);
 long long rgbd360_map_extract_dev(rgbd360_map* map, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3);
 
+/* ---- point-to-point ICP of a frame against the map (csrc/map_align.h) -----------------------------------------------------------
+ * The reference's registration programs put a cloud-to-cloud ICP on voxel-filtered clouds next to the dense alignment
+ * (RegisterPairRGBD360.cpp:111-118, MethodsRegisterRGBD360.cpp:294-320, OdometryRGBD360.cpp:98-114 and 210-222: filterVoxel, then
+ * setInputSource / setInputTarget / align(guess); OdometryKeyFrame360.cpp:124-140).  Here the target is the resident map: the nearest
+ * neighbour of a point is the nearest voxel CENTROID among the 3 x 3 x 3 cells around the point, a bounded number of hash probes, and
+ * the Gauss-Newton loop runs on the device with one stream synchronisation per alignment.  Per source point at the current pose T
+ * (16 floats, column-major, world <- frame):
+ *   1 steps 1-5 of the map's definition above (point, the map's box, pose, range, voxel index i), bit for bit; skipped, box-rejected
+ *     and out-of-range points are counted as in rgbd360_map_stats and contribute nothing.
+ *   2 candidates: the centre cell i first, then the other 26 cells i + (dx, dy, dz) in the order of three nested loops, dz outermost
+ *     and dx innermost, each ascending over -1, 0, 1 (ascending keys).  A cell is a candidate if it is in the table with
+ *     count >= min_count.  A read-only lookup ends at the first empty slot or after the table's probe bound (2048 slots, the whole
+ *     table when it is smaller).  A neighbour index outside the 21-bit key range is no candidate; it is never wrapped.
+ *   3 centroid c_k = (float)((double)S_k / ((double)count * 1048576.0)), the read-out's expression.
+ *   4 distance e_k = w_k - c_k, d2 = (e_x e_x + e_y e_y) + e_z e_z in float32, every operation rounded on its own.  The match is the
+ *     candidate of smallest d2; a later candidate replaces the current one only if it is strictly smaller (a tie goes to the earlier
+ *     one).  It is kept iff d2 <= max_dist * max_dist (the product in float32).
+ *   5 sums over the kept matches in float64, every term formed in double from the float32 w and e: n, sum w (3), sum w_j w_k for
+ *     j <= k (xx, xy, xz, yy, yz, zz), sum e (3), sum w x e (3), sum (e_x e_x + e_y e_y) + e_z e_z -- 17 in all.  No floating-point
+ *     atomics: a workgroup reduces its points into one partial row and the rows are added in ascending order, so the sums are the
+ *     same from run to run.
+ *   6 step: J = [I | -[w]x], the increment pose <- pseudo_exp(v, omega) pose; H = sum J^T J and g = sum J^T e assembled from the 17
+ *     sums in double, cast to float32, then the step of the dense alignment (csrc/gn_math.h, gn::step with lambda 0).
+ *     rank(H) != 6: RGBD360_ILL_POSED, pose_out = the last pose.  n < min_matches: RGBD360_NO_VALID_PIXELS.  Converged when
+ *     v.v <= eps and omega.omega <= eps in float32 after the step is applied (a stated simplification of PCL's
+ *     setTransformationEpsilon).  At most max_iters steps (the reference: 10).
+ *   7 one more evaluation at pose_out gives n_matched, fitness = sum e.e / n (PCL's getFitnessScore over the kept matches), hessian
+ *     and gradient (and NO_VALID_PIXELS when n < min_matches there and nothing else was reported).
+ * max_dist must lie in (0, leaf]: within that range the 27 cells hold every centroid closer than max_dist (up to rounding at cell
+ * faces), so the match is the true nearest centroid; a larger radius would need (2r + 1)^3 probes.  Callers who need a wider basin
+ * align against a coarser map first.
+ * Differences from the reference, stated: its active choice is pcl::GeneralizedIterativeClosestPoint at 0.3 - 0.4 m over a kd-tree of
+ * the other cloud; this is the point-to-point form on the grid, against centroids.  PCL is not part of the reference tree: parity
+ * with PCL is unpinned.  Out of scope: GICP covariances, point-to-plane residuals (the map has no normals), radii above one leaf, a
+ * coarse-to-fine chain inside the library, several GPUs. */
+typedef struct {
+    float max_dist;            /* setMaxCorrespondenceDistance, in (0, leaf]; default: leaf */
+    int   max_iters;           /* setMaximumIterations: 10 (OdometryRGBD360.cpp:102) */
+    float eps;                 /* on |v|^2 and |omega|^2 of the last step: 1e-6 */
+    int   min_count;           /* points a voxel must hold to be a candidate: 1 */
+    long long min_matches;     /* kept matches an evaluation must have: 6 */
+} rgbd360_map_align_params;
+typedef struct {
+    int status, iterations, converged;      /* RGBD360_OK / ILL_POSED / NO_VALID_PIXELS; steps applied; 1 when the last step was below eps */
+    long long n_valid, n_box_rejected, n_out_of_range, n_matched;      /* of the final evaluation at pose_out */
+    double fitness;            /* sum e.e / n_matched of the final evaluation (0 when nothing matched) */
+    float hessian[36], gradient[6];         /* column-major 6x6, of the final evaluation */
+} rgbd360_map_align_result;
+void   rgbd360_map_default_align_params(const rgbd360_map* map, rgbd360_map_align_params* p);
+/* A sphere frame (as in rgbd360_map_insert_sphere, without colour) from `guess`.  The map is not changed.  Returns the status (>= 0,
+ * also in result->status; result may be NULL); -1 bad arguments, nothing launched: max_dist outside (0, leaf], max_iters < 0 or
+ * > 1000, min_count < 1, a NULL depth / guess / pose_out, a bad convention or depth type.  params NULL: the defaults.  An empty image
+ * returns RGBD360_NO_VALID_PIXELS with pose_out = guess. */
+int    rgbd360_map_align_sphere(rgbd360_map* map, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                const float guess[16], int on_device, const rgbd360_map_align_params* params, float pose_out[16],
+                                rgbd360_map_align_result* result);
+/* The same for n points xyz[3 n] in the frame's coordinates (the filtered cloud of the reference's call sites). */
+int    rgbd360_map_align_cloud(rgbd360_map* map, const float* xyz, long long n, const float guess[16], int on_device,
+                               const rgbd360_map_align_params* params, float pose_out[16], rgbd360_map_align_result* result);
+
 /* ---- one process, several GPUs (BASELINE.json configs[3]) ---------------------------------------------------
  * The sequence path shards by independent frame pairs: device d gets the contiguous pairs rgbd360_shard_range(n_frames-1, d,
  * n_gpus) and therefore the frames lo..hi (one boundary frame is shared by two neighbours); one host thread per device drives

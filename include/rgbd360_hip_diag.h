@@ -83,6 +83,27 @@ int rgbd360_map_time_kernels(rgbd360_map* map, const uint8_t* rgb_dev, size_t rg
                              int depth_type, int rows, int cols, int convention, const float pose[16], int reps, float avg_us[5],
                              long long* global_updates);
 
+/* One evaluation of the map alignment (rgbd360_map_align_*, rgbd360_hip.h: steps 1-5 of its definition) at `pose`, and the trace of
+ * the map's last alignment.  depth != NULL: the sphere frame; otherwise the n points xyz.  sums[17]: n, sum w (3), sum w_j w_k (xx, xy,
+ * xz, yy, yz, zz), sum e (3), sum w x e (3), sum e.e; counters[3]: n_valid, n_box_rejected, n_out_of_range.  key3_dev / d2_dev (DEVICE
+ * arrays of 3 / 1 values per input point, may be NULL): the key (i_x, i_y, i_z) of the kept match, or three times INT32_MIN where the
+ * point has none, and d2 of the nearest candidate whether kept or not (+Inf where the point has no candidate or did not reach the
+ * search).  pose == NULL: no evaluation, the trace only.  trace (may be NULL): the first min(max_trace, steps) records of the last
+ * rgbd360_map_align_* call of this map, one per applied step: the kept matches and sum e.e of the evaluation the step came from, and
+ * the step; *n_trace (may be NULL): the number of steps. */
+typedef struct { long long n; double sum_sq; float update[6]; } rgbd360_map_align_trace;
+int rgbd360_map_align_eval(rgbd360_map* map, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                           const float* xyz, long long n, const float pose[16], int on_device, const rgbd360_map_align_params* params,
+                           double sums[17], long long counters[3], int32_t* key3_dev, float* d2_dev, int max_trace, int* n_trace,
+                           rgbd360_map_align_trace* trace);
+/* The alignment's kernels under HIP events on a sphere frame in device memory, averages over `reps` launches in microseconds:
+ * avg_us[0] k_vmap_icp_eval, [1] k_vmap_icp_solve, [2] one k_vmap_insert launch of the frame into the map as it is (the map holds the
+ * frame once more afterwards), [3] a device-to-device copy of the frame's depth bytes, [4] a whole alignment of params->max_iters
+ * iterations from `pose` (enqueue to synchronisation, wall clock).  *probes (may be NULL): table slots read per point that reached the
+ * search, in one evaluation at `pose`. */
+int rgbd360_map_time_align(rgbd360_map* map, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                           const float pose[16], const rgbd360_map_align_params* params, int reps, float avg_us[5], double* probes);
+
 /* The same timer with the launches rotating over n_ctx contexts of one device (each with its own copy of a frame pair) on
  * ctxs[0]'s stream: once n_ctx x the level's working set exceeds the 256 MiB Infinity Cache every launch is fed from HBM. */
 int rgbd360_time_eval_kernel_rotating(rgbd360_ctx* const* ctxs, int n_ctx, int level, const float pose[16], int method,

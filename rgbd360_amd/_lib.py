@@ -31,6 +31,7 @@ SYMBOLS = [
     "rgbd360_map_create", "rgbd360_map_destroy", "rgbd360_map_last_error", "rgbd360_map_bytes", "rgbd360_map_set_box",
     "rgbd360_map_insert_sphere", "rgbd360_map_insert_cloud", "rgbd360_map_size", "rgbd360_map_clear", "rgbd360_map_extract",
     "rgbd360_map_extract_dev", "rgbd360_map_time_kernels",
+    "rgbd360_map_default_align_params", "rgbd360_map_align_sphere", "rgbd360_map_align_cloud", "rgbd360_map_align_eval", "rgbd360_map_time_align",
 ]
 
 
@@ -71,6 +72,20 @@ class Plane(C.Structure):
 
 class MapStats(C.Structure):       # rgbd360_map_stats
     _fields_ = [(n, C.c_longlong) for n in ("n_valid", "n_box_rejected", "n_out_of_range", "n_added", "n_dropped_full", "n_voxels")]
+
+
+class MapAlignParams(C.Structure):       # rgbd360_map_align_params
+    _fields_ = [("max_dist", C.c_float), ("max_iters", C.c_int), ("eps", C.c_float), ("min_count", C.c_int), ("min_matches", C.c_longlong)]
+
+
+class MapAlignResult(C.Structure):       # rgbd360_map_align_result
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("converged", C.c_int), ("n_valid", C.c_longlong), ("n_box_rejected", C.c_longlong),
+                ("n_out_of_range", C.c_longlong), ("n_matched", C.c_longlong), ("fitness", C.c_double), ("hessian", C.c_float * 36),
+                ("gradient", C.c_float * 6)]
+
+
+class MapAlignTrace(C.Structure):        # rgbd360_map_align_trace (rgbd360_hip_diag.h)
+    _fields_ = [("n", C.c_longlong), ("sum_sq", C.c_double), ("update", C.c_float * 6)]
 
 
 class PbmapParams(C.Structure):
@@ -245,5 +260,12 @@ def load() -> C.CDLL:
         f.argtypes = [vp, ll, vp, vp, vp, vp]
         f.restype = ll
     L.rgbd360_map_time_kernels.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, vp, C.POINTER(ll)]
+    L.rgbd360_map_default_align_params.argtypes = [vp, C.POINTER(MapAlignParams)]
+    L.rgbd360_map_default_align_params.restype = None
+    L.rgbd360_map_align_sphere.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, C.POINTER(MapAlignParams), f32p, C.POINTER(MapAlignResult)]
+    L.rgbd360_map_align_cloud.argtypes = [vp, vp, ll, f32p, i32, C.POINTER(MapAlignParams), f32p, C.POINTER(MapAlignResult)]
+    L.rgbd360_map_align_eval.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, vp, ll, f32p, i32, C.POINTER(MapAlignParams), vp, vp, vp, vp, i32,
+                                         C.POINTER(i32), vp]
+    L.rgbd360_map_time_align.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, C.POINTER(MapAlignParams), i32, vp, C.POINTER(C.c_double)]
     _lib = L
     return L

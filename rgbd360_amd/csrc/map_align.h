@@ -1,0 +1,547 @@
+// map_align.h -- point-to-point ICP of a posed sphere frame, or of a cloud, against the resident voxel map (voxel_map.h): the
+// cloud-to-cloud ICP the reference's registration programs put next to the dense alignment
+//   filter.filterVoxel(cloud); icp.setInputSource(src); icp.setInputTarget(trg); icp.align(*aligned, guess);
+// (RegisterPairRGBD360.cpp:111-118, MethodsRegisterRGBD360.cpp:294-320, OdometryRGBD360.cpp:98-114, 210-222,
+// OdometryKeyFrame360.cpp:124-140) with the map as its target.  Part of the Frame360 translation unit, behind voxel_map.h and gn_math.h.
+//
+// Definition (include/rgbd360_hip.h, "point-to-point ICP of a frame against the map"; tests/map_align_reference.py
+// restates it in numpy).  Per source point at the current pose: steps 1-5 of the map through vmap::classify; the 27 cells around the
+// point's voxel, the centre first, then dz / dy / dx ascending; per cell found with count >= min_count the read-out's centroid, e = w - c
+// and d2 in float32; the smallest d2 wins, a tie goes to the earlier cell; kept iff d2 <= max_dist^2; 17 float64 sums over the kept
+// matches; H and g of J = [I | -[w]x] from the sums, gn::step, the stop tests.  max_dist lies in (0, leaf]: the 27 cells then hold every
+// centroid closer than max_dist (up to rounding at cell faces -- a centroid may lie an ulp outside its cell), so the match is the true
+// nearest centroid; a larger radius would need (2r + 1)^3 probes, callers who need a wider basin align against a coarser map first.
+// No cell is pruned: all 27 are looked up whatever the point's place in its cell.
+//
+//   k_vmap_icp_eval   the shape of k_vmap_insert: 256 threads, four points per thread 256 apart, all loads of a thread first.  Per point
+//                     the first probe of all 27 cells is loaded before any is looked at (27 independent 8-byte loads in flight); a
+//                     probe sequence goes on with plain loads.  The table is never written.  A wave's 22 doubles (17 sums, three
+//                     counters, the probe and search counts) go through a butterfly of lane exchanges, the four waves through LDS, and
+//                     the workgroup writes one partial row.  The pose comes from the loop's state in device memory; a launch of the
+//                     loop returns at once when the state says the loop has ended.
+//   k_vmap_icp_solve  one workgroup: the rows added in ascending order (one lane per column), H and g, gn::step, status and the stop
+//                     test, one trace record per applied step, the new pose and the state word.
+//   host              max_iters x (eval, solve), the final eval and its solve, one copy of the state, ONE synchronisation; no host read
+//                     between iterations.
+// Cost: up to 27 dependent-free first probes of 8 bytes per point against random 64-byte slots, plus 32 bytes per occupied candidate;
+// tools/map_align_perf.py measures it (profiles/map_align_perf.txt).
+#pragma once
+#include <chrono>
+
+namespace vmap {
+
+constexpr int kIcpSums = 17;
+constexpr int kIcpWords = 22;        // a partial row: the 17 sums, n_valid, n_box_rejected, n_out_of_range, probes, points searched (all doubles: exact integers)
+constexpr int kIcpMaxIters = 1000;
+constexpr int kNoKey = -2147483647 - 1;
+
+struct IcpState {
+    float pose[16];
+    int done, status, iterations, converged;
+    double row[kIcpWords];           // the totals of the last evaluation that was summed
+    float H[36], g[6];
+};
+struct IcpPose {
+    float m[16];
+};
+
+// the slot of `key` from its first probe on (slot, k0 = the key word there), read only; -1: not in the table
+__device__ __forceinline__ long long find(const unsigned long long* __restrict__ table, unsigned long long mask, unsigned long long key, unsigned long long slot,
+                                          unsigned long long k0, unsigned& probes) {
+    const unsigned long long n_probes = mask < kMaxProbes ? mask + 1 : kMaxProbes;
+    for (unsigned long long p = 1;; ++p) {
+        if (k0 == key) return (long long)slot;
+        if (k0 == kEmpty || p >= n_probes) return -1;
+        slot = (slot + 1) & mask;
+        k0 = table[slot * kFields];
+        ++probes;
+    }
+}
+
+// cell c of the 27 in the definition's order: 0 the centre, then dz, dy, dx ascending without the centre
+__host__ __device__ inline void icp_cell(int c, int& dx, int& dy, int& dz) {
+    int q = c == 0 ? 13 : c <= 13 ? c - 1 : c;      // position in the nested loops (13 = the centre)
+    dx = q % 3 - 1;
+    dy = q / 3 % 3 - 1;
+    dz = q / 9 - 1;
+}
+
+// H (column-major) and g of J = [I | -[w]x] from the 17 sums
+__host__ __device__ inline void icp_assemble(const double* s, float* H, float* g) {
+    const double n = s[0], wx = s[1], wy = s[2], wz = s[3], xx = s[4], xy = s[5], xz = s[6], yy = s[7], yz = s[8], zz = s[9];
+    const double Hd[6][6] = {{n, 0, 0, 0, wz, -wy},   {0, n, 0, -wz, 0, wx},    {0, 0, n, wy, -wx, 0},
+                             {0, -wz, wy, yy + zz, -xy, -xz}, {wz, 0, -wx, -xy, xx + zz, -yz}, {-wy, wx, 0, -xz, -yz, xx + yy}};
+    for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) H[c * 6 + r] = (float)Hd[r][c];
+    for (int k = 0; k < 6; ++k) g[k] = (float)s[10 + k];
+}
+
+__global__ void k_vmap_icp_init(IcpState* __restrict__ st, IcpPose guess) {
+    const int t = threadIdx.x;
+    if (t < 16) st->pose[t] = guess.m[t];
+    if (t < kIcpWords) st->row[t] = 0.0;
+    if (t < 36) st->H[t] = 0.f;
+    if (t < 6) st->g[t] = 0.f;
+    if (t == 0) st->done = st->status = st->iterations = st->converged = 0;
+}
+
+template <int SRC>
+__global__ __launch_bounds__(kThreads) void k_vmap_icp_eval(Params P, Source src, const unsigned long long* __restrict__ table, unsigned long long mask,
+                                                            unsigned long long min_count, float max_dist2, const IcpState* __restrict__ st, int final_pass,
+                                                            double* __restrict__ part, int32_t* __restrict__ key3, float* __restrict__ d2_out) {
+#pragma clang fp contract(off)
+    if (!final_pass && st->done) return;
+    __shared__ double s_red[kThreads / 64][kIcpWords];
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) P.pose[k] = st->pose[k];
+
+    // all loads of the thread first
+    float x[kPerThread], y[kPerThread], z[kPerThread];
+    bool in[kPerThread];
+    long long index[kPerThread];
+    if (SRC == 0) {
+        const int r = blockIdx.y;
+        const uint8_t* drow = (const uint8_t*)src.depth + (size_t)r * src.depth_step;
+        const float sp = src.sin_phi[r], cp = src.cos_phi[r];
+        float d[kPerThread], sth[kPerThread], cth[kPerThread];
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const int col = blockIdx.x * kTile + t + kThreads * k;
+            in[k] = col < src.cols;
+            const int cc = in[k] ? col : src.cols - 1;
+            index[k] = (long long)r * src.cols + cc;
+            d[k] = src.depth_type == 0 ? 0.001f * (float)((const uint16_t*)drow)[cc] : ((const float*)drow)[cc];
+            sth[k] = src.sin_theta[cc];
+            cth[k] = src.cos_theta[cc];
+        }
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) r360::sphere_point(src.convention, d[k], sp, cp, sth[k], cth[k], x[k], y[k], z[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const long long i = (long long)blockIdx.x * kTile + t + kThreads * k;
+            in[k] = i < src.n;
+            const size_t ii = in[k] ? (size_t)i : 0;
+            index[k] = (long long)ii;
+            x[k] = src.xyz[3 * ii];
+            y[k] = src.xyz[3 * ii + 1];
+            z[k] = src.xyz[3 * ii + 2];
+        }
+    }
+
+    double acc[kIcpWords];
+#pragma unroll
+    for (int q = 0; q < kIcpWords; ++q) acc[q] = 0.0;
+    unsigned n_probes = 0;
+#pragma unroll
+    for (int k = 0; k < kPerThread; ++k) {
+        if (!in[k]) continue;
+        unsigned long long key = 0;
+        long long f[3];
+        float w[3];
+        const int cls = classify(P, x[k], y[k], z[k], key, f, w);
+        acc[17] += cls >= 1 ? 1.0 : 0.0;
+        acc[18] += cls == 1 ? 1.0 : 0.0;
+        acc[19] += cls == 2 ? 1.0 : 0.0;
+        float best = __builtin_inff();
+        unsigned long long best_key = kEmpty;
+        float be[3] = {0.f, 0.f, 0.f};
+        if (cls == 3) {
+            acc[21] += 1.0;
+            const long long ib[3] = {(long long)(key & 0x1fffffull), (long long)((key >> 21) & 0x1fffffull), (long long)(key >> 42)};
+            unsigned long long k0[27];
+            // the first probe of every cell, before any is looked at
+#pragma unroll
+            for (int c = 0; c < 27; ++c) {
+                int dx, dy, dz;
+                icp_cell(c, dx, dy, dz);
+                const long long nx = ib[0] + dx, ny = ib[1] + dy, nz = ib[2] + dz;
+                const bool ok = nx >= 0 && nx < (1ll << 21) && ny >= 0 && ny < (1ll << 21) && nz >= 0 && nz < (1ll << 21);
+                const unsigned long long ck = ((unsigned long long)nz << 42) | ((unsigned long long)ny << 21) | (unsigned long long)nx;
+                k0[c] = ok ? table[(mix64(ck) & mask) * kFields] : kEmpty;
+                n_probes += ok ? 1u : 0u;
+            }
+#pragma unroll
+            for (int c = 0; c < 27; ++c) {
+                if (k0[c] == kEmpty) continue;       // an empty first slot, or no key at all: no candidate
+                int dx, dy, dz;
+                icp_cell(c, dx, dy, dz);
+                const unsigned long long ck = ((unsigned long long)(ib[2] + dz) << 42) | ((unsigned long long)(ib[1] + dy) << 21) | (unsigned long long)(ib[0] + dx);
+                const long long slot = find(table, mask, ck, mix64(ck) & mask, k0[c], n_probes);
+                if (slot < 0) continue;
+                const unsigned long long* rec = table + (unsigned long long)slot * kFields;
+                const unsigned long long cnt = rec[1];
+                if (cnt < min_count || cnt == 0) continue;
+                const double den = (double)cnt * kFix;
+                float e[3];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) e[q] = w[q] - (float)((double)(long long)rec[2 + q] / den);
+                const float d2 = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+                if (d2 < best) {
+                    best = d2;
+                    best_key = ck;
+                    be[0] = e[0];
+                    be[1] = e[1];
+                    be[2] = e[2];
+                }
+            }
+        }
+        const bool kept = best_key != kEmpty && best <= max_dist2;
+        if (key3) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) key3[3 * index[k] + q] = kept ? (int32_t)((best_key >> (21 * q)) & 0x1fffffull) - kBias : kNoKey;
+        }
+        if (d2_out) d2_out[index[k]] = best;
+        if (kept) {
+            const double wx = w[0], wy = w[1], wz = w[2], ex = be[0], ey = be[1], ez = be[2];
+            acc[0] += 1.0;
+            acc[1] += wx;
+            acc[2] += wy;
+            acc[3] += wz;
+            acc[4] += wx * wx;
+            acc[5] += wx * wy;
+            acc[6] += wx * wz;
+            acc[7] += wy * wy;
+            acc[8] += wy * wz;
+            acc[9] += wz * wz;
+            acc[10] += ex;
+            acc[11] += ey;
+            acc[12] += ez;
+            acc[13] += wy * ez - wz * ey;
+            acc[14] += wz * ex - wx * ez;
+            acc[15] += wx * ey - wy * ex;
+            acc[16] += (ex * ex + ey * ey) + ez * ez;
+        }
+    }
+    acc[20] = (double)n_probes;
+
+    // wave, then workgroup: a fixed tree, the same sums from run to run
+#pragma unroll
+    for (int q = 0; q < kIcpWords; ++q) {
+#pragma unroll
+        for (int off = 32; off; off >>= 1) acc[q] += __shfl_xor(acc[q], off);
+    }
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < kIcpWords; ++q) s_red[t >> 6][q] = acc[q];
+    }
+    __syncthreads();
+    if (t < kIcpWords) {
+        double s = s_red[0][t];
+        for (int wv = 1; wv < kThreads / 64; ++wv) s += s_red[wv][t];
+        const size_t block = SRC == 0 ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
+        part[block * kIcpWords + t] = s;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_vmap_icp_solve(IcpState* __restrict__ st, rgbd360_map_align_trace* __restrict__ trace, const double* __restrict__ part,
+                                                       int n_rows, int final_pass, long long min_matches, float eps) {
+#pragma clang fp contract(off)
+    if (!final_pass && st->done) return;
+    __shared__ double s_row[kIcpWords];
+    const int t = threadIdx.x;
+    if (t < kIcpWords) {         // the rows in ascending order
+        double s = 0.0;
+        for (int r = 0; r < n_rows; ++r) s += part[(size_t)r * kIcpWords + t];
+        s_row[t] = s;
+        st->row[t] = s;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    const long long n = (long long)s_row[0];
+    if (final_pass) {
+        icp_assemble(s_row, st->H, st->g);
+        if (st->status == RGBD360_OK && n < min_matches) st->status = RGBD360_NO_VALID_PIXELS;
+        st->done = 1;
+        return;
+    }
+    if (n < min_matches) {
+        st->status = RGBD360_NO_VALID_PIXELS;
+        st->done = 1;
+        return;
+    }
+    float H[36], g[6], pose[16], pose_new[16], u[6];
+    icp_assemble(s_row, H, g);
+    for (int k = 0; k < 16; ++k) pose[k] = st->pose[k];
+    if (gn::step(H, g, 0.f, pose, pose_new, u) != 0) {
+        st->status = RGBD360_ILL_POSED;
+        st->done = 1;
+        return;
+    }
+    for (int k = 0; k < 16; ++k) st->pose[k] = pose_new[k];
+    rgbd360_map_align_trace rec;
+    rec.n = n;
+    rec.sum_sq = s_row[16];
+    for (int k = 0; k < 6; ++k) rec.update[k] = u[k];
+    trace[st->iterations] = rec;
+    st->iterations += 1;
+    const float vv = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2], ww = (u[3] * u[3] + u[4] * u[4]) + u[5] * u[5];
+    if (vv <= eps && ww <= eps) {
+        st->converged = 1;
+        st->done = 1;
+    }
+}
+
+}  // namespace vmap
+
+namespace {
+
+// what one alignment call works on: the source in device memory, the launch grid, the checked parameters
+struct IcpJob {
+    vmap::Source src;
+    bool cloud;
+    dim3 grid;
+    int n_rows;
+    long long n_points;
+    rgbd360_map_align_params p;
+};
+
+int icp_check_params(rgbd360_map* m, const rgbd360_map_align_params* params, rgbd360_map_align_params& p) {
+    if (params) p = *params;
+    else rgbd360_map_default_align_params(m, &p);
+    if (!(p.max_dist > 0.f && p.max_dist <= m->leaf)) return vmap_fail(m, -1, "max_dist must lie in (0, leaf]");
+    if (p.max_iters < 0 || p.max_iters > vmap::kIcpMaxIters) return vmap_fail(m, -1, "max_iters must lie in 0 .. 1000");
+    if (p.min_count < 1) return vmap_fail(m, -1, "min_count must be at least 1");
+    if (!(p.eps >= 0.f)) return vmap_fail(m, -1, "eps must not be negative");
+    return 0;
+}
+// the source of a call in device memory (a host source is copied on the stream), the grid and the buffers; 1: an empty input
+int icp_prepare(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
+                int on_device, IcpJob& job) {
+    job.cloud = depth == nullptr;
+    if (job.cloud) {
+        if (n < 0 || n >= (1ll << 40)) return vmap_fail(m, -1, "bad point count");
+        if (n == 0) return 1;
+        if (!xyz) return vmap_fail(m, -1, "xyz must not be null");
+        hipSetDevice(m->s->p.device);
+        if (!on_device) {
+            HIPC(m, m->up_depth.ensure((size_t)n * 3 * sizeof(float)));
+            HIPC(m, hipMemcpyAsync(m->up_depth, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, m->s->stream));
+            xyz = reinterpret_cast<const float*>(m->up_depth.get());
+        }
+        job.src = {nullptr, 0, nullptr, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, xyz, n};
+        job.grid = dim3((unsigned)((n + vmap::kTile - 1) / vmap::kTile));
+        job.n_points = n;
+    } else {
+        hipSetDevice(m->s->p.device);
+        if (!on_device) {
+            const size_t drow = (size_t)cols * (depth_type == 0 ? 2 : 4);
+            HIPC(m, m->up_depth.ensure(drow * rows));
+            HIPC(m, hipMemcpy2DAsync(m->up_depth, drow, depth, depth_step, drow, rows, hipMemcpyHostToDevice, m->s->stream));
+            depth = m->up_depth;
+            depth_step = drow;
+        }
+        if (const int rc = vmap_sphere_source(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, job.src)) return rc;
+        job.grid = dim3((cols + vmap::kTile - 1) / vmap::kTile, rows);
+        job.n_points = (long long)rows * cols;
+    }
+    job.n_rows = (int)(job.grid.x * job.grid.y);
+    const size_t state_bytes = sizeof(vmap::IcpState) + (size_t)std::max(job.p.max_iters, 1) * sizeof(rgbd360_map_align_trace);
+    HIPC(m, m->a_part.ensure((size_t)job.n_rows * vmap::kIcpWords));
+    HIPC(m, m->a_state.ensure(state_bytes));
+    HIPC(m, m->a_host.ensure(state_bytes));
+    return 0;
+}
+vmap::IcpState* icp_state(rgbd360_map* m) { return reinterpret_cast<vmap::IcpState*>(m->a_state.get()); }
+rgbd360_map_align_trace* icp_trace(rgbd360_map* m) { return reinterpret_cast<rgbd360_map_align_trace*>(m->a_state.get() + sizeof(vmap::IcpState)); }
+
+int icp_launch_init(rgbd360_map* m, const float pose[16]) {
+    vmap::IcpPose g;
+    memcpy(g.m, pose, sizeof(g.m));
+    hipLaunchKernelGGL(vmap::k_vmap_icp_init, dim3(1), dim3(64), 0, m->s->stream, icp_state(m), g);
+    HIPC(m, hipGetLastError());
+    return 0;
+}
+int icp_launch_eval(rgbd360_map* m, const IcpJob& job, const vmap::Params& P, int final_pass, int32_t* key3, float* d2) {
+    const float max_dist2 = job.p.max_dist * job.p.max_dist;
+    with_choice<0, 1>(job.cloud, [&](auto S) {
+        hipLaunchKernelGGL((vmap::k_vmap_icp_eval<decltype(S)::value>), job.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.src,
+                           (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, max_dist2,
+                           (const vmap::IcpState*)icp_state(m), final_pass, m->a_part.get(), key3, d2);
+    });
+    HIPC(m, hipGetLastError());
+    return 0;
+}
+int icp_launch_solve(rgbd360_map* m, const IcpJob& job, int final_pass) {
+    hipLaunchKernelGGL(vmap::k_vmap_icp_solve, dim3(1), dim3(64), 0, m->s->stream, icp_state(m), icp_trace(m), (const double*)m->a_part.get(), job.n_rows,
+                       final_pass, job.p.min_matches, job.p.eps);
+    HIPC(m, hipGetLastError());
+    return 0;
+}
+// init, max_iters x (eval, solve), the final pass, the state's copy: enqueued, not waited for
+int icp_enqueue(rgbd360_map* m, const IcpJob& job, const float guess[16], int iters, int32_t* key3, float* d2) {
+    const vmap::Params P = vmap_params(m, guess);
+    if (const int rc = icp_launch_init(m, guess)) return rc;
+    for (int it = 0; it < iters; ++it) {
+        if (const int rc = icp_launch_eval(m, job, P, 0, nullptr, nullptr)) return rc;
+        if (const int rc = icp_launch_solve(m, job, 0)) return rc;
+    }
+    if (const int rc = icp_launch_eval(m, job, P, 1, key3, d2)) return rc;
+    if (const int rc = icp_launch_solve(m, job, 1)) return rc;
+    const size_t bytes = sizeof(vmap::IcpState) + (size_t)iters * sizeof(rgbd360_map_align_trace);
+    HIPC(m, hipMemcpyAsync(m->a_host, m->a_state, bytes, hipMemcpyDeviceToHost, m->s->stream));
+    return 0;
+}
+void icp_fill_result(const vmap::IcpState& st, rgbd360_map_align_result* res) {
+    if (!res) return;
+    res->status = st.status;
+    res->iterations = st.iterations;
+    res->converged = st.converged;
+    res->n_valid = (long long)st.row[17];
+    res->n_box_rejected = (long long)st.row[18];
+    res->n_out_of_range = (long long)st.row[19];
+    res->n_matched = (long long)st.row[0];
+    res->fitness = st.row[0] > 0.0 ? st.row[16] / st.row[0] : 0.0;
+    memcpy(res->hessian, st.H, sizeof(res->hessian));
+    memcpy(res->gradient, st.g, sizeof(res->gradient));
+}
+int icp_align(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
+              const float guess[16], int on_device, const rgbd360_map_align_params* params, float pose_out[16], rgbd360_map_align_result* result) {
+    IcpJob job;
+    if (const int rc = icp_check_params(m, params, job.p)) return rc;
+    if (!guess || !pose_out) return vmap_fail(m, -1, "guess and pose_out must not be null");
+    const int prep = icp_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job);
+    if (prep < 0) return prep;
+    m->a_trace.clear();
+    if (prep == 1) {             // nothing to align
+        memcpy(pose_out, guess, 16 * sizeof(float));
+        if (result) {
+            memset(result, 0, sizeof(*result));
+            result->status = RGBD360_NO_VALID_PIXELS;
+        }
+        return RGBD360_NO_VALID_PIXELS;
+    }
+    if (const int rc = icp_enqueue(m, job, guess, job.p.max_iters, nullptr, nullptr)) return rc;
+    HIPC(m, hipStreamSynchronize(m->s->stream));
+    const vmap::IcpState& st = *reinterpret_cast<const vmap::IcpState*>(m->a_host.get());
+    const rgbd360_map_align_trace* tr = reinterpret_cast<const rgbd360_map_align_trace*>(m->a_host.get() + sizeof(vmap::IcpState));
+    m->a_trace.assign(tr, tr + st.iterations);
+    memcpy(pose_out, st.pose, 16 * sizeof(float));
+    icp_fill_result(st, result);
+    return st.status;
+}
+}  // namespace
+
+extern "C" void rgbd360_map_default_align_params(const rgbd360_map* m, rgbd360_map_align_params* p) {
+    if (!p) return;
+    p->max_dist = m ? m->leaf : 0.05f;
+    p->max_iters = 10;       // OdometryRGBD360.cpp:102
+    p->eps = 1e-6f;
+    p->min_count = 1;
+    p->min_matches = 6;
+}
+
+extern "C" int rgbd360_map_align_sphere(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                        const float guess[16], int on_device, const rgbd360_map_align_params* params, float pose_out[16],
+                                        rgbd360_map_align_result* result) {
+    if (!m) return -1;
+    m->err.clear();
+    const int chk = vmap_check_sphere(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, guess);
+    if (chk < 0) return chk;
+    // (an empty image: a cloud of no points)
+    return icp_align(m, chk == 1 ? nullptr : depth, depth_step, depth_type, rows, cols, convention, nullptr, 0, guess, on_device, params, pose_out, result);
+}
+
+extern "C" int rgbd360_map_align_cloud(rgbd360_map* m, const float* xyz, long long n, const float guess[16], int on_device,
+                                       const rgbd360_map_align_params* params, float pose_out[16], rgbd360_map_align_result* result) {
+    if (!m) return -1;
+    m->err.clear();
+    return icp_align(m, nullptr, 0, 0, 0, 0, 0, xyz, n, guess, on_device, params, pose_out, result);
+}
+
+// measurement and tests (rgbd360_hip_diag.h)
+extern "C" int rgbd360_map_align_eval(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                      const float* xyz, long long n, const float pose[16], int on_device, const rgbd360_map_align_params* params,
+                                      double sums[17], long long counters[3], int32_t* key3_dev, float* d2_dev, int max_trace, int* n_trace,
+                                      rgbd360_map_align_trace* trace) {
+    if (!m) return -1;
+    m->err.clear();
+    if (n_trace) *n_trace = (int)m->a_trace.size();
+    for (int k = 0; trace && k < max_trace && k < (int)m->a_trace.size(); ++k) trace[k] = m->a_trace[k];
+    if (!pose) return 0;
+    IcpJob job;
+    if (const int rc = icp_check_params(m, params, job.p)) return rc;
+    if (depth) {
+        const int chk = vmap_check_sphere(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, pose);
+        if (chk < 0) return chk;
+        if (chk == 1) depth = nullptr, n = 0;
+    }
+    for (int k = 0; k < vmap::kIcpSums && sums; ++k) sums[k] = 0.0;
+    for (int k = 0; k < 3 && counters; ++k) counters[k] = 0;
+    job.p.max_iters = 0;
+    const int prep = icp_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job);
+    if (prep < 0) return prep;
+    if (prep == 1) return 0;
+    if (const int rc = icp_enqueue(m, job, pose, 0, key3_dev, d2_dev)) return rc;
+    HIPC(m, hipStreamSynchronize(m->s->stream));
+    const vmap::IcpState& st = *reinterpret_cast<const vmap::IcpState*>(m->a_host.get());
+    for (int k = 0; k < vmap::kIcpSums && sums; ++k) sums[k] = st.row[k];
+    for (int k = 0; k < 3 && counters; ++k) counters[k] = (long long)st.row[17 + k];
+    return 0;
+}
+
+extern "C" int rgbd360_map_time_align(rgbd360_map* m, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                      const float pose[16], const rgbd360_map_align_params* params, int reps, float avg_us[5], double* probes) {
+    if (!m) return -1;
+    m->err.clear();
+    const int chk = vmap_check_sphere(m, nullptr, 0, depth_dev, depth_step, depth_type, rows, cols, convention, pose);
+    if (chk < 0) return chk;
+    if (chk == 1 || reps < 1 || !avg_us) return vmap_fail(m, -1, "bad arguments");
+    IcpJob job;
+    if (const int rc = icp_check_params(m, params, job.p)) return rc;
+    const int prep = icp_prepare(m, depth_dev, depth_step, depth_type, rows, cols, convention, nullptr, 0, 1, job);
+    if (prep != 0) return prep;
+    const size_t drow = (size_t)cols * (depth_type == 0 ? 2 : 4);
+    HIPC(m, m->up_depth.ensure(drow * rows));
+    hipStream_t stream = m->s->stream;
+    const vmap::Params P = vmap_params(m, pose);
+    hipEvent_t e0 = nullptr, e1 = nullptr;       // made last, destroyed on every path below
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+        if (e0) hipEventDestroy(e0);
+        (void)hipGetLastError();
+        return vmap_fail(m, -103, "hipEventCreate failed");
+    }
+    int rc = 0;
+    auto timed = [&](float& out, int count, auto&& body) {
+        float ms = 0.f;
+        if (rc != 0) return;
+        if (hipEventRecord(e0, stream) != hipSuccess) rc = vmap_fail(m, -100, "hipEventRecord failed");
+        for (int r = 0; r < count && rc == 0; ++r) rc = body();
+        if (rc == 0 && (hipEventRecord(e1, stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+            rc = vmap_fail(m, -100, "timing the kernels failed");
+        out = ms * 1000.f / (float)count;
+    };
+    rc = icp_launch_init(m, pose);
+    if (rc == 0) rc = icp_launch_eval(m, job, P, 1, nullptr, nullptr);      // once untimed: code and tables loaded
+    timed(avg_us[0], reps, [&] { return icp_launch_eval(m, job, P, 1, nullptr, nullptr); });
+    timed(avg_us[1], reps, [&] { return icp_launch_solve(m, job, 1); });
+    if (rc == 0 && probes) {
+        vmap::IcpState st;
+        if (hipMemcpy(&st, m->a_state, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) rc = vmap_fail(m, -100, "reading the state failed");
+        *probes = st.row[21] > 0.0 ? st.row[20] / st.row[21] : 0.0;
+    }
+    timed(avg_us[2], 1, [&] { return vmap_launch_insert(m, P, job.src, false); });
+    if (rc == 0) {
+        rgbd360_map_stats stats;
+        rc = std::min(vmap_finish_insert(m, &stats), 0);
+    }
+    timed(avg_us[3], reps, [&] {
+        return hipMemcpy2DAsync(m->up_depth, drow, depth_dev, depth_step, drow, rows, hipMemcpyDeviceToDevice, stream) == hipSuccess ? 0 : -100;
+    });
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    if (rc) {
+        (void)hipGetLastError();
+        return rc;
+    }
+    double wall = 0.0;
+    for (int r = 0; r < reps; ++r) {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (const int rc2 = icp_enqueue(m, job, pose, job.p.max_iters, nullptr, nullptr)) return rc2;
+        HIPC(m, hipStreamSynchronize(stream));
+        wall += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    }
+    avg_us[4] = (float)(wall / reps);
+    return 0;
+}

@@ -1257,6 +1257,8 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
 // the resident voxel-grid global map (rgbd360_map_*)
 // ---------------------------------------------------------------------------------------------------------
 #include "voxel_map.h"
+#include "gn_math.h"
+#include "map_align.h"
 
 #ifdef RGBD360_HULL_DBG
 extern "C" int rgbd360_debug_hull_stats(unsigned long long* out /* [4096][8] */) {

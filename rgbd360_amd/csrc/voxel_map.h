@@ -3,7 +3,8 @@
 //   pcl::transformPointCloud(*frame->sphereCloud, *tc, currentPose); *viewer.globalMap += *tc; filter.filterVoxel(viewer.globalMap);
 // (OdometryRGBD360.cpp:242-268; the same steps at OdometryKeyFrame360.cpp:316-343, SphereGraphSLAM.cpp:116-137, 193-209,
 // KFsphere_SLAM.cpp:236, 558; the filter class is FilterPointCloud.h:63-99).  Part of the Frame360 translation unit
-// (rgbd360_frame360.hip includes it behind its helpers: F360State, HIPC, sphere_tables_dev).
+// (rgbd360_frame360.hip includes it behind its helpers: F360State, HIPC, sphere_tables_dev; map_align.h, the alignment of a frame against
+// the map, follows it).
 //
 // Definition, per input point and in this order (tests/voxel_map_reference.py restates it in numpy):
 //   1 point   from a sphere image: r360::sphere_point of the pixel, the bits of rgbd360_sphere_cloud; from a cloud: the three floats.
@@ -63,6 +64,12 @@ struct rgbd360_map {
     DevBuf<float> x_xyz;                 // the host read-out's device side
     DevBuf<uint8_t> x_rgb;
     DevBuf<int32_t> x_count, x_key;
+    // alignment against the map (map_align.h): one partial row per workgroup, the loop's state with its trace behind it, the state's
+    // pinned copy, and the trace of the last alignment as the host keeps it
+    DevBuf<double> a_part;
+    DevBuf<unsigned char> a_state;
+    PinnedBuf<unsigned char> a_host;
+    std::vector<rgbd360_map_align_trace> a_trace;
 };
 
 namespace vmap {
@@ -102,12 +109,11 @@ __host__ __device__ inline unsigned long long mix64(unsigned long long k) {     
     return k;
 }
 
-// steps 1-6 of one point: 0 skipped, 1 outside the box, 2 out of range, 3 kept (key and the three fixed-point terms)
-__device__ __forceinline__ int classify(const Params& P, float x, float y, float z, unsigned long long& key, long long f[3]) {
+// steps 1-6 of one point: 0 skipped, 1 outside the box, 2 out of range, 3 kept (key, the three fixed-point terms and the posed point w)
+__device__ __forceinline__ int classify(const Params& P, float x, float y, float z, unsigned long long& key, long long f[3], float w[3]) {
 #pragma clang fp contract(off)
     if (!(isfinite(x) && isfinite(y) && isfinite(z))) return 0;
     if (P.has_box && !(P.lo[0] <= x && x <= P.hi[0] && P.lo[1] <= y && y <= P.hi[1] && P.lo[2] <= z && z <= P.hi[2])) return 1;
-    float w[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) w[k] = ((P.pose[k] * x + P.pose[k + 4] * y) + P.pose[k + 8] * z) + P.pose[k + 12];
     if (!(fabsf(w[0]) < 4096.f && fabsf(w[1]) < 4096.f && fabsf(w[2]) < 4096.f)) return 2;
@@ -119,6 +125,10 @@ __device__ __forceinline__ int classify(const Params& P, float x, float y, float
     }
     key = (i[2] << 42) | (i[1] << 21) | i[0];
     return 3;
+}
+__device__ __forceinline__ int classify(const Params& P, float x, float y, float z, unsigned long long& key, long long f[3]) {
+    float w[3];
+    return classify(P, x, y, z, key, f, w);
 }
 
 // the slot of `key`, claimed if the key is new; -1: the key is new and no free slot lies within the probe bound

@@ -5,6 +5,7 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
 
     gmap = VoxelMap(reg, leaf=0.05, capacity=1 << 20)
     stats = gmap.insert_sphere(rgb, depth, currentPose, convention=0)
+    pose, res = gmap.align_sphere(depth, guess, convention=0)      # point-to-point ICP of a frame against the map (csrc/map_align.h)
     xyz, rgb, count, key = gmap.extract()          # sorted by (i_z, i_y, i_x)
 
 Every point has weight one and the sums are integers: the map does not depend on the order of the frames.
@@ -17,7 +18,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from .register import Rgbd360Error, _ptr, pose_to_cm
+from .register import Rgbd360Error, _ptr, pose_from_cm, pose_to_cm
 
 MAP_FULL = 3      # RGBD360_MAP_FULL
 
@@ -127,6 +128,58 @@ class VoxelMap:
         st = _lib.MapStats()
         rc = self._L.rgbd360_map_insert_cloud(self._handle(), _ptr(x), None if c is None else _ptr(c), x.shape[0], _ptr(p), 0, C.byref(st))
         return self._stats(rc, st)
+
+    # ---- alignment of a frame against the map (rgbd360_map_align_*; the reference's cloud ICP, OdometryRGBD360.cpp:98-114, 210-222)
+    def align_params(self, max_dist=None, max_iters=None, eps=None, min_count=None, min_matches=None):
+        """The defaults (max_dist = leaf, 10 iterations, eps 1e-6, min_count 1, min_matches 6) with the given fields replaced."""
+        p = _lib.MapAlignParams()
+        self._L.rgbd360_map_default_align_params(self._handle(), C.byref(p))
+        for name, v in (("max_dist", max_dist), ("max_iters", max_iters), ("eps", eps), ("min_count", min_count), ("min_matches", min_matches)):
+            if v is not None:
+                setattr(p, name, v)
+        return p
+
+    def _align_result(self, rc, out, res):
+        self._check(rc)
+        r = {name: getattr(res, name) for name, _ in _lib.MapAlignResult._fields_ if name not in ("hessian", "gradient")}
+        r["hessian"] = np.array(res.hessian, np.float32).reshape(6, 6).T.copy()
+        r["gradient"] = np.array(res.gradient, np.float32)
+        return pose_from_cm(out), r
+
+    def align_sphere(self, depth, guess, convention: int = 0, **params):
+        """Point-to-point ICP of the sphere frame `depth` (as in insert_sphere) against the map from `guess` (4x4 world <- frame); the
+        nearest neighbour is the nearest voxel centroid within max_dist <= leaf.  Returns (pose 4x4, result dict with status,
+        iterations, converged, the counters, n_matched, fitness, hessian, gradient).  The map is not changed."""
+        d = np.asarray(depth)
+        if d.dtype not in (np.uint16, np.float32) or d.ndim != 2:
+            raise Rgbd360Error("VoxelMap.align_sphere: depth must be HxW uint16 millimetres or float32 metres")
+        if d.size and d.strides[1] != d.dtype.itemsize:
+            d = np.ascontiguousarray(d)
+        p = self.align_params(**params)
+        g = pose_to_cm(guess)
+        out = np.zeros(16, np.float32)
+        res = _lib.MapAlignResult()
+        rc = self._L.rgbd360_map_align_sphere(self._handle(), _ptr(d), d.strides[0], 0 if d.dtype == np.uint16 else 1, d.shape[0], d.shape[1],
+                                              int(convention), _ptr(g), 0, C.byref(p), _ptr(out), C.byref(res))
+        return self._align_result(rc, out, res)
+
+    def align_cloud(self, xyz, guess, **params):
+        """The same for a cloud xyz: n x 3 float32 in the frame's coordinates."""
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        p = self.align_params(**params)
+        g = pose_to_cm(guess)
+        out = np.zeros(16, np.float32)
+        res = _lib.MapAlignResult()
+        rc = self._L.rgbd360_map_align_cloud(self._handle(), _ptr(x), x.shape[0], _ptr(g), 0, C.byref(p), _ptr(out), C.byref(res))
+        return self._align_result(rc, out, res)
+
+    def align_trace(self):
+        """One record per step of the last align call: (n, sum_sq, update[6]) (rgbd360_map_align_eval, the diagnostics header)."""
+        n = C.c_int()
+        self._check(self._L.rgbd360_map_align_eval(self._handle(), None, 0, 0, 0, 0, 0, None, 0, None, 0, None, None, None, None, None, 0, C.byref(n), None))
+        tr = (_lib.MapAlignTrace * max(n.value, 1))()
+        self._check(self._L.rgbd360_map_align_eval(self._handle(), None, 0, 0, 0, 0, 0, None, 0, None, 0, None, None, None, None, None, n.value, None, tr))
+        return [(int(t.n), float(t.sum_sq), np.array(t.update, np.float32)) for t in tr[:n.value]]
 
     # ---- read-out
     def __len__(self) -> int:
