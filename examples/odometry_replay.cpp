@@ -4,7 +4,7 @@
 //     frame_%03d.rgb  (H*W*3 uint8)   frame_%03d.depth (H*W uint16 mm)
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/odometry_replay.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o odometry_replay
-// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map]]
+// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane]]
 //         --sequence: all frames are loaded first and the frame loop runs inside the library (alignSequence)
 //         --multi N:  the same sequence sharded over N GPUs of this node from this one process (rgbd360_multi_*: one host thread
 //                     per device, contiguous shards of pairs, one ncclAllGather of the solved poses over xGMI); prints the
@@ -21,6 +21,9 @@
 //                     (GlobalMap::alignSphere; the cloud ICP of OdometryRGBD360.cpp:98-114, 210-222 with the map as its target): a
 //                     correction against everything seen so far.  An accepted refinement (status 0) replaces currentPose; prints one
 //                     extra "refine" line per frame.  Without the option the output is what it was.
+//         --refine-on-map-plane: the same with the point-to-plane form (GlobalMap::alignSpherePlane: the plane cost of the GICP those call
+//                     sites use); prints one "refine-plane" line per frame with the contributing points, the unsupported and nonplanar
+//                     ones and both fitness values.  Takes precedence over --refine-on-map.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -161,11 +164,12 @@ int main(int argc, char** argv) {
     const bool use_pbmap = argc > 5 && std::string(argv[5]) == "--pbmap";
     std::string map_file;
     float leaf = 0.05f;
-    bool refine_on_map = false;
+    bool refine_on_map = false, refine_on_map_plane = false;
     for (int a = 5; a < argc; ++a) {
         if (a + 1 < argc && std::string(argv[a]) == "--map") map_file = argv[a + 1];
         if (a + 1 < argc && std::string(argv[a]) == "--leaf") leaf = (float)atof(argv[a + 1]);
         if (std::string(argv[a]) == "--refine-on-map") refine_on_map = true;
+        if (std::string(argv[a]) == "--refine-on-map-plane") refine_on_map_plane = true;
     }
     std::unique_ptr<rgbd360::GlobalMap> globalMap;      // declared behind align360: destroyed before its context
     auto add_to_map = [&](const Frame& f) {                                                      // :242, 266-268
@@ -206,7 +210,15 @@ int main(int argc, char** argv) {
         printf("pair %d status %d sso %.4f rel_t %.5f %.5f %.5f pose_t %.5f %.5f %.5f\n", k - 1, align360.status(), align360.SSO,
                rel(0, 3), rel(1, 3), rel(2, 3), currentPose(0, 3), currentPose(1, 3), currentPose(2, 3));
         fprintf(stderr, "entropy %d %.5f\n", k - 1, align360.calcEntropy());                     // :207 (commented out in the source)
-        if (globalMap && refine_on_map) {
+        if (globalMap && refine_on_map_plane) {
+            rgbd360::Mat4f refined = currentPose;
+            const int status = globalMap->alignSpherePlane(frame2.sphereDepth, currentPose, refined, /*convention=*/0);
+            const rgbd360_map_align_plane_result& r = globalMap->alignPlaneResult();
+            printf("refine-plane %d status %d iterations %d matched %lld fitness %.6f pose_t %.5f %.5f %.5f unsupported %lld nonplanar %lld fitness_point %.6f\n",
+                   k - 1, status, r.iterations, r.n_matched, r.fitness, refined(0, 3), refined(1, 3), refined(2, 3), r.n_unsupported, r.n_nonplanar,
+                   r.fitness_point);
+            if (status == RGBD360_OK) currentPose = refined;
+        } else if (globalMap && refine_on_map) {
             rgbd360::Mat4f refined = currentPose;
             const int status = globalMap->alignSphere(frame2.sphereDepth, currentPose, refined, /*convention=*/0);
             const rgbd360_map_align_result& r = globalMap->alignResult();

@@ -13,6 +13,8 @@
 // The cloud ICP of the same programs (OdometryRGBD360.cpp:98-114, 210-222: filterVoxel, icp.setInputSource / setInputTarget / align(guess);
 // RegisterPairRGBD360.cpp:111-118, MethodsRegisterRGBD360.cpp:294-320, OdometryKeyFrame360.cpp:124-140) with the map as its target:
 //     globalMap.alignSphere(frame.sphereDepth, guess, pose)     point-to-point, nearest voxel centroid within max_dist <= leaf
+//     globalMap.alignSpherePlane(frame.sphereDepth, guess, pose)   point-to-plane: the same match, the plane fitted to the centroids around it
+//                                                                  (the call sites use pcl::GeneralizedIterativeClosestPoint, a plane cost)
 #pragma once
 
 #include <stdexcept>
@@ -86,7 +88,28 @@ class GlobalMap {
         check(rc, "rgbd360_map_align_cloud");
         return rc;
     }
-    const rgbd360_map_align_result& alignResult() const { return align_; }      // of the last align call
+    const rgbd360_map_align_result& alignResult() const { return align_; }      // of the last alignSphere / alignCloud call
+
+    // Point-to-plane ICP against the map (rgbd360_map_align_plane_*): the matches of alignSphere / alignCloud, the residual along the normal
+    // of the plane fitted to the centroids of the occupied cells around the point; corners and edges (no plane) contribute nothing.
+    rgbd360_map_align_plane_params alignPlaneParams() const {
+        rgbd360_map_align_plane_params p;
+        rgbd360_map_default_align_plane_params(map_, &p);
+        return p;
+    }
+    int alignSpherePlane(const ImageView& depth, const Mat4f& guess, Mat4f& pose, int convention = 0, const rgbd360_map_align_plane_params* params = nullptr) {
+        if (depth.type == ImageView::U8C3) throw std::runtime_error("GlobalMap::alignSpherePlane: a 16UC1 / 32FC1 depth image");
+        const int rc = rgbd360_map_align_plane_sphere(map_, depth.data, depth.step, depth.type == ImageView::U16C1 ? 0 : 1, depth.rows, depth.cols, convention,
+                                                      guess.m, 0, params, pose.m, &alignPlane_);
+        check(rc, "rgbd360_map_align_plane_sphere");
+        return rc;
+    }
+    int alignCloudPlane(const float* xyz, long long n, const Mat4f& guess, Mat4f& pose, const rgbd360_map_align_plane_params* params = nullptr) {
+        const int rc = rgbd360_map_align_plane_cloud(map_, xyz, n, guess.m, 0, params, pose.m, &alignPlane_);
+        check(rc, "rgbd360_map_align_plane_cloud");
+        return rc;
+    }
+    const rgbd360_map_align_plane_result& alignPlaneResult() const { return alignPlane_; }      // of the last alignSpherePlane / alignCloudPlane call
 
     long long size() const { return rgbd360_map_size(map_); }
     size_t bytes() const { return rgbd360_map_bytes(map_); }
@@ -120,6 +143,7 @@ class GlobalMap {
     rgbd360_map* map_ = nullptr;
     rgbd360_map_stats stats_{};
     rgbd360_map_align_result align_{};
+    rgbd360_map_align_plane_result alignPlane_{};
 };
 
 }  // namespace rgbd360

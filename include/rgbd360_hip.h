@@ -286,8 +286,8 @@ long long rgbd360_map_extract_dev(rgbd360_map* map, long long max_out, float* xy
  * align against a coarser map first.
  * Differences from the reference, stated: its active choice is pcl::GeneralizedIterativeClosestPoint at 0.3 - 0.4 m over a kd-tree of
  * the other cloud; this is the point-to-point form on the grid, against centroids.  PCL is not part of the reference tree: parity
- * with PCL is unpinned.  Out of scope: GICP covariances, point-to-plane residuals (the map has no normals), radii above one leaf, a
- * coarse-to-fine chain inside the library, several GPUs. */
+ * with PCL is unpinned.  The point-to-plane form of the same alignment follows below (rgbd360_map_align_plane_*).  Out of scope: GICP's
+ * per-point covariance weighting, radii above one leaf, a coarse-to-fine chain inside the library, several GPUs. */
 typedef struct {
     float max_dist;            /* setMaxCorrespondenceDistance, in (0, leaf]; default: leaf */
     int   max_iters;           /* setMaximumIterations: 10 (OdometryRGBD360.cpp:102) */
@@ -312,6 +312,65 @@ int    rgbd360_map_align_sphere(rgbd360_map* map, const void* depth, size_t dept
 /* The same for n points xyz[3 n] in the frame's coordinates (the filtered cloud of the reference's call sites). */
 int    rgbd360_map_align_cloud(rgbd360_map* map, const float* xyz, long long n, const float guess[16], int on_device,
                                const rgbd360_map_align_params* params, float pose_out[16], rgbd360_map_align_result* result);
+
+/* ---- point-to-plane ICP of a frame against the map (csrc/map_align_plane.h) -----------------------------------------------------
+ * Every cloud ICP call site of the reference uses pcl::GeneralizedIterativeClosestPoint, a plane-to-plane cost (OdometryRGBD360.cpp:98-114
+ * and 210-222, RegisterPairRGBD360.cpp:111-118, MethodsRegisterRGBD360.cpp:294-320).  Against one centroid per cell of a lattice the
+ * point-to-point residual above has a tangential part of up to half a leaf along a wall, which says nothing about the pose and pulls the
+ * translation towards the lattice; the distance to a plane fitted to the centroids around the point has none.  The map stores no normals:
+ * the plane comes from the centroids of the 27 cells the lookup reads anyway.  Per source point at the current pose T:
+ *   1 candidates and match: steps 1-4 of the point-to-point definition above, bit for bit -- the map's steps 1-5, the 27 cells in the
+ *     same order, count >= min_count, the read-out's centroid, d2 in float32, a tie to the earlier cell, kept iff d2 <= max_dist^2,
+ *     max_dist in (0, leaf].  The winning key and d2 of a point are those of rgbd360_map_align_*.
+ *   2 support: over ALL m candidates of step 2 (not only the match) e_j = (double)w - (double)c_j per component; sum e (3) and
+ *     sum e e^T (xx, xy, xz, yy, yz, zz) in float64, the candidates in the cells' order.  e_mean = sum e / m (= w - mu, mu the mean of
+ *     the centroids), C = sum e e^T / m - e_mean e_mean^T, every operation rounded on its own.  A kept point with m < min_support is
+ *     counted in n_unsupported and contributes nothing.
+ *   3 plane: with c2 = (C00 + C11) + C22, c1 = ((C00 C11 - C01^2) + (C00 C22 - C02^2)) + (C11 C22 - C12^2), c0 = det C by the first row,
+ *     the smallest eigenvalue l0 by Newton's method on l^3 - c2 l^2 + c1 l - c0 from l = 0 (Horner form; at most 12 steps; it ends when
+ *     the derivative is not positive or |step| <= 1e-15 c2).  The normal n is the largest (by squared length, the earlier on a tie) of
+ *     the cross products rows 0 x 1, 0 x 2, 1 x 2 of C - l0 I, divided by its length.  The middle eigenvalue: s = c2 - l0,
+ *     p = c1 - l0 s, l1 = 0.5 (s - sqrt(max(s s - 4 p, 0))).  The point is planar iff the largest squared cross product is > 0, l1 > 0
+ *     and l0 <= max_flatness l1; otherwise it is counted in n_nonplanar and contributes nothing (room corners and edges).  Float64,
+ *     only + - x / sqrt, no fused multiply-add: host, device and a restatement in IEEE arithmetic agree bit for bit.  The sign of n is
+ *     what the cross product gives; nothing depends on it.
+ *   4 residual r = (n_x e_mean_x + n_y e_mean_y) + n_z e_mean_z, the distance of w from the plane through mu; row J = [n ; w x n]
+ *     (= n^T [I | -[w]x]) for the increment pose <- pseudo_exp(v, omega) pose; float64 from the float32 w and the float64 n.
+ *   5 sums over the contributing points in float64, no floating-point atomics, one partial row per workgroup, rows added in ascending
+ *     order: n, the 21 upper-triangle terms of sum J J^T, sum J r (6), sum r r, sum e_match . e_match (the point-to-point fitness of the
+ *     same matches), and the counters.
+ *   6 step, stop tests, statuses and the final pass as in steps 6-7 above: H and g cast to float32, gn::step with lambda 0,
+ *     RGBD360_ILL_POSED on rank(H) < 6 (a single wall is ill-posed: the correct answer), RGBD360_NO_VALID_PIXELS when fewer than
+ *     min_matches points contribute, converged on v.v <= eps and omega.omega <= eps, one stream synchronisation per alignment.
+ *     fitness = sum r r / n, fitness_point = sum e_match . e_match / n, n_matched = n (the contributing points).
+ * Differences from GICP, stated: planes on the target side only (the source point is a point), no per-point covariance weighting (every
+ * contributing point has weight one), and PCL is not part of the reference tree: parity with PCL is unpinned. */
+typedef struct {
+    float max_dist;            /* as in rgbd360_map_align_params */
+    int   max_iters;
+    float eps;
+    int   min_count;
+    long long min_matches;     /* contributing points an evaluation must have: 6 */
+    int   min_support;         /* candidates (occupied cells of the 27) a point's plane needs, 1 .. 27: 5 */
+    float max_flatness;        /* largest l0 / l1 of a planar support, >= 0: 0.05 (about 2e-3 for a wall whose centroids lie within 2 mm of
+                                  it, about 0.3 for a wall-to-wall corner: settings, not measurements) */
+} rgbd360_map_align_plane_params;
+typedef struct {
+    int status, iterations, converged;
+    long long n_valid, n_box_rejected, n_out_of_range, n_matched;      /* of the final evaluation; n_matched: the contributing points */
+    double fitness;            /* sum r r / n_matched (0 when nothing contributed) */
+    float hessian[36], gradient[6];
+    long long n_unsupported, n_nonplanar;   /* kept matches with fewer than min_support candidates / whose support is not planar */
+    double fitness_point;      /* sum e.e / n_matched over the same matches: rgbd360_map_align_result.fitness's scale */
+} rgbd360_map_align_plane_result;
+void   rgbd360_map_default_align_plane_params(const rgbd360_map* map, rgbd360_map_align_plane_params* p);
+/* As rgbd360_map_align_sphere / _cloud (arguments, return values, refusals; also -1 for min_support outside 1 .. 27 or a negative or
+ * NaN max_flatness).  The map is not changed. */
+int    rgbd360_map_align_plane_sphere(rgbd360_map* map, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                      const float guess[16], int on_device, const rgbd360_map_align_plane_params* params, float pose_out[16],
+                                      rgbd360_map_align_plane_result* result);
+int    rgbd360_map_align_plane_cloud(rgbd360_map* map, const float* xyz, long long n, const float guess[16], int on_device,
+                                     const rgbd360_map_align_plane_params* params, float pose_out[16], rgbd360_map_align_plane_result* result);
 
 /* ---- one process, several GPUs (BASELINE.json configs[3]) ---------------------------------------------------
  * The sequence path shards by independent frame pairs: device d gets the contiguous pairs rgbd360_shard_range(n_frames-1, d,

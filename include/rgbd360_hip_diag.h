@@ -104,6 +104,27 @@ int rgbd360_map_align_eval(rgbd360_map* map, const void* depth, size_t depth_ste
 int rgbd360_map_time_align(rgbd360_map* map, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
                            const float pose[16], const rgbd360_map_align_params* params, int reps, float avg_us[5], double* probes);
 
+/* One evaluation of the point-to-plane alignment (rgbd360_map_align_plane_*, rgbd360_hip.h: steps 1-5 of its definition) at `pose`,
+ * inputs as in rgbd360_map_align_eval.  row[30]: n, the 21 upper-triangle terms of sum J J^T row by row, sum J r (6), sum r r,
+ * sum e_match . e_match; counters[5]: n_valid, n_box_rejected, n_out_of_range, n_unsupported, n_nonplanar.  DEVICE arrays per input
+ * point, any may be NULL: key3_dev / d2_dev as in rgbd360_map_align_eval (the kept match whatever became of the point afterwards),
+ * normal_r_dev four doubles (the normal and r as the sums take them, unrounded; zeros unless the class is 1), class_dev one byte:
+ * 0 no kept match, 1 contributing, 2 unsupported, 3 nonplanar.  The trace of the last alignment, of either kind, is
+ * rgbd360_map_align_eval's. */
+int rgbd360_map_align_plane_eval(rgbd360_map* map, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                 const float* xyz, long long n, const float pose[16], int on_device,
+                                 const rgbd360_map_align_plane_params* params, double row[30], long long counters[5], int32_t* key3_dev,
+                                 float* d2_dev, double* normal_r_dev, uint8_t* class_dev);
+/* Step 3 of that definition on the host (the function the kernel calls, compiled for the CPU): cov = C00, C01, C02, C11, C12, C22.
+ * normal[3]; eigen[2] (may be NULL) = l0, l1.  1 planar, 0 not, -1 a NULL argument.  Needs no device. */
+int rgbd360_map_plane_fit(const double cov[6], double max_flatness, double normal[3], double eigen[2]);
+/* The point-to-plane kernels under HIP events on a sphere frame in device memory, averages over `reps` launches in microseconds:
+ * avg_us[0] k_vmap_plane_eval, [1] k_vmap_icp_eval on the same frame, map and five shared parameters in the same run, [2]
+ * k_vmap_plane_solve, [3] a whole point-to-plane alignment of params->max_iters iterations from `pose` (enqueue to synchronisation, wall
+ * clock).  *probes as in rgbd360_map_time_align.  The map is not changed. */
+int rgbd360_map_time_align_plane(rgbd360_map* map, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                 const float pose[16], const rgbd360_map_align_plane_params* params, int reps, float avg_us[4], double* probes);
+
 /* The same timer with the launches rotating over n_ctx contexts of one device (each with its own copy of a frame pair) on
  * ctxs[0]'s stream: once n_ctx x the level's working set exceeds the 256 MiB Infinity Cache every launch is fed from HBM. */
 int rgbd360_time_eval_kernel_rotating(rgbd360_ctx* const* ctxs, int n_ctx, int level, const float pose[16], int method,

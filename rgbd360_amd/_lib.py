@@ -32,6 +32,8 @@ SYMBOLS = [
     "rgbd360_map_insert_sphere", "rgbd360_map_insert_cloud", "rgbd360_map_size", "rgbd360_map_clear", "rgbd360_map_extract",
     "rgbd360_map_extract_dev", "rgbd360_map_time_kernels",
     "rgbd360_map_default_align_params", "rgbd360_map_align_sphere", "rgbd360_map_align_cloud", "rgbd360_map_align_eval", "rgbd360_map_time_align",
+    "rgbd360_map_default_align_plane_params", "rgbd360_map_align_plane_sphere", "rgbd360_map_align_plane_cloud", "rgbd360_map_align_plane_eval",
+    "rgbd360_map_plane_fit", "rgbd360_map_time_align_plane",
 ]
 
 
@@ -82,6 +84,14 @@ class MapAlignResult(C.Structure):       # rgbd360_map_align_result
     _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("converged", C.c_int), ("n_valid", C.c_longlong), ("n_box_rejected", C.c_longlong),
                 ("n_out_of_range", C.c_longlong), ("n_matched", C.c_longlong), ("fitness", C.c_double), ("hessian", C.c_float * 36),
                 ("gradient", C.c_float * 6)]
+
+
+class MapAlignPlaneParams(C.Structure):  # rgbd360_map_align_plane_params
+    _fields_ = MapAlignParams._fields_ + [("min_support", C.c_int), ("max_flatness", C.c_float)]
+
+
+class MapAlignPlaneResult(C.Structure):  # rgbd360_map_align_plane_result
+    _fields_ = MapAlignResult._fields_ + [("n_unsupported", C.c_longlong), ("n_nonplanar", C.c_longlong), ("fitness_point", C.c_double)]
 
 
 class MapAlignTrace(C.Structure):        # rgbd360_map_align_trace (rgbd360_hip_diag.h)
@@ -267,5 +277,15 @@ def load() -> C.CDLL:
     L.rgbd360_map_align_eval.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, vp, ll, f32p, i32, C.POINTER(MapAlignParams), vp, vp, vp, vp, i32,
                                          C.POINTER(i32), vp]
     L.rgbd360_map_time_align.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, C.POINTER(MapAlignParams), i32, vp, C.POINTER(C.c_double)]
+    L.rgbd360_map_default_align_plane_params.argtypes = [vp, C.POINTER(MapAlignPlaneParams)]
+    L.rgbd360_map_default_align_plane_params.restype = None
+    L.rgbd360_map_align_plane_sphere.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, C.POINTER(MapAlignPlaneParams), f32p,
+                                                 C.POINTER(MapAlignPlaneResult)]
+    L.rgbd360_map_align_plane_cloud.argtypes = [vp, vp, ll, f32p, i32, C.POINTER(MapAlignPlaneParams), f32p, C.POINTER(MapAlignPlaneResult)]
+    L.rgbd360_map_align_plane_eval.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, vp, ll, f32p, i32, C.POINTER(MapAlignPlaneParams), vp, vp, vp, vp,
+                                               vp, vp]
+    L.rgbd360_map_plane_fit.argtypes = [vp, C.c_double, vp, vp]
+    L.rgbd360_map_time_align_plane.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, C.POINTER(MapAlignPlaneParams), i32, vp,
+                                               C.POINTER(C.c_double)]
     _lib = L
     return L

@@ -306,9 +306,10 @@ int icp_check_params(rgbd360_map* m, const rgbd360_map_align_params* params, rgb
     if (!(p.eps >= 0.f)) return vmap_fail(m, -1, "eps must not be negative");
     return 0;
 }
-// the source of a call in device memory (a host source is copied on the stream), the grid and the buffers; 1: an empty input
+// the source of a call in device memory (a host source is copied on the stream), the grid and the buffers; 1: an empty input.
+// row_words / state_size: the partial row's width and the loop state's size (map_align_plane.h has a wider row and its own state)
 int icp_prepare(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
-                int on_device, IcpJob& job) {
+                int on_device, IcpJob& job, int row_words = vmap::kIcpWords, size_t state_size = sizeof(vmap::IcpState)) {
     job.cloud = depth == nullptr;
     if (job.cloud) {
         if (n < 0 || n >= (1ll << 40)) return vmap_fail(m, -1, "bad point count");
@@ -337,8 +338,8 @@ int icp_prepare(rgbd360_map* m, const void* depth, size_t depth_step, int depth_
         job.n_points = (long long)rows * cols;
     }
     job.n_rows = (int)(job.grid.x * job.grid.y);
-    const size_t state_bytes = sizeof(vmap::IcpState) + (size_t)std::max(job.p.max_iters, 1) * sizeof(rgbd360_map_align_trace);
-    HIPC(m, m->a_part.ensure((size_t)job.n_rows * vmap::kIcpWords));
+    const size_t state_bytes = state_size + (size_t)std::max(job.p.max_iters, 1) * sizeof(rgbd360_map_align_trace);
+    HIPC(m, m->a_part.ensure((size_t)job.n_rows * row_words));
     HIPC(m, m->a_state.ensure(state_bytes));
     HIPC(m, m->a_host.ensure(state_bytes));
     return 0;
@@ -369,19 +370,27 @@ int icp_launch_solve(rgbd360_map* m, const IcpJob& job, int final_pass) {
     HIPC(m, hipGetLastError());
     return 0;
 }
-// init, max_iters x (eval, solve), the final pass, the state's copy: enqueued, not waited for
-int icp_enqueue(rgbd360_map* m, const IcpJob& job, const float guess[16], int iters, int32_t* key3, float* d2) {
-    const vmap::Params P = vmap_params(m, guess);
-    if (const int rc = icp_launch_init(m, guess)) return rc;
+// init, max_iters x (eval, solve), the final pass, the state's copy: enqueued, not waited for.  eval(final_pass) and solve(final_pass)
+// launch one kernel each; the state of state_size bytes has the trace behind it
+template <class Init, class Eval, class Solve>
+int icp_enqueue_loop(rgbd360_map* m, int iters, size_t state_size, Init&& init, Eval&& eval, Solve&& solve) {
+    if (const int rc = init()) return rc;
     for (int it = 0; it < iters; ++it) {
-        if (const int rc = icp_launch_eval(m, job, P, 0, nullptr, nullptr)) return rc;
-        if (const int rc = icp_launch_solve(m, job, 0)) return rc;
+        if (const int rc = eval(0)) return rc;
+        if (const int rc = solve(0)) return rc;
     }
-    if (const int rc = icp_launch_eval(m, job, P, 1, key3, d2)) return rc;
-    if (const int rc = icp_launch_solve(m, job, 1)) return rc;
-    const size_t bytes = sizeof(vmap::IcpState) + (size_t)iters * sizeof(rgbd360_map_align_trace);
+    if (const int rc = eval(1)) return rc;
+    if (const int rc = solve(1)) return rc;
+    const size_t bytes = state_size + (size_t)iters * sizeof(rgbd360_map_align_trace);
     HIPC(m, hipMemcpyAsync(m->a_host, m->a_state, bytes, hipMemcpyDeviceToHost, m->s->stream));
     return 0;
+}
+int icp_enqueue(rgbd360_map* m, const IcpJob& job, const float guess[16], int iters, int32_t* key3, float* d2) {
+    const vmap::Params P = vmap_params(m, guess);
+    return icp_enqueue_loop(
+        m, iters, sizeof(vmap::IcpState), [&] { return icp_launch_init(m, guess); },
+        [&](int final_pass) { return icp_launch_eval(m, job, P, final_pass, final_pass ? key3 : nullptr, final_pass ? d2 : nullptr); },
+        [&](int final_pass) { return icp_launch_solve(m, job, final_pass); });
 }
 void icp_fill_result(const vmap::IcpState& st, rgbd360_map_align_result* res) {
     if (!res) return;

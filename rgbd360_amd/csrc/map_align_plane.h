@@ -1,0 +1,591 @@
+// map_align_plane.h -- point-to-plane ICP of a posed sphere frame, or of a cloud, against the resident voxel map: the plane cost the
+// reference's call sites actually use (pcl::GeneralizedIterativeClosestPoint, a plane-to-plane cost: OdometryRGBD360.cpp:98-114, 210-222,
+// RegisterPairRGBD360.cpp:111-118, MethodsRegisterRGBD360.cpp:294-320) with the map as its target.  Part of the Frame360 translation unit,
+// behind map_align.h, whose lookup (vmap::find, icp_cell), host machinery (icp_prepare, icp_enqueue_loop) and trace it shares.
+//
+// Definition (include/rgbd360_hip.h, "point-to-plane ICP of a frame against the map"; tests/map_align_plane_reference.py
+// restates it in numpy).  Per source point at the current pose:
+//   1 candidates and match: steps 1-4 of map_align.h, bit for bit (the same key and d2 per point).
+//   2 support: over ALL m candidates e_j = (double)w - (double)c_j, sum e (3) and sum e e^T (6) in float64 in the cells' order;
+//     e_mean = sum e / m (= w - mu, mu the mean centroid), C = sum e e^T / m - e_mean e_mean^T.  A kept point with m < min_support is
+//     counted in n_unsupported.
+//   3 plane: vmap::plane_fit below -- the smallest eigenvalue of C by Newton's method on the characteristic polynomial from 0, its vector
+//     from the largest cross product of two rows of C - l0 I, the middle eigenvalue from the deflated quadratic; planar iff the cross
+//     product is not zero, l1 > 0 and l0 <= max_flatness l1, else the point is counted in n_nonplanar (room corners and edges).
+//   4 r = n . e_mean, J = [n ; w x n] in float64.
+//   5 37 float64 sums per workgroup row (kPlaneWords), the rows added in ascending order; no floating-point atomics.
+//   6 H and g straight from the row, cast to float32, gn::step with lambda 0, the stop tests and statuses of map_align.h.
+// The map stores no normals and insertion is unchanged: the plane comes from the centroids the lookup has already loaded.
+//
+//   k_vmap_plane_eval   the shape of k_vmap_icp_eval (256 threads, four points per thread one after another through one row
+//                       accumulator, all 27 first probes in flight before any is looked at, the table read-only); the nine support sums
+//                       ride in the candidate loop, the plane fit runs once per kept point with enough support.
+//   k_vmap_plane_solve  one workgroup, the structure of k_vmap_icp_solve.
+#pragma once
+
+namespace vmap {
+
+// a partial row: n, the 21 upper-triangle terms of sum J J^T (row by row), sum J r (6), sum r r, sum e_match . e_match, then the counters
+// n_valid, n_box_rejected, n_out_of_range, n_unsupported, n_nonplanar, probes, points searched (all doubles: exact integers)
+constexpr int kPlaneWords = 37;
+enum { kPlN = 0, kPlH = 1, kPlG = 22, kPlRR = 28, kPlEE = 29, kPlValid = 30, kPlBox = 31, kPlRange = 32, kPlUnsupported = 33, kPlNonplanar = 34,
+       kPlProbes = 35, kPlSearched = 36 };
+enum { kClassNone = 0, kClassKept = 1, kClassUnsupported = 2, kClassNonplanar = 3 };
+
+struct PlaneState {
+    float pose[16];
+    int done, status, iterations, converged;
+    double row[kPlaneWords];         // the totals of the last evaluation that was summed
+    float H[36], g[6];
+};
+
+// The plane of a support: a = the upper triangle (00, 01, 02, 11, 12, 22) of the covariance C.  n: the unit eigenvector of the smallest
+// eigenvalue l0; true iff the support is planar.  Float64 with + - x / sqrt only, every operation rounded on its own: the host, the device
+// and a restatement in any IEEE arithmetic give the same bits.  (The Newton iteration and the cross-product eigenvector are those of
+// k_f360_slot_frames, frame360_kernels.h, which keeps its own copy: DESIGN.md 3.13.)
+__host__ __device__ inline bool plane_fit(const double a[6], double max_flatness, double n[3], double& l0_out, double& l1_out) {
+#pragma clang fp contract(off)
+    const double a00 = a[0], a01 = a[1], a02 = a[2], a11 = a[3], a12 = a[4], a22 = a[5];
+    // f(l) = l^3 - c2 l^2 + c1 l - c0
+    const double c2 = (a00 + a11) + a22;
+    const double c1 = ((a00 * a11 - a01 * a01) + (a00 * a22 - a02 * a02)) + (a11 * a22 - a12 * a12);
+    const double c0 = (a00 * (a11 * a22 - a12 * a12) - a01 * (a01 * a22 - a12 * a02)) + a02 * (a01 * a12 - a11 * a02);
+    double l = 0.0;
+    for (int it = 0; it < 12; ++it) {
+        const double f = ((l - c2) * l + c1) * l - c0, df = (3.0 * l - 2.0 * c2) * l + c1;
+        if (!(df > 0.0)) break;
+        const double step = f / df;
+        l = l - step;
+        if ((step < 0.0 ? -step : step) <= 1e-15 * c2) break;
+    }
+    const double r0[3] = {a00 - l, a01, a02}, r1[3] = {a01, a11 - l, a12}, r2[3] = {a02, a12, a22 - l};
+    const double n01[3] = {r0[1] * r1[2] - r0[2] * r1[1], r0[2] * r1[0] - r0[0] * r1[2], r0[0] * r1[1] - r0[1] * r1[0]};
+    const double n02[3] = {r0[1] * r2[2] - r0[2] * r2[1], r0[2] * r2[0] - r0[0] * r2[2], r0[0] * r2[1] - r0[1] * r2[0]};
+    const double n12[3] = {r1[1] * r2[2] - r1[2] * r2[1], r1[2] * r2[0] - r1[0] * r2[2], r1[0] * r2[1] - r1[1] * r2[0]};
+    const double q01 = (n01[0] * n01[0] + n01[1] * n01[1]) + n01[2] * n01[2];
+    const double q02 = (n02[0] * n02[0] + n02[1] * n02[1]) + n02[2] * n02[2];
+    const double q12 = (n12[0] * n12[0] + n12[1] * n12[1]) + n12[2] * n12[2];
+    double qq = q01;
+    n[0] = n01[0], n[1] = n01[1], n[2] = n01[2];
+    if (q02 > qq) qq = q02, n[0] = n02[0], n[1] = n02[1], n[2] = n02[2];
+    if (q12 > qq) qq = q12, n[0] = n12[0], n[1] = n12[1], n[2] = n12[2];
+    // the middle eigenvalue: the smaller root of the quadratic left when l0 is divided out
+    const double s = c2 - l, p = c1 - l * s;
+    const double disc = s * s - 4.0 * p;
+    const double l1 = 0.5 * (s - sqrt(disc > 0.0 ? disc : 0.0));
+    l0_out = l;
+    l1_out = l1;
+    if (!(qq > 0.0)) {
+        n[0] = n[1] = n[2] = 0.0;
+        return false;
+    }
+    const double len = sqrt(qq);
+    n[0] = n[0] / len;
+    n[1] = n[1] / len;
+    n[2] = n[2] / len;
+    return l1 > 0.0 && l <= max_flatness * l1;
+}
+
+__global__ void k_vmap_plane_init(PlaneState* __restrict__ st, IcpPose guess) {
+    const int t = threadIdx.x;
+    if (t < 16) st->pose[t] = guess.m[t];
+    if (t < kPlaneWords) st->row[t] = 0.0;
+    if (t < 36) st->H[t] = 0.f;
+    if (t < 6) st->g[t] = 0.f;
+    if (t == 0) st->done = st->status = st->iterations = st->converged = 0;
+}
+
+// per-point outputs (tests; any may be null): key3 / d2_out as in k_vmap_icp_eval (the key of the kept MATCH whatever the point's class),
+// nr_out four doubles per point (the normal and r; zeros unless the class is kept), class_out one byte per point
+template <int SRC>
+__global__ __launch_bounds__(kThreads) void k_vmap_plane_eval(Params P, Source src, const unsigned long long* __restrict__ table, unsigned long long mask,
+                                                              unsigned long long min_count, float max_dist2, unsigned min_support, double max_flatness,
+                                                              const PlaneState* __restrict__ st, int final_pass, double* __restrict__ part,
+                                                              int32_t* __restrict__ key3, float* __restrict__ d2_out, double* __restrict__ nr_out,
+                                                              uint8_t* __restrict__ class_out) {
+#pragma clang fp contract(off)
+    if (!final_pass && st->done) return;
+    __shared__ double s_red[kThreads / 64][kPlaneWords];
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) P.pose[k] = st->pose[k];
+
+    // all loads of the thread first
+    float x[kPerThread], y[kPerThread], z[kPerThread];
+    bool in[kPerThread];
+    long long index[kPerThread];
+    if (SRC == 0) {
+        const int r = blockIdx.y;
+        const uint8_t* drow = (const uint8_t*)src.depth + (size_t)r * src.depth_step;
+        const float sp = src.sin_phi[r], cp = src.cos_phi[r];
+        float d[kPerThread], sth[kPerThread], cth[kPerThread];
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const int col = blockIdx.x * kTile + t + kThreads * k;
+            in[k] = col < src.cols;
+            const int cc = in[k] ? col : src.cols - 1;
+            index[k] = (long long)r * src.cols + cc;
+            d[k] = src.depth_type == 0 ? 0.001f * (float)((const uint16_t*)drow)[cc] : ((const float*)drow)[cc];
+            sth[k] = src.sin_theta[cc];
+            cth[k] = src.cos_theta[cc];
+        }
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) r360::sphere_point(src.convention, d[k], sp, cp, sth[k], cth[k], x[k], y[k], z[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const long long i = (long long)blockIdx.x * kTile + t + kThreads * k;
+            in[k] = i < src.n;
+            const size_t ii = in[k] ? (size_t)i : 0;
+            index[k] = (long long)ii;
+            x[k] = src.xyz[3 * ii];
+            y[k] = src.xyz[3 * ii + 1];
+            z[k] = src.xyz[3 * ii + 2];
+        }
+    }
+
+    double acc[kPlRR + 2];           // n, H (21), g (6), r r, e.e; the counters are integers until the reduction
+#pragma unroll
+    for (int q = 0; q < kPlRR + 2; ++q) acc[q] = 0.0;
+    unsigned n_probes = 0, n_valid = 0, n_box = 0, n_range = 0, n_unsupported = 0, n_nonplanar = 0, n_searched = 0;
+    // one point after another through the one accumulator
+#pragma unroll
+    for (int k = 0; k < kPerThread; ++k) {
+        if (!in[k]) continue;
+        unsigned long long key = 0;
+        long long f[3];
+        float w[3];
+        const int cls = classify(P, x[k], y[k], z[k], key, f, w);
+        n_valid += cls >= 1 ? 1u : 0u;
+        n_box += cls == 1 ? 1u : 0u;
+        n_range += cls == 2 ? 1u : 0u;
+        float best = __builtin_inff();
+        unsigned long long best_key = kEmpty;
+        float be[3] = {0.f, 0.f, 0.f};
+        double se[3] = {0.0, 0.0, 0.0}, see[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        unsigned m = 0;
+        if (cls == 3) {
+            n_searched += 1u;
+            const long long ib[3] = {(long long)(key & 0x1fffffull), (long long)((key >> 21) & 0x1fffffull), (long long)(key >> 42)};
+            unsigned long long k0[27];
+            // the first probe of every cell, before any is looked at
+#pragma unroll
+            for (int c = 0; c < 27; ++c) {
+                int dx, dy, dz;
+                icp_cell(c, dx, dy, dz);
+                const long long nx = ib[0] + dx, ny = ib[1] + dy, nz = ib[2] + dz;
+                const bool ok = nx >= 0 && nx < (1ll << 21) && ny >= 0 && ny < (1ll << 21) && nz >= 0 && nz < (1ll << 21);
+                const unsigned long long ck = ((unsigned long long)nz << 42) | ((unsigned long long)ny << 21) | (unsigned long long)nx;
+                k0[c] = ok ? table[(mix64(ck) & mask) * kFields] : kEmpty;
+                n_probes += ok ? 1u : 0u;
+            }
+#pragma unroll
+            for (int c = 0; c < 27; ++c) {
+                if (k0[c] == kEmpty) continue;       // an empty first slot, or no key at all: no candidate
+                int dx, dy, dz;
+                icp_cell(c, dx, dy, dz);
+                const unsigned long long ck = ((unsigned long long)(ib[2] + dz) << 42) | ((unsigned long long)(ib[1] + dy) << 21) | (unsigned long long)(ib[0] + dx);
+                const long long slot = find(table, mask, ck, mix64(ck) & mask, k0[c], n_probes);
+                if (slot < 0) continue;
+                const unsigned long long* rec = table + (unsigned long long)slot * kFields;
+                const unsigned long long cnt = rec[1];
+                if (cnt < min_count || cnt == 0) continue;
+                const double den = (double)cnt * kFix;
+                float cf[3], e[3];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    cf[q] = (float)((double)(long long)rec[2 + q] / den);
+                    e[q] = w[q] - cf[q];
+                }
+                const float d2 = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+                if (d2 < best) {
+                    best = d2;
+                    best_key = ck;
+                    be[0] = e[0];
+                    be[1] = e[1];
+                    be[2] = e[2];
+                }
+                // the support: every candidate, the difference in double
+                const double ex = (double)w[0] - (double)cf[0], ey = (double)w[1] - (double)cf[1], ez = (double)w[2] - (double)cf[2];
+                m += 1u;
+                se[0] += ex;
+                se[1] += ey;
+                se[2] += ez;
+                see[0] += ex * ex;
+                see[1] += ex * ey;
+                see[2] += ex * ez;
+                see[3] += ey * ey;
+                see[4] += ey * ez;
+                see[5] += ez * ez;
+            }
+        }
+        const bool kept = best_key != kEmpty && best <= max_dist2;
+        int pclass = kClassNone;
+        double nrm[3] = {0.0, 0.0, 0.0}, r = 0.0;
+        if (kept && m < min_support) {
+            pclass = kClassUnsupported;
+            n_unsupported += 1u;
+        } else if (kept) {
+            const double dm = (double)m;
+            const double mx = se[0] / dm, my = se[1] / dm, mz = se[2] / dm;
+            const double cov[6] = {see[0] / dm - mx * mx, see[1] / dm - mx * my, see[2] / dm - mx * mz,
+                                   see[3] / dm - my * my, see[4] / dm - my * mz, see[5] / dm - mz * mz};
+            double l0, l1;
+            if (plane_fit(cov, max_flatness, nrm, l0, l1)) {
+                pclass = kClassKept;
+                r = (nrm[0] * mx + nrm[1] * my) + nrm[2] * mz;
+                const double wx = w[0], wy = w[1], wz = w[2];
+                const double J[6] = {nrm[0], nrm[1], nrm[2], wy * nrm[2] - wz * nrm[1], wz * nrm[0] - wx * nrm[2], wx * nrm[1] - wy * nrm[0]};
+                const double ex = be[0], ey = be[1], ez = be[2];
+                acc[kPlN] += 1.0;
+                int h = kPlH;
+#pragma unroll
+                for (int a = 0; a < 6; ++a) {
+#pragma unroll
+                    for (int b = a; b < 6; ++b) acc[h++] += J[a] * J[b];
+                }
+#pragma unroll
+                for (int a = 0; a < 6; ++a) acc[kPlG + a] += J[a] * r;
+                acc[kPlRR] += r * r;
+                acc[kPlEE] += (ex * ex + ey * ey) + ez * ez;
+            } else {
+                pclass = kClassNonplanar;
+                n_nonplanar += 1u;
+                nrm[0] = nrm[1] = nrm[2] = 0.0;
+            }
+        }
+        if (key3) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) key3[3 * index[k] + q] = kept ? (int32_t)((best_key >> (21 * q)) & 0x1fffffull) - kBias : kNoKey;
+        }
+        if (d2_out) d2_out[index[k]] = best;
+        if (nr_out) {
+            nr_out[4 * index[k]] = nrm[0];
+            nr_out[4 * index[k] + 1] = nrm[1];
+            nr_out[4 * index[k] + 2] = nrm[2];
+            nr_out[4 * index[k] + 3] = r;
+        }
+        if (class_out) class_out[index[k]] = (uint8_t)pclass;
+    }
+
+    // wave, then workgroup: a fixed tree, the same sums from run to run
+    double row[kPlaneWords];
+#pragma unroll
+    for (int q = 0; q < kPlRR + 2; ++q) row[q] = acc[q];
+    row[kPlValid] = (double)n_valid;
+    row[kPlBox] = (double)n_box;
+    row[kPlRange] = (double)n_range;
+    row[kPlUnsupported] = (double)n_unsupported;
+    row[kPlNonplanar] = (double)n_nonplanar;
+    row[kPlProbes] = (double)n_probes;
+    row[kPlSearched] = (double)n_searched;
+#pragma unroll
+    for (int q = 0; q < kPlaneWords; ++q) {
+#pragma unroll
+        for (int off = 32; off; off >>= 1) row[q] += __shfl_xor(row[q], off);
+    }
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < kPlaneWords; ++q) s_red[t >> 6][q] = row[q];
+    }
+    __syncthreads();
+    if (t < kPlaneWords) {
+        double s = s_red[0][t];
+        for (int wv = 1; wv < kThreads / 64; ++wv) s += s_red[wv][t];
+        const size_t block = SRC == 0 ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
+        part[block * kPlaneWords + t] = s;
+    }
+}
+
+// H (column-major, symmetric) and g from the row
+__host__ __device__ inline void plane_assemble(const double* s, float* H, float* g) {
+    int h = kPlH;
+    for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b, ++h) H[b * 6 + a] = H[a * 6 + b] = (float)s[h];
+    for (int k = 0; k < 6; ++k) g[k] = (float)s[kPlG + k];
+}
+
+__global__ __launch_bounds__(64) void k_vmap_plane_solve(PlaneState* __restrict__ st, rgbd360_map_align_trace* __restrict__ trace, const double* __restrict__ part,
+                                                         int n_rows, int final_pass, long long min_matches, float eps) {
+#pragma clang fp contract(off)
+    if (!final_pass && st->done) return;
+    __shared__ double s_row[kPlaneWords];
+    const int t = threadIdx.x;
+    if (t < kPlaneWords) {       // the rows in ascending order
+        double s = 0.0;
+        for (int r = 0; r < n_rows; ++r) s += part[(size_t)r * kPlaneWords + t];
+        s_row[t] = s;
+        st->row[t] = s;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    const long long n = (long long)s_row[kPlN];
+    if (final_pass) {
+        plane_assemble(s_row, st->H, st->g);
+        if (st->status == RGBD360_OK && n < min_matches) st->status = RGBD360_NO_VALID_PIXELS;
+        st->done = 1;
+        return;
+    }
+    if (n < min_matches) {
+        st->status = RGBD360_NO_VALID_PIXELS;
+        st->done = 1;
+        return;
+    }
+    float H[36], g[6], pose[16], pose_new[16], u[6];
+    plane_assemble(s_row, H, g);
+    for (int k = 0; k < 16; ++k) pose[k] = st->pose[k];
+    if (gn::step(H, g, 0.f, pose, pose_new, u) != 0) {
+        st->status = RGBD360_ILL_POSED;
+        st->done = 1;
+        return;
+    }
+    for (int k = 0; k < 16; ++k) st->pose[k] = pose_new[k];
+    rgbd360_map_align_trace rec;
+    rec.n = n;
+    rec.sum_sq = s_row[kPlRR];
+    for (int k = 0; k < 6; ++k) rec.update[k] = u[k];
+    trace[st->iterations] = rec;
+    st->iterations += 1;
+    const float vv = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2], ww = (u[3] * u[3] + u[4] * u[4]) + u[5] * u[5];
+    if (vv <= eps && ww <= eps) {
+        st->converged = 1;
+        st->done = 1;
+    }
+}
+
+}  // namespace vmap
+
+namespace {
+
+struct PlaneJob {
+    IcpJob icp;                  // the source, the grid and the five fields the two methods share
+    int min_support;
+    float max_flatness;
+};
+
+int plane_check_params(rgbd360_map* m, const rgbd360_map_align_plane_params* params, PlaneJob& job) {
+    rgbd360_map_align_plane_params p;
+    if (params) p = *params;
+    else rgbd360_map_default_align_plane_params(m, &p);
+    const rgbd360_map_align_params shared = {p.max_dist, p.max_iters, p.eps, p.min_count, p.min_matches};
+    if (const int rc = icp_check_params(m, &shared, job.icp.p)) return rc;
+    if (p.min_support < 1 || p.min_support > 27) return vmap_fail(m, -1, "min_support must lie in 1 .. 27");
+    if (!(p.max_flatness >= 0.f)) return vmap_fail(m, -1, "max_flatness must not be negative");
+    job.min_support = p.min_support;
+    job.max_flatness = p.max_flatness;
+    return 0;
+}
+int plane_prepare(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
+                  int on_device, PlaneJob& job) {
+    return icp_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job.icp, vmap::kPlaneWords, sizeof(vmap::PlaneState));
+}
+vmap::PlaneState* plane_state(rgbd360_map* m) { return reinterpret_cast<vmap::PlaneState*>(m->a_state.get()); }
+rgbd360_map_align_trace* plane_trace(rgbd360_map* m) {
+    return reinterpret_cast<rgbd360_map_align_trace*>(m->a_state.get() + sizeof(vmap::PlaneState));
+}
+
+int plane_launch_init(rgbd360_map* m, const float pose[16]) {
+    vmap::IcpPose g;
+    memcpy(g.m, pose, sizeof(g.m));
+    hipLaunchKernelGGL(vmap::k_vmap_plane_init, dim3(1), dim3(64), 0, m->s->stream, plane_state(m), g);
+    HIPC(m, hipGetLastError());
+    return 0;
+}
+int plane_launch_eval(rgbd360_map* m, const PlaneJob& job, const vmap::Params& P, int final_pass, int32_t* key3, float* d2, double* nr, uint8_t* cls) {
+    const float max_dist2 = job.icp.p.max_dist * job.icp.p.max_dist;
+    with_choice<0, 1>(job.icp.cloud, [&](auto S) {
+        hipLaunchKernelGGL((vmap::k_vmap_plane_eval<decltype(S)::value>), job.icp.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.icp.src,
+                           (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.icp.p.min_count, max_dist2,
+                           (unsigned)job.min_support, (double)job.max_flatness, (const vmap::PlaneState*)plane_state(m), final_pass, m->a_part.get(), key3,
+                           d2, nr, cls);
+    });
+    HIPC(m, hipGetLastError());
+    return 0;
+}
+int plane_launch_solve(rgbd360_map* m, const PlaneJob& job, int final_pass) {
+    hipLaunchKernelGGL(vmap::k_vmap_plane_solve, dim3(1), dim3(64), 0, m->s->stream, plane_state(m), plane_trace(m), (const double*)m->a_part.get(),
+                       job.icp.n_rows, final_pass, job.icp.p.min_matches, job.icp.p.eps);
+    HIPC(m, hipGetLastError());
+    return 0;
+}
+int plane_enqueue(rgbd360_map* m, const PlaneJob& job, const float guess[16], int iters, int32_t* key3, float* d2, double* nr, uint8_t* cls) {
+    const vmap::Params P = vmap_params(m, guess);
+    return icp_enqueue_loop(
+        m, iters, sizeof(vmap::PlaneState), [&] { return plane_launch_init(m, guess); },
+        [&](int final_pass) {
+            return final_pass ? plane_launch_eval(m, job, P, 1, key3, d2, nr, cls) : plane_launch_eval(m, job, P, 0, nullptr, nullptr, nullptr, nullptr);
+        },
+        [&](int final_pass) { return plane_launch_solve(m, job, final_pass); });
+}
+void plane_fill_result(const vmap::PlaneState& st, rgbd360_map_align_plane_result* res) {
+    if (!res) return;
+    const double n = st.row[vmap::kPlN];
+    res->status = st.status;
+    res->iterations = st.iterations;
+    res->converged = st.converged;
+    res->n_valid = (long long)st.row[vmap::kPlValid];
+    res->n_box_rejected = (long long)st.row[vmap::kPlBox];
+    res->n_out_of_range = (long long)st.row[vmap::kPlRange];
+    res->n_matched = (long long)n;
+    res->fitness = n > 0.0 ? st.row[vmap::kPlRR] / n : 0.0;
+    memcpy(res->hessian, st.H, sizeof(res->hessian));
+    memcpy(res->gradient, st.g, sizeof(res->gradient));
+    res->n_unsupported = (long long)st.row[vmap::kPlUnsupported];
+    res->n_nonplanar = (long long)st.row[vmap::kPlNonplanar];
+    res->fitness_point = n > 0.0 ? st.row[vmap::kPlEE] / n : 0.0;
+}
+int plane_align(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
+                const float guess[16], int on_device, const rgbd360_map_align_plane_params* params, float pose_out[16],
+                rgbd360_map_align_plane_result* result) {
+    PlaneJob job;
+    if (const int rc = plane_check_params(m, params, job)) return rc;
+    if (!guess || !pose_out) return vmap_fail(m, -1, "guess and pose_out must not be null");
+    const int prep = plane_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job);
+    if (prep < 0) return prep;
+    m->a_trace.clear();
+    if (prep == 1) {             // nothing to align
+        memcpy(pose_out, guess, 16 * sizeof(float));
+        if (result) {
+            memset(result, 0, sizeof(*result));
+            result->status = RGBD360_NO_VALID_PIXELS;
+        }
+        return RGBD360_NO_VALID_PIXELS;
+    }
+    if (const int rc = plane_enqueue(m, job, guess, job.icp.p.max_iters, nullptr, nullptr, nullptr, nullptr)) return rc;
+    HIPC(m, hipStreamSynchronize(m->s->stream));
+    const vmap::PlaneState& st = *reinterpret_cast<const vmap::PlaneState*>(m->a_host.get());
+    const rgbd360_map_align_trace* tr = reinterpret_cast<const rgbd360_map_align_trace*>(m->a_host.get() + sizeof(vmap::PlaneState));
+    m->a_trace.assign(tr, tr + st.iterations);
+    memcpy(pose_out, st.pose, 16 * sizeof(float));
+    plane_fill_result(st, result);
+    return st.status;
+}
+}  // namespace
+
+extern "C" void rgbd360_map_default_align_plane_params(const rgbd360_map* m, rgbd360_map_align_plane_params* p) {
+    if (!p) return;
+    rgbd360_map_align_params shared;
+    rgbd360_map_default_align_params(m, &shared);
+    p->max_dist = shared.max_dist;
+    p->max_iters = shared.max_iters;
+    p->eps = shared.eps;
+    p->min_count = shared.min_count;
+    p->min_matches = shared.min_matches;
+    p->min_support = 5;
+    p->max_flatness = 0.05f;
+}
+
+extern "C" int rgbd360_map_align_plane_sphere(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                              const float guess[16], int on_device, const rgbd360_map_align_plane_params* params, float pose_out[16],
+                                              rgbd360_map_align_plane_result* result) {
+    if (!m) return -1;
+    m->err.clear();
+    const int chk = vmap_check_sphere(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, guess);
+    if (chk < 0) return chk;
+    // (an empty image: a cloud of no points)
+    return plane_align(m, chk == 1 ? nullptr : depth, depth_step, depth_type, rows, cols, convention, nullptr, 0, guess, on_device, params, pose_out, result);
+}
+
+extern "C" int rgbd360_map_align_plane_cloud(rgbd360_map* m, const float* xyz, long long n, const float guess[16], int on_device,
+                                             const rgbd360_map_align_plane_params* params, float pose_out[16], rgbd360_map_align_plane_result* result) {
+    if (!m) return -1;
+    m->err.clear();
+    return plane_align(m, nullptr, 0, 0, 0, 0, 0, xyz, n, guess, on_device, params, pose_out, result);
+}
+
+// measurement and tests (rgbd360_hip_diag.h)
+extern "C" int rgbd360_map_plane_fit(const double cov[6], double max_flatness, double normal[3], double eigen[2]) {
+    if (!cov || !normal) return -1;
+    double l0 = 0.0, l1 = 0.0;
+    const bool planar = vmap::plane_fit(cov, max_flatness, normal, l0, l1);
+    if (eigen) eigen[0] = l0, eigen[1] = l1;
+    return planar ? 1 : 0;
+}
+
+extern "C" int rgbd360_map_align_plane_eval(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                            const float* xyz, long long n, const float pose[16], int on_device,
+                                            const rgbd360_map_align_plane_params* params, double row[30], long long counters[5], int32_t* key3_dev,
+                                            float* d2_dev, double* normal_r_dev, uint8_t* class_dev) {
+    if (!m) return -1;
+    m->err.clear();
+    if (!pose) return vmap_fail(m, -1, "pose must not be null");
+    PlaneJob job;
+    if (const int rc = plane_check_params(m, params, job)) return rc;
+    if (depth) {
+        const int chk = vmap_check_sphere(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, pose);
+        if (chk < 0) return chk;
+        if (chk == 1) depth = nullptr, n = 0;
+    }
+    for (int k = 0; k < vmap::kPlValid && row; ++k) row[k] = 0.0;
+    for (int k = 0; k < 5 && counters; ++k) counters[k] = 0;
+    job.icp.p.max_iters = 0;
+    const int prep = plane_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job);
+    if (prep < 0) return prep;
+    if (prep == 1) return 0;
+    if (const int rc = plane_enqueue(m, job, pose, 0, key3_dev, d2_dev, normal_r_dev, class_dev)) return rc;
+    HIPC(m, hipStreamSynchronize(m->s->stream));
+    const vmap::PlaneState& st = *reinterpret_cast<const vmap::PlaneState*>(m->a_host.get());
+    for (int k = 0; k < vmap::kPlValid && row; ++k) row[k] = st.row[k];
+    for (int k = 0; k < 5 && counters; ++k) counters[k] = (long long)st.row[vmap::kPlValid + k];
+    return 0;
+}
+
+extern "C" int rgbd360_map_time_align_plane(rgbd360_map* m, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                            const float pose[16], const rgbd360_map_align_plane_params* params, int reps, float avg_us[4], double* probes) {
+    if (!m) return -1;
+    m->err.clear();
+    const int chk = vmap_check_sphere(m, nullptr, 0, depth_dev, depth_step, depth_type, rows, cols, convention, pose);
+    if (chk < 0) return chk;
+    if (chk == 1 || reps < 1 || !avg_us) return vmap_fail(m, -1, "bad arguments");
+    PlaneJob job;
+    if (const int rc = plane_check_params(m, params, job)) return rc;
+    // (the wider row and the larger state serve the point-to-point launches below as well)
+    const int prep = plane_prepare(m, depth_dev, depth_step, depth_type, rows, cols, convention, nullptr, 0, 1, job);
+    if (prep != 0) return prep;
+    hipStream_t stream = m->s->stream;
+    const vmap::Params P = vmap_params(m, pose);
+    hipEvent_t e0 = nullptr, e1 = nullptr;       // made last, destroyed on every path below
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+        if (e0) hipEventDestroy(e0);
+        (void)hipGetLastError();
+        return vmap_fail(m, -103, "hipEventCreate failed");
+    }
+    int rc = 0;
+    auto timed = [&](float& out, int count, auto&& body) {
+        float ms = 0.f;
+        if (rc != 0) return;
+        if (hipEventRecord(e0, stream) != hipSuccess) rc = vmap_fail(m, -100, "hipEventRecord failed");
+        for (int r = 0; r < count && rc == 0; ++r) rc = body();
+        if (rc == 0 && (hipEventRecord(e1, stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+            rc = vmap_fail(m, -100, "timing the kernels failed");
+        out = ms * 1000.f / (float)count;
+    };
+    // the point-to-point kernel first, on the same frame, map and buffers, then the plane kernels, whose state stays behind
+    rc = icp_launch_init(m, pose);
+    if (rc == 0) rc = icp_launch_eval(m, job.icp, P, 1, nullptr, nullptr);      // once untimed: code and tables loaded
+    timed(avg_us[1], reps, [&] { return icp_launch_eval(m, job.icp, P, 1, nullptr, nullptr); });
+    if (rc == 0) rc = plane_launch_init(m, pose);
+    if (rc == 0) rc = plane_launch_eval(m, job, P, 1, nullptr, nullptr, nullptr, nullptr);
+    timed(avg_us[0], reps, [&] { return plane_launch_eval(m, job, P, 1, nullptr, nullptr, nullptr, nullptr); });
+    timed(avg_us[2], reps, [&] { return plane_launch_solve(m, job, 1); });
+    if (rc == 0 && probes) {
+        vmap::PlaneState st;
+        if (hipMemcpy(&st, m->a_state, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) rc = vmap_fail(m, -100, "reading the state failed");
+        *probes = st.row[vmap::kPlSearched] > 0.0 ? st.row[vmap::kPlProbes] / st.row[vmap::kPlSearched] : 0.0;
+    }
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    if (rc) {
+        (void)hipGetLastError();
+        return rc;
+    }
+    double wall = 0.0;
+    for (int r = 0; r < reps; ++r) {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (const int rc2 = plane_enqueue(m, job, pose, job.icp.p.max_iters, nullptr, nullptr, nullptr, nullptr)) return rc2;
+        HIPC(m, hipStreamSynchronize(stream));
+        wall += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    }
+    avg_us[3] = (float)(wall / reps);
+    return 0;
+}

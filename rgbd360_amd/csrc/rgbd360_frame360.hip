@@ -1259,6 +1259,7 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
 #include "voxel_map.h"
 #include "gn_math.h"
 #include "map_align.h"
+#include "map_align_plane.h"
 
 #ifdef RGBD360_HULL_DBG
 extern "C" int rgbd360_debug_hull_stats(unsigned long long* out /* [4096][8] */) {

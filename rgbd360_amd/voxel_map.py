@@ -6,6 +6,7 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
     gmap = VoxelMap(reg, leaf=0.05, capacity=1 << 20)
     stats = gmap.insert_sphere(rgb, depth, currentPose, convention=0)
     pose, res = gmap.align_sphere(depth, guess, convention=0)      # point-to-point ICP of a frame against the map (csrc/map_align.h)
+    pose, res = gmap.align_sphere_plane(depth, guess, convention=0)    # point-to-plane: planes fitted to the centroids (csrc/map_align_plane.h)
     xyz, rgb, count, key = gmap.extract()          # sorted by (i_z, i_y, i_x)
 
 Every point has weight one and the sums are integers: the map does not depend on the order of the frames.
@@ -141,7 +142,7 @@ class VoxelMap:
 
     def _align_result(self, rc, out, res):
         self._check(rc)
-        r = {name: getattr(res, name) for name, _ in _lib.MapAlignResult._fields_ if name not in ("hessian", "gradient")}
+        r = {name: getattr(res, name) for name, _ in res._fields_ if name not in ("hessian", "gradient")}
         r["hessian"] = np.array(res.hessian, np.float32).reshape(6, 6).T.copy()
         r["gradient"] = np.array(res.gradient, np.float32)
         return pose_from_cm(out), r
@@ -173,8 +174,48 @@ class VoxelMap:
         rc = self._L.rgbd360_map_align_cloud(self._handle(), _ptr(x), x.shape[0], _ptr(g), 0, C.byref(p), _ptr(out), C.byref(res))
         return self._align_result(rc, out, res)
 
+    # ---- point-to-plane (rgbd360_map_align_plane_*: the same matches, the residual along the normal of a plane fitted to the centroids
+    #      of the occupied cells around the point; the plane cost of the reference's GICP call sites)
+    def align_plane_params(self, max_dist=None, max_iters=None, eps=None, min_count=None, min_matches=None, min_support=None, max_flatness=None):
+        """align_params' defaults, min_support = 5 and max_flatness = 0.05, with the given fields replaced."""
+        p = _lib.MapAlignPlaneParams()
+        self._L.rgbd360_map_default_align_plane_params(self._handle(), C.byref(p))
+        for name, v in (("max_dist", max_dist), ("max_iters", max_iters), ("eps", eps), ("min_count", min_count), ("min_matches", min_matches),
+                        ("min_support", min_support), ("max_flatness", max_flatness)):
+            if v is not None:
+                setattr(p, name, v)
+        return p
+
+    def align_sphere_plane(self, depth, guess, convention: int = 0, **params):
+        """Point-to-plane ICP of the sphere frame `depth` against the map from `guess`: align_sphere's matches, each with the plane fitted
+        to the centroids of the occupied cells around the point.  Returns (pose 4x4, result dict: align_sphere's fields -- n_matched counts
+        the contributing points, fitness is the mean squared plane distance -- plus n_unsupported, n_nonplanar and fitness_point, the
+        point-to-point fitness of the same matches).  The map is not changed."""
+        d = np.asarray(depth)
+        if d.dtype not in (np.uint16, np.float32) or d.ndim != 2:
+            raise Rgbd360Error("VoxelMap.align_sphere_plane: depth must be HxW uint16 millimetres or float32 metres")
+        if d.size and d.strides[1] != d.dtype.itemsize:
+            d = np.ascontiguousarray(d)
+        p = self.align_plane_params(**params)
+        g = pose_to_cm(guess)
+        out = np.zeros(16, np.float32)
+        res = _lib.MapAlignPlaneResult()
+        rc = self._L.rgbd360_map_align_plane_sphere(self._handle(), _ptr(d), d.strides[0], 0 if d.dtype == np.uint16 else 1, d.shape[0], d.shape[1],
+                                                    int(convention), _ptr(g), 0, C.byref(p), _ptr(out), C.byref(res))
+        return self._align_result(rc, out, res)
+
+    def align_cloud_plane(self, xyz, guess, **params):
+        """The same for a cloud xyz: n x 3 float32 in the frame's coordinates."""
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        p = self.align_plane_params(**params)
+        g = pose_to_cm(guess)
+        out = np.zeros(16, np.float32)
+        res = _lib.MapAlignPlaneResult()
+        rc = self._L.rgbd360_map_align_plane_cloud(self._handle(), _ptr(x), x.shape[0], _ptr(g), 0, C.byref(p), _ptr(out), C.byref(res))
+        return self._align_result(rc, out, res)
+
     def align_trace(self):
-        """One record per step of the last align call: (n, sum_sq, update[6]) (rgbd360_map_align_eval, the diagnostics header)."""
+        """One record per step of the last align call of either kind: (n, sum_sq, update[6]) (rgbd360_map_align_eval, the diagnostics header)."""
         n = C.c_int()
         self._check(self._L.rgbd360_map_align_eval(self._handle(), None, 0, 0, 0, 0, 0, None, 0, None, 0, None, None, None, None, None, 0, C.byref(n), None))
         tr = (_lib.MapAlignTrace * max(n.value, 1))()
