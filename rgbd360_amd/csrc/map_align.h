@@ -13,6 +13,12 @@
 // nearest centroid; a larger radius would need (2r + 1)^3 probes, callers who need a wider basin align against a coarser map first.
 // No cell is pruned: all 27 are looked up whatever the point's place in its cell.
 //
+// This header also holds what every method of alignment against the map shares with the loop (map_align_plane.h is the second
+// method): the loop's state, init and solve kernels (LoopState<WORDS>, k_vmap_icp_init<WORDS>, k_vmap_icp_solve<Row>) and the host driver
+// (icp_prepare, icp_enqueue<M>, icp_align<M>, icp_eval<M>).  A method is an evaluation kernel, a row description (PointMethod) and a host
+// description (PointIcp).  The evaluation kernels keep their own text of the source load, the 27-cell search and the block epilogue
+// (docs/HISTORY.md, last section: shared forms did not compile to the same code and could not be measured).
+//
 //   k_vmap_icp_eval   the shape of k_vmap_insert: 256 threads, four points per thread 256 apart, all loads of a thread first.  Per point
 //                     the first probe of all 27 cells is loaded before any is looked at (27 independent 8-byte loads in flight); a
 //                     probe sequence goes on with plain loads.  The table is never written.  A wave's 22 doubles (17 sums, three
@@ -24,7 +30,7 @@
 //   host              max_iters x (eval, solve), the final eval and its solve, one copy of the state, ONE synchronisation; no host read
 //                     between iterations.
 // Cost: up to 27 dependent-free first probes of 8 bytes per point against random 64-byte slots, plus 32 bytes per occupied candidate;
-// tools/map_align_perf.py measures it (profiles/map_align_perf.txt).
+// tools/map_align_perf.py measures it.
 #pragma once
 #include <chrono>
 
@@ -32,13 +38,16 @@ namespace vmap {
 
 constexpr int kIcpSums = 17;
 constexpr int kIcpWords = 22;        // a partial row: the 17 sums, n_valid, n_box_rejected, n_out_of_range, probes, points searched (all doubles: exact integers)
+constexpr int kIcpMaxWords = 37;     // the widest row of any method (map_align_plane.h): the buffers of a map serve every method
 constexpr int kIcpMaxIters = 1000;
 constexpr int kNoKey = -2147483647 - 1;
 
-struct IcpState {
+// the loop's state in device memory, the trace behind it; WORDS: the method's row
+template <int WORDS>
+struct LoopState {
     float pose[16];
     int done, status, iterations, converged;
-    double row[kIcpWords];           // the totals of the last evaluation that was summed
+    double row[WORDS];               // the totals of the last evaluation that was summed
     float H[36], g[6];
 };
 struct IcpPose {
@@ -76,10 +85,18 @@ __host__ __device__ inline void icp_assemble(const double* s, float* H, float* g
     for (int k = 0; k < 6; ++k) g[k] = (float)s[10 + k];
 }
 
-__global__ void k_vmap_icp_init(IcpState* __restrict__ st, IcpPose guess) {
+// What the loop needs to know of a method's row: its width, where n and the traced sum of squares are, where the counters start (the
+// sums lie in front of them: n_valid, n_box_rejected, n_out_of_range, the method's own, then probes and points searched), H and g.
+struct PointMethod {
+    static constexpr int kWords = kIcpWords, kN = 0, kSumSq = 16, kCounters = 17, kProbes = 20, kSearched = 21;
+    __host__ __device__ static void assemble(const double* s, float* H, float* g) { icp_assemble(s, H, g); }
+};
+
+template <int WORDS>
+__global__ void k_vmap_icp_init(LoopState<WORDS>* __restrict__ st, IcpPose guess) {
     const int t = threadIdx.x;
     if (t < 16) st->pose[t] = guess.m[t];
-    if (t < kIcpWords) st->row[t] = 0.0;
+    if (t < WORDS) st->row[t] = 0.0;
     if (t < 36) st->H[t] = 0.f;
     if (t < 6) st->g[t] = 0.f;
     if (t == 0) st->done = st->status = st->iterations = st->converged = 0;
@@ -87,7 +104,7 @@ __global__ void k_vmap_icp_init(IcpState* __restrict__ st, IcpPose guess) {
 
 template <int SRC>
 __global__ __launch_bounds__(kThreads) void k_vmap_icp_eval(Params P, Source src, const unsigned long long* __restrict__ table, unsigned long long mask,
-                                                            unsigned long long min_count, float max_dist2, const IcpState* __restrict__ st, int final_pass,
+                                                            unsigned long long min_count, float max_dist2, const LoopState<kIcpWords>* __restrict__ st, int final_pass,
                                                             double* __restrict__ part, int32_t* __restrict__ key3, float* __restrict__ d2_out) {
 #pragma clang fp contract(off)
     if (!final_pass && st->done) return;
@@ -235,23 +252,26 @@ __global__ __launch_bounds__(kThreads) void k_vmap_icp_eval(Params P, Source src
     }
 }
 
-__global__ __launch_bounds__(64) void k_vmap_icp_solve(IcpState* __restrict__ st, rgbd360_map_align_trace* __restrict__ trace, const double* __restrict__ part,
-                                                       int n_rows, int final_pass, long long min_matches, float eps) {
+// one workgroup: the rows added in ascending order (one lane per column), then lane 0: H and g, gn::step, status and the stop test, one
+// trace record per applied step, the new pose and the state word
+template <class M>
+__global__ __launch_bounds__(64) void k_vmap_icp_solve(LoopState<M::kWords>* __restrict__ st, rgbd360_map_align_trace* __restrict__ trace,
+                                                       const double* __restrict__ part, int n_rows, int final_pass, long long min_matches, float eps) {
 #pragma clang fp contract(off)
     if (!final_pass && st->done) return;
-    __shared__ double s_row[kIcpWords];
+    __shared__ double s_row[M::kWords];
     const int t = threadIdx.x;
-    if (t < kIcpWords) {         // the rows in ascending order
+    if (t < M::kWords) {         // the rows in ascending order
         double s = 0.0;
-        for (int r = 0; r < n_rows; ++r) s += part[(size_t)r * kIcpWords + t];
+        for (int r = 0; r < n_rows; ++r) s += part[(size_t)r * M::kWords + t];
         s_row[t] = s;
         st->row[t] = s;
     }
     __syncthreads();
     if (t != 0) return;
-    const long long n = (long long)s_row[0];
+    const long long n = (long long)s_row[M::kN];
     if (final_pass) {
-        icp_assemble(s_row, st->H, st->g);
+        M::assemble(s_row, st->H, st->g);
         if (st->status == RGBD360_OK && n < min_matches) st->status = RGBD360_NO_VALID_PIXELS;
         st->done = 1;
         return;
@@ -262,7 +282,7 @@ __global__ __launch_bounds__(64) void k_vmap_icp_solve(IcpState* __restrict__ st
         return;
     }
     float H[36], g[6], pose[16], pose_new[16], u[6];
-    icp_assemble(s_row, H, g);
+    M::assemble(s_row, H, g);
     for (int k = 0; k < 16; ++k) pose[k] = st->pose[k];
     if (gn::step(H, g, 0.f, pose, pose_new, u) != 0) {
         st->status = RGBD360_ILL_POSED;
@@ -272,7 +292,7 @@ __global__ __launch_bounds__(64) void k_vmap_icp_solve(IcpState* __restrict__ st
     for (int k = 0; k < 16; ++k) st->pose[k] = pose_new[k];
     rgbd360_map_align_trace rec;
     rec.n = n;
-    rec.sum_sq = s_row[16];
+    rec.sum_sq = s_row[M::kSumSq];
     for (int k = 0; k < 6; ++k) rec.update[k] = u[k];
     trace[st->iterations] = rec;
     st->iterations += 1;
@@ -287,7 +307,7 @@ __global__ __launch_bounds__(64) void k_vmap_icp_solve(IcpState* __restrict__ st
 
 namespace {
 
-// what one alignment call works on: the source in device memory, the launch grid, the checked parameters
+// what one alignment call works on: the source in device memory, the launch grid, the checked parameters (the last two: point-to-plane)
 struct IcpJob {
     vmap::Source src;
     bool cloud;
@@ -295,6 +315,8 @@ struct IcpJob {
     int n_rows;
     long long n_points;
     rgbd360_map_align_params p;
+    int min_support;
+    float max_flatness;
 };
 
 int icp_check_params(rgbd360_map* m, const rgbd360_map_align_params* params, rgbd360_map_align_params& p) {
@@ -306,10 +328,10 @@ int icp_check_params(rgbd360_map* m, const rgbd360_map_align_params* params, rgb
     if (!(p.eps >= 0.f)) return vmap_fail(m, -1, "eps must not be negative");
     return 0;
 }
-// the source of a call in device memory (a host source is copied on the stream), the grid and the buffers; 1: an empty input.
-// row_words / state_size: the partial row's width and the loop state's size (map_align_plane.h has a wider row and its own state)
+// the source of a call in device memory (a host source is copied on the stream), the grid and the buffers, wide enough for every
+// method; 1: an empty input
 int icp_prepare(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
-                int on_device, IcpJob& job, int row_words = vmap::kIcpWords, size_t state_size = sizeof(vmap::IcpState)) {
+                int on_device, IcpJob& job) {
     job.cloud = depth == nullptr;
     if (job.cloud) {
         if (n < 0 || n >= (1ll << 40)) return vmap_fail(m, -1, "bad point count");
@@ -338,98 +360,162 @@ int icp_prepare(rgbd360_map* m, const void* depth, size_t depth_step, int depth_
         job.n_points = (long long)rows * cols;
     }
     job.n_rows = (int)(job.grid.x * job.grid.y);
-    const size_t state_bytes = state_size + (size_t)std::max(job.p.max_iters, 1) * sizeof(rgbd360_map_align_trace);
-    HIPC(m, m->a_part.ensure((size_t)job.n_rows * row_words));
+    const size_t state_bytes = sizeof(vmap::LoopState<vmap::kIcpMaxWords>) + (size_t)std::max(job.p.max_iters, 1) * sizeof(rgbd360_map_align_trace);
+    HIPC(m, m->a_part.ensure((size_t)job.n_rows * vmap::kIcpMaxWords));
     HIPC(m, m->a_state.ensure(state_bytes));
     HIPC(m, m->a_host.ensure(state_bytes));
     return 0;
 }
-vmap::IcpState* icp_state(rgbd360_map* m) { return reinterpret_cast<vmap::IcpState*>(m->a_state.get()); }
-rgbd360_map_align_trace* icp_trace(rgbd360_map* m) { return reinterpret_cast<rgbd360_map_align_trace*>(m->a_state.get() + sizeof(vmap::IcpState)); }
 
+// A method M (PointIcp here, PlaneIcp in map_align_plane.h) is its row (Row = vmap::PointMethod, also its base) and, for the host: Params and Result, the
+// public structs; Out, the per-point output pointers of an evaluation; check(m, params, job), the checked parameters into the job;
+// launch_eval(m, job, P, final_pass, out), the evaluation kernel; fill_extra(st, res), the result fields the method adds.
+template <class M>
+using IcpState = vmap::LoopState<M::kWords>;
+template <class M>
+IcpState<M>* icp_state(rgbd360_map* m) { return reinterpret_cast<IcpState<M>*>(m->a_state.get()); }
+template <class M>
+rgbd360_map_align_trace* icp_trace(rgbd360_map* m) { return reinterpret_cast<rgbd360_map_align_trace*>(m->a_state.get() + sizeof(IcpState<M>)); }
+
+template <class M>
 int icp_launch_init(rgbd360_map* m, const float pose[16]) {
     vmap::IcpPose g;
     memcpy(g.m, pose, sizeof(g.m));
-    hipLaunchKernelGGL(vmap::k_vmap_icp_init, dim3(1), dim3(64), 0, m->s->stream, icp_state(m), g);
+    hipLaunchKernelGGL((vmap::k_vmap_icp_init<M::kWords>), dim3(1), dim3(64), 0, m->s->stream, icp_state<M>(m), g);
     HIPC(m, hipGetLastError());
     return 0;
 }
-int icp_launch_eval(rgbd360_map* m, const IcpJob& job, const vmap::Params& P, int final_pass, int32_t* key3, float* d2) {
-    const float max_dist2 = job.p.max_dist * job.p.max_dist;
-    with_choice<0, 1>(job.cloud, [&](auto S) {
-        hipLaunchKernelGGL((vmap::k_vmap_icp_eval<decltype(S)::value>), job.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.src,
-                           (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, max_dist2,
-                           (const vmap::IcpState*)icp_state(m), final_pass, m->a_part.get(), key3, d2);
-    });
-    HIPC(m, hipGetLastError());
-    return 0;
-}
+template <class M>
 int icp_launch_solve(rgbd360_map* m, const IcpJob& job, int final_pass) {
-    hipLaunchKernelGGL(vmap::k_vmap_icp_solve, dim3(1), dim3(64), 0, m->s->stream, icp_state(m), icp_trace(m), (const double*)m->a_part.get(), job.n_rows,
-                       final_pass, job.p.min_matches, job.p.eps);
+    hipLaunchKernelGGL((vmap::k_vmap_icp_solve<typename M::Row>), dim3(1), dim3(64), 0, m->s->stream, icp_state<M>(m), icp_trace<M>(m), (const double*)m->a_part.get(),
+                       job.n_rows, final_pass, job.p.min_matches, job.p.eps);
     HIPC(m, hipGetLastError());
     return 0;
 }
-// init, max_iters x (eval, solve), the final pass, the state's copy: enqueued, not waited for.  eval(final_pass) and solve(final_pass)
-// launch one kernel each; the state of state_size bytes has the trace behind it
-template <class Init, class Eval, class Solve>
-int icp_enqueue_loop(rgbd360_map* m, int iters, size_t state_size, Init&& init, Eval&& eval, Solve&& solve) {
-    if (const int rc = init()) return rc;
+// init, iters x (eval, solve), the final pass with the per-point outputs, the copy of the state and its trace: enqueued, not waited for
+template <class M>
+int icp_enqueue(rgbd360_map* m, const IcpJob& job, const float guess[16], int iters, const typename M::Out& out) {
+    const vmap::Params P = vmap_params(m, guess);
+    if (const int rc = icp_launch_init<M>(m, guess)) return rc;
     for (int it = 0; it < iters; ++it) {
-        if (const int rc = eval(0)) return rc;
-        if (const int rc = solve(0)) return rc;
+        if (const int rc = M::launch_eval(m, job, P, 0, typename M::Out{})) return rc;
+        if (const int rc = icp_launch_solve<M>(m, job, 0)) return rc;
     }
-    if (const int rc = eval(1)) return rc;
-    if (const int rc = solve(1)) return rc;
-    const size_t bytes = state_size + (size_t)iters * sizeof(rgbd360_map_align_trace);
+    if (const int rc = M::launch_eval(m, job, P, 1, out)) return rc;
+    if (const int rc = icp_launch_solve<M>(m, job, 1)) return rc;
+    const size_t bytes = sizeof(IcpState<M>) + (size_t)iters * sizeof(rgbd360_map_align_trace);
     HIPC(m, hipMemcpyAsync(m->a_host, m->a_state, bytes, hipMemcpyDeviceToHost, m->s->stream));
     return 0;
 }
-int icp_enqueue(rgbd360_map* m, const IcpJob& job, const float guess[16], int iters, int32_t* key3, float* d2) {
-    const vmap::Params P = vmap_params(m, guess);
-    return icp_enqueue_loop(
-        m, iters, sizeof(vmap::IcpState), [&] { return icp_launch_init(m, guess); },
-        [&](int final_pass) { return icp_launch_eval(m, job, P, final_pass, final_pass ? key3 : nullptr, final_pass ? d2 : nullptr); },
-        [&](int final_pass) { return icp_launch_solve(m, job, final_pass); });
-}
-void icp_fill_result(const vmap::IcpState& st, rgbd360_map_align_result* res) {
-    if (!res) return;
-    res->status = st.status;
-    res->iterations = st.iterations;
-    res->converged = st.converged;
-    res->n_valid = (long long)st.row[17];
-    res->n_box_rejected = (long long)st.row[18];
-    res->n_out_of_range = (long long)st.row[19];
-    res->n_matched = (long long)st.row[0];
-    res->fitness = st.row[0] > 0.0 ? st.row[16] / st.row[0] : 0.0;
-    memcpy(res->hessian, st.H, sizeof(res->hessian));
-    memcpy(res->gradient, st.g, sizeof(res->gradient));
-}
+template <class M>
+const IcpState<M>& icp_host_state(rgbd360_map* m) { return *reinterpret_cast<const IcpState<M>*>(m->a_host.get()); }
+
+template <class M>
 int icp_align(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
-              const float guess[16], int on_device, const rgbd360_map_align_params* params, float pose_out[16], rgbd360_map_align_result* result) {
+              const float guess[16], int on_device, const typename M::Params* params, float pose_out[16], typename M::Result* res) {
     IcpJob job;
-    if (const int rc = icp_check_params(m, params, job.p)) return rc;
+    if (const int rc = M::check(m, params, job)) return rc;
     if (!guess || !pose_out) return vmap_fail(m, -1, "guess and pose_out must not be null");
     const int prep = icp_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job);
     if (prep < 0) return prep;
     m->a_trace.clear();
     if (prep == 1) {             // nothing to align
         memcpy(pose_out, guess, 16 * sizeof(float));
-        if (result) {
-            memset(result, 0, sizeof(*result));
-            result->status = RGBD360_NO_VALID_PIXELS;
+        if (res) {
+            memset(res, 0, sizeof(*res));
+            res->status = RGBD360_NO_VALID_PIXELS;
         }
         return RGBD360_NO_VALID_PIXELS;
     }
-    if (const int rc = icp_enqueue(m, job, guess, job.p.max_iters, nullptr, nullptr)) return rc;
+    if (const int rc = icp_enqueue<M>(m, job, guess, job.p.max_iters, typename M::Out{})) return rc;
     HIPC(m, hipStreamSynchronize(m->s->stream));
-    const vmap::IcpState& st = *reinterpret_cast<const vmap::IcpState*>(m->a_host.get());
-    const rgbd360_map_align_trace* tr = reinterpret_cast<const rgbd360_map_align_trace*>(m->a_host.get() + sizeof(vmap::IcpState));
+    const IcpState<M>& st = icp_host_state<M>(m);
+    const rgbd360_map_align_trace* tr = reinterpret_cast<const rgbd360_map_align_trace*>(m->a_host.get() + sizeof(IcpState<M>));
     m->a_trace.assign(tr, tr + st.iterations);
     memcpy(pose_out, st.pose, 16 * sizeof(float));
-    icp_fill_result(st, result);
+    if (res) {
+        const double nm = st.row[M::kN];
+        res->status = st.status;
+        res->iterations = st.iterations;
+        res->converged = st.converged;
+        res->n_valid = (long long)st.row[M::kCounters];
+        res->n_box_rejected = (long long)st.row[M::kCounters + 1];
+        res->n_out_of_range = (long long)st.row[M::kCounters + 2];
+        res->n_matched = (long long)nm;
+        res->fitness = nm > 0.0 ? st.row[M::kSumSq] / nm : 0.0;
+        memcpy(res->hessian, st.H, sizeof(res->hessian));
+        memcpy(res->gradient, st.g, sizeof(res->gradient));
+        M::fill_extra(st, res);
+    }
     return st.status;
 }
+// one evaluation at `pose` (the diag entries): the sums in front of the counters, the method's counters, the per-point outputs
+template <class M>
+int icp_eval(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
+             const float pose[16], int on_device, const typename M::Params* params, double* sums, long long* counters, const typename M::Out& out) {
+    constexpr int n_counters = M::kProbes - M::kCounters;
+    IcpJob job;
+    if (const int rc = M::check(m, params, job)) return rc;
+    if (depth) {
+        const int chk = vmap_check_sphere(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, pose);
+        if (chk < 0) return chk;
+        if (chk == 1) depth = nullptr, n = 0;
+    }
+    for (int k = 0; k < M::kCounters && sums; ++k) sums[k] = 0.0;
+    for (int k = 0; k < n_counters && counters; ++k) counters[k] = 0;
+    job.p.max_iters = 0;
+    const int prep = icp_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job);
+    if (prep < 0) return prep;
+    if (prep == 1) return 0;
+    if (const int rc = icp_enqueue<M>(m, job, pose, 0, out)) return rc;
+    HIPC(m, hipStreamSynchronize(m->s->stream));
+    const IcpState<M>& st = icp_host_state<M>(m);
+    for (int k = 0; k < M::kCounters && sums; ++k) sums[k] = st.row[k];
+    for (int k = 0; k < n_counters && counters; ++k) counters[k] = (long long)st.row[M::kCounters + k];
+    return 0;
+}
+// measurement: probes per point searched of the evaluation summed last, and the wall time of a whole alignment
+template <class M>
+int icp_read_probes(rgbd360_map* m, double* probes) {
+    IcpState<M> st;
+    if (hipMemcpy(&st, m->a_state, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) return vmap_fail(m, -100, "reading the state failed");
+    *probes = st.row[M::kSearched] > 0.0 ? st.row[M::kProbes] / st.row[M::kSearched] : 0.0;
+    return 0;
+}
+template <class M>
+int icp_time_whole(rgbd360_map* m, const IcpJob& job, const float pose[16], int reps, float& avg_us) {
+    double wall = 0.0;
+    for (int r = 0; r < reps; ++r) {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (const int rc = icp_enqueue<M>(m, job, pose, job.p.max_iters, typename M::Out{})) return rc;
+        HIPC(m, hipStreamSynchronize(m->s->stream));
+        wall += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    }
+    avg_us = (float)(wall / reps);
+    return 0;
+}
+
+struct PointIcp : vmap::PointMethod {
+    using Row = vmap::PointMethod;
+    using Params = rgbd360_map_align_params;
+    using Result = rgbd360_map_align_result;
+    struct Out {
+        int32_t* key3 = nullptr;
+        float* d2 = nullptr;
+    };
+    static int check(rgbd360_map* m, const Params* params, IcpJob& job) { return icp_check_params(m, params, job.p); }
+    static int launch_eval(rgbd360_map* m, const IcpJob& job, const vmap::Params& P, int final_pass, const Out& o) {
+        const float max_dist2 = job.p.max_dist * job.p.max_dist;
+        with_choice<0, 1>(job.cloud, [&](auto S) {
+            hipLaunchKernelGGL((vmap::k_vmap_icp_eval<decltype(S)::value>), job.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.src,
+                               (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, max_dist2,
+                               (const IcpState<PointIcp>*)icp_state<PointIcp>(m), final_pass, m->a_part.get(), o.key3, o.d2);
+        });
+        HIPC(m, hipGetLastError());
+        return 0;
+    }
+    static void fill_extra(const IcpState<PointIcp>&, Result*) {}
+};
 }  // namespace
 
 extern "C" void rgbd360_map_default_align_params(const rgbd360_map* m, rgbd360_map_align_params* p) {
@@ -449,14 +535,14 @@ extern "C" int rgbd360_map_align_sphere(rgbd360_map* m, const void* depth, size_
     const int chk = vmap_check_sphere(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, guess);
     if (chk < 0) return chk;
     // (an empty image: a cloud of no points)
-    return icp_align(m, chk == 1 ? nullptr : depth, depth_step, depth_type, rows, cols, convention, nullptr, 0, guess, on_device, params, pose_out, result);
+    return icp_align<PointIcp>(m, chk == 1 ? nullptr : depth, depth_step, depth_type, rows, cols, convention, nullptr, 0, guess, on_device, params, pose_out, result);
 }
 
 extern "C" int rgbd360_map_align_cloud(rgbd360_map* m, const float* xyz, long long n, const float guess[16], int on_device,
                                        const rgbd360_map_align_params* params, float pose_out[16], rgbd360_map_align_result* result) {
     if (!m) return -1;
     m->err.clear();
-    return icp_align(m, nullptr, 0, 0, 0, 0, 0, xyz, n, guess, on_device, params, pose_out, result);
+    return icp_align<PointIcp>(m, nullptr, 0, 0, 0, 0, 0, xyz, n, guess, on_device, params, pose_out, result);
 }
 
 // measurement and tests (rgbd360_hip_diag.h)
@@ -469,25 +555,7 @@ extern "C" int rgbd360_map_align_eval(rgbd360_map* m, const void* depth, size_t 
     if (n_trace) *n_trace = (int)m->a_trace.size();
     for (int k = 0; trace && k < max_trace && k < (int)m->a_trace.size(); ++k) trace[k] = m->a_trace[k];
     if (!pose) return 0;
-    IcpJob job;
-    if (const int rc = icp_check_params(m, params, job.p)) return rc;
-    if (depth) {
-        const int chk = vmap_check_sphere(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, pose);
-        if (chk < 0) return chk;
-        if (chk == 1) depth = nullptr, n = 0;
-    }
-    for (int k = 0; k < vmap::kIcpSums && sums; ++k) sums[k] = 0.0;
-    for (int k = 0; k < 3 && counters; ++k) counters[k] = 0;
-    job.p.max_iters = 0;
-    const int prep = icp_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job);
-    if (prep < 0) return prep;
-    if (prep == 1) return 0;
-    if (const int rc = icp_enqueue(m, job, pose, 0, key3_dev, d2_dev)) return rc;
-    HIPC(m, hipStreamSynchronize(m->s->stream));
-    const vmap::IcpState& st = *reinterpret_cast<const vmap::IcpState*>(m->a_host.get());
-    for (int k = 0; k < vmap::kIcpSums && sums; ++k) sums[k] = st.row[k];
-    for (int k = 0; k < 3 && counters; ++k) counters[k] = (long long)st.row[17 + k];
-    return 0;
+    return icp_eval<PointIcp>(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, pose, on_device, params, sums, counters, {key3_dev, d2_dev});
 }
 
 extern "C" int rgbd360_map_time_align(rgbd360_map* m, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
@@ -498,59 +566,32 @@ extern "C" int rgbd360_map_time_align(rgbd360_map* m, const void* depth_dev, siz
     if (chk < 0) return chk;
     if (chk == 1 || reps < 1 || !avg_us) return vmap_fail(m, -1, "bad arguments");
     IcpJob job;
-    if (const int rc = icp_check_params(m, params, job.p)) return rc;
+    if (const int rc = PointIcp::check(m, params, job)) return rc;
     const int prep = icp_prepare(m, depth_dev, depth_step, depth_type, rows, cols, convention, nullptr, 0, 1, job);
     if (prep != 0) return prep;
     const size_t drow = (size_t)cols * (depth_type == 0 ? 2 : 4);
     HIPC(m, m->up_depth.ensure(drow * rows));
     hipStream_t stream = m->s->stream;
     const vmap::Params P = vmap_params(m, pose);
-    hipEvent_t e0 = nullptr, e1 = nullptr;       // made last, destroyed on every path below
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        if (e0) hipEventDestroy(e0);
-        (void)hipGetLastError();
-        return vmap_fail(m, -103, "hipEventCreate failed");
-    }
-    int rc = 0;
-    auto timed = [&](float& out, int count, auto&& body) {
-        float ms = 0.f;
-        if (rc != 0) return;
-        if (hipEventRecord(e0, stream) != hipSuccess) rc = vmap_fail(m, -100, "hipEventRecord failed");
-        for (int r = 0; r < count && rc == 0; ++r) rc = body();
-        if (rc == 0 && (hipEventRecord(e1, stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-            rc = vmap_fail(m, -100, "timing the kernels failed");
-        out = ms * 1000.f / (float)count;
-    };
-    rc = icp_launch_init(m, pose);
-    if (rc == 0) rc = icp_launch_eval(m, job, P, 1, nullptr, nullptr);      // once untimed: code and tables loaded
-    timed(avg_us[0], reps, [&] { return icp_launch_eval(m, job, P, 1, nullptr, nullptr); });
-    timed(avg_us[1], reps, [&] { return icp_launch_solve(m, job, 1); });
-    if (rc == 0 && probes) {
-        vmap::IcpState st;
-        if (hipMemcpy(&st, m->a_state, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) rc = vmap_fail(m, -100, "reading the state failed");
-        *probes = st.row[21] > 0.0 ? st.row[20] / st.row[21] : 0.0;
-    }
-    timed(avg_us[2], 1, [&] { return vmap_launch_insert(m, P, job.src, false); });
+    VmapTimer timer(m, stream);      // made last
+    if (timer.rc) return timer.rc;
+    int& rc = timer.rc;
+    rc = icp_launch_init<PointIcp>(m, pose);
+    if (rc == 0) rc = PointIcp::launch_eval(m, job, P, 1, {});      // once untimed: code and tables loaded
+    timer.timed(avg_us[0], reps, [&] { return PointIcp::launch_eval(m, job, P, 1, {}); });
+    timer.timed(avg_us[1], reps, [&] { return icp_launch_solve<PointIcp>(m, job, 1); });
+    if (rc == 0 && probes) rc = icp_read_probes<PointIcp>(m, probes);
+    timer.timed(avg_us[2], 1, [&] { return vmap_launch_insert(m, P, job.src, false); });
     if (rc == 0) {
         rgbd360_map_stats stats;
         rc = std::min(vmap_finish_insert(m, &stats), 0);
     }
-    timed(avg_us[3], reps, [&] {
+    timer.timed(avg_us[3], reps, [&] {
         return hipMemcpy2DAsync(m->up_depth, drow, depth_dev, depth_step, drow, rows, hipMemcpyDeviceToDevice, stream) == hipSuccess ? 0 : -100;
     });
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
     if (rc) {
         (void)hipGetLastError();
         return rc;
     }
-    double wall = 0.0;
-    for (int r = 0; r < reps; ++r) {
-        const auto t0 = std::chrono::steady_clock::now();
-        if (const int rc2 = icp_enqueue(m, job, pose, job.p.max_iters, nullptr, nullptr)) return rc2;
-        HIPC(m, hipStreamSynchronize(stream));
-        wall += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    }
-    avg_us[4] = (float)(wall / reps);
-    return 0;
+    return icp_time_whole<PointIcp>(m, job, pose, reps, avg_us[4]);
 }

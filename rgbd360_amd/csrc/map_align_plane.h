@@ -1,7 +1,8 @@
 // map_align_plane.h -- point-to-plane ICP of a posed sphere frame, or of a cloud, against the resident voxel map: the plane cost the
 // reference's call sites actually use (pcl::GeneralizedIterativeClosestPoint, a plane-to-plane cost: OdometryRGBD360.cpp:98-114, 210-222,
 // RegisterPairRGBD360.cpp:111-118, MethodsRegisterRGBD360.cpp:294-320) with the map as its target.  Part of the Frame360 translation unit,
-// behind map_align.h, whose lookup (vmap::find, icp_cell), host machinery (icp_prepare, icp_enqueue_loop) and trace it shares.
+// behind map_align.h, which holds what the methods share: the lookup (vmap::find, icp_cell), the loop's state and kernels, the host
+// driver and the trace.  Here: the plane fit, the evaluation kernel, the row's description (PlaneMethod) and the host's (PlaneIcp).
 //
 // Definition (include/rgbd360_hip.h, "point-to-plane ICP of a frame against the map"; tests/map_align_plane_reference.py
 // restates it in numpy).  Per source point at the current pose:
@@ -20,7 +21,7 @@
 //   k_vmap_plane_eval   the shape of k_vmap_icp_eval (256 threads, four points per thread one after another through one row
 //                       accumulator, all 27 first probes in flight before any is looked at, the table read-only); the nine support sums
 //                       ride in the candidate loop, the plane fit runs once per kept point with enough support.
-//   k_vmap_plane_solve  one workgroup, the structure of k_vmap_icp_solve.
+//   k_vmap_icp_solve<PlaneMethod>  map_align.h's solve kernel on this row.
 #pragma once
 
 namespace vmap {
@@ -31,13 +32,6 @@ constexpr int kPlaneWords = 37;
 enum { kPlN = 0, kPlH = 1, kPlG = 22, kPlRR = 28, kPlEE = 29, kPlValid = 30, kPlBox = 31, kPlRange = 32, kPlUnsupported = 33, kPlNonplanar = 34,
        kPlProbes = 35, kPlSearched = 36 };
 enum { kClassNone = 0, kClassKept = 1, kClassUnsupported = 2, kClassNonplanar = 3 };
-
-struct PlaneState {
-    float pose[16];
-    int done, status, iterations, converged;
-    double row[kPlaneWords];         // the totals of the last evaluation that was summed
-    float H[36], g[6];
-};
 
 // The plane of a support: a = the upper triangle (00, 01, 02, 11, 12, 22) of the covariance C.  n: the unit eigenvector of the smallest
 // eigenvalue l0; true iff the support is planar.  Float64 with + - x / sqrt only, every operation rounded on its own: the host, the device
@@ -86,21 +80,12 @@ __host__ __device__ inline bool plane_fit(const double a[6], double max_flatness
     return l1 > 0.0 && l <= max_flatness * l1;
 }
 
-__global__ void k_vmap_plane_init(PlaneState* __restrict__ st, IcpPose guess) {
-    const int t = threadIdx.x;
-    if (t < 16) st->pose[t] = guess.m[t];
-    if (t < kPlaneWords) st->row[t] = 0.0;
-    if (t < 36) st->H[t] = 0.f;
-    if (t < 6) st->g[t] = 0.f;
-    if (t == 0) st->done = st->status = st->iterations = st->converged = 0;
-}
-
 // per-point outputs (tests; any may be null): key3 / d2_out as in k_vmap_icp_eval (the key of the kept MATCH whatever the point's class),
 // nr_out four doubles per point (the normal and r; zeros unless the class is kept), class_out one byte per point
 template <int SRC>
 __global__ __launch_bounds__(kThreads) void k_vmap_plane_eval(Params P, Source src, const unsigned long long* __restrict__ table, unsigned long long mask,
                                                               unsigned long long min_count, float max_dist2, unsigned min_support, double max_flatness,
-                                                              const PlaneState* __restrict__ st, int final_pass, double* __restrict__ part,
+                                                              const LoopState<kPlaneWords>* __restrict__ st, int final_pass, double* __restrict__ part,
                                                               int32_t* __restrict__ key3, float* __restrict__ d2_out, double* __restrict__ nr_out,
                                                               uint8_t* __restrict__ class_out) {
 #pragma clang fp contract(off)
@@ -305,161 +290,56 @@ __host__ __device__ inline void plane_assemble(const double* s, float* H, float*
     for (int k = 0; k < 6; ++k) g[k] = (float)s[kPlG + k];
 }
 
-__global__ __launch_bounds__(64) void k_vmap_plane_solve(PlaneState* __restrict__ st, rgbd360_map_align_trace* __restrict__ trace, const double* __restrict__ part,
-                                                         int n_rows, int final_pass, long long min_matches, float eps) {
-#pragma clang fp contract(off)
-    if (!final_pass && st->done) return;
-    __shared__ double s_row[kPlaneWords];
-    const int t = threadIdx.x;
-    if (t < kPlaneWords) {       // the rows in ascending order
-        double s = 0.0;
-        for (int r = 0; r < n_rows; ++r) s += part[(size_t)r * kPlaneWords + t];
-        s_row[t] = s;
-        st->row[t] = s;
-    }
-    __syncthreads();
-    if (t != 0) return;
-    const long long n = (long long)s_row[kPlN];
-    if (final_pass) {
-        plane_assemble(s_row, st->H, st->g);
-        if (st->status == RGBD360_OK && n < min_matches) st->status = RGBD360_NO_VALID_PIXELS;
-        st->done = 1;
-        return;
-    }
-    if (n < min_matches) {
-        st->status = RGBD360_NO_VALID_PIXELS;
-        st->done = 1;
-        return;
-    }
-    float H[36], g[6], pose[16], pose_new[16], u[6];
-    plane_assemble(s_row, H, g);
-    for (int k = 0; k < 16; ++k) pose[k] = st->pose[k];
-    if (gn::step(H, g, 0.f, pose, pose_new, u) != 0) {
-        st->status = RGBD360_ILL_POSED;
-        st->done = 1;
-        return;
-    }
-    for (int k = 0; k < 16; ++k) st->pose[k] = pose_new[k];
-    rgbd360_map_align_trace rec;
-    rec.n = n;
-    rec.sum_sq = s_row[kPlRR];
-    for (int k = 0; k < 6; ++k) rec.update[k] = u[k];
-    trace[st->iterations] = rec;
-    st->iterations += 1;
-    const float vv = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2], ww = (u[3] * u[3] + u[4] * u[4]) + u[5] * u[5];
-    if (vv <= eps && ww <= eps) {
-        st->converged = 1;
-        st->done = 1;
-    }
-}
+struct PlaneMethod {
+    static constexpr int kWords = kPlaneWords, kN = kPlN, kSumSq = kPlRR, kCounters = kPlValid, kProbes = kPlProbes, kSearched = kPlSearched;
+    __host__ __device__ static void assemble(const double* s, float* H, float* g) { plane_assemble(s, H, g); }
+};
+static_assert(kPlaneWords <= kIcpMaxWords, "the buffers of a map hold the widest row");
 
 }  // namespace vmap
 
 namespace {
 
-struct PlaneJob {
-    IcpJob icp;                  // the source, the grid and the five fields the two methods share
-    int min_support;
-    float max_flatness;
-};
-
-int plane_check_params(rgbd360_map* m, const rgbd360_map_align_plane_params* params, PlaneJob& job) {
-    rgbd360_map_align_plane_params p;
-    if (params) p = *params;
-    else rgbd360_map_default_align_plane_params(m, &p);
-    const rgbd360_map_align_params shared = {p.max_dist, p.max_iters, p.eps, p.min_count, p.min_matches};
-    if (const int rc = icp_check_params(m, &shared, job.icp.p)) return rc;
-    if (p.min_support < 1 || p.min_support > 27) return vmap_fail(m, -1, "min_support must lie in 1 .. 27");
-    if (!(p.max_flatness >= 0.f)) return vmap_fail(m, -1, "max_flatness must not be negative");
-    job.min_support = p.min_support;
-    job.max_flatness = p.max_flatness;
-    return 0;
-}
-int plane_prepare(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
-                  int on_device, PlaneJob& job) {
-    return icp_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job.icp, vmap::kPlaneWords, sizeof(vmap::PlaneState));
-}
-vmap::PlaneState* plane_state(rgbd360_map* m) { return reinterpret_cast<vmap::PlaneState*>(m->a_state.get()); }
-rgbd360_map_align_trace* plane_trace(rgbd360_map* m) {
-    return reinterpret_cast<rgbd360_map_align_trace*>(m->a_state.get() + sizeof(vmap::PlaneState));
-}
-
-int plane_launch_init(rgbd360_map* m, const float pose[16]) {
-    vmap::IcpPose g;
-    memcpy(g.m, pose, sizeof(g.m));
-    hipLaunchKernelGGL(vmap::k_vmap_plane_init, dim3(1), dim3(64), 0, m->s->stream, plane_state(m), g);
-    HIPC(m, hipGetLastError());
-    return 0;
-}
-int plane_launch_eval(rgbd360_map* m, const PlaneJob& job, const vmap::Params& P, int final_pass, int32_t* key3, float* d2, double* nr, uint8_t* cls) {
-    const float max_dist2 = job.icp.p.max_dist * job.icp.p.max_dist;
-    with_choice<0, 1>(job.icp.cloud, [&](auto S) {
-        hipLaunchKernelGGL((vmap::k_vmap_plane_eval<decltype(S)::value>), job.icp.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.icp.src,
-                           (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.icp.p.min_count, max_dist2,
-                           (unsigned)job.min_support, (double)job.max_flatness, (const vmap::PlaneState*)plane_state(m), final_pass, m->a_part.get(), key3,
-                           d2, nr, cls);
-    });
-    HIPC(m, hipGetLastError());
-    return 0;
-}
-int plane_launch_solve(rgbd360_map* m, const PlaneJob& job, int final_pass) {
-    hipLaunchKernelGGL(vmap::k_vmap_plane_solve, dim3(1), dim3(64), 0, m->s->stream, plane_state(m), plane_trace(m), (const double*)m->a_part.get(),
-                       job.icp.n_rows, final_pass, job.icp.p.min_matches, job.icp.p.eps);
-    HIPC(m, hipGetLastError());
-    return 0;
-}
-int plane_enqueue(rgbd360_map* m, const PlaneJob& job, const float guess[16], int iters, int32_t* key3, float* d2, double* nr, uint8_t* cls) {
-    const vmap::Params P = vmap_params(m, guess);
-    return icp_enqueue_loop(
-        m, iters, sizeof(vmap::PlaneState), [&] { return plane_launch_init(m, guess); },
-        [&](int final_pass) {
-            return final_pass ? plane_launch_eval(m, job, P, 1, key3, d2, nr, cls) : plane_launch_eval(m, job, P, 0, nullptr, nullptr, nullptr, nullptr);
-        },
-        [&](int final_pass) { return plane_launch_solve(m, job, final_pass); });
-}
-void plane_fill_result(const vmap::PlaneState& st, rgbd360_map_align_plane_result* res) {
-    if (!res) return;
-    const double n = st.row[vmap::kPlN];
-    res->status = st.status;
-    res->iterations = st.iterations;
-    res->converged = st.converged;
-    res->n_valid = (long long)st.row[vmap::kPlValid];
-    res->n_box_rejected = (long long)st.row[vmap::kPlBox];
-    res->n_out_of_range = (long long)st.row[vmap::kPlRange];
-    res->n_matched = (long long)n;
-    res->fitness = n > 0.0 ? st.row[vmap::kPlRR] / n : 0.0;
-    memcpy(res->hessian, st.H, sizeof(res->hessian));
-    memcpy(res->gradient, st.g, sizeof(res->gradient));
-    res->n_unsupported = (long long)st.row[vmap::kPlUnsupported];
-    res->n_nonplanar = (long long)st.row[vmap::kPlNonplanar];
-    res->fitness_point = n > 0.0 ? st.row[vmap::kPlEE] / n : 0.0;
-}
-int plane_align(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
-                const float guess[16], int on_device, const rgbd360_map_align_plane_params* params, float pose_out[16],
-                rgbd360_map_align_plane_result* result) {
-    PlaneJob job;
-    if (const int rc = plane_check_params(m, params, job)) return rc;
-    if (!guess || !pose_out) return vmap_fail(m, -1, "guess and pose_out must not be null");
-    const int prep = plane_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job);
-    if (prep < 0) return prep;
-    m->a_trace.clear();
-    if (prep == 1) {             // nothing to align
-        memcpy(pose_out, guess, 16 * sizeof(float));
-        if (result) {
-            memset(result, 0, sizeof(*result));
-            result->status = RGBD360_NO_VALID_PIXELS;
-        }
-        return RGBD360_NO_VALID_PIXELS;
+struct PlaneIcp : vmap::PlaneMethod {
+    using Row = vmap::PlaneMethod;
+    using Params = rgbd360_map_align_plane_params;
+    using Result = rgbd360_map_align_plane_result;
+    struct Out {                 // (the key of the kept MATCH whatever the point's class)
+        int32_t* key3 = nullptr;
+        float* d2 = nullptr;
+        double* normal_r = nullptr;
+        uint8_t* cls = nullptr;
+    };
+    static int check(rgbd360_map* m, const Params* params, IcpJob& job) {
+        Params p;
+        if (params) p = *params;
+        else rgbd360_map_default_align_plane_params(m, &p);
+        const rgbd360_map_align_params shared = {p.max_dist, p.max_iters, p.eps, p.min_count, p.min_matches};
+        if (const int rc = icp_check_params(m, &shared, job.p)) return rc;
+        if (p.min_support < 1 || p.min_support > 27) return vmap_fail(m, -1, "min_support must lie in 1 .. 27");
+        if (!(p.max_flatness >= 0.f)) return vmap_fail(m, -1, "max_flatness must not be negative");
+        job.min_support = p.min_support;
+        job.max_flatness = p.max_flatness;
+        return 0;
     }
-    if (const int rc = plane_enqueue(m, job, guess, job.icp.p.max_iters, nullptr, nullptr, nullptr, nullptr)) return rc;
-    HIPC(m, hipStreamSynchronize(m->s->stream));
-    const vmap::PlaneState& st = *reinterpret_cast<const vmap::PlaneState*>(m->a_host.get());
-    const rgbd360_map_align_trace* tr = reinterpret_cast<const rgbd360_map_align_trace*>(m->a_host.get() + sizeof(vmap::PlaneState));
-    m->a_trace.assign(tr, tr + st.iterations);
-    memcpy(pose_out, st.pose, 16 * sizeof(float));
-    plane_fill_result(st, result);
-    return st.status;
-}
+    static int launch_eval(rgbd360_map* m, const IcpJob& job, const vmap::Params& P, int final_pass, const Out& o) {
+        const float max_dist2 = job.p.max_dist * job.p.max_dist;
+        with_choice<0, 1>(job.cloud, [&](auto S) {
+            hipLaunchKernelGGL((vmap::k_vmap_plane_eval<decltype(S)::value>), job.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.src,
+                               (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, max_dist2,
+                               (unsigned)job.min_support, (double)job.max_flatness, (const IcpState<PlaneIcp>*)icp_state<PlaneIcp>(m), final_pass,
+                               m->a_part.get(), o.key3, o.d2, o.normal_r, o.cls);
+        });
+        HIPC(m, hipGetLastError());
+        return 0;
+    }
+    static void fill_extra(const IcpState<PlaneIcp>& st, Result* res) {
+        const double n = st.row[vmap::kPlN];
+        res->n_unsupported = (long long)st.row[vmap::kPlUnsupported];
+        res->n_nonplanar = (long long)st.row[vmap::kPlNonplanar];
+        res->fitness_point = n > 0.0 ? st.row[vmap::kPlEE] / n : 0.0;
+    }
+};
 }  // namespace
 
 extern "C" void rgbd360_map_default_align_plane_params(const rgbd360_map* m, rgbd360_map_align_plane_params* p) {
@@ -483,14 +363,14 @@ extern "C" int rgbd360_map_align_plane_sphere(rgbd360_map* m, const void* depth,
     const int chk = vmap_check_sphere(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, guess);
     if (chk < 0) return chk;
     // (an empty image: a cloud of no points)
-    return plane_align(m, chk == 1 ? nullptr : depth, depth_step, depth_type, rows, cols, convention, nullptr, 0, guess, on_device, params, pose_out, result);
+    return icp_align<PlaneIcp>(m, chk == 1 ? nullptr : depth, depth_step, depth_type, rows, cols, convention, nullptr, 0, guess, on_device, params, pose_out, result);
 }
 
 extern "C" int rgbd360_map_align_plane_cloud(rgbd360_map* m, const float* xyz, long long n, const float guess[16], int on_device,
                                              const rgbd360_map_align_plane_params* params, float pose_out[16], rgbd360_map_align_plane_result* result) {
     if (!m) return -1;
     m->err.clear();
-    return plane_align(m, nullptr, 0, 0, 0, 0, 0, xyz, n, guess, on_device, params, pose_out, result);
+    return icp_align<PlaneIcp>(m, nullptr, 0, 0, 0, 0, 0, xyz, n, guess, on_device, params, pose_out, result);
 }
 
 // measurement and tests (rgbd360_hip_diag.h)
@@ -509,25 +389,8 @@ extern "C" int rgbd360_map_align_plane_eval(rgbd360_map* m, const void* depth, s
     if (!m) return -1;
     m->err.clear();
     if (!pose) return vmap_fail(m, -1, "pose must not be null");
-    PlaneJob job;
-    if (const int rc = plane_check_params(m, params, job)) return rc;
-    if (depth) {
-        const int chk = vmap_check_sphere(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, pose);
-        if (chk < 0) return chk;
-        if (chk == 1) depth = nullptr, n = 0;
-    }
-    for (int k = 0; k < vmap::kPlValid && row; ++k) row[k] = 0.0;
-    for (int k = 0; k < 5 && counters; ++k) counters[k] = 0;
-    job.icp.p.max_iters = 0;
-    const int prep = plane_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job);
-    if (prep < 0) return prep;
-    if (prep == 1) return 0;
-    if (const int rc = plane_enqueue(m, job, pose, 0, key3_dev, d2_dev, normal_r_dev, class_dev)) return rc;
-    HIPC(m, hipStreamSynchronize(m->s->stream));
-    const vmap::PlaneState& st = *reinterpret_cast<const vmap::PlaneState*>(m->a_host.get());
-    for (int k = 0; k < vmap::kPlValid && row; ++k) row[k] = st.row[k];
-    for (int k = 0; k < 5 && counters; ++k) counters[k] = (long long)st.row[vmap::kPlValid + k];
-    return 0;
+    return icp_eval<PlaneIcp>(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, pose, on_device, params, row, counters,
+                              {key3_dev, d2_dev, normal_r_dev, class_dev});
 }
 
 extern "C" int rgbd360_map_time_align_plane(rgbd360_map* m, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
@@ -537,55 +400,26 @@ extern "C" int rgbd360_map_time_align_plane(rgbd360_map* m, const void* depth_de
     const int chk = vmap_check_sphere(m, nullptr, 0, depth_dev, depth_step, depth_type, rows, cols, convention, pose);
     if (chk < 0) return chk;
     if (chk == 1 || reps < 1 || !avg_us) return vmap_fail(m, -1, "bad arguments");
-    PlaneJob job;
-    if (const int rc = plane_check_params(m, params, job)) return rc;
-    // (the wider row and the larger state serve the point-to-point launches below as well)
-    const int prep = plane_prepare(m, depth_dev, depth_step, depth_type, rows, cols, convention, nullptr, 0, 1, job);
+    IcpJob job;
+    if (const int rc = PlaneIcp::check(m, params, job)) return rc;
+    const int prep = icp_prepare(m, depth_dev, depth_step, depth_type, rows, cols, convention, nullptr, 0, 1, job);
     if (prep != 0) return prep;
-    hipStream_t stream = m->s->stream;
     const vmap::Params P = vmap_params(m, pose);
-    hipEvent_t e0 = nullptr, e1 = nullptr;       // made last, destroyed on every path below
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        if (e0) hipEventDestroy(e0);
-        (void)hipGetLastError();
-        return vmap_fail(m, -103, "hipEventCreate failed");
-    }
-    int rc = 0;
-    auto timed = [&](float& out, int count, auto&& body) {
-        float ms = 0.f;
-        if (rc != 0) return;
-        if (hipEventRecord(e0, stream) != hipSuccess) rc = vmap_fail(m, -100, "hipEventRecord failed");
-        for (int r = 0; r < count && rc == 0; ++r) rc = body();
-        if (rc == 0 && (hipEventRecord(e1, stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-            rc = vmap_fail(m, -100, "timing the kernels failed");
-        out = ms * 1000.f / (float)count;
-    };
+    VmapTimer timer(m, m->s->stream);        // made last
+    if (timer.rc) return timer.rc;
+    int& rc = timer.rc;
     // the point-to-point kernel first, on the same frame, map and buffers, then the plane kernels, whose state stays behind
-    rc = icp_launch_init(m, pose);
-    if (rc == 0) rc = icp_launch_eval(m, job.icp, P, 1, nullptr, nullptr);      // once untimed: code and tables loaded
-    timed(avg_us[1], reps, [&] { return icp_launch_eval(m, job.icp, P, 1, nullptr, nullptr); });
-    if (rc == 0) rc = plane_launch_init(m, pose);
-    if (rc == 0) rc = plane_launch_eval(m, job, P, 1, nullptr, nullptr, nullptr, nullptr);
-    timed(avg_us[0], reps, [&] { return plane_launch_eval(m, job, P, 1, nullptr, nullptr, nullptr, nullptr); });
-    timed(avg_us[2], reps, [&] { return plane_launch_solve(m, job, 1); });
-    if (rc == 0 && probes) {
-        vmap::PlaneState st;
-        if (hipMemcpy(&st, m->a_state, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) rc = vmap_fail(m, -100, "reading the state failed");
-        *probes = st.row[vmap::kPlSearched] > 0.0 ? st.row[vmap::kPlProbes] / st.row[vmap::kPlSearched] : 0.0;
-    }
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
+    rc = icp_launch_init<PointIcp>(m, pose);
+    if (rc == 0) rc = PointIcp::launch_eval(m, job, P, 1, {});      // once untimed: code and tables loaded
+    timer.timed(avg_us[1], reps, [&] { return PointIcp::launch_eval(m, job, P, 1, {}); });
+    if (rc == 0) rc = icp_launch_init<PlaneIcp>(m, pose);
+    if (rc == 0) rc = PlaneIcp::launch_eval(m, job, P, 1, {});
+    timer.timed(avg_us[0], reps, [&] { return PlaneIcp::launch_eval(m, job, P, 1, {}); });
+    timer.timed(avg_us[2], reps, [&] { return icp_launch_solve<PlaneIcp>(m, job, 1); });
+    if (rc == 0 && probes) rc = icp_read_probes<PlaneIcp>(m, probes);
     if (rc) {
         (void)hipGetLastError();
         return rc;
     }
-    double wall = 0.0;
-    for (int r = 0; r < reps; ++r) {
-        const auto t0 = std::chrono::steady_clock::now();
-        if (const int rc2 = plane_enqueue(m, job, pose, job.icp.p.max_iters, nullptr, nullptr, nullptr, nullptr)) return rc2;
-        HIPC(m, hipStreamSynchronize(stream));
-        wall += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    }
-    avg_us[3] = (float)(wall / reps);
-    return 0;
+    return icp_time_whole<PlaneIcp>(m, job, pose, reps, avg_us[3]);
 }

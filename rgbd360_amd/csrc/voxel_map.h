@@ -331,6 +331,37 @@ int vmap_fail(rgbd360_map* m, int code, const char* msg) {
     m->err = msg;
     return code;
 }
+// Two events around work on a stream (the rgbd360_map_time_* entries).  rc: the first failure, of the timer or of a body; once it is set
+// nothing more is recorded or run.  The events go with the timer.
+struct VmapTimer {
+    rgbd360_map* m;
+    hipStream_t stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = 0;
+    VmapTimer(rgbd360_map* m_, hipStream_t stream_) : m(m_), stream(stream_) {
+        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+            (void)hipGetLastError();
+            rc = vmap_fail(m, -103, "hipEventCreate failed");
+        }
+    }
+    VmapTimer(const VmapTimer&) = delete;
+    VmapTimer& operator=(const VmapTimer&) = delete;
+    ~VmapTimer() {
+        if (e0) hipEventDestroy(e0);
+        if (e1) hipEventDestroy(e1);
+    }
+    // out: microseconds per call of `count` calls of body() (0: fine) between the two events
+    template <class Body>
+    void timed(float& out, int count, Body&& body) {
+        float ms = 0.f;
+        if (rc != 0) return;
+        if (hipEventRecord(e0, stream) != hipSuccess) rc = vmap_fail(m, -100, "hipEventRecord failed");
+        for (int r = 0; r < count && rc == 0; ++r) rc = body();
+        if (rc == 0 && (hipEventRecord(e1, stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+            rc = vmap_fail(m, -100, "timing the kernels failed");
+        out = ms * 1000.f / (float)count;
+    }
+};
 int vmap_clear_dev(rgbd360_map* m) {
     const unsigned long long words = m->n_slots * vmap::kFields;
     hipLaunchKernelGGL(vmap::k_vmap_clear, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, m->s->stream, m->table, words);
@@ -598,23 +629,14 @@ extern "C" int rgbd360_map_time_kernels(rgbd360_map* m, const uint8_t* rgb_dev, 
     const size_t drow = (size_t)cols * (depth_type == 0 ? 2 : 4), crow = rgb_dev ? (size_t)cols * 3 : 0;
     HIPC(m, m->up_depth.ensure(drow * rows));
     if (crow) HIPC(m, m->up_rgb.ensure(crow * rows));
-    hipEvent_t e0 = nullptr, e1 = nullptr;       // made last, destroyed on every path below
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        if (e0) hipEventDestroy(e0);
-        (void)hipGetLastError();
-        return vmap_fail(m, -103, "hipEventCreate failed");
-    }
+    VmapTimer timer(m, ctx->stream);         // made last
+    if (timer.rc) return timer.rc;
     double sum[5] = {0, 0, 0, 0, 0};
-    int rc = 0;
+    int& rc = timer.rc;
     auto timed = [&](int which, auto&& body) {
-        float ms = 0.f;
-        if (rc != 0) return;         // nothing is recorded around a stream that has already failed
-        if (hipEventRecord(e0, ctx->stream) != hipSuccess) rc = vmap_fail(m, -100, "hipEventRecord failed");
-        if (rc == 0) rc = body();
-        if (rc == 0 && (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                        hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-            rc = vmap_fail(m, -100, "timing the kernels failed");
-        sum[which] += (double)ms * 1000.0;
+        float us = 0.f;
+        timer.timed(us, 1, body);
+        sum[which] += (double)us;
     };
     rgbd360_map_stats st;
     for (int r = 0; r < reps && rc == 0; ++r) {
@@ -643,8 +665,6 @@ extern "C" int rgbd360_map_time_kernels(rgbd360_map* m, const uint8_t* rgb_dev, 
             return 0;
         });
     }
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
     if (rc) {
         (void)hipGetLastError();
         return rc;
