@@ -4,7 +4,7 @@
 //     frame_%03d.rgb  (H*W*3 uint8)   frame_%03d.depth (H*W uint16 mm)
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/odometry_replay.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o odometry_replay
-// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane]]
+// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane] [--render-map PREFIX]]
 //         --sequence: all frames are loaded first and the frame loop runs inside the library (alignSequence)
 //         --multi N:  the same sequence sharded over N GPUs of this node from this one process (rgbd360_multi_*: one host thread
 //                     per device, contiguous shards of pairs, one ncclAllGather of the solved poses over xGMI); prints the
@@ -24,6 +24,10 @@
 //         --refine-on-map-plane: the same with the point-to-plane form (GlobalMap::alignSpherePlane: the plane cost of the GICP those call
 //                     sites use); prints one "refine-plane" line per frame with the contributing points, the unsupported and nonplanar
 //                     ones and both fitness values.  Takes precedence over --refine-on-map.
+//         --render-map PREFIX: (needs --map) after the replay the map is rendered as a spherical frame of the input's size at the last
+//                     pose (GlobalMap::renderSphere: the reference's viewer.globalMap, OdometryRGBD360.cpp:242-268, as a panorama) and
+//                     written as PREFIX_rgb.ppm (P6) and PREFIX_depth.pfm (Pf, metres, 0 in holes, rows bottom to top); prints one
+//                     "render" line with the counters.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -162,14 +166,19 @@ int main(int argc, char** argv) {
         return 0;
     }
     const bool use_pbmap = argc > 5 && std::string(argv[5]) == "--pbmap";
-    std::string map_file;
+    std::string map_file, render_prefix;
     float leaf = 0.05f;
     bool refine_on_map = false, refine_on_map_plane = false;
     for (int a = 5; a < argc; ++a) {
         if (a + 1 < argc && std::string(argv[a]) == "--map") map_file = argv[a + 1];
         if (a + 1 < argc && std::string(argv[a]) == "--leaf") leaf = (float)atof(argv[a + 1]);
+        if (a + 1 < argc && std::string(argv[a]) == "--render-map") render_prefix = argv[a + 1];
         if (std::string(argv[a]) == "--refine-on-map") refine_on_map = true;
         if (std::string(argv[a]) == "--refine-on-map-plane") refine_on_map_plane = true;
+    }
+    if (!render_prefix.empty() && map_file.empty()) {
+        fprintf(stderr, "--render-map needs --map\n");
+        return 2;
     }
     std::unique_ptr<rgbd360::GlobalMap> globalMap;      // declared behind align360: destroyed before its context
     auto add_to_map = [&](const Frame& f) {                                                      // :242, 266-268
@@ -234,6 +243,24 @@ int main(int argc, char** argv) {
         FILE* f = fopen(map_file.c_str(), "w");
         if (!f) return 6;
         for (const rgbd360::MapPoint& p : globalMap->points()) fprintf(f, "%.6f %.6f %.6f %d %d %d %d\n", p.x, p.y, p.z, p.r, p.g, p.b, p.count);
+        fclose(f);
+    }
+    if (globalMap && !render_prefix.empty()) {
+        std::vector<float> depth;
+        std::vector<uint8_t> rgb;
+        globalMap->renderSphere(h, w, currentPose, depth, rgb);
+        const rgbd360_map_render_stats& st = globalMap->renderStats();
+        printf("render voxels %lld below_min_count %lld near %lld splatted %lld pixels_covered %lld\n", st.n_voxels, st.n_below_min_count, st.n_near,
+               st.n_splatted, st.n_pixels_covered);
+        FILE* f = fopen((render_prefix + "_rgb.ppm").c_str(), "wb");
+        if (!f) return 7;
+        fprintf(f, "P6\n%d %d\n255\n", w, h);
+        fwrite(rgb.data(), 1, rgb.size(), f);
+        fclose(f);
+        f = fopen((render_prefix + "_depth.pfm").c_str(), "wb");
+        if (!f) return 7;
+        fprintf(f, "Pf\n%d %d\n-1.0\n", w, h);            // little-endian floats, the bottom row first
+        for (int r = h - 1; r >= 0; --r) fwrite(depth.data() + (size_t)r * w, sizeof(float), (size_t)w, f);
         fclose(f);
     }
     return 0;

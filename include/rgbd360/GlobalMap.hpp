@@ -15,6 +15,9 @@
 //     globalMap.alignSphere(frame.sphereDepth, guess, pose)     point-to-point, nearest voxel centroid within max_dist <= leaf
 //     globalMap.alignSpherePlane(frame.sphereDepth, guess, pose)   point-to-plane: the same match, the plane fitted to the centroids around it
 //                                                                  (the call sites use pcl::GeneralizedIterativeClosestPoint, a plane cost)
+// The map as a spherical RGB-D frame (rgbd360_map_render_*: the reference shows viewer.globalMap in a PCL window, OdometryRGBD360.cpp:242-268,
+// and aligns against keyframes, OdometryKeyFrame360.cpp): a z-buffered splat of the table into the panorama of the dense alignment,
+//     globalMap.renderSphere(rows, cols, pose, depth, rgb)     whose outputs RegisterPhotoICP::setTargetFrame takes as they are
 #pragma once
 
 #include <stdexcept>
@@ -111,6 +114,28 @@ class GlobalMap {
     }
     const rgbd360_map_align_plane_result& alignPlaneResult() const { return alignPlane_; }      // of the last alignSpherePlane / alignCloudPlane call
 
+    // The map splatted into the full-sphere panorama of rows x cols at `pose` (world <- frame), the nearest voxel winning a pixel
+    // (rgbd360_map_render_sphere; defaults: min_count 1, near = leaf, splat 1.0, max_half 8).  The vectors are resized; depth is float32
+    // metres with 0 in holes, rgb 8UC3, count (may be nullptr) the winner's points with 0 in holes, key3 (may be nullptr) its (i_x, i_y, i_z).
+    // The map is not changed.  renderStats() has the counters of the last call.
+    rgbd360_map_render_params renderParams() const {
+        rgbd360_map_render_params p;
+        rgbd360_map_default_render_params(map_, &p);
+        return p;
+    }
+    void renderSphere(int rows, int cols, const Mat4f& pose, std::vector<float>& depth, std::vector<uint8_t>& rgb, std::vector<int32_t>* count = nullptr,
+                      std::vector<int32_t>* key3 = nullptr, const rgbd360_map_render_params* params = nullptr) {
+        const size_t n = rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0;
+        depth.assign(n, 0.f);
+        rgb.assign(3 * n, 0);
+        if (count) count->assign(n, 0);
+        if (key3) key3->assign(3 * n, 0);
+        check(rgbd360_map_render_sphere(map_, rows, cols, pose.m, params, depth.data(), rgb.data(), count ? count->data() : nullptr,
+                                        key3 ? key3->data() : nullptr, &render_),
+              "rgbd360_map_render_sphere");
+    }
+    const rgbd360_map_render_stats& renderStats() const { return render_; }      // of the last renderSphere call
+
     long long size() const { return rgbd360_map_size(map_); }
     size_t bytes() const { return rgbd360_map_bytes(map_); }
     void clear() { check(rgbd360_map_clear(map_), "rgbd360_map_clear"); }
@@ -144,6 +169,7 @@ class GlobalMap {
     rgbd360_map_stats stats_{};
     rgbd360_map_align_result align_{};
     rgbd360_map_align_plane_result alignPlane_{};
+    rgbd360_map_render_stats render_{};
 };
 
 }  // namespace rgbd360

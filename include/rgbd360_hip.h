@@ -372,6 +372,52 @@ int    rgbd360_map_align_plane_sphere(rgbd360_map* map, const void* depth, size_
 int    rgbd360_map_align_plane_cloud(rgbd360_map* map, const float* xyz, long long n, const float guess[16], int on_device,
                                      const rgbd360_map_align_plane_params* params, float pose_out[16], rgbd360_map_align_plane_result* result);
 
+/* ---- the map rendered as a spherical frame (csrc/map_render.h) -------------------------------------------------------------------
+ * The reference looks at its global map in a PCL window (viewer.globalMap, OdometryRGBD360.cpp:242-268) and aligns new frames against
+ * keyframes (OdometryKeyFrame360.cpp).  Here the map is turned back into what the dense alignment takes: a full-sphere RGB-D panorama
+ * at a pose, a z-buffered splat of the table.  depth and rgb go straight into rgbd360_set_target (depth_type 1) -- frame-to-model
+ * alignment against everything inserted so far -- and the panorama is the map's picture.  The pixel grid is that of rgbd360_set_target
+ * for an image of rows x cols (RPI.h:4567-4582).  pose: 16 floats, column-major, world <- frame, as for every map entry.
+ *   1 inverse pose  formed once on the host: Rinv = R^T, tinv_k = -(R_0k t_x + R_1k t_y + R_2k t_z) evaluated in double from the float32
+ *                   inputs, summed left to right, rounded to float32.  R is taken to be a rotation; this is not checked.
+ *   2 voxel         every occupied voxel with count >= min_count takes part; centroid c_k = (float)((double)S_k / ((double)count *
+ *                   1048576.0)) and colour S_c / count are the read-out's expressions, bit for bit.
+ *   3 projection    the dense alignment's warp in the device arithmetic (the one rgbd360_set_index_arithmetic(ctx, 0) selects, the
+ *                   oracle's math_mode 1) at the pose of step 1 with c as the source point: target row r', column c', d^2 and visibility.
+ *                   dist = the correctly rounded float32 square root of d^2.  A voxel is skipped and counted in n_near when it is not
+ *                   visible, when dist is not finite or when dist < near (default: leaf, which drops the voxel the camera sits in).
+ *   4 footprint     half-width in pixels h = min(max_half, (int)(foot * (1 / dist))), the reciprocal correctly rounded, the product in
+ *                   float32, the cast truncating; foot = (splat * leaf) * angle_res_inv, both products in float32 in that order.  The voxel
+ *                   covers the rows r' - h .. r' + h clipped to [0, rows) and the columns c' - h .. c' + h modulo cols (the panorama is
+ *                   closed in theta); when 2 h + 1 >= cols every column once.  splat = 0 gives single pixels.
+ *   5 visibility    per pixel the voxel of smallest dist wins (positive float32 values compared by their bit patterns); on equal bits
+ *                   the smaller packed key (i_z, i_y, i_x from the top, the table's own key).  A slot index, an arrival order or a thread
+ *                   never decides: the image does not depend on the order of insertion, on the table's capacity or on the run.
+ *   6 outputs       row-major rows x cols, any pointer may be NULL: depth float32 = the winner's dist, 0 where nothing landed; rgb 8UC3
+ *                   tightly packed = the winner's colour; count int32 = the winner's point count (the hole mask: 0 in holes); key3
+ *                   3 x int32 = (i_x, i_y, i_z), 0 in holes.  The statistics are exact integers.
+ * Stated limitations: the depth across a footprint is the centroid's dist (flat-shaded discs); the footprint is a square in pixels and
+ * is not widened towards the poles; silhouettes grow by the footprint; the map holds no surface normals.  Out of scope: anti-aliased
+ * or normal-shaded splats, ray casting through the grid, pinhole views. */
+typedef struct {
+    int   min_count;           /* points a voxel must hold to be drawn: 1 */
+    float near;                /* voxels closer than this are skipped: leaf */
+    float splat;               /* footprint in leaves at unit distance, >= 0: 1.0 */
+    int   max_half;            /* largest footprint half-width in pixels, 0 .. 64: 8 */
+} rgbd360_map_render_params;
+typedef struct { long long n_voxels, n_below_min_count, n_near, n_splatted, n_pixels_covered; } rgbd360_map_render_stats;
+void   rgbd360_map_default_render_params(const rgbd360_map* map, rgbd360_map_render_params* p);
+/* Host outputs; the call waits for them.  0; -1 bad arguments, nothing launched: a NULL pose, rows or cols negative or outside what a
+ * level of the dense alignment accepts (2 x 8 .. < 16 Mpx, both sides < 32768), min_count < 1, max_half outside 0 .. 64, splat or near
+ * negative or not finite.  params NULL: the defaults.  An empty map or rows * cols == 0 returns 0 with zero-filled outputs and
+ * statistics and launches no kernel.  A render never writes the table; the two work planes (12 bytes per pixel) belong to the map. */
+int    rgbd360_map_render_sphere(rgbd360_map* map, int rows, int cols, const float pose[16], const rgbd360_map_render_params* params,
+                                 float* depth, uint8_t* rgb, int32_t* count, int32_t* key3, rgbd360_map_render_stats* stats);
+/* The same into device arrays on the map's device (stats_dev too): enqueued on the context's stream, the call does not wait. */
+int    rgbd360_map_render_sphere_dev(rgbd360_map* map, int rows, int cols, const float pose[16], const rgbd360_map_render_params* params,
+                                     float* depth_dev, uint8_t* rgb_dev, int32_t* count_dev, int32_t* key3_dev,
+                                     rgbd360_map_render_stats* stats_dev);
+
 /* ---- one process, several GPUs (BASELINE.json configs[3]) ---------------------------------------------------
  * The sequence path shards by independent frame pairs: device d gets the contiguous pairs rgbd360_shard_range(n_frames-1, d,
  * n_gpus) and therefore the frames lo..hi (one boundary frame is shared by two neighbours); one host thread per device drives

@@ -125,6 +125,15 @@ int rgbd360_map_plane_fit(const double cov[6], double max_flatness, double norma
 int rgbd360_map_time_align_plane(rgbd360_map* map, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
                                  const float pose[16], const rgbd360_map_align_plane_params* params, int reps, float avg_us[4], double* probes);
 
+/* The render's kernels (rgbd360_map_render_*, rgbd360_hip.h) under HIP events, averages over `reps` back-to-back launches in
+ * microseconds: avg_us[0] k_vmap_render_depth, [1] k_vmap_render_key, [2] k_vmap_render_resolve (all four planes), [3] the whole
+ * rgbd360_map_render_sphere_dev sequence (the clears and the three passes), [4] ONE k_vmap_extract launch (centroids only) over the
+ * same table: the cost of merely scanning it.  form: 0 every lane walks its own voxel's footprint, 1 a wave walks the footprints of
+ * its voxels together (csrc/map_render.h).  stats (may be NULL): those of one render; *atomics (may be NULL): atomicMin operations the
+ * depth pass of one render issued (the key pass issues at most as many).  Outputs go to the map's staging; the map is not changed. */
+int rgbd360_map_time_render(rgbd360_map* map, int rows, int cols, const float pose[16], const rgbd360_map_render_params* params, int form,
+                            int reps, float avg_us[5], rgbd360_map_render_stats* stats, long long* atomics);
+
 /* The same timer with the launches rotating over n_ctx contexts of one device (each with its own copy of a frame pair) on
  * ctxs[0]'s stream: once n_ctx x the level's working set exceeds the 256 MiB Infinity Cache every launch is fed from HBM. */
 int rgbd360_time_eval_kernel_rotating(rgbd360_ctx* const* ctxs, int n_ctx, int level, const float pose[16], int method,

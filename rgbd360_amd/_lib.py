@@ -34,6 +34,7 @@ SYMBOLS = [
     "rgbd360_map_default_align_params", "rgbd360_map_align_sphere", "rgbd360_map_align_cloud", "rgbd360_map_align_eval", "rgbd360_map_time_align",
     "rgbd360_map_default_align_plane_params", "rgbd360_map_align_plane_sphere", "rgbd360_map_align_plane_cloud", "rgbd360_map_align_plane_eval",
     "rgbd360_map_plane_fit", "rgbd360_map_time_align_plane",
+    "rgbd360_map_default_render_params", "rgbd360_map_render_sphere", "rgbd360_map_render_sphere_dev", "rgbd360_map_time_render",
 ]
 
 
@@ -96,6 +97,14 @@ class MapAlignPlaneResult(C.Structure):  # rgbd360_map_align_plane_result
 
 class MapAlignTrace(C.Structure):        # rgbd360_map_align_trace (rgbd360_hip_diag.h)
     _fields_ = [("n", C.c_longlong), ("sum_sq", C.c_double), ("update", C.c_float * 6)]
+
+
+class MapRenderParams(C.Structure):     # rgbd360_map_render_params
+    _fields_ = [("min_count", C.c_int), ("near", C.c_float), ("splat", C.c_float), ("max_half", C.c_int)]
+
+
+class MapRenderStats(C.Structure):      # rgbd360_map_render_stats
+    _fields_ = [(n, C.c_longlong) for n in ("n_voxels", "n_below_min_count", "n_near", "n_splatted", "n_pixels_covered")]
 
 
 class PbmapParams(C.Structure):
@@ -287,5 +296,10 @@ def load() -> C.CDLL:
     L.rgbd360_map_plane_fit.argtypes = [vp, C.c_double, vp, vp]
     L.rgbd360_map_time_align_plane.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, C.POINTER(MapAlignPlaneParams), i32, vp,
                                                C.POINTER(C.c_double)]
+    L.rgbd360_map_default_render_params.argtypes = [vp, C.POINTER(MapRenderParams)]
+    L.rgbd360_map_default_render_params.restype = None
+    L.rgbd360_map_render_sphere.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRenderParams), vp, vp, vp, vp, C.POINTER(MapRenderStats)]
+    L.rgbd360_map_render_sphere_dev.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRenderParams), vp, vp, vp, vp, vp]
+    L.rgbd360_map_time_render.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRenderParams), i32, i32, vp, C.POINTER(MapRenderStats), C.POINTER(ll)]
     _lib = L
     return L

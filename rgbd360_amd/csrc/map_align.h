@@ -54,18 +54,7 @@ struct IcpPose {
     float m[16];
 };
 
-// the slot of `key` from its first probe on (slot, k0 = the key word there), read only; -1: not in the table
-__device__ __forceinline__ long long find(const unsigned long long* __restrict__ table, unsigned long long mask, unsigned long long key, unsigned long long slot,
-                                          unsigned long long k0, unsigned& probes) {
-    const unsigned long long n_probes = mask < kMaxProbes ? mask + 1 : kMaxProbes;
-    for (unsigned long long p = 1;; ++p) {
-        if (k0 == key) return (long long)slot;
-        if (k0 == kEmpty || p >= n_probes) return -1;
-        slot = (slot + 1) & mask;
-        k0 = table[slot * kFields];
-        ++probes;
-    }
-}
+// (the read-only lookup vmap::find: map_table.h)
 
 // cell c of the 27 in the definition's order: 0 the centre, then dz, dy, dx ascending without the centre
 __host__ __device__ inline void icp_cell(int c, int& dx, int& dy, int& dz) {

@@ -1947,6 +1947,7 @@ F360State* rgbd360_ctx_f360(rgbd360_ctx* ctx) {
 }
 void rgbd360_ctx_set_error(rgbd360_ctx* ctx, const char* msg) { ctx->err = msg ? msg : ""; }
 
+#include "map_render.h"
 #include "frame_store.h"
 #include "multi_gpu.h"
 

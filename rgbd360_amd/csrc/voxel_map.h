@@ -47,6 +47,7 @@
 //                   only above about 90 % load -- size the table for twice the voxels expected.
 //   k_vmap_extract  one lane per slot; a wave reserves its output range with one counter add and every lane stores its record.
 #pragma once
+#include "map_table.h"
 
 struct rgbd360_map {
     rgbd360_ctx* ctx = nullptr;
@@ -70,17 +71,19 @@ struct rgbd360_map {
     DevBuf<unsigned char> a_state;
     PinnedBuf<unsigned char> a_host;
     std::vector<rgbd360_map_align_trace> a_trace;
+    // the map rendered as a spherical frame (map_render.h, in the other translation unit through map_table.h): the two work planes, the
+    // counters with their pinned copy, the host entry's outputs on the device
+    DevBuf<uint32_t> r_dist;
+    DevBuf<unsigned long long> r_key, r_stats;
+    PinnedBuf<unsigned long long> r_hstats;
+    DevBuf<uint8_t> r_stage;
 };
 
 namespace vmap {
 
 constexpr int kThreads = 256, kPerThread = 4, kTile = kThreads * kPerThread;
 constexpr int kLdsSlots = 512, kLdsProbes = 16;
-constexpr unsigned long long kMaxProbes = 2048;             // of one key in the HBM table (the head comment: probe bound)
-constexpr int kFields = 8;                                  // 64-bit words per slot: key, count, Sx, Sy, Sz, Sr, Sg, Sb
-constexpr unsigned long long kEmpty = ~0ull;
-constexpr int kBias = 1 << 20;                              // |i_k| <= 4096 / 0.004 * (1 + 2^-23) < 2^20
-constexpr double kFix = 1048576.0;
+// (the slot layout kFields / kEmpty / kBias / kFix, the probe bound kMaxProbes and the hash mix64: map_table.h)
 enum { kStValid, kStBox, kStRange, kStAdded, kStDropped, kStNew, kStUpdates, kStExtract, kStWords };
 
 struct Params {
@@ -99,15 +102,6 @@ struct Source {                  // SRC 0: a sphere image; SRC 1: a cloud of n p
     const float* xyz;
     long long n;
 };
-
-__host__ __device__ inline unsigned long long mix64(unsigned long long k) {      // (the 64-bit finaliser of MurmurHash3)
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return k;
-}
 
 // steps 1-6 of one point: 0 skipped, 1 outside the box, 2 out of range, 3 kept (key, the three fixed-point terms and the posed point w)
 __device__ __forceinline__ int classify(const Params& P, float x, float y, float z, unsigned long long& key, long long f[3], float w[3]) {
@@ -606,6 +600,36 @@ extern "C" long long rgbd360_map_extract(rgbd360_map* m, long long max_out, floa
         if (count) count[o] = h_count[k];
     }
     return m->n_voxels;
+}
+
+// the seam to map_render.h (map_table.h)
+void rgbd360_map_view(const rgbd360_map* m, vmap::RenderView* v) {
+    *v = {m->s->p.device, m->s->stream, m->table.get(), m->n_slots, m->leaf, m->n_voxels, m->r_dist.get(), m->r_key.get(), m->r_stats.get(), m->r_hstats.get(),
+          m->r_stage.get()};
+}
+int rgbd360_map_render_view(rgbd360_map* m, size_t n_pixels, bool stage, vmap::RenderView* v) {
+    hipSetDevice(m->s->p.device);
+    HIPC(m, m->r_dist.ensure(n_pixels));
+    HIPC(m, m->r_key.ensure(n_pixels));
+    HIPC(m, m->r_stats.ensure(vmap::kRnWords));
+    HIPC(m, m->r_hstats.ensure(vmap::kRnWords));
+    if (stage) HIPC(m, m->r_stage.ensure(n_pixels * 23));
+    rgbd360_map_view(m, v);
+    return 0;
+}
+int rgbd360_map_set_error(rgbd360_map* m, int code, const char* msg) { return vmap_fail(m, code, msg); }
+int rgbd360_map_time_extract_scan(rgbd360_map* m, int reps, float* avg_us) {
+    hipSetDevice(m->s->p.device);
+    if (m->x_xyz.ensure(3 * (size_t)m->n_voxels + 3) != hipSuccess) return vmap_fail(m, -103, "out of memory");
+    VmapTimer timer(m, m->s->stream);
+    timer.timed(*avg_us, reps, [&] {     // (with the clear of its counter, as in every extract call)
+        hipMemsetAsync(m->d_stats + vmap::kStExtract, 0, sizeof(unsigned long long), m->s->stream);
+        hipLaunchKernelGGL(vmap::k_vmap_extract, dim3((unsigned)((m->n_slots + 255) / 256)), dim3(256), 0, m->s->stream, m->table, m->n_slots, m->n_voxels,
+                           m->d_stats + vmap::kStExtract, m->x_xyz, (uint8_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+        return 0;
+    });
+    if (timer.rc == 0 && hipGetLastError() != hipSuccess) return vmap_fail(m, -100, "the extract launch failed");
+    return timer.rc;
 }
 
 // measurement (rgbd360_hip_diag.h)

@@ -7,6 +7,7 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
     stats = gmap.insert_sphere(rgb, depth, currentPose, convention=0)
     pose, res = gmap.align_sphere(depth, guess, convention=0)      # point-to-point ICP of a frame against the map (csrc/map_align.h)
     pose, res = gmap.align_sphere_plane(depth, guess, convention=0)    # point-to-plane: planes fitted to the centroids (csrc/map_align_plane.h)
+    depth, rgb, count, key3, stats = gmap.render_sphere(rows, cols, pose)      # the map as a spherical RGB-D frame (csrc/map_render.h)
     xyz, rgb, count, key = gmap.extract()          # sorted by (i_z, i_y, i_x)
 
 Every point has weight one and the sums are integers: the map does not depend on the order of the frames.
@@ -221,6 +222,34 @@ class VoxelMap:
         tr = (_lib.MapAlignTrace * max(n.value, 1))()
         self._check(self._L.rgbd360_map_align_eval(self._handle(), None, 0, 0, 0, 0, 0, None, 0, None, 0, None, None, None, None, None, n.value, None, tr))
         return [(int(t.n), float(t.sum_sq), np.array(t.update, np.float32)) for t in tr[:n.value]]
+
+    # ---- the map as a spherical frame (rgbd360_map_render_sphere: the reference's viewer.globalMap, OdometryRGBD360.cpp:242-268, as a
+    #      panorama; the keyframe target of OdometryKeyFrame360.cpp with the whole map as the model)
+    def render_params(self, min_count=None, near=None, splat=None, max_half=None):
+        """The defaults (min_count 1, near = leaf, splat 1.0, max_half 8) with the given fields replaced."""
+        p = _lib.MapRenderParams()
+        self._L.rgbd360_map_default_render_params(self._handle(), C.byref(p))
+        for name, v in (("min_count", min_count), ("near", near), ("splat", splat), ("max_half", max_half)):
+            if v is not None:
+                setattr(p, name, v)
+        return p
+
+    def render_sphere(self, rows: int, cols: int, pose, **params):
+        """The map splatted into the full-sphere panorama of rows x cols at `pose` (4x4 world <- frame), the nearest voxel winning a
+        pixel.  Returns (depth HxW float32 metres, 0 in holes; rgb HxWx3 uint8; count HxW int32, 0 in holes; key3 HxWx3 int32; the
+        statistics as a dict).  depth and rgb are what RegisterPhotoICP.setTargetFrame takes.  The map is not changed."""
+        rows, cols = int(rows), int(cols)
+        p = self.render_params(**params)
+        g = pose_to_cm(pose)
+        shape = (max(rows, 0), max(cols, 0))
+        depth = np.zeros(shape, np.float32)
+        rgb = np.zeros(shape + (3,), np.uint8)
+        count = np.zeros(shape, np.int32)
+        key3 = np.zeros(shape + (3,), np.int32)
+        st = _lib.MapRenderStats()
+        self._check(self._L.rgbd360_map_render_sphere(self._handle(), rows, cols, _ptr(g), C.byref(p), _ptr(depth), _ptr(rgb), _ptr(count), _ptr(key3),
+                                                      C.byref(st)))
+        return depth, rgb, count, key3, {name: int(getattr(st, name)) for name, _ in _lib.MapRenderStats._fields_}
 
     # ---- read-out
     def __len__(self) -> int:
