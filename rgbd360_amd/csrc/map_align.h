@@ -16,21 +16,22 @@
 // This header also holds what every method of alignment against the map shares with the loop (map_align_plane.h is the second
 // method): the loop's state, init and solve kernels (LoopState<WORDS>, k_vmap_icp_init<WORDS>, k_vmap_icp_solve<Row>) and the host driver
 // (icp_prepare, icp_enqueue<M>, icp_align<M>, icp_eval<M>).  A method is an evaluation kernel, a row description (PointMethod) and a host
-// description (PointIcp).  The evaluation kernels keep their own text of the source load, the 27-cell search and the block epilogue
-// (docs/HISTORY.md, last section: shared forms did not compile to the same code and could not be measured).
+// description (PointIcp).  The evaluation kernels of every method are built from three shared pieces: the source load
+// (vmap::load_points, voxel_map.h, also k_vmap_insert's), the candidate search (vmap::search27 with the method's Support) and the block
+// epilogue (vmap::block_row_sum); a method's own text is its per-point tail.  tests/test_map_align_bits_gpu.py pins their bytes.
 //
-//   k_vmap_icp_eval   the shape of k_vmap_insert: 256 threads, four points per thread 256 apart, all loads of a thread first.  Per point
-//                     the first probe of all 27 cells is loaded before any is looked at (27 independent 8-byte loads in flight); a
-//                     probe sequence goes on with plain loads.  The table is never written.  A wave's 22 doubles (17 sums, three
-//                     counters, the probe and search counts) go through a butterfly of lane exchanges, the four waves through LDS, and
-//                     the workgroup writes one partial row.  The pose comes from the loop's state in device memory; a launch of the
+//   k_vmap_icp_eval   the shape of k_vmap_insert: 256 threads, four points per thread 256 apart, all loads of a thread first
+//                     (load_points).  Per point search27: the first probe of all 27 cells is loaded before any is looked at (27
+//                     independent 8-byte loads in flight); a probe sequence goes on with plain loads.  The table is never written.
+//                     block_row_sum: a wave's 22 doubles (17 sums, three counters, the probe and search counts) go through a butterfly
+//                     of lane exchanges, the four waves through LDS, and the workgroup writes one partial row.  The pose comes from the loop's state in device memory; a launch of the
 //                     loop returns at once when the state says the loop has ended.
 //   k_vmap_icp_solve  one workgroup: the rows added in ascending order (one lane per column), H and g, gn::step, status and the stop
 //                     test, one trace record per applied step, the new pose and the state word.
 //   host              max_iters x (eval, solve), the final eval and its solve, one copy of the state, ONE synchronisation; no host read
 //                     between iterations.
 // Cost: up to 27 dependent-free first probes of 8 bytes per point against random 64-byte slots, plus 32 bytes per occupied candidate;
-// tools/map_align_perf.py measures it.
+// tools/map_align_perf.py measures it (profiles/map_align_perf.txt).
 #pragma once
 #include <chrono>
 
@@ -62,6 +63,100 @@ __host__ __device__ inline void icp_cell(int c, int& dx, int& dy, int& dz) {
     dx = q % 3 - 1;
     dy = q / 3 % 3 - 1;
     dz = q / 9 - 1;
+}
+
+// The candidate search of every method: the 27 cells around the voxel `key` of the posed point w, in icp_cell's order.  The first probe of
+// all 27 is loaded before any is looked at (27 independent 8-byte loads in flight; a cell outside the 21-bit range has no key and costs
+// no probe); then per cell vmap::find, count >= min_count, the read-out's centroid cf, e = w - cf and d2 in float32; the smallest d2 wins,
+// a tie stays with the earlier cell.  A method's Support sees every candidate after that comparison: nothing for point-to-point, the
+// nine support sums for point-to-plane (map_align_plane.h).  This one function is why both methods match the same key with the same d2.
+struct NoSupport {
+    __device__ __forceinline__ void add(const float*, const float*) {}
+};
+template <class Support>
+struct Match {
+    float best = __builtin_inff();           // d2 of the nearest candidate, its key (kEmpty: none) and e = w - its centroid
+    unsigned long long best_key = kEmpty;
+    float be[3] = {0.f, 0.f, 0.f};
+    Support support;
+};
+template <class Support>
+__device__ __forceinline__ Match<Support> search27(const unsigned long long* __restrict__ table, unsigned long long mask, unsigned long long min_count,
+                                                   unsigned long long key, const float w[3], unsigned& n_probes) {
+#pragma clang fp contract(off)
+    Match<Support> mt;
+    const long long ib[3] = {(long long)(key & 0x1fffffull), (long long)((key >> 21) & 0x1fffffull), (long long)(key >> 42)};
+    unsigned long long k0[27];
+#pragma unroll
+    for (int c = 0; c < 27; ++c) {
+        int dx, dy, dz;
+        icp_cell(c, dx, dy, dz);
+        const long long nx = ib[0] + dx, ny = ib[1] + dy, nz = ib[2] + dz;
+        const bool ok = nx >= 0 && nx < (1ll << 21) && ny >= 0 && ny < (1ll << 21) && nz >= 0 && nz < (1ll << 21);
+        k0[c] = ok ? table[(mix64(pack_key(nx, ny, nz)) & mask) * kFields] : kEmpty;
+        n_probes += ok ? 1u : 0u;
+    }
+#pragma unroll
+    for (int c = 0; c < 27; ++c) {
+        if (k0[c] == kEmpty) continue;       // an empty first slot, or no key at all: no candidate
+        int dx, dy, dz;
+        icp_cell(c, dx, dy, dz);
+        const unsigned long long ck = pack_key(ib[0] + dx, ib[1] + dy, ib[2] + dz);
+        const long long slot = find(table, mask, ck, mix64(ck) & mask, k0[c], n_probes);
+        if (slot < 0) continue;
+        const unsigned long long* rec = table + (unsigned long long)slot * kFields;
+        const unsigned long long cnt = rec[1];
+        if (cnt < min_count || cnt == 0) continue;
+        float cf[3], e[3];
+        centroid(rec, cnt, cf);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) e[q] = w[q] - cf[q];
+        const float d2 = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+        if (d2 < mt.best) {
+            mt.best = d2;
+            mt.best_key = ck;
+            mt.be[0] = e[0];
+            mt.be[1] = e[1];
+            mt.be[2] = e[2];
+        }
+        mt.support.add(w, cf);
+    }
+    return mt;
+}
+
+// The epilogue of an evaluation kernel: the thread's row summed over the wave (a butterfly, lane offsets 32 .. 1), the four waves
+// through LDS in ascending order, one partial row per workgroup -- a fixed tree, the same sums from run to run.
+template <int WORDS>
+__device__ __forceinline__ void block_row_sum(double row[WORDS], double (*s_red)[WORDS], double* __restrict__ part_row) {
+#pragma clang fp contract(off)
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < WORDS; ++q) {
+#pragma unroll
+        for (int off = 32; off; off >>= 1) row[q] += __shfl_xor(row[q], off);
+    }
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < WORDS; ++q) s_red[t >> 6][q] = row[q];
+    }
+    __syncthreads();
+    if (t < WORDS) {
+        double s = s_red[0][t];
+        for (int wv = 1; wv < kThreads / 64; ++wv) s += s_red[wv][t];
+        part_row[t] = s;
+    }
+}
+// the workgroup's partial row: a row per tile of an image row (SRC 0), per tile of the cloud (SRC 1)
+template <int SRC>
+__device__ __forceinline__ size_t block_row() {
+    return SRC == 0 ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
+}
+// the per-point key output: the matched voxel's indices, kNoKey x 3 without a kept match
+__device__ __forceinline__ void store_key3(int32_t* __restrict__ key3, unsigned long long best_key, bool kept) {
+    int32_t i3[3];
+    unpack_key3(best_key, i3);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) key3[q] = kept ? i3[q] : kNoKey;
 }
 
 // H (column-major) and g of J = [I | -[w]x] from the 17 sums
@@ -98,43 +193,13 @@ __global__ __launch_bounds__(kThreads) void k_vmap_icp_eval(Params P, Source src
 #pragma clang fp contract(off)
     if (!final_pass && st->done) return;
     __shared__ double s_red[kThreads / 64][kIcpWords];
-    const int t = threadIdx.x;
 #pragma unroll
     for (int k = 0; k < 16; ++k) P.pose[k] = st->pose[k];
 
-    // all loads of the thread first
     float x[kPerThread], y[kPerThread], z[kPerThread];
     bool in[kPerThread];
     long long index[kPerThread];
-    if (SRC == 0) {
-        const int r = blockIdx.y;
-        const uint8_t* drow = (const uint8_t*)src.depth + (size_t)r * src.depth_step;
-        const float sp = src.sin_phi[r], cp = src.cos_phi[r];
-        float d[kPerThread], sth[kPerThread], cth[kPerThread];
-#pragma unroll
-        for (int k = 0; k < kPerThread; ++k) {
-            const int col = blockIdx.x * kTile + t + kThreads * k;
-            in[k] = col < src.cols;
-            const int cc = in[k] ? col : src.cols - 1;
-            index[k] = (long long)r * src.cols + cc;
-            d[k] = src.depth_type == 0 ? 0.001f * (float)((const uint16_t*)drow)[cc] : ((const float*)drow)[cc];
-            sth[k] = src.sin_theta[cc];
-            cth[k] = src.cos_theta[cc];
-        }
-#pragma unroll
-        for (int k = 0; k < kPerThread; ++k) r360::sphere_point(src.convention, d[k], sp, cp, sth[k], cth[k], x[k], y[k], z[k]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < kPerThread; ++k) {
-            const long long i = (long long)blockIdx.x * kTile + t + kThreads * k;
-            in[k] = i < src.n;
-            const size_t ii = in[k] ? (size_t)i : 0;
-            index[k] = (long long)ii;
-            x[k] = src.xyz[3 * ii];
-            y[k] = src.xyz[3 * ii + 1];
-            z[k] = src.xyz[3 * ii + 2];
-        }
-    }
+    load_points<SRC>(src, x, y, z, in, index);
 
     double acc[kIcpWords];
 #pragma unroll
@@ -150,57 +215,16 @@ __global__ __launch_bounds__(kThreads) void k_vmap_icp_eval(Params P, Source src
         acc[17] += cls >= 1 ? 1.0 : 0.0;
         acc[18] += cls == 1 ? 1.0 : 0.0;
         acc[19] += cls == 2 ? 1.0 : 0.0;
-        float best = __builtin_inff();
-        unsigned long long best_key = kEmpty;
-        float be[3] = {0.f, 0.f, 0.f};
+        Match<NoSupport> mt;
         if (cls == 3) {
             acc[21] += 1.0;
-            const long long ib[3] = {(long long)(key & 0x1fffffull), (long long)((key >> 21) & 0x1fffffull), (long long)(key >> 42)};
-            unsigned long long k0[27];
-            // the first probe of every cell, before any is looked at
-#pragma unroll
-            for (int c = 0; c < 27; ++c) {
-                int dx, dy, dz;
-                icp_cell(c, dx, dy, dz);
-                const long long nx = ib[0] + dx, ny = ib[1] + dy, nz = ib[2] + dz;
-                const bool ok = nx >= 0 && nx < (1ll << 21) && ny >= 0 && ny < (1ll << 21) && nz >= 0 && nz < (1ll << 21);
-                const unsigned long long ck = ((unsigned long long)nz << 42) | ((unsigned long long)ny << 21) | (unsigned long long)nx;
-                k0[c] = ok ? table[(mix64(ck) & mask) * kFields] : kEmpty;
-                n_probes += ok ? 1u : 0u;
-            }
-#pragma unroll
-            for (int c = 0; c < 27; ++c) {
-                if (k0[c] == kEmpty) continue;       // an empty first slot, or no key at all: no candidate
-                int dx, dy, dz;
-                icp_cell(c, dx, dy, dz);
-                const unsigned long long ck = ((unsigned long long)(ib[2] + dz) << 42) | ((unsigned long long)(ib[1] + dy) << 21) | (unsigned long long)(ib[0] + dx);
-                const long long slot = find(table, mask, ck, mix64(ck) & mask, k0[c], n_probes);
-                if (slot < 0) continue;
-                const unsigned long long* rec = table + (unsigned long long)slot * kFields;
-                const unsigned long long cnt = rec[1];
-                if (cnt < min_count || cnt == 0) continue;
-                const double den = (double)cnt * kFix;
-                float e[3];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) e[q] = w[q] - (float)((double)(long long)rec[2 + q] / den);
-                const float d2 = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
-                if (d2 < best) {
-                    best = d2;
-                    best_key = ck;
-                    be[0] = e[0];
-                    be[1] = e[1];
-                    be[2] = e[2];
-                }
-            }
+            mt = search27<NoSupport>(table, mask, min_count, key, w, n_probes);
         }
-        const bool kept = best_key != kEmpty && best <= max_dist2;
-        if (key3) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) key3[3 * index[k] + q] = kept ? (int32_t)((best_key >> (21 * q)) & 0x1fffffull) - kBias : kNoKey;
-        }
-        if (d2_out) d2_out[index[k]] = best;
+        const bool kept = mt.best_key != kEmpty && mt.best <= max_dist2;
+        if (key3) store_key3(key3 + 3 * index[k], mt.best_key, kept);
+        if (d2_out) d2_out[index[k]] = mt.best;
         if (kept) {
-            const double wx = w[0], wy = w[1], wz = w[2], ex = be[0], ey = be[1], ez = be[2];
+            const double wx = w[0], wy = w[1], wz = w[2], ex = mt.be[0], ey = mt.be[1], ez = mt.be[2];
             acc[0] += 1.0;
             acc[1] += wx;
             acc[2] += wy;
@@ -222,23 +246,7 @@ __global__ __launch_bounds__(kThreads) void k_vmap_icp_eval(Params P, Source src
     }
     acc[20] = (double)n_probes;
 
-    // wave, then workgroup: a fixed tree, the same sums from run to run
-#pragma unroll
-    for (int q = 0; q < kIcpWords; ++q) {
-#pragma unroll
-        for (int off = 32; off; off >>= 1) acc[q] += __shfl_xor(acc[q], off);
-    }
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < kIcpWords; ++q) s_red[t >> 6][q] = acc[q];
-    }
-    __syncthreads();
-    if (t < kIcpWords) {
-        double s = s_red[0][t];
-        for (int wv = 1; wv < kThreads / 64; ++wv) s += s_red[wv][t];
-        const size_t block = SRC == 0 ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
-        part[block * kIcpWords + t] = s;
-    }
+    block_row_sum<kIcpWords>(acc, s_red, part + block_row<SRC>() * kIcpWords);
 }
 
 // one workgroup: the rows added in ascending order (one lane per column), then lane 0: H and g, gn::step, status and the stop test, one

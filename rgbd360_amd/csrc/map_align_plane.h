@@ -6,7 +6,7 @@
 //
 // Definition (include/rgbd360_hip.h, "point-to-plane ICP of a frame against the map"; tests/map_align_plane_reference.py
 // restates it in numpy).  Per source point at the current pose:
-//   1 candidates and match: steps 1-4 of map_align.h, bit for bit (the same key and d2 per point).
+//   1 candidates and match: steps 1-4 of map_align.h, bit for bit (the same key and d2 per point): both kernels call vmap::search27.
 //   2 support: over ALL m candidates e_j = (double)w - (double)c_j, sum e (3) and sum e e^T (6) in float64 in the cells' order;
 //     e_mean = sum e / m (= w - mu, mu the mean centroid), C = sum e e^T / m - e_mean e_mean^T.  A kept point with m < min_support is
 //     counted in n_unsupported.
@@ -19,8 +19,9 @@
 // The map stores no normals and insertion is unchanged: the plane comes from the centroids the lookup has already loaded.
 //
 //   k_vmap_plane_eval   the shape of k_vmap_icp_eval (256 threads, four points per thread one after another through one row
-//                       accumulator, all 27 first probes in flight before any is looked at, the table read-only); the nine support sums
-//                       ride in the candidate loop, the plane fit runs once per kept point with enough support.
+//                       accumulator, all 27 first probes in flight before any is looked at, the table read-only), built from the same
+//                       load_points, search27 and block_row_sum; the nine support sums ride in the candidate loop as search27's
+//                       PlaneSupport, the plane fit runs once per kept point with enough support.
 //   k_vmap_icp_solve<PlaneMethod>  map_align.h's solve kernel on this row.
 #pragma once
 
@@ -80,6 +81,26 @@ __host__ __device__ inline bool plane_fit(const double a[6], double max_flatness
     return l1 > 0.0 && l <= max_flatness * l1;
 }
 
+// the support of a point (step 2 of the definition): over every candidate of vmap::search27, in the cells' order, the difference in double
+struct PlaneSupport {
+    double se[3] = {0.0, 0.0, 0.0}, see[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    unsigned m = 0;
+    __device__ __forceinline__ void add(const float w[3], const float cf[3]) {
+#pragma clang fp contract(off)
+        const double ex = (double)w[0] - (double)cf[0], ey = (double)w[1] - (double)cf[1], ez = (double)w[2] - (double)cf[2];
+        m += 1u;
+        se[0] += ex;
+        se[1] += ey;
+        se[2] += ez;
+        see[0] += ex * ex;
+        see[1] += ex * ey;
+        see[2] += ex * ez;
+        see[3] += ey * ey;
+        see[4] += ey * ez;
+        see[5] += ez * ez;
+    }
+};
+
 // per-point outputs (tests; any may be null): key3 / d2_out as in k_vmap_icp_eval (the key of the kept MATCH whatever the point's class),
 // nr_out four doubles per point (the normal and r; zeros unless the class is kept), class_out one byte per point
 template <int SRC>
@@ -91,43 +112,13 @@ __global__ __launch_bounds__(kThreads) void k_vmap_plane_eval(Params P, Source s
 #pragma clang fp contract(off)
     if (!final_pass && st->done) return;
     __shared__ double s_red[kThreads / 64][kPlaneWords];
-    const int t = threadIdx.x;
 #pragma unroll
     for (int k = 0; k < 16; ++k) P.pose[k] = st->pose[k];
 
-    // all loads of the thread first
     float x[kPerThread], y[kPerThread], z[kPerThread];
     bool in[kPerThread];
     long long index[kPerThread];
-    if (SRC == 0) {
-        const int r = blockIdx.y;
-        const uint8_t* drow = (const uint8_t*)src.depth + (size_t)r * src.depth_step;
-        const float sp = src.sin_phi[r], cp = src.cos_phi[r];
-        float d[kPerThread], sth[kPerThread], cth[kPerThread];
-#pragma unroll
-        for (int k = 0; k < kPerThread; ++k) {
-            const int col = blockIdx.x * kTile + t + kThreads * k;
-            in[k] = col < src.cols;
-            const int cc = in[k] ? col : src.cols - 1;
-            index[k] = (long long)r * src.cols + cc;
-            d[k] = src.depth_type == 0 ? 0.001f * (float)((const uint16_t*)drow)[cc] : ((const float*)drow)[cc];
-            sth[k] = src.sin_theta[cc];
-            cth[k] = src.cos_theta[cc];
-        }
-#pragma unroll
-        for (int k = 0; k < kPerThread; ++k) r360::sphere_point(src.convention, d[k], sp, cp, sth[k], cth[k], x[k], y[k], z[k]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < kPerThread; ++k) {
-            const long long i = (long long)blockIdx.x * kTile + t + kThreads * k;
-            in[k] = i < src.n;
-            const size_t ii = in[k] ? (size_t)i : 0;
-            index[k] = (long long)ii;
-            x[k] = src.xyz[3 * ii];
-            y[k] = src.xyz[3 * ii + 1];
-            z[k] = src.xyz[3 * ii + 2];
-        }
-    }
+    load_points<SRC>(src, x, y, z, in, index);
 
     double acc[kPlRR + 2];           // n, H (21), g (6), r r, e.e; the counters are integers until the reduction
 #pragma unroll
@@ -144,84 +135,30 @@ __global__ __launch_bounds__(kThreads) void k_vmap_plane_eval(Params P, Source s
         n_valid += cls >= 1 ? 1u : 0u;
         n_box += cls == 1 ? 1u : 0u;
         n_range += cls == 2 ? 1u : 0u;
-        float best = __builtin_inff();
-        unsigned long long best_key = kEmpty;
-        float be[3] = {0.f, 0.f, 0.f};
-        double se[3] = {0.0, 0.0, 0.0}, see[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        unsigned m = 0;
+        Match<PlaneSupport> mt;
         if (cls == 3) {
             n_searched += 1u;
-            const long long ib[3] = {(long long)(key & 0x1fffffull), (long long)((key >> 21) & 0x1fffffull), (long long)(key >> 42)};
-            unsigned long long k0[27];
-            // the first probe of every cell, before any is looked at
-#pragma unroll
-            for (int c = 0; c < 27; ++c) {
-                int dx, dy, dz;
-                icp_cell(c, dx, dy, dz);
-                const long long nx = ib[0] + dx, ny = ib[1] + dy, nz = ib[2] + dz;
-                const bool ok = nx >= 0 && nx < (1ll << 21) && ny >= 0 && ny < (1ll << 21) && nz >= 0 && nz < (1ll << 21);
-                const unsigned long long ck = ((unsigned long long)nz << 42) | ((unsigned long long)ny << 21) | (unsigned long long)nx;
-                k0[c] = ok ? table[(mix64(ck) & mask) * kFields] : kEmpty;
-                n_probes += ok ? 1u : 0u;
-            }
-#pragma unroll
-            for (int c = 0; c < 27; ++c) {
-                if (k0[c] == kEmpty) continue;       // an empty first slot, or no key at all: no candidate
-                int dx, dy, dz;
-                icp_cell(c, dx, dy, dz);
-                const unsigned long long ck = ((unsigned long long)(ib[2] + dz) << 42) | ((unsigned long long)(ib[1] + dy) << 21) | (unsigned long long)(ib[0] + dx);
-                const long long slot = find(table, mask, ck, mix64(ck) & mask, k0[c], n_probes);
-                if (slot < 0) continue;
-                const unsigned long long* rec = table + (unsigned long long)slot * kFields;
-                const unsigned long long cnt = rec[1];
-                if (cnt < min_count || cnt == 0) continue;
-                const double den = (double)cnt * kFix;
-                float cf[3], e[3];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    cf[q] = (float)((double)(long long)rec[2 + q] / den);
-                    e[q] = w[q] - cf[q];
-                }
-                const float d2 = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
-                if (d2 < best) {
-                    best = d2;
-                    best_key = ck;
-                    be[0] = e[0];
-                    be[1] = e[1];
-                    be[2] = e[2];
-                }
-                // the support: every candidate, the difference in double
-                const double ex = (double)w[0] - (double)cf[0], ey = (double)w[1] - (double)cf[1], ez = (double)w[2] - (double)cf[2];
-                m += 1u;
-                se[0] += ex;
-                se[1] += ey;
-                se[2] += ez;
-                see[0] += ex * ex;
-                see[1] += ex * ey;
-                see[2] += ex * ez;
-                see[3] += ey * ey;
-                see[4] += ey * ez;
-                see[5] += ez * ez;
-            }
+            mt = search27<PlaneSupport>(table, mask, min_count, key, w, n_probes);
         }
-        const bool kept = best_key != kEmpty && best <= max_dist2;
+        const bool kept = mt.best_key != kEmpty && mt.best <= max_dist2;
+        const PlaneSupport& sp = mt.support;
         int pclass = kClassNone;
         double nrm[3] = {0.0, 0.0, 0.0}, r = 0.0;
-        if (kept && m < min_support) {
+        if (kept && sp.m < min_support) {
             pclass = kClassUnsupported;
             n_unsupported += 1u;
         } else if (kept) {
-            const double dm = (double)m;
-            const double mx = se[0] / dm, my = se[1] / dm, mz = se[2] / dm;
-            const double cov[6] = {see[0] / dm - mx * mx, see[1] / dm - mx * my, see[2] / dm - mx * mz,
-                                   see[3] / dm - my * my, see[4] / dm - my * mz, see[5] / dm - mz * mz};
+            const double dm = (double)sp.m;
+            const double mx = sp.se[0] / dm, my = sp.se[1] / dm, mz = sp.se[2] / dm;
+            const double cov[6] = {sp.see[0] / dm - mx * mx, sp.see[1] / dm - mx * my, sp.see[2] / dm - mx * mz,
+                                   sp.see[3] / dm - my * my, sp.see[4] / dm - my * mz, sp.see[5] / dm - mz * mz};
             double l0, l1;
             if (plane_fit(cov, max_flatness, nrm, l0, l1)) {
                 pclass = kClassKept;
                 r = (nrm[0] * mx + nrm[1] * my) + nrm[2] * mz;
                 const double wx = w[0], wy = w[1], wz = w[2];
                 const double J[6] = {nrm[0], nrm[1], nrm[2], wy * nrm[2] - wz * nrm[1], wz * nrm[0] - wx * nrm[2], wx * nrm[1] - wy * nrm[0]};
-                const double ex = be[0], ey = be[1], ez = be[2];
+                const double ex = mt.be[0], ey = mt.be[1], ez = mt.be[2];
                 acc[kPlN] += 1.0;
                 int h = kPlH;
 #pragma unroll
@@ -239,11 +176,8 @@ __global__ __launch_bounds__(kThreads) void k_vmap_plane_eval(Params P, Source s
                 nrm[0] = nrm[1] = nrm[2] = 0.0;
             }
         }
-        if (key3) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) key3[3 * index[k] + q] = kept ? (int32_t)((best_key >> (21 * q)) & 0x1fffffull) - kBias : kNoKey;
-        }
-        if (d2_out) d2_out[index[k]] = best;
+        if (key3) store_key3(key3 + 3 * index[k], mt.best_key, kept);
+        if (d2_out) d2_out[index[k]] = mt.best;
         if (nr_out) {
             nr_out[4 * index[k]] = nrm[0];
             nr_out[4 * index[k] + 1] = nrm[1];
@@ -253,7 +187,6 @@ __global__ __launch_bounds__(kThreads) void k_vmap_plane_eval(Params P, Source s
         if (class_out) class_out[index[k]] = (uint8_t)pclass;
     }
 
-    // wave, then workgroup: a fixed tree, the same sums from run to run
     double row[kPlaneWords];
 #pragma unroll
     for (int q = 0; q < kPlRR + 2; ++q) row[q] = acc[q];
@@ -264,22 +197,7 @@ __global__ __launch_bounds__(kThreads) void k_vmap_plane_eval(Params P, Source s
     row[kPlNonplanar] = (double)n_nonplanar;
     row[kPlProbes] = (double)n_probes;
     row[kPlSearched] = (double)n_searched;
-#pragma unroll
-    for (int q = 0; q < kPlaneWords; ++q) {
-#pragma unroll
-        for (int off = 32; off; off >>= 1) row[q] += __shfl_xor(row[q], off);
-    }
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < kPlaneWords; ++q) s_red[t >> 6][q] = row[q];
-    }
-    __syncthreads();
-    if (t < kPlaneWords) {
-        double s = s_red[0][t];
-        for (int wv = 1; wv < kThreads / 64; ++wv) s += s_red[wv][t];
-        const size_t block = SRC == 0 ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
-        part[block * kPlaneWords + t] = s;
-    }
+    block_row_sum<kPlaneWords>(row, s_red, part + block_row<SRC>() * kPlaneWords);
 }
 
 // H (column-major, symmetric) and g from the row

@@ -25,6 +25,20 @@ __host__ __device__ inline unsigned long long mix64(unsigned long long k) {     
     return k;
 }
 
+// a key: the three biased 21-bit indices, i_z, i_y, i_x from the top; and the unbiased indices (i_x, i_y, i_z) back out of it
+__host__ __device__ inline unsigned long long pack_key(unsigned long long ix, unsigned long long iy, unsigned long long iz) { return (iz << 42) | (iy << 21) | ix; }
+__host__ __device__ inline void unpack_key3(unsigned long long key, int32_t out[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = (int32_t)((key >> (21 * k)) & 0x1fffffull) - kBias;
+}
+// the read-out's centroid of the slot `rec`, which holds `count` points
+__device__ __forceinline__ void centroid(const unsigned long long* rec, unsigned long long count, float c[3]) {
+#pragma clang fp contract(off)
+    const double den = (double)count * kFix;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = (float)((double)(long long)rec[2 + k] / den);
+}
+
 // the slot of `key` from its first probe on (slot, k0 = the key word there), read only; -1: not in the table
 __device__ __forceinline__ long long find(const unsigned long long* __restrict__ table, unsigned long long mask, unsigned long long key, unsigned long long slot,
                                           unsigned long long k0, unsigned& probes) {

@@ -31,7 +31,8 @@
 // 64-bit words.  key = the three biased 21-bit indices packed (i_z, i_y, i_x from the top: ascending keys are the order of PCL's
 // idx = i0 + i1 dx + i2 dx dy), ~0 = empty, claimed by compare-and-swap; a key never changes once set and nothing is removed.
 //
-//   k_vmap_insert   one lane per point (four per thread, 256 apart: the shape of k_sphere_cloud_s4).  Neighbouring pixels share
+//   k_vmap_insert   one lane per point (four per thread, 256 apart: the shape of k_sphere_cloud_s4; load_points, which the evaluation
+//                   kernels of map_align.h and map_align_plane.h share).  Neighbouring pixels share
 //                   voxels, so the block first merges its 1024 points in a 512-entry LDS hash (LDS atomics); then one lane per
 //                   occupied LDS entry finds or claims the global slot, and eight lanes per entry add its seven sums over the
 //                   slot's 64 contiguous bytes: one global update per distinct key per workgroup.  (The add phase walks all 512
@@ -117,12 +118,50 @@ __device__ __forceinline__ int classify(const Params& P, float x, float y, float
         i[k] = (unsigned long long)((int)floorf(w[k] * P.inv_leaf) + kBias);
         f[k] = llrint((double)w[k] * kFix);
     }
-    key = (i[2] << 42) | (i[1] << 21) | i[0];
+    key = pack_key(i[0], i[1], i[2]);
     return 3;
 }
 __device__ __forceinline__ int classify(const Params& P, float x, float y, float z, unsigned long long& key, long long f[3]) {
     float w[3];
     return classify(P, x, y, z, key, f, w);
+}
+
+// The source load of a thread: its kPerThread points, kThreads apart in the workgroup's tile, all loads first.  in[k]: slot k holds a point
+// of the source; index[k]: its place in the per-point arrays (a place inside the source where !in[k]: every load is in bounds).
+template <int SRC>
+__device__ __forceinline__ void load_points(const Source& src, float x[kPerThread], float y[kPerThread], float z[kPerThread], bool in[kPerThread],
+                                            long long index[kPerThread]) {
+#pragma clang fp contract(off)
+    const int t = threadIdx.x;
+    if (SRC == 0) {
+        const int r = blockIdx.y;
+        const uint8_t* drow = (const uint8_t*)src.depth + (size_t)r * src.depth_step;
+        const float sp = src.sin_phi[r], cp = src.cos_phi[r];
+        float d[kPerThread], st[kPerThread], ct[kPerThread];
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const int col = blockIdx.x * kTile + t + kThreads * k;
+            in[k] = col < src.cols;
+            const int cc = in[k] ? col : src.cols - 1;
+            index[k] = (long long)r * src.cols + cc;
+            d[k] = src.depth_type == 0 ? 0.001f * (float)((const uint16_t*)drow)[cc] : ((const float*)drow)[cc];
+            st[k] = src.sin_theta[cc];
+            ct[k] = src.cos_theta[cc];
+        }
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) r360::sphere_point(src.convention, d[k], sp, cp, st[k], ct[k], x[k], y[k], z[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const long long i = (long long)blockIdx.x * kTile + t + kThreads * k;
+            in[k] = i < src.n;
+            const size_t ii = in[k] ? (size_t)i : 0;
+            index[k] = (long long)ii;
+            x[k] = src.xyz[3 * ii];
+            y[k] = src.xyz[3 * ii + 1];
+            z[k] = src.xyz[3 * ii + 2];
+        }
+    }
 }
 
 // the slot of `key`, claimed if the key is new; -1: the key is new and no free slot lies within the probe bound
@@ -161,41 +200,18 @@ __global__ __launch_bounds__(kThreads) void k_vmap_insert(Params P, Source src, 
     }
     if (t < kStWords) s_stat[t] = 0;
 
-    // all loads of the thread first
     float x[kPerThread], y[kPerThread], z[kPerThread];
-    unsigned c[kPerThread][3];
     bool in[kPerThread];
-    if (SRC == 0) {
-        const int r = blockIdx.y;
-        const uint8_t* drow = (const uint8_t*)src.depth + (size_t)r * src.depth_step;
-        const uint8_t* crow = src.rgb ? src.rgb + (size_t)r * src.rgb_step : nullptr;
-        const float sp = src.sin_phi[r], cp = src.cos_phi[r];
-        float d[kPerThread], st[kPerThread], ct[kPerThread];
+    long long index[kPerThread];
+    load_points<SRC>(src, x, y, z, in, index);
+    // the colour of each point, by its index: in the cloud (SRC 1), or in the image's row, whose pointer is moved back by the row's first
+    // index (SRC 0; the row step may be longer than 3 * cols)
+    unsigned c[kPerThread][3];
+    const uint8_t* crow = !src.rgb ? nullptr : SRC == 0 ? src.rgb + (size_t)blockIdx.y * src.rgb_step - 3 * (size_t)blockIdx.y * src.cols : src.rgb;
 #pragma unroll
-        for (int k = 0; k < kPerThread; ++k) {
-            const int col = blockIdx.x * kTile + t + kThreads * k;
-            in[k] = col < src.cols;
-            const int cc = in[k] ? col : src.cols - 1;
-            d[k] = src.depth_type == 0 ? 0.001f * (float)((const uint16_t*)drow)[cc] : ((const float*)drow)[cc];
-            st[k] = src.sin_theta[cc];
-            ct[k] = src.cos_theta[cc];
+    for (int k = 0; k < kPerThread; ++k) {
 #pragma unroll
-            for (int q = 0; q < 3; ++q) c[k][q] = crow ? crow[3 * (size_t)cc + q] : 0u;
-        }
-#pragma unroll
-        for (int k = 0; k < kPerThread; ++k) r360::sphere_point(src.convention, d[k], sp, cp, st[k], ct[k], x[k], y[k], z[k]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < kPerThread; ++k) {
-            const long long i = (long long)blockIdx.x * kTile + t + kThreads * k;
-            in[k] = i < src.n;
-            const size_t ii = in[k] ? (size_t)i : 0;
-            x[k] = src.xyz[3 * ii];
-            y[k] = src.xyz[3 * ii + 1];
-            z[k] = src.xyz[3 * ii + 2];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) c[k][q] = src.rgb ? src.rgb[3 * ii + q] : 0u;
-        }
+        for (int q = 0; q < 3; ++q) c[k][q] = crow ? crow[3 * (size_t)index[k] + q] : 0u;
     }
     __syncthreads();
 
@@ -311,10 +327,7 @@ __global__ __launch_bounds__(256) void k_vmap_extract(const unsigned long long* 
         for (int k = 0; k < 3; ++k) rgb3[3 * o + k] = (uint8_t)(rec[5 + k] / n);
     }
     if (count) count[o] = (int32_t)n;
-    if (key3) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) key3[3 * o + k] = (int32_t)((key >> (21 * k)) & 0x1fffffull) - kBias;
-    }
+    if (key3) unpack_key3(key, key3 + 3 * o);
 }
 
 }  // namespace vmap

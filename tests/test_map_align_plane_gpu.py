@@ -182,6 +182,19 @@ def test_ragged_strided_image(hip_lib, hip, reg, frame, world, depth_type):
         check_eval(device_eval(hip_lib, hip, m, world["guess"], depth=depth, min_support=3), ref)
 
 
+def test_a_strip_of_two_tiles_per_row(hip_lib, hip, reg, world):
+    """1100 x 24: a full tile and a ragged second one of 76 columns per row, the smallest shape in which all four point slots of a thread
+    and the second blockIdx.x of the sphere route hold pixels (at 256 and 250 columns only the first slot ever does)."""
+    from rgbd360_amd import synth
+    depth = synth.render(synth.trajectory_pose(0, 7), 1100, 24, 7)[1]
+    cloud = reg.sphere_cloud(depth, 2)
+    with new_map(reg, 0.1) as m:
+        m.insert_sphere(None, depth, world["P"], convention=2)
+        ref = PL.PlaneEvaluation(R.Map([(cloud, None, world["P"])], 0.1), cloud, world["guess"], 0.1, R.DEFAULT_BOX, 0.1)
+        assert ref.n > 1000
+        check_eval(device_eval(hip_lib, hip, m, world["guess"], depth=depth, point_too=True), ref)
+
+
 @pytest.mark.parametrize("convention", [0, 1])
 def test_the_other_conventions(hip_lib, hip, reg, frame, convention):
     cloud = reg.sphere_cloud(frame["depth"], convention)

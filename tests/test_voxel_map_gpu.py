@@ -69,6 +69,25 @@ def test_sphere_frame_equals_the_restatement_and_the_cloud_route(reg, frame, pos
     assert all(a.tobytes() == b.tobytes() for a, b in zip(got, got2))
 
 
+def test_a_strip_of_two_tiles_per_row(reg):
+    """1100 x 24: a full tile and a ragged second one of 76 columns per row, the smallest shape in which all four point slots of a thread
+    and the second blockIdx.x of the sphere route hold pixels (at 256 columns only the first slot ever does)."""
+    from rgbd360_amd import synth
+    rgb, depth = synth.render(synth.trajectory_pose(0, 7), 1100, 24, 7)
+    cloud, colours, pose = reg.sphere_cloud(depth, 2), rgb.reshape(-1, 3), R.general_pose()
+    ref = R.Map([(cloud, colours, pose)], 0.1)
+    assert len(ref) > 200 and ref.count.max() > 4
+    with new_map(reg, 0.1) as m:
+        st = m.insert_sphere(rgb, depth, pose, convention=2)
+        check_stats(st, ref.stats[0])
+        got = m.extract()
+        R.assert_map_equals(got, ref)
+    with new_map(reg, 0.1) as m2:
+        check_stats(m2.insert_cloud(cloud, colours, pose), ref.stats[0])
+        got2 = m2.extract()
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(got, got2))
+
+
 def test_every_point_shares_a_few_voxels(reg, frame):
     """leaf 4 m: every workgroup hits the same few voxels -- on-chip combining and contention on a handful of slots."""
     pose = R.general_pose()
