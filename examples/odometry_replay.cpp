@@ -4,7 +4,7 @@
 //     frame_%03d.rgb  (H*W*3 uint8)   frame_%03d.depth (H*W uint16 mm)
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/odometry_replay.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o odometry_replay
-// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane] [--render-map PREFIX]]
+// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane] [--render-map PREFIX] [--map-window N]]
 //         --sequence: all frames are loaded first and the frame loop runs inside the library (alignSequence)
 //         --multi N:  the same sequence sharded over N GPUs of this node from this one process (rgbd360_multi_*: one host thread
 //                     per device, contiguous shards of pairs, one ncclAllGather of the solved poses over xGMI); prints the
@@ -28,8 +28,15 @@
 //                     pose (GlobalMap::renderSphere: the reference's viewer.globalMap, OdometryRGBD360.cpp:242-268, as a panorama) and
 //                     written as PREFIX_rgb.ppm (P6) and PREFIX_depth.pfm (Pf, metres, 0 in holes, rows bottom to top); prints one
 //                     "render" line with the counters.
+//         --map-window N: (needs --map) a bounded local map, the usual odometry target: the loop keeps the images and poses of the last N
+//                     frames, and when frame k goes in, frame k - N leaves (GlobalMap::remove: the integer sums make that exact).  The
+//                     table is rebuilt (GlobalMap::rehash) when a census shows more tombstones than occupied voxels.  Prints one "window"
+//                     line per inserted frame: the frame, the occupied voxels and tombstones after it, the voxels its removal emptied,
+//                     whether the table was rebuilt, and the pose the frame went in at (16 hexadecimal floats, column-major: exact, so
+//                     that a reader can rebuild the window's map bit for bit).  Without the option the output is what it was.
 #include <cstdio>
 #include <cstdlib>
+#include <deque>
 #include <fstream>
 #include <memory>
 #include <string>
@@ -169,10 +176,12 @@ int main(int argc, char** argv) {
     std::string map_file, render_prefix;
     float leaf = 0.05f;
     bool refine_on_map = false, refine_on_map_plane = false;
+    int map_window = 0;
     for (int a = 5; a < argc; ++a) {
         if (a + 1 < argc && std::string(argv[a]) == "--map") map_file = argv[a + 1];
         if (a + 1 < argc && std::string(argv[a]) == "--leaf") leaf = (float)atof(argv[a + 1]);
         if (a + 1 < argc && std::string(argv[a]) == "--render-map") render_prefix = argv[a + 1];
+        if (a + 1 < argc && std::string(argv[a]) == "--map-window") map_window = atoi(argv[a + 1]);
         if (std::string(argv[a]) == "--refine-on-map") refine_on_map = true;
         if (std::string(argv[a]) == "--refine-on-map-plane") refine_on_map_plane = true;
     }
@@ -180,10 +189,40 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--render-map needs --map\n");
         return 2;
     }
+    if (map_window != 0 && (map_file.empty() || map_window < 0)) {
+        fprintf(stderr, "--map-window needs --map and a positive number of frames\n");
+        return 2;
+    }
     std::unique_ptr<rgbd360::GlobalMap> globalMap;      // declared behind align360: destroyed before its context
+    struct Kept {        // a frame of the window: what its removal needs
+        std::vector<uint8_t> rgb;
+        std::vector<uint16_t> depth;
+        rgbd360::Mat4f pose;
+    };
+    std::deque<Kept> window;
+    int n_inserted = 0;
     auto add_to_map = [&](const Frame& f) {                                                      // :242, 266-268
         if (!globalMap->insert(f.sphereRGB, f.sphereDepth, currentPose, /*convention=*/0))
             fprintf(stderr, "map full: %lld points dropped\n", globalMap->stats().n_dropped_full);
+        const int k = n_inserted++;
+        if (map_window == 0) return;
+        window.push_back({f.rgb, f.depth, currentPose});
+        long long emptied = 0;
+        if ((int)window.size() > map_window) {      // frame k - N leaves as it came
+            const Kept& old = window.front();
+            const rgbd360::ImageView rgb = {old.rgb.data(), f.rows, f.cols, (size_t)f.cols * 3, rgbd360::ImageView::U8C3};
+            const rgbd360::ImageView depth = {old.depth.data(), f.rows, f.cols, (size_t)f.cols * 2, rgbd360::ImageView::U16C1};
+            if (!globalMap->remove(rgb, depth, old.pose, /*convention=*/0))
+                fprintf(stderr, "map mismatch: %lld points missing, %lld refused\n", globalMap->editStats().n_missing, globalMap->editStats().n_underflow);
+            emptied = globalMap->editStats().n_voxels_emptied;
+            window.pop_front();
+        }
+        rgbd360_map_census_counts c = globalMap->census();
+        const bool rebuild = c.n_tombstones > c.n_live;
+        if (rebuild && globalMap->rehash()) c = globalMap->census();
+        printf("window %d live %lld tombstones %lld emptied %lld rehashed %d pose", k, c.n_live, c.n_tombstones, emptied, rebuild ? 1 : 0);
+        for (int q = 0; q < 16; ++q) printf(" %a", currentPose.m[q]);
+        printf("\n");
     };
     rgbd360::RegisterRGBD360 registerer(/*odometry_config=*/true);
     rgbd360::SegmentParams seg;

@@ -18,6 +18,11 @@
 // The map as a spherical RGB-D frame (rgbd360_map_render_*: the reference shows viewer.globalMap in a PCL window, OdometryRGBD360.cpp:242-268,
 // and aligns against keyframes, OdometryKeyFrame360.cpp): a z-buffered splat of the table into the panorama of the dense alignment,
 //     globalMap.renderSphere(rows, cols, pose, depth, rgb)     whose outputs RegisterPhotoICP::setTargetFrame takes as they are
+// Editing (rgbd360_map_remove_* / _move_* / _rehash / _census): the SLAM programs optimise their keyframe poses continuously and redraw the
+// map from them (SphereGraphSLAM.cpp, KFsphere_SLAM.cpp: optimizer.optimizeGraph(), getPoses(Map.vOptimizedPoses)); the sums are integers,
+// so a frame leaves the map exactly as it came,
+//     globalMap.remove(frame.sphereRGB, frame.sphereDepth, pose)            globalMap.move(rgb, depth, oldPose, optimisedPose)
+//     if (c.n_tombstones > c.n_live) globalMap.rehash();      with c = globalMap.census(); rehash(capacity) grows or shrinks the table
 #pragma once
 
 #include <stdexcept>
@@ -60,8 +65,7 @@ class GlobalMap {
     // rgbd360_sphere_cloud: 0 Frame360 (Frame360.h:555-612), 1 Frame360_stereo, 2 RegisterPhotoICP.  Returns false when the table was
     // full and points of new voxels were dropped (stats().n_dropped_full); everything else throws.
     bool insert(const ImageView& rgb, const ImageView& depth, const Mat4f& pose, int convention = 0) {
-        if (depth.type == ImageView::U8C3 || (rgb.data && (rgb.type != ImageView::U8C3 || rgb.rows != depth.rows || rgb.cols != depth.cols)))
-            throw std::runtime_error("GlobalMap::insert: an 8UC3 colour image and a 16UC1 / 32FC1 depth image of one size");
+        checkImages(rgb, depth, "GlobalMap::insert");
         return full(rgbd360_map_insert_sphere(map_, (const uint8_t*)rgb.data, rgb.step, depth.data, depth.step, depth.type == ImageView::U16C1 ? 0 : 1,
                                               depth.rows, depth.cols, convention, pose.m, 0, &stats_),
                     "rgbd360_map_insert_sphere");
@@ -69,6 +73,43 @@ class GlobalMap {
     // Any cloud in its frame's coordinates: xyz[3 n], rgb3[3 n] or nullptr.
     bool insert(const float* xyz, const uint8_t* rgb3, long long n, const Mat4f& pose) {
         return full(rgbd360_map_insert_cloud(map_, xyz, rgb3, n, pose.m, 0, &stats_), "rgbd360_map_insert_cloud");
+    }
+
+    // Undoes insert() of the same arguments (the same box, the same voxel size; that insert must have returned true), bit for bit and whatever
+    // was inserted in between.  Returns false when points were asked to leave that the map does not hold (editStats().n_missing /
+    // n_underflow): its content is then unspecified, clear() it.  Everything else throws.
+    bool remove(const ImageView& rgb, const ImageView& depth, const Mat4f& pose, int convention = 0) {
+        checkImages(rgb, depth, "GlobalMap::remove");
+        return matched(rgbd360_map_remove_sphere(map_, (const uint8_t*)rgb.data, rgb.step, depth.data, depth.step, depth.type == ImageView::U16C1 ? 0 : 1,
+                                                 depth.rows, depth.cols, convention, pose.m, 0, &edit_),
+                       "rgbd360_map_remove_sphere");
+    }
+    bool remove(const float* xyz, const uint8_t* rgb3, long long n, const Mat4f& pose) {
+        return matched(rgbd360_map_remove_cloud(map_, xyz, rgb3, n, pose.m, 0, &edit_), "rgbd360_map_remove_cloud");
+    }
+    // The frame inserted at oldPose moves to newPose (a pose-graph correction): removed and inserted over one upload.  false: a mismatch as
+    // in remove(), or the table was full as in insert() -- editStats() and stats() tell which; the insertion happens either way.
+    bool move(const ImageView& rgb, const ImageView& depth, const Mat4f& oldPose, const Mat4f& newPose, int convention = 0) {
+        checkImages(rgb, depth, "GlobalMap::move");
+        const int rc = rgbd360_map_move_sphere(map_, (const uint8_t*)rgb.data, rgb.step, depth.data, depth.step, depth.type == ImageView::U16C1 ? 0 : 1,
+                                               depth.rows, depth.cols, convention, oldPose.m, newPose.m, 0, &edit_, &stats_);
+        check(rc, "rgbd360_map_move_sphere");
+        return rc == 0;
+    }
+    bool move(const float* xyz, const uint8_t* rgb3, long long n, const Mat4f& oldPose, const Mat4f& newPose) {
+        const int rc = rgbd360_map_move_cloud(map_, xyz, rgb3, n, oldPose.m, newPose.m, 0, &edit_, &stats_);
+        check(rc, "rgbd360_map_move_cloud");
+        return rc == 0;
+    }
+    const rgbd360_map_edit_stats& editStats() const { return edit_; }      // of the last remove / move
+    // The table rebuilt without tombstones into `capacity` voxels (0: its current size): compaction, growing, shrinking.  A second table exists
+    // during the call.  false: a voxel found no slot in the new table and the map is unchanged; a capacity below size() throws.
+    bool rehash(long long capacity = 0) { return full(rgbd360_map_rehash(map_, capacity), "rgbd360_map_rehash"); }
+    // Slots, occupied voxels, tombstones, points and inconsistent slots of a read-only scan of the table.
+    rgbd360_map_census_counts census() const {
+        rgbd360_map_census_counts c{};
+        check(rgbd360_map_census(map_, &c), "rgbd360_map_census");
+        return c;
     }
 
     // Point-to-point ICP of a sphere frame, or of a cloud in its frame's coordinates, against the map from `guess` (rgbd360_map_align_*:
@@ -165,8 +206,17 @@ class GlobalMap {
         check(rc, what);
         return rc != RGBD360_MAP_FULL;
     }
+    bool matched(int rc, const char* what) const {
+        check(rc, what);
+        return rc != RGBD360_MAP_MISMATCH;
+    }
+    static void checkImages(const ImageView& rgb, const ImageView& depth, const char* who) {
+        if (depth.type == ImageView::U8C3 || (rgb.data && (rgb.type != ImageView::U8C3 || rgb.rows != depth.rows || rgb.cols != depth.cols)))
+            throw std::runtime_error(std::string(who) + ": an 8UC3 colour image and a 16UC1 / 32FC1 depth image of one size");
+    }
     rgbd360_map* map_ = nullptr;
     rgbd360_map_stats stats_{};
+    rgbd360_map_edit_stats edit_{};
     rgbd360_map_align_result align_{};
     rgbd360_map_align_plane_result alignPlane_{};
     rgbd360_map_render_stats render_{};

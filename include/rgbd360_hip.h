@@ -41,7 +41,8 @@ enum {
     RGBD360_OK = 0,
     RGBD360_ILL_POSED = 1,      /* rank(H + lambda diag H) != 6, RPI.h:4682-4690: pose_out = last accepted pose */
     RGBD360_NO_VALID_PIXELS = 2, /* the error pass found no residual (the reference would divide by zero) */
-    RGBD360_MAP_FULL = 3        /* rgbd360_map_insert_*: points of new voxels found no free slot (within the probe bound) and were dropped (counted) */
+    RGBD360_MAP_FULL = 3,       /* rgbd360_map_insert_*: points of new voxels found no free slot (within the probe bound) and were dropped (counted) */
+    RGBD360_MAP_MISMATCH = 4    /* rgbd360_map_remove_* / _move_*: points were asked to leave that the map does not hold (counted); its content is then unspecified */
 };
 
 /* Replaces the constructor defaults + setters of RegisterPhotoICP (RPI.h:201-221, 224-269) and the
@@ -214,7 +215,9 @@ int  rgbd360_store_align(rgbd360_store* st, int n_pairs, const int* trg, const i
  * accumulators.  (PCL is not part of the reference tree: parity with pcl::VoxelGrid itself is unpinned, as for the other PCL-backed
  * stages.)
  * A map is destroyed BEFORE its context and used from one thread at a time, like a store.
- * Out of scope: removing points, moving the grid, several GPUs, normals, surfaces. */
+ * A map can be edited (rgbd360_map_remove_* / _move_* / _rehash / _census below): what was inserted can be taken out again, exactly.
+ * Out of scope: removal by region or age without the source data (the map keeps no per-frame provenance), moving the grid, several
+ * GPUs, normals, surfaces. */
 typedef struct rgbd360_map rgbd360_map;
 typedef struct { long long n_valid, n_box_rejected, n_out_of_range, n_added, n_dropped_full, n_voxels; } rgbd360_map_stats;
 /* A map of `leaf` metres (>= 0.004) with room for capacity_voxels voxels (rounded up to a power of two, 64 bytes each) on ctx's
@@ -252,6 +255,53 @@ int    rgbd360_map_clear(rgbd360_map* map);
  * _extract_dev: device arrays, unsorted (which records are written when max_out < size is not defined).  Negative: an error. */
 long long rgbd360_map_extract(rgbd360_map* map, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3);
 long long rgbd360_map_extract_dev(rgbd360_map* map, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3);
+
+/* ---- editing the map: exact removal, re-posing, rehash and census (csrc/map_edit.h) ----------------------------------------------
+ * The reference's SLAM programs optimise their keyframe poses continuously and redraw the map from the corrected poses
+ * (SphereGraphSLAM.cpp, KFsphere_SLAM.cpp: optimizer.optimizeGraph(), getPoses(Map.vOptimizedPoses)); odometry against a local map
+ * needs old frames to leave it.  The sums are integers and steps 1-5 of an insertion are a pure function of (point, box, pose, leaf),
+ * so subtracting the same integer terms undoes an insertion EXACTLY, whatever was inserted in between.
+ * Removal, per point: steps 1-5 of the map's definition above, the same bits; then count -= 1, S_k -= llrint((double)w_k * 1048576.0),
+ * S_c -= colour_c (the colour iff rgb is given, mirroring insert).  The lookup is read-only: removal never claims a slot.  A slot whose
+ * count reaches 0 keeps its key (a tombstone: linear probing needs the run intact); extract, render and both alignments treat it as
+ * absent, rgbd360_map_size does not count it, a later insert of that voxel revives it, rgbd360_map_rehash drops it.
+ * The contract: the caller removes what it inserted -- the same data, pose, convention and box on a map of the same leaf -- and that
+ * insert did not return RGBD360_MAP_FULL (which of its points were dropped is not recorded).  Then the result is exact and does not
+ * depend on the order of points or workgroups: the map is, bit for bit, the map that never saw the removed frame.
+ * Outside the contract the call is still memory-safe and no count ever wraps: points whose voxel is not in the table are counted in
+ * n_missing and nothing is subtracted for them; a voxel asked for more points than it holds gives what it holds (the decrement of the
+ * count word is a compare-and-swap loop clamped to the current count), the rest is refused, counted in n_underflow, and the sums are
+ * left alone: per voxel n_removed = min(held, asked), whatever the order of points and workgroups.  If either counter is non-zero the call returns RGBD360_MAP_MISMATCH with a message: the counts stay
+ * non-negative, but the map's content is then unspecified (sums and counts no longer belong together) and the caller should clear it.
+ * n_removed + n_missing + n_underflow = the points that passed steps 1-4; n_voxels_emptied: voxels whose count reached 0 in this call;
+ * n_voxels: the map's size after it. */
+typedef struct { long long n_valid, n_box_rejected, n_out_of_range, n_removed, n_missing, n_underflow, n_voxels_emptied, n_voxels; } rgbd360_map_edit_stats;
+/* Arguments, refusals and empty inputs as for rgbd360_map_insert_sphere / _cloud.  0, RGBD360_MAP_MISMATCH, or negative. */
+int    rgbd360_map_remove_sphere(rgbd360_map* map, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step,
+                                 int depth_type, int rows, int cols, int convention, const float pose[16], int on_device,
+                                 rgbd360_map_edit_stats* stats);
+int    rgbd360_map_remove_cloud(rgbd360_map* map, const float* xyz, const uint8_t* rgb3, long long n, const float pose[16],
+                                int on_device, rgbd360_map_edit_stats* stats);
+/* Re-posing: the source is removed at pose_old and inserted at pose_new -- one upload of a host source, the removal launch and the
+ * insert launch on the map's stream, one synchronisation.  Returns the worse (larger) of the two statuses.  If the removal reports a
+ * mismatch the insertion is still performed and both statistics are filled: the caller clears the map either way. */
+int    rgbd360_map_move_sphere(rgbd360_map* map, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step,
+                               int depth_type, int rows, int cols, int convention, const float pose_old[16], const float pose_new[16],
+                               int on_device, rgbd360_map_edit_stats* removed, rgbd360_map_stats* inserted);
+int    rgbd360_map_move_cloud(rgbd360_map* map, const float* xyz, const uint8_t* rgb3, long long n, const float pose_old[16],
+                              const float pose_new[16], int on_device, rgbd360_map_edit_stats* removed, rgbd360_map_stats* inserted);
+/* Rebuilds the table without tombstones into capacity_voxels slots (rounded up to a power of two; 0 keeps the current number): the
+ * compaction, and the way to grow or shrink a map.  A second table of 64 bytes x slots exists until the call returns.  0; -1 for a
+ * capacity below the number of occupied voxels or above 2^30 (nothing is allocated); RGBD360_MAP_FULL when a voxel found no slot within
+ * the probe bound of the new table, -103 out of memory: in all three cases the map is unchanged.  Afterwards rgbd360_map_bytes reflects
+ * the new size; extract, render and both alignments give the bits they gave before (none depends on the table's layout). */
+int    rgbd360_map_rehash(rgbd360_map* map, long long capacity_voxels);
+/* A read-only scan of the table: its slots, the occupied voxels (count > 0; = rgbd360_map_size), the tombstones, the points the
+ * occupied voxels hold, and the slots whose words cannot come from insertions and contract-keeping removals: count == 0 with a non-zero
+ * sum, or count > 0 with a colour sum > 255 count or |S_k| >= count * 2^32 (|w| < 4096 in 2^-20 units).  It tells when to rehash
+ * (tombstones against occupied voxels) and whether a removal kept the contract: a voxel that empties must have all-zero sums. */
+typedef struct { long long n_slots, n_live, n_tombstones, n_points, n_inconsistent; } rgbd360_map_census_counts;
+int    rgbd360_map_census(rgbd360_map* map, rgbd360_map_census_counts* out);
 
 /* ---- point-to-point ICP of a frame against the map (csrc/map_align.h) -----------------------------------------------------------
  * The reference's registration programs put a cloud-to-cloud ICP on voxel-filtered clouds next to the dense alignment

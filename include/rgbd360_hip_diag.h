@@ -83,6 +83,17 @@ int rgbd360_map_time_kernels(rgbd360_map* map, const uint8_t* rgb_dev, size_t rg
                              int depth_type, int rows, int cols, int convention, const float pose[16], int reps, float avg_us[5],
                              long long* global_updates);
 
+/* The map's editing kernels (rgbd360_map_remove_* / _move_* / _rehash / _census, rgbd360_hip.h) under HIP events on a sphere frame in
+ * device memory, averages over `reps` rounds in microseconds.  Every round clears the map and inserts the frame twice, so that the
+ * removal empties no voxel: avg_us[0] one k_vmap_insert launch into that map (new voxels counted by their claims, the form of a map
+ * that never had a voxel emptied), [1] the removal kernel over the same map, [2] one k_vmap_insert launch counting revivals (the form
+ * of a map that may hold tombstones: a returning count add per entry), [3] the clear of a second table of the same size and
+ * k_vmap_rehash into it (the tables are not swapped), [4] the census scan, [5] one k_vmap_extract scan (centroids only) over the same
+ * table, [6] a whole move of the frame from `pose` to `pose` out of device memory (both launches and the one wait).  The map holds the
+ * frame twice afterwards. */
+int rgbd360_map_time_edit(rgbd360_map* map, const uint8_t* rgb_dev, size_t rgb_step, const void* depth_dev, size_t depth_step,
+                          int depth_type, int rows, int cols, int convention, const float pose[16], int reps, float avg_us[7]);
+
 /* One evaluation of the map alignment (rgbd360_map_align_*, rgbd360_hip.h: steps 1-5 of its definition) at `pose`, and the trace of
  * the map's last alignment.  depth != NULL: the sphere frame; otherwise the n points xyz.  sums[17]: n, sum w (3), sum w_j w_k (xx, xy,
  * xz, yy, yz, zz), sum e (3), sum w x e (3), sum e.e; counters[3]: n_valid, n_box_rejected, n_out_of_range.  key3_dev / d2_dev (DEVICE

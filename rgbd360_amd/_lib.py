@@ -31,6 +31,8 @@ SYMBOLS = [
     "rgbd360_map_create", "rgbd360_map_destroy", "rgbd360_map_last_error", "rgbd360_map_bytes", "rgbd360_map_set_box",
     "rgbd360_map_insert_sphere", "rgbd360_map_insert_cloud", "rgbd360_map_size", "rgbd360_map_clear", "rgbd360_map_extract",
     "rgbd360_map_extract_dev", "rgbd360_map_time_kernels",
+    "rgbd360_map_remove_sphere", "rgbd360_map_remove_cloud", "rgbd360_map_move_sphere", "rgbd360_map_move_cloud", "rgbd360_map_rehash",
+    "rgbd360_map_census", "rgbd360_map_time_edit",
     "rgbd360_map_default_align_params", "rgbd360_map_align_sphere", "rgbd360_map_align_cloud", "rgbd360_map_align_eval", "rgbd360_map_time_align",
     "rgbd360_map_default_align_plane_params", "rgbd360_map_align_plane_sphere", "rgbd360_map_align_plane_cloud", "rgbd360_map_align_plane_eval",
     "rgbd360_map_plane_fit", "rgbd360_map_time_align_plane",
@@ -75,6 +77,15 @@ class Plane(C.Structure):
 
 class MapStats(C.Structure):       # rgbd360_map_stats
     _fields_ = [(n, C.c_longlong) for n in ("n_valid", "n_box_rejected", "n_out_of_range", "n_added", "n_dropped_full", "n_voxels")]
+
+
+class MapEditStats(C.Structure):   # rgbd360_map_edit_stats
+    _fields_ = [(n, C.c_longlong) for n in ("n_valid", "n_box_rejected", "n_out_of_range", "n_removed", "n_missing", "n_underflow",
+                                            "n_voxels_emptied", "n_voxels")]
+
+
+class MapCensus(C.Structure):      # rgbd360_map_census_counts
+    _fields_ = [(n, C.c_longlong) for n in ("n_slots", "n_live", "n_tombstones", "n_points", "n_inconsistent")]
 
 
 class MapAlignParams(C.Structure):       # rgbd360_map_align_params
@@ -279,6 +290,14 @@ def load() -> C.CDLL:
         f.argtypes = [vp, ll, vp, vp, vp, vp]
         f.restype = ll
     L.rgbd360_map_time_kernels.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, vp, C.POINTER(ll)]
+    L.rgbd360_map_remove_sphere.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, C.POINTER(MapEditStats)]
+    L.rgbd360_map_remove_cloud.argtypes = [vp, vp, vp, ll, f32p, i32, C.POINTER(MapEditStats)]
+    L.rgbd360_map_move_sphere.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, f32p, f32p, i32, C.POINTER(MapEditStats),
+                                          C.POINTER(MapStats)]
+    L.rgbd360_map_move_cloud.argtypes = [vp, vp, vp, ll, f32p, f32p, i32, C.POINTER(MapEditStats), C.POINTER(MapStats)]
+    L.rgbd360_map_rehash.argtypes = [vp, ll]
+    L.rgbd360_map_census.argtypes = [vp, C.POINTER(MapCensus)]
+    L.rgbd360_map_time_edit.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, vp]
     L.rgbd360_map_default_align_params.argtypes = [vp, C.POINTER(MapAlignParams)]
     L.rgbd360_map_default_align_params.restype = None
     L.rgbd360_map_align_sphere.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, C.POINTER(MapAlignParams), f32p, C.POINTER(MapAlignResult)]

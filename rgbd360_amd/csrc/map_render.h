@@ -75,8 +75,8 @@ __device__ __forceinline__ void render_scan(const r360::LevelDev& lv, const r360
     const r360::PoseRT T = r360::load_pose(inv_pose.v);
     const ulonglong2* rec = reinterpret_cast<const ulonglong2*>(A.table + (s < A.n_slots ? s : 0) * kFields);
     const ulonglong2 kc = rec[0];                        // key, count
-    const bool occupied = s < A.n_slots && kc.x != kEmpty;
-    const bool takes = occupied && kc.y >= A.min_count && kc.y != 0;
+    const bool occupied = s < A.n_slots && kc.x != kEmpty && kc.y != 0;      // (count 0: a tombstone of a removal, absent)
+    const bool takes = occupied && kc.y >= A.min_count;
     float c[3] = {0.f, 0.f, 0.f};
     if (takes) {
         const ulonglong2 s01 = rec[1], s2r = rec[2];     // Sx, Sy | Sz, Sr

@@ -1257,6 +1257,7 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
 // the resident voxel-grid global map (rgbd360_map_*)
 // ---------------------------------------------------------------------------------------------------------
 #include "voxel_map.h"
+#include "map_edit.h"
 #include "gn_math.h"
 #include "map_align.h"
 #include "map_align_plane.h"

@@ -29,7 +29,9 @@
 //
 // The table: open addressing with linear probing in HBM, a power of two of 64-byte slots {key, count, Sx, Sy, Sz, Sr, Sg, Sb}, all
 // 64-bit words.  key = the three biased 21-bit indices packed (i_z, i_y, i_x from the top: ascending keys are the order of PCL's
-// idx = i0 + i1 dx + i2 dx dy), ~0 = empty, claimed by compare-and-swap; a key never changes once set and nothing is removed.
+// idx = i0 + i1 dx + i2 dx dy), ~0 = empty, claimed by compare-and-swap; a key never changes once set.  Removal (map_edit.h, DESIGN.md
+// 3.15) subtracts the integer terms an insertion added; a slot whose count reaches 0 keeps its key -- a TOMBSTONE: the probe runs stay
+// intact -- and every reader takes count == 0 as absent; a later insert of that voxel finds the key and revives the slot.
 //
 //   k_vmap_insert   one lane per point (four per thread, 256 apart: the shape of k_sphere_cloud_s4; load_points, which the evaluation
 //                   kernels of map_align.h and map_align_plane.h share).  Neighbouring pixels share
@@ -46,6 +48,12 @@
 //                   kernel running for minutes).  With it a key costs at most 128 KiB of loads.  A linear-probing run of length L at
 //                   load a has probability about exp(-(a - 1 - ln a) L): below 1e-11 at a = 0.85 and L = 2048, so the bound binds
 //                   only above about 90 % load -- size the table for twice the voxels expected.
+//   removal         the same kernel text with MODE = kRemove: the same load, classify and LDS merge; the slot phase looks the key up
+//                   read-only (find: removal never claims) and takes the entry's points off the count word in a compare-and-swap
+//                   loop that refuses to go below zero; the eight-lane phase adds the two's-complement negatives of the six sums.
+//                   MODE = kInsertRevive is the insert of a map that may hold tombstones: a new voxel is then the count add that
+//                   returned 0 (a claim or a revival), not the claim, which costs a returning atomic per entry; a map that never had
+//                   a voxel emptied keeps kInsert, the claim count.
 //   k_vmap_extract  one lane per slot; a wave reserves its output range with one counter add and every lane stores its record.
 #pragma once
 #include "map_table.h"
@@ -57,7 +65,8 @@ struct rgbd360_map {
     unsigned long long n_slots = 0;      // a power of two
     bool has_box = true;
     float lo[3] = {-2.f, -4.f, -4.f}, hi[3] = {1.f, 4.f, 4.f};      // FilterPointCloud.h:66-71
-    long long n_voxels = 0;
+    long long n_voxels = 0;              // slots with count > 0
+    bool may_hold_tombstones = false;    // a removal has emptied a voxel since the last clear / rehash: inserts count revivals (kInsertRevive)
     long long last_updates = 0;          // global updates of the last insert call (measurement)
     std::string err;
     DevBuf<unsigned long long> table, d_stats;
@@ -85,7 +94,11 @@ namespace vmap {
 constexpr int kThreads = 256, kPerThread = 4, kTile = kThreads * kPerThread;
 constexpr int kLdsSlots = 512, kLdsProbes = 16;
 // (the slot layout kFields / kEmpty / kBias / kFix, the probe bound kMaxProbes and the hash mix64: map_table.h)
-enum { kStValid, kStBox, kStRange, kStAdded, kStDropped, kStNew, kStUpdates, kStExtract, kStWords };
+enum { kStValid, kStBox, kStRange, kStAdded, kStDropped, kStNew, kStUpdates, kStExtract, kStUnderflow, kStWords };
+// what k_vmap_insert does with the points.  kRemove reads the counters as: kStAdded points removed, kStDropped points whose key is not in
+// the table (missing), kStNew voxels emptied, kStUnderflow points refused because the count would go below zero
+enum { kInsert, kRemove, kInsertRevive };
+constexpr int kStInsertWords = kStUnderflow;      // the words an insert uses: its clear in front of the kernel stays ONE 64-byte fill
 
 struct Params {
     float pose[16];
@@ -184,7 +197,39 @@ __device__ __forceinline__ long long find_or_claim(unsigned long long* table, un
     return -1;
 }
 
-template <int SRC>
+// removal's slot step for the `n` points of `key`: the slot, its count lowered by n.  -1 and a counter raised: the key is not in the table
+// (n missing), or the slot holds fewer than n points: the decrement is clamped to what is there -- the count never wraps -- the rest is
+// refused (underflow) and the sums of the whole group are left alone.  Clamping, rather than refusing all n, makes the counters what a
+// point-by-point removal gives, min(held, asked) per voxel, however the points are grouped and whichever workgroup comes first.
+__device__ __forceinline__ long long find_and_take(unsigned long long* table, unsigned long long mask, unsigned long long key, unsigned n, unsigned* s_stat) {
+    const unsigned long long first = mix64(key) & mask;
+    unsigned probes = 0;
+    const long long slot = find(table, mask, key, first, table[first * kFields], probes);
+    if (slot < 0) {
+        atomicAdd(&s_stat[kStDropped], n);
+        return -1;
+    }
+    unsigned long long* cp = table + (unsigned long long)slot * kFields + 1;
+    unsigned long long cur = __hip_atomic_load(cp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned take;
+    for (;;) {
+        take = cur < n ? (unsigned)cur : n;
+        if (take == 0) break;
+        const unsigned long long seen = atomicCAS(cp, cur, cur - take);
+        if (seen == cur) break;
+        cur = seen;
+    }
+    if (take && cur == take) atomicAdd(&s_stat[kStNew], 1u);
+    if (take) atomicAdd(&s_stat[kStAdded], take);
+    if (take < n) {
+        atomicAdd(&s_stat[kStUnderflow], n - take);
+        return -1;
+    }
+    atomicAdd(&s_stat[kStUpdates], 1u);
+    return slot;
+}
+
+template <int SRC, int MODE>
 __global__ __launch_bounds__(kThreads) void k_vmap_insert(Params P, Source src, unsigned long long* __restrict__ table, unsigned long long mask,
                                                           unsigned long long* __restrict__ stats) {
     __shared__ unsigned long long s_key[kLdsSlots];
@@ -243,15 +288,27 @@ __global__ __launch_bounds__(kThreads) void k_vmap_insert(Params P, Source src, 
             }
             h = (h + 1) & (kLdsSlots - 1);
         }
-        if (!merged) {       // the block's table is crowded around this key: the point goes to the map on its own
+        if (!merged && MODE == kRemove) {      // (as below, one point)
+            const long long slot = find_and_take(table, mask, key, 1u, s_stat);
+            if (slot >= 0) {
+                unsigned long long* rec = table + (unsigned long long)slot * kFields;
+#pragma unroll
+                for (int q = 0; q < 3; ++q) atomicAdd(rec + 2 + q, 0ull - (unsigned long long)f[q]);
+                if (src.rgb) {
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) atomicAdd(rec + 5 + q, 0ull - (unsigned long long)c[k][q]);
+                }
+            }
+        } else if (!merged) {       // the block's table is crowded around this key: the point goes to the map on its own
             bool claimed = false;
             const long long slot = find_or_claim(table, mask, key, claimed);
-            if (claimed) atomicAdd(&s_stat[kStNew], 1u);
+            if (MODE == kInsert && claimed) atomicAdd(&s_stat[kStNew], 1u);
             if (slot < 0) {
                 atomicAdd(&s_stat[kStDropped], 1u);
             } else {
                 unsigned long long* rec = table + (unsigned long long)slot * kFields;
-                atomicAdd(rec + 1, 1ull);
+                if (MODE == kInsert) atomicAdd(rec + 1, 1ull);
+                else if (atomicAdd(rec + 1, 1ull) == 0) atomicAdd(&s_stat[kStNew], 1u);
 #pragma unroll
                 for (int q = 0; q < 3; ++q) atomicAdd(rec + 2 + q, (unsigned long long)f[q]);
                 if (src.rgb) {
@@ -275,24 +332,33 @@ __global__ __launch_bounds__(kThreads) void k_vmap_insert(Params P, Source src, 
     // one lane per merged entry: its slot in the map
     for (int h = t; h < kLdsSlots; h += kThreads) {
         long long slot = -1;
-        if (s_key[h] != kEmpty) {
+        if (s_key[h] != kEmpty && MODE == kRemove) {
+            slot = find_and_take(table, mask, s_key[h], s_cnt[h], s_stat);
+        } else if (s_key[h] != kEmpty) {
             bool claimed = false;
             slot = find_or_claim(table, mask, s_key[h], claimed);
-            if (claimed) atomicAdd(&s_stat[kStNew], 1u);
+            if (MODE == kInsert && claimed) atomicAdd(&s_stat[kStNew], 1u);
             atomicAdd(&s_stat[slot < 0 ? kStDropped : kStAdded], s_cnt[h]);
             if (slot >= 0) atomicAdd(&s_stat[kStUpdates], 1u);
         }
         s_slot[h] = slot;
     }
     __syncthreads();
-    // eight lanes per entry: lane q adds word q of the slot (word 0 is the key); empty entries are skipped
+    // eight lanes per entry: lane q adds word q of the slot (word 0 is the key); empty entries are skipped.  Removal has taken the count
+    // in the slot phase and adds the negatives of the six sums.
     for (int e = t >> 3; e < kLdsSlots; e += kThreads / 8) {
         const int q = t & 7;
         const long long slot = s_slot[e];
-        if (slot < 0 || q == 0) continue;
+        if (slot < 0 || q == 0 || (MODE == kRemove && q == 1)) continue;
         const unsigned long long v = q == 1 ? (unsigned long long)s_cnt[e] : q <= 4 ? s_sum[q - 2][e] : (unsigned long long)s_rgb[q - 5][e];
-        if (v) atomicAdd(table + (unsigned long long)slot * kFields + q, v);
+        if (!v) continue;
+        unsigned long long* word = table + (unsigned long long)slot * kFields + q;
+        if (MODE == kRemove) atomicAdd(word, 0ull - v);
+        else if (MODE == kInsertRevive && q == 1) {
+            if (atomicAdd(word, v) == 0) atomicAdd(&s_stat[kStNew], 1u);
+        } else atomicAdd(word, v);
     }
+    if (MODE == kInsertRevive) __syncthreads();      // (its new voxels are counted in the phase above)
     if (t < kStWords && s_stat[t]) atomicAdd(stats + t, (unsigned long long)s_stat[t]);
 }
 
@@ -308,15 +374,16 @@ __global__ __launch_bounds__(256) void k_vmap_extract(const unsigned long long* 
     const unsigned long long s = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const unsigned long long* rec = table + (s < n_slots ? s : 0) * kFields;
-    const unsigned long long key = rec[0];
-    const bool occupied = s < n_slots && key != kEmpty;
+    const ulonglong2 kc = *reinterpret_cast<const ulonglong2*>(rec);      // key, count
+    const unsigned long long key = kc.x;
+    const bool occupied = s < n_slots && key != kEmpty && kc.y != 0;      // (count 0: a tombstone)
     const unsigned long long wave = __ballot(occupied);
     unsigned long long base = 0;
     if (lane == 0 && wave) base = atomicAdd(counter, (unsigned long long)__popcll(wave));      // one add per wave
     base = __shfl(base, 0);
     const unsigned long long o = base + (unsigned long long)__popcll(wave & ((1ull << lane) - 1ull));
     if (!occupied || (long long)o >= max_out) return;
-    const unsigned long long n = rec[1];
+    const unsigned long long n = kc.y;
     if (xyz) {
         const double den = (double)n * kFix;
 #pragma unroll
@@ -374,6 +441,7 @@ int vmap_clear_dev(rgbd360_map* m) {
     hipLaunchKernelGGL(vmap::k_vmap_clear, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, m->s->stream, m->table, words);
     HIPC(m, hipGetLastError());
     m->n_voxels = 0;
+    m->may_hold_tombstones = false;
     return 0;
 }
 vmap::Params vmap_params(const rgbd360_map* m, const float pose[16]) {
@@ -396,21 +464,32 @@ void vmap_fill_stats(const rgbd360_map* m, const unsigned long long* w, rgbd360_
     st->n_dropped_full = w ? (long long)w[vmap::kStDropped] : 0;
     st->n_voxels = m->n_voxels;
 }
-// the insert kernel over `src` (device memory), enqueued on the stream; the statistics words are cleared in front of it
-int vmap_launch_insert(rgbd360_map* m, const vmap::Params& P, const vmap::Source& src, bool cloud) {
-    HIPC(m, hipMemsetAsync(m->d_stats, 0, vmap::kStWords * sizeof(unsigned long long), m->s->stream));
+// the insert kernel over `src` (device memory) in `mode` (vmap::kInsert ..), enqueued on the stream; the statistics words are cleared in
+// front of it.  The two-argument form is an insert as the map stands: revivals are counted once a removal has emptied a voxel.
+int vmap_launch(rgbd360_map* m, const vmap::Params& P, const vmap::Source& src, bool cloud, int mode) {
+    HIPC(m, hipMemsetAsync(m->d_stats, 0, (mode == vmap::kRemove ? vmap::kStWords : vmap::kStInsertWords) * sizeof(unsigned long long), m->s->stream));
     const dim3 grid = cloud ? dim3((unsigned)((src.n + vmap::kTile - 1) / vmap::kTile)) : dim3((src.cols + vmap::kTile - 1) / vmap::kTile, src.rows);
     with_choice<0, 1>(cloud, [&](auto S) {
-        hipLaunchKernelGGL((vmap::k_vmap_insert<decltype(S)::value>), grid, dim3(vmap::kThreads), 0, m->s->stream, P, src, m->table, m->n_slots - 1, m->d_stats);
+        with_int<vmap::kInsert, vmap::kInsertRevive>(mode, [&](auto M) {
+            hipLaunchKernelGGL((vmap::k_vmap_insert<decltype(S)::value, decltype(M)::value>), grid, dim3(vmap::kThreads), 0, m->s->stream, P, src, m->table,
+                               m->n_slots - 1, m->d_stats);
+        });
     });
     HIPC(m, hipGetLastError());
     return 0;
 }
+int vmap_launch_insert(rgbd360_map* m, const vmap::Params& P, const vmap::Source& src, bool cloud) {
+    return vmap_launch(m, P, src, cloud, m->may_hold_tombstones ? vmap::kInsertRevive : vmap::kInsert);
+}
 // ... and how an insert call ends: the statistics on the host, the map's size brought up to date
+int vmap_close_insert(rgbd360_map* m, const unsigned long long* w, rgbd360_map_stats* stats);
 int vmap_finish_insert(rgbd360_map* m, rgbd360_map_stats* stats) {
-    HIPC(m, hipMemcpyAsync(m->h_stats, m->d_stats, vmap::kStWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->s->stream));
+    HIPC(m, hipMemcpyAsync(m->h_stats, m->d_stats, vmap::kStInsertWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->s->stream));
     HIPC(m, hipStreamSynchronize(m->s->stream));
-    const unsigned long long* w = m->h_stats;
+    return vmap_close_insert(m, m->h_stats, stats);
+}
+// (the counters `w` of an insert launch are on the host)
+int vmap_close_insert(rgbd360_map* m, const unsigned long long* w, rgbd360_map_stats* stats) {
     m->n_voxels += (long long)w[vmap::kStNew];
     m->last_updates = (long long)w[vmap::kStUpdates];
     vmap_fill_stats(m, w, stats);
@@ -441,6 +520,48 @@ int vmap_sphere_source(rgbd360_map* m, const uint8_t* rgb, size_t rgb_step, cons
     src = {depth, depth_step, rgb, rgb_step, depth_type, rows, cols, convention, tab, tab + cols, tab + 2 * cols, tab + 2 * cols + rows, nullptr, 0};
     return 0;
 }
+// A checked sphere image as the kernels take it: a host image (on_device == 0) goes up first, as packed copies on the map's stream -- the
+// caller's memory is free once the stream has been waited for, which every entry does before it returns
+int vmap_sphere_on_device(rgbd360_map* m, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type, int rows, int cols,
+                          int convention, int on_device, vmap::Source& src) {
+    hipSetDevice(m->s->p.device);
+    if (!on_device) {
+        const size_t drow = (size_t)cols * (depth_type == 0 ? 2 : 4);
+        HIPC(m, m->up_depth.ensure(drow * rows));
+        HIPC(m, hipMemcpy2DAsync(m->up_depth, drow, depth, depth_step, drow, rows, hipMemcpyHostToDevice, m->s->stream));
+        depth = m->up_depth;
+        depth_step = drow;
+        if (rgb) {
+            HIPC(m, m->up_rgb.ensure((size_t)cols * 3 * rows));
+            HIPC(m, hipMemcpy2DAsync(m->up_rgb, (size_t)cols * 3, rgb, rgb_step, (size_t)cols * 3, rows, hipMemcpyHostToDevice, m->s->stream));
+            rgb = m->up_rgb;
+            rgb_step = (size_t)cols * 3;
+        }
+    }
+    return vmap_sphere_source(m, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, src);
+}
+// ... and a cloud of n > 0 points
+int vmap_cloud_on_device(rgbd360_map* m, const float* xyz, const uint8_t* rgb3, long long n, int on_device, vmap::Source& src) {
+    hipSetDevice(m->s->p.device);
+    if (!on_device) {
+        HIPC(m, m->up_depth.ensure((size_t)n * 3 * sizeof(float)));
+        HIPC(m, hipMemcpyAsync(m->up_depth, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, m->s->stream));
+        xyz = reinterpret_cast<const float*>(m->up_depth.get());
+        if (rgb3) {
+            HIPC(m, m->up_rgb.ensure((size_t)n * 3));
+            HIPC(m, hipMemcpyAsync(m->up_rgb, rgb3, (size_t)n * 3, hipMemcpyHostToDevice, m->s->stream));
+            rgb3 = m->up_rgb;
+        }
+    }
+    src = {nullptr, 0, rgb3, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, xyz, n};
+    return 0;
+}
+// what an insert_cloud call checks; 1: no points (nothing to do)
+int vmap_check_cloud(rgbd360_map* m, const float* xyz, long long n, const float* pose) {
+    if (n < 0 || n >= (1ll << 40)) return vmap_fail(m, -1, "bad point count");
+    if (n > 0 && (!xyz || !pose)) return vmap_fail(m, -1, "xyz and pose must not be null");
+    return n == 0 ? 1 : 0;
+}
 }  // namespace
 
 extern "C" int rgbd360_map_create(rgbd360_ctx* ctx_, float leaf, long long capacity_voxels, rgbd360_map** out) {
@@ -458,7 +579,7 @@ extern "C" int rgbd360_map_create(rgbd360_ctx* ctx_, float leaf, long long capac
     m->n_slots = 1;
     while (m->n_slots < (unsigned long long)capacity_voxels) m->n_slots <<= 1;
     if (m->table.ensure(m->n_slots * vmap::kFields) != hipSuccess || m->d_stats.ensure(vmap::kStWords) != hipSuccess ||
-        m->h_stats.ensure(vmap::kStWords) != hipSuccess) {
+        m->h_stats.ensure(2 * vmap::kStWords) != hipSuccess) {      // (twice: a move keeps the counters of both its launches)
         (void)hipGetLastError();
         delete m;
         return fail(ctx, -103, "rgbd360_map_create: out of memory");
@@ -499,22 +620,8 @@ extern "C" int rgbd360_map_insert_sphere(rgbd360_map* m, const uint8_t* rgb, siz
     if (chk < 0) return chk;
     vmap_fill_stats(m, nullptr, stats);
     if (chk == 1) return 0;
-    hipSetDevice(m->s->p.device);
-    if (!on_device) {        // packed copies of the host images; the caller's memory is free when the call returns (vmap_finish_insert waits)
-        const size_t drow = (size_t)cols * (depth_type == 0 ? 2 : 4);
-        HIPC(m, m->up_depth.ensure(drow * rows));
-        HIPC(m, hipMemcpy2DAsync(m->up_depth, drow, depth, depth_step, drow, rows, hipMemcpyHostToDevice, m->s->stream));
-        depth = m->up_depth;
-        depth_step = drow;
-        if (rgb) {
-            HIPC(m, m->up_rgb.ensure((size_t)cols * 3 * rows));
-            HIPC(m, hipMemcpy2DAsync(m->up_rgb, (size_t)cols * 3, rgb, rgb_step, (size_t)cols * 3, rows, hipMemcpyHostToDevice, m->s->stream));
-            rgb = m->up_rgb;
-            rgb_step = (size_t)cols * 3;
-        }
-    }
     vmap::Source src;
-    if (const int rc = vmap_sphere_source(m, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, src)) return rc;
+    if (const int rc = vmap_sphere_on_device(m, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, on_device, src)) return rc;
     if (const int rc = vmap_launch_insert(m, vmap_params(m, pose), src, false)) return rc;
     return vmap_finish_insert(m, stats);
 }
@@ -523,22 +630,12 @@ extern "C" int rgbd360_map_insert_cloud(rgbd360_map* m, const float* xyz, const 
                                         rgbd360_map_stats* stats) {
     if (!m) return -1;
     m->err.clear();
-    if (n < 0 || n >= (1ll << 40)) return vmap_fail(m, -1, "bad point count");
-    if (n > 0 && (!xyz || !pose)) return vmap_fail(m, -1, "xyz and pose must not be null");
+    const int chk = vmap_check_cloud(m, xyz, n, pose);
+    if (chk < 0) return chk;
     vmap_fill_stats(m, nullptr, stats);
-    if (n == 0) return 0;
-    hipSetDevice(m->s->p.device);
-    if (!on_device) {
-        HIPC(m, m->up_depth.ensure((size_t)n * 3 * sizeof(float)));
-        HIPC(m, hipMemcpyAsync(m->up_depth, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, m->s->stream));
-        xyz = reinterpret_cast<const float*>(m->up_depth.get());
-        if (rgb3) {
-            HIPC(m, m->up_rgb.ensure((size_t)n * 3));
-            HIPC(m, hipMemcpyAsync(m->up_rgb, rgb3, (size_t)n * 3, hipMemcpyHostToDevice, m->s->stream));
-            rgb3 = m->up_rgb;
-        }
-    }
-    const vmap::Source src = {nullptr, 0, rgb3, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, xyz, n};
+    if (chk == 1) return 0;
+    vmap::Source src;
+    if (const int rc = vmap_cloud_on_device(m, xyz, rgb3, n, on_device, src)) return rc;
     if (const int rc = vmap_launch_insert(m, vmap_params(m, pose), src, true)) return rc;
     return vmap_finish_insert(m, stats);
 }

@@ -9,8 +9,12 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
     pose, res = gmap.align_sphere_plane(depth, guess, convention=0)    # point-to-plane: planes fitted to the centroids (csrc/map_align_plane.h)
     depth, rgb, count, key3, stats = gmap.render_sphere(rows, cols, pose)      # the map as a spherical RGB-D frame (csrc/map_render.h)
     xyz, rgb, count, key = gmap.extract()          # sorted by (i_z, i_y, i_x)
+    gmap.remove_sphere(rgb, depth, currentPose)    # exactly undoes that insert (csrc/map_edit.h); gmap.mismatch tells of a broken contract
+    gmap.move_sphere(rgb, depth, currentPose, correctedPose)       # a pose-graph correction: removed at the old pose, inserted at the new
+    c = gmap.census(); gmap.rehash() if c["n_tombstones"] > c["n_live"] else None      # compaction; rehash(capacity) grows or shrinks
 
-Every point has weight one and the sums are integers: the map does not depend on the order of the frames.
+Every point has weight one and the sums are integers: the map does not depend on the order of the frames, and subtracting the same
+integer terms takes a frame out again bit for bit.
 """
 from __future__ import annotations
 
@@ -23,6 +27,7 @@ from . import _lib
 from .register import Rgbd360Error, _ptr, pose_from_cm, pose_to_cm
 
 MAP_FULL = 3      # RGBD360_MAP_FULL
+MAP_MISMATCH = 4  # RGBD360_MAP_MISMATCH
 
 
 class VoxelMap:
@@ -39,6 +44,7 @@ class VoxelMap:
         self._h = h
         self._ctx_value = ctx.value
         self.full = False        # the last insert dropped points of new voxels (RGBD360_MAP_FULL)
+        self.mismatch = False    # the last removal was asked for points the map does not hold (RGBD360_MAP_MISMATCH): clear the map
 
     # ---- lifecycle
     def close(self):
@@ -96,40 +102,107 @@ class VoxelMap:
         self.full = rc == MAP_FULL
         return {name: int(getattr(st, name)) for name, _ in _lib.MapStats._fields_}
 
-    def insert_sphere(self, rgb, depth, pose, convention: int = 0):
-        """rgb: HxWx3 uint8 or None; depth: HxW uint16 millimetres or float32 metres (rows may be strided); pose: 4x4 world <- frame.
-        Returns the call's statistics; self.full tells whether points were dropped."""
+    @staticmethod
+    def _sphere_args(what, rgb, depth, convention):
+        """The image arguments of the sphere entries in front of the pose(s); the arrays they point into come back with them."""
         d = np.asarray(depth)
         if d.dtype not in (np.uint16, np.float32) or d.ndim != 2:
-            raise Rgbd360Error("VoxelMap.insert_sphere: depth must be HxW uint16 millimetres or float32 metres")
+            raise Rgbd360Error(f"VoxelMap.{what}: depth must be HxW uint16 millimetres or float32 metres")
         if d.size and d.strides[1] != d.dtype.itemsize:
             d = np.ascontiguousarray(d)
         c = None
         if rgb is not None:
             c = np.asarray(rgb)
             if c.dtype != np.uint8 or c.shape != d.shape + (3,):
-                raise Rgbd360Error("VoxelMap.insert_sphere: rgb must be HxWx3 uint8 of the depth image's size")
+                raise Rgbd360Error(f"VoxelMap.{what}: rgb must be HxWx3 uint8 of the depth image's size")
             if c.size and c.strides[1:] != (3, 1):
                 c = np.ascontiguousarray(c)
-        p = pose_to_cm(pose)
-        st = _lib.MapStats()
-        rc = self._L.rgbd360_map_insert_sphere(self._handle(), None if c is None else _ptr(c), 0 if c is None else c.strides[0], _ptr(d),
-                                               d.strides[0], 0 if d.dtype == np.uint16 else 1, d.shape[0], d.shape[1], int(convention),
-                                               _ptr(p), 0, C.byref(st))
-        return self._stats(rc, st)
+        return (None if c is None else _ptr(c), 0 if c is None else c.strides[0], _ptr(d), d.strides[0], 0 if d.dtype == np.uint16 else 1, d.shape[0],
+                d.shape[1], int(convention)), (d, c)
 
-    def insert_cloud(self, xyz, rgb3, pose):
-        """xyz: n x 3 float32 in the frame's coordinates; rgb3: n x 3 uint8 or None."""
+    @staticmethod
+    def _cloud_args(what, xyz, rgb3):
         x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
         c = None
         if rgb3 is not None:
             c = np.ascontiguousarray(rgb3, np.uint8).reshape(-1, 3)
             if c.shape != x.shape:
-                raise Rgbd360Error("VoxelMap.insert_cloud: one colour per point")
+                raise Rgbd360Error(f"VoxelMap.{what}: one colour per point")
+        return (_ptr(x), None if c is None else _ptr(c), x.shape[0]), (x, c)
+
+    def insert_sphere(self, rgb, depth, pose, convention: int = 0):
+        """rgb: HxWx3 uint8 or None; depth: HxW uint16 millimetres or float32 metres (rows may be strided); pose: 4x4 world <- frame.
+        Returns the call's statistics; self.full tells whether points were dropped."""
+        args, keep = self._sphere_args("insert_sphere", rgb, depth, convention)
         p = pose_to_cm(pose)
         st = _lib.MapStats()
-        rc = self._L.rgbd360_map_insert_cloud(self._handle(), _ptr(x), None if c is None else _ptr(c), x.shape[0], _ptr(p), 0, C.byref(st))
+        rc = self._L.rgbd360_map_insert_sphere(self._handle(), *args, _ptr(p), 0, C.byref(st))
         return self._stats(rc, st)
+
+    def insert_cloud(self, xyz, rgb3, pose):
+        """xyz: n x 3 float32 in the frame's coordinates; rgb3: n x 3 uint8 or None."""
+        args, keep = self._cloud_args("insert_cloud", xyz, rgb3)
+        p = pose_to_cm(pose)
+        st = _lib.MapStats()
+        rc = self._L.rgbd360_map_insert_cloud(self._handle(), *args, _ptr(p), 0, C.byref(st))
+        return self._stats(rc, st)
+
+    # ---- editing (rgbd360_map_remove_* / _move_* / _rehash / _census, csrc/map_edit.h): what was inserted leaves again, exactly
+    def _edit_stats(self, rc, st):
+        self.last_status = self._check(rc)
+        self.mismatch = rc == MAP_MISMATCH
+        return {name: int(getattr(st, name)) for name, _ in _lib.MapEditStats._fields_}
+
+    def remove_sphere(self, rgb, depth, pose, convention: int = 0):
+        """Undoes insert_sphere of the same arguments (the same box, a map of the same leaf; that insert must not have been `full`), bit
+        for bit and whatever was inserted in between.  Returns the statistics (n_removed, n_missing, n_underflow, n_voxels_emptied,
+        ...); self.mismatch tells that points were asked to leave that the map does not hold: its content is then unspecified."""
+        args, keep = self._sphere_args("remove_sphere", rgb, depth, convention)
+        p = pose_to_cm(pose)
+        st = _lib.MapEditStats()
+        rc = self._L.rgbd360_map_remove_sphere(self._handle(), *args, _ptr(p), 0, C.byref(st))
+        return self._edit_stats(rc, st)
+
+    def remove_cloud(self, xyz, rgb3, pose):
+        """Undoes insert_cloud of the same arguments."""
+        args, keep = self._cloud_args("remove_cloud", xyz, rgb3)
+        p = pose_to_cm(pose)
+        st = _lib.MapEditStats()
+        rc = self._L.rgbd360_map_remove_cloud(self._handle(), *args, _ptr(p), 0, C.byref(st))
+        return self._edit_stats(rc, st)
+
+    def _move_stats(self, rc, est, st):
+        removed = self._edit_stats(rc, est)
+        self.mismatch = est.n_missing != 0 or est.n_underflow != 0
+        self.full = st.n_dropped_full != 0
+        return removed, {name: int(getattr(st, name)) for name, _ in _lib.MapStats._fields_}
+
+    def move_sphere(self, rgb, depth, pose_old, pose_new, convention: int = 0):
+        """The frame inserted at pose_old moves to pose_new: removed and inserted over one upload.  Returns (removal statistics, insert
+        statistics); self.mismatch and self.full as after remove_sphere and insert_sphere (the insertion happens either way)."""
+        args, keep = self._sphere_args("move_sphere", rgb, depth, convention)
+        a, b = pose_to_cm(pose_old), pose_to_cm(pose_new)
+        est, st = _lib.MapEditStats(), _lib.MapStats()
+        rc = self._L.rgbd360_map_move_sphere(self._handle(), *args, _ptr(a), _ptr(b), 0, C.byref(est), C.byref(st))
+        return self._move_stats(rc, est, st)
+
+    def move_cloud(self, xyz, rgb3, pose_old, pose_new):
+        args, keep = self._cloud_args("move_cloud", xyz, rgb3)
+        a, b = pose_to_cm(pose_old), pose_to_cm(pose_new)
+        est, st = _lib.MapEditStats(), _lib.MapStats()
+        rc = self._L.rgbd360_map_move_cloud(self._handle(), *args, _ptr(a), _ptr(b), 0, C.byref(est), C.byref(st))
+        return self._move_stats(rc, est, st)
+
+    def rehash(self, capacity: int = 0):
+        """The table rebuilt without tombstones into `capacity` voxels (a power of two above it; 0: the current size).  Returns the status:
+        0, or MAP_FULL when a voxel found no slot in the new table (the map is unchanged); a capacity below len(self) raises."""
+        return self._check(self._L.rgbd360_map_rehash(self._handle(), int(capacity)))
+
+    def census(self):
+        """{n_slots, n_live, n_tombstones, n_points, n_inconsistent} of a read-only scan of the table."""
+        c = _lib.MapCensus()
+        self._check(self._L.rgbd360_map_census(self._handle(), C.byref(c)))
+        return {name: int(getattr(c, name)) for name, _ in _lib.MapCensus._fields_}
 
     # ---- alignment of a frame against the map (rgbd360_map_align_*; the reference's cloud ICP, OdometryRGBD360.cpp:98-114, 210-222)
     def align_params(self, max_dist=None, max_iters=None, eps=None, min_count=None, min_matches=None):
