@@ -66,7 +66,7 @@ class GlobalMap {
     // full and points of new voxels were dropped (stats().n_dropped_full); everything else throws.
     bool insert(const ImageView& rgb, const ImageView& depth, const Mat4f& pose, int convention = 0) {
         checkImages(rgb, depth, "GlobalMap::insert");
-        return full(rgbd360_map_insert_sphere(map_, (const uint8_t*)rgb.data, rgb.step, depth.data, depth.step, depth.type == ImageView::U16C1 ? 0 : 1,
+        return full(rgbd360_map_insert_sphere(map_, (const uint8_t*)rgb.data, rgb.step, depth.data, depth.step, depthType(depth),
                                               depth.rows, depth.cols, convention, pose.m, 0, &stats_),
                     "rgbd360_map_insert_sphere");
     }
@@ -80,7 +80,7 @@ class GlobalMap {
     // n_underflow): its content is then unspecified, clear() it.  Everything else throws.
     bool remove(const ImageView& rgb, const ImageView& depth, const Mat4f& pose, int convention = 0) {
         checkImages(rgb, depth, "GlobalMap::remove");
-        return matched(rgbd360_map_remove_sphere(map_, (const uint8_t*)rgb.data, rgb.step, depth.data, depth.step, depth.type == ImageView::U16C1 ? 0 : 1,
+        return matched(rgbd360_map_remove_sphere(map_, (const uint8_t*)rgb.data, rgb.step, depth.data, depth.step, depthType(depth),
                                                  depth.rows, depth.cols, convention, pose.m, 0, &edit_),
                        "rgbd360_map_remove_sphere");
     }
@@ -91,7 +91,7 @@ class GlobalMap {
     // in remove(), or the table was full as in insert() -- editStats() and stats() tell which; the insertion happens either way.
     bool move(const ImageView& rgb, const ImageView& depth, const Mat4f& oldPose, const Mat4f& newPose, int convention = 0) {
         checkImages(rgb, depth, "GlobalMap::move");
-        const int rc = rgbd360_map_move_sphere(map_, (const uint8_t*)rgb.data, rgb.step, depth.data, depth.step, depth.type == ImageView::U16C1 ? 0 : 1,
+        const int rc = rgbd360_map_move_sphere(map_, (const uint8_t*)rgb.data, rgb.step, depth.data, depth.step, depthType(depth),
                                                depth.rows, depth.cols, convention, oldPose.m, newPose.m, 0, &edit_, &stats_);
         check(rc, "rgbd360_map_move_sphere");
         return rc == 0;
@@ -122,7 +122,7 @@ class GlobalMap {
     }
     int alignSphere(const ImageView& depth, const Mat4f& guess, Mat4f& pose, int convention = 0, const rgbd360_map_align_params* params = nullptr) {
         if (depth.type == ImageView::U8C3) throw std::runtime_error("GlobalMap::alignSphere: a 16UC1 / 32FC1 depth image");
-        const int rc = rgbd360_map_align_sphere(map_, depth.data, depth.step, depth.type == ImageView::U16C1 ? 0 : 1, depth.rows, depth.cols, convention, guess.m, 0,
+        const int rc = rgbd360_map_align_sphere(map_, depth.data, depth.step, depthType(depth), depth.rows, depth.cols, convention, guess.m, 0,
                                                 params, pose.m, &align_);
         check(rc, "rgbd360_map_align_sphere");
         return rc;
@@ -143,7 +143,7 @@ class GlobalMap {
     }
     int alignSpherePlane(const ImageView& depth, const Mat4f& guess, Mat4f& pose, int convention = 0, const rgbd360_map_align_plane_params* params = nullptr) {
         if (depth.type == ImageView::U8C3) throw std::runtime_error("GlobalMap::alignSpherePlane: a 16UC1 / 32FC1 depth image");
-        const int rc = rgbd360_map_align_plane_sphere(map_, depth.data, depth.step, depth.type == ImageView::U16C1 ? 0 : 1, depth.rows, depth.cols, convention,
+        const int rc = rgbd360_map_align_plane_sphere(map_, depth.data, depth.step, depthType(depth), depth.rows, depth.cols, convention,
                                                       guess.m, 0, params, pose.m, &alignPlane_);
         check(rc, "rgbd360_map_align_plane_sphere");
         return rc;
@@ -199,6 +199,7 @@ class GlobalMap {
     rgbd360_map* handle() { return map_; }
 
    private:
+    static int depthType(const ImageView& depth) { return depth.type == ImageView::U16C1 ? 0 : 1; }      // the entries' depth_type
     void check(int rc, const char* what) const {
         if (rc < 0) throw std::runtime_error(std::string(what) + " (" + std::to_string(rc) + "): " + rgbd360_map_last_error(map_));
     }

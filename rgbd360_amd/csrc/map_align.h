@@ -15,8 +15,8 @@
 //
 // This header also holds what every method of alignment against the map shares with the loop (map_align_plane.h is the second
 // method): the loop's state, init and solve kernels (LoopState<WORDS>, k_vmap_icp_init<WORDS>, k_vmap_icp_solve<Row>) and the host driver
-// (icp_prepare, icp_enqueue<M>, icp_align<M>, icp_eval<M>).  A method is an evaluation kernel, a row description (PointMethod) and a host
-// description (PointIcp).  The evaluation kernels of every method are built from three shared pieces: the source load
+// (icp_prepare, icp_enqueue<M>, icp_align<M>, icp_eval<M>; the input of a call is voxel_map.h's MapInput).  A method is an evaluation
+// kernel, a row description (PointMethod) and a host description (PointIcp).  The evaluation kernels of every method are built from three shared pieces: the source load
 // (vmap::load_points, voxel_map.h, also k_vmap_insert's), the candidate search (vmap::search27 with the method's Support) and the block
 // epilogue (vmap::block_row_sum); a method's own text is its per-point tail.  tests/test_map_align_bits_gpu.py pins their bytes.
 //
@@ -304,13 +304,11 @@ __global__ __launch_bounds__(64) void k_vmap_icp_solve(LoopState<M::kWords>* __r
 
 namespace {
 
-// what one alignment call works on: the source in device memory, the launch grid, the checked parameters (the last two: point-to-plane)
+// what one alignment call works on: the input in device memory, the launch grid, the checked parameters (the last two: point-to-plane)
 struct IcpJob {
-    vmap::Source src;
-    bool cloud;
+    MapSource src;
     dim3 grid;
     int n_rows;
-    long long n_points;
     rgbd360_map_align_params p;
     int min_support;
     float max_flatness;
@@ -325,43 +323,20 @@ int icp_check_params(rgbd360_map* m, const rgbd360_map_align_params* params, rgb
     if (!(p.eps >= 0.f)) return vmap_fail(m, -1, "eps must not be negative");
     return 0;
 }
-// the source of a call in device memory (a host source is copied on the stream), the grid and the buffers, wide enough for every
-// method; 1: an empty input
-int icp_prepare(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
-                int on_device, IcpJob& job) {
-    job.cloud = depth == nullptr;
-    if (job.cloud) {
-        if (n < 0 || n >= (1ll << 40)) return vmap_fail(m, -1, "bad point count");
-        if (n == 0) return 1;
-        if (!xyz) return vmap_fail(m, -1, "xyz must not be null");
-        hipSetDevice(m->s->p.device);
-        if (!on_device) {
-            HIPC(m, m->up_depth.ensure((size_t)n * 3 * sizeof(float)));
-            HIPC(m, hipMemcpyAsync(m->up_depth, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, m->s->stream));
-            xyz = reinterpret_cast<const float*>(m->up_depth.get());
-        }
-        job.src = {nullptr, 0, nullptr, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, xyz, n};
-        job.grid = dim3((unsigned)((n + vmap::kTile - 1) / vmap::kTile));
-        job.n_points = n;
-    } else {
-        hipSetDevice(m->s->p.device);
-        if (!on_device) {
-            const size_t drow = (size_t)cols * (depth_type == 0 ? 2 : 4);
-            HIPC(m, m->up_depth.ensure(drow * rows));
-            HIPC(m, hipMemcpy2DAsync(m->up_depth, drow, depth, depth_step, drow, rows, hipMemcpyHostToDevice, m->s->stream));
-            depth = m->up_depth;
-            depth_step = drow;
-        }
-        if (const int rc = vmap_sphere_source(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, job.src)) return rc;
-        job.grid = dim3((cols + vmap::kTile - 1) / vmap::kTile, rows);
-        job.n_points = (long long)rows * cols;
-    }
+// the checked, non-empty input of a call in device memory (vmap_to_device), the grid and the buffers, wide enough for every method
+int icp_prepare(rgbd360_map* m, const MapInput& in, IcpJob& job) {
+    if (const int rc = vmap_to_device(m, in, job.src)) return rc;
+    job.grid = vmap_grid(job.src);
     job.n_rows = (int)(job.grid.x * job.grid.y);
     const size_t state_bytes = sizeof(vmap::LoopState<vmap::kIcpMaxWords>) + (size_t)std::max(job.p.max_iters, 1) * sizeof(rgbd360_map_align_trace);
     HIPC(m, m->a_part.ensure((size_t)job.n_rows * vmap::kIcpMaxWords));
     HIPC(m, m->a_state.ensure(state_bytes));
     HIPC(m, m->a_host.ensure(state_bytes));
     return 0;
+}
+// the input of an evaluation entry (rgbd360_hip_diag.h): the sphere frame where there is a depth image, otherwise the n points xyz
+MapInput icp_eval_input(const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n, int on_device) {
+    return depth ? sphere_input(nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, on_device) : cloud_input(xyz, nullptr, n, on_device);
 }
 
 // A method M (PointIcp here, PlaneIcp in map_align_plane.h) is its row (Row = vmap::PointMethod, also its base) and, for the host: Params and Result, the
@@ -407,16 +382,20 @@ int icp_enqueue(rgbd360_map* m, const IcpJob& job, const float guess[16], int it
 template <class M>
 const IcpState<M>& icp_host_state(rgbd360_map* m) { return *reinterpret_cast<const IcpState<M>*>(m->a_host.get()); }
 
+// an align call of method M: rgbd360_map_align_sphere / _cloud and their _plane forms
 template <class M>
-int icp_align(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
-              const float guess[16], int on_device, const typename M::Params* params, float pose_out[16], typename M::Result* res) {
+int icp_align(rgbd360_map* m, const MapInput& in, const float guess[16], const typename M::Params* params, float pose_out[16], typename M::Result* res) {
+    if (!m) return -1;
+    m->err.clear();
     IcpJob job;
     if (const int rc = M::check(m, params, job)) return rc;
     if (!guess || !pose_out) return vmap_fail(m, -1, "guess and pose_out must not be null");
-    const int prep = icp_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job);
-    if (prep < 0) return prep;
+    const int chk = vmap_check(m, in, true);
+    if (chk < 0) return chk;
+    if (chk == 0)
+        if (const int rc = icp_prepare(m, in, job)) return rc;
     m->a_trace.clear();
-    if (prep == 1) {             // nothing to align
+    if (chk == 1) {              // nothing to align
         memcpy(pose_out, guess, 16 * sizeof(float));
         if (res) {
             memset(res, 0, sizeof(*res));
@@ -448,22 +427,18 @@ int icp_align(rgbd360_map* m, const void* depth, size_t depth_step, int depth_ty
 }
 // one evaluation at `pose` (the diag entries): the sums in front of the counters, the method's counters, the per-point outputs
 template <class M>
-int icp_eval(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n,
-             const float pose[16], int on_device, const typename M::Params* params, double* sums, long long* counters, const typename M::Out& out) {
+int icp_eval(rgbd360_map* m, const MapInput& in, const float pose[16], const typename M::Params* params, double* sums, long long* counters,
+             const typename M::Out& out) {
     constexpr int n_counters = M::kProbes - M::kCounters;
     IcpJob job;
     if (const int rc = M::check(m, params, job)) return rc;
-    if (depth) {
-        const int chk = vmap_check_sphere(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, pose);
-        if (chk < 0) return chk;
-        if (chk == 1) depth = nullptr, n = 0;
-    }
+    const int chk = vmap_check(m, in, true);
+    if (chk < 0 && !in.cloud) return chk;        // (a refused cloud has always left the outputs zeroed, a refused image untouched)
     for (int k = 0; k < M::kCounters && sums; ++k) sums[k] = 0.0;
     for (int k = 0; k < n_counters && counters; ++k) counters[k] = 0;
+    if (chk != 0) return std::min(chk, 0);
     job.p.max_iters = 0;
-    const int prep = icp_prepare(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device, job);
-    if (prep < 0) return prep;
-    if (prep == 1) return 0;
+    if (const int rc = icp_prepare(m, in, job)) return rc;
     if (const int rc = icp_enqueue<M>(m, job, pose, 0, out)) return rc;
     HIPC(m, hipStreamSynchronize(m->s->stream));
     const IcpState<M>& st = icp_host_state<M>(m);
@@ -503,7 +478,7 @@ struct PointIcp : vmap::PointMethod {
     static int check(rgbd360_map* m, const Params* params, IcpJob& job) { return icp_check_params(m, params, job.p); }
     static int launch_eval(rgbd360_map* m, const IcpJob& job, const vmap::Params& P, int final_pass, const Out& o) {
         const float max_dist2 = job.p.max_dist * job.p.max_dist;
-        with_choice<0, 1>(job.cloud, [&](auto S) {
+        with_choice<0, 1>(job.src.cloud, [&](auto S) {
             hipLaunchKernelGGL((vmap::k_vmap_icp_eval<decltype(S)::value>), job.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.src,
                                (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, max_dist2,
                                (const IcpState<PointIcp>*)icp_state<PointIcp>(m), final_pass, m->a_part.get(), o.key3, o.d2);
@@ -527,19 +502,11 @@ extern "C" void rgbd360_map_default_align_params(const rgbd360_map* m, rgbd360_m
 extern "C" int rgbd360_map_align_sphere(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
                                         const float guess[16], int on_device, const rgbd360_map_align_params* params, float pose_out[16],
                                         rgbd360_map_align_result* result) {
-    if (!m) return -1;
-    m->err.clear();
-    const int chk = vmap_check_sphere(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, guess);
-    if (chk < 0) return chk;
-    // (an empty image: a cloud of no points)
-    return icp_align<PointIcp>(m, chk == 1 ? nullptr : depth, depth_step, depth_type, rows, cols, convention, nullptr, 0, guess, on_device, params, pose_out, result);
+    return icp_align<PointIcp>(m, sphere_input(nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, on_device), guess, params, pose_out, result);
 }
-
 extern "C" int rgbd360_map_align_cloud(rgbd360_map* m, const float* xyz, long long n, const float guess[16], int on_device,
                                        const rgbd360_map_align_params* params, float pose_out[16], rgbd360_map_align_result* result) {
-    if (!m) return -1;
-    m->err.clear();
-    return icp_align<PointIcp>(m, nullptr, 0, 0, 0, 0, 0, xyz, n, guess, on_device, params, pose_out, result);
+    return icp_align<PointIcp>(m, cloud_input(xyz, nullptr, n, on_device), guess, params, pose_out, result);
 }
 
 // measurement and tests (rgbd360_hip_diag.h)
@@ -552,20 +519,19 @@ extern "C" int rgbd360_map_align_eval(rgbd360_map* m, const void* depth, size_t 
     if (n_trace) *n_trace = (int)m->a_trace.size();
     for (int k = 0; trace && k < max_trace && k < (int)m->a_trace.size(); ++k) trace[k] = m->a_trace[k];
     if (!pose) return 0;
-    return icp_eval<PointIcp>(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, pose, on_device, params, sums, counters, {key3_dev, d2_dev});
+    return icp_eval<PointIcp>(m, icp_eval_input(depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device), pose, params, sums, counters,
+                              {key3_dev, d2_dev});
 }
 
 extern "C" int rgbd360_map_time_align(rgbd360_map* m, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
                                       const float pose[16], const rgbd360_map_align_params* params, int reps, float avg_us[5], double* probes) {
     if (!m) return -1;
     m->err.clear();
-    const int chk = vmap_check_sphere(m, nullptr, 0, depth_dev, depth_step, depth_type, rows, cols, convention, pose);
-    if (chk < 0) return chk;
-    if (chk == 1 || reps < 1 || !avg_us) return vmap_fail(m, -1, "bad arguments");
+    const MapInput in = sphere_input(nullptr, 0, depth_dev, depth_step, depth_type, rows, cols, convention, 1);
+    if (const int rc = vmap_check_timed(m, in, pose, reps, avg_us)) return rc;
     IcpJob job;
     if (const int rc = PointIcp::check(m, params, job)) return rc;
-    const int prep = icp_prepare(m, depth_dev, depth_step, depth_type, rows, cols, convention, nullptr, 0, 1, job);
-    if (prep != 0) return prep;
+    if (const int rc = icp_prepare(m, in, job)) return rc;
     const size_t drow = (size_t)cols * (depth_type == 0 ? 2 : 4);
     HIPC(m, m->up_depth.ensure(drow * rows));
     hipStream_t stream = m->s->stream;
@@ -578,7 +544,7 @@ extern "C" int rgbd360_map_time_align(rgbd360_map* m, const void* depth_dev, siz
     timer.timed(avg_us[0], reps, [&] { return PointIcp::launch_eval(m, job, P, 1, {}); });
     timer.timed(avg_us[1], reps, [&] { return icp_launch_solve<PointIcp>(m, job, 1); });
     if (rc == 0 && probes) rc = icp_read_probes<PointIcp>(m, probes);
-    timer.timed(avg_us[2], 1, [&] { return vmap_launch_insert(m, P, job.src, false); });
+    timer.timed(avg_us[2], 1, [&] { return vmap_launch_insert(m, P, job.src); });
     if (rc == 0) {
         rgbd360_map_stats stats;
         rc = std::min(vmap_finish_insert(m, &stats), 0);
@@ -586,9 +552,6 @@ extern "C" int rgbd360_map_time_align(rgbd360_map* m, const void* depth_dev, siz
     timer.timed(avg_us[3], reps, [&] {
         return hipMemcpy2DAsync(m->up_depth, drow, depth_dev, depth_step, drow, rows, hipMemcpyDeviceToDevice, stream) == hipSuccess ? 0 : -100;
     });
-    if (rc) {
-        (void)hipGetLastError();
-        return rc;
-    }
+    if (const int failed = timer.finish(avg_us, 0, reps)) return failed;
     return icp_time_whole<PointIcp>(m, job, pose, reps, avg_us[4]);
 }

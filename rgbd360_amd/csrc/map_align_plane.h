@@ -2,7 +2,7 @@
 // reference's call sites actually use (pcl::GeneralizedIterativeClosestPoint, a plane-to-plane cost: OdometryRGBD360.cpp:98-114, 210-222,
 // RegisterPairRGBD360.cpp:111-118, MethodsRegisterRGBD360.cpp:294-320) with the map as its target.  Part of the Frame360 translation unit,
 // behind map_align.h, which holds what the methods share: the lookup (vmap::find, icp_cell), the loop's state and kernels, the host
-// driver and the trace.  Here: the plane fit, the evaluation kernel, the row's description (PlaneMethod) and the host's (PlaneIcp).
+// driver (icp_align<M> and icp_eval<M> on a MapInput) and the trace.  Here: the plane fit, the evaluation kernel, the row's description (PlaneMethod) and the host's (PlaneIcp).
 //
 // Definition (include/rgbd360_hip.h, "point-to-plane ICP of a frame against the map"; tests/map_align_plane_reference.py
 // restates it in numpy).  Per source point at the current pose:
@@ -242,7 +242,7 @@ struct PlaneIcp : vmap::PlaneMethod {
     }
     static int launch_eval(rgbd360_map* m, const IcpJob& job, const vmap::Params& P, int final_pass, const Out& o) {
         const float max_dist2 = job.p.max_dist * job.p.max_dist;
-        with_choice<0, 1>(job.cloud, [&](auto S) {
+        with_choice<0, 1>(job.src.cloud, [&](auto S) {
             hipLaunchKernelGGL((vmap::k_vmap_plane_eval<decltype(S)::value>), job.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.src,
                                (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, max_dist2,
                                (unsigned)job.min_support, (double)job.max_flatness, (const IcpState<PlaneIcp>*)icp_state<PlaneIcp>(m), final_pass,
@@ -276,19 +276,11 @@ extern "C" void rgbd360_map_default_align_plane_params(const rgbd360_map* m, rgb
 extern "C" int rgbd360_map_align_plane_sphere(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
                                               const float guess[16], int on_device, const rgbd360_map_align_plane_params* params, float pose_out[16],
                                               rgbd360_map_align_plane_result* result) {
-    if (!m) return -1;
-    m->err.clear();
-    const int chk = vmap_check_sphere(m, nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, guess);
-    if (chk < 0) return chk;
-    // (an empty image: a cloud of no points)
-    return icp_align<PlaneIcp>(m, chk == 1 ? nullptr : depth, depth_step, depth_type, rows, cols, convention, nullptr, 0, guess, on_device, params, pose_out, result);
+    return icp_align<PlaneIcp>(m, sphere_input(nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, on_device), guess, params, pose_out, result);
 }
-
 extern "C" int rgbd360_map_align_plane_cloud(rgbd360_map* m, const float* xyz, long long n, const float guess[16], int on_device,
                                              const rgbd360_map_align_plane_params* params, float pose_out[16], rgbd360_map_align_plane_result* result) {
-    if (!m) return -1;
-    m->err.clear();
-    return icp_align<PlaneIcp>(m, nullptr, 0, 0, 0, 0, 0, xyz, n, guess, on_device, params, pose_out, result);
+    return icp_align<PlaneIcp>(m, cloud_input(xyz, nullptr, n, on_device), guess, params, pose_out, result);
 }
 
 // measurement and tests (rgbd360_hip_diag.h)
@@ -307,7 +299,7 @@ extern "C" int rgbd360_map_align_plane_eval(rgbd360_map* m, const void* depth, s
     if (!m) return -1;
     m->err.clear();
     if (!pose) return vmap_fail(m, -1, "pose must not be null");
-    return icp_eval<PlaneIcp>(m, depth, depth_step, depth_type, rows, cols, convention, xyz, n, pose, on_device, params, row, counters,
+    return icp_eval<PlaneIcp>(m, icp_eval_input(depth, depth_step, depth_type, rows, cols, convention, xyz, n, on_device), pose, params, row, counters,
                               {key3_dev, d2_dev, normal_r_dev, class_dev});
 }
 
@@ -315,13 +307,11 @@ extern "C" int rgbd360_map_time_align_plane(rgbd360_map* m, const void* depth_de
                                             const float pose[16], const rgbd360_map_align_plane_params* params, int reps, float avg_us[4], double* probes) {
     if (!m) return -1;
     m->err.clear();
-    const int chk = vmap_check_sphere(m, nullptr, 0, depth_dev, depth_step, depth_type, rows, cols, convention, pose);
-    if (chk < 0) return chk;
-    if (chk == 1 || reps < 1 || !avg_us) return vmap_fail(m, -1, "bad arguments");
+    const MapInput in = sphere_input(nullptr, 0, depth_dev, depth_step, depth_type, rows, cols, convention, 1);
+    if (const int rc = vmap_check_timed(m, in, pose, reps, avg_us)) return rc;
     IcpJob job;
     if (const int rc = PlaneIcp::check(m, params, job)) return rc;
-    const int prep = icp_prepare(m, depth_dev, depth_step, depth_type, rows, cols, convention, nullptr, 0, 1, job);
-    if (prep != 0) return prep;
+    if (const int rc = icp_prepare(m, in, job)) return rc;
     const vmap::Params P = vmap_params(m, pose);
     VmapTimer timer(m, m->s->stream);        // made last
     if (timer.rc) return timer.rc;
@@ -335,9 +325,6 @@ extern "C" int rgbd360_map_time_align_plane(rgbd360_map* m, const void* depth_de
     timer.timed(avg_us[0], reps, [&] { return PlaneIcp::launch_eval(m, job, P, 1, {}); });
     timer.timed(avg_us[2], reps, [&] { return icp_launch_solve<PlaneIcp>(m, job, 1); });
     if (rc == 0 && probes) rc = icp_read_probes<PlaneIcp>(m, probes);
-    if (rc) {
-        (void)hipGetLastError();
-        return rc;
-    }
+    if (const int failed = timer.finish(avg_us, 0, reps)) return failed;
     return icp_time_whole<PlaneIcp>(m, job, pose, reps, avg_us[3]);
 }

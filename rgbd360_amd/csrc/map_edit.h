@@ -1,6 +1,6 @@
 // map_edit.h -- editing the resident voxel map: exact removal, re-posing, rehash and census (rgbd360_map_remove_* / _move_* / _rehash /
 // _census, include/rgbd360_hip.h).  Part of the Frame360 translation unit, directly behind voxel_map.h, whose table,
-// Source, Params and kernels it works with.
+// Source, Params, kernels and input description (MapInput, vmap_check, vmap_to_device) it works with.
 //
 // What the reference's programs do with a map beyond appending to it: SphereGraphSLAM.cpp and KFsphere_SLAM.cpp optimise their keyframe
 // poses continuously (optimizer.optimizeGraph(), getPoses(Map.vOptimizedPoses)) and redraw the map from the corrected poses; a local
@@ -119,15 +119,13 @@ int vmap_close_remove(rgbd360_map* m, const unsigned long long* w, rgbd360_map_e
     return 0;
 }
 // the launches of an edit over `src`: the removal at pose_old, then (pose_new != null: a move) the insertion at pose_new; one wait
-int vmap_edit(rgbd360_map* m, const vmap::Source& src, bool cloud, const float* pose_old, const float* pose_new, rgbd360_map_edit_stats* removed,
-              rgbd360_map_stats* inserted) {
-    const size_t bytes = vmap::kStWords * sizeof(unsigned long long);
+int vmap_edit(rgbd360_map* m, const MapSource& src, const float* pose_old, const float* pose_new, rgbd360_map_edit_stats* removed, rgbd360_map_stats* inserted) {
     unsigned long long* h = m->h_stats;
-    if (const int rc = vmap_launch(m, vmap_params(m, pose_old), src, cloud, vmap::kRemove)) return rc;
-    HIPC(m, hipMemcpyAsync(h + vmap::kStWords, m->d_stats, bytes, hipMemcpyDeviceToHost, m->s->stream));
+    if (const int rc = vmap_launch(m, vmap_params(m, pose_old), src, vmap::kRemove)) return rc;
+    if (const int rc = vmap_copy_stats(m, vmap::kStWords, vmap::kStWords)) return rc;
     if (pose_new) {      // (whether the removal leaves tombstones is not known yet: revivals are counted)
-        if (const int rc = vmap_launch(m, vmap_params(m, pose_new), src, cloud, vmap::kInsertRevive)) return rc;
-        HIPC(m, hipMemcpyAsync(h, m->d_stats, bytes, hipMemcpyDeviceToHost, m->s->stream));
+        if (const int rc = vmap_launch(m, vmap_params(m, pose_new), src, vmap::kInsertRevive)) return rc;
+        if (const int rc = vmap_copy_stats(m, vmap::kStWords)) return rc;
     }
     HIPC(m, hipStreamSynchronize(m->s->stream));
     const int rc_remove = vmap_close_remove(m, h + vmap::kStWords, removed);
@@ -139,34 +137,19 @@ int vmap_edit(rgbd360_map* m, const vmap::Source& src, bool cloud, const float* 
     if (removed) removed->n_voxels = m->n_voxels;      // both statistics: the size after the call
     return std::max(rc_remove, rc_insert);
 }
-int vmap_edit_sphere(rgbd360_map* m, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type, int rows, int cols,
-                     int convention, const float* pose_old, const float* pose_new, bool move, int on_device, rgbd360_map_edit_stats* removed,
-                     rgbd360_map_stats* inserted) {
+// a remove call, or (move) a move call: rgbd360_map_remove_* / _move_*
+int vmap_edit_entry(rgbd360_map* m, const MapInput& in, const float* pose_old, const float* pose_new, bool move, rgbd360_map_edit_stats* removed,
+                    rgbd360_map_stats* inserted) {
     if (!m) return -1;
     m->err.clear();
-    const int chk = vmap_check_sphere(m, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, pose_old);
+    const int chk = vmap_check(m, in, pose_old && (!move || pose_new));
     if (chk < 0) return chk;
-    if (move && !pose_new) return vmap_fail(m, -1, "depth and pose must not be null");
     vmap_fill_edit_stats(m, nullptr, removed);
     vmap_fill_stats(m, nullptr, inserted);
     if (chk == 1) return 0;
-    vmap::Source src;
-    if (const int rc = vmap_sphere_on_device(m, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, on_device, src)) return rc;
-    return vmap_edit(m, src, false, pose_old, move ? pose_new : nullptr, removed, inserted);
-}
-int vmap_edit_cloud(rgbd360_map* m, const float* xyz, const uint8_t* rgb3, long long n, const float* pose_old, const float* pose_new, bool move,
-                    int on_device, rgbd360_map_edit_stats* removed, rgbd360_map_stats* inserted) {
-    if (!m) return -1;
-    m->err.clear();
-    const int chk = vmap_check_cloud(m, xyz, n, pose_old);
-    if (chk < 0) return chk;
-    if (move && n > 0 && !pose_new) return vmap_fail(m, -1, "xyz and pose must not be null");
-    vmap_fill_edit_stats(m, nullptr, removed);
-    vmap_fill_stats(m, nullptr, inserted);
-    if (chk == 1) return 0;
-    vmap::Source src;
-    if (const int rc = vmap_cloud_on_device(m, xyz, rgb3, n, on_device, src)) return rc;
-    return vmap_edit(m, src, true, pose_old, move ? pose_new : nullptr, removed, inserted);
+    MapSource src;
+    if (const int rc = vmap_to_device(m, in, src)) return rc;
+    return vmap_edit(m, src, pose_old, move ? pose_new : nullptr, removed, inserted);
 }
 // the census launch over the table, enqueued; its counters land in d_stats[0 .. kCnWords)
 int vmap_launch_census(rgbd360_map* m) {
@@ -192,20 +175,21 @@ static_assert(vmap::kCnWords <= vmap::kStWords, "the census counters live in the
 
 extern "C" int rgbd360_map_remove_sphere(rgbd360_map* m, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type,
                                          int rows, int cols, int convention, const float pose[16], int on_device, rgbd360_map_edit_stats* stats) {
-    return vmap_edit_sphere(m, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, pose, nullptr, false, on_device, stats, nullptr);
+    return vmap_edit_entry(m, sphere_input(rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, on_device), pose, nullptr, false, stats, nullptr);
 }
 extern "C" int rgbd360_map_remove_cloud(rgbd360_map* m, const float* xyz, const uint8_t* rgb3, long long n, const float pose[16], int on_device,
                                         rgbd360_map_edit_stats* stats) {
-    return vmap_edit_cloud(m, xyz, rgb3, n, pose, nullptr, false, on_device, stats, nullptr);
+    return vmap_edit_entry(m, cloud_input(xyz, rgb3, n, on_device), pose, nullptr, false, stats, nullptr);
 }
 extern "C" int rgbd360_map_move_sphere(rgbd360_map* m, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type, int rows,
                                        int cols, int convention, const float pose_old[16], const float pose_new[16], int on_device,
                                        rgbd360_map_edit_stats* removed, rgbd360_map_stats* inserted) {
-    return vmap_edit_sphere(m, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, pose_old, pose_new, true, on_device, removed, inserted);
+    return vmap_edit_entry(m, sphere_input(rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, on_device), pose_old, pose_new, true, removed,
+                           inserted);
 }
 extern "C" int rgbd360_map_move_cloud(rgbd360_map* m, const float* xyz, const uint8_t* rgb3, long long n, const float pose_old[16], const float pose_new[16],
                                       int on_device, rgbd360_map_edit_stats* removed, rgbd360_map_stats* inserted) {
-    return vmap_edit_cloud(m, xyz, rgb3, n, pose_old, pose_new, true, on_device, removed, inserted);
+    return vmap_edit_entry(m, cloud_input(xyz, rgb3, n, on_device), pose_old, pose_new, true, removed, inserted);
 }
 
 extern "C" int rgbd360_map_rehash(rgbd360_map* m, long long capacity_voxels) {
@@ -222,8 +206,7 @@ extern "C" int rgbd360_map_rehash(rgbd360_map* m, long long capacity_voxels) {
         return vmap_fail(m, -103, "rgbd360_map_rehash: out of memory");
     }
     if (const int rc = vmap_launch_rehash(m, fresh, n_slots)) return rc;
-    HIPC(m, hipMemcpyAsync(m->h_stats, m->d_stats, sizeof(unsigned long long), hipMemcpyDeviceToHost, m->s->stream));
-    HIPC(m, hipStreamSynchronize(m->s->stream));
+    if (const int rc = vmap_read_stats(m, 1)) return rc;
     if (m->h_stats[0]) {      // (the new table goes with `fresh`)
         m->err = "rehash: voxels found no free slot within the probe bound of the new table; the map is unchanged";
         return RGBD360_MAP_FULL;
@@ -240,8 +223,7 @@ extern "C" int rgbd360_map_census(rgbd360_map* m, rgbd360_map_census_counts* out
     if (!out) return vmap_fail(m, -1, "out must not be null");
     hipSetDevice(m->s->p.device);
     if (const int rc = vmap_launch_census(m)) return rc;
-    HIPC(m, hipMemcpyAsync(m->h_stats, m->d_stats, vmap::kCnWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->s->stream));
-    HIPC(m, hipStreamSynchronize(m->s->stream));
+    if (const int rc = vmap_read_stats(m, vmap::kCnWords)) return rc;
     const unsigned long long* w = m->h_stats;
     *out = {(long long)m->n_slots, (long long)w[vmap::kCnLive], (long long)w[vmap::kCnTombstones], (long long)w[vmap::kCnPoints],
             (long long)w[vmap::kCnInconsistent]};
@@ -253,12 +235,10 @@ extern "C" int rgbd360_map_time_edit(rgbd360_map* m, const uint8_t* rgb_dev, siz
                                      int rows, int cols, int convention, const float pose[16], int reps, float avg_us[7]) {
     if (!m) return -1;
     m->err.clear();
-    const int chk = vmap_check_sphere(m, rgb_dev, rgb_step, depth_dev, depth_step, depth_type, rows, cols, convention, pose);
-    if (chk < 0) return chk;
-    if (chk == 1 || reps < 1 || !avg_us) return vmap_fail(m, -1, "bad arguments");
-    hipSetDevice(m->s->p.device);
-    vmap::Source src;
-    if (const int rc = vmap_sphere_source(m, rgb_dev, rgb_step, depth_dev, depth_step, depth_type, rows, cols, convention, src)) return rc;
+    const MapInput in = sphere_input(rgb_dev, rgb_step, depth_dev, depth_step, depth_type, rows, cols, convention, 1);
+    if (const int rc = vmap_check_timed(m, in, pose, reps, avg_us)) return rc;
+    MapSource src;
+    if (const int rc = vmap_to_device(m, in, src)) return rc;
     const vmap::Params P = vmap_params(m, pose);
     DevBuf<unsigned long long> fresh;
     if (fresh.ensure(m->n_slots * vmap::kFields) != hipSuccess) {
@@ -266,14 +246,7 @@ extern "C" int rgbd360_map_time_edit(rgbd360_map* m, const uint8_t* rgb_dev, siz
         return vmap_fail(m, -103, "out of memory");
     }
     VmapTimer timer(m, m->s->stream);
-    if (timer.rc) return timer.rc;
-    double sum[7] = {0, 0, 0, 0, 0, 0, 0};
     int& rc = timer.rc;
-    auto timed = [&](int which, auto&& body) {
-        float us = 0.f;
-        timer.timed(us, 1, body);
-        sum[which] += (double)us;
-    };
     rgbd360_map_stats st;
     rgbd360_map_edit_stats est;
     auto close_insert = [&] {
@@ -282,36 +255,21 @@ extern "C" int rgbd360_map_time_edit(rgbd360_map* m, const uint8_t* rgb_dev, siz
     for (int r = 0; r < reps && rc == 0; ++r) {
         // the map holds the frame twice: a removal leaves every voxel live, as in a window of overlapping frames
         if ((rc = vmap_clear_dev(m)) != 0) break;
-        if ((rc = vmap_launch(m, P, src, false, vmap::kInsert)) != 0) break;
+        if ((rc = vmap_launch(m, P, src, vmap::kInsert)) != 0) break;
         close_insert();
-        timed(0, [&] { return vmap_launch(m, P, src, false, vmap::kInsert); });            // the claim count, populated map
+        timer.add(0, [&] { return vmap_launch(m, P, src, vmap::kInsert); });            // the claim count, populated map
         close_insert();
-        timed(1, [&] { return vmap_launch(m, P, src, false, vmap::kRemove); });            // the removal kernel, same map
-        if (rc == 0) {
-            const size_t bytes = vmap::kStWords * sizeof(unsigned long long);
-            if (hipMemcpyAsync(m->h_stats, m->d_stats, bytes, hipMemcpyDeviceToHost, m->s->stream) != hipSuccess || hipStreamSynchronize(m->s->stream) != hipSuccess)
-                rc = vmap_fail(m, -100, "reading the counters failed");
-            else rc = std::min(vmap_close_remove(m, m->h_stats, &est), 0);
-        }
-        timed(2, [&] { return vmap_launch(m, P, src, false, vmap::kInsertRevive); });      // the returning count add, populated map
+        timer.add(1, [&] { return vmap_launch(m, P, src, vmap::kRemove); });            // the removal kernel, same map
+        if (rc == 0) rc = vmap_read_stats(m, vmap::kStWords);
+        if (rc == 0) rc = std::min(vmap_close_remove(m, m->h_stats, &est), 0);
+        timer.add(2, [&] { return vmap_launch(m, P, src, vmap::kInsertRevive); });      // the returning count add, populated map
         close_insert();
         if (rc == 0 && m->x_xyz.ensure(3 * (size_t)m->n_voxels + 3) != hipSuccess) rc = vmap_fail(m, -103, "out of memory");
-        timed(3, [&] { return vmap_launch_rehash(m, fresh, m->n_slots); });               // clear of the new table + k_vmap_rehash
-        timed(4, [&] { return vmap_launch_census(m); });
-        timed(5, [&] {       // (with the clear of its counter, as in every extract call)
-            hipMemsetAsync(m->d_stats + vmap::kStExtract, 0, sizeof(unsigned long long), m->s->stream);
-            hipLaunchKernelGGL(vmap::k_vmap_extract, dim3((unsigned)((m->n_slots + 255) / 256)), dim3(256), 0, m->s->stream, m->table, m->n_slots, m->n_voxels,
-                               m->d_stats + vmap::kStExtract, m->x_xyz, (uint8_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
-            return 0;
-        });
+        timer.add(3, [&] { return vmap_launch_rehash(m, fresh, m->n_slots); });        // clear of the new table + k_vmap_rehash
+        timer.add(4, [&] { return vmap_launch_census(m); });
+        timer.add(5, [&] { return vmap_launch_extract_scan(m); });                     // (with the clear of its counter, as in every extract call)
         // a whole move call from device memory, enqueue to synchronisation: both launches and the one wait
-        timed(6, [&] { return std::min(vmap_edit(m, src, false, pose, pose, &est, &st), 0); });
+        timer.add(6, [&] { return std::min(vmap_edit(m, src, pose, pose, &est, &st), 0); });
     }
-    if (rc) {
-        (void)hipGetLastError();
-        return rc;
-    }
-    HIPC(m, hipGetLastError());
-    for (int k = 0; k < 7; ++k) avg_us[k] = (float)(sum[k] / reps);
-    return 0;
+    return timer.finish(avg_us, 7, reps);
 }

@@ -55,6 +55,11 @@
 //                   returned 0 (a claim or a revival), not the claim, which costs a returning atomic per entry; a map that never had
 //                   a voxel emptied keeps kInsert, the claim count.
 //   k_vmap_extract  one lane per slot; a wave reserves its output range with one counter add and every lane stores its record.
+//   host            every entry of the map that takes a frame or a cloud (here, map_edit.h, map_align.h, map_align_plane.h) describes it as
+//                   one MapInput, has vmap_check refuse it before anything is touched and vmap_to_device make it the kernels' Source
+//                   (MapSource: with which of its two forms it is; vmap_grid: its launch grid) -- DESIGN.md 3.16.  One launch of the
+//                   extract kernel (vmap_launch_extract), one read-back of the counter words (vmap_copy_stats / vmap_read_stats), one
+//                   scaffold of the rgbd360_map_time_* entries (VmapTimer).
 #pragma once
 #include "map_table.h"
 
@@ -412,6 +417,7 @@ struct VmapTimer {
     hipStream_t stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = 0;
+    double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // add()'s microseconds per slot
     VmapTimer(rgbd360_map* m_, hipStream_t stream_) : m(m_), stream(stream_) {
         if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
             (void)hipGetLastError();
@@ -435,7 +441,121 @@ struct VmapTimer {
             rc = vmap_fail(m, -100, "timing the kernels failed");
         out = ms * 1000.f / (float)count;
     }
+    // one call of body() between the events, its time added to slot `which`
+    template <class Body>
+    void add(int which, Body&& body) {
+        float us = 0.f;
+        timed(us, 1, body);
+        sum[which] += (double)us;
+    }
+    // how a time_* entry ends: the first failure, or a launch error left behind, or avg_us[0 .. n) = the slots' sums over `reps`
+    int finish(float* avg_us, int n, int reps) {
+        if (rc) {
+            (void)hipGetLastError();
+            return rc;
+        }
+        HIPC(m, hipGetLastError());
+        for (int k = 0; k < n; ++k) avg_us[k] = (float)(sum[k] / reps);
+        return 0;
+    }
 };
+
+// What a map call works on, as the caller handed it over: a sphere image or a cloud, in host memory or, on_device, in
+// device memory.  Every entry builds one, vmap_check refuses a bad one before anything is touched, vmap_to_device makes it the kernels'.
+struct MapInput {
+    bool cloud = false;
+    int on_device = 0;
+    const uint8_t* rgb = nullptr;        // the image's 8UC3 rows / the cloud's n x 3 bytes; null: no colour
+    size_t rgb_step = 0;
+    const void* depth = nullptr;
+    size_t depth_step = 0;
+    int depth_type = 0, rows = 0, cols = 0, convention = 0;
+    const float* xyz = nullptr;
+    long long n = 0;
+};
+MapInput sphere_input(const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                      int on_device) {
+    MapInput in;
+    in.on_device = on_device;
+    in.rgb = rgb, in.rgb_step = rgb_step, in.depth = depth, in.depth_step = depth_step;
+    in.depth_type = depth_type, in.rows = rows, in.cols = cols, in.convention = convention;
+    return in;
+}
+MapInput cloud_input(const float* xyz, const uint8_t* rgb3, long long n, int on_device) {
+    MapInput in;
+    in.cloud = true;
+    in.on_device = on_device;
+    in.rgb = rgb3, in.xyz = xyz, in.n = n;
+    return in;
+}
+// ... and in device memory: the kernels' Source with which of its two forms it is
+struct MapSource : vmap::Source {
+    bool cloud = false;
+};
+
+// What every entry checks of its input before anything is launched, uploaded or allocated; have_pose: the call's pose(s) are there.
+// 1: an empty image or no points (nothing to do; no points need no xyz and no pose)
+int vmap_check(rgbd360_map* m, const MapInput& in, bool have_pose) {
+    if (in.cloud) {
+        if (in.n < 0 || in.n >= (1ll << 40)) return vmap_fail(m, -1, "bad point count");
+        if (in.n > 0 && (!in.xyz || !have_pose)) return vmap_fail(m, -1, "xyz and pose must not be null");
+        return in.n == 0 ? 1 : 0;
+    }
+    if (!in.depth || !have_pose) return vmap_fail(m, -1, "depth and pose must not be null");
+    if (in.convention < 0 || in.convention > 2 || (in.depth_type != 0 && in.depth_type != 1)) return vmap_fail(m, -1, "bad convention or depth type");
+    if (in.rows < 0 || in.cols < 0 || (long long)in.rows * in.cols >= (1ll << 30)) return vmap_fail(m, -1, "bad image size");
+    if (in.rows == 0 || in.cols == 0) return 1;
+    if (in.depth_step < (size_t)in.cols * (in.depth_type == 0 ? 2 : 4) || (in.rgb && in.rgb_step < (size_t)in.cols * 3))
+        return vmap_fail(m, -1, "row step shorter than a row");
+    return 0;
+}
+// ... and of a time_* entry's device image
+int vmap_check_timed(rgbd360_map* m, const MapInput& in, const float* pose, int reps, const float* avg_us) {
+    const int chk = vmap_check(m, in, pose != nullptr);
+    if (chk < 0) return chk;
+    return chk == 1 || reps < 1 || !avg_us ? vmap_fail(m, -1, "bad arguments") : 0;
+}
+// A checked, non-empty input as the kernels take it.  A host input goes up first, as packed copies on the map's stream (the colour only
+// when there is one) -- the caller's memory is free once the stream has been waited for, which every entry does before it returns; a
+// sphere image gets the context's angle tables of its geometry.
+int vmap_to_device(rgbd360_map* m, const MapInput& in, MapSource& src) {
+    hipSetDevice(m->s->p.device);
+    const size_t n_rows = in.cloud ? 1 : (size_t)in.rows;
+    const void* points = in.cloud ? (const void*)in.xyz : in.depth;
+    const uint8_t* rgb = in.rgb;
+    size_t prow = in.cloud ? (size_t)in.n * 3 * sizeof(float) : (size_t)in.cols * (in.depth_type == 0 ? 2 : 4), pstep = in.depth_step;
+    size_t crow = in.cloud ? (size_t)in.n * 3 : (size_t)in.cols * 3, cstep = in.rgb_step;
+    auto upload = [&](DevBuf<uint8_t>& buf, const void* host, size_t step, size_t row) {
+        if (const hipError_t e = buf.ensure(row * n_rows)) return e;
+        return in.cloud ? hipMemcpyAsync(buf, host, row, hipMemcpyHostToDevice, m->s->stream)
+                        : hipMemcpy2DAsync(buf, row, host, step, row, n_rows, hipMemcpyHostToDevice, m->s->stream);
+    };
+    if (!in.on_device) {
+        HIPC(m, upload(m->up_depth, points, pstep, prow));
+        points = m->up_depth.get(), pstep = prow;
+        if (rgb) {
+            HIPC(m, upload(m->up_rgb, rgb, cstep, crow));
+            rgb = m->up_rgb.get(), cstep = crow;
+        }
+    }
+    if (in.cloud) {
+        src = {{nullptr, 0, rgb, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, static_cast<const float*>(points), in.n}, true};
+        return 0;
+    }
+    if (const int rc = sphere_tables_dev(m->s, in.rows, in.cols, in.convention)) {
+        m->err = m->s->err;
+        return rc;
+    }
+    const float* tab = m->s->f_tab;
+    src = {{points, pstep, rgb, cstep, in.depth_type, in.rows, in.cols, in.convention, tab, tab + in.cols, tab + 2 * in.cols, tab + 2 * in.cols + in.rows, nullptr, 0},
+           false};
+    return 0;
+}
+// the launch grid of a source: a workgroup per tile of kTile points, of an image row or of the cloud
+dim3 vmap_grid(const MapSource& src) {
+    return src.cloud ? dim3((unsigned)((src.n + vmap::kTile - 1) / vmap::kTile)) : dim3((src.cols + vmap::kTile - 1) / vmap::kTile, src.rows);
+}
+
 int vmap_clear_dev(rgbd360_map* m) {
     const unsigned long long words = m->n_slots * vmap::kFields;
     hipLaunchKernelGGL(vmap::k_vmap_clear, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, m->s->stream, m->table, words);
@@ -464,12 +584,22 @@ void vmap_fill_stats(const rgbd360_map* m, const unsigned long long* w, rgbd360_
     st->n_dropped_full = w ? (long long)w[vmap::kStDropped] : 0;
     st->n_voxels = m->n_voxels;
 }
-// the insert kernel over `src` (device memory) in `mode` (vmap::kInsert ..), enqueued on the stream; the statistics words are cleared in
-// front of it.  The two-argument form is an insert as the map stands: revivals are counted once a removal has emptied a voxel.
-int vmap_launch(rgbd360_map* m, const vmap::Params& P, const vmap::Source& src, bool cloud, int mode) {
+// `words` counter words from d_stats into h_stats[at ..): enqueued on the stream (vmap_copy_stats), or there when the call returns
+int vmap_copy_stats(rgbd360_map* m, int words, int at = 0) {
+    HIPC(m, hipMemcpyAsync(m->h_stats + at, m->d_stats, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->s->stream));
+    return 0;
+}
+int vmap_read_stats(rgbd360_map* m, int words, int at = 0) {
+    if (const int rc = vmap_copy_stats(m, words, at)) return rc;
+    HIPC(m, hipStreamSynchronize(m->s->stream));
+    return 0;
+}
+// the insert kernel over `src` in `mode` (vmap::kInsert ..), enqueued on the stream; the statistics words are cleared in front of it.
+// vmap_launch_insert is an insert as the map stands: revivals are counted once a removal has emptied a voxel.
+int vmap_launch(rgbd360_map* m, const vmap::Params& P, const MapSource& src, int mode) {
     HIPC(m, hipMemsetAsync(m->d_stats, 0, (mode == vmap::kRemove ? vmap::kStWords : vmap::kStInsertWords) * sizeof(unsigned long long), m->s->stream));
-    const dim3 grid = cloud ? dim3((unsigned)((src.n + vmap::kTile - 1) / vmap::kTile)) : dim3((src.cols + vmap::kTile - 1) / vmap::kTile, src.rows);
-    with_choice<0, 1>(cloud, [&](auto S) {
+    const dim3 grid = vmap_grid(src);
+    with_choice<0, 1>(src.cloud, [&](auto S) {
         with_int<vmap::kInsert, vmap::kInsertRevive>(mode, [&](auto M) {
             hipLaunchKernelGGL((vmap::k_vmap_insert<decltype(S)::value, decltype(M)::value>), grid, dim3(vmap::kThreads), 0, m->s->stream, P, src, m->table,
                                m->n_slots - 1, m->d_stats);
@@ -478,17 +608,10 @@ int vmap_launch(rgbd360_map* m, const vmap::Params& P, const vmap::Source& src, 
     HIPC(m, hipGetLastError());
     return 0;
 }
-int vmap_launch_insert(rgbd360_map* m, const vmap::Params& P, const vmap::Source& src, bool cloud) {
-    return vmap_launch(m, P, src, cloud, m->may_hold_tombstones ? vmap::kInsertRevive : vmap::kInsert);
+int vmap_launch_insert(rgbd360_map* m, const vmap::Params& P, const MapSource& src) {
+    return vmap_launch(m, P, src, m->may_hold_tombstones ? vmap::kInsertRevive : vmap::kInsert);
 }
-// ... and how an insert call ends: the statistics on the host, the map's size brought up to date
-int vmap_close_insert(rgbd360_map* m, const unsigned long long* w, rgbd360_map_stats* stats);
-int vmap_finish_insert(rgbd360_map* m, rgbd360_map_stats* stats) {
-    HIPC(m, hipMemcpyAsync(m->h_stats, m->d_stats, vmap::kStInsertWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->s->stream));
-    HIPC(m, hipStreamSynchronize(m->s->stream));
-    return vmap_close_insert(m, m->h_stats, stats);
-}
-// (the counters `w` of an insert launch are on the host)
+// how an insert ends once its counters `w` are on the host: the map's size brought up to date, the statistics, the status
 int vmap_close_insert(rgbd360_map* m, const unsigned long long* w, rgbd360_map_stats* stats) {
     m->n_voxels += (long long)w[vmap::kStNew];
     m->last_updates = (long long)w[vmap::kStUpdates];
@@ -499,69 +622,41 @@ int vmap_close_insert(rgbd360_map* m, const unsigned long long* w, rgbd360_map_s
     }
     return 0;
 }
-// what an insert_sphere call checks before anything is launched; 1: an empty image (nothing to do)
-int vmap_check_sphere(rgbd360_map* m, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type, int rows, int cols,
-                      int convention, const float* pose) {
-    if (!depth || !pose) return vmap_fail(m, -1, "depth and pose must not be null");
-    if (convention < 0 || convention > 2 || (depth_type != 0 && depth_type != 1)) return vmap_fail(m, -1, "bad convention or depth type");
-    if (rows < 0 || cols < 0 || (long long)rows * cols >= (1ll << 30)) return vmap_fail(m, -1, "bad image size");
-    if (rows == 0 || cols == 0) return 1;
-    if (depth_step < (size_t)cols * (depth_type == 0 ? 2 : 4) || (rgb && rgb_step < (size_t)cols * 3)) return vmap_fail(m, -1, "row step shorter than a row");
+int vmap_finish_insert(rgbd360_map* m, rgbd360_map_stats* stats) {
+    if (const int rc = vmap_read_stats(m, vmap::kStInsertWords)) return rc;
+    return vmap_close_insert(m, m->h_stats, stats);
+}
+// an insert call: rgbd360_map_insert_sphere / _cloud
+int vmap_insert(rgbd360_map* m, const MapInput& in, const float* pose, rgbd360_map_stats* stats) {
+    if (!m) return -1;
+    m->err.clear();
+    const int chk = vmap_check(m, in, pose != nullptr);
+    if (chk < 0) return chk;
+    vmap_fill_stats(m, nullptr, stats);
+    if (chk == 1) return 0;
+    MapSource src;
+    if (const int rc = vmap_to_device(m, in, src)) return rc;
+    if (const int rc = vmap_launch_insert(m, vmap_params(m, pose), src)) return rc;
+    return vmap_finish_insert(m, stats);
+}
+// the extract kernel into device arrays (any may be null; records beyond max_out are counted, not written), enqueued behind the clear of
+// its counter
+int vmap_launch_extract(rgbd360_map* m, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3) {
+    unsigned long long* counter = m->d_stats + vmap::kStExtract;
+    HIPC(m, hipMemsetAsync(counter, 0, sizeof(unsigned long long), m->s->stream));
+    hipLaunchKernelGGL(vmap::k_vmap_extract, dim3((unsigned)((m->n_slots + 255) / 256)), dim3(256), 0, m->s->stream, m->table, m->n_slots, max_out, counter,
+                       xyz, rgb3, count, key3);
+    HIPC(m, hipGetLastError());
     return 0;
 }
-// the kernel's view of a sphere image in device memory, with the context's angle tables of that geometry
-int vmap_sphere_source(rgbd360_map* m, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type, int rows, int cols,
-                       int convention, vmap::Source& src) {
-    if (const int rc = sphere_tables_dev(m->s, rows, cols, convention)) {
-        m->err = m->s->err;
-        return rc;
-    }
-    const float* tab = m->s->f_tab;
-    src = {depth, depth_step, rgb, rgb_step, depth_type, rows, cols, convention, tab, tab + cols, tab + 2 * cols, tab + 2 * cols + rows, nullptr, 0};
+// ... complete when the call returns
+int vmap_extract_dev(rgbd360_map* m, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3) {
+    if (const int rc = vmap_launch_extract(m, max_out, xyz, rgb3, count, key3)) return rc;
+    HIPC(m, hipStreamSynchronize(m->s->stream));
     return 0;
 }
-// A checked sphere image as the kernels take it: a host image (on_device == 0) goes up first, as packed copies on the map's stream -- the
-// caller's memory is free once the stream has been waited for, which every entry does before it returns
-int vmap_sphere_on_device(rgbd360_map* m, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type, int rows, int cols,
-                          int convention, int on_device, vmap::Source& src) {
-    hipSetDevice(m->s->p.device);
-    if (!on_device) {
-        const size_t drow = (size_t)cols * (depth_type == 0 ? 2 : 4);
-        HIPC(m, m->up_depth.ensure(drow * rows));
-        HIPC(m, hipMemcpy2DAsync(m->up_depth, drow, depth, depth_step, drow, rows, hipMemcpyHostToDevice, m->s->stream));
-        depth = m->up_depth;
-        depth_step = drow;
-        if (rgb) {
-            HIPC(m, m->up_rgb.ensure((size_t)cols * 3 * rows));
-            HIPC(m, hipMemcpy2DAsync(m->up_rgb, (size_t)cols * 3, rgb, rgb_step, (size_t)cols * 3, rows, hipMemcpyHostToDevice, m->s->stream));
-            rgb = m->up_rgb;
-            rgb_step = (size_t)cols * 3;
-        }
-    }
-    return vmap_sphere_source(m, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, src);
-}
-// ... and a cloud of n > 0 points
-int vmap_cloud_on_device(rgbd360_map* m, const float* xyz, const uint8_t* rgb3, long long n, int on_device, vmap::Source& src) {
-    hipSetDevice(m->s->p.device);
-    if (!on_device) {
-        HIPC(m, m->up_depth.ensure((size_t)n * 3 * sizeof(float)));
-        HIPC(m, hipMemcpyAsync(m->up_depth, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, m->s->stream));
-        xyz = reinterpret_cast<const float*>(m->up_depth.get());
-        if (rgb3) {
-            HIPC(m, m->up_rgb.ensure((size_t)n * 3));
-            HIPC(m, hipMemcpyAsync(m->up_rgb, rgb3, (size_t)n * 3, hipMemcpyHostToDevice, m->s->stream));
-            rgb3 = m->up_rgb;
-        }
-    }
-    src = {nullptr, 0, rgb3, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, xyz, n};
-    return 0;
-}
-// what an insert_cloud call checks; 1: no points (nothing to do)
-int vmap_check_cloud(rgbd360_map* m, const float* xyz, long long n, const float* pose) {
-    if (n < 0 || n >= (1ll << 40)) return vmap_fail(m, -1, "bad point count");
-    if (n > 0 && (!xyz || !pose)) return vmap_fail(m, -1, "xyz and pose must not be null");
-    return n == 0 ? 1 : 0;
-}
+// the scan alone (xyz only, into x_xyz), as the time_* entries measure it
+int vmap_launch_extract_scan(rgbd360_map* m) { return vmap_launch_extract(m, m->n_voxels, m->x_xyz, nullptr, nullptr, nullptr); }
 }  // namespace
 
 extern "C" int rgbd360_map_create(rgbd360_ctx* ctx_, float leaf, long long capacity_voxels, rgbd360_map** out) {
@@ -614,30 +709,11 @@ extern "C" int rgbd360_map_set_box(rgbd360_map* m, const float lo[3], const floa
 
 extern "C" int rgbd360_map_insert_sphere(rgbd360_map* m, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type,
                                          int rows, int cols, int convention, const float pose[16], int on_device, rgbd360_map_stats* stats) {
-    if (!m) return -1;
-    m->err.clear();
-    const int chk = vmap_check_sphere(m, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, pose);
-    if (chk < 0) return chk;
-    vmap_fill_stats(m, nullptr, stats);
-    if (chk == 1) return 0;
-    vmap::Source src;
-    if (const int rc = vmap_sphere_on_device(m, rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, on_device, src)) return rc;
-    if (const int rc = vmap_launch_insert(m, vmap_params(m, pose), src, false)) return rc;
-    return vmap_finish_insert(m, stats);
+    return vmap_insert(m, sphere_input(rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, on_device), pose, stats);
 }
-
 extern "C" int rgbd360_map_insert_cloud(rgbd360_map* m, const float* xyz, const uint8_t* rgb3, long long n, const float pose[16], int on_device,
                                         rgbd360_map_stats* stats) {
-    if (!m) return -1;
-    m->err.clear();
-    const int chk = vmap_check_cloud(m, xyz, n, pose);
-    if (chk < 0) return chk;
-    vmap_fill_stats(m, nullptr, stats);
-    if (chk == 1) return 0;
-    vmap::Source src;
-    if (const int rc = vmap_cloud_on_device(m, xyz, rgb3, n, on_device, src)) return rc;
-    if (const int rc = vmap_launch_insert(m, vmap_params(m, pose), src, true)) return rc;
-    return vmap_finish_insert(m, stats);
+    return vmap_insert(m, cloud_input(xyz, rgb3, n, on_device), pose, stats);
 }
 
 extern "C" long long rgbd360_map_size(rgbd360_map* m) { return m ? m->n_voxels : -1; }
@@ -649,19 +725,6 @@ extern "C" int rgbd360_map_clear(rgbd360_map* m) {
     HIPC(m, hipStreamSynchronize(m->s->stream));
     return 0;
 }
-
-namespace {
-// the extract kernel into device arrays (any may be null), complete when the call returns
-int vmap_extract_dev(rgbd360_map* m, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3) {
-    unsigned long long* counter = m->d_stats + vmap::kStExtract;
-    HIPC(m, hipMemsetAsync(counter, 0, sizeof(unsigned long long), m->s->stream));
-    hipLaunchKernelGGL(vmap::k_vmap_extract, dim3((unsigned)((m->n_slots + 255) / 256)), dim3(256), 0, m->s->stream, m->table, m->n_slots, max_out, counter,
-                       xyz, rgb3, count, key3);
-    HIPC(m, hipGetLastError());
-    HIPC(m, hipStreamSynchronize(m->s->stream));
-    return 0;
-}
-}  // namespace
 
 extern "C" long long rgbd360_map_extract_dev(rgbd360_map* m, long long max_out, float* xyz, uint8_t* rgb3, int32_t* count, int32_t* key3) {
     if (!m) return -1;
@@ -732,14 +795,8 @@ int rgbd360_map_time_extract_scan(rgbd360_map* m, int reps, float* avg_us) {
     hipSetDevice(m->s->p.device);
     if (m->x_xyz.ensure(3 * (size_t)m->n_voxels + 3) != hipSuccess) return vmap_fail(m, -103, "out of memory");
     VmapTimer timer(m, m->s->stream);
-    timer.timed(*avg_us, reps, [&] {     // (with the clear of its counter, as in every extract call)
-        hipMemsetAsync(m->d_stats + vmap::kStExtract, 0, sizeof(unsigned long long), m->s->stream);
-        hipLaunchKernelGGL(vmap::k_vmap_extract, dim3((unsigned)((m->n_slots + 255) / 256)), dim3(256), 0, m->s->stream, m->table, m->n_slots, m->n_voxels,
-                           m->d_stats + vmap::kStExtract, m->x_xyz, (uint8_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
-        return 0;
-    });
-    if (timer.rc == 0 && hipGetLastError() != hipSuccess) return vmap_fail(m, -100, "the extract launch failed");
-    return timer.rc;
+    timer.timed(*avg_us, reps, [&] { return vmap_launch_extract_scan(m); });       // (with the clear of its counter, as in every extract call)
+    return timer.finish(avg_us, 0, reps);
 }
 
 // measurement (rgbd360_hip_diag.h)
@@ -748,62 +805,43 @@ extern "C" int rgbd360_map_time_kernels(rgbd360_map* m, const uint8_t* rgb_dev, 
                                         long long* global_updates) {
     if (!m) return -1;
     m->err.clear();
-    const int chk = vmap_check_sphere(m, rgb_dev, rgb_step, depth_dev, depth_step, depth_type, rows, cols, convention, pose);
-    if (chk < 0) return chk;
-    if (chk == 1 || reps < 1 || !avg_us) return vmap_fail(m, -1, "bad arguments");
+    const MapInput in = sphere_input(rgb_dev, rgb_step, depth_dev, depth_step, depth_type, rows, cols, convention, 1);
+    if (const int rc = vmap_check_timed(m, in, pose, reps, avg_us)) return rc;
     F360State* ctx = m->s;
     hipSetDevice(ctx->p.device);
     if (const int rc = f360_begin(ctx, rows, cols, 1)) {
         m->err = ctx->err;
         return rc;
     }
-    vmap::Source src;
-    if (const int rc = vmap_sphere_source(m, rgb_dev, rgb_step, depth_dev, depth_step, depth_type, rows, cols, convention, src)) return rc;
+    MapSource src;
+    if (const int rc = vmap_to_device(m, in, src)) return rc;
     const vmap::Params P = vmap_params(m, pose);
     const size_t drow = (size_t)cols * (depth_type == 0 ? 2 : 4), crow = rgb_dev ? (size_t)cols * 3 : 0;
     HIPC(m, m->up_depth.ensure(drow * rows));
     if (crow) HIPC(m, m->up_rgb.ensure(crow * rows));
     VmapTimer timer(m, ctx->stream);         // made last
-    if (timer.rc) return timer.rc;
-    double sum[5] = {0, 0, 0, 0, 0};
     int& rc = timer.rc;
-    auto timed = [&](int which, auto&& body) {
-        float us = 0.f;
-        timer.timed(us, 1, body);
-        sum[which] += (double)us;
-    };
     rgbd360_map_stats st;
     for (int r = 0; r < reps && rc == 0; ++r) {
         if ((rc = vmap_clear_dev(m)) != 0) break;
         // (the statistics' clear is a 64-byte memset in front of the kernel, inside the window: it is part of every insert)
-        timed(0, [&] { return vmap_launch_insert(m, P, src, false); });       // an empty map
+        timer.add(0, [&] { return vmap_launch_insert(m, P, src); });       // an empty map
         if (rc == 0) rc = std::min(vmap_finish_insert(m, &st), 0);
         if (global_updates) *global_updates = m->last_updates;
-        timed(1, [&] { return vmap_launch_insert(m, P, src, false); });       // the map holds the frame's voxels: odometry's steady state
+        timer.add(1, [&] { return vmap_launch_insert(m, P, src); });       // the map holds the frame's voxels: odometry's steady state
         if (rc == 0) rc = std::min(vmap_finish_insert(m, &st), 0);
         if (rc == 0 && m->x_xyz.ensure(3 * (size_t)m->n_voxels + 3) != hipSuccess) rc = vmap_fail(m, -103, "out of memory");
-        timed(2, [&] {       // (with the clear of its counter, as in every extract call)
-            hipMemsetAsync(m->d_stats + vmap::kStExtract, 0, sizeof(unsigned long long), ctx->stream);
-            hipLaunchKernelGGL(vmap::k_vmap_extract, dim3((unsigned)((m->n_slots + 255) / 256)), dim3(256), 0, ctx->stream, m->table, m->n_slots, m->n_voxels,
-                               m->d_stats + vmap::kStExtract, m->x_xyz, (uint8_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
-            return 0;
-        });
-        timed(3, [&] {
+        timer.add(2, [&] { return vmap_launch_extract_scan(m); });         // (with the clear of its counter, as in every extract call)
+        timer.add(3, [&] {
             hipLaunchKernelGGL(r360::k_sphere_cloud_s4, dim3((cols + 1023) / 1024, rows), dim3(256), 0, ctx->stream, depth_dev, depth_step, depth_type, rows, cols,
                                convention, src.sin_theta, src.cos_theta, src.sin_phi, src.cos_phi, ctx->f_xyz);
             return 0;
         });
-        timed(4, [&] {       // the input bytes once through the device: the copy rate of the floor
+        timer.add(4, [&] {       // the input bytes once through the device: the copy rate of the floor
             hipMemcpy2DAsync(m->up_depth, drow, depth_dev, depth_step, drow, rows, hipMemcpyDeviceToDevice, ctx->stream);
             if (crow) hipMemcpy2DAsync(m->up_rgb, crow, rgb_dev, rgb_step, crow, rows, hipMemcpyDeviceToDevice, ctx->stream);
             return 0;
         });
     }
-    if (rc) {
-        (void)hipGetLastError();
-        return rc;
-    }
-    HIPC(m, hipGetLastError());
-    for (int k = 0; k < 5; ++k) avg_us[k] = (float)(sum[k] / reps);
-    return 0;
+    return timer.finish(avg_us, 5, reps);
 }

@@ -30,6 +30,11 @@ MAP_FULL = 3      # RGBD360_MAP_FULL
 MAP_MISMATCH = 4  # RGBD360_MAP_MISMATCH
 
 
+def _as_dict(st, skip=()):
+    """The fields of a ctypes struct by name."""
+    return {name: getattr(st, name) for name, _ in st._fields_ if name not in skip}
+
+
 class VoxelMap:
     def __init__(self, reg, leaf: float = 0.05, capacity: int = 1 << 20):
         """reg: the RegisterPhotoICP whose context (device, stream) the map lives on; its setters recreate the context, so configure
@@ -100,11 +105,12 @@ class VoxelMap:
     def _stats(self, rc, st):
         self.last_status = self._check(rc)
         self.full = rc == MAP_FULL
-        return {name: int(getattr(st, name)) for name, _ in _lib.MapStats._fields_}
+        return _as_dict(st)
 
     @staticmethod
-    def _sphere_args(what, rgb, depth, convention):
-        """The image arguments of the sphere entries in front of the pose(s); the arrays they point into come back with them."""
+    def _sphere_args(what, rgb, depth, convention, colour=True):
+        """The image arguments of the sphere entries in front of the pose(s) -- without the two of the colour image for the entries that
+        take none (colour=False); the arrays they point into come back with them."""
         d = np.asarray(depth)
         if d.dtype not in (np.uint16, np.float32) or d.ndim != 2:
             raise Rgbd360Error(f"VoxelMap.{what}: depth must be HxW uint16 millimetres or float32 metres")
@@ -117,8 +123,9 @@ class VoxelMap:
                 raise Rgbd360Error(f"VoxelMap.{what}: rgb must be HxWx3 uint8 of the depth image's size")
             if c.size and c.strides[1:] != (3, 1):
                 c = np.ascontiguousarray(c)
-        return (None if c is None else _ptr(c), 0 if c is None else c.strides[0], _ptr(d), d.strides[0], 0 if d.dtype == np.uint16 else 1, d.shape[0],
-                d.shape[1], int(convention)), (d, c)
+        args = (None if c is None else _ptr(c), 0 if c is None else c.strides[0], _ptr(d), d.strides[0], 0 if d.dtype == np.uint16 else 1, d.shape[0],
+                d.shape[1], int(convention))
+        return (args if colour else args[2:]), (d, c)
 
     @staticmethod
     def _cloud_args(what, xyz, rgb3):
@@ -151,7 +158,7 @@ class VoxelMap:
     def _edit_stats(self, rc, st):
         self.last_status = self._check(rc)
         self.mismatch = rc == MAP_MISMATCH
-        return {name: int(getattr(st, name)) for name, _ in _lib.MapEditStats._fields_}
+        return _as_dict(st)
 
     def remove_sphere(self, rgb, depth, pose, convention: int = 0):
         """Undoes insert_sphere of the same arguments (the same box, a map of the same leaf; that insert must not have been `full`), bit
@@ -175,7 +182,7 @@ class VoxelMap:
         removed = self._edit_stats(rc, est)
         self.mismatch = est.n_missing != 0 or est.n_underflow != 0
         self.full = st.n_dropped_full != 0
-        return removed, {name: int(getattr(st, name)) for name, _ in _lib.MapStats._fields_}
+        return removed, _as_dict(st)
 
     def move_sphere(self, rgb, depth, pose_old, pose_new, convention: int = 0):
         """The frame inserted at pose_old moves to pose_new: removed and inserted over one upload.  Returns (removal statistics, insert
@@ -202,21 +209,32 @@ class VoxelMap:
         """{n_slots, n_live, n_tombstones, n_points, n_inconsistent} of a read-only scan of the table."""
         c = _lib.MapCensus()
         self._check(self._L.rgbd360_map_census(self._handle(), C.byref(c)))
-        return {name: int(getattr(c, name)) for name, _ in _lib.MapCensus._fields_}
+        return _as_dict(c)
 
     # ---- alignment of a frame against the map (rgbd360_map_align_*; the reference's cloud ICP, OdometryRGBD360.cpp:98-114, 210-222)
-    def align_params(self, max_dist=None, max_iters=None, eps=None, min_count=None, min_matches=None):
-        """The defaults (max_dist = leaf, 10 iterations, eps 1e-6, min_count 1, min_matches 6) with the given fields replaced."""
-        p = _lib.MapAlignParams()
-        self._L.rgbd360_map_default_align_params(self._handle(), C.byref(p))
-        for name, v in (("max_dist", max_dist), ("max_iters", max_iters), ("eps", eps), ("min_count", min_count), ("min_matches", min_matches)):
+    def _params(self, struct_type, default_fn, **fields):
+        """The defaults of a parameter struct with the given fields replaced (None: the default stays)."""
+        p = struct_type()
+        default_fn(self._handle(), C.byref(p))
+        for name, v in fields.items():
+            if not hasattr(p, name):
+                raise TypeError(f"{struct_type.__name__} has no field {name!r}")
             if v is not None:
                 setattr(p, name, v)
         return p
 
-    def _align_result(self, rc, out, res):
-        self._check(rc)
-        r = {name: getattr(res, name) for name, _ in res._fields_ if name not in ("hessian", "gradient")}
+    def align_params(self, max_dist=None, max_iters=None, eps=None, min_count=None, min_matches=None):
+        """The defaults (max_dist = leaf, 10 iterations, eps 1e-6, min_count 1, min_matches 6) with the given fields replaced."""
+        return self._params(_lib.MapAlignParams, self._L.rgbd360_map_default_align_params, max_dist=max_dist, max_iters=max_iters, eps=eps,
+                            min_count=min_count, min_matches=min_matches)
+
+    def _align(self, entry, result_type, params, input_args, guess):
+        """One rgbd360_map_align_* call on a host input: (pose 4x4, the result struct as a dict)."""
+        g = pose_to_cm(guess)
+        out = np.zeros(16, np.float32)
+        res = result_type()
+        self._check(entry(self._handle(), *input_args, _ptr(g), 0, C.byref(params), _ptr(out), C.byref(res)))
+        r = _as_dict(res, skip=("hessian", "gradient"))
         r["hessian"] = np.array(res.hessian, np.float32).reshape(6, 6).T.copy()
         r["gradient"] = np.array(res.gradient, np.float32)
         return pose_from_cm(out), r
@@ -225,68 +243,33 @@ class VoxelMap:
         """Point-to-point ICP of the sphere frame `depth` (as in insert_sphere) against the map from `guess` (4x4 world <- frame); the
         nearest neighbour is the nearest voxel centroid within max_dist <= leaf.  Returns (pose 4x4, result dict with status,
         iterations, converged, the counters, n_matched, fitness, hessian, gradient).  The map is not changed."""
-        d = np.asarray(depth)
-        if d.dtype not in (np.uint16, np.float32) or d.ndim != 2:
-            raise Rgbd360Error("VoxelMap.align_sphere: depth must be HxW uint16 millimetres or float32 metres")
-        if d.size and d.strides[1] != d.dtype.itemsize:
-            d = np.ascontiguousarray(d)
-        p = self.align_params(**params)
-        g = pose_to_cm(guess)
-        out = np.zeros(16, np.float32)
-        res = _lib.MapAlignResult()
-        rc = self._L.rgbd360_map_align_sphere(self._handle(), _ptr(d), d.strides[0], 0 if d.dtype == np.uint16 else 1, d.shape[0], d.shape[1],
-                                              int(convention), _ptr(g), 0, C.byref(p), _ptr(out), C.byref(res))
-        return self._align_result(rc, out, res)
+        args, keep = self._sphere_args("align_sphere", None, depth, convention, colour=False)
+        return self._align(self._L.rgbd360_map_align_sphere, _lib.MapAlignResult, self.align_params(**params), args, guess)
 
     def align_cloud(self, xyz, guess, **params):
         """The same for a cloud xyz: n x 3 float32 in the frame's coordinates."""
         x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        p = self.align_params(**params)
-        g = pose_to_cm(guess)
-        out = np.zeros(16, np.float32)
-        res = _lib.MapAlignResult()
-        rc = self._L.rgbd360_map_align_cloud(self._handle(), _ptr(x), x.shape[0], _ptr(g), 0, C.byref(p), _ptr(out), C.byref(res))
-        return self._align_result(rc, out, res)
+        return self._align(self._L.rgbd360_map_align_cloud, _lib.MapAlignResult, self.align_params(**params), (_ptr(x), x.shape[0]), guess)
 
     # ---- point-to-plane (rgbd360_map_align_plane_*: the same matches, the residual along the normal of a plane fitted to the centroids
     #      of the occupied cells around the point; the plane cost of the reference's GICP call sites)
     def align_plane_params(self, max_dist=None, max_iters=None, eps=None, min_count=None, min_matches=None, min_support=None, max_flatness=None):
         """align_params' defaults, min_support = 5 and max_flatness = 0.05, with the given fields replaced."""
-        p = _lib.MapAlignPlaneParams()
-        self._L.rgbd360_map_default_align_plane_params(self._handle(), C.byref(p))
-        for name, v in (("max_dist", max_dist), ("max_iters", max_iters), ("eps", eps), ("min_count", min_count), ("min_matches", min_matches),
-                        ("min_support", min_support), ("max_flatness", max_flatness)):
-            if v is not None:
-                setattr(p, name, v)
-        return p
+        return self._params(_lib.MapAlignPlaneParams, self._L.rgbd360_map_default_align_plane_params, max_dist=max_dist, max_iters=max_iters, eps=eps,
+                            min_count=min_count, min_matches=min_matches, min_support=min_support, max_flatness=max_flatness)
 
     def align_sphere_plane(self, depth, guess, convention: int = 0, **params):
         """Point-to-plane ICP of the sphere frame `depth` against the map from `guess`: align_sphere's matches, each with the plane fitted
         to the centroids of the occupied cells around the point.  Returns (pose 4x4, result dict: align_sphere's fields -- n_matched counts
         the contributing points, fitness is the mean squared plane distance -- plus n_unsupported, n_nonplanar and fitness_point, the
         point-to-point fitness of the same matches).  The map is not changed."""
-        d = np.asarray(depth)
-        if d.dtype not in (np.uint16, np.float32) or d.ndim != 2:
-            raise Rgbd360Error("VoxelMap.align_sphere_plane: depth must be HxW uint16 millimetres or float32 metres")
-        if d.size and d.strides[1] != d.dtype.itemsize:
-            d = np.ascontiguousarray(d)
-        p = self.align_plane_params(**params)
-        g = pose_to_cm(guess)
-        out = np.zeros(16, np.float32)
-        res = _lib.MapAlignPlaneResult()
-        rc = self._L.rgbd360_map_align_plane_sphere(self._handle(), _ptr(d), d.strides[0], 0 if d.dtype == np.uint16 else 1, d.shape[0], d.shape[1],
-                                                    int(convention), _ptr(g), 0, C.byref(p), _ptr(out), C.byref(res))
-        return self._align_result(rc, out, res)
+        args, keep = self._sphere_args("align_sphere_plane", None, depth, convention, colour=False)
+        return self._align(self._L.rgbd360_map_align_plane_sphere, _lib.MapAlignPlaneResult, self.align_plane_params(**params), args, guess)
 
     def align_cloud_plane(self, xyz, guess, **params):
         """The same for a cloud xyz: n x 3 float32 in the frame's coordinates."""
         x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        p = self.align_plane_params(**params)
-        g = pose_to_cm(guess)
-        out = np.zeros(16, np.float32)
-        res = _lib.MapAlignPlaneResult()
-        rc = self._L.rgbd360_map_align_plane_cloud(self._handle(), _ptr(x), x.shape[0], _ptr(g), 0, C.byref(p), _ptr(out), C.byref(res))
-        return self._align_result(rc, out, res)
+        return self._align(self._L.rgbd360_map_align_plane_cloud, _lib.MapAlignPlaneResult, self.align_plane_params(**params), (_ptr(x), x.shape[0]), guess)
 
     def align_trace(self):
         """One record per step of the last align call of either kind: (n, sum_sq, update[6]) (rgbd360_map_align_eval, the diagnostics header)."""
@@ -300,12 +283,7 @@ class VoxelMap:
     #      panorama; the keyframe target of OdometryKeyFrame360.cpp with the whole map as the model)
     def render_params(self, min_count=None, near=None, splat=None, max_half=None):
         """The defaults (min_count 1, near = leaf, splat 1.0, max_half 8) with the given fields replaced."""
-        p = _lib.MapRenderParams()
-        self._L.rgbd360_map_default_render_params(self._handle(), C.byref(p))
-        for name, v in (("min_count", min_count), ("near", near), ("splat", splat), ("max_half", max_half)):
-            if v is not None:
-                setattr(p, name, v)
-        return p
+        return self._params(_lib.MapRenderParams, self._L.rgbd360_map_default_render_params, min_count=min_count, near=near, splat=splat, max_half=max_half)
 
     def render_sphere(self, rows: int, cols: int, pose, **params):
         """The map splatted into the full-sphere panorama of rows x cols at `pose` (4x4 world <- frame), the nearest voxel winning a
@@ -322,7 +300,7 @@ class VoxelMap:
         st = _lib.MapRenderStats()
         self._check(self._L.rgbd360_map_render_sphere(self._handle(), rows, cols, _ptr(g), C.byref(p), _ptr(depth), _ptr(rgb), _ptr(count), _ptr(key3),
                                                       C.byref(st)))
-        return depth, rgb, count, key3, {name: int(getattr(st, name)) for name, _ in _lib.MapRenderStats._fields_}
+        return depth, rgb, count, key3, _as_dict(st)
 
     # ---- read-out
     def __len__(self) -> int:

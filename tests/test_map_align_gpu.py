@@ -425,3 +425,20 @@ def test_odometry_replay_refines_on_the_map(reg, tmp_path):
         assert r[2:4] == ["status", "0"] and int(r[7]) > 5000 and float(r[9]) < 0.1 ** 2
     rows = np.loadtxt(str(tmp_path / "c.txt")).reshape(-1, 7)
     assert len(rows) > 1000 and int(rows[:, 6].sum()) == int(np.loadtxt(str(tmp_path / "a.txt")).reshape(-1, 7)[:, 6].sum())
+
+
+@pytest.mark.parametrize("form", ["f32_padded", "u16"])
+def test_an_alignment_from_host_and_from_device_memory_is_the_same(reg, hip_lib, form):
+    """The 1100 x 24 strip (map_input_forms.py: float32 depth with a padded row step, uint16 depth) aligned with on_device = 0 and 1: the
+    same pose bits and the same result struct."""
+    import map_input_forms as F
+    from rgbd360_amd import _lib
+    forms = F.Forms(reg)
+    try:
+        p = _lib.MapAlignParams()
+        hip_lib.rgbd360_map_default_align_params(None, C.byref(p))
+        p.max_dist = F.LEAF
+        host, dev = F.align_on_both(hip_lib, reg, forms, form, hip_lib.rgbd360_map_align_sphere, p, _lib.MapAlignResult)
+    finally:
+        forms.close()
+    assert host == dev

@@ -422,3 +422,21 @@ def test_odometry_replay_keeps_a_window_of_two_frames(reg, tmp_path):
         xyz, rgb, count, _ = fresh.extract()
     want = ["%.6f %.6f %.6f %d %d %d %d" % (x, y, z, r, g, b, n) for (x, y, z), (r, g, b), n in zip(xyz.tolist(), rgb.tolist(), count.tolist())]
     assert out.read_text().splitlines() == want and len(want) == int(lines[3][3]) > 1000
+
+
+@pytest.fixture(scope="module")
+def input_forms(reg):
+    import map_input_forms as F
+    forms = F.Forms(reg)
+    yield forms
+    forms.close()
+
+
+@pytest.mark.parametrize("op", ["remove", "move"])
+@pytest.mark.parametrize("form", ["f32_padded", "u16", "cloud"])
+def test_an_edit_from_host_and_from_device_memory_is_the_same(reg, hip_lib, input_forms, form, op):
+    """The 1100 x 24 strip (map_input_forms.py) removed from, or moved in, a map that holds it at two poses, with on_device = 0 and 1: the
+    same statistics of both kinds and the same map, byte for byte."""
+    import map_input_forms as F
+    host, dev = F.edit_on_both(hip_lib, reg, input_forms, form, op)
+    assert host == dev

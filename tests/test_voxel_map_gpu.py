@@ -360,3 +360,20 @@ def test_odometry_replay_writes_the_map(reg, tmp_path):
     assert min(np.linalg.norm(mean_point(x) - mean_point(ref)) for x in (at_identity, a_step_late)) > 0.01
     assert np.linalg.norm(got_mean - mean_point(ref)) < 5e-4
     assert abs(len(rows) - len(ref)) <= 0.02 * len(ref)
+
+
+@pytest.fixture(scope="module")
+def input_forms(reg):
+    import map_input_forms as F
+    forms = F.Forms(reg)
+    yield forms
+    forms.close()
+
+
+@pytest.mark.parametrize("form", ["f32_padded", "u16", "cloud"])
+def test_an_insert_from_host_and_from_device_memory_is_the_same(reg, hip_lib, input_forms, form):
+    """The 1100 x 24 strip (map_input_forms.py: padded row steps, uint16 without colour, the cloud) inserted with on_device = 0 and 1:
+    the same statistics and the same map, byte for byte."""
+    import map_input_forms as F
+    host, dev = F.edit_on_both(hip_lib, reg, input_forms, form, "insert")
+    assert host == dev
