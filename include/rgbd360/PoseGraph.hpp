@@ -1,0 +1,95 @@
+// rgbd360/PoseGraph.hpp -- the reference's GraphOptimizer (GraphOptimization/GraphOptimizer.h, GraphOptimizer_G2O.cpp: a thin wrapper
+// over g2o with Levenberg-Marquardt, a dense linear solver, optimize(10) and vertex 0 fixed) over the device pose-graph optimiser
+// (rgbd360_graph_*, ../rgbd360_hip.h).  Header-only, depends on the C ABI and on the PODs of RegisterPhotoICP.hpp; no g2o, no Eigen.
+// The call sites it serves, KFsphere_SLAM.cpp:262-265, 542-550, 630, 679-689:
+//     optimizer.addVertex(pose);                                              graph.addVertex(pose)            (vertex 0 is fixed)
+//     optimizer.addEdge(nearestKF, newKF, relPose, registerer.getInfoMat());  graph.addEdge(nearestKF, newKF, relPose, hessian)
+//     optimizer.optimizeGraph(); optimizer.getPoses(Map.vOptimizedPoses);     graph.optimizeGraph(); graph.getPoses(poses)
+// relPose is the pose FrameStore::align returns for target `from` and source `to`, the information matrix is rgbd360_result.hessian of the
+// same alignment, with no conversion (rgbd360_hip.h).  The optimised poses are what GlobalMap::move takes.
+#pragma once
+
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "RegisterPhotoICP.hpp"
+
+namespace rgbd360 {
+
+class PoseGraph {
+   public:
+    // The graph lives on align's context (device, stream): keep `align` alive and its setters untouched while the graph exists.
+    explicit PoseGraph(RegisterPhotoICP& align) {
+        rgbd360_ctx* ctx = align.context();
+        const int rc = rgbd360_graph_create(ctx, &g_);
+        if (rc != 0) throw std::runtime_error("rgbd360_graph_create (" + std::to_string(rc) + "): " + rgbd360_last_error(ctx));
+        rgbd360_graph_default_params(&params_);
+    }
+    ~PoseGraph() { rgbd360_graph_destroy(g_); }
+    PoseGraph(const PoseGraph&) = delete;
+    PoseGraph& operator=(const PoseGraph&) = delete;
+
+    // Returns the vertex's index.  The first vertex is fixed (GraphOptimizer_G2O.cpp:46); pass fixed = true to pin another.
+    int addVertex(const Mat4f& pose, bool fixed = false) {
+        const uint8_t f = fixed || numVertices() == 0 ? 1 : 0;
+        return check(rgbd360_graph_add_vertices(g_, 1, pose.m, &f), "rgbd360_graph_add_vertices");
+    }
+    // relativePose: frame `to` in frame `from`; informationMatrix: the 6x6 Hessian of that alignment (translation first).
+    void addEdge(int from, int to, const Mat4f& relativePose, const Mat6f& informationMatrix) {
+        check(rgbd360_graph_add_edges(g_, 1, &from, &to, relativePose.m, informationMatrix.m), "rgbd360_graph_add_edges");
+    }
+    void addEdge(int from, int to, const Mat4f& relativePose) {      // identity information
+        check(rgbd360_graph_add_edges(g_, 1, &from, &to, relativePose.m, nullptr), "rgbd360_graph_add_edges");
+    }
+    // The Hessian of an alignment result as the information matrix of its edge
+    static Mat6f information(const rgbd360_result& r) {
+        Mat6f I;
+        for (int k = 0; k < 36; ++k) I.m[k] = r.hessian[k];
+        return I;
+    }
+    void setPose(int vertex, const Mat4f& pose) { check(rgbd360_graph_set_poses(g_, vertex, 1, pose.m), "rgbd360_graph_set_poses"); }
+    void setFixed(int vertex, bool fixed) {
+        const uint8_t f = fixed ? 1 : 0;
+        check(rgbd360_graph_set_fixed(g_, vertex, 1, &f), "rgbd360_graph_set_fixed");
+    }
+    int numVertices() const { return rgbd360_graph_n_vertices(g_); }
+    int numEdges() const { return rgbd360_graph_n_edges(g_); }
+    void clear() { check(rgbd360_graph_clear(g_), "rgbd360_graph_clear"); }
+
+    rgbd360_graph_params& params() { return params_; }      // max_iters 10 (the reference's optimize(10)), ...
+    // true: RGBD360_OK; false: RGBD360_ILL_POSED (result().status).  The poses are the last accepted ones either way.
+    bool optimizeGraph() {
+        const int rc = check(rgbd360_graph_optimize(g_, &params_, &result_), "rgbd360_graph_optimize");
+        return rc == RGBD360_OK;
+    }
+    void getPoses(std::vector<Mat4f>& poses) {
+        poses.resize((size_t)numVertices());
+        if (!poses.empty()) check(rgbd360_graph_get_poses(g_, 0, (int)poses.size(), poses[0].m), "rgbd360_graph_get_poses");
+    }
+    const rgbd360_graph_result& result() const { return result_; }
+    double chi2() {
+        double c = 0.0;
+        check(rgbd360_graph_chi2(g_, &c, nullptr), "rgbd360_graph_chi2");
+        return c;
+    }
+    std::vector<rgbd360_graph_iteration> trace() {
+        int n = 0;
+        check(rgbd360_graph_get_trace(g_, 0, &n, nullptr), "rgbd360_graph_get_trace");
+        std::vector<rgbd360_graph_iteration> t((size_t)n);
+        if (n) check(rgbd360_graph_get_trace(g_, n, nullptr, t.data()), "rgbd360_graph_get_trace");
+        return t;
+    }
+    rgbd360_graph* handle() { return g_; }
+
+   private:
+    int check(int rc, const char* what) {
+        if (rc < 0) throw std::runtime_error(std::string(what) + " (" + std::to_string(rc) + "): " + rgbd360_graph_last_error(g_));
+        return rc;
+    }
+    rgbd360_graph* g_ = nullptr;
+    rgbd360_graph_params params_{};
+    rgbd360_graph_result result_{};
+};
+
+}  // namespace rgbd360

@@ -468,6 +468,85 @@ int    rgbd360_map_render_sphere_dev(rgbd360_map* map, int rows, int cols, const
                                      float* depth_dev, uint8_t* rgb_dev, int32_t* count_dev, int32_t* key3_dev,
                                      rgbd360_map_render_stats* stats_dev);
 
+/* ---- pose-graph optimisation of store edges (csrc/pose_graph.h) -----------------------------------------------------------------
+ * The reference closes its SLAM loop in g2o: optimizer.addVertex(pose), optimizer.addEdge(nearestKF, newKF, relPose, registerer.getInfoMat()),
+ * optimizer.optimizeGraph(), optimizer.getPoses(...) (KFsphere_SLAM.cpp:262-265, 542-550, 630, 679-689; GraphOptimizer_G2O.cpp:
+ * Levenberg-Marquardt, dense linear solver, optimize(10), vertex 0 fixed).  Here that step runs on the device: the edges are what
+ * rgbd360_store_align returns, the optimised poses are what rgbd360_map_move_* takes.
+ *   vertices   poses T_v (world <- frame): 16 floats column-major in and out, held in float64; each with a `fixed` flag.
+ *   edges      (i, j, Z, Omega): Z (16 floats) is frame j in frame i -- the pose rgbd360_store_align returns for target i and source j;
+ *              Omega (36 floats column-major) is used as (Omega + Omega^T) / 2 in float64, NULL = identity.
+ *   tangent    (v; w), translation first, as everywhere in csrc/gn_math.h; updates multiply on the left: T_v <- se3_exp(x_v) T_v with the
+ *              full exponential gn::se3_exp in float64.
+ *   residual   E = Z T_j^-1 T_i, r = se3_log(E), the inverse of gn::se3_exp: a = vee of the antisymmetric part of R, the angle
+ *              atan2(|a|, (tr R - 1) / 2); finite for every input, accurate for angles <= 3 rad.  T^-1 is the rigid inverse (R^T, -R^T t).
+ *              r is the left perturbation xi in Z = exp(xi) T_i^-1 T_j: the tangent in which the dense alignment forms its Hessian
+ *              (gn::step: exp(u) pose; its pseudo-exponential differs at second order only).  So rgbd360_result.hessian IS the
+ *              information matrix of the edge, with no conversion.
+ *   Jacobians  dr/dx_i = A = J_l^-1(r) Ad(Z T_j^-1), dr/dx_j = -A; J_l^-1 = I - ad/2 + ad^2/12 - ad^4/720 + ad^6/30240,
+ *              ad(r) = [ [w]x [v]x ; 0 [w]x ] (truncation below 3e-9 for |r| <= 0.5).  Per edge W = A^T Omega A and b = A^T Omega r:
+ *              H gains +W at (i,i) and (j,j), -W at (i,j) and (j,i); g gains +b at i, -b at j.
+ *   cost, loop chi2 = sum r^T Omega r.  Levenberg-Marquardt with the damping of the dense alignment, H + lambda diag(H): lambda starts at
+ *              lambda_init (1e-3), is divided by 10 after an accepted step (not below 1e-9) and multiplied by 10 after a rejected one
+ *              (RegisterRGBD360.h:389).  A step is accepted iff chi2 at the trial poses is smaller than chi2 at the current ones; a
+ *              rejected step leaves the poses unchanged.  The loop ends after max_iters iterations (10: the reference's optimize(10)),
+ *              after an accepted step with max |x| <= tol_update (converged), or with RGBD360_ILL_POSED when lambda > lambda_max or a
+ *              damped 6x6 diagonal block has no Cholesky factor.
+ *   vertices   a fixed vertex has x_v = 0; a vertex without edges is treated as fixed and counted (n_isolated); at least one vertex must
+ *              be flagged fixed (-1 otherwise).
+ *   solve      (H + lambda diag H) x = -g by conjugate gradients in float64, matrix-free over the edge list (q_i += W (p_i - p_j),
+ *              q_j -= the same, plus lambda diag(H) p), preconditioned with the inverse of the damped 6x6 diagonal blocks; it ends at
+ *              |r|_M <= cg_tol |r_0|_M, after cg_max_iters iterations, or when p.q is not positive.  The iteration count of block-Jacobi
+ *              grows with the graph's diameter.
+ *   sums       no floating-point atomics: a vertex adds its edges in edge-list order, every global scalar is a table of per-workgroup rows
+ *              added in ascending order -- two calls on equal graphs give equal bits.
+ * The host builds and uploads the incidence lists and edge arrays only when the graph changed; one stream synchronisation per
+ * Levenberg-Marquardt iteration.  A graph is destroyed BEFORE its context and used from one thread at a time.
+ * Out of scope: robust kernels, removing single edges, marginalisation, incremental solving, SE(2), landmarks, several GPUs, a stronger
+ * preconditioner. */
+typedef struct rgbd360_graph rgbd360_graph;
+typedef struct {
+    int    max_iters;          /* Levenberg-Marquardt iterations, 0 .. 10000: 10 */
+    int    cg_max_iters;       /* per solve, 1 .. 100000: 400 */
+    double tol_update;         /* on max |x| of an accepted step: 1e-6 */
+    double lambda_init;        /* 1e-3 */
+    double lambda_max;         /* 1e30 */
+    double cg_tol;             /* 1e-8 */
+} rgbd360_graph_params;
+typedef struct {
+    int status, iterations, accepted, converged;      /* RGBD360_OK / ILL_POSED; trace records; accepted steps; 1: ended on tol_update */
+    double chi2_initial, chi2_final, lambda_final;
+    long long cg_iterations;                           /* over all solves */
+    int n_fixed, n_isolated;
+} rgbd360_graph_result;
+/* one Levenberg-Marquardt iteration: chi2 at the current poses, at the trial poses, the lambda of the solve, 1 when the step was taken,
+ * the solve's iterations and |r|_M / |r_0|_M, max |x| of the step */
+typedef struct { double chi2, chi2_trial, lambda; int accepted, cg_iterations; double cg_residual, max_update; } rgbd360_graph_iteration;
+int  rgbd360_graph_create(rgbd360_ctx* ctx, rgbd360_graph** out);
+void rgbd360_graph_destroy(rgbd360_graph* g);
+const char* rgbd360_graph_last_error(rgbd360_graph* g);
+/* n vertices; fixed: n bytes, NULL = none fixed.  Returns the index of the first new vertex; -1 (nothing added) for a negative n, a NULL
+ * pose array or a non-finite entry (the message names the first such vertex of the call). */
+int  rgbd360_graph_add_vertices(rgbd360_graph* g, int n, const float* poses, const uint8_t* fixed);
+/* n edges from[k] -> to[k].  0; -1 and nothing added when an index is no vertex, from == to, an entry is not finite or the information
+ * matrix has a non-positive diagonal entry (the message names the first such edge of the call).  Repeated edges and from > to are allowed. */
+int  rgbd360_graph_add_edges(rgbd360_graph* g, int n, const int* from, const int* to, const float* rel_poses, const float* information);
+int  rgbd360_graph_set_poses(rgbd360_graph* g, int first, int n, const float* poses);
+int  rgbd360_graph_set_fixed(rgbd360_graph* g, int first, int n, const uint8_t* fixed);
+int  rgbd360_graph_n_vertices(const rgbd360_graph* g);
+int  rgbd360_graph_n_edges(const rgbd360_graph* g);
+int  rgbd360_graph_clear(rgbd360_graph* g);
+void rgbd360_graph_default_params(rgbd360_graph_params* p);
+/* Returns the status (>= 0, also in result->status; result may be NULL); -1: bad parameters or no fixed vertex, nothing launched.  A graph
+ * without vertices, edges or free vertices returns RGBD360_OK with 0 iterations. */
+int  rgbd360_graph_optimize(rgbd360_graph* g, const rgbd360_graph_params* params, rgbd360_graph_result* result);
+int  rgbd360_graph_get_poses(rgbd360_graph* g, int first, int n, float* out);
+/* chi2 at the current poses (the bits rgbd360_graph_optimize reports as chi2_initial from there); per_edge (may be NULL): r^T Omega r of
+ * every edge. */
+int  rgbd360_graph_chi2(rgbd360_graph* g, double* chi2, double* per_edge);
+/* the first min(max_trace, iterations) records of the last rgbd360_graph_optimize; *n_trace (may be NULL): iterations */
+int  rgbd360_graph_get_trace(rgbd360_graph* g, int max_trace, int* n_trace, rgbd360_graph_iteration* trace);
+
 /* ---- one process, several GPUs (BASELINE.json configs[3]) ---------------------------------------------------
  * The sequence path shards by independent frame pairs: device d gets the contiguous pairs rgbd360_shard_range(n_frames-1, d,
  * n_gpus) and therefore the frames lo..hi (one boundary frame is shared by two neighbours); one host thread per device drives

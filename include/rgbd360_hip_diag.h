@@ -136,6 +136,18 @@ int rgbd360_map_plane_fit(const double cov[6], double max_flatness, double norma
 int rgbd360_map_time_align_plane(rgbd360_map* map, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
                                  const float pose[16], const rgbd360_map_align_plane_params* params, int reps, float avg_us[4], double* probes);
 
+/* The pose graph's linearisation at its current poses (rgbd360_graph_*, rgbd360_hip.h): per edge r (6 doubles) and A = dr/dx_i (36
+ * doubles, column-major), either may be NULL.  The graph is not changed. */
+int rgbd360_graph_linearize(rgbd360_graph* g, double* r, double* A);
+/* y = (H + lambda diag H) x of that linearisation through the optimiser's own kernels (edge product and per-vertex gather): x and y hold
+ * 6 doubles per vertex of the graph; the entries of fixed and isolated vertices are read as 0 and written as 0. */
+int rgbd360_graph_apply(rgbd360_graph* g, double lambda, const double* x, double* y);
+/* The optimiser's kernels under HIP events at the current poses, averages over `reps` launches in microseconds: avg_us[0] the
+ * linearisation, [1] the per-vertex assembly, [2] - [5] the four launches of a conjugate-gradient iteration (edge product, gather,
+ * update, direction), [6] the trial poses, [7] chi2 at the trial poses, [8] the decision, [9] one of those launches returning at once on
+ * the state word.  The poses are not changed. */
+int rgbd360_graph_time_kernels(rgbd360_graph* g, int reps, float avg_us[10]);
+
 /* The render's kernels (rgbd360_map_render_*, rgbd360_hip.h) under HIP events, averages over `reps` back-to-back launches in
  * microseconds: avg_us[0] k_vmap_render_depth, [1] k_vmap_render_key, [2] k_vmap_render_resolve (all four planes), [3] the whole
  * rgbd360_map_render_sphere_dev sequence (the clears and the three passes), [4] ONE k_vmap_extract launch (centroids only) over the

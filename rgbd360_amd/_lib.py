@@ -37,6 +37,10 @@ SYMBOLS = [
     "rgbd360_map_default_align_plane_params", "rgbd360_map_align_plane_sphere", "rgbd360_map_align_plane_cloud", "rgbd360_map_align_plane_eval",
     "rgbd360_map_plane_fit", "rgbd360_map_time_align_plane",
     "rgbd360_map_default_render_params", "rgbd360_map_render_sphere", "rgbd360_map_render_sphere_dev", "rgbd360_map_time_render",
+    "rgbd360_graph_create", "rgbd360_graph_destroy", "rgbd360_graph_last_error", "rgbd360_graph_add_vertices", "rgbd360_graph_add_edges",
+    "rgbd360_graph_set_poses", "rgbd360_graph_set_fixed", "rgbd360_graph_n_vertices", "rgbd360_graph_n_edges", "rgbd360_graph_clear",
+    "rgbd360_graph_default_params", "rgbd360_graph_optimize", "rgbd360_graph_get_poses", "rgbd360_graph_chi2", "rgbd360_graph_get_trace",
+    "rgbd360_graph_linearize", "rgbd360_graph_apply", "rgbd360_graph_time_kernels",
 ]
 
 
@@ -116,6 +120,22 @@ class MapRenderParams(C.Structure):     # rgbd360_map_render_params
 
 class MapRenderStats(C.Structure):      # rgbd360_map_render_stats
     _fields_ = [(n, C.c_longlong) for n in ("n_voxels", "n_below_min_count", "n_near", "n_splatted", "n_pixels_covered")]
+
+
+class GraphParams(C.Structure):         # rgbd360_graph_params
+    _fields_ = [("max_iters", C.c_int), ("cg_max_iters", C.c_int), ("tol_update", C.c_double), ("lambda_init", C.c_double),
+                ("lambda_max", C.c_double), ("cg_tol", C.c_double)]
+
+
+class GraphResult(C.Structure):         # rgbd360_graph_result
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("accepted", C.c_int), ("converged", C.c_int), ("chi2_initial", C.c_double),
+                ("chi2_final", C.c_double), ("lambda_final", C.c_double), ("cg_iterations", C.c_longlong), ("n_fixed", C.c_int),
+                ("n_isolated", C.c_int)]
+
+
+class GraphIteration(C.Structure):      # rgbd360_graph_iteration
+    _fields_ = [("chi2", C.c_double), ("chi2_trial", C.c_double), ("lambda_", C.c_double), ("accepted", C.c_int), ("cg_iterations", C.c_int),
+                ("cg_residual", C.c_double), ("max_update", C.c_double)]
 
 
 class PbmapParams(C.Structure):
@@ -320,5 +340,26 @@ def load() -> C.CDLL:
     L.rgbd360_map_render_sphere.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRenderParams), vp, vp, vp, vp, C.POINTER(MapRenderStats)]
     L.rgbd360_map_render_sphere_dev.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRenderParams), vp, vp, vp, vp, vp]
     L.rgbd360_map_time_render.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRenderParams), i32, i32, vp, C.POINTER(MapRenderStats), C.POINTER(ll)]
+    L.rgbd360_graph_create.argtypes = [vp, C.POINTER(vp)]
+    L.rgbd360_graph_destroy.argtypes = [vp]
+    L.rgbd360_graph_destroy.restype = None
+    L.rgbd360_graph_last_error.argtypes = [vp]
+    L.rgbd360_graph_last_error.restype = C.c_char_p
+    L.rgbd360_graph_add_vertices.argtypes = [vp, i32, f32p, vp]
+    L.rgbd360_graph_add_edges.argtypes = [vp, i32, vp, vp, f32p, f32p]
+    L.rgbd360_graph_set_poses.argtypes = [vp, i32, i32, f32p]
+    L.rgbd360_graph_set_fixed.argtypes = [vp, i32, i32, vp]
+    L.rgbd360_graph_n_vertices.argtypes = [vp]
+    L.rgbd360_graph_n_edges.argtypes = [vp]
+    L.rgbd360_graph_clear.argtypes = [vp]
+    L.rgbd360_graph_default_params.argtypes = [C.POINTER(GraphParams)]
+    L.rgbd360_graph_default_params.restype = None
+    L.rgbd360_graph_optimize.argtypes = [vp, C.POINTER(GraphParams), C.POINTER(GraphResult)]
+    L.rgbd360_graph_get_poses.argtypes = [vp, i32, i32, f32p]
+    L.rgbd360_graph_chi2.argtypes = [vp, C.POINTER(C.c_double), vp]
+    L.rgbd360_graph_get_trace.argtypes = [vp, i32, C.POINTER(i32), vp]
+    L.rgbd360_graph_linearize.argtypes = [vp, vp, vp]
+    L.rgbd360_graph_apply.argtypes = [vp, C.c_double, vp, vp]
+    L.rgbd360_graph_time_kernels.argtypes = [vp, i32, vp]
     _lib = L
     return L

@@ -298,4 +298,119 @@ GN_HD inline bool lm_update(const float* H, const float* g, float lambda, const 
     return true;
 }
 
+// ---- float64 SE(3) pieces of the pose graph (pose_graph.h; rgbd360_graph_*).  Tangent order (v; w) as above; 4x4 and
+// 6x6 matrices column-major.  Only + - x / sqrt, sin, cos and atan2: the host build and the numpy restatement agree to rounding.
+
+// C = A B, 6x6
+GN_HD inline void mat6_mul(const double* A, const double* B, double* C) {
+    for (int c = 0; c < 6; ++c)
+        for (int r = 0; r < 6; ++r) {
+            double s = 0.0;
+            for (int k = 0; k < 6; ++k) s += A[k * 6 + r] * B[c * 6 + k];
+            C[c * 6 + r] = s;
+        }
+}
+
+// C = A B for rigid 4x4 transforms (the last row is taken to be 0 0 0 1 and written so)
+GN_HD inline void rigid_mul(const double* A, const double* B, double* C) {
+    for (int c = 0; c < 4; ++c) {
+        for (int r = 0; r < 3; ++r) {
+            double s = (A[0 * 4 + r] * B[c * 4 + 0] + A[1 * 4 + r] * B[c * 4 + 1]) + A[2 * 4 + r] * B[c * 4 + 2];
+            if (c == 3) s += A[12 + r];
+            C[c * 4 + r] = s;
+        }
+        C[c * 4 + 3] = c == 3 ? 1.0 : 0.0;
+    }
+}
+
+// the rigid inverse (R^T, -R^T t): R is taken to be a rotation, which is not checked
+GN_HD inline void rigid_inv(const double* T, double* I) {
+    for (int c = 0; c < 3; ++c) {
+        for (int r = 0; r < 3; ++r) I[c * 4 + r] = T[r * 4 + c];
+        I[c * 4 + 3] = 0.0;
+    }
+    for (int r = 0; r < 3; ++r) I[12 + r] = -((T[r * 4 + 0] * T[12] + T[r * 4 + 1] * T[13]) + T[r * 4 + 2] * T[14]);
+    I[15] = 1.0;
+}
+
+// r = se3_log(E), the inverse of se3_exp.  Rotation: a = vee of the antisymmetric part of R, angle = atan2(|a|, (tr R - 1) / 2),
+// w = (angle / |a|) a; |a| < 1e-4: the arcsine series when the cosine is positive, otherwise (within 1e-4 rad of pi) the axis from the
+// symmetric part of R, its sign from a.  Translation: v = t - (w x t) / 2 + D w x (w x t), D = (1 - A / (2 B)) / angle^2 with se3_exp's
+// A and B, its series below angle^2 < 1e-2.  Finite for every finite input; accurate to rounding for angles <= 3 rad.
+GN_HD inline void se3_log(const double* E, double* r) {
+    const double ax = 0.5 * (E[6] - E[9]), ay = 0.5 * (E[8] - E[2]), az = 0.5 * (E[1] - E[4]);
+    const double s = sqrt((ax * ax + ay * ay) + az * az);
+    const double c = 0.5 * (((E[0] + E[5]) + E[10]) - 1.0);
+    const double angle = atan2(s, c);
+    double wx, wy, wz;
+    if (s >= 1e-4) {
+        const double f = angle / s;
+        wx = f * ax; wy = f * ay; wz = f * az;
+    } else if (c > 0.0) {
+        const double f = 1.0 + (s * s) / 6.0;
+        wx = f * ax; wy = f * ay; wz = f * az;
+    } else {
+        const double d[3] = {E[0] - c, E[5] - c, E[10] - c};
+        const int k = d[0] >= d[1] ? (d[0] >= d[2] ? 0 : 2) : (d[1] >= d[2] ? 1 : 2);
+        const double om = 1.0 - c;
+        double n[3];
+        n[k] = sqrt((d[k] > 0.0 ? d[k] : 0.0) / om);
+        for (int m = 0; m < 3; ++m)
+            if (m != k) n[m] = n[k] > 0.0 ? 0.5 * (E[m * 4 + k] + E[k * 4 + m]) / (om * n[k]) : 0.0;
+        const double sign = (n[0] * ax + n[1] * ay) + n[2] * az < 0.0 ? -1.0 : 1.0;
+        wx = sign * angle * n[0]; wy = sign * angle * n[1]; wz = sign * angle * n[2];
+    }
+    const double th2 = (wx * wx + wy * wy) + wz * wz;
+    double D;
+    if (th2 < 1e-2) {
+        D = ((th2 / 1209600.0 + 1.0 / 30240.0) * th2 + 1.0 / 720.0) * th2 + 1.0 / 12.0;
+    } else {
+        const double th = sqrt(th2);
+        const double A = sin(th) / th, B = (1.0 - cos(th)) / th2;
+        D = (1.0 - A / (2.0 * B)) / th2;
+    }
+    const double tx = E[12], ty = E[13], tz = E[14];
+    const double cx = wy * tz - wz * ty, cy = wz * tx - wx * tz, cz = wx * ty - wy * tx;
+    const double dx = wy * cz - wz * cy, dy = wz * cx - wx * cz, dz = wx * cy - wy * cx;
+    r[0] = (tx - 0.5 * cx) + D * dx;
+    r[1] = (ty - 0.5 * cy) + D * dy;
+    r[2] = (tz - 0.5 * cz) + D * dz;
+    r[3] = wx; r[4] = wy; r[5] = wz;
+}
+
+// Ad(T) = [ R  [t]x R ; 0  R ]: se3_exp(Ad(T) x) = T se3_exp(x) T^-1
+GN_HD inline void se3_adjoint(const double* T, double* Ad) {
+    const double t[3] = {T[12], T[13], T[14]};
+    for (int c = 0; c < 3; ++c) {
+        const double R0 = T[c * 4 + 0], R1 = T[c * 4 + 1], R2 = T[c * 4 + 2];
+        Ad[c * 6 + 0] = R0; Ad[c * 6 + 1] = R1; Ad[c * 6 + 2] = R2;
+        Ad[c * 6 + 3] = 0.0; Ad[c * 6 + 4] = 0.0; Ad[c * 6 + 5] = 0.0;
+        Ad[(c + 3) * 6 + 0] = t[1] * R2 - t[2] * R1;
+        Ad[(c + 3) * 6 + 1] = t[2] * R0 - t[0] * R2;
+        Ad[(c + 3) * 6 + 2] = t[0] * R1 - t[1] * R0;
+        Ad[(c + 3) * 6 + 3] = R0; Ad[(c + 3) * 6 + 4] = R1; Ad[(c + 3) * 6 + 5] = R2;
+    }
+}
+
+// The inverse left Jacobian of SE(3) at r: se3_log(se3_exp(d) se3_exp(r)) = r + J d + O(d^2).  The series
+// J = I - ad/2 + ad^2/12 - ad^4/720 + ad^6/30240 with ad(r) = [ [w]x [v]x ; 0 [w]x ] (truncation below 3e-9 for |r| <= 0.5).
+GN_HD inline void se3_jl_inv(const double* r, double* J) {
+    double ad[36], a2[36], a4[36], a6[36];
+    for (int k = 0; k < 36; ++k) ad[k] = 0.0;
+    const double v[3] = {r[0], r[1], r[2]}, w[3] = {r[3], r[4], r[5]};
+    // [u]x column-major: column 0 = (0, u2, -u1), column 1 = (-u2, 0, u0), column 2 = (u1, -u0, 0)
+    for (int blk = 0; blk < 3; ++blk) {
+        const double* u = blk == 1 ? v : w;
+        const int r0 = blk == 2 ? 3 : 0, c0 = blk == 0 ? 0 : 3;
+        ad[(c0 + 0) * 6 + r0 + 1] = u[2];  ad[(c0 + 0) * 6 + r0 + 2] = -u[1];
+        ad[(c0 + 1) * 6 + r0 + 0] = -u[2]; ad[(c0 + 1) * 6 + r0 + 2] = u[0];
+        ad[(c0 + 2) * 6 + r0 + 0] = u[1];  ad[(c0 + 2) * 6 + r0 + 1] = -u[0];
+    }
+    mat6_mul(ad, ad, a2);
+    mat6_mul(a2, a2, a4);
+    mat6_mul(a4, a2, a6);
+    for (int k = 0; k < 36; ++k)
+        J[k] = ((((k % 7 == 0 ? 1.0 : 0.0) - 0.5 * ad[k]) + a2[k] / 12.0) - a4[k] / 720.0) + a6[k] / 30240.0;
+}
+
 }  // namespace gn

@@ -1949,5 +1949,6 @@ void rgbd360_ctx_set_error(rgbd360_ctx* ctx, const char* msg) { ctx->err = msg ?
 
 #include "map_render.h"
 #include "frame_store.h"
+#include "pose_graph.h"
 #include "multi_gpu.h"
 
