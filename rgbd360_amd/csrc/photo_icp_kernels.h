@@ -22,14 +22,12 @@
 #include "device_math.h"
 #include "gn_math.h"
 #include "libm_f32.h"
+#include "partial_row.h"
 
 namespace r360 {
 
 constexpr float  kInvalidPoint = -10000.f;      // RPI.h:40
 constexpr int    kEvalThreads = 1024;
-constexpr int    kNumPartials = 32;             // doubles per block partial
-// partial slots
-enum { P_H = 0 /*21*/, P_G = 21 /*6*/, P_E2P = 27, P_E2D = 28, P_NP = 29, P_ND = 30, P_NVIS = 31 };
 
 struct F3 {
     float a, b, c;

@@ -16,6 +16,10 @@ namespace r360 {
 struct PinK {
     float fx, fy, ox, oy;     // intrinsics of the pyramid level (RPI.h:571-575)
 };
+inline PinK level_K(const float cam[4], int level) {      // full-resolution (fx, fy, ox, oy) at a level: RPI.h:571-575, 4916-4920
+    const float scaleFactor = 1.0 / pow(2, level);
+    return {cam[0] * scaleFactor, cam[1] * scaleFactor, cam[2] * scaleFactor, cam[3] * scaleFactor};
+}
 
 // RPI.h:4277-4300: source record {x, y, z, Isrc}; x = -10000 marks a depth outside (min_depth, max_depth)
 __global__ void k_src_rec_pinhole(const float* __restrict__ depth, const float* __restrict__ gray, int rows, int cols, PinK K,

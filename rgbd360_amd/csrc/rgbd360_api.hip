@@ -33,6 +33,7 @@
 #include "pinhole_kernels.h"
 #include "warp_images.h"
 #include "f360_state.h"
+#include "lm_host.h"
 
 using namespace r360;
 
@@ -1053,19 +1054,11 @@ int rgbd360_eval_occ(rgbd360_ctx* ctx, int level, const float pose[16], int meth
     const GNState& S = *ctx->h_state;
     if (err2) *err2 = S.tot[P_E2P] + S.tot[P_E2D];
     if (n_valid) *n_valid = (long long)(S.tot[P_NP] + S.tot[P_ND]);
-    if (err2_split) { err2_split[0] = S.tot[P_E2P]; err2_split[1] = S.tot[P_E2D]; }
-    if (n_split) { n_split[0] = (long long)S.tot[P_NP]; n_split[1] = (long long)S.tot[P_ND]; }
-    if (H) memcpy(H, S.H, sizeof(float) * 36);
+    lm::Sums T;
+    T.add_row(S.tot);
+    T.write(err2_split, n_split, nullptr, nullptr, H64, g64, n_visible);
+    if (H) memcpy(H, S.H, sizeof(float) * 36);      // the device solve's own float H, g
     if (g) memcpy(g, S.g, sizeof(float) * 6);
-    if (H64 || g64) {
-        int k = 0;
-        for (int a = 0; a < 6; ++a)
-            for (int b = a; b < 6; ++b, ++k)
-                if (H64) H64[b * 6 + a] = H64[a * 6 + b] = S.tot[P_H + k];
-        if (g64)
-            for (int a = 0; a < 6; ++a) g64[a] = S.tot[P_G + a];
-    }
-    if (n_visible) *n_visible = (long long)S.tot[P_NVIS];
     return 0;
 }
 
@@ -1496,10 +1489,6 @@ int rgbd360_selftest_libm(rgbd360_ctx* ctx, uint32_t first_bits, uint32_t count,
 // Per-pixel passes on the device (pinhole_kernels.h), Levenberg-Marquardt driver on the host.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
-PinK pin_level_K(const rgbd360_ctx* ctx, int level) {         // RPI.h:571-575
-    const float scaleFactor = 1.0 / pow(2, level);
-    return {ctx->cam[0] * scaleFactor, ctx->cam[1] * scaleFactor, ctx->cam[2] * scaleFactor, ctx->cam[3] * scaleFactor};
-}
 
 int pin_check(rgbd360_ctx* ctx, int level, int method) {
     int rc = check_args(ctx, level, method);
@@ -1512,7 +1501,7 @@ int pin_check(rgbd360_ctx* ctx, int level, int method) {
 int pin_prepare_level(rgbd360_ctx* ctx, int level) {
     Level& L = ctx->levels[level];
     HIPC(ctx, L.srcRecPin.ensure((size_t)L.n));
-    const PinK K = pin_level_K(ctx, level);
+    const PinK K = level_K(ctx->cam, level);
     const float inv_fx = 1. / K.fx, inv_fy = 1. / K.fy;
     hipLaunchKernelGGL(k_src_rec_pinhole, grid2d(L.rows, L.cols), dim3(256), 0, ctx->stream, L.depthSrc, L.graySrc, L.rows, L.cols, K,
                        inv_fx, inv_fy, ctx->p.min_depth, ctx->p.max_depth, L.srcRecPin.get());
@@ -1530,7 +1519,7 @@ LevelDev pin_level_dev(const Level& L) {
 int pin_eval(rgbd360_ctx* ctx, int level, const float* pose, int method) {
     const Level& L = ctx->levels[level];
     const LevelDev lv = pin_level_dev(L);
-    const PinK K = pin_level_K(ctx, level);
+    const PinK K = level_K(ctx->cam, level);
     const EvalConsts ec = eval_consts(ctx->p);
     // two launches per evaluation: the pass (pose by kernel argument) and the reduce-only solve, which publishes the sums to the
     // host itself (was: state initialisation + pass + solve + copy, 21 us per round trip)
@@ -1569,7 +1558,7 @@ int pin_eval_occ(rgbd360_ctx* ctx, int level, const float* pose, int method, int
     int rc = pin_occ_ensure(ctx, (size_t)ctx->levels[0].n);
     if (rc) return rc;
     const LevelDev lv = pin_level_dev(L);
-    const PinK K = pin_level_K(ctx, level);
+    const PinK K = level_K(ctx->cam, level);
     const EvalConsts ec = eval_consts(ctx->p);
     Pose16 P;
     memcpy(P.v, pose, sizeof(P.v));
@@ -1593,22 +1582,6 @@ int pin_eval_occ(rgbd360_ctx* ctx, int level, const float* pose, int method, int
     HIPC(ctx, hipGetLastError());
     HIPC(ctx, hostwait::wait(ctx->tag, ctx->stream));
     return 0;
-}
-
-struct PinSums {
-    double e2p, e2d, np, nd, rows;
-    float H[36], g[6];
-    double error() const { return sqrt(e2p / nd) + sqrt(e2d / nd); }     // RPI.h:742-744: both averages / nValidDepthPts
-    double error_occ() const { return sqrt(e2p / np) + sqrt(e2d / nd); } // RPI.h:1314-1317, 1765-1768
-};
-PinSums pin_sums(const GNState& S) {
-    PinSums o;
-    o.e2p = S.tot[P_E2P]; o.e2d = S.tot[P_E2D]; o.np = S.tot[P_NP]; o.nd = S.tot[P_ND]; o.rows = S.tot[P_NVIS];
-    int k = 0;
-    for (int a = 0; a < 6; ++a)
-        for (int b = a; b < 6; ++b, ++k) o.H[b * 6 + a] = o.H[a * 6 + b] = (float)S.tot[P_H + k];
-    for (int a = 0; a < 6; ++a) o.g[a] = (float)S.tot[P_G + a];
-    return o;
 }
 
 }  // namespace
@@ -1653,21 +1626,9 @@ extern "C" int rgbd360_eval_pinhole_occ(rgbd360_ctx* ctx, int level, const float
     hipSetDevice(ctx->p.device);
     if ((rc = pin_prepare_level(ctx, level)) != 0) return rc;
     if ((rc = pin_eval_any(ctx, level, pose, method, occlusion)) != 0) return rc;
-    const GNState& S = *ctx->h_state;
-    const PinSums P = pin_sums(S);
-    if (err2_split) { err2_split[0] = P.e2p; err2_split[1] = P.e2d; }
-    if (n_split) { n_split[0] = (long long)P.np; n_split[1] = (long long)P.nd; }
-    if (H) memcpy(H, P.H, sizeof(P.H));
-    if (g) memcpy(g, P.g, sizeof(P.g));
-    if (H64 || g64) {
-        int k = 0;
-        for (int a = 0; a < 6; ++a)
-            for (int b = a; b < 6; ++b, ++k)
-                if (H64) H64[b * 6 + a] = H64[a * 6 + b] = S.tot[P_H + k];
-        if (g64)
-            for (int a = 0; a < 6; ++a) g64[a] = S.tot[P_G + a];
-    }
-    if (n_rows) *n_rows = (long long)P.rows;
+    lm::Sums S;
+    S.add_row(ctx->h_state.get()->tot);
+    S.write(err2_split, n_split, H, g, H64, g64, n_rows);
     return 0;
 }
 
@@ -1687,7 +1648,7 @@ extern "C" int rgbd360_warp_indices_pinhole(rgbd360_ctx* ctx, int level, const f
     HIPC(ctx, d_out.ensure((size_t)L.n * 2));
     Pose16 P;
     memcpy(P.v, pose, sizeof(P.v));
-    hipLaunchKernelGGL(k_warp_indices_pinhole, dim3((L.n + 255) / 256), dim3(256), 0, ctx->stream, pin_level_dev(L), pin_level_K(ctx, level),
+    hipLaunchKernelGGL(k_warp_indices_pinhole, dim3((L.n + 255) / 256), dim3(256), 0, ctx->stream, pin_level_dev(L), level_K(ctx->cam, level),
                        P, d_out.get());
     HIPC(ctx, hipMemcpyAsync(host_out_rc, d_out, (size_t)L.n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
@@ -1718,7 +1679,7 @@ template <bool PINHOLE>
 int wi_launch(rgbd360_ctx* ctx, int level, const float* pose, int method, int32_t* winner, const WarpImagesOut& out) {
     const Level& L = ctx->levels[level];
     const LevelDev lv = PINHOLE ? pin_level_dev(L) : level_dev(L);
-    const PinK K = PINHOLE ? pin_level_K(ctx, level) : PinK{0.f, 0.f, 0.f, 0.f};
+    const PinK K = PINHOLE ? level_K(ctx->cam, level) : PinK{0.f, 0.f, 0.f, 0.f};
     Pose16 P;
     memcpy(P.v, pose, sizeof(P.v));
     const dim3 grid = level_pixel_grid(L, kPixelThreads);
@@ -1816,112 +1777,58 @@ extern "C" int rgbd360_align_pinhole(rgbd360_ctx* ctx, const float guess[16], in
     if (!guess || !pose_out) return fail(ctx, -1, "null pose pointer");
     if (occlusion < 0 || occlusion > 2) return fail(ctx, -5, "occlusion must be 0, 1 or 2");
     hipSetDevice(ctx->p.device);
-    rgbd360_result R;
-    memset(&R, 0, sizeof(R));
-    float pose_estim[16], pose_estim_temp[16];
-    memcpy(pose_estim, guess, sizeof(pose_estim));
-    float H[36] = {0}, g[6] = {0};
-    double last_eval = 0, last_photo = 0, last_depth = 0, temp_eval = 0, temp_photo = 0, temp_depth = 0, final_error = 0;
-    bool any_iteration = false;
-    int status = 0;
-    PinSums P;
+    // avResidual and its two parts: of the latest evaluation, of the one before it, and what the latest trip started from
+    struct Residuals { double eval = 0, photo = 0, depth = 0; } last, before, temp;
     float sso = 0.f;
-    auto eval = [&](int level, const float* pose, double& out) -> int {
+    // RPI.h:742-744: both averages / nValidDepthPts; the _Occ passes divide the photometric sum by its own count (RPI.h:1314-1317, 1765-1768)
+    auto residuals = [&](const lm::Sums& S) {
+        Residuals r;
+        r.photo = sqrt(S.e2p / (occlusion ? S.np : S.nd));
+        r.depth = sqrt(S.e2d / S.nd);
+        r.eval = r.photo + r.depth;
+        return r;
+    };
+    auto eval = [&](int level, const float* pose, lm::Sums& S) -> int {
         const int e = pin_eval_any(ctx, level, pose, method, occlusion);
         if (e) return e;
-        P = pin_sums(*ctx->h_state);
-        out = occlusion ? P.error_occ() : P.error();
-        last_eval = out;
-        last_photo = sqrt(P.e2p / (occlusion ? P.np : P.nd));
-        last_depth = sqrt(P.e2d / P.nd);
+        S.add_row(ctx->h_state.get()->tot);
+        before = last;
+        last = residuals(S);
         return 0;
     };
     const bool pin_trace = knobs::debug("RGBD360_PIN_TRACE") != nullptr;      // debug builds: every trip's error, update, g and diag(H) on stderr
-    for (int level = ctx->p.n_pyr - 1; level >= 0 && status == 0; --level) {
-        if ((rc = pin_prepare_level(ctx, level)) != 0) return rc;
-        float lambda = 0.01f;                 // RPI.h:4303 (double 0.01 used as a float scalar by Eigen)
-        const double step = 10;
-        const unsigned LM_maxIters = 1;
-        int it = 0;
-        const int maxIters = 10;              // RPI.h:4306-4308: the pinhole driver hard-codes its own limits
-        const double tol_residual = 1e-4, tol_update = 1e-4;
-        float update_pose[6] = {1, 1, 1, 1, 1, 1};
-        double error = 0, new_error = 0;
-        if ((rc = eval(level, pose_estim, error)) != 0) return rc;
-        double diff_error = error;
-        // the first pass doubles as the H,g pass of the first trip (same pose)
-        PinSums at_pose = P;
-        auto unorm = [&]() {
-            float s2 = 0;
-            for (int i = 0; i < 6; ++i) s2 += update_pose[i] * update_pose[i];
-            return sqrtf(s2);
-        };
-        while (it < maxIters && unorm() > tol_update && diff_error > tol_residual) {
-            any_iteration = true;
-            temp_eval = last_eval; temp_photo = last_photo; temp_depth = last_depth;
-            memcpy(H, at_pose.H, sizeof(H));          // calcHessGrad(pose_estim): the fused pass at pose_estim
-            memcpy(g, at_pose.g, sizeof(g));
-            if (occlusion == 2) sso = (float)(at_pose.rows / (double)ctx->levels[level].n);      // calcHessGrad_Occ2 sets SSO (RPI.h:2016)
-            float M[36];
-            for (int k = 0; k < 36; ++k) M[k] = H[k];
-            for (int i = 0; i < 6; ++i) M[i * 6 + i] = H[i * 6 + i] + lambda * H[i * 6 + i];
-            if (gn::rank6(M) != 6 || !gn::lm_update(H, g, -1.f, pose_estim, pose_estim_temp, update_pose)) {
-                status = 1;                            // "The problem is ILL-POSED": relPose = pose_estim, return   RPI.h:4346-4353
-                break;
-            }
-            PinSums cand;
-            if ((rc = eval(level, pose_estim_temp, new_error)) != 0) return rc;
-            cand = P;
-            diff_error = error - new_error;
-            if (pin_trace) {
-                fprintf(stderr, "[pin trace] level %d it %d lambda %g: error %.10f -> %.10f, update", level, it, (double)lambda, error, new_error);
-                for (int k = 0; k < 6; ++k) fprintf(stderr, " %.9g", (double)update_pose[k]);
-                fprintf(stderr, "; g");
-                for (int k = 0; k < 6; ++k) fprintf(stderr, " %.9g", (double)g[k]);
-                fprintf(stderr, "; diag H");
-                for (int k = 0; k < 6; ++k) fprintf(stderr, " %.9g", (double)H[k * 6 + k]);
-                fprintf(stderr, "\n");
-            }
-            if (diff_error > 0) {
-                lambda /= step;
-                memcpy(pose_estim, pose_estim_temp, sizeof(pose_estim));
-                error = new_error;
-                it = it + 1;
-                at_pose = cand;
-            } else {
-                unsigned LM_it = 0;
-                while (LM_it < LM_maxIters && diff_error < 0) {
-                    lambda = lambda * step;
-                    if (!gn::lm_update(H, g, lambda, pose_estim, pose_estim_temp, update_pose)) break;
-                    if ((rc = eval(level, pose_estim_temp, new_error)) != 0) return rc;
-                    cand = P;
-                    diff_error = error - new_error;
-                    if (diff_error > 0) {
-                        memcpy(pose_estim, pose_estim_temp, sizeof(pose_estim));
-                        error = new_error;
-                        it = it + 1;
-                        at_pose = cand;
-                    } else
-                        LM_it = LM_it + 1;
-                }
-            }
-        }
-        if (status == 1) break;
-        R.iters[level & 7] = it;
-        final_error = error;
-    }
-    memcpy(pose_out, pose_estim, sizeof(pose_estim));
-    if (status == 0 && final_error != final_error) status = 2;      // NaN: no depth-valid pixel (or PHOTO only: x / nValidDepthPts)
-    R.status = status;
-    R.err_final = any_iteration ? temp_eval : last_eval;             // avResidual = avResidual_temp   RPI.h:4507-4509
-    R.rms_photo = any_iteration ? temp_photo : last_photo;
-    R.rms_depth = any_iteration ? temp_depth : last_depth;
-    if (status == 1) R.err_final = 0.0;
-    R.sso = status == 1 ? 0.f : sso;
-    memcpy(R.hessian, H, sizeof(H));
-    memcpy(R.gradient, g, sizeof(g));
+    auto on_trip = [&](const lm::Trip& t) {
+        temp = before;      // avResidual_temp: a trip's candidate is its first evaluation, so `before` is what the trip started from
+        if (occlusion == 2) sso = (float)(t.at_pose->rows / (double)ctx->levels[t.level].n);      // calcHessGrad_Occ2 sets SSO (RPI.h:2016)
+        if (!pin_trace) return;
+        fprintf(stderr, "[pin trace] level %d it %d lambda %g: error %.10f -> %.10f, update", t.level, t.it, (double)t.lambda, t.error, t.new_error);
+        for (int k = 0; k < 6; ++k) fprintf(stderr, " %.9g", (double)t.update[k]);
+        fprintf(stderr, "; g");
+        for (int k = 0; k < 6; ++k) fprintf(stderr, " %.9g", (double)t.g[k]);
+        fprintf(stderr, "; diag H");
+        for (int k = 0; k < 6; ++k) fprintf(stderr, " %.9g", (double)t.H[k * 6 + k]);
+        fprintf(stderr, "\n");
+    };
+    lm::Outcome O;
+    rc = lm::align(lm::pinhole_schedule(), ctx->p.n_pyr, guess, [&](int level) { return pin_prepare_level(ctx, level); }, eval,
+                   [&](const lm::Sums& S) { return residuals(S).eval; }, on_trip, &O);
+    if (rc) return rc;
+    memcpy(pose_out, O.pose, sizeof(O.pose));
+    if (O.status == 0 && O.final_error != O.final_error) O.status = 2;      // NaN: no depth-valid pixel (or PHOTO only: x / nValidDepthPts)
+    rgbd360_result R;
+    memset(&R, 0, sizeof(R));
+    R.status = O.status;
+    // avResidual = avResidual_temp (RPI.h:4507-4509); an ILL-POSED trip evaluates nothing, so what it started from is `last`
+    const Residuals& av = O.any_trip && O.status != 1 ? temp : last;
+    R.err_final = O.status == 1 ? 0.0 : av.eval;
+    R.rms_photo = av.photo;
+    R.rms_depth = av.depth;
+    R.sso = O.status == 1 ? 0.f : sso;
+    memcpy(R.iters, O.iters, sizeof(O.iters));
+    memcpy(R.hessian, O.H, sizeof(O.H));
+    memcpy(R.gradient, O.g, sizeof(O.g));
     if (res) *res = R;
-    return status;
+    return O.status;
 }
 
 // test hooks (rgbd360_hip_diag.h): the schedules the parity tests compare with the default ones

@@ -367,11 +367,6 @@ void rigid_inverse(const float* M, float* Inv) {       // [R | t]^-1 = [R^T | -R
     Inv[15] = 1.f;
 }
 
-PinK rig_level_K(const rgbd360_rig* R, int level) {      // RPI.h:4916-4920
-    const float scaleFactor = 1.0 / pow(2, level);
-    return {R->cam[0] * scaleFactor, R->cam[1] * scaleFactor, R->cam[2] * scaleFactor, R->cam[3] * scaleFactor};
-}
-
 // the 8 sensor images of one frame -> pyramids + records of every level (fused set-up, 1 launch per level for all sensors)
 int rig_set_frames(rgbd360_rig* R, bool target, const uint8_t* const* rgb, size_t rgb_step, const void* const* depth, size_t depth_step,
                    int depth_type, int rows, int cols) {
@@ -422,7 +417,7 @@ int rig_set_frames(rgbd360_rig* R, bool target, const uint8_t* const* rgb, size_
         A.min_depth = R->p.min_depth; A.max_depth = R->p.max_depth;
         A.live_mask = live; A.src_mask = target ? 0ull : live; A.trg_mask = target ? live : 0ull;
         A.pinhole = 1;
-        const PinK K = rig_level_K(R, l);
+        const PinK K = level_K(R->cam, l);
         A.pin_ox = K.ox; A.pin_oy = K.oy;
         A.pin_inv_fx = 1. / K.fx; A.pin_inv_fy = 1. / K.fy;      // RPI.h:4921-4922 (float = double quotient, as pin_prepare_level)
         const dim3 g((L.cols + kFsTW - 1) / kFsTW, (L.rows + kFsTH - 1) / kFsTH, R->S);
@@ -435,14 +430,6 @@ int rig_set_frames(rgbd360_rig* R, bool target, const uint8_t* const* rgb, size_
     if (target) R->have_trg = true; else R->have_src = true;
     return 0;
 }
-
-struct RigSums {
-    double e2p = 0, e2d = 0;
-    long long np = 0, nd = 0, rows = 0;
-    float H[36], g[6];
-    double H64[36], g64[6];
-    double error() const { return e2p + e2d; }      // calcPhotoICPError_robot returns error2, the plain sum
-};
 
 // the pose blocks of the warp at rig pose T (column-major); Q is filled for the reference's arithmetic only
 void rig_poses(const rgbd360_rig* R, const float* T, RigPoses* P, RigPosesRef* Q) {
@@ -473,13 +460,13 @@ void rig_poses(const rgbd360_rig* R, const float* T, RigPoses* P, RigPosesRef* Q
 
 // one fused pass over all sensors at rig pose T; per-sensor totals are cast to float and added in sensor order like
 // `Hessian += alignSensorID[sensor_id].getHessian()` (RegisterRGBD360.h:435-440)
-int rig_eval(rgbd360_rig* R, int level, const float* T, int method, RigSums* out) {
+int rig_eval(rgbd360_rig* R, int level, const float* T, int method, lm::Sums* out) {
     SeqEngine* E = R->E;
     const SeqLevel& L = E->levels[level];
     RigPoses P;
     RigPosesRef Q;
     rig_poses(R, T, &P, &Q);
-    const PinK K = rig_level_K(R, level);
+    const PinK K = level_K(R->cam, level);
     const EvalConsts ec = eval_consts(R->p);
     const dim3 g(L.nblocks, R->S), b(kEvalThreads);
     with_choice<0, 1>(R->index_libm != 0, [&](auto Lm) {
@@ -493,28 +480,7 @@ int rig_eval(rgbd360_rig* R, int level, const float* T, int method, RigSums* out
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hostwait::wait(R->tag, E->stream);      // (spin on a pinned tag: one round trip per LM evaluation)
     if (e != hipSuccess) return rfail(R, -(int)e - 1000, hipGetErrorString(e));
-    RigSums S;
-    memset(S.H, 0, sizeof(S.H)); memset(S.g, 0, sizeof(S.g));
-    memset(S.H64, 0, sizeof(S.H64)); memset(S.g64, 0, sizeof(S.g64));
-    for (int s = 0; s < R->S; ++s) {
-        const double* tot = R->h_tot + (size_t)s * kNumPartials;
-        S.e2p += tot[P_E2P]; S.e2d += tot[P_E2D];
-        S.np += (long long)tot[P_NP]; S.nd += (long long)tot[P_ND]; S.rows += (long long)tot[P_NVIS];
-        int k = 0;
-        for (int a = 0; a < 6; ++a)
-            for (int c = a; c < 6; ++c, ++k) {
-                const float v = (float)tot[P_H + k];
-                S.H[c * 6 + a] += v;
-                if (c != a) S.H[a * 6 + c] += v;
-                S.H64[c * 6 + a] += tot[P_H + k];
-                if (c != a) S.H64[a * 6 + c] += tot[P_H + k];
-            }
-        for (int a = 0; a < 6; ++a) {
-            S.g[a] += (float)tot[P_G + a];
-            S.g64[a] += tot[P_G + a];
-        }
-    }
-    *out = S;
+    for (int s = 0; s < R->S; ++s) out->add_row(R->h_tot + (size_t)s * kNumPartials);
     return 0;
 }
 
@@ -592,7 +558,7 @@ int rgbd360_rig_warp_indices(rgbd360_rig* R, int level, const float pose[16], in
     if (e != hipSuccess) return rfail(R, -(int)e - 1000, hipGetErrorString(e));
     const dim3 g((L.n + 255) / 256, R->S);
     with_choice<0, 1>(R->index_libm != 0, [&](auto Lm) {
-        hipLaunchKernelGGL(k_rig_warp_indices<Lm>, g, dim3(256), 0, E->stream, L.srcRec.get(), L.rows, L.cols, L.n, rig_level_K(R, level), P, Q, chain, d_out.get());
+        hipLaunchKernelGGL(k_rig_warp_indices<Lm>, g, dim3(256), 0, E->stream, L.srcRec.get(), L.rows, L.cols, L.n, level_K(R->cam, level), P, Q, chain, d_out.get());
     });
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(host_out_rc, d_out, bytes, hipMemcpyDeviceToHost, E->stream);
@@ -618,16 +584,10 @@ int rgbd360_rig_eval(rgbd360_rig* R, int level, const float pose[16], int method
     if (method < 0 || method > 2) return rfail(R, -4, "bad method");
     if (!pose) return rfail(R, -1, "null pose pointer");
     hipSetDevice(R->p.device);
-    RigSums S;
+    lm::Sums S;
     const int rc = rig_eval(R, level, pose, method, &S);
     if (rc) return rc;
-    if (err2_split) { err2_split[0] = S.e2p; err2_split[1] = S.e2d; }
-    if (n_split) { n_split[0] = S.np; n_split[1] = S.nd; }
-    if (H) memcpy(H, S.H, sizeof(S.H));
-    if (g) memcpy(g, S.g, sizeof(S.g));
-    if (H64) memcpy(H64, S.H64, sizeof(S.H64));
-    if (g64) memcpy(g64, S.g64, sizeof(S.g64));
-    if (n_rows) *n_rows = S.rows;
+    S.write(err2_split, n_split, H, g, H64, g64, n_rows);
     return 0;
 }
 
@@ -640,79 +600,23 @@ int rgbd360_rig_align(rgbd360_rig* R, const float guess[16], int method, float p
     if (method < 0 || method > 2) return rfail(R, -4, "bad method");
     if (!guess || !pose_out) return rfail(R, -1, "null pose pointer");
     hipSetDevice(R->p.device);
+    // FIX A: every candidate is evaluated at pose_estim_temp; the error is error2, the plain sum calcPhotoICPError_robot returns; the
+    // exponential is CPose3D::exp(update), the full one (RegisterRGBD360.h:455)
+    lm::Outcome O;
+    const int rc = lm::align(lm::rig_schedule(), R->p.n_pyr, guess, [](int) { return 0; },
+                             [&](int level, const float* pose, lm::Sums& S) { return rig_eval(R, level, pose, method, &S); },
+                             [](const lm::Sums& S) { return S.e2p + S.e2d; }, [](const lm::Trip&) {}, &O);
+    if (rc) return rc;
+    memcpy(pose_out, O.pose, sizeof(O.pose));
     rgbd360_result Rs;
     memset(&Rs, 0, sizeof(Rs));
-    float pose_estim[16], pose_estim_temp[16];
-    memcpy(pose_estim, guess, sizeof(pose_estim));
-    float Hessian[36] = {0}, Gradient[6] = {0};
-    int status = 0, rc = 0;
-    double final_error = 0;
-    for (int level = R->p.n_pyr - 1; level >= 0 && status == 0; --level) {
-        float lambda = 0.001f;                   // RegisterRGBD360.h:389 (double, used as a float scalar by Eigen)
-        const double step = 10;
-        const unsigned LM_maxIters = 1;
-        int it = 0;
-        const int maxIters = 10;
-        const double tol_residual = pow(10, -1), tol_update = pow(10, -6);
-        float update_pose[6] = {1, 1, 1, 1, 1, 1};
-        RigSums at_pose, cand;
-        if ((rc = rig_eval(R, level, pose_estim, method, &at_pose)) != 0) return rc;      // error; doubles as the first H,g pass
-        double error = at_pose.error();
-        double diff_error = error;
-        auto unorm = [&]() {
-            float s2 = 0;
-            for (int i = 0; i < 6; ++i) s2 += update_pose[i] * update_pose[i];
-            return sqrtf(s2);
-        };
-        while (it < maxIters && unorm() > tol_update && diff_error > tol_residual) {
-            memcpy(Hessian, at_pose.H, sizeof(Hessian));
-            memcpy(Gradient, at_pose.g, sizeof(Gradient));
-            float M[36];
-            for (int k = 0; k < 36; ++k) M[k] = Hessian[k];
-            for (int i = 0; i < 6; ++i) M[i * 6 + i] = Hessian[i * 6 + i] + lambda * Hessian[i * 6 + i];
-            // (lambda starts at 0.001 and is only ever multiplied or divided by step = 10: never negative, gn::lm_update always damps here;
-            // the exponential is CPose3D::exp(update), the full one   RegisterRGBD360.h:455)
-            if (gn::rank6(M) != 6 || !gn::lm_update(Hessian, Gradient, lambda, pose_estim, pose_estim_temp, update_pose)) {
-                status = 1;                      // "The problem is ILL-POSED"   RegisterRGBD360.h:443-449
-                break;
-            }
-            if ((rc = rig_eval(R, level, pose_estim_temp, method, &cand)) != 0) return rc;      // FIX A: at pose_estim_temp
-            double new_error = cand.error();
-            diff_error = error - new_error;
-            if (diff_error > 0) {
-                lambda /= step;
-                memcpy(pose_estim, pose_estim_temp, sizeof(pose_estim));
-                error = new_error;
-                it = it + 1;
-                at_pose = cand;
-            } else {
-                unsigned LM_it = 0;
-                while (LM_it < LM_maxIters && diff_error < 0) {
-                    lambda = lambda * step;
-                    if (!gn::lm_update(Hessian, Gradient, lambda, pose_estim, pose_estim_temp, update_pose)) break;
-                    if ((rc = rig_eval(R, level, pose_estim_temp, method, &cand)) != 0) return rc;
-                    new_error = cand.error();
-                    diff_error = error - new_error;
-                    if (diff_error > 0) {
-                        memcpy(pose_estim, pose_estim_temp, sizeof(pose_estim));
-                        error = new_error;
-                        it = it + 1;
-                        at_pose = cand;
-                    }
-                    LM_it = LM_it + 1;
-                }
-            }
-        }
-        Rs.iters[level & 7] = it;
-        final_error = error;
-    }
-    memcpy(pose_out, pose_estim, sizeof(pose_estim));
-    Rs.status = status;
-    Rs.err_final = final_error;
-    memcpy(Rs.hessian, Hessian, sizeof(Hessian));
-    memcpy(Rs.gradient, Gradient, sizeof(Gradient));
+    Rs.status = O.status;
+    Rs.err_final = O.final_error;
+    memcpy(Rs.iters, O.iters, sizeof(O.iters));
+    memcpy(Rs.hessian, O.H, sizeof(O.H));
+    memcpy(Rs.gradient, O.g, sizeof(O.g));
     if (res) *res = Rs;
-    return status;
+    return O.status;
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 """Same-box A/B of two (or more) builds of the library: kernel / iteration / alignment times of the single-pair path, Infinity-Cache
 resident and HBM-fed (rotating over 8 copies of the pair), plus a hash of the poses (builds that only differ in scheduling must agree).
     python tools/ab_libs.py build NAME=-DFLAG[,-DFLAG2] ...      cross-compiles rgbd360_amd/lib/librgbd360_hip_NAME.so (no GPU needed)
-    python tools/ab_libs.py run [rounds] NAME[@ENV=VAL] ...        on the GPU box; NAME 'default' = the product library; @ENV=VAL sets a variable for that arm"""
+    python tools/ab_libs.py run [rounds] NAME[@ENV=VAL] ...        on the GPU box; NAME 'default' = the product library; @ENV=VAL sets a variable for that arm
+    python tools/ab_libs.py run [rounds] hostlm NAME ...           the two host-driven alignments instead (tools/host_lm_perf.py), wall time per call"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -63,7 +64,8 @@ print("; ".join(out), "| poses", h.hexdigest()[:12])
 args = sys.argv[2:]
 rounds = int(args.pop(0)) if args and args[0].isdigit() else 2
 extra = ["4k"] if "4k" in args else []
-names = [a for a in args if a != "4k"]
+hostlm = "hostlm" in args
+names = [a for a in args if a not in ("4k", "hostlm")]
 for rnd in range(rounds):
     for name in names:
         lib, _, envs = name.partition("@")
@@ -71,5 +73,6 @@ for rnd in range(rounds):
         for kv in envs.split("@"):
             if "=" in kv:
                 env[kv.split("=", 1)[0]] = kv.split("=", 1)[1]
-        r = subprocess.run([sys.executable, "-c", CHILD, lib_of(lib)] + extra, capture_output=True, text=True, env=env)
+        prog = [os.path.join(ROOT, "tools", "host_lm_perf.py")] if hostlm else ["-c", CHILD]
+        r = subprocess.run([sys.executable] + prog + [lib_of(lib)] + extra, capture_output=True, text=True, env=env)
         print("%-10s|" % name, r.stdout.strip() or r.stderr.strip()[-600:], flush=True)
