@@ -4,6 +4,10 @@
 //   1 every new keyframe is a vertex; the alignment against its predecessor is an odometry edge, and ONE store.align round of the new
 //     keyframe against the earlier keyframes within a radius gives the closure edges (KFsphere_SLAM.cpp:262-265, 542-550, 630): the relative
 //     pose is the edge, the Hessian of the alignment its information matrix;
+//     with a minimum overlap score (8th argument) the keyframes within the radius are first ranked and cut by their sensed-space overlap
+//     with the new keyframe at the current graph poses (FrameStore::overlapMatrix at the coarsest level + overlapCandidates; the
+//     reference scores connections by the SSO of a finished alignment, LoopClosure360.h:321, 360), so that alignments are only spent
+//     on pairs that share space;
 //   2 optimizeGraph() (KFsphere_SLAM.cpp:679-689) on the device (rgbd360/PoseGraph.hpp);
 //   3 GlobalMap::move for every keyframe whose pose changed: the map follows the optimised poses without being rebuilt.
 //
@@ -11,7 +15,9 @@
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/pose_graph_slam.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o pose_graph_slam
 // Usage:  pose_graph_slam <dir> <n_frames> <width> <height> [max avDepthResidual = 0.9] [closure radius in m = 1.0] [closures per keyframe = 3]
+//         [minimum overlap score = 0: the radius rule alone]
 // Prints  keyframe <frame> vertex <v> status <s> pose <16 floats, column-major, world <- keyframe, before any optimisation>
+//         candidate <a> <b> score <x>          (only with a minimum overlap score)
 //         closure <from> <to> status <s>
 //         optimise status <s> iterations <i> chi2 <before> <after> moved <keyframes re-posed in the map>
 //         graph vertices <V> edges <E> status <s of the last optimisation> voxels <map size>
@@ -89,7 +95,7 @@ struct KeyFrame {
 
 int main(int argc, char** argv) {
     if (argc < 5) {
-        fprintf(stderr, "usage: %s <dir> <n_frames> <width> <height> [max avDepthResidual] [closure radius] [closures per keyframe]\n", argv[0]);
+        fprintf(stderr, "usage: %s <dir> <n_frames> <width> <height> [max avDepthResidual] [closure radius] [closures per keyframe] [min overlap score]\n", argv[0]);
         return 2;
     }
     const std::string dir = argv[1];
@@ -97,6 +103,7 @@ int main(int argc, char** argv) {
     const double max_residual = argc > 5 ? atof(argv[5]) : 0.9;
     const double radius = argc > 6 ? atof(argv[6]) : 1.0;
     const int max_closures = argc > 7 ? atoi(argv[7]) : 3;
+    const double min_overlap = argc > 8 ? atof(argv[8]) : 0.0;
     if (n < 1 || n > 4096 || max_closures < 0) return 2;
     try {
         rgbd360::RegisterPhotoICP align360;
@@ -146,6 +153,23 @@ int main(int argc, char** argv) {
                 if (d <= radius) near.push_back({d, u});
             }
             std::sort(near.begin(), near.end());
+            if (min_overlap > 0.0 && !near.empty()) {      // rank and cut by overlap instead of by distance
+                std::vector<int> entries;
+                std::vector<Mat4f> world;
+                for (const auto& c : near) entries.push_back(c.second);
+                std::sort(entries.begin(), entries.end());
+                entries.push_back(v);                      // the new keyframe last: it is the `b` of every candidate wanted here
+                for (int e : entries) world.push_back(keyframes[e].pose);
+                const rgbd360_overlap_params op = store.overlapDefaultParams();
+                const rgbd360::OverlapMatrix M = store.overlapMatrix(entries, world, 0.f, op);
+                const int level_px = (h >> op.level) * (w >> op.level);
+                near.clear();
+                for (const rgbd360::OverlapCandidate& c : rgbd360::overlapCandidates(M.records, M.n, level_px, (float)min_overlap, 1, max_closures, {})) {
+                    if (c.b != M.n - 1) continue;          // pairs among the old keyframes are not this round's business
+                    printf("candidate %d %d score %.6f\n", entries[c.a], v, c.score);
+                    near.push_back({-(double)c.score, entries[c.a]});
+                }
+            }
             if ((int)near.size() > max_closures) near.resize(max_closures);
             std::vector<rgbd360::FrameStore::Pair> pairs;
             std::vector<Mat4f> guesses;

@@ -1064,4 +1064,8 @@ int rgbd360_pool_sensor_planes(const rgbd360_plane* planes, int n, float max_cur
 #ifdef __cplusplus
 }
 #endif
+
+/* sensed-space overlap of stored frames (rgbd360_store_overlap*, rgbd360_overlap_*): part of this ABI, declared in a header of its own */
+#include "rgbd360_overlap.h"
+
 #endif /* RGBD360_HIP_H */

@@ -73,6 +73,15 @@ int rgbd360_time_eval_kernel(rgbd360_ctx* ctx, int level, const float pose[16], 
  * the warp alone, the yardstick for what scatter and resolve add.  Outputs go to the context's staging. */
 int rgbd360_time_warp_images(rgbd360_ctx* ctx, int level, const float pose[16], int method, int reps, float avg_us[4]);
 
+/* rgbd360_store_overlap / rgbd360_store_overlap_all (rgbd360_overlap.h) with the kernel launches of the call repeated `reps` times, each
+ * repetition (counters cleared first) between two HIP events on the store's stream: kernel_us[r] = microseconds of repetition r.
+ * out as in the product calls (the counts of the last repetition).  kernel (all-pairs entry): 0 the list kernel over the evaluated
+ * pairs, 1 the source-stationary kernel (the product call chooses by the level's size). */
+int rgbd360_store_time_overlap(rgbd360_store* st, int n_pairs, const int* trg, const int* src, const float* poses,
+                               const rgbd360_overlap_params* params, int reps, float* kernel_us, rgbd360_overlap* out);
+int rgbd360_store_time_overlap_all(rgbd360_store* st, int n, const int* entries, const float* world_poses, float max_translation,
+                                   const rgbd360_overlap_params* params, int kernel, int reps, float* kernel_us, rgbd360_overlap* out);
+
 /* The voxel map's kernels (rgbd360_map_*, rgbd360_hip.h) under HIP events on a sphere frame in device memory, averages over `reps`
  * rounds in microseconds: avg_us[0] k_vmap_insert into the EMPTY map, [1] k_vmap_insert into the map that already holds the frame's
  * voxels (the steady state of odometry), [2] k_vmap_extract (centroids only), [3] ONE k_sphere_cloud_s4 launch of the same size,

@@ -27,6 +27,8 @@ SYMBOLS = [
     "rgbd360_debug_solve_state",
     "rgbd360_store_create", "rgbd360_store_destroy", "rgbd360_store_last_error", "rgbd360_store_entry_bytes", "rgbd360_store_put",
     "rgbd360_store_occupied", "rgbd360_store_align",
+    "rgbd360_store_overlap_default_params", "rgbd360_store_overlap", "rgbd360_store_overlap_all", "rgbd360_overlap_candidates",
+    "rgbd360_overlap_representative", "rgbd360_store_time_overlap", "rgbd360_store_time_overlap_all",
     "rgbd360_warp_images", "rgbd360_warp_images_dev", "rgbd360_warp_images_pinhole", "rgbd360_time_warp_images",
     "rgbd360_map_create", "rgbd360_map_destroy", "rgbd360_map_last_error", "rgbd360_map_bytes", "rgbd360_map_set_box",
     "rgbd360_map_insert_sphere", "rgbd360_map_insert_cloud", "rgbd360_map_size", "rgbd360_map_clear", "rgbd360_map_extract",
@@ -136,6 +138,14 @@ class GraphResult(C.Structure):         # rgbd360_graph_result
 class GraphIteration(C.Structure):      # rgbd360_graph_iteration
     _fields_ = [("chi2", C.c_double), ("chi2_trial", C.c_double), ("lambda_", C.c_double), ("accepted", C.c_int), ("cg_iterations", C.c_int),
                 ("cg_residual", C.c_double), ("max_update", C.c_double)]
+
+
+class OverlapParams(C.Structure):        # rgbd360_overlap_params
+    _fields_ = [("level", C.c_int), ("tol_abs", C.c_float), ("tol_rel", C.c_float)]
+
+
+# rgbd360_overlap as a numpy record (eight int32)
+OVERLAP_FIELDS = ("evaluated", "n_valid", "n_visible", "n_target", "n_consistent", "n_behind", "n_in_front", "reserved")
 
 
 class PbmapParams(C.Structure):
@@ -292,6 +302,14 @@ def load() -> C.CDLL:
     L.rgbd360_store_put.argtypes = [vp, i32, vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32]
     L.rgbd360_store_occupied.argtypes = [vp, i32]
     L.rgbd360_store_align.argtypes = [vp, i32, vp, vp, f32p, i32, i32, i32, f32p, vp]
+    L.rgbd360_store_overlap_default_params.argtypes = [vp, C.POINTER(OverlapParams)]
+    L.rgbd360_store_overlap_default_params.restype = None
+    L.rgbd360_store_overlap.argtypes = [vp, i32, vp, vp, f32p, C.POINTER(OverlapParams), vp]
+    L.rgbd360_store_overlap_all.argtypes = [vp, i32, vp, f32p, C.c_float, C.POINTER(OverlapParams), vp, f32p]
+    L.rgbd360_overlap_candidates.argtypes = [i32, vp, i32, C.c_float, i32, i32, i32, vp, vp, i32, vp, vp, vp]
+    L.rgbd360_overlap_representative.argtypes = [i32, vp, i32, vp, i32]
+    L.rgbd360_store_time_overlap.argtypes = [vp, i32, vp, vp, f32p, C.POINTER(OverlapParams), i32, vp, vp]
+    L.rgbd360_store_time_overlap_all.argtypes = [vp, i32, vp, f32p, C.c_float, C.POINTER(OverlapParams), i32, i32, vp, vp]
     ll = C.c_longlong
     L.rgbd360_map_create.argtypes = [vp, C.c_float, ll, C.POINTER(vp)]
     L.rgbd360_map_destroy.argtypes = [vp]

@@ -38,6 +38,8 @@ struct rgbd360_store {
     SeqEngine* eng[2] = {nullptr, nullptr};      // alignment: states, partial rows and stream of up to 2 x 32 slots, no frame buffers
     StoreView eng_view[2];
     int n_eng = 0;
+    DevBuf<unsigned char> ov_table, ov_segs;      // store_overlap.h: the pair table (and its per-source segments) of a call and ...
+    DevBuf<int32_t> ov_counts;            // ... its [records][8] counters, both on put_eng's stream
     std::string err;
 };
 

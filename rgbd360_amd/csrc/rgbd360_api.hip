@@ -1856,6 +1856,7 @@ void rgbd360_ctx_set_error(rgbd360_ctx* ctx, const char* msg) { ctx->err = msg ?
 
 #include "map_render.h"
 #include "frame_store.h"
+#include "store_overlap.h"
 #include "pose_graph.h"
 #include "multi_gpu.h"
 

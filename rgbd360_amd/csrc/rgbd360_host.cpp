@@ -162,3 +162,60 @@ extern "C" int rgbd360_pool_sensor_planes(const rgbd360_plane* planes, int n, fl
     }
 }
 
+// ---- sensed-space overlap: what to do with a matrix of rgbd360_store_overlap_all (host only; the device part is csrc/store_overlap.h) ----
+namespace {
+// min of the two directions' consistent counts over the level's pixels; 0 unless both directions were evaluated
+float overlap_score(int n, const rgbd360_overlap* m, int level_px, int a, int b) {
+    const rgbd360_overlap &ab = m[(size_t)a * n + b], &ba = m[(size_t)b * n + a];
+    if (!ab.evaluated || !ba.evaluated) return 0.f;
+    return (float)std::min(ab.n_consistent, ba.n_consistent) / (float)level_px;
+}
+}  // namespace
+
+extern "C" int rgbd360_overlap_candidates(int n, const rgbd360_overlap* m, int level_px, float min_score, int min_gap, int max_per_frame,
+                                          int n_known, const int* known_a, const int* known_b, int max_out, int* out_a, int* out_b,
+                                          float* out_score) {
+    if (n < 0 || (n > 0 && !m) || level_px < 1 || n_known < 0 || (n_known > 0 && (!known_a || !known_b)) || max_out < 0) return -1;
+    try {
+        int found = 0;
+        std::vector<std::pair<float, int>> cand;
+        for (int b = 0; b < n; ++b) {
+            cand.clear();
+            for (int a = 0; a < b; ++a) {
+                if (b - a < min_gap) continue;
+                const float s = overlap_score(n, m, level_px, a, b);
+                if (!(s >= min_score)) continue;
+                bool known = false;
+                for (int k = 0; k < n_known && !known; ++k)
+                    known = (known_a[k] == a && known_b[k] == b) || (known_a[k] == b && known_b[k] == a);
+                if (!known) cand.emplace_back(s, a);
+            }
+            std::stable_sort(cand.begin(), cand.end(), [](const std::pair<float, int>& x, const std::pair<float, int>& y) { return x.first > y.first; });
+            const size_t keep = max_per_frame > 0 ? std::min(cand.size(), (size_t)max_per_frame) : cand.size();
+            for (size_t k = 0; k < keep; ++k, ++found) {
+                if (found >= max_out) continue;
+                if (out_a) out_a[found] = cand[k].second;
+                if (out_b) out_b[found] = b;
+                if (out_score) out_score[found] = cand[k].first;
+            }
+        }
+        return found;
+    } catch (const std::exception&) {
+        return -1;
+    }
+}
+
+extern "C" int rgbd360_overlap_representative(int n, const rgbd360_overlap* m, int level_px, const int* subset, int n_subset) {
+    if (n < 1 || !m || level_px < 1 || !subset || n_subset < 1) return -1;
+    for (int k = 0; k < n_subset; ++k)
+        if (subset[k] < 0 || subset[k] >= n) return -1;
+    int best = subset[0];
+    double best_sum = -1.0;
+    for (int k = 0; k < n_subset; ++k) {
+        double sum = 0.0;
+        for (int j = 0; j < n_subset; ++j)
+            if (subset[j] != subset[k]) sum += (double)overlap_score(n, m, level_px, subset[k], subset[j]);
+        if (sum > best_sum) { best_sum = sum; best = subset[k]; }
+    }
+    return best;
+}

@@ -195,3 +195,105 @@ class FrameStore:
             status[k] = res[k].status
             iters[k] = [int(res[k].iters[l]) for l in range(n_pyr)]
         return poses, status, iters, [res[k] for k in range(n)]
+
+    # ---- sensed-space overlap (rgbd360_store_overlap*, csrc/store_overlap.h)
+    def _overlap_params(self, level, tol_abs, tol_rel):
+        p = _lib.OverlapParams()
+        self._L.rgbd360_store_overlap_default_params(self._handle(), C.byref(p))
+        if level is not None:
+            p.level = int(level)
+        if tol_abs is not None:
+            p.tol_abs = float(tol_abs)
+        if tol_rel is not None:
+            p.tol_rel = float(tol_rel)
+        return p
+
+    def overlap(self, pairs, poses=None, level=None, tol_abs=None, tol_rel=None):
+        """pairs: [(target entry, source entry), ...]; poses: None (identity) or one 4x4 (source in target) per pair; level: None = the
+        coarsest; tolerances: None = the defaults (0.05 m, 0.02).  Returns a structured array (OVERLAP_DTYPE) in list order."""
+        p = np.asarray(pairs)
+        if p.size == 0:
+            p = np.zeros((0, 2), np.int32)
+        if p.ndim != 2 or p.shape[1] != 2 or not np.issubdtype(p.dtype, np.integer):
+            raise Rgbd360Error("FrameStore.overlap: pairs must be (target entry, source entry) integer tuples")
+        n = p.shape[0]
+        g = None
+        if poses is not None:
+            G = np.asarray(poses, np.float32)
+            if G.shape != (n, 4, 4):
+                raise Rgbd360Error("FrameStore.overlap: poses must be one 4x4 pose per pair")
+            g = np.ascontiguousarray(G.transpose(0, 2, 1).reshape(-1)) if n else None
+        trg = np.ascontiguousarray(p[:, 0], np.int32)
+        src = np.ascontiguousarray(p[:, 1], np.int32)
+        out = np.zeros(n, OVERLAP_DTYPE)
+        par = self._overlap_params(level, tol_abs, tol_rel)
+        self._check(self._L.rgbd360_store_overlap(self._handle(), n, trg.ctypes.data_as(C.c_void_p), src.ctypes.data_as(C.c_void_p),
+                                                  None if g is None else g.ctypes.data_as(C.c_void_p), C.byref(par),
+                                                  out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def overlap_matrix(self, entries, world_poses, max_translation: float = 0.0, level=None, tol_abs=None, tol_rel=None):
+        """entries: n distinct occupied entries; world_poses: [n,4,4] (world <- frame).  Returns (matrix [n,n] of OVERLAP_DTYPE with
+        matrix[a, b] = target entries[a], source entries[b]; rel_poses [n,n,4,4] float32, W_a^-1 W_b as the library formed them).
+        Pairs farther apart than max_translation (> 0) and the diagonal are not evaluated (all zero)."""
+        e = np.ascontiguousarray(np.asarray(entries), np.int32)
+        n = e.size
+        W = np.asarray(world_poses, np.float32)
+        if e.ndim != 1 or W.shape != (n, 4, 4):
+            raise Rgbd360Error("FrameStore.overlap_matrix: one 4x4 world pose per entry")
+        w = np.ascontiguousarray(W.transpose(0, 2, 1).reshape(-1))
+        out = np.zeros((n, n), OVERLAP_DTYPE)
+        rel = np.zeros((n, n, 16), np.float32)
+        par = self._overlap_params(level, tol_abs, tol_rel)
+        self._check(self._L.rgbd360_store_overlap_all(self._handle(), n, e.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p),
+                                                      float(max_translation), C.byref(par), out.ctypes.data_as(C.c_void_p),
+                                                      rel.ctypes.data_as(C.c_void_p)))
+        return out, np.ascontiguousarray(rel.reshape(n, n, 4, 4).transpose(0, 1, 3, 2))
+
+
+OVERLAP_DTYPE = np.dtype([(f, np.int32) for f in _lib.OVERLAP_FIELDS])
+
+
+def _matrix(m):
+    m = np.ascontiguousarray(m, OVERLAP_DTYPE)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise Rgbd360Error("overlap matrix must be [n, n]")
+    return m
+
+
+def overlap_score(matrix, level_px: int) -> np.ndarray:
+    """score[a, b] = min(m[a,b].n_consistent, m[b,a].n_consistent) / level_px, 0 unless both directions were evaluated (float32, the
+    arithmetic of rgbd360_overlap_candidates)."""
+    m = _matrix(matrix)
+    both = (m["evaluated"] != 0) & (m["evaluated"].T != 0)
+    c = np.minimum(m["n_consistent"], m["n_consistent"].T).astype(np.float32) / np.float32(level_px)
+    return np.where(both, c, np.float32(0)).astype(np.float32)
+
+
+def overlap_candidates(matrix, level_px: int, min_score: float, min_gap: int = 1, max_per_frame: int = 0, known=(), max_out=None):
+    """rgbd360_overlap_candidates (host only): (a [k], b [k], score [k], number found); known: [(a, b), ...] edges to leave out."""
+    L = _lib.load()
+    m = _matrix(matrix)
+    n = m.shape[0]
+    kn = np.asarray(list(known), np.int32).reshape(-1, 2)
+    ka, kb = np.ascontiguousarray(kn[:, 0]), np.ascontiguousarray(kn[:, 1])
+    cap = n * (n - 1) // 2 if max_out is None else int(max_out)
+    a, b, s = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float32)
+    found = L.rgbd360_overlap_candidates(n, m.ctypes.data_as(C.c_void_p), int(level_px), float(min_score), int(min_gap), int(max_per_frame),
+                                         kn.shape[0], ka.ctypes.data_as(C.c_void_p), kb.ctypes.data_as(C.c_void_p), cap,
+                                         a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p))
+    if found < 0:
+        raise Rgbd360Error("rgbd360_overlap_candidates: bad arguments")
+    k = min(found, cap)
+    return a[:k], b[:k], s[:k], found
+
+
+def overlap_representative(matrix, level_px: int, subset) -> int:
+    """rgbd360_overlap_representative (host only): the member of `subset` with the largest score sum over the subset, ties to the first."""
+    L = _lib.load()
+    m = _matrix(matrix)
+    sub = np.ascontiguousarray(np.asarray(subset), np.int32)
+    r = L.rgbd360_overlap_representative(m.shape[0], m.ctypes.data_as(C.c_void_p), int(level_px), sub.ctypes.data_as(C.c_void_p), sub.size)
+    if r < 0:
+        raise Rgbd360Error("rgbd360_overlap_representative: bad arguments")
+    return int(r)
