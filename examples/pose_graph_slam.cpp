@@ -9,16 +9,23 @@
 //     reference scores connections by the SSO of a finished alignment, LoopClosure360.h:321, 360), so that alignments are only spent
 //     on pairs that share space;
 //   2 optimizeGraph() (KFsphere_SLAM.cpp:679-689) on the device (rgbd360/PoseGraph.hpp);
+//     with a robust delta (9th argument) every closure edge gets a Cauchy kernel of that delta (g2o's setRobustKernel; the odometry edges
+//     stay quadratic), closures whose weight ends below 0.1 are switched off and the graph is optimised once more, so that an alignment
+//     that converged on the wrong surface is not baked into the map (delta is in units of sqrt(r^T Omega r).  With the alignment's
+//     Hessian as Omega that is a large number even for a good closure: on the synthetic ring of tools/dump_sequence.py s is in the
+//     thousands, and delta = 6 switches every closure off; choose delta from the `weight` lines of a first run);
 //   3 GlobalMap::move for every keyframe whose pose changed: the map follows the optimised poses without being rebuilt.
 //
 // Frames: raw files written by tools/dump_sequence.py, frame_%03d.rgb (H*W*3 uint8), frame_%03d.depth (H*W uint16 mm).
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/pose_graph_slam.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o pose_graph_slam
 // Usage:  pose_graph_slam <dir> <n_frames> <width> <height> [max avDepthResidual = 0.9] [closure radius in m = 1.0] [closures per keyframe = 3]
-//         [minimum overlap score = 0: the radius rule alone]
+//         [minimum overlap score = 0: the radius rule alone] [robust delta = 0: quadratic closures]
 // Prints  keyframe <frame> vertex <v> status <s> pose <16 floats, column-major, world <- keyframe, before any optimisation>
 //         candidate <a> <b> score <x>          (only with a minimum overlap score)
 //         closure <from> <to> status <s>
+//         weight <from> <to> <w>               (only with a robust delta: every closure after each optimisation, 0 for one switched off)
+//         rejected <from> <to>                 (only with a robust delta: a closure switched off now)
 //         optimise status <s> iterations <i> chi2 <before> <after> moved <keyframes re-posed in the map>
 //         graph vertices <V> edges <E> status <s of the last optimisation> voxels <map size>
 #include <algorithm>
@@ -95,7 +102,7 @@ struct KeyFrame {
 
 int main(int argc, char** argv) {
     if (argc < 5) {
-        fprintf(stderr, "usage: %s <dir> <n_frames> <width> <height> [max avDepthResidual] [closure radius] [closures per keyframe] [min overlap score]\n", argv[0]);
+        fprintf(stderr, "usage: %s <dir> <n_frames> <width> <height> [max avDepthResidual] [closure radius] [closures per keyframe] [min overlap score] [robust delta]\n", argv[0]);
         return 2;
     }
     const std::string dir = argv[1];
@@ -104,7 +111,8 @@ int main(int argc, char** argv) {
     const double radius = argc > 6 ? atof(argv[6]) : 1.0;
     const int max_closures = argc > 7 ? atoi(argv[7]) : 3;
     const double min_overlap = argc > 8 ? atof(argv[8]) : 0.0;
-    if (n < 1 || n > 4096 || max_closures < 0) return 2;
+    const double robust_delta = argc > 9 ? atof(argv[9]) : 0.0;
+    if (n < 1 || n > 4096 || max_closures < 0 || !(robust_delta >= 0.0)) return 2;
     try {
         rgbd360::RegisterPhotoICP align360;
         align360.setNumPyr(4);
@@ -113,6 +121,8 @@ int main(int argc, char** argv) {
         rgbd360::GlobalMap globalMap(align360, rgbd360::FilterPointCloud(), 1 << 20);
         rgbd360::PoseGraph graph(align360);
         std::vector<KeyFrame> keyframes;
+        struct Closure { int edge, from, to; bool rejected; };
+        std::vector<Closure> closure_edges;      // (only filled with a robust delta)
         int last_status = 0;
 
         auto add_keyframe = [&](int frame, std::unique_ptr<Frame> images, const Mat4f& pose, int status) {
@@ -183,12 +193,30 @@ int main(int argc, char** argv) {
                 printf("closure %d %d status %d\n", pairs[k].target, pairs[k].source, res[k].status);
                 if (res[k].status != 0) continue;
                 graph.addEdge(pairs[k].target, pairs[k].source, closures[k], rgbd360::PoseGraph::information(res[k]));
+                if (robust_delta > 0.0) {
+                    graph.setRobustKernel(graph.lastEdge(), RGBD360_GRAPH_ROBUST_CAUCHY, robust_delta);
+                    closure_edges.push_back({graph.lastEdge(), pairs[k].target, pairs[k].source, false});
+                }
                 ++added;
             }
             if (!added) continue;
             // step 2: optimise; step 3: re-pose the map
             const double before = graph.chi2();
             graph.optimizeGraph();
+            if (robust_delta > 0.0) {
+                std::vector<double> weights;
+                graph.edgeWeights(weights);
+                int rejected = 0;
+                for (Closure& c : closure_edges) printf("weight %d %d %.6f\n", c.from, c.to, weights[c.edge]);
+                for (Closure& c : closure_edges) {
+                    if (c.rejected || !(weights[c.edge] < 0.1)) continue;
+                    graph.setEdgeEnabled(c.edge, false);
+                    c.rejected = true;
+                    ++rejected;
+                    printf("rejected %d %d\n", c.from, c.to);
+                }
+                if (rejected) graph.optimizeGraph();
+            }
             last_status = graph.result().status;
             std::vector<Mat4f> poses;
             graph.getPoses(poses);

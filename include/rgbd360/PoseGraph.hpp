@@ -48,6 +48,27 @@ class PoseGraph {
         for (int k = 0; k < 36; ++k) I.m[k] = r.hessian[k];
         return I;
     }
+    int lastEdge() const { return numEdges() - 1; }      // the index of the edge addEdge added last
+    // g2o's edge->setRobustKernel: kind is RGBD360_GRAPH_ROBUST_NONE / HUBER / CAUCHY / GEMAN_MCCLURE, delta > 0 in units of sqrt(chi2)
+    void setRobustKernel(int edge, int kind, double delta) {
+        check(rgbd360_graph_set_edge_robust(g_, edge, 1, &kind, &delta), "rgbd360_graph_set_edge_robust");
+    }
+    // A disabled edge adds nothing to the cost or the normal equations; its chi2 is still reported by edgeWeights.
+    void setEdgeEnabled(int edge, bool enabled) {
+        const uint8_t f = enabled ? 1 : 0;
+        check(rgbd360_graph_set_edge_enabled(g_, edge, 1, &f), "rgbd360_graph_set_edge_enabled");
+    }
+    // Per edge at the current poses: s = r^T Omega r, the robust rho and the weight w (0 for a disabled edge).  Returns the cost.
+    double edgeWeights(std::vector<double>& w, std::vector<double>* s = nullptr, std::vector<double>* rho = nullptr) {
+        const size_t n = (size_t)numEdges();
+        double cost = 0.0;
+        w.resize(n);
+        if (s) s->resize(n);
+        if (rho) rho->resize(n);
+        check(rgbd360_graph_edge_weights(g_, &cost, s && n ? s->data() : nullptr, rho && n ? rho->data() : nullptr, n ? w.data() : nullptr),
+              "rgbd360_graph_edge_weights");
+        return cost;
+    }
     void setPose(int vertex, const Mat4f& pose) { check(rgbd360_graph_set_poses(g_, vertex, 1, pose.m), "rgbd360_graph_set_poses"); }
     void setFixed(int vertex, bool fixed) {
         const uint8_t f = fixed ? 1 : 0;

@@ -486,7 +486,7 @@ int    rgbd360_map_render_sphere_dev(rgbd360_map* map, int rows, int cols, const
  *   Jacobians  dr/dx_i = A = J_l^-1(r) Ad(Z T_j^-1), dr/dx_j = -A; J_l^-1 = I - ad/2 + ad^2/12 - ad^4/720 + ad^6/30240,
  *              ad(r) = [ [w]x [v]x ; 0 [w]x ] (truncation below 3e-9 for |r| <= 0.5).  Per edge W = A^T Omega A and b = A^T Omega r:
  *              H gains +W at (i,i) and (j,j), -W at (i,j) and (j,i); g gains +b at i, -b at j.
- *   cost, loop chi2 = sum r^T Omega r.  Levenberg-Marquardt with the damping of the dense alignment, H + lambda diag(H): lambda starts at
+ *   cost, loop chi2 = sum r^T Omega r (quadratic edges; `robust` below).  Levenberg-Marquardt with the damping of the dense alignment, H + lambda diag(H): lambda starts at
  *              lambda_init (1e-3), is divided by 10 after an accepted step (not below 1e-9) and multiplied by 10 after a rejected one
  *              (RegisterRGBD360.h:389).  A step is accepted iff chi2 at the trial poses is smaller than chi2 at the current ones; a
  *              rejected step leaves the poses unchanged.  The loop ends after max_iters iterations (10: the reference's optimize(10)),
@@ -502,9 +502,30 @@ int    rgbd360_map_render_sphere_dev(rgbd360_map* map, int rows, int cols, const
  *              added in ascending order -- two calls on equal graphs give equal bits.
  * The host builds and uploads the incidence lists and edge arrays only when the graph changed; one stream synchronisation per
  * Levenberg-Marquardt iteration.  A graph is destroyed BEFORE its context and used from one thread at a time.
- * Out of scope: robust kernels, removing single edges, marginalisation, incremental solving, SE(2), landmarks, several GPUs, a stronger
- * preconditioner. */
+ *   robust     every edge carries a kind, a delta > 0 (double) and an enabled flag; a new edge is RGBD360_GRAPH_ROBUST_NONE and enabled.
+ *              For an enabled edge s = r^T Omega r as above and, in float64 with d2 = delta * delta,
+ *                NONE           rho = s                                              w = 1
+ *                HUBER          s <= d2: rho = s; else q = sqrt(s), 2 delta q - d2   w = 1; else delta / q
+ *                CAUCHY         u = s / d2, rho = d2 log1p(u)                        w = 1 / (1 + u)
+ *                GEMAN_MCCLURE  t = d2 / (d2 + s), rho = s t                         w = t t
+ *              with w = d rho / d s.  Omega only has a positive diagonal, so s may be <= 0: whenever !(s > 0) every kind gives rho = s,
+ *              w = 1.  The cost is the sum of rho over the enabled edges, and chi2, chi2_trial, chi2_initial and chi2_final of the
+ *              result and the trace are that cost.  The linearisation is first order (Triggs; g2o's rho[1]): W_e = w_e A^T Omega A,
+ *              b_e = w_e A^T Omega r, without the second-derivative term.  Assembly, the solve, the trial poses, the accept test, the
+ *              lambda schedule and the stop rules are as above, on the robust cost.  A graph whose edges are all NONE and enabled gives the
+ *              bits it gave before the kinds existed (w is an exact 1).
+ *   disabled   a disabled edge adds nothing to the cost, H or g and does not count as an edge of its vertices: a free vertex whose edges
+ *              are all disabled is treated as fixed, counted in n_isolated, and its pose comes back bit for bit.  The enabled edges enter
+ *              every vertex sum in edge-list order, as in a graph built without the disabled ones.
+ *   caveats    the redescending kinds (CAUCHY, GEMAN_MCCLURE) can starve a vertex whose edges all have large residuals: when its damped
+ *              block then has no Cholesky factor the call ends RGBD360_ILL_POSED as above.  Iteratively re-weighted least squares
+ *              converges linearly: robust runs want tol_update around 1e-8; at 1e-10 the loop often ends on lambda_max instead.
+ * The host builds and uploads the incidence lists again when an enabled flag changed; a change of kind or delta uploads two arrays of one
+ * word per edge.
+ * Out of scope: the second-order robust term, dynamic covariance scaling and switch variables, an adaptive delta, robust weights inside
+ * the dense alignment, marginalisation, incremental solving, SE(2), landmarks, several GPUs, a stronger preconditioner. */
 typedef struct rgbd360_graph rgbd360_graph;
+enum { RGBD360_GRAPH_ROBUST_NONE = 0, RGBD360_GRAPH_ROBUST_HUBER = 1, RGBD360_GRAPH_ROBUST_CAUCHY = 2, RGBD360_GRAPH_ROBUST_GEMAN_MCCLURE = 3 };
 typedef struct {
     int    max_iters;          /* Levenberg-Marquardt iterations, 0 .. 10000: 10 */
     int    cg_max_iters;       /* per solve, 1 .. 100000: 400 */
@@ -541,9 +562,20 @@ void rgbd360_graph_default_params(rgbd360_graph_params* p);
  * without vertices, edges or free vertices returns RGBD360_OK with 0 iterations. */
 int  rgbd360_graph_optimize(rgbd360_graph* g, const rgbd360_graph_params* params, rgbd360_graph_result* result);
 int  rgbd360_graph_get_poses(rgbd360_graph* g, int first, int n, float* out);
-/* chi2 at the current poses (the bits rgbd360_graph_optimize reports as chi2_initial from there); per_edge (may be NULL): r^T Omega r of
- * every edge. */
+/* The cost at the current poses (the bits rgbd360_graph_optimize reports as chi2_initial from there): the sum of rho over the enabled
+ * edges; per_edge (may be NULL): the raw s = r^T Omega r of every edge, enabled or not, so that a rejected closure can be tested again. */
 int  rgbd360_graph_chi2(rgbd360_graph* g, double* chi2, double* per_edge);
+/* Kind and delta of the edges first .. first + n - 1.  deltas may be NULL only when every kind is NONE; the delta of a NONE edge is
+ * neither checked nor stored (a new edge's delta reads 1).  0; -1 and nothing changed when the range is outside the edges, a kind is outside 0..3, or the delta of a kind
+ * other than NONE is not finite or <= 0 (the message names the first such edge).  rgbd360_graph_clear forgets the settings. */
+int  rgbd360_graph_set_edge_robust(rgbd360_graph* g, int first, int n, const int* kinds, const double* deltas);
+/* Switches edges off (0) and on (non-zero); -1 and nothing changed when the range is outside the edges. */
+int  rgbd360_graph_set_edge_enabled(rgbd360_graph* g, int first, int n, const uint8_t* enabled);
+/* What the two setters left; kinds, deltas and enabled may each be NULL. */
+int  rgbd360_graph_get_edge_state(rgbd360_graph* g, int first, int n, int* kinds, double* deltas, uint8_t* enabled);
+/* At the current poses, per edge: s, rho and w (rho = w = 0 for a disabled edge), and *cost, bit for bit what rgbd360_graph_chi2
+ * returns.  Each of the four may be NULL. */
+int  rgbd360_graph_edge_weights(rgbd360_graph* g, double* cost, double* s, double* rho, double* w);
 /* the first min(max_trace, iterations) records of the last rgbd360_graph_optimize; *n_trace (may be NULL): iterations */
 int  rgbd360_graph_get_trace(rgbd360_graph* g, int max_trace, int* n_trace, rgbd360_graph_iteration* trace);
 

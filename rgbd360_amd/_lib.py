@@ -43,6 +43,7 @@ SYMBOLS = [
     "rgbd360_graph_set_poses", "rgbd360_graph_set_fixed", "rgbd360_graph_n_vertices", "rgbd360_graph_n_edges", "rgbd360_graph_clear",
     "rgbd360_graph_default_params", "rgbd360_graph_optimize", "rgbd360_graph_get_poses", "rgbd360_graph_chi2", "rgbd360_graph_get_trace",
     "rgbd360_graph_linearize", "rgbd360_graph_apply", "rgbd360_graph_time_kernels",
+    "rgbd360_graph_set_edge_robust", "rgbd360_graph_set_edge_enabled", "rgbd360_graph_get_edge_state", "rgbd360_graph_edge_weights",
 ]
 
 
@@ -379,5 +380,9 @@ def load() -> C.CDLL:
     L.rgbd360_graph_linearize.argtypes = [vp, vp, vp]
     L.rgbd360_graph_apply.argtypes = [vp, C.c_double, vp, vp]
     L.rgbd360_graph_time_kernels.argtypes = [vp, i32, vp]
+    L.rgbd360_graph_set_edge_robust.argtypes = [vp, i32, i32, vp, vp]
+    L.rgbd360_graph_set_edge_enabled.argtypes = [vp, i32, i32, vp]
+    L.rgbd360_graph_get_edge_state.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.rgbd360_graph_edge_weights.argtypes = [vp, C.POINTER(C.c_double), vp, vp, vp]
     _lib = L
     return L

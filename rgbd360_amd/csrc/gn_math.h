@@ -413,4 +413,27 @@ GN_HD inline void se3_jl_inv(const double* r, double* J) {
         J[k] = ((((k % 7 == 0 ? 1.0 : 0.0) - 0.5 * ad[k]) + a2[k] / 12.0) - a4[k] / 720.0) + a6[k] / 30240.0;
 }
 
+// rho(s) and w = d rho / d s of an edge's robust kind (RGBD360_GRAPH_ROBUST_*: 0 none, 1 Huber, 2 Cauchy, 3 Geman-McClure; rgbd360_hip.h)
+// at s = r^T Omega r.  Whenever !(s > 0) every kind gives (s, 1).  Kind 0 and Huber below delta^2 return s itself and an exact 1.
+GN_HD inline void robust_rho_w(int kind, double delta, double s, double* rho, double* w) {
+    *rho = s;
+    *w = 1.0;
+    if (kind == 0 || !(s > 0.0)) return;
+    const double d2 = delta * delta;
+    if (kind == 1) {
+        if (s <= d2) return;
+        const double q = sqrt(s);
+        *rho = 2.0 * delta * q - d2;
+        *w = delta / q;
+    } else if (kind == 2) {
+        const double u = s / d2;
+        *rho = d2 * log1p(u);
+        *w = 1.0 / (1.0 + u);
+    } else {
+        const double t = d2 / (d2 + s);
+        *rho = s * t;
+        *w = t * t;
+    }
+}
+
 }  // namespace gn

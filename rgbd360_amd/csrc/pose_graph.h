@@ -4,18 +4,22 @@
 // optimize(10), vertex 0 fixed; KFsphere_SLAM.cpp:679-689).
 //
 // One Levenberg-Marquardt iteration `it` is a fixed list of launches, enqueued blindly by the host:
-//   k_pg_edges<linearise>   per edge: r, W = A^T Omega A, b = A^T Omega r, chi2 -> one partial row per workgroup
+//   k_pg_edges<linearise>   per edge: r, s = r^T Omega r, the robust rho(s) and w(s), W = w A^T Omega A, b = w A^T Omega r -> one partial row of
+//                           rho per workgroup
 //   k_pg_assemble           per vertex over its CSR row: diagonal block D, gradient g, (D + lambda diag D)^-1, the PCG start
 //   cg_max_iters times      k_pg_cg_edge (t_e = W (p_i - p_j)), k_pg_cg_gather (q = sum +-t_e + lambda diag(D) p, p.q rows),
 //                           k_pg_cg_update (x, r, z, r.z rows), k_pg_cg_dir (stop test, p = z + beta p)
 //   k_pg_trial              T' = se3_exp(x) T per vertex, max |x| rows
-//   k_pg_edges<chi2>        chi2 at T'
+//   k_pg_edges<chi2>        the cost (sum of rho) at T'
 //   k_pg_decide             accept / reject, lambda, the trace record, the stop test
 // House rules: no floating-point atomics; a vertex adds its edges in CSR (= edge list) order; every global scalar is a table of
 // per-workgroup partial rows which each consumer re-adds in ascending order in its prologue (pg_rows_sum), so that all blocks take the
 // same decision from the same bits; no cooperative launch, no spin barrier, no ticket.  A kernel never reads a state word it writes:
 // the stop words are "first index that does not run" (stop_it, cg_stop_at), compared with the index the launch carries, so a launch of
 // a finished loop or of a converged PCG returns at once, and the block that records a stop cannot change what its own launch does.
+// Robust and switchable edges: per edge one word `kind` (RGBD360_GRAPH_ROBUST_*, -1 = disabled) and one `delta`.  A disabled edge has
+// rho = w = 0 and is in no vertex's CSR row, so W, b and t of it are written and never read; a quadratic edge has rho = s and w = an exact
+// 1.0, so a graph of quadratic, enabled edges keeps the bits it had before the kinds existed.
 #pragma once
 
 #include <climits>
@@ -28,10 +32,11 @@ struct rgbd360_graph_state {      // device + pinned host copy
 
 struct PgDev {
     int N, E, nbV, nbE;
-    const int *ei, *ej, *row_ptr, *inc, *is_free;
-    const double *Z, *Om;
+    const int *ei, *ej, *row_ptr, *inc, *is_free, *kind;      // kind: RGBD360_GRAPH_ROBUST_* of an enabled edge, -1 of a disabled one
+    const double *Z, *Om, *delta;
     double *T, *Tt;
-    double *r, *W, *b, *echi2, *A;          // per edge (A: diagnostics only, may be null)
+    double *r, *W, *b, *echi2, *A;          // per edge (echi2: the raw s; A: diagnostics only, may be null)
+    double *erho, *ew;                       // per edge: rho (mode 2 only) and the weight w
     double *D, *g, *Minv, *dd, *x, *res, *z, *p, *q;      // per vertex
     double *t;                               // per edge: W (p_i - p_j)
     double *rows_chi2, *rows_chi2_trial, *rows_rz0, *rows_rz /* [2][nbV] */, *rows_pq, *rows_maxx, *rows_bad;
@@ -133,15 +138,16 @@ GN_HD inline void edge_residual(const double* Ti, const double* Tj, const double
     gn::se3_log(E, r);
 }
 
-// mode 0: linearise at T (r, W, b, per-edge chi2, A when asked, chi2 rows); mode 1: chi2 at the trial poses (per-edge chi2, trial rows);
-// mode 2: chi2 at T into the trial rows (rgbd360_graph_chi2)
+// mode 0: linearise at T (r, W, b, per-edge s and w, A when asked, cost rows); mode 1: the cost at the trial poses (per-edge s, trial rows);
+// mode 2: the cost at T into the trial rows, per-edge s, rho and w (rgbd360_graph_chi2, rgbd360_graph_edge_weights)
 template <int kMode>
 __global__ void __launch_bounds__(kBlock) k_pg_edges(PgDev G, int it) {
     __shared__ double lds[kBlock];
     if (it >= 0 && G.st->stop_it <= it) return;
     const int e = blockIdx.x * kBlock + threadIdx.x;
-    double chi2 = 0.0;
+    double rho = 0.0;
     if (e < G.E) {
+        double chi2 = 0.0, w = 0.0;
         const double* P = kMode == 1 ? G.Tt : G.T;
         const double* Om = G.Om + (size_t)e * 36;
         double r[6], M[16], Or[6];
@@ -153,6 +159,10 @@ __global__ void __launch_bounds__(kBlock) k_pg_edges(PgDev G, int it) {
         }
         for (int i = 0; i < 6; ++i) chi2 += r[i] * Or[i];
         G.echi2[e] = chi2;
+        const int kind = G.kind[e];
+        if (kind >= 0) gn::robust_rho_w(kind, G.delta[e], chi2, &rho, &w);
+        if (kMode != 1) G.ew[e] = w;
+        if (kMode == 2) G.erho[e] = rho;
         if (kMode == 0) {
             double J[36], Ad[36], A[36], OA[36];
             gn::se3_jl_inv(r, J);
@@ -164,20 +174,20 @@ __global__ void __launch_bounds__(kBlock) k_pg_edges(PgDev G, int it) {
                 for (int rr = 0; rr <= c; ++rr) {
                     double s = 0.0;
                     for (int k = 0; k < 6; ++k) s += A[rr * 6 + k] * OA[c * 6 + k];
-                    W[c * 6 + rr] = s;
-                    W[rr * 6 + c] = s;
+                    W[c * 6 + rr] = w * s;
+                    W[rr * 6 + c] = w * s;
                 }
             for (int i = 0; i < 6; ++i) {
                 double s = 0.0;
                 for (int k = 0; k < 6; ++k) s += A[i * 6 + k] * Or[k];
-                G.b[(size_t)e * 6 + i] = s;
+                G.b[(size_t)e * 6 + i] = w * s;
                 G.r[(size_t)e * 6 + i] = r[i];
             }
             if (G.A)
                 for (int k = 0; k < 36; ++k) G.A[(size_t)e * 36 + k] = A[k];
         }
     }
-    const double row = block_sum(chi2, lds);
+    const double row = block_sum(rho, lds);
     if (threadIdx.x == 0) (kMode == 0 ? G.rows_chi2 : G.rows_chi2_trial)[blockIdx.x] = row;
 }
 
@@ -423,11 +433,16 @@ struct rgbd360_graph {
     std::vector<char> fixed;
     std::vector<int> ei, ej;
     std::vector<double> Z, Om;        // 16 / 36 per edge (Om symmetrised)
-    bool dirty = true;                // vertices, flags or edges changed since the CSR and edge arrays were uploaded
+    std::vector<int> kind;            // per edge: RGBD360_GRAPH_ROBUST_*
+    std::vector<double> delta;
+    std::vector<char> enabled;
+    bool dirty = true;                // vertices, flags, edges or enabled flags changed since the CSR and edge arrays were uploaded
+    bool settings_dirty = true;       // kinds or deltas changed since the two per-edge setting arrays were uploaded
+    std::vector<int> kind_up;         // what the kernels read: kind, or -1 for a disabled edge
     std::vector<int> is_free;         // per vertex: not fixed and not isolated (as of the last upload)
     int n_fixed = 0, n_isolated = 0, n_free = 0;
-    DevBuf<int> d_ei, d_ej, d_row_ptr, d_inc, d_is_free;
-    DevBuf<double> d_Z, d_Om, d_T, d_Tt, d_edge, d_vert, d_rows, d_A;
+    DevBuf<int> d_ei, d_ej, d_row_ptr, d_inc, d_is_free, d_kind;
+    DevBuf<double> d_delta, d_Z, d_Om, d_T, d_Tt, d_edge, d_vert, d_rows, d_A;
     DevBuf<rgbd360_graph_state> d_state;
     PinnedBuf<rgbd360_graph_state> h_state;
     DevBuf<rgbd360_graph_iteration> d_trace;
@@ -469,12 +484,15 @@ int graph_upload(rgbd360_graph* g, bool with_A, int max_trace) {
     const int nbV = std::max(1, (N + pg::kBlock - 1) / pg::kBlock), nbE = std::max(1, (E + pg::kBlock - 1) / pg::kBlock);
     const size_t n1 = std::max(N, 1), e1 = std::max(E, 1);
     PgDev& G = g->G;
+    const bool settings = g->dirty || g->settings_dirty;
     if (g->dirty) {
-        std::vector<int> row_ptr(N + 1, 0), inc(2 * (size_t)E);
-        for (int e = 0; e < E; ++e) { row_ptr[g->ei[e] + 1]++; row_ptr[g->ej[e] + 1]++; }
+        std::vector<int> row_ptr(N + 1, 0), inc(2 * (size_t)E);      // (a disabled edge is in no row: inc may end short of 2 E)
+        for (int e = 0; e < E; ++e)
+            if (g->enabled[e]) { row_ptr[g->ei[e] + 1]++; row_ptr[g->ej[e] + 1]++; }
         for (int v = 0; v < N; ++v) row_ptr[v + 1] += row_ptr[v];
         std::vector<int> at(row_ptr.begin(), row_ptr.end() - 1);
-        for (int e = 0; e < E; ++e) {      // a vertex's row lists its edges in edge order: side 0 = `from`, 1 = `to`
+        for (int e = 0; e < E; ++e) {      // a vertex's row lists its enabled edges in edge order: side 0 = `from`, 1 = `to`
+            if (!g->enabled[e]) continue;
             inc[at[g->ei[e]]++] = e * 2;
             inc[at[g->ej[e]]++] = e * 2 + 1;
         }
@@ -489,7 +507,8 @@ int graph_upload(rgbd360_graph* g, bool with_A, int max_trace) {
         PGC(g, g->d_ei.ensure(e1)); PGC(g, g->d_ej.ensure(e1)); PGC(g, g->d_row_ptr.ensure(n1 + 1)); PGC(g, g->d_inc.ensure(2 * e1));
         PGC(g, g->d_is_free.ensure(n1)); PGC(g, g->d_Z.ensure(16 * e1)); PGC(g, g->d_Om.ensure(36 * e1));
         PGC(g, g->d_T.ensure(16 * n1)); PGC(g, g->d_Tt.ensure(16 * n1));
-        PGC(g, g->d_edge.ensure((size_t)(6 + 36 + 6 + 1 + 6) * e1));
+        PGC(g, g->d_edge.ensure((size_t)(6 + 36 + 6 + 1 + 6 + 2) * e1));
+        PGC(g, g->d_kind.ensure(e1)); PGC(g, g->d_delta.ensure(e1));
         PGC(g, g->d_vert.ensure((size_t)(36 + 6 + 36 + 6 + 6 * 5) * n1));
         PGC(g, g->d_rows.ensure((size_t)2 * nbE + (size_t)7 * nbV));
         PGC(g, g->d_state.ensure(1)); PGC(g, g->h_state.ensure(1));
@@ -507,7 +526,9 @@ int graph_upload(rgbd360_graph* g, bool with_A, int max_trace) {
         G.ei = g->d_ei; G.ej = g->d_ej; G.row_ptr = g->d_row_ptr; G.inc = g->d_inc; G.is_free = g->d_is_free;
         G.Z = g->d_Z; G.Om = g->d_Om; G.T = g->d_T; G.Tt = g->d_Tt;
         double* pe = g->d_edge;
-        G.r = pe; pe += 6 * e1; G.W = pe; pe += 36 * e1; G.b = pe; pe += 6 * e1; G.echi2 = pe; pe += e1; G.t = pe;
+        G.r = pe; pe += 6 * e1; G.W = pe; pe += 36 * e1; G.b = pe; pe += 6 * e1; G.echi2 = pe; pe += e1; G.t = pe; pe += 6 * e1;
+        G.erho = pe; pe += e1; G.ew = pe;
+        G.kind = g->d_kind; G.delta = g->d_delta;
         double* pv = g->d_vert;
         G.D = pv; pv += 36 * n1; G.g = pv; pv += 6 * n1; G.Minv = pv; pv += 36 * n1; G.dd = pv; pv += 6 * n1;
         G.x = pv; pv += 6 * n1; G.res = pv; pv += 6 * n1; G.z = pv; pv += 6 * n1; G.p = pv; pv += 6 * n1; G.q = pv;
@@ -517,6 +538,14 @@ int graph_upload(rgbd360_graph* g, bool with_A, int max_trace) {
         G.st = g->d_state;
         g->dirty = false;
     }
+    if (settings && E) {      // two words per edge: all a change of kind or delta costs
+        g->kind_up.resize(E);
+        for (int e = 0; e < E; ++e) g->kind_up[e] = g->enabled[e] ? g->kind[e] : -1;
+        PGC(g, hipMemcpyAsync(g->d_kind, g->kind_up.data(), sizeof(int) * E, hipMemcpyHostToDevice, s));
+        PGC(g, hipMemcpyAsync(g->d_delta, g->delta.data(), sizeof(double) * E, hipMemcpyHostToDevice, s));
+        PGC(g, hipStreamSynchronize(s));      // the setters may write kind_up's sources before the next launch
+    }
+    g->settings_dirty = false;
     if (with_A) PGC(g, g->d_A.ensure(36 * e1));
     G.A = with_A ? g->d_A.get() : nullptr;
     PGC(g, g->d_trace.ensure(std::max(max_trace, 1)));
@@ -535,8 +564,9 @@ int graph_put_state(rgbd360_graph* g, double lambda) {
     return 0;
 }
 
-// chi2 at the current poses: the edge kernel's partial rows, re-added here in ascending order like every device consumer does
-int graph_chi2_now(rgbd360_graph* g, double* chi2, double* per_edge) {
+// The cost at the current poses: the edge kernel's partial rows, re-added here in ascending order like every device consumer does;
+// per edge (each may be null) the raw s, rho and w
+int graph_chi2_now(rgbd360_graph* g, double* chi2, double* per_edge, double* rho = nullptr, double* w = nullptr) {
     const int E = g->E();
     *chi2 = 0.0;
     if (!E) return 0;
@@ -547,6 +577,8 @@ int graph_chi2_now(rgbd360_graph* g, double* chi2, double* per_edge) {
     std::vector<double> rows(G.nbE);
     PGC(g, hipMemcpyAsync(rows.data(), G.rows_chi2_trial, sizeof(double) * G.nbE, hipMemcpyDeviceToHost, s));
     if (per_edge) PGC(g, hipMemcpyAsync(per_edge, G.echi2, sizeof(double) * E, hipMemcpyDeviceToHost, s));
+    if (rho) PGC(g, hipMemcpyAsync(rho, G.erho, sizeof(double) * E, hipMemcpyDeviceToHost, s));
+    if (w) PGC(g, hipMemcpyAsync(w, G.ew, sizeof(double) * E, hipMemcpyDeviceToHost, s));
     PGC(g, hipStreamSynchronize(s));
     for (int k = 0; k < G.nbE; ++k) *chi2 += rows[k];
     return 0;
@@ -581,6 +613,7 @@ int rgbd360_graph_n_edges(const rgbd360_graph* g) { return g ? g->E() : -1; }
 int rgbd360_graph_clear(rgbd360_graph* g) {
     if (!g) return -1;
     g->T.clear(); g->fixed.clear(); g->ei.clear(); g->ej.clear(); g->Z.clear(); g->Om.clear(); g->trace.clear();
+    g->kind.clear(); g->delta.clear(); g->enabled.clear();
     g->dirty = true;
     return 0;
 }
@@ -625,6 +658,9 @@ int rgbd360_graph_add_edges(rgbd360_graph* g, int n, const int* from, const int*
     for (int k = 0; k < n; ++k) {
         g->ei.push_back(from[k]);
         g->ej.push_back(to[k]);
+        g->kind.push_back(RGBD360_GRAPH_ROBUST_NONE);
+        g->delta.push_back(1.0);
+        g->enabled.push_back(1);
         for (int m = 0; m < 16; ++m) g->Z.push_back((double)rel_poses[(size_t)16 * k + m]);
         for (int c = 0; c < 6; ++c)
             for (int r = 0; r < 6; ++r)
@@ -681,6 +717,64 @@ int rgbd360_graph_chi2(rgbd360_graph* g, double* chi2, double* per_edge) {
     int rc = graph_upload(g, false, 0);
     if (rc) return rc;
     return graph_chi2_now(g, chi2, per_edge);
+}
+
+int rgbd360_graph_set_edge_robust(rgbd360_graph* g, int first, int n, const int* kinds, const double* deltas) {
+    if (!g) return -1;
+    if (n < 0 || first < 0 || (long long)first + n > g->E()) return graph_fail(g, -1, "edge range outside the graph");
+    if (n == 0) return 0;
+    if (!kinds) return graph_fail(g, -1, "null pointer");
+    for (int k = 0; k < n; ++k) {      // all of them before anything changes
+        const std::string who = "edge " + std::to_string(first + k) + ": ";
+        if (kinds[k] < RGBD360_GRAPH_ROBUST_NONE || kinds[k] > RGBD360_GRAPH_ROBUST_GEMAN_MCCLURE)
+            return graph_fail(g, -1, who + "kind = " + std::to_string(kinds[k]) + " is no robust kind");
+        if (kinds[k] != RGBD360_GRAPH_ROBUST_NONE) {
+            if (!deltas) return graph_fail(g, -1, who + "a robust kind needs a delta (null pointer)");
+            if (!std::isfinite(deltas[k]) || !(deltas[k] > 0.0)) return graph_fail(g, -1, who + "delta must be finite and > 0");
+        }
+    }
+    for (int k = 0; k < n; ++k) {
+        g->kind[first + k] = kinds[k];
+        if (deltas && kinds[k] != RGBD360_GRAPH_ROBUST_NONE) g->delta[first + k] = deltas[k];
+    }
+    g->settings_dirty = true;
+    return 0;
+}
+
+int rgbd360_graph_set_edge_enabled(rgbd360_graph* g, int first, int n, const uint8_t* enabled) {
+    if (!g) return -1;
+    if (n < 0 || first < 0 || (long long)first + n > g->E()) return graph_fail(g, -1, "edge range outside the graph");
+    if (n == 0) return 0;
+    if (!enabled) return graph_fail(g, -1, "null pointer");
+    for (int k = 0; k < n; ++k) {
+        const char en = enabled[k] ? 1 : 0;
+        if (g->enabled[first + k] != en) {      // the incidence lists are built again at the next call that runs a kernel
+            g->enabled[first + k] = en;
+            g->dirty = true;
+        }
+    }
+    return 0;
+}
+
+int rgbd360_graph_get_edge_state(rgbd360_graph* g, int first, int n, int* kinds, double* deltas, uint8_t* enabled) {
+    if (!g) return -1;
+    if (n < 0 || first < 0 || (long long)first + n > g->E()) return graph_fail(g, -1, "edge range outside the graph");
+    for (int k = 0; k < n; ++k) {
+        if (kinds) kinds[k] = g->kind[first + k];
+        if (deltas) deltas[k] = g->delta[first + k];
+        if (enabled) enabled[k] = g->enabled[first + k] ? 1 : 0;
+    }
+    return 0;
+}
+
+int rgbd360_graph_edge_weights(rgbd360_graph* g, double* cost, double* s, double* rho, double* w) {
+    if (!g) return -1;
+    int rc = graph_upload(g, false, 0);
+    if (rc) return rc;
+    double c = 0.0;
+    rc = graph_chi2_now(g, &c, s, rho, w);
+    if (cost) *cost = c;
+    return rc;
 }
 
 int rgbd360_graph_optimize(rgbd360_graph* g, const rgbd360_graph_params* params, rgbd360_graph_result* result) {

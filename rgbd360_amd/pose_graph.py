@@ -24,6 +24,7 @@ from .register import Rgbd360Error, _ptr
 from .voxel_map import _as_dict
 
 ILL_POSED = 1     # RGBD360_ILL_POSED
+ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_GEMAN_MCCLURE = 0, 1, 2, 3     # RGBD360_GRAPH_ROBUST_*
 
 
 def _poses_cm(T, what):
@@ -146,6 +147,42 @@ class PoseGraph:
         f = np.ascontiguousarray(np.asarray(fixed).reshape(-1), np.uint8)
         self._check(self._L.rgbd360_graph_set_fixed(self._handle(), int(first), int(f.size), _ptr(f)))
 
+    # ---- robust and switchable edges
+    def set_edge_robust(self, first: int, kinds, deltas=None):
+        """Kind (ROBUST_*) and delta of the edges from `first` on; a scalar kind or delta is broadcast against the other.  deltas may be
+        None only when every kind is ROBUST_NONE."""
+        k = np.asarray(kinds, np.int32)
+        d = None if deltas is None else np.asarray(deltas, np.float64)
+        sizes = {a.size for a in (k, d) if a is not None and a.ndim}
+        if len(sizes) > 1:
+            raise Rgbd360Error("PoseGraph.set_edge_robust: one kind and one delta per edge (or scalars)")
+        n = sizes.pop() if sizes else 1
+        k = np.ascontiguousarray(np.broadcast_to(k.reshape(-1) if k.ndim else k, (n,)))
+        if d is not None:
+            d = np.ascontiguousarray(np.broadcast_to(d.reshape(-1) if d.ndim else d, (n,)))
+        self._check(self._L.rgbd360_graph_set_edge_robust(self._handle(), int(first), int(n), _ptr(k), None if d is None else _ptr(d)))
+
+    def set_edge_enabled(self, first: int, enabled):
+        """Switches the edges from `first` on off (False) or on; a disabled edge adds nothing to the cost or the normal equations."""
+        f = np.ascontiguousarray(np.asarray(enabled).reshape(-1) != 0, np.uint8)
+        self._check(self._L.rgbd360_graph_set_edge_enabled(self._handle(), int(first), int(f.size), _ptr(f)))
+
+    def edge_state(self):
+        """(kinds [E] int32, deltas [E] float64, enabled [E] bool)."""
+        E = self.n_edges
+        k, d, f = np.zeros(max(E, 1), np.int32), np.zeros(max(E, 1), np.float64), np.zeros(max(E, 1), np.uint8)
+        self._check(self._L.rgbd360_graph_get_edge_state(self._handle(), 0, E, _ptr(k), _ptr(d), _ptr(f)))
+        return k[:E], d[:E], f[:E].astype(bool)
+
+    def edge_weights(self):
+        """(cost, s [E], rho [E], w [E]) float64 at the current poses: the raw s = r^T Omega r of every edge, the robust rho and the
+        weight w = d rho / d s (both 0 for a disabled edge); cost is what chi2() returns."""
+        E = self.n_edges
+        c = C.c_double()
+        s, rho, w = (np.zeros(max(E, 1), np.float64) for _ in range(3))
+        self._check(self._L.rgbd360_graph_edge_weights(self._handle(), C.byref(c), _ptr(s), _ptr(rho), _ptr(w)))
+        return c.value, s[:E], rho[:E], w[:E]
+
     def poses(self, first: int = 0, n=None) -> np.ndarray:
         """[n, 4, 4] float32."""
         n = self.n_vertices - int(first) if n is None else int(n)
@@ -174,7 +211,8 @@ class PoseGraph:
         return _as_dict(res)
 
     def chi2(self, per_edge: bool = False):
-        """chi2 at the current poses; with per_edge also the [E] float64 terms."""
+        """The cost at the current poses (the sum of rho over the enabled edges); with per_edge also the [E] float64 raw terms
+        r^T Omega r of every edge, enabled or not."""
         c = C.c_double()
         pe = np.zeros(max(self.n_edges, 1), np.float64) if per_edge else None
         self._check(self._L.rgbd360_graph_chi2(self._handle(), C.byref(c), None if pe is None else _ptr(pe)))
