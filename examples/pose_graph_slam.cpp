@@ -8,6 +8,10 @@
 //     with the new keyframe at the current graph poses (FrameStore::overlapMatrix at the coarsest level + overlapCandidates; the
 //     reference scores connections by the SSO of a finished alignment, LoopClosure360.h:321, 360), so that alignments are only spent
 //     on pairs that share space;
+//     with radius sigmas k (10th argument) the radius grows with what the graph knows about the pair: one relativeCovariances call of all
+//     earlier keyframes against the new one gives C_ab, and a keyframe is a candidate when |t_ab| <= radius + k sigma_t with
+//     sigma_t = sqrt(variance_factor * lambda_max(translation block of C_ab)) -- after a long odometry chain the new keyframe's pose relative
+//     to the old ones has drifted, which is exactly when a fixed radius around the current estimate misses the closure;
 //   2 optimizeGraph() (KFsphere_SLAM.cpp:679-689) on the device (rgbd360/PoseGraph.hpp);
 //     with a robust delta (9th argument) every closure edge gets a Cauchy kernel of that delta (g2o's setRobustKernel; the odometry edges
 //     stay quadratic), closures whose weight ends below 0.1 are switched off and the graph is optimised once more, so that an alignment
@@ -20,8 +24,9 @@
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/pose_graph_slam.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o pose_graph_slam
 // Usage:  pose_graph_slam <dir> <n_frames> <width> <height> [max avDepthResidual = 0.9] [closure radius in m = 1.0] [closures per keyframe = 3]
-//         [minimum overlap score = 0: the radius rule alone] [robust delta = 0: quadratic closures]
+//         [minimum overlap score = 0: the radius rule alone] [robust delta = 0: quadratic closures] [radius sigmas = 0: the fixed radius]
 // Prints  keyframe <frame> vertex <v> status <s> pose <16 floats, column-major, world <- keyframe, before any optimisation>
+//         uncertainty <a> <b> <sigma_t in m>   (only with radius sigmas: every earlier keyframe a against the new keyframe b)
 //         candidate <a> <b> score <x>          (only with a minimum overlap score)
 //         closure <from> <to> status <s>
 //         weight <from> <to> <w>               (only with a robust delta: every closure after each optimisation, 0 for one switched off)
@@ -94,6 +99,30 @@ static double distance(const Mat4f& A, const Mat4f& B) {
     return std::sqrt(s);
 }
 
+// the largest eigenvalue of the symmetric 3x3 translation block of a covariance (cyclic Jacobi rotations)
+static double largestTranslationVariance(const rgbd360::PoseGraph::Mat6d& C) {
+    double A[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) A[r][c] = C(r, c);
+    for (int sweep = 0; sweep < 16; ++sweep)
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                if (A[p][q] == 0.0) continue;
+                const double th = 0.5 * std::atan2(2.0 * A[p][q], A[q][q] - A[p][p]), c = std::cos(th), s = std::sin(th);
+                for (int k = 0; k < 3; ++k) {      // A <- A G, then A <- G^T A
+                    const double a = A[k][p], b = A[k][q];
+                    A[k][p] = c * a - s * b;
+                    A[k][q] = s * a + c * b;
+                }
+                for (int k = 0; k < 3; ++k) {
+                    const double a = A[p][k], b = A[q][k];
+                    A[p][k] = c * a - s * b;
+                    A[q][k] = s * a + c * b;
+                }
+            }
+    return std::max(A[0][0], std::max(A[1][1], A[2][2]));
+}
+
 struct KeyFrame {
     int frame;
     std::unique_ptr<Frame> images;      // kept: the map is re-posed from them
@@ -102,7 +131,7 @@ struct KeyFrame {
 
 int main(int argc, char** argv) {
     if (argc < 5) {
-        fprintf(stderr, "usage: %s <dir> <n_frames> <width> <height> [max avDepthResidual] [closure radius] [closures per keyframe] [min overlap score] [robust delta]\n", argv[0]);
+        fprintf(stderr, "usage: %s <dir> <n_frames> <width> <height> [max avDepthResidual] [closure radius] [closures per keyframe] [min overlap score] [robust delta] [radius sigmas]\n", argv[0]);
         return 2;
     }
     const std::string dir = argv[1];
@@ -112,7 +141,8 @@ int main(int argc, char** argv) {
     const int max_closures = argc > 7 ? atoi(argv[7]) : 3;
     const double min_overlap = argc > 8 ? atof(argv[8]) : 0.0;
     const double robust_delta = argc > 9 ? atof(argv[9]) : 0.0;
-    if (n < 1 || n > 4096 || max_closures < 0 || !(robust_delta >= 0.0)) return 2;
+    const double radius_sigmas = argc > 10 ? atof(argv[10]) : 0.0;
+    if (n < 1 || n > 4096 || max_closures < 0 || !(robust_delta >= 0.0) || !(radius_sigmas >= 0.0)) return 2;
     try {
         rgbd360::RegisterPhotoICP align360;
         align360.setNumPyr(4);
@@ -158,9 +188,21 @@ int main(int argc, char** argv) {
             guess = Mat4f::Identity();
             // ... and one round against the nearest earlier keyframes within the radius, each from the pose the graph gives it now
             std::vector<std::pair<double, int>> near;
+            std::vector<double> slack(kf > 0 ? kf : 0, 0.0);      // per earlier keyframe: radius sigmas x the 1-sigma translation uncertainty of the pair
+            if (radius_sigmas > 0.0 && kf > 0) {
+                std::vector<int> from(kf), to(kf, v);
+                for (int u = 0; u < kf; ++u) from[u] = u;
+                const std::vector<rgbd360::PoseGraph::Mat6d> C = graph.relativeCovariances(from, to);      // (all zeros when the call is ill-posed)
+                for (int u = 0; u < kf; ++u) {
+                    const double var = graph.covResult().variance_factor * largestTranslationVariance(C[u]);
+                    const double sigma_t = var > 0.0 ? std::sqrt(var) : 0.0;
+                    printf("uncertainty %d %d %.6g\n", u, v, sigma_t);
+                    slack[u] = radius_sigmas * sigma_t;
+                }
+            }
             for (int u = 0; u < kf; ++u) {
                 const double d = distance(keyframes[u].pose, keyframes[v].pose);
-                if (d <= radius) near.push_back({d, u});
+                if (d <= radius + slack[u]) near.push_back({d, u});
             }
             std::sort(near.begin(), near.end());
             if (min_overlap > 0.0 && !near.empty()) {      // rank and cut by overlap instead of by distance

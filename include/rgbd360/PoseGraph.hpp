@@ -25,6 +25,7 @@ class PoseGraph {
         const int rc = rgbd360_graph_create(ctx, &g_);
         if (rc != 0) throw std::runtime_error("rgbd360_graph_create (" + std::to_string(rc) + "): " + rgbd360_last_error(ctx));
         rgbd360_graph_default_params(&params_);
+        rgbd360_graph_default_cov_params(&cov_params_);
     }
     ~PoseGraph() { rgbd360_graph_destroy(g_); }
     PoseGraph(const PoseGraph&) = delete;
@@ -101,6 +102,31 @@ class PoseGraph {
         if (n) check(rgbd360_graph_get_trace(g_, n, nullptr, t.data()), "rgbd360_graph_get_trace");
         return t;
     }
+    // g2o's computeMarginals.  Sigma_vv of the vertices, 6x6 blocks of the inverse of the Gauss-Newton matrix at the current poses in the
+    // update tangent (translation first); covResult() holds the status, the per-call counts and the variance factor cost / dof by which a
+    // caller scales a covariance before gating on it (alignment Hessians are overconfident information matrices, rgbd360_hip.h).
+    // Returns one Mat6d per query; throws on bad arguments only: RGBD360_ILL_POSED and RGBD360_NOT_CONVERGED are covResult().status.
+    struct Mat6d {
+        double m[36];      // column-major
+        double operator()(int r, int c) const { return m[c * 6 + r]; }
+    };
+    rgbd360_graph_cov_params& covParams() { return cov_params_; }      // cg_max_iters 1000, cg_tol 1e-10
+    std::vector<Mat6d> marginals(const std::vector<int>& vertices) {
+        std::vector<Mat6d> cov(vertices.size());
+        check(rgbd360_graph_marginals(g_, (int)vertices.size(), vertices.data(), &cov_params_, cov.empty() ? nullptr : cov[0].m, nullptr, nullptr,
+                                      &cov_result_), "rgbd360_graph_marginals");
+        return cov;
+    }
+    // C_ij of the pairs (from[k], to[k]): the covariance of the left perturbation of T_i^-1 T_j, commensurate with the inverse information
+    // matrix of an edge (i, j, Z)
+    std::vector<Mat6d> relativeCovariances(const std::vector<int>& from, const std::vector<int>& to) {
+        if (from.size() != to.size()) throw std::runtime_error("PoseGraph::relativeCovariances: one from and one to per pair");
+        std::vector<Mat6d> cov(to.size());
+        check(rgbd360_graph_relative_covariances(g_, (int)to.size(), from.data(), to.data(), &cov_params_, cov.empty() ? nullptr : cov[0].m, nullptr,
+                                                 nullptr, &cov_result_), "rgbd360_graph_relative_covariances");
+        return cov;
+    }
+    const rgbd360_graph_cov_result& covResult() const { return cov_result_; }
     rgbd360_graph* handle() { return g_; }
 
    private:
@@ -111,6 +137,8 @@ class PoseGraph {
     rgbd360_graph* g_ = nullptr;
     rgbd360_graph_params params_{};
     rgbd360_graph_result result_{};
+    rgbd360_graph_cov_params cov_params_{};
+    rgbd360_graph_cov_result cov_result_{};
 };
 
 }  // namespace rgbd360

@@ -42,7 +42,8 @@ enum {
     RGBD360_ILL_POSED = 1,      /* rank(H + lambda diag H) != 6, RPI.h:4682-4690: pose_out = last accepted pose */
     RGBD360_NO_VALID_PIXELS = 2, /* the error pass found no residual (the reference would divide by zero) */
     RGBD360_MAP_FULL = 3,       /* rgbd360_map_insert_*: points of new voxels found no free slot (within the probe bound) and were dropped (counted) */
-    RGBD360_MAP_MISMATCH = 4    /* rgbd360_map_remove_* / _move_*: points were asked to leave that the map does not hold (counted); its content is then unspecified */
+    RGBD360_MAP_MISMATCH = 4,   /* rgbd360_map_remove_* / _move_*: points were asked to leave that the map does not hold (counted); its content is then unspecified */
+    RGBD360_NOT_CONVERGED = 5   /* rgbd360_graph_marginals / _relative_covariances: columns did not reach cg_tol within cg_max_iters (counted); everything is written */
 };
 
 /* Replaces the constructor defaults + setters of RegisterPhotoICP (RPI.h:201-221, 224-269) and the
@@ -522,8 +523,34 @@ int    rgbd360_map_render_sphere_dev(rgbd360_map* map, int rows, int cols, const
  *              converges linearly: robust runs want tol_update around 1e-8; at 1e-10 the loop often ends on lambda_max instead.
  * The host builds and uploads the incidence lists again when an enabled flag changed; a change of kind or delta uploads two arrays of one
  * word per edge.
+ *   covariance rgbd360_graph_marginals and rgbd360_graph_relative_covariances (csrc/pose_graph_cov.h; g2o's computeMarginals) recover 6x6 blocks of
+ *              H^-1.  H is the Gauss-Newton matrix at the CURRENT poses with lambda = 0 over the free vertices: per enabled edge
+ *              W_e = w_e A^T Omega A with the robust weight w_e, disabled edges absent, fixed and isolated vertices as above -- the matrix
+ *              the linearisation and the assembly of rgbd360_graph_optimize build.  The calls change neither poses, nor edge state, nor
+ *              the trace of the last optimisation: a following rgbd360_graph_optimize gives the bits it would have given without them.
+ *                marginal of v        Sigma_vv, the diagonal block of H^-1, in the update tangent (v; w) of T_v <- se3_exp(x_v) T_v.  A fixed
+ *                                     or isolated vertex gives an exact zero block with cg_iterations 0.
+ *                relative (i, j)      C_ij = Ad(T_i^-1) (Sigma_ii + Sigma_jj - Sigma_ij - Sigma_ji) Ad(T_i^-1)^T, i = from, j = to: the first-order
+ *                                     covariance of the left perturbation xi in T_i^-1 T_j <- exp(xi) T_i^-1 T_j, the tangent of the residual of
+ *                                     an edge (i, j, Z), so commensurate with Omega^-1 of such an edge.  Computed from ONE block solve
+ *                                     H X = E_j - E_i as (E_j - E_i)^T X, not from two marginals; a fixed end contributes no E; i == j gives zeros.
+ *              Both are symmetrised as (M + M^T) / 2 in float64 and are NOT multiplied by the variance factor.
+ *              cost is the bits rgbd360_graph_chi2 returns, dof = 6 (enabled edges) - 6 (free vertices), variance_factor = cost / dof when
+ *              dof > 0, else 1: the a-posteriori variance factor sigma0^2.  Alignment Hessians used as Omega are overconfident (DESIGN.md
+ *              3.18), so a caller who gates on a covariance scales it by variance_factor.
+ *   gauge      a queried free vertex in a connected component (over enabled edges) without a fixed vertex makes H singular: the host finds
+ *              it with a union-find, launches nothing, writes nothing to the outputs and returns RGBD360_ILL_POSED; the message names the
+ *              first such query.
+ *   cov. solve conjugate gradients as above (same preconditioner, same stop rule |r|_M <= cg_tol |r_0|_M) per right-hand side, six per query,
+ *              up to 16 queries in lock step, further queries batch after batch; every column has its own scalars and stop word and is
+ *              frozen once it stopped, so a query's bits do not depend on what shares its batch or on the order of the queries.  A query is
+ *              finished when its six columns are; cg_iterations / cg_residual report the largest of the six.  p.q <= 0 on an unfinished
+ *              column, or a diagonal block without a Cholesky factor: RGBD360_ILL_POSED.  Columns that have not stopped after cg_max_iters:
+ *              RGBD360_NOT_CONVERGED, everything is still written, n_not_converged counts the queries that have such a column and the
+ *              per-query arrays tell which (cg_residual > cg_tol).  Sums as above; one stream synchronisation per batch.
  * Out of scope: the second-order robust term, dynamic covariance scaling and switch variables, an adaptive delta, robust weights inside
- * the dense alignment, marginalisation, incremental solving, SE(2), landmarks, several GPUs, a stronger preconditioner. */
+ * the dense alignment, marginalisation (removing vertices from the graph), the full dense covariance, incremental solving, SE(2),
+ * landmarks, several GPUs, a stronger preconditioner. */
 typedef struct rgbd360_graph rgbd360_graph;
 enum { RGBD360_GRAPH_ROBUST_NONE = 0, RGBD360_GRAPH_ROBUST_HUBER = 1, RGBD360_GRAPH_ROBUST_CAUCHY = 2, RGBD360_GRAPH_ROBUST_GEMAN_MCCLURE = 3 };
 typedef struct {
@@ -578,6 +605,30 @@ int  rgbd360_graph_get_edge_state(rgbd360_graph* g, int first, int n, int* kinds
 int  rgbd360_graph_edge_weights(rgbd360_graph* g, double* cost, double* s, double* rho, double* w);
 /* the first min(max_trace, iterations) records of the last rgbd360_graph_optimize; *n_trace (may be NULL): iterations */
 int  rgbd360_graph_get_trace(rgbd360_graph* g, int max_trace, int* n_trace, rgbd360_graph_iteration* trace);
+typedef struct {
+    int    cg_max_iters;       /* per right-hand side, 1 .. 100000: 1000 */
+    double cg_tol;             /* in (0, 1): 1e-10 */
+} rgbd360_graph_cov_params;
+typedef struct {
+    int status;                /* RGBD360_OK / ILL_POSED / NOT_CONVERGED */
+    int n_queries, n_not_converged;
+    int cg_iterations_max;     /* over the queries */
+    double cg_residual_max;
+    long long dof;             /* 6 (enabled edges) - 6 (free vertices) */
+    double cost;               /* the bits rgbd360_graph_chi2 returns */
+    double variance_factor;    /* cost / dof when dof > 0, else 1 */
+    int n_fixed, n_isolated;
+} rgbd360_graph_cov_result;
+void rgbd360_graph_default_cov_params(rgbd360_graph_cov_params* p);
+/* Sigma_vv of the n vertices `vertices` (`covariance` above): cov holds n x 36 doubles, each block column-major; cg_iterations and
+ * cg_residual (n each) and result may be NULL, params NULL = the defaults.  Returns the status (also in result->status); -1 and nothing
+ * launched when an index is no vertex (the message names the first such query), an array is NULL with n > 0, cg_max_iters is outside
+ * 1 .. 100000 or cg_tol is not in (0, 1).  n == 0 returns RGBD360_OK. */
+int  rgbd360_graph_marginals(rgbd360_graph* g, int n, const int* vertices, const rgbd360_graph_cov_params* params, double* cov,
+                             int* cg_iterations, double* cg_residual, rgbd360_graph_cov_result* result);
+/* C_ij of the n pairs (from[k], to[k]); arguments and return value as above. */
+int  rgbd360_graph_relative_covariances(rgbd360_graph* g, int n, const int* from, const int* to, const rgbd360_graph_cov_params* params,
+                                        double* cov, int* cg_iterations, double* cg_residual, rgbd360_graph_cov_result* result);
 
 /* ---- one process, several GPUs (BASELINE.json configs[3]) ---------------------------------------------------
  * The sequence path shards by independent frame pairs: device d gets the contiguous pairs rgbd360_shard_range(n_frames-1, d,

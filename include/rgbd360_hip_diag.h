@@ -156,6 +156,12 @@ int rgbd360_graph_apply(rgbd360_graph* g, double lambda, const double* x, double
  * update, direction), [6] the trial poses, [7] chi2 at the trial poses, [8] the decision, [9] one of those launches returning at once on
  * the state word.  The poses are not changed. */
 int rgbd360_graph_time_kernels(rgbd360_graph* g, int reps, float avg_us[10]);
+/* The kernels of one covariance batch (rgbd360_graph_marginals of the n <= 16 vertices `vertices`, 6 n columns in lock step) under HIP
+ * events at the current poses, averages over `reps` launches in microseconds: avg_us[0] the start of the columns, [1] the edge product
+ * with one thread per (edge, column), [2] the same product with one thread per (edge, query) holding W for six columns, [3] - [5]
+ * gather, update, direction, [6] the B^T X / adjoint / symmetrisation kernel, [7] a launch returning at once on the columns' stop words.
+ * The poses are not changed. */
+int rgbd360_graph_time_cov_kernels(rgbd360_graph* g, int n, const int* vertices, int reps, float avg_us[8]);
 
 /* The render's kernels (rgbd360_map_render_*, rgbd360_hip.h) under HIP events, averages over `reps` back-to-back launches in
  * microseconds: avg_us[0] k_vmap_render_depth, [1] k_vmap_render_key, [2] k_vmap_render_resolve (all four planes), [3] the whole

@@ -44,6 +44,7 @@ SYMBOLS = [
     "rgbd360_graph_default_params", "rgbd360_graph_optimize", "rgbd360_graph_get_poses", "rgbd360_graph_chi2", "rgbd360_graph_get_trace",
     "rgbd360_graph_linearize", "rgbd360_graph_apply", "rgbd360_graph_time_kernels",
     "rgbd360_graph_set_edge_robust", "rgbd360_graph_set_edge_enabled", "rgbd360_graph_get_edge_state", "rgbd360_graph_edge_weights",
+    "rgbd360_graph_default_cov_params", "rgbd360_graph_marginals", "rgbd360_graph_relative_covariances", "rgbd360_graph_time_cov_kernels",
 ]
 
 
@@ -139,6 +140,16 @@ class GraphResult(C.Structure):         # rgbd360_graph_result
 class GraphIteration(C.Structure):      # rgbd360_graph_iteration
     _fields_ = [("chi2", C.c_double), ("chi2_trial", C.c_double), ("lambda_", C.c_double), ("accepted", C.c_int), ("cg_iterations", C.c_int),
                 ("cg_residual", C.c_double), ("max_update", C.c_double)]
+
+
+class GraphCovParams(C.Structure):      # rgbd360_graph_cov_params
+    _fields_ = [("cg_max_iters", C.c_int), ("cg_tol", C.c_double)]
+
+
+class GraphCovResult(C.Structure):      # rgbd360_graph_cov_result
+    _fields_ = [("status", C.c_int), ("n_queries", C.c_int), ("n_not_converged", C.c_int), ("cg_iterations_max", C.c_int),
+                ("cg_residual_max", C.c_double), ("dof", C.c_longlong), ("cost", C.c_double), ("variance_factor", C.c_double),
+                ("n_fixed", C.c_int), ("n_isolated", C.c_int)]
 
 
 class OverlapParams(C.Structure):        # rgbd360_overlap_params
@@ -384,5 +395,10 @@ def load() -> C.CDLL:
     L.rgbd360_graph_set_edge_enabled.argtypes = [vp, i32, i32, vp]
     L.rgbd360_graph_get_edge_state.argtypes = [vp, i32, i32, vp, vp, vp]
     L.rgbd360_graph_edge_weights.argtypes = [vp, C.POINTER(C.c_double), vp, vp, vp]
+    L.rgbd360_graph_default_cov_params.argtypes = [C.POINTER(GraphCovParams)]
+    L.rgbd360_graph_default_cov_params.restype = None
+    L.rgbd360_graph_marginals.argtypes = [vp, i32, vp, C.POINTER(GraphCovParams), vp, vp, vp, C.POINTER(GraphCovResult)]
+    L.rgbd360_graph_relative_covariances.argtypes = [vp, i32, vp, vp, C.POINTER(GraphCovParams), vp, vp, vp, C.POINTER(GraphCovResult)]
+    L.rgbd360_graph_time_cov_kernels.argtypes = [vp, i32, vp, i32, vp]
     _lib = L
     return L

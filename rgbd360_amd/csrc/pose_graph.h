@@ -443,6 +443,8 @@ struct rgbd360_graph {
     int n_fixed = 0, n_isolated = 0, n_free = 0;
     DevBuf<int> d_ei, d_ej, d_row_ptr, d_inc, d_is_free, d_kind;
     DevBuf<double> d_delta, d_Z, d_Om, d_T, d_Tt, d_edge, d_vert, d_rows, d_A;
+    DevBuf<double> d_cov;             // the column vectors, rows and outputs of a covariance batch (pose_graph_cov.h)
+    DevBuf<int> d_cov_i;
     DevBuf<rgbd360_graph_state> d_state;
     PinnedBuf<rgbd360_graph_state> h_state;
     DevBuf<rgbd360_graph_iteration> d_trace;

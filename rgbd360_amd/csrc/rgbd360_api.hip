@@ -1858,5 +1858,6 @@ void rgbd360_ctx_set_error(rgbd360_ctx* ctx, const char* msg) { ctx->err = msg ?
 #include "frame_store.h"
 #include "store_overlap.h"
 #include "pose_graph.h"
+#include "pose_graph_cov.h"
 #include "multi_gpu.h"
 

@@ -24,6 +24,7 @@ from .register import Rgbd360Error, _ptr
 from .voxel_map import _as_dict
 
 ILL_POSED = 1     # RGBD360_ILL_POSED
+NOT_CONVERGED = 5     # RGBD360_NOT_CONVERGED
 ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_GEMAN_MCCLURE = 0, 1, 2, 3     # RGBD360_GRAPH_ROBUST_*
 
 
@@ -227,6 +228,53 @@ class PoseGraph:
         self._check(self._L.rgbd360_graph_get_trace(self._handle(), n.value, None, tr))
         return [_as_dict(t) for t in tr[:n.value]]
 
+    # ---- covariances
+    def cov_params(self, **fields):
+        """The defaults (cg_max_iters 1000, cg_tol 1e-10) with the given fields replaced."""
+        p = _lib.GraphCovParams()
+        self._L.rgbd360_graph_default_cov_params(C.byref(p))
+        for name, v in fields.items():
+            if not hasattr(p, name):
+                raise TypeError(f"GraphCovParams has no field {name!r}")
+            if v is not None:
+                setattr(p, name, v)
+        return p
+
+    def _covariances(self, frm, to, params):
+        j = np.ascontiguousarray(np.asarray(to).reshape(-1), np.int32)
+        i = None if frm is None else np.ascontiguousarray(np.asarray(frm).reshape(-1), np.int32)
+        if i is not None and i.size != j.size:
+            raise Rgbd360Error("PoseGraph.relative_covariances: one from and one to per pair")
+        n = int(j.size)
+        cov = np.zeros((max(n, 1), 36), np.float64)
+        its, rr = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float64)
+        res = _lib.GraphCovResult()
+        p = self.cov_params(**params)
+        if i is None:
+            self._check(self._L.rgbd360_graph_marginals(self._handle(), n, _ptr(j), C.byref(p), _ptr(cov), _ptr(its), _ptr(rr), C.byref(res)))
+        else:
+            self._check(self._L.rgbd360_graph_relative_covariances(self._handle(), n, _ptr(i), _ptr(j), C.byref(p), _ptr(cov), _ptr(its), _ptr(rr),
+                                                                   C.byref(res)))
+        out = _as_dict(res)
+        out["cg_iterations"], out["cg_residual"] = its[:n], rr[:n]
+        if res.status != 0:
+            out["message"] = self._L.rgbd360_graph_last_error(self._h).decode()
+        return cov[:n].reshape(-1, 6, 6).transpose(0, 2, 1).copy(), out
+
+    def marginals(self, vertices, **params):
+        """(cov [n,6,6] float64, result dict): Sigma_vv, the 6x6 diagonal blocks of the inverse of the Gauss-Newton matrix at the current
+        poses (lambda = 0, robust weights, disabled edges absent), in the update tangent (v; w); exact zeros for fixed and isolated
+        vertices.  The result holds status (0, ILL_POSED, NOT_CONVERGED), n_queries, n_not_converged, cg_iterations_max, cg_residual_max,
+        dof, cost, variance_factor (cost / dof: scale a covariance by it before gating on it), n_fixed, n_isolated, the per-query arrays
+        cg_iterations and cg_residual, and `message` when the status is not 0.  params: cg_max_iters, cg_tol."""
+        return self._covariances(None, vertices, params)
+
+    def relative_covariances(self, from_, to, **params):
+        """(cov [n,6,6] float64, result dict): C_ij = Ad(T_i^-1) (Sigma_ii + Sigma_jj - Sigma_ij - Sigma_ji) Ad(T_i^-1)^T of the pairs
+        (from_[k], to[k]), the covariance of the left perturbation of T_i^-1 T_j -- the tangent of an edge (i, j, Z)'s residual, so
+        commensurate with the inverse information of such an edge.  The result is that of marginals()."""
+        return self._covariances(from_, to, params)
+
     # ---- diagnostics (rgbd360_hip_diag.h)
     def linearize(self):
         """(r [E,6], A [E,6,6]) float64 at the current poses."""
@@ -247,4 +295,11 @@ class PoseGraph:
     def time_kernels(self, reps: int = 20) -> np.ndarray:
         out = np.zeros(10, np.float32)
         self._check(self._L.rgbd360_graph_time_kernels(self._handle(), int(reps), _ptr(out)))
+        return out
+
+    def time_cov_kernels(self, vertices, reps: int = 20) -> np.ndarray:
+        """rgbd360_graph_time_cov_kernels: [8] float32 microseconds of the kernels of one covariance batch of up to 16 marginals."""
+        v = np.ascontiguousarray(np.asarray(vertices).reshape(-1), np.int32)
+        out = np.zeros(8, np.float32)
+        self._check(self._L.rgbd360_graph_time_cov_kernels(self._handle(), int(v.size), _ptr(v), int(reps), _ptr(out)))
         return out
