@@ -12,11 +12,14 @@
 //   k_pg_trial              T' = se3_exp(x) T per vertex, max |x| rows
 //   k_pg_edges<chi2>        the cost (sum of rho) at T'
 //   k_pg_decide             accept / reject, lambda, the trace record, the stop test
+// The four k_pg_cg_* kernels are the one block-Jacobi PCG of this library: they work on a view (PgCg) of `ncols` right-hand sides,
+// blockIdx.y is the column, every column has its own rows, alpha, beta and stop words.  The optimiser runs them on one column with the
+// damping lambda diag D; the covariance batch (pose_graph_cov.h) on up to 96 columns without it.
 // House rules: no floating-point atomics; a vertex adds its edges in CSR (= edge list) order; every global scalar is a table of
-// per-workgroup partial rows which each consumer re-adds in ascending order in its prologue (pg_rows_sum), so that all blocks take the
+// per-workgroup partial rows which each consumer re-adds in ascending order in its prologue (pg::rows_fold), so that all blocks take the
 // same decision from the same bits; no cooperative launch, no spin barrier, no ticket.  A kernel never reads a state word it writes:
-// the stop words are "first index that does not run" (stop_it, cg_stop_at), compared with the index the launch carries, so a launch of
-// a finished loop or of a converged PCG returns at once, and the block that records a stop cannot change what its own launch does.
+// the stop words are "first index that does not run" (stop_it, a column's stop_at), compared with the index the launch carries, so a
+// launch of a finished loop or of a converged PCG returns at once, and the block that records a stop cannot change what its own launch does.
 // Robust and switchable edges: per edge one word `kind` (RGBD360_GRAPH_ROBUST_*, -1 = disabled) and one `delta`.  A disabled edge has
 // rho = w = 0 and is in no vertex's CSR row, so W, b and t of it are written and never read; a quadratic edge has rho = s and w = an exact
 // 1.0, so a graph of quadratic, enabled edges keeps the bits it had before the kinds existed.
@@ -25,7 +28,7 @@
 #include <climits>
 
 struct rgbd360_graph_state {      // device + pinned host copy
-    int stop_it, cg_stop_at, cg_it, status, accepted, converged, iterations, pad;
+    int stop_it, cg_stop_at, cg_it, status, accepted, converged, iterations, cg_broke;      // cg_*: the optimiser's PCG column (graph_cg)
     long long cg_total;
     double lambda, chi2, chi2_initial, chi2_final, cg_res;
 };
@@ -44,52 +47,45 @@ struct PgDev {
     rgbd360_graph_iteration* trace;
 };
 
+// What the PCG kernels touch: `ncols` systems H x = b on the graph G describes (W per edge, Minv per vertex), solved in lock step.
+struct PgCg {
+    int ncols;
+    double *x, *res, *z, *p, *q;               // [column][6 N]
+    double* t;                                 // [column][6 E]
+    double *rows_rz0, *rows_rz /* [column][2][nbV] */, *rows_pq;      // [column][nbV]
+    int *stop_at, *it, *broke;                 // per column: the first iteration that does not run, iterations done, p.q <= 0 was met
+    double* resid;                             // per column: |r|_M / |r_0|_M
+    const double* dd;                          // [6 N]: the damping lambda diag D added to H, or null (none)
+};
+
 namespace pg {
 
 constexpr int kBlock = 256;
 
-// the sum of rows[0..n) in ascending order, the same bits in every thread of every block
-__device__ inline double rows_sum(const double* rows, int n, double* lds) {
+struct Sum { __device__ static double of(double acc, double v) { return acc + v; } };
+struct Max { __device__ static double of(double acc, double v) { return v > acc ? v : acc; } };      // (a NaN never raises it)
+
+// rows[0..n) folded in ascending order from 0.0, the same bits in every thread of every block
+template <class Fold>
+__device__ inline double rows_fold(const double* rows, int n, double* lds) {
     double s = 0.0;
     for (int base = 0; base < n; base += kBlock) {
         __syncthreads();
         if (base + (int)threadIdx.x < n) lds[threadIdx.x] = rows[base + threadIdx.x];
         __syncthreads();
         const int m = n - base < kBlock ? n - base : kBlock;
-        for (int k = 0; k < m; ++k) s += lds[k];
+        for (int k = 0; k < m; ++k) s = Fold::of(s, lds[k]);
     }
     __syncthreads();
     return s;
 }
-__device__ inline double rows_max(const double* rows, int n, double* lds) {
-    double s = 0.0;
-    for (int base = 0; base < n; base += kBlock) {
-        __syncthreads();
-        if (base + (int)threadIdx.x < n) lds[threadIdx.x] = rows[base + threadIdx.x];
-        __syncthreads();
-        const int m = n - base < kBlock ? n - base : kBlock;
-        for (int k = 0; k < m; ++k) s = lds[k] > s ? lds[k] : s;
-    }
-    __syncthreads();
-    return s;
-}
-// one partial row: the block's values added by a fixed tree
-__device__ inline double block_sum(double v, double* lds) {
+// one partial row: the block's values folded by a fixed tree
+template <class Fold>
+__device__ inline double block_fold(double v, double* lds) {
     lds[threadIdx.x] = v;
     __syncthreads();
     for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) lds[threadIdx.x] += lds[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double out = lds[0];
-    __syncthreads();
-    return out;
-}
-__device__ inline double block_max(double v, double* lds) {
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) lds[threadIdx.x] = lds[threadIdx.x + s] > lds[threadIdx.x] ? lds[threadIdx.x + s] : lds[threadIdx.x];
+        if ((int)threadIdx.x < s) lds[threadIdx.x] = Fold::of(lds[threadIdx.x], lds[threadIdx.x + s]);
         __syncthreads();
     }
     const double out = lds[0];
@@ -187,14 +183,14 @@ __global__ void __launch_bounds__(kBlock) k_pg_edges(PgDev G, int it) {
                 for (int k = 0; k < 36; ++k) G.A[(size_t)e * 36 + k] = A[k];
         }
     }
-    const double row = block_sum(rho, lds);
+    const double row = block_fold<Sum>(rho, lds);
     if (threadIdx.x == 0) (kMode == 0 ? G.rows_chi2 : G.rows_chi2_trial)[blockIdx.x] = row;
 }
 
 __global__ void __launch_bounds__(kBlock) k_pg_assemble(PgDev G, int it) {
     __shared__ double lds[kBlock];
     if (it >= 0 && G.st->stop_it <= it) return;
-    const double chi2 = rows_sum(G.rows_chi2, G.nbE, lds);
+    const double chi2 = rows_fold<Sum>(G.rows_chi2, G.nbE, lds);
     const double lambda = G.st->lambda;
     const int v = blockIdx.x * kBlock + threadIdx.x;
     double rz = 0.0, bad = 0.0;
@@ -241,8 +237,8 @@ __global__ void __launch_bounds__(kBlock) k_pg_assemble(PgDev G, int it) {
             }
         }
     }
-    const double row = block_sum(rz, lds);
-    const double badrow = block_max(bad, lds);
+    const double row = block_fold<Sum>(rz, lds);
+    const double badrow = block_fold<Max>(bad, lds);
     if (threadIdx.x == 0) {
         G.rows_rz0[blockIdx.x] = row;
         G.rows_rz[blockIdx.x] = row;
@@ -257,105 +253,134 @@ __global__ void __launch_bounds__(kBlock) k_pg_assemble(PgDev G, int it) {
     }
 }
 
-__global__ void __launch_bounds__(kBlock) k_pg_cg_edge(PgDev G, int it, int k) {
-    if (it >= 0 && (G.st->stop_it <= it || G.st->cg_stop_at <= k)) return;
-    const int e = blockIdx.x * kBlock + threadIdx.x;
-    if (e >= G.E) return;
-    const double* pi = G.p + (size_t)G.ei[e] * 6;
-    const double* pj = G.p + (size_t)G.ej[e] * 6;
-    const double* W = G.W + (size_t)e * 36;
+// ---- the block-Jacobi PCG: iteration k of every column of C that has not stopped.  `it` is the Levenberg-Marquardt iteration the launch
+// belongs to, or -1 outside the optimiser's loop (stop_it then decides nothing).  stop_it is never negative, so the test on `it` changes
+// nothing where the launches of the loop, which carry it >= 0, did without it.
+// Has column `col` of this launch nothing to do?  Both stop words are loaded before either is tested -- hence & and |, not && and || --
+// so that a launch waits for one round trip to memory, not for two in a row.
+__device__ inline bool cg_stopped(const PgDev& G, const PgCg& C, int col, int it, int k) {
+    const int stop_it = G.st->stop_it, stop_at = C.stop_at[col];
+    return ((it >= 0) & (stop_it <= it)) | (stop_at <= k);
+}
+
+// one column of one edge: t = W (p_i - p_j)
+__device__ inline void cg_edge_column(const PgDev& G, const PgCg& C, int e, int col, const double* W) {
+    const double* pi = C.p + ((size_t)col * G.N + G.ei[e]) * 6;
+    const double* pj = C.p + ((size_t)col * G.N + G.ej[e]) * 6;
+    double* t = C.t + ((size_t)col * G.E + e) * 6;
     double d[6];
     for (int i = 0; i < 6; ++i) d[i] = pi[i] - pj[i];
     for (int i = 0; i < 6; ++i) {
         double s = 0.0;
         for (int c = 0; c < 6; ++c) s += W[c * 6 + i] * d[c];
-        G.t[(size_t)e * 6 + i] = s;
+        t[i] = s;
     }
 }
 
-__global__ void __launch_bounds__(kBlock) k_pg_cg_gather(PgDev G, int it, int k) {
+// Two work mappings with the same bits.  kPerQuery false: grid (nbE, columns), W read from memory; true: grid (nbE, columns / 6), W held in
+// registers for the six columns of a covariance query
+template <bool kPerQuery>
+__global__ void __launch_bounds__(kBlock) k_pg_cg_edge(PgDev G, PgCg C, int it, int k) {
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    if (!kPerQuery) {
+        const int col = blockIdx.y;
+        if (cg_stopped(G, C, col, it, k) || e >= G.E) return;
+        cg_edge_column(G, C, e, col, G.W + (size_t)e * 36);
+    } else {
+        const int c0 = blockIdx.y * 6;
+        bool none = true;
+        for (int c = 0; c < 6; ++c) none &= cg_stopped(G, C, c0 + c, it, k);
+        if (none || e >= G.E) return;
+        double W[36];
+        for (int m = 0; m < 36; ++m) W[m] = G.W[(size_t)e * 36 + m];
+        for (int c = 0; c < 6; ++c)
+            if (C.stop_at[c0 + c] > k) cg_edge_column(G, C, e, c0 + c, W);
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_pg_cg_gather(PgDev G, PgCg C, int it, int k) {
     __shared__ double lds[kBlock];
-    if (it >= 0 && (G.st->stop_it <= it || G.st->cg_stop_at <= k)) return;
+    const int col = blockIdx.y;
+    if (cg_stopped(G, C, col, it, k)) return;
     const int v = blockIdx.x * kBlock + threadIdx.x;
     double pq = 0.0;
     if (v < G.N && G.is_free[v]) {
-        const double* p = G.p + (size_t)v * 6;
-        const double* dd = G.dd + (size_t)v * 6;
+        const size_t o = ((size_t)col * G.N + v) * 6;
+        const double* tc = C.t + (size_t)col * G.E * 6;
         double q[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         for (int a = G.row_ptr[v]; a < G.row_ptr[v + 1]; ++a) {
             const int code = G.inc[a];
-            const double* t = G.t + (size_t)(code >> 1) * 6;
+            const double* t = tc + (size_t)(code >> 1) * 6;
             if (code & 1)
                 for (int i = 0; i < 6; ++i) q[i] -= t[i];
             else
                 for (int i = 0; i < 6; ++i) q[i] += t[i];
         }
+        if (C.dd)      // (uniform over the grid; no zero vector in its place: -0.0 + 0.0 would flip a sign bit of q)
+            for (int i = 0; i < 6; ++i) q[i] += C.dd[(size_t)v * 6 + i] * C.p[o + i];
         for (int i = 0; i < 6; ++i) {
-            q[i] += dd[i] * p[i];
-            G.q[(size_t)v * 6 + i] = q[i];
-            pq += p[i] * q[i];
+            C.q[o + i] = q[i];
+            pq += C.p[o + i] * q[i];
         }
     }
-    const double row = block_sum(pq, lds);
-    if (threadIdx.x == 0) G.rows_pq[blockIdx.x] = row;
+    const double row = block_fold<Sum>(pq, lds);
+    if (threadIdx.x == 0) C.rows_pq[(size_t)col * G.nbV + blockIdx.x] = row;
 }
 
-__global__ void __launch_bounds__(kBlock) k_pg_cg_update(PgDev G, int it, int k) {
+__global__ void __launch_bounds__(kBlock) k_pg_cg_update(PgDev G, PgCg C, int it, int k) {
     __shared__ double lds[kBlock];
-    if (G.st->stop_it <= it || G.st->cg_stop_at <= k) return;
-    const double rz = rows_sum(G.rows_rz + (size_t)(k & 1) * G.nbV, G.nbV, lds);
-    const double pq = rows_sum(G.rows_pq, G.nbV, lds);
+    const int col = blockIdx.y;
+    if (cg_stopped(G, C, col, it, k)) return;
+    const double rz = rows_fold<Sum>(C.rows_rz + ((size_t)col * 2 + (k & 1)) * G.nbV, G.nbV, lds);
+    const double pq = rows_fold<Sum>(C.rows_pq + (size_t)col * G.nbV, G.nbV, lds);
     const bool go = pq > 0.0;
     const double alpha = go ? rz / pq : 0.0;
     const int v = blockIdx.x * kBlock + threadIdx.x;
     double rz_new = 0.0;
     if (go && v < G.N && G.is_free[v]) {
-        double* x = G.x + (size_t)v * 6;
-        double* res = G.res + (size_t)v * 6;
-        double* z = G.z + (size_t)v * 6;
-        const double* p = G.p + (size_t)v * 6;
-        const double* q = G.q + (size_t)v * 6;
+        const size_t o = ((size_t)col * G.N + v) * 6;
         const double* Minv = G.Minv + (size_t)v * 36;
         double rr[6];
         for (int i = 0; i < 6; ++i) {
-            x[i] += alpha * p[i];
-            rr[i] = res[i] - alpha * q[i];
-            res[i] = rr[i];
+            C.x[o + i] += alpha * C.p[o + i];
+            rr[i] = C.res[o + i] - alpha * C.q[o + i];
+            C.res[o + i] = rr[i];
         }
         for (int i = 0; i < 6; ++i) {
             double s = 0.0;
             for (int c = 0; c < 6; ++c) s += Minv[c * 6 + i] * rr[c];
-            z[i] = s;
+            C.z[o + i] = s;
             rz_new += rr[i] * s;
         }
     }
-    const double row = block_sum(rz_new, lds);
-    if (threadIdx.x == 0) G.rows_rz[(size_t)((k + 1) & 1) * G.nbV + blockIdx.x] = row;
+    const double row = block_fold<Sum>(rz_new, lds);
+    if (threadIdx.x == 0) C.rows_rz[((size_t)col * 2 + ((k + 1) & 1)) * G.nbV + blockIdx.x] = row;
 }
 
-__global__ void __launch_bounds__(kBlock) k_pg_cg_dir(PgDev G, int it, int k, double cg_tol) {
+__global__ void __launch_bounds__(kBlock) k_pg_cg_dir(PgDev G, PgCg C, int it, int k, double cg_tol) {
     __shared__ double lds[kBlock];
-    if (G.st->stop_it <= it || G.st->cg_stop_at <= k) return;
-    const double rz0 = rows_sum(G.rows_rz0, G.nbV, lds);
-    const double rz = rows_sum(G.rows_rz + (size_t)(k & 1) * G.nbV, G.nbV, lds);
-    const double pq = rows_sum(G.rows_pq, G.nbV, lds);
-    const double rz_new = rows_sum(G.rows_rz + (size_t)((k + 1) & 1) * G.nbV, G.nbV, lds);
-    const bool broke = !(pq > 0.0);      // nothing was updated (also the zero gradient: rz0 = 0)
+    const int col = blockIdx.y;
+    if (cg_stopped(G, C, col, it, k)) return;
+    const double rz0 = rows_fold<Sum>(C.rows_rz0 + (size_t)col * G.nbV, G.nbV, lds);
+    const double rz = rows_fold<Sum>(C.rows_rz + ((size_t)col * 2 + (k & 1)) * G.nbV, G.nbV, lds);
+    const double pq = rows_fold<Sum>(C.rows_pq + (size_t)col * G.nbV, G.nbV, lds);
+    const double rz_new = rows_fold<Sum>(C.rows_rz + ((size_t)col * 2 + ((k + 1) & 1)) * G.nbV, G.nbV, lds);
+    const bool broke = !(pq > 0.0);      // nothing was updated: H is not positive definite along p, or the column started at zero (rz0 = 0)
     const bool stop = broke || !(sqrt(rz_new > 0.0 ? rz_new : 0.0) > cg_tol * sqrt(rz0));
     if (!stop) {
         const double beta = rz_new / rz;
         const int v = blockIdx.x * kBlock + threadIdx.x;
         if (v < G.N && G.is_free[v]) {
-            double* p = G.p + (size_t)v * 6;
-            const double* z = G.z + (size_t)v * 6;
-            for (int i = 0; i < 6; ++i) p[i] = z[i] + beta * p[i];
+            const size_t o = ((size_t)col * G.N + v) * 6;
+            for (int i = 0; i < 6; ++i) C.p[o + i] = C.z[o + i] + beta * C.p[o + i];
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const double last = broke ? rz : rz_new;
-        G.st->cg_it = broke ? k : k + 1;
-        G.st->cg_res = rz0 > 0.0 ? sqrt((last > 0.0 ? last : 0.0) / rz0) : 0.0;
-        if (stop) G.st->cg_stop_at = k + 1;
+        C.it[col] = broke ? k : k + 1;
+        C.resid[col] = rz0 > 0.0 ? sqrt((last > 0.0 ? last : 0.0) / rz0) : 0.0;
+        if (broke) C.broke[col] = 1;
+        if (stop) C.stop_at[col] = k + 1;
     }
 }
 
@@ -381,17 +406,17 @@ __global__ void __launch_bounds__(kBlock) k_pg_trial(PgDev G, int it) {
             for (int k = 0; k < 16; ++k) Tt[k] = T[k];
         }
     }
-    const double row = block_max(mx, lds);
+    const double row = block_fold<Max>(mx, lds);
     if (threadIdx.x == 0) G.rows_maxx[blockIdx.x] = row;
 }
 
 __global__ void __launch_bounds__(kBlock) k_pg_decide(PgDev G, int it, int max_iters, double tol_update, double lambda_max) {
     __shared__ double lds[kBlock];
     if (G.st->stop_it <= it) return;
-    const double cur = rows_sum(G.rows_chi2, G.nbE, lds);
-    const double trial = rows_sum(G.rows_chi2_trial, G.nbE, lds);
-    const bool bad = rows_max(G.rows_bad, G.nbV, lds) > 0.0;
-    const double max_x = rows_max(G.rows_maxx, G.nbV, lds);
+    const double cur = rows_fold<Sum>(G.rows_chi2, G.nbE, lds);
+    const double trial = rows_fold<Sum>(G.rows_chi2_trial, G.nbE, lds);
+    const bool bad = rows_fold<Max>(G.rows_bad, G.nbV, lds) > 0.0;
+    const double max_x = rows_fold<Max>(G.rows_maxx, G.nbV, lds);
     const bool accept = !bad && trial < cur;
     const int v = blockIdx.x * kBlock + threadIdx.x;
     if (accept && v < G.N && G.is_free[v])
@@ -477,6 +502,71 @@ bool pg_finite(const float* v, int n) {
     return true;
 }
 
+// One device buffer cut into consecutive parts: the buffer's size is the sum of the list that hands out the pointers.
+template <class T>
+struct ArenaPart {
+    T** at;      // where the part's pointer goes
+    size_t count;
+};
+template <class T, size_t K>
+hipError_t arena_carve(DevBuf<T>& buf, const ArenaPart<T> (&parts)[K]) {
+    size_t total = 0;
+    for (const ArenaPart<T>& part : parts) total += part.count;
+    const hipError_t e = buf.ensure(total);
+    if (e != hipSuccess) return e;
+    T* p = buf;
+    for (const ArenaPart<T>& part : parts) {
+        *part.at = p;
+        p += part.count;
+    }
+    return hipSuccess;
+}
+
+// The optimiser's PCG: one column on the vectors and rows of G, damped by G.dd; its stop words are those of the device state, so that
+// k_pg_assemble starts it, k_pg_decide records it and the host reads it back with the state.  (cg_broke is written and never read.)
+PgCg graph_cg(const PgDev& G) {
+    PgCg C;
+    C.ncols = 1;
+    C.x = G.x; C.res = G.res; C.z = G.z; C.p = G.p; C.q = G.q; C.t = G.t;
+    C.rows_rz0 = G.rows_rz0; C.rows_rz = G.rows_rz; C.rows_pq = G.rows_pq;
+    C.stop_at = &G.st->cg_stop_at; C.it = &G.st->cg_it; C.broke = &G.st->cg_broke; C.resid = &G.st->cg_res;
+    C.dd = G.dd;
+    return C;
+}
+
+// One full iteration k of the PCG on every column of C.  per_query: the edge product's work mapping (k_pg_cg_edge), ncols = 6 queries then.
+void cg_launch_iteration(hipStream_t s, const PgDev& G, const PgCg& C, int it, int k, double cg_tol, bool per_query) {
+    const dim3 blk(pg::kBlock), gv(G.nbV, C.ncols);
+    if (per_query) hipLaunchKernelGGL(pg::k_pg_cg_edge<true>, dim3(G.nbE, C.ncols / 6), blk, 0, s, G, C, it, k);
+    else hipLaunchKernelGGL(pg::k_pg_cg_edge<false>, dim3(G.nbE, C.ncols), blk, 0, s, G, C, it, k);
+    hipLaunchKernelGGL(pg::k_pg_cg_gather, gv, blk, 0, s, G, C, it, k);
+    hipLaunchKernelGGL(pg::k_pg_cg_update, gv, blk, 0, s, G, C, it, k);
+    hipLaunchKernelGGL(pg::k_pg_cg_dir, gv, blk, 0, s, G, C, it, k, cg_tol);
+}
+
+// avg_us[w], w < n: the HIP-event average of `reps` launch(w) after one untimed launch(w), whose outputs are then the inputs the loop
+// would hand it.  prepare(w) runs first and may enqueue a change of the state (0, or the code to return).
+template <class Launch, class Prepare>
+int graph_time_slots(rgbd360_graph* g, int n, int reps, float* avg_us, Launch launch, Prepare prepare) {
+    rgbd360_ctx* ctx = g->ctx;
+    hipStream_t s = ctx->stream;
+    for (int which = 0; which < n; ++which) {
+        const int rc = prepare(which);
+        if (rc) return rc;
+        launch(which);
+        PGC(g, hipEventRecord(ctx->ev0, s));
+        for (int k = 0; k < reps; ++k) launch(which);
+        PGC(g, hipEventRecord(ctx->ev1, s));
+        PGC(g, hipGetLastError());
+        PGC(g, hipEventSynchronize(ctx->ev1));
+        float ms = 0.f;
+        PGC(g, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        avg_us[which] = ms * 1000.f / (float)reps;
+    }
+    PGC(g, hipStreamSynchronize(s));
+    return 0;
+}
+
 // Everything the kernels read, on the device: the CSR and the edge arrays when the graph changed, the poses always (128 bytes a vertex).
 // with_A: room for the diagnostics' per-edge Jacobians.
 int graph_upload(rgbd360_graph* g, bool with_A, int max_trace) {
@@ -509,10 +599,16 @@ int graph_upload(rgbd360_graph* g, bool with_A, int max_trace) {
         PGC(g, g->d_ei.ensure(e1)); PGC(g, g->d_ej.ensure(e1)); PGC(g, g->d_row_ptr.ensure(n1 + 1)); PGC(g, g->d_inc.ensure(2 * e1));
         PGC(g, g->d_is_free.ensure(n1)); PGC(g, g->d_Z.ensure(16 * e1)); PGC(g, g->d_Om.ensure(36 * e1));
         PGC(g, g->d_T.ensure(16 * n1)); PGC(g, g->d_Tt.ensure(16 * n1));
-        PGC(g, g->d_edge.ensure((size_t)(6 + 36 + 6 + 1 + 6 + 2) * e1));
+        const size_t bV = nbV, bE = nbE;
+        const ArenaPart<double> per_edge[] = {{&G.r, 6 * e1}, {&G.W, 36 * e1}, {&G.b, 6 * e1}, {&G.echi2, e1}, {&G.t, 6 * e1}, {&G.erho, e1}, {&G.ew, e1}};
+        const ArenaPart<double> per_vertex[] = {{&G.D, 36 * n1}, {&G.g, 6 * n1}, {&G.Minv, 36 * n1}, {&G.dd, 6 * n1}, {&G.x, 6 * n1}, {&G.res, 6 * n1},
+                                                {&G.z, 6 * n1}, {&G.p, 6 * n1}, {&G.q, 6 * n1}};
+        const ArenaPart<double> rows[] = {{&G.rows_chi2, bE}, {&G.rows_chi2_trial, bE}, {&G.rows_rz0, bV}, {&G.rows_rz, 2 * bV}, {&G.rows_pq, bV},
+                                          {&G.rows_maxx, bV}, {&G.rows_bad, bV}};
+        PGC(g, arena_carve(g->d_edge, per_edge));
         PGC(g, g->d_kind.ensure(e1)); PGC(g, g->d_delta.ensure(e1));
-        PGC(g, g->d_vert.ensure((size_t)(36 + 6 + 36 + 6 + 6 * 5) * n1));
-        PGC(g, g->d_rows.ensure((size_t)2 * nbE + (size_t)7 * nbV));
+        PGC(g, arena_carve(g->d_vert, per_vertex));
+        PGC(g, arena_carve(g->d_rows, rows));
         PGC(g, g->d_state.ensure(1)); PGC(g, g->h_state.ensure(1));
         if (E) {
             PGC(g, hipMemcpyAsync(g->d_ei, g->ei.data(), sizeof(int) * E, hipMemcpyHostToDevice, s));
@@ -527,16 +623,7 @@ int graph_upload(rgbd360_graph* g, bool with_A, int max_trace) {
         G.N = N; G.E = E; G.nbV = nbV; G.nbE = nbE;
         G.ei = g->d_ei; G.ej = g->d_ej; G.row_ptr = g->d_row_ptr; G.inc = g->d_inc; G.is_free = g->d_is_free;
         G.Z = g->d_Z; G.Om = g->d_Om; G.T = g->d_T; G.Tt = g->d_Tt;
-        double* pe = g->d_edge;
-        G.r = pe; pe += 6 * e1; G.W = pe; pe += 36 * e1; G.b = pe; pe += 6 * e1; G.echi2 = pe; pe += e1; G.t = pe; pe += 6 * e1;
-        G.erho = pe; pe += e1; G.ew = pe;
         G.kind = g->d_kind; G.delta = g->d_delta;
-        double* pv = g->d_vert;
-        G.D = pv; pv += 36 * n1; G.g = pv; pv += 6 * n1; G.Minv = pv; pv += 36 * n1; G.dd = pv; pv += 6 * n1;
-        G.x = pv; pv += 6 * n1; G.res = pv; pv += 6 * n1; G.z = pv; pv += 6 * n1; G.p = pv; pv += 6 * n1; G.q = pv;
-        double* pr = g->d_rows;
-        G.rows_chi2 = pr; pr += nbE; G.rows_chi2_trial = pr; pr += nbE; G.rows_rz0 = pr; pr += nbV; G.rows_rz = pr; pr += 2 * (size_t)nbV;
-        G.rows_pq = pr; pr += nbV; G.rows_maxx = pr; pr += nbV; G.rows_bad = pr;
         G.st = g->d_state;
         g->dirty = false;
     }
@@ -811,17 +898,13 @@ int rgbd360_graph_optimize(rgbd360_graph* g, const rgbd360_graph_params* params,
     const PgDev& G = g->G;
     rc = graph_put_state(g, P.lambda_init);
     if (rc) return rc;
+    const PgCg C = graph_cg(G);
     const dim3 blk(pg::kBlock), gv(G.nbV), ge(G.nbE);
     const rgbd360_graph_state& S = *g->h_state.get();
     for (int it = 0; it < P.max_iters; ++it) {
         hipLaunchKernelGGL(pg::k_pg_edges<0>, ge, blk, 0, s, G, it);
         hipLaunchKernelGGL(pg::k_pg_assemble, gv, blk, 0, s, G, it);
-        for (int k = 0; k < P.cg_max_iters; ++k) {
-            hipLaunchKernelGGL(pg::k_pg_cg_edge, ge, blk, 0, s, G, it, k);
-            hipLaunchKernelGGL(pg::k_pg_cg_gather, gv, blk, 0, s, G, it, k);
-            hipLaunchKernelGGL(pg::k_pg_cg_update, gv, blk, 0, s, G, it, k);
-            hipLaunchKernelGGL(pg::k_pg_cg_dir, gv, blk, 0, s, G, it, k, P.cg_tol);
-        }
+        for (int k = 0; k < P.cg_max_iters; ++k) cg_launch_iteration(s, G, C, it, k, P.cg_tol, false);
         hipLaunchKernelGGL(pg::k_pg_trial, gv, blk, 0, s, G, it);
         hipLaunchKernelGGL(pg::k_pg_edges<1>, ge, blk, 0, s, G, it);
         hipLaunchKernelGGL(pg::k_pg_decide, gv, blk, 0, s, G, it, P.max_iters, P.tol_update, P.lambda_max);
@@ -887,8 +970,9 @@ int rgbd360_graph_apply(rgbd360_graph* g, double lambda, const double* x, double
     hipLaunchKernelGGL(pg::k_pg_edges<0>, ge, blk, 0, s, G, -1);
     hipLaunchKernelGGL(pg::k_pg_assemble, gv, blk, 0, s, G, -1);
     PGC(g, hipMemcpyAsync(G.p, p.data(), sizeof(double) * 6 * N, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(pg::k_pg_cg_edge, ge, blk, 0, s, G, -1, 0);
-    hipLaunchKernelGGL(pg::k_pg_cg_gather, gv, blk, 0, s, G, -1, 0);
+    const PgCg C = graph_cg(G);
+    hipLaunchKernelGGL(pg::k_pg_cg_edge<false>, ge, blk, 0, s, G, C, -1, 0);
+    hipLaunchKernelGGL(pg::k_pg_cg_gather, gv, blk, 0, s, G, C, -1, 0);
     PGC(g, hipGetLastError());
     PGC(g, hipMemcpyAsync(y, G.q, sizeof(double) * 6 * N, hipMemcpyDeviceToHost, s));
     PGC(g, hipStreamSynchronize(s));      // (p is a local)
@@ -902,44 +986,34 @@ int rgbd360_graph_time_kernels(rgbd360_graph* g, int reps, float avg_us[10]) {
     if (rc) return rc;
     for (int k = 0; k < 10; ++k) avg_us[k] = 0.f;
     if (!g->N() || !g->E()) return 0;
-    rgbd360_ctx* ctx = g->ctx;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = g->ctx->stream;
     const PgDev& G = g->G;
     rc = graph_put_state(g, 1e-3);
     if (rc) return rc;
+    const PgCg C = graph_cg(G);
     const dim3 blk(pg::kBlock), gv(G.nbV), ge(G.nbE);
     const double inf = HUGE_VAL;
     auto launch = [&](int which) {
         switch (which) {
             case 0: hipLaunchKernelGGL(pg::k_pg_edges<0>, ge, blk, 0, s, G, 0); break;
             case 1: hipLaunchKernelGGL(pg::k_pg_assemble, gv, blk, 0, s, G, 0); break;
-            case 2: hipLaunchKernelGGL(pg::k_pg_cg_edge, ge, blk, 0, s, G, 0, 0); break;
-            case 3: hipLaunchKernelGGL(pg::k_pg_cg_gather, gv, blk, 0, s, G, 0, 0); break;
-            case 4: hipLaunchKernelGGL(pg::k_pg_cg_update, gv, blk, 0, s, G, 0, 0); break;
-            case 5: hipLaunchKernelGGL(pg::k_pg_cg_dir, gv, blk, 0, s, G, 0, 0, 0.0); break;
+            case 2: hipLaunchKernelGGL(pg::k_pg_cg_edge<false>, ge, blk, 0, s, G, C, 0, 0); break;
+            case 3: hipLaunchKernelGGL(pg::k_pg_cg_gather, gv, blk, 0, s, G, C, 0, 0); break;
+            case 4: hipLaunchKernelGGL(pg::k_pg_cg_update, gv, blk, 0, s, G, C, 0, 0); break;
+            case 5: hipLaunchKernelGGL(pg::k_pg_cg_dir, gv, blk, 0, s, G, C, 0, 0, 0.0); break;
             case 6: hipLaunchKernelGGL(pg::k_pg_trial, gv, blk, 0, s, G, 0); break;
             case 7: hipLaunchKernelGGL(pg::k_pg_edges<1>, ge, blk, 0, s, G, 0); break;
             case 8: hipLaunchKernelGGL(pg::k_pg_decide, gv, blk, 0, s, G, 0, INT_MAX, -1.0, inf); break;
-            default: hipLaunchKernelGGL(pg::k_pg_cg_edge, ge, blk, 0, s, G, 0, 0); break;
+            default: hipLaunchKernelGGL(pg::k_pg_cg_edge<false>, ge, blk, 0, s, G, C, 0, 0); break;
         }
     };
-    for (int which = 0; which < 10; ++which) {
-        if (which == 9) {      // the loop has ended: every launch returns on the state word
-            g->h_state.get()->stop_it = 0;
-            PGC(g, hipMemcpyAsync(g->d_state, g->h_state.get(), sizeof(rgbd360_graph_state), hipMemcpyHostToDevice, s));
-        }
-        launch(which);      // once untimed: its inputs are then what the loop would hand it
-        PGC(g, hipEventRecord(ctx->ev0, s));
-        for (int k = 0; k < reps; ++k) launch(which);
-        PGC(g, hipEventRecord(ctx->ev1, s));
-        PGC(g, hipGetLastError());
-        PGC(g, hipEventSynchronize(ctx->ev1));
-        float ms = 0.f;
-        PGC(g, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        avg_us[which] = ms * 1000.f / (float)reps;
-    }
-    PGC(g, hipStreamSynchronize(s));
-    return 0;
+    auto prepare = [&](int which) {      // slot 9: the loop has ended, every launch returns on the state word
+        if (which != 9) return 0;
+        g->h_state.get()->stop_it = 0;
+        PGC(g, hipMemcpyAsync(g->d_state, g->h_state.get(), sizeof(rgbd360_graph_state), hipMemcpyHostToDevice, s));
+        return 0;
+    };
+    return graph_time_slots(g, 10, reps, avg_us, launch, prepare);
 }
 
 }  // extern "C"

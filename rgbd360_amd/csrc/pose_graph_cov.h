@@ -1,18 +1,16 @@
 // pose_graph_cov.h -- marginal and relative pose covariances of the pose graph (rgbd360_graph_marginals, rgbd360_graph_relative_covariances,
-// include/rgbd360_hip.h).  Included by rgbd360_api.hip behind pose_graph.h, whose kernels it reuses unchanged for the
-// linearisation and the assembly at lambda = 0 (k_pg_edges<linearise>, k_pg_assemble: W, D, Minv = D^-1, dd = 0).
+// include/rgbd360_hip.h).  Included by rgbd360_api.hip behind pose_graph.h, whose kernels it reuses unchanged: the
+// linearisation and the assembly at lambda = 0 (k_pg_edges<linearise>, k_pg_assemble: W, D, Minv = D^-1), and the block-Jacobi PCG
+// (k_pg_cg_*) on a view of its own columns, without a damping vector and outside the optimiser's loop (it = -1).
 //
 // A 6x6 block of H^-1 is B^T X with H X = B, B = E_v (a marginal) or E_j - E_i (a relative covariance): six right-hand sides per query.
-// Up to kCovChunk queries, 6 columns each, run the block-Jacobi conjugate gradients of pose_graph.h in lock step; a batch is a fixed list
-// of launches, enqueued blindly by the host, and one stream synchronisation:
+// Up to kCovChunk queries, 6 columns each, run in lock step; a batch is a fixed list of launches, enqueued blindly by the host, and one
+// stream synchronisation:
 //   k_pgc_init              per (vertex, column): res = the column of B, z = Minv res, p = z, x = 0 -> r.z rows; the column's state words
-//   cg_max_iters times      k_pgc_edge (t_e = W (p_i - p_j)), k_pgc_gather (q = sum +-t_e, p.q rows), k_pgc_update (x, res, z, r.z rows),
-//                           k_pgc_dir (stop test, p = z + beta p)
+//   cg_max_iters times      k_pg_cg_edge, k_pg_cg_gather, k_pg_cg_update, k_pg_cg_dir (pose_graph.h)
 //   k_pgc_finish            per query: M = B^T X, Ad(T_i^-1) M Ad(T_i^-1)^T for a relative covariance, (M + M^T) / 2; iterations, residual, flags
 // Every column has its own rows ([column][workgroup]), alpha, beta and stop word; blockIdx.y is the column, so a column's arithmetic is that
-// of a batch which holds it alone, and a finished column is frozen (its launches return on its stop word).  House rules as in pose_graph.h:
-// no floating-point atomics, CSR order, rows re-added in ascending order, no kernel reads a state word it writes (stop_at is "the first
-// iteration that does not run", compared with the iteration the launch carries).
+// of a batch which holds it alone, and a finished column is frozen (its launches return on its stop word).
 // The edge product has two work mappings with the same bits: one thread per (edge, column), which reads the 36 doubles of W once per
 // column, and one thread per (edge, query), which holds W in registers for its six columns.  kCovEdgePerQuery chooses; the diagnostics
 // time both (rgbd360_graph_time_cov_kernels).  Measured on 16-query batches (profiles/pose_graph_cov_perf.txt): per query 8.4 us against
@@ -25,13 +23,9 @@ constexpr bool kCovEdgePerQuery = true;        // the edge product's work mappin
 enum { PGC_NOT_CONVERGED = 1, PGC_NOT_POSITIVE = 2 };      // per-query flags of k_pgc_finish
 
 struct PgCov {
-    int nq, ncols;                             // queries of this batch, 6 nq
-    const int *qi, *qj;                        // per query: `from` (-1: a marginal) and `to` / the vertex
-    double *x, *res, *z, *p, *q;               // [column][6 N]
-    double* t;                                 // [column][6 E]
-    double *rows_rz0, *rows_rz /* [column][2][nbV] */, *rows_pq;      // [column][nbV]
-    int *stop_at, *it, *broke;                 // per column
-    double* resid;                             // per column: |r|_M / |r_0|_M
+    PgCg cg;                                   // the 6 nq columns
+    int nq;                                    // queries of this batch
+    int *qi, *qj;                              // per query: `from` (-1: a marginal) and `to` / the vertex
     double* cov;                               // per query: 36, column-major
     int *q_it, *q_flags;                       // per query
     double* q_res;
@@ -61,141 +55,23 @@ __global__ void __launch_bounds__(kBlock) k_pgc_init(PgDev G, PgCov C) {
             }
         }
         for (int i = 0; i < 6; ++i) {
-            C.x[o + i] = 0.0;
-            C.res[o + i] = r[i];
-            C.z[o + i] = z[i];
-            C.p[o + i] = z[i];
-            C.q[o + i] = 0.0;
+            C.cg.x[o + i] = 0.0;
+            C.cg.res[o + i] = r[i];
+            C.cg.z[o + i] = z[i];
+            C.cg.p[o + i] = z[i];
+            C.cg.q[o + i] = 0.0;
         }
     }
-    const double row = block_sum(rz, lds);
+    const double row = block_fold<Sum>(rz, lds);
     if (threadIdx.x == 0) {
-        C.rows_rz0[(size_t)col * G.nbV + blockIdx.x] = row;
-        C.rows_rz[(size_t)col * 2 * G.nbV + blockIdx.x] = row;
+        C.cg.rows_rz0[(size_t)col * G.nbV + blockIdx.x] = row;
+        C.cg.rows_rz[(size_t)col * 2 * G.nbV + blockIdx.x] = row;
         if (blockIdx.x == 0) {
-            C.stop_at[col] = INT_MAX;
-            C.it[col] = 0;
-            C.broke[col] = 0;
-            C.resid[col] = 0.0;
+            C.cg.stop_at[col] = INT_MAX;
+            C.cg.it[col] = 0;
+            C.cg.broke[col] = 0;
+            C.cg.resid[col] = 0.0;
         }
-    }
-}
-
-// one column of one edge: t = W (p_i - p_j)
-__device__ inline void pgc_edge_column(const PgDev& G, const PgCov& C, int e, int col, const double* W) {
-    const double* pi = C.p + ((size_t)col * G.N + G.ei[e]) * 6;
-    const double* pj = C.p + ((size_t)col * G.N + G.ej[e]) * 6;
-    double* t = C.t + ((size_t)col * G.E + e) * 6;
-    double d[6];
-    for (int i = 0; i < 6; ++i) d[i] = pi[i] - pj[i];
-    for (int i = 0; i < 6; ++i) {
-        double s = 0.0;
-        for (int c = 0; c < 6; ++c) s += W[c * 6 + i] * d[c];
-        t[i] = s;
-    }
-}
-
-// kPerQuery false: grid (nbE, columns), W read from memory; true: grid (nbE, queries), W held for the query's six columns
-template <bool kPerQuery>
-__global__ void __launch_bounds__(kBlock) k_pgc_edge(PgDev G, PgCov C, int k) {
-    const int e = blockIdx.x * kBlock + threadIdx.x;
-    if (!kPerQuery) {
-        const int col = blockIdx.y;
-        if (C.stop_at[col] <= k || e >= G.E) return;
-        pgc_edge_column(G, C, e, col, G.W + (size_t)e * 36);
-    } else {
-        const int c0 = blockIdx.y * 6;
-        bool any = false;
-        for (int c = 0; c < 6; ++c) any |= C.stop_at[c0 + c] > k;
-        if (!any || e >= G.E) return;
-        double W[36];
-        for (int m = 0; m < 36; ++m) W[m] = G.W[(size_t)e * 36 + m];
-        for (int c = 0; c < 6; ++c)
-            if (C.stop_at[c0 + c] > k) pgc_edge_column(G, C, e, c0 + c, W);
-    }
-}
-
-__global__ void __launch_bounds__(kBlock) k_pgc_gather(PgDev G, PgCov C, int k) {
-    __shared__ double lds[kBlock];
-    const int col = blockIdx.y;
-    if (C.stop_at[col] <= k) return;
-    const int v = blockIdx.x * kBlock + threadIdx.x;
-    double pq = 0.0;
-    if (v < G.N && G.is_free[v]) {
-        const size_t o = ((size_t)col * G.N + v) * 6;
-        const double* tc = C.t + (size_t)col * G.E * 6;
-        double q[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int a = G.row_ptr[v]; a < G.row_ptr[v + 1]; ++a) {
-            const int code = G.inc[a];
-            const double* t = tc + (size_t)(code >> 1) * 6;
-            if (code & 1)
-                for (int i = 0; i < 6; ++i) q[i] -= t[i];
-            else
-                for (int i = 0; i < 6; ++i) q[i] += t[i];
-        }
-        for (int i = 0; i < 6; ++i) {
-            C.q[o + i] = q[i];
-            pq += C.p[o + i] * q[i];
-        }
-    }
-    const double row = block_sum(pq, lds);
-    if (threadIdx.x == 0) C.rows_pq[(size_t)col * G.nbV + blockIdx.x] = row;
-}
-
-__global__ void __launch_bounds__(kBlock) k_pgc_update(PgDev G, PgCov C, int k) {
-    __shared__ double lds[kBlock];
-    const int col = blockIdx.y;
-    if (C.stop_at[col] <= k) return;
-    const double rz = rows_sum(C.rows_rz + ((size_t)col * 2 + (k & 1)) * G.nbV, G.nbV, lds);
-    const double pq = rows_sum(C.rows_pq + (size_t)col * G.nbV, G.nbV, lds);
-    const bool go = pq > 0.0;
-    const double alpha = go ? rz / pq : 0.0;
-    const int v = blockIdx.x * kBlock + threadIdx.x;
-    double rz_new = 0.0;
-    if (go && v < G.N && G.is_free[v]) {
-        const size_t o = ((size_t)col * G.N + v) * 6;
-        const double* Minv = G.Minv + (size_t)v * 36;
-        double rr[6];
-        for (int i = 0; i < 6; ++i) {
-            C.x[o + i] += alpha * C.p[o + i];
-            rr[i] = C.res[o + i] - alpha * C.q[o + i];
-            C.res[o + i] = rr[i];
-        }
-        for (int i = 0; i < 6; ++i) {
-            double s = 0.0;
-            for (int c = 0; c < 6; ++c) s += Minv[c * 6 + i] * rr[c];
-            C.z[o + i] = s;
-            rz_new += rr[i] * s;
-        }
-    }
-    const double row = block_sum(rz_new, lds);
-    if (threadIdx.x == 0) C.rows_rz[((size_t)col * 2 + ((k + 1) & 1)) * G.nbV + blockIdx.x] = row;
-}
-
-__global__ void __launch_bounds__(kBlock) k_pgc_dir(PgDev G, PgCov C, int k, double cg_tol) {
-    __shared__ double lds[kBlock];
-    const int col = blockIdx.y;
-    if (C.stop_at[col] <= k) return;
-    const double rz0 = rows_sum(C.rows_rz0 + (size_t)col * G.nbV, G.nbV, lds);
-    const double rz = rows_sum(C.rows_rz + ((size_t)col * 2 + (k & 1)) * G.nbV, G.nbV, lds);
-    const double pq = rows_sum(C.rows_pq + (size_t)col * G.nbV, G.nbV, lds);
-    const double rz_new = rows_sum(C.rows_rz + ((size_t)col * 2 + ((k + 1) & 1)) * G.nbV, G.nbV, lds);
-    const bool broke = !(pq > 0.0);      // nothing was updated: H is not positive definite along p (or the column started at zero)
-    const bool stop = broke || !(sqrt(rz_new > 0.0 ? rz_new : 0.0) > cg_tol * sqrt(rz0));
-    if (!stop) {
-        const double beta = rz_new / rz;
-        const int v = blockIdx.x * kBlock + threadIdx.x;
-        if (v < G.N && G.is_free[v]) {
-            const size_t o = ((size_t)col * G.N + v) * 6;
-            for (int i = 0; i < 6; ++i) C.p[o + i] = C.z[o + i] + beta * C.p[o + i];
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const double last = broke ? rz : rz_new;
-        C.it[col] = broke ? k : k + 1;
-        C.resid[col] = rz0 > 0.0 ? sqrt((last > 0.0 ? last : 0.0) / rz0) : 0.0;
-        if (broke) C.broke[col] = 1;
-        if (stop) C.stop_at[col] = k + 1;
     }
 }
 
@@ -207,8 +83,8 @@ __global__ void __launch_bounds__(64) k_pgc_finish(PgDev G, PgCov C) {
     const int c = tid / 6, r = tid % 6;
     if (tid < 36) {
         const size_t oc = (size_t)(qd * 6 + c) * G.N;
-        double m = C.x[(oc + j) * 6 + r];      // x of a fixed or isolated vertex is 0
-        if (i >= 0) m -= C.x[(oc + i) * 6 + r];
+        double m = C.cg.x[(oc + j) * 6 + r];      // x of a fixed or isolated vertex is 0
+        if (i >= 0) m -= C.cg.x[(oc + i) * 6 + r];
         M[tid] = m;
     }
     if (i >= 0) {      // (uniform over the workgroup)
@@ -238,10 +114,10 @@ __global__ void __launch_bounds__(64) k_pgc_finish(PgDev G, PgCov C) {
         double res = 0.0;
         for (int m = 0; m < 6; ++m) {
             const int col = qd * 6 + m;
-            it = C.it[col] > it ? C.it[col] : it;
-            res = C.resid[col] > res ? C.resid[col] : res;
-            if (C.broke[col]) flags |= PGC_NOT_POSITIVE;
-            else if (C.stop_at[col] == INT_MAX) flags |= PGC_NOT_CONVERGED;
+            it = C.cg.it[col] > it ? C.cg.it[col] : it;
+            res = C.cg.resid[col] > res ? C.cg.resid[col] : res;
+            if (C.cg.broke[col]) flags |= PGC_NOT_POSITIVE;
+            else if (C.cg.stop_at[col] == INT_MAX) flags |= PGC_NOT_CONVERGED;
         }
         C.q_it[qd] = it;
         C.q_res[qd] = res;
@@ -256,31 +132,19 @@ namespace {
 // the device memory of one batch of nq queries (grows only), and C pointing into it
 int cov_buffers(rgbd360_graph* g, int nq, PgCov* out) {
     const PgDev& G = g->G;
-    const size_t cols = (size_t)6 * nq, n6 = (size_t)6 * std::max(G.N, 1), e6 = (size_t)6 * std::max(G.E, 1), nb = G.nbV;
-    PGC(g, g->d_cov.ensure(cols * (5 * n6 + e6 + 4 * nb + 1) + (size_t)nq * 37));
-    PGC(g, g->d_cov_i.ensure(cols * 3 + (size_t)nq * 4));
+    const size_t q = nq, cols = 6 * q, n6 = (size_t)6 * std::max(G.N, 1), e6 = (size_t)6 * std::max(G.E, 1), nb = G.nbV;
     PgCov C;
-    C.nq = nq; C.ncols = (int)cols;
-    double* pd = g->d_cov;
-    C.x = pd; pd += cols * n6; C.res = pd; pd += cols * n6; C.z = pd; pd += cols * n6; C.p = pd; pd += cols * n6; C.q = pd; pd += cols * n6;
-    C.t = pd; pd += cols * e6;
-    C.rows_rz0 = pd; pd += cols * nb; C.rows_rz = pd; pd += cols * 2 * nb; C.rows_pq = pd; pd += cols * nb;
-    C.resid = pd; pd += cols; C.cov = pd; pd += (size_t)nq * 36; C.q_res = pd;
-    int* pi = g->d_cov_i;
-    C.stop_at = pi; pi += cols; C.it = pi; pi += cols; C.broke = pi; pi += cols;
-    int* qi = pi; pi += nq; int* qj = pi; pi += nq;
-    C.qi = qi; C.qj = qj; C.q_it = pi; pi += nq; C.q_flags = pi;
+    PgCg& S = C.cg;
+    const ArenaPart<double> doubles[] = {{&S.x, cols * n6}, {&S.res, cols * n6}, {&S.z, cols * n6}, {&S.p, cols * n6}, {&S.q, cols * n6}, {&S.t, cols * e6},
+                                         {&S.rows_rz0, cols * nb}, {&S.rows_rz, cols * 2 * nb}, {&S.rows_pq, cols * nb}, {&S.resid, cols},
+                                         {&C.cov, q * 36}, {&C.q_res, q}};
+    const ArenaPart<int> ints[] = {{&S.stop_at, cols}, {&S.it, cols}, {&S.broke, cols}, {&C.qi, q}, {&C.qj, q}, {&C.q_it, q}, {&C.q_flags, q}};
+    PGC(g, arena_carve(g->d_cov, doubles));
+    PGC(g, arena_carve(g->d_cov_i, ints));
+    C.nq = nq; S.ncols = (int)cols;
+    S.dd = nullptr;      // lambda = 0
     *out = C;
     return 0;
-}
-
-void cov_launch_iteration(hipStream_t s, const PgDev& G, const PgCov& C, int k, double cg_tol, bool per_query) {
-    const dim3 blk(pg::kBlock), gv(G.nbV, C.ncols);
-    if (per_query) hipLaunchKernelGGL(pg::k_pgc_edge<true>, dim3(G.nbE, C.nq), blk, 0, s, G, C, k);
-    else hipLaunchKernelGGL(pg::k_pgc_edge<false>, dim3(G.nbE, C.ncols), blk, 0, s, G, C, k);
-    hipLaunchKernelGGL(pg::k_pgc_gather, gv, blk, 0, s, G, C, k);
-    hipLaunchKernelGGL(pg::k_pgc_update, gv, blk, 0, s, G, C, k);
-    hipLaunchKernelGGL(pg::k_pgc_dir, gv, blk, 0, s, G, C, k, cg_tol);
 }
 
 struct UnionFind {
@@ -387,15 +251,15 @@ int graph_covariances(rgbd360_graph* g, const char* what, bool relative, int n, 
     bool not_positive = false;
     for (size_t first = 0; first < live.size(); first += chunk) {
         const int nq = (int)std::min(live.size() - first, (size_t)chunk);
-        C.nq = nq; C.ncols = 6 * nq;
+        C.nq = nq; C.cg.ncols = 6 * nq;
         for (int k = 0; k < nq; ++k) {
             q[k] = relative ? from[live[first + k]] : -1;
             q[chunk + k] = to[live[first + k]];
         }
-        PGC(g, hipMemcpyAsync(const_cast<int*>(C.qi), q.data(), sizeof(int) * nq, hipMemcpyHostToDevice, s));
-        PGC(g, hipMemcpyAsync(const_cast<int*>(C.qj), q.data() + chunk, sizeof(int) * nq, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(pg::k_pgc_init, dim3(G.nbV, C.ncols), blk, 0, s, G, C);
-        for (int k = 0; k < P.cg_max_iters; ++k) cov_launch_iteration(s, G, C, k, P.cg_tol, kCovEdgePerQuery);
+        PGC(g, hipMemcpyAsync(C.qi, q.data(), sizeof(int) * nq, hipMemcpyHostToDevice, s));
+        PGC(g, hipMemcpyAsync(C.qj, q.data() + chunk, sizeof(int) * nq, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(pg::k_pgc_init, dim3(G.nbV, C.cg.ncols), blk, 0, s, G, C);
+        for (int k = 0; k < P.cg_max_iters; ++k) cg_launch_iteration(s, G, C.cg, -1, k, P.cg_tol, kCovEdgePerQuery);
         hipLaunchKernelGGL(pg::k_pgc_finish, dim3(nq), dim3(64), 0, s, G, C);
         PGC(g, hipGetLastError());
         PGC(g, hipMemcpyAsync(h_cov.data(), C.cov, sizeof(double) * 36 * nq, hipMemcpyDeviceToHost, s));
@@ -453,8 +317,7 @@ int rgbd360_graph_time_cov_kernels(rgbd360_graph* g, int n, const int* vertices,
     if (rc) return rc;
     for (int k = 0; k < 8; ++k) avg_us[k] = 0.f;
     if (!g->E()) return 0;
-    rgbd360_ctx* ctx = g->ctx;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = g->ctx->stream;
     const PgDev& G = g->G;
     rc = graph_put_state(g, 0.0);
     if (rc) return rc;
@@ -463,37 +326,26 @@ int rgbd360_graph_time_cov_kernels(rgbd360_graph* g, int n, const int* vertices,
     if (rc) return rc;
     std::vector<int> q(2 * (size_t)n, -1);
     for (int k = 0; k < n; ++k) q[n + k] = vertices[k];
-    PGC(g, hipMemcpyAsync(const_cast<int*>(C.qi), q.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
-    PGC(g, hipMemcpyAsync(const_cast<int*>(C.qj), q.data() + n, sizeof(int) * n, hipMemcpyHostToDevice, s));
-    const dim3 blk(pg::kBlock), gv(G.nbV, C.ncols);
+    PGC(g, hipMemcpyAsync(C.qi, q.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
+    PGC(g, hipMemcpyAsync(C.qj, q.data() + n, sizeof(int) * n, hipMemcpyHostToDevice, s));
+    const PgCg& S = C.cg;
+    const dim3 blk(pg::kBlock), gv(G.nbV, S.ncols);
     hipLaunchKernelGGL(pg::k_pg_edges<0>, dim3(G.nbE), blk, 0, s, G, -1);
     hipLaunchKernelGGL(pg::k_pg_assemble, dim3(G.nbV), blk, 0, s, G, -1);
     // every timed launch carries iteration 0 with a tolerance of 0: no column ever stops, each repetition does the full work
     auto launch = [&](int which) {
         switch (which) {
             case 0: hipLaunchKernelGGL(pg::k_pgc_init, gv, blk, 0, s, G, C); break;
-            case 1: hipLaunchKernelGGL(pg::k_pgc_edge<false>, dim3(G.nbE, C.ncols), blk, 0, s, G, C, 0); break;
-            case 2: hipLaunchKernelGGL(pg::k_pgc_edge<true>, dim3(G.nbE, C.nq), blk, 0, s, G, C, 0); break;
-            case 3: hipLaunchKernelGGL(pg::k_pgc_gather, gv, blk, 0, s, G, C, 0); break;
-            case 4: hipLaunchKernelGGL(pg::k_pgc_update, gv, blk, 0, s, G, C, 0); break;
-            case 5: hipLaunchKernelGGL(pg::k_pgc_dir, gv, blk, 0, s, G, C, 0, 0.0); break;
+            case 1: hipLaunchKernelGGL(pg::k_pg_cg_edge<false>, dim3(G.nbE, S.ncols), blk, 0, s, G, S, -1, 0); break;
+            case 2: hipLaunchKernelGGL(pg::k_pg_cg_edge<true>, dim3(G.nbE, C.nq), blk, 0, s, G, S, -1, 0); break;
+            case 3: hipLaunchKernelGGL(pg::k_pg_cg_gather, gv, blk, 0, s, G, S, -1, 0); break;
+            case 4: hipLaunchKernelGGL(pg::k_pg_cg_update, gv, blk, 0, s, G, S, -1, 0); break;
+            case 5: hipLaunchKernelGGL(pg::k_pg_cg_dir, gv, blk, 0, s, G, S, -1, 0, 0.0); break;
             case 6: hipLaunchKernelGGL(pg::k_pgc_finish, dim3(C.nq), dim3(64), 0, s, G, C); break;
-            default: hipLaunchKernelGGL(pg::k_pgc_gather, gv, blk, 0, s, G, C, INT_MAX); break;      // returns on the stop word
+            default: hipLaunchKernelGGL(pg::k_pg_cg_gather, gv, blk, 0, s, G, S, -1, INT_MAX); break;      // returns on the stop word
         }
     };
-    for (int which = 0; which < 8; ++which) {
-        launch(which);      // once untimed: its inputs are then what the loop would hand it
-        PGC(g, hipEventRecord(ctx->ev0, s));
-        for (int k = 0; k < reps; ++k) launch(which);
-        PGC(g, hipEventRecord(ctx->ev1, s));
-        PGC(g, hipGetLastError());
-        PGC(g, hipEventSynchronize(ctx->ev1));
-        float ms = 0.f;
-        PGC(g, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        avg_us[which] = ms * 1000.f / (float)reps;
-    }
-    PGC(g, hipStreamSynchronize(s));      // (q is a local)
-    return 0;
+    return graph_time_slots(g, 8, reps, avg_us, launch, [](int) { return 0; });      // (q is a local: the helper ends on a synchronisation)
 }
 
 }  // extern "C"

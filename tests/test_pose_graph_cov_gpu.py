@@ -3,6 +3,7 @@ dense inverse of tests/pose_graph_cov_reference.py on the graphs of tests/pose_g
 bound is 8 x the recorded error of the numpy restatement of the device's conjugate gradients plus 1e-13 (tests/golden/pose_graph_cov.json,
 pose_graph_cov_reference.device_bound): measured against the reference, never against the device."""
 import ctypes as C
+import json
 import os
 import subprocess
 import sys
@@ -17,6 +18,7 @@ import pose_graph_robust_reference as RR
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 IDS = [CR.case_id(n, f) for n, f in CR.CASES]
 
 
@@ -118,6 +120,27 @@ def test_lock_step_is_query_by_query(reg):
         for k in (0, 8, 15, 16):
             one, _ = dev.relative_covariances([frm[k]], [to[k]])
             assert one[0].tobytes() == rel[k].tobytes(), k
+
+
+def test_covariances_keep_the_parents_bits(reg):
+    """tests/golden/pose_graph_cov_bits.json was recorded with tests/golden/make_golden_pose_graph_cov_bits.py from the library before the
+    optimiser and the covariance batch shared one set of conjugate-gradient kernels.  Marginals and relative covariances after optimising
+    (a zero block, one workgroup and two, a full batch of 16 plus a batch of one, every column cut off at cg_max_iters = 3) and the operator
+    product at lambda = 1e-3 and 0 give those bits: cov, iterations, residuals, every result field, y.  Equality only."""
+    import make_golden_pose_graph_cov_bits as G
+    want = json.load(open(G.OUT))
+    got = G.compute(reg)
+    assert sorted(got) == sorted(want) == ["apply", "cov"]
+    assert sorted(got["cov"]) == sorted(want["cov"]) == sorted(c[0] for c in G.COV_CASES)
+    assert sorted(got["apply"]) == sorted(want["apply"]) == sorted("%s/%s" % nf for nf in G.APPLY_CASES)
+    for key in want["cov"]:
+        assert sorted(got["cov"][key]) == sorted(want["cov"][key]), key
+        for what, rec in want["cov"][key].items():
+            for field in ("result", "cg_iterations", "cg_residual", "cov_sha256"):
+                assert got["cov"][key][what][field] == rec[field], (key, what, field)
+    assert want["cov"]["n300/noisy/capped"]["marginals"]["result"]["status"] == CR.NOT_CONVERGED
+    for key in want["apply"]:
+        assert got["apply"][key] == want["apply"][key], key
 
 
 def test_covariance_calls_leave_the_optimiser_alone(reg):

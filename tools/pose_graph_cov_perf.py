@@ -27,7 +27,7 @@ from pose_graph_perf import make_graph                    # noqa: E402
 from rgbd360_amd.pose_graph import PoseGraph              # noqa: E402
 from rgbd360_amd.register import RegisterPhotoICP         # noqa: E402
 
-KERNELS = ("k_pgc_init", "k_pgc_edge<per column>", "k_pgc_edge<per query>", "k_pgc_gather", "k_pgc_update", "k_pgc_dir", "k_pgc_finish",
+KERNELS = ("k_pgc_init", "k_pg_cg_edge<per column>", "k_pg_cg_edge<per query>", "k_pg_cg_gather", "k_pg_cg_update", "k_pg_cg_dir", "k_pgc_finish",
            "a launch returning on the stop words")
 
 
