@@ -1179,6 +1179,8 @@ _occ_poses = synth.occlusion_test_poses
 @pytest.mark.parametrize("occlusion", [1, 2])
 @pytest.mark.parametrize("method", [0, 1, 2])
 def test_eval_occlusion_parity(hip_lib, oracle_mod, small_pair, method, occlusion):
+    """Every level of the 256x128 pair: 32768, 8192 and 2048 pixels, all multiples of the 1024-pixel step, so every wave of the build
+    and of the pass is full.  The same body where no level fills its last wave (250x101, 1000x37): tests/test_ragged_passes_gpu.py."""
     reg, ora, T = _pair_ctx(hip_lib, oracle_mod, _occluder_pair(small_pair))
     conflicts = 0
     for level in range(3):
@@ -1410,7 +1412,8 @@ def _pinhole_probe_pose(T):
 @pytest.mark.parametrize("method", [0, 1, 2])
 def test_pinhole_occlusion_eval_parity(hip_lib, oracle_mod, method, occ):
     """errorPhotoICP_Occ1/2 + calcHessGrad_Occ1/2 at one pose: counts (integer work, the z-buffer's accept chain included) exact,
-    sums within the float tolerances of the plain pass."""
+    sums within the float tolerances of the plain pass.  At 320x240: the levels have 76800, 19200 and 4800 pixels, all multiples of 64
+    (250x187, where none is: tests/test_ragged_passes_gpu.py)."""
     reg, ora, T = _pinhole_ctx(hip_lib, oracle_mod)
     longest = 0
     for level in range(3):
@@ -1436,7 +1439,8 @@ def test_pinhole_occlusion_eval_parity(hip_lib, oracle_mod, method, occ):
 def test_pinhole_occlusion_long_arrival_lists(hip_lib, oracle_mod, push):
     """Poses that pile many source pixels on one target pixel (a zoom-out, a push, a collapse of the image onto a few pixels): lists
     longer than a target's slot row are visited by scanning the key array over the box of their arrivals -- the same sequential
-    z-buffer semantics, counts exact, whatever the list length.  Both passes of both occlusion modes, every level."""
+    z-buffer semantics, counts exact, whatever the list length.  Both passes of both occlusion modes, every level of the 320x240 pair
+    (320, 160 and 80 columns; the box scan at 250, 125 and 62 columns: tests/test_ragged_passes_gpu.py)."""
     reg, ora, T = _pinhole_ctx(hip_lib, oracle_mod)
     P = np.eye(4)
     P[2, 3] = push
@@ -2327,7 +2331,8 @@ def test_alignment_in_the_reference_arithmetic_follows_the_libm_oracle(hip_lib, 
 @pytest.mark.parametrize("depth_f32", [False, True])
 def test_pinhole_warp_and_alignment_in_the_reference_arithmetic(hip_lib, oracle_mod, depth_f32):
     """rgbd360_set_index_arithmetic(ctx, 1) on the pinhole path (RPI.h:701-708 as compiled: no fused multiply-adds, 1.0 / Z in double,
-    roundf): target indices bit-equal to the oracle's math_mode 0 on every level, the Levenberg-Marquardt alignment on the libm oracle's
+    roundf): target indices bit-equal to the oracle's math_mode 0 on every level of the 320x240 pair (250x187:
+    tests/test_ragged_passes_gpu.py), the Levenberg-Marquardt alignment on the libm oracle's
     accept / reject sequence (float64 sums), plain and occlusion-aware."""
     (rgbA, dA), (rgbB, dB), T, K = synth.make_pinhole_pair(320, 240, seed=77, depth_f32=depth_f32)
     reg = _mk(hip_lib, 3, setMaskSeams=False)
