@@ -4,7 +4,7 @@
 //     frame_%03d.rgb  (H*W*3 uint8)   frame_%03d.depth (H*W uint16 mm)
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/odometry_replay.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o odometry_replay
-// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane] [--render-map PREFIX] [--map-window N]]
+// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane] [--render-map PREFIX] [--raycast-map PREFIX] [--map-window N]]
 //         --sequence: all frames are loaded first and the frame loop runs inside the library (alignSequence)
 //         --multi N:  the same sequence sharded over N GPUs of this node from this one process (rgbd360_multi_*: one host thread
 //                     per device, contiguous shards of pairs, one ncclAllGather of the solved poses over xGMI); prints the
@@ -28,6 +28,8 @@
 //                     pose (GlobalMap::renderSphere: the reference's viewer.globalMap, OdometryRGBD360.cpp:242-268, as a panorama) and
 //                     written as PREFIX_rgb.ppm (P6) and PREFIX_depth.pfm (Pf, metres, 0 in holes, rows bottom to top); prints one
 //                     "render" line with the counters.
+//         --raycast-map PREFIX: (needs --map) the same two images by ray casting through the map (GlobalMap::raycastSphere: per pixel the
+//                     first occupied voxel along the pixel's ray); prints one "raycast" line with the counters.
 //         --map-window N: (needs --map) a bounded local map, the usual odometry target: the loop keeps the images and poses of the last N
 //                     frames, and when frame k goes in, frame k - N leaves (GlobalMap::remove: the integer sums make that exact).  The
 //                     table is rebuilt (GlobalMap::rehash) when a census shows more tombstones than occupied voxels.  Prints one "window"
@@ -173,7 +175,7 @@ int main(int argc, char** argv) {
         return 0;
     }
     const bool use_pbmap = argc > 5 && std::string(argv[5]) == "--pbmap";
-    std::string map_file, render_prefix;
+    std::string map_file, render_prefix, raycast_prefix;
     float leaf = 0.05f;
     bool refine_on_map = false, refine_on_map_plane = false;
     int map_window = 0;
@@ -181,12 +183,17 @@ int main(int argc, char** argv) {
         if (a + 1 < argc && std::string(argv[a]) == "--map") map_file = argv[a + 1];
         if (a + 1 < argc && std::string(argv[a]) == "--leaf") leaf = (float)atof(argv[a + 1]);
         if (a + 1 < argc && std::string(argv[a]) == "--render-map") render_prefix = argv[a + 1];
+        if (a + 1 < argc && std::string(argv[a]) == "--raycast-map") raycast_prefix = argv[a + 1];
         if (a + 1 < argc && std::string(argv[a]) == "--map-window") map_window = atoi(argv[a + 1]);
         if (std::string(argv[a]) == "--refine-on-map") refine_on_map = true;
         if (std::string(argv[a]) == "--refine-on-map-plane") refine_on_map_plane = true;
     }
     if (!render_prefix.empty() && map_file.empty()) {
         fprintf(stderr, "--render-map needs --map\n");
+        return 2;
+    }
+    if (!raycast_prefix.empty() && map_file.empty()) {
+        fprintf(stderr, "--raycast-map needs --map\n");
         return 2;
     }
     if (map_window != 0 && (map_file.empty() || map_window < 0)) {
@@ -284,6 +291,20 @@ int main(int argc, char** argv) {
         for (const rgbd360::MapPoint& p : globalMap->points()) fprintf(f, "%.6f %.6f %.6f %d %d %d %d\n", p.x, p.y, p.z, p.r, p.g, p.b, p.count);
         fclose(f);
     }
+    // a view of the map as PREFIX_rgb.ppm and PREFIX_depth.pfm; false: a file could not be written
+    auto write_view = [&](const std::string& prefix, const std::vector<float>& depth, const std::vector<uint8_t>& rgb) {
+        FILE* f = fopen((prefix + "_rgb.ppm").c_str(), "wb");
+        if (!f) return false;
+        fprintf(f, "P6\n%d %d\n255\n", w, h);
+        fwrite(rgb.data(), 1, rgb.size(), f);
+        fclose(f);
+        f = fopen((prefix + "_depth.pfm").c_str(), "wb");
+        if (!f) return false;
+        fprintf(f, "Pf\n%d %d\n-1.0\n", w, h);            // little-endian floats, the bottom row first
+        for (int r = h - 1; r >= 0; --r) fwrite(depth.data() + (size_t)r * w, sizeof(float), (size_t)w, f);
+        fclose(f);
+        return true;
+    };
     if (globalMap && !render_prefix.empty()) {
         std::vector<float> depth;
         std::vector<uint8_t> rgb;
@@ -291,16 +312,16 @@ int main(int argc, char** argv) {
         const rgbd360_map_render_stats& st = globalMap->renderStats();
         printf("render voxels %lld below_min_count %lld near %lld splatted %lld pixels_covered %lld\n", st.n_voxels, st.n_below_min_count, st.n_near,
                st.n_splatted, st.n_pixels_covered);
-        FILE* f = fopen((render_prefix + "_rgb.ppm").c_str(), "wb");
-        if (!f) return 7;
-        fprintf(f, "P6\n%d %d\n255\n", w, h);
-        fwrite(rgb.data(), 1, rgb.size(), f);
-        fclose(f);
-        f = fopen((render_prefix + "_depth.pfm").c_str(), "wb");
-        if (!f) return 7;
-        fprintf(f, "Pf\n%d %d\n-1.0\n", w, h);            // little-endian floats, the bottom row first
-        for (int r = h - 1; r >= 0; --r) fwrite(depth.data() + (size_t)r * w, sizeof(float), (size_t)w, f);
-        fclose(f);
+        if (!write_view(render_prefix, depth, rgb)) return 7;
+    }
+    if (globalMap && !raycast_prefix.empty()) {
+        std::vector<float> depth;
+        std::vector<uint8_t> rgb;
+        globalMap->raycastSphere(h, w, currentPose, depth, rgb);
+        const rgbd360_map_raycast_stats& st = globalMap->raycastStats();
+        printf("raycast rays %lld hits %lld miss_box %lld left_box %lld t_max %lld max_steps %lld bad_rays %lld steps %lld lookups %lld\n", st.n_rays, st.n_hits,
+               st.n_miss_box, st.n_left_box, st.n_t_max, st.n_max_steps, st.n_bad_rays, st.n_steps, st.n_lookups);
+        if (!write_view(raycast_prefix, depth, rgb)) return 7;
     }
     return 0;
 }

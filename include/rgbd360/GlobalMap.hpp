@@ -18,6 +18,9 @@
 // The map as a spherical RGB-D frame (rgbd360_map_render_*: the reference shows viewer.globalMap in a PCL window, OdometryRGBD360.cpp:242-268,
 // and aligns against keyframes, OdometryKeyFrame360.cpp): a z-buffered splat of the table into the panorama of the dense alignment,
 //     globalMap.renderSphere(rows, cols, pose, depth, rgb)     whose outputs RegisterPhotoICP::setTargetFrame takes as they are
+// Ray casting through the map (rgbd360_map_raycast*): the first occupied voxel along a ray -- the same panorama as a per-pixel first hit,
+// or any list of rays (pinhole views, single beams, the line of sight between two keyframe poses),
+//     globalMap.raycastSphere(rows, cols, pose, depth, rgb)    globalMap.raycast(origins, dirs, t, &key3, &count, &rgb, &status)
 // Editing (rgbd360_map_remove_* / _move_* / _rehash / _census): the SLAM programs optimise their keyframe poses continuously and redraw the
 // map from them (SphereGraphSLAM.cpp, KFsphere_SLAM.cpp: optimizer.optimizeGraph(), getPoses(Map.vOptimizedPoses)); the sums are integers,
 // so a frame leaves the map exactly as it came,
@@ -177,6 +180,43 @@ class GlobalMap {
     }
     const rgbd360_map_render_stats& renderStats() const { return render_; }      // of the last renderSphere call
 
+    // Ray casting (rgbd360_map_raycast*; defaults: min_count 1, t_min = leaf, t_max and max_offset +inf, max_steps 8192): per ray the first
+    // voxel with count >= min_count along o + t d.  raycast: origins and dirs hold 3 floats per ray (world coordinates); t is resized, 0 on a
+    // miss; key3, count, rgb, status (RGBD360_RAY_*) may be nullptr.  raycastSphere: the panorama of renderSphere, each pixel the first hit of
+    // its ray; depth and rgb are what RegisterPhotoICP::setTargetFrame takes.  The map is not changed.  raycastStats() has the counters of the
+    // last call of either.
+    rgbd360_map_raycast_params raycastParams() const {
+        rgbd360_map_raycast_params p;
+        rgbd360_map_default_raycast_params(map_, &p);
+        return p;
+    }
+    void raycast(const std::vector<float>& origins, const std::vector<float>& dirs, std::vector<float>& t, std::vector<int32_t>* key3 = nullptr,
+                 std::vector<int32_t>* count = nullptr, std::vector<uint8_t>* rgb = nullptr, std::vector<int32_t>* status = nullptr,
+                 const rgbd360_map_raycast_params* params = nullptr) {
+        if (origins.size() != dirs.size() || origins.size() % 3 != 0) throw std::runtime_error("GlobalMap::raycast: origins and dirs must hold 3 floats per ray");
+        const size_t n = origins.size() / 3;
+        t.assign(n, 0.f);
+        if (key3) key3->assign(3 * n, 0);
+        if (count) count->assign(n, 0);
+        if (rgb) rgb->assign(3 * n, 0);
+        if (status) status->assign(n, 0);
+        check(rgbd360_map_raycast(map_, (long long)n, origins.data(), dirs.data(), 0, params, t.data(), key3 ? key3->data() : nullptr,
+                                  count ? count->data() : nullptr, rgb ? rgb->data() : nullptr, status ? status->data() : nullptr, &raycast_),
+              "rgbd360_map_raycast");
+    }
+    void raycastSphere(int rows, int cols, const Mat4f& pose, std::vector<float>& depth, std::vector<uint8_t>& rgb, std::vector<int32_t>* count = nullptr,
+                       std::vector<int32_t>* key3 = nullptr, const rgbd360_map_raycast_params* params = nullptr) {
+        const size_t n = rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0;
+        depth.assign(n, 0.f);
+        rgb.assign(3 * n, 0);
+        if (count) count->assign(n, 0);
+        if (key3) key3->assign(3 * n, 0);
+        check(rgbd360_map_raycast_sphere(map_, rows, cols, pose.m, params, depth.data(), rgb.data(), count ? count->data() : nullptr,
+                                         key3 ? key3->data() : nullptr, &raycast_),
+              "rgbd360_map_raycast_sphere");
+    }
+    const rgbd360_map_raycast_stats& raycastStats() const { return raycast_; }      // of the last raycast / raycastSphere call
+
     long long size() const { return rgbd360_map_size(map_); }
     size_t bytes() const { return rgbd360_map_bytes(map_); }
     void clear() { check(rgbd360_map_clear(map_), "rgbd360_map_clear"); }
@@ -221,6 +261,7 @@ class GlobalMap {
     rgbd360_map_align_result align_{};
     rgbd360_map_align_plane_result alignPlane_{};
     rgbd360_map_render_stats render_{};
+    rgbd360_map_raycast_stats raycast_{};
 };
 
 }  // namespace rgbd360

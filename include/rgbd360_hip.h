@@ -449,7 +449,7 @@ int    rgbd360_map_align_plane_cloud(rgbd360_map* map, const float* xyz, long lo
  *                   3 x int32 = (i_x, i_y, i_z), 0 in holes.  The statistics are exact integers.
  * Stated limitations: the depth across a footprint is the centroid's dist (flat-shaded discs); the footprint is a square in pixels and
  * is not widened towards the poles; silhouettes grow by the footprint; the map holds no surface normals.  Out of scope: anti-aliased
- * or normal-shaded splats, ray casting through the grid, pinhole views. */
+ * or normal-shaded splats.  (The first surface along a ray, and with it any other view: rgbd360_map_raycast below.) */
 typedef struct {
     int   min_count;           /* points a voxel must hold to be drawn: 1 */
     float near;                /* voxels closer than this are skipped: leaf */
@@ -468,6 +468,78 @@ int    rgbd360_map_render_sphere(rgbd360_map* map, int rows, int cols, const flo
 int    rgbd360_map_render_sphere_dev(rgbd360_map* map, int rows, int cols, const float pose[16], const rgbd360_map_render_params* params,
                                      float* depth_dev, uint8_t* rgb_dev, int32_t* count_dev, int32_t* key3_dev,
                                      rgbd360_map_render_stats* stats_dev);
+
+/* ---- ray casting through the map (csrc/map_raycast.h) ---------------------------------------------------------------------------
+ * What a map is usually asked: the first surface along a ray.  A list of rays (pinhole views, single beams, the line of sight between
+ * two keyframe poses), or every pixel of the dense alignment's full-sphere panorama at a pose: the model image of frame-to-model
+ * alignment as a per-pixel first hit where rgbd360_map_render_sphere splats.  The result is a function of the voxel set and the ray
+ * alone: it does not depend on the order of insertion, on the table's capacity, on slot indices or on the run.  A ray cast never writes
+ * the table.  All traversal arithmetic is float64 + - x / without contraction; o, d, the centroid and inv_leaf = 1.0f / leaf enter as
+ * the doubles of their float32 values.
+ *   1 ray         origin o and direction d, float32 triples in world coordinates; the point at t >= 0 is o + t d.  d need not be a unit
+ *                 vector: t is in units of |d|.  A component not finite, or d = 0: status RGBD360_RAY_BAD, nothing traversed.
+ *   2 grid        g_k = o_k inv_leaf, u_k = d_k inv_leaf (exact products), r_k = 1 / u_k.  The ray meets the cell boundary b of axis k
+ *                 (the plane between the cells b - 1 and b; cells are [i, i + 1)) at T_k(b) = (b - g_k) r_k -- two roundings, a function
+ *                 of b alone and never a running sum, so a boundary's time does not depend on the path to it.  u_k = 0: T_k = +inf.
+ *   3 clip        against the box of the live voxels, the cells lo_k .. hi_k (the integer key bounds over the voxels with count > 0, a
+ *                 function of the voxel set): t0 = max(0, near_k), t1 = min(far_k) over the axes with u_k != 0, near / far the smaller
+ *                 / larger of T_k(lo_k) and T_k(hi_k + 1); an axis with u_k = 0 misses unless lo_k <= g_k < hi_k + 1.  t0 > t1:
+ *                 status RGBD360_RAY_MISS_BOX, zero steps.
+ *   4 start       the cell i_k = floor(g_k + t0 u_k), clamped to lo_k .. hi_k; t_in = t0.
+ *   5 per cell    (Amanatides-Woo)  t_in > t_max: status RGBD360_RAY_T_MAX.  max_steps cells visited: RGBD360_RAY_MAX_STEPS.  Else the
+ *                 cell is counted as a step; t_out = the smallest T_k(next boundary of axis k); on equal times the LOWEST axis index
+ *                 steps (x before y before z).  The cell is a candidate if its voxel holds count >= min_count points; removed voxels
+ *                 (tombstones) and empty cells are air.  c = the read-out's float32 centroid, bit for bit;
+ *                 s = (((c_x - o_x) d_x + (c_y - o_y) d_y) + (c_z - o_z) d_z) / ((d_x d_x + d_y d_y) + d_z d_z), the centroid's
+ *                 projection on the ray; t_hit = min(max(s, t_in), t_out).  The candidate is rejected, and the traversal goes on, when
+ *                 t_hit < t_min (default: leaf, which drops the voxel the camera sits in) or when the centroid lies farther than
+ *                 max_offset leaves from the ray: ((e_x e_x + e_y e_y) + e_z e_z) (inv_leaf inv_leaf) > max_offset max_offset with
+ *                 e_k = (c_k - o_k) - s d_k (default +inf: the test is off).  Else: status RGBD360_RAY_HIT.
+ *   6 advance     the axis of t_out moves one cell by the sign of u_k; a cell outside lo .. hi ends the ray with RGBD360_RAY_LEFT_BOX
+ *                 (the box lies inside the key range |i| < 2^20, so no index outside that range is ever looked up).  t_in = t_out.
+ *   7 outputs     per ray, any pointer may be NULL: t float32 = (float)t_hit, 0 on a miss (the render's hole convention); key3 3 x int32
+ *                 = (i_x, i_y, i_z); count int32; rgb3 = the read-out's colour S_c / count; status int32.  All zero on a miss but status.
+ *                 The statistics are exact integers.  n_steps: cells visited.  n_lookups: lookups in the voxel table, the one number
+ *                 that depends on the form of the traversal (the coarse layer looks up live cells only; the plain form every cell).
+ * The coarse layer (bricks of 8^3 cells: brick key -> 512-bit mask, plus the live-key bounds) belongs to the map, is built on the first
+ * ray cast after the map was written (two scans of the table; that call waits for the first) and changes no output bit.
+ * Stated limitations: cells are cubes -- a ray that clips an occupied cell's corner hits it unless max_offset is set; the depth inside a
+ * cell is the centroid's projection, with no normals and no interpolation between cells; the layer costs extra device memory per map
+ * (12 bytes per brick-table slot, a power of two >= 2 x voxels, and 64 bytes per occupied brick).  Out of scope: carving or any write
+ * to the map from a ray cast, normals or shaded output. */
+enum { RGBD360_RAY_MISS_BOX = 0, RGBD360_RAY_HIT = 1, RGBD360_RAY_LEFT_BOX = 2, RGBD360_RAY_T_MAX = 3, RGBD360_RAY_MAX_STEPS = 4, RGBD360_RAY_BAD = 5 };
+typedef struct {
+    int   min_count;           /* points a voxel must hold to stop a ray: 1 */
+    float t_min;               /* hits nearer than this are passed through: leaf */
+    float t_max;               /* the ray ends where a cell's entry lies beyond this: +inf */
+    float max_offset;          /* largest distance of the centroid from the ray, in leaves: +inf (off) */
+    int   max_steps;           /* cells a ray may visit, 1 .. 2^23: 8192 */
+} rgbd360_map_raycast_params;
+typedef struct {
+    long long n_rays, n_hits, n_miss_box, n_left_box, n_t_max, n_max_steps, n_bad_rays, n_steps, n_lookups;
+} rgbd360_map_raycast_stats;
+void   rgbd360_map_default_raycast_params(const rgbd360_map* map, rgbd360_map_raycast_params* p);
+/* n rays: origins and dirs are n x 3 float32.  on_device 0: every array is host memory; 1: origins, dirs and the five outputs are
+ * device arrays on the map's device.  stats is host memory and the call waits in both cases.  0; -1 bad arguments, nothing launched:
+ * n < 0 or >= 2^31, origins or dirs NULL with n > 0, min_count < 1, t_min negative or not finite, t_max or max_offset negative or not
+ * a number, max_steps outside 1 .. 2^23.  params NULL: the defaults.  An empty map or n == 0 returns 0 with zero-filled outputs and
+ * statistics and launches no kernel. */
+int    rgbd360_map_raycast(rgbd360_map* map, long long n, const float* origins, const float* dirs, int on_device,
+                           const rgbd360_map_raycast_params* params, float* t, int32_t* key3, int32_t* count, uint8_t* rgb3, int32_t* status,
+                           rgbd360_map_raycast_stats* stats);
+/* The panorama: the pixel grid, the pose convention, the output planes and the argument checks of rgbd360_map_render_sphere.  The ray of
+ * pixel (r, c) starts at the pose's translation; its direction is the pixel's unit vector f = (sin phi_r, (-cos phi_r) sin theta_c,
+ * (-cos phi_r) cos theta_c) in float32 -- the dense alignment's source point at depth 1 (RPI.h:4556-4571), with theta_c = c angle_res and
+ * phi_r = (half_nRows - r) angle_res in float32 and their sine and cosine taken in double and rounded to float32 (at most an ulp from
+ * the alignment's own tables, and no function of a C library's sinf) -- rotated by the pose, d_k = (R_k0 f_x + R_k1 f_y) + R_k2 f_z, every
+ * product and sum rounded to float32 on its own.  depth = t; depth and rgb go straight into rgbd360_set_target with depth_type 1. */
+int    rgbd360_map_raycast_sphere(rgbd360_map* map, int rows, int cols, const float pose[16], const rgbd360_map_raycast_params* params,
+                                  float* depth, uint8_t* rgb, int32_t* count, int32_t* key3, rgbd360_map_raycast_stats* stats);
+/* The same into device arrays on the map's device (stats_dev too): enqueued on the context's stream; the call waits only where the
+ * coarse layer has to be rebuilt. */
+int    rgbd360_map_raycast_sphere_dev(rgbd360_map* map, int rows, int cols, const float pose[16], const rgbd360_map_raycast_params* params,
+                                      float* depth_dev, uint8_t* rgb_dev, int32_t* count_dev, int32_t* key3_dev,
+                                      rgbd360_map_raycast_stats* stats_dev);
 
 /* ---- pose-graph optimisation of store edges (csrc/pose_graph.h) -----------------------------------------------------------------
  * The reference closes its SLAM loop in g2o: optimizer.addVertex(pose), optimizer.addEdge(nearestKF, newKF, relPose, registerer.getInfoMat()),

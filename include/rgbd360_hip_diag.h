@@ -172,6 +172,18 @@ int rgbd360_graph_time_cov_kernels(rgbd360_graph* g, int n, const int* vertices,
 int rgbd360_map_time_render(rgbd360_map* map, int rows, int cols, const float pose[16], const rgbd360_map_render_params* params, int form,
                             int reps, float avg_us[5], rgbd360_map_render_stats* stats, long long* atomics);
 
+/* The ray cast's traversal switch (rgbd360_map_raycast*, rgbd360_hip.h): plain != 0 selects the one-level traversal, one voxel-table
+ * lookup per cell, for every later ray cast of this map; 0 (the default) the coarse layer.  The outputs are the same bits. */
+int rgbd360_map_raycast_set_plain(rgbd360_map* map, int plain);
+/* The ray cast under HIP events, one figure per repetition in microseconds (the caller takes medians): build_us[r] the layer build (both
+ * scans, their clears and the read-back between them), cast_us[r] one traversal launch with the clear of its counters, scan_us[r] (may
+ * be NULL) ONE k_vmap_extract launch (centroids only) over the same table, the cost of merely scanning it.  origins_dev NULL: the
+ * panorama of rows x cols at pose; else the n rays of the two device arrays.  plain: as above, for this call only.  stats (may be
+ * NULL): those of the last launch; *layer_bytes (may be NULL): device memory of the layer.  The map is not changed. */
+int rgbd360_map_time_raycast(rgbd360_map* map, long long n, const float* origins_dev, const float* dirs_dev, int rows, int cols, const float pose[16],
+                             const rgbd360_map_raycast_params* params, int plain, int reps, float* build_us, float* cast_us, float* scan_us,
+                             rgbd360_map_raycast_stats* stats, long long* layer_bytes);
+
 /* The same timer with the launches rotating over n_ctx contexts of one device (each with its own copy of a frame pair) on
  * ctxs[0]'s stream: once n_ctx x the level's working set exceeds the 256 MiB Infinity Cache every launch is fed from HBM. */
 int rgbd360_time_eval_kernel_rotating(rgbd360_ctx* const* ctxs, int n_ctx, int level, const float pose[16], int method,

@@ -39,6 +39,8 @@ SYMBOLS = [
     "rgbd360_map_default_align_plane_params", "rgbd360_map_align_plane_sphere", "rgbd360_map_align_plane_cloud", "rgbd360_map_align_plane_eval",
     "rgbd360_map_plane_fit", "rgbd360_map_time_align_plane",
     "rgbd360_map_default_render_params", "rgbd360_map_render_sphere", "rgbd360_map_render_sphere_dev", "rgbd360_map_time_render",
+    "rgbd360_map_default_raycast_params", "rgbd360_map_raycast", "rgbd360_map_raycast_sphere", "rgbd360_map_raycast_sphere_dev",
+    "rgbd360_map_raycast_set_plain", "rgbd360_map_time_raycast",
     "rgbd360_graph_create", "rgbd360_graph_destroy", "rgbd360_graph_last_error", "rgbd360_graph_add_vertices", "rgbd360_graph_add_edges",
     "rgbd360_graph_set_poses", "rgbd360_graph_set_fixed", "rgbd360_graph_n_vertices", "rgbd360_graph_n_edges", "rgbd360_graph_clear",
     "rgbd360_graph_default_params", "rgbd360_graph_optimize", "rgbd360_graph_get_poses", "rgbd360_graph_chi2", "rgbd360_graph_get_trace",
@@ -124,6 +126,15 @@ class MapRenderParams(C.Structure):     # rgbd360_map_render_params
 
 class MapRenderStats(C.Structure):      # rgbd360_map_render_stats
     _fields_ = [(n, C.c_longlong) for n in ("n_voxels", "n_below_min_count", "n_near", "n_splatted", "n_pixels_covered")]
+
+
+class MapRaycastParams(C.Structure):    # rgbd360_map_raycast_params
+    _fields_ = [("min_count", C.c_int), ("t_min", C.c_float), ("t_max", C.c_float), ("max_offset", C.c_float), ("max_steps", C.c_int)]
+
+
+class MapRaycastStats(C.Structure):     # rgbd360_map_raycast_stats
+    _fields_ = [(n, C.c_longlong) for n in ("n_rays", "n_hits", "n_miss_box", "n_left_box", "n_t_max", "n_max_steps", "n_bad_rays", "n_steps",
+                                            "n_lookups")]
 
 
 class GraphParams(C.Structure):         # rgbd360_graph_params
@@ -370,6 +381,14 @@ def load() -> C.CDLL:
     L.rgbd360_map_render_sphere.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRenderParams), vp, vp, vp, vp, C.POINTER(MapRenderStats)]
     L.rgbd360_map_render_sphere_dev.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRenderParams), vp, vp, vp, vp, vp]
     L.rgbd360_map_time_render.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRenderParams), i32, i32, vp, C.POINTER(MapRenderStats), C.POINTER(ll)]
+    L.rgbd360_map_default_raycast_params.argtypes = [vp, C.POINTER(MapRaycastParams)]
+    L.rgbd360_map_default_raycast_params.restype = None
+    L.rgbd360_map_raycast.argtypes = [vp, ll, vp, vp, i32, C.POINTER(MapRaycastParams), vp, vp, vp, vp, vp, C.POINTER(MapRaycastStats)]
+    L.rgbd360_map_raycast_sphere.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRaycastParams), vp, vp, vp, vp, C.POINTER(MapRaycastStats)]
+    L.rgbd360_map_raycast_sphere_dev.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRaycastParams), vp, vp, vp, vp, vp]
+    L.rgbd360_map_raycast_set_plain.argtypes = [vp, i32]
+    L.rgbd360_map_time_raycast.argtypes = [vp, ll, vp, vp, i32, i32, f32p, C.POINTER(MapRaycastParams), i32, i32, vp, vp, vp, C.POINTER(MapRaycastStats),
+                                           C.POINTER(ll)]
     L.rgbd360_graph_create.argtypes = [vp, C.POINTER(vp)]
     L.rgbd360_graph_destroy.argtypes = [vp]
     L.rgbd360_graph_destroy.restype = None

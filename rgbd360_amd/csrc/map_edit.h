@@ -214,6 +214,7 @@ extern "C" int rgbd360_map_rehash(rgbd360_map* m, long long capacity_voxels) {
     m->table = std::move(fresh);      // (the old table goes with `fresh`; the stream is idle)
     m->n_slots = n_slots;
     m->may_hold_tombstones = false;
+    ++m->revision;
     return 0;
 }
 

@@ -32,7 +32,7 @@ __host__ __device__ inline void unpack_key3(unsigned long long key, int32_t out[
     for (int k = 0; k < 3; ++k) out[k] = (int32_t)((key >> (21 * k)) & 0x1fffffull) - kBias;
 }
 // the read-out's centroid of the slot `rec`, which holds `count` points
-__device__ __forceinline__ void centroid(const unsigned long long* rec, unsigned long long count, float c[3]) {
+__host__ __device__ __forceinline__ void centroid(const unsigned long long* rec, unsigned long long count, float c[3]) {
 #pragma clang fp contract(off)
     const double den = (double)count * kFix;
 #pragma unroll

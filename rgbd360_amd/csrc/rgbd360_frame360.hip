@@ -1258,6 +1258,7 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
 // ---------------------------------------------------------------------------------------------------------
 #include "voxel_map.h"
 #include "map_edit.h"
+#include "map_raycast.h"
 #include "gn_math.h"
 #include "map_align.h"
 #include "map_align_plane.h"

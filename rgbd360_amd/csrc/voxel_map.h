@@ -92,6 +92,20 @@ struct rgbd360_map {
     DevBuf<unsigned long long> r_key, r_stats;
     PinnedBuf<unsigned long long> r_hstats;
     DevBuf<uint8_t> r_stage;
+    // ray casting (map_raycast.h).  revision: bumped on the host by every entry that writes the table (insert, remove, move, clear, rehash);
+    // the coarse layer and the live-key bounds are those of revision rc_rev and are rebuilt when the two differ
+    unsigned long long revision = 1, rc_rev = 0;
+    DevBuf<unsigned long long> rc_bkeys, rc_masks, rc_stats;      // brick keys, brick masks (eight words each), the counters
+    DevBuf<uint32_t> rc_bidx;                                     // per brick slot: the brick's number
+    DevBuf<unsigned> rc_words;                                    // the layer scan's bounds and brick count ...
+    PinnedBuf<unsigned> rc_hwords;                                // ... and their pinned copy
+    PinnedBuf<unsigned long long> rc_hstats;
+    unsigned long long rc_bslots = 0, rc_bricks = 0;
+    int rc_lo[3] = {0, 0, 0}, rc_hi[3] = {-1, -1, -1};            // the live box, unbiased cell indices
+    DevBuf<float> rc_tab, rc_rays;                                // a panorama's angle tables (of rc_tab_rows x rc_tab_cols); a host list's rays
+    int rc_tab_rows = 0, rc_tab_cols = 0;
+    DevBuf<uint8_t> rc_stage;                                     // the host entries' outputs on the device: 27 bytes per ray
+    bool rc_plain = false;                                        // the one-level traversal (rgbd360_map_raycast_set_plain)
 };
 
 namespace vmap {
@@ -562,6 +576,7 @@ int vmap_clear_dev(rgbd360_map* m) {
     HIPC(m, hipGetLastError());
     m->n_voxels = 0;
     m->may_hold_tombstones = false;
+    ++m->revision;
     return 0;
 }
 vmap::Params vmap_params(const rgbd360_map* m, const float pose[16]) {
@@ -597,6 +612,7 @@ int vmap_read_stats(rgbd360_map* m, int words, int at = 0) {
 // the insert kernel over `src` in `mode` (vmap::kInsert ..), enqueued on the stream; the statistics words are cleared in front of it.
 // vmap_launch_insert is an insert as the map stands: revivals are counted once a removal has emptied a voxel.
 int vmap_launch(rgbd360_map* m, const vmap::Params& P, const MapSource& src, int mode) {
+    ++m->revision;
     HIPC(m, hipMemsetAsync(m->d_stats, 0, (mode == vmap::kRemove ? vmap::kStWords : vmap::kStInsertWords) * sizeof(unsigned long long), m->s->stream));
     const dim3 grid = vmap_grid(src);
     with_choice<0, 1>(src.cloud, [&](auto S) {

@@ -8,6 +8,8 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
     pose, res = gmap.align_sphere(depth, guess, convention=0)      # point-to-point ICP of a frame against the map (csrc/map_align.h)
     pose, res = gmap.align_sphere_plane(depth, guess, convention=0)    # point-to-plane: planes fitted to the centroids (csrc/map_align_plane.h)
     depth, rgb, count, key3, stats = gmap.render_sphere(rows, cols, pose)      # the map as a spherical RGB-D frame (csrc/map_render.h)
+    depth, rgb, count, key3, stats = gmap.raycast_sphere(rows, cols, pose)     # ... as a per-pixel first hit (csrc/map_raycast.h)
+    t, key3, count, rgb, status, stats = gmap.raycast(origins, dirs)           # the first voxel along each ray of a list
     xyz, rgb, count, key = gmap.extract()          # sorted by (i_z, i_y, i_x)
     gmap.remove_sphere(rgb, depth, currentPose)    # exactly undoes that insert (csrc/map_edit.h); gmap.mismatch tells of a broken contract
     gmap.move_sphere(rgb, depth, currentPose, correctedPose)       # a pose-graph correction: removed at the old pose, inserted at the new
@@ -28,6 +30,7 @@ from .register import Rgbd360Error, _ptr, pose_from_cm, pose_to_cm
 
 MAP_FULL = 3      # RGBD360_MAP_FULL
 MAP_MISMATCH = 4  # RGBD360_MAP_MISMATCH
+RAY_MISS_BOX, RAY_HIT, RAY_LEFT_BOX, RAY_T_MAX, RAY_MAX_STEPS, RAY_BAD = range(6)      # RGBD360_RAY_*
 
 
 def _as_dict(st, skip=()):
@@ -301,6 +304,53 @@ class VoxelMap:
         self._check(self._L.rgbd360_map_render_sphere(self._handle(), rows, cols, _ptr(g), C.byref(p), _ptr(depth), _ptr(rgb), _ptr(count), _ptr(key3),
                                                       C.byref(st)))
         return depth, rgb, count, key3, _as_dict(st)
+
+    # ---- ray casting through the map (rgbd360_map_raycast*: the first occupied voxel along a ray; csrc/map_raycast.h)
+    def raycast_params(self, min_count=None, t_min=None, t_max=None, max_offset=None, max_steps=None):
+        """The defaults (min_count 1, t_min = leaf, t_max +inf, max_offset +inf = off, max_steps 8192) with the given fields replaced."""
+        return self._params(_lib.MapRaycastParams, self._L.rgbd360_map_default_raycast_params, min_count=min_count, t_min=t_min, t_max=t_max,
+                            max_offset=max_offset, max_steps=max_steps)
+
+    def raycast(self, origins, dirs, **params):
+        """The first voxel along each of n rays (origins, dirs: n x 3 float32, world coordinates; a point of the ray is o + t d).  Returns
+        (t [n] float32, 0 on a miss; key3 [n, 3] int32; count [n] int32; rgb [n, 3] uint8; status [n] int32 = RAY_*; the statistics as a
+        dict).  The map is not changed."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise Rgbd360Error("VoxelMap.raycast: origins and dirs must have the same shape")
+        n = o.shape[0]
+        p = self.raycast_params(**params)
+        t = np.zeros(n, np.float32)
+        key3 = np.zeros((n, 3), np.int32)
+        count = np.zeros(n, np.int32)
+        rgb = np.zeros((n, 3), np.uint8)
+        status = np.zeros(n, np.int32)
+        st = _lib.MapRaycastStats()
+        self._check(self._L.rgbd360_map_raycast(self._handle(), n, _ptr(o), _ptr(d), 0, C.byref(p), _ptr(t), _ptr(key3), _ptr(count), _ptr(rgb),
+                                                _ptr(status), C.byref(st)))
+        return t, key3, count, rgb, status, _as_dict(st)
+
+    def raycast_sphere(self, rows: int, cols: int, pose, **params):
+        """The full-sphere panorama of rows x cols at `pose` (4x4 world <- frame) by ray casting: per pixel the first voxel along the
+        pixel's ray.  Returns what render_sphere returns, (depth, rgb, count, key3, the statistics as a dict); depth and rgb are what
+        RegisterPhotoICP.setTargetFrame takes.  The map is not changed."""
+        rows, cols = int(rows), int(cols)
+        p = self.raycast_params(**params)
+        g = pose_to_cm(pose)
+        shape = (max(rows, 0), max(cols, 0))
+        depth = np.zeros(shape, np.float32)
+        rgb = np.zeros(shape + (3,), np.uint8)
+        count = np.zeros(shape, np.int32)
+        key3 = np.zeros(shape + (3,), np.int32)
+        st = _lib.MapRaycastStats()
+        self._check(self._L.rgbd360_map_raycast_sphere(self._handle(), rows, cols, _ptr(g), C.byref(p), _ptr(depth), _ptr(rgb), _ptr(count), _ptr(key3),
+                                                       C.byref(st)))
+        return depth, rgb, count, key3, _as_dict(st)
+
+    def raycast_set_plain(self, plain: bool):
+        """Diagnostics: the one-level traversal instead of the coarse layer for the later ray casts; the outputs are the same bits."""
+        self._check(self._L.rgbd360_map_raycast_set_plain(self._handle(), int(bool(plain))))
 
     # ---- read-out
     def __len__(self) -> int:
