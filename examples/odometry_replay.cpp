@@ -4,7 +4,7 @@
 //     frame_%03d.rgb  (H*W*3 uint8)   frame_%03d.depth (H*W uint16 mm)
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/odometry_replay.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o odometry_replay
-// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane] [--render-map PREFIX] [--raycast-map PREFIX] [--map-window N]]
+// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane] [--render-map PREFIX] [--raycast-map PREFIX] [--map-normals OUT] [--raycast-surface PREFIX] [--map-window N]]
 //         --sequence: all frames are loaded first and the frame loop runs inside the library (alignSequence)
 //         --multi N:  the same sequence sharded over N GPUs of this node from this one process (rgbd360_multi_*: one host thread
 //                     per device, contiguous shards of pairs, one ncclAllGather of the solved poses over xGMI); prints the
@@ -30,6 +30,10 @@
 //                     "render" line with the counters.
 //         --raycast-map PREFIX: (needs --map) the same two images by ray casting through the map (GlobalMap::raycastSphere: per pixel the
 //                     first occupied voxel along the pixel's ray); prints one "raycast" line with the counters.
+//         --map-normals OUT: (needs --map) the map as an oriented cloud, one line "x y z nx ny nz curvature status" per voxel
+//                     (GlobalMap::normals: a normal per voxel fitted to the centroids around it, facing the last pose; status RGBD360_NORMAL_*).
+//         --raycast-surface PREFIX: (needs --map) the ray-cast panorama with the surface (GlobalMap::raycastSurfaceSphere): the depth on the
+//                     plane fitted around each hit voxel and PREFIX_normal.pfm, the world-frame normal per pixel.
 //         --map-window N: (needs --map) a bounded local map, the usual odometry target: the loop keeps the images and poses of the last N
 //                     frames, and when frame k goes in, frame k - N leaves (GlobalMap::remove: the integer sums make that exact).  The
 //                     table is rebuilt (GlobalMap::rehash) when a census shows more tombstones than occupied voxels.  Prints one "window"
@@ -175,7 +179,7 @@ int main(int argc, char** argv) {
         return 0;
     }
     const bool use_pbmap = argc > 5 && std::string(argv[5]) == "--pbmap";
-    std::string map_file, render_prefix, raycast_prefix;
+    std::string map_file, render_prefix, raycast_prefix, normals_file, surface_prefix;
     float leaf = 0.05f;
     bool refine_on_map = false, refine_on_map_plane = false;
     int map_window = 0;
@@ -185,6 +189,8 @@ int main(int argc, char** argv) {
         if (a + 1 < argc && std::string(argv[a]) == "--render-map") render_prefix = argv[a + 1];
         if (a + 1 < argc && std::string(argv[a]) == "--raycast-map") raycast_prefix = argv[a + 1];
         if (a + 1 < argc && std::string(argv[a]) == "--map-window") map_window = atoi(argv[a + 1]);
+        if (a + 1 < argc && std::string(argv[a]) == "--map-normals") normals_file = argv[a + 1];
+        if (a + 1 < argc && std::string(argv[a]) == "--raycast-surface") surface_prefix = argv[a + 1];
         if (std::string(argv[a]) == "--refine-on-map") refine_on_map = true;
         if (std::string(argv[a]) == "--refine-on-map-plane") refine_on_map_plane = true;
     }
@@ -194,6 +200,10 @@ int main(int argc, char** argv) {
     }
     if (!raycast_prefix.empty() && map_file.empty()) {
         fprintf(stderr, "--raycast-map needs --map\n");
+        return 2;
+    }
+    if ((!normals_file.empty() || !surface_prefix.empty()) && map_file.empty()) {
+        fprintf(stderr, "--map-normals and --raycast-surface need --map\n");
         return 2;
     }
     if (map_window != 0 && (map_file.empty() || map_window < 0)) {
@@ -322,6 +332,35 @@ int main(int argc, char** argv) {
         printf("raycast rays %lld hits %lld miss_box %lld left_box %lld t_max %lld max_steps %lld bad_rays %lld steps %lld lookups %lld\n", st.n_rays, st.n_hits,
                st.n_miss_box, st.n_left_box, st.n_t_max, st.n_max_steps, st.n_bad_rays, st.n_steps, st.n_lookups);
         if (!write_view(raycast_prefix, depth, rgb)) return 7;
+    }
+    if (globalMap && !normals_file.empty()) {      // the oriented cloud: the normals face the last pose
+        std::vector<float> xyz, normal, curvature;
+        std::vector<int32_t> status;
+        const float viewpoint[3] = {currentPose(0, 3), currentPose(1, 3), currentPose(2, 3)};
+        const long long nv = globalMap->normals(xyz, normal, &curvature, &status, nullptr, nullptr, viewpoint);
+        const rgbd360_map_normal_stats& st = globalMap->normalStats();
+        printf("normals voxels %lld below_min_count %lld unsupported %lld nonplanar %lld normals %lld\n", st.n_voxels, st.n_below_min_count, st.n_unsupported,
+               st.n_nonplanar, st.n_normals);
+        FILE* f = fopen(normals_file.c_str(), "w");
+        if (!f) return 6;
+        for (long long k = 0; k < nv; ++k)
+            fprintf(f, "%.6f %.6f %.6f %.6f %.6f %.6f %.6g %d\n", xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2], normal[3 * k], normal[3 * k + 1], normal[3 * k + 2],
+                    curvature[k], status[k]);
+        fclose(f);
+    }
+    if (globalMap && !surface_prefix.empty()) {      // PREFIX_rgb.ppm, PREFIX_depth.pfm and PREFIX_normal.pfm (a colour PFM: x, y, z)
+        std::vector<float> depth, normal;
+        std::vector<uint8_t> rgb;
+        globalMap->raycastSurfaceSphere(h, w, currentPose, depth, normal, rgb);
+        const rgbd360_map_raycast_stats& st = globalMap->raycastStats();
+        printf("raycast-surface rays %lld hits %lld on_plane %lld steps %lld lookups %lld\n", st.n_rays, st.n_hits, globalMap->onPlane(), st.n_steps,
+               st.n_lookups);
+        if (!write_view(surface_prefix, depth, rgb)) return 7;
+        FILE* f = fopen((surface_prefix + "_normal.pfm").c_str(), "wb");
+        if (!f) return 7;
+        fprintf(f, "PF\n%d %d\n-1.0\n", w, h);
+        for (int r = h - 1; r >= 0; --r) fwrite(normal.data() + (size_t)r * w * 3, sizeof(float), (size_t)w * 3, f);
+        fclose(f);
     }
     return 0;
 }

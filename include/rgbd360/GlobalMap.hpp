@@ -21,6 +21,9 @@
 // Ray casting through the map (rgbd360_map_raycast*): the first occupied voxel along a ray -- the same panorama as a per-pixel first hit,
 // or any list of rays (pinhole views, single beams, the line of sight between two keyframe poses),
 //     globalMap.raycastSphere(rows, cols, pose, depth, rgb)    globalMap.raycast(origins, dirs, t, &key3, &count, &rgb, &status)
+// Surface normals (rgbd360_map_normals, rgbd360_map_raycast_surface*): one normal per voxel, fitted to the centroids around it and kept with
+// the map -- the map as an oriented cloud, and the ray cast with the depth on the fitted plane and a normal per hit,
+//     globalMap.normals(xyz, normal, &curvature, &status)      globalMap.raycastSurfaceSphere(rows, cols, pose, depth, normal, rgb)
 // Editing (rgbd360_map_remove_* / _move_* / _rehash / _census): the SLAM programs optimise their keyframe poses continuously and redraw the
 // map from them (SphereGraphSLAM.cpp, KFsphere_SLAM.cpp: optimizer.optimizeGraph(), getPoses(Map.vOptimizedPoses)); the sums are integers,
 // so a frame leaves the map exactly as it came,
@@ -215,7 +218,68 @@ class GlobalMap {
                                          key3 ? key3->data() : nullptr, &raycast_),
               "rgbd360_map_raycast_sphere");
     }
-    const rgbd360_map_raycast_stats& raycastStats() const { return raycast_; }      // of the last raycast / raycastSphere call
+    const rgbd360_map_raycast_stats& raycastStats() const { return raycast_; }      // of the last raycast / raycastSphere call, plain or surface
+
+    // Surface normals (rgbd360_map_normals, rgbd360_map_raycast_surface*; defaults: min_count 1, min_support 5, max_flatness 0.05, max_shift
+    // 2.0 leaves): one normal per voxel, fitted to the centroids of the 27 cells around it and kept resident with the map.  normals: one
+    // record per voxel in no specified order; xyz is resized, the others may be nullptr; status is RGBD360_NORMAL_*, the normal is zero unless
+    // it is RGBD360_NORMAL_OK; with a viewpoint (3 floats, world) the normals face it.  Returns the voxel count; normalStats() has the counts.
+    // raycastSurface / raycastSurfaceSphere: raycast / raycastSphere with, per hit, the voxel's normal (3 floats, world, facing the ray's
+    // origin) and the depth on the plane through the voxel's centroid where it is taken; onPlane() counts those rays.
+    rgbd360_map_normal_params normalParams() const {
+        rgbd360_map_normal_params p;
+        rgbd360_map_default_normal_params(map_, &p);
+        return p;
+    }
+    long long normals(std::vector<float>& xyz, std::vector<float>& normal, std::vector<float>* curvature = nullptr, std::vector<int32_t>* status = nullptr,
+                      std::vector<int32_t>* count = nullptr, std::vector<int32_t>* key3 = nullptr, const float* viewpoint = nullptr,
+                      const rgbd360_map_normal_params* params = nullptr) {
+        const size_t n = (size_t)size();
+        xyz.assign(3 * n, 0.f);
+        normal.assign(3 * n, 0.f);
+        if (curvature) curvature->assign(n, 0.f);
+        if (status) status->assign(n, 0);
+        if (count) count->assign(n, 0);
+        if (key3) key3->assign(3 * n, 0);
+        const long long got = rgbd360_map_normals(map_, params, viewpoint, (long long)n, xyz.data(), normal.data(), curvature ? curvature->data() : nullptr,
+                                                  status ? status->data() : nullptr, count ? count->data() : nullptr, key3 ? key3->data() : nullptr,
+                                                  &normal_);
+        if (got != (long long)n) throw std::runtime_error(std::string("rgbd360_map_normals: ") + rgbd360_map_last_error(map_));
+        return got;
+    }
+    const rgbd360_map_normal_stats& normalStats() const { return normal_; }      // of the last normals call
+    void raycastSurface(const std::vector<float>& origins, const std::vector<float>& dirs, std::vector<float>& t, std::vector<float>& normal,
+                        std::vector<int32_t>* key3 = nullptr, std::vector<int32_t>* count = nullptr, std::vector<uint8_t>* rgb = nullptr,
+                        std::vector<int32_t>* status = nullptr, const rgbd360_map_raycast_params* rayParams = nullptr,
+                        const rgbd360_map_normal_params* normalParams = nullptr) {
+        if (origins.size() != dirs.size() || origins.size() % 3 != 0)
+            throw std::runtime_error("GlobalMap::raycastSurface: origins and dirs must hold 3 floats per ray");
+        const size_t n = origins.size() / 3;
+        t.assign(n, 0.f);
+        normal.assign(3 * n, 0.f);
+        if (key3) key3->assign(3 * n, 0);
+        if (count) count->assign(n, 0);
+        if (rgb) rgb->assign(3 * n, 0);
+        if (status) status->assign(n, 0);
+        check(rgbd360_map_raycast_surface(map_, (long long)n, origins.data(), dirs.data(), 0, rayParams, normalParams, t.data(), normal.data(),
+                                          key3 ? key3->data() : nullptr, count ? count->data() : nullptr, rgb ? rgb->data() : nullptr,
+                                          status ? status->data() : nullptr, &onPlane_, &raycast_),
+              "rgbd360_map_raycast_surface");
+    }
+    void raycastSurfaceSphere(int rows, int cols, const Mat4f& pose, std::vector<float>& depth, std::vector<float>& normal, std::vector<uint8_t>& rgb,
+                              std::vector<int32_t>* count = nullptr, std::vector<int32_t>* key3 = nullptr,
+                              const rgbd360_map_raycast_params* rayParams = nullptr, const rgbd360_map_normal_params* normalParams = nullptr) {
+        const size_t n = rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0;
+        depth.assign(n, 0.f);
+        normal.assign(3 * n, 0.f);
+        rgb.assign(3 * n, 0);
+        if (count) count->assign(n, 0);
+        if (key3) key3->assign(3 * n, 0);
+        check(rgbd360_map_raycast_surface_sphere(map_, rows, cols, pose.m, rayParams, normalParams, depth.data(), normal.data(), rgb.data(),
+                                                 count ? count->data() : nullptr, key3 ? key3->data() : nullptr, &onPlane_, &raycast_),
+              "rgbd360_map_raycast_surface_sphere");
+    }
+    long long onPlane() const { return onPlane_; }      // of the last raycastSurface / raycastSurfaceSphere call
 
     long long size() const { return rgbd360_map_size(map_); }
     size_t bytes() const { return rgbd360_map_bytes(map_); }
@@ -262,6 +326,8 @@ class GlobalMap {
     rgbd360_map_align_plane_result alignPlane_{};
     rgbd360_map_render_stats render_{};
     rgbd360_map_raycast_stats raycast_{};
+    rgbd360_map_normal_stats normal_{};
+    long long onPlane_ = 0;
 };
 
 }  // namespace rgbd360

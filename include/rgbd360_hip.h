@@ -368,8 +368,9 @@ int    rgbd360_map_align_cloud(rgbd360_map* map, const float* xyz, long long n, 
  * Every cloud ICP call site of the reference uses pcl::GeneralizedIterativeClosestPoint, a plane-to-plane cost (OdometryRGBD360.cpp:98-114
  * and 210-222, RegisterPairRGBD360.cpp:111-118, MethodsRegisterRGBD360.cpp:294-320).  Against one centroid per cell of a lattice the
  * point-to-point residual above has a tangential part of up to half a leaf along a wall, which says nothing about the pose and pulls the
- * translation towards the lattice; the distance to a plane fitted to the centroids around the point has none.  The map stores no normals:
- * the plane comes from the centroids of the 27 cells the lookup reads anyway.  Per source point at the current pose T:
+ * translation towards the lattice; the distance to a plane fitted to the centroids around the point has none.  The plane is
+ * fitted around the posed point from the centroids of the 27 cells the lookup reads anyway (the map's resident per-voxel normals,
+ * rgbd360_map_normals below, are fitted around a voxel and are not used here).  Per source point at the current pose T:
  *   1 candidates and match: steps 1-4 of the point-to-point definition above, bit for bit -- the map's steps 1-5, the 27 cells in the
  *     same order, count >= min_count, the read-out's centroid, d2 in float32, a tie to the earlier cell, kept iff d2 <= max_dist^2,
  *     max_dist in (0, leaf].  The winning key and d2 of a point are those of rgbd360_map_align_*.
@@ -448,8 +449,9 @@ int    rgbd360_map_align_plane_cloud(rgbd360_map* map, const float* xyz, long lo
  *                   tightly packed = the winner's colour; count int32 = the winner's point count (the hole mask: 0 in holes); key3
  *                   3 x int32 = (i_x, i_y, i_z), 0 in holes.  The statistics are exact integers.
  * Stated limitations: the depth across a footprint is the centroid's dist (flat-shaded discs); the footprint is a square in pixels and
- * is not widened towards the poles; silhouettes grow by the footprint; the map holds no surface normals.  Out of scope: anti-aliased
- * or normal-shaded splats.  (The first surface along a ray, and with it any other view: rgbd360_map_raycast below.) */
+ * is not widened towards the poles; silhouettes grow by the footprint; the render does not use the map's surface normals.  Out of scope:
+ * anti-aliased or normal-shaded splats.  (The first surface along a ray, and with it any other view: rgbd360_map_raycast below; the
+ * surface with its normals: rgbd360_map_raycast_surface below.) */
 typedef struct {
     int   min_count;           /* points a voxel must hold to be drawn: 1 */
     float near;                /* voxels closer than this are skipped: leaf */
@@ -504,9 +506,9 @@ int    rgbd360_map_render_sphere_dev(rgbd360_map* map, int rows, int cols, const
  * The coarse layer (bricks of 8^3 cells: brick key -> 512-bit mask, plus the live-key bounds) belongs to the map, is built on the first
  * ray cast after the map was written (two scans of the table; that call waits for the first) and changes no output bit.
  * Stated limitations: cells are cubes -- a ray that clips an occupied cell's corner hits it unless max_offset is set; the depth inside a
- * cell is the centroid's projection, with no normals and no interpolation between cells; the layer costs extra device memory per map
- * (12 bytes per brick-table slot, a power of two >= 2 x voxels, and 64 bytes per occupied brick).  Out of scope: carving or any write
- * to the map from a ray cast, normals or shaded output. */
+ * cell is the centroid's projection, a staircase of cells (the depth on the plane fitted around the hit voxel, and its normal:
+ * rgbd360_map_raycast_surface below); the layer costs extra device memory per map (12 bytes per brick-table slot, a power of two
+ * >= 2 x voxels, and 64 bytes per occupied brick).  Out of scope: carving or any write to the map from a ray cast, shaded output. */
 enum { RGBD360_RAY_MISS_BOX = 0, RGBD360_RAY_HIT = 1, RGBD360_RAY_LEFT_BOX = 2, RGBD360_RAY_T_MAX = 3, RGBD360_RAY_MAX_STEPS = 4, RGBD360_RAY_BAD = 5 };
 typedef struct {
     int   min_count;           /* points a voxel must hold to stop a ray: 1 */
@@ -540,6 +542,76 @@ int    rgbd360_map_raycast_sphere(rgbd360_map* map, int rows, int cols, const fl
 int    rgbd360_map_raycast_sphere_dev(rgbd360_map* map, int rows, int cols, const float pose[16], const rgbd360_map_raycast_params* params,
                                       float* depth_dev, uint8_t* rgb_dev, int32_t* count_dev, int32_t* key3_dev,
                                       rgbd360_map_raycast_stats* stats_dev);
+
+/* ---- surface normals of the map (csrc/map_normals.h) -------------------------------------------------------------------------------
+ * One normal per voxel, fitted to the centroids around it, kept resident next to the table; a read-out with normals and a ray cast that
+ * returns the surface -- a normal per hit and a depth on the fitted plane instead of the staircase of cell centroids -- are its two
+ * consumers.  The normal of a voxel is a function of the voxel set and of (min_count, min_support, max_flatness) alone: it does not
+ * depend on the order of insertion, on the table's capacity, on a slot index or on the run.  Nothing here writes the table.
+ *   1 voxel       v with count >= min_count; w = the read-out's float32 centroid of v.  Below min_count: status RGBD360_NORMAL_NONE.
+ *   2 support     steps 2-3 of the point-to-plane definition above with v's own key as the centre and w as the point: the candidates are
+ *                 the voxels with count >= min_count among the 27 cells, the centre first, then dz / dy / dx ascending; v itself is one
+ *                 (e = 0); tombstones and empty cells are absent; a neighbour index outside the 21-bit key range does not exist and is
+ *                 not looked up.  The nine sums in float64, e_mean and C as there.  m < min_support: RGBD360_NORMAL_UNSUPPORTED.
+ *   3 plane       the plane function of step 3 there (rgbd360_map_plane_fit, the diagnostics header).  Not planar:
+ *                 RGBD360_NORMAL_NONPLANAR.  Else RGBD360_NORMAL_OK.
+ *   4 normal      n32_k = (float)n_k; canonical sign: the component of n32 of largest magnitude (the earliest on a tie) is positive,
+ *                 otherwise all three are negated.  Every consumer uses n32 widened to double.  curvature = (float)(l0 / c2), c2 =
+ *                 (C00 + C11) + C22 (lambda_min over the sum of the eigenvalues), 0 when c2 is not positive.  The normal is zero unless
+ *                 the status is OK; the curvature is zero unless it is OK or NONPLANAR.
+ * The layer: 16 bytes per table slot of device memory beside the table (a quarter of the table; rgbd360_map_bytes stays the table's
+ * size), owned by the map, built by the first call that needs it -- one launch over the slots -- and reused until the map is written
+ * or one of the three parameters differs.  max_shift is no parameter of the layer.
+ * Out of scope: shaded or anti-aliased output; normals from the points inside a voxel (insertion is unchanged); neighbourhoods wider
+ * than the 27 cells; camera-frame normals (normals are in world coordinates); rgbd360_map_align_plane_* on the resident normals (its
+ * plane is fitted around the posed point, not around a voxel, and its bits are pinned). */
+enum { RGBD360_NORMAL_NONE = 0, RGBD360_NORMAL_OK = 1, RGBD360_NORMAL_UNSUPPORTED = 2, RGBD360_NORMAL_NONPLANAR = 3 };
+typedef struct {
+    int   min_count;           /* points a voxel must hold to have a normal and to support one: 1 */
+    int   min_support;         /* candidates (occupied cells of the 27) a normal needs, 1 .. 27: 5 */
+    float max_flatness;        /* largest l0 / l1 of a planar support, >= 0: 0.05 (rgbd360_map_align_plane_params) */
+    float max_shift;           /* surface cast only: how far, in leaves, the plane point may lie from the hit voxel's centroid, >= 0: 2.0
+                                  (a setting, not a measurement: on oblique noisy walls 1.5 still rejected 0.5 - 1.7 % of the hits of a probe
+                                  and 2.0 none; 0 keeps every depth of the plain cast) */
+} rgbd360_map_normal_params;
+typedef struct { long long n_voxels, n_below_min_count, n_unsupported, n_nonplanar, n_normals; } rgbd360_map_normal_stats;
+void      rgbd360_map_default_normal_params(const rgbd360_map* map, rgbd360_map_normal_params* p);
+/* One record per voxel with count > 0, in the manner of rgbd360_map_extract but in NO specified order (key3 and xyz come along): returns
+ * the voxel count; at most max_out records are written; any output pointer may be NULL.  xyz [3], count and key3 [3] are the read-out's
+ * bits; normal [3], curvature and status as defined above.  viewpoint (3 floats, world; may be NULL): an OK normal is negated when
+ * ((n_x e_x + n_y e_y) + n_z e_z) < 0 for e = viewpoint - w in double, so that it faces the viewpoint; NULL keeps the canonical sign.
+ * stats (may be NULL): exact counts over the whole map, whatever max_out.  Host arrays; the call waits.  -1, nothing launched and no
+ * output touched: min_count < 1, min_support outside 1 .. 27, max_flatness or max_shift negative or NaN, a viewpoint that is not finite,
+ * max_out < 0.  params NULL: the defaults.  An empty map returns 0 with zero statistics and launches no kernel. */
+long long rgbd360_map_normals(rgbd360_map* map, const rgbd360_map_normal_params* params, const float viewpoint[3], long long max_out, float* xyz,
+                              float* normal, float* curvature, int32_t* status, int32_t* count, int32_t* key3, rgbd360_map_normal_stats* stats);
+/* The same into device arrays on the map's device (stats_dev too; params and viewpoint are host memory): enqueued on the context's
+ * stream, the call does not wait. */
+long long rgbd360_map_normals_dev(rgbd360_map* map, const rgbd360_map_normal_params* params, const float viewpoint[3], long long max_out,
+                                  float* xyz_dev, float* normal_dev, float* curvature_dev, int32_t* status_dev, int32_t* count_dev,
+                                  int32_t* key3_dev, rgbd360_map_normal_stats* stats_dev);
+/* The surface cast.  Rays, checks, refusals (and those of the normal parameters above), empty inputs, output planes, pose convention and
+ * stream behaviour are those of rgbd360_map_raycast / _sphere / _sphere_dev; the traversal and the hit decision (with the centroid's
+ * projection) are the same, so status, key3, count, rgb and stats are byte-equal to the plain entry's on the same rays.  On a hit whose
+ * voxel is RGBD360_NORMAL_OK, with n = n32 widened, c the voxel's centroid, all in double without contraction:
+ *   q = (n_x d_x + n_y d_y) + n_z d_z; normal = n32, negated when q > 0 (it faces the ray's origin).  If q != 0:
+ *   t_p = ((n_x (c_x - o_x) + n_y (c_y - o_y)) + n_z (c_z - o_z)) / q, f_k = (o_k + t_p d_k) - c_k; the plane depth is taken iff
+ *   t_p >= t_min and ((f_x f_x + f_y f_y) + f_z f_z) (inv_leaf inv_leaf) <= max_shift max_shift -- it is NOT clamped to the cell (clamping
+ *   gives the gain away) -- and then t = (float)t_p.
+ * Every other hit keeps the plain entry's t bit for bit and has a zero normal; a miss has zeros.  normal: 3 floats per ray / pixel, world
+ * coordinates.  n_on_plane (may be NULL; host memory where stats is, device memory for the _dev entry): the rays whose plane depth was
+ * taken.  The sphere variant's depth and rgb go straight into rgbd360_set_target. */
+int       rgbd360_map_raycast_surface(rgbd360_map* map, long long n, const float* origins, const float* dirs, int on_device,
+                                      const rgbd360_map_raycast_params* ray_params, const rgbd360_map_normal_params* normal_params, float* t,
+                                      float* normal, int32_t* key3, int32_t* count, uint8_t* rgb3, int32_t* status, long long* n_on_plane,
+                                      rgbd360_map_raycast_stats* stats);
+int       rgbd360_map_raycast_surface_sphere(rgbd360_map* map, int rows, int cols, const float pose[16], const rgbd360_map_raycast_params* ray_params,
+                                             const rgbd360_map_normal_params* normal_params, float* depth, float* normal, uint8_t* rgb,
+                                             int32_t* count, int32_t* key3, long long* n_on_plane, rgbd360_map_raycast_stats* stats);
+int       rgbd360_map_raycast_surface_sphere_dev(rgbd360_map* map, int rows, int cols, const float pose[16],
+                                                 const rgbd360_map_raycast_params* ray_params, const rgbd360_map_normal_params* normal_params,
+                                                 float* depth_dev, float* normal_dev, uint8_t* rgb_dev, int32_t* count_dev, int32_t* key3_dev,
+                                                 long long* n_on_plane_dev, rgbd360_map_raycast_stats* stats_dev);
 
 /* ---- pose-graph optimisation of store edges (csrc/pose_graph.h) -----------------------------------------------------------------
  * The reference closes its SLAM loop in g2o: optimizer.addVertex(pose), optimizer.addEdge(nearestKF, newKF, relPose, registerer.getInfoMat()),

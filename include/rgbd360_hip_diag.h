@@ -183,6 +183,13 @@ int rgbd360_map_raycast_set_plain(rgbd360_map* map, int plain);
 int rgbd360_map_time_raycast(rgbd360_map* map, long long n, const float* origins_dev, const float* dirs_dev, int rows, int cols, const float pose[16],
                              const rgbd360_map_raycast_params* params, int plain, int reps, float* build_us, float* cast_us, float* scan_us,
                              rgbd360_map_raycast_stats* stats, long long* layer_bytes);
+/* The build of the normal layer (rgbd360_map_normals, rgbd360_hip.h) under HIP events: build_us[r], r < reps, one k_vmap_normals launch over
+ * the table with the clear of its counters, in microseconds (the caller takes medians); one untimed build runs first.  scan_us[r] (may
+ * be NULL): ONE k_vmap_extract launch (centroids only) over the same table, the cost of merely scanning it.  stats (may be NULL): those
+ * of the last build; *layer_bytes (may be NULL): device memory of the layer.  -1 on an empty map.  The layer stays valid
+ * for the parameters given; the map is not changed. */
+int rgbd360_map_time_normals(rgbd360_map* map, const rgbd360_map_normal_params* params, int reps, float* build_us, float* scan_us,
+                             rgbd360_map_normal_stats* stats, long long* layer_bytes);
 
 /* The same timer with the launches rotating over n_ctx contexts of one device (each with its own copy of a frame pair) on
  * ctxs[0]'s stream: once n_ctx x the level's working set exceeds the 256 MiB Infinity Cache every launch is fed from HBM. */

@@ -41,6 +41,8 @@ SYMBOLS = [
     "rgbd360_map_default_render_params", "rgbd360_map_render_sphere", "rgbd360_map_render_sphere_dev", "rgbd360_map_time_render",
     "rgbd360_map_default_raycast_params", "rgbd360_map_raycast", "rgbd360_map_raycast_sphere", "rgbd360_map_raycast_sphere_dev",
     "rgbd360_map_raycast_set_plain", "rgbd360_map_time_raycast",
+    "rgbd360_map_default_normal_params", "rgbd360_map_normals", "rgbd360_map_normals_dev", "rgbd360_map_raycast_surface",
+    "rgbd360_map_raycast_surface_sphere", "rgbd360_map_raycast_surface_sphere_dev", "rgbd360_map_time_normals",
     "rgbd360_graph_create", "rgbd360_graph_destroy", "rgbd360_graph_last_error", "rgbd360_graph_add_vertices", "rgbd360_graph_add_edges",
     "rgbd360_graph_set_poses", "rgbd360_graph_set_fixed", "rgbd360_graph_n_vertices", "rgbd360_graph_n_edges", "rgbd360_graph_clear",
     "rgbd360_graph_default_params", "rgbd360_graph_optimize", "rgbd360_graph_get_poses", "rgbd360_graph_chi2", "rgbd360_graph_get_trace",
@@ -135,6 +137,14 @@ class MapRaycastParams(C.Structure):    # rgbd360_map_raycast_params
 class MapRaycastStats(C.Structure):     # rgbd360_map_raycast_stats
     _fields_ = [(n, C.c_longlong) for n in ("n_rays", "n_hits", "n_miss_box", "n_left_box", "n_t_max", "n_max_steps", "n_bad_rays", "n_steps",
                                             "n_lookups")]
+
+
+class MapNormalParams(C.Structure):     # rgbd360_map_normal_params
+    _fields_ = [("min_count", C.c_int), ("min_support", C.c_int), ("max_flatness", C.c_float), ("max_shift", C.c_float)]
+
+
+class MapNormalStats(C.Structure):      # rgbd360_map_normal_stats
+    _fields_ = [(n, C.c_longlong) for n in ("n_voxels", "n_below_min_count", "n_unsupported", "n_nonplanar", "n_normals")]
 
 
 class GraphParams(C.Structure):         # rgbd360_graph_params
@@ -389,6 +399,19 @@ def load() -> C.CDLL:
     L.rgbd360_map_raycast_set_plain.argtypes = [vp, i32]
     L.rgbd360_map_time_raycast.argtypes = [vp, ll, vp, vp, i32, i32, f32p, C.POINTER(MapRaycastParams), i32, i32, vp, vp, vp, C.POINTER(MapRaycastStats),
                                            C.POINTER(ll)]
+    L.rgbd360_map_default_normal_params.argtypes = [vp, C.POINTER(MapNormalParams)]
+    L.rgbd360_map_default_normal_params.restype = None
+    L.rgbd360_map_normals.argtypes = [vp, C.POINTER(MapNormalParams), vp, ll, vp, vp, vp, vp, vp, vp, C.POINTER(MapNormalStats)]
+    L.rgbd360_map_normals.restype = ll
+    L.rgbd360_map_normals_dev.argtypes = [vp, C.POINTER(MapNormalParams), vp, ll, vp, vp, vp, vp, vp, vp, vp]
+    L.rgbd360_map_normals_dev.restype = ll
+    L.rgbd360_map_raycast_surface.argtypes = [vp, ll, vp, vp, i32, C.POINTER(MapRaycastParams), C.POINTER(MapNormalParams), vp, vp, vp, vp, vp, vp,
+                                              C.POINTER(ll), C.POINTER(MapRaycastStats)]
+    L.rgbd360_map_raycast_surface_sphere.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRaycastParams), C.POINTER(MapNormalParams), vp, vp, vp, vp, vp,
+                                                     C.POINTER(ll), C.POINTER(MapRaycastStats)]
+    L.rgbd360_map_raycast_surface_sphere_dev.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRaycastParams), C.POINTER(MapNormalParams), vp, vp, vp, vp, vp,
+                                                         vp, vp]
+    L.rgbd360_map_time_normals.argtypes = [vp, C.POINTER(MapNormalParams), i32, vp, vp, C.POINTER(MapNormalStats), C.POINTER(ll)]
     L.rgbd360_graph_create.argtypes = [vp, C.POINTER(vp)]
     L.rgbd360_graph_destroy.argtypes = [vp]
     L.rgbd360_graph_destroy.restype = None

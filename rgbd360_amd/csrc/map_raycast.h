@@ -1,7 +1,9 @@
 // map_raycast.h -- ray casting through the resident voxel map (voxel_map.h): the first occupied voxel along each ray of a list, or of every
 // pixel of the dense alignment's full-sphere panorama at a pose.  Where map_render.h splats centroids into pixels, this walks the grid:
 // the model image of frame-to-model alignment as a per-pixel first hit, any view as a list of rays, line-of-sight checks.
-// Part of the Frame360 translation unit (rgbd360_frame360.hip includes it behind voxel_map.h and map_edit.h).
+// Part of the Frame360 translation unit (rgbd360_frame360.hip includes it behind voxel_map.h, map_edit.h and map_normals.h).
+// The surface cast (rgbd360_map_raycast_surface*) is the same kernel and the same host entries with SURFACE / a RaySurface: the traversal
+// and the hit decision below unchanged, then per hit the normal of the voxel and the depth on its plane (vmap::surface_step, map_normals.h).
 //
 // Definition (include/rgbd360_hip.h, "ray casting through the map"; tests/map_raycast_reference.py restates it).  All
 // traversal arithmetic is float64 + - x / with contraction off; o, d, the centroid and inv_leaf enter as the doubles of their float32 values.
@@ -348,10 +350,15 @@ struct RayJob {
     int32_t *key3, *count;
     uint8_t* rgb3;
     int32_t* status;
-    unsigned long long* stats;
+    unsigned long long* stats;                           // kRsWords counters; the surface cast: one more, the rays whose plane depth was taken
+    const uint4* normals;                                // the surface cast (SURFACE): the normal layer (map_normals.h), a record per slot ...
+    double shift2_max;                                   // ... max_shift^2 ...
+    float* normal;                                       // ... and its normal output, may be null
 };
 
-template <bool LAYER, bool SPHERE>
+// SURFACE: the surface cast.  The traversal and the hit decision are the plain cast's; a hit whose voxel has a normal gets it, facing the
+// ray's origin, and the depth of the plane through the voxel's centroid where vmap::surface_step takes it.
+template <bool LAYER, bool SPHERE, bool SURFACE>
 __global__ __launch_bounds__(kRayThreads) void k_vmap_raycast(RayJob J) {
 #pragma clang fp contract(off)
     const long long idx = (long long)blockIdx.x * kRayThreads + threadIdx.x;
@@ -389,6 +396,14 @@ __global__ __launch_bounds__(kRayThreads) void k_vmap_raycast(RayJob J) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) col[k] = H.rec[5 + k] / cnt;
     }
+    double t = H.t;
+    float nrm[3] = {0.f, 0.f, 0.f};
+    bool on_plane = false;
+    if (SURFACE && hit) {
+        float c[3];
+        centroid(H.rec, cnt, c);
+        on_plane = surface_step(J.normals[(H.rec - J.G.table) / kFields], c, o, d, J.P.t_min, (double)J.P.inv_leaf, J.shift2_max, nrm, t);
+    }
     if (J.stats) {
         unsigned long long steps = (unsigned long long)H.steps, lookups = (unsigned long long)H.lookups;
 #pragma unroll
@@ -399,8 +414,9 @@ __global__ __launch_bounds__(kRayThreads) void k_vmap_raycast(RayJob J) {
         unsigned long long b[6];
 #pragma unroll
         for (int q = 0; q < 6; ++q) b[q] = __ballot(H.status == q);
-        const unsigned long long b_in = __ballot(in);
+        const unsigned long long b_in = __ballot(in), b_plane = SURFACE ? __ballot(on_plane) : 0ull;
         if ((threadIdx.x & 63) == 0 && b_in) {      // one add per wave and counter
+            if (SURFACE && b_plane) atomicAdd(J.stats + kRsWords, (unsigned long long)__popcll(b_plane));
             atomicAdd(J.stats + kRsRays, (unsigned long long)__popcll(b_in));
             if (b[kRayHit]) atomicAdd(J.stats + kRsHits, (unsigned long long)__popcll(b[kRayHit]));
             if (b[kRayMissBox]) atomicAdd(J.stats + kRsMissBox, (unsigned long long)__popcll(b[kRayMissBox]));
@@ -413,7 +429,11 @@ __global__ __launch_bounds__(kRayThreads) void k_vmap_raycast(RayJob J) {
         }
     }
     if (!in) return;
-    if (J.t) J.t[ii] = hit ? (float)H.t : 0.f;
+    if (J.t) J.t[ii] = hit ? (float)t : 0.f;
+    if (SURFACE && J.normal) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) J.normal[3 * ii + k] = nrm[k];
+    }
     if (J.key3) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) J.key3[3 * ii + k] = hit ? H.cell[k] : 0;
@@ -448,6 +468,14 @@ int ray_check_params(rgbd360_map* m, const rgbd360_map_raycast_params* params, r
     if (p.max_steps < 1 || p.max_steps > (1 << 23)) return vmap_fail(m, -1, "max_steps must lie in 1 .. 2^23");
     return 0;
 }
+// What the surface entries (rgbd360_map_raycast_surface*) add to a cast; a null RaySurface is the plain cast.  normal and n_on_plane are
+// host or device memory as the entry's other outputs and its statistics are.
+struct RaySurface {
+    const rgbd360_map_normal_params* params;
+    float* normal;
+    long long* n_on_plane;
+};
+int ray_check_surface(rgbd360_map* m, const RaySurface* sf, rgbd360_map_normal_params& np) { return sf ? normal_check_params(m, sf->params, np) : 0; }
 
 // The coarse layer and the live-key bounds of the map as it stands: rebuilt when the map has been written since (the revision word).
 // The call waits for the first scan (the brick count sizes the masks).  n_voxels > 0.
@@ -503,13 +531,21 @@ vmap::RayJob ray_job(const rgbd360_map* m, const rgbd360_map_raycast_params& p) 
     J.stats = m->rc_stats;
     return J;
 }
-// the kernel over the job, enqueued behind the clear of its counters; plain: the one-level traversal
-int ray_launch(rgbd360_map* m, const vmap::RayJob& J, bool sphere, bool plain) {
-    HIPC(m, hipMemsetAsync(m->rc_stats, 0, vmap::kRsWords * sizeof(unsigned long long), m->s->stream));
+// ... of a surface cast: also the normal layer (ray_prepare has built it) and max_shift
+void ray_surface_job(const rgbd360_map* m, vmap::RayJob& J, const rgbd360_map_normal_params& np) {
+    J.normals = m->nm_layer;
+    J.shift2_max = (double)np.max_shift * (double)np.max_shift;
+}
+// the kernel over the job, enqueued behind the clear of its counters; plain: the one-level traversal; surface: the surface cast
+int ray_launch(rgbd360_map* m, const vmap::RayJob& J, bool sphere, bool plain, bool surface = false) {
+    HIPC(m, hipMemsetAsync(m->rc_stats, 0, (vmap::kRsWords + 1) * sizeof(unsigned long long), m->s->stream));
     const dim3 grid((unsigned)((J.n + vmap::kRayThreads - 1) / vmap::kRayThreads)), block(vmap::kRayThreads);
     with_choice<1, 0>(plain, [&](auto L) {
         with_choice<0, 1>(sphere, [&](auto S) {
-            hipLaunchKernelGGL((vmap::k_vmap_raycast<decltype(L)::value != 0, decltype(S)::value != 0>), grid, block, 0, m->s->stream, J);
+            with_choice<0, 1>(surface, [&](auto F) {
+                hipLaunchKernelGGL((vmap::k_vmap_raycast<decltype(L)::value != 0, decltype(S)::value != 0, decltype(F)::value != 0>), grid, block, 0,
+                                   m->s->stream, J);
+            });
         });
     });
     HIPC(m, hipGetLastError());
@@ -563,12 +599,177 @@ void ray_sphere_job(const rgbd360_map* m, vmap::RayJob& J, int rows, int cols, c
     J.sin_theta = tab, J.cos_theta = tab + cols, J.sin_phi = tab + 2 * cols, J.cos_phi = tab + 2 * cols + rows;
     memcpy(J.pose, pose, sizeof(J.pose));
 }
-// the buffers every cast needs, and the layer
-int ray_prepare(rgbd360_map* m) {
+// the buffers every cast needs (the counters and, behind them, the surface cast's n_on_plane), the coarse layer and, for a surface cast
+// (np), the normal layer
+int ray_prepare(rgbd360_map* m, const rgbd360_map_normal_params* np = nullptr) {
     hipSetDevice(m->s->p.device);
-    HIPC(m, m->rc_stats.ensure(vmap::kRsWords));
-    HIPC(m, m->rc_hstats.ensure(vmap::kRsWords));
-    return ray_layer(m);
+    HIPC(m, m->rc_stats.ensure(vmap::kRsWords + 1));
+    HIPC(m, m->rc_hstats.ensure(vmap::kRsWords + 1));
+    if (const int rc = ray_layer(m)) return rc;
+    return np ? normals_layer(m, *np) : 0;
+}
+
+// rgbd360_map_raycast and, with sf, rgbd360_map_raycast_surface
+int ray_cast_list(rgbd360_map* m, long long n, const float* origins, const float* dirs, int on_device, const rgbd360_map_raycast_params* params, float* t,
+                  int32_t* key3, int32_t* count, uint8_t* rgb3, int32_t* status, rgbd360_map_raycast_stats* stats, const RaySurface* sf) {
+    if (!m) return -1;
+    m->err.clear();
+    rgbd360_map_raycast_params p;
+    rgbd360_map_normal_params np;
+    if (const int rc = ray_check_params(m, params, p)) return rc;
+    if (const int rc = ray_check_surface(m, sf, np)) return rc;
+    if (n < 0 || n >= (1ll << 31)) return vmap_fail(m, -1, "bad ray count");
+    if (n > 0 && (!origins || !dirs)) return vmap_fail(m, -1, "origins and dirs must not be null");
+    ray_fill_stats(nullptr, stats);
+    if (sf && sf->n_on_plane) *sf->n_on_plane = 0;
+    if (n == 0) return 0;
+    hipSetDevice(m->s->p.device);
+    hipStream_t stream = m->s->stream;
+    const size_t N = (size_t)n;
+    float* normal = sf ? sf->normal : nullptr;
+    if (m->n_voxels == 0) {      // nothing to hit: zero-filled outputs (status 0: the ray meets no box), no kernel
+        if (on_device) {
+            if (t) HIPC(m, hipMemsetAsync(t, 0, N * sizeof(float), stream));
+            if (normal) HIPC(m, hipMemsetAsync(normal, 0, N * 3 * sizeof(float), stream));
+            if (key3) HIPC(m, hipMemsetAsync(key3, 0, N * 3 * sizeof(int32_t), stream));
+            if (count) HIPC(m, hipMemsetAsync(count, 0, N * sizeof(int32_t), stream));
+            if (rgb3) HIPC(m, hipMemsetAsync(rgb3, 0, N * 3, stream));
+            if (status) HIPC(m, hipMemsetAsync(status, 0, N * sizeof(int32_t), stream));
+            HIPC(m, hipStreamSynchronize(stream));
+        } else {
+            if (t) memset(t, 0, N * sizeof(float));
+            if (normal) memset(normal, 0, N * 3 * sizeof(float));
+            if (key3) memset(key3, 0, N * 3 * sizeof(int32_t));
+            if (count) memset(count, 0, N * sizeof(int32_t));
+            if (rgb3) memset(rgb3, 0, N * 3);
+            if (status) memset(status, 0, N * sizeof(int32_t));
+        }
+        return 0;
+    }
+    if (const int rc = ray_prepare(m, sf ? &np : nullptr)) return rc;
+    vmap::RayJob J = ray_job(m, p);
+    if (sf) ray_surface_job(m, J, np);
+    J.n = n;
+    if (on_device) {
+        J.origins = origins, J.dirs = dirs;
+        J.t = t, J.key3 = key3, J.count = count, J.rgb3 = rgb3, J.status = status, J.normal = normal;
+    } else {
+        // the rays up, the outputs staged: t, count, status, key3, normal (4-byte arrays first), then rgb3
+        HIPC(m, m->rc_rays.ensure(6 * N));
+        HIPC(m, m->rc_stage.ensure(39 * N));
+        HIPC(m, hipMemcpyAsync(m->rc_rays, origins, 3 * N * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIPC(m, hipMemcpyAsync(m->rc_rays + 3 * N, dirs, 3 * N * sizeof(float), hipMemcpyHostToDevice, stream));
+        uint8_t* sg = m->rc_stage;
+        J.origins = m->rc_rays, J.dirs = m->rc_rays + 3 * N;
+        J.t = t ? reinterpret_cast<float*>(sg) : nullptr;
+        J.count = count ? reinterpret_cast<int32_t*>(sg + 4 * N) : nullptr;
+        J.status = status ? reinterpret_cast<int32_t*>(sg + 8 * N) : nullptr;
+        J.key3 = key3 ? reinterpret_cast<int32_t*>(sg + 12 * N) : nullptr;
+        J.normal = normal ? reinterpret_cast<float*>(sg + 24 * N) : nullptr;
+        J.rgb3 = rgb3 ? sg + 36 * N : nullptr;
+    }
+    if (const int rc = ray_launch(m, J, false, m->rc_plain, sf != nullptr)) return rc;
+    if (!on_device) {
+        if (t) HIPC(m, hipMemcpyAsync(t, J.t, N * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (count) HIPC(m, hipMemcpyAsync(count, J.count, N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        if (status) HIPC(m, hipMemcpyAsync(status, J.status, N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        if (key3) HIPC(m, hipMemcpyAsync(key3, J.key3, N * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        if (normal) HIPC(m, hipMemcpyAsync(normal, J.normal, N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (rgb3) HIPC(m, hipMemcpyAsync(rgb3, J.rgb3, N * 3, hipMemcpyDeviceToHost, stream));
+    }
+    HIPC(m, hipMemcpyAsync(m->rc_hstats, m->rc_stats, (vmap::kRsWords + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIPC(m, hipStreamSynchronize(stream));
+    ray_fill_stats(m->rc_hstats, stats);
+    if (sf && sf->n_on_plane) *sf->n_on_plane = (long long)m->rc_hstats[vmap::kRsWords];
+    return 0;
+}
+
+// rgbd360_map_raycast_sphere and, with sf, rgbd360_map_raycast_surface_sphere
+int ray_cast_sphere(rgbd360_map* m, int rows, int cols, const float* pose, const rgbd360_map_raycast_params* params, float* depth, uint8_t* rgb, int32_t* count,
+                    int32_t* key3, rgbd360_map_raycast_stats* stats, const RaySurface* sf) {
+    if (!m) return -1;
+    m->err.clear();
+    rgbd360_map_raycast_params p;
+    rgbd360_map_normal_params np;
+    if (const int rc = ray_check_params(m, params, p)) return rc;
+    if (const int rc = ray_check_surface(m, sf, np)) return rc;
+    const int chk = ray_sphere_check(m, rows, cols, pose);
+    if (chk < 0) return chk;
+    ray_fill_stats(nullptr, stats);
+    if (sf && sf->n_on_plane) *sf->n_on_plane = 0;
+    if (chk == 1) return 0;
+    const size_t n = (size_t)rows * cols;
+    float* normal = sf ? sf->normal : nullptr;
+    if (m->n_voxels == 0) {
+        if (depth) memset(depth, 0, n * sizeof(float));
+        if (normal) memset(normal, 0, n * 3 * sizeof(float));
+        if (rgb) memset(rgb, 0, n * 3);
+        if (count) memset(count, 0, n * sizeof(int32_t));
+        if (key3) memset(key3, 0, n * 3 * sizeof(int32_t));
+        return 0;
+    }
+    if (const int rc = ray_prepare(m, sf ? &np : nullptr)) return rc;
+    if (const int rc = ray_sphere_tables(m, rows, cols)) return rc;
+    hipStream_t stream = m->s->stream;
+    HIPC(m, m->rc_stage.ensure(39 * n));
+    uint8_t* sg = m->rc_stage;
+    vmap::RayJob J = ray_job(m, p);
+    if (sf) ray_surface_job(m, J, np);
+    ray_sphere_job(m, J, rows, cols, pose);
+    J.t = depth ? reinterpret_cast<float*>(sg) : nullptr;
+    J.count = count ? reinterpret_cast<int32_t*>(sg + 4 * n) : nullptr;
+    J.key3 = key3 ? reinterpret_cast<int32_t*>(sg + 12 * n) : nullptr;
+    J.normal = normal ? reinterpret_cast<float*>(sg + 24 * n) : nullptr;
+    J.rgb3 = rgb ? sg + 36 * n : nullptr;
+    if (const int rc = ray_launch(m, J, true, m->rc_plain, sf != nullptr)) return rc;
+    if (depth) HIPC(m, hipMemcpyAsync(depth, J.t, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (normal) HIPC(m, hipMemcpyAsync(normal, J.normal, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (rgb) HIPC(m, hipMemcpyAsync(rgb, J.rgb3, n * 3, hipMemcpyDeviceToHost, stream));
+    if (count) HIPC(m, hipMemcpyAsync(count, J.count, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (key3) HIPC(m, hipMemcpyAsync(key3, J.key3, n * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIPC(m, hipMemcpyAsync(m->rc_hstats, m->rc_stats, (vmap::kRsWords + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIPC(m, hipStreamSynchronize(stream));
+    ray_fill_stats(m->rc_hstats, stats);
+    if (sf && sf->n_on_plane) *sf->n_on_plane = (long long)m->rc_hstats[vmap::kRsWords];
+    return 0;
+}
+
+// rgbd360_map_raycast_sphere_dev and, with sf, rgbd360_map_raycast_surface_sphere_dev
+int ray_cast_sphere_dev(rgbd360_map* m, int rows, int cols, const float* pose, const rgbd360_map_raycast_params* params, float* depth_dev, uint8_t* rgb_dev,
+                        int32_t* count_dev, int32_t* key3_dev, rgbd360_map_raycast_stats* stats_dev, const RaySurface* sf) {
+    if (!m) return -1;
+    m->err.clear();
+    rgbd360_map_raycast_params p;
+    rgbd360_map_normal_params np;
+    if (const int rc = ray_check_params(m, params, p)) return rc;
+    if (const int rc = ray_check_surface(m, sf, np)) return rc;
+    const int chk = ray_sphere_check(m, rows, cols, pose);
+    if (chk < 0) return chk;
+    hipSetDevice(m->s->p.device);
+    hipStream_t stream = m->s->stream;
+    float* normal_dev = sf ? sf->normal : nullptr;
+    long long* on_plane_dev = sf ? sf->n_on_plane : nullptr;
+    if (chk == 1 || m->n_voxels == 0) {      // nothing to hit: the outputs are cleared on the stream, no kernel
+        const size_t n = chk == 1 ? 0 : (size_t)rows * cols;
+        if (depth_dev && n) HIPC(m, hipMemsetAsync(depth_dev, 0, n * sizeof(float), stream));
+        if (normal_dev && n) HIPC(m, hipMemsetAsync(normal_dev, 0, n * 3 * sizeof(float), stream));
+        if (rgb_dev && n) HIPC(m, hipMemsetAsync(rgb_dev, 0, n * 3, stream));
+        if (count_dev && n) HIPC(m, hipMemsetAsync(count_dev, 0, n * sizeof(int32_t), stream));
+        if (key3_dev && n) HIPC(m, hipMemsetAsync(key3_dev, 0, n * 3 * sizeof(int32_t), stream));
+        if (stats_dev) HIPC(m, hipMemsetAsync(stats_dev, 0, sizeof(rgbd360_map_raycast_stats), stream));
+        if (on_plane_dev) HIPC(m, hipMemsetAsync(on_plane_dev, 0, sizeof(long long), stream));
+        return 0;
+    }
+    if (const int rc = ray_prepare(m, sf ? &np : nullptr)) return rc;
+    if (const int rc = ray_sphere_tables(m, rows, cols)) return rc;
+    vmap::RayJob J = ray_job(m, p);
+    if (sf) ray_surface_job(m, J, np);
+    ray_sphere_job(m, J, rows, cols, pose);
+    J.t = depth_dev, J.rgb3 = rgb_dev, J.count = count_dev, J.key3 = key3_dev, J.normal = normal_dev;
+    if (const int rc = ray_launch(m, J, true, m->rc_plain, sf != nullptr)) return rc;
+    if (stats_dev) HIPC(m, hipMemcpyAsync(stats_dev, m->rc_stats, sizeof(rgbd360_map_raycast_stats), hipMemcpyDeviceToDevice, stream));
+    if (on_plane_dev) HIPC(m, hipMemcpyAsync(on_plane_dev, m->rc_stats + vmap::kRsWords, sizeof(long long), hipMemcpyDeviceToDevice, stream));
+    return 0;
 }
 
 }  // namespace
@@ -584,135 +785,36 @@ extern "C" void rgbd360_map_default_raycast_params(const rgbd360_map* m, rgbd360
 
 extern "C" int rgbd360_map_raycast(rgbd360_map* m, long long n, const float* origins, const float* dirs, int on_device, const rgbd360_map_raycast_params* params,
                                    float* t, int32_t* key3, int32_t* count, uint8_t* rgb3, int32_t* status, rgbd360_map_raycast_stats* stats) {
-    if (!m) return -1;
-    m->err.clear();
-    rgbd360_map_raycast_params p;
-    if (const int rc = ray_check_params(m, params, p)) return rc;
-    if (n < 0 || n >= (1ll << 31)) return vmap_fail(m, -1, "bad ray count");
-    if (n > 0 && (!origins || !dirs)) return vmap_fail(m, -1, "origins and dirs must not be null");
-    ray_fill_stats(nullptr, stats);
-    if (n == 0) return 0;
-    hipSetDevice(m->s->p.device);
-    hipStream_t stream = m->s->stream;
-    const size_t N = (size_t)n;
-    if (m->n_voxels == 0) {      // nothing to hit: zero-filled outputs (status 0: the ray meets no box), no kernel
-        if (on_device) {
-            if (t) HIPC(m, hipMemsetAsync(t, 0, N * sizeof(float), stream));
-            if (key3) HIPC(m, hipMemsetAsync(key3, 0, N * 3 * sizeof(int32_t), stream));
-            if (count) HIPC(m, hipMemsetAsync(count, 0, N * sizeof(int32_t), stream));
-            if (rgb3) HIPC(m, hipMemsetAsync(rgb3, 0, N * 3, stream));
-            if (status) HIPC(m, hipMemsetAsync(status, 0, N * sizeof(int32_t), stream));
-            HIPC(m, hipStreamSynchronize(stream));
-        } else {
-            if (t) memset(t, 0, N * sizeof(float));
-            if (key3) memset(key3, 0, N * 3 * sizeof(int32_t));
-            if (count) memset(count, 0, N * sizeof(int32_t));
-            if (rgb3) memset(rgb3, 0, N * 3);
-            if (status) memset(status, 0, N * sizeof(int32_t));
-        }
-        return 0;
-    }
-    if (const int rc = ray_prepare(m)) return rc;
-    vmap::RayJob J = ray_job(m, p);
-    J.n = n;
-    if (on_device) {
-        J.origins = origins, J.dirs = dirs;
-        J.t = t, J.key3 = key3, J.count = count, J.rgb3 = rgb3, J.status = status;
-    } else {
-        // the rays up, the outputs staged: t, count, status, key3 (4-byte arrays first), then rgb3
-        HIPC(m, m->rc_rays.ensure(6 * N));
-        HIPC(m, m->rc_stage.ensure(27 * N));
-        HIPC(m, hipMemcpyAsync(m->rc_rays, origins, 3 * N * sizeof(float), hipMemcpyHostToDevice, stream));
-        HIPC(m, hipMemcpyAsync(m->rc_rays + 3 * N, dirs, 3 * N * sizeof(float), hipMemcpyHostToDevice, stream));
-        uint8_t* sg = m->rc_stage;
-        J.origins = m->rc_rays, J.dirs = m->rc_rays + 3 * N;
-        J.t = t ? reinterpret_cast<float*>(sg) : nullptr;
-        J.count = count ? reinterpret_cast<int32_t*>(sg + 4 * N) : nullptr;
-        J.status = status ? reinterpret_cast<int32_t*>(sg + 8 * N) : nullptr;
-        J.key3 = key3 ? reinterpret_cast<int32_t*>(sg + 12 * N) : nullptr;
-        J.rgb3 = rgb3 ? sg + 24 * N : nullptr;
-    }
-    if (const int rc = ray_launch(m, J, false, m->rc_plain)) return rc;
-    if (!on_device) {
-        if (t) HIPC(m, hipMemcpyAsync(t, J.t, N * sizeof(float), hipMemcpyDeviceToHost, stream));
-        if (count) HIPC(m, hipMemcpyAsync(count, J.count, N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        if (status) HIPC(m, hipMemcpyAsync(status, J.status, N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        if (key3) HIPC(m, hipMemcpyAsync(key3, J.key3, N * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        if (rgb3) HIPC(m, hipMemcpyAsync(rgb3, J.rgb3, N * 3, hipMemcpyDeviceToHost, stream));
-    }
-    HIPC(m, hipMemcpyAsync(m->rc_hstats, m->rc_stats, vmap::kRsWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    HIPC(m, hipStreamSynchronize(stream));
-    ray_fill_stats(m->rc_hstats, stats);
-    return 0;
+    return ray_cast_list(m, n, origins, dirs, on_device, params, t, key3, count, rgb3, status, stats, nullptr);
 }
-
 extern "C" int rgbd360_map_raycast_sphere(rgbd360_map* m, int rows, int cols, const float pose[16], const rgbd360_map_raycast_params* params, float* depth,
                                           uint8_t* rgb, int32_t* count, int32_t* key3, rgbd360_map_raycast_stats* stats) {
-    if (!m) return -1;
-    m->err.clear();
-    rgbd360_map_raycast_params p;
-    if (const int rc = ray_check_params(m, params, p)) return rc;
-    const int chk = ray_sphere_check(m, rows, cols, pose);
-    if (chk < 0) return chk;
-    ray_fill_stats(nullptr, stats);
-    if (chk == 1) return 0;
-    const size_t n = (size_t)rows * cols;
-    if (m->n_voxels == 0) {
-        if (depth) memset(depth, 0, n * sizeof(float));
-        if (rgb) memset(rgb, 0, n * 3);
-        if (count) memset(count, 0, n * sizeof(int32_t));
-        if (key3) memset(key3, 0, n * 3 * sizeof(int32_t));
-        return 0;
-    }
-    if (const int rc = ray_prepare(m)) return rc;
-    if (const int rc = ray_sphere_tables(m, rows, cols)) return rc;
-    hipStream_t stream = m->s->stream;
-    HIPC(m, m->rc_stage.ensure(27 * n));
-    uint8_t* sg = m->rc_stage;
-    vmap::RayJob J = ray_job(m, p);
-    ray_sphere_job(m, J, rows, cols, pose);
-    J.t = depth ? reinterpret_cast<float*>(sg) : nullptr;
-    J.count = count ? reinterpret_cast<int32_t*>(sg + 4 * n) : nullptr;
-    J.key3 = key3 ? reinterpret_cast<int32_t*>(sg + 12 * n) : nullptr;
-    J.rgb3 = rgb ? sg + 24 * n : nullptr;
-    if (const int rc = ray_launch(m, J, true, m->rc_plain)) return rc;
-    if (depth) HIPC(m, hipMemcpyAsync(depth, J.t, n * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (rgb) HIPC(m, hipMemcpyAsync(rgb, J.rgb3, n * 3, hipMemcpyDeviceToHost, stream));
-    if (count) HIPC(m, hipMemcpyAsync(count, J.count, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    if (key3) HIPC(m, hipMemcpyAsync(key3, J.key3, n * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    HIPC(m, hipMemcpyAsync(m->rc_hstats, m->rc_stats, vmap::kRsWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    HIPC(m, hipStreamSynchronize(stream));
-    ray_fill_stats(m->rc_hstats, stats);
-    return 0;
+    return ray_cast_sphere(m, rows, cols, pose, params, depth, rgb, count, key3, stats, nullptr);
 }
-
 extern "C" int rgbd360_map_raycast_sphere_dev(rgbd360_map* m, int rows, int cols, const float pose[16], const rgbd360_map_raycast_params* params,
                                               float* depth_dev, uint8_t* rgb_dev, int32_t* count_dev, int32_t* key3_dev, rgbd360_map_raycast_stats* stats_dev) {
-    if (!m) return -1;
-    m->err.clear();
-    rgbd360_map_raycast_params p;
-    if (const int rc = ray_check_params(m, params, p)) return rc;
-    const int chk = ray_sphere_check(m, rows, cols, pose);
-    if (chk < 0) return chk;
-    hipSetDevice(m->s->p.device);
-    hipStream_t stream = m->s->stream;
-    if (chk == 1 || m->n_voxels == 0) {      // nothing to hit: the outputs are cleared on the stream, no kernel
-        const size_t n = chk == 1 ? 0 : (size_t)rows * cols;
-        if (depth_dev && n) HIPC(m, hipMemsetAsync(depth_dev, 0, n * sizeof(float), stream));
-        if (rgb_dev && n) HIPC(m, hipMemsetAsync(rgb_dev, 0, n * 3, stream));
-        if (count_dev && n) HIPC(m, hipMemsetAsync(count_dev, 0, n * sizeof(int32_t), stream));
-        if (key3_dev && n) HIPC(m, hipMemsetAsync(key3_dev, 0, n * 3 * sizeof(int32_t), stream));
-        if (stats_dev) HIPC(m, hipMemsetAsync(stats_dev, 0, sizeof(rgbd360_map_raycast_stats), stream));
-        return 0;
-    }
-    if (const int rc = ray_prepare(m)) return rc;
-    if (const int rc = ray_sphere_tables(m, rows, cols)) return rc;
-    vmap::RayJob J = ray_job(m, p);
-    ray_sphere_job(m, J, rows, cols, pose);
-    J.t = depth_dev, J.rgb3 = rgb_dev, J.count = count_dev, J.key3 = key3_dev;
-    if (const int rc = ray_launch(m, J, true, m->rc_plain)) return rc;
-    if (stats_dev) HIPC(m, hipMemcpyAsync(stats_dev, m->rc_stats, sizeof(rgbd360_map_raycast_stats), hipMemcpyDeviceToDevice, stream));
-    return 0;
+    return ray_cast_sphere_dev(m, rows, cols, pose, params, depth_dev, rgb_dev, count_dev, key3_dev, stats_dev, nullptr);
+}
+
+// the surface cast: the same rays, checks and outputs, with the normal of each hit and the depth on its plane (map_normals.h)
+extern "C" int rgbd360_map_raycast_surface(rgbd360_map* m, long long n, const float* origins, const float* dirs, int on_device,
+                                           const rgbd360_map_raycast_params* ray_params, const rgbd360_map_normal_params* normal_params, float* t, float* normal,
+                                           int32_t* key3, int32_t* count, uint8_t* rgb3, int32_t* status, long long* n_on_plane,
+                                           rgbd360_map_raycast_stats* stats) {
+    const RaySurface sf = {normal_params, normal, n_on_plane};
+    return ray_cast_list(m, n, origins, dirs, on_device, ray_params, t, key3, count, rgb3, status, stats, &sf);
+}
+extern "C" int rgbd360_map_raycast_surface_sphere(rgbd360_map* m, int rows, int cols, const float pose[16], const rgbd360_map_raycast_params* ray_params,
+                                                  const rgbd360_map_normal_params* normal_params, float* depth, float* normal, uint8_t* rgb, int32_t* count,
+                                                  int32_t* key3, long long* n_on_plane, rgbd360_map_raycast_stats* stats) {
+    const RaySurface sf = {normal_params, normal, n_on_plane};
+    return ray_cast_sphere(m, rows, cols, pose, ray_params, depth, rgb, count, key3, stats, &sf);
+}
+extern "C" int rgbd360_map_raycast_surface_sphere_dev(rgbd360_map* m, int rows, int cols, const float pose[16], const rgbd360_map_raycast_params* ray_params,
+                                                      const rgbd360_map_normal_params* normal_params, float* depth_dev, float* normal_dev, uint8_t* rgb_dev,
+                                                      int32_t* count_dev, int32_t* key3_dev, long long* n_on_plane_dev, rgbd360_map_raycast_stats* stats_dev) {
+    const RaySurface sf = {normal_params, normal_dev, n_on_plane_dev};
+    return ray_cast_sphere_dev(m, rows, cols, pose, ray_params, depth_dev, rgb_dev, count_dev, key3_dev, stats_dev, &sf);
 }
 
 // measurement and the traversal switch (rgbd360_hip_diag.h)

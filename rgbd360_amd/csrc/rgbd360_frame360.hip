@@ -1258,10 +1258,11 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
 // ---------------------------------------------------------------------------------------------------------
 #include "voxel_map.h"
 #include "map_edit.h"
-#include "map_raycast.h"
 #include "gn_math.h"
 #include "map_align.h"
 #include "map_align_plane.h"
+#include "map_normals.h"
+#include "map_raycast.h"
 
 #ifdef RGBD360_HULL_DBG
 extern "C" int rgbd360_debug_hull_stats(unsigned long long* out /* [4096][8] */) {

@@ -106,6 +106,15 @@ struct rgbd360_map {
     int rc_tab_rows = 0, rc_tab_cols = 0;
     DevBuf<uint8_t> rc_stage;                                     // the host entries' outputs on the device: 27 bytes per ray
     bool rc_plain = false;                                        // the one-level traversal (rgbd360_map_raycast_set_plain)
+    // surface normals (map_normals.h): one 16-byte record per slot, those of revision nm_rev under the three fit parameters nm_*; rebuilt
+    // when the revision or a parameter differs
+    unsigned long long nm_rev = 0;
+    int nm_min_count = 0, nm_min_support = 0;
+    float nm_max_flatness = 0.f;
+    DevBuf<uint4> nm_layer;
+    DevBuf<unsigned long long> nm_stats;                          // the build's counters and the read-out's record counter ...
+    PinnedBuf<unsigned long long> nm_hstats;                      // ... and their pinned copy
+    DevBuf<uint8_t> nm_stage;                                     // the host read-out's records on the device: 48 bytes each
 };
 
 namespace vmap {

@@ -10,6 +10,8 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
     depth, rgb, count, key3, stats = gmap.render_sphere(rows, cols, pose)      # the map as a spherical RGB-D frame (csrc/map_render.h)
     depth, rgb, count, key3, stats = gmap.raycast_sphere(rows, cols, pose)     # ... as a per-pixel first hit (csrc/map_raycast.h)
     t, key3, count, rgb, status, stats = gmap.raycast(origins, dirs)           # the first voxel along each ray of a list
+    xyz, normal, curvature, status, count, key3, stats = gmap.normals(viewpoint)   # one normal per voxel (csrc/map_normals.h) ...
+    depth, normal, rgb, count, key3, n_on_plane, stats = gmap.raycast_surface_sphere(rows, cols, pose)     # ... and the surface a ray meets
     xyz, rgb, count, key = gmap.extract()          # sorted by (i_z, i_y, i_x)
     gmap.remove_sphere(rgb, depth, currentPose)    # exactly undoes that insert (csrc/map_edit.h); gmap.mismatch tells of a broken contract
     gmap.move_sphere(rgb, depth, currentPose, correctedPose)       # a pose-graph correction: removed at the old pose, inserted at the new
@@ -31,6 +33,7 @@ from .register import Rgbd360Error, _ptr, pose_from_cm, pose_to_cm
 MAP_FULL = 3      # RGBD360_MAP_FULL
 MAP_MISMATCH = 4  # RGBD360_MAP_MISMATCH
 RAY_MISS_BOX, RAY_HIT, RAY_LEFT_BOX, RAY_T_MAX, RAY_MAX_STEPS, RAY_BAD = range(6)      # RGBD360_RAY_*
+NORMAL_NONE, NORMAL_OK, NORMAL_UNSUPPORTED, NORMAL_NONPLANAR = range(4)                # RGBD360_NORMAL_*
 
 
 def _as_dict(st, skip=()):
@@ -347,6 +350,76 @@ class VoxelMap:
         self._check(self._L.rgbd360_map_raycast_sphere(self._handle(), rows, cols, _ptr(g), C.byref(p), _ptr(depth), _ptr(rgb), _ptr(count), _ptr(key3),
                                                        C.byref(st)))
         return depth, rgb, count, key3, _as_dict(st)
+
+    # ---- surface normals (rgbd360_map_normals, rgbd360_map_raycast_surface*: one normal per voxel fitted to the centroids of the 27 cells
+    #      around it, resident next to the table; csrc/map_normals.h)
+    def normal_params(self, min_count=None, min_support=None, max_flatness=None, max_shift=None):
+        """The defaults (min_count 1, min_support 5, max_flatness 0.05, max_shift 2.0 leaves) with the given fields replaced."""
+        return self._params(_lib.MapNormalParams, self._L.rgbd360_map_default_normal_params, min_count=min_count, min_support=min_support,
+                            max_flatness=max_flatness, max_shift=max_shift)
+
+    def normals(self, viewpoint=None, max_out=None, **params):
+        """One record per voxel, in no specified order: (xyz [k, 3] float32, normal [k, 3] float32, curvature [k] float32, status [k] int32 =
+        NORMAL_*, count [k] int32, key3 [k, 3] int32, the statistics as a dict), k = min(len, max_out).  viewpoint (3 floats, world): the
+        normals face it; None: the canonical sign (the largest component positive).  The normal is zero unless the status is NORMAL_OK."""
+        p = self.normal_params(**params)
+        v = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float32).reshape(3)
+        n = len(self)
+        k = n if max_out is None else min(n, int(max_out))
+        xyz, normal, key3 = np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros((k, 3), np.int32)
+        curvature, status, count = np.zeros(k, np.float32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        st = _lib.MapNormalStats()
+        got = self._L.rgbd360_map_normals(self._handle(), C.byref(p), None if v is None else _ptr(v), k, _ptr(xyz), _ptr(normal), _ptr(curvature),
+                                          _ptr(status), _ptr(count), _ptr(key3), C.byref(st))
+        if got != n:
+            raise Rgbd360Error(f"rgbd360_map_normals failed ({got}): {self._L.rgbd360_map_last_error(self._h).decode()}")
+        return xyz, normal, curvature, status, count, key3, _as_dict(st)
+
+    def _surface_params(self, params):
+        names = ("min_support", "max_flatness", "max_shift", "normal_min_count")
+        nm = {k: params.pop(k) for k in names if k in params}
+        nm["min_count"] = nm.pop("normal_min_count", None)
+        return self.raycast_params(**params), self.normal_params(**nm)
+
+    def raycast_surface(self, origins, dirs, **params):
+        """raycast with the surface: (t, normal [n, 3] float32, key3, count, rgb, status, n_on_plane, the statistics).  A hit whose voxel has
+        a normal gets it, facing the ray's origin, and the depth on the plane through the voxel's centroid (n_on_plane counts those); all
+        else is raycast's, bit for bit.  params: raycast_params' fields, and min_support, max_flatness, max_shift, normal_min_count."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise Rgbd360Error("VoxelMap.raycast_surface: origins and dirs must have the same shape")
+        n = o.shape[0]
+        p, q = self._surface_params(params)
+        t = np.zeros(n, np.float32)
+        normal = np.zeros((n, 3), np.float32)
+        key3 = np.zeros((n, 3), np.int32)
+        count = np.zeros(n, np.int32)
+        rgb = np.zeros((n, 3), np.uint8)
+        status = np.zeros(n, np.int32)
+        on_plane = C.c_longlong()
+        st = _lib.MapRaycastStats()
+        self._check(self._L.rgbd360_map_raycast_surface(self._handle(), n, _ptr(o), _ptr(d), 0, C.byref(p), C.byref(q), _ptr(t), _ptr(normal), _ptr(key3),
+                                                        _ptr(count), _ptr(rgb), _ptr(status), C.byref(on_plane), C.byref(st)))
+        return t, normal, key3, count, rgb, status, int(on_plane.value), _as_dict(st)
+
+    def raycast_surface_sphere(self, rows: int, cols: int, pose, **params):
+        """raycast_sphere with the surface: (depth, normal HxWx3 float32 in world coordinates, rgb, count, key3, n_on_plane, the
+        statistics); depth and rgb are what RegisterPhotoICP.setTargetFrame takes."""
+        rows, cols = int(rows), int(cols)
+        p, q = self._surface_params(params)
+        g = pose_to_cm(pose)
+        shape = (max(rows, 0), max(cols, 0))
+        depth = np.zeros(shape, np.float32)
+        normal = np.zeros(shape + (3,), np.float32)
+        rgb = np.zeros(shape + (3,), np.uint8)
+        count = np.zeros(shape, np.int32)
+        key3 = np.zeros(shape + (3,), np.int32)
+        on_plane = C.c_longlong()
+        st = _lib.MapRaycastStats()
+        self._check(self._L.rgbd360_map_raycast_surface_sphere(self._handle(), rows, cols, _ptr(g), C.byref(p), C.byref(q), _ptr(depth), _ptr(normal),
+                                                               _ptr(rgb), _ptr(count), _ptr(key3), C.byref(on_plane), C.byref(st)))
+        return depth, normal, rgb, count, key3, int(on_plane.value), _as_dict(st)
 
     def raycast_set_plain(self, plain: bool):
         """Diagnostics: the one-level traversal instead of the coarse layer for the later ray casts; the outputs are the same bits."""
