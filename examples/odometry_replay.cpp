@@ -4,7 +4,7 @@
 //     frame_%03d.rgb  (H*W*3 uint8)   frame_%03d.depth (H*W uint16 mm)
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/odometry_replay.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o odometry_replay
-// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane] [--render-map PREFIX] [--raycast-map PREFIX] [--map-normals OUT] [--raycast-surface PREFIX] [--map-window N]]
+// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane | --refine-on-map-c2f SHIFT [--plane]] [--render-map PREFIX] [--raycast-map PREFIX] [--map-normals OUT] [--raycast-surface PREFIX] [--map-window N]]
 //         --sequence: all frames are loaded first and the frame loop runs inside the library (alignSequence)
 //         --multi N:  the same sequence sharded over N GPUs of this node from this one process (rgbd360_multi_*: one host thread
 //                     per device, contiguous shards of pairs, one ncclAllGather of the solved poses over xGMI); prints the
@@ -24,6 +24,10 @@
 //         --refine-on-map-plane: the same with the point-to-plane form (GlobalMap::alignSpherePlane: the plane cost of the GICP those call
 //                     sites use); prints one "refine-plane" line per frame with the contributing points, the unsupported and nonplanar
 //                     ones and both fitness values.  Takes precedence over --refine-on-map.
+//         --refine-on-map-c2f SHIFT [--plane]: the same through the map pyramid (GlobalMap::alignSphereCoarseToFine): the ICP runs on the maps of
+//                     leaf * 2^SHIFT .. leaf, merged out of the resident table, each level from the pose of the one before -- a capture range of
+//                     2^SHIFT leaves where the two options above have one; --plane: the point-to-plane form on every level.  Prints one
+//                     "refine-c2f" line per frame and one "  level" line per level.  Takes precedence over both.
 //         --render-map PREFIX: (needs --map) after the replay the map is rendered as a spherical frame of the input's size at the last
 //                     pose (GlobalMap::renderSphere: the reference's viewer.globalMap, OdometryRGBD360.cpp:242-268, as a panorama) and
 //                     written as PREFIX_rgb.ppm (P6) and PREFIX_depth.pfm (Pf, metres, 0 in holes, rows bottom to top); prints one
@@ -181,7 +185,8 @@ int main(int argc, char** argv) {
     const bool use_pbmap = argc > 5 && std::string(argv[5]) == "--pbmap";
     std::string map_file, render_prefix, raycast_prefix, normals_file, surface_prefix;
     float leaf = 0.05f;
-    bool refine_on_map = false, refine_on_map_plane = false;
+    bool refine_on_map = false, refine_on_map_plane = false, c2f_plane = false;
+    int c2f_shift = -1;
     int map_window = 0;
     for (int a = 5; a < argc; ++a) {
         if (a + 1 < argc && std::string(argv[a]) == "--map") map_file = argv[a + 1];
@@ -193,6 +198,8 @@ int main(int argc, char** argv) {
         if (a + 1 < argc && std::string(argv[a]) == "--raycast-surface") surface_prefix = argv[a + 1];
         if (std::string(argv[a]) == "--refine-on-map") refine_on_map = true;
         if (std::string(argv[a]) == "--refine-on-map-plane") refine_on_map_plane = true;
+        if (a + 1 < argc && std::string(argv[a]) == "--refine-on-map-c2f") c2f_shift = atoi(argv[a + 1]);
+        if (std::string(argv[a]) == "--plane") c2f_plane = true;
     }
     if (!render_prefix.empty() && map_file.empty()) {
         fprintf(stderr, "--render-map needs --map\n");
@@ -275,7 +282,22 @@ int main(int argc, char** argv) {
         printf("pair %d status %d sso %.4f rel_t %.5f %.5f %.5f pose_t %.5f %.5f %.5f\n", k - 1, align360.status(), align360.SSO,
                rel(0, 3), rel(1, 3), rel(2, 3), currentPose(0, 3), currentPose(1, 3), currentPose(2, 3));
         fprintf(stderr, "entropy %d %.5f\n", k - 1, align360.calcEntropy());                     // :207 (commented out in the source)
-        if (globalMap && refine_on_map_plane) {
+        if (globalMap && c2f_shift >= 0) {
+            rgbd360::Mat4f refined = currentPose;
+            rgbd360_map_c2f_params p = globalMap->c2fParams();
+            p.top_shift = c2f_shift;
+            p.kind = c2f_plane ? 1 : 0;
+            const int status = globalMap->alignSphereCoarseToFine(frame2.sphereDepth, currentPose, refined, /*convention=*/0, &p);
+            const rgbd360_map_c2f_result& r = globalMap->c2fResult();
+            const rgbd360_map_c2f_level& last = r.levels[r.n_levels - 1];
+            printf("refine-c2f %d status %d levels %d kind %d matched %lld fitness %.6f pose_t %.5f %.5f %.5f pyramid_bytes %zu\n", k - 1, status, r.n_levels,
+                   p.kind, last.n_matched, last.fitness, refined(0, 3), refined(1, 3), refined(2, 3), globalMap->pyramidBytes());
+            for (int l = 0; l < r.n_levels; ++l)
+                printf("  level %d shift %d status %d iterations %d converged %d matched %lld fitness %.6f pose_t %.5f %.5f %.5f\n", k - 1, r.levels[l].shift,
+                       r.levels[l].status, r.levels[l].iterations, r.levels[l].converged, r.levels[l].n_matched, r.levels[l].fitness, r.levels[l].pose[12],
+                       r.levels[l].pose[13], r.levels[l].pose[14]);
+            if (status == RGBD360_OK) currentPose = refined;
+        } else if (globalMap && refine_on_map_plane) {
             rgbd360::Mat4f refined = currentPose;
             const int status = globalMap->alignSpherePlane(frame2.sphereDepth, currentPose, refined, /*convention=*/0);
             const rgbd360_map_align_plane_result& r = globalMap->alignPlaneResult();

@@ -15,6 +15,9 @@
 //     globalMap.alignSphere(frame.sphereDepth, guess, pose)     point-to-point, nearest voxel centroid within max_dist <= leaf
 //     globalMap.alignSpherePlane(frame.sphereDepth, guess, pose)   point-to-plane: the same match, the plane fitted to the centroids around it
 //                                                                  (the call sites use pcl::GeneralizedIterativeClosestPoint, a plane cost)
+// Both match within one voxel; a guess further off goes through the map pyramid (rgbd360_map_level, rgbd360_map_align_c2f_*: the maps of
+// 2, 4, 8 .. times the voxel size are merged out of the table, exactly, and the ICP runs from the coarsest down),
+//     globalMap.alignSphereCoarseToFine(frame.sphereDepth, guess, pose)     c2fResult().levels[k]: what each level did
 // The map as a spherical RGB-D frame (rgbd360_map_render_*: the reference shows viewer.globalMap in a PCL window, OdometryRGBD360.cpp:242-268,
 // and aligns against keyframes, OdometryKeyFrame360.cpp): a z-buffered splat of the table into the panorama of the dense alignment,
 //     globalMap.renderSphere(rows, cols, pose, depth, rgb)     whose outputs RegisterPhotoICP::setTargetFrame takes as they are
@@ -160,6 +163,32 @@ class GlobalMap {
         return rc;
     }
     const rgbd360_map_align_plane_result& alignPlaneResult() const { return alignPlane_; }      // of the last alignSpherePlane / alignCloudPlane call
+
+    // Coarse-to-fine ICP (rgbd360_map_align_c2f_*): alignSphere / alignCloud (kind 0) or their Plane forms (kind 1) on the levels
+    // top_shift .. 0 of the map pyramid, level s being the map at voxelSize * 2^s merged out of the table; each level starts from the pose the
+    // one before ended on and matches within max_dist_leaves of ITS voxel size, so top_shift 3 captures eight voxel sizes.  The levels are
+    // built or refreshed by the call (device memory beside the table: pyramidBytes(); releaseLevels() frees it).  The map is not changed.
+    // Returns level 0's status; c2fResult() has every level's status, iterations, matches, fitness and pose.
+    rgbd360_map_c2f_params c2fParams() const {
+        rgbd360_map_c2f_params p;
+        rgbd360_map_default_c2f_params(map_, &p);
+        return p;
+    }
+    int alignSphereCoarseToFine(const ImageView& depth, const Mat4f& guess, Mat4f& pose, int convention = 0, const rgbd360_map_c2f_params* params = nullptr) {
+        if (depth.type == ImageView::U8C3) throw std::runtime_error("GlobalMap::alignSphereCoarseToFine: a 16UC1 / 32FC1 depth image");
+        const int rc = rgbd360_map_align_c2f_sphere(map_, depth.data, depth.step, depthType(depth), depth.rows, depth.cols, convention, guess.m, 0,
+                                                    params, pose.m, &c2f_);
+        check(rc, "rgbd360_map_align_c2f_sphere");
+        return rc;
+    }
+    int alignCloudCoarseToFine(const float* xyz, long long n, const Mat4f& guess, Mat4f& pose, const rgbd360_map_c2f_params* params = nullptr) {
+        const int rc = rgbd360_map_align_c2f_cloud(map_, xyz, n, guess.m, 0, params, pose.m, &c2f_);
+        check(rc, "rgbd360_map_align_c2f_cloud");
+        return rc;
+    }
+    const rgbd360_map_c2f_result& c2fResult() const { return c2f_; }      // of the last alignSphereCoarseToFine / alignCloudCoarseToFine call
+    size_t pyramidBytes() const { return rgbd360_map_pyramid_bytes(map_); }
+    void releaseLevels() { check(rgbd360_map_release_levels(map_), "rgbd360_map_release_levels"); }
 
     // The map splatted into the full-sphere panorama of rows x cols at `pose` (world <- frame), the nearest voxel winning a pixel
     // (rgbd360_map_render_sphere; defaults: min_count 1, near = leaf, splat 1.0, max_half 8).  The vectors are resized; depth is float32
@@ -324,6 +353,7 @@ class GlobalMap {
     rgbd360_map_edit_stats edit_{};
     rgbd360_map_align_result align_{};
     rgbd360_map_align_plane_result alignPlane_{};
+    rgbd360_map_c2f_result c2f_{};
     rgbd360_map_render_stats render_{};
     rgbd360_map_raycast_stats raycast_{};
     rgbd360_map_normal_stats normal_{};

@@ -338,7 +338,8 @@ int    rgbd360_map_census(rgbd360_map* map, rgbd360_map_census_counts* out);
  * Differences from the reference, stated: its active choice is pcl::GeneralizedIterativeClosestPoint at 0.3 - 0.4 m over a kd-tree of
  * the other cloud; this is the point-to-point form on the grid, against centroids.  PCL is not part of the reference tree: parity
  * with PCL is unpinned.  The point-to-plane form of the same alignment follows below (rgbd360_map_align_plane_*).  Out of scope: GICP's
- * per-point covariance weighting, radii above one leaf, a coarse-to-fine chain inside the library, several GPUs. */
+ * per-point covariance weighting, radii above one leaf, several GPUs.  (A coarse-to-fine chain over coarser maps derived from this one:
+ * rgbd360_map_align_c2f_* below.) */
 typedef struct {
     float max_dist;            /* setMaxCorrespondenceDistance, in (0, leaf]; default: leaf */
     int   max_iters;           /* setMaximumIterations: 10 (OdometryRGBD360.cpp:102) */
@@ -612,6 +613,71 @@ int       rgbd360_map_raycast_surface_sphere_dev(rgbd360_map* map, int rows, int
                                                  const rgbd360_map_raycast_params* ray_params, const rgbd360_map_normal_params* normal_params,
                                                  float* depth_dev, float* normal_dev, uint8_t* rgb_dev, int32_t* count_dev, int32_t* key3_dev,
                                                  long long* n_on_plane_dev, rgbd360_map_raycast_stats* stats_dev);
+
+/* ---- the map pyramid and coarse-to-fine ICP against it (csrc/map_pyramid.h) -------------------------------------------------------
+ * Both ICPs above match within one leaf, so their capture range is one leaf; the reference's call sites run at 0.3 - 0.4 m.  The coarser
+ * maps a wider basin needs are a function of the resident table.  Level s (1 <= s <= RGBD360_MAP_MAX_SHIFT) of a map is the map with
+ * leaf' = leaf 2^s, inv_leaf' = inv_leaf 2^-s (both exact), the same box, one voxel per distinct (i_x >> s, i_y >> s, i_z >> s)
+ * (arithmetic shifts: -1 and -2 merge at s = 1, -1 and 0 never do) over the parent's voxels with count > 0, and as its seven words
+ * (count, S_x, S_y, S_z, S_r, S_g, S_b) the integer sums of theirs.  That is the contract.  Since fl(w inv_leaf') = fl(w inv_leaf) 2^-s
+ * while the product is a normal float, the level equals, word for word, the map the same inserts build at leaf' -- for every point
+ * whose |w_k inv_leaf| is 0 or >= 2^-126 2^s on all axes (a subnormal product may round differently: such a point lies within 1e-36 m of
+ * a coordinate plane).  Levels are exact, independent of the order of insertion and of the table's layout.
+ * Levels belong to the parent and are built on demand, level s out of level s - 1 by one kernel (integer atomics only), into a table of
+ * the next power of two at or above twice the voxels of the level below (at least 1024 slots), so that no voxel is ever dropped; they are
+ * device memory BESIDE the table: rgbd360_map_bytes stays the table's, rgbd360_map_pyramid_bytes is the levels'.  A level remembers the
+ * parent's state it was built from and is rebuilt by the next rgbd360_map_level / _align_c2f_* call after the parent was written;
+ * between such calls it keeps the content of the last one.  Nothing is maintained incrementally. */
+#define RGBD360_MAP_MAX_SHIFT 6
+/* Builds or refreshes levels 1 .. shift and hands out level `shift` as a BORROWED handle: every entry that only reads a map takes it
+ * (size, bytes, extract, census, both alignments with their default-params and diagnostic eval entries, render, both ray casts,
+ * normals, last_error); every entry that writes one (insert, remove, move, clear, rehash, set_box) refuses it with -1 and a message
+ * before anything is touched; rgbd360_map_destroy of it does nothing.  The handle stays the same pointer for later calls with the same
+ * shift and is valid until the parent is destroyed or rgbd360_map_release_levels is called.  The box is the parent's at the time of the
+ * call.  0; -1 for a shift outside 1 .. RGBD360_MAP_MAX_SHIFT, a NULL argument or a `map` that is itself a level; -103 out of memory;
+ * RGBD360_MAP_FULL if a build dropped a voxel (not expected at half load): then levels from that one up are gone. */
+int    rgbd360_map_level(rgbd360_map* map, int shift, rgbd360_map** level);
+/* device memory of the levels' tables (0 without levels; their ray-cast and normal layers and work buffers are not counted, as for a map) */
+size_t rgbd360_map_pyramid_bytes(const rgbd360_map* map);
+/* frees every level; handles handed out become invalid.  0; -1 for NULL or a level. */
+int    rgbd360_map_release_levels(rgbd360_map* map);
+/* Coarse-to-fine: for s = top_shift .. 0 the alignment of `kind` above runs on level s (level 0 is the map itself) from the pose the
+ * level before ended on, with max_dist = max_dist_leaves x that level's leaf (the product in float32) and the other parameters as
+ * given.  A level that ends with a status other than RGBD360_OK hands on the pose it was given.  The input is checked and uploaded
+ * once.  Each level's step is, bit for bit, the single-level entry called on rgbd360_map_level(map, s) with that pose and those
+ * parameters.  top_shift 0 is the single-level call. */
+typedef struct {
+    int   top_shift;           /* the coarsest level, 0 .. RGBD360_MAP_MAX_SHIFT: 3 */
+    int   kind;                /* 0 point-to-point (rgbd360_map_align_*), 1 point-to-plane (rgbd360_map_align_plane_*), on every level */
+    int   max_iters;           /* per level; these four as in rgbd360_map_align_params: 10, 1, 1e-6, 6 */
+    int   min_count;
+    float eps;
+    float max_dist_leaves;     /* in (0, 1]: 1 */
+    long long min_matches;
+    int   min_support;         /* kind 1, as in rgbd360_map_align_plane_params: 5, 0.05 */
+    float max_flatness;
+} rgbd360_map_c2f_params;
+typedef struct {
+    int shift, status, iterations, converged;                          /* of this level's alignment */
+    long long n_valid, n_box_rejected, n_out_of_range, n_matched;      /* of its final evaluation */
+    double fitness;
+    float pose[16];            /* the pose it ended on (its own result; what it hands on is this only when status is RGBD360_OK) */
+} rgbd360_map_c2f_level;
+typedef struct {
+    int n_levels;              /* top_shift + 1; levels[0] is the coarsest, levels[n_levels - 1] the map itself */
+    rgbd360_map_c2f_level levels[RGBD360_MAP_MAX_SHIFT + 1];
+    float hessian[36], gradient[6];         /* of level 0's final evaluation */
+} rgbd360_map_c2f_result;
+void   rgbd360_map_default_c2f_params(const rgbd360_map* map, rgbd360_map_c2f_params* p);
+/* Arguments, refusals and empty inputs as for rgbd360_map_align_sphere / _cloud; also -1 for top_shift outside 0 .. RGBD360_MAP_MAX_SHIFT,
+ * a kind other than 0 or 1, max_dist_leaves outside (0, 1] or a `map` that is itself a level, and what rgbd360_map_level returns when a
+ * level cannot be built.  The status returned and pose_out are those of level 0.  Neither the map nor a level's table is written;
+ * levels 1 .. top_shift are refreshed first. */
+int    rgbd360_map_align_c2f_sphere(rgbd360_map* map, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                    const float guess[16], int on_device, const rgbd360_map_c2f_params* params, float pose_out[16],
+                                    rgbd360_map_c2f_result* result);
+int    rgbd360_map_align_c2f_cloud(rgbd360_map* map, const float* xyz, long long n, const float guess[16], int on_device,
+                                   const rgbd360_map_c2f_params* params, float pose_out[16], rgbd360_map_c2f_result* result);
 
 /* ---- pose-graph optimisation of store edges (csrc/pose_graph.h) -----------------------------------------------------------------
  * The reference closes its SLAM loop in g2o: optimizer.addVertex(pose), optimizer.addEdge(nearestKF, newKF, relPose, registerer.getInfoMat()),

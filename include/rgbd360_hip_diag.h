@@ -191,6 +191,14 @@ int rgbd360_map_time_raycast(rgbd360_map* map, long long n, const float* origins
 int rgbd360_map_time_normals(rgbd360_map* map, const rgbd360_map_normal_params* params, int reps, float* build_us, float* scan_us,
                              rgbd360_map_normal_stats* stats, long long* layer_bytes);
 
+/* The build of the map pyramid (rgbd360_map_level, rgbd360_hip.h) under HIP events, averages over `reps` in microseconds: avg_us[s - 1],
+ * 1 <= s <= top_shift, the build of level s out of level s - 1 (the clear of its table and of the counters, one k_vmap_coarsen launch);
+ * avg_us[6] the builds of levels 1 .. top_shift back to back; avg_us[7] ONE k_vmap_extract launch (centroids only) over the parent's
+ * table, the cost of merely scanning it.  Entries of levels above top_shift are 0.  counters (may be NULL): per level s four words at
+ * 4 (s - 1): live slots read, voxels created, points carried, voxels dropped.  Levels 1 .. top_shift are refreshed first (untimed) and
+ * are valid afterwards; the map is not changed. */
+int rgbd360_map_time_coarsen(rgbd360_map* map, int top_shift, int reps, float avg_us[8], long long* counters);
+
 /* The same timer with the launches rotating over n_ctx contexts of one device (each with its own copy of a frame pair) on
  * ctxs[0]'s stream: once n_ctx x the level's working set exceeds the 256 MiB Infinity Cache every launch is fed from HBM. */
 int rgbd360_time_eval_kernel_rotating(rgbd360_ctx* const* ctxs, int n_ctx, int level, const float pose[16], int method,

@@ -43,6 +43,8 @@ SYMBOLS = [
     "rgbd360_map_raycast_set_plain", "rgbd360_map_time_raycast",
     "rgbd360_map_default_normal_params", "rgbd360_map_normals", "rgbd360_map_normals_dev", "rgbd360_map_raycast_surface",
     "rgbd360_map_raycast_surface_sphere", "rgbd360_map_raycast_surface_sphere_dev", "rgbd360_map_time_normals",
+    "rgbd360_map_level", "rgbd360_map_pyramid_bytes", "rgbd360_map_release_levels", "rgbd360_map_default_c2f_params",
+    "rgbd360_map_align_c2f_sphere", "rgbd360_map_align_c2f_cloud", "rgbd360_map_time_coarsen",
     "rgbd360_graph_create", "rgbd360_graph_destroy", "rgbd360_graph_last_error", "rgbd360_graph_add_vertices", "rgbd360_graph_add_edges",
     "rgbd360_graph_set_poses", "rgbd360_graph_set_fixed", "rgbd360_graph_n_vertices", "rgbd360_graph_n_edges", "rgbd360_graph_clear",
     "rgbd360_graph_default_params", "rgbd360_graph_optimize", "rgbd360_graph_get_poses", "rgbd360_graph_chi2", "rgbd360_graph_get_trace",
@@ -120,6 +122,24 @@ class MapAlignPlaneResult(C.Structure):  # rgbd360_map_align_plane_result
 
 class MapAlignTrace(C.Structure):        # rgbd360_map_align_trace (rgbd360_hip_diag.h)
     _fields_ = [("n", C.c_longlong), ("sum_sq", C.c_double), ("update", C.c_float * 6)]
+
+
+MAP_MAX_SHIFT = 6                        # RGBD360_MAP_MAX_SHIFT
+
+
+class MapC2fParams(C.Structure):         # rgbd360_map_c2f_params
+    _fields_ = [("top_shift", C.c_int), ("kind", C.c_int), ("max_iters", C.c_int), ("min_count", C.c_int), ("eps", C.c_float),
+                ("max_dist_leaves", C.c_float), ("min_matches", C.c_longlong), ("min_support", C.c_int), ("max_flatness", C.c_float)]
+
+
+class MapC2fLevel(C.Structure):          # rgbd360_map_c2f_level
+    _fields_ = [("shift", C.c_int), ("status", C.c_int), ("iterations", C.c_int), ("converged", C.c_int), ("n_valid", C.c_longlong),
+                ("n_box_rejected", C.c_longlong), ("n_out_of_range", C.c_longlong), ("n_matched", C.c_longlong), ("fitness", C.c_double),
+                ("pose", C.c_float * 16)]
+
+
+class MapC2fResult(C.Structure):         # rgbd360_map_c2f_result
+    _fields_ = [("n_levels", C.c_int), ("levels", MapC2fLevel * (MAP_MAX_SHIFT + 1)), ("hessian", C.c_float * 36), ("gradient", C.c_float * 6)]
 
 
 class MapRenderParams(C.Structure):     # rgbd360_map_render_params
@@ -412,6 +432,15 @@ def load() -> C.CDLL:
     L.rgbd360_map_raycast_surface_sphere_dev.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRaycastParams), C.POINTER(MapNormalParams), vp, vp, vp, vp, vp,
                                                          vp, vp]
     L.rgbd360_map_time_normals.argtypes = [vp, C.POINTER(MapNormalParams), i32, vp, vp, C.POINTER(MapNormalStats), C.POINTER(ll)]
+    L.rgbd360_map_level.argtypes = [vp, i32, C.POINTER(vp)]
+    L.rgbd360_map_pyramid_bytes.argtypes = [vp]
+    L.rgbd360_map_pyramid_bytes.restype = C.c_size_t
+    L.rgbd360_map_release_levels.argtypes = [vp]
+    L.rgbd360_map_default_c2f_params.argtypes = [vp, C.POINTER(MapC2fParams)]
+    L.rgbd360_map_default_c2f_params.restype = None
+    L.rgbd360_map_align_c2f_sphere.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, C.POINTER(MapC2fParams), f32p, C.POINTER(MapC2fResult)]
+    L.rgbd360_map_align_c2f_cloud.argtypes = [vp, vp, ll, f32p, i32, C.POINTER(MapC2fParams), f32p, C.POINTER(MapC2fResult)]
+    L.rgbd360_map_time_coarsen.argtypes = [vp, i32, i32, vp, vp]
     L.rgbd360_graph_create.argtypes = [vp, C.POINTER(vp)]
     L.rgbd360_graph_destroy.argtypes = [vp]
     L.rgbd360_graph_destroy.restype = None

@@ -323,9 +323,9 @@ int icp_check_params(rgbd360_map* m, const rgbd360_map_align_params* params, rgb
     if (!(p.eps >= 0.f)) return vmap_fail(m, -1, "eps must not be negative");
     return 0;
 }
-// the checked, non-empty input of a call in device memory (vmap_to_device), the grid and the buffers, wide enough for every method
-int icp_prepare(rgbd360_map* m, const MapInput& in, IcpJob& job) {
-    if (const int rc = vmap_to_device(m, in, job.src)) return rc;
+// the grid of a job's source and the buffers, wide enough for every method; icp_prepare: the checked, non-empty input of a call into
+// device memory first (vmap_to_device)
+int icp_buffers(rgbd360_map* m, IcpJob& job) {      // (job.src is set: also the source another map uploaded, map_pyramid.h)
     job.grid = vmap_grid(job.src);
     job.n_rows = (int)(job.grid.x * job.grid.y);
     const size_t state_bytes = sizeof(vmap::LoopState<vmap::kIcpMaxWords>) + (size_t)std::max(job.p.max_iters, 1) * sizeof(rgbd360_map_align_trace);
@@ -333,6 +333,10 @@ int icp_prepare(rgbd360_map* m, const MapInput& in, IcpJob& job) {
     HIPC(m, m->a_state.ensure(state_bytes));
     HIPC(m, m->a_host.ensure(state_bytes));
     return 0;
+}
+int icp_prepare(rgbd360_map* m, const MapInput& in, IcpJob& job) {
+    if (const int rc = vmap_to_device(m, in, job.src)) return rc;
+    return icp_buffers(m, job);
 }
 // the input of an evaluation entry (rgbd360_hip_diag.h): the sphere frame where there is a depth image, otherwise the n points xyz
 MapInput icp_eval_input(const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention, const float* xyz, long long n, int on_device) {
@@ -382,6 +386,8 @@ int icp_enqueue(rgbd360_map* m, const IcpJob& job, const float guess[16], int it
 template <class M>
 const IcpState<M>& icp_host_state(rgbd360_map* m) { return *reinterpret_cast<const IcpState<M>*>(m->a_host.get()); }
 
+template <class M>
+int icp_run(rgbd360_map* m, const IcpJob& job, const float guess[16], float pose_out[16], typename M::Result* res);
 // an align call of method M: rgbd360_map_align_sphere / _cloud and their _plane forms
 template <class M>
 int icp_align(rgbd360_map* m, const MapInput& in, const float guess[16], const typename M::Params* params, float pose_out[16], typename M::Result* res) {
@@ -403,6 +409,11 @@ int icp_align(rgbd360_map* m, const MapInput& in, const float guess[16], const t
         }
         return RGBD360_NO_VALID_PIXELS;
     }
+    return icp_run<M>(m, job, guess, pose_out, res);
+}
+// the loop of a prepared job from `guess`: enqueue, the one synchronisation, the trace, the pose and the result
+template <class M>
+int icp_run(rgbd360_map* m, const IcpJob& job, const float guess[16], float pose_out[16], typename M::Result* res) {
     if (const int rc = icp_enqueue<M>(m, job, guess, job.p.max_iters, typename M::Out{})) return rc;
     HIPC(m, hipStreamSynchronize(m->s->stream));
     const IcpState<M>& st = icp_host_state<M>(m);
@@ -527,6 +538,7 @@ extern "C" int rgbd360_map_time_align(rgbd360_map* m, const void* depth_dev, siz
                                       const float pose[16], const rgbd360_map_align_params* params, int reps, float avg_us[5], double* probes) {
     if (!m) return -1;
     m->err.clear();
+    if (const int rc = vmap_refuse_level(m)) return rc;      // (avg_us[2] inserts the frame)
     const MapInput in = sphere_input(nullptr, 0, depth_dev, depth_step, depth_type, rows, cols, convention, 1);
     if (const int rc = vmap_check_timed(m, in, pose, reps, avg_us)) return rc;
     IcpJob job;

@@ -142,6 +142,7 @@ int vmap_edit_entry(rgbd360_map* m, const MapInput& in, const float* pose_old, c
                     rgbd360_map_stats* inserted) {
     if (!m) return -1;
     m->err.clear();
+    if (const int rc = vmap_refuse_level(m)) return rc;
     const int chk = vmap_check(m, in, pose_old && (!move || pose_new));
     if (chk < 0) return chk;
     vmap_fill_edit_stats(m, nullptr, removed);
@@ -195,6 +196,7 @@ extern "C" int rgbd360_map_move_cloud(rgbd360_map* m, const float* xyz, const ui
 extern "C" int rgbd360_map_rehash(rgbd360_map* m, long long capacity_voxels) {
     if (!m) return -1;
     m->err.clear();
+    if (const int rc = vmap_refuse_level(m)) return rc;
     if (capacity_voxels < 0 || capacity_voxels > (1ll << 30)) return vmap_fail(m, -1, "capacity must be 0 (the current size) or 1 .. 2^30 voxels");
     unsigned long long n_slots = capacity_voxels ? 1 : m->n_slots;
     while (n_slots < (unsigned long long)capacity_voxels) n_slots <<= 1;
@@ -236,6 +238,7 @@ extern "C" int rgbd360_map_time_edit(rgbd360_map* m, const uint8_t* rgb_dev, siz
                                      int rows, int cols, int convention, const float pose[16], int reps, float avg_us[7]) {
     if (!m) return -1;
     m->err.clear();
+    if (const int rc = vmap_refuse_level(m)) return rc;      // (it clears, fills and edits the map)
     const MapInput in = sphere_input(rgb_dev, rgb_step, depth_dev, depth_step, depth_type, rows, cols, convention, 1);
     if (const int rc = vmap_check_timed(m, in, pose, reps, avg_us)) return rc;
     MapSource src;

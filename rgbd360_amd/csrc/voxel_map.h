@@ -61,6 +61,8 @@
 //                   extract kernel (vmap_launch_extract), one read-back of the counter words (vmap_copy_stats / vmap_read_stats), one
 //                   scaffold of the rgbd360_map_time_* entries (VmapTimer).
 #pragma once
+#include <memory>
+
 #include "map_table.h"
 
 struct rgbd360_map {
@@ -115,6 +117,13 @@ struct rgbd360_map {
     DevBuf<unsigned long long> nm_stats;                          // the build's counters and the read-out's record counter ...
     PinnedBuf<unsigned long long> nm_hstats;                      // ... and their pinned copy
     DevBuf<uint8_t> nm_stage;                                     // the host read-out's records on the device: 48 bytes each
+    // the map pyramid (map_pyramid.h).  levels[s - 1]: level s of this map, the map of leaf * 2^s merged out of this table, owned here and
+    // built on demand.  parent != null: this map IS such a level (of shift `shift`), a borrowed handle that every reading entry takes and
+    // every writing entry refuses (vmap_refuse_level); lv_rev: the parent's revision its content is that of (0: never built)
+    rgbd360_map* parent = nullptr;
+    int shift = 0;
+    unsigned long long lv_rev = 0;
+    std::vector<std::unique_ptr<rgbd360_map>> levels;
 };
 
 namespace vmap {
@@ -433,6 +442,10 @@ int vmap_fail(rgbd360_map* m, int code, const char* msg) {
     m->err = msg;
     return code;
 }
+// what every entry that writes a map says to a level of the pyramid (map_pyramid.h), before anything is touched
+int vmap_refuse_level(rgbd360_map* m) {
+    return m->parent ? vmap_fail(m, -1, "a level of a map pyramid is read-only: write its parent") : 0;
+}
 // Two events around work on a stream (the rgbd360_map_time_* entries).  rc: the first failure, of the timer or of a body; once it is set
 // nothing more is recorded or run.  The events go with the timer.
 struct VmapTimer {
@@ -655,6 +668,7 @@ int vmap_finish_insert(rgbd360_map* m, rgbd360_map_stats* stats) {
 int vmap_insert(rgbd360_map* m, const MapInput& in, const float* pose, rgbd360_map_stats* stats) {
     if (!m) return -1;
     m->err.clear();
+    if (const int rc = vmap_refuse_level(m)) return rc;
     const int chk = vmap_check(m, in, pose != nullptr);
     if (chk < 0) return chk;
     vmap_fill_stats(m, nullptr, stats);
@@ -713,7 +727,7 @@ extern "C" int rgbd360_map_create(rgbd360_ctx* ctx_, float leaf, long long capac
     return 0;
 }
 extern "C" void rgbd360_map_destroy(rgbd360_map* m) {
-    if (!m) return;
+    if (!m || m->parent) return;      // (a level goes with its parent)
     hipSetDevice(m->s->p.device);
     hipStreamSynchronize(m->s->stream);
     delete m;
@@ -723,6 +737,7 @@ extern "C" size_t rgbd360_map_bytes(const rgbd360_map* m) { return m ? (size_t)m
 extern "C" int rgbd360_map_set_box(rgbd360_map* m, const float lo[3], const float hi[3]) {
     if (!m) return -1;
     m->err.clear();
+    if (const int rc = vmap_refuse_level(m)) return rc;
     if (!lo != !hi) return vmap_fail(m, -1, "both limits or none");
     m->has_box = lo != nullptr;
     for (int k = 0; k < 3 && lo; ++k) {
@@ -745,6 +760,7 @@ extern "C" long long rgbd360_map_size(rgbd360_map* m) { return m ? m->n_voxels :
 extern "C" int rgbd360_map_clear(rgbd360_map* m) {
     if (!m) return -1;
     m->err.clear();
+    if (const int rc = vmap_refuse_level(m)) return rc;
     hipSetDevice(m->s->p.device);
     if (const int rc = vmap_clear_dev(m)) return rc;
     HIPC(m, hipStreamSynchronize(m->s->stream));
@@ -830,6 +846,7 @@ extern "C" int rgbd360_map_time_kernels(rgbd360_map* m, const uint8_t* rgb_dev, 
                                         long long* global_updates) {
     if (!m) return -1;
     m->err.clear();
+    if (const int rc = vmap_refuse_level(m)) return rc;      // (it clears and fills the map)
     const MapInput in = sphere_input(rgb_dev, rgb_step, depth_dev, depth_step, depth_type, rows, cols, convention, 1);
     if (const int rc = vmap_check_timed(m, in, pose, reps, avg_us)) return rc;
     F360State* ctx = m->s;

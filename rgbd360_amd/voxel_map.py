@@ -16,6 +16,8 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
     gmap.remove_sphere(rgb, depth, currentPose)    # exactly undoes that insert (csrc/map_edit.h); gmap.mismatch tells of a broken contract
     gmap.move_sphere(rgb, depth, currentPose, correctedPose)       # a pose-graph correction: removed at the old pose, inserted at the new
     c = gmap.census(); gmap.rehash() if c["n_tombstones"] > c["n_live"] else None      # compaction; rehash(capacity) grows or shrinks
+    coarse = gmap.level(2)                         # the map at leaf * 4, merged out of the table (csrc/map_pyramid.h): a read-only VoxelMap
+    pose, res = gmap.align_sphere_c2f(depth, guess, convention=0, top_shift=3)     # ICP on levels 3, 2, 1, 0: a basin of 8 leaves
 
 Every point has weight one and the sums are integers: the map does not depend on the order of the frames, and subtracting the same
 integer terms takes a frame out again bit for bit.
@@ -41,6 +43,23 @@ def _as_dict(st, skip=()):
     return {name: getattr(st, name) for name, _ in st._fields_ if name not in skip}
 
 
+def check_shift(shift, lowest: int = 1) -> int:
+    """A level's shift, lowest .. RGBD360_MAP_MAX_SHIFT, or Rgbd360Error."""
+    if isinstance(shift, bool) or int(shift) != shift or not lowest <= int(shift) <= _lib.MAP_MAX_SHIFT:
+        raise Rgbd360Error(f"VoxelMap: a shift must be an integer in {lowest} .. {_lib.MAP_MAX_SHIFT}, not {shift!r}")
+    return int(shift)
+
+
+def check_c2f_params(p):
+    """What rgbd360_map_align_c2f_* refuses of a MapC2fParams on its own fields, refused here with the field's name."""
+    check_shift(p.top_shift, 0)
+    if p.kind not in (0, 1):
+        raise Rgbd360Error("VoxelMap: kind must be 0 / 'point' or 1 / 'plane'")
+    if not 0.0 < p.max_dist_leaves <= 1.0:      # (NaN fails both)
+        raise Rgbd360Error("VoxelMap: max_dist_leaves must lie in (0, 1]")
+    return p
+
+
 class VoxelMap:
     def __init__(self, reg, leaf: float = 0.05, capacity: int = 1 << 20):
         """reg: the RegisterPhotoICP whose context (device, stream) the map lives on; its setters recreate the context, so configure
@@ -54,11 +73,17 @@ class VoxelMap:
             raise Rgbd360Error(f"rgbd360_map_create failed ({rc}): {self._L.rgbd360_last_error(ctx).decode()}")
         self._h = h
         self._ctx_value = ctx.value
+        self._parent = None      # a level of a pyramid (level()): the map it belongs to
+        self._level_gen = 0      # raised when the levels are released: views made before are stale
         self.full = False        # the last insert dropped points of new voxels (RGBD360_MAP_FULL)
         self.mismatch = False    # the last removal was asked for points the map does not hold (RGBD360_MAP_MISMATCH): clear the map
 
     # ---- lifecycle
     def close(self):
+        if self._parent is not None:      # a level goes with its parent
+            self._h = None
+            return
+        self._level_gen += 1
         if self._h is not None:
             if self._reg._h is not None and self._reg._h.value == self._ctx_value:
                 self._L.rgbd360_map_destroy(self._h)
@@ -84,6 +109,8 @@ class VoxelMap:
             raise Rgbd360Error("VoxelMap is closed")
         if self._reg._h is None or self._reg._h.value != self._ctx_value:
             raise Rgbd360Error("VoxelMap: the registration context was closed or recreated (a setter was called) after the map was made")
+        if self._parent is not None and (self._parent._h is None or self._parent._level_gen != self._gen):
+            raise Rgbd360Error("VoxelMap: this level's parent was closed or its levels were released")
         return self._h
 
     def _check(self, rc: int):
@@ -284,6 +311,73 @@ class VoxelMap:
         tr = (_lib.MapAlignTrace * max(n.value, 1))()
         self._check(self._L.rgbd360_map_align_eval(self._handle(), None, 0, 0, 0, 0, 0, None, 0, None, 0, None, None, None, None, None, n.value, None, tr))
         return [(int(t.n), float(t.sum_sq), np.array(t.update, np.float32)) for t in tr[:n.value]]
+
+    # ---- the map pyramid and coarse-to-fine ICP (rgbd360_map_level, rgbd360_map_align_c2f_*; csrc/map_pyramid.h): level s is the map of
+    #      leaf * 2^s merged out of this table by index >> s, exact; the chain aligns on levels top_shift .. 0, each from the pose before
+    def level(self, shift: int) -> "VoxelMap":
+        """Level `shift` (1 .. 6) of this map as a non-owning, read-only VoxelMap: levels 1 .. shift are built or refreshed now and keep
+        that content until the next level() / align_*_c2f call.  Readers work on it (len, extract, census, align_*, render_sphere,
+        raycast*, normals); writers raise.  It is valid until the parent is closed or release_levels() is called."""
+        shift = check_shift(shift)
+        if self._parent is not None:
+            raise Rgbd360Error("VoxelMap.level: a level has no levels of its own")
+        h = C.c_void_p()
+        self._check(self._L.rgbd360_map_level(self._handle(), shift, C.byref(h)))
+        view = VoxelMap.__new__(VoxelMap)
+        view._L, view._reg, view._h, view._ctx_value = self._L, self._reg, h, self._ctx_value
+        view._parent, view._gen, view._level_gen = self, self._level_gen, 0
+        view.full = view.mismatch = False
+        view.shift = shift
+        return view
+
+    @property
+    def pyramid_bytes(self) -> int:
+        """Device memory of the levels' tables (`bytes` stays the table of this map alone)."""
+        return int(self._L.rgbd360_map_pyramid_bytes(self._handle()))
+
+    def release_levels(self):
+        """Frees every level; views handed out by level() become unusable."""
+        self._check(self._L.rgbd360_map_release_levels(self._handle()))
+        self._level_gen += 1
+
+    def c2f_params(self, top_shift=None, kind=None, max_iters=None, eps=None, min_count=None, min_matches=None, max_dist_leaves=None,
+                   min_support=None, max_flatness=None):
+        """The defaults (top_shift 3, kind 0 = point-to-point, max_dist_leaves 1, the single-level defaults for the rest) with the given
+        fields replaced.  kind: 0 / 1 or "point" / "plane"."""
+        kind = {"point": 0, "plane": 1}.get(kind, kind)
+        p = self._params(_lib.MapC2fParams, self._L.rgbd360_map_default_c2f_params, top_shift=top_shift, kind=kind, max_iters=max_iters, eps=eps,
+                         min_count=min_count, min_matches=min_matches, max_dist_leaves=max_dist_leaves, min_support=min_support,
+                         max_flatness=max_flatness)
+        return check_c2f_params(p)
+
+    def _align_c2f(self, entry, params, input_args, guess):
+        g = pose_to_cm(guess)
+        out = np.zeros(16, np.float32)
+        res = _lib.MapC2fResult()
+        self._check(entry(self._handle(), *input_args, _ptr(g), 0, C.byref(params), _ptr(out), C.byref(res)))
+        levels = []
+        for lv in res.levels[:res.n_levels]:
+            d = _as_dict(lv, skip=("pose",))
+            d["pose"] = pose_from_cm(np.array(lv.pose, np.float32))
+            levels.append(d)
+        r = dict(levels[-1], levels=levels, n_levels=int(res.n_levels)) if levels else dict(levels=levels, n_levels=0)
+        r["hessian"] = np.array(res.hessian, np.float32).reshape(6, 6).T.copy()
+        r["gradient"] = np.array(res.gradient, np.float32)
+        return pose_from_cm(out), r
+
+    def align_sphere_c2f(self, depth, guess, convention: int = 0, **params):
+        """Coarse-to-fine ICP of the sphere frame `depth` from `guess`: align_sphere (kind 0) or align_sphere_plane (kind 1) on levels
+        top_shift .. 0, each with max_dist = max_dist_leaves x its leaf and from the pose the level before ended on (a level that does not
+        end OK hands on the pose it was given).  Returns (pose 4x4, result dict: level 0's status, iterations, converged, counters,
+        n_matched, fitness, hessian, gradient, and `levels`, one dict per level from the coarsest down with shift, those fields and the
+        pose it ended on).  Neither the map nor its levels' tables are written."""
+        args, keep = self._sphere_args("align_sphere_c2f", None, depth, convention, colour=False)
+        return self._align_c2f(self._L.rgbd360_map_align_c2f_sphere, self.c2f_params(**params), args, guess)
+
+    def align_cloud_c2f(self, xyz, guess, **params):
+        """The same for a cloud xyz: n x 3 float32 in the frame's coordinates."""
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        return self._align_c2f(self._L.rgbd360_map_align_c2f_cloud, self.c2f_params(**params), (_ptr(x), x.shape[0]), guess)
 
     # ---- the map as a spherical frame (rgbd360_map_render_sphere: the reference's viewer.globalMap, OdometryRGBD360.cpp:242-268, as a
     #      panorama; the keyframe target of OdometryKeyFrame360.cpp with the whole map as the model)
