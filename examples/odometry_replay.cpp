@@ -4,7 +4,7 @@
 //     frame_%03d.rgb  (H*W*3 uint8)   frame_%03d.depth (H*W uint16 mm)
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/odometry_replay.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o odometry_replay
-// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane | --refine-on-map-c2f SHIFT [--plane]] [--render-map PREFIX] [--raycast-map PREFIX] [--map-normals OUT] [--raycast-surface PREFIX] [--map-window N]]
+// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane | --refine-on-map-c2f SHIFT [--plane]] [--render-map PREFIX] [--raycast-map PREFIX] [--map-normals OUT] [--raycast-surface PREFIX] [--map-window N | --carve]]
 //         --sequence: all frames are loaded first and the frame loop runs inside the library (alignSequence)
 //         --multi N:  the same sequence sharded over N GPUs of this node from this one process (rgbd360_multi_*: one host thread
 //                     per device, contiguous shards of pairs, one ncclAllGather of the solved poses over xGMI); prints the
@@ -44,6 +44,10 @@
 //                     line per inserted frame: the frame, the occupied voxels and tombstones after it, the voxels its removal emptied,
 //                     whether the table was rebuilt, and the pose the frame went in at (16 hexadecimal floats, column-major: exact, so
 //                     that a reader can rebuild the window's map bit for bit).  Without the option the output is what it was.
+//         --carve: (needs --map, not with --map-window) after each insert the same frame observes the map (GlobalMap::observe: every pixel
+//                     is a line of sight) and the voxels it looks straight through and does not measure are erased (GlobalMap::carve): what
+//                     an earlier frame left in space that this one sees to be free.  Prints one "carve" line per inserted frame with the
+//                     votes given and the voxels and points erased.  A lossy edit, hence not with the window, whose removals are exact.
 #include <cstdio>
 #include <cstdlib>
 #include <deque>
@@ -188,7 +192,9 @@ int main(int argc, char** argv) {
     bool refine_on_map = false, refine_on_map_plane = false, c2f_plane = false;
     int c2f_shift = -1;
     int map_window = 0;
+    bool carve = false;
     for (int a = 5; a < argc; ++a) {
+        if (std::string(argv[a]) == "--carve") carve = true;
         if (a + 1 < argc && std::string(argv[a]) == "--map") map_file = argv[a + 1];
         if (a + 1 < argc && std::string(argv[a]) == "--leaf") leaf = (float)atof(argv[a + 1]);
         if (a + 1 < argc && std::string(argv[a]) == "--render-map") render_prefix = argv[a + 1];
@@ -217,6 +223,10 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--map-window needs --map and a positive number of frames\n");
         return 2;
     }
+    if (carve && (map_file.empty() || map_window != 0)) {
+        fprintf(stderr, "--carve needs --map and does not go with --map-window\n");
+        return 2;
+    }
     std::unique_ptr<rgbd360::GlobalMap> globalMap;      // declared behind align360: destroyed before its context
     struct Kept {        // a frame of the window: what its removal needs
         std::vector<uint8_t> rgb;
@@ -229,6 +239,14 @@ int main(int argc, char** argv) {
         if (!globalMap->insert(f.sphereRGB, f.sphereDepth, currentPose, /*convention=*/0))
             fprintf(stderr, "map full: %lld points dropped\n", globalMap->stats().n_dropped_full);
         const int k = n_inserted++;
+        if (carve) {      // the frame just inserted protects what it measures (end-votes) and erases what it looks through
+            globalMap->observe(f.sphereDepth, currentPose, /*convention=*/0);
+            const rgbd360_map_observe_stats& o = globalMap->observeStats();
+            globalMap->carve();
+            const rgbd360_map_carve_stats& c = globalMap->carveStats();
+            printf("carve %d rays %lld through %lld end %lld voted %lld carved %lld points %lld protected %lld live %lld\n", k, o.n_valid, o.n_through, o.n_end,
+                   c.n_voted, c.n_voxels_carved, c.n_points_carved, c.n_protected_end, c.n_voxels);
+        }
         if (map_window == 0) return;
         window.push_back({f.rgb, f.depth, currentPose});
         long long emptied = 0;

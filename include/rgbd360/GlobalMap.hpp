@@ -32,6 +32,11 @@
 // so a frame leaves the map exactly as it came,
 //     globalMap.remove(frame.sphereRGB, frame.sphereDepth, pose)            globalMap.move(rgb, depth, oldPose, optimisedPose)
 //     if (c.n_tombstones > c.n_live) globalMap.rehash();      with c = globalMap.census(); rehash(capacity) grows or shrinks the table
+// Free space (rgbd360_map_observe_* / _votes / _carve): what lets the map react to what a new frame sees -- an object that moved away, a
+// ghost wall left by a pose corrected later.  Every pixel of a posed frame is a line of sight; the voxels it passes through well in front
+// of the measured point collect through-votes, the voxel it ends in an end-vote, and carve() erases the voxels seen through and not measured.
+// A lossy edit: a carved voxel forgets its points, and a later remove() of a frame that fed it returns false,
+//     globalMap.observe(frame.sphereDepth, pose);   globalMap.carve();      votes(key3, through, end) reads the counts out instead
 #pragma once
 
 #include <stdexcept>
@@ -310,6 +315,48 @@ class GlobalMap {
     }
     long long onPlane() const { return onPlane_; }      // of the last raycastSurface / raycastSurfaceSphere call
 
+    // Free-space observation and carving (rgbd360_map_observe_* / _votes / _carve; defaults: min_count 1, near = leaf, margin_leaves 2.0,
+    // margin_rel 0, max_offset 0.5 leaves, max_steps 8192, accumulate 0).  observe: every pixel of the sphere frame at `pose`, or every
+    // segment origin -> endpoint of a list (3 floats each, world coordinates), votes on the voxels it looks through; params->accumulate = 1
+    // adds to the votes of the calls before.  The table is not changed.  votes: one record per voted voxel, sorted like points(); count reads
+    // 0 for the voxels a carve erased; returns their number.  carve: erases the live voxels with through >= minThrough, end <= maxEnd and
+    // (maxCount == 0 or count <= maxCount); the votes are spent afterwards.  Stale votes (the map was written since) throw.
+    rgbd360_map_observe_params observeParams() const {
+        rgbd360_map_observe_params p;
+        rgbd360_map_default_observe_params(map_, &p);
+        return p;
+    }
+    void observe(const ImageView& depth, const Mat4f& pose, int convention = 0, const rgbd360_map_observe_params* params = nullptr) {
+        if (depth.type == ImageView::U8C3) throw std::runtime_error("GlobalMap::observe: a 16UC1 / 32FC1 depth image");
+        check(rgbd360_map_observe_sphere(map_, depth.data, depth.step, depthType(depth), depth.rows, depth.cols, convention, pose.m, 0, params, &observe_),
+              "rgbd360_map_observe_sphere");
+    }
+    void observe(const std::vector<float>& origins, const std::vector<float>& endpoints, const rgbd360_map_observe_params* params = nullptr) {
+        if (origins.size() != endpoints.size() || origins.size() % 3 != 0)
+            throw std::runtime_error("GlobalMap::observe: origins and endpoints must hold 3 floats per segment");
+        check(rgbd360_map_observe_rays(map_, (long long)(origins.size() / 3), origins.data(), endpoints.data(), 0, params, &observe_), "rgbd360_map_observe_rays");
+    }
+    const rgbd360_map_observe_stats& observeStats() const { return observe_; }      // of the last observe call
+    long long votes(std::vector<int32_t>& key3, std::vector<int32_t>& through, std::vector<int32_t>& end, std::vector<int32_t>* count = nullptr) {
+        const long long n = rgbd360_map_votes(map_, 0, nullptr, nullptr, nullptr, nullptr);
+        if (n < 0) throw std::runtime_error(std::string("rgbd360_map_votes: ") + rgbd360_map_last_error(map_));
+        key3.assign(3 * (size_t)n, 0);
+        through.assign((size_t)n, 0);
+        end.assign((size_t)n, 0);
+        if (count) count->assign((size_t)n, 0);
+        const long long got = rgbd360_map_votes(map_, n, key3.data(), through.data(), end.data(), count ? count->data() : nullptr);
+        if (got != n) throw std::runtime_error(std::string("rgbd360_map_votes: ") + rgbd360_map_last_error(map_));
+        return n;
+    }
+    // Returns the voxels erased; carveStats() has the counters of the last call.
+    long long carve(int minThrough = 1, int maxEnd = 0, int maxCount = 0) {
+        check(rgbd360_map_carve(map_, minThrough, maxEnd, maxCount, &carve_), "rgbd360_map_carve");
+        return carve_.n_voxels_carved;
+    }
+    const rgbd360_map_carve_stats& carveStats() const { return carve_; }
+    size_t voteBytes() const { return rgbd360_map_vote_bytes(map_); }
+    void releaseVotes() { check(rgbd360_map_release_votes(map_), "rgbd360_map_release_votes"); }
+
     long long size() const { return rgbd360_map_size(map_); }
     size_t bytes() const { return rgbd360_map_bytes(map_); }
     void clear() { check(rgbd360_map_clear(map_), "rgbd360_map_clear"); }
@@ -357,6 +404,8 @@ class GlobalMap {
     rgbd360_map_render_stats render_{};
     rgbd360_map_raycast_stats raycast_{};
     rgbd360_map_normal_stats normal_{};
+    rgbd360_map_observe_stats observe_{};
+    rgbd360_map_carve_stats carve_{};
     long long onPlane_ = 0;
 };
 

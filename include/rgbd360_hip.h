@@ -217,8 +217,8 @@ int  rgbd360_store_align(rgbd360_store* st, int n_pairs, const int* trg, const i
  * stages.)
  * A map is destroyed BEFORE its context and used from one thread at a time, like a store.
  * A map can be edited (rgbd360_map_remove_* / _move_* / _rehash / _census below): what was inserted can be taken out again, exactly.
- * Out of scope: removal by region or age without the source data (the map keeps no per-frame provenance), moving the grid, several
- * GPUs, normals, surfaces. */
+ * Voxels that later measurements look straight through can be erased without the source data (rgbd360_map_observe_* / _carve below).
+ * Out of scope: removal by age, per-frame or per-voxel provenance, moving the grid, several GPUs. */
 typedef struct rgbd360_map rgbd360_map;
 typedef struct { long long n_valid, n_box_rejected, n_out_of_range, n_added, n_dropped_full, n_voxels; } rgbd360_map_stats;
 /* A map of `leaf` metres (>= 0.004) with room for capacity_voxels voxels (rounded up to a power of two, 64 bytes each) on ctx's
@@ -275,7 +275,11 @@ long long rgbd360_map_extract_dev(rgbd360_map* map, long long max_out, float* xy
  * left alone: per voxel n_removed = min(held, asked), whatever the order of points and workgroups.  If either counter is non-zero the call returns RGBD360_MAP_MISMATCH with a message: the counts stay
  * non-negative, but the map's content is then unspecified (sums and counts no longer belong together) and the caller should clear it.
  * n_removed + n_missing + n_underflow = the points that passed steps 1-4; n_voxels_emptied: voxels whose count reached 0 in this call;
- * n_voxels: the map's size after it. */
+ * n_voxels: the map's size after it.
+ * Carving (rgbd360_map_carve below) is a lossy edit outside this contract: a carved voxel forgets its points.  Removing or moving a frame
+ * that fed a carved voxel reports those points in n_underflow and returns RGBD360_MAP_MISMATCH; while the voxel was not revived in between
+ * nothing is subtracted for them and the map stays consistent (n_inconsistent == 0 in the census); once it was revived the content is
+ * unspecified as above. */
 typedef struct { long long n_valid, n_box_rejected, n_out_of_range, n_removed, n_missing, n_underflow, n_voxels_emptied, n_voxels; } rgbd360_map_edit_stats;
 /* Arguments, refusals and empty inputs as for rgbd360_map_insert_sphere / _cloud.  0, RGBD360_MAP_MISMATCH, or negative. */
 int    rgbd360_map_remove_sphere(rgbd360_map* map, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step,
@@ -509,7 +513,8 @@ int    rgbd360_map_render_sphere_dev(rgbd360_map* map, int rows, int cols, const
  * Stated limitations: cells are cubes -- a ray that clips an occupied cell's corner hits it unless max_offset is set; the depth inside a
  * cell is the centroid's projection, a staircase of cells (the depth on the plane fitted around the hit voxel, and its normal:
  * rgbd360_map_raycast_surface below); the layer costs extra device memory per map (12 bytes per brick-table slot, a power of two
- * >= 2 x voxels, and 64 bytes per occupied brick).  Out of scope: carving or any write to the map from a ray cast, shaded output. */
+ * >= 2 x voxels, and 64 bytes per occupied brick).  The same traversal, not ending at a candidate, is the line of sight of
+ * rgbd360_map_observe_* below (free-space votes and carving).  Out of scope: shaded output. */
 enum { RGBD360_RAY_MISS_BOX = 0, RGBD360_RAY_HIT = 1, RGBD360_RAY_LEFT_BOX = 2, RGBD360_RAY_T_MAX = 3, RGBD360_RAY_MAX_STEPS = 4, RGBD360_RAY_BAD = 5 };
 typedef struct {
     int   min_count;           /* points a voxel must hold to stop a ray: 1 */
@@ -613,6 +618,95 @@ int       rgbd360_map_raycast_surface_sphere_dev(rgbd360_map* map, int rows, int
                                                  const rgbd360_map_raycast_params* ray_params, const rgbd360_map_normal_params* normal_params,
                                                  float* depth_dev, float* normal_dev, uint8_t* rgb_dev, int32_t* count_dev, int32_t* key3_dev,
                                                  long long* n_on_plane_dev, rgbd360_map_raycast_stats* stats_dev);
+
+/* ---- free-space observation and carving of the map (csrc/map_carve.h) -----------------------------------------------------------
+ * What lets the map react to what a new frame sees: an object that moved away, a ghost wall left by a pose that was corrected later,
+ * points dropped into space that a later frame looks straight through.  Every measurement of a posed depth frame, or of a list of rays,
+ * is a line of sight.  The map voxels it passes through well in front of the measured point are SEEN THROUGH: rgbd360_map_observe_*
+ * counts that per voxel (the votes: a free-space check), rgbd360_map_votes reads the counts out and rgbd360_map_carve erases the voxels
+ * that thresholds on them condemn.  An observation never writes the table.  All traversal arithmetic is float64 + - x / without
+ * contraction, as for the ray cast above, whose steps these are; there is no square root and no libm call in it.  The votes are a
+ * function of the voxel set and the measurements alone: not of the order of insertion, the table's capacity, slot indices or the run.
+ *   1 segment     from a sphere image: the world point w of steps 1, 3 and 4 of the map's definition (the point of the pixel and
+ *                 convention, the pose, the range check).  The box of step 2 is NOT applied: a point outside the box is not stored, but it
+ *                 still proves free space.  o = the pose's translation.  From a list: origins and endpoints, n x 3 float32 in world
+ *                 coordinates; o the origin, w the endpoint, range-checked as in step 4.  d_k = w_k - o_k, rounded to float32: the
+ *                 measurement lies at t = 1.  A measurement is invalid -- counted in n_skipped, nothing traversed, no vote -- when the
+ *                 point or w is not finite or out of range, o or d is not finite, or d = 0.
+ *   2 walk        steps 2 - 6 of the ray cast with t_max = 1 and max_steps as there, but the walk does not end at a candidate: it ends
+ *                 where a cell's entry lies beyond t = 1, where it leaves the box of the live voxels, or after max_steps cells
+ *                 (n_max_steps).  A segment that misses the box (n_miss_box) visits nothing.  The coarse layer's jump through absent
+ *                 bricks is kept: it changes no vote and no counter but n_lookups.
+ *   3 through     a cell is considered when its voxel is live with count >= min_count.  c, s, t_in, t_out and
+ *                 th = min(max(s, t_in), t_out) are those of step 5 of the ray cast, off2 = ((e_x e_x + e_y e_y) + e_z e_z) (inv_leaf
+ *                 inv_leaf) its squared offset in leaves, dd = (d_x d_x + d_y d_y) + d_z d_z.  The voxel gets one through-vote iff
+ *                   (th th) dd >= near near                       (near in metres; default: leaf, which drops the voxel the camera sits in),
+ *                   q = (1 - th) - margin_rel >= 0 and (q q) dd >= (margin_leaves leaf)^2
+ *                                                                 (it lies at least margin_leaves leaf + margin_rel |d| metres in front of
+ *                                                                 the measured point; defaults 2.0 and 0), and
+ *                   off2 <= max_offset max_offset                 (default 0.5 leaves: a segment that only clips a cell's corner does not vote).
+ *                 near, margin_rel, margin_leaves, leaf and max_offset enter as the doubles of their float32 values.
+ *   4 end         the voxel of step 5 of the map's definition for w -- (int)floorf(w_k * inv_leaf) in float32, the voxel this measurement
+ *                 would feed -- gets one end-vote if it is live (count > 0).  End-votes protect the surfaces the frame also measures: a
+ *                 wall seen at a grazing angle by one ray and frontally by others.
+ *   5 votes       one 64-bit word per table slot in a side array: through-votes in the low 32 bits, end-votes in the high 32 bits; every
+ *                 vote is one 64-bit atomic add, and the add that sees 0 counts the voxel in n_voxels_voted (exact, whatever the order).
+ *                 The array is allocated by the first observation (8 bytes per slot: rgbd360_map_vote_bytes) and freed by
+ *                 rgbd360_map_release_votes, rgbd360_map_rehash and rgbd360_map_destroy.  It belongs to the table as it stood when the
+ *                 votes were taken: once the map is written (insert, remove, move, clear) the votes are stale.
+ *   6 carve       per live voxel with a non-zero vote word (n_voted): erased iff through >= min_through, end <= max_end, and
+ *                 max_count == 0 or count <= max_count.  n_protected_end: through >= min_through but end > max_end; n_protected_count:
+ *                 both hold but count > max_count.  Erasing sets the count and the six sums to 0 and keeps the key: exactly the
+ *                 tombstone a removal leaves.  The map's size falls by n_voxels_carved; the coarse layer, the normals and the pyramid
+ *                 levels follow on their next use.  A carve marks the votes spent.
+ * Statistics of an observation, exact integers: n_rays measurements, n_valid + n_skipped = n_rays, n_miss_box and n_max_steps among
+ * the valid ones, n_steps cells visited, n_lookups voxel-table lookups of the walk (the one number that depends on the form of the
+ * traversal; the end-vote's lookup is not counted), n_through and n_end votes given, n_voxels_voted voxels whose word left 0 in this call.
+ * The contract with exact removal (rgbd360_map_remove_* / _move_* above).  Carving is a LOSSY edit: a carved voxel forgets its points.
+ * A later removal or move of a frame that fed a carved voxel reports those points in n_underflow and returns RGBD360_MAP_MISMATCH; as
+ * long as the voxel was not revived in between nothing is subtracted for them and the map stays consistent (rgbd360_map_census:
+ * n_inconsistent == 0), every other voxel is what the removal contract makes it.  Once a carved voxel was revived by an insert, removing
+ * a frame that fed it before the carve leaves the map unspecified, as any removal outside the contract does.  Per-voxel provenance,
+ * which would lift this, stays out of scope, as do normal-based rejection of grazing rays, occupancy probabilities, carving inside
+ * pyramid levels and several GPUs. */
+typedef struct {
+    int   min_count;           /* points a voxel must hold to be voted on: 1 */
+    float near;                /* voxels nearer than this to the origin, in metres, are not voted on: leaf */
+    float margin_leaves;       /* the free margin in front of the measured point, in leaves ...: 2.0 */
+    float margin_rel;          /* ... plus this share of the measured range: 0 */
+    float max_offset;          /* largest distance of the centroid from the segment, in leaves: 0.5 */
+    int   max_steps;           /* cells a segment may visit, 1 .. 2^23: 8192 */
+    int   accumulate;          /* 0: the votes are zeroed first; 1: the votes are added to */
+} rgbd360_map_observe_params;
+typedef struct {
+    long long n_rays, n_valid, n_skipped, n_miss_box, n_max_steps, n_steps, n_lookups, n_through, n_end, n_voxels_voted;
+} rgbd360_map_observe_stats;
+typedef struct { long long n_voted, n_voxels_carved, n_points_carved, n_protected_end, n_protected_count, n_voxels; } rgbd360_map_carve_stats;
+void   rgbd360_map_default_observe_params(const rgbd360_map* map, rgbd360_map_observe_params* p);
+/* The frame's arguments, refusals and empty inputs as for rgbd360_map_insert_sphere (no colour); stats is host memory and the call waits.
+ * 0; -1, nothing launched and the votes untouched: a bad frame or NULL pose; min_count < 1; near, margin_leaves or margin_rel negative
+ * or not finite; max_offset negative or not a number; max_steps outside 1 .. 2^23; accumulate not 0 or 1; a map that is a pyramid level;
+ * accumulate = 1 when the votes are spent, when the map was written since they were taken, or when the measurements accumulated would
+ * reach 2^31 (accumulate = 1 on a map without votes starts them).  An empty image or an empty map returns 0 with zero statistics,
+ * launches no kernel and leaves the votes as they were.  params NULL: the defaults. */
+int    rgbd360_map_observe_sphere(rgbd360_map* map, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                  const float pose[16], int on_device, const rgbd360_map_observe_params* params, rgbd360_map_observe_stats* stats);
+/* The same for n segments: origins and endpoints are n x 3 float32 (on_device 1: device arrays on the map's device).  Also -1: n < 0 or
+ * >= 2^31, origins or endpoints NULL with n > 0.  n == 0 as an empty image. */
+int    rgbd360_map_observe_rays(rgbd360_map* map, long long n, const float* origins, const float* endpoints, int on_device,
+                                const rgbd360_map_observe_params* params, rgbd360_map_observe_stats* stats);
+/* The votes: one record per voxel with a non-zero vote word into host arrays (any may be NULL), sorted ascending by (i_z, i_y, i_x) like
+ * rgbd360_map_extract: key3 = (i_x, i_y, i_z), the through- and end-votes, and the voxel's count at the time of the call -- 0 for the
+ * voxels a carve erased.  Returns the number of voted voxels and writes min(that, max_out) records; -1 when the map holds no votes or
+ * was written since they were taken by anything other than rgbd360_map_carve. */
+long long rgbd360_map_votes(rgbd360_map* map, long long max_out, int32_t* key3, int32_t* through, int32_t* end, int32_t* count);
+/* Step 6 over the votes as they stand; stats (may be NULL) as above, n_voxels the map's size after the call.  0; -1, the map untouched:
+ * min_through < 1, max_end < 0 or max_count < 0; a pyramid level; no votes; the votes are spent; the map was written since they were
+ * taken. */
+int    rgbd360_map_carve(rgbd360_map* map, int min_through, int max_end, int max_count, rgbd360_map_carve_stats* stats);
+/* bytes of device memory the vote array occupies (0: none), and its release */
+size_t rgbd360_map_vote_bytes(const rgbd360_map* map);
+int    rgbd360_map_release_votes(rgbd360_map* map);
 
 /* ---- the map pyramid and coarse-to-fine ICP against it (csrc/map_pyramid.h) -------------------------------------------------------
  * Both ICPs above match within one leaf, so their capture range is one leaf; the reference's call sites run at 0.3 - 0.4 m.  The coarser

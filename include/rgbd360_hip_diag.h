@@ -183,6 +183,14 @@ int rgbd360_map_raycast_set_plain(rgbd360_map* map, int plain);
 int rgbd360_map_time_raycast(rgbd360_map* map, long long n, const float* origins_dev, const float* dirs_dev, int rows, int cols, const float pose[16],
                              const rgbd360_map_raycast_params* params, int plain, int reps, float* build_us, float* cast_us, float* scan_us,
                              rgbd360_map_raycast_stats* stats, long long* layer_bytes);
+/* An observation (rgbd360_map_observe_sphere, rgbd360_hip.h) under HIP events, one figure per repetition in microseconds (the caller takes
+ * medians): observe_us[r] one k_vmap_observe launch over the device image with the clear of its counters, on zeroed votes (the coarse
+ * layer is built before the first); carve_us[r] (may be NULL) ONE k_vmap_carve launch over the table with thresholds that no voxel meets:
+ * the carve's scan, the table unchanged.  plain: the one-level traversal, for this call only.  stats (may be NULL): those of the last
+ * launch.  The votes of the last repetition stay with the map. */
+int rgbd360_map_time_observe(rgbd360_map* map, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                             const float pose[16], const rgbd360_map_observe_params* params, int plain, int reps, float* observe_us, float* carve_us,
+                             rgbd360_map_observe_stats* stats);
 /* The build of the normal layer (rgbd360_map_normals, rgbd360_hip.h) under HIP events: build_us[r], r < reps, one k_vmap_normals launch over
  * the table with the clear of its counters, in microseconds (the caller takes medians); one untimed build runs first.  scan_us[r] (may
  * be NULL): ONE k_vmap_extract launch (centroids only) over the same table, the cost of merely scanning it.  stats (may be NULL): those

@@ -43,6 +43,8 @@ SYMBOLS = [
     "rgbd360_map_raycast_set_plain", "rgbd360_map_time_raycast",
     "rgbd360_map_default_normal_params", "rgbd360_map_normals", "rgbd360_map_normals_dev", "rgbd360_map_raycast_surface",
     "rgbd360_map_raycast_surface_sphere", "rgbd360_map_raycast_surface_sphere_dev", "rgbd360_map_time_normals",
+    "rgbd360_map_default_observe_params", "rgbd360_map_observe_sphere", "rgbd360_map_observe_rays", "rgbd360_map_votes", "rgbd360_map_carve",
+    "rgbd360_map_vote_bytes", "rgbd360_map_release_votes", "rgbd360_map_time_observe",
     "rgbd360_map_level", "rgbd360_map_pyramid_bytes", "rgbd360_map_release_levels", "rgbd360_map_default_c2f_params",
     "rgbd360_map_align_c2f_sphere", "rgbd360_map_align_c2f_cloud", "rgbd360_map_time_coarsen",
     "rgbd360_graph_create", "rgbd360_graph_destroy", "rgbd360_graph_last_error", "rgbd360_graph_add_vertices", "rgbd360_graph_add_edges",
@@ -165,6 +167,20 @@ class MapNormalParams(C.Structure):     # rgbd360_map_normal_params
 
 class MapNormalStats(C.Structure):      # rgbd360_map_normal_stats
     _fields_ = [(n, C.c_longlong) for n in ("n_voxels", "n_below_min_count", "n_unsupported", "n_nonplanar", "n_normals")]
+
+
+class MapObserveParams(C.Structure):    # rgbd360_map_observe_params
+    _fields_ = [("min_count", C.c_int), ("near", C.c_float), ("margin_leaves", C.c_float), ("margin_rel", C.c_float), ("max_offset", C.c_float),
+                ("max_steps", C.c_int), ("accumulate", C.c_int)]
+
+
+class MapObserveStats(C.Structure):     # rgbd360_map_observe_stats
+    _fields_ = [(n, C.c_longlong) for n in ("n_rays", "n_valid", "n_skipped", "n_miss_box", "n_max_steps", "n_steps", "n_lookups", "n_through", "n_end",
+                                            "n_voxels_voted")]
+
+
+class MapCarveStats(C.Structure):       # rgbd360_map_carve_stats
+    _fields_ = [(n, C.c_longlong) for n in ("n_voted", "n_voxels_carved", "n_points_carved", "n_protected_end", "n_protected_count", "n_voxels")]
 
 
 class GraphParams(C.Structure):         # rgbd360_graph_params
@@ -432,6 +448,18 @@ def load() -> C.CDLL:
     L.rgbd360_map_raycast_surface_sphere_dev.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRaycastParams), C.POINTER(MapNormalParams), vp, vp, vp, vp, vp,
                                                          vp, vp]
     L.rgbd360_map_time_normals.argtypes = [vp, C.POINTER(MapNormalParams), i32, vp, vp, C.POINTER(MapNormalStats), C.POINTER(ll)]
+    L.rgbd360_map_default_observe_params.argtypes = [vp, C.POINTER(MapObserveParams)]
+    L.rgbd360_map_default_observe_params.restype = None
+    L.rgbd360_map_observe_sphere.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, C.POINTER(MapObserveParams), C.POINTER(MapObserveStats)]
+    L.rgbd360_map_observe_rays.argtypes = [vp, ll, vp, vp, i32, C.POINTER(MapObserveParams), C.POINTER(MapObserveStats)]
+    L.rgbd360_map_votes.argtypes = [vp, ll, vp, vp, vp, vp]
+    L.rgbd360_map_votes.restype = ll
+    L.rgbd360_map_carve.argtypes = [vp, i32, i32, i32, C.POINTER(MapCarveStats)]
+    L.rgbd360_map_vote_bytes.argtypes = [vp]
+    L.rgbd360_map_vote_bytes.restype = C.c_size_t
+    L.rgbd360_map_release_votes.argtypes = [vp]
+    L.rgbd360_map_time_observe.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, C.POINTER(MapObserveParams), i32, i32, vp, vp,
+                                           C.POINTER(MapObserveStats)]
     L.rgbd360_map_level.argtypes = [vp, i32, C.POINTER(vp)]
     L.rgbd360_map_pyramid_bytes.argtypes = [vp]
     L.rgbd360_map_pyramid_bytes.restype = C.c_size_t

@@ -217,6 +217,7 @@ extern "C" int rgbd360_map_rehash(rgbd360_map* m, long long capacity_voxels) {
     m->n_slots = n_slots;
     m->may_hold_tombstones = false;
     ++m->revision;
+    vmap_drop_votes(m);      // (they are per slot)
     return 0;
 }
 

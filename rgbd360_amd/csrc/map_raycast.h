@@ -38,7 +38,9 @@
 // bit, except n_lookups (voxel-table lookups: every cell for the plain form, live cells only for the layered one).
 //
 // One lane per ray; a wave runs until its longest ray ends.  cast_ray is host-device and takes the tables through a Grid, so that the
-// same text can be run against a host-side map.
+// same text can be run against a host-side map.  What happens at a candidate is a compile-time policy: FirstHit, the ray cast (the
+// candidate that passes ends the ray), or one that is handed every candidate and lets the walk go on (map_carve.h: the line of sight
+// of a measurement).  The first-hit instantiation is the code it was before the policy (same registers, no scratch: DESIGN.md 3.22).
 #pragma once
 #include <limits>
 
@@ -71,10 +73,18 @@ struct RayResult {
     long long steps, lookups;
 };
 
+// What a traversal does with a candidate (a live cell of count >= min_count, step 5).  FirstHit: the ray cast -- the candidate that passes
+// t_min and max_offset ends the ray.  A policy with kStops = false (map_carve.h: the through-votes of a line of sight) is handed every
+// candidate -- its slot, t_hit, |d|^2 and the squared offset in leaves -- and the walk goes on to t_max, the box or max_steps.
+struct FirstHit {
+    static constexpr bool kStops = true;
+    __host__ __device__ void cell(const unsigned long long*, double, double, double) {}
+};
+
 // Steps 1-7 for one ray.  Grid: voxel(key) -> the slot's eight words or null; brick(brick key) -> the brick's eight mask words or null.
 // (No array is indexed by a run-time axis: the selects keep i, T in registers.)
-template <bool LAYER, class Grid>
-__host__ __device__ inline void cast_ray(const Grid& G, const RayParams& P, const float o[3], const float d[3], RayResult& H) {
+template <bool LAYER, class Grid, class Policy>
+__host__ __device__ inline void cast_ray(const Grid& G, const RayParams& P, const float o[3], const float d[3], RayResult& H, Policy& policy) {
 #pragma clang fp contract(off)
     const double kInf = __builtin_inf();
     H.status = kRayBad;
@@ -217,7 +227,10 @@ __host__ __device__ inline void cast_ray(const Grid& G, const RayParams& P, cons
                 const double s = ((e0 * (double)d[0] + e1 * (double)d[1]) + e2 * (double)d[2]) / dd;
                 double th = s > t_in ? s : t_in;
                 th = th < t_out ? th : t_out;
-                if (th >= P.t_min) {
+                if (!Policy::kStops) {
+                    const double f0 = e0 - s * (double)d[0], f1 = e1 - s * (double)d[1], f2 = e2 - s * (double)d[2];
+                    policy.cell(rec, th, dd, ((f0 * f0 + f1 * f1) + f2 * f2) * (inv * inv));
+                } else if (th >= P.t_min) {
                     const double f0 = e0 - s * (double)d[0], f1 = e1 - s * (double)d[1], f2 = e2 - s * (double)d[2];
                     const double off2 = ((f0 * f0 + f1 * f1) + f2 * f2) * (inv * inv);
                     if (!(off2 > P.off2_max)) {
@@ -249,6 +262,11 @@ __host__ __device__ inline void cast_ray(const Grid& G, const RayParams& P, cons
     H.status = status;
     H.steps = steps;
     H.lookups = lookups;
+}
+template <bool LAYER, class Grid>
+__host__ __device__ inline void cast_ray(const Grid& G, const RayParams& P, const float o[3], const float d[3], RayResult& H) {
+    FirstHit first_hit;
+    cast_ray<LAYER>(G, P, o, d, H, first_hit);
 }
 
 #if !defined(RGBD360_RAYCAST_CORE_ONLY)

@@ -117,6 +117,15 @@ struct rgbd360_map {
     DevBuf<unsigned long long> nm_stats;                          // the build's counters and the read-out's record counter ...
     PinnedBuf<unsigned long long> nm_hstats;                      // ... and their pinned copy
     DevBuf<uint8_t> nm_stage;                                     // the host read-out's records on the device: 48 bytes each
+    // free-space observation and carving (map_carve.h): one vote word per slot (through-votes low, end-votes high), taken on the table of
+    // revision vt_rev; vt_rays_n: the measurements accumulated in it, vt_voted: the slots with a non-zero word; vt_spent: a carve has used it
+    DevBuf<unsigned long long> vt_votes, vt_stats;
+    PinnedBuf<unsigned long long> vt_hstats;
+    DevBuf<int32_t> vt_out;                                       // the read-out's records on the device: six words each
+    DevBuf<float> vt_rays;                                        // a host list's origins and endpoints
+    unsigned long long vt_rev = 0;
+    long long vt_rays_n = 0, vt_voted = 0;
+    bool vt_have = false, vt_spent = false;
     // the map pyramid (map_pyramid.h).  levels[s - 1]: level s of this map, the map of leaf * 2^s merged out of this table, owned here and
     // built on demand.  parent != null: this map IS such a level (of shift `shift`), a borrowed handle that every reading entry takes and
     // every writing entry refuses (vmap_refuse_level); lv_rev: the parent's revision its content is that of (0: never built)
@@ -154,6 +163,14 @@ struct Source {                  // SRC 0: a sphere image; SRC 1: a cloud of n p
     long long n;
 };
 
+// step 5: the key of the voxel that the posed point w (step 4 passed: |w_k| < 4096) feeds
+__device__ __forceinline__ unsigned long long point_key(const float w[3], float inv_leaf) {
+#pragma clang fp contract(off)
+    unsigned long long i[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) i[k] = (unsigned long long)((int)floorf(w[k] * inv_leaf) + kBias);
+    return pack_key(i[0], i[1], i[2]);
+}
 // steps 1-6 of one point: 0 skipped, 1 outside the box, 2 out of range, 3 kept (key, the three fixed-point terms and the posed point w)
 __device__ __forceinline__ int classify(const Params& P, float x, float y, float z, unsigned long long& key, long long f[3], float w[3]) {
 #pragma clang fp contract(off)
@@ -162,13 +179,9 @@ __device__ __forceinline__ int classify(const Params& P, float x, float y, float
 #pragma unroll
     for (int k = 0; k < 3; ++k) w[k] = ((P.pose[k] * x + P.pose[k + 4] * y) + P.pose[k + 8] * z) + P.pose[k + 12];
     if (!(fabsf(w[0]) < 4096.f && fabsf(w[1]) < 4096.f && fabsf(w[2]) < 4096.f)) return 2;
-    unsigned long long i[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        i[k] = (unsigned long long)((int)floorf(w[k] * P.inv_leaf) + kBias);
-        f[k] = llrint((double)w[k] * kFix);
-    }
-    key = pack_key(i[0], i[1], i[2]);
+    for (int k = 0; k < 3; ++k) f[k] = llrint((double)w[k] * kFix);
+    key = point_key(w, P.inv_leaf);
     return 3;
 }
 __device__ __forceinline__ int classify(const Params& P, float x, float y, float z, unsigned long long& key, long long f[3]) {
@@ -176,21 +189,21 @@ __device__ __forceinline__ int classify(const Params& P, float x, float y, float
     return classify(P, x, y, z, key, f, w);
 }
 
-// The source load of a thread: its kPerThread points, kThreads apart in the workgroup's tile, all loads first.  in[k]: slot k holds a point
-// of the source; index[k]: its place in the per-point arrays (a place inside the source where !in[k]: every load is in bounds).
-template <int SRC>
-__device__ __forceinline__ void load_points(const Source& src, float x[kPerThread], float y[kPerThread], float z[kPerThread], bool in[kPerThread],
-                                            long long index[kPerThread]) {
+// The source load of a thread: its N points (kPerThread unless stated; map_carve.h takes one), kThreads apart in the workgroup's tile of
+// kThreads N points, all loads first.  in[k]: slot k holds a point of the source; index[k]: its place in the per-point arrays (a place
+// inside the source where !in[k]: every load is in bounds).
+template <int SRC, int N = kPerThread>
+__device__ __forceinline__ void load_points(const Source& src, float x[N], float y[N], float z[N], bool in[N], long long index[N]) {
 #pragma clang fp contract(off)
     const int t = threadIdx.x;
     if (SRC == 0) {
         const int r = blockIdx.y;
         const uint8_t* drow = (const uint8_t*)src.depth + (size_t)r * src.depth_step;
         const float sp = src.sin_phi[r], cp = src.cos_phi[r];
-        float d[kPerThread], st[kPerThread], ct[kPerThread];
+        float d[N], st[N], ct[N];
 #pragma unroll
-        for (int k = 0; k < kPerThread; ++k) {
-            const int col = blockIdx.x * kTile + t + kThreads * k;
+        for (int k = 0; k < N; ++k) {
+            const int col = blockIdx.x * (kThreads * N) + t + kThreads * k;
             in[k] = col < src.cols;
             const int cc = in[k] ? col : src.cols - 1;
             index[k] = (long long)r * src.cols + cc;
@@ -199,11 +212,11 @@ __device__ __forceinline__ void load_points(const Source& src, float x[kPerThrea
             ct[k] = src.cos_theta[cc];
         }
 #pragma unroll
-        for (int k = 0; k < kPerThread; ++k) r360::sphere_point(src.convention, d[k], sp, cp, st[k], ct[k], x[k], y[k], z[k]);
+        for (int k = 0; k < N; ++k) r360::sphere_point(src.convention, d[k], sp, cp, st[k], ct[k], x[k], y[k], z[k]);
     } else {
 #pragma unroll
-        for (int k = 0; k < kPerThread; ++k) {
-            const long long i = (long long)blockIdx.x * kTile + t + kThreads * k;
+        for (int k = 0; k < N; ++k) {
+            const long long i = (long long)blockIdx.x * (kThreads * N) + t + kThreads * k;
             in[k] = i < src.n;
             const size_t ii = in[k] ? (size_t)i : 0;
             index[k] = (long long)ii;
@@ -445,6 +458,13 @@ int vmap_fail(rgbd360_map* m, int code, const char* msg) {
 // what every entry that writes a map says to a level of the pyramid (map_pyramid.h), before anything is touched
 int vmap_refuse_level(rgbd360_map* m) {
     return m->parent ? vmap_fail(m, -1, "a level of a map pyramid is read-only: write its parent") : 0;
+}
+// the vote array (map_carve.h) goes: rgbd360_map_release_votes, and rgbd360_map_rehash, which moves every voxel to another slot
+void vmap_drop_votes(rgbd360_map* m) {
+    hipSetDevice(m->s->p.device);
+    m->vt_votes.release();
+    m->vt_have = m->vt_spent = false;
+    m->vt_rays_n = m->vt_voted = 0;
 }
 // Two events around work on a stream (the rgbd360_map_time_* entries).  rc: the first failure, of the timer or of a body; once it is set
 // nothing more is recorded or run.  The events go with the timer.

@@ -12,6 +12,7 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
     t, key3, count, rgb, status, stats = gmap.raycast(origins, dirs)           # the first voxel along each ray of a list
     xyz, normal, curvature, status, count, key3, stats = gmap.normals(viewpoint)   # one normal per voxel (csrc/map_normals.h) ...
     depth, normal, rgb, count, key3, n_on_plane, stats = gmap.raycast_surface_sphere(rows, cols, pose)     # ... and the surface a ray meets
+    gmap.observe_sphere(depth, currentPose); gmap.carve()      # the voxels the frame looks straight through leave (csrc/map_carve.h)
     xyz, rgb, count, key = gmap.extract()          # sorted by (i_z, i_y, i_x)
     gmap.remove_sphere(rgb, depth, currentPose)    # exactly undoes that insert (csrc/map_edit.h); gmap.mismatch tells of a broken contract
     gmap.move_sphere(rgb, depth, currentPose, correctedPose)       # a pose-graph correction: removed at the old pose, inserted at the new
@@ -518,6 +519,65 @@ class VoxelMap:
     def raycast_set_plain(self, plain: bool):
         """Diagnostics: the one-level traversal instead of the coarse layer for the later ray casts; the outputs are the same bits."""
         self._check(self._L.rgbd360_map_raycast_set_plain(self._handle(), int(bool(plain))))
+
+    # ---- free-space observation and carving (rgbd360_map_observe_* / _votes / _carve: the voxels a posed frame looks straight through,
+    #      counted per voxel and erased on request; csrc/map_carve.h)
+    def observe_params(self, min_count=None, near=None, margin_leaves=None, margin_rel=None, max_offset=None, max_steps=None, accumulate=None):
+        """The defaults (min_count 1, near = leaf, margin_leaves 2.0, margin_rel 0, max_offset 0.5 leaves, max_steps 8192, accumulate 0) with
+        the given fields replaced."""
+        accumulate = None if accumulate is None else int(accumulate)
+        return self._params(_lib.MapObserveParams, self._L.rgbd360_map_default_observe_params, min_count=min_count, near=near,
+                            margin_leaves=margin_leaves, margin_rel=margin_rel, max_offset=max_offset, max_steps=max_steps, accumulate=accumulate)
+
+    def observe_sphere(self, depth, pose, convention: int = 0, **params):
+        """Every pixel of the sphere frame `depth` (as in insert_sphere) at `pose` is a line of sight: the map voxels it passes through
+        well in front of the measured point get a through-vote, the voxel the point would feed an end-vote.  accumulate=True adds to the
+        votes of earlier observations.  Returns the statistics as a dict.  The map's table is not changed."""
+        args, keep = self._sphere_args("observe_sphere", None, depth, convention, colour=False)
+        p = self.observe_params(**params)
+        g = pose_to_cm(pose)
+        st = _lib.MapObserveStats()
+        self._check(self._L.rgbd360_map_observe_sphere(self._handle(), *args, _ptr(g), 0, C.byref(p), C.byref(st)))
+        return _as_dict(st)
+
+    def observe_rays(self, origins, endpoints, **params):
+        """The same for n segments (origins, endpoints: n x 3 float32, world coordinates; the measurement is the endpoint)."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        w = np.ascontiguousarray(endpoints, np.float32).reshape(-1, 3)
+        if o.shape != w.shape:
+            raise Rgbd360Error("VoxelMap.observe_rays: origins and endpoints must have the same shape")
+        p = self.observe_params(**params)
+        st = _lib.MapObserveStats()
+        self._check(self._L.rgbd360_map_observe_rays(self._handle(), o.shape[0], _ptr(o), _ptr(w), 0, C.byref(p), C.byref(st)))
+        return _as_dict(st)
+
+    def votes(self, max_out=None):
+        """(key3 [k, 3] int32, through [k] int32, end [k] int32, count [k] int32) of the voxels with a vote, ascending by (i_z, i_y, i_x);
+        count is the voxel's count now, 0 once a carve erased it.  Raises when the map holds no votes or was written since they were taken."""
+        n = self._L.rgbd360_map_votes(self._handle(), 0, None, None, None, None)
+        if n < 0:
+            raise Rgbd360Error(f"rgbd360_map_votes failed ({n}): {self._L.rgbd360_map_last_error(self._h).decode()}")
+        k = n if max_out is None else min(n, int(max_out))
+        key3 = np.zeros((k, 3), np.int32)
+        through, end, count = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        got = self._L.rgbd360_map_votes(self._handle(), k, _ptr(key3), _ptr(through), _ptr(end), _ptr(count))
+        if got != n:
+            raise Rgbd360Error(f"rgbd360_map_votes failed ({got}): {self._L.rgbd360_map_last_error(self._h).decode()}")
+        return key3, through, end, count
+
+    def carve(self, min_through: int = 1, max_end: int = 0, max_count: int = 0):
+        """Erases the live voxels with through >= min_through, end <= max_end and (max_count == 0 or count <= max_count); the votes are
+        spent afterwards.  A lossy edit: a later remove of a frame that fed a carved voxel reports a mismatch.  Returns the statistics."""
+        st = _lib.MapCarveStats()
+        self._check(self._L.rgbd360_map_carve(self._handle(), int(min_through), int(max_end), int(max_count), C.byref(st)))
+        return _as_dict(st)
+
+    def vote_bytes(self) -> int:
+        """Device memory of the vote array (8 bytes per slot once an observation was made; 0 after release_votes or rehash)."""
+        return int(self._L.rgbd360_map_vote_bytes(self._handle()))
+
+    def release_votes(self):
+        self._check(self._L.rgbd360_map_release_votes(self._handle()))
 
     # ---- read-out
     def __len__(self) -> int:
