@@ -15,7 +15,10 @@
 //     globalMap.alignSphere(frame.sphereDepth, guess, pose)     point-to-point, nearest voxel centroid within max_dist <= leaf
 //     globalMap.alignSpherePlane(frame.sphereDepth, guess, pose)   point-to-plane: the same match, the plane fitted to the centroids around it
 //                                                                  (the call sites use pcl::GeneralizedIterativeClosestPoint, a plane cost)
-// Both match within one voxel; a guess further off goes through the map pyramid (rgbd360_map_level, rgbd360_map_align_c2f_*: the maps of
+//     globalMap.alignCloudGICP(xyz, normals, n, guess, pose)      generalized ICP (rgbd360_map_align_gicp_*): the same match weighted by the
+//     globalMap.alignMapGICP(otherMap, guess, pose)               inverse of both sides' covariances -- the map's per-voxel normals and
+//     globalMap.alignSphereGICP(frame.sphereDepth, guess, pose)   the source's normals, which may be another map's: "filterVoxel both, then GICP"
+// All match within one voxel; a guess further off goes through the map pyramid (rgbd360_map_level, rgbd360_map_align_c2f_*: the maps of
 // 2, 4, 8 .. times the voxel size are merged out of the table, exactly, and the ICP runs from the coarsest down),
 //     globalMap.alignSphereCoarseToFine(frame.sphereDepth, guess, pose)     c2fResult().levels[k]: what each level did
 // The map as a spherical RGB-D frame (rgbd360_map_render_*: the reference shows viewer.globalMap in a PCL window, OdometryRGBD360.cpp:242-268,
@@ -39,6 +42,7 @@
 //     globalMap.observe(frame.sphereDepth, pose);   globalMap.carve();      votes(key3, through, end) reads the counts out instead
 #pragma once
 
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -168,6 +172,50 @@ class GlobalMap {
         return rc;
     }
     const rgbd360_map_align_plane_result& alignPlaneResult() const { return alignPlane_; }      // of the last alignSpherePlane / alignCloudPlane call
+
+    // Generalized ICP against the map (rgbd360_map_align_gicp_*): the matches of alignSphere / alignCloud, each weighted by
+    // (C_B + C_A)^-1 -- C_B from the matched voxel's resident normal, C_A from the source point's normal (`normals`: 3 n floats in the
+    // frame's coordinates, or nullptr).  A pair without a planar side counts as point-to-point.  alignGicpResult() has the counts.
+    rgbd360_map_align_gicp_params alignGicpParams() const {
+        rgbd360_map_align_gicp_params p;
+        rgbd360_map_default_align_gicp_params(map_, &p);
+        return p;
+    }
+    int alignCloudGICP(const float* xyz, const float* normals, long long n, const Mat4f& guess, Mat4f& pose, const rgbd360_map_align_gicp_params* params = nullptr) {
+        const int rc = rgbd360_map_align_gicp_cloud(map_, xyz, normals, n, guess.m, 0, params, pose.m, &alignGicp_);
+        check(rc, "rgbd360_map_align_gicp_cloud");
+        return rc;
+    }
+    int alignSphereGICP(const ImageView& depth, const Mat4f& guess, Mat4f& pose, int convention = 0, const rgbd360_map_align_gicp_params* params = nullptr) {
+        if (depth.type == ImageView::U8C3) throw std::runtime_error("GlobalMap::alignSphereGICP: a 16UC1 / 32FC1 depth image");
+        const int rc = rgbd360_map_align_gicp_sphere(map_, depth.data, depth.step, depthType(depth), depth.rows, depth.cols, convention, guess.m, 0,
+                                                     params, pose.m, &alignGicp_);
+        check(rc, "rgbd360_map_align_gicp_sphere");
+        return rc;
+    }
+    // Another map as the source (guess, pose: this map's world <- the source's world): the source's voxels with their normals, fitted under
+    // this call's min_count / min_support / max_flatness, in ascending (i_z, i_y, i_x) order so that the sums are the same from run to run.
+    int alignMapGICP(GlobalMap& source, const Mat4f& guess, Mat4f& pose, const rgbd360_map_align_gicp_params* params = nullptr) {
+        const rgbd360_map_align_gicp_params p = params ? *params : alignGicpParams();
+        rgbd360_map_normal_params np;
+        rgbd360_map_default_normal_params(source.map_, &np);
+        np.min_count = p.min_count, np.min_support = p.min_support, np.max_flatness = p.max_flatness;
+        std::vector<float> xyz, normal;
+        std::vector<int32_t> key3;
+        const size_t n = (size_t)source.normals(xyz, normal, nullptr, nullptr, nullptr, &key3, nullptr, &np);
+        std::vector<size_t> order(n);
+        for (size_t k = 0; k < n; ++k) order[k] = k;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+            for (int q = 2; q >= 0; --q)
+                if (key3[3 * a + q] != key3[3 * b + q]) return key3[3 * a + q] < key3[3 * b + q];
+            return false;
+        });
+        std::vector<float> sx(3 * n), sn(3 * n);
+        for (size_t o = 0; o < n; ++o)
+            for (int q = 0; q < 3; ++q) sx[3 * o + q] = xyz[3 * order[o] + q], sn[3 * o + q] = normal[3 * order[o] + q];
+        return alignCloudGICP(sx.data(), sn.data(), (long long)n, guess, pose, &p);
+    }
+    const rgbd360_map_align_gicp_result& alignGicpResult() const { return alignGicp_; }      // of the last align*GICP call
 
     // Coarse-to-fine ICP (rgbd360_map_align_c2f_*): alignSphere / alignCloud (kind 0) or their Plane forms (kind 1) on the levels
     // top_shift .. 0 of the map pyramid, level s being the map at voxelSize * 2^s merged out of the table; each level starts from the pose the
@@ -400,6 +448,7 @@ class GlobalMap {
     rgbd360_map_edit_stats edit_{};
     rgbd360_map_align_result align_{};
     rgbd360_map_align_plane_result alignPlane_{};
+    rgbd360_map_align_gicp_result alignGicp_{};
     rgbd360_map_c2f_result c2f_{};
     rgbd360_map_render_stats render_{};
     rgbd360_map_raycast_stats raycast_{};

@@ -341,9 +341,9 @@ int    rgbd360_map_census(rgbd360_map* map, rgbd360_map_census_counts* out);
  * align against a coarser map first.
  * Differences from the reference, stated: its active choice is pcl::GeneralizedIterativeClosestPoint at 0.3 - 0.4 m over a kd-tree of
  * the other cloud; this is the point-to-point form on the grid, against centroids.  PCL is not part of the reference tree: parity
- * with PCL is unpinned.  The point-to-plane form of the same alignment follows below (rgbd360_map_align_plane_*).  Out of scope: GICP's
- * per-point covariance weighting, radii above one leaf, several GPUs.  (A coarse-to-fine chain over coarser maps derived from this one:
- * rgbd360_map_align_c2f_* below.) */
+ * with PCL is unpinned.  The point-to-plane form of the same alignment follows below (rgbd360_map_align_plane_*), GICP's cost with its
+ * per-match covariance weighting further down (rgbd360_map_align_gicp_*).  Out of scope: radii above one leaf, several GPUs.  (A
+ * coarse-to-fine chain over coarser maps derived from this one: rgbd360_map_align_c2f_* below.) */
 typedef struct {
     float max_dist;            /* setMaxCorrespondenceDistance, in (0, leaf]; default: leaf */
     int   max_iters;           /* setMaximumIterations: 10 (OdometryRGBD360.cpp:102) */
@@ -400,8 +400,9 @@ int    rgbd360_map_align_cloud(rgbd360_map* map, const float* xyz, long long n, 
  *     RGBD360_ILL_POSED on rank(H) < 6 (a single wall is ill-posed: the correct answer), RGBD360_NO_VALID_PIXELS when fewer than
  *     min_matches points contribute, converged on v.v <= eps and omega.omega <= eps, one stream synchronisation per alignment.
  *     fitness = sum r r / n, fitness_point = sum e_match . e_match / n, n_matched = n (the contributing points).
- * Differences from GICP, stated: planes on the target side only (the source point is a point), no per-point covariance weighting (every
- * contributing point has weight one), and PCL is not part of the reference tree: parity with PCL is unpinned. */
+ * Differences from GICP, stated: planes on the target side only (the source point is a point) and every contributing point has weight
+ * one -- the weighted plane-to-plane cost is rgbd360_map_align_gicp_* below; PCL is not part of the reference tree: parity with PCL is
+ * unpinned. */
 typedef struct {
     float max_dist;            /* as in rgbd360_map_align_params */
     int   max_iters;
@@ -618,6 +619,80 @@ int       rgbd360_map_raycast_surface_sphere_dev(rgbd360_map* map, int rows, int
                                                  const rgbd360_map_raycast_params* ray_params, const rgbd360_map_normal_params* normal_params,
                                                  float* depth_dev, float* normal_dev, uint8_t* rgb_dev, int32_t* count_dev, int32_t* key3_dev,
                                                  long long* n_on_plane_dev, rgbd360_map_raycast_stats* stats_dev);
+
+/* ---- generalized ICP against the map (csrc/map_align_gicp.h) ---------------------------------------------------------------------
+ * The cost the reference's cloud ICP call sites actually minimise: pcl::GeneralizedIterativeClosestPoint on two voxel-filtered clouds
+ * (OdometryRGBD360.cpp:98-114 and 210-222, RegisterPairRGBD360.cpp:111-118, MethodsRegisterRGBD360.cpp:294-320,
+ * OdometryKeyFrame360.cpp:124-140) -- Segal, Haehnel and Thrun's plane-to-plane ICP.  Every match has a 3 x 3 weight built from a
+ * covariance on either side; here the target's covariance comes from the map's resident per-voxel normal (the section above) and the
+ * source's from a normal per source point, which may be those of another voxel map: "filterVoxel both, then GICP", and also the
+ * alignment of one submap against another.  Planar pairs constrain along their normals; a pair without a planar side degrades to
+ * point-to-point instead of dropping out, which is what rgbd360_map_align_plane_* does with corners and edges.
+ * Everything below is float64 with + - x / sqrt only, every operation rounded on its own (no fused multiply-add): host, device and a
+ * restatement in IEEE arithmetic agree bit for bit per point.  Per source point at the current pose T = [R | t]:
+ *   1 match: steps 1-4 of the point-to-point definition, bit for bit -- the map's steps 1-5, the 27 cells in the same order,
+ *     count >= min_count, the read-out's centroid, d2 in float32, a tie to the earlier cell, kept iff d2 <= max_dist^2, max_dist in
+ *     (0, leaf].  The key and d2 of a point are those of rgbd360_map_align_*.  e = the float32 w - c of the match, widened to double.
+ *   2 target covariance: if use_target_normals != 0 and the matched voxel is RGBD360_NORMAL_OK in the normal layer of
+ *     (min_count, min_support, max_flatness) -- this call's min_count; the layer is built or reused exactly as by the surface cast --
+ *     nb = the doubles of its float32 normal as stored and C_B[j][k] = delta_jk - s (nb_j nb_k), s = 1.0 - (double)epsilon (the
+ *     off-diagonal terms as 0.0 - s (nb_j nb_k)).  Otherwise C_B = I.
+ *   3 source covariance: a source normal is present for point i iff a normal array was passed, its three floats are finite and
+ *     q = (n_x n_x + n_y n_y) + n_z n_z > 0 (in double).  Then n^ = n / sqrt(q), na_k = (R_k0 n^_x + R_k1 n^_y) + R_k2 n^_z with R the
+ *     doubles of the float32 pose, and C_A[j][k] = delta_jk - s (na_j na_k).  Otherwise C_A = 0: the source point is a point.
+ *     These are the special cases of Segal et al.: no normal on either side is point-to-point (M = I exactly), target normals only is
+ *     point-to-plane with weight 1 / epsilon along the normal and 1 across it, normals on both sides is plane-to-plane.
+ *   4 weight: A = C_B + C_A per element, symmetric;  c00 = A11 A22 - A12 A12, c01 = A02 A12 - A01 A22, c02 = A01 A12 - A02 A11,
+ *     c11 = A00 A22 - A02 A02, c12 = A01 A02 - A00 A12, c22 = A00 A11 - A01 A01, det = (A00 c00 + A01 c01) + A02 c02, M_jk = c_jk / det.
+ *     A is positive definite for epsilon in (0, 1] (its eigenvalues are at least epsilon): there is no failure branch.
+ *   5 terms: J = [I | -[w]x], the point method's Jacobian, for the increment pose <- pseudo_exp(v, omega) pose.  Its columns are
+ *     u_0..2, the unit vectors, and u_3 = (0, -w_z, w_y), u_4 = (w_z, 0, -w_x), u_5 = (-w_y, w_x, 0) (u_3+k = e_k x w).  m_b = M u_b,
+ *     q = M e, each a sum of products left to right, (a + b) + c; a component of u that is 0 contributes no term and one that is 1 no
+ *     product.  H_ab = u_a . m_b for a <= b, g_a = u_a . q, cost = (e_x q_x + e_y q_y) + e_z q_z, ee = (e_x e_x + e_y e_y) + e_z e_z.
+ *   6 row: n, the 21 H terms row by row, the 6 g terms, sum cost, sum ee, then the counters n_valid, n_box_rejected, n_out_of_range,
+ *     n_target_planes (kept matches with a target normal), n_source_planes (kept matches with a source normal), n_plane_pairs (both),
+ *     probes and points searched: 38 doubles.  One partial row per workgroup, the rows added in ascending order; no floating-point
+ *     atomics: the same sums from run to run.
+ *   7 loop: steps 6-7 of the point method unchanged -- H and g cast to float32, gn::step with lambda 0, RGBD360_ILL_POSED on
+ *     rank(H) < 6, RGBD360_NO_VALID_PIXELS below min_matches, converged on v.v <= eps and omega.omega <= eps, at most max_iters steps,
+ *     the final evaluation, one stream synchronisation.  fitness = sum cost / n, fitness_point = sum ee / n.
+ * The table and the map are never written; the normal layer is the map's own (16 bytes per slot, see above).
+ * Differences from PCL's GICP, stated: PCL minimises with BFGS and keeps the weights of a set of correspondences fixed while it does;
+ * here it is Gauss-Newton with M re-formed from the current rotation at every evaluation (M's dependence on the pose is not
+ * differentiated).  PCL's covariances come from the 20 nearest neighbours of every point of either cloud; here from the normal of the
+ * matched voxel (fitted to the centroids of its 27 cells) and from the normals the caller passes.  The match is the nearest centroid
+ * within one leaf, not a kd-tree search within 0.3 - 0.4 m.  PCL is not part of the reference tree: parity with PCL is unpinned.
+ * rgbd360_map_align_c2f_* does not take this method. */
+typedef struct {
+    float max_dist;            /* as in rgbd360_map_align_params */
+    int   max_iters;
+    float eps;
+    int   min_count;           /* also the normal layer's */
+    long long min_matches;     /* kept matches an evaluation must have: 6 */
+    float epsilon;             /* the covariance of a plane along its normal, in (0, 1]: 1e-3 (PCL's gicp_epsilon); 1 makes every side isotropic */
+    int   use_target_normals;  /* 0: C_B = I for every match; default 1 */
+    int   min_support;         /* of the normal layer, 1 .. 27: 5 */
+    float max_flatness;        /* of the normal layer, >= 0: 0.05 */
+} rgbd360_map_align_gicp_params;
+typedef struct {
+    int status, iterations, converged;
+    long long n_valid, n_box_rejected, n_out_of_range, n_matched;      /* of the final evaluation; n_matched: the kept matches */
+    double fitness;            /* sum e^T M e / n_matched (0 when nothing matched) */
+    float hessian[36], gradient[6];
+    long long n_target_planes, n_source_planes, n_plane_pairs;   /* kept matches with a target normal / a source normal / both */
+    double fitness_point;      /* sum e.e / n_matched over the same matches: rgbd360_map_align_result.fitness's scale */
+} rgbd360_map_align_gicp_result;
+void   rgbd360_map_default_align_gicp_params(const rgbd360_map* map, rgbd360_map_align_gicp_params* p);
+/* As rgbd360_map_align_cloud (arguments, return values, refusals, an empty map, an empty input; also -1 for epsilon outside (0, 1] or
+ * NaN, min_support outside 1 .. 27, a negative or NaN max_flatness).  normal: 3 n floats in the frame's coordinates where xyz is (host
+ * or device memory), one per point, any length; NULL: no source normals.  A normal that is zero or not finite marks a point without
+ * one.  rgbd360_map_align_trace's records work as for the other methods (sum_sq: sum cost). */
+int    rgbd360_map_align_gicp_cloud(rgbd360_map* map, const float* xyz, const float* normal, long long n, const float guess[16], int on_device,
+                                    const rgbd360_map_align_gicp_params* params, float pose_out[16], rgbd360_map_align_gicp_result* result);
+/* A sphere frame, as rgbd360_map_align_sphere.  It takes no source normals: the point-to-plane limit on the resident normals. */
+int    rgbd360_map_align_gicp_sphere(rgbd360_map* map, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                     const float guess[16], int on_device, const rgbd360_map_align_gicp_params* params, float pose_out[16],
+                                     rgbd360_map_align_gicp_result* result);
 
 /* ---- free-space observation and carving of the map (csrc/map_carve.h) -----------------------------------------------------------
  * What lets the map react to what a new frame sees: an object that moved away, a ghost wall left by a pose that was corrected later,

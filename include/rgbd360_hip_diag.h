@@ -145,6 +145,27 @@ int rgbd360_map_plane_fit(const double cov[6], double max_flatness, double norma
 int rgbd360_map_time_align_plane(rgbd360_map* map, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
                                  const float pose[16], const rgbd360_map_align_plane_params* params, int reps, float avg_us[4], double* probes);
 
+/* One evaluation of generalized ICP against the map (rgbd360_map_align_gicp_*, rgbd360_hip.h: steps 1-6 of its definition) at `pose`,
+ * inputs as in rgbd360_map_align_plane_eval; normal: the cloud's 3 n normals where xyz is, or NULL (ignored with a depth image).
+ * row[30]: n, the 21 upper-triangle terms of sum J^T M J row by row, sum J^T M e (6), sum e^T M e, sum e.e; counters[6]: n_valid,
+ * n_box_rejected, n_out_of_range, n_target_planes, n_source_planes, n_plane_pairs.  DEVICE arrays per input point, any may be NULL:
+ * key3_dev / d2_dev as in rgbd360_map_align_eval, weight_cost_dev seven doubles (M00 M01 M02 M11 M12 M22 and e^T M e as the sums take
+ * them; zeros without a kept match), class_dev one byte: bit 0 a kept match, bit 1 a target normal was used, bit 2 a source normal. */
+int rgbd360_map_align_gicp_eval(rgbd360_map* map, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                const float* xyz, const float* normal, long long n, const float pose[16], int on_device,
+                                const rgbd360_map_align_gicp_params* params, double row[30], long long counters[6], int32_t* key3_dev,
+                                float* d2_dev, double* weight_cost_dev, uint8_t* class_dev);
+/* Steps 2-4 of that definition on the host (the function the kernel calls, compiled for the CPU): nb the target normal (has_b: the
+ * voxel has one), na the source normal as passed (has_a: an array was passed), pose column-major, M = M00 M01 M02 M11 M12 M22.
+ * Returns 2 x (a target normal was used) + 4 x (a source normal was used), -1 on a NULL argument.  Needs no device. */
+int rgbd360_map_gicp_weight(const double nb[3], int has_b, const float na[3], int has_a, const float pose[16], float epsilon, double M[6]);
+/* The kernels of the three methods under HIP events on a sphere frame in device memory, averages over `reps` launches in microseconds:
+ * avg_us[0] k_vmap_gicp_eval (the normal layer built beforehand), [1] k_vmap_icp_eval and [2] k_vmap_plane_eval on the same frame, map
+ * and shared parameters in the same run, [3] the solve kernel on this method's row, [4] a whole alignment of params->max_iters
+ * iterations from `pose` (enqueue to synchronisation, wall clock).  *probes as in rgbd360_map_time_align.  The map is not changed. */
+int rgbd360_map_time_align_gicp(rgbd360_map* map, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
+                                const float pose[16], const rgbd360_map_align_gicp_params* params, int reps, float avg_us[5], double* probes);
+
 /* The pose graph's linearisation at its current poses (rgbd360_graph_*, rgbd360_hip.h): per edge r (6 doubles) and A = dr/dx_i (36
  * doubles, column-major), either may be NULL.  The graph is not changed. */
 int rgbd360_graph_linearize(rgbd360_graph* g, double* r, double* A);

@@ -38,6 +38,8 @@ SYMBOLS = [
     "rgbd360_map_default_align_params", "rgbd360_map_align_sphere", "rgbd360_map_align_cloud", "rgbd360_map_align_eval", "rgbd360_map_time_align",
     "rgbd360_map_default_align_plane_params", "rgbd360_map_align_plane_sphere", "rgbd360_map_align_plane_cloud", "rgbd360_map_align_plane_eval",
     "rgbd360_map_plane_fit", "rgbd360_map_time_align_plane",
+    "rgbd360_map_default_align_gicp_params", "rgbd360_map_align_gicp_sphere", "rgbd360_map_align_gicp_cloud", "rgbd360_map_align_gicp_eval",
+    "rgbd360_map_gicp_weight", "rgbd360_map_time_align_gicp",
     "rgbd360_map_default_render_params", "rgbd360_map_render_sphere", "rgbd360_map_render_sphere_dev", "rgbd360_map_time_render",
     "rgbd360_map_default_raycast_params", "rgbd360_map_raycast", "rgbd360_map_raycast_sphere", "rgbd360_map_raycast_sphere_dev",
     "rgbd360_map_raycast_set_plain", "rgbd360_map_time_raycast",
@@ -120,6 +122,15 @@ class MapAlignPlaneParams(C.Structure):  # rgbd360_map_align_plane_params
 
 class MapAlignPlaneResult(C.Structure):  # rgbd360_map_align_plane_result
     _fields_ = MapAlignResult._fields_ + [("n_unsupported", C.c_longlong), ("n_nonplanar", C.c_longlong), ("fitness_point", C.c_double)]
+
+
+class MapAlignGicpParams(C.Structure):   # rgbd360_map_align_gicp_params
+    _fields_ = MapAlignParams._fields_ + [("epsilon", C.c_float), ("use_target_normals", C.c_int), ("min_support", C.c_int), ("max_flatness", C.c_float)]
+
+
+class MapAlignGicpResult(C.Structure):   # rgbd360_map_align_gicp_result
+    _fields_ = MapAlignResult._fields_ + [("n_target_planes", C.c_longlong), ("n_source_planes", C.c_longlong), ("n_plane_pairs", C.c_longlong),
+                                          ("fitness_point", C.c_double)]
 
 
 class MapAlignTrace(C.Structure):        # rgbd360_map_align_trace (rgbd360_hip_diag.h)
@@ -422,6 +433,16 @@ def load() -> C.CDLL:
     L.rgbd360_map_plane_fit.argtypes = [vp, C.c_double, vp, vp]
     L.rgbd360_map_time_align_plane.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, C.POINTER(MapAlignPlaneParams), i32, vp,
                                                C.POINTER(C.c_double)]
+    L.rgbd360_map_default_align_gicp_params.argtypes = [vp, C.POINTER(MapAlignGicpParams)]
+    L.rgbd360_map_default_align_gicp_params.restype = None
+    L.rgbd360_map_align_gicp_sphere.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, C.POINTER(MapAlignGicpParams), f32p,
+                                                C.POINTER(MapAlignGicpResult)]
+    L.rgbd360_map_align_gicp_cloud.argtypes = [vp, vp, vp, ll, f32p, i32, C.POINTER(MapAlignGicpParams), f32p, C.POINTER(MapAlignGicpResult)]
+    L.rgbd360_map_align_gicp_eval.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, vp, vp, ll, f32p, i32, C.POINTER(MapAlignGicpParams), vp, vp, vp,
+                                              vp, vp, vp]
+    L.rgbd360_map_gicp_weight.argtypes = [vp, i32, vp, i32, vp, C.c_float, vp]
+    L.rgbd360_map_time_align_gicp.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, C.POINTER(MapAlignGicpParams), i32, vp,
+                                              C.POINTER(C.c_double)]
     L.rgbd360_map_default_render_params.argtypes = [vp, C.POINTER(MapRenderParams)]
     L.rgbd360_map_default_render_params.restype = None
     L.rgbd360_map_render_sphere.argtypes = [vp, i32, i32, f32p, C.POINTER(MapRenderParams), vp, vp, vp, vp, C.POINTER(MapRenderStats)]

@@ -14,7 +14,7 @@
 // No cell is pruned: all 27 are looked up whatever the point's place in its cell.
 //
 // This header also holds what every method of alignment against the map shares with the loop (map_align_plane.h is the second
-// method): the loop's state, init and solve kernels (LoopState<WORDS>, k_vmap_icp_init<WORDS>, k_vmap_icp_solve<Row>) and the host driver
+// method, map_align_gicp.h the third): the loop's state, init and solve kernels (LoopState<WORDS>, k_vmap_icp_init<WORDS>, k_vmap_icp_solve<Row>) and the host driver
 // (icp_prepare, icp_enqueue<M>, icp_align<M>, icp_eval<M>; the input of a call is voxel_map.h's MapInput).  A method is an evaluation
 // kernel, a row description (PointMethod) and a host description (PointIcp).  The evaluation kernels of every method are built from three shared pieces: the source load
 // (vmap::load_points, voxel_map.h, also k_vmap_insert's), the candidate search (vmap::search27 with the method's Support) and the block
@@ -39,7 +39,7 @@ namespace vmap {
 
 constexpr int kIcpSums = 17;
 constexpr int kIcpWords = 22;        // a partial row: the 17 sums, n_valid, n_box_rejected, n_out_of_range, probes, points searched (all doubles: exact integers)
-constexpr int kIcpMaxWords = 37;     // the widest row of any method (map_align_plane.h): the buffers of a map serve every method
+constexpr int kIcpMaxWords = 38;     // the widest row of any method (map_align_gicp.h): the buffers of a map serve every method
 constexpr int kIcpMaxIters = 1000;
 constexpr int kNoKey = -2147483647 - 1;
 
@@ -75,8 +75,9 @@ struct NoSupport {
 };
 template <class Support>
 struct Match {
-    float best = __builtin_inff();           // d2 of the nearest candidate, its key (kEmpty: none) and e = w - its centroid
+    float best = __builtin_inff();           // d2 of the nearest candidate, its key (kEmpty: none), its slot and e = w - its centroid
     unsigned long long best_key = kEmpty;
+    long long best_slot = -1;                // (read by map_align_gicp.h alone: the normal layer's record of the match)
     float be[3] = {0.f, 0.f, 0.f};
     Support support;
 };
@@ -115,6 +116,7 @@ __device__ __forceinline__ Match<Support> search27(const unsigned long long* __r
         if (d2 < mt.best) {
             mt.best = d2;
             mt.best_key = ck;
+            mt.best_slot = slot;
             mt.be[0] = e[0];
             mt.be[1] = e[1];
             mt.be[2] = e[2];
@@ -304,7 +306,8 @@ __global__ __launch_bounds__(64) void k_vmap_icp_solve(LoopState<M::kWords>* __r
 
 namespace {
 
-// what one alignment call works on: the input in device memory, the launch grid, the checked parameters (the last two: point-to-plane)
+// what one alignment call works on: the input in device memory, the launch grid, the checked parameters (min_support, max_flatness:
+// point-to-plane and the normal layer of generalized ICP; the last three: generalized ICP, map_align_gicp.h)
 struct IcpJob {
     MapSource src;
     dim3 grid;
@@ -312,6 +315,9 @@ struct IcpJob {
     rgbd360_map_align_params p;
     int min_support;
     float max_flatness;
+    float epsilon = 0.f;
+    int use_target_normals = 0;
+    const float* normal = nullptr;       // the source's normals in device memory, three floats per point of a cloud; null: none
 };
 
 int icp_check_params(rgbd360_map* m, const rgbd360_map_align_params* params, rgbd360_map_align_params& p) {
@@ -336,6 +342,13 @@ int icp_buffers(rgbd360_map* m, IcpJob& job) {      // (job.src is set: also the
 }
 int icp_prepare(rgbd360_map* m, const MapInput& in, IcpJob& job) {
     if (const int rc = vmap_to_device(m, in, job.src)) return rc;
+    job.normal = in.normal;
+    if (in.normal && !in.on_device) {        // (a cloud's: behind its points on the stream)
+        const size_t bytes = (size_t)in.n * 3 * sizeof(float);
+        HIPC(m, m->up_normal.ensure(bytes));
+        HIPC(m, hipMemcpyAsync(m->up_normal, in.normal, bytes, hipMemcpyHostToDevice, m->s->stream));
+        job.normal = reinterpret_cast<const float*>(m->up_normal.get());
+    }
     return icp_buffers(m, job);
 }
 // the input of an evaluation entry (rgbd360_hip_diag.h): the sphere frame where there is a depth image, otherwise the n points xyz

@@ -79,6 +79,7 @@ struct rgbd360_map {
     DevBuf<unsigned long long> table, d_stats;
     PinnedBuf<unsigned long long> h_stats;
     DevBuf<uint8_t> up_depth, up_rgb;    // a host frame / cloud on its way to the kernel
+    DevBuf<uint8_t> up_normal;           // ... and a host cloud's normals (map_align_gicp.h)
     DevBuf<float> x_xyz;                 // the host read-out's device side
     DevBuf<uint8_t> x_rgb;
     DevBuf<int32_t> x_count, x_key;
@@ -528,6 +529,7 @@ struct MapInput {
     int depth_type = 0, rows = 0, cols = 0, convention = 0;
     const float* xyz = nullptr;
     long long n = 0;
+    const float* normal = nullptr;       // a cloud's normals, 3 n floats where the points are (generalized ICP alone, map_align_gicp.h); null: none
 };
 MapInput sphere_input(const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
                       int on_device) {

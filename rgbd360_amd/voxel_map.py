@@ -7,6 +7,8 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
     stats = gmap.insert_sphere(rgb, depth, currentPose, convention=0)
     pose, res = gmap.align_sphere(depth, guess, convention=0)      # point-to-point ICP of a frame against the map (csrc/map_align.h)
     pose, res = gmap.align_sphere_plane(depth, guess, convention=0)    # point-to-plane: planes fitted to the centroids (csrc/map_align_plane.h)
+    pose, res = gmap.align_cloud_gicp(xyz, guess, normals=n)       # generalized ICP: per-match covariance weights (csrc/map_align_gicp.h)
+    pose, res = gmap.align_map_gicp(other_map, guess)              # ... of another map's voxels and normals: submap against submap
     depth, rgb, count, key3, stats = gmap.render_sphere(rows, cols, pose)      # the map as a spherical RGB-D frame (csrc/map_render.h)
     depth, rgb, count, key3, stats = gmap.raycast_sphere(rows, cols, pose)     # ... as a per-pixel first hit (csrc/map_raycast.h)
     t, key3, count, rgb, status, stats = gmap.raycast(origins, dirs)           # the first voxel along each ray of a list
@@ -304,6 +306,54 @@ class VoxelMap:
         """The same for a cloud xyz: n x 3 float32 in the frame's coordinates."""
         x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
         return self._align(self._L.rgbd360_map_align_plane_cloud, _lib.MapAlignPlaneResult, self.align_plane_params(**params), (_ptr(x), x.shape[0]), guess)
+
+    # ---- generalized ICP (rgbd360_map_align_gicp_*: the same matches, each weighted by (C_B + C_A)^-1 with the target's covariance from the
+    #      matched voxel's resident normal and the source's from a normal per point; the cost of the reference's GICP call sites)
+    def align_gicp_params(self, max_dist=None, max_iters=None, eps=None, min_count=None, min_matches=None, epsilon=None, use_target_normals=None,
+                          min_support=None, max_flatness=None):
+        """align_params' defaults, epsilon = 1e-3, use_target_normals = 1, min_support = 5 and max_flatness = 0.05, with the given fields
+        replaced."""
+        use_target_normals = None if use_target_normals is None else int(use_target_normals)
+        return self._params(_lib.MapAlignGicpParams, self._L.rgbd360_map_default_align_gicp_params, max_dist=max_dist, max_iters=max_iters, eps=eps,
+                            min_count=min_count, min_matches=min_matches, epsilon=epsilon, use_target_normals=use_target_normals,
+                            min_support=min_support, max_flatness=max_flatness)
+
+    def align_cloud_gicp(self, xyz, guess, normals=None, **params):
+        """Generalized ICP of the cloud xyz (n x 3 float32 in the frame's coordinates) against the map from `guess`: align_cloud's matches,
+        each weighted by the inverse of the sum of the two sides' covariances -- the map's per-voxel normals (normals()) on the target side,
+        `normals` (n x 3 float32 in the frame's coordinates; a zero or non-finite row: none for that point; None: none at all) on the source
+        side.  Returns (pose 4x4, result dict: align_cloud's fields -- fitness is the mean weighted cost -- plus n_target_planes,
+        n_source_planes, n_plane_pairs and fitness_point).  The map is not changed."""
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nrm = None
+        if normals is not None:
+            nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+            if nrm.shape != x.shape:
+                raise Rgbd360Error("VoxelMap.align_cloud_gicp: one normal per point")
+        args = (_ptr(x), None if nrm is None else _ptr(nrm), x.shape[0])
+        return self._align(self._L.rgbd360_map_align_gicp_cloud, _lib.MapAlignGicpResult, self.align_gicp_params(**params), args, guess)
+
+    def align_sphere_gicp(self, depth, guess, convention: int = 0, **params):
+        """The same for the sphere frame `depth`, which has no source normals: point-to-plane on the map's resident normals, weight
+        1 / epsilon along a voxel's normal and 1 across it, point-to-point where the matched voxel has none."""
+        args, keep = self._sphere_args("align_sphere_gicp", None, depth, convention, colour=False)
+        return self._align(self._L.rgbd360_map_align_gicp_sphere, _lib.MapAlignGicpResult, self.align_gicp_params(**params), args, guess)
+
+    def gicp_source(self, **normal_params):
+        """This map as the source of another map's align_map_gicp: (xyz, normals), its voxels' centroids and normals (zero where a voxel has
+        none) ordered by (i_z, i_y, i_x), so that the sums of an alignment are the same from run to run."""
+        xyz, normal, _, _, _, key3, _ = self.normals(**normal_params)
+        order = np.lexsort((key3[:, 0], key3[:, 1], key3[:, 2]))
+        return np.ascontiguousarray(xyz[order]), np.ascontiguousarray(normal[order])
+
+    def align_map_gicp(self, source_map, guess, **params):
+        """Plane-to-plane ICP of another VoxelMap against this one from `guess` (4x4, this map's world <- the source map's world): the
+        source's voxels (source_map.gicp_source(), its normals fitted under this call's min_count, min_support and max_flatness) through
+        align_cloud_gicp.  "Voxel-filter both clouds, then GICP", and the alignment of two submaps of a loop closure.  As for any cloud, this
+        map's box applies to the source's centroids in the source's own coordinates; set_box(None, None) where that is not wanted."""
+        fit = {k: params[k] for k in ("min_count", "min_support", "max_flatness") if params.get(k) is not None}
+        xyz, normal = source_map.gicp_source(**fit)
+        return self.align_cloud_gicp(xyz, guess, normals=normal, **params)
 
     def align_trace(self):
         """One record per step of the last align call of either kind: (n, sum_sq, update[6]) (rgbd360_map_align_eval, the diagnostics header)."""
