@@ -4,7 +4,7 @@
 //     frame_%03d.rgb  (H*W*3 uint8)   frame_%03d.depth (H*W uint16 mm)
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/odometry_replay.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o odometry_replay
-// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane | --refine-on-map-c2f SHIFT [--plane]] [--render-map PREFIX] [--raycast-map PREFIX] [--map-normals OUT] [--raycast-surface PREFIX] [--map-window N | --carve]]
+// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane | --refine-on-map-c2f SHIFT [--plane]] [--render-map PREFIX] [--raycast-map PREFIX] [--map-normals OUT] [--raycast-surface PREFIX] [--map-planes OUT] [--map-window N | --carve]]
 //         --sequence: all frames are loaded first and the frame loop runs inside the library (alignSequence)
 //         --multi N:  the same sequence sharded over N GPUs of this node from this one process (rgbd360_multi_*: one host thread
 //                     per device, contiguous shards of pairs, one ncclAllGather of the solved poses over xGMI); prints the
@@ -38,6 +38,10 @@
 //                     (GlobalMap::normals: a normal per voxel fitted to the centroids around it, facing the last pose; status RGBD360_NORMAL_*).
 //         --raycast-surface PREFIX: (needs --map) the ray-cast panorama with the surface (GlobalMap::raycastSurfaceSphere): the depth on the
 //                     plane fitted around each hit voxel and PREFIX_normal.pfm, the world-frame normal per pixel.
+//         --map-planes OUT: (needs --map) the map's planar regions (GlobalMap::planes: connected voxels of like normals, the plane set a lost
+//                     frame is registered against, GlobalMap::relocalize), one line "ix iy iz N P cx cy cz nx ny nz d area curvature" per plane
+//                     by root key: the root voxel's key, the voxels and points of the region, its centroid, normal, offset, hull area and
+//                     curvature; prints one "planes" line with the counters.
 //         --map-window N: (needs --map) a bounded local map, the usual odometry target: the loop keeps the images and poses of the last N
 //                     frames, and when frame k goes in, frame k - N leaves (GlobalMap::remove: the integer sums make that exact).  The
 //                     table is rebuilt (GlobalMap::rehash) when a census shows more tombstones than occupied voxels.  Prints one "window"
@@ -187,7 +191,7 @@ int main(int argc, char** argv) {
         return 0;
     }
     const bool use_pbmap = argc > 5 && std::string(argv[5]) == "--pbmap";
-    std::string map_file, render_prefix, raycast_prefix, normals_file, surface_prefix;
+    std::string map_file, render_prefix, raycast_prefix, normals_file, surface_prefix, planes_file;
     float leaf = 0.05f;
     bool refine_on_map = false, refine_on_map_plane = false, c2f_plane = false;
     int c2f_shift = -1;
@@ -202,6 +206,7 @@ int main(int argc, char** argv) {
         if (a + 1 < argc && std::string(argv[a]) == "--map-window") map_window = atoi(argv[a + 1]);
         if (a + 1 < argc && std::string(argv[a]) == "--map-normals") normals_file = argv[a + 1];
         if (a + 1 < argc && std::string(argv[a]) == "--raycast-surface") surface_prefix = argv[a + 1];
+        if (a + 1 < argc && std::string(argv[a]) == "--map-planes") planes_file = argv[a + 1];
         if (std::string(argv[a]) == "--refine-on-map") refine_on_map = true;
         if (std::string(argv[a]) == "--refine-on-map-plane") refine_on_map_plane = true;
         if (a + 1 < argc && std::string(argv[a]) == "--refine-on-map-c2f") c2f_shift = atoi(argv[a + 1]);
@@ -217,6 +222,10 @@ int main(int argc, char** argv) {
     }
     if ((!normals_file.empty() || !surface_prefix.empty()) && map_file.empty()) {
         fprintf(stderr, "--map-normals and --raycast-surface need --map\n");
+        return 2;
+    }
+    if (!planes_file.empty() && map_file.empty()) {
+        fprintf(stderr, "--map-planes: need --map\n");
         return 2;
     }
     if (map_window != 0 && (map_file.empty() || map_window < 0)) {
@@ -400,6 +409,25 @@ int main(int argc, char** argv) {
         if (!f) return 7;
         fprintf(f, "PF\n%d %d\n-1.0\n", w, h);
         for (int r = h - 1; r >= 0; --r) fwrite(normal.data() + (size_t)r * w * 3, sizeof(float), (size_t)w * 3, f);
+        fclose(f);
+    }
+    if (globalMap && !planes_file.empty()) {      // the map's planar regions: what a lost frame is registered against (GlobalMap::relocalize)
+        std::vector<int32_t> root_key3, key3, label_key3, plane_index;
+        const std::vector<rgbd360_plane> planes = globalMap->planes(&root_key3);
+        const rgbd360_map_plane_seg_stats st = globalMap->planeSegStats();
+        globalMap->planeLabels(key3, label_key3, plane_index);
+        std::vector<long long> n_voxels(planes.size(), 0);      // N of a plane: the voxels that carry its index
+        for (const int32_t a : plane_index)
+            if (a >= 0 && (size_t)a < n_voxels.size()) ++n_voxels[(size_t)a];
+        printf("planes voxels %lld eligible %lld links %lld regions %lld available %lld planes %zu in_planes %lld\n", st.n_voxels, st.n_eligible, st.n_links,
+               st.n_regions, st.n_planes_available, planes.size(), st.n_voxels_in_planes);
+        FILE* f = fopen(planes_file.c_str(), "w");
+        if (!f) return 6;
+        for (size_t k = 0; k < planes.size(); ++k) {
+            const rgbd360_plane& P = planes[k];
+            fprintf(f, "%d %d %d %lld %d %.6f %.6f %.6f %.6f %.6f %.6f %.6f %.6f %.6g\n", root_key3[3 * k], root_key3[3 * k + 1], root_key3[3 * k + 2], n_voxels[k],
+                    P.count, P.centroid[0], P.centroid[1], P.centroid[2], P.normal[0], P.normal[1], P.normal[2], P.d, P.area, P.curvature);
+        }
         fclose(f);
     }
     return 0;

@@ -40,6 +40,11 @@
 // of the measured point collect through-votes, the voxel it ends in an end-vote, and carve() erases the voxels seen through and not measured.
 // A lossy edit: a carved voxel forgets its points, and a later remove() of a frame that fed it returns false,
 //     globalMap.observe(frame.sphereDepth, pose);   globalMap.carve();      votes(key3, through, end) reads the counts out instead
+// Relocalisation (rgbd360_map_planes, rgbd360_map_plane_labels): the reference's Relocalizer360 (Relocalizer360.h:78-93) places a lost frame
+// with  registerer.RegisterPbMap(keyframe, lostFrame, ..)  against the planes of what it has mapped, without an initial guess.  The map
+// segmented into planar regions under its per-voxel normals is that plane set for the whole map,
+//     globalMap.planes()      int status = globalMap.relocalize(framePlanes, pose)     0: accepted, pose = world <- frame
+// (the loop over keyframes and its thresholds -- at least 5 matched planes, matched area above 10 -- stay the caller's policy)
 #pragma once
 
 #include <algorithm>
@@ -405,6 +410,60 @@ class GlobalMap {
     size_t voteBytes() const { return rgbd360_map_vote_bytes(map_); }
     void releaseVotes() { check(rgbd360_map_release_votes(map_), "rgbd360_map_release_votes"); }
 
+    // Planar regions and relocalisation (rgbd360_map_planes / _plane_labels; defaults: the normals' min_count 1, min_support 5, max_flatness
+    // 0.05, then max_voxel_curvature inf, cos_angle cos 5 deg, max_offset 0.5 leaves, min_voxels 50, max_curvature 0.0013).  planes: the map's
+    // planar regions by root key ascending, normals facing `viewpoint` (3 floats, world; nullptr: the origin), rootKey3 (may be nullptr) the
+    // key of each region's root voxel; every plane that passes the filters comes back (the buffer grows to planeSegStats().n_planes_available).
+    // planeLabels: one record per voxel in no specified order -- its key, its region's root key (its own where it has no normal), and the
+    // region's place in planes() or -1.  relocalize: rgbd360_register_planes(ref = the map's planes, trg = framePlanes): the status (0: accepted),
+    // pose = world <- frame, info (may be nullptr) the 6 x 6 information matrix; match (may be nullptr) gets, per map plane, the index of the frame
+    // plane matched or -1.  mapPlanes (may be nullptr): the map planes used.
+    rgbd360_map_plane_seg_params planeSegParams() const {
+        rgbd360_map_plane_seg_params p;
+        rgbd360_map_default_plane_seg_params(map_, &p);
+        return p;
+    }
+    std::vector<rgbd360_plane> planes(std::vector<int32_t>* rootKey3 = nullptr, const float* viewpoint = nullptr,
+                                      const rgbd360_map_plane_seg_params* params = nullptr) {
+        std::vector<rgbd360_plane> out(64);
+        int n = 0;
+        for (;;) {
+            if (rootKey3) rootKey3->assign(3 * out.size(), 0);
+            check(rgbd360_map_planes(map_, params, viewpoint, (int)out.size(), out.data(), rootKey3 ? rootKey3->data() : nullptr, &n, &planeSeg_),
+                  "rgbd360_map_planes");
+            if (planeSeg_.n_planes_available <= (long long)out.size()) break;
+            out.resize((size_t)planeSeg_.n_planes_available);
+        }
+        out.resize((size_t)n);
+        if (rootKey3) rootKey3->resize(3 * (size_t)n);
+        return out;
+    }
+    long long planeLabels(std::vector<int32_t>& key3, std::vector<int32_t>& labelKey3, std::vector<int32_t>& planeIndex,
+                          const rgbd360_map_plane_seg_params* params = nullptr) {
+        const size_t n = (size_t)size();
+        key3.assign(3 * n, 0);
+        labelKey3.assign(3 * n, 0);
+        planeIndex.assign(n, -1);
+        const long long got = rgbd360_map_plane_labels(map_, params, (long long)n, key3.data(), labelKey3.data(), planeIndex.data());
+        if (got != (long long)n) throw std::runtime_error(std::string("rgbd360_map_plane_labels: ") + rgbd360_map_last_error(map_));
+        return got;
+    }
+    const rgbd360_map_plane_seg_stats& planeSegStats() const { return planeSeg_; }      // of the last planes / relocalize call
+    int relocalize(const std::vector<rgbd360_plane>& framePlanes, Mat4f& pose, float* info = nullptr, std::vector<int32_t>* match = nullptr,
+                   int maxMatchPlanes = 0, int registMode = 0, const rgbd360_pbmap_params* pbmapParams = nullptr,
+                   const rgbd360_map_plane_seg_params* params = nullptr, std::vector<rgbd360_plane>* mapPlanes = nullptr) {
+        const std::vector<rgbd360_plane> ref = planes(nullptr, nullptr, params);
+        if (match) match->assign(std::max<size_t>(ref.size(), 1), -1);
+        const int rc = rgbd360_register_planes(ref.data(), (int)ref.size(), framePlanes.data(), (int)framePlanes.size(), maxMatchPlanes, registMode,
+                                               pbmapParams, pose.m, info, match ? match->data() : nullptr, nullptr, nullptr);
+        if (rc < 0) throw std::runtime_error("rgbd360_register_planes: bad arguments");
+        if (match) match->resize(ref.size());
+        if (mapPlanes) *mapPlanes = ref;
+        return rc;
+    }
+    size_t planeBytes() const { return rgbd360_map_plane_bytes(map_); }
+    void releasePlanes() { check(rgbd360_map_release_planes(map_), "rgbd360_map_release_planes"); }
+
     long long size() const { return rgbd360_map_size(map_); }
     size_t bytes() const { return rgbd360_map_bytes(map_); }
     void clear() { check(rgbd360_map_clear(map_), "rgbd360_map_clear"); }
@@ -453,6 +512,7 @@ class GlobalMap {
     rgbd360_map_render_stats render_{};
     rgbd360_map_raycast_stats raycast_{};
     rgbd360_map_normal_stats normal_{};
+    rgbd360_map_plane_seg_stats planeSeg_{};
     rgbd360_map_observe_stats observe_{};
     rgbd360_map_carve_stats carve_{};
     long long onPlane_ = 0;

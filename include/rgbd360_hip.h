@@ -1523,6 +1523,97 @@ int rgbd360_group_planes(const rgbd360_plane* planes, const int* n_per_sensor, i
 int rgbd360_pool_sensor_planes(const rgbd360_plane* planes, int n, float max_curvature, float min_area, float max_elongation, float cos_normal,
                                float dist_normal, float proximity, rgbd360_plane* out, int max_out, int* n_out);
 
+/* ---- planar regions of the map (csrc/map_planes.h) ---------------------------------------------------------------------------------
+ * The voxel map segmented into planes: connected components of the occupied voxels under the per-voxel normals of "surface normals of
+ * the map" above, each flat enough component an rgbd360_plane -- a PbMap of the global map, the other operand of
+ * rgbd360_register_planes when a frame has to be placed in the map WITHOUT an initial guess (the reference's Relocalizer360,
+ * include/Relocalizer360.h:78-93, runs RegisterPbMap of the lost frame against the planes of what it has mapped).  The result is a
+ * function of the voxel set and the parameters alone: it does not depend on the order of insertion, the table's capacity, slot
+ * indices, rehashes or the run.  Nothing here writes the table.  tests/map_planes_reference.py restates the definition in numpy.
+ * Predicates: float64 + - x on the float32 values as stored, every operation rounded on its own (no contraction); a dot product is
+ * ((x x' + y y') + z z').
+ *   eligible  a voxel whose status is RGBD360_NORMAL_OK in the normal layer of this call's (min_count, min_support, max_flatness) -- the
+ *             layer is built or reused exactly as the surface cast does -- and whose stored curvature is <= max_voxel_curvature.
+ *   link      two eligible voxels u, v whose keys differ by one of the 26 non-zero offsets of {-1, 0, 1}^3 (an index outside the 21-bit
+ *             range does not exist; tombstones and empty cells are absent) are linked iff |n_u . n_v| >= cos_angle (the absolute value:
+ *             the canonical sign of a normal can flip between neighbours) and, with e = c_v - c_u of the read-out centroids (float64),
+ *             |n_u . e| <= max_offset leaf and |n_v . e| <= max_offset leaf; the bound is the one product (double)max_offset x
+ *             (double)leaf.  Symmetric bit for bit; an unordered pair counts once in n_links.
+ *   region    a connected component of the link graph (a singleton is one).  Its root is the member with the smallest packed key, the
+ *             (i_z, i_y, i_x) order of rgbd360_map_extract; the root's key3 is the region's label.
+ *   sums      exact integers, unit weight per voxel (point density does not bias a wall's extent): N = member voxels, P = the sum of
+ *             their counts and, with r the root's centroid and q_k = rint(((double)c_k - (double)r_k) x 2^16) (half to even), the three
+ *             sums of q_k and the six of q_j q_k in 64-bit integers.
+ *   range     with E = the largest |i_k - i_k(root)| over the members and the three axes, a region is in range iff
+ *             N ((E + 2) (double)leaf 2^16)^2 < 2^62 in float64 (rgbd360_map_plane_sums_in_range, the diagnostics header): |q_k| is below
+ *             (E + 2) leaf 2^16, so no sum can leave the int64 range.  Decided from N and E BEFORE any sum is read; a region with
+ *             N >= min_voxels that is out of range makes the call return -8 (the frame plane calls' "region moments out of range") with
+ *             no output touched.  At leaf 0.1 a region of 10^5 voxels may span 100 m.
+ *   plane     from the sums alone, on the host in float64 (rgbd360_map_plane_from_sums): a region with N >= min_voxels whose curvature
+ *             l0 / trace of the covariance of the voxel centroids is <= max_curvature.  centroid, normal, curvature, elongation, ppal_dir
+ *             and area_moment as the frame plane calls derive them from their moments; the normal faces `viewpoint` (NULL: the world's
+ *             origin), d = -n . centroid, count = P, root = the plane's ordinal in the returned list (its label, the root's key3, comes
+ *             in root_key3_out), color_count = color_mode_count = 0: the matcher skips its colour tests.
+ *   hull      the region's extreme members in the 64 in-plane directions RGBD360_MAP_PLANE_DIRS[k] = (a_k, b_k), about 1024 (cos, sin)
+ *             of 2 pi k / 64, literal so that no library's cosine enters: with (u, v) a member centroid's float64 coordinates about the
+ *             record's float32 centroid in the float32 basis (e1, e2) the host derived from the sums (the two in-plane eigenvectors), the
+ *             member with the largest u a_k + v b_k, a tie going to the smaller key.  area, center_hull, hull_points, hull_n and hull[]
+ *             are the frame plane calls' hull of those extremes; the vertices run counter-clockwise seen from the normal's side.
+ *   selection planes come back by root key ascending.  When more than max_planes pass the filters the max_planes of largest N are kept,
+ *             ties going to the smaller root key, still in root-key order; n_planes_available counts all that passed.
+ * Known limits, not bugs: pairwise linking walks round gently curved surfaces and the region's curvature filter then drops the WHOLE
+ * region (the behaviour of PCL's organised segmentation); a wall thicker than one voxel gives two parallel regions; regions are not
+ * merged across gaps (rgbd360_merge_planes does that for callers who want it).
+ * The label layer (32 bytes per table slot) lies in device memory beside the table and belongs to the map: built by the first call that
+ * needs it, reused while the map is unwritten and the parameters stand, freed with the map or by rgbd360_map_release_planes, reported by
+ * rgbd360_map_plane_bytes (rgbd360_map_bytes stays the table's size).  The calls work on a level of the pyramid as every reader does.
+ * Out of scope: colour descriptors of map planes, device-side outputs, merging across gaps, incremental upkeep of the labels, labels
+ * inside the ICPs, the keyframe loop and acceptance thresholds of Relocalizer360::relocalize (caller policy), several GPUs. */
+typedef struct {
+    int   min_count;             /* the normal layer's three (rgbd360_map_normal_params): 1 */
+    int   min_support;           /* 5 */
+    float max_flatness;          /* 0.05 */
+    float max_voxel_curvature;   /* an eligible voxel's largest stored curvature, >= 0: +inf */
+    float cos_angle;             /* smallest |n_u . n_v| of a link, in [0, 1]: cos 5 deg (voxel normals on a noisy wall were measured up to
+                                    1.4 deg off, so two neighbours can differ by about 3 deg) */
+    float max_offset;            /* largest offset of a neighbour's centroid along either normal, in leaves, >= 0: 0.5 */
+    int   min_voxels;            /* smallest N of a plane, >= 1: 50 (0.125 m2 of voxels at the default leaf 0.05 m: the reference's
+                                    min_area_plane, 0.12 m2) */
+    float max_curvature;         /* largest region curvature of a plane, >= 0: 0.0013 (the reference's plane constant) */
+    /* The defaults are settings, not measurements.  Probe (the numpy restatement on the relocalisation scene of
+     * tests/map_planes_reference.py, an asymmetric room of nine faces at leaf 0.1 m, axis-aligned and again turned by 25 degrees): every
+     * face is one region in both maps.  With min_voxels = 20, the first value tried, the turned copy also returned three slivers of 21, 21
+     * and 42 voxels, columns of voxels along the junctions of oblique walls; 50 leaves exactly the nine faces in both, and the matcher
+     * accepts the pair.  The other values stood as first chosen. */
+} rgbd360_map_plane_seg_params;
+typedef struct { long long n_voxels, n_eligible, n_links, n_regions, n_planes_available, n_voxels_in_planes; } rgbd360_map_plane_seg_stats;
+static const short RGBD360_MAP_PLANE_DIRS[64][2] = {
+    {1024, 0}, {1019, 100}, {1004, 200}, {980, 297}, {946, 392}, {903, 483}, {851, 569}, {792, 650}, {724, 724}, {650, 792}, {569, 851},
+    {483, 903}, {392, 946}, {297, 980}, {200, 1004}, {100, 1019}, {0, 1024}, {-100, 1019}, {-200, 1004}, {-297, 980}, {-392, 946},
+    {-483, 903}, {-569, 851}, {-650, 792}, {-724, 724}, {-792, 650}, {-851, 569}, {-903, 483}, {-946, 392}, {-980, 297}, {-1004, 200},
+    {-1019, 100}, {-1024, 0}, {-1019, -100}, {-1004, -200}, {-980, -297}, {-946, -392}, {-903, -483}, {-851, -569}, {-792, -650},
+    {-724, -724}, {-650, -792}, {-569, -851}, {-483, -903}, {-392, -946}, {-297, -980}, {-200, -1004}, {-100, -1019}, {0, -1024},
+    {100, -1019}, {200, -1004}, {297, -980}, {392, -946}, {483, -903}, {569, -851}, {650, -792}, {724, -724}, {792, -650}, {851, -569},
+    {903, -483}, {946, -392}, {980, -297}, {1004, -200}, {1019, -100}};
+void      rgbd360_map_default_plane_seg_params(const rgbd360_map* map, rgbd360_map_plane_seg_params* p);
+/* The planes of the map.  planes_out (max_planes records) and root_key3_out (3 ints per plane) receive min(max_planes, passed) planes,
+ * n_planes_out their number; stats (exact counts, whatever max_planes; n_voxels_in_planes sums N over all planes that passed).  Any
+ * output pointer may be NULL; params NULL: the defaults; viewpoint NULL: the origin.  Host arrays; the call waits.  Returns 0; an empty
+ * map returns 0 with zero statistics and launches nothing.  -1 with rgbd360_map_last_error set and no output byte touched: min_count < 1,
+ * min_support outside 1 .. 27, a negative or NaN threshold, cos_angle outside [0, 1], min_voxels < 1, max_planes < 0, a viewpoint that is
+ * not finite.  -8: a region out of range (above). */
+int       rgbd360_map_planes(rgbd360_map* map, const rgbd360_map_plane_seg_params* params, const float viewpoint[3], int max_planes,
+                             rgbd360_plane* planes_out, int32_t* root_key3_out, int* n_planes_out, rgbd360_map_plane_seg_stats* stats);
+/* One record per voxel with count > 0, in NO specified order; returns the voxel count, writes at most max_out records.  key3: the
+ * voxel; label_key3: its region's root key3 (an ineligible voxel: its own key); plane_index: the ordinal, by root key ascending, of its
+ * region among ALL planes that passed the filters -- the plane's place in rgbd360_map_planes' list whenever max_planes does not cut it
+ * -- or -1 (no plane, or an ineligible voxel).  Refusals as above, and max_out < 0. */
+long long rgbd360_map_plane_labels(rgbd360_map* map, const rgbd360_map_plane_seg_params* params, long long max_out, int32_t* key3,
+                                   int32_t* label_key3, int32_t* plane_index);
+/* Device memory of the label layer and its region lists (0: none); rgbd360_map_release_planes frees it, the next call rebuilds. */
+size_t    rgbd360_map_plane_bytes(const rgbd360_map* map);
+int       rgbd360_map_release_planes(rgbd360_map* map);
+
 #ifdef __cplusplus
 }
 #endif

@@ -220,6 +220,28 @@ int rgbd360_map_time_observe(rgbd360_map* map, const void* depth_dev, size_t dep
 int rgbd360_map_time_normals(rgbd360_map* map, const rgbd360_map_normal_params* params, int reps, float* build_us, float* scan_us,
                              rgbd360_map_normal_stats* stats, long long* layer_bytes);
 
+/* A plane record from a region's sums on the host (planar regions of the map, rgbd360_hip.h; the function rgbd360_map_planes calls): N
+ * member voxels, P points, the root's centroid, sums[9] = the three sums of q_k then those of q_x q_x, q_x q_y, q_x q_z, q_y q_y, q_y q_z,
+ * q_z q_z.  plane: centroid, normal (facing viewpoint; NULL: the origin), d, curvature, count = P, root = 0, elongation, ppal_dir,
+ * area_moment, area = area_moment, center_hull = centroid, no hull and no colour.  0, or -1 on a NULL argument or N < 1.  Needs no device. */
+int rgbd360_map_plane_from_sums(long long n_voxels, long long n_points, const float root_centroid[3], const long long sums[9],
+                                const float viewpoint[3], rgbd360_plane* plane);
+/* The same with the hull: member_xyz (3 floats) and member_key3 (3 ints) of the region's n_voxels members, in any order.  The extremes
+ * are taken on the host, operation for operation as the device takes them, so the record is byte for byte the one rgbd360_map_planes
+ * returns for that region (but for `root`, 0 here).  Needs no device. */
+int rgbd360_map_plane_from_members(long long n_voxels, long long n_points, const float root_centroid[3], const long long sums[9],
+                                   const float* member_xyz, const int32_t* member_key3, const float viewpoint[3], rgbd360_plane* plane);
+/* The range rule of a region's sums: 1 iff n_voxels ((extent_cells + 2) (double)leaf 2^16)^2 < 2^62 in float64, else 0.  Needs no device. */
+int rgbd360_map_plane_sums_in_range(long long n_voxels, long long extent_cells, float leaf);
+/* The build of the planar segmentation (rgbd360_map_planes) under HIP events: stage_us[8 r + k], r < reps, the stages of rebuild r in
+ * microseconds -- 0 the clear of the layer (k_vmap_pl_init), 1 k_vmap_pl_link, 2 k_vmap_pl_compress, 3 k_vmap_pl_count, 4
+ * k_vmap_pl_roots, 5 k_vmap_pl_sums, 6 k_vmap_pl_scatter, 7 k_vmap_pl_extremes; the host work between them is not in any of them.  One
+ * untimed build runs first; the normal layer is built before and is not part of the stages.  merge_waves: 1 the sums pass as shipped (a
+ * wave whose members share one region adds once), 0 every lane adds on its own.  stats (may be NULL): those of the last build.  -1 on
+ * an empty map.  The map is not changed. */
+int rgbd360_map_time_planes(rgbd360_map* map, const rgbd360_map_plane_seg_params* params, int reps, int merge_waves, float* stage_us,
+                            rgbd360_map_plane_seg_stats* stats);
+
 /* The build of the map pyramid (rgbd360_map_level, rgbd360_hip.h) under HIP events, averages over `reps` in microseconds: avg_us[s - 1],
  * 1 <= s <= top_shift, the build of level s out of level s - 1 (the clear of its table and of the counters, one k_vmap_coarsen launch);
  * avg_us[6] the builds of levels 1 .. top_shift back to back; avg_us[7] ONE k_vmap_extract launch (centroids only) over the parent's

@@ -49,6 +49,9 @@ SYMBOLS = [
     "rgbd360_map_vote_bytes", "rgbd360_map_release_votes", "rgbd360_map_time_observe",
     "rgbd360_map_level", "rgbd360_map_pyramid_bytes", "rgbd360_map_release_levels", "rgbd360_map_default_c2f_params",
     "rgbd360_map_align_c2f_sphere", "rgbd360_map_align_c2f_cloud", "rgbd360_map_time_coarsen",
+    "rgbd360_map_default_plane_seg_params", "rgbd360_map_planes", "rgbd360_map_plane_labels", "rgbd360_map_plane_bytes",
+    "rgbd360_map_release_planes", "rgbd360_map_plane_from_sums", "rgbd360_map_plane_from_members", "rgbd360_map_plane_sums_in_range",
+    "rgbd360_map_time_planes",
     "rgbd360_graph_create", "rgbd360_graph_destroy", "rgbd360_graph_last_error", "rgbd360_graph_add_vertices", "rgbd360_graph_add_edges",
     "rgbd360_graph_set_poses", "rgbd360_graph_set_fixed", "rgbd360_graph_n_vertices", "rgbd360_graph_n_edges", "rgbd360_graph_clear",
     "rgbd360_graph_default_params", "rgbd360_graph_optimize", "rgbd360_graph_get_poses", "rgbd360_graph_chi2", "rgbd360_graph_get_trace",
@@ -178,6 +181,26 @@ class MapNormalParams(C.Structure):     # rgbd360_map_normal_params
 
 class MapNormalStats(C.Structure):      # rgbd360_map_normal_stats
     _fields_ = [(n, C.c_longlong) for n in ("n_voxels", "n_below_min_count", "n_unsupported", "n_nonplanar", "n_normals")]
+
+
+class MapPlaneSegParams(C.Structure):   # rgbd360_map_plane_seg_params
+    _fields_ = [("min_count", C.c_int), ("min_support", C.c_int), ("max_flatness", C.c_float), ("max_voxel_curvature", C.c_float),
+                ("cos_angle", C.c_float), ("max_offset", C.c_float), ("min_voxels", C.c_int), ("max_curvature", C.c_float)]
+
+
+class MapPlaneSegStats(C.Structure):    # rgbd360_map_plane_seg_stats
+    _fields_ = [(n, C.c_longlong) for n in ("n_voxels", "n_eligible", "n_links", "n_regions", "n_planes_available", "n_voxels_in_planes")]
+
+
+# RGBD360_MAP_PLANE_DIRS: the 64 in-plane directions of a map plane's hull, (a_k, b_k) about 1024 (cos, sin) of 2 pi k / 64
+MAP_PLANE_DIRS = (
+    (1024, 0), (1019, 100), (1004, 200), (980, 297), (946, 392), (903, 483), (851, 569), (792, 650), (724, 724), (650, 792), (569, 851),
+    (483, 903), (392, 946), (297, 980), (200, 1004), (100, 1019), (0, 1024), (-100, 1019), (-200, 1004), (-297, 980), (-392, 946),
+    (-483, 903), (-569, 851), (-650, 792), (-724, 724), (-792, 650), (-851, 569), (-903, 483), (-946, 392), (-980, 297), (-1004, 200),
+    (-1019, 100), (-1024, 0), (-1019, -100), (-1004, -200), (-980, -297), (-946, -392), (-903, -483), (-851, -569), (-792, -650),
+    (-724, -724), (-650, -792), (-569, -851), (-483, -903), (-392, -946), (-297, -980), (-200, -1004), (-100, -1019), (0, -1024),
+    (100, -1019), (200, -1004), (297, -980), (392, -946), (483, -903), (569, -851), (650, -792), (724, -724), (792, -650), (851, -569),
+    (903, -483), (946, -392), (980, -297), (1004, -200), (1019, -100))
 
 
 class MapObserveParams(C.Structure):    # rgbd360_map_observe_params
@@ -481,6 +504,18 @@ def load() -> C.CDLL:
     L.rgbd360_map_release_votes.argtypes = [vp]
     L.rgbd360_map_time_observe.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, C.POINTER(MapObserveParams), i32, i32, vp, vp,
                                            C.POINTER(MapObserveStats)]
+    L.rgbd360_map_default_plane_seg_params.argtypes = [vp, C.POINTER(MapPlaneSegParams)]
+    L.rgbd360_map_default_plane_seg_params.restype = None
+    L.rgbd360_map_planes.argtypes = [vp, C.POINTER(MapPlaneSegParams), vp, i32, vp, vp, C.POINTER(i32), C.POINTER(MapPlaneSegStats)]
+    L.rgbd360_map_plane_labels.argtypes = [vp, C.POINTER(MapPlaneSegParams), ll, vp, vp, vp]
+    L.rgbd360_map_plane_labels.restype = ll
+    L.rgbd360_map_plane_bytes.argtypes = [vp]
+    L.rgbd360_map_plane_bytes.restype = C.c_size_t
+    L.rgbd360_map_release_planes.argtypes = [vp]
+    L.rgbd360_map_plane_from_sums.argtypes = [ll, ll, vp, vp, vp, C.POINTER(Plane)]
+    L.rgbd360_map_plane_from_members.argtypes = [ll, ll, vp, vp, vp, vp, vp, C.POINTER(Plane)]
+    L.rgbd360_map_plane_sums_in_range.argtypes = [ll, ll, C.c_float]
+    L.rgbd360_map_time_planes.argtypes = [vp, C.POINTER(MapPlaneSegParams), i32, i32, vp, C.POINTER(MapPlaneSegStats)]
     L.rgbd360_map_level.argtypes = [vp, i32, C.POINTER(vp)]
     L.rgbd360_map_pyramid_bytes.argtypes = [vp]
     L.rgbd360_map_pyramid_bytes.restype = C.c_size_t

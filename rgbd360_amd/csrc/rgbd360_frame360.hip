@@ -443,11 +443,9 @@ struct RegionFit {
     double c[3], C[3][3], evals[3], evecs[3][3];
     float area_moment, elongation, ppal_dir[3];
 };
-RegionFit region_fit(const f360::F360SlotRecord& R) {
+// m: the three first and six second moments in metres, N: what they were summed over (the frame's regions here, the map's in map_planes.h)
+RegionFit region_fit_moments(const double m[9], double N) {
     RegionFit f;
-    double m[9];
-    for (int q = 0; q < 9; ++q) m[q] = (double)(long long)R.mom[q] / f360::kMomScale;      // fixed point -> metres
-    const double N = R.count;
     const double cx = m[0] / N, cy = m[1] / N, cz = m[2] / N;
     const double C[3][3] = {{m[3] / N - cx * cx, m[4] / N - cx * cy, m[5] / N - cx * cz},
                             {m[4] / N - cx * cy, m[6] / N - cy * cy, m[7] / N - cy * cz},
@@ -460,6 +458,11 @@ RegionFit region_fit(const f360::F360SlotRecord& R) {
     f.elongation = (float)(l1 > 0 ? sqrt(l2 / l1) : INFINITY);
     for (int q = 0; q < 3; ++q) f.ppal_dir[q] = (float)f.evecs[2][q];
     return f;
+}
+RegionFit region_fit(const f360::F360SlotRecord& R) {
+    double m[9];
+    for (int q = 0; q < 9; ++q) m[q] = (double)(long long)R.mom[q] / f360::kMomScale;      // fixed point -> metres
+    return region_fit_moments(m, (double)R.count);
 }
 // ... into the plane record (f360_planes_dev for the regions of `segment`, f360_refine_dev again for the grown inlier sets)
 void apply_extent(rgbd360_plane& P, const RegionFit& f, int count) {
@@ -1266,6 +1269,7 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
 #include "map_align_gicp.h"
 #include "map_raycast.h"
 #include "map_carve.h"
+#include "map_planes.h"
 
 #ifdef RGBD360_HULL_DBG
 extern "C" int rgbd360_debug_hull_stats(unsigned long long* out /* [4096][8] */) {

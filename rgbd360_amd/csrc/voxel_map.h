@@ -65,6 +65,15 @@
 
 #include "map_table.h"
 
+// a planar region that passed the filters (map_planes.h), as the map keeps it between calls: what rgbd360_map_plane_from_sums takes, the
+// in-plane frame its extremes were taken in and those extremes
+struct VmapPlaneRec {
+    unsigned long long root_key;
+    long long n_voxels, n_points, sums[9];
+    float root_centroid[3], origin[3], e1[3], e2[3];
+    float uv[64][2];
+};
+
 struct rgbd360_map {
     rgbd360_ctx* ctx = nullptr;
     F360State* s = nullptr;              // the context's Frame360 state: device, stream, the resident angle tables (not owned)
@@ -127,6 +136,21 @@ struct rgbd360_map {
     unsigned long long vt_rev = 0;
     long long vt_rays_n = 0, vt_voted = 0;
     bool vt_have = false, vt_spent = false;
+    // planar regions (map_planes.h): the label layer (32 bytes per slot) and the region lists of revision pl_rev under the parameters
+    // pl_params, with the planes that passed the filters as the host keeps them (root key ascending); rebuilt when either differs
+    unsigned long long pl_rev = 0;
+    rgbd360_map_plane_seg_params pl_params = {};
+    DevBuf<unsigned long long> pl_layer;                          // per slot: smallest key, points | root slot, voxels, extent, region id
+    DevBuf<unsigned long long> pl_roots, pl_sums, pl_stats;       // eight words / nine sums per qualifying region; the counters
+    PinnedBuf<unsigned long long> pl_hstats;
+    DevBuf<int> pl_plane_of, pl_cursor;                           // per qualifying region: its plane's ordinal or -1; per plane: members scattered
+    DevBuf<unsigned long long> pl_offset, pl_members;             // per plane: where its members start; three words per member (u, v, key)
+    DevBuf<float> pl_frames;                                      // per plane: origin, e1, e2 (nine floats, padded to twelve)
+    DevBuf<unsigned long long> pl_ranges, pl_partial, pl_extremes;      // the extremes' work: ranges of the lists, the chunks' winners, the planes' 64
+    DevBuf<int32_t> pl_stage;                                     // the label read-out's records on the device: seven words each
+    std::vector<VmapPlaneRec> pl_planes;
+    rgbd360_map_plane_seg_stats pl_host_stats = {};
+    bool pl_merge_waves = true;                                   // (rgbd360_map_time_planes: the sums pass without its per-wave merge)
     // the map pyramid (map_pyramid.h).  levels[s - 1]: level s of this map, the map of leaf * 2^s merged out of this table, owned here and
     // built on demand.  parent != null: this map IS such a level (of shift `shift`), a borrowed handle that every reading entry takes and
     // every writing entry refuses (vmap_refuse_level); lv_rev: the parent's revision its content is that of (0: never built)

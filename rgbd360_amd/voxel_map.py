@@ -14,6 +14,8 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
     t, key3, count, rgb, status, stats = gmap.raycast(origins, dirs)           # the first voxel along each ray of a list
     xyz, normal, curvature, status, count, key3, stats = gmap.normals(viewpoint)   # one normal per voxel (csrc/map_normals.h) ...
     depth, normal, rgb, count, key3, n_on_plane, stats = gmap.raycast_surface_sphere(rows, cols, pose)     # ... and the surface a ray meets
+    planes, root_key3, stats = gmap.planes()       # the map segmented into planar regions (csrc/map_planes.h): a PbMap of the map ...
+    found = gmap.relocalize(frame_planes)          # ... against which a lost frame is placed without a guess: found["pose"] if status 0
     gmap.observe_sphere(depth, currentPose); gmap.carve()      # the voxels the frame looks straight through leave (csrc/map_carve.h)
     xyz, rgb, count, key = gmap.extract()          # sorted by (i_z, i_y, i_x)
     gmap.remove_sphere(rgb, depth, currentPose)    # exactly undoes that insert (csrc/map_edit.h); gmap.mismatch tells of a broken contract
@@ -32,8 +34,8 @@ import warnings
 
 import numpy as np
 
-from . import _lib
-from .register import Rgbd360Error, _ptr, pose_from_cm, pose_to_cm
+from . import _lib, pbmap
+from .register import Rgbd360Error, _planes_to_dicts, _ptr, pose_from_cm, pose_to_cm
 
 MAP_FULL = 3      # RGBD360_MAP_FULL
 MAP_MISMATCH = 4  # RGBD360_MAP_MISMATCH
@@ -628,6 +630,56 @@ class VoxelMap:
 
     def release_votes(self):
         self._check(self._L.rgbd360_map_release_votes(self._handle()))
+
+    # ---- planar regions and relocalisation (rgbd360_map_planes, rgbd360_map_plane_labels; csrc/map_planes.h): the map segmented into
+    #      planes, a PbMap of the global map, and a frame placed in it without an initial guess (the reference's Relocalizer360)
+    def plane_seg_params(self, **kw):
+        """The defaults (min_count 1, min_support 5, max_flatness 0.05, max_voxel_curvature inf, cos_angle cos 5 deg, max_offset 0.5
+        leaves, min_voxels 50, max_curvature 0.0013) with the given fields replaced."""
+        return self._params(_lib.MapPlaneSegParams, self._L.rgbd360_map_default_plane_seg_params, **kw)
+
+    def planes(self, viewpoint=None, max_planes: int = 256, **params):
+        """(planes, root_key3 [k, 3] int32, the statistics): the map's planar regions as the plane dicts of the frame plane calls, by root
+        key ascending, with the key of each region's root voxel.  viewpoint: three floats the normals face (None: the origin).  More than
+        max_planes passing the filters: the max_planes of most voxels; the statistics' n_planes_available counts them all."""
+        p = self.plane_seg_params(**params)
+        v = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float32).reshape(3)
+        k = max(int(max_planes), 0)
+        arr = (_lib.Plane * max(k, 1))()
+        key3 = np.zeros((k, 3), np.int32)
+        n, st = C.c_int(0), _lib.MapPlaneSegStats()
+        self._check(self._L.rgbd360_map_planes(self._handle(), C.byref(p), None if v is None else _ptr(v), int(max_planes), C.cast(arr, C.c_void_p),
+                                               _ptr(key3), C.byref(n), C.byref(st)))
+        return _planes_to_dicts(arr, n.value), key3[:n.value].copy(), _as_dict(st)
+
+    def plane_labels(self, **params):
+        """One record per voxel, in no specified order: (key3 [k, 3] int32, label_key3 [k, 3] int32 = the root key of the voxel's region,
+        its own key where it is not eligible, plane_index [k] int32 = the region's place among the planes that pass the filters, -1:
+        none)."""
+        p = self.plane_seg_params(**params)
+        k = len(self)
+        key3, label, index = np.zeros((k, 3), np.int32), np.zeros((k, 3), np.int32), np.full(k, -1, np.int32)
+        got = self._L.rgbd360_map_plane_labels(self._handle(), C.byref(p), k, _ptr(key3), _ptr(label), _ptr(index))
+        if got != k:
+            raise Rgbd360Error(f"rgbd360_map_plane_labels failed ({got}): {self._L.rgbd360_map_last_error(self._h).decode()}")
+        return key3, label, index
+
+    def relocalize(self, frame_planes, max_match_planes: int = 0, regist_mode: int = pbmap.DEFAULT_6DoF, params=None, **seg_params):
+        """The frame whose planes are `frame_planes` (plane dicts in the frame's coordinates) placed in the map without an initial guess:
+        pbmap.register_planes(ref = the map's planes, trg = frame_planes).  Returns that dict -- status 0 accepted, pose 4x4 world <- frame,
+        info, match {map plane: frame plane}, area_matched -- with map_planes, root_key3 and stats, the map planes it was matched against.
+        seg_params: viewpoint, max_planes and plane_seg_params' fields."""
+        map_planes, root_key3, stats = self.planes(**seg_params)
+        out = pbmap.register_planes(map_planes, frame_planes, max_match_planes=max_match_planes, regist_mode=regist_mode, params=params)
+        out.update(map_planes=map_planes, root_key3=root_key3, stats=stats)
+        return out
+
+    def plane_bytes(self) -> int:
+        """Device memory of the label layer and the region lists (0 after release_planes)."""
+        return int(self._L.rgbd360_map_plane_bytes(self._handle()))
+
+    def release_planes(self):
+        self._check(self._L.rgbd360_map_release_planes(self._handle()))
 
     # ---- read-out
     def __len__(self) -> int:
