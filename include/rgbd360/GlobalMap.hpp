@@ -45,6 +45,12 @@
 // segmented into planar regions under its per-voxel normals is that plane set for the whole map,
 //     globalMap.planes()      int status = globalMap.relocalize(framePlanes, pose)     0: accepted, pose = world <- frame
 // (the loop over keyframes and its thresholds -- at least 5 matched planes, matched area above 10 -- stay the caller's policy)
+// Submaps (rgbd360_map_merge / _unmerge / _records / _add_records): what a pose graph can move is a window of frames, not every frame.  A
+// small map per keyframe window is composed into the global map at the window's pose and, after a correction, taken out and put back at
+// the new one -- without the original frames, one launch each; the sums are integers, so both directions are exact,
+//     globalMap.merge(submap, &pose);      globalMap.unmerge(submap, &oldPose); globalMap.merge(submap, &newPose);
+//     globalMap.merge(other)               pose == nullptr: the union of two maps of one voxel size, word for word
+//     copy.addRecords(globalMap.records())    a map copied, or written out and read back, with its bits intact
 #pragma once
 
 #include <algorithm>
@@ -247,6 +253,38 @@ class GlobalMap {
     const rgbd360_map_c2f_result& c2fResult() const { return c2f_; }      // of the last alignSphereCoarseToFine / alignCloudCoarseToFine call
     size_t pyramidBytes() const { return rgbd360_map_pyramid_bytes(map_); }
     void releaseLevels() { check(rgbd360_map_release_levels(map_), "rgbd360_map_release_levels"); }
+
+    // Composing maps (rgbd360_map_merge / _unmerge / _records / _add_records).  merge: the live voxels of `source` added to this map --
+    // pose nullptr: sum mode (equal voxel sizes, the keys kept, the seven words added: the map that received both maps' insertions, bit for
+    // bit); a pose (this map's world <- the source's world): each source voxel enters as its count of coincident points at its posed centroid,
+    // its colour sums kept.  Returns false when the table was full as insert() does (mergeStats().n_voxels_dropped).  unmerge: the same terms
+    // taken off again -- the same unchanged source, pose and params, and that merge returned true: then this map is, bit for bit, the map
+    // that never saw the merge.  Returns false on a mismatch as remove() does (mergeStats().n_missing / n_underflow).  records: the live slots
+    // as they are, 8 words per voxel {key, count, Sx, Sy, Sz, Sr, Sg, Sb}, ascending key; addRecords adds such a list in sum mode (equal keys
+    // add up; a bad record throws and leaves the map unchanged) and returns false when the table was full.
+    rgbd360_map_merge_params mergeParams() const {
+        rgbd360_map_merge_params p;
+        rgbd360_map_default_merge_params(map_, &p);
+        return p;
+    }
+    bool merge(GlobalMap& source, const Mat4f* pose = nullptr, const rgbd360_map_merge_params* params = nullptr) {
+        return full(rgbd360_map_merge(map_, source.map_, pose ? pose->m : nullptr, params, &merge_), "rgbd360_map_merge");
+    }
+    bool unmerge(GlobalMap& source, const Mat4f* pose = nullptr, const rgbd360_map_merge_params* params = nullptr) {
+        return matched(rgbd360_map_unmerge(map_, source.map_, pose ? pose->m : nullptr, params, &merge_), "rgbd360_map_unmerge");
+    }
+    std::vector<uint64_t> records() const {
+        const long long n = size();
+        std::vector<uint64_t> out((size_t)n * 8);
+        const long long got = n ? rgbd360_map_records(map_, n, out.data()) : 0;
+        if (got != n) throw std::runtime_error(std::string("rgbd360_map_records: ") + rgbd360_map_last_error(map_));
+        return out;
+    }
+    bool addRecords(const std::vector<uint64_t>& records) {
+        if (records.size() % 8 != 0) throw std::runtime_error("GlobalMap::addRecords: 8 words per record");
+        return full(rgbd360_map_add_records(map_, records.data(), (long long)(records.size() / 8), 0, &merge_), "rgbd360_map_add_records");
+    }
+    const rgbd360_map_merge_stats& mergeStats() const { return merge_; }      // of the last merge / unmerge / addRecords
 
     // The map splatted into the full-sphere panorama of rows x cols at `pose` (world <- frame), the nearest voxel winning a pixel
     // (rgbd360_map_render_sphere; defaults: min_count 1, near = leaf, splat 1.0, max_half 8).  The vectors are resized; depth is float32
@@ -515,6 +553,7 @@ class GlobalMap {
     rgbd360_map_plane_seg_stats planeSeg_{};
     rgbd360_map_observe_stats observe_{};
     rgbd360_map_carve_stats carve_{};
+    rgbd360_map_merge_stats merge_{};
     long long onPlane_ = 0;
 };
 

@@ -848,6 +848,62 @@ int    rgbd360_map_align_c2f_sphere(rgbd360_map* map, const void* depth, size_t 
 int    rgbd360_map_align_c2f_cloud(rgbd360_map* map, const float* xyz, long long n, const float guess[16], int on_device,
                                    const rgbd360_map_c2f_params* params, float pose_out[16], rgbd360_map_c2f_result* result);
 
+/* ---- composing maps: merge at a pose, exact un-merge, table records (csrc/map_merge.h) -------------------------------------------------
+ * Submaps: a small map per keyframe window, the pose graph moves the windows, the global map is composed from them.  The table's sums
+ * are integers, so composition is exact and reversible, as removal and the pyramid are.  The source of a merge is the set of live
+ * voxels of `src` (count >= min_count, default 1), each with its words {key, n, Sx, Sy, Sz, Sr, Sg, Sb}.
+ * Pose mode (pose != NULL: 16 floats, column-major, the destination's world <- the source's world; the leaves may differ).  Per source
+ * voxel, in this order:
+ *   1 centroid  c_k = (float)((double)S_k / ((double)n * 1048576.0)): the read-out's bits.
+ *   2 box       none: the content passed the source's box when it was inserted.
+ *   3 pose      w_k = ((R_k0 c_x + R_k1 c_y) + R_k2 c_z) + t_k in float32, every product and sum rounded on its own: step 3 of an insert.
+ *   4 range     dropped and counted unless every w_k is finite and |w_k| < 4096; a source voxel of 2^31 points or more is out of range too.
+ *   5 voxel     i_k = (int)floorf(w_k * inv_leaf) with the DESTINATION's inv_leaf.
+ *   6 sums      into that destination voxel: count += n, S_k += n * llrint((double)w_k * 1048576.0) (in int64: n < 2^31), S_c += S_c(src).
+ * The result is the insertion of n coincident points at the posed centroid, with the colour total kept: rgbd360_map_census reports
+ * n_inconsistent == 0 afterwards.
+ * Sum mode (pose == NULL; src's leaf must be bit-equal to dst's): the key is kept and all seven words are added.  dst is then, bit for
+ * bit, the map that received both maps' insertions.
+ * Un-merge takes the same terms off again, in removal's manner: a read-only lookup, the count lowered in a compare-and-swap loop that
+ * never goes below zero, the two's-complement negatives of the six sums added; emptied voxels stay as tombstones.  The contract: the same
+ * source, unchanged since the merge, the same pose and min_count, and that merge did not return RGBD360_MAP_FULL.  Then dst is, bit for
+ * bit, the map that never saw the merge, whatever was inserted in between.  Outside the contract no word wraps: a source voxel whose
+ * destination is not in the table counts its points in n_missing; one asked for more than the destination holds takes what is there,
+ * counts the rest in n_underflow and leaves the sums alone (per voxel, as rgbd360_map_remove_*); the call returns RGBD360_MAP_MISMATCH.
+ * Both write dst as any writer does (levels, ray-cast, normal and plane layers follow, votes go stale, rgbd360_map_size is exact with
+ * and without tombstones in dst); src is only read and may be a level of a pyramid.  Both maps belong to one context.
+ * Statistics: n_voxels_read / n_points_read = n_*_below_min_count + n_*_out_of_range + n_*_dropped + n_*_added, voxels and points each.
+ * merge: n_*_dropped found no free slot; n_voxels_new were created (or revived).  un-merge: n_*_added are the voxels taken off in full
+ * and the points taken off, n_voxels_new the voxels emptied, n_voxels_dropped the voxels missing or short, n_points_dropped =
+ * n_missing + n_underflow.  n_voxels: dst's size after the call.
+ * Out of scope: sum mode across leaves, several GPUs, incremental upkeep of the layers, any interpolation or splatting of a posed voxel
+ * over several cells. */
+typedef struct {
+    int min_count;             /* source voxels with fewer points are skipped (and counted): 1 */
+} rgbd360_map_merge_params;
+typedef struct {
+    long long n_voxels_read, n_points_read, n_voxels_below_min_count, n_points_below_min_count, n_voxels_out_of_range, n_points_out_of_range;
+    long long n_voxels_added, n_points_added, n_voxels_new, n_voxels_dropped, n_points_dropped, n_missing, n_underflow, n_voxels;
+} rgbd360_map_merge_stats;
+void   rgbd360_map_default_merge_params(const rgbd360_map* map, rgbd360_map_merge_params* p);
+/* params and stats may be NULL.  0; RGBD360_MAP_FULL (merge: voxels already present still receive their terms); RGBD360_MAP_MISMATCH
+ * (un-merge); -1 with a message in dst's last error and nothing launched for a NULL map, dst == src, a level as dst, maps of different
+ * contexts, unequal leaves in sum mode, a pose with a non-finite entry or min_count < 1.  An empty source returns 0 and touches nothing. */
+int    rgbd360_map_merge(rgbd360_map* dst, rgbd360_map* src, const float pose[16], const rgbd360_map_merge_params* params,
+                         rgbd360_map_merge_stats* stats);
+int    rgbd360_map_unmerge(rgbd360_map* dst, rgbd360_map* src, const float pose[16], const rgbd360_map_merge_params* params,
+                           rgbd360_map_merge_stats* stats);
+/* A map's live slots as they are: 8 x uint64 per voxel {key, n, Sx, Sy, Sz, Sr, Sg, Sb} (key = i_z + 2^20 << 42 | i_y + 2^20 << 21 |
+ * i_x + 2^20; the sums in two's complement), ascending key.  Returns the voxel count and writes min(that, max_out) records to host
+ * memory; negative: an error.  A map rebuilt from its records is the same map. */
+long long rgbd360_map_records(rgbd360_map* map, long long max_out, uint64_t* records);
+/* Adds n such records in sum mode (host memory, or on_device: device memory on the map's device); equal keys in one list add up.
+ * Before anything is written a device pass checks every record: the key is not the empty marker (all ones) and is below 2^63 (three
+ * 21-bit indices), the count lies in 1 .. 2^31 - 1, every colour sum is <= 255 count and every |S_k| < count 2^32.  One bad record
+ * fails the call with -1 and a message naming how many were bad; the map is untouched.  0, RGBD360_MAP_FULL, or negative; n == 0
+ * returns 0 and touches nothing.  stats (may be NULL) as for a merge. */
+int    rgbd360_map_add_records(rgbd360_map* map, const uint64_t* records, long long n, int on_device, rgbd360_map_merge_stats* stats);
+
 /* ---- pose-graph optimisation of store edges (csrc/pose_graph.h) -----------------------------------------------------------------
  * The reference closes its SLAM loop in g2o: optimizer.addVertex(pose), optimizer.addEdge(nearestKF, newKF, relPose, registerer.getInfoMat()),
  * optimizer.optimizeGraph(), optimizer.getPoses(...) (KFsphere_SLAM.cpp:262-265, 542-550, 630, 679-689; GraphOptimizer_G2O.cpp:

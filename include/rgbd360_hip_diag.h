@@ -250,6 +250,14 @@ int rgbd360_map_time_planes(rgbd360_map* map, const rgbd360_map_plane_seg_params
  * are valid afterwards; the map is not changed. */
 int rgbd360_map_time_coarsen(rgbd360_map* map, int top_shift, int reps, float avg_us[8], long long* counters);
 
+/* The merge kernel (rgbd360_map_merge / _unmerge, rgbd360_hip.h) under HIP events, averages over `reps` in microseconds per launch, each
+ * with the clear of its counters: avg_us[0] src merged into an EMPTY scratch table of dst's size, leaf and fill state (every destination
+ * voxel is claimed), avg_us[1] merged into it a second time (every destination voxel is found), avg_us[2] one of the two taken off
+ * again (the un-merge kernel), avg_us[3] ONE k_vmap_extract launch (centroids only) over src's table, the cost of merely scanning it.
+ * pose as for rgbd360_map_merge (NULL: sum mode).  The scratch table goes when the call returns; neither map is changed.  Refusals as
+ * for rgbd360_map_merge. */
+int rgbd360_map_time_merge(rgbd360_map* dst, rgbd360_map* src, const float pose[16], int reps, float* avg_us);
+
 /* The same timer with the launches rotating over n_ctx contexts of one device (each with its own copy of a frame pair) on
  * ctxs[0]'s stream: once n_ctx x the level's working set exceeds the 256 MiB Infinity Cache every launch is fed from HBM. */
 int rgbd360_time_eval_kernel_rotating(rgbd360_ctx* const* ctxs, int n_ctx, int level, const float pose[16], int method,

@@ -49,6 +49,8 @@ SYMBOLS = [
     "rgbd360_map_vote_bytes", "rgbd360_map_release_votes", "rgbd360_map_time_observe",
     "rgbd360_map_level", "rgbd360_map_pyramid_bytes", "rgbd360_map_release_levels", "rgbd360_map_default_c2f_params",
     "rgbd360_map_align_c2f_sphere", "rgbd360_map_align_c2f_cloud", "rgbd360_map_time_coarsen",
+    "rgbd360_map_default_merge_params", "rgbd360_map_merge", "rgbd360_map_unmerge", "rgbd360_map_records", "rgbd360_map_add_records",
+    "rgbd360_map_time_merge",
     "rgbd360_map_default_plane_seg_params", "rgbd360_map_planes", "rgbd360_map_plane_labels", "rgbd360_map_plane_bytes",
     "rgbd360_map_release_planes", "rgbd360_map_plane_from_sums", "rgbd360_map_plane_from_members", "rgbd360_map_plane_sums_in_range",
     "rgbd360_map_time_planes",
@@ -156,6 +158,16 @@ class MapC2fLevel(C.Structure):          # rgbd360_map_c2f_level
 
 class MapC2fResult(C.Structure):         # rgbd360_map_c2f_result
     _fields_ = [("n_levels", C.c_int), ("levels", MapC2fLevel * (MAP_MAX_SHIFT + 1)), ("hessian", C.c_float * 36), ("gradient", C.c_float * 6)]
+
+
+class MapMergeParams(C.Structure):      # rgbd360_map_merge_params
+    _fields_ = [("min_count", C.c_int)]
+
+
+class MapMergeStats(C.Structure):       # rgbd360_map_merge_stats
+    _fields_ = [(n, C.c_longlong) for n in ("n_voxels_read", "n_points_read", "n_voxels_below_min_count", "n_points_below_min_count",
+                                            "n_voxels_out_of_range", "n_points_out_of_range", "n_voxels_added", "n_points_added", "n_voxels_new",
+                                            "n_voxels_dropped", "n_points_dropped", "n_missing", "n_underflow", "n_voxels")]
 
 
 class MapRenderParams(C.Structure):     # rgbd360_map_render_params
@@ -525,6 +537,14 @@ def load() -> C.CDLL:
     L.rgbd360_map_align_c2f_sphere.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, C.POINTER(MapC2fParams), f32p, C.POINTER(MapC2fResult)]
     L.rgbd360_map_align_c2f_cloud.argtypes = [vp, vp, ll, f32p, i32, C.POINTER(MapC2fParams), f32p, C.POINTER(MapC2fResult)]
     L.rgbd360_map_time_coarsen.argtypes = [vp, i32, i32, vp, vp]
+    L.rgbd360_map_default_merge_params.argtypes = [vp, C.POINTER(MapMergeParams)]
+    L.rgbd360_map_default_merge_params.restype = None
+    for f in (L.rgbd360_map_merge, L.rgbd360_map_unmerge):
+        f.argtypes = [vp, vp, f32p, C.POINTER(MapMergeParams), C.POINTER(MapMergeStats)]
+    L.rgbd360_map_records.argtypes = [vp, ll, vp]
+    L.rgbd360_map_records.restype = ll
+    L.rgbd360_map_add_records.argtypes = [vp, vp, ll, i32, C.POINTER(MapMergeStats)]
+    L.rgbd360_map_time_merge.argtypes = [vp, vp, f32p, i32, vp]
     L.rgbd360_graph_create.argtypes = [vp, C.POINTER(vp)]
     L.rgbd360_graph_destroy.argtypes = [vp]
     L.rgbd360_graph_destroy.restype = None

@@ -158,6 +158,8 @@ struct rgbd360_map {
     int shift = 0;
     unsigned long long lv_rev = 0;
     std::vector<std::unique_ptr<rgbd360_map>> levels;
+    // composing maps (map_merge.h): a record list on the device, the read-out's or a host list's on its way to the kernel
+    DevBuf<unsigned long long> mg_records;
 };
 
 namespace vmap {

@@ -23,6 +23,9 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
     c = gmap.census(); gmap.rehash() if c["n_tombstones"] > c["n_live"] else None      # compaction; rehash(capacity) grows or shrinks
     coarse = gmap.level(2)                         # the map at leaf * 4, merged out of the table (csrc/map_pyramid.h): a read-only VoxelMap
     pose, res = gmap.align_sphere_c2f(depth, guess, convention=0, top_shift=3)     # ICP on levels 3, 2, 1, 0: a basin of 8 leaves
+    gmap.merge(submap, pose); gmap.unmerge(submap, pose)       # a submap's voxels added at a pose and taken off again, exactly (csrc/map_merge.h)
+    gmap.merge(other)                              # pose None: the union of two maps of one leaf, word for word
+    gmap.save(path); copy = VoxelMap.load(reg, path)           # records(): the table's slots as they are; add_records() puts them back
 
 Every point has weight one and the sums are integers: the map does not depend on the order of the frames, and subtracting the same
 integer terms takes a frame out again bit for bit.
@@ -78,6 +81,8 @@ class VoxelMap:
             raise Rgbd360Error(f"rgbd360_map_create failed ({rc}): {self._L.rgbd360_last_error(ctx).decode()}")
         self._h = h
         self._ctx_value = ctx.value
+        self.leaf = float(np.float32(leaf))      # as the map holds it (float32)
+        self._box = (True, np.array([-2.0, -4.0, -4.0], np.float32), np.array([1.0, 4.0, 4.0], np.float32))      # rgbd360_map_create's default
         self._parent = None      # a level of a pyramid (level()): the map it belongs to
         self._level_gen = 0      # raised when the levels are released: views made before are stale
         self.full = False        # the last insert dropped points of new voxels (RGBD360_MAP_FULL)
@@ -134,10 +139,18 @@ class VoxelMap:
             raise Rgbd360Error("VoxelMap.set_box: both limits or none")
         if lo is None:
             self._check(self._L.rgbd360_map_set_box(self._handle(), None, None))
+            self._box = (False,) + self._box[1:]
             return
         lo = np.ascontiguousarray(lo, np.float32).reshape(3)
         hi = np.ascontiguousarray(hi, np.float32).reshape(3)
         self._check(self._L.rgbd360_map_set_box(self._handle(), _ptr(lo), _ptr(hi)))
+        self._box = (True, lo.copy(), hi.copy())
+
+    @property
+    def box(self):
+        """(has_box, lo [3] float32, hi [3] float32) as set_box left them (a level: its parent's)."""
+        has_box, lo, hi = (self if self._parent is None else self._parent)._box
+        return has_box, lo.copy(), hi.copy()
 
     # ---- insertion
     def _stats(self, rc, st):
@@ -381,6 +394,7 @@ class VoxelMap:
         view._parent, view._gen, view._level_gen = self, self._level_gen, 0
         view.full = view.mismatch = False
         view.shift = shift
+        view.leaf = float(np.float32(self.leaf) * np.float32(2.0 ** shift))
         return view
 
     @property
@@ -431,6 +445,89 @@ class VoxelMap:
         """The same for a cloud xyz: n x 3 float32 in the frame's coordinates."""
         x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
         return self._align_c2f(self._L.rgbd360_map_align_c2f_cloud, self.c2f_params(**params), (_ptr(x), x.shape[0]), guess)
+
+    # ---- composing maps (rgbd360_map_merge / _unmerge / _records / _add_records; csrc/map_merge.h): voxel records moved between tables --
+    #      a submap merged into a global map at a pose and taken out again exactly, a map copied, saved and loaded with its bits intact
+    def merge_params(self, min_count=None):
+        """The default (min_count 1) with the given field replaced."""
+        return self._params(_lib.MapMergeParams, self._L.rgbd360_map_default_merge_params, min_count=min_count)
+
+    def _merge(self, entry, source, pose, params):
+        if not isinstance(source, VoxelMap):
+            raise Rgbd360Error("VoxelMap.merge / unmerge: the source must be a VoxelMap")
+        p = self.merge_params(**params)
+        g = None if pose is None else pose_to_cm(pose)
+        st = _lib.MapMergeStats()
+        rc = entry(self._handle(), source._handle(), None if g is None else _ptr(g), C.byref(p), C.byref(st))
+        self.last_status = self._check(rc)
+        return rc, _as_dict(st)
+
+    def merge(self, source, pose=None, **params):
+        """The live voxels of `source` (another VoxelMap, or a level of one) added to this map.  pose None: sum mode -- equal leaves, the
+        keys kept, the seven words added: this map becomes the map that received both maps' insertions, bit for bit.  pose 4x4 (this
+        map's world <- the source's world): each source voxel enters as its count of coincident points at its posed centroid, its colour
+        sums kept; the leaves may differ.  Returns the statistics; self.full tells whether new voxels were dropped."""
+        rc, st = self._merge(self._L.rgbd360_map_merge, source, pose, params)
+        self.full = rc == MAP_FULL
+        return st
+
+    def unmerge(self, source, pose=None, **params):
+        """Undoes merge(source, pose, **params) of the same, unchanged source (that merge must not have been `full`), bit for bit and
+        whatever was inserted in between; emptied voxels stay as tombstones (rehash()).  Returns the statistics (n_voxels_new: voxels
+        emptied); self.mismatch tells that voxels were asked to leave that the map does not hold: its content is then unspecified."""
+        rc, st = self._merge(self._L.rgbd360_map_unmerge, source, pose, params)
+        self.mismatch = rc == MAP_MISMATCH
+        return st
+
+    def records(self, max_out=None):
+        """The live slots as they are: uint64 [k, 8] = (key, count, Sx, Sy, Sz, Sr, Sg, Sb) per voxel (the sums in two's complement), ascending
+        key = ascending (i_z, i_y, i_x), k = min(len, max_out)."""
+        n = len(self)
+        k = n if max_out is None else min(n, int(max_out))
+        rec = np.zeros((k, 8), np.uint64)
+        got = self._L.rgbd360_map_records(self._handle(), k, _ptr(rec))
+        if got != n:
+            raise Rgbd360Error(f"rgbd360_map_records failed ({got}): {self._L.rgbd360_map_last_error(self._h).decode()}")
+        return rec
+
+    def add_records(self, records):
+        """Adds a list of records (uint64 [n, 8], as records() returns them) in sum mode; equal keys add up.  Every record is checked on the
+        device first; one bad record raises and leaves the map unchanged.  Returns the statistics; self.full as after merge."""
+        rec = np.ascontiguousarray(records, np.uint64).reshape(-1, 8)
+        st = _lib.MapMergeStats()
+        rc = self._L.rgbd360_map_add_records(self._handle(), _ptr(rec), rec.shape[0], 0, C.byref(st))
+        self.last_status = self._check(rc)
+        self.full = rc == MAP_FULL
+        return _as_dict(st)
+
+    def save(self, path):
+        """numpy.savez of the records, the leaf and the box (has_box, lo, hi): load() gives the same map back."""
+        has_box, lo, hi = self.box
+        with open(path, "wb") as f:
+            np.savez(f, records=self.records(), leaf=np.array([self.leaf], np.float32), has_box=np.array([has_box], np.uint8), lo=lo, hi=hi)
+
+    @classmethod
+    def load(cls, reg, path, capacity=None, leaf=None):
+        """A new map on reg's context with the content, leaf and box of a save() file; capacity None: twice the file's voxels, at least 1024.
+        leaf given: a file whose leaf bits differ is refused."""
+        with np.load(path) as f:
+            rec, file_leaf = np.ascontiguousarray(f["records"], np.uint64).reshape(-1, 8), np.float32(f["leaf"][0])
+            has_box, lo, hi = bool(f["has_box"][0]), np.array(f["lo"], np.float32), np.array(f["hi"], np.float32)
+        if leaf is not None and np.float32(leaf).tobytes() != file_leaf.tobytes():
+            raise Rgbd360Error(f"VoxelMap.load: the file's leaf {file_leaf!r} is not the leaf asked for, {np.float32(leaf)!r}")
+        m = cls(reg, float(file_leaf), max(2 * len(rec), 1024) if capacity is None else int(capacity))
+        try:
+            if has_box:
+                m.set_box(lo, hi)
+            else:
+                m.set_box(None, None)
+            m.add_records(rec)
+            if m.full:
+                raise Rgbd360Error("VoxelMap.load: the capacity is too small for the file's voxels")
+        except Exception:
+            m.close()
+            raise
+        return m
 
     # ---- the map as a spherical frame (rgbd360_map_render_sphere: the reference's viewer.globalMap, OdometryRGBD360.cpp:242-268, as a
     #      panorama; the keyframe target of OdometryKeyFrame360.cpp with the whole map as the model)
