@@ -4,7 +4,7 @@
 //     frame_%03d.rgb  (H*W*3 uint8)   frame_%03d.depth (H*W uint16 mm)
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/odometry_replay.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o odometry_replay
-// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane | --refine-on-map-c2f SHIFT [--plane]] [--render-map PREFIX] [--raycast-map PREFIX] [--map-normals OUT] [--raycast-surface PREFIX] [--map-planes OUT] [--map-window N | --carve]]
+// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane | --refine-on-map-colour | --refine-on-map-c2f SHIFT [--plane]] [--render-map PREFIX] [--raycast-map PREFIX] [--map-normals OUT] [--raycast-surface PREFIX] [--map-planes OUT] [--map-window N | --carve]]
 //         --sequence: all frames are loaded first and the frame loop runs inside the library (alignSequence)
 //         --multi N:  the same sequence sharded over N GPUs of this node from this one process (rgbd360_multi_*: one host thread
 //                     per device, contiguous shards of pairs, one ncclAllGather of the solved poses over xGMI); prints the
@@ -24,6 +24,9 @@
 //         --refine-on-map-plane: the same with the point-to-plane form (GlobalMap::alignSpherePlane: the plane cost of the GICP those call
 //                     sites use); prints one "refine-plane" line per frame with the contributing points, the unsupported and nonplanar
 //                     ones and both fitness values.  Takes precedence over --refine-on-map.
+//         --refine-on-map-colour: the same with coloured ICP (GlobalMap::alignSphereColour: point-to-plane on the map's normals plus a photometric
+//                     term on its intensity gradients, which holds the pose along a corridor or a floor); one line per frame "refine-colour ..."
+//                     with the dropped and zero-gradient counts and both rms values.  Takes precedence over the two above.
 //         --refine-on-map-c2f SHIFT [--plane]: the same through the map pyramid (GlobalMap::alignSphereCoarseToFine): the ICP runs on the maps of
 //                     leaf * 2^SHIFT .. leaf, merged out of the resident table, each level from the pose of the one before -- a capture range of
 //                     2^SHIFT leaves where the two options above have one; --plane: the point-to-plane form on every level.  Prints one
@@ -193,7 +196,7 @@ int main(int argc, char** argv) {
     const bool use_pbmap = argc > 5 && std::string(argv[5]) == "--pbmap";
     std::string map_file, render_prefix, raycast_prefix, normals_file, surface_prefix, planes_file;
     float leaf = 0.05f;
-    bool refine_on_map = false, refine_on_map_plane = false, c2f_plane = false;
+    bool refine_on_map = false, refine_on_map_plane = false, refine_on_map_colour = false, c2f_plane = false;
     int c2f_shift = -1;
     int map_window = 0;
     bool carve = false;
@@ -209,6 +212,7 @@ int main(int argc, char** argv) {
         if (a + 1 < argc && std::string(argv[a]) == "--map-planes") planes_file = argv[a + 1];
         if (std::string(argv[a]) == "--refine-on-map") refine_on_map = true;
         if (std::string(argv[a]) == "--refine-on-map-plane") refine_on_map_plane = true;
+        if (std::string(argv[a]) == "--refine-on-map-colour") refine_on_map_colour = true;
         if (a + 1 < argc && std::string(argv[a]) == "--refine-on-map-c2f") c2f_shift = atoi(argv[a + 1]);
         if (std::string(argv[a]) == "--plane") c2f_plane = true;
     }
@@ -323,6 +327,15 @@ int main(int argc, char** argv) {
                 printf("  level %d shift %d status %d iterations %d converged %d matched %lld fitness %.6f pose_t %.5f %.5f %.5f\n", k - 1, r.levels[l].shift,
                        r.levels[l].status, r.levels[l].iterations, r.levels[l].converged, r.levels[l].n_matched, r.levels[l].fitness, r.levels[l].pose[12],
                        r.levels[l].pose[13], r.levels[l].pose[14]);
+            if (status == RGBD360_OK) currentPose = refined;
+        } else if (globalMap && refine_on_map_colour) {
+            rgbd360::Mat4f refined = currentPose;
+            const int status = globalMap->alignSphereColour(frame2.sphereRGB, frame2.sphereDepth, currentPose, refined, /*convention=*/0);
+            const rgbd360_map_align_colour_result& r = globalMap->alignColourResult();
+            printf("refine-colour %d status %d iterations %d matched %lld fitness %.6g pose_t %.5f %.5f %.5f no_normal %lld no_gradient %lld rms_geometric %.6f "
+                   "rms_colour %.6f\n",
+                   k - 1, status, r.iterations, r.n_matched, r.fitness, refined(0, 3), refined(1, 3), refined(2, 3), r.n_no_normal, r.n_no_gradient,
+                   r.rms_geometric, r.rms_colour);
             if (status == RGBD360_OK) currentPose = refined;
         } else if (globalMap && refine_on_map_plane) {
             rgbd360::Mat4f refined = currentPose;

@@ -18,6 +18,9 @@
 //     globalMap.alignCloudGICP(xyz, normals, n, guess, pose)      generalized ICP (rgbd360_map_align_gicp_*): the same match weighted by the
 //     globalMap.alignMapGICP(otherMap, guess, pose)               inverse of both sides' covariances -- the map's per-voxel normals and
 //     globalMap.alignSphereGICP(frame.sphereDepth, guess, pose)   the source's normals, which may be another map's: "filterVoxel both, then GICP"
+//     globalMap.alignSphereColour(frame.sphereRGB, frame.sphereDepth, guess, pose)   coloured ICP (rgbd360_map_align_colour_*): point-to-plane
+//                                                                  on the map's normals plus a photometric term on its intensity gradients
+//                                                                  (globalMap.colours), which holds the pose along a corridor or a floor
 // All match within one voxel; a guess further off goes through the map pyramid (rgbd360_map_level, rgbd360_map_align_c2f_*: the maps of
 // 2, 4, 8 .. times the voxel size are merged out of the table, exactly, and the ICP runs from the coarsest down),
 //     globalMap.alignSphereCoarseToFine(frame.sphereDepth, guess, pose)     c2fResult().levels[k]: what each level did
@@ -228,6 +231,32 @@ class GlobalMap {
     }
     const rgbd360_map_align_gicp_result& alignGicpResult() const { return alignGicp_; }      // of the last align*GICP call
 
+    // Coloured ICP against the map (rgbd360_map_align_colour_*): the matches of alignSphere / alignCloud, the point-to-plane residual along the
+    // matched voxel's resident normal (weight lambda_geometric) joined with the difference between the map's intensity, carried along its
+    // resident tangent-plane gradient (colours()) to the point, and the point's own (weight 1 - lambda_geometric): the texture holds the pose
+    // where geometry slides.  The colours are required: rgb an 8UC3 image of the depth image's size, rgb3 n x 3 bytes.
+    rgbd360_map_align_colour_params alignColourParams() const {
+        rgbd360_map_align_colour_params p;
+        rgbd360_map_default_align_colour_params(map_, &p);
+        return p;
+    }
+    int alignSphereColour(const ImageView& rgb, const ImageView& depth, const Mat4f& guess, Mat4f& pose, int convention = 0,
+                          const rgbd360_map_align_colour_params* params = nullptr) {
+        if (rgb.type != ImageView::U8C3 || depth.type == ImageView::U8C3 || rgb.rows != depth.rows || rgb.cols != depth.cols)
+            throw std::runtime_error("GlobalMap::alignSphereColour: an 8UC3 image and a 16UC1 / 32FC1 depth image of one size");
+        const int rc = rgbd360_map_align_colour_sphere(map_, static_cast<const uint8_t*>(rgb.data), rgb.step, depth.data, depth.step, depthType(depth),
+                                                       depth.rows, depth.cols, convention, guess.m, 0, params, pose.m, &alignColour_);
+        check(rc, "rgbd360_map_align_colour_sphere");
+        return rc;
+    }
+    int alignCloudColour(const float* xyz, const uint8_t* rgb3, long long n, const Mat4f& guess, Mat4f& pose,
+                         const rgbd360_map_align_colour_params* params = nullptr) {
+        const int rc = rgbd360_map_align_colour_cloud(map_, xyz, rgb3, n, guess.m, 0, params, pose.m, &alignColour_);
+        check(rc, "rgbd360_map_align_colour_cloud");
+        return rc;
+    }
+    const rgbd360_map_align_colour_result& alignColourResult() const { return alignColour_; }      // of the last align*Colour call
+
     // Coarse-to-fine ICP (rgbd360_map_align_c2f_*): alignSphere / alignCloud (kind 0) or their Plane forms (kind 1) on the levels
     // top_shift .. 0 of the map pyramid, level s being the map at voxelSize * 2^s merged out of the table; each level starts from the pose the
     // one before ended on and matches within max_dist_leaves of ITS voxel size, so top_shift 3 captures eight voxel sizes.  The levels are
@@ -373,6 +402,32 @@ class GlobalMap {
         return got;
     }
     const rgbd360_map_normal_stats& normalStats() const { return normal_; }      // of the last normals call
+    // Colour (rgbd360_map_colours; defaults: the normals' three, min_gradient_support 4, min_spread 0.01): one intensity per voxel and its
+    // gradient on the voxel's tangent plane (3 floats per metre, world), kept resident with the map.  One record per voxel ordered as
+    // extract(); xyz is resized, the others may be nullptr; status is RGBD360_COLOUR_*, the gradient is zero unless it is RGBD360_COLOUR_OK.
+    // Returns the voxel count; colourStats() has the counts.
+    rgbd360_map_colour_params colourParams() const {
+        rgbd360_map_colour_params p;
+        rgbd360_map_default_colour_params(map_, &p);
+        return p;
+    }
+    long long colours(std::vector<float>& xyz, std::vector<float>& intensity, std::vector<float>& gradient, std::vector<int32_t>* status = nullptr,
+                      std::vector<int32_t>* count = nullptr, std::vector<int32_t>* key3 = nullptr, const rgbd360_map_colour_params* params = nullptr) {
+        const size_t n = (size_t)size();
+        xyz.assign(3 * n, 0.f);
+        intensity.assign(n, 0.f);
+        gradient.assign(3 * n, 0.f);
+        if (status) status->assign(n, 0);
+        if (count) count->assign(n, 0);
+        if (key3) key3->assign(3 * n, 0);
+        const long long got = rgbd360_map_colours(map_, params, (long long)n, xyz.data(), intensity.data(), gradient.data(), status ? status->data() : nullptr,
+                                                  count ? count->data() : nullptr, key3 ? key3->data() : nullptr, &colour_);
+        if (got != (long long)n) throw std::runtime_error(std::string("rgbd360_map_colours: ") + rgbd360_map_last_error(map_));
+        return got;
+    }
+    const rgbd360_map_colour_stats& colourStats() const { return colour_; }      // of the last colours call
+    size_t colourBytes() const { return rgbd360_map_colour_bytes(map_); }
+    void releaseColours() { check(rgbd360_map_release_colours(map_), "rgbd360_map_release_colours"); }
     void raycastSurface(const std::vector<float>& origins, const std::vector<float>& dirs, std::vector<float>& t, std::vector<float>& normal,
                         std::vector<int32_t>* key3 = nullptr, std::vector<int32_t>* count = nullptr, std::vector<uint8_t>* rgb = nullptr,
                         std::vector<int32_t>* status = nullptr, const rgbd360_map_raycast_params* rayParams = nullptr,
@@ -546,10 +601,12 @@ class GlobalMap {
     rgbd360_map_align_result align_{};
     rgbd360_map_align_plane_result alignPlane_{};
     rgbd360_map_align_gicp_result alignGicp_{};
+    rgbd360_map_align_colour_result alignColour_{};
     rgbd360_map_c2f_result c2f_{};
     rgbd360_map_render_stats render_{};
     rgbd360_map_raycast_stats raycast_{};
     rgbd360_map_normal_stats normal_{};
+    rgbd360_map_colour_stats colour_{};
     rgbd360_map_plane_seg_stats planeSeg_{};
     rgbd360_map_observe_stats observe_{};
     rgbd360_map_carve_stats carve_{};

@@ -694,6 +694,119 @@ int    rgbd360_map_align_gicp_sphere(rgbd360_map* map, const void* depth, size_t
                                      const float guess[16], int on_device, const rgbd360_map_align_gicp_params* params, float pose_out[16],
                                      rgbd360_map_align_gicp_result* result);
 
+/* ---- colour of the map (csrc/map_colour.h) ---------------------------------------------------------------------------------------
+ * What an alignment needs of the colour sums every slot keeps: one intensity per voxel and its gradient on the voxel's tangent plane,
+ * fitted to the intensities of the voxels around it, kept resident next to the table like the normals it builds on.  A function of the
+ * voxel set, its colour sums and the five parameters alone: not of the order of insertion, the table's capacity, a slot index or the
+ * run.  Float64 with + - x / sqrt only, every operation rounded on its own and in the order written: host, device and a restatement in
+ * IEEE arithmetic agree bit for bit.  Nothing here writes the table.
+ *   1 intensity   Y = 4899 Sr + 9617 Sg + 1868 Sb in int64 (the dense alignment's gray weights, their sum 2^14), I64 = (double)Y /
+ *                 (((double)count 16384) 255), in [0, 1].  A voxel's I = (float)I64.  A source point's intensity (coloured ICP below) is I64
+ *                 of its three bytes with count 1, kept as a double.
+ *   2 status      RGBD360_COLOUR_NONE: count < min_count.  RGBD360_COLOUR_NO_NORMAL: the voxel is not RGBD360_NORMAL_OK in the normal
+ *                 layer of (min_count, min_support, max_flatness).  Otherwise the fit decides: RGBD360_COLOUR_OK or _NO_GRADIENT.
+ *   3 basis       n = the doubles of the voxel's float32 normal; k = the axis of smallest |n_k|, the lowest index on a tie; t = e_k x n
+ *                 (k = 0: (0, -n_z, n_y); 1: (n_z, 0, -n_x); 2: (-n_y, n_x, 0)); u = t / sqrt((t_x t_x + t_y t_y) + t_z t_z); v = n x u.
+ *   4 fit         the neighbours are the voxels with count >= min_count in the 27 cells, the voxel itself left out, in the cells' order
+ *                 of the alignments (the centre first, then dz / dy / dx ascending).  Per neighbour r = the float32 difference of the
+ *                 read-out's centroids, neighbour minus voxel, widened; a = (r_x u_x + r_y u_y) + r_z u_z, b the same with v,
+ *                 delta = (double)I_nb - (double)I; m counts them, Saa += a a, Sab += a b, Sbb += b b, Sad += a delta, Sbd += b delta.
+ *                 NO_GRADIENT when m < min_gradient_support, or unless det > min_spread (tr tr) with det = Saa Sbb - Sab Sab and
+ *                 tr = Saa + Sbb (neighbours on one line, or too few directions: det / tr^2 is lambda_0 lambda_1 / (lambda_0 + lambda_1)^2 of
+ *                 their tangential scatter, at most 1/4).  Else du = (Sad Sbb - Sbd Sab) / det, dv = (Saa Sbd - Sab Sad) / det and
+ *                 d_k = (float)(du u_k + dv v_k): the gradient in world coordinates, per metre, tangent to the voxel's plane.  d is zero
+ *                 unless the status is OK.
+ * The layer: 16 bytes per table slot of device memory beside the table (I with the status in its two spare top bits, then d),
+ * owned by the map, built by the first call that needs it -- one launch over the slots behind the normal layer's -- reused until the
+ * map is written or one of the five parameters differs, freed with the map or by rgbd360_map_release_colours (rgbd360_map_bytes stays
+ * the table's size).  A map that was fed without colours has I = 0 and d = 0 everywhere; nothing detects it: that is the caller's
+ * business.  Out of scope: colour gradients from the points inside a voxel, neighbourhoods wider than the 27 cells, exposure
+ * compensation. */
+enum { RGBD360_COLOUR_NONE = 0, RGBD360_COLOUR_OK = 1, RGBD360_COLOUR_NO_NORMAL = 2, RGBD360_COLOUR_NO_GRADIENT = 3 };
+typedef struct {
+    int   min_count;             /* the normal layer's three (rgbd360_map_normal_params): 1 */
+    int   min_support;           /* 5 */
+    float max_flatness;          /* 0.05 */
+    int   min_gradient_support;  /* neighbours a gradient needs, 1 .. 26: 4 */
+    float min_spread;            /* smallest det / tr^2 of the neighbours' tangential scatter, >= 0: 0.01 (the smaller spread about a tenth of
+                                    the larger) */
+} rgbd360_map_colour_params;
+typedef struct { long long n_voxels, n_below_min_count, n_no_normal, n_no_gradient, n_gradients; } rgbd360_map_colour_stats;
+void      rgbd360_map_default_colour_params(const rgbd360_map* map, rgbd360_map_colour_params* p);
+/* One record per voxel with count > 0, sorted as rgbd360_map_extract sorts ((i_z, i_y, i_x) ascending): returns the voxel count; the first
+ * max_out records are written; any output pointer may be NULL.  xyz [3], count and key3 [3] are the read-out's bits; intensity, gradient
+ * [3] and status as defined above.  stats (may be NULL): exact counts over the whole map, whatever max_out.  Host arrays; the call waits.
+ * -1, nothing launched and no output touched: min_count < 1, min_support outside 1 .. 27, min_gradient_support outside 1 .. 26,
+ * max_flatness or min_spread negative or NaN, max_out < 0.  params NULL: the defaults.  An empty map returns 0 with zero statistics and
+ * launches no kernel. */
+long long rgbd360_map_colours(rgbd360_map* map, const rgbd360_map_colour_params* params, long long max_out, float* xyz, float* intensity,
+                              float* gradient, int32_t* status, int32_t* count, int32_t* key3, rgbd360_map_colour_stats* stats);
+/* The same into device arrays on the map's device (stats_dev too; params is host memory), in NO specified order (key3 and xyz come
+ * along), at most max_out records: enqueued on the context's stream, the call does not wait. */
+long long rgbd360_map_colours_dev(rgbd360_map* map, const rgbd360_map_colour_params* params, long long max_out, float* xyz_dev, float* intensity_dev,
+                                  float* gradient_dev, int32_t* status_dev, int32_t* count_dev, int32_t* key3_dev, rgbd360_map_colour_stats* stats_dev);
+/* Device memory of the colour layer (0: none); rgbd360_map_release_colours frees it, the next call that needs it rebuilds. */
+size_t    rgbd360_map_colour_bytes(const rgbd360_map* map);
+int       rgbd360_map_release_colours(rgbd360_map* map);
+
+/* ---- coloured ICP against the map (csrc/map_align_colour.h) ------------------------------------------------------------------------
+ * Park, Zhou and Koltun's coloured point-cloud registration (Open3D's registration_colored_icp) with the map as the target: the
+ * point-to-plane term on the map's resident normals joined with a photometric term on the resident intensity gradients above.  Indoors
+ * -- a corridor, a floor and one wall -- geometry leaves the pose unobservable along the surfaces; the texture on them does not.
+ * Float64 with + - x / only, every operation rounded on its own.  Per source point at the current pose:
+ *   1 match: steps 1-4 of the point-to-point definition, bit for bit; e = the float32 w - c of the match, widened to double.
+ *   2 class: a kept match whose voxel is not RGBD360_NORMAL_OK in the normal layer of (min_count, min_support, max_flatness) is dropped
+ *     and counted in n_no_normal.  Otherwise n = the doubles of its float32 normal and I, d = those of its colour record under
+ *     (min_gradient_support, min_spread) -- both layers built or reused as their read-outs do; with RGBD360_COLOUR_NO_GRADIENT d = 0, the
+ *     point is counted in n_no_gradient and stays.  I_q = the source point's intensity (step 1 of the section above).
+ *   3 residuals: r_G = (n_x e_x + n_y e_y) + n_z e_z; p_k = e_k - r_G n_k; r_C = (I + ((d_x p_x + d_y p_y) + d_z p_z)) - I_q.
+ *   4 rows, for the increment pose <- pseudo_exp(v, omega) pose: J_G = [n | w x n], J_C = [d | w x d] (d is tangent, so the derivative of
+ *     the projection drops out), w x n = (w_y n_z - w_z n_y, w_z n_x - w_x n_z, w_x n_y - w_y n_x).
+ *   5 sums: l = (double)lambda_geometric, c = 1.0 - l, sG_a = l J_G,a, sC_a = c J_C,a; H_ab += sG_a J_G,b + sC_a J_C,b for a <= b,
+ *     g_a += sG_a r_G + sC_a r_C, cost += l (r_G r_G) + c (r_C r_C), gg += r_G r_G, cc += r_C r_C.
+ *   6 row: n, the 21 H terms row by row, the 6 g terms, cost, gg, cc, then the counters n_valid, n_box_rejected, n_out_of_range,
+ *     n_no_normal, n_no_gradient, probes and points searched: 38 doubles.  One partial row per workgroup, the rows added in ascending
+ *     order; no floating-point atomics.
+ *   7 loop: as for the other methods -- H and g cast to float32, gn::step with lambda 0, RGBD360_ILL_POSED on rank(H) < 6,
+ *     RGBD360_NO_VALID_PIXELS below min_matches, converged on v.v <= eps and omega.omega <= eps, at most max_iters steps, the final
+ *     evaluation, one stream synchronisation.  fitness = cost / n.
+ * With lambda_geometric = 1 everything but cc is independent of the colours (point-to-plane on the resident normals); 0 is the
+ * photometric term alone.  The table is never written.  Differences from Open3D, stated: the target's gradient comes from the voxels of
+ * the 27 cells, not from a radius search; no robust kernel on either term; sqrt(lambda) is not folded into the residuals (the same
+ * normal equations).  Out of scope: a colour switch in rgbd360_map_align_c2f_*, colour on the source side of a map-against-map
+ * alignment, exposure compensation. */
+typedef struct {
+    float max_dist;              /* as in rgbd360_map_align_params */
+    int   max_iters;
+    float eps;
+    int   min_count;             /* also the two layers' */
+    long long min_matches;       /* contributing points an evaluation must have: 6 */
+    float lambda_geometric;      /* the geometric term's weight in [0, 1], the photometric term's is 1 - lambda: 0.968 (Open3D's) */
+    int   min_support;           /* of the normal layer: 5 */
+    float max_flatness;          /* 0.05 */
+    int   min_gradient_support;  /* of the colour layer: 4 */
+    float min_spread;            /* 0.01 */
+} rgbd360_map_align_colour_params;
+typedef struct {
+    int status, iterations, converged;
+    long long n_valid, n_box_rejected, n_out_of_range, n_matched;      /* of the final evaluation; n_matched: the contributing points */
+    double fitness;              /* (lambda sum r_G^2 + (1 - lambda) sum r_C^2) / n_matched (0 when nothing matched) */
+    float hessian[36], gradient[6];
+    long long n_no_normal, n_no_gradient;      /* kept matches dropped for want of a normal / contributing with a zero gradient */
+    double rms_geometric, rms_colour;          /* sqrt(sum r_G^2 / n_matched) in metres, sqrt(sum r_C^2 / n_matched) in intensity units */
+} rgbd360_map_align_colour_result;
+void   rgbd360_map_default_align_colour_params(const rgbd360_map* map, rgbd360_map_align_colour_params* p);
+/* As rgbd360_map_align_cloud (arguments, return values, refusals, an empty map, an empty input) with the cloud's colours rgb3, n x 3
+ * bytes where xyz is, as rgbd360_map_insert_cloud takes them.  Also -1, before anything is launched: rgb3 NULL with n > 0, lambda_geometric
+ * outside [0, 1] or NaN, and what rgbd360_map_colours refuses of the layers' parameters.  rgbd360_map_align_trace's records work as for
+ * the other methods (sum_sq: the cost). */
+int    rgbd360_map_align_colour_cloud(rgbd360_map* map, const float* xyz, const uint8_t* rgb3, long long n, const float guess[16], int on_device,
+                                      const rgbd360_map_align_colour_params* params, float pose_out[16], rgbd360_map_align_colour_result* result);
+/* A sphere frame with its colour image, as rgbd360_map_insert_sphere takes the two; rgb NULL is refused. */
+int    rgbd360_map_align_colour_sphere(rgbd360_map* map, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type,
+                                       int rows, int cols, int convention, const float guess[16], int on_device,
+                                       const rgbd360_map_align_colour_params* params, float pose_out[16], rgbd360_map_align_colour_result* result);
+
 /* ---- free-space observation and carving of the map (csrc/map_carve.h) -----------------------------------------------------------
  * What lets the map react to what a new frame sees: an object that moved away, a ghost wall left by a pose that was corrected later,
  * points dropped into space that a later frame looks straight through.  Every measurement of a posed depth frame, or of a list of rays,

@@ -166,6 +166,41 @@ int rgbd360_map_gicp_weight(const double nb[3], int has_b, const float na[3], in
 int rgbd360_map_time_align_gicp(rgbd360_map* map, const void* depth_dev, size_t depth_step, int depth_type, int rows, int cols, int convention,
                                 const float pose[16], const rgbd360_map_align_gicp_params* params, int reps, float avg_us[5], double* probes);
 
+/* Steps 3-4 of the colour layer's definition (colour of the map, rgbd360_hip.h) on the host -- the function k_vmap_colour_layer runs,
+ * compiled for the CPU: the voxel's float32 normal and intensity, its m neighbours in their order as r (3 m floats, the float32 centroid
+ * differences) and intensity_nb (m floats).  gradient: d.  Returns RGBD360_COLOUR_OK or RGBD360_COLOUR_NO_GRADIENT, -1 on a NULL argument.
+ * Needs no device. */
+int rgbd360_map_colour_gradient(const float normal[3], float intensity, int m, const float* r, const float* intensity_nb, int min_gradient_support,
+                                float min_spread, float gradient[3]);
+/* Step 1 of that definition on the host: I64 of the colour sums of `count` points (0 when count < 1).  Needs no device. */
+double rgbd360_map_colour_intensity(long long sr, long long sg, long long sb, long long count);
+/* The build of the colour layer under HIP events: build_us[r], r < reps, one k_vmap_colour_layer launch over the table with the clear of
+ * its counters (the normal layer standing), normals_us[r] (may be NULL) one k_vmap_normals launch likewise and scan_us[r] (may be NULL) ONE
+ * k_vmap_extract launch (centroids only) over the same table, all in the same run, in microseconds (the caller takes medians); one
+ * untimed build of both layers runs first.  stats (may be NULL): those of the last build; *layer_bytes (may be NULL): device memory of
+ * the layer.  -1 on an empty map.  Both layers stay valid for the parameters given; the map is not changed. */
+int rgbd360_map_time_colours(rgbd360_map* map, const rgbd360_map_colour_params* params, int reps, float* build_us, float* normals_us, float* scan_us,
+                             rgbd360_map_colour_stats* stats, long long* layer_bytes);
+/* One evaluation of coloured ICP against the map (rgbd360_map_align_colour_*, rgbd360_hip.h: steps 1-6 of its definition) at `pose`: the
+ * sphere frame (rgb, depth) where depth is not NULL, otherwise the cloud (xyz, rgb3, n); host memory, or device memory with on_device.
+ * row[31]: n, the 21 upper-triangle terms of H row by row, g (6), cost, sum r_G^2, sum r_C^2; counters[5]: n_valid, n_box_rejected,
+ * n_out_of_range, n_no_normal, n_no_gradient.  DEVICE arrays per input point, any may be NULL: key3_dev / d2_dev as in
+ * rgbd360_map_align_eval (the key of the kept match whatever the point's class), residuals_dev two doubles (r_G, r_C; zeros unless the
+ * point contributes), class_dev one byte: bit 0 a kept match, bit 1 dropped for want of a normal, bit 2 it contributes with d = 0.
+ * -1 without colours: a cloud's row and counters are then zeroed, an image's outputs untouched. */
+int rgbd360_map_align_colour_eval(rgbd360_map* map, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type, int rows,
+                                  int cols, int convention, const float* xyz, const uint8_t* rgb3, long long n, const float pose[16], int on_device,
+                                  const rgbd360_map_align_colour_params* params, double row[31], long long counters[5], int32_t* key3_dev,
+                                  float* d2_dev, double* residuals_dev, uint8_t* class_dev);
+/* The coloured evaluation beside generalized ICP's under HIP events on a sphere frame in device memory, averages over `reps` launches in
+ * microseconds: avg_us[0] k_vmap_colour_eval (both layers built beforehand), [1] k_vmap_gicp_eval (epsilon 1e-3, target normals) on the
+ * same frame, map and shared parameters in the same run, [2] the solve kernel on this method's row, [3] a whole alignment of
+ * params->max_iters iterations from `pose` (enqueue to synchronisation, wall clock).  *probes as in rgbd360_map_time_align.  The map is
+ * not changed. */
+int rgbd360_map_time_align_colour(rgbd360_map* map, const uint8_t* rgb_dev, size_t rgb_step, const void* depth_dev, size_t depth_step, int depth_type,
+                                  int rows, int cols, int convention, const float pose[16], const rgbd360_map_align_colour_params* params, int reps,
+                                  float avg_us[4], double* probes);
+
 /* The pose graph's linearisation at its current poses (rgbd360_graph_*, rgbd360_hip.h): per edge r (6 doubles) and A = dr/dx_i (36
  * doubles, column-major), either may be NULL.  The graph is not changed. */
 int rgbd360_graph_linearize(rgbd360_graph* g, double* r, double* A);

@@ -40,6 +40,10 @@ SYMBOLS = [
     "rgbd360_map_plane_fit", "rgbd360_map_time_align_plane",
     "rgbd360_map_default_align_gicp_params", "rgbd360_map_align_gicp_sphere", "rgbd360_map_align_gicp_cloud", "rgbd360_map_align_gicp_eval",
     "rgbd360_map_gicp_weight", "rgbd360_map_time_align_gicp",
+    "rgbd360_map_default_colour_params", "rgbd360_map_colours", "rgbd360_map_colours_dev", "rgbd360_map_colour_bytes", "rgbd360_map_release_colours",
+    "rgbd360_map_colour_gradient", "rgbd360_map_colour_intensity", "rgbd360_map_time_colours",
+    "rgbd360_map_default_align_colour_params", "rgbd360_map_align_colour_sphere", "rgbd360_map_align_colour_cloud", "rgbd360_map_align_colour_eval",
+    "rgbd360_map_time_align_colour",
     "rgbd360_map_default_render_params", "rgbd360_map_render_sphere", "rgbd360_map_render_sphere_dev", "rgbd360_map_time_render",
     "rgbd360_map_default_raycast_params", "rgbd360_map_raycast", "rgbd360_map_raycast_sphere", "rgbd360_map_raycast_sphere_dev",
     "rgbd360_map_raycast_set_plain", "rgbd360_map_time_raycast",
@@ -136,6 +140,24 @@ class MapAlignGicpParams(C.Structure):   # rgbd360_map_align_gicp_params
 class MapAlignGicpResult(C.Structure):   # rgbd360_map_align_gicp_result
     _fields_ = MapAlignResult._fields_ + [("n_target_planes", C.c_longlong), ("n_source_planes", C.c_longlong), ("n_plane_pairs", C.c_longlong),
                                           ("fitness_point", C.c_double)]
+
+
+class MapColourParams(C.Structure):      # rgbd360_map_colour_params
+    _fields_ = [("min_count", C.c_int), ("min_support", C.c_int), ("max_flatness", C.c_float), ("min_gradient_support", C.c_int), ("min_spread", C.c_float)]
+
+
+class MapColourStats(C.Structure):       # rgbd360_map_colour_stats
+    _fields_ = [(n, C.c_longlong) for n in ("n_voxels", "n_below_min_count", "n_no_normal", "n_no_gradient", "n_gradients")]
+
+
+class MapAlignColourParams(C.Structure):     # rgbd360_map_align_colour_params
+    _fields_ = MapAlignParams._fields_ + [("lambda_geometric", C.c_float), ("min_support", C.c_int), ("max_flatness", C.c_float),
+                                          ("min_gradient_support", C.c_int), ("min_spread", C.c_float)]
+
+
+class MapAlignColourResult(C.Structure):     # rgbd360_map_align_colour_result
+    _fields_ = MapAlignResult._fields_ + [("n_no_normal", C.c_longlong), ("n_no_gradient", C.c_longlong), ("rms_geometric", C.c_double),
+                                          ("rms_colour", C.c_double)]
 
 
 class MapAlignTrace(C.Structure):        # rgbd360_map_align_trace (rgbd360_hip_diag.h)
@@ -491,6 +513,28 @@ def load() -> C.CDLL:
     L.rgbd360_map_raycast_set_plain.argtypes = [vp, i32]
     L.rgbd360_map_time_raycast.argtypes = [vp, ll, vp, vp, i32, i32, f32p, C.POINTER(MapRaycastParams), i32, i32, vp, vp, vp, C.POINTER(MapRaycastStats),
                                            C.POINTER(ll)]
+    L.rgbd360_map_default_colour_params.argtypes = [vp, C.POINTER(MapColourParams)]
+    L.rgbd360_map_default_colour_params.restype = None
+    L.rgbd360_map_colours.argtypes = [vp, C.POINTER(MapColourParams), ll, vp, vp, vp, vp, vp, vp, C.POINTER(MapColourStats)]
+    L.rgbd360_map_colours.restype = ll
+    L.rgbd360_map_colours_dev.argtypes = [vp, C.POINTER(MapColourParams), ll, vp, vp, vp, vp, vp, vp, vp]
+    L.rgbd360_map_colours_dev.restype = ll
+    L.rgbd360_map_colour_bytes.argtypes = [vp]
+    L.rgbd360_map_colour_bytes.restype = C.c_size_t
+    L.rgbd360_map_release_colours.argtypes = [vp]
+    L.rgbd360_map_colour_gradient.argtypes = [vp, C.c_float, i32, vp, vp, i32, C.c_float, vp]
+    L.rgbd360_map_colour_intensity.argtypes = [ll, ll, ll, ll]
+    L.rgbd360_map_colour_intensity.restype = C.c_double
+    L.rgbd360_map_time_colours.argtypes = [vp, C.POINTER(MapColourParams), i32, vp, vp, vp, C.POINTER(MapColourStats), C.POINTER(ll)]
+    L.rgbd360_map_default_align_colour_params.argtypes = [vp, C.POINTER(MapAlignColourParams)]
+    L.rgbd360_map_default_align_colour_params.restype = None
+    L.rgbd360_map_align_colour_sphere.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, C.POINTER(MapAlignColourParams), f32p,
+                                                  C.POINTER(MapAlignColourResult)]
+    L.rgbd360_map_align_colour_cloud.argtypes = [vp, vp, vp, ll, f32p, i32, C.POINTER(MapAlignColourParams), f32p, C.POINTER(MapAlignColourResult)]
+    L.rgbd360_map_align_colour_eval.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, vp, vp, ll, f32p, i32,
+                                                C.POINTER(MapAlignColourParams), vp, vp, vp, vp, vp, vp]
+    L.rgbd360_map_time_align_colour.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, f32p, C.POINTER(MapAlignColourParams), i32, vp,
+                                                C.POINTER(C.c_double)]
     L.rgbd360_map_default_normal_params.argtypes = [vp, C.POINTER(MapNormalParams)]
     L.rgbd360_map_default_normal_params.restype = None
     L.rgbd360_map_normals.argtypes = [vp, C.POINTER(MapNormalParams), vp, ll, vp, vp, vp, vp, vp, vp, C.POINTER(MapNormalStats)]

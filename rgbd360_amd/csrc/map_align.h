@@ -14,7 +14,7 @@
 // No cell is pruned: all 27 are looked up whatever the point's place in its cell.
 //
 // This header also holds what every method of alignment against the map shares with the loop (map_align_plane.h is the second
-// method, map_align_gicp.h the third): the loop's state, init and solve kernels (LoopState<WORDS>, k_vmap_icp_init<WORDS>, k_vmap_icp_solve<Row>) and the host driver
+// method, map_align_gicp.h the third, map_align_colour.h the fourth): the loop's state, init and solve kernels (LoopState<WORDS>, k_vmap_icp_init<WORDS>, k_vmap_icp_solve<Row>) and the host driver
 // (icp_prepare, icp_enqueue<M>, icp_align<M>, icp_eval<M>; the input of a call is voxel_map.h's MapInput).  A method is an evaluation
 // kernel, a row description (PointMethod) and a host description (PointIcp).  The evaluation kernels of every method are built from three shared pieces: the source load
 // (vmap::load_points, voxel_map.h, also k_vmap_insert's), the candidate search (vmap::search27 with the method's Support) and the block
@@ -307,7 +307,8 @@ __global__ __launch_bounds__(64) void k_vmap_icp_solve(LoopState<M::kWords>* __r
 namespace {
 
 // what one alignment call works on: the input in device memory, the launch grid, the checked parameters (min_support, max_flatness:
-// point-to-plane and the normal layer of generalized ICP; the last three: generalized ICP, map_align_gicp.h)
+// point-to-plane and the normal layer of generalized ICP; the next three: generalized ICP, map_align_gicp.h; the last three: coloured ICP,
+// map_align_colour.h)
 struct IcpJob {
     MapSource src;
     dim3 grid;
@@ -318,6 +319,9 @@ struct IcpJob {
     float epsilon = 0.f;
     int use_target_normals = 0;
     const float* normal = nullptr;       // the source's normals in device memory, three floats per point of a cloud; null: none
+    float lambda_geometric = 1.f;
+    int min_gradient_support = 0;
+    float min_spread = 0.f;
 };
 
 int icp_check_params(rgbd360_map* m, const rgbd360_map_align_params* params, rgbd360_map_align_params& p) {

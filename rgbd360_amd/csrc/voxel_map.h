@@ -127,6 +127,14 @@ struct rgbd360_map {
     DevBuf<unsigned long long> nm_stats;                          // the build's counters and the read-out's record counter ...
     PinnedBuf<unsigned long long> nm_hstats;                      // ... and their pinned copy
     DevBuf<uint8_t> nm_stage;                                     // the host read-out's records on the device: 48 bytes each
+    // colour (map_colour.h): one 16-byte record per slot (intensity with the status in its two top bits, the tangent-plane gradient), those
+    // of revision cl_rev under the five fit parameters cl_params; rebuilt when the revision or a parameter differs
+    unsigned long long cl_rev = 0;
+    rgbd360_map_colour_params cl_params = {};
+    DevBuf<uint4> cl_layer;
+    DevBuf<unsigned long long> cl_stats;
+    PinnedBuf<unsigned long long> cl_hstats;
+    DevBuf<uint8_t> cl_stage;                                     // the host read-out's records on the device: 48 bytes each
     // free-space observation and carving (map_carve.h): one vote word per slot (through-votes low, end-votes high), taken on the table of
     // revision vt_rev; vt_rays_n: the measurements accumulated in it, vt_voted: the slots with a non-zero word; vt_spent: a carve has used it
     DevBuf<unsigned long long> vt_votes, vt_stats;

@@ -13,6 +13,8 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
     depth, rgb, count, key3, stats = gmap.raycast_sphere(rows, cols, pose)     # ... as a per-pixel first hit (csrc/map_raycast.h)
     t, key3, count, rgb, status, stats = gmap.raycast(origins, dirs)           # the first voxel along each ray of a list
     xyz, normal, curvature, status, count, key3, stats = gmap.normals(viewpoint)   # one normal per voxel (csrc/map_normals.h) ...
+    xyz, intensity, gradient, status, count, key3, stats = gmap.colours()          # one intensity and tangent gradient per voxel (csrc/map_colour.h)
+    pose, res = gmap.align_sphere_colour(rgb, depth, guess)        # coloured ICP: point-to-plane plus photometric (csrc/map_align_colour.h)
     depth, normal, rgb, count, key3, n_on_plane, stats = gmap.raycast_surface_sphere(rows, cols, pose)     # ... and the surface a ray meets
     planes, root_key3, stats = gmap.planes()       # the map segmented into planar regions (csrc/map_planes.h): a PbMap of the map ...
     found = gmap.relocalize(frame_planes)          # ... against which a lost frame is placed without a guess: found["pose"] if status 0
@@ -44,6 +46,7 @@ MAP_FULL = 3      # RGBD360_MAP_FULL
 MAP_MISMATCH = 4  # RGBD360_MAP_MISMATCH
 RAY_MISS_BOX, RAY_HIT, RAY_LEFT_BOX, RAY_T_MAX, RAY_MAX_STEPS, RAY_BAD = range(6)      # RGBD360_RAY_*
 NORMAL_NONE, NORMAL_OK, NORMAL_UNSUPPORTED, NORMAL_NONPLANAR = range(4)                # RGBD360_NORMAL_*
+COLOUR_NONE, COLOUR_OK, COLOUR_NO_NORMAL, COLOUR_NO_GRADIENT = range(4)                # RGBD360_COLOUR_*
 
 
 def _as_dict(st, skip=()):
@@ -370,6 +373,42 @@ class VoxelMap:
         xyz, normal = source_map.gicp_source(**fit)
         return self.align_cloud_gicp(xyz, guess, normals=normal, **params)
 
+    # ---- coloured ICP (rgbd360_map_align_colour_*: the same matches, point-to-plane on the map's resident normals joined with a photometric
+    #      term on its resident intensity gradients, colours(); csrc/map_align_colour.h)
+    def align_colour_params(self, max_dist=None, max_iters=None, eps=None, min_count=None, min_matches=None, lambda_geometric=None, min_support=None,
+                            max_flatness=None, min_gradient_support=None, min_spread=None):
+        """align_plane_params' defaults, lambda_geometric = 0.968, min_gradient_support = 4 and min_spread = 0.01, with the given fields
+        replaced.  A lambda_geometric outside [0, 1] and supports outside their ranges raise here."""
+        if lambda_geometric is not None and not 0.0 <= float(lambda_geometric) <= 1.0:
+            raise Rgbd360Error("VoxelMap.align_colour_params: lambda_geometric must lie in [0, 1]")
+        if min_support is not None and not 1 <= int(min_support) <= 27:
+            raise Rgbd360Error("VoxelMap.align_colour_params: min_support must lie in 1 .. 27")
+        if min_gradient_support is not None and not 1 <= int(min_gradient_support) <= 26:
+            raise Rgbd360Error("VoxelMap.align_colour_params: min_gradient_support must lie in 1 .. 26")
+        return self._params(_lib.MapAlignColourParams, self._L.rgbd360_map_default_align_colour_params, max_dist=max_dist, max_iters=max_iters, eps=eps,
+                            min_count=min_count, min_matches=min_matches, lambda_geometric=lambda_geometric, min_support=min_support,
+                            max_flatness=max_flatness, min_gradient_support=min_gradient_support, min_spread=min_spread)
+
+    def align_cloud_colour(self, xyz, rgb3, guess, **params):
+        """Coloured ICP of the cloud xyz (n x 3 float32 in the frame's coordinates) with its colours rgb3 (n x 3 uint8, required) against the
+        map from `guess`: align_cloud's matches, the point-to-plane residual along the matched voxel's resident normal weighted
+        lambda_geometric, and the difference between the map's intensity, carried along its tangent-plane gradient to the point, and the
+        point's own, weighted 1 - lambda_geometric.  Returns (pose 4x4, result dict: align_cloud's fields -- fitness is the mean joint cost
+        -- plus n_no_normal, n_no_gradient, rms_geometric and rms_colour).  The map, which must have been fed with colours, is not changed."""
+        if rgb3 is None:
+            raise Rgbd360Error("VoxelMap.align_cloud_colour: the cloud's colours are required")
+        args, keep = self._cloud_args("align_cloud_colour", xyz, rgb3)
+        p = self.align_colour_params(**params)
+        return self._align(self._L.rgbd360_map_align_colour_cloud, _lib.MapAlignColourResult, p, args, guess)
+
+    def align_sphere_colour(self, rgb, depth, guess, convention: int = 0, **params):
+        """The same for the sphere frame (rgb, depth) as insert_sphere takes it; rgb is required."""
+        if rgb is None:
+            raise Rgbd360Error("VoxelMap.align_sphere_colour: the frame's colour image is required")
+        args, keep = self._sphere_args("align_sphere_colour", rgb, depth, convention)
+        p = self.align_colour_params(**params)
+        return self._align(self._L.rgbd360_map_align_colour_sphere, _lib.MapAlignColourResult, p, args, guess)
+
     def align_trace(self):
         """One record per step of the last align call of either kind: (n, sum_sq, update[6]) (rgbd360_map_align_eval, the diagnostics header)."""
         n = C.c_int()
@@ -618,6 +657,39 @@ class VoxelMap:
         if got != n:
             raise Rgbd360Error(f"rgbd360_map_normals failed ({got}): {self._L.rgbd360_map_last_error(self._h).decode()}")
         return xyz, normal, curvature, status, count, key3, _as_dict(st)
+
+    # ---- colour (rgbd360_map_colours: one intensity per voxel and its gradient on the voxel's tangent plane, resident next to the table;
+    #      csrc/map_colour.h)
+    def colour_params(self, min_count=None, min_support=None, max_flatness=None, min_gradient_support=None, min_spread=None):
+        """The defaults (min_count 1, min_support 5, max_flatness 0.05, min_gradient_support 4, min_spread 0.01) with the given fields
+        replaced."""
+        return self._params(_lib.MapColourParams, self._L.rgbd360_map_default_colour_params, min_count=min_count, min_support=min_support,
+                            max_flatness=max_flatness, min_gradient_support=min_gradient_support, min_spread=min_spread)
+
+    def colours(self, max_out=None, **params):
+        """One record per voxel, ordered by (i_z, i_y, i_x) as extract(): (xyz [k, 3] float32, intensity [k] float32 in [0, 1], gradient
+        [k, 3] float32 per metre, world coordinates, tangent to the voxel's plane, status [k] int32 = COLOUR_*, count [k] int32, key3 [k, 3]
+        int32, the statistics as a dict), k = min(len, max_out).  The gradient is zero unless the status is COLOUR_OK.  A map fed without
+        colours has zero intensities and gradients."""
+        p = self.colour_params(**params)
+        n = len(self)
+        k = n if max_out is None else min(n, int(max_out))
+        xyz, gradient, key3 = np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32), np.zeros((k, 3), np.int32)
+        intensity, status, count = np.zeros(k, np.float32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        st = _lib.MapColourStats()
+        got = self._L.rgbd360_map_colours(self._handle(), C.byref(p), k, _ptr(xyz), _ptr(intensity), _ptr(gradient), _ptr(status), _ptr(count), _ptr(key3),
+                                          C.byref(st))
+        if got != n:
+            raise Rgbd360Error(f"rgbd360_map_colours failed ({got}): {self._L.rgbd360_map_last_error(self._h).decode()}")
+        return xyz, intensity, gradient, status, count, key3, _as_dict(st)
+
+    @property
+    def colour_bytes(self) -> int:
+        """Device memory of the colour layer (16 bytes per slot once a call needed it; 0 after release_colours)."""
+        return int(self._L.rgbd360_map_colour_bytes(self._handle()))
+
+    def release_colours(self):
+        self._check(self._L.rgbd360_map_release_colours(self._handle()))
 
     def _surface_params(self, params):
         names = ("min_support", "max_flatness", "max_shift", "normal_min_count")

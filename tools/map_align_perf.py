@@ -3,6 +3,7 @@ to one insert of the same frame and to a copy of its bytes.
 
     python tools/map_align_perf.py [--sizes 2048x1024,1920x320] [--reps 20] [--leaf 0.05] [--out profiles/map_align_perf.txt]
     python tools/map_align_perf.py --gicp [--rounds 3] --out profiles/map_align_gicp_perf.txt
+    python tools/map_align_perf.py --colour [--rounds 3] --out profiles/map_align_colour_perf.txt
 
 Per size (the synthetic room, uint16 depth in device memory, convention 2, the map holds the frame at a general pose, the default box;
 the alignment starts 1 cm and 3 mrad beside that pose), from HIP events in ONE run (rgbd360_map_time_align): k_vmap_icp_eval,
@@ -14,6 +15,11 @@ launches behind a converged loop return at once).
 alignment): the evaluation kernels of generalized ICP, point-to-point and point-to-plane on the same frame, map and buffers in one run,
 the solve kernel on the widest row, and a whole alignment of each method, repeated --rounds times so that the spread between rounds
 stands next to the differences between the methods.
+
+--colour reports coloured ICP instead (the map holds the frame WITH its colours): the build of the colour layer next to the build of the
+normal layer and to a bare scan of the table in the same run (rgbd360_map_time_colours, medians over --reps builds), then per round
+k_vmap_colour_eval next to k_vmap_gicp_eval on the same frame, map and buffers, the solve and a whole coloured alignment
+(rgbd360_map_time_align_colour).
 """
 import argparse
 import ctypes as C
@@ -57,6 +63,49 @@ def methods_side_by_side(say, m, d_depth, depth, W, H, beside, a):
         say("    %5d | %10.1f %6.1f %6.1f | %19.1f | %21.1f %6.1f %6.1f | %.2f" % (r, ug[0], ug[1], ug[2], ug[3], ug[4], ul[3], up[4], ug[0] / ug[2]))
 
 
+def colour_report(say, hip, reg, P, beside, a):
+    """--colour: per size the layer build (against the normal layer's build and a bare table scan) and the evaluation (against
+    k_vmap_gicp_eval), all figures from the same run."""
+    from rgbd360_amd import _lib
+    say("rgbd360_map_colours / rgbd360_map_align_colour_*: HIP events, leaf %.3f m = max_dist, default box, microseconds" % a.leaf)
+    for size in a.sizes.split(","):
+        W, H = (int(x) for x in size.split("x"))
+        rgb, depth = synth.render(synth.trajectory_pose(0, 7), W, H, 7)[:2]
+        rgb, depth = np.ascontiguousarray(rgb), np.ascontiguousarray(depth)
+        d_depth, d_rgb = C.c_void_p(), C.c_void_p()
+        assert hip.hipMalloc(C.byref(d_depth), depth.nbytes) == 0 and hip.hipMemcpy(d_depth, _ptr(depth), depth.nbytes, 1) == 0
+        assert hip.hipMalloc(C.byref(d_rgb), rgb.nbytes) == 0 and hip.hipMemcpy(d_rgb, _ptr(rgb), rgb.nbytes, 1) == 0
+        with VoxelMap(reg, a.leaf, 1 << 21) as m:
+            st = m.insert_sphere(rgb, depth, P, convention=2)
+            cp = m.colour_params()
+            build, normals, scan = (np.zeros(a.reps, np.float32) for _ in range(3))
+            cs, layer_bytes = _lib.MapColourStats(), C.c_longlong(0)
+            rc = m._L.rgbd360_map_time_colours(m._handle(), C.byref(cp), a.reps, _ptr(build), _ptr(normals), _ptr(scan), C.byref(cs), C.byref(layer_bytes))
+            assert rc == 0, (rc, m._L.rgbd360_map_last_error(m._h))
+            say("%dx%d: %d pixels, %d reach the search, %d voxels in a table of %d MiB, the colour layer %d MiB: %d gradients, %d voxels without a normal, "
+                "%d without a gradient" % (W, H, W * H, st["n_added"], st["n_voxels"], m.bytes >> 20, layer_bytes.value >> 20, cs.n_gradients, cs.n_no_normal,
+                                           cs.n_no_gradient))
+            say("    layer builds, medians of %d: k_vmap_colour_layer %.1f | k_vmap_normals %.1f | bare table scan (k_vmap_extract, centroids) %.1f | "
+                "colour / normals %.2f | colour / scan %.2f" % (a.reps, np.median(build), np.median(normals), np.median(scan),
+                                                                np.median(build) / np.median(normals), np.median(build) / np.median(scan)))
+            pose, res = m.align_sphere_colour(rgb, depth, beside, convention=2)
+            _, rg = m.align_sphere_gicp(depth, beside, convention=2)
+            say("    coloured ICP from the guess: status %d, %d steps (converged %d), %d contributing, %d dropped without a normal, %d with a zero gradient, "
+                "rms %.5f m / %.5f; generalized ICP: %d steps, %d matches" % (res["status"], res["iterations"], res["converged"], res["n_matched"],
+                                                                              res["n_no_normal"], res["n_no_gradient"], res["rms_geometric"], res["rms_colour"],
+                                                                              rg["iterations"], rg["n_matched"]))
+            pc = m.align_colour_params()
+            args = (d_rgb, W * 3, d_depth, W * depth.itemsize, 0 if depth.dtype == np.uint16 else 1, H, W, 2, _ptr(pose_to_cm(beside)))
+            say("    round | eval: colour  gicp | solve (38-word row) | whole coloured alignment | colour eval / gicp eval | slots read per searched point")
+            for r in range(a.rounds):
+                us, probes = np.zeros(4, np.float32), C.c_double(0)
+                rc = m._L.rgbd360_map_time_align_colour(m._handle(), *args, C.byref(pc), a.reps, _ptr(us), C.byref(probes))
+                assert rc == 0, (rc, m._L.rgbd360_map_last_error(m._h))
+                say("    %5d | %12.1f %5.1f | %19.1f | %24.1f | %23.2f | %.2f" % (r, us[0], us[1], us[2], us[3], us[0] / us[1], probes.value))
+        hip.hipFree(d_depth)
+        hip.hipFree(d_rgb)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="2048x1024,1920x320")
@@ -64,7 +113,8 @@ def main():
     ap.add_argument("--leaf", type=float, default=0.05)
     ap.add_argument("--out", default="")
     ap.add_argument("--gicp", action="store_true", help="the three methods side by side")
-    ap.add_argument("--rounds", type=int, default=3, help="with --gicp: repetitions of the whole comparison")
+    ap.add_argument("--colour", action="store_true", help="coloured ICP: the layer build and the evaluation next to generalized ICP's")
+    ap.add_argument("--rounds", type=int, default=3, help="with --gicp / --colour: repetitions of the whole comparison")
     a = ap.parse_args()
     lines = []
 
@@ -77,14 +127,17 @@ def main():
     hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     hip.hipFree.argtypes = [C.c_void_p]
 
-    say("rgbd360_map_align_*: HIP-event averages over %d launches, leaf %.3f m = max_dist, default box, microseconds" % (a.reps, a.leaf))
     reg = RegisterPhotoICP()
     P = general_pose()
     beside = P.copy()
     beside[:3, 3] += np.array([0.006, -0.006, 0.005], np.float32)
     c, s = np.cos(0.003), np.sin(0.003)
     beside = (np.array([[c, -s, 0, 0], [s, c, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]]) @ beside.astype(np.float64)).astype(np.float32)
-    for size in a.sizes.split(","):
+    if a.colour:
+        colour_report(say, hip, reg, P, beside, a)
+    else:
+        say("rgbd360_map_align_*: HIP-event averages over %d launches, leaf %.3f m = max_dist, default box, microseconds" % (a.reps, a.leaf))
+    for size in ([] if a.colour else a.sizes.split(",")):
         W, H = (int(x) for x in size.split("x"))
         _, depth = synth.render(synth.trajectory_pose(0, 7), W, H, 7)
         depth = np.ascontiguousarray(depth)
