@@ -1530,6 +1530,92 @@ void rgbd360_depth_model_free(rgbd360_depth_model* model);
 int  rgbd360_depth_model_info(const rgbd360_depth_model* model, int dims[6], double* bin_depth);
 int  rgbd360_depth_model_undistort(const rgbd360_depth_model* model, float* depth_m, size_t depth_step, int rows, int cols);
 
+/* ---- training the depth model against the map (csrc/depth_train.h) ---------------------------------------------------------------------
+ * The eight model files above belong to one physical rig.  This is the training half of the same CLAMS code -- DiscreteFrustum::addExample
+ * and DiscreteDepthDistortionModel::accumulate(ground_truth, measurement), OpenNI2_Grabber/third_party/CLAMS/
+ * discrete_depth_distortion_model.cpp:21-36 and 193-217 -- with the ground truth taken from the resident map: the depth image a sensor
+ * should have seen at a pose is one surface cast (rgbd360_map_raycast_surface) of the sensor's pinhole rays.  The loop CLAMS describes:
+ * map from trusted short-range data (a near box, or a short t_max), train, save the models where Calib360::loadIntrinsicCalibration reads
+ * them (Calib360.h:104-119), undistort, re-map.  A trainer has the shape of DiscreteDepthDistortionModel's constructor (:116-139):
+ * num_bins_x = width / bin_width, num_bins_y = height / bin_height, every frustum with max_dist = 10 and num_bins = ceil(10 / bin_depth)
+ * slices (CLAMS' defaults: bins of 8 x 6 pixels, bin_depth 2.0, smoothing 1), and keeps three 64-bit integer words per (frustum, slice) on
+ * the device -- count, num, den, [num_bins_y][num_bins_x][num_bins], zero after create and clear; 320 x 240 with 4 x 3 bins: under 1 MB.
+ * The sums are integers added by integer atomics: their bits do not depend on the order of the frames, the launch shape or the run.
+ * An example is a ground-truth z `gt` and a measured z `meas`, float32 metres widened to double; all arithmetic float64 + - x / floor
+ * without contraction.
+ *   1 measurement   meas is a measurement iff it is finite and > 0 (depth_type 0, uint16 millimetres: non-zero, 0.001f (float)v in float32
+ *                   as rgbd360_set_target scales it).  Otherwise the pixel counts in n_no_measurement.
+ *   2 range         meas > max_range or gt > max_range: n_out_of_range.
+ *   3 multiplier    mult = gt / meas; mult > max_mult || mult < min_mult: n_mult_rejected (addExample's comparison, in double, against the
+ *                   doubles of the float32 parameters).
+ *   4 slice         idx = min(num_bins - 1, (int)floor(meas / bin_depth)).
+ *   5 frustum       (min(v / bin_height, num_bins_y - 1), min(u / bin_width, num_bins_x - 1)) of pixel (v, u).
+ *   6 sums          count += 1; num += llrint(gt gt 1048576.0); den += llrint(gt meas 1048576.0): CLAMS' sums of gt^2 and gt meas at a
+ *                   resolution of 2^-20 m^2.  With max_range <= 16 a term is below 2^28; a call is refused (-1, nothing launched) once the
+ *                   examples so far plus rows cols reach 2^34, so no word can wrap.  n_examples.
+ * Every pixel lands in exactly one counter of rgbd360_depth_train_stats; they sum to n_pixels.
+ * Finalisation (host, float64): N = smoothing + num 2^-20, D = smoothing + den 2^-20, multiplier = (float)(N / D), or 1 when D == 0;
+ * counts = (float)(smoothing + count); the file's numerators and denominators are (float)N and (float)D.
+ * Stated differences from CLAMS: it keeps float32 running sums in pixel order (they depend on the order and saturate) and re-forms the
+ * multiplier after every example; here the sums are exact integers and the multiplier is formed once.
+ * Out of scope: continuing from a model file's float32 sums; a device-side undistort; extrinsic calibration; several GPUs inside one
+ * trainer (rgbd360_depth_trainer_add_sums is the seam). */
+typedef struct rgbd360_depth_trainer rgbd360_depth_trainer;
+typedef struct {
+    rgbd360_map_raycast_params ray;      /* the map route's surface cast: the two casts' own defaults */
+    rgbd360_map_normal_params  normal;
+    int   require_plane;                 /* map route: only hits whose plane depth was taken: 1 */
+    float min_cos_incidence;             /* map route: smallest |cos| between ray and normal, [0, 1]: 0 (off; a setting, not a measurement) */
+    float min_mult, max_mult;            /* MIN_MULT, MAX_MULT (stream_sequence/typedefs.h:6-7): 0.7, 1.3; 0 <= min_mult <= max_mult */
+    float max_range;                     /* (0, 16]: 10 */
+} rgbd360_depth_train_params;
+typedef struct {
+    long long n_pixels, n_no_measurement, n_no_hit, n_off_plane, n_grazing, n_out_of_range, n_mult_rejected, n_examples;
+} rgbd360_depth_train_stats;
+/* 0; -1 (where the source asserts): width % bin_width != 0 or height % bin_height != 0, a side outside 1 .. 16384, bin_depth not positive,
+ * smoothing < 0, more than 2^26 bins; -103 out of memory.  The trainer lives on the context's device and stream; destroy it first. */
+int  rgbd360_depth_trainer_create(rgbd360_ctx* ctx, int width, int height, int bin_width, int bin_height, double bin_depth, int smoothing,
+                                  rgbd360_depth_trainer** out);
+void rgbd360_depth_trainer_destroy(rgbd360_depth_trainer* trainer);
+const char* rgbd360_depth_trainer_last_error(rgbd360_depth_trainer* trainer);
+int  rgbd360_depth_trainer_clear(rgbd360_depth_trainer* trainer);
+void rgbd360_depth_default_train_params(const rgbd360_map* map, rgbd360_depth_train_params* p);
+/* CLAMS' accumulate(ground_truth, measurement): two images of the trainer's size and of one depth_type (0 uint16 millimetres, 1 float32
+ * metres), host memory or (on_device 1) device memory on the context's device.  A gt pixel that is 0, negative or not finite counts in
+ * n_no_hit; otherwise steps 1-6.  params NULL: the defaults (only min_mult, max_mult and max_range matter here).  stats (may be NULL) is
+ * host memory; the call waits.  -1, nothing launched: an image that is not the trainer's size, a NULL image, a row step shorter than a
+ * row, a bad depth_type, max_range outside (0, 16], min_mult negative or above max_mult, a full trainer.  rows cols == 0: 0, zero
+ * statistics, nothing launched. */
+int  rgbd360_depth_trainer_accumulate_images(rgbd360_depth_trainer* trainer, const void* gt, size_t gt_step, const void* meas, size_t meas_step,
+                                             int depth_type, int rows, int cols, int on_device, const rgbd360_depth_train_params* params,
+                                             rgbd360_depth_train_stats* stats);
+/* The ground truth cast out of the map (a map of the trainer's context; it is not written).  The ray of pixel (v, u) starts at o = the
+ * translation of sensor_pose (world <- sensor, column-major; frame pose x Calib360::Rt_[s] for a rig); in the sensor frame
+ * f = ((u - cx) / fx, (v - cy) / fy, 1) in float32, every operation rounded on its own, and d_k = (R_k0 f_x + R_k1 f_y) + R_k2 f_z, the
+ * rounding of rgbd360_map_raycast_sphere.  Because f_z = 1 the ray parameter t is the sensor-frame z: gt is the surface cast's t, bit for
+ * bit what rgbd360_map_raycast_surface returns for (o, d) under params->ray and params->normal.  Gates, in this order: a pixel without a
+ * measurement casts no ray (n_no_measurement); a miss of any status: n_no_hit; with require_plane, a hit whose plane depth was not
+ * taken: n_off_plane; with min_cos_incidence > 0, a hit without a normal or with |q| < min_cos_incidence sqrt((d_x d_x + d_y d_y) + d_z d_z),
+ * q = (n_x d_x + n_y d_y) + n_z d_z the surface step's product in double: n_grazing; then steps 2-6.  gt_out (rows x cols float32, may be
+ * NULL; device memory with on_device 1): the gt of every pixel that reached step 2, 0 elsewhere.  The coarse layer and the normal layer
+ * are built or reused exactly as the surface cast does.  Refusals: those of the image route and of the two casts' parameters, a NULL or
+ * foreign map, a pose or pinhole that is not finite, fx or fy zero, min_cos_incidence outside [0, 1].  An empty map, or rows cols == 0,
+ * returns 0 with zero statistics (and a zero gt_out) and launches nothing. */
+int  rgbd360_depth_trainer_accumulate_map(rgbd360_depth_trainer* trainer, rgbd360_map* map, const void* meas, size_t meas_step, int depth_type,
+                                          int rows, int cols, float fx, float fy, float cx, float cy, const float sensor_pose[16], int on_device,
+                                          const rgbd360_depth_train_params* params, float* gt_out, rgbd360_depth_train_stats* stats);
+/* The sums as host arrays [num_bins_y][num_bins_x][num_bins], and the sums of another trainer of the same shape added to this one (other
+ * processes, other GPUs, a checkpoint): -1 for negative words, words no trainer can hold, or a trainer that would be full. */
+int  rgbd360_depth_trainer_sums(rgbd360_depth_trainer* trainer, int64_t* count, int64_t* num, int64_t* den);
+int  rgbd360_depth_trainer_add_sums(rgbd360_depth_trainer* trainer, const int64_t* count, const int64_t* num, const int64_t* den);
+/* The model of the sums as they stand (the finalisation above; free it with rgbd360_depth_model_free), the same from host arrays without
+ * a context (-1: a shape rgbd360_depth_trainer_create refuses, a NULL pointer, a negative word), and the file of a model in the layout
+ * rgbd360_depth_model_load reads (0; 1 cannot open or write; -1 bad arguments): load followed by save reproduces a file byte for byte. */
+int  rgbd360_depth_trainer_model(rgbd360_depth_trainer* trainer, rgbd360_depth_model** out);
+int  rgbd360_depth_model_from_sums(int width, int height, int bin_width, int bin_height, double bin_depth, int smoothing, const int64_t* count,
+                                   const int64_t* num, const int64_t* den, rgbd360_depth_model** out);
+int  rgbd360_depth_model_save(const rgbd360_depth_model* model, const char* path);
+
 /* ---- pinhole single-sensor alignment ------------------------------------------------------ */
 
 /* RegisterPhotoICP::setCameraMatrix (RPI.h:254-257): fx, fy, ox, oy of the full-resolution sensor image; the pyramid

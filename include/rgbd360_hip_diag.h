@@ -239,6 +239,20 @@ int rgbd360_map_raycast_set_plain(rgbd360_map* map, int plain);
 int rgbd360_map_time_raycast(rgbd360_map* map, long long n, const float* origins_dev, const float* dirs_dev, int rows, int cols, const float pose[16],
                              const rgbd360_map_raycast_params* params, int plain, int reps, float* build_us, float* cast_us, float* scan_us,
                              rgbd360_map_raycast_stats* stats, long long* layer_bytes);
+/* How k_depth_train adds a lane's three terms (rgbd360_depth_trainer_accumulate_*, rgbd360_hip.h; csrc/depth_train.h), for every later
+ * call of this trainer: 0 plain per-lane 64-bit atomics, 1 the lanes of equal bin merged over the wave and one atomic per bin and word,
+ * 2 (the default: the fastest, profiles/depth_train_perf.txt) a per-block LDS table flushed once per touched word.  The sums are the
+ * same bits. */
+int rgbd360_depth_trainer_set_form(rgbd360_depth_trainer* trainer, int form);
+/* The map route's kernel under HIP events, one figure per repetition in microseconds (the caller takes medians): train_us[form * reps + r]
+ * one k_depth_train launch in form 0, 1, 2 with the clear of its counters over the device image meas_dev of the trainer's size, cast_us[r]
+ * one launch of the surface cast (k_vmap_raycast<.., SURFACE>; depth, normal and status planes) over the n = rows cols rays of the two
+ * device arrays, which the caller forms by the map route's definition.  stats (may be NULL): those of the last k_depth_train launch.  The
+ * trainer's sums are put back as they were; the map is not changed. */
+int rgbd360_depth_trainer_time_map(rgbd360_depth_trainer* trainer, rgbd360_map* map, const void* meas_dev, size_t meas_step, int depth_type, float fx,
+                                   float fy, float cx, float cy, const float sensor_pose[16], const rgbd360_depth_train_params* params,
+                                   const float* origins_dev, const float* dirs_dev, int reps, float* train_us, float* cast_us,
+                                   rgbd360_depth_train_stats* stats);
 /* An observation (rgbd360_map_observe_sphere, rgbd360_hip.h) under HIP events, one figure per repetition in microseconds (the caller takes
  * medians): observe_us[r] one k_vmap_observe launch over the device image with the clear of its counters, on zeroed votes (the coarse
  * layer is built before the first); carve_us[r] (may be NULL) ONE k_vmap_carve launch over the table with thresholds that no voxel meets:

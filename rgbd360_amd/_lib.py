@@ -64,6 +64,10 @@ SYMBOLS = [
     "rgbd360_graph_linearize", "rgbd360_graph_apply", "rgbd360_graph_time_kernels",
     "rgbd360_graph_set_edge_robust", "rgbd360_graph_set_edge_enabled", "rgbd360_graph_get_edge_state", "rgbd360_graph_edge_weights",
     "rgbd360_graph_default_cov_params", "rgbd360_graph_marginals", "rgbd360_graph_relative_covariances", "rgbd360_graph_time_cov_kernels",
+    "rgbd360_depth_trainer_create", "rgbd360_depth_trainer_destroy", "rgbd360_depth_trainer_last_error", "rgbd360_depth_trainer_clear",
+    "rgbd360_depth_default_train_params", "rgbd360_depth_trainer_accumulate_images", "rgbd360_depth_trainer_accumulate_map",
+    "rgbd360_depth_trainer_sums", "rgbd360_depth_trainer_add_sums", "rgbd360_depth_trainer_model", "rgbd360_depth_model_from_sums",
+    "rgbd360_depth_model_save", "rgbd360_depth_trainer_set_form", "rgbd360_depth_trainer_time_map",
 ]
 
 
@@ -211,6 +215,16 @@ class MapRaycastStats(C.Structure):     # rgbd360_map_raycast_stats
 
 class MapNormalParams(C.Structure):     # rgbd360_map_normal_params
     _fields_ = [("min_count", C.c_int), ("min_support", C.c_int), ("max_flatness", C.c_float), ("max_shift", C.c_float)]
+
+
+class DepthTrainParams(C.Structure):    # rgbd360_depth_train_params
+    _fields_ = [("ray", MapRaycastParams), ("normal", MapNormalParams), ("require_plane", C.c_int), ("min_cos_incidence", C.c_float),
+                ("min_mult", C.c_float), ("max_mult", C.c_float), ("max_range", C.c_float)]
+
+
+class DepthTrainStats(C.Structure):     # rgbd360_depth_train_stats
+    _fields_ = [(n, C.c_longlong) for n in ("n_pixels", "n_no_measurement", "n_no_hit", "n_off_plane", "n_grazing", "n_out_of_range",
+                                            "n_mult_rejected", "n_examples")]
 
 
 class MapNormalStats(C.Structure):      # rgbd360_map_normal_stats
@@ -363,6 +377,26 @@ def load() -> C.CDLL:
     L.rgbd360_depth_model_free.restype = None
     L.rgbd360_depth_model_info.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_double)]
     L.rgbd360_depth_model_undistort.argtypes = [vp, vp, C.c_size_t, i32, i32]
+    L.rgbd360_depth_model_from_sums.argtypes = [i32, i32, i32, i32, C.c_double, i32, vp, vp, vp, C.POINTER(vp)]
+    L.rgbd360_depth_model_save.argtypes = [vp, C.c_char_p]
+    L.rgbd360_depth_trainer_create.argtypes = [vp, i32, i32, i32, i32, C.c_double, i32, C.POINTER(vp)]
+    L.rgbd360_depth_trainer_destroy.argtypes = [vp]
+    L.rgbd360_depth_trainer_destroy.restype = None
+    L.rgbd360_depth_trainer_last_error.argtypes = [vp]
+    L.rgbd360_depth_trainer_last_error.restype = C.c_char_p
+    L.rgbd360_depth_trainer_clear.argtypes = [vp]
+    L.rgbd360_depth_default_train_params.argtypes = [vp, C.POINTER(DepthTrainParams)]
+    L.rgbd360_depth_default_train_params.restype = None
+    L.rgbd360_depth_trainer_accumulate_images.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, C.POINTER(DepthTrainParams),
+                                                          C.POINTER(DepthTrainStats)]
+    L.rgbd360_depth_trainer_accumulate_map.argtypes = [vp, vp, vp, C.c_size_t, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, f32p, i32,
+                                                       C.POINTER(DepthTrainParams), vp, C.POINTER(DepthTrainStats)]
+    L.rgbd360_depth_trainer_sums.argtypes = [vp, vp, vp, vp]
+    L.rgbd360_depth_trainer_add_sums.argtypes = [vp, vp, vp, vp]
+    L.rgbd360_depth_trainer_model.argtypes = [vp, C.POINTER(vp)]
+    L.rgbd360_depth_trainer_set_form.argtypes = [vp, i32]
+    L.rgbd360_depth_trainer_time_map.argtypes = [vp, vp, vp, C.c_size_t, i32, C.c_float, C.c_float, C.c_float, C.c_float, f32p,
+                                                 C.POINTER(DepthTrainParams), vp, vp, i32, vp, vp, C.POINTER(DepthTrainStats)]
     L.rgbd360_pool_sensor_planes.argtypes = [vp, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp, i32, C.POINTER(i32)]
     L.rgbd360_pool_sensor_planes.restype = i32
     L.rgbd360_debug_set_schedule.argtypes = [vp, i32, i32]

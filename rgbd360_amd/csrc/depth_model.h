@@ -23,7 +23,7 @@ namespace depthmodel {
 struct Frustum {
     double max_dist = 0, bin_depth = 0;
     int num_bins = 0;
-    std::vector<float> counts, multipliers;
+    std::vector<float> counts, numerators, denominators, multipliers;      // the file's four vectors, all kept: load then save is the same file
 };
 struct Model {
     int width = 0, height = 0, bin_width = 0, bin_height = 0, num_bins_x = 0, num_bins_y = 0;
@@ -56,19 +56,69 @@ inline int load(const char* path, Model& M) {
         M.frustums.assign((size_t)M.num_bins_x * M.num_bins_y, Frustum());
         bool ok = true;
         for (Frustum& F : M.frustums) {
-            std::vector<float> skip;
             int32_t nb;
-            ok = read_exact(f, &F.max_dist, 8) && read_exact(f, &nb, 4) && read_exact(f, &F.bin_depth, 8) && read_vec(f, F.counts) && read_vec(f, skip) &&
-                 read_vec(f, skip) && read_vec(f, F.multipliers);
+            ok = read_exact(f, &F.max_dist, 8) && read_exact(f, &nb, 4) && read_exact(f, &F.bin_depth, 8) && read_vec(f, F.counts) &&
+                 read_vec(f, F.numerators) && read_vec(f, F.denominators) && read_vec(f, F.multipliers);
             if (!ok) break;
             F.num_bins = nb;
-            ok = nb >= 1 && (int)F.counts.size() == nb && (int)F.multipliers.size() == nb && F.bin_depth > 0;
+            ok = nb >= 1 && (int)F.counts.size() == nb && (int)F.multipliers.size() == nb && F.bin_depth > 0;      // (what undistort indexes)
             if (!ok) break;
         }
         if (ok) rc = 0;
     } while (false);
     std::fclose(f);
     return rc;
+}
+// DiscreteDepthDistortionModel::serialize / DiscreteFrustum::serialize: the layout above, every vector as {4, size, 1}.  0 ok, 1 cannot
+// open or write
+inline bool write_vec(std::FILE* f, const std::vector<float>& v) {
+    const int32_t hdr[3] = {4, (int32_t)v.size(), 1};
+    return std::fwrite(hdr, 1, sizeof(hdr), f) == sizeof(hdr) && (v.empty() || std::fwrite(v.data(), 4, v.size(), f) == v.size());
+}
+inline int save(const char* path, const Model& M) {
+    std::FILE* f = std::fopen(path, "wb");
+    if (!f) return 1;
+    const int32_t a[4] = {M.width, M.height, M.bin_width, M.bin_height}, b[2] = {M.num_bins_x, M.num_bins_y};
+    bool ok = std::fputs("DiscreteDepthDistortionModel v01\n", f) >= 0 && std::fwrite(a, 1, sizeof(a), f) == sizeof(a) &&
+              std::fwrite(&M.bin_depth, 1, 8, f) == 8 && std::fwrite(b, 1, sizeof(b), f) == sizeof(b);
+    for (size_t k = 0; ok && k < M.frustums.size(); ++k) {
+        const Frustum& F = M.frustums[k];
+        const int32_t nb = F.num_bins;
+        ok = std::fwrite(&F.max_dist, 1, 8, f) == 8 && std::fwrite(&nb, 1, 4, f) == 4 && std::fwrite(&F.bin_depth, 1, 8, f) == 8 && write_vec(f, F.counts) &&
+             write_vec(f, F.numerators) && write_vec(f, F.denominators) && write_vec(f, F.multipliers);
+    }
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? 0 : 1;
+}
+// The model of a training run's integer sums (csrc/depth_train.h; include/rgbd360_hip.h, "training the depth model"): the shape of
+// DiscreteDepthDistortionModel's constructor (discrete_depth_distortion_model.cpp:116-139, DiscreteFrustum :10-19: max_dist 10, num_bins =
+// ceil(10 / bin_depth)), count / num / den [num_bins_y][num_bins_x][num_bins] with num and den in units of 2^-20 m^2.  In float64:
+// N = smoothing + num 2^-20, D = smoothing + den 2^-20, multiplier (float)(N / D) or 1 when D == 0, counts (float)(smoothing + count).
+inline int train_num_bins(double bin_depth) { return (int)std::ceil(10.0 / bin_depth); }
+inline bool from_sums(int width, int height, int bin_width, int bin_height, double bin_depth, int smoothing, const int64_t* count, const int64_t* num,
+                      const int64_t* den, Model& M) {
+    if (width < 1 || height < 1 || width > 16384 || height > 16384 || bin_width < 1 || bin_height < 1 || width % bin_width != 0 ||
+        height % bin_height != 0 || !(bin_depth > 0) || !(10.0 / bin_depth <= 4096.0) || smoothing < 0)
+        return false;
+    M.width = width; M.height = height; M.bin_width = bin_width; M.bin_height = bin_height; M.bin_depth = bin_depth;
+    M.num_bins_x = width / bin_width; M.num_bins_y = height / bin_height;
+    const int nb = train_num_bins(bin_depth);
+    M.frustums.assign((size_t)M.num_bins_x * M.num_bins_y, Frustum());
+    for (size_t k = 0; k < M.frustums.size(); ++k) {
+        Frustum& F = M.frustums[k];
+        F.max_dist = 10.0; F.bin_depth = bin_depth; F.num_bins = nb;
+        F.counts.resize((size_t)nb); F.numerators.resize((size_t)nb); F.denominators.resize((size_t)nb); F.multipliers.resize((size_t)nb);
+        for (int i = 0; i < nb; ++i) {
+            const size_t w = k * (size_t)nb + (size_t)i;
+            if (count[w] < 0 || num[w] < 0 || den[w] < 0) return false;
+            const double N = (double)smoothing + (double)num[w] * (1.0 / 1048576.0), D = (double)smoothing + (double)den[w] * (1.0 / 1048576.0);
+            F.counts[(size_t)i] = (float)((double)smoothing + (double)count[w]);
+            F.numerators[(size_t)i] = (float)N;
+            F.denominators[(size_t)i] = (float)D;
+            F.multipliers[(size_t)i] = D == 0.0 ? 1.f : (float)(N / D);
+        }
+    }
+    return true;
 }
 // DiscreteDepthDistortionModel::downsampleParams: the model of the full-resolution sensor used on images `step` times smaller
 inline bool downsample(Model& M, int step) {

@@ -1273,6 +1273,7 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
 #include "map_raycast.h"
 #include "map_carve.h"
 #include "map_planes.h"
+#include "depth_train.h"
 
 #ifdef RGBD360_HULL_DBG
 extern "C" int rgbd360_debug_hull_stats(unsigned long long* out /* [4096][8] */) {

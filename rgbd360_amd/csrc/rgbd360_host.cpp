@@ -45,6 +45,24 @@ extern "C" int rgbd360_depth_model_undistort(const rgbd360_depth_model* model, f
     if (!model || !depth_m || rows < 1 || cols < 1 || depth_step < (size_t)cols * 4) return -1;
     return depthmodel::undistort(model->m, depth_m, depth_step, rows, cols) ? 0 : -1;
 }
+// the model of a training run's sums (csrc/depth_train.h keeps them on the device; these two need no context)
+extern "C" int rgbd360_depth_model_from_sums(int width, int height, int bin_width, int bin_height, double bin_depth, int smoothing, const int64_t* count,
+                                             const int64_t* num, const int64_t* den, rgbd360_depth_model** out) {
+    if (out) *out = nullptr;
+    if (!out || !count || !num || !den) return -1;
+    try {
+        std::unique_ptr<rgbd360_depth_model> M(new rgbd360_depth_model());
+        if (!depthmodel::from_sums(width, height, bin_width, bin_height, bin_depth, smoothing, count, num, den, M->m)) return -1;
+        *out = M.release();
+        return 0;
+    } catch (const std::exception&) {
+        return -1;
+    }
+}
+extern "C" int rgbd360_depth_model_save(const rgbd360_depth_model* model, const char* path) {
+    if (!model || !path) return -1;
+    return depthmodel::save(path, model->m);
+}
 
 
 // ---------------------------------------------------------------------------------------------------------

@@ -518,12 +518,44 @@ class DepthModel:
         rc = self._L.rgbd360_depth_model_load(str(path).encode(), int(downsample), C.byref(h))
         if rc != 0:
             raise Rgbd360Error("rgbd360_depth_model_load(%s): %s" % (path, {1: "cannot open", 2: "not a model file, truncated, or bins not divisible"}.get(rc, "bad arguments")))
+        self._adopt(h)
+
+    def _adopt(self, h):
         self._h = h
         dims = (C.c_int32 * 6)()
         bd = C.c_double()
         self._L.rgbd360_depth_model_info(self._h, dims, C.byref(bd))
         self.width, self.height, self.bin_width, self.bin_height, self.num_bins_x, self.num_bins_y = [int(x) for x in dims]
         self.bin_depth = float(bd.value)
+
+    @classmethod
+    def _from_handle(cls, h):
+        """The model behind a rgbd360_depth_model* this object now owns (DepthTrainer.model)."""
+        m = cls.__new__(cls)
+        m._L = _lib.load()
+        m._adopt(h)
+        return m
+
+    @classmethod
+    def from_sums(cls, width, height, bin_width, bin_height, bin_depth, smoothing, count, num, den):
+        """rgbd360_depth_model_from_sums: the model of a training run's integer sums (DepthTrainer.sums; int64 arrays
+        [num_bins_y][num_bins_x][num_bins], num and den in units of 2^-20 m^2).  Host only."""
+        L = _lib.load()
+        nb = int(np.ceil(10.0 / bin_depth)) if bin_depth > 0 else 0
+        shape = (height // max(bin_height, 1), width // max(bin_width, 1), nb)
+        arrs = [np.ascontiguousarray(a, np.int64) for a in (count, num, den)]
+        if any(a.shape != shape for a in arrs):
+            raise Rgbd360Error("DepthModel.from_sums: count, num and den must have the shape %s" % (shape,))
+        h = C.c_void_p()
+        if L.rgbd360_depth_model_from_sums(int(width), int(height), int(bin_width), int(bin_height), float(bin_depth), int(smoothing), _ptr(arrs[0]),
+                                           _ptr(arrs[1]), _ptr(arrs[2]), C.byref(h)) != 0:
+            raise Rgbd360Error("rgbd360_depth_model_from_sums: bad shape or negative sums")
+        return cls._from_handle(h)
+
+    def save(self, path):
+        """rgbd360_depth_model_save: the file DepthModel(path, 1) and Calib360::loadIntrinsicCalibration read."""
+        if self._L.rgbd360_depth_model_save(self._h, str(path).encode()) != 0:
+            raise Rgbd360Error("rgbd360_depth_model_save(%s): cannot write" % (path,))
 
     def undistort(self, depth_m):
         """The corrected copy of a float32 depth image in metres (0 = no measurement)."""
