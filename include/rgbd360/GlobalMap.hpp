@@ -24,6 +24,8 @@
 // All match within one voxel; a guess further off goes through the map pyramid (rgbd360_map_level, rgbd360_map_align_c2f_*: the maps of
 // 2, 4, 8 .. times the voxel size are merged out of the table, exactly, and the ICP runs from the coarsest down),
 //     globalMap.alignSphereCoarseToFine(frame.sphereDepth, guess, pose)     c2fResult().levels[k]: what each level did
+// or starts from many guesses at once (rgbd360_map_align_batch_*: many clouds or guesses in lock step, each job the single call's bytes),
+//     globalMap.alignBatchCloud(clouds, jobs, poses, results); GlobalMap::bestJob(results)     examples/map_multistart.cpp
 // The map as a spherical RGB-D frame (rgbd360_map_render_*: the reference shows viewer.globalMap in a PCL window, OdometryRGBD360.cpp:242-268,
 // and aligns against keyframes, OdometryKeyFrame360.cpp): a z-buffered splat of the table into the panorama of the dense alignment,
 //     globalMap.renderSphere(rows, cols, pose, depth, rgb)     whose outputs RegisterPhotoICP::setTargetFrame takes as they are
@@ -62,6 +64,7 @@
 #include <vector>
 
 #include "RegisterPhotoICP.hpp"
+#include "../rgbd360_hip_diag.h"      // rgbd360_map_align_batch_trace (batchTrace)
 
 namespace rgbd360 {
 
@@ -186,6 +189,66 @@ class GlobalMap {
         return rc;
     }
     const rgbd360_map_align_plane_result& alignPlaneResult() const { return alignPlane_; }      // of the last alignSpherePlane / alignCloudPlane call
+
+    // Many alignments in lock step (rgbd360_map_align_batch_* / rgbd360_map_align_plane_batch_*): inputs of one form and jobs (input index,
+    // guess); per job poses[j] and results[j] are exactly what alignCloud / alignSphere (their Plane forms) return for that input from that
+    // guess, with 2 max_iters + 3 launches and one synchronisation for the whole batch.  The frames of a batch share one size and depth type.
+    // batchTrace(j): the steps of job j of the last batch;
+    // bestJob: the job of most matches (then the smaller fitness, then the smaller index) among those that ended OK with at least
+    // minMatched matches, -1 if none -- a policy for the jobs of one input from several guesses, not part of the alignment.
+    static rgbd360_map_batch_job batchJob(int input, const Mat4f& guess) {
+        rgbd360_map_batch_job j;
+        j.input = input;
+        std::copy(guess.m, guess.m + 16, j.guess);
+        return j;
+    }
+    void alignBatchCloud(const std::vector<rgbd360_map_batch_cloud>& clouds, const std::vector<rgbd360_map_batch_job>& jobs, std::vector<Mat4f>& poses,
+                         std::vector<rgbd360_map_align_result>& results, const rgbd360_map_align_params* params = nullptr) {
+        poses.resize(jobs.size());
+        results.assign(jobs.size(), rgbd360_map_align_result());
+        check(rgbd360_map_align_batch_cloud(map_, clouds.data(), (int)clouds.size(), 0, jobs.data(), (int)jobs.size(), params, posesOut(poses), results.data()),
+              "rgbd360_map_align_batch_cloud");
+    }
+    void alignBatchCloudPlane(const std::vector<rgbd360_map_batch_cloud>& clouds, const std::vector<rgbd360_map_batch_job>& jobs, std::vector<Mat4f>& poses,
+                              std::vector<rgbd360_map_align_plane_result>& results, const rgbd360_map_align_plane_params* params = nullptr) {
+        poses.resize(jobs.size());
+        results.assign(jobs.size(), rgbd360_map_align_plane_result());
+        check(rgbd360_map_align_plane_batch_cloud(map_, clouds.data(), (int)clouds.size(), 0, jobs.data(), (int)jobs.size(), params, posesOut(poses),
+                                                  results.data()),
+              "rgbd360_map_align_plane_batch_cloud");
+    }
+    void alignBatchSphere(const std::vector<ImageView>& depths, const std::vector<rgbd360_map_batch_job>& jobs, std::vector<Mat4f>& poses,
+                          std::vector<rgbd360_map_align_result>& results, int convention = 0, const rgbd360_map_align_params* params = nullptr) {
+        const std::vector<rgbd360_map_batch_frame> frames = batchFrames(depths, "GlobalMap::alignBatchSphere");
+        poses.resize(jobs.size());
+        results.assign(jobs.size(), rgbd360_map_align_result());
+        check(rgbd360_map_align_batch_sphere(map_, frames.data(), (int)frames.size(), depthType(depths[0]), depths[0].rows, depths[0].cols, convention, 0,
+                                             jobs.data(), (int)jobs.size(), params, posesOut(poses), results.data()),
+              "rgbd360_map_align_batch_sphere");
+    }
+    void alignBatchSpherePlane(const std::vector<ImageView>& depths, const std::vector<rgbd360_map_batch_job>& jobs, std::vector<Mat4f>& poses,
+                               std::vector<rgbd360_map_align_plane_result>& results, int convention = 0,
+                               const rgbd360_map_align_plane_params* params = nullptr) {
+        const std::vector<rgbd360_map_batch_frame> frames = batchFrames(depths, "GlobalMap::alignBatchSpherePlane");
+        poses.resize(jobs.size());
+        results.assign(jobs.size(), rgbd360_map_align_plane_result());
+        check(rgbd360_map_align_plane_batch_sphere(map_, frames.data(), (int)frames.size(), depthType(depths[0]), depths[0].rows, depths[0].cols, convention,
+                                                   0, jobs.data(), (int)jobs.size(), params, posesOut(poses), results.data()),
+              "rgbd360_map_align_plane_batch_sphere");
+    }
+    std::vector<rgbd360_map_align_trace> batchTrace(int job) {
+        int n = 0;
+        check(rgbd360_map_align_batch_trace(map_, job, 0, &n, nullptr), "rgbd360_map_align_batch_trace");
+        std::vector<rgbd360_map_align_trace> trace((size_t)n);
+        check(rgbd360_map_align_batch_trace(map_, job, n, nullptr, trace.data()), "rgbd360_map_align_batch_trace");
+        return trace;
+    }
+    static int bestJob(const std::vector<rgbd360_map_align_result>& results, long long minMatched = 0) {
+        return rgbd360_map_align_best(results.data(), (int)results.size(), minMatched);
+    }
+    static int bestJob(const std::vector<rgbd360_map_align_plane_result>& results, long long minMatched = 0) {
+        return rgbd360_map_align_plane_best(results.data(), (int)results.size(), minMatched);
+    }
 
     // Generalized ICP against the map (rgbd360_map_align_gicp_*): the matches of alignSphere / alignCloud, each weighted by
     // (C_B + C_A)^-1 -- C_B from the matched voxel's resident normal, C_A from the source point's normal (`normals`: 3 n floats in the
@@ -594,6 +657,21 @@ class GlobalMap {
     static void checkImages(const ImageView& rgb, const ImageView& depth, const char* who) {
         if (depth.type == ImageView::U8C3 || (rgb.data && (rgb.type != ImageView::U8C3 || rgb.rows != depth.rows || rgb.cols != depth.cols)))
             throw std::runtime_error(std::string(who) + ": an 8UC3 colour image and a 16UC1 / 32FC1 depth image of one size");
+    }
+    // the batch entries' outputs and inputs: the poses as 16 floats each; the frames of a batch, all of the first one's size and type
+    static float* posesOut(std::vector<Mat4f>& poses) {
+        static_assert(sizeof(Mat4f) == 16 * sizeof(float), "a Mat4f is its 16 floats");
+        return poses.empty() ? nullptr : poses[0].m;
+    }
+    static std::vector<rgbd360_map_batch_frame> batchFrames(const std::vector<ImageView>& depths, const char* who) {
+        if (depths.empty()) throw std::runtime_error(std::string(who) + ": no frames");
+        std::vector<rgbd360_map_batch_frame> frames;
+        for (const ImageView& d : depths) {
+            if (d.type == ImageView::U8C3 || d.type != depths[0].type || d.rows != depths[0].rows || d.cols != depths[0].cols)
+                throw std::runtime_error(std::string(who) + ": 16UC1 / 32FC1 depth images of one size and type");
+            frames.push_back({d.data, d.step});
+        }
+        return frames;
     }
     rgbd360_map* map_ = nullptr;
     rgbd360_map_stats stats_{};

@@ -430,6 +430,57 @@ int    rgbd360_map_align_plane_sphere(rgbd360_map* map, const void* depth, size_
 int    rgbd360_map_align_plane_cloud(rgbd360_map* map, const float* xyz, long long n, const float guess[16], int on_device,
                                      const rgbd360_map_align_plane_params* params, float pose_out[16], rgbd360_map_align_plane_result* result);
 
+/* ---- many alignments against the map in lock step (csrc/map_align_batch.h) ---------------------------------------------------------
+ * The callers of the alignments above rarely come with one input and one guess: relocalisation tries a lattice of guesses because the
+ * basin of one call is about a leaf wide (max_dist <= leaf), a pose-graph correction re-refines the keyframes of a window, a rig brings
+ * eight clouds.  One call each is n synchronisations and n x (2 max_iters + 3) launches of a few workgroups.  A batch is n_inputs
+ * inputs of one form -- all clouds, or all sphere frames of one geometry (rows, cols, depth_type and convention are given once: the
+ * context holds the angle tables of one geometry) -- and n_jobs jobs, each (input index, guess[16]); one params struct holds for all.
+ * The definition is the single call: for every job j, poses_out + 16 j, results[j] (the whole struct, hessian and gradient included)
+ * and the trace (rgbd360_map_align_batch_trace, rgbd360_hip_diag.h) are byte for byte what rgbd360_map_align_cloud / _sphere
+ * (rgbd360_map_align_plane_cloud / _sphere) return on the same map for inputs[jobs[j].input] from jobs[j].guess with the same params.
+ * No job's bytes depend on which other jobs are in the batch, on their order or on n_jobs.  The map is not changed.  Statuses are per
+ * job: a job that ends early (converged, RGBD360_ILL_POSED, RGBD360_NO_VALID_PIXELS) stops, the others go on; a job on an empty input
+ * (n = 0; rows or cols = 0) has RGBD360_NO_VALID_PIXELS, its guess as its pose and a zeroed result, as the single call.  The jobs iterate
+ * in lock step: one init launch, max_iters x (evaluation over the workgroups of all jobs, solve with one workgroup per job), the final
+ * pass, one copy of all states, ONE synchronisation -- 2 max_iters + 3 launches whatever n_jobs is.  Host inputs are uploaded packed,
+ * each once however many jobs use it.
+ * Returns 0 when the batch ran (the statuses are in the results; results may be NULL).  Returns -1 with rgbd360_map_last_error set,
+ * nothing launched, uploaded or allocated and the outputs untouched, for: what the single calls refuse (of the params, of any input);
+ * n_jobs or n_inputs outside 1 .. RGBD360_MAP_BATCH_MAX; a job's input index outside 0 .. n_inputs - 1; a NULL inputs, jobs or
+ * poses_out; a batch whose jobs need more than RGBD360_MAP_BATCH_MAX_ROWS workgroups in all (a job of a cloud of n points needs
+ * ceil(n / 1024), of a frame rows x ceil(cols / 1024): the partial rows take 304 bytes each); host inputs of more than
+ * RGBD360_MAP_BATCH_MAX_UPLOAD bytes packed (each used input once, rounded up to 256 bytes).  A level of a pyramid (rgbd360_map_level) is
+ * accepted as the single calls accept it.  Out of scope: generalized and coloured ICP in batch form (the driver is written over the
+ * method, as the single loop is), a batched coarse-to-fine chain, clouds and frames mixed or frames of different geometry, parameters per
+ * job, per-point outputs, several GPUs. */
+#define RGBD360_MAP_BATCH_MAX        1024
+#define RGBD360_MAP_BATCH_MAX_ROWS   (1 << 20)
+#define RGBD360_MAP_BATCH_MAX_UPLOAD (1ull << 30)
+typedef struct { const float* xyz; long long n; } rgbd360_map_batch_cloud;              /* n points xyz[3 n] in the frame's coordinates */
+typedef struct { const void* depth; size_t depth_step; } rgbd360_map_batch_frame;       /* a depth image of the batch's geometry */
+typedef struct { int input; float guess[16]; } rgbd360_map_batch_job;                   /* column-major, world <- frame */
+/* inputs, jobs: host arrays; on_device: the xyz / depth pointers of ALL inputs are device memory.  params NULL: the defaults. */
+int    rgbd360_map_align_batch_cloud(rgbd360_map* map, const rgbd360_map_batch_cloud* inputs, int n_inputs, int on_device,
+                                     const rgbd360_map_batch_job* jobs, int n_jobs, const rgbd360_map_align_params* params, float* poses_out,
+                                     rgbd360_map_align_result* results);
+int    rgbd360_map_align_batch_sphere(rgbd360_map* map, const rgbd360_map_batch_frame* inputs, int n_inputs, int depth_type, int rows, int cols,
+                                      int convention, int on_device, const rgbd360_map_batch_job* jobs, int n_jobs,
+                                      const rgbd360_map_align_params* params, float* poses_out, rgbd360_map_align_result* results);
+int    rgbd360_map_align_plane_batch_cloud(rgbd360_map* map, const rgbd360_map_batch_cloud* inputs, int n_inputs, int on_device,
+                                           const rgbd360_map_batch_job* jobs, int n_jobs, const rgbd360_map_align_plane_params* params,
+                                           float* poses_out, rgbd360_map_align_plane_result* results);
+int    rgbd360_map_align_plane_batch_sphere(rgbd360_map* map, const rgbd360_map_batch_frame* inputs, int n_inputs, int depth_type, int rows, int cols,
+                                            int convention, int on_device, const rgbd360_map_batch_job* jobs, int n_jobs,
+                                            const rgbd360_map_align_plane_params* params, float* poses_out,
+                                            rgbd360_map_align_plane_result* results);
+/* The winner among n results, host only: eligible are the jobs with status == RGBD360_OK and n_matched >= min_matched; the winner has
+ * the largest n_matched, then the smaller fitness, then the smaller index.  -1 when none is eligible, n <= 0 or results is NULL.  This
+ * is a policy for the jobs of ONE input from several guesses -- an inlier count; across inputs of different size it says nothing -- and
+ * no part of the alignment: a caller with a better criterion reads the results itself. */
+int    rgbd360_map_align_best(const rgbd360_map_align_result* results, int n, long long min_matched);
+int    rgbd360_map_align_plane_best(const rgbd360_map_align_plane_result* results, int n, long long min_matched);
+
 /* ---- the map rendered as a spherical frame (csrc/map_render.h) -------------------------------------------------------------------
  * The reference looks at its global map in a PCL window (viewer.globalMap, OdometryRGBD360.cpp:242-268) and aligns new frames against
  * keyframes (OdometryKeyFrame360.cpp).  Here the map is turned back into what the dense alignment takes: a full-sphere RGB-D panorama

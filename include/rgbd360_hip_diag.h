@@ -116,6 +116,11 @@ int rgbd360_map_align_eval(rgbd360_map* map, const void* depth, size_t depth_ste
                            const float* xyz, long long n, const float pose[16], int on_device, const rgbd360_map_align_params* params,
                            double sums[17], long long counters[3], int32_t* key3_dev, float* d2_dev, int max_trace, int* n_trace,
                            rgbd360_map_align_trace* trace);
+/* The trace of job `job` of the map's last batch (rgbd360_map_align_batch_* / rgbd360_map_align_plane_batch_*, rgbd360_hip.h): trace
+ * (may be NULL) gets the first min(max_trace, steps) records, *n_trace (may be NULL) the number of steps; the records are those of the
+ * single call of that job.  A job on an empty input has none.  0; -1 for a job outside the last batch (none yet: every job).  After a
+ * batch the single-call trace above is empty; after a single call the batch's traces stay what they were. */
+int rgbd360_map_align_batch_trace(rgbd360_map* map, int job, int max_trace, int* n_trace, rgbd360_map_align_trace* trace);
 /* The alignment's kernels under HIP events on a sphere frame in device memory, averages over `reps` launches in microseconds:
  * avg_us[0] k_vmap_icp_eval, [1] k_vmap_icp_solve, [2] one k_vmap_insert launch of the frame into the map as it is (the map holds the
  * frame once more afterwards), [3] a device-to-device copy of the frame's depth bytes, [4] a whole alignment of params->max_iters

@@ -38,6 +38,8 @@ SYMBOLS = [
     "rgbd360_map_default_align_params", "rgbd360_map_align_sphere", "rgbd360_map_align_cloud", "rgbd360_map_align_eval", "rgbd360_map_time_align",
     "rgbd360_map_default_align_plane_params", "rgbd360_map_align_plane_sphere", "rgbd360_map_align_plane_cloud", "rgbd360_map_align_plane_eval",
     "rgbd360_map_plane_fit", "rgbd360_map_time_align_plane",
+    "rgbd360_map_align_batch_cloud", "rgbd360_map_align_batch_sphere", "rgbd360_map_align_plane_batch_cloud", "rgbd360_map_align_plane_batch_sphere",
+    "rgbd360_map_align_best", "rgbd360_map_align_plane_best", "rgbd360_map_align_batch_trace",
     "rgbd360_map_default_align_gicp_params", "rgbd360_map_align_gicp_sphere", "rgbd360_map_align_gicp_cloud", "rgbd360_map_align_gicp_eval",
     "rgbd360_map_gicp_weight", "rgbd360_map_time_align_gicp",
     "rgbd360_map_default_colour_params", "rgbd360_map_colours", "rgbd360_map_colours_dev", "rgbd360_map_colour_bytes", "rgbd360_map_release_colours",
@@ -166,6 +168,21 @@ class MapAlignColourResult(C.Structure):     # rgbd360_map_align_colour_result
 
 class MapAlignTrace(C.Structure):        # rgbd360_map_align_trace (rgbd360_hip_diag.h)
     _fields_ = [("n", C.c_longlong), ("sum_sq", C.c_double), ("update", C.c_float * 6)]
+
+
+MAP_BATCH_MAX = 1024                     # RGBD360_MAP_BATCH_MAX
+
+
+class MapBatchCloud(C.Structure):        # rgbd360_map_batch_cloud
+    _fields_ = [("xyz", C.c_void_p), ("n", C.c_longlong)]
+
+
+class MapBatchFrame(C.Structure):        # rgbd360_map_batch_frame
+    _fields_ = [("depth", C.c_void_p), ("depth_step", C.c_size_t)]
+
+
+class MapBatchJob(C.Structure):          # rgbd360_map_batch_job
+    _fields_ = [("input", C.c_int), ("guess", C.c_float * 16)]
 
 
 MAP_MAX_SHIFT = 6                        # RGBD360_MAP_MAX_SHIFT
@@ -519,6 +536,12 @@ def load() -> C.CDLL:
     L.rgbd360_map_align_plane_sphere.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, f32p, i32, C.POINTER(MapAlignPlaneParams), f32p,
                                                  C.POINTER(MapAlignPlaneResult)]
     L.rgbd360_map_align_plane_cloud.argtypes = [vp, vp, ll, f32p, i32, C.POINTER(MapAlignPlaneParams), f32p, C.POINTER(MapAlignPlaneResult)]
+    for name, pt, rt in (("rgbd360_map_align", MapAlignParams, MapAlignResult), ("rgbd360_map_align_plane", MapAlignPlaneParams, MapAlignPlaneResult)):
+        getattr(L, name + "_batch_cloud").argtypes = [vp, C.POINTER(MapBatchCloud), i32, i32, C.POINTER(MapBatchJob), i32, C.POINTER(pt), vp, C.POINTER(rt)]
+        getattr(L, name + "_batch_sphere").argtypes = [vp, C.POINTER(MapBatchFrame), i32, i32, i32, i32, i32, i32, C.POINTER(MapBatchJob), i32, C.POINTER(pt), vp,
+                                                       C.POINTER(rt)]
+        getattr(L, name + "_best").argtypes = [C.POINTER(rt), i32, ll]
+    L.rgbd360_map_align_batch_trace.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(MapAlignTrace)]
     L.rgbd360_map_align_plane_eval.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, vp, ll, f32p, i32, C.POINTER(MapAlignPlaneParams), vp, vp, vp, vp,
                                                vp, vp]
     L.rgbd360_map_plane_fit.argtypes = [vp, C.c_double, vp, vp]

@@ -188,6 +188,9 @@ __global__ void k_vmap_icp_init(LoopState<WORDS>* __restrict__ st, IcpPose guess
     if (t == 0) st->done = st->status = st->iterations = st->converged = 0;
 }
 
+// (the body behind the pose is map_align_eval_tile.h, that of k_vmap_icp_solve map_align_solve_rows.h: texts the batched kernels of
+// map_align_batch.h include too, so that a tile gives the same row and a job the same step in both; as included bodies, not as functions
+// both call, they leave these kernels' machine code what it was)
 template <int SRC>
 __global__ __launch_bounds__(kThreads) void k_vmap_icp_eval(Params P, Source src, const unsigned long long* __restrict__ table, unsigned long long mask,
                                                             unsigned long long min_count, float max_dist2, const LoopState<kIcpWords>* __restrict__ st, int final_pass,
@@ -197,58 +200,9 @@ __global__ __launch_bounds__(kThreads) void k_vmap_icp_eval(Params P, Source src
     __shared__ double s_red[kThreads / 64][kIcpWords];
 #pragma unroll
     for (int k = 0; k < 16; ++k) P.pose[k] = st->pose[k];
-
-    float x[kPerThread], y[kPerThread], z[kPerThread];
-    bool in[kPerThread];
-    long long index[kPerThread];
-    load_points<SRC>(src, x, y, z, in, index);
-
-    double acc[kIcpWords];
-#pragma unroll
-    for (int q = 0; q < kIcpWords; ++q) acc[q] = 0.0;
-    unsigned n_probes = 0;
-#pragma unroll
-    for (int k = 0; k < kPerThread; ++k) {
-        if (!in[k]) continue;
-        unsigned long long key = 0;
-        long long f[3];
-        float w[3];
-        const int cls = classify(P, x[k], y[k], z[k], key, f, w);
-        acc[17] += cls >= 1 ? 1.0 : 0.0;
-        acc[18] += cls == 1 ? 1.0 : 0.0;
-        acc[19] += cls == 2 ? 1.0 : 0.0;
-        Match<NoSupport> mt;
-        if (cls == 3) {
-            acc[21] += 1.0;
-            mt = search27<NoSupport>(table, mask, min_count, key, w, n_probes);
-        }
-        const bool kept = mt.best_key != kEmpty && mt.best <= max_dist2;
-        if (key3) store_key3(key3 + 3 * index[k], mt.best_key, kept);
-        if (d2_out) d2_out[index[k]] = mt.best;
-        if (kept) {
-            const double wx = w[0], wy = w[1], wz = w[2], ex = mt.be[0], ey = mt.be[1], ez = mt.be[2];
-            acc[0] += 1.0;
-            acc[1] += wx;
-            acc[2] += wy;
-            acc[3] += wz;
-            acc[4] += wx * wx;
-            acc[5] += wx * wy;
-            acc[6] += wx * wz;
-            acc[7] += wy * wy;
-            acc[8] += wy * wz;
-            acc[9] += wz * wz;
-            acc[10] += ex;
-            acc[11] += ey;
-            acc[12] += ez;
-            acc[13] += wy * ez - wz * ey;
-            acc[14] += wz * ex - wx * ez;
-            acc[15] += wx * ey - wy * ex;
-            acc[16] += (ex * ex + ey * ey) + ez * ez;
-        }
-    }
-    acc[20] = (double)n_probes;
-
-    block_row_sum<kIcpWords>(acc, s_red, part + block_row<SRC>() * kIcpWords);
+    const unsigned bx = blockIdx.x, by = blockIdx.y;
+    const auto part_row = [&] { return part + block_row<SRC>() * kIcpWords; };
+#include "map_align_eval_tile.h"
 }
 
 // one workgroup: the rows added in ascending order (one lane per column), then lane 0: H and g, gn::step, status and the stop test, one
@@ -259,47 +213,7 @@ __global__ __launch_bounds__(64) void k_vmap_icp_solve(LoopState<M::kWords>* __r
 #pragma clang fp contract(off)
     if (!final_pass && st->done) return;
     __shared__ double s_row[M::kWords];
-    const int t = threadIdx.x;
-    if (t < M::kWords) {         // the rows in ascending order
-        double s = 0.0;
-        for (int r = 0; r < n_rows; ++r) s += part[(size_t)r * M::kWords + t];
-        s_row[t] = s;
-        st->row[t] = s;
-    }
-    __syncthreads();
-    if (t != 0) return;
-    const long long n = (long long)s_row[M::kN];
-    if (final_pass) {
-        M::assemble(s_row, st->H, st->g);
-        if (st->status == RGBD360_OK && n < min_matches) st->status = RGBD360_NO_VALID_PIXELS;
-        st->done = 1;
-        return;
-    }
-    if (n < min_matches) {
-        st->status = RGBD360_NO_VALID_PIXELS;
-        st->done = 1;
-        return;
-    }
-    float H[36], g[6], pose[16], pose_new[16], u[6];
-    M::assemble(s_row, H, g);
-    for (int k = 0; k < 16; ++k) pose[k] = st->pose[k];
-    if (gn::step(H, g, 0.f, pose, pose_new, u) != 0) {
-        st->status = RGBD360_ILL_POSED;
-        st->done = 1;
-        return;
-    }
-    for (int k = 0; k < 16; ++k) st->pose[k] = pose_new[k];
-    rgbd360_map_align_trace rec;
-    rec.n = n;
-    rec.sum_sq = s_row[M::kSumSq];
-    for (int k = 0; k < 6; ++k) rec.update[k] = u[k];
-    trace[st->iterations] = rec;
-    st->iterations += 1;
-    const float vv = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2], ww = (u[3] * u[3] + u[4] * u[4]) + u[5] * u[5];
-    if (vv <= eps && ww <= eps) {
-        st->converged = 1;
-        st->done = 1;
-    }
+#include "map_align_solve_rows.h"
 }
 
 }  // namespace vmap
@@ -403,6 +317,23 @@ int icp_enqueue(rgbd360_map* m, const IcpJob& job, const float guess[16], int it
 template <class M>
 const IcpState<M>& icp_host_state(rgbd360_map* m) { return *reinterpret_cast<const IcpState<M>*>(m->a_host.get()); }
 
+// the result struct of an alignment from the state it ended in (also of every job of a batch, map_align_batch.h)
+template <class M>
+void icp_fill_result(const IcpState<M>& st, typename M::Result* res) {
+    const double nm = st.row[M::kN];
+    res->status = st.status;
+    res->iterations = st.iterations;
+    res->converged = st.converged;
+    res->n_valid = (long long)st.row[M::kCounters];
+    res->n_box_rejected = (long long)st.row[M::kCounters + 1];
+    res->n_out_of_range = (long long)st.row[M::kCounters + 2];
+    res->n_matched = (long long)nm;
+    res->fitness = nm > 0.0 ? st.row[M::kSumSq] / nm : 0.0;
+    memcpy(res->hessian, st.H, sizeof(res->hessian));
+    memcpy(res->gradient, st.g, sizeof(res->gradient));
+    M::fill_extra(st, res);
+}
+
 template <class M>
 int icp_run(rgbd360_map* m, const IcpJob& job, const float guess[16], float pose_out[16], typename M::Result* res);
 // an align call of method M: rgbd360_map_align_sphere / _cloud and their _plane forms
@@ -437,20 +368,7 @@ int icp_run(rgbd360_map* m, const IcpJob& job, const float guess[16], float pose
     const rgbd360_map_align_trace* tr = reinterpret_cast<const rgbd360_map_align_trace*>(m->a_host.get() + sizeof(IcpState<M>));
     m->a_trace.assign(tr, tr + st.iterations);
     memcpy(pose_out, st.pose, 16 * sizeof(float));
-    if (res) {
-        const double nm = st.row[M::kN];
-        res->status = st.status;
-        res->iterations = st.iterations;
-        res->converged = st.converged;
-        res->n_valid = (long long)st.row[M::kCounters];
-        res->n_box_rejected = (long long)st.row[M::kCounters + 1];
-        res->n_out_of_range = (long long)st.row[M::kCounters + 2];
-        res->n_matched = (long long)nm;
-        res->fitness = nm > 0.0 ? st.row[M::kSumSq] / nm : 0.0;
-        memcpy(res->hessian, st.H, sizeof(res->hessian));
-        memcpy(res->gradient, st.g, sizeof(res->gradient));
-        M::fill_extra(st, res);
-    }
+    if (res) icp_fill_result<M>(st, res);
     return st.status;
 }
 // one evaluation at `pose` (the diag entries): the sums in front of the counters, the method's counters, the per-point outputs

@@ -1264,6 +1264,7 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
 #include "gn_math.h"
 #include "map_align.h"
 #include "map_align_plane.h"
+#include "map_align_batch.h"
 #include "map_pyramid.h"
 #include "map_merge.h"
 #include "map_normals.h"

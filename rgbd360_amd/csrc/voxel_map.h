@@ -98,6 +98,11 @@ struct rgbd360_map {
     DevBuf<unsigned char> a_state;
     PinnedBuf<unsigned char> a_host;
     std::vector<rgbd360_map_align_trace> a_trace;
+    // ... and of many in lock step (map_align_batch.h): the jobs and the prefix of their workgroup counts, on the device and pinned; the
+    // traces of the last batch, one per job
+    DevBuf<unsigned char> b_desc;
+    PinnedBuf<unsigned char> b_desc_host;
+    std::vector<std::vector<rgbd360_map_align_trace>> b_trace;
     // the map rendered as a spherical frame (map_render.h, in the other translation unit through map_table.h): the two work planes, the
     // counters with their pinned copy, the host entry's outputs on the device
     DevBuf<uint32_t> r_dist;
@@ -226,19 +231,20 @@ __device__ __forceinline__ int classify(const Params& P, float x, float y, float
 
 // The source load of a thread: its N points (kPerThread unless stated; map_carve.h takes one), kThreads apart in the workgroup's tile of
 // kThreads N points, all loads first.  in[k]: slot k holds a point of the source; index[k]: its place in the per-point arrays (a place
-// inside the source where !in[k]: every load is in bounds).
+// inside the source where !in[k]: every load is in bounds).  (bx, by): the workgroup's tile and image row -- blockIdx in a launch over
+// one source (the second form below), the job's own in a launch over many (map_align_batch.h).
 template <int SRC, int N = kPerThread>
-__device__ __forceinline__ void load_points(const Source& src, float x[N], float y[N], float z[N], bool in[N], long long index[N]) {
+__device__ __forceinline__ void load_points(const Source& src, unsigned bx, unsigned by, float x[N], float y[N], float z[N], bool in[N], long long index[N]) {
 #pragma clang fp contract(off)
     const int t = threadIdx.x;
     if (SRC == 0) {
-        const int r = blockIdx.y;
+        const int r = by;
         const uint8_t* drow = (const uint8_t*)src.depth + (size_t)r * src.depth_step;
         const float sp = src.sin_phi[r], cp = src.cos_phi[r];
         float d[N], st[N], ct[N];
 #pragma unroll
         for (int k = 0; k < N; ++k) {
-            const int col = blockIdx.x * (kThreads * N) + t + kThreads * k;
+            const int col = bx * (kThreads * N) + t + kThreads * k;
             in[k] = col < src.cols;
             const int cc = in[k] ? col : src.cols - 1;
             index[k] = (long long)r * src.cols + cc;
@@ -251,7 +257,7 @@ __device__ __forceinline__ void load_points(const Source& src, float x[N], float
     } else {
 #pragma unroll
         for (int k = 0; k < N; ++k) {
-            const long long i = (long long)blockIdx.x * (kThreads * N) + t + kThreads * k;
+            const long long i = (long long)bx * (kThreads * N) + t + kThreads * k;
             in[k] = i < src.n;
             const size_t ii = in[k] ? (size_t)i : 0;
             index[k] = (long long)ii;
@@ -260,6 +266,10 @@ __device__ __forceinline__ void load_points(const Source& src, float x[N], float
             z[k] = src.xyz[3 * ii + 2];
         }
     }
+}
+template <int SRC, int N = kPerThread>
+__device__ __forceinline__ void load_points(const Source& src, float x[N], float y[N], float z[N], bool in[N], long long index[N]) {
+    load_points<SRC, N>(src, blockIdx.x, blockIdx.y, x, y, z, in, index);
 }
 
 // the slot of `key`, claimed if the key is new; -1: the key is new and no free slot lies within the probe bound

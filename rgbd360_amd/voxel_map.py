@@ -7,6 +7,8 @@ Mirror of rgbd360_map_* (include/rgbd360_hip.h, csrc/voxel_map.h): the map half 
     stats = gmap.insert_sphere(rgb, depth, currentPose, convention=0)
     pose, res = gmap.align_sphere(depth, guess, convention=0)      # point-to-point ICP of a frame against the map (csrc/map_align.h)
     pose, res = gmap.align_sphere_plane(depth, guess, convention=0)    # point-to-plane: planes fitted to the centroids (csrc/map_align_plane.h)
+    poses, results = gmap.align_batch_cloud([xyz], [(0, g) for g in guesses], method="plane")      # many clouds or guesses in lock step, each
+    best = gmap.best_job(results)                                  # job the single call's bytes (csrc/map_align_batch.h); the start of most matches
     pose, res = gmap.align_cloud_gicp(xyz, guess, normals=n)       # generalized ICP: per-match covariance weights (csrc/map_align_gicp.h)
     pose, res = gmap.align_map_gicp(other_map, guess)              # ... of another map's voxels and normals: submap against submap
     depth, rgb, count, key3, stats = gmap.render_sphere(rows, cols, pose)      # the map as a spherical RGB-D frame (csrc/map_render.h)
@@ -416,6 +418,81 @@ class VoxelMap:
         tr = (_lib.MapAlignTrace * max(n.value, 1))()
         self._check(self._L.rgbd360_map_align_eval(self._handle(), None, 0, 0, 0, 0, 0, None, 0, None, 0, None, None, None, None, None, n.value, None, tr))
         return [(int(t.n), float(t.sum_sq), np.array(t.update, np.float32)) for t in tr[:n.value]]
+
+    # ---- many alignments in lock step (rgbd360_map_align_batch_* / rgbd360_map_align_plane_batch_*; csrc/map_align_batch.h): every job is the
+    #      single call of its input from its guess, byte for byte; 2 max_iters + 3 launches and one synchronisation for the whole batch
+    def _align_batch(self, form, method, inputs, geometry, jobs, params):
+        if method not in ("point", "plane"):
+            raise Rgbd360Error("VoxelMap.align_batch_*: method must be 'point' or 'plane'")
+        plane = method == "plane"
+        p = (self.align_plane_params if plane else self.align_params)(**params)
+        jobs = list(jobs)
+        if not 1 <= len(jobs) <= _lib.MAP_BATCH_MAX or not 1 <= len(inputs) <= _lib.MAP_BATCH_MAX:
+            raise Rgbd360Error(f"VoxelMap.align_batch_{form}: 1 .. {_lib.MAP_BATCH_MAX} inputs and jobs")
+        J = (_lib.MapBatchJob * len(jobs))()
+        for k, (i, guess) in enumerate(jobs):
+            J[k].input = int(i)
+            J[k].guess[:] = pose_to_cm(guess).tolist()
+        poses = np.zeros((len(jobs), 16), np.float32)
+        res = ((_lib.MapAlignPlaneResult if plane else _lib.MapAlignResult) * len(jobs))()
+        entry = getattr(self._L, ("rgbd360_map_align_plane_batch_" if plane else "rgbd360_map_align_batch_") + form)
+        self._check(entry(self._handle(), inputs, len(inputs), *geometry, 0, J, len(jobs), C.byref(p), _ptr(poses), res))
+        out = []
+        for r in res:
+            d = _as_dict(r, skip=("hessian", "gradient"))
+            d["hessian"] = np.array(r.hessian, np.float32).reshape(6, 6).T.copy()
+            d["gradient"] = np.array(r.gradient, np.float32)
+            out.append(d)
+        return np.stack([pose_from_cm(q) for q in poses]), out
+
+    def align_batch_cloud(self, clouds, jobs, method: str = "point", **params):
+        """Many alignments of clouds against the map in lock step.  clouds: a list of n x 3 float32 arrays in their frames' coordinates;
+        jobs: a list of (index into clouds, guess 4x4); method: "point" (align_cloud) or "plane" (align_cloud_plane); params: the method's,
+        one set for all jobs.  Returns (poses [n_jobs, 4, 4], a list of result dicts): per job exactly what the single call returns.  A job
+        that ends early stops, the others go on; the map is not changed.  align_batch_trace(j) gives a job's trace, best_job a winner."""
+        xs = [np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in clouds]
+        I = (_lib.MapBatchCloud * max(len(xs), 1))()
+        for k, x in enumerate(xs):
+            I[k].xyz, I[k].n = x.ctypes.data, x.shape[0]
+        return self._align_batch("cloud", method, I if xs else [], (), jobs, params)
+
+    def align_batch_sphere(self, depths, jobs, convention: int = 0, method: str = "point", **params):
+        """The same for sphere frames: depths, a list of HxW depth images of ONE size and type (uint16 millimetres or float32 metres; rows may
+        be strided); jobs: (index into depths, guess 4x4)."""
+        ds = []
+        for depth in depths:
+            d = np.asarray(depth)
+            if d.dtype not in (np.uint16, np.float32) or d.ndim != 2:
+                raise Rgbd360Error("VoxelMap.align_batch_sphere: depth must be HxW uint16 millimetres or float32 metres")
+            if d.size and d.strides[1] != d.dtype.itemsize:
+                d = np.ascontiguousarray(d)
+            if ds and (d.shape != ds[0].shape or d.dtype != ds[0].dtype):
+                raise Rgbd360Error("VoxelMap.align_batch_sphere: the frames of a batch share one size and depth type")
+            ds.append(d)
+        I = (_lib.MapBatchFrame * max(len(ds), 1))()
+        for k, d in enumerate(ds):
+            I[k].depth, I[k].depth_step = d.ctypes.data, d.strides[0]
+        geometry = (0 if ds[0].dtype == np.uint16 else 1, ds[0].shape[0], ds[0].shape[1], int(convention)) if ds else (0, 0, 0, int(convention))
+        return self._align_batch("sphere", method, I if ds else [], geometry, jobs, params)
+
+    def align_batch_trace(self, job: int):
+        """One record per step of job `job` of the last align_batch_* call: (n, sum_sq, update[6]), as align_trace after the single call."""
+        n = C.c_int()
+        self._check(self._L.rgbd360_map_align_batch_trace(self._handle(), int(job), 0, C.byref(n), None))
+        tr = (_lib.MapAlignTrace * max(n.value, 1))()
+        self._check(self._L.rgbd360_map_align_batch_trace(self._handle(), int(job), n.value, None, tr))
+        return [(int(t.n), float(t.sum_sq), np.array(t.update, np.float32)) for t in tr[:n.value]]
+
+    def best_job(self, results, min_matched: int = 0) -> int:
+        """The winner among the result dicts of align_batch_* (rgbd360_map_align_best): status OK and n_matched >= min_matched; the largest
+        n_matched, then the smaller fitness, then the smaller index; -1 when there is none.  A policy for the jobs of ONE input from several
+        guesses (an inlier count), not part of the alignment."""
+        results = list(results)
+        plane = bool(results) and "fitness_point" in results[0]
+        R = ((_lib.MapAlignPlaneResult if plane else _lib.MapAlignResult) * max(len(results), 1))()
+        for k, r in enumerate(results):
+            R[k].status, R[k].n_matched, R[k].fitness = int(r["status"]), int(r["n_matched"]), float(r["fitness"])
+        return int((self._L.rgbd360_map_align_plane_best if plane else self._L.rgbd360_map_align_best)(R, len(results), int(min_matched)))
 
     # ---- the map pyramid and coarse-to-fine ICP (rgbd360_map_level, rgbd360_map_align_c2f_*; csrc/map_pyramid.h): level s is the map of
     #      leaf * 2^s merged out of this table by index >> s, exact; the chain aligns on levels top_shift .. 0, each from the pose before
