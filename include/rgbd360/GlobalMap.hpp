@@ -26,6 +26,8 @@
 //     globalMap.alignSphereCoarseToFine(frame.sphereDepth, guess, pose)     c2fResult().levels[k]: what each level did
 // or starts from many guesses at once (rgbd360_map_align_batch_*: many clouds or guesses in lock step, each job the single call's bytes),
 //     globalMap.alignBatchCloud(clouds, jobs, poses, results); GlobalMap::bestJob(results)     examples/map_multistart.cpp
+// The rig's extrinsics, and optionally the rig poses of a window, against the map (rgbd360_map_calibrate_rig_*),
+//     globalMap.calibrateRigDepth(depths, calib.K(), poses, extrinsics); GlobalMap::saveExtrinsics(extrinsics, dir)     examples/calibrate_extrinsics.cpp
 // The map as a spherical RGB-D frame (rgbd360_map_render_*: the reference shows viewer.globalMap in a PCL window, OdometryRGBD360.cpp:242-268,
 // and aligns against keyframes, OdometryKeyFrame360.cpp): a z-buffered splat of the table into the panorama of the dense alignment,
 //     globalMap.renderSphere(rows, cols, pose, depth, rgb)     whose outputs RegisterPhotoICP::setTargetFrame takes as they are
@@ -59,6 +61,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -248,6 +251,52 @@ class GlobalMap {
     }
     static int bestJob(const std::vector<rgbd360_map_align_plane_result>& results, long long minMatched = 0) {
         return rgbd360_map_align_plane_best(results.data(), (int)results.size(), minMatched);
+    }
+
+    // The rig's extrinsics against the map (rgbd360_map_calibrate_rig_*): clouds[k S + s] the cloud of sensor s in frame k in the sensor's
+    // coordinates, poses (K, world <- rig) and extrinsics (S, rig <- sensor: Calib360::Rt_) in/out.  One unknown per free sensor shared
+    // over all frames; with refine_poses (which needs a fixed_sensor) also one per frame: a small bundle adjustment of a keyframe window.
+    // Returns the status; rigCalibResult() and rigCalibSensors() have the final evaluation.  The map is not changed: re-map with move().
+    rgbd360_rig_calib_params rigCalibParams() const {
+        rgbd360_rig_calib_params p;
+        rgbd360_map_default_rig_calib_params(map_, &p);
+        return p;
+    }
+    int calibrateRigClouds(const std::vector<rgbd360_map_batch_cloud>& clouds, std::vector<Mat4f>& poses, std::vector<Mat4f>& extrinsics,
+                           const rgbd360_rig_calib_params* params = nullptr) {
+        if (clouds.size() != poses.size() * extrinsics.size()) throw std::runtime_error("GlobalMap::calibrateRigClouds: one cloud per frame and sensor");
+        rigSensors_.assign(extrinsics.size(), rgbd360_rig_calib_sensor());
+        const int rc = rgbd360_map_calibrate_rig_clouds(map_, clouds.data(), (int)poses.size(), (int)extrinsics.size(), 0, posesOut(poses), posesOut(extrinsics),
+                                                        params, &rigCalib_, rigSensors_.data());
+        check(rc, "rgbd360_map_calibrate_rig_clouds");
+        return rc;
+    }
+    // The same from K S pinhole depth images of one size and type (depths[k S + s]); K4 = {fx, fy, cx, cy} (Calib360::K()).
+    int calibrateRigDepth(const std::vector<ImageView>& depths, const std::array<float, 4>& K4, std::vector<Mat4f>& poses, std::vector<Mat4f>& extrinsics,
+                          const rgbd360_rig_calib_params* params = nullptr) {
+        if (depths.empty() || depths.size() != poses.size() * extrinsics.size())
+            throw std::runtime_error("GlobalMap::calibrateRigDepth: one image per frame and sensor");
+        std::vector<rgbd360_map_batch_frame> in(depths.size());
+        for (size_t k = 0; k < depths.size(); ++k) {
+            if (depths[k].rows != depths[0].rows || depths[k].cols != depths[0].cols || depths[k].type != depths[0].type)
+                throw std::runtime_error("GlobalMap::calibrateRigDepth: the images of a call share one size and depth type");
+            in[k].depth = depths[k].data;
+            in[k].depth_step = depths[k].step;
+        }
+        rigSensors_.assign(extrinsics.size(), rgbd360_rig_calib_sensor());
+        const int rc = rgbd360_map_calibrate_rig_depth(map_, in.data(), depthType(depths[0]), depths[0].rows, depths[0].cols, K4[0], K4[1], K4[2], K4[3],
+                                                       (int)poses.size(), (int)extrinsics.size(), 0, posesOut(poses), posesOut(extrinsics), params, &rigCalib_,
+                                                       rigSensors_.data());
+        check(rc, "rgbd360_map_calibrate_rig_depth");
+        return rc;
+    }
+    const rgbd360_rig_calib_result& rigCalibResult() const { return rigCalib_; }
+    const std::vector<rgbd360_rig_calib_sensor>& rigCalibSensors() const { return rigSensors_; }
+    // Rt_01.txt .. in `dir`, where Calib360::loadExtrinsicCalibration reads them
+    static bool saveExtrinsics(const std::vector<Mat4f>& extrinsics, const std::string& dir) {
+        std::vector<float> flat(16 * extrinsics.size());
+        for (size_t s = 0; s < extrinsics.size(); ++s) std::copy(extrinsics[s].m, extrinsics[s].m + 16, flat.begin() + 16 * s);
+        return rgbd360_rig_save_extrinsics(flat.data(), (int)extrinsics.size(), dir.c_str()) == 0;
     }
 
     // Generalized ICP against the map (rgbd360_map_align_gicp_*): the matches of alignSphere / alignCloud, each weighted by
@@ -689,6 +738,8 @@ class GlobalMap {
     rgbd360_map_observe_stats observe_{};
     rgbd360_map_carve_stats carve_{};
     rgbd360_map_merge_stats merge_{};
+    rgbd360_rig_calib_result rigCalib_{};
+    std::vector<rgbd360_rig_calib_sensor> rigSensors_;
     long long onPlane_ = 0;
 };
 

@@ -481,6 +481,80 @@ int    rgbd360_map_align_plane_batch_sphere(rgbd360_map* map, const rgbd360_map_
 int    rgbd360_map_align_best(const rgbd360_map_align_result* results, int n, long long min_matched);
 int    rgbd360_map_align_plane_best(const rgbd360_map_align_plane_result* results, int n, long long min_matched);
 
+/* ---- the rig's extrinsics against the map (csrc/rig_calib.h) ------------------------------------------------------------------------
+ * Calib360::loadExtrinsicCalibration (Calib360.h:122-131) reads Rt_01.txt .. Rt_08.txt, the rig <- sensor poses that
+ * rgbd360_rig_create takes and every rig pose is multiplied by.  This call produces them from what is resident: a map built from posed
+ * frames, the point-to-plane evaluation against it and the lock-step batch above.  With refine_poses the same call is a small bundle
+ * adjustment of a keyframe window against the map.  The reference's own method (Calibrator::CalibrateRotation / CalibrateTranslation
+ * from matched planes of adjacent sensors) is not restated.
+ * Inputs: K = n_frames frames and S = n_sensors sensors, 1 <= S <= RGBD360_RIG_CALIB_MAX_SENSORS, K S <= RGBD360_MAP_BATCH_MAX; the
+ *   bounds RGBD360_MAP_BATCH_MAX_ROWS / _MAX_UPLOAD apply to the K S inputs as to a batch.  inputs[k S + s] is the cloud of sensor s in
+ *   frame k in the sensor's coordinates (n = 0: the sensor has no data in that frame).  poses[16 K]: world <- rig; extrinsics[16 S]:
+ *   rig <- sensor; column-major float32, both in/out.
+ * Evaluation: P_ks = T_k E_s by gn_math.h's 4 x 4 product in float32, C(r, c) = ((A(r,0) B(0,c) + A(r,1) B(1,c)) + A(r,2) B(2,c)) +
+ *   A(r,3) B(3,c).  Input (k, s) is evaluated at P_ks by steps 1-5 of the point-to-plane definition above, bit for bit (the batch's
+ *   evaluation launch, unchanged).  Its partial rows added in ascending order give, in float64, n_ks, A_ks (6 x 6, from the 21 upper-
+ *   triangle sums), b_ks (sum J r) and sum r r, in the world-left parameterisation P <- pseudo_exp(xi) P.  An input with
+ *   n_ks < min_input_matches contributes nothing; n_inputs_used counts the others.
+ * Unknowns: epsilon_s per free sensor, E_s <- pseudo_exp(epsilon_s) E_s; with refine_poses delta_k per frame, T_k <- pseudo_exp(delta_k)
+ *   T_k.  To first order xi_ks = delta_k + Ad(T_k) epsilon_s, Ad(T) = [[R, [t]x R], [0, R]] for twists ordered (v, omega), formed in
+ *   float64 from the float32 pose.
+ * Normal equations, float64 with + - x / sqrt and no contraction, sums of products ascending from 0.0, sums over s and over k ascending
+ *   over the contributing inputs: C_ks = A_ks Ad_k, G_ks = Ad_k^T C_ks, gs_ks = Ad_k^T b_ks; F_k = sum_s A_ks, f_k = -(sum_s b_ks);
+ *   G_s = sum_k G_ks, g_s = -(sum_k gs_ks).  lambda >= 0 (default 0) replaces every diagonal entry d of F_k and of the reduced matrix
+ *   by d + lambda d; there is no adaptive damping.
+ * Solve: with refine_poses every frame with a contributing input is eliminated: L_k the Cholesky factor of F_k (column j ascending;
+ *   element (i, j), i >= j: F_ij - sum_{p < j} L_ip L_jp with p ascending; the diagonal's square root, the others divided by it),
+ *   z_k = L_k^-1 f_k and W_ks = L_k^-1 C_ks by forward substitution.  A frame without a contributing input is skipped and left untouched
+ *   (n_frames_skipped).  The reduced matrix over the F free sensors, 6 F x 6 F, lower triangle: M_ij = [same sensor] sum_k G_ks(i, j) -
+ *   sum_k (W_k,si^T W_k,sj)(i, j), rhs_i = g_s(i) - sum_k (W_k,si^T z_k)(i); the G sum first, then frame after frame the six products of
+ *   a frame summed from 0.0 and subtracted.  (Of the nearly symmetric G_ks the lower triangle is read.)  Cholesky as above, L y = rhs
+ *   and L^T epsilon = y column by column, then L_k^T delta_k = z_k - sum_s W_ks epsilon_s.  F <= 15 with a fixed sensor (90 x 90), 16
+ *   without; the packed triangle of 96 x 97 / 2 doubles lies in one workgroup's LDS.
+ *   Pivot rule, a setting: a pivot <= 1e-12 x its undamped diagonal entry (or a NaN) ends the call with RGBD360_ILL_POSED; it holds for
+ *   the frame blocks and the reduced matrix.  A free sensor without any contributing input is such a pivot.
+ *   The updates are cast to float32 and applied with gn_math.h's pseudo-exponential and 4 x 4 product; the new P_ks are the inputs' poses
+ *   of the next evaluation.
+ * Gauge: T_k -> T_k G^-1, E_s -> G E_s changes no residual.  With refine_poses a fixed_sensor in 0 .. S - 1 is required (-1 otherwise);
+ *   without it fixed_sensor may be -1: the sensors decouple, M is block diagonal and a sensor's extrinsic does not depend on which other
+ *   sensors are in the call (the stop test and the statuses are the call's).
+ * Stop and statuses: converged when v.v <= eps and omega.omega <= eps for every block's float32 update; at most plane.max_iters steps,
+ *   then one final evaluation at the returned poses, of which n_matched, cost = sum r r, fitness = cost / n_matched and the per-sensor
+ *   records are.  RGBD360_NO_VALID_PIXELS when the contributing points of all inputs are fewer than plane.min_matches.  The last iterate
+ *   is returned, as the single loops do.  The iterates need not settle: the evaluation's floor is about a hundredth of a leaf.
+ * Schedule: one init launch, max_iters x (the batched evaluation + 3 solve launches), the final pass, one copy, ONE synchronisation:
+ *   4 max_iters + 5 launches whatever K and S are.  No floating-point atomics, no inline assembly.  The map is not changed; a level of
+ *   a pyramid is accepted as the single calls accept it; callers chain coarse -> fine by calling again.
+ * The call estimates extrinsics against a map built with the OLD extrinsics: CLAMS alternates calibrate, re-map (rgbd360_map_move /
+ * _merge), repeat; the alternation is the caller's loop (examples/calibrate_extrinsics.cpp).
+ * Returns the status.  Returns -1 with rgbd360_map_last_error set, nothing launched and the outputs untouched, for: what the batch
+ * refuses; K < 1, S outside 1 .. 16, K S > RGBD360_MAP_BATCH_MAX; NULL inputs, poses or extrinsics; poses or extrinsics that are not
+ * finite; refine_poses without a fixed_sensor; fixed_sensor outside -1 .. S - 1; lambda negative or not finite; min_input_matches < 1.
+ * Out of scope: the reference's control-plane method, per-sensor intrinsics, robust weights, sphere-frame inputs, several GPUs. */
+#define RGBD360_RIG_CALIB_MAX_SENSORS 16
+typedef struct { rgbd360_map_align_plane_params plane; int refine_poses, fixed_sensor; float lambda; long long min_input_matches; } rgbd360_rig_calib_params;
+typedef struct { int status, iterations, converged, n_inputs_used, n_frames_skipped; long long n_matched; double cost, fitness; } rgbd360_rig_calib_result;
+typedef struct { long long n_matched; double cost; float hessian[36], gradient[6]; } rgbd360_rig_calib_sensor;   /* G_s and sum_k gs_ks, final evaluation, rig frame */
+/* the point-to-plane defaults; refine_poses 0, fixed_sensor -1, lambda 0, min_input_matches 6 */
+void   rgbd360_map_default_rig_calib_params(const rgbd360_map* map, rgbd360_rig_calib_params* p);
+/* inputs: a host array of K S clouds, frame-major; on_device: the xyz pointers of ALL inputs are device memory.  params NULL: the
+ * defaults.  result and sensors (S records) may be NULL. */
+int    rgbd360_map_calibrate_rig_clouds(rgbd360_map* map, const rgbd360_map_batch_cloud* inputs, int n_frames, int n_sensors, int on_device,
+                                        float* poses, float* extrinsics, const rgbd360_rig_calib_params* params, rgbd360_rig_calib_result* result,
+                                        rgbd360_rig_calib_sensor* sensors);
+/* The same from K S pinhole depth images of one geometry (depth_type 0 uint16 millimetres, z = 0.001f (float)v; 1 float32 metres), each
+ * turned into a packed cloud of rows cols points on the device by one launch over all images: the ray of pixel (v, u) is
+ * f = (((float)u - cx) / fx, ((float)v - cy) / fy, 1), the ray of rgbd360_depth_trainer_accumulate_map, every float32 operation rounded
+ * on its own, the point (z f_x, z f_y, z).  A pixel without a measurement (0; not finite, zero or negative) becomes a NaN triple, which
+ * the evaluation skips.  The call then proceeds exactly as _clouds on device memory.  Also refused: a pinhole that is not finite, fx or
+ * fy zero, a bad depth_type or image size, a NULL image, a row step shorter than a row. */
+int    rgbd360_map_calibrate_rig_depth(rgbd360_map* map, const rgbd360_map_batch_frame* depth, int depth_type, int rows, int cols, float fx, float fy,
+                                       float cx, float cy, int n_frames, int n_sensors, int on_device, float* poses, float* extrinsics,
+                                       const rgbd360_rig_calib_params* params, rgbd360_rig_calib_result* result, rgbd360_rig_calib_sensor* sensors);
+/* Rt_0N.txt, N = 1 .. n_sensors, in `dir`: four lines of four numbers, row by row, printed with %.9g (a float32 survives the round trip):
+ * the layout Calib360::loadExtrinsicCalibration reads.  Host only.  0; 1 a file could not be written; -1 bad arguments. */
+int    rgbd360_rig_save_extrinsics(const float* extrinsics, int n_sensors, const char* dir);
+
 /* ---- the map rendered as a spherical frame (csrc/map_render.h) -------------------------------------------------------------------
  * The reference looks at its global map in a PCL window (viewer.globalMap, OdometryRGBD360.cpp:242-268) and aligns new frames against
  * keyframes (OdometryKeyFrame360.cpp).  Here the map is turned back into what the dense alignment takes: a full-sphere RGB-D panorama
@@ -1609,8 +1683,8 @@ int  rgbd360_depth_model_undistort(const rgbd360_depth_model* model, float* dept
  * counts = (float)(smoothing + count); the file's numerators and denominators are (float)N and (float)D.
  * Stated differences from CLAMS: it keeps float32 running sums in pixel order (they depend on the order and saturate) and re-forms the
  * multiplier after every example; here the sums are exact integers and the multiplier is formed once.
- * Out of scope: continuing from a model file's float32 sums; a device-side undistort; extrinsic calibration; several GPUs inside one
- * trainer (rgbd360_depth_trainer_add_sums is the seam). */
+ * Out of scope: continuing from a model file's float32 sums; a device-side undistort; several GPUs inside one trainer
+ * (rgbd360_depth_trainer_add_sums is the seam).  The extrinsics of the same rig: rgbd360_map_calibrate_rig_* above. */
 typedef struct rgbd360_depth_trainer rgbd360_depth_trainer;
 typedef struct {
     rgbd360_map_raycast_params ray;      /* the map route's surface cast: the two casts' own defaults */

@@ -112,6 +112,7 @@ int rgbd360_map_time_edit(rgbd360_map* map, const uint8_t* rgb_dev, size_t rgb_s
  * rgbd360_map_align_* call of this map, one per applied step: the kept matches and sum e.e of the evaluation the step came from, and
  * the step; *n_trace (may be NULL): the number of steps. */
 typedef struct { long long n; double sum_sq; float update[6]; } rgbd360_map_align_trace;
+typedef struct { long long n; double cost; float max_vv, max_ww; } rgbd360_rig_calib_step;       /* rgbd360_rig_calib_trace below */
 int rgbd360_map_align_eval(rgbd360_map* map, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
                            const float* xyz, long long n, const float pose[16], int on_device, const rgbd360_map_align_params* params,
                            double sums[17], long long counters[3], int32_t* key3_dev, float* d2_dev, int max_trace, int* n_trace,
@@ -121,6 +122,26 @@ int rgbd360_map_align_eval(rgbd360_map* map, const void* depth, size_t depth_ste
  * single call of that job.  A job on an empty input has none.  0; -1 for a job outside the last batch (none yet: every job).  After a
  * batch the single-call trace above is empty; after a single call the batch's traces stay what they were. */
 int rgbd360_map_align_batch_trace(rgbd360_map* map, int job, int max_trace, int* n_trace, rgbd360_map_align_trace* trace);
+/* The rig calibration's solve (csrc/rig_calib.h; the definition is in rgbd360_hip.h) on given rows: rows[30 (k S + s)] the 30 sums of
+ * input (k, s) -- n, the 21 upper-triangle terms, sum J r (6), sum r r, sum e.e -- poses[16 K], extrinsics[16 S] and params (not NULL; only
+ * refine_poses, fixed_sensor, lambda, min_input_matches and plane.min_matches matter) -> one step: updates[6 (K + S)] the float32 delta_k
+ * then epsilon_s as applied (zeros where there is none), the new poses and extrinsics, the status (RGBD360_OK, RGBD360_ILL_POSED,
+ * RGBD360_NO_VALID_PIXELS; the inputs are returned unchanged unless OK).  _host is the host build of the one solve text, _dev runs the
+ * kernels of a call on the map's stream (k_rig_init, k_rig_input with each row as its input's only partial row, k_rig_frames,
+ * k_rig_solve): the same bytes.  Any output may be NULL.  0; -1 bad arguments. */
+int rgbd360_rig_calib_solve_host(const double* rows, int n_frames, int n_sensors, const float* poses, const float* extrinsics,
+                                 const rgbd360_rig_calib_params* params, float* updates, float* poses_new, float* extrinsics_new, int* status);
+int rgbd360_rig_calib_solve_dev(rgbd360_map* map, const double* rows, int n_frames, int n_sensors, const float* poses, const float* extrinsics,
+                                const rgbd360_rig_calib_params* params, float* updates, float* poses_new, float* extrinsics_new, int* status);
+/* The solve launches of one rig-calibration step under HIP events on the given rows with their gradients zeroed (the updates are then
+ * exactly zero, the poses stay and every repetition solves the same system), averages over `reps` launch chains in microseconds:
+ * avg_us[0] k_rig_init alone, [1] init + k_rig_input, [2] + k_rig_frames, [3] + k_rig_solve; a kernel's time is the difference of two
+ * chains.  0; -1 bad arguments. */
+int rgbd360_rig_calib_time_solve(rgbd360_map* map, const double* rows, int n_frames, int n_sensors, const float* poses, const float* extrinsics,
+                                 const rgbd360_rig_calib_params* params, int reps, float avg_us[4]);
+/* The trace of the map's last rig calibration, one record per applied step: the contributing points and sum r r of the evaluation the
+ * step was solved from, the largest v.v and omega.omega over the blocks' float32 updates.  As rgbd360_map_align_batch_trace. */
+int rgbd360_rig_calib_trace(rgbd360_map* map, int max_trace, int* n_trace, rgbd360_rig_calib_step* trace);
 /* The alignment's kernels under HIP events on a sphere frame in device memory, averages over `reps` launches in microseconds:
  * avg_us[0] k_vmap_icp_eval, [1] k_vmap_icp_solve, [2] one k_vmap_insert launch of the frame into the map as it is (the map holds the
  * frame once more afterwards), [3] a device-to-device copy of the frame's depth bytes, [4] a whole alignment of params->max_iters

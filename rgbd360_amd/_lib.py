@@ -40,6 +40,8 @@ SYMBOLS = [
     "rgbd360_map_plane_fit", "rgbd360_map_time_align_plane",
     "rgbd360_map_align_batch_cloud", "rgbd360_map_align_batch_sphere", "rgbd360_map_align_plane_batch_cloud", "rgbd360_map_align_plane_batch_sphere",
     "rgbd360_map_align_best", "rgbd360_map_align_plane_best", "rgbd360_map_align_batch_trace",
+    "rgbd360_map_default_rig_calib_params", "rgbd360_map_calibrate_rig_clouds", "rgbd360_map_calibrate_rig_depth", "rgbd360_rig_save_extrinsics",
+    "rgbd360_rig_calib_solve_host", "rgbd360_rig_calib_solve_dev", "rgbd360_rig_calib_trace", "rgbd360_rig_calib_time_solve",
     "rgbd360_map_default_align_gicp_params", "rgbd360_map_align_gicp_sphere", "rgbd360_map_align_gicp_cloud", "rgbd360_map_align_gicp_eval",
     "rgbd360_map_gicp_weight", "rgbd360_map_time_align_gicp",
     "rgbd360_map_default_colour_params", "rgbd360_map_colours", "rgbd360_map_colours_dev", "rgbd360_map_colour_bytes", "rgbd360_map_release_colours",
@@ -183,6 +185,27 @@ class MapBatchFrame(C.Structure):        # rgbd360_map_batch_frame
 
 class MapBatchJob(C.Structure):          # rgbd360_map_batch_job
     _fields_ = [("input", C.c_int), ("guess", C.c_float * 16)]
+
+
+RIG_CALIB_MAX_SENSORS = 16               # RGBD360_RIG_CALIB_MAX_SENSORS
+
+
+class RigCalibParams(C.Structure):       # rgbd360_rig_calib_params
+    _fields_ = [("plane", MapAlignPlaneParams), ("refine_poses", C.c_int), ("fixed_sensor", C.c_int), ("lambda_", C.c_float),
+                ("min_input_matches", C.c_longlong)]
+
+
+class RigCalibResult(C.Structure):       # rgbd360_rig_calib_result
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("converged", C.c_int), ("n_inputs_used", C.c_int), ("n_frames_skipped", C.c_int),
+                ("n_matched", C.c_longlong), ("cost", C.c_double), ("fitness", C.c_double)]
+
+
+class RigCalibSensor(C.Structure):       # rgbd360_rig_calib_sensor
+    _fields_ = [("n_matched", C.c_longlong), ("cost", C.c_double), ("hessian", C.c_float * 36), ("gradient", C.c_float * 6)]
+
+
+class RigCalibStep(C.Structure):         # rgbd360_rig_calib_step (rgbd360_hip_diag.h)
+    _fields_ = [("n", C.c_longlong), ("cost", C.c_double), ("max_vv", C.c_float), ("max_ww", C.c_float)]
 
 
 MAP_MAX_SHIFT = 6                        # RGBD360_MAP_MAX_SHIFT
@@ -542,6 +565,16 @@ def load() -> C.CDLL:
                                                        C.POINTER(rt)]
         getattr(L, name + "_best").argtypes = [C.POINTER(rt), i32, ll]
     L.rgbd360_map_align_batch_trace.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(MapAlignTrace)]
+    L.rgbd360_map_default_rig_calib_params.argtypes = [vp, C.POINTER(RigCalibParams)]
+    L.rgbd360_map_default_rig_calib_params.restype = None
+    rig_tail = [i32, i32, i32, vp, vp, C.POINTER(RigCalibParams), C.POINTER(RigCalibResult), C.POINTER(RigCalibSensor)]
+    L.rgbd360_map_calibrate_rig_clouds.argtypes = [vp, C.POINTER(MapBatchCloud)] + rig_tail
+    L.rgbd360_map_calibrate_rig_depth.argtypes = [vp, C.POINTER(MapBatchFrame), i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float] + rig_tail
+    L.rgbd360_rig_save_extrinsics.argtypes = [vp, i32, C.c_char_p]
+    L.rgbd360_rig_calib_solve_host.argtypes = [vp, i32, i32, vp, vp, C.POINTER(RigCalibParams), vp, vp, vp, C.POINTER(i32)]
+    L.rgbd360_rig_calib_solve_dev.argtypes = [vp] + L.rgbd360_rig_calib_solve_host.argtypes
+    L.rgbd360_rig_calib_trace.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(RigCalibStep)]
+    L.rgbd360_rig_calib_time_solve.argtypes = [vp, vp, i32, i32, vp, vp, C.POINTER(RigCalibParams), i32, vp]
     L.rgbd360_map_align_plane_eval.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32, vp, ll, f32p, i32, C.POINTER(MapAlignPlaneParams), vp, vp, vp, vp,
                                                vp, vp]
     L.rgbd360_map_plane_fit.argtypes = [vp, C.c_double, vp, vp]

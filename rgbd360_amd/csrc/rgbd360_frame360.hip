@@ -1265,6 +1265,7 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
 #include "map_align.h"
 #include "map_align_plane.h"
 #include "map_align_batch.h"
+#include "rig_calib.h"
 #include "map_pyramid.h"
 #include "map_merge.h"
 #include "map_normals.h"

@@ -103,6 +103,12 @@ struct rgbd360_map {
     DevBuf<unsigned char> b_desc;
     PinnedBuf<unsigned char> b_desc_host;
     std::vector<std::vector<rgbd360_map_align_trace>> b_trace;
+    // ... and of a rig calibration (rig_calib.h): the block that is copied back with its pinned copy, the work records, the clouds and
+    // image descriptors of a _depth call, the trace of the last call
+    DevBuf<unsigned char> c_out, c_work, c_img;
+    PinnedBuf<unsigned char> c_host, c_img_host;
+    DevBuf<float> c_cloud;
+    std::vector<rgbd360_rig_calib_step> c_trace;
     // the map rendered as a spherical frame (map_render.h, in the other translation unit through map_table.h): the two work planes, the
     // counters with their pinned copy, the host entry's outputs on the device
     DevBuf<uint32_t> r_dist;

@@ -494,6 +494,76 @@ class VoxelMap:
             R[k].status, R[k].n_matched, R[k].fitness = int(r["status"]), int(r["n_matched"]), float(r["fitness"])
         return int((self._L.rgbd360_map_align_plane_best if plane else self._L.rgbd360_map_align_best)(R, len(results), int(min_matched)))
 
+    # ---- the rig's extrinsics against the map (rgbd360_map_calibrate_rig_*; csrc/rig_calib.h): K frames x S sensors, one unknown per free
+    #      sensor shared over all frames and, with refine_poses, one per frame; 4 max_iters + 5 launches and one synchronisation
+    def rig_calib_params(self, refine_poses=None, fixed_sensor=None, lambda_=None, min_input_matches=None, **plane):
+        """The defaults (the point-to-plane ones, refine_poses 0, fixed_sensor -1, lambda 0, min_input_matches 6) with the given fields replaced."""
+        p = _lib.RigCalibParams()
+        self._L.rgbd360_map_default_rig_calib_params(self._handle(), C.byref(p))
+        p.plane = self.align_plane_params(**plane)
+        for name, value in (("refine_poses", refine_poses), ("fixed_sensor", fixed_sensor), ("lambda_", lambda_), ("min_input_matches", min_input_matches)):
+            if value is not None:
+                setattr(p, name, value)
+        return p
+
+    def _calibrate_rig(self, entry, head, poses, extrinsics, params):
+        T = np.stack([pose_to_cm(P) for P in poses]).astype(np.float32)
+        E = np.stack([pose_to_cm(P) for P in extrinsics]).astype(np.float32)
+        K, S = len(T), len(E)
+        p = self.rig_calib_params(**params)
+        res = _lib.RigCalibResult()
+        sen = (_lib.RigCalibSensor * S)()
+        self._check(entry(self._handle(), *head, K, S, 0, _ptr(T), _ptr(E), C.byref(p), C.byref(res), sen))
+        sensors = []
+        for r in sen:
+            sensors.append({"n_matched": int(r.n_matched), "cost": float(r.cost), "hessian": np.array(r.hessian, np.float32).reshape(6, 6).T.copy(),
+                            "gradient": np.array(r.gradient, np.float32)})
+        return np.stack([pose_from_cm(q) for q in T]), np.stack([pose_from_cm(q) for q in E]), dict(_as_dict(res), sensors=sensors)
+
+    def calibrate_rig_clouds(self, clouds, poses, extrinsics, **params):
+        """The rig's extrinsics against the map.  clouds: K x S arrays (n x 3 float32, the cloud of sensor s in frame k in the sensor's
+        coordinates; an empty array: no data), as a list of K lists of S or a flat frame-major list; poses: K world <- rig 4x4; extrinsics: S
+        rig <- sensor 4x4; params: rig_calib_params' (refine_poses needs a fixed_sensor).  Returns (poses, extrinsics, result dict with the
+        per-sensor records under "sensors").  The map is not changed."""
+        flat = [x for row in clouds for x in row] if len(clouds) and isinstance(clouds[0], (list, tuple)) else list(clouds)
+        if len(flat) != len(poses) * len(extrinsics):
+            raise Rgbd360Error("VoxelMap.calibrate_rig_clouds: one cloud per frame and sensor")
+        xs = [np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in flat]
+        I = (_lib.MapBatchCloud * max(len(xs), 1))()
+        for k, x in enumerate(xs):
+            I[k].xyz, I[k].n = x.ctypes.data, x.shape[0]
+        return self._calibrate_rig(self._L.rgbd360_map_calibrate_rig_clouds, (I,), poses, extrinsics, params)
+
+    def calibrate_rig_depth(self, depths, K4, poses, extrinsics, **params):
+        """The same from K x S pinhole depth images of ONE size and type (uint16 millimetres or float32 metres; rows may be strided), flat
+        frame-major; K4 = (fx, fy, cx, cy)."""
+        ds = []
+        for depth in depths:
+            d = np.asarray(depth)
+            if d.dtype not in (np.uint16, np.float32) or d.ndim != 2:
+                raise Rgbd360Error("VoxelMap.calibrate_rig_depth: depth must be HxW uint16 millimetres or float32 metres")
+            if d.size and d.strides[1] != d.dtype.itemsize:
+                d = np.ascontiguousarray(d)
+            if ds and (d.shape != ds[0].shape or d.dtype != ds[0].dtype):
+                raise Rgbd360Error("VoxelMap.calibrate_rig_depth: the images of a call share one size and depth type")
+            ds.append(d)
+        if not ds or len(ds) != len(poses) * len(extrinsics):
+            raise Rgbd360Error("VoxelMap.calibrate_rig_depth: one image per frame and sensor")
+        I = (_lib.MapBatchFrame * len(ds))()
+        for k, d in enumerate(ds):
+            I[k].depth, I[k].depth_step = d.ctypes.data, d.strides[0]
+        fx, fy, cx, cy = (float(v) for v in K4)
+        head = (I, 0 if ds[0].dtype == np.uint16 else 1, ds[0].shape[0], ds[0].shape[1], fx, fy, cx, cy)
+        return self._calibrate_rig(self._L.rgbd360_map_calibrate_rig_depth, head, poses, extrinsics, params)
+
+    def rig_calib_trace(self):
+        """One record per step of the last calibrate_rig_* call: (n, cost, largest v.v, largest w.w over the blocks' updates)."""
+        n = C.c_int()
+        self._check(self._L.rgbd360_rig_calib_trace(self._handle(), 0, C.byref(n), None))
+        tr = (_lib.RigCalibStep * max(n.value, 1))()
+        self._check(self._L.rgbd360_rig_calib_trace(self._handle(), n.value, None, tr))
+        return [(int(t.n), float(t.cost), float(t.max_vv), float(t.max_ww)) for t in tr[:n.value]]
+
     # ---- the map pyramid and coarse-to-fine ICP (rgbd360_map_level, rgbd360_map_align_c2f_*; csrc/map_pyramid.h): level s is the map of
     #      leaf * 2^s merged out of this table by index >> s, exact; the chain aligns on levels top_shift .. 0, each from the pose before
     def level(self, shift: int) -> "VoxelMap":
