@@ -1,7 +1,9 @@
 // calibrate_depth.cpp -- the CLAMS loop on a recorded sequence of the 8-sensor rig: map from trusted short-range data, train the eight
 // sensors' depth-distortion models against that map, save them where Calib360::loadIntrinsicCalibration reads them (Calib360.h:104-119).
 // The training half of clams::DiscreteDepthDistortionModel (OpenNI2_Grabber/third_party/CLAMS/discrete_depth_distortion_model.cpp:21-36,
-// 193-217) on the device: include/rgbd360/DepthTrainer.hpp, rgbd360_depth_trainer_* (rgbd360_hip.h, "training the depth model").
+// 193-217) on the device: include/rgbd360/DepthTrainer.hpp, rgbd360_depth_trainer_* (rgbd360_hip.h, "training the depth model").  The
+// models are then applied and judged on the device too (rgbd360_depth_models_*, "applying the depth models on the device"): every fifth
+// frame is held out of the training, and its raw against corrected RMS and bias to the map are printed.
 //
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/calibrate_depth.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o calibrate_depth
@@ -102,20 +104,35 @@ int main(int argc, char** argv) {
         // 2 train: all eight sensors of every frame against the map (4 x 3-pixel bins on the rig's half-size images: the files' 8 x 6)
         DepthTrainerRig rig(align, cols, rows, 4, 3, bin_depth, 1);
         rgbd360_depth_train_stats total{};
-        for (int k = 0; k < n_frames; ++k) rig.accumulate(*frames[(size_t)k], poses[(size_t)k], map, nullptr, &total);
+        //   every fifth frame is held out of the training and judges the models in step 3
+        const auto held_out = [&](int k) { return n_frames >= 5 && k % 5 == 4; };
+        for (int k = 0; k < n_frames; ++k)
+            if (!held_out(k)) rig.accumulate(*frames[(size_t)k], poses[(size_t)k], map, nullptr, &total);
         std::printf("pixels %lld: no measurement %lld, no hit %lld, off plane %lld, grazing %lld, out of range %lld, multiplier rejected %lld, examples %lld\n",
                     total.n_pixels, total.n_no_measurement, total.n_no_hit, total.n_off_plane, total.n_grazing, total.n_out_of_range, total.n_mult_rejected,
                     total.n_examples);
         if (total.n_examples == 0) return 4;
 
-        // 3 the eight files, in the full-resolution form Calib360::loadIntrinsicCalibration halves; then undistort and re-map with them
+        // 3 the eight files, in the full-resolution form Calib360::loadIntrinsicCalibration halves; then undistort with them
         rig.saveIntrinsicCalibration(out_dir);
         if (!calib.loadIntrinsicCalibration(out_dir)) {
             std::fprintf(stderr, "cannot read back the models written to %s\n", out_dir.c_str());
             return 3;
         }
-        frames[0]->undistort();
         std::printf("wrote %s/distortion_model1..8\n", out_dir.c_str());
+        //   on the device: the models resident (DepthModels), the first frame's eight images corrected in one launch, and the held-out
+        //   frames' raw against corrected error to the map (rgbd360_depth_evaluate_map), sensor by sensor
+        DepthModels models(align, calib);
+        frames[0]->undistortOnDevice(align.context(), models.handle());
+        rgbd360_depth_eval_sums sums{};
+        for (int k = 0; k < n_frames; ++k) {
+            if (n_frames >= 5 && !held_out(k)) continue;
+            for (int s = 0; s < 8; ++s)
+                DepthModels::add(sums, models.evaluate(map, s, frames[(size_t)k]->sensorDepth(s), K, DepthTrainerRig::multiply(poses[(size_t)k], calib.Rt_[(size_t)s])));
+        }
+        std::printf("%s frames against the map, %lld examples: RMS %.4f m raw, %.4f m corrected; bias %+.4f m raw, %+.4f m corrected\n",
+                    n_frames >= 5 ? "held-out" : "training", sums.n, DepthModels::rms(sums.raw_ee, sums.n), DepthModels::rms(sums.cor_ee, sums.n),
+                    DepthModels::bias(sums.raw_e, sums.n), DepthModels::bias(sums.cor_e, sums.n));
     } catch (const std::exception& e) {
         std::fprintf(stderr, "%s\n", e.what());
         return 3;

@@ -161,8 +161,98 @@ class DepthTrainerRig {
         return C;
     }
 
+    // the models as they stand, for DepthModels below
+    std::vector<std::shared_ptr<rgbd360_depth_model>> models() const {
+        std::vector<std::shared_ptr<rgbd360_depth_model>> out;
+        for (const auto& t : trainers_) out.push_back(t->model());
+        return out;
+    }
+
    private:
     std::array<std::unique_ptr<DepthTrainer>, 8> trainers_;
+};
+
+// The depth models of a rig's sensors resident on the device (rgbd360_depth_models_*, rgbd360_hip.h, "applying the depth models on the
+// device"): the step "undistort" of CLAMS' loop without leaving the device.  A null model means identity.  The set lives on `align`'s
+// context: destroy it before the context.
+class DepthModels {
+   public:
+    DepthModels(RegisterPhotoICP& align, const std::vector<std::shared_ptr<rgbd360_depth_model>>& models) : ctx_(align.context()), n_((int)models.size()) {
+        std::vector<const rgbd360_depth_model*> raw;
+        for (const auto& m : models) raw.push_back(m.get());
+        const int rc = rgbd360_depth_models_create(ctx_, raw.data(), n_, &set_);
+        if (rc != 0) throw std::runtime_error("rgbd360_depth_models_create (" + std::to_string(rc) + "): " + rgbd360_last_error(ctx_));
+    }
+    // the models a calibration holds (Calib360::loadIntrinsicCalibration, DepthTrainerRig::install)
+    DepthModels(RegisterPhotoICP& align, const Calib360& calib)
+        : DepthModels(align, std::vector<std::shared_ptr<rgbd360_depth_model>>(calib.intrinsic_model_.begin(), calib.intrinsic_model_.end())) {}
+    ~DepthModels() { rgbd360_depth_models_destroy(set_); }
+    DepthModels(const DepthModels&) = delete;
+    DepthModels& operator=(const DepthModels&) = delete;
+
+    int sensors() const { return n_; }
+    size_t bytes() const { return rgbd360_depth_models_bytes(set_); }
+    const rgbd360_depth_models* handle() const { return set_; }
+    // one sensor's model replaced (null: identity), e.g. after a training round
+    void set(int sensor, const rgbd360_depth_model* model) { check(rgbd360_depth_models_set(set_, sensor, model), "rgbd360_depth_models_set"); }
+
+    // images[i] (host memory; 16UC1 mm, converted as Frame360::undistort converts, or 32FC1 m; one size and type) corrected by the model of
+    // sensorOfImage[i] into out[i * rows * cols ..], float32 metres: one launch, one synchronisation
+    void undistort(const std::vector<ImageView>& images, const std::vector<int>& sensorOfImage, std::vector<float>& out) const {
+        if (images.empty() || images.size() != sensorOfImage.size()) throw std::invalid_argument("DepthModels::undistort: one sensor per image");
+        std::vector<rgbd360_map_batch_frame> in = frames(images, "DepthModels::undistort");
+        const size_t n = (size_t)images[0].rows * (size_t)images[0].cols;
+        out.resize(n * images.size());
+        std::vector<float*> dst(images.size());
+        for (size_t i = 0; i < images.size(); ++i) dst[i] = out.data() + i * n;
+        check(rgbd360_depth_undistort(ctx_, set_, in.data(), sensorOfImage.data(), (int)images.size(), depthType(images[0]), images[0].rows, images[0].cols, 0,
+                                      dst.data(), (size_t)images[0].cols * 4),
+              "rgbd360_depth_undistort");
+    }
+    // depths[k S + s] (host memory) into the corrected clouds of the sensors' frames in device memory (3 rows cols floats per image; NaN
+    // triples without a measurement), ready for GlobalMap's device-memory inputs
+    void rigClouds(const std::vector<ImageView>& depths, const std::array<float, 4>& K4, int n_frames, float* xyz_out_dev) const {
+        if (depths.empty() || depths.size() != (size_t)n_frames * (size_t)n_) throw std::invalid_argument("DepthModels::rigClouds: one image per frame and sensor");
+        std::vector<rgbd360_map_batch_frame> in = frames(depths, "DepthModels::rigClouds");
+        check(rgbd360_rig_depth_clouds(ctx_, set_, in.data(), n_frames, n_, depthType(depths[0]), depths[0].rows, depths[0].cols, K4[0], K4[1], K4[2], K4[3], 0,
+                                       xyz_out_dev),
+              "rgbd360_rig_depth_clouds");
+    }
+    // `sensor`'s model judged on one image against the map: the sums of the raw and the corrected error over the trainer's examples
+    // (add the sums of several images; rms() and bias() read them).  stats (may be null): the trainer's counters
+    rgbd360_depth_eval_sums evaluate(GlobalMap& map, int sensor, const ImageView& measurement, const std::array<float, 4>& K, const Mat4f& sensorPose,
+                                     const rgbd360_depth_train_params* params = nullptr, rgbd360_depth_train_stats* stats = nullptr) const {
+        rgbd360_depth_eval_sums sums{};
+        check(rgbd360_depth_evaluate_map(ctx_, map.handle(), set_, sensor, measurement.data, measurement.step, depthType(measurement), measurement.rows,
+                                         measurement.cols, K[0], K[1], K[2], K[3], sensorPose.m, 0, params, stats, &sums),
+              "rgbd360_depth_evaluate_map");
+        return sums;
+    }
+    static void add(rgbd360_depth_eval_sums& total, const rgbd360_depth_eval_sums& s) {
+        total.n += s.n, total.raw_e += s.raw_e, total.raw_ee += s.raw_ee, total.cor_e += s.cor_e, total.cor_ee += s.cor_ee;
+    }
+    // metres, of sums in units of 2^-30 m^2 and 2^-30 m
+    static double rms(long long ee, long long n) { return n > 0 ? std::sqrt((double)ee / 1073741824.0 / (double)n) : 0.0; }
+    static double bias(long long e, long long n) { return n > 0 ? (double)e / 1073741824.0 / (double)n : 0.0; }
+
+   private:
+    static int depthType(const ImageView& depth) { return depth.type == ImageView::U16C1 ? 0 : 1; }
+    static std::vector<rgbd360_map_batch_frame> frames(const std::vector<ImageView>& images, const char* what) {
+        std::vector<rgbd360_map_batch_frame> in(images.size());
+        for (size_t k = 0; k < images.size(); ++k) {
+            if (images[k].rows != images[0].rows || images[k].cols != images[0].cols || images[k].type != images[0].type)
+                throw std::invalid_argument(std::string(what) + ": the images of a call share one size and depth type");
+            in[k].depth = images[k].data;
+            in[k].depth_step = images[k].step;
+        }
+        return in;
+    }
+    void check(int rc, const char* what) const {
+        if (rc != 0) throw std::runtime_error(std::string(what) + " (" + std::to_string(rc) + "): " + rgbd360_last_error(ctx_));
+    }
+    rgbd360_ctx* ctx_;
+    int n_;
+    rgbd360_depth_models* set_ = nullptr;
 };
 
 }  // namespace rgbd360

@@ -1,6 +1,6 @@
 // Frame360.hpp -- C++ adapter over the C ABI (include/rgbd360_hip.h) with the public surface of the reference's Frame360 and
 // Calib360 (include/Frame360.h:93-1148, include/Calib360.h:44-134 of EduFdez/rgbd360) for the stages this library runs on the
-// device: loadFrame, undistort (host), fastStitchImage360 (host), stitchSphericalImage, buildSphereCloud, buildSphereCloud_fromImage, getPlanes (= the eight getPlanesSensor calls, groupPlanes,
+// device: loadFrame, undistort (host; undistortOnDevice: the same bytes from resident models), fastStitchImage360 (host), stitchSphericalImage, buildSphereCloud, buildSphereCloud_fromImage, getPlanes (= the eight getPlanesSensor calls, groupPlanes,
 // mergePlanes), getPlanesSensor, segmentPlanes (the one-panorama variant of Frame360_stereo.h:835-980), getPlanarArea,
 // getAverageIntensity -- same member and method names, so call sites such as RegisterPairRGBD360.cpp:95-110 or
 // OdometryRGBD360.cpp:150-176 (`frame.loadFrame(file); frame.stitchSphericalImage(); frame.getPlanes(); ... frame.planes.vPlanes`)
@@ -181,6 +181,26 @@ class Frame360 {
                 depth_undist_.clear();
                 throw std::runtime_error("Frame360::undistort: the sensor images are not of the model's size");
             }
+        }
+    }
+    // The same on the device from resident models (rgbd360_depth_models_create over the eight sensors; rgbd360::DepthModels::handle(),
+    // DepthTrainer.hpp): one launch over the eight images, the same bytes in depth_undist_ as undistort() leaves.
+    void undistortOnDevice(rgbd360_ctx* ctx, const rgbd360_depth_models* set) {
+        need_images("undistortOnDevice");
+        const size_t n = (size_t)srows_ * scols_;
+        depth_undist_.resize(8 * n);
+        rgbd360_map_batch_frame in[8];
+        float* out[8];
+        int sensor[8];
+        for (int s = 0; s < 8; ++s) {
+            in[s].depth = depth8_.data() + (size_t)s * n;
+            in[s].depth_step = (size_t)scols_ * 2;
+            out[s] = depth_undist_.data() + (size_t)s * n;
+            sensor[s] = s;
+        }
+        if (rgbd360_depth_undistort(ctx, set, in, sensor, 8, 0, srows_, scols_, 0, out, (size_t)scols_ * 4) != 0) {
+            depth_undist_.clear();
+            throw std::runtime_error(std::string("Frame360::undistortOnDevice: ") + rgbd360_last_error(ctx));
         }
     }
     bool undistorted() const { return !depth_undist_.empty(); }

@@ -274,6 +274,11 @@ class GlobalMap {
     // The same from K S pinhole depth images of one size and type (depths[k S + s]); K4 = {fx, fy, cx, cy} (Calib360::K()).
     int calibrateRigDepth(const std::vector<ImageView>& depths, const std::array<float, 4>& K4, std::vector<Mat4f>& poses, std::vector<Mat4f>& extrinsics,
                           const rgbd360_rig_calib_params* params = nullptr) {
+        return calibrateRigDepth(nullptr, depths, K4, poses, extrinsics, params);
+    }
+    // ... with every image corrected on the device by its sensor's depth model first (DepthModels::handle(), DepthTrainer.hpp; null: none)
+    int calibrateRigDepth(const rgbd360_depth_models* models, const std::vector<ImageView>& depths, const std::array<float, 4>& K4, std::vector<Mat4f>& poses,
+                          std::vector<Mat4f>& extrinsics, const rgbd360_rig_calib_params* params = nullptr) {
         if (depths.empty() || depths.size() != poses.size() * extrinsics.size())
             throw std::runtime_error("GlobalMap::calibrateRigDepth: one image per frame and sensor");
         std::vector<rgbd360_map_batch_frame> in(depths.size());
@@ -284,10 +289,10 @@ class GlobalMap {
             in[k].depth_step = depths[k].step;
         }
         rigSensors_.assign(extrinsics.size(), rgbd360_rig_calib_sensor());
-        const int rc = rgbd360_map_calibrate_rig_depth(map_, in.data(), depthType(depths[0]), depths[0].rows, depths[0].cols, K4[0], K4[1], K4[2], K4[3],
-                                                       (int)poses.size(), (int)extrinsics.size(), 0, posesOut(poses), posesOut(extrinsics), params, &rigCalib_,
-                                                       rigSensors_.data());
-        check(rc, "rgbd360_map_calibrate_rig_depth");
+        const int rc = rgbd360_map_calibrate_rig_depth_models(map_, models, in.data(), depthType(depths[0]), depths[0].rows, depths[0].cols, K4[0], K4[1], K4[2],
+                                                              K4[3], (int)poses.size(), (int)extrinsics.size(), 0, posesOut(poses), posesOut(extrinsics), params,
+                                                              &rigCalib_, rigSensors_.data());
+        check(rc, "rgbd360_map_calibrate_rig_depth_models");
         return rc;
     }
     const rgbd360_rig_calib_result& rigCalibResult() const { return rigCalib_; }

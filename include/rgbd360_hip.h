@@ -1645,7 +1645,8 @@ int rgbd360_sensor_planes_ex(rgbd360_ctx* ctx, const void* depth, size_t depth_s
  * in metres before the clouds are built.  The model (CLAMS, Teichman et al.; vendored by the reference under
  * OpenNI2_Grabber/third_party/CLAMS) cuts the image into bins of pixels, each with a multiplier per depth slice; z becomes z * m with m
  * interpolated between the two slices around z when both saw >= 50 training examples (rgbd360_amd/csrc/depth_model.h restates file
- * layout and arithmetic).  Host only, no context needed.
+ * layout and arithmetic).  These entries are host only, no context needed; the same correction on the device, for a whole rig, is
+ * rgbd360_depth_undistort below.
  *   load:      0 ok, 1 cannot open, 2 not a model file / truncated / bins not divisible by `downsample`, -1 bad arguments.
  *   info:      dims = {width, height, bin_width, bin_height, num_bins_x, num_bins_y} after the down-sampling.
  *   undistort: rows x cols float32 metres, in place (0 = no measurement stays 0); the image must have the model's size (-1 otherwise). */
@@ -1683,8 +1684,9 @@ int  rgbd360_depth_model_undistort(const rgbd360_depth_model* model, float* dept
  * counts = (float)(smoothing + count); the file's numerators and denominators are (float)N and (float)D.
  * Stated differences from CLAMS: it keeps float32 running sums in pixel order (they depend on the order and saturate) and re-forms the
  * multiplier after every example; here the sums are exact integers and the multiplier is formed once.
- * Out of scope: continuing from a model file's float32 sums; a device-side undistort; several GPUs inside one trainer
- * (rgbd360_depth_trainer_add_sums is the seam).  The extrinsics of the same rig: rgbd360_map_calibrate_rig_* above. */
+ * Out of scope: continuing from a model file's float32 sums; several GPUs inside one trainer (rgbd360_depth_trainer_add_sums is the
+ * seam).  Applying and judging the models on the device: rgbd360_depth_models_* below.  The extrinsics of the same rig:
+ * rgbd360_map_calibrate_rig_* above. */
 typedef struct rgbd360_depth_trainer rgbd360_depth_trainer;
 typedef struct {
     rgbd360_map_raycast_params ray;      /* the map route's surface cast: the two casts' own defaults */
@@ -1740,6 +1742,69 @@ int  rgbd360_depth_trainer_model(rgbd360_depth_trainer* trainer, rgbd360_depth_m
 int  rgbd360_depth_model_from_sums(int width, int height, int bin_width, int bin_height, double bin_depth, int smoothing, const int64_t* count,
                                    const int64_t* num, const int64_t* den, rgbd360_depth_model** out);
 int  rgbd360_depth_model_save(const rgbd360_depth_model* model, const char* path);
+
+/* ---- applying the depth models on the device (csrc/depth_apply.h) ----------------------------------------------------------------------
+ * The step "undistort" of CLAMS' loop -- map, train, save, undistort, re-map, calibrate, repeat -- from device memory: the models of a
+ * rig's S sensors resident on the device, 1 <= S <= RGBD360_RIG_CALIB_MAX_SENSORS, a NULL model meaning identity, all others of one
+ * width x height.  The resident form is one packed, pointer-free blob that keeps every frustum's own num_bins and bin_depth and, per
+ * slice, the float32 multiplier and count as loaded; every model rgbd360_depth_model_load or _from_sums can hold is represented exactly,
+ * and a set whose blob would exceed 1 GiB is refused.  ONE __host__ __device__ function corrects a pixel on that blob: DiscreteFrustum's
+ * index / undistort / interpolatedUndistort as csrc/depth_model.h restates them, operation for operation, without contraction --
+ * the float64 floor(z / bin_depth), the !(q < num_bins - 1) clamp, start = (float)(bin_depth idx), the half-slice test in double, the
+ * float32 fall-back z multipliers[max(idx, 0)] when a neighbour slice is missing or saw fewer than 50 examples, else the float64
+ * interpolation and (float)((double)z mult).  Frustum of pixel (v, u): (min(v / bin_height, nby - 1), min(u / bin_width, nbx - 1)).  A z
+ * that is 0, negative or NaN is left as it is (payload included); +Inf takes the fall-back branch, as on the host.  The host run of the
+ * same function: rgbd360_depth_models_undistort_packed_host (rgbd360_hip_diag.h).
+ * The two millimetre conversions (they differ for 38850 of the 65535 non-zero raw values, first 5, 9, 10, 11):
+ *   rgbd360_depth_undistort            (float)(0.001 (double)raw): Frame360::undistort's and OpenCV's convertTo(.., 0.001)
+ *   rgbd360_rig_depth_clouds, rgbd360_map_calibrate_rig_depth_models, rgbd360_depth_evaluate_map
+ *                                      0.001f (float)raw: rgbd360_set_target's, the trainer's and rgbd360_map_calibrate_rig_depth's
+ * All entries: -1 with rgbd360_last_error(ctx) set (the map's error string for _calibrate_rig_depth_models), nothing launched or
+ * uploaded, outputs untouched, for a NULL pointer, an image size that is not the set's, a row step shorter than a row, a bad depth_type,
+ * a sensor outside 0 .. S - 1, a set of another context, a pinhole that is not finite or fx / fy zero.  No images or rows cols == 0:
+ * 0, nothing launched. */
+typedef struct rgbd360_depth_models rgbd360_depth_models;
+/* models[n_sensors] (host objects; they are not kept).  The set lives on the context's device and stream; destroy it first.  _bytes: the
+ * device memory of the blob.  _set replaces one sensor's model (NULL: identity) after a training round, under the same size rules; it
+ * waits for the stream before the blob changes. */
+int    rgbd360_depth_models_create(rgbd360_ctx* ctx, const rgbd360_depth_model* const* models, int n_sensors, rgbd360_depth_models** out);
+void   rgbd360_depth_models_destroy(rgbd360_depth_models* set);
+size_t rgbd360_depth_models_bytes(const rgbd360_depth_models* set);
+int    rgbd360_depth_models_set(rgbd360_depth_models* set, int sensor, const rgbd360_depth_model* model);
+/* n images (depth_type 0 uint16 millimetres, 1 float32 metres; host memory, or device memory with on_device 1, then out_m too) corrected
+ * by the models of sensors sensor_of_image[i] into float32 metres out_m[i] (row step out_step): ONE launch over all images, one lane per
+ * pixel, ONE synchronisation.  With depth_type 1 out_m[i] may be the input itself.  For every image the output equals
+ * rgbd360_depth_model_undistort run on the host on the same float32 image, byte for byte; bytes beyond cols in a padded output row are
+ * not written.  set NULL (sensor_of_image is then not read), or a sensor without a model: the converted input. */
+int    rgbd360_depth_undistort(rgbd360_ctx* ctx, const rgbd360_depth_models* set, const rgbd360_map_batch_frame* images, const int* sensor_of_image,
+                               int n_images, int depth_type, int rows, int cols, int on_device, float* const* out_m, size_t out_step);
+/* What rgbd360_map_calibrate_rig_depth does in its first launch, public and with the correction: image k S + s becomes the packed cloud
+ * xyz_out_dev[3 rows cols (k S + s) ..] (device memory) in the SENSOR's frame, a NaN triple where there is no measurement.  Conversion
+ * and ray are that call's; with a set (of n_sensors sensors) z is first corrected by sensor s's model, and a corrected z that is not
+ * finite and positive gives a NaN triple.  set NULL, or a sensor without a model: the bytes of rgbd360_map_calibrate_rig_depth's launch.
+ * Re-mapping with corrected depth is this call followed by rgbd360_map_insert_cloud (device memory) per (k, s) at T_k E_s. */
+int    rgbd360_rig_depth_clouds(rgbd360_ctx* ctx, const rgbd360_depth_models* set, const rgbd360_map_batch_frame* images, int n_frames, int n_sensors,
+                                int depth_type, int rows, int cols, float fx, float fy, float cx, float cy, int on_device, float* xyz_out_dev);
+/* rgbd360_map_calibrate_rig_depth on corrected depth: poses, extrinsics, result, sensor records and trace are byte for byte those of
+ * rgbd360_rig_depth_clouds followed by rgbd360_map_calibrate_rig_clouds (on_device 1) on its output; with set NULL those of
+ * rgbd360_map_calibrate_rig_depth.  The set is of the map's context and of n_sensors sensors. */
+int    rgbd360_map_calibrate_rig_depth_models(rgbd360_map* map, const rgbd360_depth_models* set, const rgbd360_map_batch_frame* depth, int depth_type,
+                                              int rows, int cols, float fx, float fy, float cx, float cy, int n_frames, int n_sensors, int on_device,
+                                              float* poses, float* extrinsics, const rgbd360_rig_calib_params* params, rgbd360_rig_calib_result* result,
+                                              rgbd360_rig_calib_sensor* sensors);
+/* A model judged against the map.  Ground truth, gates and counters are those of rgbd360_depth_trainer_accumulate_map, steps
+ * "measurement" to "multiplier", bit for bit (the same device code), all taken on the RAW measurement, so both sums below range over
+ * the same pixels, the n_examples of stats.  Per example, float64 without contraction: e_raw = meas - gt, e_cor = z' - gt, z' the
+ * measurement corrected by `sensor`'s model (set NULL: z' = meas), float32 widened to double.  n = the examples; *_e = sum of
+ * llrint(e 2^30), signed (the bias, in units of 2^-30 m); *_ee = sum of llrint(e e 2^30) (the mean square, 2^-30 m^2).  64-bit integer
+ * atomics only, one add per wave and word after a reduction over the wave: the bits do not depend on the launch shape, the run or the
+ * order of calls, and the sums of several images are joined by integer addition.  With max_range <= 16 a raw term is below 2^38 (and a
+ * corrected one as long as z' stays below 2 max_range); a call of more than 2^24 pixels is refused, so no word can wrap.  Refusals:
+ * those above and what accumulate_map refuses.  An empty map: 0 with zero statistics and sums. */
+typedef struct { long long n, raw_e, raw_ee, cor_e, cor_ee; } rgbd360_depth_eval_sums;
+int    rgbd360_depth_evaluate_map(rgbd360_ctx* ctx, rgbd360_map* map, const rgbd360_depth_models* set, int sensor, const void* meas, size_t meas_step,
+                                  int depth_type, int rows, int cols, float fx, float fy, float cx, float cy, const float sensor_pose[16], int on_device,
+                                  const rgbd360_depth_train_params* params, rgbd360_depth_train_stats* stats, rgbd360_depth_eval_sums* sums);
 
 /* ---- pinhole single-sensor alignment ------------------------------------------------------ */
 

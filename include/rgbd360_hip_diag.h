@@ -279,6 +279,23 @@ int rgbd360_depth_trainer_time_map(rgbd360_depth_trainer* trainer, rgbd360_map* 
                                    float fy, float cx, float cy, const float sensor_pose[16], const rgbd360_depth_train_params* params,
                                    const float* origins_dev, const float* dirs_dev, int reps, float* train_us, float* cast_us,
                                    rgbd360_depth_train_stats* stats);
+/* The packed, pointer-free form of a rig's depth models that rgbd360_depth_models_create keeps on the device (rgbd360_hip.h, "applying
+ * the depth models on the device"; csrc/depth_apply.h) and the per-pixel text over it run on the CPU.  Host only, no context, no device.
+ *   pack:    models[n_sensors], a NULL entry: identity.  blob NULL: *bytes = the size needed; else *bytes is the room of blob and, on
+ *            return, the size written.  -1: what rgbd360_depth_models_create refuses, or too little room.
+ *   repack:  old_blob with `sensor` replaced by model (NULL: identity), as rgbd360_depth_models_set does; the other sections are copied.
+ *   undistort_packed_host: rgbd360_depth_model_undistort over the blob -- the SAME __host__ __device__ function the kernels call, so the
+ *            packing and the arithmetic are checked without a GPU.  In place; a sensor with a model needs an image of the set's size. */
+int rgbd360_depth_models_pack(const rgbd360_depth_model* const* models, int n_sensors, void* blob, size_t* bytes);
+int rgbd360_depth_models_repack(const void* old_blob, int sensor, const rgbd360_depth_model* model, void* blob, size_t* bytes);
+int rgbd360_depth_models_undistort_packed_host(const void* blob, int sensor, float* depth_m, size_t depth_step, int rows, int cols);
+/* The kernel of a rgbd360_depth_undistort, rgbd360_rig_depth_clouds or rgbd360_depth_evaluate_map call (the last with the clear of its
+ * counters) under HIP events: timing(ctx, 1) makes every such call of the context record an event in front of and behind its launch,
+ * last_us gives the microseconds of the last one (-1 without a timed call).  time_copy: a device-to-device copy of `bytes` on the
+ * context's stream between the same events, the yardstick of the stand-alone undistort (tools/depth_apply_perf.py). */
+int rgbd360_depth_apply_timing(rgbd360_ctx* ctx, int on);
+int rgbd360_depth_apply_last_us(rgbd360_ctx* ctx, float* us);
+int rgbd360_depth_apply_time_copy(rgbd360_ctx* ctx, void* dst_dev, const void* src_dev, size_t bytes, float* us);
 /* An observation (rgbd360_map_observe_sphere, rgbd360_hip.h) under HIP events, one figure per repetition in microseconds (the caller takes
  * medians): observe_us[r] one k_vmap_observe launch over the device image with the clear of its counters, on zeroed votes (the coarse
  * layer is built before the first); carve_us[r] (may be NULL) ONE k_vmap_carve launch over the table with thresholds that no voxel meets:

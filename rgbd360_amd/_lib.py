@@ -72,6 +72,10 @@ SYMBOLS = [
     "rgbd360_depth_default_train_params", "rgbd360_depth_trainer_accumulate_images", "rgbd360_depth_trainer_accumulate_map",
     "rgbd360_depth_trainer_sums", "rgbd360_depth_trainer_add_sums", "rgbd360_depth_trainer_model", "rgbd360_depth_model_from_sums",
     "rgbd360_depth_model_save", "rgbd360_depth_trainer_set_form", "rgbd360_depth_trainer_time_map",
+    "rgbd360_depth_models_create", "rgbd360_depth_models_destroy", "rgbd360_depth_models_bytes", "rgbd360_depth_models_set",
+    "rgbd360_depth_undistort", "rgbd360_rig_depth_clouds", "rgbd360_map_calibrate_rig_depth_models", "rgbd360_depth_evaluate_map",
+    "rgbd360_depth_models_pack", "rgbd360_depth_models_repack", "rgbd360_depth_models_undistort_packed_host",
+    "rgbd360_depth_apply_timing", "rgbd360_depth_apply_last_us", "rgbd360_depth_apply_time_copy",
 ]
 
 
@@ -267,6 +271,10 @@ class DepthTrainStats(C.Structure):     # rgbd360_depth_train_stats
                                             "n_mult_rejected", "n_examples")]
 
 
+class DepthEvalSums(C.Structure):       # rgbd360_depth_eval_sums
+    _fields_ = [(n, C.c_longlong) for n in ("n", "raw_e", "raw_ee", "cor_e", "cor_ee")]
+
+
 class MapNormalStats(C.Structure):      # rgbd360_map_normal_stats
     _fields_ = [(n, C.c_longlong) for n in ("n_voxels", "n_below_min_count", "n_unsupported", "n_nonplanar", "n_normals")]
 
@@ -435,6 +443,22 @@ def load() -> C.CDLL:
     L.rgbd360_depth_trainer_add_sums.argtypes = [vp, vp, vp, vp]
     L.rgbd360_depth_trainer_model.argtypes = [vp, C.POINTER(vp)]
     L.rgbd360_depth_trainer_set_form.argtypes = [vp, i32]
+    L.rgbd360_depth_models_create.argtypes = [vp, C.POINTER(vp), i32, C.POINTER(vp)]
+    L.rgbd360_depth_models_destroy.argtypes = [vp]
+    L.rgbd360_depth_models_destroy.restype = None
+    L.rgbd360_depth_models_bytes.argtypes = [vp]
+    L.rgbd360_depth_models_bytes.restype = C.c_size_t
+    L.rgbd360_depth_models_set.argtypes = [vp, i32, vp]
+    L.rgbd360_depth_undistort.argtypes = [vp, vp, C.POINTER(MapBatchFrame), C.POINTER(i32), i32, i32, i32, i32, i32, C.POINTER(vp), C.c_size_t]
+    L.rgbd360_rig_depth_clouds.argtypes = [vp, vp, C.POINTER(MapBatchFrame), i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, i32, vp]
+    L.rgbd360_depth_evaluate_map.argtypes = [vp, vp, vp, i32, vp, C.c_size_t, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, f32p, i32,
+                                             C.POINTER(DepthTrainParams), C.POINTER(DepthTrainStats), C.POINTER(DepthEvalSums)]
+    L.rgbd360_depth_models_pack.argtypes = [C.POINTER(vp), i32, vp, C.POINTER(C.c_size_t)]
+    L.rgbd360_depth_models_repack.argtypes = [vp, i32, vp, vp, C.POINTER(C.c_size_t)]
+    L.rgbd360_depth_models_undistort_packed_host.argtypes = [vp, i32, vp, C.c_size_t, i32, i32]
+    L.rgbd360_depth_apply_timing.argtypes = [vp, i32]
+    L.rgbd360_depth_apply_last_us.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rgbd360_depth_apply_time_copy.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(C.c_float)]
     L.rgbd360_depth_trainer_time_map.argtypes = [vp, vp, vp, C.c_size_t, i32, C.c_float, C.c_float, C.c_float, C.c_float, f32p,
                                                  C.POINTER(DepthTrainParams), vp, vp, i32, vp, vp, C.POINTER(DepthTrainStats)]
     L.rgbd360_pool_sensor_planes.argtypes = [vp, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp, i32, C.POINTER(i32)]
@@ -570,6 +594,7 @@ def load() -> C.CDLL:
     rig_tail = [i32, i32, i32, vp, vp, C.POINTER(RigCalibParams), C.POINTER(RigCalibResult), C.POINTER(RigCalibSensor)]
     L.rgbd360_map_calibrate_rig_clouds.argtypes = [vp, C.POINTER(MapBatchCloud)] + rig_tail
     L.rgbd360_map_calibrate_rig_depth.argtypes = [vp, C.POINTER(MapBatchFrame), i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float] + rig_tail
+    L.rgbd360_map_calibrate_rig_depth_models.argtypes = [vp, vp, C.POINTER(MapBatchFrame), i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float] + rig_tail
     L.rgbd360_rig_save_extrinsics.argtypes = [vp, i32, C.c_char_p]
     L.rgbd360_rig_calib_solve_host.argtypes = [vp, i32, i32, vp, vp, C.POINTER(RigCalibParams), vp, vp, vp, C.POINTER(i32)]
     L.rgbd360_rig_calib_solve_dev.argtypes = [vp] + L.rgbd360_rig_calib_solve_host.argtypes

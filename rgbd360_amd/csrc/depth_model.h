@@ -7,7 +7,8 @@
 // File layout (restated from the reference's serialisation code): the line "DiscreteDepthDistortionModel v01", then raw little-endian
 // scalars width, height, bin_width, bin_height (int32), bin_depth (float64), num_bins_x, num_bins_y (int32), then per frustum (row of
 // bins after row of bins) max_dist (float64), num_bins (int32), bin_depth (float64) and four float32 vectors {counts, total numerators,
-// total denominators, multipliers}, each written as {4, rows, cols} (int32) + data.  Host code; no device work (8 x 320 x 240 pixels).
+// total denominators, multipliers}, each written as {4, rows, cols} (int32) + data.  Host code; depth_apply.h packs these models for the
+// device and restates slice_of / undistort_px below, operation for operation, as one __host__ __device__ function.
 #pragma once
 
 #include <algorithm>

@@ -63,6 +63,16 @@ struct F360State {
     PinnedBuf<float4> f_models_host;                              // pinned staging of the refinement's plane models
     DevBuf<unsigned> b_mm;                                        // per-block {min, max} codes of the depth range
     PinnedBuf<unsigned> b_mm_host{hostwait::kPublishedFlags};     // ... the pair, published into pinned memory
+    // applying the depth models (depth_apply.h): host images on their way to a kernel, the image records, the results of a host call,
+    // the counters and sums of an evaluation
+    DevBuf<uint8_t> da_up;
+    DevBuf<unsigned char> da_img;
+    PinnedBuf<unsigned char> da_img_host;
+    DevBuf<float> da_out;
+    DevBuf<unsigned long long> da_words;
+    PinnedBuf<unsigned long long> da_words_host;
+    hipEvent_t da_ev[2] = {nullptr, nullptr};      // measurement (rgbd360_depth_apply_timing): around the kernel of a depth_apply.h entry
+    bool da_timing = false, da_timed = false;
     DevBuf<float> f_tab;
     int f_tab_rows = 0, f_tab_cols = 0, f_tab_conv = -1;      // what the resident angle tables were built for
     // measurement (rgbd360_frame_planes_stage_timing): events on `stream` at the stage boundaries of a frame_planes call -- before the
@@ -124,6 +134,8 @@ F360State* f360_state_create(int device, hipStream_t stream) {
 void f360_state_destroy(F360State* ctx) {
     if (!ctx) return;
     for (hipEvent_t e : ctx->f_stage_ev)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : ctx->da_ev)
         if (e) hipEventDestroy(e);
     hostwait::spin_tag_free(&ctx->tag);
     delete ctx;
@@ -1276,6 +1288,7 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
 #include "map_carve.h"
 #include "map_planes.h"
 #include "depth_train.h"
+#include "depth_apply.h"
 
 #ifdef RGBD360_HULL_DBG
 extern "C" int rgbd360_debug_hull_stats(unsigned long long* out /* [4096][8] */) {

@@ -12,7 +12,10 @@
 #include <vector>
 
 #include "../../include/rgbd360_hip.h"
+#include "../../include/rgbd360_hip_diag.h"
 #include "depth_model.h"
+#define DEPTH_APPLY_PACKER
+#include "depth_apply.h"
 #include "pbmap_register.h"
 
 // ---- the sensors' intrinsic depth model (depth_model.h): host only ----
@@ -62,6 +65,21 @@ extern "C" int rgbd360_depth_model_from_sums(int width, int height, int bin_widt
 extern "C" int rgbd360_depth_model_save(const rgbd360_depth_model* model, const char* path) {
     if (!model || !path) return -1;
     return depthmodel::save(path, model->m);
+}
+// the packed form of a rig's models and the per-pixel text over it on the host (csrc/depth_apply.h; rgbd360_hip_diag.h)
+extern "C" int rgbd360_depth_models_pack(const rgbd360_depth_model* const* models, int n_sensors, void* blob, size_t* bytes) {
+    if (!models || !bytes || n_sensors < 1 || n_sensors > depthapply::kMaxSensors) return -1;
+    const depthmodel::Model* of[depthapply::kMaxSensors];
+    for (int s = 0; s < n_sensors; ++s) of[s] = models[s] ? &models[s]->m : nullptr;
+    return depthapply::pack(of, n_sensors, nullptr, 0, blob, bytes);
+}
+extern "C" int rgbd360_depth_models_repack(const void* old_blob, int sensor, const rgbd360_depth_model* model, void* blob, size_t* bytes) {
+    if (!old_blob || !bytes) return -1;
+    const depthmodel::Model* one = model ? &model->m : nullptr;
+    return depthapply::pack(&one, 0, old_blob, sensor, blob, bytes);
+}
+extern "C" int rgbd360_depth_models_undistort_packed_host(const void* blob, int sensor, float* depth_m, size_t depth_step, int rows, int cols) {
+    return depthapply::undistort_packed(blob, sensor, depth_m, depth_step, rows, cols);
 }
 
 

@@ -13,6 +13,7 @@
 //
 //   k_rig_pinhole_cloud   all K S pinhole depth images of a _depth call into packed clouds, one launch: f = ((u - cx) / fx, (v - cy) / fy, 1)
 //                         in float32, the point z f; a pixel without a measurement a NaN triple.
+//                         (its pixel is pinhole_pixel, which depth_apply.h's k_rig_cloud_models instantiates with a correction of z.)
 //   k_rig_init            one launch: the head, the inputs' records and, per live input, its loop state at P_ks = T_k E_s (gn::mat4_mul).
 //   k_rig_input           one 64-lane workgroup per live input: the partial rows added in ascending order (the first loop of
 //                         map_align_solve_rows.h on the 30 sums), then lane 0: A, b, A Ad, Ad^T A Ad, Ad^T b.
@@ -443,8 +444,15 @@ struct Image {
     size_t step;
 };
 
-__global__ __launch_bounds__(256) void k_rig_pinhole_cloud(const Image* __restrict__ images, int depth_type, int rows, int cols, float fx, float fy, float cx,
-                                                           float cy, float* __restrict__ out) {
+// A pixel of the cloud formation.  Correct: what depth_apply.h's k_rig_cloud_models does to a measured z (and whether it is still a
+// measurement) before the ray product; k_rig_pinhole_cloud has none.
+struct NoCorrection {
+    static constexpr bool kOn = false;
+    __device__ bool operator()(int, int, int, float&) const { return true; }
+};
+template <class Correct>
+__device__ __forceinline__ void pinhole_pixel(const Image* __restrict__ images, int depth_type, int rows, int cols, float fx, float fy, float cx, float cy,
+                                              float* __restrict__ out, const Correct& correct) {
     const long long n = (long long)rows * cols, i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const Image im = images[blockIdx.y];
@@ -460,6 +468,7 @@ __global__ __launch_bounds__(256) void k_rig_pinhole_cloud(const Image* __restri
         z = reinterpret_cast<const float*>(line)[u];
         ok = z > 0.f && z < __builtin_inff();
     }
+    if (Correct::kOn) ok = ok && correct((int)blockIdx.y, v, u, z);
     const float nan = __builtin_nanf("");
     const float x = (float)u - cx, y = (float)v - cy;
     const float f0 = x / fx, f1 = y / fy;
@@ -467,6 +476,11 @@ __global__ __launch_bounds__(256) void k_rig_pinhole_cloud(const Image* __restri
     p[0] = ok ? z * f0 : nan;
     p[1] = ok ? z * f1 : nan;
     p[2] = ok ? z : nan;
+}
+
+__global__ __launch_bounds__(256) void k_rig_pinhole_cloud(const Image* __restrict__ images, int depth_type, int rows, int cols, float fx, float fy, float cx,
+                                                           float cy, float* __restrict__ out) {
+    pinhole_pixel(images, depth_type, rows, cols, fx, fy, cx, cy, out, NoCorrection{});
 }
 
 // live_of_input[i]: the job of input i among the live ones, -1: an empty input
@@ -786,28 +800,66 @@ extern "C" int rgbd360_map_calibrate_rig_clouds(rgbd360_map* m, const rgbd360_ma
     return rig_calibrate(m, in, n_frames, n_sensors, poses, extrinsics, p, base, result, sensors);
 }
 
-extern "C" int rgbd360_map_calibrate_rig_depth(rgbd360_map* m, const rgbd360_map_batch_frame* depth, int depth_type, int rows, int cols, float fx, float fy,
-                                               float cx, float cy, int n_frames, int n_sensors, int on_device, float* poses, float* extrinsics,
-                                               const rgbd360_rig_calib_params* params, rgbd360_rig_calib_result* result, rgbd360_rig_calib_sensor* sensors) {
-    if (!m) return -1;
-    m->err.clear();
+namespace {
+// What the depth entries (here and in depth_apply.h) refuse of n_inputs pinhole images before anything is launched or uploaded: the
+// reason, or null; upload: the bytes of the host images packed side by side.
+const char* rig_depth_refusal(const rgbd360_map_batch_frame* depth, int n_inputs, int depth_type, int rows, int cols, float fx, float fy, float cx, float cy,
+                              int on_device, unsigned long long& upload) {
+    const float pin[4] = {fx, fy, cx, cy};
+    if (!rig_finite(pin, 4) || fx == 0.f || fy == 0.f) return "the pinhole must be finite, fx and fy not zero";
+    if (depth_type != 0 && depth_type != 1) return "bad depth type";
+    if (rows < 0 || cols < 0 || (long long)rows * cols >= (1ll << 30)) return "bad image size";
+    const size_t prow = (size_t)cols * (depth_type == 0 ? 2 : 4);
+    const long long n = (long long)rows * cols;
+    upload = 0;
+    for (int i = 0; i < n_inputs && n > 0; ++i) {
+        if (!depth[i].depth) return "a depth image must not be null";
+        if (depth[i].depth_step < prow) return "row step shorter than a row";
+        if (!on_device) upload = batch_align256((size_t)(upload + prow * rows));
+    }
+    if (upload > kBatchMaxUpload) return "the host inputs of the call exceed RGBD360_MAP_BATCH_MAX_UPLOAD bytes";
+    return nullptr;
+}
+// The images of a checked call where a kernel reads them: host images packed into `up`, the descriptors through img_host into img.
+// `o` takes the error text (a map or a Frame360 state).
+template <class Owner>
+int rig_depth_stage(Owner* o, hipStream_t stream, const rgbd360_map_batch_frame* depth, int n_inputs, int depth_type, int rows, int cols, int on_device,
+                    unsigned long long upload, DevBuf<uint8_t>& up, DevBuf<unsigned char>& img, PinnedBuf<unsigned char>& img_host) {
+    const size_t prow = (size_t)cols * (depth_type == 0 ? 2 : 4);
+    const size_t desc = sizeof(rigc::Image) * (size_t)n_inputs;
+    HIPC(o, img.ensure(desc));
+    HIPC(o, img_host.ensure(desc));
+    if (upload) HIPC(o, up.ensure((size_t)upload));
+    rigc::Image* hi = reinterpret_cast<rigc::Image*>(img_host.get());
+    size_t at = 0;
+    for (int i = 0; i < n_inputs; ++i) {
+        hi[i] = {depth[i].depth, depth[i].depth_step};
+        if (!on_device) {
+            uint8_t* dst = up.get() + at;
+            HIPC(o, hipMemcpy2DAsync(dst, prow, depth[i].depth, depth[i].depth_step, prow, (size_t)rows, hipMemcpyHostToDevice, stream));
+            hi[i] = {dst, prow};
+            at = batch_align256(at + prow * rows);
+        }
+    }
+    HIPC(o, hipMemcpyAsync(img, img_host, desc, hipMemcpyHostToDevice, stream));
+    return 0;
+}
+// the launch of the cloud formation over staged images; depth_apply.h defines it (with a set of depth models: its own kernel)
+template <class Owner>
+int rig_depth_launch(Owner* o, hipStream_t stream, const rgbd360_depth_models* set, const rigc::Image* images, int n_inputs, int n_sensors, int depth_type, int rows,
+                     int cols, float fx, float fy, float cx, float cy, float* out);
+
+// rgbd360_map_calibrate_rig_depth and, with a set, rgbd360_map_calibrate_rig_depth_models
+int rig_calibrate_depth(rgbd360_map* m, const rgbd360_depth_models* set, const rgbd360_map_batch_frame* depth, int depth_type, int rows, int cols, float fx, float fy,
+                        float cx, float cy, int n_frames, int n_sensors, int on_device, float* poses, float* extrinsics, const rgbd360_rig_calib_params* params,
+                        rgbd360_rig_calib_result* result, rgbd360_rig_calib_sensor* sensors) {
     rgbd360_rig_calib_params p;
     IcpJob base;
     if (const int rc = rig_check_call(m, depth, n_frames, n_sensors, poses, extrinsics, params, p, base)) return rc;
-    const float pin[4] = {fx, fy, cx, cy};
-    if (!rig_finite(pin, 4) || fx == 0.f || fy == 0.f) return vmap_fail(m, -1, "the pinhole must be finite, fx and fy not zero");
-    if (depth_type != 0 && depth_type != 1) return vmap_fail(m, -1, "bad depth type");
-    if (rows < 0 || cols < 0 || (long long)rows * cols >= (1ll << 30)) return vmap_fail(m, -1, "bad image size");
     const int n_inputs = n_frames * n_sensors;
-    const size_t prow = (size_t)cols * (depth_type == 0 ? 2 : 4);
     const long long n = (long long)rows * cols;
     unsigned long long upload = 0;
-    for (int i = 0; i < n_inputs && n > 0; ++i) {
-        if (!depth[i].depth) return vmap_fail(m, -1, "a depth image must not be null");
-        if (depth[i].depth_step < prow) return vmap_fail(m, -1, "row step shorter than a row");
-        if (!on_device) upload = batch_align256((size_t)(upload + prow * rows));
-    }
-    if (upload > kBatchMaxUpload) return vmap_fail(m, -1, "the host inputs of the call exceed RGBD360_MAP_BATCH_MAX_UPLOAD bytes");
+    if (const char* why = rig_depth_refusal(depth, n_inputs, depth_type, rows, cols, fx, fy, cx, cy, on_device, upload)) return vmap_fail(m, -1, why);
     const unsigned long long rows_each = (unsigned long long)((n + vmap::kTile - 1) / vmap::kTile);
     if (rows_each * (unsigned long long)n_inputs > (unsigned long long)kBatchMaxRows)
         return vmap_fail(m, -1, "the inputs of the call need more than RGBD360_MAP_BATCH_MAX_ROWS workgroups");
@@ -815,29 +867,23 @@ extern "C" int rgbd360_map_calibrate_rig_depth(rgbd360_map* m, const rgbd360_map
     if (n > 0) {
         hipSetDevice(m->s->p.device);
         hipStream_t stream = m->s->stream;
-        const size_t desc = sizeof(rigc::Image) * (size_t)n_inputs;
         HIPC(m, m->c_cloud.ensure((size_t)n_inputs * (size_t)n * 3));
-        HIPC(m, m->c_img.ensure(desc));
-        HIPC(m, m->c_img_host.ensure(desc));
-        if (upload) HIPC(m, m->up_depth.ensure((size_t)upload));
-        rigc::Image* hi = reinterpret_cast<rigc::Image*>(m->c_img_host.get());
-        size_t at = 0;
-        for (int i = 0; i < n_inputs; ++i) {
-            hi[i] = {depth[i].depth, depth[i].depth_step};
-            if (!on_device) {
-                uint8_t* dst = m->up_depth.get() + at;
-                HIPC(m, hipMemcpy2DAsync(dst, prow, depth[i].depth, depth[i].depth_step, prow, (size_t)rows, hipMemcpyHostToDevice, stream));
-                hi[i] = {dst, prow};
-                at = batch_align256(at + prow * rows);
-            }
-        }
-        HIPC(m, hipMemcpyAsync(m->c_img, m->c_img_host, desc, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(rigc::k_rig_pinhole_cloud, dim3((unsigned)((n + 255) / 256), (unsigned)n_inputs), dim3(256), 0, stream,
-                           reinterpret_cast<const rigc::Image*>(m->c_img.get()), depth_type, rows, cols, fx, fy, cx, cy, m->c_cloud.get());
-        HIPC(m, hipGetLastError());
+        if (const int rc = rig_depth_stage(m, stream, depth, n_inputs, depth_type, rows, cols, on_device, upload, m->up_depth, m->c_img, m->c_img_host)) return rc;
+        if (const int rc = rig_depth_launch(m, stream, set, reinterpret_cast<const rigc::Image*>(m->c_img.get()), n_inputs, n_sensors, depth_type, rows, cols, fx,
+                                            fy, cx, cy, m->c_cloud.get()))
+            return rc;
     }
     for (int i = 0; i < n_inputs; ++i) in[(size_t)i] = cloud_input(n > 0 ? m->c_cloud.get() + (size_t)i * (size_t)n * 3 : nullptr, nullptr, n, 1);
     return rig_calibrate(m, in, n_frames, n_sensors, poses, extrinsics, p, base, result, sensors);
+}
+}  // namespace
+
+extern "C" int rgbd360_map_calibrate_rig_depth(rgbd360_map* m, const rgbd360_map_batch_frame* depth, int depth_type, int rows, int cols, float fx, float fy,
+                                               float cx, float cy, int n_frames, int n_sensors, int on_device, float* poses, float* extrinsics,
+                                               const rgbd360_rig_calib_params* params, rgbd360_rig_calib_result* result, rgbd360_rig_calib_sensor* sensors) {
+    if (!m) return -1;
+    m->err.clear();
+    return rig_calibrate_depth(m, nullptr, depth, depth_type, rows, cols, fx, fy, cx, cy, n_frames, n_sensors, on_device, poses, extrinsics, params, result, sensors);
 }
 
 extern "C" int rgbd360_rig_save_extrinsics(const float* extrinsics, int n_sensors, const char* dir) {

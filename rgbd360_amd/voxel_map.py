@@ -534,9 +534,10 @@ class VoxelMap:
             I[k].xyz, I[k].n = x.ctypes.data, x.shape[0]
         return self._calibrate_rig(self._L.rgbd360_map_calibrate_rig_clouds, (I,), poses, extrinsics, params)
 
-    def calibrate_rig_depth(self, depths, K4, poses, extrinsics, **params):
+    def calibrate_rig_depth(self, depths, K4, poses, extrinsics, models=None, **params):
         """The same from K x S pinhole depth images of ONE size and type (uint16 millimetres or float32 metres; rows may be strided), flat
-        frame-major; K4 = (fx, fy, cx, cy)."""
+        frame-major; K4 = (fx, fy, cx, cy).  models: a depth_train.DepthModels of the S sensors; every image is corrected by its sensor's
+        model on the device before its cloud is formed (rgbd360_map_calibrate_rig_depth_models)."""
         ds = []
         for depth in depths:
             d = np.asarray(depth)
@@ -554,6 +555,8 @@ class VoxelMap:
             I[k].depth, I[k].depth_step = d.ctypes.data, d.strides[0]
         fx, fy, cx, cy = (float(v) for v in K4)
         head = (I, 0 if ds[0].dtype == np.uint16 else 1, ds[0].shape[0], ds[0].shape[1], fx, fy, cx, cy)
+        if models is not None:
+            return self._calibrate_rig(self._L.rgbd360_map_calibrate_rig_depth_models, (models._handle(),) + head, poses, extrinsics, params)
         return self._calibrate_rig(self._L.rgbd360_map_calibrate_rig_depth, head, poses, extrinsics, params)
 
     def rig_calib_trace(self):
