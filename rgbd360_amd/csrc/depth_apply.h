@@ -26,7 +26,7 @@
 //                         Frame360::undistort's and OpenCV's convertTo(.., 0.001) -- NOT the 0.001f (float)v of the map entries.
 //   k_rig_cloud_models    k_rig_pinhole_cloud with z corrected by the image's sensor before the ray product; the pixel's text is
 //                         rigc::pinhole_pixel, shared with that kernel.
-//   k_depth_eval          depth_train_gates.h, the text k_depth_train includes: the trainer's gates (on the RAW measurement), then per example
+//   k_depth_eval          vmap::train_gates, the function k_depth_train calls: the trainer's gates (on the RAW measurement), then per example
 //                         e_raw = meas - gt, e_cor = z' - gt in float64 and five integer terms, summed over the wave, one 64-bit integer
 //                         atomic per wave and word.
 #pragma once
@@ -261,21 +261,19 @@ struct EvalJob {
     unsigned long long* sums;            // [depthapply::kEvWords]
 };
 
-// k_depth_train<true, LAYER>'s pixel (its tile, its gates, its counters: the texts that kernel includes), with the example judged
+// k_depth_train<true, LAYER>'s pixel (its tile, its gates, its counters: the functions that kernel calls), with the example judged
 // instead of added to a trainer's sums.  J.stats are the counters; J.sums, J.form and J.gt_out are not read.
 template <bool LAYER>
 __global__ __launch_bounds__(kTrainThreads) void k_depth_eval(TrainJob J, EvalJob E) {
 #pragma clang fp contract(off)
-    constexpr bool MAP = true;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int u = blockIdx.x * kTrainTile + (wave & 1) * 8 + (lane & 7), v = blockIdx.y * kTrainTile + (wave >> 1) * 8 + (lane >> 3);
     const bool in = u < J.cols && v < J.rows;
-#include "depth_train_gates.h"
-    (void)bin, (void)term;               // (an example is not added to a trainer's sums here)
+    const TrainPixel px = train_gates<true, LAYER>(J, v, u, in);       // (an example is not added to a trainer's sums here: no bin, no terms)
     long long ev[depthapply::kEvWords] = {0ll, 0ll, 0ll, 0ll, 0ll};
-    if (example) {
-        const double gt = (double)gt32, meas = (double)meas32;
-        const float zc = E.blob ? depthapply::apply_px(E.blob, E.sensor, v, u, meas32) : meas32;
+    if (px.example) {
+        const double gt = (double)px.gt32, meas = (double)px.meas32;
+        const float zc = E.blob ? depthapply::apply_px(E.blob, E.sensor, v, u, px.meas32) : px.meas32;
         const double e_raw = meas - gt, e_cor = (double)zc - gt;
         ev[depthapply::kEvN] = 1ll;
         ev[depthapply::kEvRawE] = __double2ll_rn(e_raw * depthapply::kEvalFix);
@@ -283,7 +281,7 @@ __global__ __launch_bounds__(kTrainThreads) void k_depth_eval(TrainJob J, EvalJo
         ev[depthapply::kEvCorE] = __double2ll_rn(e_cor * depthapply::kEvalFix);
         ev[depthapply::kEvCorEE] = __double2ll_rn(e_cor * e_cor * depthapply::kEvalFix);
     }
-    if (__ballot(example)) {             // (the wave's lanes alike)
+    if (__ballot(px.example)) {          // (the wave's lanes alike)
 #pragma unroll
         for (int q = 0; q < depthapply::kEvWords; ++q) {
             long long s = ev[q];
@@ -292,7 +290,7 @@ __global__ __launch_bounds__(kTrainThreads) void k_depth_eval(TrainJob J, EvalJo
             if (lane == 0 && s) atomicAdd(E.sums + q, (unsigned long long)s);      // one add per wave and word
         }
     }
-#include "depth_train_counters.h"
+    train_counters(J.stats, lane, in, px.cat);
 }
 
 }  // namespace vmap

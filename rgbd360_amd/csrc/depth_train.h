@@ -32,8 +32,8 @@
 //                               bin summed over the wave and one atomic per bin and word (vmap::wave_add_by_key, map_planes.h), 2 a
 //                               per-block LDS table (integer LDS atomics; one slot per distinct bin of the block, claimed by an LDS
 //                               compare-and-swap) flushed once per touched word.  Counters through ballots, one add per wave.
-//                               The gates and the counters are depth_train_gates.h and depth_train_counters.h: the texts
-//                               depth_apply.h's k_depth_eval includes too.
+//                               The gates and the counters are train_gates and train_counters, the functions depth_apply.h's
+//                               k_depth_eval calls too: the evaluation judges a model on exactly the trainer's examples.
 #pragma once
 
 struct rgbd360_depth_trainer {
@@ -84,6 +84,97 @@ __device__ __forceinline__ float train_depth_at(const void* img, size_t step, in
     return depth_type == 0 ? 0.001f * (float)((const uint16_t*)row)[u] : ((const float*)row)[u];
 }
 
+// what the gates leave of a pixel: the measurement and the ground truth, cat (the one counter of the pixel), reached (step 2 onwards),
+// example, and an example's bin and three terms
+struct TrainPixel {
+    float meas32, gt32;
+    int cat;
+    bool reached, example;
+    int bin;
+    long long term[3];
+};
+// steps "measurement ... multiplier" of pixel (v, u) of the map or image route; in: whether it lies in the image
+template <bool MAP, bool LAYER>
+__device__ __forceinline__ TrainPixel train_gates(const TrainJob& J, int v, int u, bool in) {
+#pragma clang fp contract(off)
+    TrainPixel px;
+    const float meas32 = in ? train_depth_at(J.meas, J.meas_step, J.depth_type, v, u) : 0.f;
+    const bool measured = in && __builtin_isfinite(meas32) && meas32 > 0.f;
+    int cat = kTrNoMeas;                 // the one counter of this pixel
+    float gt32 = 0.f;
+    if (MAP) {
+        if (measured) {
+            const float fx = ((float)u - J.cx) / J.fx, fy = ((float)v - J.cy) / J.fy, fz = 1.f;
+            float o[3], d[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                d[k] = (J.pose[k] * fx + J.pose[k + 4] * fy) + J.pose[k + 8] * fz;
+                o[k] = J.pose[12 + k];
+            }
+            RayResult H;
+            cast_ray<LAYER>(J.G, J.P, o, d, H);
+            cat = kTrNoHit;
+            if (H.status == kRayHit) {
+                const uint4 rec = J.normals[(H.rec - J.G.table) / kFields];
+                float c[3], nrm[3];
+                centroid(H.rec, H.rec[1], c);
+                double t = H.t;
+                const bool on_plane = surface_step(rec, c, o, d, J.P.t_min, (double)J.P.inv_leaf, J.shift2_max, nrm, t);
+                cat = kTrExamples;
+                if (J.require_plane && !on_plane) {
+                    cat = kTrOffPlane;
+                } else if (J.min_cos > 0.0) {
+                    const NormalRec R = normal_unpack(rec);
+                    const double q = ((double)R.n[0] * (double)d[0] + (double)R.n[1] * (double)d[1]) + (double)R.n[2] * (double)d[2];
+                    const double dd = ((double)d[0] * (double)d[0] + (double)d[1] * (double)d[1]) + (double)d[2] * (double)d[2];
+                    if (R.status != kClassKept || fabs(q) < J.min_cos * sqrt(dd)) cat = kTrGrazing;
+                }
+                if (cat == kTrExamples) gt32 = (float)t;
+            }
+        }
+    } else if (in) {
+        const float g = train_depth_at(J.gt, J.gt_step, J.depth_type, v, u);
+        if (!(__builtin_isfinite(g) && g > 0.f)) cat = kTrNoHit;
+        else if (measured) cat = kTrExamples, gt32 = g;
+    }
+    const bool reached = in && cat == kTrExamples;      // step 2 onwards
+    long long term[3] = {0ll, 0ll, 0ll};
+    int bin = 0;
+    if (reached) {
+        const double gt = (double)gt32, meas = (double)meas32;
+        const double mult = gt / meas;
+        if (meas > J.max_range || gt > J.max_range) {
+            cat = kTrRange;
+        } else if (mult > J.max_mult || mult < J.min_mult) {
+            cat = kTrMult;
+        } else {
+            const double sl = __builtin_floor(meas / J.bin_depth);
+            const int idx = sl < (double)(J.nb - 1) ? (int)sl : J.nb - 1;
+            const int by = min(v / J.bin_height, J.nby - 1), bx = min(u / J.bin_width, J.nbx - 1);
+            bin = (by * J.nbx + bx) * J.nb + idx;
+            term[0] = 1ll;
+            term[1] = __double2ll_rn(gt * gt * 1048576.0);
+            term[2] = __double2ll_rn(gt * meas * 1048576.0);
+        }
+    }
+    px.meas32 = meas32, px.gt32 = gt32, px.cat = cat, px.reached = reached, px.example = reached && cat == kTrExamples, px.bin = bin;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) px.term[q] = term[q];
+    return px;
+}
+// the counters of a pixel's wave (rgbd360_depth_train_stats) through ballots
+__device__ __forceinline__ void train_counters(unsigned long long* stats, int lane, bool in, int cat) {
+    unsigned long long b[kTrWords];
+#pragma unroll
+    for (int q = 1; q < kTrWords; ++q) b[q] = __ballot(in && cat == q);
+    b[kTrPixels] = __ballot(in);
+    if (lane == 0 && b[kTrPixels]) {      // one add per wave and counter
+#pragma unroll
+        for (int q = 0; q < kTrWords; ++q)
+            if (b[q]) atomicAdd(stats + q, (unsigned long long)__popcll(b[q]));
+    }
+}
+
 template <bool MAP, bool LAYER>
 __global__ __launch_bounds__(kTrainThreads) void k_depth_train(TrainJob J) {
 #pragma clang fp contract(off)
@@ -98,9 +189,10 @@ __global__ __launch_bounds__(kTrainThreads) void k_depth_train(TrainJob J) {
         for (int q = 0; q < 3; ++q) l_val[3 * threadIdx.x + q] = 0ull;
         __syncthreads();
     }
-#include "depth_train_gates.h"
+    const TrainPixel px = train_gates<MAP, LAYER>(J, v, u, in);
     if (J.form == 2) {
-        if (example) {
+        if (px.example) {
+            const int bin = px.bin;
             unsigned slot = ((unsigned)bin * 2654435761u) >> 24;      // (at most 256 distinct bins in a block: every one finds a slot)
             for (;;) {
                 const int k0 = atomicCAS(&l_key[slot], -1, bin);
@@ -108,7 +200,7 @@ __global__ __launch_bounds__(kTrainThreads) void k_depth_train(TrainJob J) {
                 slot = (slot + 1) & (kTrainThreads - 1);
             }
 #pragma unroll
-            for (int q = 0; q < 3; ++q) atomicAdd(&l_val[3 * slot + q], (unsigned long long)term[q]);
+            for (int q = 0; q < 3; ++q) atomicAdd(&l_val[3 * slot + q], (unsigned long long)px.term[q]);
         }
         __syncthreads();
         const int k0 = l_key[threadIdx.x];
@@ -117,10 +209,10 @@ __global__ __launch_bounds__(kTrainThreads) void k_depth_train(TrainJob J) {
             for (int q = 0; q < 3; ++q) atomicAdd(J.sums + (size_t)k0 * 3 + q, l_val[3 * threadIdx.x + q]);
         }
     } else {
-        wave_add_by_key<3>(example, bin, term, J.sums, J.form == 1);
+        wave_add_by_key<3>(px.example, px.bin, px.term, J.sums, J.form == 1);
     }
-#include "depth_train_counters.h"
-    if (in && J.gt_out) J.gt_out[(size_t)v * J.cols + u] = reached ? gt32 : 0.f;
+    train_counters(J.stats, lane, in, px.cat);
+    if (in && J.gt_out) J.gt_out[(size_t)v * J.cols + u] = px.reached ? px.gt32 : 0.f;
 }
 
 }  // namespace vmap

@@ -13,19 +13,23 @@
 // nearest centroid; a larger radius would need (2r + 1)^3 probes, callers who need a wider basin align against a coarser map first.
 // No cell is pruned: all 27 are looked up whatever the point's place in its cell.
 //
-// This header also holds what every method of alignment against the map shares with the loop (map_align_plane.h is the second
-// method, map_align_gicp.h the third, map_align_colour.h the fourth): the loop's state, init and solve kernels (LoopState<WORDS>, k_vmap_icp_init<WORDS>, k_vmap_icp_solve<Row>) and the host driver
-// (icp_prepare, icp_enqueue<M>, icp_align<M>, icp_eval<M>; the input of a call is voxel_map.h's MapInput).  A method is an evaluation
-// kernel, a row description (PointMethod) and a host description (PointIcp).  The evaluation kernels of every method are built from three shared pieces: the source load
+// This header also holds what every method of alignment against the map shares (map_align_plane.h is the second method,
+// map_align_gicp.h the third, map_align_colour.h the fourth): the evaluation (eval_tile<M, SRC, OUT> and its two kernels, k_vmap_eval<M, SRC>
+// here and k_vmap_eval_batch<M, SRC> in map_align_batch.h), the loop's state, init and solve (LoopState<WORDS>, icp_init_state,
+// icp_solve_rows<M>, k_vmap_icp_init<WORDS>, k_vmap_icp_solve<M>) and the host driver (icp_prepare, icp_launch_eval<M>, icp_enqueue<M>,
+// icp_align<M>, icp_eval<M>; the input of a call is voxel_map.h's MapInput).  A method is a row description with its Support, Args and
+// Tail (PointMethod) and a host description (PointIcp).  eval_tile is built from three shared pieces: the source load
 // (vmap::load_points, voxel_map.h, also k_vmap_insert's), the candidate search (vmap::search27 with the method's Support) and the block
-// epilogue (vmap::block_row_sum); a method's own text is its per-point tail.  tests/test_map_align_bits_gpu.py pins their bytes.
+// epilogue (vmap::block_row_sum); a method's own text is its per-point tail.  tests/test_map_align_bits_gpu.py pins the bytes of all four.
 //
-//   k_vmap_icp_eval   the shape of k_vmap_insert: 256 threads, four points per thread 256 apart, all loads of a thread first
+//   k_vmap_eval       the shape of k_vmap_insert: 256 threads, four points per thread 256 apart, all loads of a thread first
 //                     (load_points).  Per point search27: the first probe of all 27 cells is loaded before any is looked at (27
 //                     independent 8-byte loads in flight); a probe sequence goes on with plain loads.  The table is never written.
-//                     block_row_sum: a wave's 22 doubles (17 sums, three counters, the probe and search counts) go through a butterfly
-//                     of lane exchanges, the four waves through LDS, and the workgroup writes one partial row.  The pose comes from the loop's state in device memory; a launch of the
-//                     loop returns at once when the state says the loop has ended.
+//                     block_row_sum: a wave's row (point-to-point: 22 doubles -- 17 sums, three counters, the probe and search counts)
+//                     goes through a butterfly of lane exchanges, the four waves through LDS, and the workgroup writes one partial row.
+//                     The pose comes from the loop's state in device memory; a launch of the loop returns at once when the state says
+//                     the loop has ended.  (The measurement tools print it under the labels k_vmap_icp_eval, k_vmap_plane_eval,
+//                     k_vmap_gicp_eval and k_vmap_colour_eval, one per method, as earlier profiles do.)
 //   k_vmap_icp_solve  one workgroup: the rows added in ascending order (one lane per column), H and g, gn::step, status and the stop
 //                     test, one trace record per applied step, the new pose and the state word.
 //   host              max_iters x (eval, solve), the final eval and its solve, one copy of the state, ONE synchronisation; no host read
@@ -171,49 +175,206 @@ __host__ __device__ inline void icp_assemble(const double* s, float* H, float* g
     for (int k = 0; k < 6; ++k) g[k] = (float)s[10 + k];
 }
 
-// What the loop needs to know of a method's row: its width, where n and the traced sum of squares are, where the counters start (the
-// sums lie in front of them: n_valid, n_box_rejected, n_out_of_range, the method's own, then probes and points searched), H and g.
+// What every evaluation takes besides its method's own arguments: the table, the match rule, the per-point outputs of every method
+// (tests; either may be null): the matched voxel's indices and d2.
+struct EvalCommon {
+    const unsigned long long* table;
+    unsigned long long mask, min_count;
+    float max_dist2;
+    int32_t* key3;
+    float* d2_out;
+};
+
+// One workgroup's tile (bx, of image row by) of a source at the pose in P into one partial row: the evaluation of every method M, in the
+// single kernel and in the batched one, so that a tile gives the same row in both.  M is a row description: its places (kWords,
+// kCounters, kProbes, kSearched), the Support its search27 carries, its Args (a plain struct: its parameters and its extra per-point
+// output pointers) and its Tail, the per-thread object that is the method's own text:
+//   begin<SRC>(src, by)                    what it needs of the source beyond the points (coloured ICP: where the row's colours are)
+//   add(index, pose, w, match, kept, a)    a point of the thread into its sums and own counters
+//   store(index, a)                        that point's extra outputs
+//   row(out)                               its sums and own counters into the row
+// OUT: whether the per-point outputs exist at all (the batch has none: what only they need is then not kept).
+template <class M, int SRC, bool OUT>
+__device__ __forceinline__ void eval_tile(const Params& P, const Source& src, unsigned bx, unsigned by, const EvalCommon& c, const typename M::Args& a,
+                                          double (*s_red)[M::kWords], double* __restrict__ part_row) {
+#pragma clang fp contract(off)
+    float x[kPerThread], y[kPerThread], z[kPerThread];
+    bool in[kPerThread];
+    long long index[kPerThread];
+    load_points<SRC>(src, bx, by, x, y, z, in, index);
+    typename M::Tail tail;
+    tail.template begin<SRC>(src, by);
+
+    unsigned n_probes = 0, n_valid = 0, n_box = 0, n_range = 0, n_searched = 0;      // (integers until the reduction)
+    // one point after another through the one accumulator
+#pragma unroll
+    for (int k = 0; k < kPerThread; ++k) {
+        if (!in[k]) continue;
+        unsigned long long key = 0;
+        long long f[3];
+        float w[3];
+        const int cls = classify(P, x[k], y[k], z[k], key, f, w);
+        n_valid += cls >= 1 ? 1u : 0u;
+        n_box += cls == 1 ? 1u : 0u;
+        n_range += cls == 2 ? 1u : 0u;
+        Match<typename M::Support> mt;
+        if (cls == 3) {
+            n_searched += 1u;
+            mt = search27<typename M::Support>(c.table, c.mask, c.min_count, key, w, n_probes);
+        }
+        const bool kept = mt.best_key != kEmpty && mt.best <= c.max_dist2;
+        if (OUT && c.key3) store_key3(c.key3 + 3 * index[k], mt.best_key, kept);
+        if (OUT && c.d2_out) c.d2_out[index[k]] = mt.best;
+        tail.add(index[k], P.pose, w, mt, kept, a);
+        if (OUT) tail.store(index[k], a);
+    }
+
+    double row[M::kWords];
+    tail.row(row);
+    row[M::kCounters] = (double)n_valid;
+    row[M::kCounters + 1] = (double)n_box;
+    row[M::kCounters + 2] = (double)n_range;
+    row[M::kProbes] = (double)n_probes;
+    row[M::kSearched] = (double)n_searched;
+    block_row_sum<M::kWords>(row, s_red, part_row);
+}
+
+// a tail that needs nothing of the source beyond the points
+struct PointsOnly {
+    template <int SRC>
+    __device__ __forceinline__ void begin(const Source&, unsigned) {}
+};
+
+// point-to-point's tail: the 17 sums of a kept match
+struct PointTail : PointsOnly {
+    double acc[kIcpSums];
+    __device__ __forceinline__ PointTail() {
+#pragma unroll
+        for (int q = 0; q < kIcpSums; ++q) acc[q] = 0.0;
+    }
+    template <class Args>
+    __device__ __forceinline__ void add(long long, const float*, const float w[3], const Match<NoSupport>& mt, bool kept, const Args&) {
+#pragma clang fp contract(off)
+        if (kept) {
+            const double wx = w[0], wy = w[1], wz = w[2], ex = mt.be[0], ey = mt.be[1], ez = mt.be[2];
+            acc[0] += 1.0;
+            acc[1] += wx;
+            acc[2] += wy;
+            acc[3] += wz;
+            acc[4] += wx * wx;
+            acc[5] += wx * wy;
+            acc[6] += wx * wz;
+            acc[7] += wy * wy;
+            acc[8] += wy * wz;
+            acc[9] += wz * wz;
+            acc[10] += ex;
+            acc[11] += ey;
+            acc[12] += ez;
+            acc[13] += wy * ez - wz * ey;
+            acc[14] += wz * ex - wx * ez;
+            acc[15] += wx * ey - wy * ex;
+            acc[16] += (ex * ex + ey * ey) + ez * ez;
+        }
+    }
+    template <class Args>
+    __device__ __forceinline__ void store(long long, const Args&) {}
+    __device__ __forceinline__ void row(double* out) const {
+#pragma unroll
+        for (int q = 0; q < kIcpSums; ++q) out[q] = acc[q];
+    }
+};
+
+// What the loop and the evaluation need to know of a method: the row's width, where n and the traced sum of squares are, where the
+// counters start (the sums lie in front of them: n_valid, n_box_rejected, n_out_of_range, the method's own, then probes and points
+// searched), H and g; and eval_tile's Support, Args and Tail.
 struct PointMethod {
     static constexpr int kWords = kIcpWords, kN = 0, kSumSq = 16, kCounters = 17, kProbes = 20, kSearched = 21;
     __host__ __device__ static void assemble(const double* s, float* H, float* g) { icp_assemble(s, H, g); }
+    using Support = NoSupport;
+    struct Args {};
+    using Tail = PointTail;
 };
 
 template <int WORDS>
-__global__ void k_vmap_icp_init(LoopState<WORDS>* __restrict__ st, IcpPose guess) {
+__device__ __forceinline__ void icp_init_state(LoopState<WORDS>* __restrict__ st, const float* guess) {
     const int t = threadIdx.x;
-    if (t < 16) st->pose[t] = guess.m[t];
+    if (t < 16) st->pose[t] = guess[t];
     if (t < WORDS) st->row[t] = 0.0;
     if (t < 36) st->H[t] = 0.f;
     if (t < 6) st->g[t] = 0.f;
     if (t == 0) st->done = st->status = st->iterations = st->converged = 0;
 }
-
-// (the body behind the pose is map_align_eval_tile.h, that of k_vmap_icp_solve map_align_solve_rows.h: texts the batched kernels of
-// map_align_batch.h include too, so that a tile gives the same row and a job the same step in both; as included bodies, not as functions
-// both call, they leave these kernels' machine code what it was)
-template <int SRC>
-__global__ __launch_bounds__(kThreads) void k_vmap_icp_eval(Params P, Source src, const unsigned long long* __restrict__ table, unsigned long long mask,
-                                                            unsigned long long min_count, float max_dist2, const LoopState<kIcpWords>* __restrict__ st, int final_pass,
-                                                            double* __restrict__ part, int32_t* __restrict__ key3, float* __restrict__ d2_out) {
-#pragma clang fp contract(off)
-    if (!final_pass && st->done) return;
-    __shared__ double s_red[kThreads / 64][kIcpWords];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) P.pose[k] = st->pose[k];
-    const unsigned bx = blockIdx.x, by = blockIdx.y;
-    const auto part_row = [&] { return part + block_row<SRC>() * kIcpWords; };
-#include "map_align_eval_tile.h"
+template <int WORDS>
+__global__ void k_vmap_icp_init(LoopState<WORDS>* __restrict__ st, IcpPose guess) {
+    icp_init_state(st, guess.m);
 }
 
-// one workgroup: the rows added in ascending order (one lane per column), then lane 0: H and g, gn::step, status and the stop test, one
-// trace record per applied step, the new pose and the state word
+// the evaluation of the loop: the pose comes from the loop's state; a launch returns at once when the state says the loop has ended
+template <class M, int SRC>
+__global__ __launch_bounds__(kThreads) void k_vmap_eval(Params P, Source src, EvalCommon c, typename M::Args a, const LoopState<M::kWords>* __restrict__ st,
+                                                        int final_pass, double* __restrict__ part) {
+#pragma clang fp contract(off)
+    if (!final_pass && st->done) return;
+    __shared__ double s_red[kThreads / 64][M::kWords];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) P.pose[k] = st->pose[k];
+    eval_tile<M, SRC, true>(P, src, blockIdx.x, blockIdx.y, c, a, s_red, part + block_row<SRC>() * M::kWords);
+}
+
+// The solve of one alignment (the single kernel's, a job's of the batched one): the rows added in ascending order (one lane per column),
+// then lane 0: H and g, gn::step, status and the stop test, one trace record per applied step, the new pose and the state word
+template <class M>
+__device__ __forceinline__ void icp_solve_rows(LoopState<M::kWords>* __restrict__ st, rgbd360_map_align_trace* __restrict__ trace, const double* __restrict__ part,
+                                               int n_rows, int final_pass, long long min_matches, float eps, double* s_row) {
+#pragma clang fp contract(off)
+    const int t = threadIdx.x;
+    if (t < M::kWords) {         // the rows in ascending order
+        double s = 0.0;
+        for (int r = 0; r < n_rows; ++r) s += part[(size_t)r * M::kWords + t];
+        s_row[t] = s;
+        st->row[t] = s;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    const long long n = (long long)s_row[M::kN];
+    if (final_pass) {
+        M::assemble(s_row, st->H, st->g);
+        if (st->status == RGBD360_OK && n < min_matches) st->status = RGBD360_NO_VALID_PIXELS;
+        st->done = 1;
+        return;
+    }
+    if (n < min_matches) {
+        st->status = RGBD360_NO_VALID_PIXELS;
+        st->done = 1;
+        return;
+    }
+    float H[36], g[6], pose[16], pose_new[16], u[6];
+    M::assemble(s_row, H, g);
+    for (int k = 0; k < 16; ++k) pose[k] = st->pose[k];
+    if (gn::step(H, g, 0.f, pose, pose_new, u) != 0) {
+        st->status = RGBD360_ILL_POSED;
+        st->done = 1;
+        return;
+    }
+    for (int k = 0; k < 16; ++k) st->pose[k] = pose_new[k];
+    rgbd360_map_align_trace rec;
+    rec.n = n;
+    rec.sum_sq = s_row[M::kSumSq];
+    for (int k = 0; k < 6; ++k) rec.update[k] = u[k];
+    trace[st->iterations] = rec;
+    st->iterations += 1;
+    const float vv = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2], ww = (u[3] * u[3] + u[4] * u[4]) + u[5] * u[5];
+    if (vv <= eps && ww <= eps) {
+        st->converged = 1;
+        st->done = 1;
+    }
+}
 template <class M>
 __global__ __launch_bounds__(64) void k_vmap_icp_solve(LoopState<M::kWords>* __restrict__ st, rgbd360_map_align_trace* __restrict__ trace,
                                                        const double* __restrict__ part, int n_rows, int final_pass, long long min_matches, float eps) {
-#pragma clang fp contract(off)
     if (!final_pass && st->done) return;
     __shared__ double s_row[M::kWords];
-#include "map_align_solve_rows.h"
+    icp_solve_rows<M>(st, trace, part, n_rows, final_pass, min_matches, eps, s_row);
 }
 
 }  // namespace vmap
@@ -276,7 +437,7 @@ MapInput icp_eval_input(const void* depth, size_t depth_step, int depth_type, in
 
 // A method M (PointIcp here, PlaneIcp in map_align_plane.h) is its row (Row = vmap::PointMethod, also its base) and, for the host: Params and Result, the
 // public structs; Out, the per-point output pointers of an evaluation; check(m, params, job), the checked parameters into the job;
-// launch_eval(m, job, P, final_pass, out), the evaluation kernel; fill_extra(st, res), the result fields the method adds.
+// eval_args(m, job, out, args), what the evaluation kernel takes beyond EvalCommon; fill_extra(st, res), the result fields the method adds.
 template <class M>
 using IcpState = vmap::LoopState<M::kWords>;
 template <class M>
@@ -289,6 +450,23 @@ int icp_launch_init(rgbd360_map* m, const float pose[16]) {
     vmap::IcpPose g;
     memcpy(g.m, pose, sizeof(g.m));
     hipLaunchKernelGGL((vmap::k_vmap_icp_init<M::kWords>), dim3(1), dim3(64), 0, m->s->stream, icp_state<M>(m), g);
+    HIPC(m, hipGetLastError());
+    return 0;
+}
+// what every evaluation of a job takes; the per-point outputs of a final pass, or none
+vmap::EvalCommon icp_common(rgbd360_map* m, const IcpJob& job, int32_t* key3, float* d2) {
+    return {(const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, job.p.max_dist * job.p.max_dist, key3, d2};
+}
+// the evaluation kernel of method M on a job: M::eval_args is the method's host-side preparation (its layers, its parameters, its outputs)
+template <class M>
+int icp_launch_eval(rgbd360_map* m, const IcpJob& job, const vmap::Params& P, int final_pass, const typename M::Out& o) {
+    typename M::Args a{};
+    if (const int rc = M::eval_args(m, job, o, a)) return rc;
+    const vmap::EvalCommon c = icp_common(m, job, o.key3, o.d2);
+    with_choice<0, 1>(job.src.cloud, [&](auto S) {
+        hipLaunchKernelGGL((vmap::k_vmap_eval<typename M::Row, decltype(S)::value>), job.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.src, c, a,
+                           (const IcpState<M>*)icp_state<M>(m), final_pass, m->a_part.get());
+    });
     HIPC(m, hipGetLastError());
     return 0;
 }
@@ -305,10 +483,10 @@ int icp_enqueue(rgbd360_map* m, const IcpJob& job, const float guess[16], int it
     const vmap::Params P = vmap_params(m, guess);
     if (const int rc = icp_launch_init<M>(m, guess)) return rc;
     for (int it = 0; it < iters; ++it) {
-        if (const int rc = M::launch_eval(m, job, P, 0, typename M::Out{})) return rc;
+        if (const int rc = icp_launch_eval<M>(m, job, P, 0, typename M::Out{})) return rc;
         if (const int rc = icp_launch_solve<M>(m, job, 0)) return rc;
     }
-    if (const int rc = M::launch_eval(m, job, P, 1, out)) return rc;
+    if (const int rc = icp_launch_eval<M>(m, job, P, 1, out)) return rc;
     if (const int rc = icp_launch_solve<M>(m, job, 1)) return rc;
     const size_t bytes = sizeof(IcpState<M>) + (size_t)iters * sizeof(rgbd360_map_align_trace);
     HIPC(m, hipMemcpyAsync(m->a_host, m->a_state, bytes, hipMemcpyDeviceToHost, m->s->stream));
@@ -422,16 +600,7 @@ struct PointIcp : vmap::PointMethod {
         float* d2 = nullptr;
     };
     static int check(rgbd360_map* m, const Params* params, IcpJob& job) { return icp_check_params(m, params, job.p); }
-    static int launch_eval(rgbd360_map* m, const IcpJob& job, const vmap::Params& P, int final_pass, const Out& o) {
-        const float max_dist2 = job.p.max_dist * job.p.max_dist;
-        with_choice<0, 1>(job.src.cloud, [&](auto S) {
-            hipLaunchKernelGGL((vmap::k_vmap_icp_eval<decltype(S)::value>), job.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.src,
-                               (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, max_dist2,
-                               (const IcpState<PointIcp>*)icp_state<PointIcp>(m), final_pass, m->a_part.get(), o.key3, o.d2);
-        });
-        HIPC(m, hipGetLastError());
-        return 0;
-    }
+    static int eval_args(rgbd360_map*, const IcpJob&, const Out&, Args&) { return 0; }
     static void fill_extra(const IcpState<PointIcp>&, Result*) {}
 };
 }  // namespace
@@ -487,8 +656,8 @@ extern "C" int rgbd360_map_time_align(rgbd360_map* m, const void* depth_dev, siz
     if (timer.rc) return timer.rc;
     int& rc = timer.rc;
     rc = icp_launch_init<PointIcp>(m, pose);
-    if (rc == 0) rc = PointIcp::launch_eval(m, job, P, 1, {});      // once untimed: code and tables loaded
-    timer.timed(avg_us[0], reps, [&] { return PointIcp::launch_eval(m, job, P, 1, {}); });
+    if (rc == 0) rc = icp_launch_eval<PointIcp>(m, job, P, 1, {});      // once untimed: code and tables loaded
+    timer.timed(avg_us[0], reps, [&] { return icp_launch_eval<PointIcp>(m, job, P, 1, {}); });
     timer.timed(avg_us[1], reps, [&] { return icp_launch_solve<PointIcp>(m, job, 1); });
     if (rc == 0 && probes) rc = icp_read_probes<PointIcp>(m, probes);
     timer.timed(avg_us[2], 1, [&] { return vmap_launch_insert(m, P, job.src); });

@@ -5,21 +5,21 @@
 // pay a synchronisation apiece.  Part of the Frame360 translation unit, behind map_align.h and map_align_plane.h.
 //
 // Definition (include/rgbd360_hip.h, "many alignments against the map in lock step").  The driver is written over the
-// method description M as icp_enqueue<M> is (map_align.h); a method joins by naming its batched evaluation launch (BatchEval<M>).  Point-to-
-// point and point-to-plane are instantiated.
+// method description M as icp_enqueue<M> is (map_align.h), the batched evaluation launch (batch_launch_eval<M>) included.  Point-to-point
+// and point-to-plane are instantiated.
 //
 //   BatchJob                     a job in device memory: its Source, its guess, its own grid extent (tiles per image row, workgroups), its
 //                                LoopState and trace, its slice of the partial rows.  Next to the jobs the exclusive prefix of their
 //                                workgroup counts.
-//   k_vmap_icp_init_batch        one 64-lane workgroup per job: k_vmap_icp_init on the job's state from the job's guess.
-//   k_vmap_icp_eval_batch<SRC>   ONE flat launch over the workgroups of all jobs.  A workgroup finds its job by bisection of the prefix
-//   k_vmap_plane_eval_batch<SRC> table (at most 10 steps for 1024 jobs, the same in every lane), returns before any other load when the job
-//                                has ended, and evaluates tile (local % gx, local / gx) of the job's source at the job's pose with the
-//                                text of the single kernels (map_align_eval_tile.h, map_align_plane_eval_tile.h) into row `local` of the
-//                                job's slice: the row vmap::block_row gives under the job's own grid.  Clouds of one batch may differ in
-//                                size 100-fold: a grid.z per job over the largest grid would launch mostly empty workgroups.
-//   k_vmap_icp_solve_batch<Row>  one 64-lane workgroup per job: the text of k_vmap_icp_solve (map_align_solve_rows.h) on the job's state,
-//                                rows (ascending) and trace.  The same rows added in the same order: the sums of the single call.
+//   k_vmap_icp_init_batch        one 64-lane workgroup per job: icp_init_state, as k_vmap_icp_init, on the job's state from the job's guess.
+//   k_vmap_eval_batch<M, SRC>    ONE flat launch over the workgroups of all jobs.  A workgroup finds its job by bisection of the prefix
+//                                table (at most 10 steps for 1024 jobs, the same in every lane), returns before any other load when the job
+//                                has ended, and evaluates tile (local % gx, local / gx) of the job's source at the job's pose with
+//                                eval_tile<M, SRC, false>, the function k_vmap_eval calls, into row `local` of the job's slice: the row
+//                                vmap::block_row gives under the job's own grid.  Clouds of one batch may differ in size 100-fold: a
+//                                grid.z per job over the largest grid would launch mostly empty workgroups.
+//   k_vmap_icp_solve_batch<Row>  one 64-lane workgroup per job: icp_solve_rows<Row>, the function k_vmap_icp_solve calls, on the job's
+//                                state, rows (ascending) and trace.  The same rows added in the same order: the sums of the single call.
 //   host                         one init, max_iters x (eval, solve), the final pass, one copy of all states and traces, ONE
 //                                synchronisation: 2 max_iters + 3 launches whatever n_jobs is.  Host inputs go up packed into the map's
 //                                upload buffer at 256-byte aligned offsets, each once however many jobs use it.
@@ -51,71 +51,34 @@ __device__ __forceinline__ int batch_job_of(const unsigned* __restrict__ prefix,
 template <int WORDS>
 __global__ __launch_bounds__(64) void k_vmap_icp_init_batch(const BatchJob* __restrict__ jobs) {
     const BatchJob& job = jobs[blockIdx.x];
-    LoopState<WORDS>* st = static_cast<LoopState<WORDS>*>(job.state);
-    const int t = threadIdx.x;
-    if (t < 16) st->pose[t] = job.guess[t];
-    if (t < WORDS) st->row[t] = 0.0;
-    if (t < 36) st->H[t] = 0.f;
-    if (t < 6) st->g[t] = 0.f;
-    if (t == 0) st->done = st->status = st->iterations = st->converged = 0;
+    icp_init_state(static_cast<LoopState<WORDS>*>(job.state), job.guess);
 }
 
-template <int SRC>
-__global__ __launch_bounds__(kThreads) void k_vmap_icp_eval_batch(Params P, const BatchJob* __restrict__ jobs, const unsigned* __restrict__ prefix, int n_jobs,
-                                                                  const unsigned long long* __restrict__ table, unsigned long long mask,
-                                                                  unsigned long long min_count, float max_dist2, int final_pass) {
+// (no per-point outputs in a batch: the pointers of c and a are null and not looked at)
+template <class M, int SRC>
+__global__ __launch_bounds__(kThreads) void k_vmap_eval_batch(Params P, const BatchJob* __restrict__ jobs, const unsigned* __restrict__ prefix, int n_jobs,
+                                                              EvalCommon c, typename M::Args a, int final_pass) {
 #pragma clang fp contract(off)
     const int j = batch_job_of(prefix, n_jobs, blockIdx.x);
     const BatchJob& job = jobs[j];
-    const LoopState<kIcpWords>* st = static_cast<const LoopState<kIcpWords>*>(job.state);
+    const LoopState<M::kWords>* st = static_cast<const LoopState<M::kWords>*>(job.state);
     if (!final_pass && st->done) return;
-    __shared__ double s_red[kThreads / 64][kIcpWords];
+    __shared__ double s_red[kThreads / 64][M::kWords];
 #pragma unroll
     for (int k = 0; k < 16; ++k) P.pose[k] = st->pose[k];
     const Source src = job.src;
     const unsigned local = blockIdx.x - prefix[j], gx = job.gx;
     const unsigned bx = SRC == 0 ? local % gx : local, by = SRC == 0 ? local / gx : 0u;
-    const auto part_row = [&] { return job.part + (size_t)local * kIcpWords; };
-    int32_t* const key3 = nullptr;       // (no per-point outputs in a batch)
-    float* const d2_out = nullptr;
-#include "map_align_eval_tile.h"
-}
-
-template <int SRC>
-__global__ __launch_bounds__(kThreads) void k_vmap_plane_eval_batch(Params P, const BatchJob* __restrict__ jobs, const unsigned* __restrict__ prefix, int n_jobs,
-                                                                    const unsigned long long* __restrict__ table, unsigned long long mask,
-                                                                    unsigned long long min_count, float max_dist2, unsigned min_support, double max_flatness,
-                                                                    int final_pass) {
-#pragma clang fp contract(off)
-    const int j = batch_job_of(prefix, n_jobs, blockIdx.x);
-    const BatchJob& job = jobs[j];
-    const LoopState<kPlaneWords>* st = static_cast<const LoopState<kPlaneWords>*>(job.state);
-    if (!final_pass && st->done) return;
-    __shared__ double s_red[kThreads / 64][kPlaneWords];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) P.pose[k] = st->pose[k];
-    const Source src = job.src;
-    const unsigned local = blockIdx.x - prefix[j], gx = job.gx;
-    const unsigned bx = SRC == 0 ? local % gx : local, by = SRC == 0 ? local / gx : 0u;
-    const auto part_row = [&] { return job.part + (size_t)local * kPlaneWords; };
-    int32_t* const key3 = nullptr;       // (no per-point outputs in a batch)
-    float* const d2_out = nullptr;
-    double* const nr_out = nullptr;
-    uint8_t* const class_out = nullptr;
-#include "map_align_plane_eval_tile.h"
+    eval_tile<M, SRC, false>(P, src, bx, by, c, a, s_red, job.part + (size_t)local * M::kWords);
 }
 
 template <class M>
 __global__ __launch_bounds__(64) void k_vmap_icp_solve_batch(const BatchJob* __restrict__ jobs, int final_pass, long long min_matches, float eps) {
-#pragma clang fp contract(off)
     const BatchJob& job = jobs[blockIdx.x];
     LoopState<M::kWords>* const st = static_cast<LoopState<M::kWords>*>(job.state);
     if (!final_pass && st->done) return;
     __shared__ double s_row[M::kWords];
-    rgbd360_map_align_trace* const trace = job.trace;
-    const double* const part = job.part;
-    const int n_rows = (int)job.n_rows;
-#include "map_align_solve_rows.h"
+    icp_solve_rows<M>(st, job.trace, job.part, (int)job.n_rows, final_pass, min_matches, eps, s_row);
 }
 
 }  // namespace vmap
@@ -135,34 +98,19 @@ struct BatchLaunch {
     bool cloud;
 };
 
-// the batched evaluation launch of a method
+// the batched evaluation launch of method M: icp_launch_eval's preparation, no per-point outputs
 template <class M>
-struct BatchEval;
-template <>
-struct BatchEval<PointIcp> {
-    static int launch(rgbd360_map* m, const IcpJob& job, const BatchLaunch& b, const vmap::Params& P, int final_pass) {
-        const float max_dist2 = job.p.max_dist * job.p.max_dist;
-        with_choice<0, 1>(b.cloud, [&](auto S) {
-            hipLaunchKernelGGL((vmap::k_vmap_icp_eval_batch<decltype(S)::value>), dim3(b.n_rows), dim3(vmap::kThreads), 0, m->s->stream, P, b.jobs, b.prefix,
-                               b.n_jobs, (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, max_dist2, final_pass);
-        });
-        HIPC(m, hipGetLastError());
-        return 0;
-    }
-};
-template <>
-struct BatchEval<PlaneIcp> {
-    static int launch(rgbd360_map* m, const IcpJob& job, const BatchLaunch& b, const vmap::Params& P, int final_pass) {
-        const float max_dist2 = job.p.max_dist * job.p.max_dist;
-        with_choice<0, 1>(b.cloud, [&](auto S) {
-            hipLaunchKernelGGL((vmap::k_vmap_plane_eval_batch<decltype(S)::value>), dim3(b.n_rows), dim3(vmap::kThreads), 0, m->s->stream, P, b.jobs, b.prefix,
-                               b.n_jobs, (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, max_dist2,
-                               (unsigned)job.min_support, (double)job.max_flatness, final_pass);
-        });
-        HIPC(m, hipGetLastError());
-        return 0;
-    }
-};
+int batch_launch_eval(rgbd360_map* m, const IcpJob& job, const BatchLaunch& b, const vmap::Params& P, int final_pass) {
+    typename M::Args a{};
+    if (const int rc = M::eval_args(m, job, typename M::Out{}, a)) return rc;
+    const vmap::EvalCommon c = icp_common(m, job, nullptr, nullptr);
+    with_choice<0, 1>(b.cloud, [&](auto S) {
+        hipLaunchKernelGGL((vmap::k_vmap_eval_batch<typename M::Row, decltype(S)::value>), dim3(b.n_rows), dim3(vmap::kThreads), 0, m->s->stream, P, b.jobs, b.prefix,
+                           b.n_jobs, c, a, final_pass);
+    });
+    HIPC(m, hipGetLastError());
+    return 0;
+}
 
 size_t batch_align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -302,7 +250,7 @@ int icp_align_batch(rgbd360_map* m, const std::vector<MapInput>& inputs, const r
     HIPC(m, hipGetLastError());
     for (int it = 0; it <= iters; ++it) {
         const int final_pass = it == iters ? 1 : 0;
-        if (const int rc = BatchEval<M>::launch(m, base, b, P, final_pass)) return rc;
+        if (const int rc = batch_launch_eval<M>(m, base, b, P, final_pass)) return rc;
         hipLaunchKernelGGL((vmap::k_vmap_icp_solve_batch<typename M::Row>), dim3(n_live), dim3(64), 0, stream, b.jobs, final_pass, base.p.min_matches, base.p.eps);
         HIPC(m, hipGetLastError());
     }

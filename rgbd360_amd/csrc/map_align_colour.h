@@ -2,8 +2,8 @@
 // of a posed sphere frame, or of a cloud with colours, against the resident voxel map: the geometric point-to-plane term on the map's
 // resident normals joined with a photometric term on the map's resident intensity gradients, which observes the pose along the surfaces
 // where geometry alone slides (a corridor, a floor and one wall).  Part of the Frame360 translation unit, behind map_colour.h: the two
-// layers are the map's (normals_layer, colour_layer), the match, the row sum and the loop are map_align.h's.  Here: the evaluation kernel,
-// the row's description (ColourMethod) and the host's (ColourIcp).
+// layers are the map's (normals_layer, colour_layer), the match, the row sum and the loop are map_align.h's.  Here: the evaluation's tail
+// (ColourTail), the row's description (ColourMethod) and the host's (ColourIcp).
 //
 // Definition (include/rgbd360_hip.h, "coloured ICP against the map"; tests/map_colour_reference.py restates it in numpy).
 // Per source point at the current pose, float64 with + - x / only, no contraction:
@@ -19,10 +19,9 @@
 //   6 38 float64 words per workgroup row (kColourWords), the rows added in ascending order; no floating-point atomics.
 //   7 H and g straight from the row, cast to float32, gn::step with lambda 0, the stop tests and statuses of map_align.h.
 //
-//   k_vmap_colour_eval   the shape of k_vmap_gicp_eval (256 threads, four points per thread one after another through one row accumulator
-//                        of 31 doubles, load_points, search27, block_row_sum, the pose from the loop's state, the table and both layers
-//                        read-only).  Per kept point two independent 16-byte reads at the matched slot (the slot rides in search27's
-//                        Match); the source's three colour bytes are loaded with its point.
+//   k_vmap_eval<ColourMethod, SRC>  map_align.h's evaluation on this row, the table and both layers read-only.  Per kept point two
+//                        independent 16-byte reads at the matched slot (the slot rides in search27's Match) and, beside them, the
+//                        source point's three colour bytes (ColourTail).
 //   k_vmap_icp_solve<ColourMethod>  map_align.h's solve kernel on this row.
 #pragma once
 
@@ -35,61 +34,40 @@ enum { kCoN = 0, kCoH = 1, kCoG = 22, kCoCost = 28, kCoGG = 29, kCoCC = 30, kCoV
        kCoProbes = 36, kCoSearched = 37 };
 enum { kColourKept = 1, kColourNoNormal = 2, kColourNoGradient = 4 };      // the bits of a point's class byte
 
-// per-point outputs (tests; any may be null): key3 / d2_out as in k_vmap_icp_eval (the key of the kept MATCH whatever the point's class),
-// res_out two doubles per point (r_G and r_C; zeros unless the point contributes), class_out one byte per point: kColourKept a kept
-// match, | kColourNoNormal it was dropped, | kColourNoGradient it contributes with d = 0.
-template <int SRC>
-__global__ __launch_bounds__(kThreads) void k_vmap_colour_eval(Params P, Source src, const unsigned long long* __restrict__ table, unsigned long long mask,
-                                                               unsigned long long min_count, float max_dist2, const uint4* __restrict__ normals,
-                                                               const uint4* __restrict__ colours, float lambda_geometric,
-                                                               const LoopState<kColourWords>* __restrict__ st, int final_pass, double* __restrict__ part,
-                                                               int32_t* __restrict__ key3, float* __restrict__ d2_out, double* __restrict__ res_out,
-                                                               uint8_t* __restrict__ class_out) {
-#pragma clang fp contract(off)
-    if (!final_pass && st->done) return;
-    __shared__ double s_red[kThreads / 64][kColourWords];
+// what the evaluation takes beyond EvalCommon: the map's two layers by slot.  The per-point outputs (tests; either may be null): res_out
+// two doubles per point (r_G and r_C; zeros unless the point contributes), class_out one byte per point: kColourKept a kept match, |
+// kColourNoNormal it was dropped, | kColourNoGradient it contributes with d = 0 (key3: the key of the kept MATCH whatever the class).
+struct ColourArgs {
+    const uint4* normals;
+    const uint4* colours;
+    float lambda_geometric;
+    double* res_out;
+    uint8_t* class_out;
+};
+// coloured ICP's tail: steps 2-5 of the definition
+struct ColourTail {
+    const uint8_t* crow;             // the colours by the point's index, as k_vmap_insert takes them (the image's row pointer moved back by the row's first index)
+    double acc[kCoCC + 1];           // n, H (21), g (6), the cost, r_G r_G, r_C r_C
+    unsigned n_no_normal = 0, n_no_gradient = 0;
+    int pclass;                      // of the point added last, for store(): its class and residuals
+    double rg, rc;
+    __device__ __forceinline__ ColourTail() {
 #pragma unroll
-    for (int k = 0; k < 16; ++k) P.pose[k] = st->pose[k];
-
-    float x[kPerThread], y[kPerThread], z[kPerThread];
-    bool in[kPerThread];
-    long long index[kPerThread];
-    load_points<SRC>(src, x, y, z, in, index);
-    // the colour of each point by its index, as k_vmap_insert takes it (the image's row pointer moved back by the row's first index)
-    const uint8_t* crow = SRC == 0 ? src.rgb + (size_t)blockIdx.y * src.rgb_step - 3 * (size_t)blockIdx.y * src.cols : src.rgb;
-    unsigned char c[kPerThread][3];
-#pragma unroll
-    for (int k = 0; k < kPerThread; ++k) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) c[k][q] = crow[3 * (size_t)index[k] + q];
+        for (int q = 0; q <= kCoCC; ++q) acc[q] = 0.0;
     }
-    const double lam = (double)lambda_geometric, oml = 1.0 - lam;
-
-    double acc[kCoCC + 1];           // n, H (21), g (6), the cost, r_G r_G, r_C r_C; the counters are integers until the reduction
-#pragma unroll
-    for (int q = 0; q <= kCoCC; ++q) acc[q] = 0.0;
-    unsigned n_probes = 0, n_valid = 0, n_box = 0, n_range = 0, n_no_normal = 0, n_no_gradient = 0, n_searched = 0;
-    // one point after another through the one accumulator
-#pragma unroll
-    for (int k = 0; k < kPerThread; ++k) {
-        if (!in[k]) continue;
-        unsigned long long key = 0;
-        long long f[3];
-        float w[3];
-        const int cls = classify(P, x[k], y[k], z[k], key, f, w);
-        n_valid += cls >= 1 ? 1u : 0u;
-        n_box += cls == 1 ? 1u : 0u;
-        n_range += cls == 2 ? 1u : 0u;
-        Match<NoSupport> mt;
-        if (cls == 3) {
-            n_searched += 1u;
-            mt = search27<NoSupport>(table, mask, min_count, key, w, n_probes);
-        }
-        const bool kept = mt.best_key != kEmpty && mt.best <= max_dist2;
-        int pclass = 0;
-        double rg = 0.0, rc = 0.0;
+    template <int SRC>
+    __device__ __forceinline__ void begin(const Source& src, unsigned by) {
+        crow = SRC == 0 ? src.rgb + (size_t)by * src.rgb_step - 3 * (size_t)by * src.cols : src.rgb;
+    }
+    __device__ __forceinline__ void add(long long index, const float*, const float w[3], const Match<NoSupport>& mt, bool kept, const ColourArgs& args) {
+#pragma clang fp contract(off)
+        const double lam = (double)args.lambda_geometric, oml = 1.0 - lam;
+        pclass = 0;
+        rg = 0.0, rc = 0.0;
         if (kept) {
-            const uint4 nw = normals[mt.best_slot], cw = colours[mt.best_slot];      // the two reads, neither waits for the other
+            const uint4 nw = args.normals[mt.best_slot], cw = args.colours[mt.best_slot];      // the two reads and the point's three bytes: none waits for another
+            const uint8_t* c = crow + 3 * (size_t)index;
+            const unsigned c0 = c[0], c1 = c[1], c2 = c[2];
             const NormalRec nr = normal_unpack(nw);
             const ColourRec cr = colour_unpack(cw);
             if (nr.status != kClassKept) {
@@ -103,7 +81,7 @@ __global__ __launch_bounds__(kThreads) void k_vmap_colour_eval(Params P, Source 
                 const double wx = w[0], wy = w[1], wz = w[2], ex = mt.be[0], ey = mt.be[1], ez = mt.be[2];
                 rg = (nx * ex + ny * ey) + nz * ez;
                 const double px = ex - rg * nx, py = ey - rg * ny, pz = ez - rg * nz;
-                rc = ((double)cr.I + ((dx * px + dy * py) + dz * pz)) - intensity64(c[k][0], c[k][1], c[k][2], 1ull);
+                rc = ((double)cr.I + ((dx * px + dy * py) + dz * pz)) - intensity64(c0, c1, c2, 1ull);
                 const double JG[6] = {nx, ny, nz, wy * nz - wz * ny, wz * nx - wx * nz, wx * ny - wy * nx};
                 const double JC[6] = {dx, dy, dz, wy * dz - wz * dy, wz * dx - wx * dz, wx * dy - wy * dx};
                 acc[kCoN] += 1.0;
@@ -121,32 +99,30 @@ __global__ __launch_bounds__(kThreads) void k_vmap_colour_eval(Params P, Source 
                 acc[kCoCC] += cc;
             }
         }
-        if (key3) store_key3(key3 + 3 * index[k], mt.best_key, kept);
-        if (d2_out) d2_out[index[k]] = mt.best;
-        if (res_out) {
-            res_out[2 * index[k]] = rg;
-            res_out[2 * index[k] + 1] = rc;
-        }
-        if (class_out) class_out[index[k]] = (uint8_t)pclass;
     }
-
-    double row[kColourWords];
+    __device__ __forceinline__ void store(long long index, const ColourArgs& args) const {
+        if (args.res_out) {
+            args.res_out[2 * index] = rg;
+            args.res_out[2 * index + 1] = rc;
+        }
+        if (args.class_out) args.class_out[index] = (uint8_t)pclass;
+    }
+    __device__ __forceinline__ void row(double* out) const {
 #pragma unroll
-    for (int q = 0; q <= kCoCC; ++q) row[q] = acc[q];
-    row[kCoValid] = (double)n_valid;
-    row[kCoBox] = (double)n_box;
-    row[kCoRange] = (double)n_range;
-    row[kCoNoNormal] = (double)n_no_normal;
-    row[kCoNoGradient] = (double)n_no_gradient;
-    row[kCoProbes] = (double)n_probes;
-    row[kCoSearched] = (double)n_searched;
-    block_row_sum<kColourWords>(row, s_red, part + block_row<SRC>() * kColourWords);
-}
+        for (int q = 0; q <= kCoCC; ++q) out[q] = acc[q];
+        out[kCoNoNormal] = (double)n_no_normal;
+        out[kCoNoGradient] = (double)n_no_gradient;
+    }
+};
 
 struct ColourMethod {
     static constexpr int kWords = kColourWords, kN = kCoN, kSumSq = kCoCost, kCounters = kCoValid, kProbes = kCoProbes, kSearched = kCoSearched;
     __host__ __device__ static void assemble(const double* s, float* H, float* g) { plane_assemble(s, H, g); }      // (the plane row's places)
+    using Support = NoSupport;
+    using Args = ColourArgs;
+    using Tail = ColourTail;
 };
+static_assert(kCoValid + 1 == kCoBox && kCoValid + 2 == kCoRange, "the three counters of every method lead the row's counters");
 static_assert(kCoH == kPlH && kCoG == kPlG, "H and g lie where plane_assemble reads them");
 static_assert(kColourWords <= kIcpMaxWords, "the buffers of a map hold the widest row");
 
@@ -184,8 +160,8 @@ struct ColourIcp : vmap::ColourMethod {
         return 0;
     }
     // the map's two layers under this call's parameters, built or reused (a comparison on the host while the map's revision and the
-    // parameters stand), then the kernel behind them on the stream
-    static int launch_eval(rgbd360_map* m, const IcpJob& job, const vmap::Params& P, int final_pass, const Out& o) {
+    // parameters stand), ahead of the kernel on the stream
+    static int eval_args(rgbd360_map* m, const IcpJob& job, const Out& o, Args& a) {
         if (!job.src.rgb) return vmap_fail(m, -1, "coloured ICP needs the source's colours");
         const uint4 *normals = nullptr, *colours = nullptr;
         if (m->n_voxels > 0) {       // (an empty map matches nothing: the layers are never read)
@@ -194,14 +170,7 @@ struct ColourIcp : vmap::ColourMethod {
             normals = m->nm_layer.get();
             colours = m->cl_layer.get();
         }
-        const float max_dist2 = job.p.max_dist * job.p.max_dist;
-        with_choice<0, 1>(job.src.cloud, [&](auto S) {
-            hipLaunchKernelGGL((vmap::k_vmap_colour_eval<decltype(S)::value>), job.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.src,
-                               (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, max_dist2, normals, colours,
-                               job.lambda_geometric, (const IcpState<ColourIcp>*)icp_state<ColourIcp>(m), final_pass, m->a_part.get(), o.key3, o.d2,
-                               o.residuals, o.cls);
-        });
-        HIPC(m, hipGetLastError());
+        a = {normals, colours, job.lambda_geometric, o.residuals, o.cls};
         return 0;
     }
     static void fill_extra(const IcpState<ColourIcp>& st, Result* res) {
@@ -290,11 +259,11 @@ extern "C" int rgbd360_map_time_align_colour(rgbd360_map* m, const uint8_t* rgb_
     int& rc = timer.rc;
     // generalized ICP's kernel first, on the same frame, map and buffers, then this method's, whose state stays behind
     rc = icp_launch_init<GicpIcp>(m, pose);
-    if (rc == 0) rc = GicpIcp::launch_eval(m, job, P, 1, {});       // once untimed: code and tables loaded, the normal layer built
-    timer.timed(avg_us[1], reps, [&] { return GicpIcp::launch_eval(m, job, P, 1, {}); });
+    if (rc == 0) rc = icp_launch_eval<GicpIcp>(m, job, P, 1, {});       // once untimed: code and tables loaded, the normal layer built
+    timer.timed(avg_us[1], reps, [&] { return icp_launch_eval<GicpIcp>(m, job, P, 1, {}); });
     if (rc == 0) rc = icp_launch_init<ColourIcp>(m, pose);
-    if (rc == 0) rc = ColourIcp::launch_eval(m, job, P, 1, {});     // (and the colour layer built)
-    timer.timed(avg_us[0], reps, [&] { return ColourIcp::launch_eval(m, job, P, 1, {}); });
+    if (rc == 0) rc = icp_launch_eval<ColourIcp>(m, job, P, 1, {});     // (and the colour layer built)
+    timer.timed(avg_us[0], reps, [&] { return icp_launch_eval<ColourIcp>(m, job, P, 1, {}); });
     timer.timed(avg_us[2], reps, [&] { return icp_launch_solve<ColourIcp>(m, job, 1); });
     if (rc == 0 && probes) rc = icp_read_probes<ColourIcp>(m, probes);
     if (const int failed = timer.finish(avg_us, 0, reps)) return failed;

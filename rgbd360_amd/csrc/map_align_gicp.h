@@ -3,8 +3,8 @@
 // (pcl::GeneralizedIterativeClosestPoint on two voxel-filtered clouds: OdometryRGBD360.cpp:98-114, 210-222, RegisterPairRGBD360.cpp:111-118,
 // MethodsRegisterRGBD360.cpp:294-320, OdometryKeyFrame360.cpp:124-140) with the map as its target.  Part of the Frame360 translation
 // unit, behind map_normals.h: the target's covariance model is the map's resident per-voxel normal (normals_layer), the match, the row
-// sum and the loop are map_align.h's.  Here: the weight of a match, the evaluation kernel, the row's description (GicpMethod) and the
-// host's (GicpIcp).
+// sum and the loop are map_align.h's.  Here: the weight of a match, the evaluation's tail (GicpTail), the row's description (GicpMethod)
+// and the host's (GicpIcp).
 //
 // Definition (include/rgbd360_hip.h, "generalized ICP against the map"; tests/map_align_gicp_reference.py restates it in
 // numpy).  Per source point at the current pose T = [R | t], float64 with + - x / sqrt only, no contraction:
@@ -22,10 +22,9 @@
 // normal and 1 across it, normals on both sides plane-to-plane; a pair without a planar side degrades to point-to-point instead of
 // dropping out, which is what map_align_plane.h does with corners and edges.
 //
-//   k_vmap_gicp_eval   the shape of k_vmap_plane_eval (256 threads, four points per thread one after another through one row
-//                      accumulator of 30 doubles, load_points, search27, block_row_sum, the pose from the loop's state, the table and
-//                      the layer read-only).  No plane fit in the loop: per kept point ONE 16-byte read of the matched slot's record
-//                      in the normal layer (the slot rides in search27's Match) and, with a normal array, 12 bytes of the source.
+//   k_vmap_eval<GicpMethod, SRC>  map_align.h's evaluation on this row, the table and the layer read-only.  No plane fit in the loop: per
+//                      kept point ONE 16-byte read of the matched slot's record in the normal layer (the slot rides in search27's Match)
+//                      and, with a normal array, 12 bytes of the source (GicpTail).
 //   k_vmap_icp_solve<GicpMethod>  map_align.h's solve kernel on this row.
 #pragma once
 
@@ -87,65 +86,48 @@ __host__ __device__ inline int gicp_weight(const double nb[3], bool has_b, const
     return (has_b ? kGicpTarget : 0) | (has_source ? kGicpSource : 0);
 }
 
-// per-point outputs (tests; any may be null): key3 / d2_out as in k_vmap_icp_eval, mc_out seven doubles per point (M00 M01 M02 M11 M12 M22
-// and the cost e^T M e; zeros without a kept match), class_out one byte per point (kGicpKept | kGicpTarget | kGicpSource).
-// normal: the source's normals by the point's index (a cloud's), or null; layer: the map's normal records by slot, or null (no target
-// normals are used).
-template <int SRC>
-__global__ __launch_bounds__(kThreads) void k_vmap_gicp_eval(Params P, Source src, const float* __restrict__ normal, const unsigned long long* __restrict__ table,
-                                                             unsigned long long mask, unsigned long long min_count, float max_dist2,
-                                                             const uint4* __restrict__ layer, float epsilon, const LoopState<kGicpWords>* __restrict__ st,
-                                                             int final_pass, double* __restrict__ part, int32_t* __restrict__ key3, float* __restrict__ d2_out,
-                                                             double* __restrict__ mc_out, uint8_t* __restrict__ class_out) {
+// what the evaluation takes beyond EvalCommon.  normal: the source's normals by the point's index (a cloud's), or null; layer: the map's
+// normal records by slot, or null (no target normals are used).  The per-point outputs (tests; either may be null): mc_out seven doubles
+// per point (M00 M01 M02 M11 M12 M22 and the cost e^T M e; zeros without a kept match), class_out one byte per point (kGicpKept |
+// kGicpTarget | kGicpSource).
+struct GicpArgs {
+    const float* normal;
+    const uint4* layer;
+    float epsilon;
+    double* mc_out;
+    uint8_t* class_out;
+};
+// generalized ICP's tail: steps 2-5 of the definition
+struct GicpTail : PointsOnly {
+    double acc[kGcEE + 1];           // n, H (21), g (6), e^T M e, e.e
+    unsigned n_target = 0, n_source = 0, n_pairs = 0;
+    int pclass;                      // of the point added last, for store(): its class, weight and cost
+    double M[6], cost;
+    __device__ __forceinline__ GicpTail() {
+#pragma unroll
+        for (int q = 0; q <= kGcEE; ++q) acc[q] = 0.0;
+    }
+    __device__ __forceinline__ void add(long long index, const float pose[16], const float w[3], const Match<NoSupport>& mt, bool kept, const GicpArgs& args) {
 #pragma clang fp contract(off)
-    if (!final_pass && st->done) return;
-    __shared__ double s_red[kThreads / 64][kGicpWords];
+        pclass = 0;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) P.pose[k] = st->pose[k];
-
-    float x[kPerThread], y[kPerThread], z[kPerThread];
-    bool in[kPerThread];
-    long long index[kPerThread];
-    load_points<SRC>(src, x, y, z, in, index);
-
-    double acc[kGcEE + 1];           // n, H (21), g (6), e^T M e, e.e; the counters are integers until the reduction
-#pragma unroll
-    for (int q = 0; q <= kGcEE; ++q) acc[q] = 0.0;
-    unsigned n_probes = 0, n_valid = 0, n_box = 0, n_range = 0, n_target = 0, n_source = 0, n_pairs = 0, n_searched = 0;
-    // one point after another through the one accumulator
-#pragma unroll
-    for (int k = 0; k < kPerThread; ++k) {
-        if (!in[k]) continue;
-        unsigned long long key = 0;
-        long long f[3];
-        float w[3];
-        const int cls = classify(P, x[k], y[k], z[k], key, f, w);
-        n_valid += cls >= 1 ? 1u : 0u;
-        n_box += cls == 1 ? 1u : 0u;
-        n_range += cls == 2 ? 1u : 0u;
-        Match<NoSupport> mt;
-        if (cls == 3) {
-            n_searched += 1u;
-            mt = search27<NoSupport>(table, mask, min_count, key, w, n_probes);
-        }
-        const bool kept = mt.best_key != kEmpty && mt.best <= max_dist2;
-        int pclass = 0;
-        double M[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, cost = 0.0;
+        for (int q = 0; q < 6; ++q) M[q] = 0.0;
+        cost = 0.0;
         if (kept) {
             double nb[3] = {0.0, 0.0, 0.0};
             bool has_b = false;
-            if (layer) {             // the one 16-byte read
-                const NormalRec rec = normal_unpack(layer[mt.best_slot]);
+            if (args.layer) {        // the one 16-byte read
+                const NormalRec rec = normal_unpack(args.layer[mt.best_slot]);
                 has_b = rec.status == kClassKept;
 #pragma unroll
                 for (int q = 0; q < 3; ++q) nb[q] = (double)rec.n[q];
             }
             float na[3] = {0.f, 0.f, 0.f};
-            if (normal) {
+            if (args.normal) {
 #pragma unroll
-                for (int q = 0; q < 3; ++q) na[q] = normal[3 * index[k] + q];
+                for (int q = 0; q < 3; ++q) na[q] = args.normal[3 * index + q];
             }
-            const int used = gicp_weight(nb, has_b, na, normal != nullptr, P.pose, epsilon, M);
+            const int used = gicp_weight(nb, has_b, na, args.normal != nullptr, pose, args.epsilon, M);
             pclass = kGicpKept | used;
             n_target += used & kGicpTarget ? 1u : 0u;
             n_source += used & kGicpSource ? 1u : 0u;
@@ -175,34 +157,32 @@ __global__ __launch_bounds__(kThreads) void k_vmap_gicp_eval(Params P, Source sr
             acc[kGcCost] += cost;
             acc[kGcEE] += (ex * ex + ey * ey) + ez * ez;
         }
-        if (key3) store_key3(key3 + 3 * index[k], mt.best_key, kept);
-        if (d2_out) d2_out[index[k]] = mt.best;
-        if (mc_out) {
-#pragma unroll
-            for (int q = 0; q < 6; ++q) mc_out[7 * index[k] + q] = M[q];
-            mc_out[7 * index[k] + 6] = cost;
-        }
-        if (class_out) class_out[index[k]] = (uint8_t)pclass;
     }
-
-    double row[kGicpWords];
+    __device__ __forceinline__ void store(long long index, const GicpArgs& args) const {
+        if (args.mc_out) {
 #pragma unroll
-    for (int q = 0; q <= kGcEE; ++q) row[q] = acc[q];
-    row[kGcValid] = (double)n_valid;
-    row[kGcBox] = (double)n_box;
-    row[kGcRange] = (double)n_range;
-    row[kGcTarget] = (double)n_target;
-    row[kGcSource] = (double)n_source;
-    row[kGcPairs] = (double)n_pairs;
-    row[kGcProbes] = (double)n_probes;
-    row[kGcSearched] = (double)n_searched;
-    block_row_sum<kGicpWords>(row, s_red, part + block_row<SRC>() * kGicpWords);
-}
+            for (int q = 0; q < 6; ++q) args.mc_out[7 * index + q] = M[q];
+            args.mc_out[7 * index + 6] = cost;
+        }
+        if (args.class_out) args.class_out[index] = (uint8_t)pclass;
+    }
+    __device__ __forceinline__ void row(double* out) const {
+#pragma unroll
+        for (int q = 0; q <= kGcEE; ++q) out[q] = acc[q];
+        out[kGcTarget] = (double)n_target;
+        out[kGcSource] = (double)n_source;
+        out[kGcPairs] = (double)n_pairs;
+    }
+};
 
 struct GicpMethod {
     static constexpr int kWords = kGicpWords, kN = kGcN, kSumSq = kGcCost, kCounters = kGcValid, kProbes = kGcProbes, kSearched = kGcSearched;
     __host__ __device__ static void assemble(const double* s, float* H, float* g) { plane_assemble(s, H, g); }      // (the plane row's places)
+    using Support = NoSupport;
+    using Args = GicpArgs;
+    using Tail = GicpTail;
 };
+static_assert(kGcValid + 1 == kGcBox && kGcValid + 2 == kGcRange, "the three counters of every method lead the row's counters");
 static_assert(kGcH == kPlH && kGcG == kPlG, "H and g lie where plane_assemble reads them");
 static_assert(kGicpWords <= kIcpMaxWords, "the buffers of a map hold the widest row");
 
@@ -238,22 +218,15 @@ struct GicpIcp : vmap::GicpMethod {
         return 0;
     }
     // the map's normal layer under this call's parameters, built or reused as the surface cast does (normals_layer: a comparison on the
-    // host while the map's revision and the parameters stand), then the kernel behind it on the stream
-    static int launch_eval(rgbd360_map* m, const IcpJob& job, const vmap::Params& P, int final_pass, const Out& o) {
+    // host while the map's revision and the parameters stand), ahead of the kernel on the stream
+    static int eval_args(rgbd360_map* m, const IcpJob& job, const Out& o, Args& a) {
         const uint4* layer = nullptr;
         if (job.use_target_normals && m->n_voxels > 0) {
             const rgbd360_map_normal_params np = {job.p.min_count, job.min_support, job.max_flatness, 0.f};
             if (const int rc = normals_layer(m, np)) return rc;
             layer = m->nm_layer.get();
         }
-        const float max_dist2 = job.p.max_dist * job.p.max_dist;
-        const float* normal = job.src.cloud ? job.normal : nullptr;
-        with_choice<0, 1>(job.src.cloud, [&](auto S) {
-            hipLaunchKernelGGL((vmap::k_vmap_gicp_eval<decltype(S)::value>), job.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.src, normal,
-                               (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, max_dist2, layer, job.epsilon,
-                               (const IcpState<GicpIcp>*)icp_state<GicpIcp>(m), final_pass, m->a_part.get(), o.key3, o.d2, o.weight_cost, o.cls);
-        });
-        HIPC(m, hipGetLastError());
+        a = {job.src.cloud ? job.normal : nullptr, layer, job.epsilon, o.weight_cost, o.cls};
         return 0;
     }
     static void fill_extra(const IcpState<GicpIcp>& st, Result* res) {
@@ -333,14 +306,14 @@ extern "C" int rgbd360_map_time_align_gicp(rgbd360_map* m, const void* depth_dev
     int& rc = timer.rc;
     // the point-to-point and point-to-plane kernels first, on the same frame, map and buffers, then this method's, whose state stays behind
     rc = icp_launch_init<PointIcp>(m, pose);
-    if (rc == 0) rc = PointIcp::launch_eval(m, job, P, 1, {});      // once untimed: code and tables loaded
-    timer.timed(avg_us[1], reps, [&] { return PointIcp::launch_eval(m, job, P, 1, {}); });
+    if (rc == 0) rc = icp_launch_eval<PointIcp>(m, job, P, 1, {});      // once untimed: code and tables loaded
+    timer.timed(avg_us[1], reps, [&] { return icp_launch_eval<PointIcp>(m, job, P, 1, {}); });
     if (rc == 0) rc = icp_launch_init<PlaneIcp>(m, pose);
-    if (rc == 0) rc = PlaneIcp::launch_eval(m, job, P, 1, {});
-    timer.timed(avg_us[2], reps, [&] { return PlaneIcp::launch_eval(m, job, P, 1, {}); });
+    if (rc == 0) rc = icp_launch_eval<PlaneIcp>(m, job, P, 1, {});
+    timer.timed(avg_us[2], reps, [&] { return icp_launch_eval<PlaneIcp>(m, job, P, 1, {}); });
     if (rc == 0) rc = icp_launch_init<GicpIcp>(m, pose);
-    if (rc == 0) rc = GicpIcp::launch_eval(m, job, P, 1, {});       // (and the normal layer built)
-    timer.timed(avg_us[0], reps, [&] { return GicpIcp::launch_eval(m, job, P, 1, {}); });
+    if (rc == 0) rc = icp_launch_eval<GicpIcp>(m, job, P, 1, {});       // (and the normal layer built)
+    timer.timed(avg_us[0], reps, [&] { return icp_launch_eval<GicpIcp>(m, job, P, 1, {}); });
     timer.timed(avg_us[3], reps, [&] { return icp_launch_solve<GicpIcp>(m, job, 1); });
     if (rc == 0 && probes) rc = icp_read_probes<GicpIcp>(m, probes);
     if (const int failed = timer.finish(avg_us, 0, reps)) return failed;

@@ -2,11 +2,11 @@
 // reference's call sites actually use (pcl::GeneralizedIterativeClosestPoint, a plane-to-plane cost: OdometryRGBD360.cpp:98-114, 210-222,
 // RegisterPairRGBD360.cpp:111-118, MethodsRegisterRGBD360.cpp:294-320) with the map as its target.  Part of the Frame360 translation unit,
 // behind map_align.h, which holds what the methods share: the lookup (vmap::find, icp_cell), the loop's state and kernels, the host
-// driver (icp_align<M> and icp_eval<M> on a MapInput) and the trace.  Here: the plane fit, the evaluation kernel, the row's description (PlaneMethod) and the host's (PlaneIcp).
+// driver (icp_align<M> and icp_eval<M> on a MapInput) and the trace.  Here: the plane fit, the evaluation's tail (PlaneTail), the row's description (PlaneMethod) and the host's (PlaneIcp).
 //
 // Definition (include/rgbd360_hip.h, "point-to-plane ICP of a frame against the map"; tests/map_align_plane_reference.py
 // restates it in numpy).  Per source point at the current pose:
-//   1 candidates and match: steps 1-4 of map_align.h, bit for bit (the same key and d2 per point): both kernels call vmap::search27.
+//   1 candidates and match: steps 1-4 of map_align.h, bit for bit (the same key and d2 per point): eval_tile's, whatever the method.
 //   2 support: over ALL m candidates e_j = (double)w - (double)c_j, sum e (3) and sum e e^T (6) in float64 in the cells' order;
 //     e_mean = sum e / m (= w - mu, mu the mean centroid), C = sum e e^T / m - e_mean e_mean^T.  A kept point with m < min_support is
 //     counted in n_unsupported.
@@ -18,10 +18,8 @@
 //   6 H and g straight from the row, cast to float32, gn::step with lambda 0, the stop tests and statuses of map_align.h.
 // The map stores no normals and insertion is unchanged: the plane comes from the centroids the lookup has already loaded.
 //
-//   k_vmap_plane_eval   the shape of k_vmap_icp_eval (256 threads, four points per thread one after another through one row
-//                       accumulator, all 27 first probes in flight before any is looked at, the table read-only), built from the same
-//                       load_points, search27 and block_row_sum; the nine support sums ride in the candidate loop as search27's
-//                       PlaneSupport, the plane fit runs once per kept point with enough support.
+//   k_vmap_eval<PlaneMethod, SRC>  map_align.h's evaluation on this row: the nine support sums ride in the candidate loop as search27's
+//                       PlaneSupport, the plane fit runs once per kept point with enough support (PlaneTail).
 //   k_vmap_icp_solve<PlaneMethod>  map_align.h's solve kernel on this row.
 #pragma once
 
@@ -101,24 +99,78 @@ struct PlaneSupport {
     }
 };
 
-// per-point outputs (tests; any may be null): key3 / d2_out as in k_vmap_icp_eval (the key of the kept MATCH whatever the point's class),
-// nr_out four doubles per point (the normal and r; zeros unless the class is kept), class_out one byte per point.  The body behind the pose
-// is map_align_plane_eval_tile.h: the text k_vmap_plane_eval_batch (map_align_batch.h) includes too, so that a tile gives the same row in both.
-template <int SRC>
-__global__ __launch_bounds__(kThreads) void k_vmap_plane_eval(Params P, Source src, const unsigned long long* __restrict__ table, unsigned long long mask,
-                                                              unsigned long long min_count, float max_dist2, unsigned min_support, double max_flatness,
-                                                              const LoopState<kPlaneWords>* __restrict__ st, int final_pass, double* __restrict__ part,
-                                                              int32_t* __restrict__ key3, float* __restrict__ d2_out, double* __restrict__ nr_out,
-                                                              uint8_t* __restrict__ class_out) {
-#pragma clang fp contract(off)
-    if (!final_pass && st->done) return;
-    __shared__ double s_red[kThreads / 64][kPlaneWords];
+// what the evaluation takes beyond EvalCommon; the per-point outputs (tests; either may be null): nr_out four doubles per point (the
+// normal and r; zeros unless the class is kept), class_out one byte per point (key3: the key of the kept MATCH whatever the point's class)
+struct PlaneArgs {
+    unsigned min_support;
+    double max_flatness;
+    double* nr_out;
+    uint8_t* class_out;
+};
+// point-to-plane's tail: steps 2-5 of the definition on the support search27 carried
+struct PlaneTail : PointsOnly {
+    double acc[kPlRR + 2];           // n, H (21), g (6), r r, e.e
+    unsigned n_unsupported = 0, n_nonplanar = 0;
+    int pclass;                      // of the point added last, for store(): its class, normal and r
+    double nrm[3], r;
+    __device__ __forceinline__ PlaneTail() {
 #pragma unroll
-    for (int k = 0; k < 16; ++k) P.pose[k] = st->pose[k];
-    const unsigned bx = blockIdx.x, by = blockIdx.y;
-    const auto part_row = [&] { return part + block_row<SRC>() * kPlaneWords; };
-#include "map_align_plane_eval_tile.h"
-}
+        for (int q = 0; q < kPlRR + 2; ++q) acc[q] = 0.0;
+    }
+    __device__ __forceinline__ void add(long long, const float*, const float w[3], const Match<PlaneSupport>& mt, bool kept, const PlaneArgs& args) {
+#pragma clang fp contract(off)
+        const PlaneSupport& sp = mt.support;
+        pclass = kClassNone;
+        nrm[0] = nrm[1] = nrm[2] = 0.0, r = 0.0;
+        if (kept && sp.m < args.min_support) {
+            pclass = kClassUnsupported;
+            n_unsupported += 1u;
+        } else if (kept) {
+            const double dm = (double)sp.m;
+            const double mx = sp.se[0] / dm, my = sp.se[1] / dm, mz = sp.se[2] / dm;
+            const double cov[6] = {sp.see[0] / dm - mx * mx, sp.see[1] / dm - mx * my, sp.see[2] / dm - mx * mz,
+                                   sp.see[3] / dm - my * my, sp.see[4] / dm - my * mz, sp.see[5] / dm - mz * mz};
+            double l0, l1;
+            if (plane_fit(cov, args.max_flatness, nrm, l0, l1)) {
+                pclass = kClassKept;
+                r = (nrm[0] * mx + nrm[1] * my) + nrm[2] * mz;
+                const double wx = w[0], wy = w[1], wz = w[2];
+                const double J[6] = {nrm[0], nrm[1], nrm[2], wy * nrm[2] - wz * nrm[1], wz * nrm[0] - wx * nrm[2], wx * nrm[1] - wy * nrm[0]};
+                const double ex = mt.be[0], ey = mt.be[1], ez = mt.be[2];
+                acc[kPlN] += 1.0;
+                int h = kPlH;
+#pragma unroll
+                for (int a = 0; a < 6; ++a) {
+#pragma unroll
+                    for (int b = a; b < 6; ++b) acc[h++] += J[a] * J[b];
+                }
+#pragma unroll
+                for (int a = 0; a < 6; ++a) acc[kPlG + a] += J[a] * r;
+                acc[kPlRR] += r * r;
+                acc[kPlEE] += (ex * ex + ey * ey) + ez * ez;
+            } else {
+                pclass = kClassNonplanar;
+                n_nonplanar += 1u;
+                nrm[0] = nrm[1] = nrm[2] = 0.0;
+            }
+        }
+    }
+    __device__ __forceinline__ void store(long long index, const PlaneArgs& args) const {
+        if (args.nr_out) {
+            args.nr_out[4 * index] = nrm[0];
+            args.nr_out[4 * index + 1] = nrm[1];
+            args.nr_out[4 * index + 2] = nrm[2];
+            args.nr_out[4 * index + 3] = r;
+        }
+        if (args.class_out) args.class_out[index] = (uint8_t)pclass;
+    }
+    __device__ __forceinline__ void row(double* out) const {
+#pragma unroll
+        for (int q = 0; q < kPlRR + 2; ++q) out[q] = acc[q];
+        out[kPlUnsupported] = (double)n_unsupported;
+        out[kPlNonplanar] = (double)n_nonplanar;
+    }
+};
 
 // H (column-major, symmetric) and g from the row
 __host__ __device__ inline void plane_assemble(const double* s, float* H, float* g) {
@@ -131,7 +183,11 @@ __host__ __device__ inline void plane_assemble(const double* s, float* H, float*
 struct PlaneMethod {
     static constexpr int kWords = kPlaneWords, kN = kPlN, kSumSq = kPlRR, kCounters = kPlValid, kProbes = kPlProbes, kSearched = kPlSearched;
     __host__ __device__ static void assemble(const double* s, float* H, float* g) { plane_assemble(s, H, g); }
+    using Support = PlaneSupport;
+    using Args = PlaneArgs;
+    using Tail = PlaneTail;
 };
+static_assert(kPlValid + 1 == kPlBox && kPlValid + 2 == kPlRange, "the three counters of every method lead the row's counters");
 static_assert(kPlaneWords <= kIcpMaxWords, "the buffers of a map hold the widest row");
 
 }  // namespace vmap
@@ -160,15 +216,8 @@ struct PlaneIcp : vmap::PlaneMethod {
         job.max_flatness = p.max_flatness;
         return 0;
     }
-    static int launch_eval(rgbd360_map* m, const IcpJob& job, const vmap::Params& P, int final_pass, const Out& o) {
-        const float max_dist2 = job.p.max_dist * job.p.max_dist;
-        with_choice<0, 1>(job.src.cloud, [&](auto S) {
-            hipLaunchKernelGGL((vmap::k_vmap_plane_eval<decltype(S)::value>), job.grid, dim3(vmap::kThreads), 0, m->s->stream, P, job.src,
-                               (const unsigned long long*)m->table.get(), m->n_slots - 1, (unsigned long long)job.p.min_count, max_dist2,
-                               (unsigned)job.min_support, (double)job.max_flatness, (const IcpState<PlaneIcp>*)icp_state<PlaneIcp>(m), final_pass,
-                               m->a_part.get(), o.key3, o.d2, o.normal_r, o.cls);
-        });
-        HIPC(m, hipGetLastError());
+    static int eval_args(rgbd360_map*, const IcpJob& job, const Out& o, Args& a) {
+        a = {(unsigned)job.min_support, (double)job.max_flatness, o.normal_r, o.cls};
         return 0;
     }
     static void fill_extra(const IcpState<PlaneIcp>& st, Result* res) {
@@ -238,11 +287,11 @@ extern "C" int rgbd360_map_time_align_plane(rgbd360_map* m, const void* depth_de
     int& rc = timer.rc;
     // the point-to-point kernel first, on the same frame, map and buffers, then the plane kernels, whose state stays behind
     rc = icp_launch_init<PointIcp>(m, pose);
-    if (rc == 0) rc = PointIcp::launch_eval(m, job, P, 1, {});      // once untimed: code and tables loaded
-    timer.timed(avg_us[1], reps, [&] { return PointIcp::launch_eval(m, job, P, 1, {}); });
+    if (rc == 0) rc = icp_launch_eval<PointIcp>(m, job, P, 1, {});      // once untimed: code and tables loaded
+    timer.timed(avg_us[1], reps, [&] { return icp_launch_eval<PointIcp>(m, job, P, 1, {}); });
     if (rc == 0) rc = icp_launch_init<PlaneIcp>(m, pose);
-    if (rc == 0) rc = PlaneIcp::launch_eval(m, job, P, 1, {});
-    timer.timed(avg_us[0], reps, [&] { return PlaneIcp::launch_eval(m, job, P, 1, {}); });
+    if (rc == 0) rc = icp_launch_eval<PlaneIcp>(m, job, P, 1, {});
+    timer.timed(avg_us[0], reps, [&] { return icp_launch_eval<PlaneIcp>(m, job, P, 1, {}); });
     timer.timed(avg_us[2], reps, [&] { return icp_launch_solve<PlaneIcp>(m, job, 1); });
     if (rc == 0 && probes) rc = icp_read_probes<PlaneIcp>(m, probes);
     if (const int failed = timer.finish(avg_us, 0, reps)) return failed;

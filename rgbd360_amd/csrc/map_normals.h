@@ -6,7 +6,7 @@
 // Definition (include/rgbd360_hip.h, "surface normals of the map"; tests/map_normals_reference.py restates it).  Per
 // voxel v with count >= min_count: w = the read-out's float32 centroid of v; steps 2-3 of the point-to-plane definition
 // (map_align_plane.h) with v's own key as the centre and w as the point -- vmap::search27<PlaneSupport>, the covariance of
-// k_vmap_plane_eval, vmap::plane_fit; status NONE (below min_count) / OK / UNSUPPORTED (m < min_support) / NONPLANAR = vmap::kClass*;
+// PlaneTail (map_align_plane.h), vmap::plane_fit; status NONE (below min_count) / OK / UNSUPPORTED (m < min_support) / NONPLANAR = vmap::kClass*;
 // n32_k = (float)n_k, negated as a whole unless its component of largest magnitude (the earliest on a tie) is positive; curvature
 // (float)(l0 / c2), c2 the covariance's trace, 0 when c2 is not positive; normal zero unless OK, curvature zero unless OK or NONPLANAR.
 // A function of the voxel set and the three parameters alone.

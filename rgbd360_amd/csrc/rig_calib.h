@@ -16,7 +16,7 @@
 //                         (its pixel is pinhole_pixel, which depth_apply.h's k_rig_cloud_models instantiates with a correction of z.)
 //   k_rig_init            one launch: the head, the inputs' records and, per live input, its loop state at P_ks = T_k E_s (gn::mat4_mul).
 //   k_rig_input           one 64-lane workgroup per live input: the partial rows added in ascending order (the first loop of
-//                         map_align_solve_rows.h on the 30 sums), then lane 0: A, b, A Ad, Ad^T A Ad, Ad^T b.
+//                         icp_solve_rows on the 30 sums), then lane 0: A, b, A Ad, Ad^T A Ad, Ad^T b.
 //   k_rig_frames          one lane per frame: F_k, f_k, with refine_poses the 6 x 6 Cholesky, L^-1 f_k and L^-1 C_ks.
 //   k_rig_solve           ONE workgroup: totals and statuses, the reduced matrix (packed lower triangle in LDS: 96 x 97 / 2 doubles),
 //                         Cholesky, the substitutions, the updates applied, the new P_ks into the inputs' states, the trace and the stop test.
@@ -741,7 +741,7 @@ int rig_calibrate(rgbd360_map* m, const std::vector<MapInput>& inputs, int K, in
     for (int it = 0; it <= iters; ++it) {
         const int final_pass = it == iters ? 1 : 0;
         if (n_live)
-            if (const int rc = BatchEval<PlaneIcp>::launch(m, base, b, VP, final_pass)) return rc;
+            if (const int rc = batch_launch_eval<PlaneIcp>(m, base, b, VP, final_pass)) return rc;
         if (const int rc = rig_launch_solve(m, d, final_pass)) return rc;
     }
     HIPC(m, hipMemcpyAsync(m->c_host, m->c_out, lay.out_bytes, hipMemcpyDeviceToHost, stream));

@@ -1,4 +1,4 @@
-"""The bytes of both alignments against the voxel map (csrc/map_align.h, csrc/map_align_plane.h) against the fixture recorded on an MI355X
+"""The bytes of the four alignments against the voxel map (csrc/map_align.h and the methods' headers) against the fixture recorded on an MI355X
 before the evaluation kernels were last changed (tests/golden/map_align_bits.json, tools/map_align_bits.py): per case the float64 sums,
 the counters, a digest of every per-point output, and the whole alignment -- pose, normal equations, fitness, every trace record -- byte
 for byte.  The restatement tests bound the sums to 2e-6; this one holds the summation order and the schedule-independent bits still."""
@@ -32,9 +32,11 @@ def computed(hip_lib, recorder):
 def test_every_case_equals_the_fixture_byte_for_byte(recorder, computed):
     with open(recorder.OUT) as f:
         want = json.load(f)["cases"]
-    # 6 inputs x 2 methods x 2 poses, the strip and both leaves of the frame among them
-    assert len(want) == 24 and sorted(want) == sorted(computed)
-    assert {"frame/leaf0.05/point/map_pose", "frame/leaf0.1/plane/perturbed", "strip/leaf0.1/plane/perturbed", "ragged/leaf0.1/point/perturbed"} <= set(want)
+    # 6 inputs x 4 methods x 2 poses, the strip and both leaves of the frame among them, and generalized ICP with source normals on the 3 clouds
+    assert len(want) == 54 and sorted(want) == sorted(computed)
+    assert {"frame/leaf0.05/point/map_pose", "frame/leaf0.1/plane/perturbed", "strip/leaf0.1/plane/perturbed", "ragged/leaf0.1/point/perturbed",
+            "frame/leaf0.05/gicp/map_pose", "strip/leaf0.1/gicp/perturbed", "cloud/leaf0.05/gicp_normals/perturbed", "ragged/leaf0.1/gicp_normals/map_pose",
+            "frame/leaf0.1/colour/perturbed", "strip/leaf0.1/colour/map_pose", "ragged/leaf0.1/colour/perturbed"} <= set(want)
     differ = []
     for case in sorted(want):
         for part in ("eval", "align"):
@@ -55,7 +57,8 @@ def test_the_cases_are_not_trivial(recorder, computed):
             assert rec["align"]["iterations"] >= 2 and len(rec["align"]["trace"]) == rec["align"]["iterations"], case
         else:
             assert rec["eval"]["sums"] != computed[case.replace("map_pose", "perturbed")]["eval"]["sums"], case
-    for case, rec in computed.items():      # step 1 of the point-to-plane definition: the same key and d2 per point as point-to-point
-        if "/plane/" in case:
-            other = computed[case.replace("/plane/", "/point/")]["eval"]
+    for case, rec in computed.items():      # step 1 of every other definition: the same key and d2 per point as point-to-point
+        method = case.split("/")[2]
+        if method != "point":
+            other = computed[case.replace("/%s/" % method, "/point/")]["eval"]
             assert rec["eval"]["key3"] == other["key3"] and rec["eval"]["d2"] == other["d2"], case

@@ -98,7 +98,7 @@ def lib():
 
 @pytest.mark.parametrize("epsilon", [1e-3, 1.0, 0.25])
 def test_the_library_function_is_the_restatement_bit_for_bit(lib, epsilon):
-    """rgbd360_map_gicp_weight is the host compile of the function k_vmap_gicp_eval calls: + - x / sqrt in float64 without contraction
+    """rgbd360_map_gicp_weight is the host compile of the function the generalized ICP evaluation (GicpTail) calls: + - x / sqrt in float64 without contraction
     give numpy's bits.  Some source normals are zero, NaN or infinite: those points have none."""
     from rgbd360_amd.register import pose_to_cm
     n_cases = 0

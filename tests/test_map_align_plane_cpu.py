@@ -109,7 +109,7 @@ def test_plane_function_special_supports():
 
 
 def test_the_library_function_is_the_restatement_bit_for_bit(support_set):
-    """rgbd360_map_plane_fit is the host compile of the function k_vmap_plane_eval calls: + - x / sqrt in float64 without contraction
+    """rgbd360_map_plane_fit is the host compile of the function the point-to-plane evaluation (PlaneTail) calls: + - x / sqrt in float64 without contraction
     give the same bits as numpy's, verdict, normal and both eigenvalues."""
     from rgbd360_amd import build
     L = C.CDLL(build.build())

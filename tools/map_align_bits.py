@@ -1,21 +1,23 @@
-"""The bytes both alignments against the voxel map produce on the device, recorded as a fixture: tests/golden/map_align_bits.json.
+"""The bytes the four alignments against the voxel map produce on the device, recorded as a fixture: tests/golden/map_align_bits.json.
 
     python tools/map_align_bits.py [--out tests/golden/map_align_bits.json]       (RGBD360_LIB: the build of the library to record from)
 
 tests/test_map_align_bits_gpu.py recomputes every case with compute() below and compares it with the file, byte for byte: a change of
-the evaluation kernels (csrc/map_align.h, csrc/map_align_plane.h) that moves one bit of a sum, of a per-point output or of an aligned
+the evaluation kernels (csrc/map_align.h and the methods' headers) that moves one bit of a sum, of a per-point output or of an aligned
 pose fails it.  Record from the library the change is measured against, BEFORE the kernels change.  Every case is computed twice in the
 process and nothing is written if the two differ.
 
-Inputs, all from seeds (nothing large is stored), every map at voxel_map_reference.general_pose() with capacity 1 << 16 and the default box:
+Inputs, all from seeds (nothing large is stored), every map at voxel_map_reference.general_pose() with capacity 1 << 16 and the default box,
+fed with the colour image synth returns with the depth (a cloud takes the bytes of its pixels):
   frame    frame 0 of synth.make_pair(256, 128, seed=1234), uint16 depth, convention 2, the sphere route; maps of leaf 0.05 and 0.1
   cloud    reg.sphere_cloud of that frame (32 768 points, 32 workgroups), the cloud route against the same two maps
   ragged   2 * 1024 + 37 of its valid points, evenly spaced (tests/test_map_align_plane_gpu.py, test_ragged_cloud_sizes), leaf 0.1
   strip    synth.render(synth.trajectory_pose(0, 7), 1100, 24, 7) in a map of its own, leaf 0.1: a full tile and a ragged second tile of
            76 columns per row, the smallest shape in which all four point slots of a thread and a second blockIdx.x of the sphere route
            hold pixels (at 256 and 200 columns only the first slot ever does)
-Per input, method (point, plane) and pose (the map's, and map_align_reference.perturbed(P, 0.01, 0.003, 8)):
-  eval     the diag evaluation entry: the 17 / 30 float64 sums as hex, the counters, a SHA-256 of each per-point array
+Per input, method and pose (the map's, and map_align_reference.perturbed(P, 0.01, 0.003, 8)); the methods are point, plane, gicp (no source
+normals), colour and, on the three cloud inputs, gicp_normals (a unit normal per point from seed 5):
+  eval     the diag evaluation entry: the 17 / 30 / 30 / 31 float64 sums as hex, the counters, a SHA-256 of each per-point array
   align    the public entry from that pose with default parameters: status, iterations, converged, pose, hessian, gradient and the
            fitness fields as hex, the counters, every trace record as hex
 """
@@ -39,10 +41,14 @@ import voxel_map_reference as R                                      # noqa: E40
 
 OUT = os.path.join(ROOT, "tests", "golden", "map_align_bits.json")
 # per method: the diag entry, its parameter maker, sums, counters, the per-point arrays (name, dtype, values per point)
+_KEY_D2 = (("key3", np.int32, 3), ("d2", np.float32, 1))
+_GICP = ("rgbd360_map_align_gicp_eval", "align_gicp_params", 30, 6, _KEY_D2 + (("weight_cost", np.float64, 7), ("class", np.uint8, 1)))
 METHODS = {
-    "point": ("rgbd360_map_align_eval", "align_params", 17, 3, (("key3", np.int32, 3), ("d2", np.float32, 1))),
-    "plane": ("rgbd360_map_align_plane_eval", "align_plane_params", 30, 5,
-              (("key3", np.int32, 3), ("d2", np.float32, 1), ("normal_r", np.float64, 4), ("class", np.uint8, 1))),
+    "point": ("rgbd360_map_align_eval", "align_params", 17, 3, _KEY_D2),
+    "plane": ("rgbd360_map_align_plane_eval", "align_plane_params", 30, 5, _KEY_D2 + (("normal_r", np.float64, 4), ("class", np.uint8, 1))),
+    "gicp": _GICP,
+    "gicp_normals": _GICP,           # (cloud inputs only)
+    "colour": ("rgbd360_map_align_colour_eval", "align_colour_params", 31, 5, _KEY_D2 + (("residuals", np.float64, 2), ("class", np.uint8, 1))),
 }
 
 
@@ -54,33 +60,54 @@ def _hip():
     return h
 
 
+class Source:
+    """An input of the alignments: the sphere route's images, or the cloud route's points with their colours and seeded normals."""
+
+    def __init__(self, rgb=None, depth=None, xyz=None, rgb3=None):
+        self.rgb, self.depth = rgb, depth
+        self.xyz = None if xyz is None else np.ascontiguousarray(xyz, np.float32)
+        self.rgb3 = None if rgb3 is None else np.ascontiguousarray(rgb3, np.uint8)
+        self.n = depth.size if depth is not None else len(self.xyz)
+        self.normals = None
+        if xyz is not None:
+            v = np.random.default_rng(5).standard_normal((self.n, 3))
+            self.normals = np.ascontiguousarray(v / np.linalg.norm(v, axis=1, keepdims=True), np.float32)
+
+    def methods(self):
+        return [k for k in METHODS if k != "gicp_normals" or self.xyz is not None]
+
+
 def inputs(reg):
-    """[(name, leaf, map source depth, depth of the sphere route | None, cloud of the cloud route | None)]"""
-    depth = np.ascontiguousarray(synth.make_pair(256, 128, seed=1234)[0][1])
-    assert depth.dtype == np.uint16
-    cloud = reg.sphere_cloud(depth, 2)
+    """[(name, leaf, (rgb, depth) of the map, Source)]"""
+    rgb, depth = (np.ascontiguousarray(a) for a in synth.make_pair(256, 128, seed=1234)[0])
+    assert depth.dtype == np.uint16 and rgb.shape == depth.shape + (3,)
+    cloud, rgb3 = reg.sphere_cloud(depth, 2), rgb.reshape(-1, 3)
     valid = np.nonzero(np.isfinite(cloud).all(axis=1))[0]
-    ragged = cloud[valid[np.linspace(0, len(valid) - 1, 2 * 1024 + 37).astype(np.int64)]]
-    strip = np.ascontiguousarray(synth.render(synth.trajectory_pose(0, 7), 1100, 24, 7)[1])
+    pick = valid[np.linspace(0, len(valid) - 1, 2 * 1024 + 37).astype(np.int64)]
+    srgb, strip = (np.ascontiguousarray(a) for a in synth.render(synth.trajectory_pose(0, 7), 1100, 24, 7))
     assert strip.shape == (24, 1100) and strip.dtype == np.uint16
-    return [("frame", 0.05, depth, depth, None), ("frame", 0.1, depth, depth, None), ("cloud", 0.05, depth, None, cloud), ("cloud", 0.1, depth, None, cloud),
-            ("ragged", 0.1, depth, None, ragged), ("strip", 0.1, strip, strip, None)]
+    frame, whole = Source(rgb=rgb, depth=depth), Source(xyz=cloud, rgb3=rgb3)
+    return [("frame", 0.05, (rgb, depth), frame), ("frame", 0.1, (rgb, depth), frame), ("cloud", 0.05, (rgb, depth), whole), ("cloud", 0.1, (rgb, depth), whole),
+            ("ragged", 0.1, (rgb, depth), Source(xyz=cloud[pick], rgb3=rgb3[pick])), ("strip", 0.1, (srgb, strip), Source(rgb=srgb, depth=strip))]
 
 
-def evaluate(hip, m, method, pose, depth, xyz):
+def evaluate(hip, m, method, pose, s):
     entry, params, n_sums, n_counters, arrays = METHODS[method]
-    n = depth.size if depth is not None else len(xyz)
-    host = [np.zeros((n, k), dt) for _, dt, k in arrays]
+    host = [np.zeros((s.n, k), dt) for _, dt, k in arrays]
     dev = [C.c_void_p() for _ in arrays]
     for d, a in zip(dev, host):
         assert hip.hipMalloc(C.byref(d), a.nbytes) == 0
     sums, counters = np.zeros(n_sums, np.float64), np.zeros(n_counters, np.int64)
     p = getattr(m, params)()
-    if depth is not None:
-        src = (_ptr(depth), depth.strides[0], 0, depth.shape[0], depth.shape[1], 2, None, 0)
+    image = (_ptr(s.depth), s.depth.strides[0], 0, s.depth.shape[0], s.depth.shape[1], 2) if s.depth is not None else (None, 0, 0, 0, 0, 0)
+    xyz = None if s.xyz is None else _ptr(s.xyz)
+    n = 0 if s.xyz is None else s.n
+    if method == "colour":
+        src = ((_ptr(s.rgb), s.rgb.strides[0]) if s.depth is not None else (None, 0)) + image + (xyz, None if s.xyz is None else _ptr(s.rgb3), n)
+    elif method.startswith("gicp"):
+        src = image + (xyz, _ptr(s.normals) if method == "gicp_normals" else None, n)
     else:
-        xyz = np.ascontiguousarray(xyz, np.float32)
-        src = (None, 0, 0, 0, 0, 0, _ptr(xyz), len(xyz))
+        src = image + (xyz, n)
     tail = (0, None, None) if method == "point" else ()
     rc = getattr(m._L, entry)(m._handle(), *src, _ptr(pose_to_cm(pose)), 0, C.byref(p), _ptr(sums), _ptr(counters), *dev, *tail)
     assert rc == 0, (rc, m._L.rgbd360_map_last_error(m._handle()))
@@ -92,12 +119,15 @@ def evaluate(hip, m, method, pose, depth, xyz):
     return out
 
 
-def align(m, method, pose, depth, xyz):
-    suffix = "" if method == "point" else "_plane"
-    if depth is not None:
-        out, res = getattr(m, "align_sphere" + suffix)(depth, pose, convention=2)
+def align(m, method, pose, s):
+    suffix = {"point": "", "gicp_normals": "_gicp"}.get(method, "_" + method)
+    extra = {"normals": s.normals} if method == "gicp_normals" else {}
+    if s.depth is not None:
+        head = (s.rgb, s.depth) if method == "colour" else (s.depth,)
+        out, res = getattr(m, "align_sphere" + suffix)(*head, pose, convention=2)
     else:
-        out, res = getattr(m, "align_cloud" + suffix)(xyz, pose)
+        head = (s.xyz, s.rgb3) if method == "colour" else (s.xyz,)
+        out, res = getattr(m, "align_cloud" + suffix)(*head, pose, **extra)
     rec = {k: (np.asarray(v).tobytes().hex() if isinstance(v, (float, np.ndarray)) else int(v)) for k, v in res.items()}
     rec["pose"] = out.tobytes().hex()
     rec["trace"] = [np.int64(n).tobytes().hex() + np.float64(ss).tobytes().hex() + u.tobytes().hex() for n, ss, u in m.align_trace()]
@@ -110,13 +140,13 @@ def compute(reg):
     P = R.general_pose()
     poses = (("map_pose", P), ("perturbed", A.perturbed(P, 0.01, 0.003, 8)))
     cases = {}
-    for name, leaf, source, depth, xyz in inputs(reg):
+    for name, leaf, (rgb, depth), source in inputs(reg):
         with VoxelMap(reg, leaf, 1 << 16) as m:
-            m.insert_sphere(None, source, P, convention=2)
-            for method in METHODS:
+            m.insert_sphere(rgb, depth, P, convention=2)
+            for method in source.methods():
                 for at, pose in poses:
-                    cases["%s/leaf%g/%s/%s" % (name, leaf, method, at)] = {"eval": evaluate(hip, m, method, pose, depth, xyz),
-                                                                          "align": align(m, method, pose, depth, xyz)}
+                    cases["%s/leaf%g/%s/%s" % (name, leaf, method, at)] = {"eval": evaluate(hip, m, method, pose, source),
+                                                                          "align": align(m, method, pose, source)}
     return cases
 
 

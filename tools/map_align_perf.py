@@ -6,8 +6,8 @@ to one insert of the same frame and to a copy of its bytes.
     python tools/map_align_perf.py --colour [--rounds 3] --out profiles/map_align_colour_perf.txt
 
 Per size (the synthetic room, uint16 depth in device memory, convention 2, the map holds the frame at a general pose, the default box;
-the alignment starts 1 cm and 3 mrad beside that pose), from HIP events in ONE run (rgbd360_map_time_align): k_vmap_icp_eval,
-k_vmap_icp_solve, one k_vmap_insert launch into the populated map, the device-to-device copy of the frame's depth bytes, the table
+the alignment starts 1 cm and 3 mrad beside that pose), from HIP events in ONE run (rgbd360_map_time_align): the point-to-point
+evaluation, k_vmap_icp_solve, one k_vmap_insert launch into the populated map, the device-to-device copy of the frame's depth bytes, the table
 slots read per point that reached the search, and a whole alignment of 10 iterations (enqueue to synchronisation, wall clock; the
 launches behind a converged loop return at once).
 
@@ -18,8 +18,12 @@ stands next to the differences between the methods.
 
 --colour reports coloured ICP instead (the map holds the frame WITH its colours): the build of the colour layer next to the build of the
 normal layer and to a bare scan of the table in the same run (rgbd360_map_time_colours, medians over --reps builds), then per round
-k_vmap_colour_eval next to k_vmap_gicp_eval on the same frame, map and buffers, the solve and a whole coloured alignment
+the coloured evaluation next to generalized ICP's on the same frame, map and buffers, the solve and a whole coloured alignment
 (rgbd360_map_time_align_colour).
+
+The evaluation of every method is one kernel template, k_vmap_eval<M, SRC> (csrc/map_align.h).  The report lines keep the labels
+k_vmap_icp_eval, k_vmap_plane_eval, k_vmap_gicp_eval and k_vmap_colour_eval for its four instantiations: they are labels, not kernel
+names, kept so that old and new profiles compare line by line.
 """
 import argparse
 import ctypes as C

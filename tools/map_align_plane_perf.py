@@ -4,11 +4,13 @@ frame and map.
     python tools/map_align_plane_perf.py [--sizes 2048x1024,1920x320] [--reps 20] [--leaf 0.05] [--out profiles/map_align_plane_perf.txt]
 
 Per size (the synthetic room, uint16 depth in device memory, convention 2, the map holds the frame at a general pose, the default box;
-the alignment starts 1 cm and 3 mrad beside that pose), from HIP events in ONE run (rgbd360_map_time_align_plane): k_vmap_plane_eval,
-k_vmap_icp_eval with the same five shared parameters, k_vmap_plane_solve, the table slots read per point that reached the search, and a
+the alignment starts 1 cm and 3 mrad beside that pose), from HIP events in ONE run (rgbd360_map_time_align_plane): the point-to-plane
+evaluation, the point-to-point one with the same five shared parameters, the solve on the plane row, the table slots read per point that reached the search, and a
 whole point-to-plane alignment of 10 iterations (enqueue to synchronisation, wall clock; the launches behind a converged loop return at
 once).  The two eval kernels alternate in `--rounds` rounds within the process, so that a drift of the clock shows as a spread between
-rounds and not as a difference between the kernels; the report gives every round.
+rounds and not as a difference between the kernels; the report gives every round.  Its labels k_vmap_plane_eval, k_vmap_icp_eval and
+k_vmap_plane_solve stand for k_vmap_eval<PlaneMethod, SRC>, k_vmap_eval<PointMethod, SRC> and k_vmap_icp_solve<PlaneMethod>
+(csrc/map_align.h): labels, not kernel names, kept so that old and new profiles compare line by line.
 """
 import argparse
 import ctypes as C
