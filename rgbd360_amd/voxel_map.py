@@ -572,12 +572,18 @@ class VoxelMap:
     def level(self, shift: int) -> "VoxelMap":
         """Level `shift` (1 .. 6) of this map as a non-owning, read-only VoxelMap: levels 1 .. shift are built or refreshed now and keep
         that content until the next level() / align_*_c2f call.  Readers work on it (len, extract, census, align_*, render_sphere,
-        raycast*, normals); writers raise.  It is valid until the parent is closed or release_levels() is called."""
+        raycast*, normals); writers raise.  It is valid until the parent is closed or release_levels() is called.  A build that drops a
+        voxel (RGBD360_MAP_FULL: no free slot within the probe bound of the level's table) raises; the parent is unchanged."""
         shift = check_shift(shift)
         if self._parent is not None:
             raise Rgbd360Error("VoxelMap.level: a level has no levels of its own")
         h = C.c_void_p()
-        self._check(self._L.rgbd360_map_level(self._handle(), shift, C.byref(h)))
+        rc = self._L.rgbd360_map_level(self._handle(), shift, C.byref(h))
+        if rc != 0:      # a failed build took the levels from the failing one up with it: views made before are stale
+            self._level_gen += 1
+        self.last_status = self._check(rc)
+        if rc == MAP_FULL:
+            raise Rgbd360Error(f"rgbd360_map_level failed ({rc}, MAP_FULL): {self._L.rgbd360_map_last_error(self._h).decode()}")
         view = VoxelMap.__new__(VoxelMap)
         view._L, view._reg, view._h, view._ctx_value = self._L, self._reg, h, self._ctx_value
         view._parent, view._gen, view._level_gen = self, self._level_gen, 0
@@ -610,7 +616,10 @@ class VoxelMap:
         g = pose_to_cm(guess)
         out = np.zeros(16, np.float32)
         res = _lib.MapC2fResult()
-        self._check(entry(self._handle(), *input_args, _ptr(g), 0, C.byref(params), _ptr(out), C.byref(res)))
+        rc = self._check(entry(self._handle(), *input_args, _ptr(g), 0, C.byref(params), _ptr(out), C.byref(res)))
+        if rc == MAP_FULL:       # a level could not be built (level()): nothing was aligned, and views of the levels are stale
+            self._level_gen += 1
+            raise Rgbd360Error(f"rgbd360_map_align_c2f failed ({rc}, MAP_FULL): {self._L.rgbd360_map_last_error(self._h).decode()}")
         levels = []
         for lv in res.levels[:res.n_levels]:
             d = _as_dict(lv, skip=("pose",))
