@@ -187,18 +187,11 @@ __device__ __forceinline__ void warp_pixel_libm(const PoseRT& T, const WarpConst
     tr = (fr >= -2147483648.f && fr < 2147483648.f) ? (int)fr : (int)0x80000000;
     tc = (fc >= -2147483648.f && fc < 2147483648.f) ? (int)fc : (int)0x80000000;
 }
-__device__ __forceinline__ void warp_pixel_rc(const PoseRT& T, const WarpConsts& wc, float px, float py, float pz,
-                                              const LevelDev& lv, float& X, float& Y, float& Z, float& rho2, float& d2,
-                                              int& tr, int& tc, unsigned long long& vis_mask, float& inv_rho) {
-#ifndef RGBD360_NO_LIBM_WARP                          // (A/B builds of the default path without the branch: tools/ab_libs.py)
-    if (lv.libm) {                                    // uniform (a kernel argument)
-        warp_pixel_libm(T, wc, px, py, pz, lv, X, Y, Z, d2, tr, tc);
-        rho2 = fmaf(Z, Z, Y * Y);                     // float32 data of the Jacobian, like inv_rho
-        (void)sqrt_rn(rho2, inv_rho);
-        vis_mask = __builtin_amdgcn_ballot_w64((unsigned)tr < (unsigned)lv.rows) & __builtin_amdgcn_ballot_w64((unsigned)tc < (unsigned)lv.cols);
-        return;
-    }
-#endif
+// the fast definition's arithmetic (warp_pixel_rc without the choice of index arithmetic; the fused launch's warm-up asks it for the
+// indices at the previous pose)
+__device__ __forceinline__ void warp_pixel_fast(const PoseRT& T, const WarpConsts& wc, float px, float py, float pz,
+                                                const LevelDev& lv, float& X, float& Y, float& Z, float& rho2, float& d2,
+                                                int& tr, int& tc, unsigned long long& vis_mask, float& inv_rho) {
     X = fmaf(T.r02, pz, fmaf(T.r01, py, fmaf(T.r00, px, wc.tx)));
     Y = fmaf(T.r12, pz, fmaf(T.r11, py, fmaf(T.r10, px, wc.ty)));
     Z = fmaf(T.r22, pz, fmaf(T.r21, py, fmaf(T.r20, px, wc.tz)));
@@ -220,6 +213,20 @@ __device__ __forceinline__ void warp_pixel_rc(const PoseRT& T, const WarpConsts&
     // predicates of the per-pixel pass are kept as 64-bit lane masks (the compares' own SGPR results, combined on the scalar unit): the
     // ballot of a COMBINED bool costs a v_cndmask + v_cmp pair per use with this compiler
     vis_mask = __builtin_amdgcn_ballot_w64((unsigned)tr < (unsigned)lv.rows) & __builtin_amdgcn_ballot_w64((unsigned)tc < (unsigned)lv.cols);
+}
+__device__ __forceinline__ void warp_pixel_rc(const PoseRT& T, const WarpConsts& wc, float px, float py, float pz,
+                                              const LevelDev& lv, float& X, float& Y, float& Z, float& rho2, float& d2,
+                                              int& tr, int& tc, unsigned long long& vis_mask, float& inv_rho) {
+#ifndef RGBD360_NO_LIBM_WARP                          // (A/B builds of the default path without the branch: tools/ab_libs.py)
+    if (lv.libm) {                                    // uniform (a kernel argument)
+        warp_pixel_libm(T, wc, px, py, pz, lv, X, Y, Z, d2, tr, tc);
+        rho2 = fmaf(Z, Z, Y * Y);                     // float32 data of the Jacobian, like inv_rho
+        (void)sqrt_rn(rho2, inv_rho);
+        vis_mask = __builtin_amdgcn_ballot_w64((unsigned)tr < (unsigned)lv.rows) & __builtin_amdgcn_ballot_w64((unsigned)tc < (unsigned)lv.cols);
+        return;
+    }
+#endif
+    warp_pixel_fast(T, wc, px, py, pz, lv, X, Y, Z, rho2, d2, tr, tc, vis_mask, inv_rho);
 }
 __device__ __forceinline__ unsigned warp_pixel(const PoseRT& T, const WarpConsts& wc, float px, float py, float pz,
                                                const LevelDev& lv, float& X, float& Y, float& Z, float& rho2, float& d2,
@@ -599,8 +606,10 @@ __device__ __forceinline__ void consume_stage(PixW& w, const LevelDev& lv, const
 // stands for the waves w and w + 8, and the block sum runs over the same 16 wave rows in the same order -- bit-identical sums.
 #ifdef RGBD360_EVAL_STAMPS
 #define ESTAMP(i) es[i] = __builtin_amdgcn_s_memrealtime() - es0
+#define ESTAMP_FIRST_CONSUME(k) if ((k) == 0) ESTAMP(5)      // the span's first consume_stage is over: the pipeline is filled
 #else
 #define ESTAMP(i)
+#define ESTAMP_FIRST_CONSUME(k)
 #endif
 // Everything behind the gate: the software-pipelined pixel loop and the block reduction.  On entry the first warp stage (wA, the
 // pixel at i) has been issued and sB holds the source record of the pixel at i + THREADS.
@@ -657,6 +666,7 @@ __device__ __forceinline__ void eval_span(const PoseRT& T, const WarpConsts& wc,
         warp_stage<METHOD, CHECK, SRC>(sB, tid < end - fpx(k + 1), T, wc, lv, bufs, wB);                                \
         sB = load_step(k + 3);                                                                                          \
         consume_stage<METHOD, HG>(wA, lv, ec, AA);                                                                      \
+        ESTAMP_FIRST_CONSUME(k);                                                                                        \
         warp_stage<METHOD, CHECK, SRC>(sA, tid < end - fpx(k + 2), T, wc, lv, bufs, wA);                                \
         sA = load_step(k + 4);                                                                                          \
         consume_stage<METHOD, HG>(wB, lv, ec, AB);
@@ -674,9 +684,11 @@ __device__ __forceinline__ void eval_span(const PoseRT& T, const WarpConsts& wc,
     if (k + 1 < my_steps) {
         warp_stage<METHOD, true, SRC>(sB, tid < end - fpx(k + 1), T, wc, lv, bufs, wB);
         consume_stage<METHOD, HG>(wA, lv, ec, AA);
+        ESTAMP_FIRST_CONSUME(k);
         consume_stage<METHOD, HG>(wB, lv, ec, AB);
     } else {
         consume_stage<METHOD, HG>(wA, lv, ec, AA);
+        ESTAMP_FIRST_CONSUME(k);
     }
     // (Round 3, measured and dropped: FOUR register sets, unrolled by four -- gathers three steps ahead, source records six -- to
     // cover an HBM miss instead of an Infinity-Cache hit: 95 / 111 VGPRs, same sums, and SLOWER everywhere on one box, resident
@@ -727,7 +739,10 @@ __device__ __forceinline__ void eval_span(const PoseRT& T, const WarpConsts& wc,
         double* o = partials + (size_t)(nb + (b == 0 ? 0 : 1)) * kNumPartials;
         for (int k = 0; k < 5; ++k) o[k] = (double)es[k];
         o[5] = (double)es0;
+        o[6] = (double)es[5];      // wave 0's first consume_stage done
         }
+    if (threadIdx.x == THREADS - 64 && (b == 0 || b == nb - 1))      // ... and the youngest wave's
+        partials[(size_t)(nb + (b == 0 ? 0 : 1)) * kNumPartials + 7] = (double)es[5];
     if (threadIdx.x == 0) {     // per-block (start, end) of the last launch: rows nb+8 ...
         double* pb = partials + (size_t)(nb + 8) * kNumPartials + 2 * b;
         pb[0] = (double)es0;
@@ -1763,8 +1778,15 @@ __device__ __forceinline__ void solve_wave1_ft(SolveShared& sh, const SolveWave1
     SOLVE_STAMP_T(stamp_cand, 64);      // update, exponential, candidate pose done
 }
 // solve_waves for the fused launches: wave 1 first in the text behind the barrier and chosen by a SCALAR test, so that it falls through
-// into its path; waves 0 and 2 take the branches.
-__device__ __forceinline__ void solve_waves_ft(SolveShared& sh, const SolveCfg& cfg, const float lam_spec, const bool rank_now, const int h_slot) {
+// into its path; waves 0 and 2 take the branches.  `idle` is what the waves WITHOUT a role in the solve (3 and up) do meanwhile instead
+// of parking at the barrier behind it: nothing (NoIdleWork) everywhere but in k_eval_fs, whose waves warm the first gathers of the pass.
+// It is the last arm of the chain: its code lies behind wave 1's, and waves 0 - 2 never see it.
+struct NoIdleWork {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <class IDLE = NoIdleWork>
+__device__ __forceinline__ void solve_waves_ft(SolveShared& sh, const SolveCfg& cfg, const float lam_spec, const bool rank_now, const int h_slot,
+                                               const IDLE& idle = IDLE()) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (__builtin_expect(cfg.mode == 0 && wave == 1, 1)) {
@@ -1780,6 +1802,8 @@ __device__ __forceinline__ void solve_waves_ft(SolveShared& sh, const SolveCfg& 
     } else if (cfg.mode == 0 && wave == 2 && rank_now) {
         solve_rank_wave(sh, lam_spec);
         SOLVE_STAMP_T(7, 128);     // rank done
+    } else if (wave >= 3) {
+        idle();
     }
 #ifndef RGBD360_SOLVE_TWICE
     SOLVE_STAMP(2);
@@ -1800,6 +1824,12 @@ __device__ __forceinline__ void solve_staged_ft(SolveShared& sh, const SolveCfg&
 __device__ __forceinline__ float uniform_f(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
+__device__ __forceinline__ void pose_from_lds(const float* P, PoseRT& T) {      // P: a column-major 4 x 4 in LDS
+    T.r00 = uniform_f(P[0]); T.r10 = uniform_f(P[1]); T.r20 = uniform_f(P[2]);
+    T.r01 = uniform_f(P[4]); T.r11 = uniform_f(P[5]); T.r21 = uniform_f(P[6]);
+    T.r02 = uniform_f(P[8]); T.r12 = uniform_f(P[9]); T.r22 = uniform_f(P[10]);
+    T.tx = uniform_f(P[12]); T.ty = uniform_f(P[13]); T.tz = uniform_f(P[14]);
+}
 
 // The solve half of a fused launch, behind stage_pending (and the schedule's initialisation): solves the pending pass on the block's
 // own LDS copy of the state, decides what the new state is, hands every wave the pose the new state's `cand` holds (scalar registers)
@@ -1812,7 +1842,8 @@ struct FsDecision {
     int level_now;
     float lam_spec;
 };
-__device__ __forceinline__ FsDecision fs_solve_decide(SolveShared& sh, const int pend, const SolveCfg& cfg, const int level, PoseRT& T) {
+template <class IDLE>
+__device__ __forceinline__ FsDecision fs_solve_decide(SolveShared& sh, const int pend, const SolveCfg& cfg, const int level, PoseRT& T, const IDLE& idle) {
     float lam_spec = 0.f;
     int solved_level = 0;
     if (pend > 0) {                             // uniform: the previous launch ran a pass
@@ -1822,7 +1853,7 @@ __device__ __forceinline__ FsDecision fs_solve_decide(SolveShared& sh, const int
         int h_slot = solve_h_slot(threadIdx.x & 63);
         asm volatile("" : "+v"(h_slot));      // (formed here, not sunk behind the barrier to its use)
         lam_spec = solve_totals(sh);
-        solve_waves_ft(sh, c, lam_spec, /*rank_now=*/false, h_slot);
+        solve_waves_ft(sh, c, lam_spec, /*rank_now=*/false, h_slot, idle);
         __syncthreads();
     }
     // What solve_finish would now do to the state -- commit the step (on the inverse's word: the rank test, the longest of the three
@@ -1839,10 +1870,7 @@ __device__ __forceinline__ FsDecision fs_solve_decide(SolveShared& sh, const int
     d.run = !done_now && d.level_now == level;      // uniform; k_eval's gate on the new state
     d.lam_spec = lam_spec;
     const float* P = d.commit ? sh.shCand : (d.handover ? sh.sst.pose : sh.sst.cand);      // the pose the new state's `cand` holds
-    T.r00 = uniform_f(P[0]); T.r10 = uniform_f(P[1]); T.r20 = uniform_f(P[2]);
-    T.r01 = uniform_f(P[4]); T.r11 = uniform_f(P[5]); T.r21 = uniform_f(P[6]);
-    T.r02 = uniform_f(P[8]); T.r12 = uniform_f(P[9]); T.r22 = uniform_f(P[10]);
-    T.tx = uniform_f(P[12]); T.ty = uniform_f(P[13]); T.tz = uniform_f(P[14]);
+    pose_from_lds(P, T);
     return d;
 }
 // one wave (all 64 lanes): the rank verdict on the step just committed, then the new state.  ILL-POSED (RPI.h:4684-4689): status 1,
@@ -1889,12 +1917,83 @@ __device__ __forceinline__ void fs_write_state(SolveShared& sh, const FsDecision
         reinterpret_cast<int*>(st_out)[w] = val;
     }
 }
+template <class IDLE = NoIdleWork>
 __device__ __forceinline__ bool fs_solve_and_publish(SolveShared& sh, const int pend, const SolveCfg& cfg, const int level, const int nb,
-                                                     const int n_level_px, GNState* __restrict__ st_out, PoseRT& T) {
-    const FsDecision d = fs_solve_decide(sh, pend, cfg, level, T);
+                                                     const int n_level_px, GNState* __restrict__ st_out, PoseRT& T, const IDLE& idle = IDLE()) {
+    const FsDecision d = fs_solve_decide(sh, pend, cfg, level, T, idle);
     if (blockIdx.x == 0 && (threadIdx.x >> 6) == 2) fs_write_state(sh, d, nb, n_level_px, st_out);      // block 0, wave 2
     return d.run;
 }
+
+// WARM-UP of the pass's first gathers, by the waves the solve leaves idle (k_eval_fs's `idle` of solve_waves_ft).  The gathers of a
+// span's first steps cannot be issued before the new pose exists, and only one further warp stage stands in front of the first
+// consume_stage: a far-memory round trip, exposed in every launch (0.7 us from the first warp stage to the end of the first
+// consume_stage on wave 0, 2.2 us on the SIMD's youngest wave: profiles/fused_warm_ab.txt).  The pose the pending pass ran at
+// (sst.cand, in LDS since stage_pending; the solve's wave 0 does not write it) is one Gauss-Newton step away from the new one -- a
+// fraction of a pixel once an alignment is under way -- so the records the first two steps will gather lie in the 128-byte lines
+// their pixels hit at the OLD pose.  The idle waves request one dword of each of those records while waves 0 - 2 solve; the values
+// are dropped.  Nothing the pass computes depends on it: same arithmetic, same order, same bits.  A step of many pixels (the first
+// iterations from a far guess) warms the wrong lines and costs the memory system two gathers per lane, nothing else; offsets off the
+// image are the descriptor's business here as in warp_stage; the fast index arithmetic serves both index modes (a line, not an index,
+// is what has to agree).  What the measurements decided (same file):
+//   - one dword, not the record: the line is what is wanted, and a record that straddles two lines costs two;
+//   - nobody WAITS for the values in front of the barrier behind the solve (that wait, on thirteen waves, made the launch slower than
+//     without the warm-up): they land in `slot`, registers of the kernel's own, dropped behind the pass's first warp stage -- by then
+//     the wave has to wait for younger loads anyway;
+//   - waves 5, 9 and 13 stay out: they share the SIMD of wave 1, whose chain is what every wave is waiting for (totals -> candidate
+//     pose 1.28 -> 1.38 us with them in);
+//   - spans of fewer than kWarmMinSteps steps stay out: on the small levels (one or two steps per span) the first gathers ARE the
+//     pass, nothing was gained, and the launch took 0.2 - 0.3 us longer.
+// RGBD360_NO_WARM: the launch without it; RGBD360_WARM_SHORT_SPANS: without the last rule (A/B builds, tools/ab_libs.py).
+constexpr int kWarmMinSteps = 4;      // (eval_span's threshold for rebalancing the waves: the spans that have a steady state)
+template <int METHOD, int SRC>
+struct WarmFirstGathers {
+    const SolveShared& sh;
+    const LevelDev& lv;
+    const EvalBufs& bufs;
+    const typename SrcForm<SRC>::T &sA, &sB;
+    const int level, span_px;
+    int* slot;      // [4]: photo A / B, depth A / B
+    // byte offset of the target record the pixel of `sraw` hits at pose T (warp_stage's)
+    __device__ __forceinline__ unsigned record_offset(const typename SrcForm<SRC>::T& sraw, const PoseRT& T, const WarpConsts& wc) const {
+        const float4 s = SrcForm<SRC>::value(sraw, lv);
+        float X, Y, Z, rho2, d2, inv_rho;
+        int tr, tc;
+        unsigned long long vis;
+        warp_pixel_fast(T, wc, s.x, s.y, s.z, lv, X, Y, Z, rho2, d2, tr, tc, vis, inv_rho);
+        return __umul24(tr, bufs.row_bytes) + __umul24(tc, 12u);
+    }
+    __device__ __forceinline__ void operator()() const {
+#ifndef RGBD360_NO_WARM
+        // (wave 0 may be setting `done` at this moment: either answer is right, the values are dropped)
+        if (sh.sst.level_active != level || sh.sst.done) return;      // uniform: the pending pass was another level's, or the level is over
+#ifndef RGBD360_WARM_SHORT_SPANS
+        if (span_px <= (kWarmMinSteps - 1) * kEvalThreads) return;    // uniform
+#endif
+        if (((threadIdx.x >> 6) & 3) == 1) return;                    // wave 1's SIMD
+        const float* P = sh.sst.cand;
+        PoseRT T;
+        pose_from_lds(P, T);
+        const WarpConsts wc = make_warp_consts(T, lv);
+        const unsigned offA = record_offset(sA, T, wc), offB = record_offset(sB, T, wc);
+        if (METHOD != 1) {
+            slot[0] = __builtin_amdgcn_raw_buffer_load_b32(bufs.trgP, (int)offA, 0, 0);
+            slot[1] = __builtin_amdgcn_raw_buffer_load_b32(bufs.trgP, (int)offB, 0, 0);
+        }
+        if (METHOD != 0) {
+            slot[2] = __builtin_amdgcn_raw_buffer_load_b32(bufs.trgD, (int)offA, 0, 0);
+            slot[3] = __builtin_amdgcn_raw_buffer_load_b32(bufs.trgD, (int)offB, 0, 0);
+        }
+#endif
+    }
+    // where the values end: an empty statement that names them (the compiler waits for them here, and keeps the loads)
+    __device__ __forceinline__ void drop() const {
+#ifndef RGBD360_NO_WARM
+        if (METHOD != 1) asm volatile("" :: "v"(slot[0]), "v"(slot[1]));
+        if (METHOD != 0) asm volatile("" :: "v"(slot[2]), "v"(slot[3]));
+#endif
+    }
+};
 
 template <int METHOD, int SRC = 0>
 __global__ __launch_bounds__(kEvalThreads) void k_eval_fs(const GNState* __restrict__ st_in, GNState* __restrict__ st_out,
@@ -1938,12 +2037,16 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_fs(const GNState* __restr
     const typename SrcForm<SRC>::T sA = SrcForm<SRC>::load(lv, src0, n_px, base, (unsigned)threadIdx.x << 4, cur);
     const typename SrcForm<SRC>::T sB = SrcForm<SRC>::load(lv, src0, n_px, base + kEvalThreads, (unsigned)threadIdx.x << 4, cur);
     PoseRT T;
-    const bool run = fs_solve_and_publish(sh, pend, cfg, level, nb, lv.n, st_out, T);
+    // (an init.on launch has pend = 0: its pose is known, there is no solve to hide behind and no warm-up)
+    int warm_slot[4] = {0, 0, 0, 0};
+    const WarmFirstGathers<METHOD, SRC> warm = {sh, lv, bufs, sA, sB, level, end - base, warm_slot};
+    const bool run = fs_solve_and_publish(sh, pend, cfg, level, nb, lv.n, st_out, T, warm);
     if (!run) return;
     const WarpConsts wc = make_warp_consts(T, lv);
     ESTAMP(0);
     PixW wA;
     warp_stage<METHOD, true, SRC>(sA, i < end, T, wc, lv, bufs, wA);
+    warm.drop();
     ESTAMP(1);
     eval_span<METHOD, true, kEvalThreads, SRC>(T, wc, lv, ec, bufs, src0, n_px, base, end, b, nb, wA, sB, cur, partials_out, es, es0);
 }

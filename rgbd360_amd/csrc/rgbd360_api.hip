@@ -1382,12 +1382,12 @@ int rgbd360_time_solve_kernel(rgbd360_ctx* ctx, int level, int mode, int reps, f
     return 0;
 }
 
-int rgbd360_debug_eval_stamps(rgbd360_ctx* ctx, int level, double out[12]) {
+int rgbd360_debug_eval_stamps(rgbd360_ctx* ctx, int level, double out[16]) {      // blocks 0 and nb - 1, 8 values each
     if (!ctx || !out || level < 0 || level >= (int)ctx->levels.size()) return -1;
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     const int nb = ctx->levels[level].nblocks;
-    HIPC(ctx, hipMemcpy(out, ctx->d_partials + (size_t)nb * kNumPartials, 6 * sizeof(double), hipMemcpyDeviceToHost));
-    HIPC(ctx, hipMemcpy(out + 6, ctx->d_partials + (size_t)(nb + 1) * kNumPartials, 6 * sizeof(double), hipMemcpyDeviceToHost));
+    HIPC(ctx, hipMemcpy(out, ctx->d_partials + (size_t)nb * kNumPartials, 8 * sizeof(double), hipMemcpyDeviceToHost));
+    HIPC(ctx, hipMemcpy(out + 8, ctx->d_partials + (size_t)(nb + 1) * kNumPartials, 8 * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

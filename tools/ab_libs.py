@@ -76,3 +76,5 @@ for rnd in range(rounds):
         prog = [os.path.join(ROOT, "tools", "host_lm_perf.py")] if hostlm else ["-c", CHILD]
         r = subprocess.run([sys.executable] + prog + [lib_of(lib)] + extra, capture_output=True, text=True, env=env)
         print("%-10s|" % name, r.stdout.strip() or r.stderr.strip()[-600:], flush=True)
+        if r.returncode != 0:      # a child that died leaves the card in an unknown state: no further arm is started on it
+            sys.exit("arm %s ended with status %d: stopping" % (name, r.returncode))
