@@ -38,6 +38,14 @@ int rgbd360_forced_iters_batch(rgbd360_ctx* ctx, int n_pairs, const uint8_t* rgb
  * out_i: {status, done, level_active, it, n_evals, pend_nb}; cand_out / update_out (may be NULL): the state's candidate pose / update. */
 int rgbd360_debug_solve_partials(rgbd360_ctx* ctx, int level, const double row[32], int method, int fused, int out_i[6],
                                  float cand_out[16], float update_out[6]);
+/* One pending solve on a hand-made partial TABLE at the identity pose on `level`: table rows 0 ... n_rows - 1 = `rows` (n_rows x 32
+ * doubles, 1 <= n_rows <= 256), every other row zero, the state's pend_nb = n_rows.  route 0: k_solve on n_rows rows; 1: the prologue
+ * of the fused launch k_eval_fs; 2: k_solve_pending; routes 1 and 2 are launched with rows_hint (1 ... 256) as the host's bound on the
+ * pending rows -- a bound below n_rows is the late-row path: the device notices and fetches the rest.  tot_out: the state's 32 column
+ * totals (a wrong row group or summation order shows in their bits; one row cannot show it).  out_i, cand_out (may be NULL): as
+ * rgbd360_debug_solve_partials.  Both frames must be set. */
+int rgbd360_debug_solve_table(rgbd360_ctx* ctx, int level, const double* rows, int n_rows, int rows_hint, int method, int route,
+                              double tot_out[32], int out_i[6], float cand_out[16]);
 /* One solve from a chosen Gauss-Newton state: the state of `level` is initialised at in->pose (pose and cand), then update, lambda,
  * error, first and it are overwritten with the given values; the solve runs with the given termination settings (max_iters,
  * tol_residual, tol_update, forced) and error form (occlusion 0: sqrt(sum / n); 1 / 2: photo RMS + depth RMS) on the partial row

@@ -24,7 +24,7 @@ SYMBOLS = [
     "rgbd360_rig_create", "rgbd360_rig_destroy", "rgbd360_rig_last_error", "rgbd360_rig_set_target", "rgbd360_rig_set_source",
     "rgbd360_rig_eval", "rgbd360_rig_align", "rgbd360_rig_use_saliency", "rgbd360_rig_set_index_arithmetic", "rgbd360_rig_get_index_arithmetic",
     "rgbd360_rig_warp_indices", "rgbd360_debug_solve_partials",
-    "rgbd360_debug_solve_state",
+    "rgbd360_debug_solve_state", "rgbd360_debug_solve_table",
     "rgbd360_store_create", "rgbd360_store_destroy", "rgbd360_store_last_error", "rgbd360_store_entry_bytes", "rgbd360_store_put",
     "rgbd360_store_occupied", "rgbd360_store_align",
     "rgbd360_store_overlap_default_params", "rgbd360_store_overlap", "rgbd360_store_overlap_all", "rgbd360_overlap_candidates",
@@ -492,6 +492,7 @@ def load() -> C.CDLL:
                                              C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rgbd360_debug_solve_partials.argtypes = [vp, i32, vp, i32, i32, vp, f32p, f32p]
     L.rgbd360_debug_solve_state.argtypes = [vp, i32, vp, C.POINTER(SolveStateIn), i32, i32, i32, C.POINTER(SolveStateOut)]
+    L.rgbd360_debug_solve_table.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, f32p]
     L.rgbd360_set_plane_refinement.argtypes = [vp, i32, C.c_float]
     L.rgbd360_set_plane_color_image.argtypes = [vp, vp, C.c_size_t, i32, i32, i32, i32]
     L.rgbd360_plane_refinement_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

@@ -284,6 +284,13 @@ __device__ __forceinline__ double add_other_half_d(double v) {
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(hi), "+v"(hi2));
     return __hiloint2double(hi, lo) + __hiloint2double(hi2, lo2);
 }
+// v(lane) + v(lane ^ 16) in every lane (float64): the 16-lane rows 0 <-> 1 and 2 <-> 3 exchanged by v_permlane16_swap
+__device__ __forceinline__ double add_other_row_d(double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v), lo2 = lo, hi2 = hi;
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(lo), "+v"(lo2));      // lo: the even row of every pair | lo2: the odd row
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(hi), "+v"(hi2));
+    return __hiloint2double(hi, lo) + __hiloint2double(hi2, lo2);
+}
 __device__ __forceinline__ float swap16_add(float a, float b) {   // even rows: a's row pair, odd rows: b's row pair
     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
     return a + b;
@@ -1480,33 +1487,81 @@ __device__ __forceinline__ int stage_pending(SolveShared& sh, const GNState* __r
     constexpr int J = kPendingRows / Q;
     static_assert(J * Q == kPendingRows && J <= 16, "whole batches");
     const int tid = threadIdx.x;
-    const int v = tid % kNumPartials, q = tid / kNumPartials;
-    double tmp[J];
-    tmp[0] = partials[(size_t)q * kNumPartials + v];
-#pragma unroll
-    for (int j = 1; j < J; ++j) tmp[j] = 0.0;
-    // (fall-through = the full table: the level-0 launch runs straight-line code -- as an if / else with the short form first its loads
-    // left 0.2 us later, behind a taken branch into a cold instruction-cache line)
-    if (rows_hint > Q) {                        // uniform: a scalar compare on a preloaded argument
-#pragma unroll
-        for (int j = 1; j < J; ++j) tmp[j] = partials[(size_t)(q + j * Q) * kNumPartials + v];
-    }
-    int word = 0;
-    if (tid < kStateWords) word = reinterpret_cast<const int*>(st_in)[tid];
+    // The table is fetched by the block's first kRowLoadWaves waves in 16-byte pieces: thread t holds row group q = t / 16 and the value pair
+    // (2 vp, 2 vp + 1), vp = t % 16, of the rows q, q + Q, ..., q + (J - 1) Q.  Batch j of the table is 8 KB of consecutive bytes and the
+    // thread's piece of it lies at byte 16 t: one 32-bit vector offset serves every load, the batch bases are formed on the scalar unit
+    // (global_load_dwordx4 with a scalar base), and a wave's request is 1 KB of consecutive bytes (four rows) -- half as many requests
+    // per CU as with 8-byte pieces, no 64-bit vector address arithmetic in front of them.  The other waves request nothing here and go
+    // straight on to the source records.  Every sum keeps its association: per value s = 0 + x_0 + x_1 + ... in row order with the
+    // explicit zero terms, then red[w] = s[2 w] + s[2 w + 1] (reduce_rows_to_lds' pairs; the row groups 4 w' ... 4 w' + 3 of loading
+    // wave w' lie in its four 16-lane rows, so one row swap brings the two partners of red[2 w'] and of red[2 w' + 1] together).
+    constexpr int kRowLoadWaves = kSolveThreads / 64 / 2;
+    static_assert(kNumPartials == 32 && Q == 32 && kStateWords <= kRowLoadWaves * 64, "16-byte row fetch: 16 lanes per row group, the state staged by the loading waves");
+    struct alignas(16) D2 { double x, y; };
+    constexpr unsigned kBatchBytes = Q * kNumPartials * sizeof(double);
     const int nb = st_in->pend_nb;        // uniform (scalar load)
-    // The host's bound is checked, not trusted: a state that holds more pending rows than the short form requested gets the rest now
-    // (a second round trip, never taken by the library's own schedules; without it those rows would silently count as zero).
-    if (nb > Q && rows_hint <= Q) {             // uniform
+    // (threads < kStateWords only, and deliberately not zeroed for the others: the compiler shares the long form's code with the late-row arm,
+    // where the state's load is already pending, and a plain write of this register there waits for that load -- on the long form, for a row)
+    int word;
+    // (fall-through = the full table on a loading wave: the level-0 launch runs straight-line code -- as an if / else with the short
+    // form first its loads left 0.2 us later, behind a taken branch into a cold instruction-cache line)
+    if (__builtin_amdgcn_readfirstlane(tid) < kRowLoadWaves * 64) {      // wave-uniform: a scalar branch
+        const unsigned piece = (unsigned)tid * 16u;
+        D2 tmp[J];
+        auto fetch = [&](const int j) {
+            // scalar base + 32-bit vector offset: the 8 KB step does not fit a load's immediate offset and would, as a constant, be folded
+            // into a 64-bit vector address; the offset is named per load because the instruction selector only sees the zero-extension
+            // of a value defined in the load's own basic block
+            unsigned step = j * kBatchBytes, off = piece;
+            asm("" : "+s"(step));
+            asm("" : "+v"(off));
+            tmp[j] = *reinterpret_cast<const D2*>(reinterpret_cast<const char*>(partials) + step + off);
+        };
+        auto fetch_rest = [&]() {
 #pragma unroll
-        for (int j = 1; j < J; ++j) tmp[j] = partials[(size_t)(q + j * Q) * kNumPartials + v];
-    }
+            for (int j = 1; j < J; ++j) fetch(j);
+        };
+        auto stage_word = [&]() {
+            if (tid < kStateWords) word = reinterpret_cast<const int*>(st_in)[tid];
 #ifdef RGBD360_SOLVE_STAMPS
-    if (tid == 0) sh.stamp[3] = __builtin_amdgcn_s_memrealtime();      // loads issued (absolute; made relative below)
+            if (tid == 0) sh.stamp[3] = __builtin_amdgcn_s_memrealtime();      // loads issued (absolute; made relative below)
 #endif
-    double s = 0.0;
+        };
+        // rest: batches 1 ... J - 1 were requested; without them their terms are the explicit zeros they would be with nb <= Q
+        auto sum_to_lds = [&](const bool rest) {
+            const int q = tid >> 4, vp = tid & 15;
+            double s0 = 0.0, s1 = 0.0;
 #pragma unroll
-    for (int j = 0; j < J; ++j) s += (q + j * Q < nb) ? tmp[j] : 0.0;      // the order of solve_block's sum (its zero rows add nothing)
-    reduce_rows_to_lds(sh, s);
+            for (int j = 0; j < J; ++j) {       // the order of solve_block's sum (its zero rows add nothing)
+                const bool in = (j == 0 || rest) && q + j * Q < nb;
+                s0 += in ? tmp[j].x : 0.0;
+                s1 += in ? tmp[j].y : 0.0;
+            }
+            const double p0 = add_other_row_d(s0), p1 = add_other_row_d(s1);      // rows 0, 1: s[4 w'] + s[4 w' + 1]; rows 2, 3: s[4 w' + 2] + s[4 w' + 3]
+            if ((tid & 16) == 0) {
+                double* const red = &sh.red[tid >> 5][2 * vp];              // row 0 -> red[2 w'], row 2 -> red[2 w' + 1]
+                red[0] = p0;
+                red[1] = p1;
+            }
+        };
+        fetch(0);
+        if (__builtin_expect(rows_hint > Q, 1)) {      // uniform: a scalar compare on a kernel argument
+            fetch_rest();
+            stage_word();
+            __builtin_amdgcn_sched_barrier(0);      // every request is out before the first use of a row (the scheduler would put the state's behind it)
+            sum_to_lds(true);
+        } else {
+            stage_word();
+            // The host's bound is checked, not trusted: a state that holds more pending rows than the short form requested gets the rest
+            // now (a second round trip, never taken by the library's own schedules; without it those rows would silently count as zero).
+            if (nb > Q) {                       // uniform
+                fetch_rest();
+                sum_to_lds(true);
+            } else {
+                sum_to_lds(false);
+            }
+        }
+    }
     if (tid < kStateWords) reinterpret_cast<int*>(&sh.sst)[tid] = word;
 #ifdef RGBD360_SOLVE_STAMPS
     if (tid == 0) {

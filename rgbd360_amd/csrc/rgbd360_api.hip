@@ -1167,6 +1167,47 @@ int rgbd360_debug_solve_partials(rgbd360_ctx* ctx, int level, const double row[3
     return 0;
 }
 
+// One pending solve on a hand-made partial TABLE (rgbd360_hip_diag.h): rows 0 ... n_rows - 1 = `rows`, every other row zero, pend_nb = n_rows,
+// through k_solve (route 0), the prologue of k_eval_fs (1) or k_solve_pending (2); the fused routes are told to expect rows_hint rows.
+// What a single row cannot show -- which row group a row is summed in, and in which order -- shows in tot.
+int rgbd360_debug_solve_table(rgbd360_ctx* ctx, int level, const double* rows, int n_rows, int rows_hint, int method, int route,
+                              double tot_out[32], int out_i[6], float cand_out[16]) {
+    int rc = check_args(ctx, level, method);
+    if (rc) return rc;
+    if (!rows || !tot_out || !out_i || n_rows < 1 || n_rows > kPendingRows || rows_hint < 1 || rows_hint > kPendingRows || route < 0 || route > 2)
+        return fail(ctx, -1, "bad arguments");
+    if (route && !fused_ok(ctx, 0)) return fail(ctx, -1, "the fused-solve schedule is switched off");
+    hipSetDevice(ctx->p.device);
+    const Level& L = ctx->levels[level];
+    float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    launch_level_init(ctx, level, I, 1);
+    const size_t table_rows = (size_t)std::max((ctx->max_blocks + 31) / 32 * 32, kPendingRows);
+    HIPC(ctx, hipMemsetAsync(ctx->d_partials, 0, table_rows * kNumPartials * sizeof(double), ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(ctx->d_partials, rows, (size_t)n_rows * kNumPartials * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (route == 0) {
+        SolveCfg cfg;
+        cfg.level = level; cfg.mode = 0; cfg.n_pixels = L.n;
+        cfg.forced = 0; cfg.max_iters = ctx->p.max_iters; cfg.occ = 0;
+        cfg.tol_residual = ctx->p.tol_residual; cfg.tol_update = ctx->p.tol_update;
+        hipLaunchKernelGGL(k_solve, dim3(1), dim3(kSolveThreads), 0, ctx->stream, ctx->d_state, ctx->d_partials, n_rows, cfg);
+    } else {
+        const int pend[2] = {n_rows, L.n};          // as if a pass of this level had just written n_rows rows
+        HIPC(ctx, hipMemcpyAsync(&ctx->d_state[0].pend_nb, pend, sizeof(pend), hipMemcpyHostToDevice, ctx->stream));
+        ctx->pend_rows_hint = rows_hint;
+        if (route == 1) launch_eval_fused(ctx, level, method, 0);      // the state is read as this launch leaves it
+        else launch_solve_pending(ctx, 0, false);
+    }
+    HIPC(ctx, hipGetLastError());
+    rc = read_state_sync(ctx);
+    ctx->pend_rows_hint = kPendingRows;             // whatever follows knows no bound
+    if (rc) return rc;
+    const GNState& S = *ctx->h_state;
+    memcpy(tot_out, S.tot, sizeof(double) * kNumPartials);
+    out_i[0] = S.status; out_i[1] = S.done; out_i[2] = S.level_active; out_i[3] = S.it; out_i[4] = S.n_evals; out_i[5] = S.pend_nb;
+    if (cand_out) memcpy(cand_out, S.cand, sizeof(float) * 16);
+    return 0;
+}
+
 // One solve from a chosen state (rgbd360_hip_diag.h): the state is initialised at in->pose like a level entry, the rest of the
 // chosen state is written over it field by field, and the row is placed as in rgbd360_debug_solve_partials.
 int rgbd360_debug_solve_state(rgbd360_ctx* ctx, int level, const double row[32], const rgbd360_solve_state_in* in, int method,

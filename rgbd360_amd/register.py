@@ -422,6 +422,18 @@ class RegisterPhotoICP:
                     pose=pose_from_cm(np.array(so.pose[:], np.float32)), update=np.array(so.update[:], np.float32),
                     lam=so.lambda_, error=so.error, new_error=so.new_error, diff_error=so.diff_error)
 
+    def debug_solve_table(self, level: int, rows, rows_hint=None, method: int = 0, route: int = 0):
+        """rgbd360_debug_solve_table: one pending solve on a hand-made partial table (rows: n_rows x 32 float64, the rest of the table
+        zero, pend_nb = n_rows) through k_solve (route 0), the prologue of k_eval_fs (1) or k_solve_pending (2); rows_hint (default
+        n_rows): the host's bound on the pending rows the fused routes are launched with.  Returns the state's column totals `tot`."""
+        rows = np.ascontiguousarray(rows, np.float64)
+        assert rows.ndim == 2 and rows.shape[1] == 32
+        tot, out_i, cand = np.zeros(32, np.float64), np.zeros(6, np.int32), np.zeros(16, np.float32)
+        self._check(self._L.rgbd360_debug_solve_table(self._ctx(), level, _ptr(rows), rows.shape[0], int(rows_hint or rows.shape[0]), method, route,
+                                                      _ptr(tot), _ptr(out_i), _ptr(cand)))
+        return dict(tot=tot, status=int(out_i[0]), done=int(out_i[1]), level_active=int(out_i[2]), it=int(out_i[3]), n_evals=int(out_i[4]),
+                    pend_nb=int(out_i[5]), cand=pose_from_cm(cand))
+
     def forced_iters_call(self, level: int, pose0, method: int, n_iters: int):
         """A closure that runs rgbd360_forced_iters with every argument converted ONCE (for timed loops: the numpy / ctypes
         conversions of forced_iters cost 10-15 us per call, as much as a Gauss-Newton iteration).  call() -> status;

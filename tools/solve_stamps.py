@@ -4,6 +4,8 @@ then on the GPU box:
     python tools/solve_stamps.py                      phase ends of one launch, levels 0 and 3, methods 0 and 2 (2048x1024)
     python tools/solve_stamps.py chain [RUNS] [LIB]   "totals -> candidate pose done" of RUNS launches (default 5), 2048x1024 and 256x128;
                                                       LIB: another stamps build of the library (A/B against another commit's)
+    python tools/solve_stamps.py fetch [RUNS] [LIB]   the row fetch of stage_pending: "loads issued", "row sums in LDS" (behind the barrier), totals
+                                                      and candidate pose, mean over RUNS launches, 2048x1024 and 256x128
     python tools/solve_stamps.py twice [RUNS]         the RGBD360_SOLVE_TWICE build: wave 1 of every block walks its path a first time into
                                                       spare LDS slots and then for real -- the cold and the warm price of the same code,
                                                       per phase (inverse done / update + exponential + candidate done)"""
@@ -54,6 +56,12 @@ print("library", os.path.basename(_lib.LIB_PATH))
 for cols, rows, n_pyr in ((2048, 1024, 4), (256, 128, 2)):
     reg = make_reg(cols, rows, n_pyr)
     stamps_of(reg, 0, 0)       # (the first schedule of a context pays for allocations)
+    if mode == "fetch":
+        a = np.array([stamps_of(reg, 0, 0) for _ in range(runs)])
+        m = a.mean(axis=0)
+        print("%dx%d | loads issued %.3f | row sums in LDS %.3f (min %.2f max %.2f) | totals %.3f | candidate pose %.3f | state written %.3f us  (mean of %d launches)"
+              % (cols, rows, m[3], m[0], a[:, 0].min(), a[:, 0].max(), m[1], m[6], m[4], runs), flush=True)
+        continue
     for run in range(runs):
         s = stamps_of(reg, 0, 0)
         if mode == "twice":      # stamps 7 / 2: the first walk's inverse / candidate; 5 / 6: the second's
