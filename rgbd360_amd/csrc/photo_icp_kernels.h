@@ -938,19 +938,32 @@ __device__ __forceinline__ float bcast(float v, int lane_uniform) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane_uniform));
 }
 
-// Lanes 0-5 hold the columns of M, lanes 6-11 the columns of the identity; returns false when a pivot is zero.
-// On return lanes 6-11 hold the columns of M^-1 in x[0..5].
-__device__ __forceinline__ bool lu_inverse6_lanes(const float* M /*LDS, column-major*/, int lane, float x[6]) {
-    float a[6];
+// lu_inverse6_lanes: lanes 0-5 hold the columns of M, lanes 6-11 the columns of the identity; returns false when a pivot is zero.  On
+// return lanes 6-11 hold the columns of M^-1 in x[0..5].  No EXEC-divergent region and no branch per step (why: above solve_wave1): the
+// column comes from one read at a clamped address (lanes >= 6 read column 5 and drop it), the identity from lane predicates, the
+// elimination's lane > k is a select.  The elimination runs first WITHOUT row swaps and only notes whether some step's pivot was not its
+// diagonal entry; if so -- normal equations: rarely -- it is done again from the matrix with the swap arms, behind the path.  Where no
+// step swaps the two eliminations are the same operations, so the result is the swapping one's bit for bit either way.
+__device__ __forceinline__ void lu_load6(const float* M, const int lane, float a[6]) {
+    const bool is_m = lane < 6;
+    const int col = is_m ? lane : 5;
 #pragma unroll
-    for (int r = 0; r < 6; ++r) a[r] = lane < 6 ? M[lane * 6 + r] : ((lane - 6) == r ? 1.f : 0.f);
-    bool ok = true;
-    float rk[6];                    // reciprocals of the six pivots (wave-uniform): the elimination's multipliers AND the back substitution's divisors
+    for (int r = 0; r < 6; ++r) {
+        const float m = M[col * 6 + r];
+        const float id = (lane - 6) == r ? 1.f : 0.f;
+        a[r] = is_m ? m : id;
+    }
+}
+// rk: the reciprocals of the six pivots (wave-uniform), the elimination's multipliers AND the back substitution's divisors.  Returns
+// whether every pivot was where the elimination took it from (always, with SWAPS).
+template <bool SWAPS>
+__device__ __forceinline__ bool lu_eliminate6(float a[6], float rk[6], const int lane, bool& ok) {
+    bool in_place = true;
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
         float ck[6];
 #pragma unroll
-        for (int r = k; r < 6; ++r) ck[r] = bcast(a[r], k);      // (rows above k are finished: round 5 stopped broadcasting them)
+        for (int r = k; r < 6; ++r) ck[r] = bcast(a[r], k);      // (rows above k are finished)
         // Pivot search on the SCALAR unit: the column's six values are wave-uniform (v_readlane results), and for finite values
         // |x| > |y| is the unsigned comparison of their bit patterns without the sign -- integer compares and selects the scalar ALU
         // does beside the vector pipe (as float compares they were 15 v_cmp + 30 v_cndmask of the solve's one busy wave).  Same pivot as
@@ -965,26 +978,43 @@ __device__ __forceinline__ bool lu_inverse6_lanes(const float* M /*LDS, column-m
                 piv = r;
             }
         }
-        if (best == 0u) ok = false;
-        // the row swap under a SCALAR branch (piv is wave-uniform): plain register swaps in the one arm that runs -- as selects over every
-        // candidate row they were 70 of the inverse's 285 vector instructions, each a link of the launch's longest dependent chain
-        const int pv = __builtin_amdgcn_readfirstlane(piv);
-        if (pv != k) {              // (normal equations: the diagonal entry is the pivot more often than not -- one scalar test then)
+        ok = best == 0u ? false : ok;
+        if (SWAPS) {
+            // the row swap under a SCALAR branch (piv is wave-uniform): plain register swaps in the one arm that runs -- as selects over
+            // every candidate row they were 70 of the inverse's 285 vector instructions, each a link of the launch's longest dependent chain
+            const int pv = __builtin_amdgcn_readfirstlane(piv);
+            if (pv != k) {
 #pragma unroll
-            for (int r = k + 1; r < 6; ++r)
-                if (pv == r) {
-                    asm volatile("v_swap_b32 %0, %1" : "+v"(a[k]), "+v"(a[r]));      // (an asm statement is not if-converted into selects)
-                    const float t = ck[k]; ck[k] = ck[r]; ck[r] = t;
-                }
+                for (int r = k + 1; r < 6; ++r)
+                    if (pv == r) {
+                        asm volatile("v_swap_b32 %0, %1" : "+v"(a[k]), "+v"(a[r]));      // (an asm statement is not if-converted into selects)
+                        const float t = ck[k]; ck[k] = ck[r]; ck[r] = t;
+                    }
+            }
+        } else {
+            in_place = piv != k ? false : in_place;
         }
         // multipliers l = c_r / c_k through ONE exact reciprocal per step (the five IEEE division sequences were the longest
         // dependent chain of the kernel); l differs from the quotient by at most one rounding
         rk[k] = rcp_rn(ck[k]);
+        const bool below = lane > k;
 #pragma unroll
         for (int r = k + 1; r < 6; ++r) {
             const float l = ck[r] * rk[k];
-            if (lane > k) a[r] -= l * a[k];
+            const float t = a[r] - l * a[k];
+            a[r] = below ? t : a[r];
         }
+    }
+    return in_place;
+}
+__device__ __forceinline__ bool lu_inverse6_lanes(const float* M /*LDS, column-major*/, int lane, float x[6]) {
+    float a[6], rk[6];
+    bool ok = true;
+    lu_load6(M, lane, a);
+    if (__builtin_expect(!lu_eliminate6<false>(a, rk, lane, ok), 0)) {
+        ok = true;
+        lu_load6(M, lane, a);
+        lu_eliminate6<true>(a, rk, lane, ok);
     }
     // back substitution on the right-hand-side lanes: U[r][c] is row r of lane c; U[r][r] is step r's pivot (row r is final once step r
     // has run: later steps swap and update rows below it only), so 1 / U[r][r] is the reciprocal that step already formed
@@ -1097,6 +1127,8 @@ __device__ __forceinline__ int qr_rank6_lanes(const float* M /*LDS, column-major
 // the rank test and the 6x6 inverse on two waves side by side.
 // ---------------------------------------------------------------------------------------------------------
 constexpr int kSolveThreads = 1024;
+constexpr int kStateWords = sizeof(GNState) / 4;      // the state moves between memory and LDS word by word, one thread per word
+static_assert(sizeof(GNState) % 4 == 0 && kStateWords <= kSolveThreads, "GNState staging");
 // LDS of one solve: the staged state, the per-thread-group partial sums and the hand-over slots of the three working waves.
 struct SolveShared {
     GNState sst;
@@ -1160,184 +1192,232 @@ __device__ __forceinline__ int solve_rank_wave(SolveShared& sh, const float lam_
     return rk;
 }
 
-// solve_waves: three waves side by side -- wave 0 the bookkeeping, wave 1 the 6x6 inverse, the update, the SE(3) exponential and
-// the candidate pose, wave 2 the rank test (rank_now; the fused launch runs it later, on one block only).  No barrier behind it.
-__device__ __forceinline__ void solve_waves(SolveShared& sh, const SolveCfg& cfg, const float lam_spec, const bool rank_now) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+// Wave 0 (lanes 0-41): the bookkeeping -- accept test, stop test, what the state records.  Lane 0 takes the scalar decisions, lanes
+// 0-41 move the 36 + 6 matrix entries.
+__device__ __forceinline__ void solve_bookkeeping_wave(SolveShared& sh, const SolveCfg& cfg, const int lane) {
     GNState* st = &sh.sst;
     const double* tot = sh.sst.tot;
-    // ---- waves 1 and 2 start the 6x6 work speculatively, in parallel with the bookkeeping of wave 0: a step is only ever
-    //      computed from the H of THIS pass (go implies take, see below), and the damping of the rank test is known from the
-    //      state before the decision: lambda on the first pass of a level, lambda / 5 after an accepted step (a rejected
-    //      step ends the level, so its result is simply dropped).  RPI.h:4682, 4693, 4718 ----
-    if (cfg.mode == 0 && wave == 2 && rank_now) {
+    // normal equations at the evaluated pose (float like the reference's `hessian` / `gradient`): lane l < 36 owns
+    // H(r,c), r = l/6, c = l%6 (upper-triangle slot a*(13-a)/2 + (b-a)); lanes 36-41 own g
+    float hval = 0.f;
+    if (lane < 36) {
+        const int r = lane / 6, c = lane - 6 * r;
+        const int aa = r < c ? r : c, bb = r < c ? c : r;
+        hval = (float)tot[P_H + (aa * (13 - aa)) / 2 + (bb - aa)];
+    } else if (lane < 42) {
+        hval = (float)tot[P_G + lane - 36];
+    }
+    int take = 0, go = 0;
+    if (lane == 0) {
+        st->n_evals += 1;
+        const double err2 = tot[P_E2P] + tot[P_E2D];
+        const double nvalid = tot[P_NP] + tot[P_ND];
+        const double new_error = cfg.occ == 0 ? sqrt(err2 / nvalid)      // RPI.h:2738
+                                              : sqrt(tot[P_E2P] / tot[P_NP]) + sqrt(tot[P_E2D] / tot[P_ND]);
+        st->new_error = new_error;
+        if (cfg.mode == 1) {
+            take = 1;
+        } else {
+            bool stop = false;
+            if (st->first) {
+                st->first = 0;
+                if (nvalid == 0.0 || new_error != new_error) {      // no residuals (occlusion modes: 0/0 of an unused modality)
+                    st->status = 2;
+                    st->done = 1;
+                    stop = true;
+                } else {
+                    st->error = new_error;           // RPI.h:4599
+                    st->diff_error = new_error;      // RPI.h:4605
+                    take = 1;                        // cand == pose
+                }
+            } else {
+                const double diff = st->error - new_error;   // RPI.h:4713
+                st->diff_error = diff;
+                if (cfg.forced || diff > cfg.tol_residual) {  // RPI.h:4715-4722
+                    st->lambda = st->lambda / 5.0;
+                    st->error = new_error;
+                    st->it += 1;
+                    st->iters[cfg.level & 7] = st->it;
+                    take = 2;                        // 2: also promote cand -> pose
+                }
+            }
+            if (take) {
+                st->acc_e2p = tot[P_E2P];
+                st->acc_e2d = tot[P_E2D];
+                st->acc_np = (long long)tot[P_NP];
+                st->acc_nd = (long long)tot[P_ND];
+                st->acc_nvis = (long long)tot[P_NVIS];
+            }
+            if (!stop) {
+                // while(it < maxIters && update_pose.norm() > tol_update && diff_error > tol_residual)   RPI.h:4611
+                float un = 0.f;
+                for (int i = 0; i < 6; ++i) un += st->update[i] * st->update[i];
+                un = sqrtf(un);
+                go = cfg.forced || (st->it < cfg.max_iters && (double)un > cfg.tol_update && st->diff_error > cfg.tol_residual);
+                if (!go) st->done = 1;
+            }
+            if (go) {
+                st->used_nvis = st->acc_nvis;
+                st->used_npix = cfg.n_pixels;
+            }
+        }
+        sh.shGo = go;
+    }
+    take = __builtin_amdgcn_readfirstlane(take);
+    go = __builtin_amdgcn_readfirstlane(go);
+    if (take == 2 && lane < 16) st->pose[lane] = st->cand[lane];
+    if (take) {
+        if (lane < 36) st->H[lane] = hval;
+        else if (lane < 42) st->g[lane - 36] = hval;
+    }
+    if (go) {
+        // a step is only ever computed right after its pose was taken (go implies take), so hval is H / g at `pose`;
+        // record them as "used" (what the reference's `hessian` / `SSO` members hold afterwards)
+        if (lane < 36) {
+            st->Hused[lane] = hval;
+        } else if (lane < 42) {
+            st->gused[lane - 36] = hval;
+        }
+    }
+}
+
+// Wave 1's chain is FALL-THROUGH code.  A fused launch (k_eval_fs, k_occ_build_fs) walks it once, one wave per CU, with fifteen waves
+// parked at the barrier and the instruction cache freshly invalidated: what it pays for is taken branches into lines not fetched yet,
+// not arithmetic.  So the common case (the diagonal entry is every step's pivot, a rotation with angle^2 < 0.25) falls through from the
+// barrier behind solve_totals to the store of shCand: no EXEC-divergent region (lane predicates become selects; stores go to a clamped
+// slot, where the lanes that share it hold the same value) and no taken branch (the swap arms and the two rare arms of the exponential
+// lie behind it, __builtin_expect).  tests/test_solve_path_isa.py reads this off the ISA; k_solve, k_solve_b and k_solve_pending run the
+// same code.
+//
+// where wave 1 leaves its results (the diagnostic build runs the path a first time into spare slots)
+struct SolveWave1Slots {
+    float *H, *Inv, *E, *Cand, *Upd;
+    int* LuOk;
+};
+// LDS index of tot's H(r, c) slot for lane l = 6 r + c (upper triangle, a (13 - a) / 2 + (b - a)); lanes >= 36 get lane 35's.  Depends
+// on the lane alone: formed in front of the barrier of solve_totals, off the chain.
+__device__ __forceinline__ int solve_h_slot(const int lane) {
+    const int l = lane < 36 ? lane : 35;
+    const int r = l / 6, c = l - 6 * r;
+    const int aa = r < c ? r : c, bb = r < c ? c : r;
+    return P_H + (aa * (13 - aa)) / 2 + (bb - aa);
+}
+// c ? a : b of two values that exist already: a select, where a conditional expression with work in its arms is compiled into a branch
+template <typename T>
+__device__ __forceinline__ T pick(const bool c, const T a, const T b) {
+    return c ? a : b;
+}
+// the two rare arms of the exponential's coefficients (no rotation: both stay 0; angle^2 >= 0.25: the general form)
+__device__ __forceinline__ void solve_exp_coeffs_rare(const double theta_sq, const bool rot, double& ca, double& cb) {
+    ca = 0.0;
+    cb = 0.0;
+    if (rot) gn::sinc_cosc(sqrt(theta_sq), ca, cb);
+}
+// Wave 1 (all 64 lanes, mode 0): H -> its inverse -> the update -> the SE(3) exponential -> the candidate pose.  h_slot: solve_h_slot(lane).
+__device__ __forceinline__ void solve_wave1(SolveShared& sh, const SolveWave1Slots& o, const int lane, const int h_slot,
+                                            const int stamp_inv, const int stamp_cand) {
+    const double* tot = sh.sst.tot;
+    const int l36 = lane < 36 ? lane : 35, l16 = lane & 15, l6 = lane < 6 ? lane : 5;
+    o.H[l36] = (float)tot[h_slot];         // (lanes 35-63: the same value into the same slot)
+    float x[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const bool ok = lu_inverse6_lanes(o.H, lane, x);     // hessian.inverse()   RPI.h:4693
+#pragma unroll
+    for (int r = 0; r < 6; ++r) asm volatile("" : "+v"(x[r]));      // (the back substitution stays in front of the six stores, not under their lane mask)
+    // lanes 6-11 own the inverse's columns; every other lane stores what it holds into a slot nobody reads (a store under a lane mask is a
+    // branch on EXEC in the path)
+    float* const own = o.Inv + (lane - 6) * 6;
+    __shared__ float nobodys_slots[36];      // written, never read (an LDS object of its own: SolveShared keeps its layout)
+    float* const nobodys = nobodys_slots + l6 * 6;
+    float* const xcol = pick(lane >= 6 && lane < 12, own, nobodys);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) xcol[r] = x[r];
+    *o.LuOk = ok ? 1 : 0;               // (wave-uniform: every lane stores the same word)
+    SOLVE_STAMP_T(stamp_inv, 64);      // inverse done
+    // update_pose = (-H^-1) * g, row min(lane, 5), summed in column order; kept aside until wave 0 has decided (its test of the loop
+    // condition still reads the previous update)
+    float upd = 0.f;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) upd += (-o.Inv[c * 6 + l6]) * (float)tot[P_G + c];
+    o.Upd[l6] = upd;
+    // CPose3D::exp(update, true) (RPI.h:4697): every lane evaluates the two scalar coefficients, lane 4*j+i (mod 16) assembles element (i,j)
+    const double ux = (double)bcast(upd, 0), uy = (double)bcast(upd, 1), uz = (double)bcast(upd, 2);
+    const double wx = (double)bcast(upd, 3), wy = (double)bcast(upd, 4), wz = (double)bcast(upd, 5);
+    // sin(a)/a and (1 - cos a)/a^2 are series in a^2: no square root on the launch's critical path for the angles a Gauss-Newton update
+    // has (a^2 < 0.25: the Maclaurin branch of gn::sinc_cosc, to which a^2 is handed directly -- it differs from sqrt(a^2)^2 by an ulp
+    // of a double, invisible behind the cast to float32 of RPI.h:4697)
+    const double theta_sq = wx * wx + wy * wy + wz * wz;
+    double ca, cb;
+    const bool rot = theta_sq >= (128 * 2.220446049250313e-16) * (128 * 2.220446049250313e-16);
+    if (__builtin_expect(rot && theta_sq < 0.25, 1)) gn::sinc_cosc_sq(theta_sq, ca, cb);
+    else solve_exp_coeffs_rare(theta_sq, rot, ca, cb);
+    {
+        // W = skew(w), W2 = W W, element (i, j), written with selects: a W[i][k] lookup with a per-lane index puts the matrix into
+        // scratch memory (it was the only scratch use of the whole library).  Off the diagonal W2_ij = w_i w_j and W_ij = -/+ w_k (k the
+        // third index); on it W2_ii = -(w_a^2) - (w_b^2), added in the order of the matrix product.  Every operand is formed first,
+        // then picked: no lane mask.
+        const int i = l16 & 3, j = l16 >> 2, kk = 3 - i - j;
+        const bool on_diag = i == j, rot_part = i < 3 && j < 3, trans_part = j == 3 && i < 3, minus = (j - i + 3) % 3 == 1;
+        const double diag = pick(on_diag, 1.0, 0.0);
+        const double wi = pick(i == 0, wx, pick(i == 1, wy, wz)), wj = pick(j == 0, wx, pick(j == 1, wy, wz));
+        const double wk = pick(kk == 0, wx, pick(kk == 1, wy, wz));
+        const double first = pick(i == 2, wy, wz), second = pick(i == 0, wy, wx);      // k ascending, k != i
+        double W2d = (0.0 - first * first) - second * second, W2o = wi * wj;
+        asm volatile("" : "+v"(W2d), "+v"(W2o));      // (as operands of the select they would go back under lane masks)
+        const double Wij = pick(on_diag, 0.0, pick(minus, -wk, wk));
+        const double W2ij = pick(on_diag, W2d, W2o);
+        double er = diag + (ca * Wij + cb * W2ij);
+        asm volatile("" : "+v"(er));
+        const double ut = pick(i == 0, ux, pick(i == 1, uy, uz));
+        const double e = pick(rot_part, pick(rot, er, diag), pick(trans_part, ut, diag));
+        o.E[l16] = (float)e;
+    }
+    // pose_estim_temp = exp(...).cast<float>() * pose_estim: whenever a step is taken the pose it starts from is the candidate of this
+    // pass (accepted: pose := cand; first pass of a level: cand == pose)
+    {
+        const int c = l16 >> 2, r = l16 & 3;
+        const float* P = sh.sst.cand;
+        o.Cand[l16] = ((o.E[0 * 4 + r] * P[c * 4 + 0] + o.E[1 * 4 + r] * P[c * 4 + 1]) + o.E[2 * 4 + r] * P[c * 4 + 2]) + o.E[3 * 4 + r] * P[c * 4 + 3];
+    }
+    SOLVE_STAMP_T(stamp_cand, 64);      // update, exponential, candidate pose done
+}
+
+// solve_waves: three waves side by side -- wave 0 the bookkeeping, wave 1 the 6x6 inverse, the update, the SE(3) exponential and the
+// candidate pose, wave 2 the rank test (rank_now; the fused launch runs it later, on one block only).  No barrier behind it.
+// Waves 1 and 2 work speculatively, in parallel with the bookkeeping of wave 0: a step is only ever computed from the H of THIS pass
+// (go implies take, see solve_bookkeeping_wave), and the damping of the rank test is known from the state before the decision: lambda
+// on the first pass of a level, lambda / 5 after an accepted step (a rejected step ends the level, so its result is simply dropped).
+// RPI.h:4682, 4693, 4718.
+// Wave 1 comes first in the text behind the barrier and is chosen by a SCALAR test, so that it falls through into its path; waves 0
+// and 2 take the branches.  `idle` is what the waves WITHOUT a role in the solve (3 and up) do meanwhile instead of parking at the
+// barrier behind it: nothing (NoIdleWork) everywhere but in k_eval_fs, whose waves warm the first gathers of the pass.  It is the last
+// arm of the chain: its code lies behind wave 1's, and waves 0 - 2 never see it.
+struct NoIdleWork {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <class IDLE = NoIdleWork>
+__device__ __forceinline__ void solve_waves(SolveShared& sh, const SolveCfg& cfg, const float lam_spec, const bool rank_now, const int h_slot,
+                                            const IDLE& idle = IDLE()) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (__builtin_expect(cfg.mode == 0 && wave == 1, 1)) {
+#ifdef RGBD360_SOLVE_TWICE
+        // diagnostic: the same code a first time into spare slots (stamps 7 and 2), then for real (5 and 6) -- the cold and the warm price
+        const SolveWave1Slots dry = {sh.dry, sh.dry + 36, sh.dry + 72, sh.dry + 88, sh.dry + 104, &sh.dryLuOk};
+        solve_wave1(sh, dry, lane, h_slot, 7, 2);
+#endif
+        const SolveWave1Slots out = {sh.shH, sh.shInv, sh.shE, sh.shCand, sh.shUpd, &sh.shLuOk};
+        solve_wave1(sh, out, lane, h_slot, 5, 6);
+    } else if (wave == 0) {
+        solve_bookkeeping_wave(sh, cfg, lane);
+    } else if (cfg.mode == 0 && wave == 2 && rank_now) {
         solve_rank_wave(sh, lam_spec);
         SOLVE_STAMP_T(7, 128);     // rank done
+    } else if (wave >= 3) {
+        idle();
     }
-    if (cfg.mode == 0 && wave == 1) {
-        float hval = 0.f;
-        if (lane < 36) {
-            const int r = lane / 6, c = lane - 6 * r;
-            const int aa = r < c ? r : c, bb = r < c ? c : r;
-            hval = (float)tot[P_H + (aa * (13 - aa)) / 2 + (bb - aa)];
-        }
-        {
-            if (lane < 36) sh.shH[lane] = hval;
-            float x[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            const bool ok = lu_inverse6_lanes(sh.shH, lane, x);     // hessian.inverse()   RPI.h:4693
-            if (lane >= 6 && lane < 12) {
-#pragma unroll
-                for (int r = 0; r < 6; ++r) sh.shInv[(lane - 6) * 6 + r] = x[r];
-            }
-            if (lane == 0) sh.shLuOk = ok ? 1 : 0;
-            SOLVE_STAMP_T(5, 64);      // inverse done
-            // update_pose = (-H^-1) * g, row `lane`, summed in column order; kept aside until wave 0 has decided (its test
-            // of the loop condition still reads the previous update)
-            float upd = 0.f;
-            if (lane < 6) {
-#pragma unroll
-                for (int c = 0; c < 6; ++c) upd += (-sh.shInv[c * 6 + lane]) * (float)tot[P_G + c];
-                sh.shUpd[lane] = upd;
-            }
-            // CPose3D::exp(update, true) (RPI.h:4697): every lane evaluates the two scalar coefficients, lane 4*j+i
-            // assembles element (i,j) of the 4x4
-            const double ux = (double)bcast(upd, 0), uy = (double)bcast(upd, 1), uz = (double)bcast(upd, 2);
-            const double wx = (double)bcast(upd, 3), wy = (double)bcast(upd, 4), wz = (double)bcast(upd, 5);
-            // sin(a)/a and (1 - cos a)/a^2 are series in a^2: no square root on the launch's critical path for the angles a Gauss-Newton
-            // update has (round 5; a^2 < 0.25: the Maclaurin branch of gn::sinc_cosc, to which a^2 is handed directly -- it differs from
-            // sqrt(a^2)^2 by an ulp of a double, invisible behind the cast to float32 of RPI.h:4697)
-            const double theta_sq = wx * wx + wy * wy + wz * wz;
-            double ca = 0.0, cb = 0.0;
-            const bool rot = theta_sq >= (128 * 2.220446049250313e-16) * (128 * 2.220446049250313e-16);
-            if (rot) {
-                if (theta_sq < 0.25) gn::sinc_cosc_sq(theta_sq, ca, cb);
-                else gn::sinc_cosc(sqrt(theta_sq), ca, cb);
-            }
-            if (lane < 16) {
-                const int i = lane & 3, j = lane >> 2;
-                double e = (i == j) ? 1.0 : 0.0;
-                if (i < 3 && j < 3) {
-                    if (rot) {
-                        // W = skew(w), W2 = W W, element (i, j), written with selects: a W[i][k] lookup with a per-lane index puts
-                        // the matrix into scratch memory (the only scratch use of the whole library).  Off the diagonal
-                        // W2_ij = w_i w_j and W_ij = -/+ w_k (k the third index); on it W2_ii = -(w_a^2) - (w_b^2), added in the
-                        // order of the matrix product.
-                        const double wi = i == 0 ? wx : (i == 1 ? wy : wz), wj = j == 0 ? wx : (j == 1 ? wy : wz);
-                        const int kk = 3 - i - j;
-                        const double wk = kk == 0 ? wx : (kk == 1 ? wy : wz);
-                        double Wij, W2ij;
-                        if (i == j) {
-                            Wij = 0.0;
-                            const double first = i == 2 ? wy : wz, second = i == 0 ? wy : wx;      // k ascending, k != i
-                            W2ij = (0.0 - first * first) - second * second;
-                        } else {
-                            Wij = ((j - i + 3) % 3 == 1) ? -wk : wk;
-                            W2ij = wi * wj;
-                        }
-                        e += ca * Wij + cb * W2ij;
-                    }
-                } else if (j == 3 && i < 3) {
-                    e = i == 0 ? ux : (i == 1 ? uy : uz);
-                }
-                sh.shE[lane] = (float)e;
-            }
-            // pose_estim_temp = exp(...).cast<float>() * pose_estim: whenever a step is taken the pose it starts from is the
-            // candidate of this pass (accepted: pose := cand; first pass of a level: cand == pose)
-            if (lane < 16) {
-                const int c = lane >> 2, r = lane & 3;
-                const float* P = sh.sst.cand;
-                sh.shCand[lane] = ((sh.shE[0 * 4 + r] * P[c * 4 + 0] + sh.shE[1 * 4 + r] * P[c * 4 + 1]) + sh.shE[2 * 4 + r] * P[c * 4 + 2]) +
-                               sh.shE[3 * 4 + r] * P[c * 4 + 3];
-            }
-            SOLVE_STAMP_T(6, 64);      // update, exponential, candidate pose done
-        }
-    }
-    // ---- bookkeeping on wave 0: lane 0 takes the scalar decisions, lanes 0-41 move the 36 + 6 matrix entries ----
-    if (wave == 0) {
-        // normal equations at the evaluated pose (float like the reference's `hessian` / `gradient`): lane l < 36 owns
-        // H(r,c), r = l/6, c = l%6 (upper-triangle slot a*(13-a)/2 + (b-a)); lanes 36-41 own g
-        float hval = 0.f;
-        if (lane < 36) {
-            const int r = lane / 6, c = lane - 6 * r;
-            const int aa = r < c ? r : c, bb = r < c ? c : r;
-            hval = (float)tot[P_H + (aa * (13 - aa)) / 2 + (bb - aa)];
-        } else if (lane < 42) {
-            hval = (float)tot[P_G + lane - 36];
-        }
-        int take = 0, go = 0;
-        if (lane == 0) {
-            st->n_evals += 1;
-            const double err2 = tot[P_E2P] + tot[P_E2D];
-            const double nvalid = tot[P_NP] + tot[P_ND];
-            const double new_error = cfg.occ == 0 ? sqrt(err2 / nvalid)      // RPI.h:2738
-                                                  : sqrt(tot[P_E2P] / tot[P_NP]) + sqrt(tot[P_E2D] / tot[P_ND]);
-            st->new_error = new_error;
-            if (cfg.mode == 1) {
-                take = 1;
-            } else {
-                bool stop = false;
-                if (st->first) {
-                    st->first = 0;
-                    if (nvalid == 0.0 || new_error != new_error) {      // no residuals (occlusion modes: 0/0 of an unused modality)
-                        st->status = 2;
-                        st->done = 1;
-                        stop = true;
-                    } else {
-                        st->error = new_error;           // RPI.h:4599
-                        st->diff_error = new_error;      // RPI.h:4605
-                        take = 1;                        // cand == pose
-                    }
-                } else {
-                    const double diff = st->error - new_error;   // RPI.h:4713
-                    st->diff_error = diff;
-                    if (cfg.forced || diff > cfg.tol_residual) {  // RPI.h:4715-4722
-                        st->lambda = st->lambda / 5.0;
-                        st->error = new_error;
-                        st->it += 1;
-                        st->iters[cfg.level & 7] = st->it;
-                        take = 2;                        // 2: also promote cand -> pose
-                    }
-                }
-                if (take) {
-                    st->acc_e2p = tot[P_E2P];
-                    st->acc_e2d = tot[P_E2D];
-                    st->acc_np = (long long)tot[P_NP];
-                    st->acc_nd = (long long)tot[P_ND];
-                    st->acc_nvis = (long long)tot[P_NVIS];
-                }
-                if (!stop) {
-                    // while(it < maxIters && update_pose.norm() > tol_update && diff_error > tol_residual)   RPI.h:4611
-                    float un = 0.f;
-                    for (int i = 0; i < 6; ++i) un += st->update[i] * st->update[i];
-                    un = sqrtf(un);
-                    go = cfg.forced || (st->it < cfg.max_iters && (double)un > cfg.tol_update && st->diff_error > cfg.tol_residual);
-                    if (!go) st->done = 1;
-                }
-                if (go) {
-                    st->used_nvis = st->acc_nvis;
-                    st->used_npix = cfg.n_pixels;
-                }
-            }
-            sh.shGo = go;
-        }
-        take = __builtin_amdgcn_readfirstlane(take);
-        go = __builtin_amdgcn_readfirstlane(go);
-        if (take == 2 && lane < 16) st->pose[lane] = st->cand[lane];
-        if (take) {
-            if (lane < 36) st->H[lane] = hval;
-            else if (lane < 42) st->g[lane - 36] = hval;
-        }
-        if (go) {
-            // a step is only ever computed right after its pose was taken, so hval is H / g at `pose`;
-            // record them as "used" (what the reference's `hessian` / `SSO` members hold afterwards)
-            if (lane < 36) {
-                st->Hused[lane] = hval;
-            } else if (lane < 42) {
-                st->gused[lane - 36] = hval;
-            }
-        }
-    }
+#ifndef RGBD360_SOLVE_TWICE
     SOLVE_STAMP(2);
+#endif
 }
 
 // solve_finish (behind a barrier that follows solve_waves): commits the step or the ILL-POSED status, hands a finished level over to
@@ -1379,17 +1459,30 @@ __device__ __forceinline__ void solve_finish(SolveShared& sh, const SolveCfg& cf
 }
 
 __device__ __forceinline__ void solve_staged(SolveShared& sh, const SolveCfg& cfg) {
+    int h_slot = solve_h_slot(threadIdx.x & 63);
+    asm volatile("" : "+v"(h_slot));      // (formed here, not sunk behind the barrier to its use)
     const float lam_spec = solve_totals(sh);
-    solve_waves(sh, cfg, lam_spec, true);
+    solve_waves(sh, cfg, lam_spec, true, h_slot);
     __syncthreads();            // bookkeeping (wave 0), inverse (wave 1) and rank (wave 2) are all done
     solve_finish(sh, cfg);
+}
+// The report to the host at the end of a schedule's last launch, where cfg.host_state is set (by every thread of the block): the staged
+// state to the pinned copy, then the tag the host spins on (csrc/host_wait.h).  One wave writes the state's ~230 words and runs the one
+// system-scope fence: sixteen waves each asking for a write-back cost the launch 3-4 us.  (cfg by value: through a reference to the
+// kernel argument its three fields were fetched earlier in the launch, and k_solve_pending was not the machine code it had been.)
+__device__ __forceinline__ void publish_state_to_host(const SolveShared& sh, const SolveCfg cfg) {
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        for (int w = tid; w < kStateWords; w += 64) reinterpret_cast<int*>(cfg.host_state)[w] = reinterpret_cast<const int*>(&sh.sst)[w];
+        __threadfence_system();
+    }
+    __syncthreads();
+    if (tid == 0) __hip_atomic_store(cfg.host_tag, cfg.host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 __device__ __forceinline__ void solve_block(GNState* st_g, const double* __restrict__ partials, const int nb, const SolveCfg& cfg) {
     // The state is staged through LDS: one coalesced read while the partials are being reduced, one coalesced
     // write-back at the end; the single-lane bookkeeping then never waits on global memory.
     __shared__ SolveShared sh;
-    constexpr int kStateWords = sizeof(GNState) / 4;
-    static_assert(sizeof(GNState) % 4 == 0 && kStateWords <= kSolveThreads, "GNState staging");
     const int tid = threadIdx.x;
 #ifdef RGBD360_SOLVE_STAMPS
     if (tid == 0) sh.stamp0 = __builtin_amdgcn_s_memrealtime();
@@ -1414,14 +1507,7 @@ __device__ __forceinline__ void solve_block(GNState* st_g, const double* __restr
     __syncthreads();
     SOLVE_STAMP(0);
     if (cfg.mode == 0 && (sh.sst.done || sh.sst.level_active != cfg.level)) {            // uniform: finished / other level
-        if (cfg.host_state) {                               // the schedule's last launch reports even when it has nothing to do
-            if (tid < 64) {
-                for (int w = tid; w < kStateWords; w += 64) reinterpret_cast<int*>(cfg.host_state)[w] = reinterpret_cast<const int*>(&sh.sst)[w];
-                __threadfence_system();
-            }
-            __syncthreads();
-            if (tid == 0) __hip_atomic_store(cfg.host_tag, cfg.host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        if (cfg.host_state) publish_state_to_host(sh, cfg);      // the schedule's last launch reports even when it has nothing to do
         return;
     }
     solve_staged(sh, cfg);
@@ -1433,16 +1519,7 @@ __device__ __forceinline__ void solve_block(GNState* st_g, const double* __restr
     __syncthreads();
 #endif
     if (tid < kStateWords) reinterpret_cast<int*>(st_g)[tid] = reinterpret_cast<const int*>(&sh.sst)[tid];
-    if (cfg.host_state) {                                   // uniform
-        // (one wave writes the state's ~230 words and runs the one system-scope fence: sixteen waves each asking for a write-back cost
-        // the launch 3-4 us)
-        if (tid < 64) {
-            for (int w = tid; w < kStateWords; w += 64) reinterpret_cast<int*>(cfg.host_state)[w] = reinterpret_cast<const int*>(&sh.sst)[w];
-            __threadfence_system();
-        }
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(cfg.host_tag, cfg.host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (cfg.host_state) publish_state_to_host(sh, cfg);      // uniform
 }
 __global__ __launch_bounds__(kSolveThreads) void k_solve(GNState* st_g, const double* __restrict__ partials, int nb,
                                                           SolveCfg cfg) {
@@ -1482,7 +1559,6 @@ constexpr int kMaxPendingRows = kPendingRows;     // the fused schedule needs ev
 // with the bound they request one batch of 32 rows (8 KB per workgroup) instead of all 256 (64 KB through one CU's 64 B / clock L1 fill
 // path: 0.5 us of the prologue of a launch that has 1 us of pixel work).  Rows beyond pend_nb add nothing either way: same sums.
 __device__ __forceinline__ int stage_pending(SolveShared& sh, const GNState* __restrict__ st_in, const double* __restrict__ partials, const int rows_hint) {
-    constexpr int kStateWords = sizeof(GNState) / 4;
     constexpr int Q = kSolveThreads / kNumPartials;
     constexpr int J = kPendingRows / Q;
     static_assert(J * Q == kPendingRows && J <= 16, "whole batches");
@@ -1573,307 +1649,6 @@ __device__ __forceinline__ int stage_pending(SolveShared& sh, const GNState* __r
     return nb;
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// The fused launches' form of wave 1's half of solve_waves (k_eval_fs, k_occ_build_fs, k_solve_pending): the same float operations
-// in the same order on the same lanes into the same LDS slots -- only the SHAPE of the machine code differs.  A fused launch walks
-// this code once, one wave per CU, with fifteen waves parked at the barrier and the instruction cache freshly invalidated: what it
-// pays for is taken branches into lines not fetched yet, not arithmetic.  So the common case (the diagonal entry is every step's
-// pivot, a rotation with angle^2 < 0.25) is FALL-THROUGH code from the barrier behind solve_totals to the store of shCand: no
-// EXEC-divergent region (lane predicates become selects; stores go to a clamped slot, where the lanes that share it hold the same
-// value) and no taken branch (the swap arms and the two rare arms of the exponential lie behind it, __builtin_expect).
-// k_solve / k_solve_b keep solve_waves as it stands: the fused-versus-two-launch tests compare the two forms on the device, bit for bit.
-// ---------------------------------------------------------------------------------------------------------
-// Wave 0's bookkeeping for solve_waves_ft: the statements of solve_waves' own wave-0 block (lane 0 takes the scalar decisions, lanes 0-41
-// move the 36 + 6 matrix entries), which stays where it is until solve_waves is retired -- keep the two in step.
-__device__ __forceinline__ void solve_bookkeeping_wave(SolveShared& sh, const SolveCfg& cfg, const int lane) {
-    GNState* st = &sh.sst;
-    const double* tot = sh.sst.tot;
-    // normal equations at the evaluated pose (float like the reference's `hessian` / `gradient`): lane l < 36 owns
-    // H(r,c), r = l/6, c = l%6 (upper-triangle slot a*(13-a)/2 + (b-a)); lanes 36-41 own g
-    float hval = 0.f;
-    if (lane < 36) {
-        const int r = lane / 6, c = lane - 6 * r;
-        const int aa = r < c ? r : c, bb = r < c ? c : r;
-        hval = (float)tot[P_H + (aa * (13 - aa)) / 2 + (bb - aa)];
-    } else if (lane < 42) {
-        hval = (float)tot[P_G + lane - 36];
-    }
-    int take = 0, go = 0;
-    if (lane == 0) {
-        st->n_evals += 1;
-        const double err2 = tot[P_E2P] + tot[P_E2D];
-        const double nvalid = tot[P_NP] + tot[P_ND];
-        const double new_error = cfg.occ == 0 ? sqrt(err2 / nvalid)      // RPI.h:2738
-                                              : sqrt(tot[P_E2P] / tot[P_NP]) + sqrt(tot[P_E2D] / tot[P_ND]);
-        st->new_error = new_error;
-        if (cfg.mode == 1) {
-            take = 1;
-        } else {
-            bool stop = false;
-            if (st->first) {
-                st->first = 0;
-                if (nvalid == 0.0 || new_error != new_error) {      // no residuals (occlusion modes: 0/0 of an unused modality)
-                    st->status = 2;
-                    st->done = 1;
-                    stop = true;
-                } else {
-                    st->error = new_error;           // RPI.h:4599
-                    st->diff_error = new_error;      // RPI.h:4605
-                    take = 1;                        // cand == pose
-                }
-            } else {
-                const double diff = st->error - new_error;   // RPI.h:4713
-                st->diff_error = diff;
-                if (cfg.forced || diff > cfg.tol_residual) {  // RPI.h:4715-4722
-                    st->lambda = st->lambda / 5.0;
-                    st->error = new_error;
-                    st->it += 1;
-                    st->iters[cfg.level & 7] = st->it;
-                    take = 2;                        // 2: also promote cand -> pose
-                }
-            }
-            if (take) {
-                st->acc_e2p = tot[P_E2P];
-                st->acc_e2d = tot[P_E2D];
-                st->acc_np = (long long)tot[P_NP];
-                st->acc_nd = (long long)tot[P_ND];
-                st->acc_nvis = (long long)tot[P_NVIS];
-            }
-            if (!stop) {
-                // while(it < maxIters && update_pose.norm() > tol_update && diff_error > tol_residual)   RPI.h:4611
-                float un = 0.f;
-                for (int i = 0; i < 6; ++i) un += st->update[i] * st->update[i];
-                un = sqrtf(un);
-                go = cfg.forced || (st->it < cfg.max_iters && (double)un > cfg.tol_update && st->diff_error > cfg.tol_residual);
-                if (!go) st->done = 1;
-            }
-            if (go) {
-                st->used_nvis = st->acc_nvis;
-                st->used_npix = cfg.n_pixels;
-            }
-        }
-        sh.shGo = go;
-    }
-    take = __builtin_amdgcn_readfirstlane(take);
-    go = __builtin_amdgcn_readfirstlane(go);
-    if (take == 2 && lane < 16) st->pose[lane] = st->cand[lane];
-    if (take) {
-        if (lane < 36) st->H[lane] = hval;
-        else if (lane < 42) st->g[lane - 36] = hval;
-    }
-    if (go) {
-        // a step is only ever computed right after its pose was taken, so hval is H / g at `pose`;
-        // record them as "used" (what the reference's `hessian` / `SSO` members hold afterwards)
-        if (lane < 36) {
-            st->Hused[lane] = hval;
-        } else if (lane < 42) {
-            st->gused[lane - 36] = hval;
-        }
-    }
-}
-
-// where wave 1 leaves its results (the diagnostic build runs the path a first time into spare slots)
-struct SolveWave1Slots {
-    float *H, *Inv, *E, *Cand, *Upd;
-    int* LuOk;
-};
-// LDS index of tot's H(r, c) slot for lane l = 6 r + c (upper triangle, a (13 - a) / 2 + (b - a)); lanes >= 36 get lane 35's.  Depends
-// on the lane alone: formed in front of the barrier of solve_totals, off the chain.
-__device__ __forceinline__ int solve_h_slot(const int lane) {
-    const int l = lane < 36 ? lane : 35;
-    const int r = l / 6, c = l - 6 * r;
-    const int aa = r < c ? r : c, bb = r < c ? c : r;
-    return P_H + (aa * (13 - aa)) / 2 + (bb - aa);
-}
-// lu_inverse6_lanes without EXEC-divergent regions and without a branch per step.  The column comes from one read at a clamped address
-// (lanes >= 6 read column 5 and drop it), the identity from lane predicates, the elimination's lane > k is a select.  The elimination
-// runs first WITHOUT row swaps and only notes whether some step's pivot was not its diagonal entry (the scalar search stays: same pivot
-// as lu_inverse6_lanes); if so -- normal equations: rarely -- it is done again from the matrix with the swap arms, behind the path.
-// Where no step swaps the two forms are the same operations, so the result is lu_inverse6_lanes's bit for bit either way.
-__device__ __forceinline__ void lu_load6_ft(const float* M, const int lane, float a[6]) {
-    const bool is_m = lane < 6;
-    const int col = is_m ? lane : 5;
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-        const float m = M[col * 6 + r];
-        const float id = (lane - 6) == r ? 1.f : 0.f;
-        a[r] = is_m ? m : id;
-    }
-}
-// returns whether every pivot was where the elimination took it from (always, with SWAPS)
-template <bool SWAPS>
-__device__ __forceinline__ bool lu_eliminate6_ft(float a[6], float rk[6], const int lane, bool& ok) {
-    bool in_place = true;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        float ck[6];
-#pragma unroll
-        for (int r = k; r < 6; ++r) ck[r] = bcast(a[r], k);
-        int piv = k;
-        unsigned best = __float_as_uint(ck[k]) & 0x7fffffffu;
-#pragma unroll
-        for (int r = k + 1; r < 6; ++r) {
-            const unsigned v = __float_as_uint(ck[r]) & 0x7fffffffu;
-            if (v > best) {
-                best = v;
-                piv = r;
-            }
-        }
-        ok = best == 0u ? false : ok;
-        if (SWAPS) {
-            const int pv = __builtin_amdgcn_readfirstlane(piv);
-            if (pv != k) {
-#pragma unroll
-                for (int r = k + 1; r < 6; ++r)
-                    if (pv == r) {
-                        asm volatile("v_swap_b32 %0, %1" : "+v"(a[k]), "+v"(a[r]));
-                        const float t = ck[k]; ck[k] = ck[r]; ck[r] = t;
-                    }
-            }
-        } else {
-            in_place = piv != k ? false : in_place;
-        }
-        rk[k] = rcp_rn(ck[k]);
-        const bool below = lane > k;
-#pragma unroll
-        for (int r = k + 1; r < 6; ++r) {
-            const float l = ck[r] * rk[k];
-            const float t = a[r] - l * a[k];
-            a[r] = below ? t : a[r];
-        }
-    }
-    return in_place;
-}
-__device__ __forceinline__ bool lu_inverse6_lanes_ft(const float* M /*LDS, column-major*/, int lane, float x[6]) {
-    float a[6], rk[6];
-    bool ok = true;
-    lu_load6_ft(M, lane, a);
-    if (__builtin_expect(!lu_eliminate6_ft<false>(a, rk, lane, ok), 0)) {
-        ok = true;
-        lu_load6_ft(M, lane, a);
-        lu_eliminate6_ft<true>(a, rk, lane, ok);
-    }
-#pragma unroll
-    for (int r = 5; r >= 0; --r) {
-        float sacc = a[r];
-#pragma unroll
-        for (int c = r + 1; c < 6; ++c) sacc -= bcast(a[r], c) * x[c];
-        x[r] = sacc * rk[r];
-    }
-    return ok;
-}
-// c ? a : b of two values that exist already: a select, where a conditional expression with work in its arms is compiled into a branch
-template <typename T>
-__device__ __forceinline__ T pick(const bool c, const T a, const T b) {
-    return c ? a : b;
-}
-// the two rare arms of the exponential's coefficients (no rotation: both stay 0; angle^2 >= 0.25: the general form)
-__device__ __forceinline__ void solve_exp_coeffs_rare(const double theta_sq, const bool rot, double& ca, double& cb) {
-    ca = 0.0;
-    cb = 0.0;
-    if (rot) gn::sinc_cosc(sqrt(theta_sq), ca, cb);
-}
-// Wave 1 (all 64 lanes, mode 0): H -> its inverse -> the update -> the SE(3) exponential -> the candidate pose.  h_slot: solve_h_slot(lane).
-__device__ __forceinline__ void solve_wave1_ft(SolveShared& sh, const SolveWave1Slots& o, const int lane, const int h_slot,
-                                               const int stamp_inv, const int stamp_cand) {
-    const double* tot = sh.sst.tot;
-    const int l36 = lane < 36 ? lane : 35, l16 = lane & 15, l6 = lane < 6 ? lane : 5;
-    o.H[l36] = (float)tot[h_slot];         // (lanes 35-63: the same value into the same slot)
-    float x[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const bool ok = lu_inverse6_lanes_ft(o.H, lane, x);     // hessian.inverse()   RPI.h:4693
-#pragma unroll
-    for (int r = 0; r < 6; ++r) asm volatile("" : "+v"(x[r]));      // (the back substitution stays in front of the six stores, not under their lane mask)
-    // lanes 6-11 own the inverse's columns; every other lane stores what it holds into a slot nobody reads (a store under a lane mask is a
-    // branch on EXEC in the path)
-    float* const own = o.Inv + (lane - 6) * 6;
-    __shared__ float nobodys_slots[36];      // written, never read (an LDS object of its own: SolveShared keeps its layout)
-    float* const nobodys = nobodys_slots + l6 * 6;
-    float* const xcol = pick(lane >= 6 && lane < 12, own, nobodys);
-#pragma unroll
-    for (int r = 0; r < 6; ++r) xcol[r] = x[r];
-    *o.LuOk = ok ? 1 : 0;               // (wave-uniform: every lane stores the same word)
-    SOLVE_STAMP_T(stamp_inv, 64);      // inverse done
-    // update_pose = (-H^-1) * g, row min(lane, 5), summed in column order; kept aside until wave 0 has decided
-    float upd = 0.f;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) upd += (-o.Inv[c * 6 + l6]) * (float)tot[P_G + c];
-    o.Upd[l6] = upd;
-    // CPose3D::exp(update, true) (RPI.h:4697): every lane evaluates the two scalar coefficients, lane 4*j+i (mod 16) assembles element (i,j)
-    const double ux = (double)bcast(upd, 0), uy = (double)bcast(upd, 1), uz = (double)bcast(upd, 2);
-    const double wx = (double)bcast(upd, 3), wy = (double)bcast(upd, 4), wz = (double)bcast(upd, 5);
-    const double theta_sq = wx * wx + wy * wy + wz * wz;      // (the series in angle^2: see solve_waves)
-    double ca, cb;
-    const bool rot = theta_sq >= (128 * 2.220446049250313e-16) * (128 * 2.220446049250313e-16);
-    if (__builtin_expect(rot && theta_sq < 0.25, 1)) gn::sinc_cosc_sq(theta_sq, ca, cb);
-    else solve_exp_coeffs_rare(theta_sq, rot, ca, cb);
-    {
-        // W = skew(w), W2 = W W, element (i, j) (see solve_waves) -- every operand formed first, then picked: no lane mask
-        const int i = l16 & 3, j = l16 >> 2, kk = 3 - i - j;
-        const bool on_diag = i == j, rot_part = i < 3 && j < 3, trans_part = j == 3 && i < 3, minus = (j - i + 3) % 3 == 1;
-        const double diag = pick(on_diag, 1.0, 0.0);
-        const double wi = pick(i == 0, wx, pick(i == 1, wy, wz)), wj = pick(j == 0, wx, pick(j == 1, wy, wz));
-        const double wk = pick(kk == 0, wx, pick(kk == 1, wy, wz));
-        const double first = pick(i == 2, wy, wz), second = pick(i == 0, wy, wx);      // k ascending, k != i
-        double W2d = (0.0 - first * first) - second * second, W2o = wi * wj;
-        asm volatile("" : "+v"(W2d), "+v"(W2o));      // (as operands of the select they would go back under lane masks)
-        const double Wij = pick(on_diag, 0.0, pick(minus, -wk, wk));
-        const double W2ij = pick(on_diag, W2d, W2o);
-        double er = diag + (ca * Wij + cb * W2ij);
-        asm volatile("" : "+v"(er));
-        const double ut = pick(i == 0, ux, pick(i == 1, uy, uz));
-        const double e = pick(rot_part, pick(rot, er, diag), pick(trans_part, ut, diag));
-        o.E[l16] = (float)e;
-    }
-    // pose_estim_temp = exp(...).cast<float>() * pose_estim (see solve_waves)
-    {
-        const int c = l16 >> 2, r = l16 & 3;
-        const float* P = sh.sst.cand;
-        o.Cand[l16] = ((o.E[0 * 4 + r] * P[c * 4 + 0] + o.E[1 * 4 + r] * P[c * 4 + 1]) + o.E[2 * 4 + r] * P[c * 4 + 2]) + o.E[3 * 4 + r] * P[c * 4 + 3];
-    }
-    SOLVE_STAMP_T(stamp_cand, 64);      // update, exponential, candidate pose done
-}
-// solve_waves for the fused launches: wave 1 first in the text behind the barrier and chosen by a SCALAR test, so that it falls through
-// into its path; waves 0 and 2 take the branches.  `idle` is what the waves WITHOUT a role in the solve (3 and up) do meanwhile instead
-// of parking at the barrier behind it: nothing (NoIdleWork) everywhere but in k_eval_fs, whose waves warm the first gathers of the pass.
-// It is the last arm of the chain: its code lies behind wave 1's, and waves 0 - 2 never see it.
-struct NoIdleWork {
-    __device__ __forceinline__ void operator()() const {}
-};
-template <class IDLE = NoIdleWork>
-__device__ __forceinline__ void solve_waves_ft(SolveShared& sh, const SolveCfg& cfg, const float lam_spec, const bool rank_now, const int h_slot,
-                                               const IDLE& idle = IDLE()) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (__builtin_expect(cfg.mode == 0 && wave == 1, 1)) {
-#ifdef RGBD360_SOLVE_TWICE
-        // diagnostic: the same code a first time into spare slots (stamps 7 and 2), then for real (5 and 6) -- the cold and the warm price
-        const SolveWave1Slots dry = {sh.dry, sh.dry + 36, sh.dry + 72, sh.dry + 88, sh.dry + 104, &sh.dryLuOk};
-        solve_wave1_ft(sh, dry, lane, h_slot, 7, 2);
-#endif
-        const SolveWave1Slots out = {sh.shH, sh.shInv, sh.shE, sh.shCand, sh.shUpd, &sh.shLuOk};
-        solve_wave1_ft(sh, out, lane, h_slot, 5, 6);
-    } else if (wave == 0) {
-        solve_bookkeeping_wave(sh, cfg, lane);
-    } else if (cfg.mode == 0 && wave == 2 && rank_now) {
-        solve_rank_wave(sh, lam_spec);
-        SOLVE_STAMP_T(7, 128);     // rank done
-    } else if (wave >= 3) {
-        idle();
-    }
-#ifndef RGBD360_SOLVE_TWICE
-    SOLVE_STAMP(2);
-#endif
-}
-
-// the same with wave 1 on the fall-through form of its path (solve_waves_ft): the fused schedule's tail launch
-__device__ __forceinline__ void solve_staged_ft(SolveShared& sh, const SolveCfg& cfg) {
-    int h_slot = solve_h_slot(threadIdx.x & 63);
-    asm volatile("" : "+v"(h_slot));      // (formed here, not sunk behind the barrier to its use)
-    const float lam_spec = solve_totals(sh);
-    solve_waves_ft(sh, cfg, lam_spec, true, h_slot);
-    __syncthreads();
-    solve_finish(sh, cfg);
-}
 
 // wave-uniform pose out of LDS into scalar registers (the pixel loop reads it as SGPR operands, like the scalar loads of k_eval)
 __device__ __forceinline__ float uniform_f(float v) {
@@ -1908,7 +1683,7 @@ __device__ __forceinline__ FsDecision fs_solve_decide(SolveShared& sh, const int
         int h_slot = solve_h_slot(threadIdx.x & 63);
         asm volatile("" : "+v"(h_slot));      // (formed here, not sunk behind the barrier to its use)
         lam_spec = solve_totals(sh);
-        solve_waves_ft(sh, c, lam_spec, /*rank_now=*/false, h_slot, idle);
+        solve_waves(sh, c, lam_spec, /*rank_now=*/false, h_slot, idle);
         __syncthreads();
     }
     // What solve_finish would now do to the state -- commit the step (on the inverse's word: the rank test, the longest of the three
@@ -1931,7 +1706,6 @@ __device__ __forceinline__ FsDecision fs_solve_decide(SolveShared& sh, const int
 // one wave (all 64 lanes): the rank verdict on the step just committed, then the new state.  ILL-POSED (RPI.h:4684-4689): status 1,
 // level done, candidate and update as they were -- and no pending pass: the rows this launch writes are never read.
 __device__ __forceinline__ void fs_write_state(SolveShared& sh, const FsDecision& d, const int nb, const int n_level_px, GNState* st_out) {
-    constexpr int kStateWords = sizeof(GNState) / 4;
     const bool commit = d.commit, ill = d.ill, handover = d.handover, run = d.run;
     const int level_now = d.level_now;
     const int lane = threadIdx.x & 63;
@@ -1980,7 +1754,7 @@ __device__ __forceinline__ bool fs_solve_and_publish(SolveShared& sh, const int 
     return d.run;
 }
 
-// WARM-UP of the pass's first gathers, by the waves the solve leaves idle (k_eval_fs's `idle` of solve_waves_ft).  The gathers of a
+// WARM-UP of the pass's first gathers, by the waves the solve leaves idle (k_eval_fs's `idle` of solve_waves).  The gathers of a
 // span's first steps cannot be issued before the new pose exists, and only one further warp stage stands in front of the first
 // consume_stage: a far-memory round trip, exposed in every launch (0.7 us from the first warp stage to the end of the first
 // consume_stage on wave 0, 2.2 us on the SIMD's youngest wave: profiles/fused_warm_ab.txt).  The pose the pending pass ran at
@@ -2063,7 +1837,6 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_fs(const GNState* __restr
     const unsigned long long es0 = 0;
 #endif
     __shared__ SolveShared sh;
-    constexpr int kStateWords = sizeof(GNState) / 4;
 #ifdef RGBD360_SOLVE_STAMPS
     if (threadIdx.x == 0) sh.stamp0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -2111,28 +1884,18 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_fs(const GNState* __restr
 __global__ __launch_bounds__(kSolveThreads) void k_solve_pending(GNState* st_g, const double* __restrict__ partials, int pend_rows_hint,
                                                                   SolveCfg cfg) {
     __shared__ SolveShared sh;
-    constexpr int kStateWords = sizeof(GNState) / 4;
     const int tid = threadIdx.x;
     const int pend = stage_pending(sh, st_g, partials, pend_rows_hint);
     if (pend > 0) {
         SolveCfg c = cfg;
         c.level = sh.sst.level_active;
         c.n_pixels = sh.sst.pend_npix;
-        solve_staged_ft(sh, c);
+        solve_staged(sh, c);
         if (tid == 0) sh.sst.pend_nb = 0;
         __syncthreads();
     }
     if (tid < kStateWords) reinterpret_cast<int*>(st_g)[tid] = reinterpret_cast<const int*>(&sh.sst)[tid];
-    if (cfg.host_state) {                                   // uniform
-        // (one wave writes the state's ~230 words and runs the one system-scope fence: sixteen waves each asking for a write-back cost
-        // the launch 3-4 us)
-        if (tid < 64) {
-            for (int w = tid; w < kStateWords; w += 64) reinterpret_cast<int*>(cfg.host_state)[w] = reinterpret_cast<const int*>(&sh.sst)[w];
-            __threadfence_system();
-        }
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(cfg.host_tag, cfg.host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (cfg.host_state) publish_state_to_host(sh, cfg);      // uniform
 }
 
 // Standalone GN step for tests: one thread.

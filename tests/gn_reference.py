@@ -1,5 +1,6 @@
 """CPU references for the serial Gauss-Newton step of the spherical path (RPI.h:4599-4722; gn_math.h, photo_icp_kernels.h
-qr_rank6_lanes / lu_inverse6_lanes / solve_waves / solve_finish).  No GPU needed.
+qr_rank6_lanes / lu_inverse6_lanes / solve_waves / solve_finish: one form, run by k_solve / k_solve_b and by the fused launches alike;
+the bits of the form k_solve ran before it are recorded in tests/golden/solve_bits.json, cases in tests/solve_cases.py).  No GPU needed.
 
 - rank6_f32: (H + lambda diag H).rank() restated operation for operation in float32 (batched numpy, IEEE per element, no
   contraction), with the Householder quotients as divisions ("div": gn::rank6, the oracle, Eigen) or as products with a correctly
@@ -190,7 +191,7 @@ def inverse6_f32(H, quotient: str = "div", track: bool = False):
 
 
 def update_f32(H, g, quotient: str = "rcp"):
-    """update = (-H^-1) g, row r summed in column order from 0 (RPI.h:4693; solve_waves wave 1 / gn::step)."""
+    """update = (-H^-1) g, row r summed in column order from 0 (RPI.h:4693; solve_wave1 / gn::step)."""
     inv, ok = inverse6_f32(H, quotient)
     if not ok:
         return None
@@ -345,7 +346,7 @@ def error_of(e2p, e2d, n_p, n_d, occ: int) -> float:
 
 
 def decide(st: SolveState, new_error: float, nvalid: float, max_iters: int, tol_residual: float, tol_update: float, forced: int):
-    """The scalar decisions of one pass (wave 0 of solve_waves).  Mutates st; returns (take, go, lam32) -- take 2: the candidate
+    """The scalar decisions of one pass (solve_bookkeeping_wave, wave 0 of solve_waves).  Mutates st; returns (take, go, lam32) -- take 2: the candidate
     was accepted (pose := cand), go: a step is computed, lam32: the damping of its rank test."""
     lam32 = F(st.lam if st.first else st.lam / 5.0)
     st.n_evals += 1

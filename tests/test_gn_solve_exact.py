@@ -1,7 +1,11 @@
 """The serial Gauss-Newton step of the spherical path (solve_waves / solve_finish / fs_write_state, qr_rank6_lanes /
 lu_inverse6_lanes, photo_icp_kernels.h) driven from chosen states through rgbd360_debug_solve_state, against the float64 / float32 /
 mpmath references of tests/gn_reference.py and the CPU oracle.  Every case runs through the three routes -- k_solve (0), the prologue
-of the fused launch k_eval_fs (1), the same with the row late in the table (2) -- which must agree bit for bit."""
+of the fused launch k_eval_fs (1), the same with the row late in the table (2) -- which must agree bit for bit.  The three routes
+run the same solve code (route 0 had a form of its own once); the hand-made cases -- the pseudo-exponential's branches, the
+bookkeeping, the rank and pivot edges -- are also compared, on every route, with the bits that old form of route 0 left in
+tests/golden/solve_bits.json (tools/solve_bits.py; the cases live in tests/solve_cases.py).  The large sweeps are not in the file:
+gn_reference.update_f32 pins their update bit for bit and the oracle their verdicts."""
 import ctypes as C
 import math
 
@@ -9,6 +13,7 @@ import numpy as np
 import pytest
 
 import gn_reference as R
+import solve_cases as S
 from rgbd360_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -40,10 +45,25 @@ KEYS_I = ("status", "done", "level_active", "it", "n_evals", "iters")
 KEYS_F = ("lam", "error", "new_error", "diff_error")
 
 
-def _run(reg, level, row, **kw):
-    """All three routes; asserts they agree bit for bit and returns route 0's state."""
+@pytest.fixture(scope="module")
+def recorded():
+    return S.load_recorded()
+
+
+def _run_case(reg, recorded, case):
+    """_run on a case of tests/solve_cases.py, every route against the case's recorded bits."""
+    return _run(reg, case["level"], case["row"], recorded=recorded[case["name"]], **case["kw"])
+
+
+def _run(reg, level, row, recorded=None, **kw):
+    """All three routes; asserts they agree bit for bit -- and with the recorded state, where there is one (pend_nb on route 0 only: a
+    fused launch leaves its own pass pending, as many rows as its frame has) -- and returns route 0's state."""
     outs = [reg.debug_solve_state(level, row, route=r, **kw) for r in ROUTES]
     o0 = outs[0]
+    if recorded is not None:
+        for r, o in zip(ROUTES, outs):
+            differ = S.differences(o, recorded, skip=("pend_nb",) if r else ())
+            assert not differ, (r, differ)
     for o in outs[1:]:
         for k in KEYS_I:
             assert o[k] == o0[k], (k, o, o0)
@@ -121,15 +141,15 @@ def test_rank_verdict_equals_the_oracle_on_the_near_threshold_sweep(reg, oracle_
     assert not bad, bad[:10]
 
 
-def test_rank_and_pivot_edges_agree_with_the_oracle(reg, oracle_mod):
+def test_rank_and_pivot_edges_agree_with_the_oracle(reg, oracle_mod, recorded):
     """An exact zero LU pivot, an exactly singular matrix, and entries scaled by 2^j so that squared column norms overflow or
     underflow float32: the device's verdict is the oracle gn_step's (rank test, then the inverse's zero-pivot test), whatever it is."""
-    for H, g, name in R.rank_edge_cases():
-        for k in (0, 6):
-            lam = R.device_lambda(k)
-            st, _, upd = oracle_mod.gn_step(H, g, F(lam), np.eye(4))
-            out = _run(reg, 0, _step_row(H, g), lam=lam)
-            assert out["status"] == st, (name, k, out["status"], st)
+    cases = S.rank_edge_cases()
+    assert len(cases) == 2 * len(R.rank_edge_cases())
+    for c in cases:
+        st, _, upd = oracle_mod.gn_step(c["H"], c["g"], F(c["lam"]), np.eye(4))
+        out = _run_case(reg, recorded, c)
+        assert out["status"] == st, (c["label"], c["k"], out["status"], st)
 
 
 # -------------------------------------------------------------------------------------------------------------------------------
@@ -169,107 +189,53 @@ def _oracle_pexp(L, v):
     return E.reshape(4, 4).T.copy()
 
 
-def test_pseudo_exponential_branches(reg, oracle_mod):
+def test_pseudo_exponential_branches(reg, oracle_mod, recorded):
     """H = 2^k I makes the update exactly -2^-k g.  Rotation angles 0, 2^-45 (the threshold of gn::se3_pseudo_exp) and one float32
     step on either side, 1e-8, 0.49 / 0.5 / 0.51 (theta^2 = 0.25: series against sin / cos), 1, 2, 3.1, pi, 3.5.  At the identity
     pose the candidate is within 1 ulp of float32(Rodrigues(update)) evaluated in mpmath, its translation column is the update bit
     for bit, and around the threshold the branch is gn::se3_pseudo_exp's; at another pose the candidate is within
     8 u (|E||P|) of the float64 product."""
     L = oracle_mod.lib()
-    rng = np.random.default_rng(44)
     thr = R.ROT_THRESHOLD
-    angles = [0.0, 1e-8, 0.49, 0.5, 0.51, 1.0, 2.0, 3.1, math.pi, 3.5]
-    axis_cases = [np.array([thr, 0, 0]), np.array([0, np.nextafter(F(thr), F(0)), 0]), np.array([0, 0, np.nextafter(F(thr), F(1))])]
-    P = np.eye(4, dtype=F)
-    P[:3, :3] = np.asarray(R.pseudo_exp_mp(np.array([0, 0, 0, 0.3, -0.2, 0.5]))[:3, :3], F)
-    P[:3, 3] = F([0.4, -1.5, 2.25])
-    ws = []
-    for a in angles:
-        d = rng.normal(size=3)
-        ws.append(d / np.linalg.norm(d) * a)
-    ws += axis_cases
-    kexp = 3
-    H = np.eye(6) * 2.0 ** kexp
-    for w in ws:
-        u = np.concatenate([rng.normal(size=3) * 0.1, w]).astype(F)
-        g = (-u.astype(np.float64) * 2.0 ** kexp)
-        for pose in (np.eye(4, dtype=F), P):
-            out = _run(reg, 0, _step_row(H, g), pose=pose)
-            assert out["status"] == 0 and np.array_equal(_bits(out["update"]), _bits(u)), (out["update"], u)
-            cand = out["cand"]
-            v = u.astype(np.float64)
-            if pose is P:
-                E = R.pseudo_exp_mp(v)
-                want = E @ P.astype(np.float64)
-                bound = 8 * R.U32 * (np.abs(E) @ np.abs(P.astype(np.float64)))
-                assert np.all(np.abs(cand - want) <= bound), (np.linalg.norm(w), np.abs(cand - want) / np.maximum(bound, 1e-300))
-                continue
-            assert np.array_equal(_bits(cand[:3, 3]), _bits(u[:3]))
-            assert np.array_equal(cand[3], F([0, 0, 0, 1]))
-            wn = float(np.linalg.norm(v[3:]))
-            if abs(wn - thr) <= thr * 1e-6 or wn == 0.0:
-                E_o = _oracle_pexp(L, v).astype(F)
-                assert np.array_equal(cand[:3, :3] != np.eye(3, dtype=F), E_o[:3, :3] != np.eye(3, dtype=F)), (wn, cand, E_o)
-                assert np.array_equal(cand[:3, :3], E_o[:3, :3]), (wn, cand, E_o)
-            else:
-                want = R.pseudo_exp_f32_mp(v)
-                assert _ulps(cand, want).max() <= 1, (wn, _ulps(cand, want))
+    cases = S.pseudo_exp_cases()
+    assert len(cases) == 26
+    for c in cases:
+        w, u, P = c["w"], c["u"], c["P"]
+        out = _run_case(reg, recorded, c)
+        assert out["status"] == 0 and np.array_equal(_bits(out["update"]), _bits(u)), (out["update"], u)
+        cand = out["cand"]
+        v = u.astype(np.float64)
+        if c["at_P"]:
+            E = R.pseudo_exp_mp(v)
+            want = E @ P.astype(np.float64)
+            bound = 8 * R.U32 * (np.abs(E) @ np.abs(P.astype(np.float64)))
+            assert np.all(np.abs(cand - want) <= bound), (np.linalg.norm(w), np.abs(cand - want) / np.maximum(bound, 1e-300))
+            continue
+        assert np.array_equal(_bits(cand[:3, 3]), _bits(u[:3]))
+        assert np.array_equal(cand[3], F([0, 0, 0, 1]))
+        wn = float(np.linalg.norm(v[3:]))
+        if abs(wn - thr) <= thr * 1e-6 or wn == 0.0:
+            E_o = _oracle_pexp(L, v).astype(F)
+            assert np.array_equal(cand[:3, :3] != np.eye(3, dtype=F), E_o[:3, :3] != np.eye(3, dtype=F)), (wn, cand, E_o)
+            assert np.array_equal(cand[:3, :3], E_o[:3, :3]), (wn, cand, E_o)
+        else:
+            want = R.pseudo_exp_f32_mp(v)
+            assert _ulps(cand, want).max() <= 1, (wn, _ulps(cand, want))
 
 
 # -------------------------------------------------------------------------------------------------------------------------------
 # 5. the bookkeeping against the restatement
 # -------------------------------------------------------------------------------------------------------------------------------
-def _bk_cases():
-    H = np.diag([4.0, 5.0, 6.0, 7.0, 8.0, 9.0])
-    g = np.array([0.3, -0.2, 0.1, 0.0, 0.0, 0.0])
-    rng = np.random.default_rng(55)
-    P = np.eye(4, dtype=F)
-    P[:3, :3] = np.asarray(R.pseudo_exp_mp(np.array([0, 0, 0, -0.1, 0.25, 0.05]))[:3, :3], F)
-    P[:3, 3] = F([0.2, 0.1, -0.3])
-    tol = 2.0 ** -10
-    ok_sums = dict(e2=(3000.0, 5000.0), n=(1200, 800, 1500))      # error sqrt(8000 / 2000) = 2 exactly
-    upd = F([0.01, -0.02, 0.005, 0.001, 0.0, 0.002])
-    base = dict(pose=P, update=upd, lam=0.04, error=2.0 + 0.5, first=0, it=3, max_iters=10, tol_residual=tol, tol_update=1e-4,
-                forced=0, occlusion=0, level=0, **ok_sums)
-    cases = {
-        "first pass": dict(base, first=1, lam=1.0, it=0, error=0.0),
-        "accept": base,
-        "diff equals tol": dict(base, error=2.0 + tol),
-        "diff one ulp above tol": dict(base, error=np.nextafter(2.0 + tol, 3.0)),
-        "reject": dict(base, error=2.0 - 0.25),
-        "it = max_iters - 1": dict(base, it=9),
-        "it = max_iters - 2": dict(base, it=8),
-        "it = max_iters": dict(base, it=10),
-        "|update| = tol_update": dict(base, update=F([2.0 ** -12, 0, 0, 0, 0, 0]), tol_update=2.0 ** -12),
-        "|update| one ulp above": dict(base, update=F([np.nextafter(F(2.0 ** -12), F(1)), 0, 0, 0, 0, 0]), tol_update=2.0 ** -12),
-        "forced, rejected diff": dict(base, error=1.0, forced=1),
-        "occ 1, depth empty, first": dict(base, first=1, lam=1.0, it=0, occlusion=1, e2=(3000.0, 0.0), n=(1200, 0, 1500)),
-        "occ 2, photo empty, first": dict(base, first=1, lam=1.0, it=0, occlusion=2, e2=(0.0, 5000.0), n=(0, 800, 1500)),
-        "occ 1, depth sum without count, first": dict(base, first=1, lam=1.0, it=0, occlusion=1, e2=(3000.0, 7.0), n=(1200, 0, 1500)),
-        "occ 2, depth empty, later": dict(base, occlusion=2, e2=(3000.0, 0.0), n=(1200, 0, 1500)),
-        "occ 1, both present": dict(base, occlusion=1, error=9.0),
-        "NaN, first": dict(base, first=1, lam=1.0, it=0, e2=(float("nan"), 5000.0)),
-        "NaN, later": dict(base, e2=(float("nan"), 5000.0)),
-        "no residuals, first": dict(base, first=1, lam=1.0, it=0, n=(0, 0, 0), e2=(0.0, 0.0)),
-        "level 1 finished: handover": dict(base, level=1, error=2.0 - 0.25),
-        "level 1 accepted": dict(base, level=1),
-        "level 1 at the iteration limit: handover": dict(base, level=1, it=9),
-        "level 1 forced at the limit": dict(base, level=1, it=9, forced=1),
-    }
-    return H, g, cases
-
-
-def test_bookkeeping_matches_the_restatement(reg):
+def test_bookkeeping_matches_the_restatement(reg, recorded):
     """Accept when diff > tol_residual (diff equal: no), it against max_iters, |update| against tol_update, forced, the occlusion
     error sqrt(E2P / NP) + sqrt(E2D / ND) with a modality empty, NaN totals, no residuals, and the hand-over of a finished level to
     the next finer one: every field of the state equals gn_reference.solve_step's."""
-    H, g, cases = _bk_cases()
+    H, g, cases = S.bookkeeping_cases()
+    assert len(cases) == 23
     H32, g32 = H.astype(F), g.astype(F)
-    for name, c in cases.items():
-        row = R.partial_row(H, g, e2=c["e2"], n=c["n"])
-        out = _run(reg, c["level"], row, pose=c["pose"], update=c["update"], lam=c["lam"], error=c["error"], first=c["first"],
-                   it=c["it"], max_iters=c["max_iters"], tol_residual=c["tol_residual"], tol_update=c["tol_update"], forced=c["forced"],
-                   occlusion=c["occlusion"])
+    for case in cases:
+        name, c = case["label"], case["c"]
+        out = _run_case(reg, recorded, case)
         st = R.SolveState(level=c["level"], pose=c["pose"], update=c["update"], lam=c["lam"], error=c["error"], first=c["first"],
                           it=c["it"])
         want = R.solve_step(st, H32, g32, c["e2"][0], c["e2"][1], c["n"][0], c["n"][1], occ=c["occlusion"], max_iters=c["max_iters"],

@@ -1,5 +1,7 @@
 """The fused launches fetch the pending pass's partial table in 16-byte pieces on eight waves (stage_pending, photo_icp_kernels.h); the
-two-launch solve (k_solve, solve_block) keeps the 8-byte form on sixteen.  Both must form every column total in the same association:
+two-launch solve (k_solve, solve_block) keeps the 8-byte form on sixteen, for any row count.  The row fetch is all that differs between
+the routes: behind it k_solve runs the same solve code as the fused launches (solve_staged; it had a form of its own once, whose bits
+tests/golden/solve_bits.json holds).  Both fetches must form every column total in the same association:
 
     s[q]   = 0.0 + x[q] + x[q + 32] + ... + x[q + 224]          q = 0 ... 31, rows >= n_rows count as explicit 0.0 terms
     red[w] = s[2 w] + s[2 w + 1]                                w = 0 ... 15
