@@ -4,7 +4,7 @@
 //     frame_%03d.rgb  (H*W*3 uint8)   frame_%03d.depth (H*W uint16 mm)
 // Build:  g++ -std=c++17 -O2 -Iinclude examples/odometry_replay.cpp -Lrgbd360_amd/lib -lrgbd360_hip
 //             -Wl,-rpath,$PWD/rgbd360_amd/lib -o odometry_replay
-// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane | --refine-on-map-colour | --refine-on-map-c2f SHIFT [--plane]] [--render-map PREFIX] [--raycast-map PREFIX] [--map-normals OUT] [--raycast-surface PREFIX] [--map-planes OUT] [--map-window N | --carve]]
+// Usage:  odometry_replay <dir> <n_frames> <width> <height> [--sequence | --multi <n_gpus> | --pbmap | --link] [--map FILE [--leaf L] [--refine-on-map | --refine-on-map-plane | --refine-on-map-colour | --refine-on-map-c2f SHIFT [--plane]] [--map-robust KIND DELTA] [--render-map PREFIX] [--raycast-map PREFIX] [--map-normals OUT] [--raycast-surface PREFIX] [--map-planes OUT] [--map-window N | --carve]]
 //         --sequence: all frames are loaded first and the frame loop runs inside the library (alignSequence)
 //         --multi N:  the same sequence sharded over N GPUs of this node from this one process (rgbd360_multi_*: one host thread
 //                     per device, contiguous shards of pairs, one ncclAllGather of the solved poses over xGMI); prints the
@@ -31,6 +31,9 @@
 //                     leaf * 2^SHIFT .. leaf, merged out of the resident table, each level from the pose of the one before -- a capture range of
 //                     2^SHIFT leaves where the two options above have one; --plane: the point-to-plane form on every level.  Prints one
 //                     "refine-c2f" line per frame and one "  level" line per level.  Takes precedence over both.
+//         --map-robust KIND DELTA: (with a refine option) the robust kernel of whichever method refines (GlobalMap::setAlignRobust): KIND huber,
+//                     cauchy or geman_mcclure, DELTA in metres (the colour method: in the units of the square root of its joint cost); one
+//                     extra "  robust" line per frame with sum w, the contributing points and those with w < 1 (GlobalMap::robustInfo).
 //         --render-map PREFIX: (needs --map) after the replay the map is rendered as a spherical frame of the input's size at the last
 //                     pose (GlobalMap::renderSphere: the reference's viewer.globalMap, OdometryRGBD360.cpp:242-268, as a panorama) and
 //                     written as PREFIX_rgb.ppm (P6) and PREFIX_depth.pfm (Pf, metres, 0 in holes, rows bottom to top); prints one
@@ -198,6 +201,8 @@ int main(int argc, char** argv) {
     float leaf = 0.05f;
     bool refine_on_map = false, refine_on_map_plane = false, refine_on_map_colour = false, c2f_plane = false;
     int c2f_shift = -1;
+    int robust_kind = RGBD360_MAP_ROBUST_NONE;
+    double robust_delta = 0.0;
     int map_window = 0;
     bool carve = false;
     for (int a = 5; a < argc; ++a) {
@@ -215,6 +220,16 @@ int main(int argc, char** argv) {
         if (std::string(argv[a]) == "--refine-on-map-colour") refine_on_map_colour = true;
         if (a + 1 < argc && std::string(argv[a]) == "--refine-on-map-c2f") c2f_shift = atoi(argv[a + 1]);
         if (std::string(argv[a]) == "--plane") c2f_plane = true;
+        if (a + 2 < argc && std::string(argv[a]) == "--map-robust") {
+            const std::string kind = argv[a + 1];
+            robust_kind = kind == "huber" ? RGBD360_MAP_ROBUST_HUBER : kind == "cauchy" ? RGBD360_MAP_ROBUST_CAUCHY
+                        : kind == "geman_mcclure" ? RGBD360_MAP_ROBUST_GEMAN_MCCLURE : -1;
+            robust_delta = atof(argv[a + 2]);
+        }
+    }
+    if (robust_kind < 0 || (robust_kind != RGBD360_MAP_ROBUST_NONE && (map_file.empty() || !(robust_delta > 0.0)))) {
+        fprintf(stderr, "--map-robust needs --map, a kind (huber, cauchy, geman_mcclure) and a positive delta\n");
+        return 2;
     }
     if (!render_prefix.empty() && map_file.empty()) {
         fprintf(stderr, "--render-map needs --map\n");
@@ -291,6 +306,11 @@ int main(int argc, char** argv) {
     if (use_pbmap) planes1 = rgbd360::segmentPlanes(align360, frame1.sphereDepth, seg);
     if (!map_file.empty()) {
         globalMap.reset(new rgbd360::GlobalMap(align360, rgbd360::FilterPointCloud(leaf)));
+        if (robust_kind != RGBD360_MAP_ROBUST_NONE) {       // of the method that refines
+            const int method = c2f_shift >= 0 ? (c2f_plane ? RGBD360_MAP_METHOD_PLANE : RGBD360_MAP_METHOD_POINT)
+                             : refine_on_map_colour ? RGBD360_MAP_METHOD_COLOUR : refine_on_map_plane ? RGBD360_MAP_METHOD_PLANE : RGBD360_MAP_METHOD_POINT;
+            globalMap->setAlignRobust(method, robust_kind, robust_delta);
+        }
         add_to_map(frame1);                                                                     // the first frame, at the identity
     }
     for (int k = 1; k < n; ++k) {
@@ -352,6 +372,11 @@ int main(int argc, char** argv) {
             printf("refine %d status %d iterations %d matched %lld fitness %.6f pose_t %.5f %.5f %.5f\n", k - 1, status, r.iterations, r.n_matched, r.fitness,
                    refined(0, 3), refined(1, 3), refined(2, 3));
             if (status == RGBD360_OK) currentPose = refined;
+        }
+        if (globalMap && robust_kind != RGBD360_MAP_ROBUST_NONE && (refine_on_map || refine_on_map_plane || refine_on_map_colour || c2f_shift >= 0)) {
+            const rgbd360_map_robust_info ri = globalMap->robustInfo();
+            printf("  robust %d method %d kind %d delta %.6g sum_w %.3f contributing %lld downweighted %lld\n", k - 1, ri.method, ri.kind, ri.delta_eff, ri.sum_w,
+                   ri.n, ri.n_downweighted);
         }
         if (globalMap) add_to_map(frame2);
         std::swap(frame1, frame2);

@@ -193,6 +193,30 @@ class GlobalMap {
     }
     const rgbd360_map_align_plane_result& alignPlaneResult() const { return alignPlane_; }      // of the last alignSpherePlane / alignCloudPlane call
 
+    // Robust kernels (rgbd360_map_set_align_robust): a setting of the map per method (RGBD360_MAP_METHOD_*), kind RGBD360_MAP_ROBUST_*, delta in
+    // the units of the square root of the method's cost term (metres for point and plane).  Every align* call of the method, the batches,
+    // alignSphereCoarseToFine and alignMapGICP honour it; RGBD360_MAP_ROBUST_NONE (the default) is the quadratic call.  robustInfo(): what the
+    // last single alignment did with it (sum w, the contributing points, those with w < 1); robustInfo(job): a job of the last batch.
+    void setAlignRobust(int method, int kind, double delta = 0.0, bool scaleWithLevel = false) {
+        const rgbd360_map_robust r = {kind, scaleWithLevel ? 1 : 0, delta};
+        check(rgbd360_map_set_align_robust(map_, method, &r), "rgbd360_map_set_align_robust");
+    }
+    rgbd360_map_robust alignRobust(int method) {
+        rgbd360_map_robust r = {};
+        check(rgbd360_map_get_align_robust(map_, method, &r), "rgbd360_map_get_align_robust");
+        return r;
+    }
+    rgbd360_map_robust_info robustInfo() {
+        rgbd360_map_robust_info info = {};
+        check(rgbd360_map_align_robust_info(map_, &info), "rgbd360_map_align_robust_info");
+        return info;
+    }
+    rgbd360_map_robust_info robustInfo(int job) {
+        rgbd360_map_robust_info info = {};
+        check(rgbd360_map_align_batch_robust_info(map_, job, &info), "rgbd360_map_align_batch_robust_info");
+        return info;
+    }
+
     // Many alignments in lock step (rgbd360_map_align_batch_* / rgbd360_map_align_plane_batch_*): inputs of one form and jobs (input index,
     // guess); per job poses[j] and results[j] are exactly what alignCloud / alignSphere (their Plane forms) return for that input from that
     // guess, with 2 max_iters + 3 launches and one synchronisation for the whole batch.  The frames of a batch share one size and depth type.

@@ -530,6 +530,7 @@ int    rgbd360_map_align_plane_best(const rgbd360_map_align_plane_result* result
  * Returns the status.  Returns -1 with rgbd360_map_last_error set, nothing launched and the outputs untouched, for: what the batch
  * refuses; K < 1, S outside 1 .. 16, K S > RGBD360_MAP_BATCH_MAX; NULL inputs, poses or extrinsics; poses or extrinsics that are not
  * finite; refine_poses without a fixed_sensor; fixed_sensor outside -1 .. S - 1; lambda negative or not finite; min_input_matches < 1.
+ * The map's robust setting for the plane method (rgbd360_map_set_align_robust) is NOT honoured: the calibration keeps the quadratic kernels.
  * Out of scope: the reference's control-plane method, per-sensor intrinsics, robust weights, sphere-frame inputs, several GPUs. */
 #define RGBD360_RIG_CALIB_MAX_SENSORS 16
 typedef struct { rgbd360_map_align_plane_params plane; int refine_poses, fixed_sensor; float lambda; long long min_input_matches; } rgbd360_rig_calib_params;
@@ -897,7 +898,7 @@ int       rgbd360_map_release_colours(rgbd360_map* map);
  *     evaluation, one stream synchronisation.  fitness = cost / n.
  * With lambda_geometric = 1 everything but cc is independent of the colours (point-to-plane on the resident normals); 0 is the
  * photometric term alone.  The table is never written.  Differences from Open3D, stated: the target's gradient comes from the voxels of
- * the 27 cells, not from a radius search; no robust kernel on either term; sqrt(lambda) is not folded into the residuals (the same
+ * the 27 cells, not from a radius search; a robust kernel is a setting of the map (below: one joint weight for both terms); sqrt(lambda) is not folded into the residuals (the same
  * normal equations).  Out of scope: a colour switch in rgbd360_map_align_c2f_*, colour on the source side of a map-against-map
  * alignment, exposure compensation. */
 typedef struct {
@@ -931,6 +932,58 @@ int    rgbd360_map_align_colour_cloud(rgbd360_map* map, const float* xyz, const 
 int    rgbd360_map_align_colour_sphere(rgbd360_map* map, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type,
                                        int rows, int cols, int convention, const float guess[16], int on_device,
                                        const rgbd360_map_align_colour_params* params, float pose_out[16], rgbd360_map_align_colour_result* result);
+
+/* ---- robust kernels of the alignments against the map (csrc/map_align_robust.h) ----------------------------------------------------
+ * The match gate max_dist <= leaf is all that keeps a wrong match out of the four alignments above: at leaf 0.1 m a surface 4 - 6 cm
+ * from where the map has it -- a box that moved, a door, a ghost wall, a person -- still matches and enters the normal equations at full
+ * weight.  A robust kernel gives every contributing point one weight, computed from the residual the method already has; the kinds and
+ * their formulas are the pose graph's (gn::robust_rho_w, one text for host and device; RGBD360_MAP_ROBUST_* equal RGBD360_GRAPH_ROBUST_*).
+ * Float64 with + - x / sqrt only (Cauchy's rho also log1p), every operation rounded on its own; tests/map_align_robust_reference.py
+ * restates it in numpy.
+ *   cost term   a kept, contributing point of method M has the per-point cost term s, exactly the double the quadratic evaluation adds to
+ *               its cost word: point (e_x e_x + e_y e_y) + e_z e_z; plane r r; generalized ICP its cost e^T M e; colour
+ *               l (r_G r_G) + c (r_C r_C) -- one joint weight for both terms.
+ *   weight      (rho, w) = robust_rho_w(kind, delta_eff, s): Huber rho = s, w = 1 for s <= delta^2, else rho = 2 delta sqrt(s) - delta^2,
+ *               w = delta / sqrt(s); Cauchy rho = delta^2 log1p(s / delta^2), w = 1 / (1 + s / delta^2); Geman-McClure t = delta^2 /
+ *               (delta^2 + s), rho = s t, w = t t.  s = 0 gives (0, 1) for every kind.  delta is in the units of sqrt(s): metres for point
+ *               and plane.  delta_eff = delta 2^shift on the level `shift` of a map pyramid when scale_with_level is set (exact), else delta.
+ *   row         M's row with two words behind it.  Every word in front of M's cost word receives w t, t the quadratic evaluation's own
+ *               term rounded as it rounds it (e.g. t = J_a J_b), then the one product w t, then the add: word 0 holds sum w.  The cost
+ *               word receives rho.  The diagnostic sums behind it (sum e.e, sum r_G^2, sum r_C^2) and all counters stay unweighted.
+ *               Word kWords: the number of contributing points n -- what min_matches, n_matched, the trace's n and fitness = sum rho / n
+ *               use.  Word kWords + 1: the number of points with w < 1.  H and g are assembled from the weighted words as M assembles
+ *               them; the trace's sum_sq is sum rho.  The returned Hessian and gradient are the weighted ones: an edge built from a
+ *               robust alignment carries less information where the alignment distrusted its matches.
+ * The setting is per method and resident in the map; it is no layer and bumps no revision.  Every method starts at
+ * RGBD360_MAP_ROBUST_NONE, and with NONE no robust kernel is launched: the call is the quadratic call, byte for byte.  Honoured by
+ * rgbd360_map_align_* / _plane_* / _gicp_* / _colour_* (sphere and cloud), rgbd360_map_align_batch_* and _plane_batch_* (_best compares
+ * the robust fitness), rgbd360_map_align_c2f_* (a level uses its root's setting) and whatever is built on them.  NOT honoured by
+ * rgbd360_map_calibrate_rig_*, the depth trainer and evaluator, and the plane relocalisation: they keep the quadratic kernels.
+ * Out of scope: separate weights for the two terms of coloured ICP, an adaptive delta, the second-order term of the loss, any change to
+ * the match gate.  Limit, stated: a robust kernel needs the displaced surface to be the minority of what constrains a direction; where
+ * it is the majority every kind locks onto it. */
+enum { RGBD360_MAP_METHOD_POINT = 0, RGBD360_MAP_METHOD_PLANE = 1, RGBD360_MAP_METHOD_GICP = 2, RGBD360_MAP_METHOD_COLOUR = 3 };
+enum { RGBD360_MAP_ROBUST_NONE = 0, RGBD360_MAP_ROBUST_HUBER = 1, RGBD360_MAP_ROBUST_CAUCHY = 2, RGBD360_MAP_ROBUST_GEMAN_MCCLURE = 3 };
+typedef struct {
+    int    kind;               /* RGBD360_MAP_ROBUST_*: NONE */
+    int    scale_with_level;   /* != 0: delta x 2^shift on level `shift` of the map's pyramid: 0 */
+    double delta;              /* > 0 and finite unless kind is NONE (then ignored), in the units of sqrt(s) */
+} rgbd360_map_robust;
+typedef struct {
+    int    method, kind;       /* of the alignment reported; kind NONE: the quadratic call (sum_w = n, n_downweighted = 0) */
+    double delta_eff;          /* the delta the kernels took */
+    double sum_w;              /* word 0 of the final evaluation's row */
+    long long n, n_downweighted;       /* its contributing points, and those of them with w < 1 */
+} rgbd360_map_robust_info;
+/* 0; -1 with rgbd360_map_last_error set and the setting untouched: a NULL map or setting, an unknown method, a kind outside 0 .. 3, a
+ * delta that is not finite and positive when the kind is not NONE, a `map` that is a level of a pyramid (levels follow their root). */
+int    rgbd360_map_set_align_robust(rgbd360_map* map, int method, const rgbd360_map_robust* robust);
+/* The method's setting (a level: its root's); -1 for a NULL map or output or an unknown method, the output untouched. */
+int    rgbd360_map_get_align_robust(rgbd360_map* map, int method, rgbd360_map_robust* robust);
+/* What the last single alignment on this map did (rgbd360_map_align_c2f_*: its finest level); all zero before the first.  The
+ * second: job `job` of the map's last batch; -1 when there is no such job. */
+int    rgbd360_map_align_robust_info(rgbd360_map* map, rgbd360_map_robust_info* info);
+int    rgbd360_map_align_batch_robust_info(rgbd360_map* map, int job, rgbd360_map_robust_info* info);
 
 /* ---- free-space observation and carving of the map (csrc/map_carve.h) -----------------------------------------------------------
  * What lets the map react to what a new frame sees: an object that moved away, a ghost wall left by a pose that was corrected later,
@@ -1727,7 +1780,8 @@ int  rgbd360_depth_trainer_accumulate_images(rgbd360_depth_trainer* trainer, con
  * NULL; device memory with on_device 1): the gt of every pixel that reached step 2, 0 elsewhere.  The coarse layer and the normal layer
  * are built or reused exactly as the surface cast does.  Refusals: those of the image route and of the two casts' parameters, a NULL or
  * foreign map, a pose or pinhole that is not finite, fx or fy zero, min_cos_incidence outside [0, 1].  An empty map, or rows cols == 0,
- * returns 0 with zero statistics (and a zero gt_out) and launches nothing. */
+ * returns 0 with zero statistics (and a zero gt_out) and launches nothing.  The map's robust settings (rgbd360_map_set_align_robust) play
+ * no part here or in the evaluator. */
 int  rgbd360_depth_trainer_accumulate_map(rgbd360_depth_trainer* trainer, rgbd360_map* map, const void* meas, size_t meas_step, int depth_type,
                                           int rows, int cols, float fx, float fy, float cx, float cy, const float sensor_pose[16], int on_device,
                                           const rgbd360_depth_train_params* params, float* gt_out, rgbd360_depth_train_stats* stats);
@@ -2013,7 +2067,8 @@ int rgbd360_pool_sensor_planes(const rgbd360_plane* planes, int n, float max_cur
  * needs it, reused while the map is unwritten and the parameters stand, freed with the map or by rgbd360_map_release_planes, reported by
  * rgbd360_map_plane_bytes (rgbd360_map_bytes stays the table's size).  The calls work on a level of the pyramid as every reader does.
  * Out of scope: colour descriptors of map planes, device-side outputs, merging across gaps, incremental upkeep of the labels, labels
- * inside the ICPs, the keyframe loop and acceptance thresholds of Relocalizer360::relocalize (caller policy), several GPUs. */
+ * inside the ICPs, the keyframe loop and acceptance thresholds of Relocalizer360::relocalize (caller policy), several GPUs.  The map's
+ * robust settings (rgbd360_map_set_align_robust) are not honoured here. */
 typedef struct {
     int   min_count;             /* the normal layer's three (rgbd360_map_normal_params): 1 */
     int   min_support;           /* 5 */

@@ -234,6 +234,25 @@ int rgbd360_map_align_colour_eval(rgbd360_map* map, const uint8_t* rgb, size_t r
 int rgbd360_map_time_align_colour(rgbd360_map* map, const uint8_t* rgb_dev, size_t rgb_step, const void* depth_dev, size_t depth_step, int depth_type,
                                   int rows, int cols, int convention, const float pose[16], const rgbd360_map_align_colour_params* params, int reps,
                                   float avg_us[4], double* probes);
+/* One evaluation of `method` (RGBD360_MAP_METHOD_*) in its robust form (rgbd360_hip.h, "robust kernels of the alignments against the map")
+ * at `pose`, under the map's setting for the method, which must not be RGBD360_MAP_ROBUST_NONE.  The input forms are those of the four
+ * evaluation entries above together: the sphere frame (depth; rgb for the colour method) where depth is not NULL, otherwise the cloud
+ * (xyz, n; normal for generalized ICP, may be NULL; rgb3 for the colour method); host memory, or device memory with on_device.  params:
+ * the method's own parameter struct (rgbd360_map_align_params / _plane_params / _gicp_params / _colour_params), NULL: its defaults.
+ * row[40]: the whole robust row -- the method's row, counters and probe words included, as doubles, then the number of contributing points
+ * and the number of them with w < 1; the words behind the method's width + 2 are zero.  w_dev (a DEVICE array, may be NULL): w per input
+ * point, 0.0 for a point that does not contribute.  -1 with the outputs untouched: what the method's entry refuses, an unknown method, a
+ * method whose setting is NONE. */
+int rgbd360_map_align_robust_eval(rgbd360_map* map, int method, const uint8_t* rgb, size_t rgb_step, const void* depth, size_t depth_step, int depth_type,
+                                  int rows, int cols, int convention, const float* xyz, const float* normal, const uint8_t* rgb3, long long n,
+                                  const float pose[16], int on_device, const void* params, double row[40], double* w_dev);
+/* The robust form of `method` next to its quadratic form under HIP events on a sphere frame in device memory (rgb_dev: the colour method
+ * alone), the same frame, map, buffers and parameters, the launches of the two forms alternating, averages over `reps` pairs in
+ * microseconds: avg_us[0] the robust evaluation kernel, [1] the quadratic one, [2] the solve kernel on the robust row, [3] on the
+ * quadratic row, [4] a whole robust alignment of params->max_iters iterations from `pose` (enqueue to synchronisation, wall clock), [5] a
+ * whole quadratic one.  The map's setting for the method must not be NONE.  The map is not changed. */
+int rgbd360_map_time_align_robust(rgbd360_map* map, int method, const uint8_t* rgb_dev, size_t rgb_step, const void* depth_dev, size_t depth_step,
+                                  int depth_type, int rows, int cols, int convention, const float pose[16], const void* params, int reps, float avg_us[6]);
 
 /* The pose graph's linearisation at its current poses (rgbd360_graph_*, rgbd360_hip.h): per edge r (6 doubles) and A = dr/dx_i (36
  * doubles, column-major), either may be NULL.  The graph is not changed. */

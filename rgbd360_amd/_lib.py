@@ -48,6 +48,8 @@ SYMBOLS = [
     "rgbd360_map_colour_gradient", "rgbd360_map_colour_intensity", "rgbd360_map_time_colours",
     "rgbd360_map_default_align_colour_params", "rgbd360_map_align_colour_sphere", "rgbd360_map_align_colour_cloud", "rgbd360_map_align_colour_eval",
     "rgbd360_map_time_align_colour",
+    "rgbd360_map_set_align_robust", "rgbd360_map_get_align_robust", "rgbd360_map_align_robust_info", "rgbd360_map_align_batch_robust_info",
+    "rgbd360_map_align_robust_eval", "rgbd360_map_time_align_robust",
     "rgbd360_map_default_render_params", "rgbd360_map_render_sphere", "rgbd360_map_render_sphere_dev", "rgbd360_map_time_render",
     "rgbd360_map_default_raycast_params", "rgbd360_map_raycast", "rgbd360_map_raycast_sphere", "rgbd360_map_raycast_sphere_dev",
     "rgbd360_map_raycast_set_plain", "rgbd360_map_time_raycast",
@@ -170,6 +172,18 @@ class MapAlignColourParams(C.Structure):     # rgbd360_map_align_colour_params
 class MapAlignColourResult(C.Structure):     # rgbd360_map_align_colour_result
     _fields_ = MapAlignResult._fields_ + [("n_no_normal", C.c_longlong), ("n_no_gradient", C.c_longlong), ("rms_geometric", C.c_double),
                                           ("rms_colour", C.c_double)]
+
+
+class MapRobust(C.Structure):            # rgbd360_map_robust
+    _fields_ = [("kind", C.c_int), ("scale_with_level", C.c_int), ("delta", C.c_double)]
+
+
+class MapRobustInfo(C.Structure):        # rgbd360_map_robust_info
+    _fields_ = [("method", C.c_int), ("kind", C.c_int), ("delta_eff", C.c_double), ("sum_w", C.c_double), ("n", C.c_longlong), ("n_downweighted", C.c_longlong)]
+
+
+MAP_METHOD_POINT, MAP_METHOD_PLANE, MAP_METHOD_GICP, MAP_METHOD_COLOUR = 0, 1, 2, 3                     # RGBD360_MAP_METHOD_*
+MAP_ROBUST_NONE, MAP_ROBUST_HUBER, MAP_ROBUST_CAUCHY, MAP_ROBUST_GEMAN_MCCLURE = 0, 1, 2, 3             # RGBD360_MAP_ROBUST_*
 
 
 class MapAlignTrace(C.Structure):        # rgbd360_map_align_trace (rgbd360_hip_diag.h)
@@ -651,6 +665,12 @@ def load() -> C.CDLL:
                                                 C.POINTER(MapAlignColourParams), vp, vp, vp, vp, vp, vp]
     L.rgbd360_map_time_align_colour.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, f32p, C.POINTER(MapAlignColourParams), i32, vp,
                                                 C.POINTER(C.c_double)]
+    L.rgbd360_map_set_align_robust.argtypes = [vp, i32, C.POINTER(MapRobust)]
+    L.rgbd360_map_get_align_robust.argtypes = [vp, i32, C.POINTER(MapRobust)]
+    L.rgbd360_map_align_robust_info.argtypes = [vp, C.POINTER(MapRobustInfo)]
+    L.rgbd360_map_align_batch_robust_info.argtypes = [vp, i32, C.POINTER(MapRobustInfo)]
+    L.rgbd360_map_align_robust_eval.argtypes = [vp, i32, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, vp, vp, vp, ll, f32p, i32, vp, vp, vp]
+    L.rgbd360_map_time_align_robust.argtypes = [vp, i32, vp, C.c_size_t, vp, C.c_size_t, i32, i32, i32, i32, f32p, vp, i32, vp]
     L.rgbd360_map_default_normal_params.argtypes = [vp, C.POINTER(MapNormalParams)]
     L.rgbd360_map_default_normal_params.restype = None
     L.rgbd360_map_normals.argtypes = [vp, C.POINTER(MapNormalParams), vp, ll, vp, vp, vp, vp, vp, vp, C.POINTER(MapNormalStats)]

@@ -18,7 +18,7 @@ _CSRC = os.path.join(_HERE, "csrc")
 _SHARED = ["knobs.h", "host_wait.h", "device_math.h", "f360_state.h", "dispatch.h"]
 UNITS = {
     "rgbd360_api.hip": ["photo_icp_kernels.h", "occlusion_kernels.h", "pinhole_kernels.h", "warp_images.h", "map_render.h", "map_table.h", "gn_math.h", "lm_host.h", "partial_row.h", "level_geom.h", "sequence_engine.h", "frame_store.h", "store_overlap.h", "pose_graph.h", "pose_graph_cov.h", "rig_dense.h", "multi_gpu.h", "libm_f32.h", "dev_buf.h", "wave_scan.h"] + _SHARED,
-    "rgbd360_frame360.hip": ["frame360_kernels.h", "voxel_map.h", "map_edit.h", "map_raycast.h", "map_carve.h", "map_normals.h", "map_planes.h", "depth_train.h", "depth_apply.h", "map_align_gicp.h", "map_colour.h", "map_align_colour.h", "map_table.h", "map_align.h", "map_align_plane.h", "map_align_batch.h", "rig_calib.h", "map_pyramid.h", "map_merge.h", "gn_math.h", "pbmap_register.h", "dev_buf.h", "wave_scan.h"] + _SHARED,
+    "rgbd360_frame360.hip": ["frame360_kernels.h", "voxel_map.h", "map_edit.h", "map_raycast.h", "map_carve.h", "map_normals.h", "map_planes.h", "depth_train.h", "depth_apply.h", "map_align_gicp.h", "map_colour.h", "map_align_colour.h", "map_align_robust.h", "map_table.h", "map_align.h", "map_align_plane.h", "map_align_batch.h", "rig_calib.h", "map_pyramid.h", "map_merge.h", "gn_math.h", "pbmap_register.h", "dev_buf.h", "wave_scan.h"] + _SHARED,
     "rgbd360_host.cpp": ["depth_model.h", "depth_apply.h", "pbmap_register.h"],
 }
 SRC = os.path.join(_CSRC, "rgbd360_api.hip")

@@ -43,7 +43,7 @@ namespace vmap {
 
 constexpr int kIcpSums = 17;
 constexpr int kIcpWords = 22;        // a partial row: the 17 sums, n_valid, n_box_rejected, n_out_of_range, probes, points searched (all doubles: exact integers)
-constexpr int kIcpMaxWords = 38;     // the widest row of any method (map_align_gicp.h): the buffers of a map serve every method
+constexpr int kIcpMaxWords = 40;     // the widest row of any method (the robust rows of map_align_gicp.h and map_align_colour.h): the buffers of a map serve every method
 constexpr int kIcpMaxIters = 1000;
 constexpr int kNoKey = -2147483647 - 1;
 
@@ -245,55 +245,128 @@ struct PointsOnly {
     __device__ __forceinline__ void begin(const Source&, unsigned) {}
 };
 
+// The weight of a point in its method's sums: a tail is written once, over a weight policy.  A tail calls clear() per point, set(s, args)
+// before its accumulation block with s the point's cost term AS A CALLABLE (one text: the expression the quadratic tail adds to its cost
+// word), adds wt(t) for every term t in front of the cost word and rho(s) into the cost word, and hands store() and row() on.  UnitWeight
+// is the quadratic cost: set() is nothing, wt(t) is t and rho(s) evaluates s where the tail always evaluated it, so the tail over it is
+// the machine code it was before there were policies (tools/device_asm_diff.py).  RobustWeight evaluates s in set().  RobustWeight (include/rgbd360_hip.h, "robust kernels of the alignments against the
+// map") takes w and rho from gn::robust_rho_w -- the pose graph's text -- under the launch's kind and delta; one double,
+// w, is live across the accumulation block.  It counts the contributing points and those with w < 1: the two words a robust row has behind
+// its method's.
+struct UnitWeight {
+    __device__ __forceinline__ void clear() {}
+    template <class S, class Args>
+    __device__ __forceinline__ void set(const S&, const Args&) {}
+    __device__ __forceinline__ double operator()(double t) const { return t; }
+    template <class S>
+    __device__ __forceinline__ double rho(const S& s) const { return s(); }
+    template <class Args>
+    __device__ __forceinline__ void store(long long, const Args&) const {}
+    __device__ __forceinline__ void row(double*) const {}
+};
+struct RobustWeight {
+    double w = 0.0, rho_s = 0.0;     // of the point added last (w = 0: it does not contribute)
+    unsigned n = 0, n_down = 0;
+    __device__ __forceinline__ void clear() { w = 0.0; }
+    template <class S, class Args>
+    __device__ __forceinline__ void set(const S& s, const Args& a) {
+        gn::robust_rho_w(a.kind, a.delta, s(), &rho_s, &w);
+        n += 1u;
+        n_down += w < 1.0 ? 1u : 0u;
+    }
+    __device__ __forceinline__ double operator()(double t) const {
+#pragma clang fp contract(off)
+        return w * t;
+    }
+    template <class S>
+    __device__ __forceinline__ double rho(const S&) const { return rho_s; }
+    template <class Args>
+    __device__ __forceinline__ void store(long long index, const Args& a) const {
+        if (a.w_out) a.w_out[index] = w;
+    }
+    __device__ __forceinline__ void row(double* out) const {
+        out[0] = (double)n;
+        out[1] = (double)n_down;
+    }
+};
+
 // point-to-point's tail: the 17 sums of a kept match
-struct PointTail : PointsOnly {
+template <class W>
+struct PointTailT : PointsOnly {
     double acc[kIcpSums];
-    __device__ __forceinline__ PointTail() {
+    W wt;
+    __device__ __forceinline__ PointTailT() {
 #pragma unroll
         for (int q = 0; q < kIcpSums; ++q) acc[q] = 0.0;
     }
     template <class Args>
-    __device__ __forceinline__ void add(long long, const float*, const float w[3], const Match<NoSupport>& mt, bool kept, const Args&) {
+    __device__ __forceinline__ void add(long long, const float*, const float w[3], const Match<NoSupport>& mt, bool kept, const Args& args) {
 #pragma clang fp contract(off)
+        wt.clear();
         if (kept) {
             const double wx = w[0], wy = w[1], wz = w[2], ex = mt.be[0], ey = mt.be[1], ez = mt.be[2];
-            acc[0] += 1.0;
-            acc[1] += wx;
-            acc[2] += wy;
-            acc[3] += wz;
-            acc[4] += wx * wx;
-            acc[5] += wx * wy;
-            acc[6] += wx * wz;
-            acc[7] += wy * wy;
-            acc[8] += wy * wz;
-            acc[9] += wz * wz;
-            acc[10] += ex;
-            acc[11] += ey;
-            acc[12] += ez;
-            acc[13] += wy * ez - wz * ey;
-            acc[14] += wz * ex - wx * ez;
-            acc[15] += wx * ey - wy * ex;
-            acc[16] += (ex * ex + ey * ey) + ez * ez;
+            const auto s = [&] { return (ex * ex + ey * ey) + ez * ez; };
+            wt.set(s, args);
+            acc[0] += wt(1.0);
+            acc[1] += wt(wx);
+            acc[2] += wt(wy);
+            acc[3] += wt(wz);
+            acc[4] += wt(wx * wx);
+            acc[5] += wt(wx * wy);
+            acc[6] += wt(wx * wz);
+            acc[7] += wt(wy * wy);
+            acc[8] += wt(wy * wz);
+            acc[9] += wt(wz * wz);
+            acc[10] += wt(ex);
+            acc[11] += wt(ey);
+            acc[12] += wt(ez);
+            acc[13] += wt(wy * ez - wz * ey);
+            acc[14] += wt(wz * ex - wx * ez);
+            acc[15] += wt(wx * ey - wy * ex);
+            acc[16] += wt.rho(s);
         }
     }
     template <class Args>
-    __device__ __forceinline__ void store(long long, const Args&) {}
+    __device__ __forceinline__ void store(long long index, const Args& args) const { wt.store(index, args); }
     __device__ __forceinline__ void row(double* out) const {
 #pragma unroll
         for (int q = 0; q < kIcpSums; ++q) out[q] = acc[q];
+        wt.row(out + kIcpWords);
     }
 };
+using PointTail = PointTailT<UnitWeight>;
 
 // What the loop and the evaluation need to know of a method: the row's width, where n and the traced sum of squares are, where the
 // counters start (the sums lie in front of them: n_valid, n_box_rejected, n_out_of_range, the method's own, then probes and points
-// searched), H and g; and eval_tile's Support, Args and Tail.
+// searched), H and g; and eval_tile's Support, Args and Tail (TailT: the tail over a weight policy).
 struct PointMethod {
     static constexpr int kWords = kIcpWords, kN = 0, kSumSq = 16, kCounters = 17, kProbes = 20, kSearched = 21;
     __host__ __device__ static void assemble(const double* s, float* H, float* g) { icp_assemble(s, H, g); }
     using Support = NoSupport;
     struct Args {};
     using Tail = PointTail;
+    template <class W>
+    using TailT = PointTailT<W>;
 };
+
+// The robust form of a method M: M's row with two words behind it -- the contributing points (the row's kN: min_matches, n_matched, the
+// trace's n and the fitness count them, word 0 holds sum w) and those with w < 1 -- M's tail over RobustWeight, M's assemble.  kind and
+// delta are runtime values, uniform over the launch: one instantiation per method.  w_out (tests; may be null): w per input point, 0.0
+// for a point that does not contribute.
+template <class M>
+struct Robust {
+    static constexpr int kWords = M::kWords + 2, kN = M::kWords, kDown = M::kWords + 1, kSumSq = M::kSumSq, kCounters = M::kCounters,
+                         kProbes = M::kProbes, kSearched = M::kSearched;
+    __host__ __device__ static void assemble(const double* s, float* H, float* g) { M::assemble(s, H, g); }
+    using Support = typename M::Support;
+    struct Args : M::Args {
+        int kind;
+        double delta;
+        double* w_out;
+    };
+    using Tail = typename M::template TailT<RobustWeight>;
+};
+static_assert(Robust<PointMethod>::kWords <= kIcpMaxWords, "the buffers of a map hold the widest row");
 
 template <int WORDS>
 __device__ __forceinline__ void icp_init_state(LoopState<WORDS>* __restrict__ st, const float* guess) {
@@ -397,6 +470,8 @@ struct IcpJob {
     float lambda_geometric = 1.f;
     int min_gradient_support = 0;
     float min_spread = 0.f;
+    int robust_kind = RGBD360_MAP_ROBUST_NONE;       // the robust form of a method alone (RobustIcp): the kind and delta of this call's level
+    double robust_delta = 0.0;
 };
 
 int icp_check_params(rgbd360_map* m, const rgbd360_map_align_params* params, rgbd360_map_align_params& p) {
@@ -509,11 +584,23 @@ void icp_fill_result(const IcpState<M>& st, typename M::Result* res) {
     res->fitness = nm > 0.0 ? st.row[M::kSumSq] / nm : 0.0;
     memcpy(res->hessian, st.H, sizeof(res->hessian));
     memcpy(res->gradient, st.g, sizeof(res->gradient));
-    M::fill_extra(st, res);
+    M::fill_extra(st.row, nm, res);
 }
 
 template <class M>
 int icp_run(rgbd360_map* m, const IcpJob& job, const float guess[16], float pose_out[16], typename M::Result* res);
+// what rgbd360_map_align_robust_info reports of an alignment of method M that ended with the row `row` (a quadratic one: every weight is 1)
+template <class M>
+rgbd360_map_robust_info icp_robust_info(const IcpJob& job, const double* row) {
+    rgbd360_map_robust_info o = {};
+    o.method = M::kMethod;
+    o.kind = job.robust_kind;
+    o.delta_eff = job.robust_delta;
+    o.sum_w = row[0];
+    o.n = (long long)row[M::kN];
+    o.n_downweighted = job.robust_kind != RGBD360_MAP_ROBUST_NONE ? (long long)row[M::kWords - 1] : 0;      // (a robust row's last word)
+    return o;
+}
 // an align call of method M: rgbd360_map_align_sphere / _cloud and their _plane forms
 template <class M>
 int icp_align(rgbd360_map* m, const MapInput& in, const float guess[16], const typename M::Params* params, float pose_out[16], typename M::Result* res) {
@@ -547,6 +634,7 @@ int icp_run(rgbd360_map* m, const IcpJob& job, const float guess[16], float pose
     m->a_trace.assign(tr, tr + st.iterations);
     memcpy(pose_out, st.pose, 16 * sizeof(float));
     if (res) icp_fill_result<M>(st, res);
+    m->a_robust = icp_robust_info<M>(job, st.row);
     return st.status;
 }
 // one evaluation at `pose` (the diag entries): the sums in front of the counters, the method's counters, the per-point outputs
@@ -591,8 +679,50 @@ int icp_time_whole(rgbd360_map* m, const IcpJob& job, const float pose[16], int 
     return 0;
 }
 
+// The robust form of the method B: B's host description on the row vmap::Robust<B::Row>.  The kind and delta are the
+// map's setting for the method (rgbd360_map_set_align_robust) -- a level's is its root's, delta x 2^shift with scale_with_level -- read
+// into the job by check(), so that one call uses one setting; Out has w per point behind B's outputs.
+inline const rgbd360_map_robust& icp_robust_setting(const rgbd360_map* m, int method) { return (m->parent ? m->parent : m)->robust[method]; }
+template <class B>
+struct RobustIcp : vmap::Robust<typename B::Row> {
+    using Row = vmap::Robust<typename B::Row>;
+    using Params = typename B::Params;
+    using Result = typename B::Result;
+    using Args = typename Row::Args;
+    static constexpr int kMethod = B::kMethod;
+    struct Out : B::Out {
+        double* w = nullptr;
+    };
+    static int check(rgbd360_map* m, const Params* params, IcpJob& job) {
+        if (const int rc = B::check(m, params, job)) return rc;
+        const rgbd360_map_robust& s = icp_robust_setting(m, kMethod);
+        job.robust_kind = s.kind;
+        job.robust_delta = s.scale_with_level ? ldexp(s.delta, m->shift) : s.delta;
+        return 0;
+    }
+    static int eval_args(rgbd360_map* m, const IcpJob& job, const Out& o, Args& a) {
+        if (const int rc = B::eval_args(m, job, o, a)) return rc;
+        a.kind = job.robust_kind;
+        a.delta = job.robust_delta;
+        a.w_out = o.w;
+        return 0;
+    }
+    static void fill_extra(const double* row, double n, Result* res) { B::fill_extra(row, n, res); }
+};
+// a call of method B in the form the map's setting for B asks for: f(IcpTag<M>), M = B with RGBD360_MAP_ROBUST_NONE (the quadratic call,
+// as it was before there was a setting), else RobustIcp<B>
+template <class M>
+struct IcpTag {
+    using type = M;
+};
+template <class B, class F>
+int icp_by_setting(const rgbd360_map* m, F&& f) {
+    return m && icp_robust_setting(m, B::kMethod).kind != RGBD360_MAP_ROBUST_NONE ? f(IcpTag<RobustIcp<B>>{}) : f(IcpTag<B>{});
+}
+
 struct PointIcp : vmap::PointMethod {
     using Row = vmap::PointMethod;
+    static constexpr int kMethod = RGBD360_MAP_METHOD_POINT;
     using Params = rgbd360_map_align_params;
     using Result = rgbd360_map_align_result;
     struct Out {
@@ -601,7 +731,7 @@ struct PointIcp : vmap::PointMethod {
     };
     static int check(rgbd360_map* m, const Params* params, IcpJob& job) { return icp_check_params(m, params, job.p); }
     static int eval_args(rgbd360_map*, const IcpJob&, const Out&, Args&) { return 0; }
-    static void fill_extra(const IcpState<PointIcp>&, Result*) {}
+    static void fill_extra(const double*, double, Result*) {}
 };
 }  // namespace
 
@@ -617,11 +747,16 @@ extern "C" void rgbd360_map_default_align_params(const rgbd360_map* m, rgbd360_m
 extern "C" int rgbd360_map_align_sphere(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
                                         const float guess[16], int on_device, const rgbd360_map_align_params* params, float pose_out[16],
                                         rgbd360_map_align_result* result) {
-    return icp_align<PointIcp>(m, sphere_input(nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, on_device), guess, params, pose_out, result);
+    return icp_by_setting<PointIcp>(m, [&](auto M) {
+        return icp_align<typename decltype(M)::type>(m, sphere_input(nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, on_device), guess, params,
+                                                     pose_out, result);
+    });
 }
 extern "C" int rgbd360_map_align_cloud(rgbd360_map* m, const float* xyz, long long n, const float guess[16], int on_device,
                                        const rgbd360_map_align_params* params, float pose_out[16], rgbd360_map_align_result* result) {
-    return icp_align<PointIcp>(m, cloud_input(xyz, nullptr, n, on_device), guess, params, pose_out, result);
+    return icp_by_setting<PointIcp>(m, [&](auto M) {
+        return icp_align<typename decltype(M)::type>(m, cloud_input(xyz, nullptr, n, on_device), guess, params, pose_out, result);
+    });
 }
 
 // measurement and tests (rgbd360_hip_diag.h)

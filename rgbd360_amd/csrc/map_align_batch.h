@@ -167,6 +167,8 @@ int icp_align_batch(rgbd360_map* m, const std::vector<MapInput>& inputs, const r
     // the batch runs from here on
     m->a_trace.clear();
     m->b_trace.assign((size_t)n_jobs, {});
+    const double no_row[M::kWords] = {};     // (a job of an empty input: nothing contributed)
+    m->b_robust.assign((size_t)n_jobs, icp_robust_info<M>(base, no_row));
     for (int j = 0; j < n_jobs; ++j) {       // a job of an empty input: the single call's answer; the others are overwritten below
         if (rows_of[jobs[j].input] != 0) continue;
         memcpy(poses_out + 16 * (size_t)j, jobs[j].guess, 16 * sizeof(float));
@@ -265,6 +267,7 @@ int icp_align_batch(rgbd360_map* m, const std::vector<MapInput>& inputs, const r
         m->b_trace[j].assign(tr, tr + st.iterations);
         memcpy(poses_out + 16 * (size_t)j, st.pose, 16 * sizeof(float));
         if (results) icp_fill_result<M>(st, &results[j]);
+        m->b_robust[j] = icp_robust_info<M>(base, st.row);
     }
     return 0;
 }
@@ -311,23 +314,31 @@ int batch_best(const R* results, int n, long long min_matched) {
 extern "C" int rgbd360_map_align_batch_cloud(rgbd360_map* m, const rgbd360_map_batch_cloud* inputs, int n_inputs, int on_device,
                                              const rgbd360_map_batch_job* jobs, int n_jobs, const rgbd360_map_align_params* params, float* poses_out,
                                              rgbd360_map_align_result* results) {
-    return batch_clouds<PointIcp>(m, inputs, n_inputs, on_device, jobs, n_jobs, params, poses_out, results);
+    return icp_by_setting<PointIcp>(m, [&](auto M) {
+        return batch_clouds<typename decltype(M)::type>(m, inputs, n_inputs, on_device, jobs, n_jobs, params, poses_out, results);
+    });
 }
 extern "C" int rgbd360_map_align_batch_sphere(rgbd360_map* m, const rgbd360_map_batch_frame* inputs, int n_inputs, int depth_type, int rows, int cols,
                                               int convention, int on_device, const rgbd360_map_batch_job* jobs, int n_jobs,
                                               const rgbd360_map_align_params* params, float* poses_out, rgbd360_map_align_result* results) {
-    return batch_frames<PointIcp>(m, inputs, n_inputs, depth_type, rows, cols, convention, on_device, jobs, n_jobs, params, poses_out, results);
+    return icp_by_setting<PointIcp>(m, [&](auto M) {
+        return batch_frames<typename decltype(M)::type>(m, inputs, n_inputs, depth_type, rows, cols, convention, on_device, jobs, n_jobs, params, poses_out, results);
+    });
 }
 extern "C" int rgbd360_map_align_plane_batch_cloud(rgbd360_map* m, const rgbd360_map_batch_cloud* inputs, int n_inputs, int on_device,
                                                    const rgbd360_map_batch_job* jobs, int n_jobs, const rgbd360_map_align_plane_params* params,
                                                    float* poses_out, rgbd360_map_align_plane_result* results) {
-    return batch_clouds<PlaneIcp>(m, inputs, n_inputs, on_device, jobs, n_jobs, params, poses_out, results);
+    return icp_by_setting<PlaneIcp>(m, [&](auto M) {
+        return batch_clouds<typename decltype(M)::type>(m, inputs, n_inputs, on_device, jobs, n_jobs, params, poses_out, results);
+    });
 }
 extern "C" int rgbd360_map_align_plane_batch_sphere(rgbd360_map* m, const rgbd360_map_batch_frame* inputs, int n_inputs, int depth_type, int rows, int cols,
                                                     int convention, int on_device, const rgbd360_map_batch_job* jobs, int n_jobs,
                                                     const rgbd360_map_align_plane_params* params, float* poses_out,
                                                     rgbd360_map_align_plane_result* results) {
-    return batch_frames<PlaneIcp>(m, inputs, n_inputs, depth_type, rows, cols, convention, on_device, jobs, n_jobs, params, poses_out, results);
+    return icp_by_setting<PlaneIcp>(m, [&](auto M) {
+        return batch_frames<typename decltype(M)::type>(m, inputs, n_inputs, depth_type, rows, cols, convention, on_device, jobs, n_jobs, params, poses_out, results);
+    });
 }
 extern "C" int rgbd360_map_align_best(const rgbd360_map_align_result* results, int n, long long min_matched) { return batch_best(results, n, min_matched); }
 extern "C" int rgbd360_map_align_plane_best(const rgbd360_map_align_plane_result* results, int n, long long min_matched) {

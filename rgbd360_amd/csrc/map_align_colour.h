@@ -44,14 +44,16 @@ struct ColourArgs {
     double* res_out;
     uint8_t* class_out;
 };
-// coloured ICP's tail: steps 2-5 of the definition
-struct ColourTail {
+// coloured ICP's tail: steps 2-5 of the definition; W: the weight policy (map_align.h), one joint weight for both terms
+template <class W>
+struct ColourTailT {
     const uint8_t* crow;             // the colours by the point's index, as k_vmap_insert takes them (the image's row pointer moved back by the row's first index)
     double acc[kCoCC + 1];           // n, H (21), g (6), the cost, r_G r_G, r_C r_C
+    W wt;
     unsigned n_no_normal = 0, n_no_gradient = 0;
     int pclass;                      // of the point added last, for store(): its class and residuals
     double rg, rc;
-    __device__ __forceinline__ ColourTail() {
+    __device__ __forceinline__ ColourTailT() {
 #pragma unroll
         for (int q = 0; q <= kCoCC; ++q) acc[q] = 0.0;
     }
@@ -59,9 +61,11 @@ struct ColourTail {
     __device__ __forceinline__ void begin(const Source& src, unsigned by) {
         crow = SRC == 0 ? src.rgb + (size_t)by * src.rgb_step - 3 * (size_t)by * src.cols : src.rgb;
     }
-    __device__ __forceinline__ void add(long long index, const float*, const float w[3], const Match<NoSupport>& mt, bool kept, const ColourArgs& args) {
+    template <class Args>
+    __device__ __forceinline__ void add(long long index, const float*, const float w[3], const Match<NoSupport>& mt, bool kept, const Args& args) {
 #pragma clang fp contract(off)
         const double lam = (double)args.lambda_geometric, oml = 1.0 - lam;
+        wt.clear();
         pclass = 0;
         rg = 0.0, rc = 0.0;
         if (kept) {
@@ -84,23 +88,27 @@ struct ColourTail {
                 rc = ((double)cr.I + ((dx * px + dy * py) + dz * pz)) - intensity64(c0, c1, c2, 1ull);
                 const double JG[6] = {nx, ny, nz, wy * nz - wz * ny, wz * nx - wx * nz, wx * ny - wy * nx};
                 const double JC[6] = {dx, dy, dz, wy * dz - wz * dy, wz * dx - wx * dz, wx * dy - wy * dx};
-                acc[kCoN] += 1.0;
+                const auto s = [&] { return lam * (rg * rg) + oml * (rc * rc); };
+                wt.set(s, args);
+                acc[kCoN] += wt(1.0);
                 int h = kCoH;
 #pragma unroll
                 for (int a = 0; a < 6; ++a) {
                     const double sg = lam * JG[a], sc = oml * JC[a];
 #pragma unroll
-                    for (int b = a; b < 6; ++b) acc[h++] += sg * JG[b] + sc * JC[b];
-                    acc[kCoG + a] += sg * rg + sc * rc;
+                    for (int b = a; b < 6; ++b) acc[h++] += wt(sg * JG[b] + sc * JC[b]);
+                    acc[kCoG + a] += wt(sg * rg + sc * rc);
                 }
                 const double gg = rg * rg, cc = rc * rc;
-                acc[kCoCost] += lam * gg + oml * cc;
+                acc[kCoCost] += wt.rho(s);
                 acc[kCoGG] += gg;
                 acc[kCoCC] += cc;
             }
         }
     }
-    __device__ __forceinline__ void store(long long index, const ColourArgs& args) const {
+    template <class Args>
+    __device__ __forceinline__ void store(long long index, const Args& args) const {
+        wt.store(index, args);
         if (args.res_out) {
             args.res_out[2 * index] = rg;
             args.res_out[2 * index + 1] = rc;
@@ -112,8 +120,10 @@ struct ColourTail {
         for (int q = 0; q <= kCoCC; ++q) out[q] = acc[q];
         out[kCoNoNormal] = (double)n_no_normal;
         out[kCoNoGradient] = (double)n_no_gradient;
+        wt.row(out + kColourWords);
     }
 };
+using ColourTail = ColourTailT<UnitWeight>;
 
 struct ColourMethod {
     static constexpr int kWords = kColourWords, kN = kCoN, kSumSq = kCoCost, kCounters = kCoValid, kProbes = kCoProbes, kSearched = kCoSearched;
@@ -121,6 +131,8 @@ struct ColourMethod {
     using Support = NoSupport;
     using Args = ColourArgs;
     using Tail = ColourTail;
+    template <class W>
+    using TailT = ColourTailT<W>;
 };
 static_assert(kCoValid + 1 == kCoBox && kCoValid + 2 == kCoRange, "the three counters of every method lead the row's counters");
 static_assert(kCoH == kPlH && kCoG == kPlG, "H and g lie where plane_assemble reads them");
@@ -134,6 +146,7 @@ static_assert(sizeof(rgbd360_map_align_colour_params) == 48 && sizeof(rgbd360_ma
 
 struct ColourIcp : vmap::ColourMethod {
     using Row = vmap::ColourMethod;
+    static constexpr int kMethod = RGBD360_MAP_METHOD_COLOUR;
     using Params = rgbd360_map_align_colour_params;
     using Result = rgbd360_map_align_colour_result;
     struct Out {
@@ -173,12 +186,11 @@ struct ColourIcp : vmap::ColourMethod {
         a = {normals, colours, job.lambda_geometric, o.residuals, o.cls};
         return 0;
     }
-    static void fill_extra(const IcpState<ColourIcp>& st, Result* res) {
-        const double n = st.row[vmap::kCoN];
-        res->n_no_normal = (long long)st.row[vmap::kCoNoNormal];
-        res->n_no_gradient = (long long)st.row[vmap::kCoNoGradient];
-        res->rms_geometric = n > 0.0 ? sqrt(st.row[vmap::kCoGG] / n) : 0.0;
-        res->rms_colour = n > 0.0 ? sqrt(st.row[vmap::kCoCC] / n) : 0.0;
+    static void fill_extra(const double* row, double n, Result* res) {      // (n: the contributing points)
+        res->n_no_normal = (long long)row[vmap::kCoNoNormal];
+        res->n_no_gradient = (long long)row[vmap::kCoNoGradient];
+        res->rms_geometric = n > 0.0 ? sqrt(row[vmap::kCoGG] / n) : 0.0;
+        res->rms_colour = n > 0.0 ? sqrt(row[vmap::kCoCC] / n) : 0.0;
     }
 };
 
@@ -211,14 +223,14 @@ extern "C" int rgbd360_map_align_colour_sphere(rgbd360_map* m, const uint8_t* rg
     if (!m) return -1;
     const MapInput in = sphere_input(rgb, rgb_step, depth, depth_step, depth_type, rows, cols, convention, on_device);
     if (colour_missing(in)) return vmap_fail(m, -1, "coloured ICP needs the frame's colours");
-    return icp_align<ColourIcp>(m, in, guess, params, pose_out, result);
+    return icp_by_setting<ColourIcp>(m, [&](auto M) { return icp_align<typename decltype(M)::type>(m, in, guess, params, pose_out, result); });
 }
 extern "C" int rgbd360_map_align_colour_cloud(rgbd360_map* m, const float* xyz, const uint8_t* rgb3, long long n, const float guess[16], int on_device,
                                               const rgbd360_map_align_colour_params* params, float pose_out[16], rgbd360_map_align_colour_result* result) {
     if (!m) return -1;
     const MapInput in = cloud_input(xyz, rgb3, n, on_device);
     if (colour_missing(in)) return vmap_fail(m, -1, "coloured ICP needs the cloud's colours");
-    return icp_align<ColourIcp>(m, in, guess, params, pose_out, result);
+    return icp_by_setting<ColourIcp>(m, [&](auto M) { return icp_align<typename decltype(M)::type>(m, in, guess, params, pose_out, result); });
 }
 
 // measurement and tests (rgbd360_hip_diag.h)

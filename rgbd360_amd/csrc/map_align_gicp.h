@@ -97,18 +97,22 @@ struct GicpArgs {
     double* mc_out;
     uint8_t* class_out;
 };
-// generalized ICP's tail: steps 2-5 of the definition
-struct GicpTail : PointsOnly {
+// generalized ICP's tail: steps 2-5 of the definition; W: the weight policy (map_align.h)
+template <class W>
+struct GicpTailT : PointsOnly {
     double acc[kGcEE + 1];           // n, H (21), g (6), e^T M e, e.e
+    W wt;
     unsigned n_target = 0, n_source = 0, n_pairs = 0;
     int pclass;                      // of the point added last, for store(): its class, weight and cost
     double M[6], cost;
-    __device__ __forceinline__ GicpTail() {
+    __device__ __forceinline__ GicpTailT() {
 #pragma unroll
         for (int q = 0; q <= kGcEE; ++q) acc[q] = 0.0;
     }
-    __device__ __forceinline__ void add(long long index, const float pose[16], const float w[3], const Match<NoSupport>& mt, bool kept, const GicpArgs& args) {
+    template <class Args>
+    __device__ __forceinline__ void add(long long index, const float pose[16], const float w[3], const Match<NoSupport>& mt, bool kept, const Args& args) {
 #pragma clang fp contract(off)
+        wt.clear();
         pclass = 0;
 #pragma unroll
         for (int q = 0; q < 6; ++q) M[q] = 0.0;
@@ -140,25 +144,29 @@ struct GicpTail : PointsOnly {
             const double m4[3] = {wz * m00 - wx * m02, wz * m01 - wx * m12, wz * m02 - wx * m22};
             const double m5[3] = {wx * m01 - wy * m00, wx * m11 - wy * m01, wx * m12 - wy * m02};
             cost = (ex * qx + ey * qy) + ez * qz;
-            acc[kGcN] += 1.0;
+            const auto s = [&] { return cost; };
+            wt.set(s, args);
+            acc[kGcN] += wt(1.0);
             double* H = acc + kGcH;  // rows 0 .. 5 of the upper triangle
-            H[0] += m00, H[1] += m01, H[2] += m02, H[3] += m3[0], H[4] += m4[0], H[5] += m5[0];
-            H[6] += m11, H[7] += m12, H[8] += m3[1], H[9] += m4[1], H[10] += m5[1];
-            H[11] += m22, H[12] += m3[2], H[13] += m4[2], H[14] += m5[2];
-            H[15] += wy * m3[2] - wz * m3[1], H[16] += wy * m4[2] - wz * m4[1], H[17] += wy * m5[2] - wz * m5[1];
-            H[18] += wz * m4[0] - wx * m4[2], H[19] += wz * m5[0] - wx * m5[2];
-            H[20] += wx * m5[1] - wy * m5[0];
-            acc[kGcG] += qx;
-            acc[kGcG + 1] += qy;
-            acc[kGcG + 2] += qz;
-            acc[kGcG + 3] += wy * qz - wz * qy;
-            acc[kGcG + 4] += wz * qx - wx * qz;
-            acc[kGcG + 5] += wx * qy - wy * qx;
-            acc[kGcCost] += cost;
+            H[0] += wt(m00), H[1] += wt(m01), H[2] += wt(m02), H[3] += wt(m3[0]), H[4] += wt(m4[0]), H[5] += wt(m5[0]);
+            H[6] += wt(m11), H[7] += wt(m12), H[8] += wt(m3[1]), H[9] += wt(m4[1]), H[10] += wt(m5[1]);
+            H[11] += wt(m22), H[12] += wt(m3[2]), H[13] += wt(m4[2]), H[14] += wt(m5[2]);
+            H[15] += wt(wy * m3[2] - wz * m3[1]), H[16] += wt(wy * m4[2] - wz * m4[1]), H[17] += wt(wy * m5[2] - wz * m5[1]);
+            H[18] += wt(wz * m4[0] - wx * m4[2]), H[19] += wt(wz * m5[0] - wx * m5[2]);
+            H[20] += wt(wx * m5[1] - wy * m5[0]);
+            acc[kGcG] += wt(qx);
+            acc[kGcG + 1] += wt(qy);
+            acc[kGcG + 2] += wt(qz);
+            acc[kGcG + 3] += wt(wy * qz - wz * qy);
+            acc[kGcG + 4] += wt(wz * qx - wx * qz);
+            acc[kGcG + 5] += wt(wx * qy - wy * qx);
+            acc[kGcCost] += wt.rho(s);
             acc[kGcEE] += (ex * ex + ey * ey) + ez * ez;
         }
     }
-    __device__ __forceinline__ void store(long long index, const GicpArgs& args) const {
+    template <class Args>
+    __device__ __forceinline__ void store(long long index, const Args& args) const {
+        wt.store(index, args);
         if (args.mc_out) {
 #pragma unroll
             for (int q = 0; q < 6; ++q) args.mc_out[7 * index + q] = M[q];
@@ -172,8 +180,10 @@ struct GicpTail : PointsOnly {
         out[kGcTarget] = (double)n_target;
         out[kGcSource] = (double)n_source;
         out[kGcPairs] = (double)n_pairs;
+        wt.row(out + kGicpWords);
     }
 };
+using GicpTail = GicpTailT<UnitWeight>;
 
 struct GicpMethod {
     static constexpr int kWords = kGicpWords, kN = kGcN, kSumSq = kGcCost, kCounters = kGcValid, kProbes = kGcProbes, kSearched = kGcSearched;
@@ -181,6 +191,8 @@ struct GicpMethod {
     using Support = NoSupport;
     using Args = GicpArgs;
     using Tail = GicpTail;
+    template <class W>
+    using TailT = GicpTailT<W>;
 };
 static_assert(kGcValid + 1 == kGcBox && kGcValid + 2 == kGcRange, "the three counters of every method lead the row's counters");
 static_assert(kGcH == kPlH && kGcG == kPlG, "H and g lie where plane_assemble reads them");
@@ -194,6 +206,7 @@ static_assert(sizeof(rgbd360_map_align_gicp_params) == 40 && sizeof(rgbd360_map_
 
 struct GicpIcp : vmap::GicpMethod {
     using Row = vmap::GicpMethod;
+    static constexpr int kMethod = RGBD360_MAP_METHOD_GICP;
     using Params = rgbd360_map_align_gicp_params;
     using Result = rgbd360_map_align_gicp_result;
     struct Out {
@@ -229,12 +242,11 @@ struct GicpIcp : vmap::GicpMethod {
         a = {job.src.cloud ? job.normal : nullptr, layer, job.epsilon, o.weight_cost, o.cls};
         return 0;
     }
-    static void fill_extra(const IcpState<GicpIcp>& st, Result* res) {
-        const double n = st.row[vmap::kGcN];
-        res->n_target_planes = (long long)st.row[vmap::kGcTarget];
-        res->n_source_planes = (long long)st.row[vmap::kGcSource];
-        res->n_plane_pairs = (long long)st.row[vmap::kGcPairs];
-        res->fitness_point = n > 0.0 ? st.row[vmap::kGcEE] / n : 0.0;
+    static void fill_extra(const double* row, double n, Result* res) {      // (n: the kept matches)
+        res->n_target_planes = (long long)row[vmap::kGcTarget];
+        res->n_source_planes = (long long)row[vmap::kGcSource];
+        res->n_plane_pairs = (long long)row[vmap::kGcPairs];
+        res->fitness_point = n > 0.0 ? row[vmap::kGcEE] / n : 0.0;
     }
 };
 
@@ -264,11 +276,16 @@ extern "C" void rgbd360_map_default_align_gicp_params(const rgbd360_map* m, rgbd
 extern "C" int rgbd360_map_align_gicp_sphere(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
                                              const float guess[16], int on_device, const rgbd360_map_align_gicp_params* params, float pose_out[16],
                                              rgbd360_map_align_gicp_result* result) {
-    return icp_align<GicpIcp>(m, sphere_input(nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, on_device), guess, params, pose_out, result);
+    return icp_by_setting<GicpIcp>(m, [&](auto M) {
+        return icp_align<typename decltype(M)::type>(m, sphere_input(nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, on_device), guess, params,
+                                                     pose_out, result);
+    });
 }
 extern "C" int rgbd360_map_align_gicp_cloud(rgbd360_map* m, const float* xyz, const float* normal, long long n, const float guess[16], int on_device,
                                             const rgbd360_map_align_gicp_params* params, float pose_out[16], rgbd360_map_align_gicp_result* result) {
-    return icp_align<GicpIcp>(m, gicp_cloud_input(xyz, normal, n, on_device), guess, params, pose_out, result);
+    return icp_by_setting<GicpIcp>(m, [&](auto M) {
+        return icp_align<typename decltype(M)::type>(m, gicp_cloud_input(xyz, normal, n, on_device), guess, params, pose_out, result);
+    });
 }
 
 // measurement and tests (rgbd360_hip_diag.h)

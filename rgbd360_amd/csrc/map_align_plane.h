@@ -107,19 +107,23 @@ struct PlaneArgs {
     double* nr_out;
     uint8_t* class_out;
 };
-// point-to-plane's tail: steps 2-5 of the definition on the support search27 carried
-struct PlaneTail : PointsOnly {
+// point-to-plane's tail: steps 2-5 of the definition on the support search27 carried; W: the weight policy (map_align.h)
+template <class W>
+struct PlaneTailT : PointsOnly {
     double acc[kPlRR + 2];           // n, H (21), g (6), r r, e.e
+    W wt;
     unsigned n_unsupported = 0, n_nonplanar = 0;
     int pclass;                      // of the point added last, for store(): its class, normal and r
     double nrm[3], r;
-    __device__ __forceinline__ PlaneTail() {
+    __device__ __forceinline__ PlaneTailT() {
 #pragma unroll
         for (int q = 0; q < kPlRR + 2; ++q) acc[q] = 0.0;
     }
-    __device__ __forceinline__ void add(long long, const float*, const float w[3], const Match<PlaneSupport>& mt, bool kept, const PlaneArgs& args) {
+    template <class Args>
+    __device__ __forceinline__ void add(long long, const float*, const float w[3], const Match<PlaneSupport>& mt, bool kept, const Args& args) {
 #pragma clang fp contract(off)
         const PlaneSupport& sp = mt.support;
+        wt.clear();
         pclass = kClassNone;
         nrm[0] = nrm[1] = nrm[2] = 0.0, r = 0.0;
         if (kept && sp.m < args.min_support) {
@@ -137,16 +141,18 @@ struct PlaneTail : PointsOnly {
                 const double wx = w[0], wy = w[1], wz = w[2];
                 const double J[6] = {nrm[0], nrm[1], nrm[2], wy * nrm[2] - wz * nrm[1], wz * nrm[0] - wx * nrm[2], wx * nrm[1] - wy * nrm[0]};
                 const double ex = mt.be[0], ey = mt.be[1], ez = mt.be[2];
-                acc[kPlN] += 1.0;
+                const auto s = [&] { return r * r; };
+                wt.set(s, args);
+                acc[kPlN] += wt(1.0);
                 int h = kPlH;
 #pragma unroll
                 for (int a = 0; a < 6; ++a) {
 #pragma unroll
-                    for (int b = a; b < 6; ++b) acc[h++] += J[a] * J[b];
+                    for (int b = a; b < 6; ++b) acc[h++] += wt(J[a] * J[b]);
                 }
 #pragma unroll
-                for (int a = 0; a < 6; ++a) acc[kPlG + a] += J[a] * r;
-                acc[kPlRR] += r * r;
+                for (int a = 0; a < 6; ++a) acc[kPlG + a] += wt(J[a] * r);
+                acc[kPlRR] += wt.rho(s);
                 acc[kPlEE] += (ex * ex + ey * ey) + ez * ez;
             } else {
                 pclass = kClassNonplanar;
@@ -155,7 +161,9 @@ struct PlaneTail : PointsOnly {
             }
         }
     }
-    __device__ __forceinline__ void store(long long index, const PlaneArgs& args) const {
+    template <class Args>
+    __device__ __forceinline__ void store(long long index, const Args& args) const {
+        wt.store(index, args);
         if (args.nr_out) {
             args.nr_out[4 * index] = nrm[0];
             args.nr_out[4 * index + 1] = nrm[1];
@@ -169,8 +177,10 @@ struct PlaneTail : PointsOnly {
         for (int q = 0; q < kPlRR + 2; ++q) out[q] = acc[q];
         out[kPlUnsupported] = (double)n_unsupported;
         out[kPlNonplanar] = (double)n_nonplanar;
+        wt.row(out + kPlaneWords);
     }
 };
+using PlaneTail = PlaneTailT<UnitWeight>;
 
 // H (column-major, symmetric) and g from the row
 __host__ __device__ inline void plane_assemble(const double* s, float* H, float* g) {
@@ -186,6 +196,8 @@ struct PlaneMethod {
     using Support = PlaneSupport;
     using Args = PlaneArgs;
     using Tail = PlaneTail;
+    template <class W>
+    using TailT = PlaneTailT<W>;
 };
 static_assert(kPlValid + 1 == kPlBox && kPlValid + 2 == kPlRange, "the three counters of every method lead the row's counters");
 static_assert(kPlaneWords <= kIcpMaxWords, "the buffers of a map hold the widest row");
@@ -196,6 +208,7 @@ namespace {
 
 struct PlaneIcp : vmap::PlaneMethod {
     using Row = vmap::PlaneMethod;
+    static constexpr int kMethod = RGBD360_MAP_METHOD_PLANE;
     using Params = rgbd360_map_align_plane_params;
     using Result = rgbd360_map_align_plane_result;
     struct Out {                 // (the key of the kept MATCH whatever the point's class)
@@ -220,11 +233,10 @@ struct PlaneIcp : vmap::PlaneMethod {
         a = {(unsigned)job.min_support, (double)job.max_flatness, o.normal_r, o.cls};
         return 0;
     }
-    static void fill_extra(const IcpState<PlaneIcp>& st, Result* res) {
-        const double n = st.row[vmap::kPlN];
-        res->n_unsupported = (long long)st.row[vmap::kPlUnsupported];
-        res->n_nonplanar = (long long)st.row[vmap::kPlNonplanar];
-        res->fitness_point = n > 0.0 ? st.row[vmap::kPlEE] / n : 0.0;
+    static void fill_extra(const double* row, double n, Result* res) {      // (n: the contributing points)
+        res->n_unsupported = (long long)row[vmap::kPlUnsupported];
+        res->n_nonplanar = (long long)row[vmap::kPlNonplanar];
+        res->fitness_point = n > 0.0 ? row[vmap::kPlEE] / n : 0.0;
     }
 };
 }  // namespace
@@ -245,11 +257,16 @@ extern "C" void rgbd360_map_default_align_plane_params(const rgbd360_map* m, rgb
 extern "C" int rgbd360_map_align_plane_sphere(rgbd360_map* m, const void* depth, size_t depth_step, int depth_type, int rows, int cols, int convention,
                                               const float guess[16], int on_device, const rgbd360_map_align_plane_params* params, float pose_out[16],
                                               rgbd360_map_align_plane_result* result) {
-    return icp_align<PlaneIcp>(m, sphere_input(nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, on_device), guess, params, pose_out, result);
+    return icp_by_setting<PlaneIcp>(m, [&](auto M) {
+        return icp_align<typename decltype(M)::type>(m, sphere_input(nullptr, 0, depth, depth_step, depth_type, rows, cols, convention, on_device), guess, params,
+                                                     pose_out, result);
+    });
 }
 extern "C" int rgbd360_map_align_plane_cloud(rgbd360_map* m, const float* xyz, long long n, const float guess[16], int on_device,
                                              const rgbd360_map_align_plane_params* params, float pose_out[16], rgbd360_map_align_plane_result* result) {
-    return icp_align<PlaneIcp>(m, cloud_input(xyz, nullptr, n, on_device), guess, params, pose_out, result);
+    return icp_by_setting<PlaneIcp>(m, [&](auto M) {
+        return icp_align<typename decltype(M)::type>(m, cloud_input(xyz, nullptr, n, on_device), guess, params, pose_out, result);
+    });
 }
 
 // measurement and tests (rgbd360_hip_diag.h)

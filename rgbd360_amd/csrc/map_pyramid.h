@@ -214,6 +214,7 @@ int c2f_chain(rgbd360_map* m, const MapInput& in, const float guess[16], const r
         float ended[16];
         typename M::Result r;
         if (rc == 0) rc = icp_run<M>(lv, job, pose, ended, &r);
+        if (rc >= 0 && lv != m) m->a_robust = lv->a_robust;      // (the root reports the finest level run)
         if (rc < 0) {
             if (lv != m) m->err = lv->err;
             return rc;
@@ -239,7 +240,8 @@ int c2f_align(rgbd360_map* m, const MapInput& in, const float guess[16], const r
     m->err.clear();
     rgbd360_map_c2f_params p;
     if (const int rc = c2f_check(m, params, p)) return rc;
-    return p.kind == 0 ? c2f_chain<PointIcp>(m, in, guess, p, pose_out, res) : c2f_chain<PlaneIcp>(m, in, guess, p, pose_out, res);
+    auto chain = [&](auto M) { return c2f_chain<typename decltype(M)::type>(m, in, guess, p, pose_out, res); };
+    return p.kind == 0 ? icp_by_setting<PointIcp>(m, chain) : icp_by_setting<PlaneIcp>(m, chain);
 }
 
 }  // namespace

@@ -1284,6 +1284,7 @@ extern "C" int rgbd360_stitch_sphere(rgbd360_ctx* ctx_, const uint8_t* rgb8, con
 #include "map_align_gicp.h"
 #include "map_colour.h"
 #include "map_align_colour.h"
+#include "map_align_robust.h"
 #include "map_raycast.h"
 #include "map_carve.h"
 #include "map_planes.h"

@@ -98,6 +98,11 @@ struct rgbd360_map {
     DevBuf<unsigned char> a_state;
     PinnedBuf<unsigned char> a_host;
     std::vector<rgbd360_map_align_trace> a_trace;
+    // ... the robust kernel of each method (RGBD360_MAP_METHOD_*; map_align_robust.h): a setting, no layer and no revision; a level reads
+    // its root's.  What the last single alignment and the jobs of the last batch did with it.
+    rgbd360_map_robust robust[4] = {};
+    rgbd360_map_robust_info a_robust = {};
+    std::vector<rgbd360_map_robust_info> b_robust;
     // ... and of many in lock step (map_align_batch.h): the jobs and the prefix of their workgroup counts, on the device and pinned; the
     // traces of the last batch, one per job
     DevBuf<unsigned char> b_desc;

@@ -411,6 +411,35 @@ class VoxelMap:
         p = self.align_colour_params(**params)
         return self._align(self._L.rgbd360_map_align_colour_sphere, _lib.MapAlignColourResult, p, args, guess)
 
+    # ---- robust kernels of the alignments (rgbd360_map_set_align_robust; csrc/map_align_robust.h): a setting of the map per method
+    METHODS = {"point": _lib.MAP_METHOD_POINT, "plane": _lib.MAP_METHOD_PLANE, "gicp": _lib.MAP_METHOD_GICP, "colour": _lib.MAP_METHOD_COLOUR}
+    ROBUST_KINDS = {"none": _lib.MAP_ROBUST_NONE, "huber": _lib.MAP_ROBUST_HUBER, "cauchy": _lib.MAP_ROBUST_CAUCHY,
+                    "geman_mcclure": _lib.MAP_ROBUST_GEMAN_MCCLURE}
+
+    def set_align_robust(self, method, kind, delta: float = 0.0, scale_with_level: bool = False):
+        """The robust kernel of `method` ("point", "plane", "gicp", "colour" or RGBD360_MAP_METHOD_*) from now on: kind "none", "huber",
+        "cauchy" or "geman_mcclure" (or RGBD360_MAP_ROBUST_*), delta > 0 in the units of the square root of the method's cost term (metres
+        for point and plane); scale_with_level: delta x 2^shift on level `shift` of the pyramid.  Every align_* call of the method,
+        align_batch_* and align_*_c2f honour it; with "none" they are the quadratic calls.  The map's content is not touched."""
+        r = _lib.MapRobust(int(self.ROBUST_KINDS.get(kind, kind)), 1 if scale_with_level else 0, float(delta))
+        self._check(self._L.rgbd360_map_set_align_robust(self._handle(), int(self.METHODS.get(method, method)), C.byref(r)))
+
+    def align_robust(self, method):
+        """The setting of `method`: dict(kind, scale_with_level, delta)."""
+        r = _lib.MapRobust()
+        self._check(self._L.rgbd360_map_get_align_robust(self._handle(), int(self.METHODS.get(method, method)), C.byref(r)))
+        return _as_dict(r)
+
+    def robust_info(self, job=None):
+        """What the last single alignment did with its robust kernel (job None), or job `job` of the last batch: dict(method, kind, delta_eff,
+        sum_w, n, n_downweighted)."""
+        info = _lib.MapRobustInfo()
+        if job is None:
+            self._check(self._L.rgbd360_map_align_robust_info(self._handle(), C.byref(info)))
+        else:
+            self._check(self._L.rgbd360_map_align_batch_robust_info(self._handle(), int(job), C.byref(info)))
+        return _as_dict(info)
+
     def align_trace(self):
         """One record per step of the last align call of either kind: (n, sum_sq, update[6]) (rgbd360_map_align_eval, the diagnostics header)."""
         n = C.c_int()

@@ -4,6 +4,7 @@ to one insert of the same frame and to a copy of its bytes.
     python tools/map_align_perf.py [--sizes 2048x1024,1920x320] [--reps 20] [--leaf 0.05] [--out profiles/map_align_perf.txt]
     python tools/map_align_perf.py --gicp [--rounds 3] --out profiles/map_align_gicp_perf.txt
     python tools/map_align_perf.py --colour [--rounds 3] --out profiles/map_align_colour_perf.txt
+    python tools/map_align_perf.py --robust [--rounds 5] --out profiles/map_align_robust_perf.txt
 
 Per size (the synthetic room, uint16 depth in device memory, convention 2, the map holds the frame at a general pose, the default box;
 the alignment starts 1 cm and 3 mrad beside that pose), from HIP events in ONE run (rgbd360_map_time_align): the point-to-point
@@ -20,6 +21,12 @@ stands next to the differences between the methods.
 normal layer and to a bare scan of the table in the same run (rgbd360_map_time_colours, medians over --reps builds), then per round
 the coloured evaluation next to generalized ICP's on the same frame, map and buffers, the solve and a whole coloured alignment
 (rgbd360_map_time_align_colour).
+
+--robust reports the robust form of every method next to its quadratic form (rgbd360_map_time_align_robust: the same frame, map, buffers
+and parameters in one process, the launches of the two forms alternating): the evaluation kernel, the solve kernel and a whole alignment
+of both forms per method and kind, medians over --rounds calls of --reps pairs each, the ratio robust / quadratic, and the spread of the
+quadratic evaluation between the rounds, which is what a ratio has to exceed to mean anything.  The quadratic kernels are the machine
+code they were before there was a robust form (tools/device_asm_diff.py), so the quadratic column is the baseline.
 
 The evaluation of every method is one kernel template, k_vmap_eval<M, SRC> (csrc/map_align.h).  The report lines keep the labels
 k_vmap_icp_eval, k_vmap_plane_eval, k_vmap_gicp_eval and k_vmap_colour_eval for its four instantiations: they are labels, not kernel
@@ -110,6 +117,47 @@ def colour_report(say, hip, reg, P, beside, a):
         hip.hipFree(d_rgb)
 
 
+ROBUST_DELTA = {"point": 0.03, "plane": 0.01, "gicp": 0.3, "colour": 0.01}      # near the median square root of each method's cost term at the guess
+
+
+def robust_report(say, hip, reg, P, beside, a):
+    """--robust: per size, method and kind the robust form next to the quadratic one, all figures from alternating launches of one process."""
+    say("rgbd360_map_set_align_robust: robust / quadratic form of every method, HIP events, alternating launches, medians of %d rounds of %d pairs, "
+        "leaf %.3f m = max_dist, default box, microseconds" % (a.rounds, a.reps, a.leaf))
+    for size in a.sizes.split(","):
+        W, H = (int(x) for x in size.split("x"))
+        rgb, depth = (np.ascontiguousarray(x) for x in synth.render(synth.trajectory_pose(0, 7), W, H, 7)[:2])
+        d_depth, d_rgb = C.c_void_p(), C.c_void_p()
+        assert hip.hipMalloc(C.byref(d_depth), depth.nbytes) == 0 and hip.hipMemcpy(d_depth, _ptr(depth), depth.nbytes, 1) == 0
+        assert hip.hipMalloc(C.byref(d_rgb), rgb.nbytes) == 0 and hip.hipMemcpy(d_rgb, _ptr(rgb), rgb.nbytes, 1) == 0
+        with VoxelMap(reg, a.leaf, 1 << 21) as m:
+            st = m.insert_sphere(rgb, depth, P, convention=2)
+            say("%dx%d: %d pixels, %d reach the search, %d voxels in a table of %d MiB" % (W, H, W * H, st["n_added"], st["n_voxels"], m.bytes >> 20))
+            say("    method kind          delta | eval: robust  quadratic  ratio (spread of quadratic) | solve: robust  quadratic | whole alignment: robust  quadratic  ratio"
+                " | contributing  down-weighted  sum w")
+            for code, method in enumerate(("point", "plane", "gicp", "colour")):
+                p = getattr(m, {"point": "align_params", "plane": "align_plane_params", "gicp": "align_gicp_params", "colour": "align_colour_params"}[method])()
+                head = (d_rgb, W * 3) if method == "colour" else (None, 0)
+                args = head + (d_depth, W * depth.itemsize, 0 if depth.dtype == np.uint16 else 1, H, W, 2, _ptr(pose_to_cm(beside)))
+                for kind in ("huber", "cauchy", "geman_mcclure"):
+                    m.set_align_robust(method, kind, ROBUST_DELTA[method])
+                    us = np.zeros((a.rounds, 6), np.float32)
+                    for r in range(a.rounds):
+                        rc = m._L.rgbd360_map_time_align_robust(m._handle(), code, *args, C.byref(p), a.reps, _ptr(us[r]))
+                        assert rc == 0, (rc, m._L.rgbd360_map_last_error(m._h))
+                    run = {"point": m.align_sphere, "plane": m.align_sphere_plane, "gicp": m.align_sphere_gicp}.get(method)
+                    _ = run(depth, beside, convention=2) if run else m.align_sphere_colour(rgb, depth, beside, convention=2)
+                    info = m.robust_info()      # (of that alignment's final evaluation)
+                    m.set_align_robust(method, "none")
+                    med = np.median(us, axis=0)
+                    spread = (us[:, 1].max() - us[:, 1].min()) / med[1]
+                    say("    %-6s %-13s %5.2f | %12.1f %10.1f %6.3f (%.3f) | %13.1f %10.1f | %24.1f %10.1f %6.3f | %12d %14d %6.0f"
+                        % (method, kind, ROBUST_DELTA[method], med[0], med[1], med[0] / med[1], spread, med[2], med[3], med[4], med[5], med[4] / med[5],
+                           info["n"], info["n_downweighted"], info["sum_w"]))
+        hip.hipFree(d_depth)
+        hip.hipFree(d_rgb)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="2048x1024,1920x320")
@@ -118,7 +166,8 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--gicp", action="store_true", help="the three methods side by side")
     ap.add_argument("--colour", action="store_true", help="coloured ICP: the layer build and the evaluation next to generalized ICP's")
-    ap.add_argument("--rounds", type=int, default=3, help="with --gicp / --colour: repetitions of the whole comparison")
+    ap.add_argument("--robust", action="store_true", help="the robust form of every method next to its quadratic form")
+    ap.add_argument("--rounds", type=int, default=3, help="with --gicp / --colour / --robust: repetitions of the whole comparison")
     a = ap.parse_args()
     lines = []
 
@@ -137,11 +186,13 @@ def main():
     beside[:3, 3] += np.array([0.006, -0.006, 0.005], np.float32)
     c, s = np.cos(0.003), np.sin(0.003)
     beside = (np.array([[c, -s, 0, 0], [s, c, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]]) @ beside.astype(np.float64)).astype(np.float32)
-    if a.colour:
+    if a.robust:
+        robust_report(say, hip, reg, P, beside, a)
+    elif a.colour:
         colour_report(say, hip, reg, P, beside, a)
     else:
         say("rgbd360_map_align_*: HIP-event averages over %d launches, leaf %.3f m = max_dist, default box, microseconds" % (a.reps, a.leaf))
-    for size in ([] if a.colour else a.sizes.split(",")):
+    for size in ([] if a.colour or a.robust else a.sizes.split(",")):
         W, H = (int(x) for x in size.split("x"))
         _, depth = synth.render(synth.trajectory_pose(0, 7), W, H, 7)
         depth = np.ascontiguousarray(depth)
